@@ -299,6 +299,31 @@ def roofline_of(rows, extra=None):
     return out
 
 
+DUMP_FRAMES = 8192              # frames of the headline's outputs --dump-outputs writes (~36 MB)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(np, torch, out, first_frame, out_dir):
+    """The arrays the headline's encode_long returned, for a fixed seeded sample of its frames (the whole batch when it
+    is smaller), as out_dir/<name>.npy: mantissa codes as float32 (uint16 values), side info as float64 (int32 values),
+    and frame_index, the global stream index of every sampled frame.  Both exact, so two builds compare bit for bit."""
+    n = out["overall_scale"].shape[0]
+    pick = np.sort(np.random.default_rng(20240611).choice(n, size=min(n, DUMP_FRAMES), replace=False))
+    idx = torch.from_numpy(pick).to(out["overall_scale"].device)
+    arrays = {"frame_index": (pick + first_frame).astype(np.float64)}
+    for k, t in out.items():
+        host = t.index_select(0, idx).cpu().numpy()
+        if k == "mantissa" and host.dtype == np.int16:
+            arrays[k] = host.view(np.uint16).astype(np.float32)     # 16-bit codes travel as int16 storage
+        else:
+            arrays[k] = host.astype(np.float32 if k == "mantissa" else np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, "output dump of %d bytes exceeds %d" % (total, DUMP_LIMIT_BYTES)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -314,7 +339,13 @@ def main():
     ap.add_argument("--skip-extras", action="store_true", help="only the headline measurement (profiling runs)")
     ap.add_argument("--only", choices=["stereo", "switch"], default=None,
                     help="profiling runs: ONLY the timed loop of configs[2] / configs[3] (prints a short JSON line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline's last timed step computed (a fixed sample of its frames) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.only:
+        ap.error("--dump-outputs writes the headline's outputs; --only does not run the headline")
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     rank = int(os.environ.get("RANK", "0"))
@@ -359,14 +390,17 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(device)
 
+    last_out = [None]
+
     def timed_steps(fn):
-        """W warm-up steps, then exactly K steps between barriers; max over ranks of the elapsed time."""
+        """W warm-up steps, then exactly K steps between barriers; max over ranks of the elapsed time.  What the last
+        timed step returned is kept in last_out[0]."""
         for _ in range(args.warmup):
             fn()
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            fn()
+            last_out[0] = fn()
         torch.cuda.synchronize(device)
         elapsed = time.perf_counter() - t0
         barrier()
@@ -408,6 +442,9 @@ def main():
     assert count == F
     (pcm,) = stream_slices(torch, device, "c2", first, F)
     elapsed = timed_steps(lambda: enc.encode_long(pcm, None, F, mantissa16=True))
+    if args.dump_outputs and rank == 0:
+        # before anything else reuses the output buffers of the last timed step
+        dump_outputs(np, torch, last_out[0], first, args.dump_outputs)
     kms = kernel_ms(lambda: enc.encode_long(pcm, None, F, mantissa16=True))
     coded = coded_line_fraction(np, enc.encode_long(pcm, None, F, mantissa16=True), enc.h.bands(HOP, HOP))
     line = None
