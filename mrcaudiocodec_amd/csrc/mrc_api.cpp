@@ -3,6 +3,7 @@
 // of mrc_kernels.hip or fails.
 #include "mrc_handle.hpp"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -24,6 +25,24 @@ int get_shape(mrc_handle* h, int a, int b, const HostShape** out) {
         HostShape hs;
         std::string err;
         if (!build_shape(h->cfg, a, b, &hs, &err)) return fail(h, MRC_ERR_INVALID, err);
+        // The generic kernels hold a whole block in LDS: a shape whose workgroup would need more than the device gives one
+        // is refused here rather than at its first launch.  (smr_kernel's layout is the largest for every shape that gets
+        // near the limit; the packer's per-chunk buffers and the bit allocation's stay below it.)  smr_kernel also scans
+        // a block's peaks in a fixed number of slots: at most (N/2 - 101) / 2 peaks, N/2 <= 1123 lines.
+        if (!smr_peaks_fit(hs.dev)) {
+            free_shape(&hs);
+            return fail(h, MRC_ERR_INVALID, "block shape too long for the masking model's peak scan (N/2 <= 1123 lines)");
+        }
+        int ldsMax = 0;
+        MRC_HIP(h, hipDeviceGetAttribute(&ldsMax, hipDeviceAttributeMaxSharedMemoryPerBlock, h->device));
+        const size_t need = std::max(smr_generic_lds_bytes(hs.dev), mdct_generic_lds_bytes(hs.dev));
+        if (need > (size_t)ldsMax) {
+            free_shape(&hs);
+            char msg[160];
+            std::snprintf(msg, sizeof msg, "block shape (%d,%d) needs %zu bytes of LDS per workgroup, the device allows %d",
+                          a, b, need, ldsMax);
+            return fail(h, MRC_ERR_INVALID, msg);
+        }
         it = h->shapes.emplace(key, std::move(hs)).first;
     }
     *out = &it->second;
@@ -521,7 +540,11 @@ int encode_host(mrc_handle* h, int64_t n, int a, int b, const double* left, cons
     const size_t szBand = (size_t)n * nstream * S.nBands * sizeof(int32_t);
     const size_t szMant = (size_t)n * nstream * S.halfN * sizeof(int32_t), szRes = (size_t)n * sizeof(int32_t);
     const size_t szLines = (size_t)n * nsig * S.halfN * sizeof(double);
-    if (n <= kSmallBatch) {
+    // (the chained back end's scan covers <= 64 coded bands, 2..16 mantissa bits and lines in units of four, at most
+    // kChainMaxLinesPerItem of them per block -- chained_core checks the same; other shapes take the batch path)
+    const bool chainable = nstream * S.nBands <= 64 && S.maxMantBits >= 2 && S.maxMantBits <= 16 && (S.halfN & 3) == 0 &&
+                           nstream * S.halfN <= kChainMaxLinesPerItem;
+    if (n <= kSmallBatch && chainable) {
         // The per-block seam (pacfileThem.py:649,820 -> codecThem.py:205-278 hands over ONE block per call).  Two things made
         // such a call slow (0.45 ms per joint block in round 3): every array in its own pageable copy (ten staging round trips
         // of the runtime), and the batch path's bit allocation -- one LANE per frame walking the greedy loop, ~135 us alone

@@ -93,10 +93,13 @@ int chained_core(mrc_handle* h, int64_t n_streams, const void* pcm_left, const v
     for (int g = 0; g < nGroups; ++g) {
         MRC_TRY(get_shape(h, shapeA[g], shapeB[g], &hs[g]));
         const DevShape& S = hs[g]->dev;
-        const int nTot = (g == 4 ? 1 : 2) * S.nBands;
+        const int nstream = g == 4 ? 1 : 2, nTot = nstream * S.nBands;
         if (nTot > 64 || S.maxMantBits < 2 || S.maxMantBits > 16 || (S.halfN & 3))
             return fail(h, MRC_ERR_INVALID, "mrc_encode_chained: shape outside what the chained back end covers "
                                             "(<= 32 bands, 2..16 mantissa bits, lines a multiple of 4)");
+        if (nstream * S.halfN > kChainMaxLinesPerItem)
+            return fail(h, MRC_ERR_INVALID, "mrc_encode_chained: block too long for the chained back end (more than 2048 "
+                                            "coded lines per block: n_mdct_lines <= 1024 in joint stereo)");
     }
     // ---- the schedule, pass 1: validate, sort the blocks into their shape groups (the offsets phase A needs).  The rest of
     // the schedule (items in file order, chunk maps, headers) is only needed by the serial scan and the packer: it is built

@@ -78,6 +78,7 @@ int scale_factor_host(double v, int nScaleBits, int nMantBits);
 hipError_t launch_mdct(const DevShape& S, int64_t nFrames, const void* chL, const void* chR, int fmt,
                        int64_t stride, const int64_t* offsets, bool applyWindow, double* lines, int* oscale,
                        hipStream_t st);
+size_t mdct_generic_lds_bytes(const DevShape& S);   // dynamic LDS of mdct_kernel (and decode_kernel) for shape S
 // mrc_kernels_long.hip -- long-block specialisation (a = b = 1024)
 bool mdct_long_applicable(const DevShape& S, int64_t stride, const int64_t* offsets, const void* chL,
                           const void* chR, int fmt);
@@ -86,6 +87,8 @@ hipError_t launch_mdct_long(const DevShape& S, int64_t nFrames, const void* chL,
 hipError_t launch_window(const DevShape& S, int64_t nBlocks, const double* in, double* out, hipStream_t st);
 hipError_t launch_unscale(int64_t nBlocks, int halfN, const double* scaled, const int* oscale, double* lines,
                           hipStream_t st);
+size_t smr_generic_lds_bytes(const DevShape& S);    // dynamic LDS of smr_kernel for shape S
+bool smr_peaks_fit(const DevShape& S);              // can smr_kernel hold every peak a block of shape S may have?
 hipError_t launch_smr(const DevShape& S, int64_t nFrames, const void* chL, const void* chR, int fmt,
                       int64_t stride, const int64_t* offsets, const double* lines, const int* oscale,
                       double* smr, double* thresh, double* bandPeak /* [frames*signals][nBands] or null */,
@@ -156,6 +159,7 @@ hipError_t launch_pack_export(const void* ws, int64_t nChunks, long long* hostOu
 const int* pack_error_flag(const void* ws, int64_t nChunks);          // device addresses inside ws
 const long long* pack_total_bytes(const void* ws, int64_t nChunks);
 // mrc_kernels_chain.hip -- chained stream encode: reservoir-free preparation per block, serial scan per stream
+constexpr int kChainMaxLinesPerItem = 2 * 1024;  // coded lines one scan item holds (all its streams together)
 struct ChainGroupDev {               // what chain_phase_b_kernel knows about one block-shape group (device memory)
     int joint, nb, nTot, M, K, nEv, maxN, nScaleBits, nstream, pad_;
     double budgetMono, budgetJointPre, blkswA, blkswB;          // codecThem.py:299-308, 381-396

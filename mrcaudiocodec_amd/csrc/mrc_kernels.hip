@@ -664,6 +664,8 @@ static int mdct_wave_slots(size_t lds) {
     return (int)std::min<size_t>(3, std::max<size_t>(1, (160u << 10) / perWg)) * cus;
 }
 
+size_t mdct_generic_lds_bytes(const DevShape& S) { return (size_t)(2 * S.N) * sizeof(double); }
+
 hipError_t launch_mdct(const DevShape& S, int64_t nFrames, const void* chL, const void* chR, int fmt, int64_t stride,
                        const int64_t* offsets, bool applyWindow, double* lines, int* oscale, hipStream_t st) {
     if (nFrames <= 0) return hipSuccess;
@@ -674,13 +676,14 @@ hipError_t launch_mdct(const DevShape& S, int64_t nFrames, const void* chL, cons
     // 1024 + 128 and 128 + 1024: one), windowed: mdct_wave_kernel.  Its wavefronts walk runs of up to kMdctMaxRun groups; the
     // number of wavefronts is a whole multiple of what the chip holds at once (mdct_wave_slots), so that a launch of one to
     // three rounds of workgroups -- the block-switched step's sizes -- has no thin last round.
-    if (applyWindow && !(reinterpret_cast<uintptr_t>(lines) & 15) && ((S.N == 256 && S.shift == 0) || S.N == 1152)) {
+    if (applyWindow && !(reinterpret_cast<uintptr_t>(lines) & 15) &&
+        ((S.N == 256 && S.shift == 0) || (S.N == 1152 && (S.shift == 224 || S.shift == -224)))) {
         const int64_t nUnits = nFrames * nsig;
         const int U = S.N == 256 ? 4 : 1;
         const int64_t groups = (nUnits + U - 1) / U;
         // transition blocks fold in registers (shift -+224: chunk pairing 15 / 1)
-        const int k64 = S.N == 1152 ? (S.shift == -224 ? 15 : S.shift == 224 ? 1 : -1) : 0;
-        if (k64 < 0) return hipErrorInvalidValue;       // (N = 1152 comes from 1024 + 128 or 128 + 1024 only)
+        // (the other N = 1152 shapes, (576,576) for one, take mdct_kernel below)
+        const int k64 = S.N == 1152 ? (S.shift == -224 ? 15 : 1) : 0;
         const size_t ldsW = (size_t)(kMdctWaves * (k64 ? S.N : U * S.N + 2 * U * S.Q) + (k64 ? 6 : 2) * S.Q) * sizeof(double);
         int64_t nWaves = 0;
         unsigned grid = 0;
@@ -705,7 +708,7 @@ hipError_t launch_mdct(const DevShape& S, int64_t nFrames, const void* chL, cons
 #undef MRC_MDCT_WAVE
         return hipGetLastError();
     }
-    size_t lds = (size_t)(2 * S.N) * sizeof(double);
+    const size_t lds = mdct_generic_lds_bytes(S);
     // a short block (N <= 256: 64 complex FFT points) is one wavefront's work; longer ones take four
 #define MRC_MDCT_LAUNCH(TY, THREADS)                                                                                  \
     hipLaunchKernelGGL((mdct_kernel<TY, THREADS>), dim3((unsigned)(nFrames * nsig)), dim3(THREADS), lds, st, S, nsig,   \

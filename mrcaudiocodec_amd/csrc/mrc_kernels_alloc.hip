@@ -260,7 +260,8 @@ __global__ __launch_bounds__(kWave) void quantize_kernel(DevShape S, int jointAr
         // scaling by 2^overallScale is exact, so max and scale commute
         const double peak = ldexp(bandPeak[(f * nsig + sig) * nb + lane], osc[sig]);
         const int sf = scale_factor_dev(peak, S.nScaleBits, ba);
-        sInfo[lane] = (unsigned)ba | ((unsigned)sf << 8) | ((unsigned)osc[sig] << 16) | ((unsigned)sig << 24);
+        // (sf is -1 for a band without bits when nScaleBits = 1: kept inside its byte, or it would overwrite the signal)
+        sInfo[lane] = (unsigned)ba | (((unsigned)sf & 0xffu) << 8) | ((unsigned)osc[sig] << 16) | ((unsigned)sig << 24);
         scaleFactor[(f * nstream + strm) * nb + lane] = sf;
     }
     __syncthreads();

@@ -277,7 +277,7 @@ __device__ unsigned long long gChainProf[16];
 // ~2 us for them).
 // NT threads per workgroup: 256 when many streams share the chip (eight streams per CU), 512 for a few long streams (the
 // line-parallel half of an item -- mantissas, prices -- then runs on eight waves instead of four).
-constexpr int kMaxLinesPerItem = 2 * 1024;                                    // two coded streams of <= 1024 lines
+constexpr int kMaxLinesPerItem = kChainMaxLinesPerItem;                       // two coded streams of <= 1024 lines
 template <int NT> struct ChainDims {
     static constexpr int kEvPerThread = (kMaxEvents + NT) / NT;               // the events / prefix sums a thread stages
     static constexpr int kUnitsPerThread = (kMaxLinesPerItem / 4 + NT - 1) / NT;   // units of four lines per thread

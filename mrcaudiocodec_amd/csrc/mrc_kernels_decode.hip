@@ -120,7 +120,7 @@ hipError_t launch_decode(const DevShape& S, int64_t nBlocks, int nStreams, const
                          const int* scaleFactor, const int* bitAlloc, const int* mantissa, const int64_t* outOffset,
                          double* outL, double* outR, hipStream_t st) {
     if (nBlocks <= 0) return hipSuccess;
-    const size_t lds = (size_t)2 * S.N * sizeof(double);
+    const size_t lds = mdct_generic_lds_bytes(S);          // (the same [2N] doubles as mdct_kernel)
     hipLaunchKernelGGL(decode_kernel, dim3((unsigned)(nBlocks * nStreams)), dim3(kThreads), lds, st, S, nStreams, oscale,
                        msSwitch, scaleFactor, bitAlloc, mantissa, outOffset, outL, outR);
     return hipGetLastError();

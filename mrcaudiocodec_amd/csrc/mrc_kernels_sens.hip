@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256) void sensitivity_kernel(DevShape S, int joint,
         const int band = tid % nb, strm = tid / nb;
         const int sig = joint ? (msSwitch[f * nb + band] ? 2 + strm : strm) : 0;
         const int ba = bitAlloc[(f * nstream + strm) * nb + band], sf = scaleFactor[(f * nstream + strm) * nb + band];
-        sInfo[tid] = (unsigned)ba | ((unsigned)sf << 8) | ((unsigned)oscale[f * nsig + sig] << 16) | ((unsigned)sig << 24);
+        sInfo[tid] = (unsigned)ba | (((unsigned)sf & 0xffu) << 8) | ((unsigned)oscale[f * nsig + sig] << 16) | ((unsigned)sig << 24);
         sKey[tid] = smr[(f * nsig + sig) * nb + band];
     }
     __syncthreads();

@@ -426,6 +426,10 @@ __host__ __device__ constexpr SmrLds smr_layout(int H, int M, int last, int* tot
     return lay;
 }
 
+// The suffix scans over a frame's maskers (smr_body) hold kWave * kSmrMaxSeg entries: at most that many peaks + 1 per block,
+// which bounds the block sizes the kernel takes (smr_peaks_fit)
+constexpr int kSmrMaxSeg = 8;
+
 // Slope nodes: the most maskers a block of DIM lines can take through them.  Rows of kNodeCols doubles for every fourth
 // masker (+ row 0) lie between the per-line counts and the log10 table (where the peak bins and the Bark grid were); the masker
 // table (4 P) and the in-band prefix sums (2 (P + 1)) share the first FFT buffer with the band keys and the 2^x table (96).
@@ -1165,7 +1169,7 @@ __device__ __forceinline__ void smr_body(DevShape S, int nsigArg, const SampleT*
         // most (DIM - 101) / 2 (13 for the short block: one per lane; 237 for the transition blocks: four; 461 for the long
         // block: eight -- but a frame that takes the slope nodes has at most 308: five.  Besides the shorter serial chain,
         // five entries of 32 bytes per lane put the lanes 160 bytes apart; at 256 bytes all 64 read the same bank)
-        constexpr int kSegAny = DIM == 128 ? 1 : DIM == 576 ? 4 : 8;
+        constexpr int kSegAny = DIM == 128 ? 1 : DIM == 576 ? 4 : kSmrMaxSeg;
         constexpr int kSegNodes = DIM == 1024 ? 5 : kSegAny;
         static_assert(DIM != 1024 || kWave * kSegNodes > node_max_maskers(1024), "segments of the scans");
         auto scan_sc = [&](auto segC) {
@@ -1878,6 +1882,17 @@ extern "C" int mrc_debug_phase_cycles(unsigned long long* out32, int reset) {
     return e == hipSuccess ? 0 : -1;
 }
 #endif
+
+bool smr_peaks_fit(const DevShape& S) {
+    // peak bins p = 1 .. peakLast - 2 (psychoac.py:160), no two of them adjacent
+    return (S.peakLast - 1) / 2 + 1 <= kWave * kSmrMaxSeg;
+}
+
+size_t smr_generic_lds_bytes(const DevShape& S) {
+    size_t lds = 0;
+    (void)smr_launch_layout(S, &lds);
+    return lds;
+}
 
 hipError_t launch_smr(const DevShape& S, int64_t nFrames, const void* chL, const void* chR, int fmt, int64_t stride,
                       const int64_t* offsets, const double* lines, const int* oscale, double* smr, double* thresh,
