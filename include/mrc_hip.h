@@ -457,6 +457,37 @@ int mrc_dev_decode(mrc_handle* h, int a, int b, int64_t n_blocks, int n_streams,
 int mrc_pcm16(mrc_handle* h, int64_t n, const double* x, int16_t* out);
 int mrc_dev_pcm16(mrc_handle* h, int64_t n, const double* x, int16_t* out, void* stream);
 
+/* ---- decode on the device (round 5: SURVEY 8 row f-4) ----
+ * The chunk parser of mrc_unpack_blocks runs on the device too (csrc/mrc_unpack.hpp, one lane per channel chunk).
+ *
+ * mrc_dev_unpack_blocks: the same contract and fixed-stride layout as mrc_unpack_blocks (pacfileThem.py:176-302 /
+ * 341-560), every array -- buf [len], chunk_offset [n_blocks * n_channels] and the outputs -- in device memory; the
+ * codec parameters are the handle's.  Synchronises `stream`; MRC_ERR_INVALID exactly where the host parser refuses:
+ * a chunk outside buf, a read past a chunk's end, a table id outside {0..3, 15}, a stored allocation above 16 bits,
+ * bits that are no code of the chunk's Huffman table, the chunks of one block in different shapes (mrc_last_error names
+ * the first bad chunk).  The outputs are then unspecified. */
+int mrc_dev_unpack_blocks(mrc_handle* h, int64_t n_blocks, int n_channels, int joint, const uint8_t* buf, int64_t len,
+                          const int64_t* chunk_offset, int32_t* a, int32_t* b, int32_t* huff_table, int32_t* overall_scale,
+                          int32_t* ms_switch, int32_t* scale_factor, int32_t* bit_alloc, int32_t* mantissa, void* stream);
+/* mrc_decode_pac_pcm16: n_files whole `.pac` files -- file f is buf[file_offset[f], file_offset[f + 1]), host memory,
+ * pageable or not -- to 16-bit PCM in host memory, in ONE call: the bytes cross PCIe once, chunk parsing, Huffman
+ * decoding, dequantisation, IMDCT, overlap-add (pacfileThem.py:302-315, codecThem.py:30-134) and the codes of
+ * pcmfile.py:163-172 run on the device.  File f's samples go to out[sample_offset[f], sample_offset[f + 1]) interleaved
+ * in WAV order (pcmfile.py:141-153: sample t of channel c at t * n_channels[f] + c), the first n_mdct_lines samples of
+ * each file -- the MDCT's half-block delay -- dropped as the reference's decode loop drops them (pacfileThem.py:1176-1179).
+ * Bit-identical to mrc_unpack_blocks + mrc_dev_decode per block shape + mrc_dev_pcm16 (pacfile.decode_pac_pcm16).
+ * Every file must carry the handle's sample_rate, n_mdct_lines, n_scale_bits and n_mant_size_bits (else
+ * MRC_ERR_INVALID, the text names the file); mono and stereo files may be mixed; a file with a header and no chunks
+ * decodes to no samples.  out_cap counts int16 values: if it is too small the call returns MRC_ERR_NOMEM before any
+ * device work, writes nothing to out and still fills sample_offset [n_files + 1] (sample_offset[n_files] = the size
+ * needed) and n_channels [n_files].  Device memory: the handle's, reused from call to call (~9 bytes per coded line
+ * and 16 per output sample and channel). */
+int mrc_decode_pac_pcm16(mrc_handle* h, int64_t n_files, const uint8_t* buf, const int64_t* file_offset, int16_t* out,
+                         int64_t out_cap, int64_t* sample_offset, int32_t* n_channels);
+/* Device time of the last mrc_decode_pac_pcm16 call (ms): [0] host -> device copy, [1] unpack kernel, [2] synthesis
+ * (decode_kernel launches + interleaved pcm16), [3] device -> host copy. */
+int mrc_get_decode_ms(mrc_handle* h, double* ms /*[4]*/);
+
 /* Per-stage device time of the most recent mrc_dev_encode / stage call when timing is enabled
  * (hipEvents on the launch stream; the call then synchronises).  ms[0..2] = mdct, smr, alloc+quant. */
 int mrc_set_timing(mrc_handle* h, int enabled);

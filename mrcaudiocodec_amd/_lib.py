@@ -149,6 +149,9 @@ def _load():
         "mrc_set_option": (C.c_int, [H, C.c_int, C.c_int]),
         "mrc_get_option": (C.c_int, [H, C.c_int, _i32p]),
         "mrc_get_stage_ms": (C.c_int, [H, _f64p]),
+        "mrc_dev_unpack_blocks": (C.c_int, [H, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64] + [C.c_void_p] * 10),
+        "mrc_decode_pac_pcm16": (C.c_int, [H, C.c_int64, _u8p, _i64p, C.c_void_p, C.c_int64, _i64p, _i32p]),
+        "mrc_get_decode_ms": (C.c_int, [H, _f64p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = the library does not export the header's symbol
@@ -628,6 +631,51 @@ class Handle:
 
     def dev_pcm16(self, n, x, out, stream=None):
         self._check(lib.mrc_dev_pcm16(self._h, n, x, out, stream))
+
+    def dev_unpack_blocks(self, n_blocks, n_channels, joint, buf, length, chunk_offset, a, b, huff_table, overall_scale,
+                          ms_switch, scale_factor, bit_alloc, mantissa, stream=None):
+        """mrc_dev_unpack_blocks: the chunk parser of pacfile.unpack_blocks on the device, same fixed-stride layout; every
+        array argument is a DEVICE address.  Waits for the stream; a chunk the host parser would refuse raises MrcError."""
+        self._check(lib.mrc_dev_unpack_blocks(self._h, int(n_blocks), int(n_channels), 1 if joint else 0, buf, int(length),
+                                              chunk_offset, a, b, huff_table, overall_scale, ms_switch, scale_factor,
+                                              bit_alloc, mantissa, stream))
+
+    def decode_pac_pcm16(self, bufs, interleaved=True):
+        """mrc_decode_pac_pcm16: whole `.pac` files (bytes-like, one or a list) -> 16-bit PCM, parsed and decoded on the
+        device in one call.  Returns a list with one int16 array per file: [samples][nCh] in WAV order (views of one
+        interleaved buffer) or, interleaved=False, [nCh][samples] as pacfile.decode_pac_pcm16 returns it."""
+        if isinstance(bufs, (bytes, bytearray, memoryview, np.ndarray)):
+            bufs = [bufs]
+        n = len(bufs)
+        sizes = np.fromiter((len(b) for b in bufs), dtype=np.int64, count=n)
+        file_offset = np.zeros(n + 1, np.int64)
+        np.cumsum(sizes, out=file_offset[1:])
+        if n == 1:
+            data = np.ascontiguousarray(np.frombuffer(bufs[0], np.uint8))
+        else:
+            data = np.frombuffer(b"".join(bytes(b) for b in bufs), np.uint8)
+        sample_offset = np.zeros(n + 1, np.int64)
+        nch = np.zeros(max(n, 1), np.int32)
+        # a first guess (typical files code ~3 bits per sample); a short one costs only the host's header / chunk scan
+        out = np.empty(6 * data.size + 4096, np.int16)
+        args = lambda o: (self._h, n, _p(data, _u8p), _p(file_offset, _i64p), o.ctypes.data_as(C.c_void_p), o.size,
+                          _p(sample_offset, _i64p), _p(nch, _i32p))
+        rc = lib.mrc_decode_pac_pcm16(*args(out))
+        if rc == MRC_ERR_NOMEM and int(sample_offset[n]) > out.size:
+            out = np.empty(int(sample_offset[n]), np.int16)
+            rc = lib.mrc_decode_pac_pcm16(*args(out))
+        self._check(rc)
+        res = []
+        for f in range(n):
+            v = out[sample_offset[f]:sample_offset[f + 1]].reshape(-1, int(nch[f]))
+            res.append(v if interleaved else v.T)
+        return res
+
+    def decode_ms(self):
+        """device time of the last decode_pac_pcm16: H2D copy, unpack, synthesis (decode + pcm16), D2H copy (ms)"""
+        ms = np.zeros(4, np.float64)
+        self._check(lib.mrc_get_decode_ms(self._h, _p(ms, _f64p)))
+        return ms
 
     def transient_peaks(self, streams, sos):
         """streams [nCh][(nHops+1)*hop], float64 signed fractions or the file's int16 PCM codes -> peaks

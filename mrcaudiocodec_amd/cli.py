@@ -8,9 +8,9 @@ chained through the Huffman savings, Close()'s flush block, `.pac` framing -- ke
 and bit packing in C++ on the host.  Like the reference: stereo input only, and the last hop of the file is
 analysed but never encoded.
 
-Decode direction ("next" row f-4):  python -m mrcaudiocodec_amd.cli -d in.pac out.wav
-C++ chunk parser on the host, dequantise / M-S / IMDCT / window / overlap-add and the 16-bit PCM codes on the GPU,
-WAV header of pcmfile.py:141-153.  The first decoded block (the MDCT's half-block delay) is dropped as in the
+Decode direction (row f-4):  python -m mrcaudiocodec_amd.cli -d in.pac out.wav
+One library call (mrc_decode_pac_pcm16): chunk parsing and Huffman decoding, dequantise / M-S / IMDCT / window /
+overlap-add and the interleaved 16-bit PCM codes all on the GPU, then the WAV header of pcmfile.py:141-153.  The first decoded block (the MDCT's half-block delay) is dropped as in the
 reference's loop; everything after it is written, header sample count = what was decoded.
 """
 import argparse
@@ -115,13 +115,17 @@ def encode_wav(in_path, out_path=None, use_huffman=True, device_id=0, handle=Non
     return data
 
 
+def wav_header(n_ch, n_data_bytes, sample_rate):
+    """pcmfile.py:141-153"""
+    return pack('<4sL4s4sLHHLLHH4sL', b"RIFF", 36 + n_data_bytes, b"WAVE", b"fmt ", 16, 1, n_ch, sample_rate,
+                sample_rate * n_ch * 2, n_ch * 2, 16, b"data", n_data_bytes)
+
+
 def wav_bytes(pcm, sample_rate):
     """pcmfile.py:141-153 header + interleaved little-endian int16 samples; pcm int16 [nCh][samples]."""
     n_ch, n = pcm.shape
     data = np.ascontiguousarray(pcm.T).astype("<i2").tobytes()
-    head = pack('<4sL4s4sLHHLLHH4sL', b"RIFF", 36 + len(data), b"WAVE", b"fmt ", 16, 1, n_ch, sample_rate,
-                sample_rate * n_ch * 2, n_ch * 2, 16, b"data", len(data))
-    return head + data
+    return wav_header(n_ch, len(data), sample_rate) + data
 
 
 def decode_pac_file(pac_path, wav_path, device_id=0):
@@ -131,13 +135,14 @@ def decode_pac_file(pac_path, wav_path, device_id=0):
     h = Handle(sample_rate=cfg.sample_rate, n_mdct_lines=cfg.n_mdct_lines, n_scale_bits=cfg.n_scale_bits,
                n_mant_size_bits=cfg.n_mant_size_bits, device_id=device_id)
     try:
-        pcm = pacfile.decode_pac_pcm16(h, buf)
+        inter = h.decode_pac_pcm16(buf)[0]          # [samples][nCh] in WAV order, parsed and decoded on the device
     finally:
         h.close()
-    data = wav_bytes(pcm, cfg.sample_rate)
+    data = inter.astype("<i2", copy=False)
     with open(wav_path, "wb") as fp:
-        fp.write(data)
-    return pcm
+        fp.write(wav_header(inter.shape[1], data.nbytes, cfg.sample_rate))
+        fp.write(data.tobytes())
+    return inter.T
 
 
 def main(argv=None):

@@ -124,6 +124,7 @@ void mrc_destroy(mrc_handle* h) {
     h->wsPipe.release();
     h->packWs.release();
     h->chain.release();
+    h->dec.release();
     h->ws.release();
     for (DevBuf* b : {&h->inL, &h->inR, &h->inAux, &h->inAux2, &h->inAux3,
                       &h->outA, &h->outB, &h->outC, &h->outD, &h->outE, &h->outF, &h->outG})

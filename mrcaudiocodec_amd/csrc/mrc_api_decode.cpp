@@ -1,0 +1,388 @@
+// Decode of whole `.pac` files on the device: the host reads headers, chunk lengths and each chunk's block-switch bits
+// (4 bits into its payload) -- enough to know every block's shape and where its samples go -- and nothing else.  Bytes and
+// plan cross PCIe in one copy; chunk parsing (unpack_dense_kernel), dequantisation / IMDCT / overlap-add
+// (decode_kernel, unchanged) and the interleaved 16-bit codes (pcm16_interleave_kernel) run on the device; one copy
+// brings the WAV-order samples back.
+//
+// Blocks are grouped exactly as pacfile.decode_pac groups them: a stereo file of more than one block is joint blocks
+// followed by the two non-joint chunks Close() wrote (pacfileThem.py:973-984), every other file is non-joint blocks.
+// A group is a (block shape, kind): one decode_kernel launch each, over all files of the call.  The output planes hold
+// every file one after the other, channel 1 one plane stride behind channel 0; each output sample receives at most two
+// atomic contributions, so the order of the blocks does not change a bit of the result.
+#include "mrc_handle.hpp"
+
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <thread>
+
+using namespace mrc;
+
+namespace {
+
+inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
+
+UnpackParams unpack_params(const mrc_config& c) {
+    UnpackParams P;
+    P.nScaleBits = c.n_scale_bits;
+    P.nMantSizeBits = c.n_mant_size_bits;
+    P.blkBitsA = c.blksw_bits_a;
+    P.blkBitsB = c.blksw_bits_b;
+    P.nShort = c.n_short;
+    P.nLines = c.n_mdct_lines;
+    return P;
+}
+
+// block shapes in the order of UnpackBands: (L,L), (L,S), (S,L), (S,S)
+inline void shape_ab(const mrc_config& c, int s, int* a, int* b) {
+    *a = (s & 2) ? c.n_short : c.n_mdct_lines;
+    *b = (s & 1) ? c.n_short : c.n_mdct_lines;
+}
+
+// decode tables + band tables of the four shapes in device memory, once per handle
+int ensure_consts(mrc_handle* h) {
+    DecodeBufs& d = h->dec;
+    MRC_HIP(h, hipSetDevice(h->device));
+    if (d.consts.p) return MRC_OK;
+    std::vector<int> cnt[4];
+    size_t bandOff[4], bytes = align_up(sizeof(UnpackTables));
+    for (int s = 0; s < 4; ++s) {
+        int a, b;
+        shape_ab(h->cfg, s, &a, &b);
+        // (a shape of more lines than n_mdct_lines would not fit mrc_unpack_blocks' fixed stride either: refused)
+        if (!band_table(h->cfg, a, b, &cnt[s]) || (int)cnt[s].size() > MRC_MAX_BANDS || (a + b) / 2 > h->cfg.n_mdct_lines)
+            cnt[s].clear(), d.bands.nBands[s] = -1;
+        else d.bands.nBands[s] = (int)cnt[s].size();
+        d.bands.halfN[s] = (a + b) / 2;
+        bandOff[s] = bytes;
+        bytes += align_up(sizeof(int) * (cnt[s].size() + 1));
+    }
+    std::vector<unsigned char> blob(bytes, 0);
+    unpack_tables((UnpackTables*)blob.data());
+    for (int s = 0; s < 4; ++s)
+        if (!cnt[s].empty()) std::memcpy(blob.data() + bandOff[s], cnt[s].data(), sizeof(int) * cnt[s].size());
+    MRC_HIP(h, d.consts.reserve(bytes));
+    MRC_HIP(h, hipMemcpy(d.consts.p, blob.data(), bytes, hipMemcpyHostToDevice));
+    for (int s = 0; s < 4; ++s) d.bands.bandN[s] = (const int*)(d.consts.as<unsigned char>() + bandOff[s]);
+    if (!d.pinErr) MRC_HIP(h, hipHostMalloc((void**)&d.pinErr, sizeof(UnpackErr), hipHostMallocDefault));
+    for (auto& e : d.ev)
+        if (!e) MRC_HIP(h, hipEventCreate(&e));
+    return MRC_OK;
+}
+
+const char* status_text(int flag) {
+    if (flag & (1 << kUnpackBadTable)) return "table id not in {0..3, 15}";
+    if (flag & (1 << kUnpackBadAlloc)) return "bit allocation above 16";
+    if (flag & (1 << kUnpackBadCode)) return "bits that are no Huffman code of the table";
+    if (flag & (1 << kUnpackBadShape)) return "block shape without a band table or not the block's";
+    return "read past the end of a chunk";
+}
+
+// err <- {0, INT_MAX} on the stream
+int reset_err(mrc_handle* h, hipStream_t st) {
+    DecodeBufs& d = h->dec;
+    MRC_HIP(h, d.err.reserve(sizeof(UnpackErr)));
+    UnpackErr* e = d.err.as<UnpackErr>();
+    MRC_HIP(h, hipMemsetAsync(&e->flag, 0, sizeof(int), st));
+    MRC_HIP(h, hipMemsetD32Async((hipDeviceptr_t)&e->firstBad, 0x7fffffff, 1, st));
+    return MRC_OK;
+}
+
+// memcpy over a few host threads for large copies (page-locked staging <-> the caller's memory)
+void copy_host(void* dst, const void* src, size_t n) {
+    const size_t kSlice = (size_t)8 << 20;
+    int nt = (int)std::min<size_t>(8, n / kSlice);
+    if (nt <= 1) { std::memcpy(dst, src, n); return; }
+    std::vector<std::thread> pool;
+    for (int t = 0; t < nt; ++t) {
+        const size_t lo = n * t / nt, hi = n * (t + 1) / nt;
+        pool.emplace_back([=] { std::memcpy((char*)dst + lo, (const char*)src + lo, hi - lo); });
+    }
+    for (auto& th : pool) th.join();
+}
+
+struct FileInfo {
+    int nch = 0;
+    int64_t firstChunk = 0, nChunks = 0;   // into the call's chunk list
+    int64_t xStart = 0, extent = 0, total = 0;
+};
+
+}  // namespace
+
+extern "C" {
+
+int mrc_dev_unpack_blocks(mrc_handle* h, int64_t n_blocks, int n_channels, int joint, const uint8_t* buf, int64_t len,
+                          const int64_t* chunk_offset, int32_t* a, int32_t* b, int32_t* huff_table, int32_t* overall_scale,
+                          int32_t* ms_switch, int32_t* scale_factor, int32_t* bit_alloc, int32_t* mantissa, void* stream) {
+    if (!h) return MRC_ERR_INVALID;
+    const mrc_config& c = h->cfg;
+    if (!buf || !chunk_offset || !a || !b || !huff_table || !overall_scale || !scale_factor || !bit_alloc || !mantissa ||
+        n_blocks < 0 || n_channels < 1 || n_channels > 2 || (joint && (n_channels != 2 || !ms_switch)) || len < 0 ||
+        c.n_mdct_lines <= 0 || c.n_scale_bits < 1 || c.n_scale_bits > 4 || c.n_mant_size_bits < 1 || c.n_mant_size_bits > 8)
+        return fail(h, MRC_ERR_INVALID, "mrc_dev_unpack_blocks: bad argument");
+    MRC_TRY(ensure_consts(h));
+    hipStream_t st = pick_stream(h, stream);
+    MRC_TRY(reset_err(h, st));
+    UnpackFixedOut O{a, b, huff_table, overall_scale, ms_switch, scale_factor, bit_alloc, mantissa};
+    MRC_HIP(h, launch_unpack_fixed(unpack_params(c), h->dec.bands, h->dec.consts.as<UnpackTables>(), n_blocks, n_channels,
+                                   joint ? 1 : 0, buf, len, chunk_offset, O, h->dec.err.as<UnpackErr>(), st));
+    MRC_HIP(h, hipMemcpyAsync(h->dec.pinErr, h->dec.err.p, sizeof(UnpackErr), hipMemcpyDeviceToHost, st));
+    MRC_HIP(h, hipStreamSynchronize(st));
+    if (h->dec.pinErr->flag) {
+        char msg[160];
+        std::snprintf(msg, sizeof msg, "mrc_dev_unpack_blocks: chunk %d: %s", h->dec.pinErr->firstBad,
+                      status_text(h->dec.pinErr->flag));
+        return fail(h, MRC_ERR_INVALID, msg);
+    }
+    return MRC_OK;
+}
+
+int mrc_decode_pac_pcm16(mrc_handle* h, int64_t n_files, const uint8_t* buf, const int64_t* file_offset, int16_t* out,
+                         int64_t out_cap, int64_t* sample_offset, int32_t* n_channels) {
+    if (!h) return MRC_ERR_INVALID;
+    if (n_files < 0 || !file_offset || !sample_offset || !n_channels || out_cap < 0 || (n_files > 0 && !buf))
+        return fail(h, MRC_ERR_INVALID, "mrc_decode_pac_pcm16: bad argument");
+    const mrc_config& hc = h->cfg;
+    const int L = hc.n_mdct_lines;
+    const UnpackParams P = unpack_params(hc);
+    char msg[200];
+    sample_offset[0] = 0;
+    for (int64_t f = 0; f < n_files; ++f)
+        if (file_offset[0] < 0 || file_offset[f + 1] < file_offset[f])
+            return fail(h, MRC_ERR_INVALID, "mrc_decode_pac_pcm16: file_offset must not decrease");
+    if (n_files == 0) return MRC_OK;
+    MRC_TRY(ensure_consts(h));
+    DecodeBufs& d = h->dec;
+
+    // ---- host plan, pass 1: headers, chunks, block shapes, where each file's samples go
+    const uint8_t* base = buf + file_offset[0];
+    const int64_t inBytes = file_offset[n_files] - file_offset[0];
+    std::vector<FileInfo> files((size_t)n_files);
+    std::vector<int64_t> chunkOff;                 // relative to base
+    std::vector<unsigned char> chunkShape;
+    int64_t planeStride = 0;
+    bool anyStereo = false;
+    for (int64_t f = 0; f < n_files; ++f) {
+        const uint8_t* fb = buf + file_offset[f];
+        const int64_t flen = file_offset[f + 1] - file_offset[f];
+        mrc_config fc = hc;
+        int32_t nch = 0;
+        uint32_t ns = 0;
+        int64_t doff = 0;
+        if (mrc_pac_read_header(fb, flen, &fc, &nch, &ns, &doff) != MRC_OK) {
+            std::snprintf(msg, sizeof msg, "mrc_decode_pac_pcm16: file %lld: not a .pac header", (long long)f);
+            return fail(h, MRC_ERR_INVALID, msg);
+        }
+        const struct { const char* name; int file, handle; } par[4] = {
+            {"sample_rate", fc.sample_rate, hc.sample_rate}, {"n_mdct_lines", fc.n_mdct_lines, hc.n_mdct_lines},
+            {"n_scale_bits", fc.n_scale_bits, hc.n_scale_bits}, {"n_mant_size_bits", fc.n_mant_size_bits, hc.n_mant_size_bits}};
+        for (const auto& q : par)
+            if (q.file != q.handle) {
+                std::snprintf(msg, sizeof msg, "mrc_decode_pac_pcm16: file %lld has %s = %d, the handle was created with %d",
+                              (long long)f, q.name, q.file, q.handle);
+                return fail(h, MRC_ERR_INVALID, msg);
+            }
+        FileInfo& fi = files[(size_t)f];
+        fi.nch = nch;
+        fi.firstChunk = (int64_t)chunkOff.size();
+        for (int64_t off = doff; off + 4 <= flen;) {       // mrc_pac_scan_chunks
+            const int64_t nBytes = unpack_u32le(fb + off);
+            if (off + 4 + nBytes > flen) {
+                std::snprintf(msg, sizeof msg, "mrc_decode_pac_pcm16: file %lld: truncated chunk at byte %lld", (long long)f,
+                              (long long)off);
+                return fail(h, MRC_ERR_INVALID, msg);
+            }
+            int shape;
+            if (unpack_chunk_shape(fb + off + 4, nBytes, P, &shape) != kUnpackOk || d.bands.nBands[shape] < 0) {
+                std::snprintf(msg, sizeof msg, "mrc_decode_pac_pcm16: file %lld: chunk at byte %lld has no block shape",
+                              (long long)f, (long long)off);
+                return fail(h, MRC_ERR_INVALID, msg);
+            }
+            chunkOff.push_back(file_offset[f] - file_offset[0] + off);
+            chunkShape.push_back((unsigned char)shape);
+            off += 4 + nBytes;
+        }
+        fi.nChunks = (int64_t)chunkOff.size() - fi.firstChunk;
+        if (fi.nChunks % nch) {
+            std::snprintf(msg, sizeof msg, "mrc_decode_pac_pcm16: file %lld: %lld chunks for %d channels", (long long)f,
+                          (long long)fi.nChunks, nch);
+            return fail(h, MRC_ERR_INVALID, msg);
+        }
+        int64_t start = 0;
+        for (int64_t i = 0; i < fi.nChunks / nch; ++i) {
+            const int s = chunkShape[(size_t)(fi.firstChunk + i * nch)];
+            if (nch == 2 && chunkShape[(size_t)(fi.firstChunk + i * nch + 1)] != s) {
+                std::snprintf(msg, sizeof msg, "mrc_decode_pac_pcm16: file %lld: the chunks of block %lld differ in shape",
+                              (long long)f, (long long)i);
+                return fail(h, MRC_ERR_INVALID, msg);
+            }
+            int a, b;
+            shape_ab(hc, s, &a, &b);
+            fi.extent = std::max(fi.extent, start + a + b);   // (a file whose shapes do not chain still stays in its plane)
+            fi.total = start + a + b;                          // pacfile.decode_pac: last block's start + a + b
+            start += a;
+        }
+        fi.xStart = planeStride;
+        planeStride += fi.extent;
+        anyStereo |= nch == 2;
+        n_channels[f] = nch;
+        sample_offset[f + 1] = sample_offset[f] + std::max<int64_t>(0, fi.total - L) * nch;
+    }
+    const int64_t nOut = sample_offset[n_files];
+    if (nOut > out_cap || (nOut > 0 && !out)) {
+        std::snprintf(msg, sizeof msg, "mrc_decode_pac_pcm16: the files decode to %lld values, out_cap is %lld",
+                      (long long)nOut, (long long)out_cap);
+        return fail(h, MRC_ERR_NOMEM, msg);
+    }
+
+    // ---- pass 2: groups and slots; plan entries ordered by (group, joint channel) so that a wave parses one kind
+    int64_t nSlots[kUnpackGroups] = {}, nCat[2 * kUnpackGroups] = {};
+    for (const FileInfo& fi : files) {
+        const int64_t nb = fi.nChunks / fi.nch, nJoint = (fi.nch == 2 && nb > 1) ? nb - 1 : 0;
+        for (int64_t i = 0; i < nb; ++i) {
+            const int s = chunkShape[(size_t)(fi.firstChunk + i * fi.nch)];
+            if (i < nJoint) { nSlots[s * 2] += 1; nCat[s * 4] += 1; nCat[s * 4 + 1] += 1; }
+            else { nSlots[s * 2 + 1] += fi.nch; nCat[s * 4 + 2] += fi.nch; }
+        }
+    }
+    const int64_t nChunks = (int64_t)chunkOff.size();
+    int64_t catPos[2 * kUnpackGroups], slotBase[kUnpackGroups];
+    for (int64_t k = 0, p = 0; k < 2 * kUnpackGroups; p += nCat[k], ++k) catPos[k] = p;
+    for (int64_t g = 0, p = 0; g < kUnpackGroups; p += nSlots[g], ++g) slotBase[g] = p;
+    const HostShape* hs[4] = {};
+    for (int s = 0; s < 4; ++s)
+        if (nSlots[s * 2] + nSlots[s * 2 + 1]) {
+            int a, b;
+            shape_ab(hc, s, &a, &b);
+            MRC_TRY(get_shape(h, a, b, &hs[s]));
+            if (hs[s]->dev.nBands != d.bands.nBands[s]) return fail(h, MRC_ERR_INVALID, "mrc_decode_pac_pcm16: band tables disagree");
+        }
+    int64_t totalSlots = 0;
+    for (int g = 0; g < kUnpackGroups; ++g) totalSlots += nSlots[g];
+
+    // staging layout (one H2D copy): bytes | plan | groups | block offsets | outStart [n+1] | xStart [n] | nch [n]
+    const size_t oPlan = align_up((size_t)inBytes), oGroups = oPlan + align_up(sizeof(UnpackPlanEntry) * nChunks),
+                 oOffs = oGroups + align_up(sizeof(UnpackGroupDev) * kUnpackGroups),
+                 oOutStart = oOffs + align_up(sizeof(long long) * totalSlots),
+                 oXStart = oOutStart + align_up(sizeof(long long) * (n_files + 1)),
+                 oNch = oXStart + align_up(sizeof(long long) * n_files), inTotal = oNch + align_up(sizeof(int) * n_files);
+    // device arrays of the groups
+    size_t gOff[kUnpackGroups][5], gBytes = 0;
+    for (int g = 0; g < kUnpackGroups; ++g) {
+        const int s = g / 2, joint = !(g & 1), nb = std::max(d.bands.nBands[s], 0), half = d.bands.halfN[s];
+        const int64_t n = nSlots[g], ns = joint ? 2 : 1;
+        const size_t sz[5] = {sizeof(int) * n * (joint ? 4 : 1), joint ? sizeof(int) * n * nb : 0, sizeof(int) * n * ns * nb,
+                              sizeof(int) * n * ns * nb, sizeof(int) * n * ns * half};
+        for (int k = 0; k < 5; ++k) { gOff[g][k] = gBytes; gBytes += align_up(sz[k]); }
+    }
+    const int64_t xDoubles = planeStride * (anyStereo ? 2 : 1);
+    MRC_HIP(h, d.pinIn.reserve(inTotal));
+    MRC_HIP(h, d.in.reserve(inTotal));
+    MRC_HIP(h, d.groups.reserve(std::max<size_t>(gBytes, 256)));
+    MRC_HIP(h, d.x.reserve(std::max<size_t>(sizeof(double) * xDoubles, 256)));
+    MRC_HIP(h, d.pcm.reserve(std::max<size_t>(sizeof(int16_t) * nOut, 256)));
+    MRC_HIP(h, d.pinOut.reserve(std::max<size_t>(sizeof(int16_t) * nOut, 256)));
+
+    unsigned char* pin = (unsigned char*)d.pinIn.p;
+    copy_host(pin, base, (size_t)inBytes);
+    UnpackPlanEntry* plan = (UnpackPlanEntry*)(pin + oPlan);
+    UnpackGroupDev* gd = (UnpackGroupDev*)(pin + oGroups);
+    long long* offs = (long long*)(pin + oOffs);
+    long long* outStart = (long long*)(pin + oOutStart);
+    long long* xStart = (long long*)(pin + oXStart);
+    int* nchDev = (int*)(pin + oNch);
+    unsigned char* gBase = d.groups.as<unsigned char>();
+    for (int g = 0; g < kUnpackGroups; ++g) {
+        const int s = g / 2;
+        UnpackGroupDev& G = gd[g];
+        G.shape = s;
+        G.joint = !(g & 1);
+        G.nb = std::max(d.bands.nBands[s], 0);
+        G.halfN = d.bands.halfN[s];
+        int** ptr[5] = {&G.oscale, &G.ms, &G.sf, &G.ba, &G.mant};
+        for (int k = 0; k < 5; ++k) *ptr[k] = (int*)(gBase + gOff[g][k]);
+    }
+    int64_t slotNext[kUnpackGroups] = {};
+    for (int64_t f = 0; f < n_files; ++f) {
+        const FileInfo& fi = files[(size_t)f];
+        const int64_t nb = fi.nChunks / fi.nch, nJoint = (fi.nch == 2 && nb > 1) ? nb - 1 : 0;
+        int64_t start = 0;
+        for (int64_t i = 0; i < nb; ++i) {
+            const int64_t c0 = fi.firstChunk + i * fi.nch;
+            const int s = chunkShape[(size_t)c0];
+            if (i < nJoint) {
+                const int g = s * 2;
+                const int slot = (int)slotNext[g]++;
+                plan[catPos[s * 4]++] = UnpackPlanEntry{chunkOff[(size_t)c0], g * 2, slot};
+                plan[catPos[s * 4 + 1]++] = UnpackPlanEntry{chunkOff[(size_t)c0 + 1], g * 2 + 1, slot};
+                offs[slotBase[g] + slot] = fi.xStart + start;
+            } else {
+                const int g = s * 2 + 1;
+                for (int ch = 0; ch < fi.nch; ++ch) {
+                    const int slot = (int)slotNext[g]++;
+                    plan[catPos[s * 4 + 2]++] = UnpackPlanEntry{chunkOff[(size_t)c0 + ch], g * 2, slot};
+                    offs[slotBase[g] + slot] = ch * planeStride + fi.xStart + start;
+                }
+            }
+            int a, b;
+            shape_ab(hc, s, &a, &b);
+            start += a;
+        }
+        outStart[f] = sample_offset[f];
+        xStart[f] = fi.xStart;
+        nchDev[f] = fi.nch;
+    }
+    outStart[n_files] = nOut;
+
+    // ---- device
+    hipStream_t st = h->stream;
+    unsigned char* din = d.in.as<unsigned char>();
+    MRC_HIP(h, hipEventRecord(d.ev[0], st));
+    MRC_HIP(h, hipMemcpyAsync(din, pin, inTotal, hipMemcpyHostToDevice, st));
+    MRC_HIP(h, hipEventRecord(d.ev[1], st));
+    MRC_TRY(reset_err(h, st));
+    MRC_HIP(h, launch_unpack_dense(P, d.bands, d.consts.as<UnpackTables>(), nChunks, (const UnpackPlanEntry*)(din + oPlan),
+                                   din, inBytes, (const UnpackGroupDev*)(din + oGroups), d.err.as<UnpackErr>(), st));
+    MRC_HIP(h, hipEventRecord(d.ev[2], st));
+    MRC_HIP(h, hipMemcpyAsync(d.pinErr, d.err.p, sizeof(UnpackErr), hipMemcpyDeviceToHost, st));
+    MRC_HIP(h, hipStreamSynchronize(st));
+    if (d.pinErr->flag) {
+        const int64_t c = d.pinErr->firstBad;
+        const int64_t at = c < nChunks ? plan[c].off + file_offset[0] : 0;
+        const int64_t f = std::upper_bound(file_offset, file_offset + n_files + 1, at) - file_offset - 1;
+        std::snprintf(msg, sizeof msg, "mrc_decode_pac_pcm16: file %lld: chunk at byte %lld: %s", (long long)f,
+                      (long long)(at - file_offset[std::max<int64_t>(f, 0)]), status_text(d.pinErr->flag));
+        return fail(h, MRC_ERR_INVALID, msg);
+    }
+    double* x = d.x.as<double>();
+    MRC_HIP(h, hipMemsetAsync(x, 0, sizeof(double) * xDoubles, st));
+    for (int g = 0; g < kUnpackGroups; ++g) {
+        if (!nSlots[g]) continue;
+        const UnpackGroupDev& G = gd[g];
+        MRC_HIP(h, launch_decode(hs[g / 2]->dev, nSlots[g], G.joint ? 2 : 1, G.oscale, G.joint ? G.ms : nullptr, G.sf, G.ba,
+                                 G.mant, (const int64_t*)(din + oOffs) + slotBase[g], x, G.joint ? x + planeStride : nullptr,
+                                 st));
+    }
+    short* pcm = d.pcm.as<short>();
+    MRC_HIP(h, launch_pcm16_interleave(n_files, nOut, (const long long*)(din + oOutStart), (const long long*)(din + oXStart),
+                                       (const int*)(din + oNch), L, x, planeStride, pcm, st));
+    MRC_HIP(h, hipEventRecord(d.ev[3], st));
+    if (nOut) MRC_HIP(h, hipMemcpyAsync(d.pinOut.p, pcm, sizeof(int16_t) * nOut, hipMemcpyDeviceToHost, st));
+    MRC_HIP(h, hipEventRecord(d.ev[4], st));
+    MRC_HIP(h, hipStreamSynchronize(st));
+    for (int i = 0; i < 4; ++i) {
+        float ms = 0;
+        MRC_HIP(h, hipEventElapsedTime(&ms, d.ev[i], d.ev[i + 1]));
+        d.ms[i] = ms;
+    }
+    if (nOut) copy_host(out, d.pinOut.p, sizeof(int16_t) * nOut);
+    return MRC_OK;
+}
+
+int mrc_get_decode_ms(mrc_handle* h, double* ms) {
+    if (!h || !ms) return MRC_ERR_INVALID;
+    for (int i = 0; i < 4; ++i) ms[i] = h->dec.ms[i];
+    return MRC_OK;
+}
+
+}  // extern "C"

@@ -98,6 +98,27 @@ struct ChainBufs {
     }
 };
 
+// Device decode of whole `.pac` files (mrc_api_decode.cpp): reused from call to call
+struct DecodeBufs {
+    DevBuf consts;                   // UnpackTables + the band tables of the four block shapes (built once)
+    UnpackBands bands{};             // ... with device pointers into consts
+    DevBuf in;                       // one H2D copy: bytes | plan | group descriptors | block offsets | file tables
+    DevBuf groups;                   // dense per-(shape, kind) arrays decode_kernel reads
+    DevBuf x, pcm, err;              // decoded planes (float64), interleaved int16, UnpackErr
+    PinnedBuf pinIn, pinOut;
+    UnpackErr* pinErr = nullptr;     // page-locked copy of err
+    hipEvent_t ev[5] = {};           // start | copied in | unpacked | synthesised | copied out
+    double ms[4] = {0, 0, 0, 0};
+    void release() {
+        for (DevBuf* b : {&consts, &in, &groups, &x, &pcm, &err}) b->release();
+        pinIn.release();
+        pinOut.release();
+        if (pinErr) (void)hipHostFree(pinErr);
+        pinErr = nullptr;
+        for (auto& e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    }
+};
+
 }  // namespace mrc
 
 struct mrc_handle {
@@ -119,6 +140,7 @@ struct mrc_handle {
     mrc::DevBuf packWs;              // mrc_dev_pack_blocks: chunk sizes / positions / (table ids)
     int64_t packLastChunks = 0, packLastCap = 0;   // ... of the most recent call (mrc_dev_pack_status)
     mrc::ChainBufs chain;            // mrc_encode_chained_*: see mrc_api_chain.cpp
+    mrc::DecodeBufs dec;             // mrc_dev_unpack_blocks / mrc_decode_pac_pcm16: see mrc_api_decode.cpp
     double chainMs[4] = {0, 0, 0, 0};   // last chained encode: phase A, phase B, pack, whole call (host clock)
     bool timing = false;
     bool exactSpread = false;        // mrc_set_option(MRC_OPT_EXACT_SPREAD)

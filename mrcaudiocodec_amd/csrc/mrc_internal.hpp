@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 #include "mrc_hip.h"
+#include "mrc_unpack.hpp"
 
 namespace mrc {
 
@@ -158,6 +159,32 @@ hipError_t launch_pack_export(const void* ws, int64_t nChunks, long long* hostOu
                               hipStream_t st);
 const int* pack_error_flag(const void* ws, int64_t nChunks);          // device addresses inside ws
 const long long* pack_total_bytes(const void* ws, int64_t nChunks);
+// mrc_kernels_unpack.hip -- `.pac` chunk parsing on the device (the parser itself: mrc_unpack.hpp)
+void unpack_tables(UnpackTables* out);                      // host, from the table data in mrc_pack.cpp
+struct UnpackErr { int flag; int firstBad; };               // first bad chunk (lowest index) and its UnpackStatus
+// layout of mrc_unpack_blocks: chunk c = blk * nch + ch, buf / chunkOffset / outputs in device memory
+hipError_t launch_unpack_fixed(const UnpackParams& P, const UnpackBands& B, const UnpackTables* T /* device */,
+                               int64_t nBlocks, int nch, int joint, const uint8_t* buf, int64_t len,
+                               const int64_t* chunkOffset, const UnpackFixedOut& O, UnpackErr* err, hipStream_t st);
+// dense per-(shape, kind) group arrays that launch_decode consumes, at slots the host plan assigns
+constexpr int kUnpackGroups = 8;     // (shape 0..3) x (joint, non-joint): group = shape * 2 + (non-joint)
+struct UnpackGroupDev {
+    int shape, joint, nb, halfN;
+    int* oscale;                     // [n][joint ? 4 : 1]
+    int* ms;                         // [n][nb] (joint)
+    int* sf;                         // [n][joint ? 2 : 1][nb]
+    int* ba;
+    int* mant;                       // [n][joint ? 2 : 1][halfN]
+};
+struct UnpackPlanEntry { long long off; int groupStream; int slot; };   // groupStream = group * 2 + stream (joint ch)
+hipError_t launch_unpack_dense(const UnpackParams& P, const UnpackBands& B, const UnpackTables* T, int64_t nChunks,
+                               const UnpackPlanEntry* plan, const uint8_t* buf, int64_t len,
+                               const UnpackGroupDev* groups /* device [kUnpackGroups] */, UnpackErr* err, hipStream_t st);
+// decoded planes -> WAV-order interleaved int16 per file, the first skip samples of each file dropped: file f's values
+// are [outStart[f], outStart[f + 1]), its channel c at x[c * planeStride + xStart[f] + skip + t]
+hipError_t launch_pcm16_interleave(int64_t nFiles, int64_t nOut, const long long* outStart, const long long* xStart,
+                                   const int* nch, int skip, const double* x, int64_t planeStride, short* out,
+                                   hipStream_t st);
 // mrc_kernels_chain.hip -- chained stream encode: reservoir-free preparation per block, serial scan per stream
 constexpr int kChainMaxLinesPerItem = 2 * 1024;  // coded lines one scan item holds (all its streams together)
 struct ChainGroupDev {               // what chain_phase_b_kernel knows about one block-shape group (device memory)

@@ -328,6 +328,14 @@ void pack_tables(PackTables* out) {
         out->escape[t] = kTables[t].escape;
     }
 }
+void unpack_tables(UnpackTables* out) {
+    static_assert(kUnpackPeekBits == kPeekBits && kUnpackRawTable == kRawTable, "device and host parser tables");
+    for (int t = 0; t < 4; ++t) {
+        for (int w = 0; w < (1 << kPeekBits); ++w)
+            out->lut[t * (1 << kPeekBits) + w] = (unsigned short)((unsigned)kDecLut.value[t][w] | (unsigned)kDecLut.len[t][w] << 8);
+        out->escape[t] = kTables[t].escape;
+    }
+}
 }  // namespace mrc
 
 extern "C" {

@@ -299,3 +299,10 @@ def decode_pac_pcm16(handle, buf):
     pcm = torch.empty(x.shape, dtype=torch.int16, device=x.device)
     handle.dev_pcm16(x.numel(), x.data_ptr(), pcm.data_ptr(), torch.cuda.current_stream(x.device).cuda_stream)
     return pcm.cpu().numpy()
+
+
+def decode_pac_files(handle, bufs):
+    """Many `.pac` files (or one) to 16-bit PCM in ONE call on the GPU of `handle` (created with the files' parameters):
+    the bytes cross PCIe once, chunk parsing and Huffman decoding run on the device as well (mrc_decode_pac_pcm16).
+    -> list of int16 [nCh][samples], bit-identical to decode_pac_pcm16 of each file (views of one WAV-order buffer)."""
+    return handle.decode_pac_pcm16(bufs, interleaved=False)
