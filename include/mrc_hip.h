@@ -353,7 +353,7 @@ int mrc_dev_pack_status(mrc_handle* h, int64_t* total_bytes, void* stream);
  *   reservoir_in [n_streams] (NULL: zeros): codingParams.bitReservoir at the start (pacfileThem.py:1111), e.g. handed
  *     over from the previous shard of a long stream.
  *   use_huffman = 0: EncodeNoHuff's raw mantissas (table id 15).  with_flush: append Close()'s two non-joint chunks
- *     per stream (the stream must then end with a long block, as the reference's Close() assumes).
+ *     per stream (one for mono streams) (the stream must then end with a long block, as the reference's Close() assumes).
  *   num_samples [n_streams] (NULL: no headers): the header's sample count (the WAV's, pacfileThem.py:1103); the header
  *     of stream s is written in front of its first chunk, so out[stream_byte_offset[s] .. stream_byte_offset[s + 1])
  *     is the complete `.pac` file of stream s.
@@ -363,11 +363,21 @@ int mrc_dev_pack_status(mrc_handle* h, int64_t* total_bytes, void* stream);
  *     NULL only the stream starts come back).  reservoir_out (NULL or [n_streams]): codingParams.bitReservoir after the
  *     last block.
  *     reservoir_trace (NULL or [n_items]): ... after every block (tests).
+ * MONO streams: pcm_right == NULL (as in mrc_dev_encode / mrc_encode_stream_pcm16).  The encode loop is then the
+ *   reference's with WriteDataBlock in place of JointWriteDataBlock (pacfileThem.py:622-790, codecThem.py:205-231): a
+ *   header with nChannels = 1, ONE non-joint chunk per block with the reservoir carried from block to block, and with
+ *   with_flush ONE Close() chunk per stream (the last hop followed by a hop of zeros).  n_items = blocks + n_streams
+ *   with_flush; item_byte_offset and reservoir_trace hold one entry per item as for stereo.  Everything else -- shapes,
+ *   slabs, reservoir_in / reservoir_out, mrc_chain_fetch_output, MRC_OPT_SENSITIVITY -- works as for stereo streams.
  * mrc_dev_encode_chained_pac: the same with pcm_left / pcm_right / out in DEVICE memory (all other pointers host);
  * it synchronises `stream` before it returns (the byte offsets come back).  mrc_get_chain_ms: device time of the last
- * chained call -- ms[0] phase A + preparation, ms[1] the serial scan, ms[2] packing, ms[3] all three. */
+ * chained call -- ms[0] phase A + preparation, ms[1] the serial scan, ms[2] packing, ms[3] all three.
+ * mrc_chain_out_bound: the output bound of a call on stereo streams; mrc_chain_out_bound_ex: of a call on n_channels = 1
+ * (mono) or 2 (stereo) streams (mrc_chain_out_bound == mrc_chain_out_bound_ex with 2). */
 int64_t mrc_chain_out_bound(mrc_handle* h, int64_t n_streams, const int64_t* block_start, const int32_t* block_a,
                             const int32_t* block_b, int with_flush, int with_headers);
+int64_t mrc_chain_out_bound_ex(mrc_handle* h, int n_channels, int64_t n_streams, const int64_t* block_start,
+                               const int32_t* block_a, const int32_t* block_b, int with_flush, int with_headers);
 int mrc_encode_chained_stream_pcm16_pac(mrc_handle* h, int64_t n_streams, const int16_t* pcm_left, const int16_t* pcm_right,
                                         int64_t stream_stride, const int64_t* block_start, const int64_t* block_offset,
                                         const int32_t* block_a, const int32_t* block_b, const int32_t* reservoir_in,

@@ -110,6 +110,7 @@ def _load():
                                 [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, _i64p, C.c_void_p]),
         "mrc_dev_pack_status": (C.c_int, [H, _i64p, C.c_void_p]),
         "mrc_chain_out_bound": (C.c_int64, [H, C.c_int64, _i64p, _i32p, _i32p, C.c_int, C.c_int]),
+        "mrc_chain_out_bound_ex": (C.c_int64, [H, C.c_int, C.c_int64, _i64p, _i32p, _i32p, C.c_int, C.c_int]),
         "mrc_encode_chained_stream_pcm16_pac": (C.c_int, [H, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, _i64p, _i64p, _i32p,
                                                           _i32p, _i32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
                                                           _i64p, _i64p, _i32p, _i32p, _i64p]),
@@ -425,20 +426,26 @@ class Handle:
         """mrc_encode_chained_stream_pac: stereo streams [nStreams][stride] -- int16 PCM codes or float64 signed fractions,
         each starting with its prior hop -- + the block shapes of every stream -> the `.pac` bytes of every stream (with
         num_samples: complete files, header included), the bit reservoir carried from block to block on the device.
-        device = (left_ptr, right_ptr, sample_format, stride, out_ptr, out_cap): everything stays in HBM
+        pcm_right None: MONO streams (one chunk per block, one Close() chunk, nChannels = 1 in the header).
+        device = (left_ptr, right_ptr or None, sample_format, stride, out_ptr, out_cap): everything stays in HBM
         (mrc_dev_encode_chained_pac; `bytes` is then None).
         -> dict: bytes (uint8), stream_offset [nStreams + 1], reservoir_out [nStreams], total, (trace), and with want_items
         item_offset [nItems + 1]: where every block's bytes start (costs a read-back of all chunk positions)."""
         start, off, a, b = self._chain_schedule(shapes)
         n_streams = len(shapes)
         if device is None:
-            pl, pr = np.atleast_2d(pcm_left), np.atleast_2d(pcm_right)
+            mono = pcm_right is None
+            pl = np.atleast_2d(pcm_left)
             dt = np.int16 if pl.dtype == np.int16 else np.float64
-            pl, pr = np.ascontiguousarray(pl, dtype=dt), np.ascontiguousarray(pr, dtype=dt)
-            if pl.shape != pr.shape or pl.shape[0] != n_streams:
+            pl = np.ascontiguousarray(pl, dtype=dt)
+            pr = None if mono else np.ascontiguousarray(np.atleast_2d(pcm_right), dtype=dt)
+            if (not mono and pl.shape != pr.shape) or pl.ndim != 2 or pl.shape[0] != n_streams:
                 raise ValueError("pcm_left / pcm_right must be [nStreams][stride], one row per shape list")
             stride, fmt = pl.shape[1], (1 if dt == np.int16 else 0)
-        n_items = len(off) + (2 * n_streams if with_flush else 0)
+        else:
+            mono = device[1] is None
+        nch = 1 if mono else 2
+        n_items = len(off) + (nch * n_streams if with_flush else 0)
         ns = None if num_samples is None else np.ascontiguousarray(num_samples, dtype=np.uint32)
         if ns is not None and ns.shape != (n_streams,):
             raise ValueError("num_samples: one value per stream")
@@ -458,8 +465,7 @@ class Handle:
             self._check(lib.mrc_dev_encode_chained_pac(self._h, n_streams, dl, dr, int(fmt), int(stride), *sched, dout, int(dcap),
                                                        *tail, stream))
         else:
-            bound = int(lib.mrc_chain_out_bound(self._h, n_streams, _p(start, _i64p), _p(a, _i32p), _p(b, _i32p),
-                                                1 if with_flush else 0, 0 if ns is None else 1))
+            bound = self.chain_out_bound(start, a, b, with_flush, ns is not None, nch)
             if bound < 0:
                 raise MrcError("mrc_chain_out_bound failed (%d): block shape out of range" % bound)
             # a buffer for typical content (~3 bits per sample); if the streams pack to more, the call says how much and
@@ -482,6 +488,13 @@ class Handle:
         if want_trace:
             out["reservoir_trace"] = trace
         return out
+
+    def chain_out_bound(self, block_start, block_a, block_b, with_flush=True, with_headers=True, n_channels=2):
+        """mrc_chain_out_bound_ex: the worst-case output bytes of a chained call on n_channels = 1 (mono) or 2 streams."""
+        start = np.ascontiguousarray(block_start, dtype=np.int64)
+        a, b = np.ascontiguousarray(block_a, dtype=np.int32), np.ascontiguousarray(block_b, dtype=np.int32)
+        return int(lib.mrc_chain_out_bound_ex(self._h, int(n_channels), len(start) - 1, _p(start, _i64p), _p(a, _i32p),
+                                              _p(b, _i32p), 1 if with_flush else 0, 1 if with_headers else 0))
 
     def chain_ms(self):
         """device time of the last chained encode: phase A + preparation, serial scan, packing, all three (ms)"""

@@ -1,12 +1,14 @@
 """
 Encode direction of the reference's command line (`python pacfileThem.py in.wav`, pacfileThem.py:1064-1231)
-on the MI355X path:  python -m mrcaudiocodec_amd.cli in.wav out.pac [--no-huffman] [--device N]
+on the MI355X path:  python -m mrcaudiocodec_amd.cli in.wav out.pac [--no-huffman] [--device N]  (mono or stereo)
 
 WAV ingest (pcmfile.py:34-102: 16-bit PCM, int16 code c -> sign(c) 2|c|/65535), transient detection with
 one hop of look-ahead (pacfileThem.py:1025-1056, 1182-1214), joint-stereo blocks with the bit reservoir
-chained through the Huffman savings, Close()'s flush block, `.pac` framing -- kernels on the GPU, Huffman
-and bit packing in C++ on the host.  Like the reference: stereo input only, and the last hop of the file is
-analysed but never encoded.
+chained through the Huffman savings, Close()'s flush block, `.pac` framing -- the whole loop in one library call on
+the GPU.  Like the reference, the last hop of the file is analysed but never encoded.
+Mono WAVs: the same loop with WriteDataBlock in place of JointWriteDataBlock (the reference library's mono path,
+pacfileThem.py:622-790 and the commented-out call at 1218): one-channel blocks, one Close() block.  Other channel
+counts are refused: the file format's readers stop at two channels and Close() flushes at most two.
 
 Decode direction (row f-4):  python -m mrcaudiocodec_amd.cli -d in.pac out.wav
 One library call (mrc_decode_pac_pcm16): chunk parsing and Huffman decoding, dequantise / M-S / IMDCT / window /
@@ -72,8 +74,9 @@ def encode_wav(in_path, out_path=None, use_huffman=True, device_id=0, handle=Non
     The file's int16 codes go to the device as they are: the transient detector (mrc_transient_peaks_ex) and the whole
     encode loop (ONE call, mrc_encode_chained_stream_pcm16_pac) read them there; 2 bytes per sample on the host."""
     rate, n_ch, num_samples, pcm = read_wav_pcm(in_path)
-    if n_ch != 2:
-        raise ValueError("stereo input only (the reference's JointEncode indexes data[0], data[1])")
+    if n_ch not in (1, 2):
+        raise ValueError("%d-channel input: mono and stereo WAV files only (the .pac readers refuse more than two channels "
+                         "and the reference's Close() flushes at most two)" % n_ch)
     h = handle if handle is not None else Handle(sample_rate=rate, device_id=device_id)
     was_exact = h.get_option(1)
     was_sens = h.get_option(5)
@@ -84,13 +87,14 @@ def encode_wav(in_path, out_path=None, use_huffman=True, device_id=0, handle=Non
         h.sensitivity()
     try:
         L = h.cfg.n_mdct_lines
-        codes = np.concatenate([np.zeros((2, L), np.int16), pcm], axis=1)      # the zero prior hop (pacfileThem.py:615-618)
+        codes = np.concatenate([np.zeros((n_ch, L), np.int16), pcm], axis=1)   # the zero prior hop (pacfileThem.py:615-618)
+        right = None if n_ch == 1 else codes[1][None]                          # (None: mono streams)
         shapes = transient.block_shape_array(h, codes)
         if not len(shapes):
             raise ValueError("file too short: fewer than two hops")
         if shapes[-1, 2] != L:
             raise ValueError("the stream must end with a long block (the reference's Close() assumes it)")
-        r = h.encode_chained_pac(codes[0][None], codes[1][None], [shapes], use_huffman=use_huffman, with_flush=True,
+        r = h.encode_chained_pac(codes[0][None], right, [shapes], use_huffman=use_huffman, with_flush=True,
                                  num_samples=[num_samples])
         data = r["bytes"].tobytes()
         if certify is not None:
@@ -100,7 +104,7 @@ def encode_wav(in_path, out_path=None, use_huffman=True, device_id=0, handle=Non
             if near and not exact_spread:
                 h.set_option(5, 0)
                 h.set_option(1, 1)
-                again = h.encode_chained_pac(codes[0][None], codes[1][None], [shapes], use_huffman=use_huffman, with_flush=True,
+                again = h.encode_chained_pac(codes[0][None], right, [shapes], use_huffman=use_huffman, with_flush=True,
                                              num_samples=[num_samples])
                 certify["bytes_equal_exact_spread"] = again["bytes"].tobytes() == data
     finally:
@@ -146,7 +150,7 @@ def decode_pac_file(pac_path, wav_path, device_id=0):
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description="Encode a stereo 16-bit WAV to .pac (or, with -d, decode a .pac to WAV) "
+    ap = argparse.ArgumentParser(description="Encode a mono or stereo 16-bit WAV to .pac (or, with -d, decode a .pac to WAV) "
                                              "on an MI355X")
     ap.add_argument("src")
     ap.add_argument("dst")

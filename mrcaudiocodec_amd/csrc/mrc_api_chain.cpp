@@ -1,6 +1,7 @@
 // C ABI, chained stream encode (include/mrc_hip.h: mrc_encode_chained_stream_pcm16_pac, mrc_dev_encode_chained_pac):
 // the encode direction of the reference's command line (pacfileThem.py:1159-1214, Close() 973-984, file header 586-613)
-// for whole stereo streams in ONE call, block shapes in, `.pac` bytes out.
+// for whole stereo streams in ONE call, block shapes in, `.pac` bytes out -- and, with pcm_right == nullptr, the same loop
+// for mono streams with WriteDataBlock in place of JointWriteDataBlock (pacfileThem.py:622-790, codecThem.py:205-231).
 //
 //   phase A   per block shape, ONE launch set over all blocks of all streams: windowed MDCT, overall scale, M/S switch,
 //             SMRs, band peaks (the batch kernels) -- nothing here depends on the bit reservoir;
@@ -10,6 +11,10 @@
 //   pack      per block shape plan / write kernels of the device packer around ONE prefix sum over all chunks in file
 //             order, the file headers in front of every stream.
 // No computation happens in this file.
+//
+// Items, in file order per stream:  stereo  one joint block (two chunks) per block shape, Close()'s two one-channel blocks
+//                                           (one chunk each);
+//                                   mono    one one-channel block (one chunk) per block shape, Close()'s one block.
 #include "mrc_handle.hpp"
 
 #include <cstring>
@@ -41,25 +46,33 @@ int mrc_get_chain_ms(mrc_handle* h, double* ms) {
     return MRC_OK;
 }
 
-int64_t mrc_chain_out_bound(mrc_handle* h, int64_t n_streams, const int64_t* block_start, const int32_t* block_a,
-                            const int32_t* block_b, int with_flush, int with_headers) {
-    if (!h || n_streams < 0 || !block_start || !block_a || !block_b) return MRC_ERR_INVALID;
+int64_t mrc_chain_out_bound_ex(mrc_handle* h, int n_channels, int64_t n_streams, const int64_t* block_start,
+                               const int32_t* block_a, const int32_t* block_b, int with_flush, int with_headers) {
+    if (!h || (n_channels != 1 && n_channels != 2) || n_streams < 0 || !block_start || !block_a || !block_b)
+        return MRC_ERR_INVALID;
     const int L = h->cfg.n_mdct_lines, Sh = h->cfg.n_short;
+    const int joint = n_channels == 2 ? 1 : 0;           // stereo: joint blocks; mono: one-channel blocks
     // a stream has four block shapes: their bounds once, not one band table per block
     const int sa[4] = {L, L, Sh, Sh}, sb[4] = {L, Sh, Sh, L};
     int64_t shapeBound[4];
-    for (int g = 0; g < 4; ++g) shapeBound[g] = mrc_pack_bound(&h->cfg, sa[g], sb[g], 2, 1);
+    for (int g = 0; g < 4; ++g) shapeBound[g] = mrc_pack_bound(&h->cfg, sa[g], sb[g], n_channels, joint);
     int64_t total = 0;
     for (int64_t i = block_start[0]; i < block_start[n_streams]; ++i) {
         const int g = (block_a[i] == L ? 0 : 2) + ((block_a[i] == L) == (block_b[i] == L) ? 0 : 1);
         int64_t bnd = shapeBound[g];
-        if (block_a[i] != sa[g] || block_b[i] != sb[g]) bnd = mrc_pack_bound(&h->cfg, block_a[i], block_b[i], 2, 1);   // (refused later)
+        if (block_a[i] != sa[g] || block_b[i] != sb[g])
+            bnd = mrc_pack_bound(&h->cfg, block_a[i], block_b[i], n_channels, joint);   // (refused later)
         if (bnd < 0) return MRC_ERR_INVALID;
         total += bnd;
     }
-    if (with_flush) total += n_streams * mrc_pack_bound(&h->cfg, L, L, 2, 0);
+    if (with_flush) total += n_streams * mrc_pack_bound(&h->cfg, L, L, n_channels, 0);
     if (with_headers) total += n_streams * 128;
     return total;
+}
+
+int64_t mrc_chain_out_bound(mrc_handle* h, int64_t n_streams, const int64_t* block_start, const int32_t* block_a,
+                            const int32_t* block_b, int with_flush, int with_headers) {
+    return mrc_chain_out_bound_ex(h, 2, n_streams, block_start, block_a, block_b, with_flush, with_headers);
 }
 
 }  // extern "C"
@@ -67,14 +80,14 @@ int64_t mrc_chain_out_bound(mrc_handle* h, int64_t n_streams, const int64_t* blo
 namespace {
 
 // One SLAB of a chained encode: all of the streams [0, n_streams) handed over, every buffer sized for exactly these blocks
-// (the entry points below cut a call into slabs).
+// (the entry points below cut a call into slabs).  pcm_right == nullptr: mono streams.
 int chained_core(mrc_handle* h, int64_t n_streams, const void* pcm_left, const void* pcm_right,
                  int sample_format, int64_t stream_stride, const int64_t* block_start, const int64_t* block_offset,
                  const int32_t* block_a, const int32_t* block_b, const int32_t* reservoir_in,
                  int use_huffman, int with_flush, const uint32_t* num_samples, uint8_t* out, int64_t out_cap,
                  int64_t* stream_byte_offset, int64_t* item_byte_offset, int32_t* reservoir_out,
                  int32_t* reservoir_trace, int64_t* total_bytes, void* stream) {
-    if (!h || n_streams < 0 || !pcm_left || !pcm_right || stream_stride <= 0 || !block_start || !block_offset ||
+    if (!h || n_streams < 0 || !pcm_left || stream_stride <= 0 || !block_start || !block_offset ||
         !block_a || !block_b || !out || out_cap < 0 || !stream_byte_offset || !total_bytes ||
         (sample_format != MRC_SAMPLES_F64 && sample_format != MRC_SAMPLES_PCM16))
         return fail(h, MRC_ERR_INVALID, "mrc_encode_chained: bad argument");
@@ -84,6 +97,8 @@ int chained_core(mrc_handle* h, int64_t n_streams, const void* pcm_left, const v
     if (n_streams == 0) return MRC_OK;
     const mrc_config& cfg = h->cfg;
     const int L = cfg.n_mdct_lines, Sh = cfg.n_short;
+    // stereo: groups 0-3 joint (two chunks per block), Close() two one-channel items; mono: every item one channel
+    const int nch = pcm_right ? 2 : 1, stereo = nch == 2;
     const int64_t b0 = block_start[0], nB = block_start[n_streams] - b0;
     if (nB < n_streams) return fail(h, MRC_ERR_INVALID, "mrc_encode_chained: every stream needs at least one block");
     // ---- the block shapes of the reference's block switching (pacfileThem.py:1192-1210); group 4: Close()'s blocks
@@ -93,7 +108,7 @@ int chained_core(mrc_handle* h, int64_t n_streams, const void* pcm_left, const v
     for (int g = 0; g < nGroups; ++g) {
         MRC_TRY(get_shape(h, shapeA[g], shapeB[g], &hs[g]));
         const DevShape& S = hs[g]->dev;
-        const int nstream = g == 4 ? 1 : 2, nTot = nstream * S.nBands;
+        const int nstream = (g == 4 || !stereo) ? 1 : 2, nTot = nstream * S.nBands;
         if (nTot > 64 || S.maxMantBits < 2 || S.maxMantBits > 16 || (S.halfN & 3))
             return fail(h, MRC_ERR_INVALID, "mrc_encode_chained: shape outside what the chained back end covers "
                                             "(<= 32 bands, 2..16 mantissa bits, lines a multiple of 4)");
@@ -104,8 +119,8 @@ int chained_core(mrc_handle* h, int64_t n_streams, const void* pcm_left, const v
     // ---- the schedule, pass 1: validate, sort the blocks into their shape groups (the offsets phase A needs).  The rest of
     // the schedule (items in file order, chunk maps, headers) is only needed by the serial scan and the packer: it is built
     // and uploaded in pass 2, AFTER phase A's launches are queued, so the device works while the host prepares it.
-    const int64_t nItems = nB + (with_flush ? 2 * n_streams : 0);
-    const int64_t nChunks = 2 * nB + (with_flush ? 2 * n_streams : 0);
+    const int64_t nItems = nB + (with_flush ? nch * n_streams : 0);
+    const int64_t nChunks = nch * nB + (with_flush ? nch * n_streams : 0);
     std::vector<uint8_t> groupOf((size_t)nB);
     std::vector<int64_t> offs[kChainGroups];
     std::vector<long long> tailOff((size_t)n_streams);
@@ -150,7 +165,7 @@ int chained_core(mrc_handle* h, int64_t n_streams, const void* pcm_left, const v
     if (with_flush) {
         // the tail offsets ride in the offsets buffer of group 4 (its blocks are laid out explicitly, stride 2 L)
         MRC_TRY(upload(h, C.g[4].offsets, tailOff, st));
-        MRC_HIP(h, C.flushPcm.reserve((size_t)n_streams * 2 * 2 * L * sampleBytes));
+        MRC_HIP(h, C.flushPcm.reserve((size_t)n_streams * nch * 2 * L * sampleBytes));
         MRC_HIP(h, launch_chain_flush_gather(n_streams, L, pcm_left, pcm_right, sample_format, stream_stride,
                                              C.g[4].offsets.as<long long>(), C.flushPcm.p, st));
     }
@@ -160,8 +175,8 @@ int chained_core(mrc_handle* h, int64_t n_streams, const void* pcm_left, const v
     int64_t count[kChainGroups] = {};
     for (int g = 0; g < nGroups; ++g) {
         const DevShape& S = hs[g]->dev;
-        const int joint = g == 4 ? 0 : 1, nsig = joint ? 4 : 1, nstream = joint ? 2 : 1;
-        const int64_t m = g == 4 ? 2 * n_streams : (int64_t)offs[g].size();
+        const int joint = (g == 4 || !stereo) ? 0 : 1, nsig = joint ? 4 : 1, nstream = joint ? 2 : 1;
+        const int64_t m = g == 4 ? nch * n_streams : (int64_t)offs[g].size();
         count[g] = m;
         ChainGroupBufs& B = C.g[g];
         const int nTot = nstream * S.nBands, nEv = (int)chain_events_per_block(S, joint);
@@ -171,7 +186,7 @@ int chained_core(mrc_handle* h, int64_t n_streams, const void* pcm_left, const v
             MRC_HIP(h, B.oscale.reserve((size_t)m * nsig * sizeof(int32_t)));
             MRC_HIP(h, B.smr.reserve((size_t)m * nsig * S.nBands * sizeof(double)));
             MRC_HIP(h, B.peak.reserve((size_t)m * nsig * S.nBands * sizeof(double)));
-            MRC_HIP(h, B.ms.reserve((size_t)m * S.nBands * sizeof(int32_t)));
+            if (joint) MRC_HIP(h, B.ms.reserve((size_t)m * S.nBands * sizeof(int32_t)));
             MRC_HIP(h, B.ev.reserve((size_t)m * nEv * sizeof(unsigned)));
             MRC_HIP(h, B.pre.reserve((size_t)m * (nEv + 1) * sizeof(unsigned)));
             MRC_HIP(h, B.bitAlloc.reserve((size_t)m * nTot * sizeof(int32_t)));
@@ -181,10 +196,10 @@ int chained_core(mrc_handle* h, int64_t n_streams, const void* pcm_left, const v
             if (g == 4)
                 MRC_TRY(encode_phase_a(h, S, m, C.flushPcm.p, nullptr, sample_format, 2 * (int64_t)L, nullptr, B.lines.as<double>(),
                                        B.oscale.as<int32_t>(), nullptr, B.smr.as<double>(), B.peak.as<double>(), st, false));
-            else
+            else                                             // (pcm_right == nullptr: the mono kernels, no M/S switch)
                 MRC_TRY(encode_phase_a(h, S, m, pcm_left, pcm_right, sample_format, 0, B.offsets.as<int64_t>(),
-                                       B.lines.as<double>(), B.oscale.as<int32_t>(), B.ms.as<int32_t>(), B.smr.as<double>(),
-                                       B.peak.as<double>(), st, false));
+                                       B.lines.as<double>(), B.oscale.as<int32_t>(), joint ? B.ms.as<int32_t>() : nullptr,
+                                       B.smr.as<double>(), B.peak.as<double>(), st, false));
             MRC_HIP(h, launch_chain_prep(S, joint, m, B.smr.as<double>(), joint ? B.ms.as<int32_t>() : nullptr,
                                          B.ev.as<unsigned>(), B.pre.as<unsigned>(),
                                          h->chainForceFallback ? 1 : 0, st));
@@ -197,7 +212,7 @@ int chained_core(mrc_handle* h, int64_t n_streams, const void* pcm_left, const v
         D.budgetMono = S.budgetMono; D.budgetJointPre = S.budgetJointPre; D.blkswA = S.blkswA; D.blkswB = S.blkswB;
         D.bandOfLine = S.bandOfLine; D.bandN = S.bandN;
         D.lines = B.lines.as<double>(); D.peak = B.peak.as<double>(); D.oscale = B.oscale.as<int32_t>();
-        D.ms = B.ms.as<int32_t>(); D.ev = B.ev.as<unsigned>();
+        D.ms = joint ? B.ms.as<int32_t>() : nullptr; D.ev = B.ev.as<unsigned>();
         D.pre = B.pre.as<unsigned>();
         D.bitAlloc = B.bitAlloc.as<int32_t>(); D.scaleFactor = B.scaleFactor.as<int32_t>();
         D.mant = B.mant.as<unsigned short>(); D.table = B.table.as<int32_t>();
@@ -209,8 +224,8 @@ int chained_core(mrc_handle* h, int64_t n_streams, const void* pcm_left, const v
     itemChunk.resize((size_t)nItems + 1);
     chunkStream.resize((size_t)nChunks);
     resIn.assign((size_t)n_streams, 0);
-    for (int g = 0; g < 4; ++g) chunkMap[g].resize(2 * offs[g].size());
-    if (with_flush) chunkMap[4].resize((size_t)2 * n_streams);
+    for (int g = 0; g < 4; ++g) chunkMap[g].resize(nch * offs[g].size());
+    if (with_flush) chunkMap[4].resize((size_t)nch * n_streams);
     {
         int64_t it = 0, ch = 0;
         size_t idx[kChainGroups] = {};
@@ -221,15 +236,17 @@ int chained_core(mrc_handle* h, int64_t n_streams, const void* pcm_left, const v
                 const int g = groupOf[(size_t)(i - b0)];
                 const size_t k = idx[g]++;
                 items[(size_t)it] = (int32_t)((unsigned)g << 28 | (unsigned)k);
-                chunkMap[g][2 * k] = ch; chunkMap[g][2 * k + 1] = ch + 1;
                 itemChunk[(size_t)it] = ch;
-                chunkStream[(size_t)ch] = chunkStream[(size_t)ch + 1] = (int32_t)s;
-                ch += 2; ++it;
+                for (int c = 0; c < nch; ++c) {
+                    chunkMap[g][nch * k + c] = ch;
+                    chunkStream[(size_t)ch++] = (int32_t)s;
+                }
+                ++it;
             }
             if (with_flush)
-                for (int c = 0; c < 2; ++c) {                      // codec.Encode: channel after channel
-                    items[(size_t)it] = (int32_t)(4u << 28 | (unsigned)(2 * s + c));
-                    chunkMap[4][(size_t)(2 * s + c)] = ch;
+                for (int c = 0; c < nch; ++c) {                    // codec.Encode: channel after channel
+                    items[(size_t)it] = (int32_t)(4u << 28 | (unsigned)(nch * s + c));
+                    chunkMap[4][(size_t)(nch * s + c)] = ch;
                     itemChunk[(size_t)it] = ch;
                     chunkStream[(size_t)ch] = (int32_t)s;
                     ++ch; ++it;
@@ -246,7 +263,7 @@ int chained_core(mrc_handle* h, int64_t n_streams, const void* pcm_left, const v
         // the reference's padding rule, pacfileThem.py:595-597: padded when it ALREADY is a multiple of nMDCTLines)
         uint8_t one[256];
         int64_t len = 0;
-        if (mrc_pac_header(&cfg, 2, num_samples[0], one, sizeof(one), &len) != MRC_OK || len < 14)
+        if (mrc_pac_header(&cfg, nch, num_samples[0], one, sizeof(one), &len) != MRC_OK || len < 14)
             return fail(h, MRC_ERR_INVALID, "mrc_encode_chained: mrc_pac_header failed");
         hdrLen = (int)len;
         hdr.resize((size_t)n_streams * len);
@@ -278,7 +295,7 @@ int chained_core(mrc_handle* h, int64_t n_streams, const void* pcm_left, const v
     if (h->sensOn)                                       // MRC_OPT_SENSITIVITY: the scan's decisions, group by group
         for (int g = 0; g < nGroups; ++g) {
             ChainGroupBufs& B = C.g[g];
-            const int joint = g == 4 ? 0 : 1;
+            const int joint = desc[g].joint;
             MRC_HIP(h, launch_sensitivity(hs[g]->dev, count[g], joint, B.lines.as<double>(), B.oscale.as<int32_t>(),
                                           B.smr.as<double>(), B.peak.as<double>(), joint ? B.ms.as<int32_t>() : nullptr,
                                           B.bitAlloc.as<int32_t>(), B.scaleFactor.as<int32_t>(),
@@ -291,7 +308,7 @@ int chained_core(mrc_handle* h, int64_t n_streams, const void* pcm_left, const v
     MRC_HIP(h, hipMemsetAsync(W.errorFlag, 0, sizeof(int), st));
     PackParams P[kChainGroups];
     for (int g = 0; g < nGroups; ++g) {
-        const int joint = g == 4 ? 0 : 1;
+        const int joint = desc[g].joint;
         P[g].nch = joint ? 2 : 1; P[g].joint = joint; P[g].useHuffman = use_huffman ? 1 : 0;
         P[g].nScaleBits = cfg.n_scale_bits; P[g].nMantSizeBits = cfg.n_mant_size_bits;
         P[g].blkBitsA = cfg.blksw_bits_a; P[g].blkBitsB = cfg.blksw_bits_b;
@@ -401,6 +418,7 @@ int chained_slabs(mrc_handle* h, int64_t n_streams, const void* pcm_left, const 
     for (int64_t s = 0; s < n_streams; ++s)
         if (block_start[s + 1] <= block_start[s]) return fail(h, MRC_ERR_INVALID, "mrc_encode_chained: every stream needs at least one block");
     const size_t sampleBytes = sample_format == MRC_SAMPLES_PCM16 ? sizeof(int16_t) : sizeof(double);
+    const int nch = pcm_right ? 2 : 1;                   // (pcm_right == nullptr: mono streams)
     const std::vector<Slab> slabs = plan_slabs(n_streams, block_start, h->chainSlabBlocks > 0 ? h->chainSlabBlocks : (int64_t)1 << 40);
     ChainBufs& C = h->chain;
     C.lastTotal = -1;
@@ -411,14 +429,14 @@ int chained_slabs(mrc_handle* h, int64_t n_streams, const void* pcm_left, const 
     int32_t carry = 0;
     for (const Slab& sl : slabs) {
         const char* pl = (const char*)pcm_left + (size_t)sl.s0 * stream_stride * sampleBytes;
-        const char* pr = (const char*)pcm_right + (size_t)sl.s0 * stream_stride * sampleBytes;
+        const char* pr = pcm_right ? (const char*)pcm_right + (size_t)sl.s0 * stream_stride * sampleBytes : nullptr;
         const int64_t bs2[2] = {sl.i0, sl.i1};
         const int64_t* bs = sl.timeSlab ? bs2 : block_start + sl.s0;
         const int flush = with_flush && sl.last;
         const uint32_t* nsamp = (num_samples && sl.first) ? num_samples + sl.s0 : nullptr;
         const int32_t* resIn = sl.timeSlab ? (sl.first ? (reservoir_in ? reservoir_in + sl.s0 : nullptr) : &carry)
                                            : (reservoir_in ? reservoir_in + sl.s0 : nullptr);
-        const int64_t nItems = (sl.i1 - sl.i0) + (flush ? 2 * sl.ns : 0);
+        const int64_t nItems = (sl.i1 - sl.i0) + (flush ? nch * sl.ns : 0);
         sOff.assign((size_t)sl.ns + 1, 0);
         if (item_byte_offset) iOff.assign((size_t)nItems + 1, 0);
         int64_t slabTotal = 0;
@@ -426,7 +444,7 @@ int chained_slabs(mrc_handle* h, int64_t n_streams, const void* pcm_left, const 
         int64_t cap;
         if (direct_out && !overflow) { dst = direct_out + written; cap = out_cap - written; }
         else {
-            const int64_t bound = mrc_chain_out_bound(h, sl.ns, bs, block_a, block_b, flush, nsamp != nullptr);
+            const int64_t bound = mrc_chain_out_bound_ex(h, nch, sl.ns, bs, block_a, block_b, flush, nsamp != nullptr);
             if (bound < 0) return fail(h, MRC_ERR_INVALID, "mrc_encode_chained: block shape out of range");
             MRC_HIP(h, hipSetDevice(h->device));
             MRC_HIP(h, C.out.reserve((size_t)bound + 1));
@@ -474,7 +492,7 @@ int mrc_dev_encode_chained_pac(mrc_handle* h, int64_t n_streams, const void* pcm
                                int use_huffman, int with_flush, const uint32_t* num_samples, uint8_t* out, int64_t out_cap,
                                int64_t* stream_byte_offset, int64_t* item_byte_offset, int32_t* reservoir_out,
                                int32_t* reservoir_trace, int64_t* total_bytes, void* stream) {
-    if (!h || !pcm_left || !pcm_right || stream_stride <= 0 || !block_offset || !block_a || !block_b || !out || out_cap < 0 ||
+    if (!h || !pcm_left || stream_stride <= 0 || !block_offset || !block_a || !block_b || !out || out_cap < 0 ||
         (sample_format != MRC_SAMPLES_F64 && sample_format != MRC_SAMPLES_PCM16))
         return fail(h, MRC_ERR_INVALID, "mrc_encode_chained: bad argument");
     return chained_slabs(h, n_streams, pcm_left, pcm_right, sample_format, stream_stride, block_start, block_offset, block_a,
@@ -489,24 +507,24 @@ int mrc_encode_chained_stream_pac(mrc_handle* h, int64_t n_streams, const void* 
                                   const int32_t* reservoir_in, int use_huffman, int with_flush, const uint32_t* num_samples,
                                   uint8_t* out, int64_t out_cap, int64_t* stream_byte_offset, int64_t* item_byte_offset,
                                   int32_t* reservoir_out, int32_t* reservoir_trace, int64_t* total_bytes) {
-    if (!h || n_streams < 0 || !pcm_left || !pcm_right || stream_stride <= 0 || !out || !total_bytes || !block_start ||
+    if (!h || n_streams < 0 || !pcm_left || stream_stride <= 0 || !out || !total_bytes || !block_start ||
         (sample_format != MRC_SAMPLES_F64 && sample_format != MRC_SAMPLES_PCM16))
         return fail(h, MRC_ERR_INVALID, "mrc_encode_chained_stream_pac: bad argument");
     MRC_HIP(h, hipSetDevice(h->device));
     ChainBufs& C = h->chain;
     const size_t pcmBytes = (size_t)n_streams * stream_stride * (sample_format == MRC_SAMPLES_PCM16 ? sizeof(int16_t) : sizeof(double));
     MRC_HIP(h, C.pcmL.reserve(pcmBytes ? pcmBytes : 1));
-    MRC_HIP(h, C.pcmR.reserve(pcmBytes ? pcmBytes : 1));
+    if (pcm_right) MRC_HIP(h, C.pcmR.reserve(pcmBytes ? pcmBytes : 1));      // (mono streams: no right channel)
     SyncGuard guard{h->stream};
     if (pcmBytes) {
         MRC_HIP(h, hipMemcpyAsync(C.pcmL.p, pcm_left, pcmBytes, hipMemcpyHostToDevice, h->stream));
-        MRC_HIP(h, hipMemcpyAsync(C.pcmR.p, pcm_right, pcmBytes, hipMemcpyHostToDevice, h->stream));
+        if (pcm_right) MRC_HIP(h, hipMemcpyAsync(C.pcmR.p, pcm_right, pcmBytes, hipMemcpyHostToDevice, h->stream));
     }
     // every slab packs into the handle's device buffer (sized for the slab's worst case) and its bytes are copied behind the
     // previous slab's in the caller's buffer, which only has to hold what the streams really pack to
     hipStream_t st = h->stream;
     mrc_handle* hh = h;
-    int rc = chained_slabs(h, n_streams, C.pcmL.p, C.pcmR.p, sample_format, stream_stride, block_start, block_offset, block_a,
+    int rc = chained_slabs(h, n_streams, C.pcmL.p, pcm_right ? C.pcmR.p : nullptr, sample_format, stream_stride, block_start, block_offset, block_a,
                            block_b, reservoir_in, use_huffman, with_flush, num_samples, out_cap, stream_byte_offset,
                            item_byte_offset, reservoir_out, reservoir_trace, total_bytes, h->stream, nullptr,
                            [out, st, hh](uint8_t* buf, int64_t n, int64_t at) {

@@ -209,7 +209,7 @@ hipError_t launch_chain_prep(const DevShape& S, int joint, int64_t nBlocks, cons
 hipError_t launch_chain_phase_b(int64_t nStreams, const ChainGroupDev* groups, const int* items, const long long* itemStart,
                                 int* reservoir, int* resTrace, int useHuffman, int threads /* 0: chosen by stream count */,
                                 hipStream_t st);
-hipError_t launch_chain_flush_gather(int64_t nStreams, int L, const void* pcmL, const void* pcmR, int fmt, int64_t stride,
+hipError_t launch_chain_flush_gather(int64_t nStreams, int L, const void* pcmL, const void* pcmR /* null: mono */, int fmt, int64_t stride,
                                      const long long* tailOffset, void* out, hipStream_t st);
 hipError_t launch_chain_headers(int64_t nStreams, int hdrLen, const unsigned char* hdr, const long long* firstChunk,
                                 const long long* pos, unsigned char* out, long long outCap, long long* streamPos,

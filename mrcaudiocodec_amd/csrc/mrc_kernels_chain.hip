@@ -785,13 +785,15 @@ __global__ __launch_bounds__(NT) void chain_phase_b_kernel(
     if (tid == 0) reservoir[strmId] = resReg;
 }
 
-// Close() (pacfileThem.py:973-984): per stream and channel the last coded hop followed by a hop of zeros
+// Close() (pacfileThem.py:973-984): per stream and channel the last coded hop followed by a hop of zeros (nch = 2: stereo
+// streams, pcmR read; nch = 1: mono streams, pcmR not read)
 template <class T>
-__global__ void chain_flush_gather_kernel(int64_t nStreams, int L, const T* __restrict__ pcmL, const T* __restrict__ pcmR,
-                                          int64_t stride, const long long* __restrict__ tailOffset, T* __restrict__ out) {
-    const int64_t u = blockIdx.x;                         // stream * 2 + channel
-    const int64_t s = u >> 1;
-    const T* src = ((u & 1) ? pcmR : pcmL) + s * stride + tailOffset[s];
+__global__ void chain_flush_gather_kernel(int64_t nStreams, int nch, int L, const T* __restrict__ pcmL,
+                                          const T* __restrict__ pcmR, int64_t stride, const long long* __restrict__ tailOffset,
+                                          T* __restrict__ out) {
+    const int64_t u = blockIdx.x;                         // stream * nch + channel
+    const int64_t s = nch == 2 ? u >> 1 : u;
+    const T* src = ((nch == 2 && (u & 1)) ? pcmR : pcmL) + s * stride + tailOffset[s];
     T* dst = out + u * 2 * (int64_t)L;
     for (int i = threadIdx.x; i < L; i += blockDim.x) { dst[i] = src[i]; dst[L + i] = (T)0; }
 }
@@ -853,11 +855,13 @@ hipError_t launch_chain_phase_b(int64_t nStreams, const ChainGroupDev* groups, c
 hipError_t launch_chain_flush_gather(int64_t nStreams, int L, const void* pcmL, const void* pcmR, int fmt, int64_t stride,
                                      const long long* tailOffset, void* out, hipStream_t st) {
     if (nStreams <= 0) return hipSuccess;
+    const int nch = pcmR ? 2 : 1;                         // (pcmR == nullptr: mono streams)
+    const dim3 grid((unsigned)(nch * nStreams));
     if (fmt == kSampleI16)
-        hipLaunchKernelGGL(chain_flush_gather_kernel<short>, dim3((unsigned)(2 * nStreams)), dim3(256), 0, st, nStreams, L,
+        hipLaunchKernelGGL(chain_flush_gather_kernel<short>, grid, dim3(256), 0, st, nStreams, nch, L,
                            (const short*)pcmL, (const short*)pcmR, stride, tailOffset, (short*)out);
     else
-        hipLaunchKernelGGL(chain_flush_gather_kernel<double>, dim3((unsigned)(2 * nStreams)), dim3(256), 0, st, nStreams, L,
+        hipLaunchKernelGGL(chain_flush_gather_kernel<double>, grid, dim3(256), 0, st, nStreams, nch, L,
                            (const double*)pcmL, (const double*)pcmR, stride, tailOffset, (double*)out);
     return hipGetLastError();
 }

@@ -7,6 +7,7 @@ with the dense arrays the GPU path returns.  Mirrors the encode half of the refe
     PACFile.WriteDataBlock       pacfileThem.py:622-790   -> pack_blocks()
     PACFile.JointWriteDataBlock  pacfileThem.py:793-972   -> pack_joint_blocks()
     the CLI's encode loop + Close pacfileThem.py:1159-1214, 973-984 -> encode_stereo_stream()
+    ... with WriteDataBlock in place of JointWriteDataBlock (1218)  -> encode_mono_stream()
 
 Block shapes are an input here; mrcaudiocodec_amd/transient.py derives them from the audio like the reference's
 transient detector, and mrcaudiocodec_amd/cli.py strings WAV ingest, detector and this writer together.
@@ -183,6 +184,63 @@ def encode_stereo_stream_per_block(handle, stream, shapes, use_huffman=True, num
         blk = np.concatenate([stream[ch, off + shapes[-1][1]:off + shapes[-1][1] + b], np.zeros(L)])[None, :]
         r = handle.encode_mono(blk, a, L, [reservoir])
         data, _, _, saved = pack_blocks(cfg, a, L, r["overall_scale"][:, None], r["scale_factor"][:, None, :],
+                                        r["bit_alloc"][:, None, :], r["mantissa"][:, None, :], use_huffman)
+        reservoir = int(r["reservoir_out"][0]) + int(saved.sum())
+        out.append(data.tobytes())
+    return b"".join(out)
+
+
+def encode_mono_stream(handle, stream, shapes, use_huffman=True, num_samples=None):
+    """encode_stereo_stream for ONE mono stream [samples] (or [1][samples]): the reference's encode loop with WriteDataBlock
+    in place of JointWriteDataBlock -- header with nChannels = 1, one non-joint chunk per shape with the bit reservoir
+    carried from block to block (codecThem.py:205-231), then Close()'s one flush chunk.  One library call.  Returns the
+    .pac bytes."""
+    stream = np.asarray(stream)
+    return encode_mono_streams(handle, stream.reshape(1, -1), [shapes], use_huffman,
+                               None if num_samples is None else [num_samples])[0]
+
+
+def encode_mono_streams(handle, streams, shapes, use_huffman=True, num_samples=None):
+    """encode_mono_stream for MANY mono streams at once: streams [nStreams][samples] (or [nStreams][1][samples]), shapes[s]
+    and num_samples[s] as in encode_stereo_streams.  Returns a list of .pac byte strings."""
+    L = handle.cfg.n_mdct_lines
+    streams = np.asarray(streams)
+    if streams.ndim == 3 and streams.shape[1] == 1:
+        streams = streams[:, 0]
+    if streams.dtype != np.int16:
+        streams = streams.astype(np.float64, copy=False)
+    nS = streams.shape[0]
+    if streams.ndim != 2 or len(shapes) != nS:
+        raise ValueError("streams [nStreams][samples] and one shape list per stream expected")
+    for sh in shapes:
+        if not len(sh) or sh[-1][2] != L:
+            raise ValueError("every stream must end with a long block (the reference's Close() assumes it)")
+    if num_samples is None:
+        num_samples = [sum(int(b) for (_, _, b) in sh) for sh in shapes]
+    r = handle.encode_chained_pac(streams, None, shapes, use_huffman=use_huffman, with_flush=True, num_samples=num_samples)
+    data, offs = r["bytes"], r["stream_offset"]
+    return [data[offs[s]:offs[s + 1]].tobytes() for s in range(nS)]
+
+
+def encode_mono_stream_per_block(handle, stream, shapes, use_huffman=True, num_samples=None):
+    """The block-at-a-time form of encode_mono_stream: one mrc_encode_mono per block, the reservoir carried on the host
+    (reservoir_out + Huffman bits_saved), C++ packer, then Close()'s block.  The cross-check of the chained mono path
+    (same bytes) and the 'before' of its speed-up."""
+    c = handle.cfg
+    cfg = make_config(c.sample_rate, c.n_mdct_lines, c.n_short, c.n_scale_bits, c.n_mant_size_bits,
+                      c.target_bits_per_sample, c.blksw_bits_a, c.blksw_bits_b)
+    L = c.n_mdct_lines
+    if shapes[-1][2] != L:
+        raise ValueError("the stream must end with a long block (the reference's Close() assumes it)")
+    stream = np.asarray(stream, dtype=np.float64).reshape(-1)
+    out = [header(cfg, 1, sum(b for (_, _, b) in shapes) if num_samples is None else num_samples)]
+    reservoir = 0
+    blocks = [(off, a, b, stream[off:off + a + b]) for (off, a, b) in shapes]
+    off, a, b = shapes[-1]
+    blocks.append((None, L, L, np.concatenate([stream[off + a:off + a + b], np.zeros(L)])))   # Close(): last hop + zeros
+    for (_, a, b, x) in blocks:
+        r = handle.encode_mono(x[None, :], a, b, [reservoir])
+        data, _, _, saved = pack_blocks(cfg, a, b, r["overall_scale"][:, None], r["scale_factor"][:, None, :],
                                         r["bit_alloc"][:, None, :], r["mantissa"][:, None, :], use_huffman)
         reservoir = int(r["reservoir_out"][0]) + int(saved.sum())
         out.append(data.tobytes())

@@ -26,13 +26,16 @@ def encode_streams_sharded(handle, streams, shapes, world, rank, use_huffman=Tru
     """This rank's share of pacfile.encode_stereo_streams: streams [nStreams][2][samples] and one shape list per stream as
     EVERY rank sees them (or can regenerate them); the rank encodes streams [first, first + n) on its own GPU with one
     chained call and returns (first, list of .pac byte strings).  Concatenated over the ranks in rank order the lists are
-    what one process returns for all streams."""
+    what one process returns for all streams.  streams [nStreams][1][samples]: mono files (pacfile.encode_mono_streams)."""
     from . import pacfile
     first, n = shard_streams(len(shapes), world, rank)
     if n == 0:
         return first, []
     ns = None if num_samples is None else list(num_samples[first:first + n])
-    return first, pacfile.encode_stereo_streams(handle, streams[first:first + n], shapes[first:first + n], use_huffman, ns)
+    mine = streams[first:first + n]
+    if getattr(mine, "ndim", 0) == 3 and mine.shape[1] == 1:
+        return first, pacfile.encode_mono_streams(handle, mine, shapes[first:first + n], use_huffman, ns)
+    return first, pacfile.encode_stereo_streams(handle, mine, shapes[first:first + n], use_huffman, ns)
 
 
 def shard_samples(first_frame, n_local, hop):
