@@ -75,7 +75,9 @@ int  mrc_device_count(void);                              /* number of HIP devic
 void mrc_default_config(mrc_config* cfg);                 /* pacfileThem.py:1105-1121 defaults, 48 kHz, device 0 */
 int  mrc_create(const mrc_config* cfg, mrc_handle** out);
 void mrc_destroy(mrc_handle* h);
-const char* mrc_last_error(const mrc_handle* h);          /* h may be NULL: error of the last failed mrc_create */
+const char* mrc_last_error(const mrc_handle* h);          /* h may be NULL: error of the last failed call without a
+                                                            * handle (mrc_create, mrc_band_table, mrc_pac_header,
+                                                            * mrc_pac_read_header) */
 
 /* Shape queries (band tables of psychoac.py:86-131 / pacfileThem.py:637-645). */
 int  mrc_shape_bands(mrc_handle* h, int a, int b, int32_t* n_bands, int32_t* n_lines /*[MRC_MAX_BANDS]*/);
@@ -249,7 +251,9 @@ int mrc_dev_encode_ex(mrc_handle* h, int a, int b, int64_t n_frames, const void*
  * the dense outputs of mrc_encode_mono / mrc_encode_joint.  Table ids: sorted names (percussive 0,
  * silence 1, speech 2, tonal 3), 15 = raw mantissas (codecThem.py:149). */
 
-/* psychoac.py:86-105 + pacfileThem.py:637-645: lines per scale-factor band of block shape (a,b). */
+/* psychoac.py:86-105 + pacfileThem.py:637-645: lines per scale-factor band of block shape (a,b).  MRC_ERR_INVALID where the
+ * reference's loop raises IndexError: the centre of the shape's last line below 15500 Hz (sample rates below ~31 kHz).
+ * mrc_create, mrc_pac_header (all four block shapes of cfg) and mrc_pac_read_header (the long shape) refuse such rates too. */
 int mrc_band_table(const mrc_config* cfg, int a, int b, int32_t* n_bands, int32_t* n_lines /*[MRC_MAX_BANDS]*/);
 /* Upper bound of the bytes one block can pack to (all its channel chunks, length prefixes included). */
 int64_t mrc_pack_bound(const mrc_config* cfg, int a, int b, int n_channels, int joint);

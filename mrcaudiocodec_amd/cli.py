@@ -20,7 +20,7 @@ from struct import pack, unpack
 
 import numpy as np
 
-from . import Handle, pacfile, transient
+from . import Handle, MrcError, pacfile, transient
 
 
 def read_wav_pcm(path, hop=1024):
@@ -77,6 +77,11 @@ def encode_wav(in_path, out_path=None, use_huffman=True, device_id=0, handle=Non
     if n_ch not in (1, 2):
         raise ValueError("%d-channel input: mono and stereo WAV files only (the .pac readers refuse more than two channels "
                          "and the reference's Close() flushes at most two)" % n_ch)
+    shape = {} if handle is None else dict(n_mdct_lines=handle.cfg.n_mdct_lines, n_short=handle.cfg.n_short)
+    try:                                 # (the rate decides the band tables: below ~31 kHz the reference's raise IndexError)
+        pacfile.header(pacfile.make_config(sample_rate=rate, **shape), n_ch, num_samples)
+    except MrcError as e:
+        raise ValueError("%d Hz input: outside the sample rates the reference can encode (%s)" % (rate, e))
     h = handle if handle is not None else Handle(sample_rate=rate, device_id=device_id)
     was_exact = h.get_option(1)
     was_sens = h.get_option(5)

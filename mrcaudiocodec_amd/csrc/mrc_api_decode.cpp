@@ -170,8 +170,8 @@ int mrc_decode_pac_pcm16(mrc_handle* h, int64_t n_files, const uint8_t* buf, con
         uint32_t ns = 0;
         int64_t doff = 0;
         if (mrc_pac_read_header(fb, flen, &fc, &nch, &ns, &doff) != MRC_OK) {
-            std::snprintf(msg, sizeof msg, "mrc_decode_pac_pcm16: file %lld: not a .pac header", (long long)f);
-            return fail(h, MRC_ERR_INVALID, msg);
+            std::snprintf(msg, sizeof msg, "mrc_decode_pac_pcm16: file %lld: not a .pac header (", (long long)f);
+            return fail(h, MRC_ERR_INVALID, msg + create_error() + ")");
         }
         const struct { const char* name; int file, handle; } par[4] = {
             {"sample_rate", fc.sample_rate, hc.sample_rate}, {"n_mdct_lines", fc.n_mdct_lines, hc.n_mdct_lines},

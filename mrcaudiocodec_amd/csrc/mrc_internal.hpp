@@ -67,6 +67,9 @@ struct HostShape {
 
 // mrc_tables.cpp
 bool band_table(const mrc_config& cfg, int a, int b, std::vector<int>* count);   // host only
+std::string band_table_error(const mrc_config& cfg, int a, int b);                 // why band_table refused
+// error text of the last failed call that has no handle (mrc_create, mrc_band_table, mrc_pac_header, mrc_pac_read_header)
+std::string& create_error();
 // The summation tree np.sum walks over each band's contiguous run of lines (pairwise summation: runs of more than 128
 // elements are halved, the first half rounded down to a multiple of 8).  -> plan laid out as DevShape::msPlan.
 void ms_plan(const std::vector<int>& bandLo, const std::vector<int>& bandN, std::vector<int>* plan, int* nLeaves,

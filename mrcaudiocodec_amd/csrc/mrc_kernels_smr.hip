@@ -353,6 +353,12 @@ __device__ __forceinline__ double recip_nr(double x) {
     r = fma(fma(-x, r, 1.0), r, r);
     return fma(fma(-x, r, 1.0), r, r);
 }
+// The ratio form of the band maximum (a2 / t) and a threshold of +inf: from ~80 kHz on, Intensity(Thresh(f)) of the top lines
+// overflows (psychoac.py:14-25), and recip_nr(+inf) is NaN (rcp gives 0, then -inf * 0).  As an atomicMax key a NaN beats every
+// ratio of the band and then drops out of the band's fmax, leaving the band at -1e300.  The line's true ratio is 0 (an excess of
+// -inf, never the band's maximum: a band's lower lines have finite thresholds), and fmax(q, 0) gives exactly that -- q >= 0
+// otherwise, and one v_max per line is all it costs.
+__device__ __forceinline__ double line_ratio(double a2, double t) { return fmax(a2 * recip_nr(t), 0.0); }
 // atan(x) for x >= 0 (psychoac.py:27-29's two calls per masker), <= 2 ulp: x <= 1: x Q(x^2), Q of degree 21 from a
 // Chebyshev fit in 60-digit arithmetic (tools/make_atan_poly.py); x > 1: pi/2 - atan(1/x).  ~40 instructions against the
 // ~90 of the library's.
@@ -1423,7 +1429,8 @@ __device__ __forceinline__ void smr_body(DevShape S, int nsigArg, const SampleT*
         // log10 is monotone: the band maximum of the RATIO is taken and converted once per band at the end
         // instead of two log10 per line (the difference to the reference's order of roundings is ~1e-14 dB, five
         // orders below what the FFT in front of it already differs by).  Lines on the floor, and every line when
-        // the caller wants the thresholds themselves, take the reference's formula.
+        // the caller wants the thresholds themselves, take the reference's formula.  (Lines under an infinite threshold:
+        // line_ratio.)
         // (a2 of a line: the intensity of its own MDCT line, psychoac.py:212)
         // = 2 xs^2 / (1/2) with xs = x 2^scale (codecThem.py:323; psychoac.py:212): the factors of two commute with the one
         // rounding of the square, so the square of 2 xs is the same double
@@ -1442,7 +1449,7 @@ __device__ __forceinline__ void smr_body(DevShape S, int nsigArg, const SampleT*
                 ex = excess_plain(t, a2, scale, logTab, &thr);
                 if (thresh && k < M) thresh[(int64_t)unit * M + k] = thr;
             } else {
-                q = a2 * recip_nr(t);
+                q = line_ratio(a2, t);
             }
             const int bnd = cur.bnd;                     // lanes past the end repeat the last line: maxima unchanged
             if (__all(bnd == __builtin_amdgcn_readfirstlane(bnd))) {
@@ -1789,7 +1796,7 @@ __global__ __launch_bounds__(kWave * kShortWaves) __attribute__((amdgpu_waves_pe
                 double thr;
                 atomicMax(&bandKey[bnd], order_key(excess_plain(t, a2, scale, logTab, &thr)));
             } else {
-                atomicMax(&ratioKey[bnd], (unsigned long long)__double_as_longlong(a2 * recip_nr(t)));
+                atomicMax(&ratioKey[bnd], (unsigned long long)__double_as_longlong(line_ratio(a2, t)));
             }
             atomicMax(&peakKey[bnd], (unsigned long long)__double_as_longlong(fabs(x)));
         }

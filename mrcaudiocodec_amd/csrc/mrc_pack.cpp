@@ -236,6 +236,12 @@ template <class F> void parallel_for(int64_t n, F body) {
 
 inline void put_u32le(uint8_t* p, uint32_t v) { p[0] = v & 255; p[1] = (v >> 8) & 255; p[2] = (v >> 16) & 255; p[3] = v >> 24; }
 
+// a refusal of a call without a handle, with its reason for mrc_last_error(NULL)
+int refuse(const std::string& why) {
+    mrc::create_error() = why;
+    return MRC_ERR_INVALID;
+}
+
 bool shape_ok(const mrc_config* cfg, int a, int b) {
     return cfg && a > 0 && b > 0 && (a + b) % 2 == 0 && cfg->n_mdct_lines > 0 && cfg->n_scale_bits >= 1 &&
            cfg->n_scale_bits <= 4 && cfg->n_mant_size_bits >= 1 && cfg->n_mant_size_bits <= 8;
@@ -341,9 +347,9 @@ void unpack_tables(UnpackTables* out) {
 extern "C" {
 
 int mrc_band_table(const mrc_config* cfg, int a, int b, int32_t* n_bands, int32_t* n_lines) {
-    if (!shape_ok(cfg, a, b) || !n_bands) return MRC_ERR_INVALID;
+    if (!shape_ok(cfg, a, b) || !n_bands) return refuse("mrc_band_table: bad argument or block shape");
     std::vector<int> cnt;
-    if (!mrc::band_table(*cfg, a, b, &cnt)) return MRC_ERR_INVALID;
+    if (!mrc::band_table(*cfg, a, b, &cnt)) return refuse("mrc_band_table: " + mrc::band_table_error(*cfg, a, b));
     *n_bands = (int32_t)cnt.size();
     if (n_lines) for (size_t i = 0; i < cnt.size(); ++i) n_lines[i] = cnt[i];
     return MRC_OK;
@@ -363,11 +369,16 @@ int64_t mrc_pack_bound(const mrc_config* cfg, int a, int b, int n_channels, int 
 
 int mrc_pac_header(const mrc_config* cfg, int n_channels, uint32_t num_samples, uint8_t* out, int64_t out_cap,
                    int64_t* out_len) {
-    if (!cfg || !out || !out_len || n_channels < 1) return MRC_ERR_INVALID;
+    if (!cfg || !out || !out_len || n_channels < 1) return refuse("mrc_pac_header: bad argument");
     std::vector<int> cnt;
-    if (!mrc::band_table(*cfg, cfg->n_mdct_lines, cfg->n_mdct_lines, &cnt)) return MRC_ERR_INVALID;
+    if (!shape_ok(cfg, cfg->n_mdct_lines, cfg->n_mdct_lines) || cfg->n_short <= 0)
+        return refuse("mrc_pac_header: bad configuration");
+    for (int s = 3; s >= 0; --s) {                     // every shape the file's blocks can have; (L,L) last: its table is written
+        const int a = (s & 1) ? cfg->n_short : cfg->n_mdct_lines, b = (s & 2) ? cfg->n_short : cfg->n_mdct_lines;
+        if (!mrc::band_table(*cfg, a, b, &cnt)) return refuse("mrc_pac_header: " + mrc::band_table_error(*cfg, a, b));
+    }
     const int64_t need = 4 + 4 + 2 + 4 + 4 + 2 + 2 + 4 + 2 * (int64_t)cnt.size();
-    if (out_cap < need) return MRC_ERR_INVALID;
+    if (out_cap < need) return refuse("mrc_pac_header: output buffer too small");
     // pacfileThem.py:595-597: padded only when numSamples ALREADY is a multiple of nMDCTLines (inverted test)
     if (num_samples % (uint32_t)cfg->n_mdct_lines == 0) num_samples += (uint32_t)cfg->n_mdct_lines;
     uint8_t* p = out;
@@ -526,8 +537,9 @@ int mrc_pack_blocks_ex(const mrc_config* cfg, int64_t n_blocks, int n_channels, 
 // ---- decode side ---------------------------------------------------------------------------------------------
 int mrc_pac_read_header(const uint8_t* buf, int64_t len, mrc_config* cfg, int32_t* n_channels, uint32_t* num_samples,
                         int64_t* data_offset) {
-    if (!buf || !cfg || !n_channels || !num_samples || !data_offset || len < 26) return MRC_ERR_INVALID;
-    if (std::memcmp(buf, "PAC ", 4) != 0) return MRC_ERR_INVALID;
+    if (!buf || !cfg || !n_channels || !num_samples || !data_offset || len < 26)
+        return refuse("mrc_pac_read_header: bad argument or fewer than 26 bytes");
+    if (std::memcmp(buf, "PAC ", 4) != 0) return refuse("mrc_pac_read_header: no \"PAC \" tag");
     cfg->sample_rate = (int32_t)get_u32le(buf + 4);
     *n_channels = (int32_t)get_u16le(buf + 8);
     *num_samples = get_u32le(buf + 10);
@@ -535,13 +547,17 @@ int mrc_pac_read_header(const uint8_t* buf, int64_t len, mrc_config* cfg, int32_
     cfg->n_scale_bits = (int32_t)get_u16le(buf + 18);
     cfg->n_mant_size_bits = (int32_t)get_u16le(buf + 20);
     const uint32_t nBands = get_u32le(buf + 22);
-    if (nBands > 4096 || 26 + 2 * (int64_t)nBands > len) return MRC_ERR_INVALID;
+    if (nBands > 4096 || 26 + 2 * (int64_t)nBands > len) return refuse("mrc_pac_read_header: band count out of range");
     // the header is untrusted input and sizes every later allocation: refuse what no encoder writes
     if (cfg->sample_rate <= 0 || *n_channels < 1 || *n_channels > 2 || cfg->n_mdct_lines < 16 ||
         cfg->n_mdct_lines > 8192 || (cfg->n_mdct_lines & (cfg->n_mdct_lines - 1)) != 0 || cfg->n_scale_bits < 1 ||
         cfg->n_scale_bits > 4 || cfg->n_mant_size_bits < 1 || cfg->n_mant_size_bits > 8)
-        return MRC_ERR_INVALID;
-    *data_offset = 26 + 2 * (int64_t)nBands;           // the band table itself is implied by rate and block length
+        return refuse("mrc_pac_read_header: header field out of range");
+    // the band table itself is implied by rate and block length: a rate the reference could not have encoded at is refused
+    std::vector<int> cnt;
+    if (!mrc::band_table(*cfg, cfg->n_mdct_lines, cfg->n_mdct_lines, &cnt))
+        return refuse("mrc_pac_read_header: " + mrc::band_table_error(*cfg, cfg->n_mdct_lines, cfg->n_mdct_lines));
+    *data_offset = 26 + 2 * (int64_t)nBands;
     return MRC_OK;
 }
 

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 
 namespace mrc {
@@ -118,6 +119,10 @@ int scale_factor_host(double v, int nScaleBits, int nMantBits) {
 // psychoac.py:86-105 with the limits chosen at pacfileThem.py:637-645: 25 critical bands for long+long
 // blocks, the 9-band table for every other shape.  Band i takes the not-yet-assigned lines whose centre
 // (n+1/2) fs/(2 halfN) lies below limit i; the last band takes the rest.
+// The reference's loop reads centre[j] BEFORE it tests j < len(centre): once every line has gone to a band below the last
+// one, the next test indexes past the end of the line array and raises IndexError.  That happens exactly when the centre of
+// the last line lies below the second-to-last limit (15500 Hz in both tables), below about 31 kHz: such a rate and shape
+// have no reference output, and the table is refused (false) rather than given an empty last band.
 bool band_table(const mrc_config& cfg, int a, int b, std::vector<int>* count) {
     const int N = a + b, halfN = N / 2;
     const bool isLong = (N == 2 * cfg.n_mdct_lines);
@@ -126,9 +131,24 @@ bool band_table(const mrc_config& cfg, int a, int b, std::vector<int>* count) {
     count->assign(nb, 0);
     int j = 0;
     for (int i = 0; i < nb - 1; ++i)
-        while (j < halfN && (j + 0.5) * (((double)cfg.sample_rate / halfN) / 2.) < lim[i]) { ++(*count)[i]; ++j; }
+        for (;;) {
+            if (j >= halfN) return false;                      // centre[j]: IndexError
+            if (!((j + 0.5) * (((double)cfg.sample_rate / halfN) / 2.) < lim[i])) break;
+            ++(*count)[i];
+            ++j;
+        }
     (*count)[nb - 1] = halfN - j;
-    return (*count)[nb - 1] >= 0;
+    return true;
+}
+
+std::string band_table_error(const mrc_config& cfg, int a, int b) {
+    const int halfN = (a + b) / 2;
+    char msg[256];
+    std::snprintf(msg, sizeof msg,
+                  "sample rate %d Hz is outside the reference's domain for block shape (%d,%d): the centre of its last "
+                  "MDCT line, %.2f Hz, lies below the 15500 Hz band limit (psychoac.py:86-105 raises IndexError)",
+                  cfg.sample_rate, a, b, (halfN - 0.5) * (((double)cfg.sample_rate / (halfN > 0 ? halfN : 1)) / 2.));
+    return msg;
 }
 
 void ms_plan(const std::vector<int>& bandLo, const std::vector<int>& bandN, std::vector<int>* plan, int* nLeaves,
@@ -190,7 +210,7 @@ bool build_shape(const mrc_config& cfg, int a, int b, HostShape* out, std::strin
 
     // band table: psychoac.py:86-105 with the limits chosen at pacfileThem.py:637-645
     std::vector<int> count;
-    if (!band_table(cfg, a, b, &count)) { *err = "band table overflow"; return false; }
+    if (!band_table(cfg, a, b, &count)) { *err = band_table_error(cfg, a, b); return false; }
     const int nb = (int)count.size();
     S.nBands = nb;
     out->bandN = count;

@@ -45,9 +45,11 @@ def get_threads():
     return int(lib.mrc_pack_get_threads())
 
 
-def _check(rc, what):
+def _check(rc, what, reason=False):
+    """reason: the call states why it refused (mrc_last_error(NULL))"""
     if rc != 0:
-        raise MrcError("%s failed (%d)" % (what, rc))
+        msg = lib.mrc_last_error(None) if reason else None
+        raise MrcError("%s failed (%d)%s" % (what, rc, ": " + msg.decode() if msg else ""))
 
 
 def _i32(a):
@@ -57,7 +59,7 @@ def _i32(a):
 def band_table(cfg, a, b):
     n = C.c_int32()
     buf = np.zeros(_lib.MRC_MAX_BANDS, dtype=np.int32)
-    _check(lib.mrc_band_table(C.byref(cfg), int(a), int(b), C.byref(n), buf.ctypes.data_as(_i32p)), "mrc_band_table")
+    _check(lib.mrc_band_table(C.byref(cfg), int(a), int(b), C.byref(n), buf.ctypes.data_as(_i32p)), "mrc_band_table", reason=True)
     return buf[:n.value].copy()
 
 
@@ -65,7 +67,7 @@ def header(cfg, n_channels, num_samples):
     out = np.zeros(256, dtype=np.uint8)
     n = C.c_int64()
     _check(lib.mrc_pac_header(C.byref(cfg), int(n_channels), int(num_samples), out.ctypes.data_as(_u8p), out.size,
-                              C.byref(n)), "mrc_pac_header")
+                              C.byref(n)), "mrc_pac_header", reason=True)
     return out[:n.value].tobytes()
 
 
@@ -254,7 +256,7 @@ def read_header(buf):
     cfg = make_config()
     nch, ns, off = C.c_int32(), C.c_uint32(), C.c_int64()
     _check(lib.mrc_pac_read_header(raw.ctypes.data_as(_u8p), raw.size, C.byref(cfg), C.byref(nch), C.byref(ns),
-                                   C.byref(off)), "mrc_pac_read_header")
+                                   C.byref(off)), "mrc_pac_read_header", reason=True)
     return cfg, nch.value, ns.value, off.value
 
 
