@@ -3,12 +3,17 @@
 bench.py -- encode throughput of the MI355X hot path (BASELINE.json metric: encode Msamples/s,
 48 kHz, 2048-point MDCT blocks).
 
-    python bench.py --gpus N --steps K --warmup W            (N = 1)
+    python bench.py --gpus N --steps K --warmup W [--full]   (N = 1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
-        bench.py --gpus N --steps K --warmup W               (N > 1, one rank per GPU)
+        bench.py --gpus N --steps K --warmup W [--full]      (N > 1, one rank per GPU)
 
 A step = one pass of the whole hot path (window+MDCT -> masked threshold/SMR -> bit allocation ->
 scale factors + mantissas) over one batch of synthetic PCM frames that is already resident in HBM.
+
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes --dump-outputs and
+prints the line (metric, value, unit, ms_per_step, the workload's config and whole_path, which the timed steps give).
+`--full` adds everything else below: per-kernel and roofline figures, the sensitivity certificate, the other layouts,
+sizes and configurations, and the CPU baseline.
 
 `value` (every N): BASELINE.json configs[1] -- mono 48 kHz Gaussian white noise (sigma 0.1 FS, 16-bit PCM), all-long
 blocks (a = b = 1024), independent-frames mode (reservoir_in = 0), F frames per GPU per step.  The content is ONE
@@ -18,7 +23,7 @@ on the data path ("weak" scaling: per-GPU work fixed).  The resident layout is t
 converted on load as pcmfile.py:91-100 does, 16-bit mantissa codes out (`f64_layout` reports the float64-in /
 int32-out layout round 1 measured).  Rank 0 prints ONE JSON line.
 
-Extra objects on the line:
+Extra objects on the line with --full:
   roofline      dominant kernel (largest share of device time): algorithmic bytes per launch / its average duration
                 (hipEvents on the launch stream) against 8 TB/s HBM; fp64 figures from the committed SQ counters.
   kernels       the same for every kernel of the path.
@@ -330,13 +335,17 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--frames", type=int, default=1 << 20, help="mono frames per GPU per step of the headline (SURVEY 8(d) C2: 2^20)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check besides the headline: per-kernel and roofline figures, the "
+                         "other layouts and configurations, the CPU baseline (--extra-frames .. --skip-extras apply to it)")
     ap.add_argument("--extra-frames", type=int, default=1 << 17, help="frames per step of the other single-GPU configurations")
     ap.add_argument("--h2h-frames", type=int, default=1 << 19, help="frames of the host-to-host stream")
     ap.add_argument("--c4-frames", type=int, default=10 ** 7 // 8,
                     help="N > 1: stereo frames per GPU per step of configs[4] (10^7 / 8: 10^7 frames at N = 8)")
     ap.add_argument("--single-hops", type=int, default=1 << 16, help="hops of the single-stream configuration")
     ap.add_argument("--cpu-frames", type=int, default=256, help="frames of the CPU baseline sample (0 = skip)")
-    ap.add_argument("--skip-extras", action="store_true", help="only the headline measurement (profiling runs)")
+    ap.add_argument("--skip-extras", action="store_true",
+                    help="only the headline with its per-kernel and roofline figures (profiling runs)")
     ap.add_argument("--only", choices=["stereo", "switch"], default=None,
                     help="profiling runs: ONLY the timed loop of configs[2] / configs[3] (prints a short JSON line)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -346,12 +355,15 @@ def main():
         ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.dump_outputs and args.only:
         ap.error("--dump-outputs writes the headline's outputs; --only does not run the headline")
+    if args.skip_extras and not args.full:
+        ap.error("--skip-extras trims a --full run; a run without --full measures the headline alone already")
+    extras = args.full and not args.skip_extras
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     cpu_line = None
-    if world == 1 and args.cpu_frames > 0 and not args.skip_extras:
+    if world == 1 and args.cpu_frames > 0 and extras:
         # first of all, before this process touches the GPU: the baseline starts one worker process per core
         for v in ("OPENBLAS_NUM_THREADS", "OMP_NUM_THREADS", "MKL_NUM_THREADS"):
             os.environ.setdefault(v, "1")
@@ -445,15 +457,14 @@ def main():
     if args.dump_outputs and rank == 0:
         # before anything else reuses the output buffers of the last timed step
         dump_outputs(np, torch, last_out[0], first, args.dump_outputs)
-    kms = kernel_ms(lambda: enc.encode_long(pcm, None, F, mantissa16=True))
-    coded = coded_line_fraction(np, enc.encode_long(pcm, None, F, mantissa16=True), enc.h.bands(HOP, HOP))
+    if args.full:
+        # per-kernel device times and the share of coded lines: encodes of their own, after the timed steps
+        kms = kernel_ms(lambda: enc.encode_long(pcm, None, F, mantissa16=True))
+        coded = coded_line_fraction(np, enc.encode_long(pcm, None, F, mantissa16=True), enc.h.bands(HOP, HOP))
     line = None
     if rank == 0:
         total_samples = float(F) * HOP * world * args.steps
-        ab = algorithmic_bytes(False, True, True, coded_line_frac=coded)
-        traffic, traffic_src = measured_traffic("mono")
-        rows = kernel_report(list(zip(KERNEL_NAMES, kms)), ab, F, traffic)
-        smr_ms = float(kms[1])
+        path_bytes = algorithmic_bytes(False, True, True)["path"]
         line = {
             "metric": "encode Msamples/sec (48 kHz, 2048-pt MDCT)",
             "value": round(total_samples / elapsed / 1e6, 3),
@@ -469,20 +480,25 @@ def main():
                                  "pcmfile.py:91-100), uint16 mantissa plane + int32 side info out",
                        "parallelism": "one global stream of %d frames, frame-sharded x%d with a one-hop halo, no collective"
                                       % (world * F, world)},
-            "roofline": roofline_of(rows, {
+        }
+        if args.full:
+            ab = algorithmic_bytes(False, True, True, coded_line_frac=coded)
+            traffic, traffic_src = measured_traffic("mono")
+            rows = kernel_report(list(zip(KERNEL_NAMES, kms)), ab, F, traffic)
+            smr_ms = float(kms[1])
+            line["roofline"] = roofline_of(rows, {
                 "traffic_source": traffic_src,
                 "limiter": "fp64 VALU issue (masker spreading + FFT + SPL conversions), not HBM -- DESIGN.md section 4",
                 "valu": measured_valu(smr_ms, F),
                 "note": "dominant kernel by device time, priced against HBM as the contract asks; the HBM-bound kernel "
-                        "of the path is mdct_long_kernel, see kernels[0]"}),
-            "kernels": rows,
-            "coded_line_fraction": round(coded, 4),
-            "whole_path": {"algorithmic_bytes_per_frame": ab["path"],
-                           "achieved_GBs": round(ab["path"] * F * world * args.steps / elapsed / 1e9, 2)},
-        }
+                        "of the path is mdct_long_kernel, see kernels[0]"})
+            line["kernels"] = rows
+            line["coded_line_fraction"] = round(coded, 4)
+        line["whole_path"] = {"algorithmic_bytes_per_frame": path_bytes,
+                              "achieved_GBs": round(path_bytes * F * world * args.steps / elapsed / 1e9, 2)}
 
     Fx = min(args.extra_frames, F)                      # batch of the other configurations
-    if not args.skip_extras and world == 1:
+    if extras and world == 1:
         # ---- the sensitivity certificate of one headline step (outside the timed region): how many of its integer decisions
         # lay within a guard band of floating-point rounding (mrc_get_sensitivity) -- what "bit-exact" means at this size
         enc.h.set_option(5, 1)
@@ -500,7 +516,7 @@ def main():
                           "of 6 dB; M/S test 1e-12 (relative) from its 0.8 threshold; spectral bins 1e-11 (relative) from a "
                           "neighbour they must beat (include/mrc_hip.h, MRC_SENS_*)")
         line["sensitivity"] = cert
-    if not args.skip_extras:
+    if extras:
         # ---- the float64-in / int32-out layout round 1 measured (continuity)
         p64 = pcm[:(Fx + 1) * HOP].double()
         x64 = (torch.sign(p64) * 2.0 * torch.abs(p64) / 65535).contiguous()
@@ -515,7 +531,7 @@ def main():
                                   "kernels": kernel_report(list(zip(KERNEL_NAMES, k64)), ab64, Fx, {})}
         del x64
 
-    if not args.skip_extras:
+    if extras:
         # ---- SURVEY.md 8(d) metric as defined: page-locked host PCM -> codes in page-locked host memory.  At N > 1 every rank
         # runs it at the same time on its own buffers (between barriers) and the slowest rank counts.
         h2h = host_to_host_leg(np, torch, enc, device, args.h2h_frames, first, barrier,
@@ -523,7 +539,7 @@ def main():
         if rank == 0:
             line["host_to_host"] = h2h
 
-    if world == 1 and not args.skip_extras:
+    if world == 1 and extras:
         F = Fx                                             # (the configurations below run at the smaller batch)
         pcm = pcm[:(F + 1) * HOP].contiguous()
         # ---- configs[2]: stereo, joint M/S path, resident
@@ -649,7 +665,7 @@ def main():
         enc._out.clear()
         torch.cuda.empty_cache()
 
-    if world > 1 and not args.skip_extras:
+    if world > 1 and extras:
         # ---- configs[4]: the C3 stereo stream, frame-sharded, joint path, host pack reported separately.  10^7 / 8 frames per
         # GPU (~54 GB of HBM: 10^7 frames at N = 8; the same per-GPU share at every N: weak scaling)
         del pcm

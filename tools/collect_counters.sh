@@ -16,14 +16,14 @@ for cfg in $configs; do
         stereo) extra="--only stereo" ;;
         switch) extra="--only switch" ;;
     esac
-    cmd="python3 $repo/bench.py --frames $frames --steps 3 --warmup 1 --cpu-frames 0 $extra"
+    cmd="python3 $repo/bench.py --frames $frames --steps 3 --warmup 1 --cpu-frames 0 --full $extra"
     rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_${cfg}_stats -- $cmd > $out/${tag}_${cfg}_stats.log 2>&1
     rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/${tag}_${cfg}_fetch -- $cmd > $out/${tag}_${cfg}_fetch.log 2>&1
     rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $out/${tag}_${cfg}_write -- $cmd > $out/${tag}_${cfg}_write.log 2>&1
     echo "collected $tag $cfg"
 done
 if [ "$sq" = "1" ]; then
-    cmd="python3 $repo/bench.py --frames $frames --steps 3 --warmup 1 --cpu-frames 0 --skip-extras"
+    cmd="python3 $repo/bench.py --frames $frames --steps 3 --warmup 1 --cpu-frames 0 --full --skip-extras"
     i=0
     for set in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_WAVES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES SQ_WAVE_CYCLES" \
                "SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_INST_CYCLES_SALU" \

@@ -12,6 +12,6 @@ for v in default "$@"; do
     [ "$v" != default ] && lib=$repo/mrcaudiocodec_amd/libmrc_hip_$v.so
     export MRC_HIP_LIBRARY=$lib
     timeout -k 10 150 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_WAVE_CYCLES \
-        --kernel-trace --output-format csv -d $out/${tag}_${v}_pc -- python3 $repo/bench.py --frames $frames --steps 2 --warmup 1 --cpu-frames 0 --skip-extras > $out/${tag}_${v}_pc.log 2>&1 || echo "$v failed"
+        --kernel-trace --output-format csv -d $out/${tag}_${v}_pc -- python3 $repo/bench.py --frames $frames --steps 2 --warmup 1 --cpu-frames 0 --full --skip-extras > $out/${tag}_${v}_pc.log 2>&1 || echo "$v failed"
     echo "done $v"
 done

@@ -3,9 +3,10 @@ import json
 import sys
 
 d = json.loads([l for l in open(sys.argv[1]).read().splitlines() if l.startswith("{")][-1])
-print("value", d["value"], "ms/step", d["ms_per_step"], "n_gpus", d["n_gpus"], "roofline", d["roofline"]["kernel"], d["roofline"]["frac"],
+rf = d.get("roofline", {})                      # (a run without --full has no roofline or kernel figures)
+print("value", d["value"], "ms/step", d["ms_per_step"], "n_gpus", d["n_gpus"], "roofline", rf.get("kernel"), rf.get("frac"),
       "coded", d.get("coded_line_fraction"))
-for k in d["kernels"]:
+for k in d.get("kernels", []):
     print("   ", k["name"], k["ms"], "ms", k["frac_hbm"])
 if "roofline" in d and d["roofline"].get("valu"):
     print("   valu", d["roofline"]["valu"])
