@@ -126,12 +126,10 @@ void mrc_destroy(mrc_handle* h) {
     h->chain.release();
     h->dec.release();
     h->ws.release();
-    for (DevBuf* b : {&h->inL, &h->inR, &h->inAux, &h->inAux2, &h->inAux3,
-                      &h->outA, &h->outB, &h->outC, &h->outD, &h->outE, &h->outF, &h->outG})
-        b->release();
+    for (DevBuf& b : h->stage) b.release();
+    h->smallBatch.release();
+    h->sos.release();
     h->sens.release();
-    h->pinIn.release();
-    h->pinOut.release();
     for (auto& ev : h->ev) if (ev) (void)hipEventDestroy(ev);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -343,17 +341,12 @@ int mrc_dev_pack_blocks(mrc_handle* h, int a, int b, int64_t n_blocks, int n_cha
         if (total_bytes) { MRC_HIP(h, hipStreamSynchronize(st)); *total_bytes = 0; }
         return MRC_OK;
     }
-    static const PackTables tables = [] { PackTables t; pack_tables(&t); return t; }();
-    PackParams P;
-    P.nch = n_channels; P.joint = joint ? 1 : 0; P.useHuffman = use_huffman ? 1 : 0;
-    P.nScaleBits = cfg.n_scale_bits; P.nMantSizeBits = cfg.n_mant_size_bits;
-    P.blkBitsA = cfg.blksw_bits_a; P.blkBitsB = cfg.blksw_bits_b;
-    P.bitA = (unsigned)(1 - a / cfg.n_mdct_lines); P.bitB = (unsigned)(1 - b / cfg.n_mdct_lines);   // py2 int division
+    const PackParams P = pack_params(cfg, a, b, n_channels, joint, use_huffman);
     const size_t wsBytes = pack_workspace_bytes(nChunks);
     MRC_HIP(h, h->packWs.reserve(wsBytes + (huff_table ? 0 : (size_t)nChunks * sizeof(int32_t))));
     int32_t* tableOut = huff_table ? huff_table : reinterpret_cast<int32_t*>(static_cast<char*>(h->packWs.p) + wsBytes);
     const int bound = (int)(mrc_pack_bound(&cfg, a, b, 1, joint) - 4);
-    MRC_HIP(h, launch_pack(S, P, tables, n_blocks, overall_scale, ms_switch, scale_factor, bit_alloc, mantissa,
+    MRC_HIP(h, launch_pack(S, P, host_pack_tables(), n_blocks, overall_scale, ms_switch, scale_factor, bit_alloc, mantissa,
                            mantissa_format, huff_table_in, tableOut, bits_saved, out, (long long)out_cap,
                            reinterpret_cast<long long*>(block_offset), h->packWs.p, bound, all_bands_non_empty(*hs), st));
     h->packLastChunks = nChunks;
@@ -500,27 +493,152 @@ int mrc_dev_encode(mrc_handle* h, int a, int b, int64_t n_frames, const double* 
                              reservoir_out, lines_out, stream);
 }
 
+}  // extern "C"
+
 // ---------------------------------------------------------------------------------------------- host API
 
 namespace {
 
-struct Staged {
-    mrc_handle* h;
-    hipStream_t st;
-    // Every host entry point owns one Staged: whichever way the function is left (also through an error return in
-    // the middle), the stream is drained before the caller's buffers -- and any host temporaries declared BEFORE the
-    // Staged object -- go out of scope under a copy that is still in flight.
-    ~Staged() { if (st) (void)hipStreamSynchronize(st); }
-    int up(DevBuf& buf, const void* src, size_t bytes) {
-        MRC_HIP(h, buf.reserve(bytes ? bytes : 1));
-        if (bytes) MRC_HIP(h, hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, st));
+// Staging of the host entry points on h->stream.  in() and out() hand out the handle's staging buffers in the order a call
+// asks for them: in() fills its buffer from the caller's array (H2D), out() remembers the array its buffer goes back to;
+// finish() queues those copies (D2H; a null array: device only) and synchronises.  No buffer is handed out twice before a
+// rewind(), so none is re-reserved under a queued launch, and in steady state nothing is allocated.  The first failure
+// sticks: later calls hand out null, and ready() and finish() return it.  Whichever way the call is left, the stream is
+// drained before the caller's arrays -- and host temporaries declared BEFORE the Stage -- go out of scope.
+class Stage {
+  public:
+    explicit Stage(mrc_handle* h) : h_(h), drain_{{h->stream}} { check(hipSetDevice(h->device), "hipSetDevice"); }
+    template <class T> const T* in(const T* src, size_t count) {
+        DevBuf* b = next(count * sizeof(T));
+        if (b && count) check(hipMemcpyAsync(b->p, src, count * sizeof(T), hipMemcpyHostToDevice, h_->stream), "hipMemcpyAsync");
+        return status_ == MRC_OK ? b->as<T>() : nullptr;
+    }
+    template <class T> T* out(T* dst, size_t count) {
+        DevBuf* b = next(count * sizeof(T));
+        if (!b) return nullptr;
+        if (dst && count) copies_.push_back({dst, b->p, count * sizeof(T)});
+        return b->as<T>();
+    }
+    int ready() const { return status_; }
+    int finish() {
+        MRC_TRY(status_);
+        for (const Copy& c : copies_) MRC_HIP(h_, hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, h_->stream));
+        copies_.clear();
+        MRC_HIP(h_, hipStreamSynchronize(h_->stream));
         return MRC_OK;
     }
-    int down(void* dst, DevBuf& buf, size_t bytes) {
-        if (bytes && dst) MRC_HIP(h, hipMemcpyAsync(dst, buf.p, bytes, hipMemcpyDeviceToHost, st));
-        return MRC_OK;
+    // buffers handed out from here on can be handed out again after a finish() (nothing queued uses them any more)
+    size_t mark() const { return used_; }
+    void rewind(size_t mark) { used_ = mark; }
+
+  private:
+    struct Copy { void* dst; const void* src; size_t bytes; };
+    mrc_handle* h_;
+    DrainGuard drain_;
+    size_t used_ = 0;
+    int status_ = MRC_OK;
+    std::vector<Copy> copies_;
+    bool check(hipError_t e, const char* what) {
+        if (e != hipSuccess && status_ == MRC_OK) status_ = hip_fail(h_, e, what);
+        return status_ == MRC_OK;
+    }
+    DevBuf* next(size_t bytes) {
+        if (status_ != MRC_OK) return nullptr;
+        if (used_ == h_->stage.size()) h_->stage.emplace_back();
+        DevBuf* b = &h_->stage[used_++];
+        return check(b->reserve(bytes ? bytes : 1), "DevBuf::reserve") ? b : nullptr;
     }
 };
+
+// 16-bit PCM in host memory, pipelined over chunks of frames: copy in on h->stIn -> encode_core and after_kernels(lane, n)
+// on h->stream -> copy out on h->stOut, over the ring of lanes and ordered by their events.  copy_out(lane, c, f0, n)
+// queues chunk c's copies `lag` chunks after its kernels were queued: 0 when the copies do not depend on what the kernels
+// found, more when the host has to read something first (the size of a packed chunk).  prepare(chunk) reserves what the
+// caller's stages need per chunk.
+template <class Prepare, class AfterKernels, class CopyOut>
+int encode_pcm16_chunks(mrc_handle* h, const DevShape& S, int64_t n_frames, const int16_t* pcm_left, const int16_t* pcm_right,
+                        const int32_t* reservoir_in, int64_t chunk_frames, int64_t lag, Prepare prepare,
+                        AfterKernels after_kernels, CopyOut copy_out) {
+    const int L = h->cfg.n_mdct_lines;
+    const int joint = pcm_right ? 1 : 0, nsig = joint ? 4 : 1, nstream = joint ? 2 : 1;
+    // default chunk: 32 768 frames (64 MiB each way: below that the fixed cost of a copy shows -- 9 000 Msamples/s at
+    // 8 192 frames against 19 000 at 32 768), halved while the stream has fewer than six chunks to pipeline
+    int64_t chunk = chunk_frames;
+    if (!chunk)
+        for (chunk = 32768; chunk > 8192 && n_frames < 6 * chunk;) chunk /= 2;
+    if (chunk > n_frames) chunk = n_frames;
+    // streams, events and chunk buffers: created on first use, buffers sized for one chunk (+ the one-hop halo in front)
+    for (hipStream_t* st : {&h->stIn, &h->stOut})
+        if (!*st) MRC_HIP(h, hipStreamCreateWithFlags(st, hipStreamNonBlocking));
+    const hipStream_t stK = h->stream;
+    const size_t szPcm = (size_t)(chunk + 1) * L * sizeof(int16_t);
+    for (auto& lane : h->lanes) {
+        for (hipEvent_t* e : {&lane.evIn, &lane.evK, &lane.evOut})
+            if (!*e) MRC_HIP(h, hipEventCreateWithFlags(e, hipEventDisableTiming));
+        MRC_HIP(h, lane.pcmL.reserve(szPcm));
+        if (joint) MRC_HIP(h, lane.pcmR.reserve(szPcm));
+        MRC_HIP(h, lane.resIn.reserve((size_t)chunk * sizeof(int32_t)));
+        MRC_HIP(h, lane.oScale.reserve((size_t)chunk * nsig * sizeof(int32_t)));
+        MRC_HIP(h, lane.ms.reserve((size_t)chunk * S.nBands * sizeof(int32_t)));
+        MRC_HIP(h, lane.ba.reserve((size_t)chunk * nstream * S.nBands * sizeof(int32_t)));
+        MRC_HIP(h, lane.sf.reserve((size_t)chunk * nstream * S.nBands * sizeof(int32_t)));
+        MRC_HIP(h, lane.mant.reserve((size_t)chunk * nstream * S.halfN * sizeof(uint16_t)));
+        MRC_HIP(h, lane.resOut.reserve((size_t)chunk * sizeof(int32_t)));
+    }
+    MRC_HIP(h, h->wsPipe.lines.reserve((size_t)chunk * nsig * S.halfN * sizeof(double)));
+    MRC_HIP(h, h->wsPipe.smr.reserve((size_t)chunk * nsig * S.nBands * sizeof(double)));
+    MRC_HIP(h, h->wsPipe.peak.reserve(alloc_workspace_bytes(S, chunk, joint)));
+    MRC_TRY(prepare(chunk));
+    DrainGuard drain{{h->stIn, stK, h->stOut}};
+    auto frames = [&](int64_t c) { return std::min(chunk, n_frames - c * chunk); };
+    auto queue = [&](int64_t c) -> int {
+        Lane& lane = h->lanes[c % kLanes];
+        const bool reused = c >= kLanes;    // the lane's events still stand for chunk c - kLanes when they are waited on here
+        const int64_t f0 = c * chunk, n = frames(c);
+        const size_t inBytes = (size_t)(n + 1) * L * sizeof(int16_t);
+        // copy in (the lane's input buffers are free once the kernels of its previous chunk have run)
+        if (reused) MRC_HIP(h, hipStreamWaitEvent(h->stIn, lane.evK, 0));
+        MRC_HIP(h, hipMemcpyAsync(lane.pcmL.p, pcm_left + f0 * L, inBytes, hipMemcpyHostToDevice, h->stIn));
+        if (joint) MRC_HIP(h, hipMemcpyAsync(lane.pcmR.p, pcm_right + f0 * L, inBytes, hipMemcpyHostToDevice, h->stIn));
+        if (reservoir_in)
+            MRC_HIP(h, hipMemcpyAsync(lane.resIn.p, reservoir_in + f0, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stIn));
+        MRC_HIP(h, hipEventRecord(lane.evIn, h->stIn));
+        // kernels (the lane's output buffers are free once its previous chunk has been copied out)
+        MRC_HIP(h, hipStreamWaitEvent(stK, lane.evIn, 0));
+        if (reused) MRC_HIP(h, hipStreamWaitEvent(stK, lane.evOut, 0));
+        MRC_TRY(encode_core(h, S, n, lane.pcmL.p, joint ? lane.pcmR.p : nullptr, kSampleI16, L, nullptr,
+                            reservoir_in ? lane.resIn.as<int32_t>() : nullptr, lane.oScale.as<int32_t>(),
+                            lane.ms.as<int32_t>(), lane.ba.as<int32_t>(), lane.sf.as<int32_t>(), lane.mant.p,
+                            MRC_MANTISSA_I16, lane.resOut.as<int32_t>(), nullptr, h->wsPipe, stK));
+        MRC_TRY(after_kernels(lane, n));
+        MRC_HIP(h, hipEventRecord(lane.evK, stK));
+        return MRC_OK;
+    };
+    auto collect = [&](int64_t c) -> int {
+        Lane& lane = h->lanes[c % kLanes];
+        MRC_TRY(copy_out(lane, c, c * chunk, frames(c)));
+        MRC_HIP(h, hipEventRecord(lane.evOut, h->stOut));
+        return MRC_OK;
+    };
+    const bool wasTiming = h->timing;
+    h->timing = false;                      // the per-kernel events of encode_core belong to ONE call at a time
+    int rc = MRC_OK;
+    const int64_t nChunks = (n_frames + chunk - 1) / chunk;
+    for (int64_t c = 0; c < nChunks + lag && rc == MRC_OK; ++c) {
+        if (c < nChunks) rc = queue(c);
+        if (rc == MRC_OK && c >= lag) rc = collect(c - lag);
+    }
+    h->timing = wasTiming;
+    if (rc != MRC_OK) return rc;
+    for (hipStream_t st : {h->stIn, stK, h->stOut}) MRC_HIP(h, hipStreamSynchronize(st));
+    return MRC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+namespace {
 
 constexpr int64_t kSmallBatch = 64;               // calls with at most this many blocks go through one page-locked buffer each way
 
@@ -534,18 +652,11 @@ int encode_host(mrc_handle* h, int64_t n, int a, int b, const double* left, cons
     MRC_TRY(get_shape(h, a, b, &hs));
     const DevShape& S = hs->dev;
     const int joint = right ? 1 : 0, nsig = joint ? 4 : 1, nstream = joint ? 2 : 1;
-    MRC_HIP(h, hipSetDevice(h->device));
-    Staged s{h, h->stream};
     const size_t inBytes = (size_t)n * S.N * sizeof(double);
     const size_t szScale = (size_t)n * nsig * sizeof(int32_t), szSw = (size_t)n * S.nBands * sizeof(int32_t);
-    const size_t szBand = (size_t)n * nstream * S.nBands * sizeof(int32_t);
-    const size_t szMant = (size_t)n * nstream * S.halfN * sizeof(int32_t), szRes = (size_t)n * sizeof(int32_t);
+    const size_t szBand = (size_t)n * nstream * S.nBands * sizeof(int32_t), szRes = (size_t)n * sizeof(int32_t);
     const size_t szLines = (size_t)n * nsig * S.halfN * sizeof(double);
-    // (the chained back end's scan covers <= 64 coded bands, 2..16 mantissa bits and lines in units of four, at most
-    // kChainMaxLinesPerItem of them per block -- chained_core checks the same; other shapes take the batch path)
-    const bool chainable = nstream * S.nBands <= 64 && S.maxMantBits >= 2 && S.maxMantBits <= 16 && (S.halfN & 3) == 0 &&
-                           nstream * S.halfN <= kChainMaxLinesPerItem;
-    if (n <= kSmallBatch && chainable) {
+    if (n <= kSmallBatch && !chain_shape_misfit(S, nstream)) {
         // The per-block seam (pacfileThem.py:649,820 -> codecThem.py:205-278 hands over ONE block per call).  Two things made
         // such a call slow (0.45 ms per joint block in round 3): every array in its own pageable copy (ten staging round trips
         // of the runtime), and the batch path's bit allocation -- one LANE per frame walking the greedy loop, ~135 us alone
@@ -557,38 +668,33 @@ int encode_host(mrc_handle* h, int64_t n, int a, int b, const double* left, cons
         //     (chain_prep_kernel) and the scan kernel with every block as a stream of its own and Huffman pricing off, which
         //     leaves exactly what JointEncodeChannels / EncodeSingleChannel return (codecThem.py:332,503: the allocation's
         //     remainder as the reservoir; the savings are the caller's, 224,274).
+        DrainGuard drain{{h->stream}};
+        SmallBatchBufs& B = h->smallBatch;
         auto al = [](size_t v) { return (v + 15) & ~(size_t)15; };
-        const int nEv = (int)chain_events_per_block(S, joint), nTot = nstream * S.nBands;
+        const int nEv = (int)chain_events_per_block(S, joint);
         const size_t szDesc = sizeof(ChainGroupDev), szItems = (size_t)n * sizeof(int32_t), szStart = (size_t)(n + 1) * sizeof(long long);
         const size_t szMant16 = (size_t)n * nstream * S.halfN * sizeof(uint16_t);
         const size_t oR = al(inBytes), oDesc = oR + (joint ? al(inBytes) : 0), oItems = oDesc + al(szDesc),
                      oStart = oItems + al(szItems), oRes = oStart + al(szStart), oScale = oRes + al(szRes),
                      oSw = oScale + al(szScale), oSf = oSw + al(joint ? szSw : 0), oBa = oSf + al(szBand), oMant = oBa + al(szBand),
                      oLines = oMant + al(szMant16), total = oLines + al(szLines);
-        MRC_HIP(h, h->pinIn.reserve(oScale));
-        MRC_HIP(h, h->pinOut.reserve(total - oRes));
-        MRC_HIP(h, h->inL.reserve(total));
-        MRC_HIP(h, h->inAux.reserve((size_t)n * nEv * sizeof(unsigned)));
-        MRC_HIP(h, h->inAux2.reserve((size_t)n * (nEv + 1) * sizeof(unsigned)));
-        MRC_HIP(h, h->outB.reserve((size_t)n * nstream * sizeof(int32_t)));          // table ids (all 15: no pricing)
+        MRC_HIP(h, B.pinIn.reserve(oScale));
+        MRC_HIP(h, B.pinOut.reserve(total - oRes));
+        MRC_HIP(h, B.layout.reserve(total));
+        MRC_HIP(h, B.ev.reserve((size_t)n * nEv * sizeof(unsigned)));
+        MRC_HIP(h, B.pre.reserve((size_t)n * (nEv + 1) * sizeof(unsigned)));
+        MRC_HIP(h, B.table.reserve((size_t)n * nstream * sizeof(int32_t)));
         Workspace& ws = h->ws;
         MRC_HIP(h, ws.smr.reserve((size_t)n * nsig * S.nBands * sizeof(double)));
         MRC_HIP(h, ws.peak.reserve(alloc_workspace_bytes(S, n, joint)));
-        char* pin = (char*)h->pinIn.p;
-        char* dev = (char*)h->inL.p;
+        char* pin = (char*)B.pinIn.p;
+        char* dev = (char*)B.layout.p;
         std::memcpy(pin, left, inBytes);
         if (joint) std::memcpy(pin + oR, right, inBytes);
-        ChainGroupDev D{};
-        D.joint = joint; D.nb = S.nBands; D.nTot = nTot; D.M = S.halfN; D.K = S.maxMantBits - 1; D.nEv = nEv;
-        D.nScaleBits = S.nScaleBits; D.nstream = nstream;
-        D.maxN = 0;
-        for (int v : hs->bandN) if (v > D.maxN) D.maxN = v;
-        D.budgetMono = S.budgetMono; D.budgetJointPre = S.budgetJointPre; D.blkswA = S.blkswA; D.blkswB = S.blkswB;
-        D.bandOfLine = S.bandOfLine; D.bandN = S.bandN;
-        D.lines = (const double*)(dev + oLines); D.peak = ws.peak.as<double>(); D.oscale = (const int*)(dev + oScale);
-        D.ms = (const int*)(dev + oSw); D.ev = h->inAux.as<unsigned>(); D.pre = h->inAux2.as<unsigned>();
-        D.bitAlloc = (int*)(dev + oBa); D.scaleFactor = (int*)(dev + oSf); D.mant = (unsigned short*)(dev + oMant);
-        D.table = h->outB.as<int32_t>();
+        const ChainGroupDev D = chain_group_desc(*hs, joint, (const double*)(dev + oLines), ws.peak.as<double>(),
+                                                 (const int*)(dev + oScale), (const int*)(dev + oSw), B.ev.as<unsigned>(),
+                                                 B.pre.as<unsigned>(), (int*)(dev + oBa), (int*)(dev + oSf),
+                                                 (unsigned short*)(dev + oMant), B.table.as<int32_t>());
         std::memcpy(pin + oDesc, &D, sizeof D);
         for (int64_t i = 0; i < n; ++i) {
             reinterpret_cast<int32_t*>(pin + oItems)[i] = (int32_t)i;                  // group 0, block i
@@ -603,7 +709,7 @@ int encode_host(mrc_handle* h, int64_t n, int a, int b, const double* left, cons
                                (int32_t*)(dev + oScale), joint ? (int32_t*)(dev + oSw) : nullptr, ws.smr.as<double>(),
                                ws.peak.as<double>(), st, timing));
         MRC_HIP(h, launch_chain_prep(S, joint, n, ws.smr.as<double>(), joint ? (const int*)(dev + oSw) : nullptr,
-                                     h->inAux.as<unsigned>(), h->inAux2.as<unsigned>(), 0, st));
+                                     B.ev.as<unsigned>(), B.pre.as<unsigned>(), 0, st));
         if (timing) MRC_HIP(h, hipEventRecord(h->ev[4], st));
         MRC_HIP(h, launch_chain_phase_b(n, (const ChainGroupDev*)(dev + oDesc), (const int*)(dev + oItems),
                                         (const long long*)(dev + oStart), (int*)(dev + oRes), nullptr, 0, h->chainThreads, st));
@@ -613,7 +719,7 @@ int encode_host(mrc_handle* h, int64_t n, int a, int b, const double* left, cons
                                           ws.smr.as<double>(), ws.peak.as<double>(), joint ? (const int*)(dev + oSw) : nullptr,
                                           (const int*)(dev + oBa), (const int*)(dev + oSf), h->sens.as<unsigned long long>(),
                                           nullptr, st));
-        char* pout = (char*)h->pinOut.p;
+        char* pout = (char*)B.pinOut.p;
         const size_t outBytes = (mdct_out ? total : oLines) - oRes;                     // (the lines only travel when asked for)
         MRC_HIP(h, hipMemcpyAsync(pout, dev + oRes, outBytes, hipMemcpyDeviceToHost, st));
         MRC_HIP(h, hipStreamSynchronize(st));
@@ -629,25 +735,21 @@ int encode_host(mrc_handle* h, int64_t n, int a, int b, const double* left, cons
         if (mdct_out) std::memcpy(mdct_out, o + oLines, szLines);
         return MRC_OK;
     }
-    MRC_TRY(s.up(h->inL, left, inBytes));
-    if (joint) MRC_TRY(s.up(h->inR, right, inBytes));
-    if (reservoir_in) MRC_TRY(s.up(h->inAux, reservoir_in, (size_t)n * sizeof(int32_t)));
-    MRC_HIP(h, h->outA.reserve(szScale)); MRC_HIP(h, h->outB.reserve(szSw)); MRC_HIP(h, h->outC.reserve(szBand));
-    MRC_HIP(h, h->outD.reserve(szBand));  MRC_HIP(h, h->outE.reserve(szMant)); MRC_HIP(h, h->outF.reserve(szRes));
-    MRC_HIP(h, h->outG.reserve(szLines));
-    MRC_TRY(mrc_dev_encode(h, a, b, n, h->inL.as<double>(), joint ? h->inR.as<double>() : nullptr, S.N, nullptr,
-                           reservoir_in ? h->inAux.as<int32_t>() : nullptr, h->outA.as<int32_t>(),
-                           h->outB.as<int32_t>(), h->outD.as<int32_t>(), h->outC.as<int32_t>(), h->outE.as<int32_t>(),
-                           h->outF.as<int32_t>(), h->outG.as<double>(), h->stream));
-    MRC_TRY(s.down(overall_scale, h->outA, szScale));
-    if (joint) MRC_TRY(s.down(ms_switch, h->outB, szSw));
-    MRC_TRY(s.down(scale_factor, h->outC, szBand));
-    MRC_TRY(s.down(bit_alloc, h->outD, szBand));
-    MRC_TRY(s.down(mantissa, h->outE, szMant));
-    MRC_TRY(s.down(reservoir_out, h->outF, szRes));
-    MRC_TRY(s.down(mdct_out, h->outG, szLines));
-    MRC_HIP(h, hipStreamSynchronize(h->stream));
-    return MRC_OK;
+    Stage s(h);
+    const double* dL = s.in(left, (size_t)n * S.N);
+    const double* dR = joint ? s.in(right, (size_t)n * S.N) : nullptr;
+    const int32_t* dResIn = reservoir_in ? s.in(reservoir_in, (size_t)n) : nullptr;
+    int32_t* dScale = s.out(overall_scale, (size_t)n * nsig);
+    int32_t* dSw = s.out(ms_switch, (size_t)n * S.nBands);
+    int32_t* dSf = s.out(scale_factor, (size_t)n * nstream * S.nBands);
+    int32_t* dBa = s.out(bit_alloc, (size_t)n * nstream * S.nBands);
+    int32_t* dMant = s.out(mantissa, (size_t)n * nstream * S.halfN);
+    int32_t* dResOut = s.out(reservoir_out, (size_t)n);
+    double* dLines = s.out(mdct_out, (size_t)n * nsig * S.halfN);
+    MRC_TRY(s.ready());
+    MRC_TRY(mrc_dev_encode(h, a, b, n, dL, dR, S.N, nullptr, dResIn, dScale, dSw, dBa, dSf, dMant, dResOut, dLines,
+                           h->stream));
+    return s.finish();
 }
 
 }  // namespace
@@ -694,82 +796,21 @@ int mrc_encode_stream_pcm16(mrc_handle* h, int64_t n_frames, const int16_t* pcm_
     MRC_TRY(get_shape(h, L, L, &hs));
     const DevShape& S = hs->dev;
     const int joint = pcm_right ? 1 : 0, nsig = joint ? 4 : 1, nstream = joint ? 2 : 1;
-    // default chunk: 32 768 frames (64 MiB each way: below that the fixed cost of a copy shows -- 9 000 Msamples/s at
-    // 8 192 frames against 19 000 at 32 768), halved while the stream has fewer than six chunks to pipeline
-    int64_t chunk = chunk_frames;
-    if (!chunk)
-        for (chunk = 32768; chunk > 8192 && n_frames < 6 * chunk;) chunk /= 2;
-    if (chunk > n_frames) chunk = n_frames;
-    // streams, events and chunk buffers: created on first use, buffers sized for one chunk (+ the one-hop halo in front)
-    for (hipStream_t* st : {&h->stIn, &h->stOut})
-        if (!*st) MRC_HIP(h, hipStreamCreateWithFlags(st, hipStreamNonBlocking));
-    const hipStream_t stK = h->stream;
-    const size_t szPcm = (size_t)(chunk + 1) * L * sizeof(int16_t);
-    for (auto& lane : h->lanes) {
-        for (hipEvent_t* e : {&lane.evIn, &lane.evK, &lane.evOut})
-            if (!*e) MRC_HIP(h, hipEventCreateWithFlags(e, hipEventDisableTiming));
-        MRC_HIP(h, lane.pcmL.reserve(szPcm));
-        if (joint) MRC_HIP(h, lane.pcmR.reserve(szPcm));
-        MRC_HIP(h, lane.resIn.reserve((size_t)chunk * sizeof(int32_t)));
-        MRC_HIP(h, lane.oScale.reserve((size_t)chunk * nsig * sizeof(int32_t)));
-        MRC_HIP(h, lane.ms.reserve((size_t)chunk * S.nBands * sizeof(int32_t)));
-        MRC_HIP(h, lane.ba.reserve((size_t)chunk * nstream * S.nBands * sizeof(int32_t)));
-        MRC_HIP(h, lane.sf.reserve((size_t)chunk * nstream * S.nBands * sizeof(int32_t)));
-        MRC_HIP(h, lane.mant.reserve((size_t)chunk * nstream * S.halfN * sizeof(uint16_t)));
-        MRC_HIP(h, lane.resOut.reserve((size_t)chunk * sizeof(int32_t)));
-    }
-    MRC_HIP(h, h->wsPipe.lines.reserve((size_t)chunk * nsig * S.halfN * sizeof(double)));
-    MRC_HIP(h, h->wsPipe.smr.reserve((size_t)chunk * nsig * S.nBands * sizeof(double)));
-    MRC_HIP(h, h->wsPipe.peak.reserve(alloc_workspace_bytes(S, chunk, joint)));
-    struct DrainAll {                       // whichever way we leave: nothing of ours is still using the caller's memory
-        mrc_handle* h;
-        ~DrainAll() { for (hipStream_t st : {h->stIn, h->stream, h->stOut}) if (st) (void)hipStreamSynchronize(st); }
-    } drain{h};
-    const bool wasTiming = h->timing;
-    h->timing = false;                      // the per-kernel events of encode_core belong to ONE call at a time
-    int rc = MRC_OK;
-    int64_t c = 0;
-    for (int64_t f0 = 0; f0 < n_frames && rc == MRC_OK; f0 += chunk, ++c) {
-        Lane& lane = h->lanes[c % kLanes];
-        const bool reused = c >= kLanes;    // the lane's events still stand for chunk c - kLanes when they are waited on here
-        const int64_t n = (n_frames - f0 < chunk) ? n_frames - f0 : chunk;
-        const size_t inBytes = (size_t)(n + 1) * L * sizeof(int16_t);
-#define MRC_Q(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { rc = hip_fail(h, e_, #call); break; } } while (0)
-        do {
-            // copy in (the lane's input buffers are free once the kernels of its previous chunk have run)
-            if (reused) MRC_Q(hipStreamWaitEvent(h->stIn, lane.evK, 0));
-            MRC_Q(hipMemcpyAsync(lane.pcmL.p, pcm_left + f0 * L, inBytes, hipMemcpyHostToDevice, h->stIn));
-            if (joint) MRC_Q(hipMemcpyAsync(lane.pcmR.p, pcm_right + f0 * L, inBytes, hipMemcpyHostToDevice, h->stIn));
-            if (reservoir_in)
-                MRC_Q(hipMemcpyAsync(lane.resIn.p, reservoir_in + f0, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stIn));
-            MRC_Q(hipEventRecord(lane.evIn, h->stIn));
-            // kernels (the lane's output buffers are free once its previous chunk has been copied out)
-            MRC_Q(hipStreamWaitEvent(stK, lane.evIn, 0));
-            if (reused) MRC_Q(hipStreamWaitEvent(stK, lane.evOut, 0));
-            rc = encode_core(h, S, n, lane.pcmL.p, joint ? lane.pcmR.p : nullptr, kSampleI16, L, nullptr,
-                             reservoir_in ? lane.resIn.as<int32_t>() : nullptr, lane.oScale.as<int32_t>(),
-                             lane.ms.as<int32_t>(), lane.ba.as<int32_t>(), lane.sf.as<int32_t>(), lane.mant.p,
-                             MRC_MANTISSA_I16, lane.resOut.as<int32_t>(), nullptr, h->wsPipe, stK);
-            if (rc != MRC_OK) break;
-            MRC_Q(hipEventRecord(lane.evK, stK));
-            // copy out
+    return encode_pcm16_chunks(
+        h, S, n_frames, pcm_left, pcm_right, reservoir_in, chunk_frames, 0, [](int64_t) -> int { return MRC_OK; },
+        [](Lane&, int64_t) -> int { return MRC_OK; },
+        [&](Lane& lane, int64_t, int64_t f0, int64_t n) -> int {
             hipStream_t so = h->stOut;
-            MRC_Q(hipStreamWaitEvent(so, lane.evK, 0));
-            MRC_Q(hipMemcpyAsync(mantissa16 + f0 * nstream * S.halfN, lane.mant.p, (size_t)n * nstream * S.halfN * sizeof(uint16_t), hipMemcpyDeviceToHost, so));
-            MRC_Q(hipMemcpyAsync(overall_scale + f0 * nsig, lane.oScale.p, (size_t)n * nsig * sizeof(int32_t), hipMemcpyDeviceToHost, so));
+            MRC_HIP(h, hipStreamWaitEvent(so, lane.evK, 0));
+            MRC_HIP(h, hipMemcpyAsync(mantissa16 + f0 * nstream * S.halfN, lane.mant.p, (size_t)n * nstream * S.halfN * sizeof(uint16_t), hipMemcpyDeviceToHost, so));
+            MRC_HIP(h, hipMemcpyAsync(overall_scale + f0 * nsig, lane.oScale.p, (size_t)n * nsig * sizeof(int32_t), hipMemcpyDeviceToHost, so));
             if (joint)
-                MRC_Q(hipMemcpyAsync(ms_switch + f0 * S.nBands, lane.ms.p, (size_t)n * S.nBands * sizeof(int32_t), hipMemcpyDeviceToHost, so));
-            MRC_Q(hipMemcpyAsync(bit_alloc + f0 * nstream * S.nBands, lane.ba.p, (size_t)n * nstream * S.nBands * sizeof(int32_t), hipMemcpyDeviceToHost, so));
-            MRC_Q(hipMemcpyAsync(scale_factor + f0 * nstream * S.nBands, lane.sf.p, (size_t)n * nstream * S.nBands * sizeof(int32_t), hipMemcpyDeviceToHost, so));
-            MRC_Q(hipMemcpyAsync(reservoir_out + f0, lane.resOut.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, so));
-            MRC_Q(hipEventRecord(lane.evOut, so));
-        } while (0);
-#undef MRC_Q
-    }
-    h->timing = wasTiming;
-    if (rc != MRC_OK) return rc;
-    for (hipStream_t st : {h->stIn, stK, h->stOut}) MRC_HIP(h, hipStreamSynchronize(st));
-    return MRC_OK;
+                MRC_HIP(h, hipMemcpyAsync(ms_switch + f0 * S.nBands, lane.ms.p, (size_t)n * S.nBands * sizeof(int32_t), hipMemcpyDeviceToHost, so));
+            MRC_HIP(h, hipMemcpyAsync(bit_alloc + f0 * nstream * S.nBands, lane.ba.p, (size_t)n * nstream * S.nBands * sizeof(int32_t), hipMemcpyDeviceToHost, so));
+            MRC_HIP(h, hipMemcpyAsync(scale_factor + f0 * nstream * S.nBands, lane.sf.p, (size_t)n * nstream * S.nBands * sizeof(int32_t), hipMemcpyDeviceToHost, so));
+            MRC_HIP(h, hipMemcpyAsync(reservoir_out + f0, lane.resOut.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, so));
+            return MRC_OK;
+        });
 }
 
 // ---- 16-bit PCM in host memory -> `.pac` chunk bytes in host memory, pipelined ---------------------------------
@@ -791,119 +832,63 @@ int mrc_encode_stream_pcm16_pac(mrc_handle* h, int64_t n_frames, const int16_t* 
     MRC_TRY(get_shape(h, L, L, &hs));
     const DevShape& S = hs->dev;
     const mrc_config& cfg = h->cfg;
-    const int joint = pcm_right ? 1 : 0, nsig = joint ? 4 : 1, nch = joint ? 2 : 1;
-    int64_t chunk = chunk_frames;
-    if (!chunk)
-        for (chunk = 32768; chunk > 8192 && n_frames < 6 * chunk;) chunk /= 2;
-    if (chunk > n_frames) chunk = n_frames;
+    const int joint = pcm_right ? 1 : 0, nch = joint ? 2 : 1;
     const int64_t bound = mrc_pack_bound(&cfg, L, L, 1, joint);             // worst case per channel chunk, length field included
     if (bound < 0) return fail(h, MRC_ERR_INVALID, "mrc_encode_stream_pcm16_pac: field widths out of range");
-    for (hipStream_t* st : {&h->stIn, &h->stOut})
-        if (!*st) MRC_HIP(h, hipStreamCreateWithFlags(st, hipStreamNonBlocking));
-    const hipStream_t stK = h->stream;
-    const size_t szPcm = (size_t)(chunk + 1) * L * sizeof(int16_t);
-    const size_t pacCap = (size_t)chunk * nch * (size_t)bound;
-    for (auto& lane : h->lanes) {
-        for (hipEvent_t* e : {&lane.evIn, &lane.evK, &lane.evOut})
-            if (!*e) MRC_HIP(h, hipEventCreateWithFlags(e, hipEventDisableTiming));
-        if (!lane.pacTotal) {
-            MRC_HIP(h, hipHostMalloc(reinterpret_cast<void**>(&lane.pacTotal), 2 * sizeof(long long), hipHostMallocDefault));
-            lane.pacTotal[0] = lane.pacTotal[1] = 0;
-        }
-        MRC_HIP(h, lane.pcmL.reserve(szPcm));
-        if (joint) MRC_HIP(h, lane.pcmR.reserve(szPcm));
-        MRC_HIP(h, lane.resIn.reserve((size_t)chunk * sizeof(int32_t)));
-        MRC_HIP(h, lane.oScale.reserve((size_t)chunk * nsig * sizeof(int32_t)));
-        MRC_HIP(h, lane.ms.reserve((size_t)chunk * S.nBands * sizeof(int32_t)));
-        MRC_HIP(h, lane.ba.reserve((size_t)chunk * nch * S.nBands * sizeof(int32_t)));
-        MRC_HIP(h, lane.sf.reserve((size_t)chunk * nch * S.nBands * sizeof(int32_t)));
-        MRC_HIP(h, lane.mant.reserve((size_t)chunk * nch * S.halfN * sizeof(uint16_t)));
-        MRC_HIP(h, lane.resOut.reserve((size_t)chunk * sizeof(int32_t)));
-        MRC_HIP(h, lane.pacBytes.reserve(pacCap));
-        MRC_HIP(h, lane.pacOffs.reserve((size_t)(chunk + 1) * sizeof(int64_t)));
-        MRC_HIP(h, lane.pacTable.reserve((size_t)chunk * nch * sizeof(int32_t)));
-        MRC_HIP(h, lane.pacSaved.reserve((size_t)chunk * nch * sizeof(int32_t)));
-    }
-    MRC_HIP(h, h->wsPipe.lines.reserve((size_t)chunk * nsig * S.halfN * sizeof(double)));
-    MRC_HIP(h, h->wsPipe.smr.reserve((size_t)chunk * nsig * S.nBands * sizeof(double)));
-    MRC_HIP(h, h->wsPipe.peak.reserve(alloc_workspace_bytes(S, chunk, joint)));
-    struct DrainAll {
-        mrc_handle* h;
-        ~DrainAll() { for (hipStream_t st : {h->stIn, h->stream, h->stOut}) if (st) (void)hipStreamSynchronize(st); }
-    } drain{h};
-    const bool wasTiming = h->timing;
-    h->timing = false;
-    int rc = MRC_OK;
-    const int64_t nChunks = (n_frames + chunk - 1) / chunk;
-    std::vector<int64_t> base((size_t)nChunks + 1, 0);                      // where every chunk's bytes start in `out`
-#define MRC_Q(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { rc = hip_fail(h, e_, #call); break; } } while (0)
-    // copies chunk c's packed form out, once its size is known (called one chunk behind the queueing loop)
-    auto collect = [&](int64_t c) {
-        Lane& lane = h->lanes[c % kLanes];
-        const int64_t f0 = c * chunk;
-        const int64_t n = (n_frames - f0 < chunk) ? n_frames - f0 : chunk;
-        do {
-            MRC_Q(hipEventSynchronize(lane.evK));
-            const long long total = lane.pacTotal[0];
-            if (lane.pacTotal[1] & 3) { rc = fail(h, MRC_ERR_INVALID, "mrc_encode_stream_pcm16_pac: internal error (table id / chunk size out of range)"); break; }
-            base[(size_t)c + 1] = base[(size_t)c] + total;
-            if (base[(size_t)c + 1] > out_cap) { rc = fail(h, MRC_ERR_NOMEM, "mrc_encode_stream_pcm16_pac: out_cap too small"); break; }
-            hipStream_t so = h->stOut;
-            MRC_Q(hipMemcpyAsync(out + base[(size_t)c], lane.pacBytes.p, (size_t)total, hipMemcpyDeviceToHost, so));
-            MRC_Q(hipMemcpyAsync(block_offset + f0, lane.pacOffs.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, so));
-            if (huff_table)
-                MRC_Q(hipMemcpyAsync(huff_table + f0 * nch, lane.pacTable.p, (size_t)n * nch * sizeof(int32_t), hipMemcpyDeviceToHost, so));
-            if (bits_saved)
-                MRC_Q(hipMemcpyAsync(bits_saved + f0 * nch, lane.pacSaved.p, (size_t)n * nch * sizeof(int32_t), hipMemcpyDeviceToHost, so));
-            if (reservoir_out)
-                MRC_Q(hipMemcpyAsync(reservoir_out + f0, lane.resOut.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, so));
-            MRC_Q(hipEventRecord(lane.evOut, so));
-        } while (0);
-    };
+    const PackParams P = pack_params(cfg, L, L, nch, joint, use_huffman);
     constexpr int64_t kCollectLag = 2;      // < kLanes - 1: chunk c's buffers are reused by chunk c + kLanes
     static_assert(kCollectLag < kLanes - 1, "a lane must be collected before it is queued again");
-    static const PackTables tables = [] { PackTables t; pack_tables(&t); return t; }();
-    PackParams P;
-    P.nch = nch; P.joint = joint; P.useHuffman = use_huffman ? 1 : 0;
-    P.nScaleBits = cfg.n_scale_bits; P.nMantSizeBits = cfg.n_mant_size_bits;
-    P.blkBitsA = cfg.blksw_bits_a; P.blkBitsB = cfg.blksw_bits_b;
-    P.bitA = 0; P.bitB = 0;                                                 // long blocks: 1 - a / nMDCTLines = 0
-    MRC_HIP(h, h->packWs.reserve(pack_workspace_bytes(chunk * nch)));
-    for (int64_t c = 0; c < nChunks && rc == MRC_OK; ++c) {
-        Lane& lane = h->lanes[c % kLanes];
-        const bool reused = c >= kLanes;
-        const int64_t f0 = c * chunk;
-        const int64_t n = (n_frames - f0 < chunk) ? n_frames - f0 : chunk;
-        const size_t inBytes = (size_t)(n + 1) * L * sizeof(int16_t);
-        do {
-            if (reused) MRC_Q(hipStreamWaitEvent(h->stIn, lane.evK, 0));
-            MRC_Q(hipMemcpyAsync(lane.pcmL.p, pcm_left + f0 * L, inBytes, hipMemcpyHostToDevice, h->stIn));
-            if (joint) MRC_Q(hipMemcpyAsync(lane.pcmR.p, pcm_right + f0 * L, inBytes, hipMemcpyHostToDevice, h->stIn));
-            if (reservoir_in)
-                MRC_Q(hipMemcpyAsync(lane.resIn.p, reservoir_in + f0, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stIn));
-            MRC_Q(hipEventRecord(lane.evIn, h->stIn));
-            MRC_Q(hipStreamWaitEvent(stK, lane.evIn, 0));
-            if (reused) MRC_Q(hipStreamWaitEvent(stK, lane.evOut, 0));      // (chunk c - kLanes was collected below, kLanes - kCollectLag turns ago)
-            rc = encode_core(h, S, n, lane.pcmL.p, joint ? lane.pcmR.p : nullptr, kSampleI16, L, nullptr,
-                             reservoir_in ? lane.resIn.as<int32_t>() : nullptr, lane.oScale.as<int32_t>(),
-                             lane.ms.as<int32_t>(), lane.ba.as<int32_t>(), lane.sf.as<int32_t>(), lane.mant.p,
-                             MRC_MANTISSA_I16, lane.resOut.as<int32_t>(), nullptr, h->wsPipe, stK);
-            if (rc != MRC_OK) break;
-            MRC_Q(launch_pack(S, P, tables, n, lane.oScale.as<int32_t>(), lane.ms.as<int32_t>(), lane.sf.as<int32_t>(),
-                              lane.ba.as<int32_t>(), lane.mant.p, MRC_MANTISSA_I16, nullptr, lane.pacTable.as<int32_t>(),
-                              lane.pacSaved.as<int32_t>(), lane.pacBytes.as<unsigned char>(), (long long)pacCap,
-                              lane.pacOffs.as<long long>(), h->packWs.p, (int)(bound - 4), all_bands_non_empty(*hs), stK));
-            MRC_Q(launch_pack_export(h->packWs.p, n * nch, lane.pacTotal, stK));   // 16 bytes, written by a kernel: no copy command
-            MRC_Q(hipEventRecord(lane.evK, stK));
-        } while (0);
-        if (rc == MRC_OK && c >= kCollectLag) collect(c - kCollectLag);
-    }
-    for (int64_t c = nChunks > kCollectLag ? nChunks - kCollectLag : 0; c < nChunks && rc == MRC_OK; ++c) collect(c);
-#undef MRC_Q
-    h->timing = wasTiming;
-    if (rc != MRC_OK) return rc;
-    for (hipStream_t st : {h->stIn, stK, h->stOut}) MRC_HIP(h, hipStreamSynchronize(st));
+    int64_t chunk = 0;
+    size_t pacCap = 0;
+    std::vector<int64_t> base;              // where every chunk's bytes start in `out`
+    MRC_TRY(encode_pcm16_chunks(
+        h, S, n_frames, pcm_left, pcm_right, reservoir_in, chunk_frames, kCollectLag,
+        [&](int64_t chunkFrames) -> int {
+            chunk = chunkFrames;
+            pacCap = (size_t)chunk * nch * (size_t)bound;
+            base.assign((size_t)((n_frames + chunk - 1) / chunk) + 1, 0);
+            for (auto& lane : h->lanes) {
+                if (!lane.pacTotal) {
+                    MRC_HIP(h, hipHostMalloc(reinterpret_cast<void**>(&lane.pacTotal), 2 * sizeof(long long), hipHostMallocDefault));
+                    lane.pacTotal[0] = lane.pacTotal[1] = 0;
+                }
+                MRC_HIP(h, lane.pacBytes.reserve(pacCap));
+                MRC_HIP(h, lane.pacOffs.reserve((size_t)(chunk + 1) * sizeof(int64_t)));
+                MRC_HIP(h, lane.pacTable.reserve((size_t)chunk * nch * sizeof(int32_t)));
+                MRC_HIP(h, lane.pacSaved.reserve((size_t)chunk * nch * sizeof(int32_t)));
+            }
+            MRC_HIP(h, h->packWs.reserve(pack_workspace_bytes(chunk * nch)));
+            return MRC_OK;
+        },
+        [&](Lane& lane, int64_t n) -> int {
+            MRC_HIP(h, launch_pack(S, P, host_pack_tables(), n, lane.oScale.as<int32_t>(), lane.ms.as<int32_t>(),
+                                   lane.sf.as<int32_t>(), lane.ba.as<int32_t>(), lane.mant.p, MRC_MANTISSA_I16, nullptr,
+                                   lane.pacTable.as<int32_t>(), lane.pacSaved.as<int32_t>(), lane.pacBytes.as<unsigned char>(),
+                                   (long long)pacCap, lane.pacOffs.as<long long>(), h->packWs.p, (int)(bound - 4),
+                                   all_bands_non_empty(*hs), h->stream));
+            MRC_HIP(h, launch_pack_export(h->packWs.p, n * nch, lane.pacTotal, h->stream));   // 16 bytes, written by a kernel: no copy command
+            return MRC_OK;
+        },
+        // copies chunk c's packed form out, once its size is known
+        [&](Lane& lane, int64_t c, int64_t f0, int64_t n) -> int {
+            MRC_HIP(h, hipEventSynchronize(lane.evK));
+            const long long total = lane.pacTotal[0];
+            if (lane.pacTotal[1] & 3) return fail(h, MRC_ERR_INVALID, "mrc_encode_stream_pcm16_pac: internal error (table id / chunk size out of range)");
+            base[(size_t)c + 1] = base[(size_t)c] + total;
+            if (base[(size_t)c + 1] > out_cap) return fail(h, MRC_ERR_NOMEM, "mrc_encode_stream_pcm16_pac: out_cap too small");
+            hipStream_t so = h->stOut;
+            MRC_HIP(h, hipMemcpyAsync(out + base[(size_t)c], lane.pacBytes.p, (size_t)total, hipMemcpyDeviceToHost, so));
+            MRC_HIP(h, hipMemcpyAsync(block_offset + f0, lane.pacOffs.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, so));
+            if (huff_table)
+                MRC_HIP(h, hipMemcpyAsync(huff_table + f0 * nch, lane.pacTable.p, (size_t)n * nch * sizeof(int32_t), hipMemcpyDeviceToHost, so));
+            if (bits_saved)
+                MRC_HIP(h, hipMemcpyAsync(bits_saved + f0 * nch, lane.pacSaved.p, (size_t)n * nch * sizeof(int32_t), hipMemcpyDeviceToHost, so));
+            if (reservoir_out)
+                MRC_HIP(h, hipMemcpyAsync(reservoir_out + f0, lane.resOut.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, so));
+            return MRC_OK;
+        }));
     // the chunks' block offsets count from their own first byte
+    const int64_t nChunks = (int64_t)base.size() - 1;
     for (int64_t c = 0; c < nChunks; ++c) {
         const int64_t f0 = c * chunk, n = (n_frames - f0 < chunk) ? n_frames - f0 : chunk;
         if (base[(size_t)c])
@@ -924,7 +909,6 @@ int encode_blocks_host(mrc_handle* h, int64_t n, const double* left, const doubl
         (right && !ms_switch) || n < 0)
         return fail(h, MRC_ERR_INVALID, "mrc_encode_blocks: bad argument");
     if (n == 0) return MRC_OK;
-    MRC_HIP(h, hipSetDevice(h->device));
     const int joint = right ? 1 : 0, nsig = joint ? 4 : 1, nstream = joint ? 2 : 1;
     const int L = h->cfg.n_mdct_lines;
     // where each block starts in the packed input, and which blocks share a shape
@@ -939,10 +923,10 @@ int encode_blocks_host(mrc_handle* h, int64_t n, const double* left, const doubl
     }
     std::vector<int64_t> offs;
     std::vector<int32_t> resG, tScale, tSw, tSf, tBa, tMant, tRes;
-    Staged s{h, h->stream};                                 // (the vectors above outlive its drain)
-    const size_t inBytes = (size_t)start[(size_t)n] * sizeof(double);
-    MRC_TRY(s.up(h->inL, left, inBytes));
-    if (joint) MRC_TRY(s.up(h->inR, right, inBytes));
+    Stage s(h);                                             // (the vectors above outlive its drain)
+    const double* dL = s.in(left, (size_t)start[(size_t)n]);
+    const double* dR = joint ? s.in(right, (size_t)start[(size_t)n]) : nullptr;
+    const size_t groupSlots = s.mark();                     // every group's buffers from here on
     for (auto& kv : groups) {
         const int ga = kv.first.first, gb = kv.first.second;
         const std::vector<int64_t>& idx = kv.second;
@@ -956,26 +940,21 @@ int encode_blocks_host(mrc_handle* h, int64_t n, const double* left, const doubl
             offs[(size_t)j] = start[(size_t)idx[(size_t)j]];
             if (reservoir_in) resG[(size_t)j] = reservoir_in[idx[(size_t)j]];
         }
-        const size_t szScale = (size_t)m * nsig * sizeof(int32_t), szSw = (size_t)m * S.nBands * sizeof(int32_t);
-        const size_t szBand = (size_t)m * nstream * S.nBands * sizeof(int32_t);
-        const size_t szMant = (size_t)m * nstream * S.halfN * sizeof(int32_t), szRes = (size_t)m * sizeof(int32_t);
-        MRC_TRY(s.up(h->inAux, offs.data(), (size_t)m * sizeof(int64_t)));
-        MRC_TRY(s.up(h->inAux2, resG.data(), szRes));
-        MRC_HIP(h, h->outA.reserve(szScale)); MRC_HIP(h, h->outB.reserve(szSw)); MRC_HIP(h, h->outC.reserve(szBand));
-        MRC_HIP(h, h->outD.reserve(szBand));  MRC_HIP(h, h->outE.reserve(szMant)); MRC_HIP(h, h->outF.reserve(szRes));
-        MRC_TRY(encode_core(h, S, m, h->inL.p, joint ? h->inR.p : nullptr, kSampleF64, 0, h->inAux.as<int64_t>(),
-                            h->inAux2.as<int32_t>(), h->outA.as<int32_t>(), h->outB.as<int32_t>(), h->outD.as<int32_t>(),
-                            h->outC.as<int32_t>(), h->outE.p, MRC_MANTISSA_I32, h->outF.as<int32_t>(), nullptr, h->ws,
-                            h->stream));
         tScale.resize((size_t)m * nsig); tSw.resize((size_t)m * S.nBands); tSf.resize((size_t)m * nstream * S.nBands);
         tBa.resize((size_t)m * nstream * S.nBands); tMant.resize((size_t)m * nstream * S.halfN); tRes.resize((size_t)m);
-        MRC_TRY(s.down(tScale.data(), h->outA, szScale));
-        if (joint) MRC_TRY(s.down(tSw.data(), h->outB, szSw));
-        MRC_TRY(s.down(tSf.data(), h->outC, szBand));
-        MRC_TRY(s.down(tBa.data(), h->outD, szBand));
-        MRC_TRY(s.down(tMant.data(), h->outE, szMant));
-        MRC_TRY(s.down(tRes.data(), h->outF, szRes));
-        MRC_HIP(h, hipStreamSynchronize(h->stream));
+        s.rewind(groupSlots);                               // (the previous group's finish() drained the stream)
+        const int64_t* dOffs = s.in(offs.data(), (size_t)m);
+        const int32_t* dResIn = s.in(resG.data(), (size_t)m);
+        int32_t* dScale = s.out(tScale.data(), tScale.size());
+        int32_t* dSw = s.out(joint ? tSw.data() : nullptr, tSw.size());
+        int32_t* dSf = s.out(tSf.data(), tSf.size());
+        int32_t* dBa = s.out(tBa.data(), tBa.size());
+        int32_t* dMant = s.out(tMant.data(), tMant.size());
+        int32_t* dResOut = s.out(tRes.data(), tRes.size());
+        MRC_TRY(s.ready());
+        MRC_TRY(encode_core(h, S, m, dL, dR, kSampleF64, 0, dOffs, dResIn, dScale, dSw, dBa, dSf, dMant, MRC_MANTISSA_I32,
+                            dResOut, nullptr, h->ws, h->stream));
+        MRC_TRY(s.finish());
         // scatter into the caller's fixed-stride arrays (rows beyond the shape's band / line count are zeroed)
         for (int64_t j = 0; j < m; ++j) {
             const int64_t i = idx[(size_t)j];
@@ -1021,40 +1000,34 @@ int mrc_quantize_uniform(mrc_handle* h, int64_t n, int n_bits, const double* x, 
     if (!h || n < 0 || !x || !code || n_bits < 1 || n_bits > 62)
         return fail(h, MRC_ERR_INVALID, "mrc_quantize_uniform: bad argument (1 <= n_bits <= 62)");
     if (n == 0) return MRC_OK;
-    MRC_HIP(h, hipSetDevice(h->device));
-    Staged s{h, h->stream};
-    MRC_TRY(s.up(h->inL, x, (size_t)n * sizeof(double)));
-    MRC_HIP(h, h->outG.reserve((size_t)n * sizeof(int64_t)));
-    MRC_HIP(h, launch_quantize_uniform(n, n_bits, h->inL.as<double>(), h->outG.as<long long>(), h->stream));
-    MRC_TRY(s.down(code, h->outG, (size_t)n * sizeof(int64_t)));
-    MRC_HIP(h, hipStreamSynchronize(h->stream));
-    return MRC_OK;
+    Stage s(h);
+    const double* dX = s.in(x, (size_t)n);
+    long long* dCode = s.out(reinterpret_cast<long long*>(code), (size_t)n);
+    MRC_TRY(s.ready());
+    MRC_HIP(h, launch_quantize_uniform(n, n_bits, dX, dCode, h->stream));
+    return s.finish();
 }
 
 int mrc_bark(mrc_handle* h, int64_t n, const double* f, double* z) {
     if (!h || n < 0 || !f || !z) return fail(h, MRC_ERR_INVALID, "mrc_bark: bad argument");
     if (n == 0) return MRC_OK;
-    MRC_HIP(h, hipSetDevice(h->device));
-    Staged s{h, h->stream};
-    MRC_TRY(s.up(h->inL, f, (size_t)n * sizeof(double)));
-    MRC_HIP(h, h->outG.reserve((size_t)n * sizeof(double)));
-    MRC_HIP(h, launch_bark(n, h->inL.as<double>(), h->outG.as<double>(), h->stream));
-    MRC_TRY(s.down(z, h->outG, (size_t)n * sizeof(double)));
-    MRC_HIP(h, hipStreamSynchronize(h->stream));
-    return MRC_OK;
+    Stage s(h);
+    const double* dF = s.in(f, (size_t)n);
+    double* dZ = s.out(z, (size_t)n);
+    MRC_TRY(s.ready());
+    MRC_HIP(h, launch_bark(n, dF, dZ, h->stream));
+    return s.finish();
 }
 
 int mrc_pcm_to_float(mrc_handle* h, int64_t n, const int16_t* pcm, double* out) {
     if (!h || n < 0 || !pcm || !out) return fail(h, MRC_ERR_INVALID, "mrc_pcm_to_float: bad argument");
     if (n == 0) return MRC_OK;
-    MRC_HIP(h, hipSetDevice(h->device));
-    Staged s{h, h->stream};
-    MRC_TRY(s.up(h->inL, pcm, (size_t)n * sizeof(int16_t)));
-    MRC_HIP(h, h->outG.reserve((size_t)n * sizeof(double)));
-    MRC_HIP(h, launch_pcm_to_float(n, h->inL.as<short>(), h->outG.as<double>(), h->stream));
-    MRC_TRY(s.down(out, h->outG, (size_t)n * sizeof(double)));
-    MRC_HIP(h, hipStreamSynchronize(h->stream));
-    return MRC_OK;
+    Stage s(h);
+    const int16_t* dPcm = s.in(pcm, (size_t)n);
+    double* dOut = s.out(out, (size_t)n);
+    MRC_TRY(s.ready());
+    MRC_HIP(h, launch_pcm_to_float(n, dPcm, dOut, h->stream));
+    return s.finish();
 }
 
 int mrc_window(mrc_handle* h, int64_t n, int a, int b, const double* blocks, double* out) {
@@ -1063,15 +1036,12 @@ int mrc_window(mrc_handle* h, int64_t n, int a, int b, const double* blocks, dou
     const HostShape* hs;
     MRC_TRY(get_shape(h, a, b, &hs));
     const DevShape& S = hs->dev;
-    MRC_HIP(h, hipSetDevice(h->device));
-    Staged s{h, h->stream};
-    const size_t bytes = (size_t)n * S.N * sizeof(double);
-    MRC_TRY(s.up(h->inL, blocks, bytes));
-    MRC_HIP(h, h->outG.reserve(bytes));
-    MRC_HIP(h, launch_window(S, n, h->inL.as<double>(), h->outG.as<double>(), h->stream));
-    MRC_TRY(s.down(out, h->outG, bytes));
-    MRC_HIP(h, hipStreamSynchronize(h->stream));
-    return MRC_OK;
+    Stage s(h);
+    const double* dBlocks = s.in(blocks, (size_t)n * S.N);
+    double* dOut = s.out(out, (size_t)n * S.N);
+    MRC_TRY(s.ready());
+    MRC_HIP(h, launch_window(S, n, dBlocks, dOut, h->stream));
+    return s.finish();
 }
 
 int mrc_mdct(mrc_handle* h, int64_t n, int a, int b, const double* blocks, int apply_window, double* lines,
@@ -1081,17 +1051,13 @@ int mrc_mdct(mrc_handle* h, int64_t n, int a, int b, const double* blocks, int a
     const HostShape* hs;
     MRC_TRY(get_shape(h, a, b, &hs));
     const DevShape& S = hs->dev;
-    MRC_HIP(h, hipSetDevice(h->device));
-    Staged s{h, h->stream};
-    MRC_TRY(s.up(h->inL, blocks, (size_t)n * S.N * sizeof(double)));
-    const size_t szLines = (size_t)n * S.halfN * sizeof(double), szScale = (size_t)n * sizeof(int32_t);
-    MRC_HIP(h, h->outG.reserve(szLines)); MRC_HIP(h, h->outA.reserve(szScale));
-    MRC_HIP(h, launch_mdct(S, n, h->inL.as<double>(), nullptr, kSampleF64, S.N, nullptr, apply_window != 0, h->outG.as<double>(),
-                           h->outA.as<int>(), h->stream));
-    MRC_TRY(s.down(lines, h->outG, szLines));
-    MRC_TRY(s.down(overall_scale, h->outA, szScale));
-    MRC_HIP(h, hipStreamSynchronize(h->stream));
-    return MRC_OK;
+    Stage s(h);
+    const double* dBlocks = s.in(blocks, (size_t)n * S.N);
+    double* dLines = s.out(lines, (size_t)n * S.halfN);
+    int32_t* dScale = s.out(overall_scale, (size_t)n);
+    MRC_TRY(s.ready());
+    MRC_HIP(h, launch_mdct(S, n, dBlocks, nullptr, kSampleF64, S.N, nullptr, apply_window != 0, dLines, dScale, h->stream));
+    return s.finish();
 }
 
 int mrc_smr(mrc_handle* h, int64_t n, int a, int b, const double* blocks, const double* scaled_lines,
@@ -1102,28 +1068,27 @@ int mrc_smr(mrc_handle* h, int64_t n, int a, int b, const double* blocks, const 
     const HostShape* hs;
     MRC_TRY(get_shape(h, a, b, &hs));
     const DevShape& S = hs->dev;
-    MRC_HIP(h, hipSetDevice(h->device));
-    Staged s{h, h->stream};
-    MRC_TRY(s.up(h->inL, blocks, (size_t)n * S.N * sizeof(double)));
-    const size_t szLines = (size_t)n * S.halfN * sizeof(double), szScale = (size_t)n * sizeof(int32_t);
-    const size_t szSmr = (size_t)n * S.nBands * sizeof(double);
-    MRC_HIP(h, h->outG.reserve(szLines)); MRC_HIP(h, h->outA.reserve(szScale));
-    MRC_HIP(h, h->outC.reserve(szSmr)); MRC_HIP(h, h->outE.reserve(szLines));
-    if (scaled_lines) {
-        MRC_TRY(s.up(h->inR, scaled_lines, szLines));
-        MRC_TRY(s.up(h->outA, overall_scale, szScale));
-        MRC_HIP(h, launch_unscale(n, S.halfN, h->inR.as<double>(), h->outA.as<int>(), h->outG.as<double>(), h->stream));
+    Stage s(h);
+    const size_t nLines = (size_t)n * S.halfN;
+    const double* dBlocks = s.in(blocks, (size_t)n * S.N);
+    double* dLines = s.out<double>(nullptr, nLines);
+    double* dSmr = s.out(smr, (size_t)n * S.nBands);
+    double* dThresh = thresh ? s.out(thresh, nLines) : nullptr;
+    const int32_t* dScale;
+    if (scaled_lines) {                                     // the caller's lines and scales, unscaled
+        const double* dScaled = s.in(scaled_lines, nLines);
+        dScale = s.in(overall_scale, (size_t)n);
+        MRC_TRY(s.ready());
+        MRC_HIP(h, launch_unscale(n, S.halfN, dScaled, dScale, dLines, h->stream));
     } else {
-        MRC_HIP(h, launch_mdct(S, n, h->inL.as<double>(), nullptr, kSampleF64, S.N, nullptr, true, h->outG.as<double>(),
-                               h->outA.as<int>(), h->stream));
+        int32_t* dMdctScale = s.out<int32_t>(nullptr, (size_t)n);
+        MRC_TRY(s.ready());
+        MRC_HIP(h, launch_mdct(S, n, dBlocks, nullptr, kSampleF64, S.N, nullptr, true, dLines, dMdctScale, h->stream));
+        dScale = dMdctScale;
     }
-    MRC_HIP(h, launch_smr(S, n, h->inL.as<double>(), nullptr, kSampleF64, S.N, nullptr, h->outG.as<double>(), h->outA.as<int>(),
-                          h->outC.as<double>(), thresh ? h->outE.as<double>() : nullptr, nullptr, nullptr, h->exactSpread,
-                          h->stream));
-    MRC_TRY(s.down(smr, h->outC, szSmr));
-    if (thresh) MRC_TRY(s.down(thresh, h->outE, szLines));
-    MRC_HIP(h, hipStreamSynchronize(h->stream));
-    return MRC_OK;
+    MRC_HIP(h, launch_smr(S, n, dBlocks, nullptr, kSampleF64, S.N, nullptr, dLines, dScale, dSmr, dThresh, nullptr, nullptr,
+                          h->exactSpread, h->stream));
+    return s.finish();
 }
 
 static int bitalloc_host(mrc_handle* h, int64_t n_cases, int n_bands, int max_mant_bits, const int32_t* n_lines,
@@ -1131,23 +1096,18 @@ static int bitalloc_host(mrc_handle* h, int64_t n_cases, int n_bands, int max_ma
     if (!h || !n_lines || !budget || !smr || !bits || !bits_left || n_cases < 0 || n_bands < 1 || n_bands > 64)
         return fail(h, MRC_ERR_INVALID, "mrc_bitalloc: bad argument (1 <= n_bands <= 64)");
     if (n_cases == 0) return MRC_OK;
-    MRC_HIP(h, hipSetDevice(h->device));
-    Staged s{h, h->stream};
-    MRC_TRY(s.up(h->inAux, n_lines, (size_t)n_bands * sizeof(int32_t)));
-    MRC_TRY(s.up(h->inAux2, budget, (size_t)n_cases * sizeof(double)));
-    MRC_TRY(s.up(h->inL, smr, (size_t)n_cases * n_bands * sizeof(double)));
-    const size_t szBits = (size_t)n_cases * n_bands * sizeof(int32_t), szLeft = (size_t)n_cases * sizeof(int32_t);
-    const size_t szSmr = (size_t)n_cases * n_bands * sizeof(double);
-    MRC_HIP(h, h->outC.reserve(szBits)); MRC_HIP(h, h->outF.reserve(szLeft));
-    if (smr_after) MRC_HIP(h, h->outG.reserve(szSmr));
-    MRC_HIP(h, launch_bitalloc_cases(n_cases, n_bands, max_mant_bits, h->inAux.as<int>(), h->inAux2.as<double>(),
-                                     h->inL.as<double>(), h->outC.as<int>(), h->outF.as<int>(),
-                                     smr_after ? h->outG.as<double>() : nullptr, h->stream));
-    MRC_TRY(s.down(bits, h->outC, szBits));
-    MRC_TRY(s.down(bits_left, h->outF, szLeft));
-    if (smr_after) MRC_TRY(s.down(smr_after, h->outG, szSmr));
-    MRC_HIP(h, hipStreamSynchronize(h->stream));
-    return MRC_OK;
+    Stage s(h);
+    const size_t nSmr = (size_t)n_cases * n_bands;
+    const int32_t* dLines = s.in(n_lines, (size_t)n_bands);
+    const double* dBudget = s.in(budget, (size_t)n_cases);
+    const double* dSmr = s.in(smr, nSmr);
+    int32_t* dBits = s.out(bits, nSmr);
+    int32_t* dLeft = s.out(bits_left, (size_t)n_cases);
+    double* dSmrAfter = smr_after ? s.out(smr_after, nSmr) : nullptr;
+    MRC_TRY(s.ready());
+    MRC_HIP(h, launch_bitalloc_cases(n_cases, n_bands, max_mant_bits, dLines, dBudget, dSmr, dBits, dLeft, dSmrAfter,
+                                     h->stream));
+    return s.finish();
 }
 
 int mrc_bitalloc(mrc_handle* h, int64_t n_cases, int n_bands, int max_mant_bits, const int32_t* n_lines,
@@ -1165,15 +1125,13 @@ int mrc_scale_factor(mrc_handle* h, int64_t n, int n_scale_bits, const double* v
     if (!h || !v || !n_mant_bits || !scale || n < 0 || n_scale_bits < 1 || n_scale_bits > 4)
         return fail(h, MRC_ERR_INVALID, "mrc_scale_factor: bad argument");
     if (n == 0) return MRC_OK;
-    MRC_HIP(h, hipSetDevice(h->device));
-    Staged s{h, h->stream};
-    MRC_TRY(s.up(h->inL, v, (size_t)n * sizeof(double)));
-    MRC_TRY(s.up(h->inAux, n_mant_bits, (size_t)n * sizeof(int32_t)));
-    MRC_HIP(h, h->outC.reserve((size_t)n * sizeof(int32_t)));
-    MRC_HIP(h, launch_scale_factor(n, n_scale_bits, h->inL.as<double>(), h->inAux.as<int>(), h->outC.as<int>(), h->stream));
-    MRC_TRY(s.down(scale, h->outC, (size_t)n * sizeof(int32_t)));
-    MRC_HIP(h, hipStreamSynchronize(h->stream));
-    return MRC_OK;
+    Stage s(h);
+    const double* dV = s.in(v, (size_t)n);
+    const int32_t* dBits = s.in(n_mant_bits, (size_t)n);
+    int32_t* dScale = s.out(scale, (size_t)n);
+    MRC_TRY(s.ready());
+    MRC_HIP(h, launch_scale_factor(n, n_scale_bits, dV, dBits, dScale, h->stream));
+    return s.finish();
 }
 
 int mrc_mantissa(mrc_handle* h, int64_t n, int n_scale_bits, const double* x, const int32_t* scale,
@@ -1181,17 +1139,14 @@ int mrc_mantissa(mrc_handle* h, int64_t n, int n_scale_bits, const double* x, co
     if (!h || !x || !scale || !n_mant_bits || !mant || n < 0 || n_scale_bits < 1 || n_scale_bits > 4)
         return fail(h, MRC_ERR_INVALID, "mrc_mantissa: bad argument");
     if (n == 0) return MRC_OK;
-    MRC_HIP(h, hipSetDevice(h->device));
-    Staged s{h, h->stream};
-    MRC_TRY(s.up(h->inL, x, (size_t)n * sizeof(double)));
-    MRC_TRY(s.up(h->inAux, scale, (size_t)n * sizeof(int32_t)));
-    MRC_TRY(s.up(h->inAux2, n_mant_bits, (size_t)n * sizeof(int32_t)));
-    MRC_HIP(h, h->outC.reserve((size_t)n * sizeof(int32_t)));
-    MRC_HIP(h, launch_mantissa(n, n_scale_bits, h->inL.as<double>(), h->inAux.as<int>(), h->inAux2.as<int>(),
-                               h->outC.as<int>(), h->stream));
-    MRC_TRY(s.down(mant, h->outC, (size_t)n * sizeof(int32_t)));
-    MRC_HIP(h, hipStreamSynchronize(h->stream));
-    return MRC_OK;
+    Stage s(h);
+    const double* dX = s.in(x, (size_t)n);
+    const int32_t* dScale = s.in(scale, (size_t)n);
+    const int32_t* dBits = s.in(n_mant_bits, (size_t)n);
+    int32_t* dMant = s.out(mant, (size_t)n);
+    MRC_TRY(s.ready());
+    MRC_HIP(h, launch_mantissa(n, n_scale_bits, dX, dScale, dBits, dMant, h->stream));
+    return s.finish();
 }
 
 int mrc_decode(mrc_handle* h, int64_t n, int a, int b, int n_streams, const int32_t* overall_scale,
@@ -1204,41 +1159,33 @@ int mrc_decode(mrc_handle* h, int64_t n, int a, int b, int n_streams, const int3
     const HostShape* hs;
     MRC_TRY(get_shape(h, a, b, &hs));
     const DevShape& S = hs->dev;
-    MRC_HIP(h, hipSetDevice(h->device));
-    std::vector<int64_t> offs((size_t)n);                   // (declared before `s`: alive until its drain)
-    Staged s{h, h->stream};
-    const size_t nOs = n_streams == 2 ? 4 : 1;
-    const size_t szBand = (size_t)n * n_streams * S.nBands * sizeof(int32_t), szM = (size_t)n * n_streams * S.halfN * sizeof(int32_t);
-    const size_t szOut = (size_t)n * n_streams * S.N * sizeof(double);
-    MRC_TRY(s.up(h->inAux, overall_scale, (size_t)n * nOs * sizeof(int32_t)));
-    MRC_TRY(s.up(h->inAux2, scale_factor, szBand));
-    MRC_TRY(s.up(h->inAux3, bit_alloc, szBand));
-    MRC_TRY(s.up(h->inL, mantissa, szM));
-    if (n_streams == 2) MRC_TRY(s.up(h->inR, ms_switch, (size_t)n * S.nBands * sizeof(int32_t)));
     // block i, channel c -> out[(i * n_streams + c) * N]: one plane, per-channel base pointers and a common offset
+    std::vector<int64_t> offs((size_t)n);                   // (declared before `s`: alive until its drain)
     for (int64_t i = 0; i < n; ++i) offs[(size_t)i] = i * n_streams * (int64_t)S.N;
-    MRC_TRY(s.up(h->outA, offs.data(), (size_t)n * sizeof(int64_t)));
-    MRC_HIP(h, h->outG.reserve(szOut));
-    MRC_HIP(h, hipMemsetAsync(h->outG.p, 0, szOut, h->stream));
-    MRC_HIP(h, launch_decode(S, n, n_streams, h->inAux.as<int>(), n_streams == 2 ? h->inR.as<int>() : nullptr,
-                             h->inAux2.as<int>(), h->inAux3.as<int>(), h->inL.as<int>(), h->outA.as<int64_t>(),
-                             h->outG.as<double>(), h->outG.as<double>() + S.N, h->stream));
-    MRC_TRY(s.down(out, h->outG, szOut));
-    MRC_HIP(h, hipStreamSynchronize(h->stream));
-    return MRC_OK;
+    Stage s(h);
+    const size_t nBand = (size_t)n * n_streams * S.nBands, nOut = (size_t)n * n_streams * S.N;
+    const int32_t* dScale = s.in(overall_scale, (size_t)n * (n_streams == 2 ? 4 : 1));
+    const int32_t* dSf = s.in(scale_factor, nBand);
+    const int32_t* dBa = s.in(bit_alloc, nBand);
+    const int32_t* dMant = s.in(mantissa, (size_t)n * n_streams * S.halfN);
+    const int32_t* dSw = n_streams == 2 ? s.in(ms_switch, (size_t)n * S.nBands) : nullptr;
+    const int64_t* dOffs = s.in(offs.data(), (size_t)n);
+    double* dOut = s.out(out, nOut);
+    MRC_TRY(s.ready());
+    MRC_HIP(h, hipMemsetAsync(dOut, 0, nOut * sizeof(double), h->stream));
+    MRC_HIP(h, launch_decode(S, n, n_streams, dScale, dSw, dSf, dBa, dMant, dOffs, dOut, dOut + S.N, h->stream));
+    return s.finish();
 }
 
 int mrc_pcm16(mrc_handle* h, int64_t n, const double* x, int16_t* out) {
     if (!h || n < 0 || !x || !out) return fail(h, MRC_ERR_INVALID, "mrc_pcm16: bad argument");
     if (n == 0) return MRC_OK;
-    MRC_HIP(h, hipSetDevice(h->device));
-    Staged s{h, h->stream};
-    MRC_TRY(s.up(h->inL, x, (size_t)n * sizeof(double)));
-    MRC_HIP(h, h->outA.reserve((size_t)n * sizeof(int16_t)));
-    MRC_HIP(h, launch_pcm16(n, h->inL.as<double>(), h->outA.as<short>(), h->stream));
-    MRC_TRY(s.down(out, h->outA, (size_t)n * sizeof(int16_t)));
-    MRC_HIP(h, hipStreamSynchronize(h->stream));
-    return MRC_OK;
+    Stage s(h);
+    const double* dX = s.in(x, (size_t)n);
+    int16_t* dOut = s.out(out, (size_t)n);
+    MRC_TRY(s.ready());
+    MRC_HIP(h, launch_pcm16(n, dX, dOut, h->stream));
+    return s.finish();
 }
 
 int mrc_huffman_gain(mrc_handle* h, int64_t n, int a, int b, int n_streams, const int32_t* bit_alloc,
@@ -1249,19 +1196,14 @@ int mrc_huffman_gain(mrc_handle* h, int64_t n, int a, int b, int n_streams, cons
     const HostShape* hs;
     MRC_TRY(get_shape(h, a, b, &hs));
     const DevShape& S = hs->dev;
-    MRC_HIP(h, hipSetDevice(h->device));
-    Staged s{h, h->stream};
-    const size_t szBa = (size_t)n * n_streams * S.nBands * sizeof(int32_t);
-    const size_t szM = (size_t)n * n_streams * S.halfN * sizeof(int32_t), szOut = (size_t)n * n_streams * sizeof(int32_t);
-    MRC_TRY(s.up(h->inAux, bit_alloc, szBa));
-    MRC_TRY(s.up(h->inL, mantissa, szM));
-    MRC_HIP(h, h->outC.reserve(szOut)); MRC_HIP(h, h->outD.reserve(szOut));
-    MRC_HIP(h, launch_huffman_gain(S, n, n_streams, h->inAux.as<int>(), h->inL.as<int>(), nullptr, h->outC.as<int>(),
-                                   h->outD.as<int>(), nullptr, h->stream));
-    MRC_TRY(s.down(huff_table, h->outC, szOut));
-    MRC_TRY(s.down(bits_saved, h->outD, szOut));
-    MRC_HIP(h, hipStreamSynchronize(h->stream));
-    return MRC_OK;
+    Stage s(h);
+    const int32_t* dBa = s.in(bit_alloc, (size_t)n * n_streams * S.nBands);
+    const int32_t* dMant = s.in(mantissa, (size_t)n * n_streams * S.halfN);
+    int32_t* dTable = s.out(huff_table, (size_t)n * n_streams);
+    int32_t* dSaved = s.out(bits_saved, (size_t)n * n_streams);
+    MRC_TRY(s.ready());
+    MRC_HIP(h, launch_huffman_gain(S, n, n_streams, dBa, dMant, nullptr, dTable, dSaved, nullptr, h->stream));
+    return s.finish();
 }
 
 // every section behind the first has b0 == 1.0 exactly (scipy's tf2sos / zpk2sos put the gain into the first section)
@@ -1281,17 +1223,14 @@ int mrc_transient_peaks_ex(mrc_handle* h, int64_t n_hops, int n_channels, int n_
     if (hop % nShort != 0) return fail(h, MRC_ERR_INVALID, "mrc_transient_peaks: n_mdct_lines must be a multiple of n_short");
     const int64_t chStride = (n_hops + 1) * (int64_t)hop;
     const size_t smp = sample_format == MRC_SAMPLES_PCM16 ? sizeof(int16_t) : sizeof(double);
-    MRC_HIP(h, hipSetDevice(h->device));
-    Staged s{h, h->stream};
-    MRC_TRY(s.up(h->inL, streams, (size_t)n_channels * chStride * smp));
-    MRC_TRY(s.up(h->inAux3, sos, (size_t)n_sections * 6 * sizeof(double)));
-    const size_t outBytes = (size_t)n_hops * n_channels * (hop / nShort + 1) * sizeof(double);
-    MRC_HIP(h, h->outG.reserve(outBytes));
-    MRC_HIP(h, launch_transient_peaks(n_hops, n_channels, hop, nShort, n_sections, h->inAux3.as<double>(),
-                                      sos_unit_b0(sos, n_sections), h->inL.p, sample_format, chStride, h->outG.as<double>(), h->stream));
-    MRC_TRY(s.down(peaks, h->outG, outBytes));
-    MRC_HIP(h, hipStreamSynchronize(h->stream));
-    return MRC_OK;
+    Stage s(h);
+    const char* dStreams = s.in(static_cast<const char*>(streams), (size_t)n_channels * chStride * smp);
+    const double* dSos = s.in(sos, (size_t)n_sections * 6);
+    double* dPeaks = s.out(peaks, (size_t)n_hops * n_channels * (hop / nShort + 1));
+    MRC_TRY(s.ready());
+    MRC_HIP(h, launch_transient_peaks(n_hops, n_channels, hop, nShort, n_sections, dSos, sos_unit_b0(sos, n_sections),
+                                      dStreams, sample_format, chStride, dPeaks, h->stream));
+    return s.finish();
 }
 
 int mrc_transient_peaks(mrc_handle* h, int64_t n_hops, int n_channels, int n_sections, const double* sos,
@@ -1311,10 +1250,10 @@ int mrc_dev_transient_peaks(mrc_handle* h, int64_t n_hops, int n_channels, int n
     MRC_HIP(h, hipSetDevice(h->device));
     hipStream_t st = pick_stream(h, stream);
     // (the filter coefficients are 6 doubles per section: staged in the handle; the copy is ordered on `st`)
-    MRC_HIP(h, h->inAux3.reserve((size_t)n_sections * 6 * sizeof(double)));
-    MRC_HIP(h, hipMemcpyAsync(h->inAux3.p, sos, (size_t)n_sections * 6 * sizeof(double), hipMemcpyHostToDevice, st));
+    MRC_HIP(h, h->sos.reserve((size_t)n_sections * 6 * sizeof(double)));
+    MRC_HIP(h, hipMemcpyAsync(h->sos.p, sos, (size_t)n_sections * 6 * sizeof(double), hipMemcpyHostToDevice, st));
     MRC_HIP(h, hipStreamSynchronize(st));                    // `sos` may be a temporary of the caller
-    MRC_HIP(h, launch_transient_peaks(n_hops, n_channels, hop, nShort, n_sections, h->inAux3.as<double>(),
+    MRC_HIP(h, launch_transient_peaks(n_hops, n_channels, hop, nShort, n_sections, h->sos.as<double>(),
                                       sos_unit_b0(sos, n_sections), streams, sample_format, channel_stride, peaks, st));
     return MRC_OK;
 }
@@ -1324,19 +1263,15 @@ int mrc_stereo_masking_factor(mrc_handle* h, int64_t n, const double* mid_thresh
     if (!h || !mid_thresh || !side_thresh || !z || !out_mid || !out_side || n < 0)
         return fail(h, MRC_ERR_INVALID, "mrc_stereo_masking_factor: bad argument");
     if (n == 0) return MRC_OK;
-    MRC_HIP(h, hipSetDevice(h->device));
-    Staged s{h, h->stream};
-    const size_t bytes = (size_t)n * sizeof(double);
-    MRC_TRY(s.up(h->inL, mid_thresh, bytes));
-    MRC_TRY(s.up(h->inR, side_thresh, bytes));
-    MRC_TRY(s.up(h->inAux3, z, bytes));
-    MRC_HIP(h, h->outG.reserve(bytes)); MRC_HIP(h, h->outE.reserve(bytes));
-    MRC_HIP(h, launch_stereo_masking(n, h->inL.as<double>(), h->inR.as<double>(), h->inAux3.as<double>(),
-                                     h->outG.as<double>(), h->outE.as<double>(), h->stream));
-    MRC_TRY(s.down(out_mid, h->outG, bytes));
-    MRC_TRY(s.down(out_side, h->outE, bytes));
-    MRC_HIP(h, hipStreamSynchronize(h->stream));
-    return MRC_OK;
+    Stage s(h);
+    const double* dMid = s.in(mid_thresh, (size_t)n);
+    const double* dSide = s.in(side_thresh, (size_t)n);
+    const double* dZ = s.in(z, (size_t)n);
+    double* dOutMid = s.out(out_mid, (size_t)n);
+    double* dOutSide = s.out(out_side, (size_t)n);
+    MRC_TRY(s.ready());
+    MRC_HIP(h, launch_stereo_masking(n, dMid, dSide, dZ, dOutMid, dOutSide, h->stream));
+    return s.finish();
 }
 
 int mrc_ms_switch(mrc_handle* h, int64_t n_blocks, int n_bands, const int32_t* n_lines, const double* lines_left,
@@ -1354,17 +1289,14 @@ int mrc_ms_switch(mrc_handle* h, int64_t n_blocks, int n_bands, const int32_t* n
     int nLeaves = 0, nInternal = 0;
     ms_plan(lo, cnt, &plan, &nLeaves, &nInternal);
     if (nLeaves + nInternal > 64) return fail(h, MRC_ERR_INVALID, "mrc_ms_switch: band table too fine (more than 64 summation nodes)");
-    MRC_HIP(h, hipSetDevice(h->device));
-    Staged s{h, h->stream};                                 // (plan, lo, cnt are declared before it: alive until its drain)
-    MRC_TRY(s.up(h->inAux, plan.data(), plan.size() * sizeof(int)));
-    MRC_TRY(s.up(h->inL, lines_left, (size_t)n_blocks * total * sizeof(double)));
-    MRC_TRY(s.up(h->inR, lines_right, (size_t)n_blocks * total * sizeof(double)));
-    MRC_HIP(h, h->outC.reserve((size_t)n_blocks * n_bands * sizeof(int32_t)));
-    MRC_HIP(h, launch_ms_switch(n_blocks, n_bands, nLeaves, nInternal, h->inAux.as<int>(), h->inL.as<double>(),
-                                h->inR.as<double>(), total, total, h->outC.as<int>(), h->stream));
-    MRC_TRY(s.down(ms_switch, h->outC, (size_t)n_blocks * n_bands * sizeof(int32_t)));
-    MRC_HIP(h, hipStreamSynchronize(h->stream));
-    return MRC_OK;
+    Stage s(h);                                             // (plan, lo, cnt are declared before it: alive until its drain)
+    const int* dPlan = s.in(plan.data(), plan.size());
+    const double* dL = s.in(lines_left, (size_t)n_blocks * total);
+    const double* dR = s.in(lines_right, (size_t)n_blocks * total);
+    int32_t* dSw = s.out(ms_switch, (size_t)n_blocks * n_bands);
+    MRC_TRY(s.ready());
+    MRC_HIP(h, launch_ms_switch(n_blocks, n_bands, nLeaves, nInternal, dPlan, dL, dR, total, total, dSw, h->stream));
+    return s.finish();
 }
 
 }  // extern "C"

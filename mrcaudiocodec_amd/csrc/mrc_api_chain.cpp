@@ -22,12 +22,35 @@
 
 using namespace mrc;
 
-namespace {
+namespace mrc {
 
-struct SyncGuard {                    // whichever way we leave: nothing queued still reads the host vectors declared before it
-    hipStream_t st;
-    ~SyncGuard() { if (st) (void)hipStreamSynchronize(st); }
-};
+const char* chain_shape_misfit(const DevShape& S, int nstream) {
+    if (nstream * S.nBands > 64 || S.maxMantBits < 2 || S.maxMantBits > 16 || (S.halfN & 3))
+        return "shape outside what the chained back end covers (<= 32 bands, 2..16 mantissa bits, lines a multiple of 4)";
+    if (nstream * S.halfN > kChainMaxLinesPerItem)
+        return "block too long for the chained back end (more than 2048 coded lines per block: n_mdct_lines <= 1024 in "
+               "joint stereo)";
+    return nullptr;
+}
+
+ChainGroupDev chain_group_desc(const HostShape& hs, int joint, const double* lines, const double* peak, const int* oscale,
+                               const int* ms, const unsigned* ev, const unsigned* pre, int* bitAlloc, int* scaleFactor,
+                               unsigned short* mant, int* table) {
+    const DevShape& S = hs.dev;
+    ChainGroupDev D{};
+    D.joint = joint; D.nb = S.nBands; D.nstream = joint ? 2 : 1; D.nTot = D.nstream * S.nBands; D.M = S.halfN;
+    D.K = S.maxMantBits - 1; D.nEv = (int)chain_events_per_block(S, joint); D.nScaleBits = S.nScaleBits;
+    for (int v : hs.bandN) if (v > D.maxN) D.maxN = v;
+    D.budgetMono = S.budgetMono; D.budgetJointPre = S.budgetJointPre; D.blkswA = S.blkswA; D.blkswB = S.blkswB;
+    D.bandOfLine = S.bandOfLine; D.bandN = S.bandN;
+    D.lines = lines; D.peak = peak; D.oscale = oscale; D.ms = ms; D.ev = ev; D.pre = pre;
+    D.bitAlloc = bitAlloc; D.scaleFactor = scaleFactor; D.mant = mant; D.table = table;
+    return D;
+}
+
+}  // namespace mrc
+
+namespace {
 
 template <class T>
 int upload(mrc_handle* h, DevBuf& buf, const std::vector<T>& v, hipStream_t st) {
@@ -108,13 +131,8 @@ int chained_core(mrc_handle* h, int64_t n_streams, const void* pcm_left, const v
     for (int g = 0; g < nGroups; ++g) {
         MRC_TRY(get_shape(h, shapeA[g], shapeB[g], &hs[g]));
         const DevShape& S = hs[g]->dev;
-        const int nstream = (g == 4 || !stereo) ? 1 : 2, nTot = nstream * S.nBands;
-        if (nTot > 64 || S.maxMantBits < 2 || S.maxMantBits > 16 || (S.halfN & 3))
-            return fail(h, MRC_ERR_INVALID, "mrc_encode_chained: shape outside what the chained back end covers "
-                                            "(<= 32 bands, 2..16 mantissa bits, lines a multiple of 4)");
-        if (nstream * S.halfN > kChainMaxLinesPerItem)
-            return fail(h, MRC_ERR_INVALID, "mrc_encode_chained: block too long for the chained back end (more than 2048 "
-                                            "coded lines per block: n_mdct_lines <= 1024 in joint stereo)");
+        if (const char* why = chain_shape_misfit(S, (g == 4 || !stereo) ? 1 : 2))
+            return fail(h, MRC_ERR_INVALID, std::string("mrc_encode_chained: ") + why);
     }
     // ---- the schedule, pass 1: validate, sort the blocks into their shape groups (the offsets phase A needs).  The rest of
     // the schedule (items in file order, chunk maps, headers) is only needed by the serial scan and the packer: it is built
@@ -160,7 +178,7 @@ int chained_core(mrc_handle* h, int64_t n_streams, const void* pcm_left, const v
     std::vector<uint8_t> hdr;
     long long total = 0;
     int bad = 0;
-    SyncGuard guard{st};
+    DrainGuard guard{{st}};
     MRC_HIP(h, hipEventRecord(C.evT[0], st));
     if (with_flush) {
         // the tail offsets ride in the offsets buffer of group 4 (its blocks are laid out explicitly, stride 2 L)
@@ -170,8 +188,7 @@ int chained_core(mrc_handle* h, int64_t n_streams, const void* pcm_left, const v
                                              C.g[4].offsets.as<long long>(), C.flushPcm.p, st));
     }
     // ---- phase A + prep, per block shape
-    ChainGroupDev desc[kChainGroups];
-    std::memset(desc, 0, sizeof(desc));
+    ChainGroupDev desc[kChainGroups] = {};
     int64_t count[kChainGroups] = {};
     for (int g = 0; g < nGroups; ++g) {
         const DevShape& S = hs[g]->dev;
@@ -204,18 +221,10 @@ int chained_core(mrc_handle* h, int64_t n_streams, const void* pcm_left, const v
                                          B.ev.as<unsigned>(), B.pre.as<unsigned>(),
                                          h->chainForceFallback ? 1 : 0, st));
         }
-        ChainGroupDev& D = desc[g];
-        D.joint = joint; D.nb = S.nBands; D.nTot = nTot; D.M = S.halfN; D.K = S.maxMantBits - 1; D.nEv = nEv;
-        D.nScaleBits = S.nScaleBits; D.nstream = nstream;
-        D.maxN = 0;
-        for (int v : hs[g]->bandN) if (v > D.maxN) D.maxN = v;
-        D.budgetMono = S.budgetMono; D.budgetJointPre = S.budgetJointPre; D.blkswA = S.blkswA; D.blkswB = S.blkswB;
-        D.bandOfLine = S.bandOfLine; D.bandN = S.bandN;
-        D.lines = B.lines.as<double>(); D.peak = B.peak.as<double>(); D.oscale = B.oscale.as<int32_t>();
-        D.ms = joint ? B.ms.as<int32_t>() : nullptr; D.ev = B.ev.as<unsigned>();
-        D.pre = B.pre.as<unsigned>();
-        D.bitAlloc = B.bitAlloc.as<int32_t>(); D.scaleFactor = B.scaleFactor.as<int32_t>();
-        D.mant = B.mant.as<unsigned short>(); D.table = B.table.as<int32_t>();
+        desc[g] = chain_group_desc(*hs[g], joint, B.lines.as<double>(), B.peak.as<double>(), B.oscale.as<int32_t>(),
+                                   joint ? B.ms.as<int32_t>() : nullptr, B.ev.as<unsigned>(), B.pre.as<unsigned>(),
+                                   B.bitAlloc.as<int32_t>(), B.scaleFactor.as<int32_t>(), B.mant.as<unsigned short>(),
+                                   B.table.as<int32_t>());
     }
     // ---- the schedule, pass 2 (the device is busy with phase A): items (group << 28 | index inside the group) per stream in
     // file order, the chunk of every item, the stream of every chunk, the chunks of every group
@@ -302,17 +311,14 @@ int chained_core(mrc_handle* h, int64_t n_streams, const void* pcm_left, const v
                                           h->sens.as<unsigned long long>(), nullptr, st));
         }
     // ---- pack: plan per shape, ONE prefix sum over the chunks in file order, write per shape
-    static const PackTables tables = [] { PackTables t; pack_tables(&t); return t; }();
+    const PackTables& tables = host_pack_tables();
     MRC_HIP(h, C.packWs.reserve(pack_workspace_bytes(nChunks)));
     const PackWs W = pack_ws_views(C.packWs.p, nChunks);
     MRC_HIP(h, hipMemsetAsync(W.errorFlag, 0, sizeof(int), st));
     PackParams P[kChainGroups];
     for (int g = 0; g < nGroups; ++g) {
         const int joint = desc[g].joint;
-        P[g].nch = joint ? 2 : 1; P[g].joint = joint; P[g].useHuffman = use_huffman ? 1 : 0;
-        P[g].nScaleBits = cfg.n_scale_bits; P[g].nMantSizeBits = cfg.n_mant_size_bits;
-        P[g].blkBitsA = cfg.blksw_bits_a; P[g].blkBitsB = cfg.blksw_bits_b;
-        P[g].bitA = (unsigned)(1 - shapeA[g] / cfg.n_mdct_lines); P[g].bitB = (unsigned)(1 - shapeB[g] / cfg.n_mdct_lines);
+        P[g] = pack_params(cfg, shapeA[g], shapeB[g], joint ? 2 : 1, joint, use_huffman);
         if (!count[g]) continue;
         ChainGroupBufs& B = C.g[g];
         const int64_t nBlk = count[g];                              // (a mono item is a one-channel block)
@@ -515,7 +521,7 @@ int mrc_encode_chained_stream_pac(mrc_handle* h, int64_t n_streams, const void* 
     const size_t pcmBytes = (size_t)n_streams * stream_stride * (sample_format == MRC_SAMPLES_PCM16 ? sizeof(int16_t) : sizeof(double));
     MRC_HIP(h, C.pcmL.reserve(pcmBytes ? pcmBytes : 1));
     if (pcm_right) MRC_HIP(h, C.pcmR.reserve(pcmBytes ? pcmBytes : 1));      // (mono streams: no right channel)
-    SyncGuard guard{h->stream};
+    DrainGuard guard{{h->stream}};
     if (pcmBytes) {
         MRC_HIP(h, hipMemcpyAsync(C.pcmL.p, pcm_left, pcmBytes, hipMemcpyHostToDevice, h->stream));
         if (pcm_right) MRC_HIP(h, hipMemcpyAsync(C.pcmR.p, pcm_right, pcmBytes, hipMemcpyHostToDevice, h->stream));

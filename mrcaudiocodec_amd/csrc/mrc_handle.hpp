@@ -6,6 +6,7 @@
 #include <map>
 #include <string>
 #include <utility>
+#include <vector>
 
 namespace mrc {
 
@@ -39,6 +40,19 @@ struct PinnedBuf {
         return e;
     }
     void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
+};
+
+// encode_host with few blocks (the per-block seam): one device layout, one page-locked copy each way (see encode_host)
+struct SmallBatchBufs {
+    DevBuf layout;                   // inputs, scan descriptor, reservoirs and results of the call, back to back
+    DevBuf ev, pre;                  // chain_prep_kernel's grant events and the bits spent before each
+    DevBuf table;                    // the scan's table ids (all 15: no pricing)
+    PinnedBuf pinIn, pinOut;
+    void release() {
+        for (DevBuf* b : {&layout, &ev, &pre, &table}) b->release();
+        pinIn.release();
+        pinOut.release();
+    }
 };
 
 // intermediate results of one encode call (lines, SMRs, band peaks); one set per stream that encodes concurrently
@@ -134,9 +148,9 @@ struct mrc_handle {
                                      //     the runtime multiplexes streams onto 4 hardware queues by default -- with the
                                      //     null stream and `stream` that is exactly four; a fifth would share a queue with
                                      //     one of the others and serialise with it: 10 000 instead of 19 000 Msamples/s)
-    // staging of the host entry points
-    mrc::DevBuf inL, inR, inAux, inAux2, inAux3, outA, outB, outC, outD, outE, outF, outG;
-    mrc::PinnedBuf pinIn, pinOut;    // ... of calls with few blocks (the per-block seam): one H2D, one D2H
+    std::vector<mrc::DevBuf> stage;  // staging of the host entry points: handed out in order by a Stage (mrc_api.cpp)
+    mrc::SmallBatchBufs smallBatch;  // ... except encode_host with few blocks
+    mrc::DevBuf sos;                 // mrc_dev_transient_peaks: the filter coefficients
     mrc::DevBuf packWs;              // mrc_dev_pack_blocks: chunk sizes / positions / (table ids)
     int64_t packLastChunks = 0, packLastCap = 0;   // ... of the most recent call (mrc_dev_pack_status)
     mrc::ChainBufs chain;            // mrc_encode_chained_*: see mrc_api_chain.cpp
@@ -179,6 +193,13 @@ inline int hip_fail(mrc_handle* h, hipError_t e, const char* what) {
         if (rc_ != MRC_OK) return rc_; \
     } while (0)
 
+// Whichever way a function is left, nothing it queued on these streams still touches the caller's memory or the host
+// temporaries declared before the guard.  (Null entries are skipped.)
+struct DrainGuard {
+    hipStream_t st[3];
+    ~DrainGuard() { for (hipStream_t s : st) if (s) (void)hipStreamSynchronize(s); }
+};
+
 // every entry point that launches comes through here first: the launches, the tables and the caller's pointers all
 // belong to the handle's device, whatever the calling thread's current device was
 int get_shape(mrc_handle* h, int a, int b, const HostShape** out);
@@ -187,6 +208,29 @@ inline bool all_bands_non_empty(const HostShape& hs) {
     return true;
 }
 inline hipStream_t pick_stream(mrc_handle* h, void* stream) { return stream ? (hipStream_t)stream : h->stream; }
+
+// the device packer's settings for blocks of shape (a, b)
+inline PackParams pack_params(const mrc_config& cfg, int a, int b, int nch, int joint, int use_huffman) {
+    PackParams P;
+    P.nch = nch; P.joint = joint ? 1 : 0; P.useHuffman = use_huffman ? 1 : 0;
+    P.nScaleBits = cfg.n_scale_bits; P.nMantSizeBits = cfg.n_mant_size_bits;
+    P.blkBitsA = cfg.blksw_bits_a; P.blkBitsB = cfg.blksw_bits_b;
+    P.bitA = (unsigned)(1 - a / cfg.n_mdct_lines); P.bitB = (unsigned)(1 - b / cfg.n_mdct_lines);   // py2 int division
+    return P;
+}
+inline const PackTables& host_pack_tables() {
+    static const PackTables tables = [] { PackTables t; pack_tables(&t); return t; }();
+    return tables;
+}
+
+// The chained back end (chain_prep_kernel + chain_phase_b_kernel), defined in mrc_api_chain.cpp.  Its scan covers <= 64
+// coded bands, 2..16 mantissa bits and lines in units of four, at most kChainMaxLinesPerItem of them per block:
+// chain_shape_misfit returns null when blocks of S with `nstream` channels fit, else which limit they break.
+const char* chain_shape_misfit(const DevShape& S, int nstream);
+// the scan's view of one block-shape group (joint: two channels with an M/S switch, else one channel)
+ChainGroupDev chain_group_desc(const HostShape& hs, int joint, const double* lines, const double* peak, const int* oscale,
+                               const int* ms, const unsigned* ev, const unsigned* pre, int* bitAlloc, int* scaleFactor,
+                               unsigned short* mant, int* table);
 
 // phase A of the per-block path (windowed MDCT + overall scale -> [M/S switch] -> SMRs and per-band peaks), defined in
 // mrc_api.cpp beside encode_core, which it is the first half of
