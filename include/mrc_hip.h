@@ -404,6 +404,47 @@ int mrc_dev_encode_chained_pac(mrc_handle* h, int64_t n_streams, const void* pcm
                                int32_t* reservoir_out, int32_t* reservoir_trace, int64_t* total_bytes, void* stream);
 int mrc_get_chain_ms(mrc_handle* h, double* ms /*[4]*/);
 
+/* ---- rate ladder: one source, several bit rates, one chained call ---------------------------------------------------
+ * mrc_encode_chained_ladder_pac encodes the streams of mrc_encode_chained_stream_pac at n_rates target bit rates at once.
+ * Output r is byte for byte what mrc_encode_chained_stream_pac writes on a handle whose config is this one's with
+ * target_bits_per_sample = target_bits_per_sample[r]: the bytes, the offsets, the reservoirs and the trace, for mono
+ * (pcm_right == NULL) and stereo streams, with and without Huffman coding or Close()'s flush, from PCM16 or F64 samples.
+ * Nothing the transform, the psychoacoustic model, the M/S switch, the grant-event order or the block shapes compute
+ * depends on the rate -- only the bit budget does (codecThem.py:299-306, 381-388) -- so all of that runs ONCE, and the
+ * serial scan runs as one workgroup per (rate, stream) side by side, each with its own budgets and reservoir.  The
+ * handle's own target_bits_per_sample is ignored and h->cfg is never changed.
+ *   n_rates in 1..MRC_MAX_RATES; target_bits_per_sample [n_rates], each finite and in (0, 64].
+ *   reservoir_in (NULL: zeros) and reservoir_out (NULL) [n_rates][n_streams]: the reservoir of every (rate, stream).
+ *   out [n_rates]: rate r's bytes go to out[r] [out_cap[r]]; size each with mrc_chain_out_bound_ex (the bound does not
+ *     depend on the rate).  If any buffer is too small the call returns MRC_ERR_NOMEM with total_bytes[r] filled for EVERY
+ *     rate (nothing is written past out_cap[r]); a second call with buffers of those sizes succeeds.
+ *   stream_byte_offset [n_rates][n_streams + 1], total_bytes [n_rates]; item_byte_offset (NULL or [n_rates][n_items + 1])
+ *     and reservoir_trace (NULL or [n_rates][n_items]) with n_items as for mrc_encode_chained_stream_pac.
+ *   MRC_ERR_INVALID, with a message naming the argument, for n_rates outside 1..MRC_MAX_RATES, a rate that is not finite
+ *   or outside (0, 64], a NULL out[r], and with MRC_OPT_SENSITIVITY on (the certificate covers one rate).
+ * Slabs (MRC_OPT_CHAIN_SLAB_BLOCKS) hold all rates; a ladder's slab takes fewer blocks, so that its device memory stays
+ * about that of a one-rate slab.  After a ladder call mrc_chain_fetch_output holds nothing (MRC_ERR_INVALID).
+ * mrc_dev_encode_chained_ladder_pac: the same with pcm_left / pcm_right and every out[r] in DEVICE memory (the array
+ * `out` itself and all other pointers host); it synchronises `stream` before it returns. */
+#define MRC_MAX_RATES 16
+int mrc_encode_chained_ladder_pac(mrc_handle* h, int n_rates, const double* target_bits_per_sample /*[n_rates]*/,
+                                  int64_t n_streams, const void* pcm_left, const void* pcm_right, int sample_format,
+                                  int64_t stream_stride, const int64_t* block_start, const int64_t* block_offset,
+                                  const int32_t* block_a, const int32_t* block_b,
+                                  const int32_t* reservoir_in /* NULL or [n_rates][n_streams] */, int use_huffman,
+                                  int with_flush, const uint32_t* num_samples, uint8_t* const* out /*[n_rates]*/,
+                                  const int64_t* out_cap /*[n_rates]*/, int64_t* stream_byte_offset /*[n_rates][n_streams + 1]*/,
+                                  int64_t* item_byte_offset /* NULL or [n_rates][n_items + 1] */,
+                                  int32_t* reservoir_out /* NULL or [n_rates][n_streams] */,
+                                  int32_t* reservoir_trace /* NULL or [n_rates][n_items] */, int64_t* total_bytes /*[n_rates]*/);
+int mrc_dev_encode_chained_ladder_pac(mrc_handle* h, int n_rates, const double* target_bits_per_sample, int64_t n_streams,
+                                      const void* pcm_left, const void* pcm_right, int sample_format, int64_t stream_stride,
+                                      const int64_t* block_start, const int64_t* block_offset, const int32_t* block_a,
+                                      const int32_t* block_b, const int32_t* reservoir_in, int use_huffman, int with_flush,
+                                      const uint32_t* num_samples, uint8_t* const* out, const int64_t* out_cap,
+                                      int64_t* stream_byte_offset, int64_t* item_byte_offset, int32_t* reservoir_out,
+                                      int32_t* reservoir_trace, int64_t* total_bytes, void* stream);
+
 /* ---- sensitivity certificate (round 4) ----
  * Bit-identity of the integers with the reference is an empirical, counted result: each of them is a floor / compare of
  * float64 values whose last bits differ between implementations (FFT factorisation, log10 / atan / 2^x), and it can only come
@@ -430,7 +471,7 @@ int mrc_get_chain_ms(mrc_handle* h, double* ms /*[4]*/);
 int mrc_get_sensitivity(mrc_handle* h, int64_t* counts /*[MRC_SENS_COUNT]*/, int reset);
 /* mrc_chain_fetch_output: the bytes of the LAST mrc_encode_chained_stream[_pcm16]_pac call on this handle, which stay in the
  * handle's device buffer until the next chained call: after MRC_ERR_NOMEM ("out_cap too small") a caller allocates
- * total_bytes and fetches them -- no second encode.  The offsets / reservoirs of that call were already returned by it. */
+ * total_bytes and fetches them -- no second encode.  After a rate ladder call nothing is held (MRC_ERR_INVALID).  The offsets / reservoirs of that call were already returned by it. */
 int mrc_chain_fetch_output(mrc_handle* h, uint8_t* out, int64_t out_cap, int64_t* total_bytes);
 
 /* ---- decode side ("next" row f-4: the reference's decoder, pacfileThem.py:130-585 + codecThem.py:30-134) ----

@@ -12,6 +12,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MRC_HIP_LIBRARY") or os.path.join(_HERE, "libmrc_hip.so")   # override: profiling builds
 
 MRC_MAX_BANDS = 32
+MRC_MAX_RATES = 16
+MRC_ERR_INVALID = -1
 MRC_ERR_NOMEM = -4
 # array arguments travel as plain addresses (c_void_p prototypes): numpy's typed `data_as` costs ~2.3 us per array, which
 # at thirteen arrays per call was a third of a one-block call through the drop-in seam; the names say what the C side expects
@@ -121,6 +123,12 @@ def _load():
                                                  _i32p, _i32p, _i32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
                                                  _i64p, _i64p, _i32p, _i32p, _i64p, C.c_void_p]),
         "mrc_get_chain_ms": (C.c_int, [H, _f64p]),
+        "mrc_encode_chained_ladder_pac": (C.c_int, [H, C.c_int, _f64p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64,
+                                                    _i64p, _i64p, _i32p, _i32p, _i32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                    _i64p, _i64p, _i64p, _i32p, _i32p, _i64p]),
+        "mrc_dev_encode_chained_ladder_pac": (C.c_int, [H, C.c_int, _f64p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64,
+                                                        _i64p, _i64p, _i32p, _i32p, _i32p, C.c_int, C.c_int, C.c_void_p,
+                                                        C.c_void_p, _i64p, _i64p, _i64p, _i32p, _i32p, _i64p, C.c_void_p]),
         "mrc_pac_read_header": (C.c_int, [_u8p, C.c_int64, C.POINTER(MrcConfig), _i32p, C.POINTER(C.c_uint32), _i64p]),
         "mrc_pac_scan_chunks": (C.c_int64, [_u8p, C.c_int64, C.c_int64, _i64p, C.c_int64]),
         "mrc_unpack_blocks": (C.c_int, [C.POINTER(MrcConfig), C.c_int64, C.c_int, C.c_int, _u8p, C.c_int64, _i64p] +
@@ -487,6 +495,88 @@ class Handle:
         out = {"bytes": buf, "stream_offset": s_off, "item_offset": i_off, "reservoir_out": res_out, "total": int(total[0])}
         if want_trace:
             out["reservoir_trace"] = trace
+        return out
+
+    def encode_chained_pac_ladder(self, pcm_left, pcm_right, shapes, rates, use_huffman=True, with_flush=True,
+                                  num_samples=None, reservoir_in=None, want_trace=False, device=None, stream=None,
+                                  want_items=False):
+        """mrc_encode_chained_ladder_pac: encode_chained_pac at every target bit rate of `rates` (bits per sample) in ONE
+        call -- phase A once, the serial scan per (rate, stream).  Result r is what encode_chained_pac gives on a handle with
+        target_bits_per_sample = rates[r]; the handle's own rate is not used.  reservoir_in: None or [nRates][nStreams].
+        device = (left_ptr, right_ptr or None, sample_format, stride, out_ptrs [nRates], out_caps [nRates]): PCM and outputs
+        in HBM (mrc_dev_encode_chained_ladder_pac; `bytes` is then None).
+        -> list of nRates dicts shaped like encode_chained_pac's."""
+        start, off, a, b = self._chain_schedule(shapes)
+        n_streams = len(start) - 1
+        rates = np.ascontiguousarray(np.atleast_1d(np.asarray(rates, dtype=np.float64)))
+        R = rates.size
+        if device is None:
+            mono = pcm_right is None
+            pl = np.atleast_2d(pcm_left)
+            dt = np.int16 if pl.dtype == np.int16 else np.float64
+            pl = np.ascontiguousarray(pl, dtype=dt)
+            pr = None if mono else np.ascontiguousarray(np.atleast_2d(pcm_right), dtype=dt)
+            if (not mono and pl.shape != pr.shape) or pl.ndim != 2 or pl.shape[0] != n_streams:
+                raise ValueError("pcm_left / pcm_right must be [nStreams][stride], one row per shape list")
+            stride, fmt = pl.shape[1], (1 if dt == np.int16 else 0)
+        else:
+            mono = device[1] is None
+        nch = 1 if mono else 2
+        n_items = len(off) + (nch * n_streams if with_flush else 0)
+        ns = None if num_samples is None else np.ascontiguousarray(num_samples, dtype=np.uint32)
+        if ns is not None and ns.shape != (n_streams,):
+            raise ValueError("num_samples: one value per stream")
+        res_in = None
+        if reservoir_in is not None:
+            res_in = _i32(np.asarray(reservoir_in))
+            if res_in.shape != (R, n_streams):
+                raise ValueError("reservoir_in must be [nRates][nStreams] = [%d][%d], got %s" % (R, n_streams, res_in.shape))
+        s_off = np.zeros((R, n_streams + 1), np.int64)
+        i_off = np.zeros((R, n_items + 1), np.int64) if want_items else None
+        res_out = np.zeros((R, n_streams), np.int32)
+        trace = np.zeros((R, n_items), np.int32) if want_trace else None
+        total = np.zeros(R, np.int64)
+        vp = lambda arr: None if arr is None else arr.ctypes.data_as(C.c_void_p)
+        sched = (_p(start, _i64p), _p(off, _i64p), _p(a, _i32p), _p(b, _i32p), _p(res_in, _i32p), 1 if use_huffman else 0,
+                 1 if with_flush else 0, vp(ns))
+        tail = (_p(s_off, _i64p), _p(i_off, _i64p), _p(res_out, _i32p), _p(trace, _i32p), _p(total, _i64p))
+        bufs = None
+        if device is not None:
+            dl, dr, fmt, stride, douts, dcaps = device
+            ptrs = (C.c_void_p * R)(*[int(p) if p else None for p in douts])
+            caps = np.ascontiguousarray(dcaps, dtype=np.int64)
+            if len(douts) != R or caps.shape != (R,):
+                raise ValueError("device: one output pointer and one capacity per rate")
+            self._check(lib.mrc_dev_encode_chained_ladder_pac(self._h, R, _p(rates, _f64p), n_streams, dl, dr, int(fmt),
+                                                              int(stride), *sched, C.cast(ptrs, C.c_void_p), _p(caps, _i64p),
+                                                              *tail, stream))
+        else:
+            bound = self.chain_out_bound(start, a, b, with_flush, ns is not None, nch)
+            if bound < 0:
+                raise MrcError("mrc_chain_out_bound failed (%d): block shape out of range" % bound)
+            # a buffer per rate for typical content (1.5x the rate's bits for a long block, at least 1 KB per block); if a rate
+            # packs to more, the call says how much and runs again with buffers of the reported sizes (a ladder keeps no
+            # output on the device)
+            per_block = [max(1024, int(1.5 * r * nch * 1024 / 8)) for r in rates]
+            bufs = [np.empty(max(min(bound, int(off.size) * pb + n_streams * 4096 + 4096), 1), np.uint8) for pb in per_block]
+            for attempt in range(2):
+                ptrs = (C.c_void_p * R)(*[buf.ctypes.data for buf in bufs])
+                caps = np.array([buf.size for buf in bufs], np.int64)
+                rc = lib.mrc_encode_chained_ladder_pac(self._h, R, _p(rates, _f64p), n_streams, vp(pl), vp(pr), fmt, stride,
+                                                       *sched, C.cast(ptrs, C.c_void_p), _p(caps, _i64p), *tail)
+                if rc == MRC_ERR_NOMEM and attempt == 0 and 0 < int(total.max()) and int(total.max()) <= bound:
+                    bufs = [buf if int(t) <= buf.size else np.empty(int(t), np.uint8) for buf, t in zip(bufs, total)]
+                    continue
+                self._check(rc)
+                break
+            bufs = [buf[:int(t)] for buf, t in zip(bufs, total)]
+        out = []
+        for r in range(R):
+            d = {"bytes": None if bufs is None else bufs[r], "stream_offset": s_off[r], "item_offset": None if i_off is None else i_off[r],
+                 "reservoir_out": res_out[r], "total": int(total[r])}
+            if want_trace:
+                d["reservoir_trace"] = trace[r]
+            out.append(d)
         return out
 
     def chain_out_bound(self, block_start, block_a, block_b, with_flush=True, with_headers=True, n_channels=2):

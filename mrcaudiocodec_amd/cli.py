@@ -10,6 +10,11 @@ Mono WAVs: the same loop with WriteDataBlock in place of JointWriteDataBlock (th
 pacfileThem.py:622-790 and the commented-out call at 1218): one-channel blocks, one Close() block.  Other channel
 counts are refused: the file format's readers stop at two channels and Close() flushes at most two.
 
+Bit rates: --bits-per-sample 4 encodes at 4 bits per sample instead of the reference's 2.86.  A comma-separated list is a
+rate LADDER, encoded in one library call (mrc_encode_chained_ladder_pac: the transform and the psychoacoustic model once,
+the reservoir scan per rate); the output name must then contain {bps}, replaced by each value as written:
+    python -m mrcaudiocodec_amd.cli in.wav out_{bps}.pac --bits-per-sample 1.5,2.86,4
+
 Decode direction (row f-4):  python -m mrcaudiocodec_amd.cli -d in.pac out.wav
 One library call (mrc_decode_pac_pcm16): chunk parsing and Huffman decoding, dequantise / M-S / IMDCT / window /
 overlap-add and the interleaved 16-bit PCM codes all on the GPU, then the WAV header of pcmfile.py:141-153.  The first decoded block (the MDCT's half-block delay) is dropped as in the
@@ -21,6 +26,7 @@ from struct import pack, unpack
 import numpy as np
 
 from . import Handle, MrcError, pacfile, transient
+from ._lib import MRC_MAX_RATES
 
 
 def read_wav_pcm(path, hop=1024):
@@ -63,8 +69,43 @@ def read_wav(path, hop=1024):
     return rate, n_ch, num_samples, np.where(mag >= 32768, 0.0, np.sign(c) * 2.0 * mag / 65535)
 
 
-def encode_wav(in_path, out_path=None, use_huffman=True, device_id=0, handle=None, exact_spread=False, certify=None):
-    """certify: a dict to fill with the sensitivity certificate of the encode (mrc_get_sensitivity: how many integer decisions
+def parse_bits_per_sample(value):
+    """--bits-per-sample: a number, or several separated by commas (a str), or a sequence of numbers -> [(text as written,
+    float)].  Every value must be finite and in (0, 64] (the rates the library takes)."""
+    if isinstance(value, str):
+        texts = [t.strip() for t in value.split(",")]
+    elif isinstance(value, (int, float, np.integer, np.floating)):
+        texts = [str(value)]
+    else:
+        texts = [str(v) for v in value]
+    if not texts or any(not t for t in texts):
+        raise ValueError("--bits-per-sample: expected a comma-separated list of numbers, got %r" % (value,))
+    out = []
+    for t in texts:
+        try:
+            v = float(t)
+        except ValueError:
+            raise ValueError("--bits-per-sample: %r is not a number" % t)
+        if not np.isfinite(v) or not 0.0 < v <= 64.0:
+            raise ValueError("--bits-per-sample: %s lies outside (0, 64]" % t)
+        out.append((t, v))
+    if len(out) > MRC_MAX_RATES:
+        raise ValueError("--bits-per-sample: at most %d rates in one ladder" % MRC_MAX_RATES)
+    return out
+
+
+def ladder_paths(out_path, rates):
+    """out_path with {bps} replaced by each rate as written"""
+    return [out_path.replace("{bps}", t) for (t, _) in rates]
+
+
+def encode_wav(in_path, out_path=None, use_huffman=True, device_id=0, handle=None, exact_spread=False, certify=None,
+               bits_per_sample=None):
+    """bits_per_sample: None -- the handle's rate (a new handle: the reference's 2.86); one value -- that target bit rate;
+    several (a comma-separated str or a sequence) -- a rate ladder in ONE chained call (mrc_encode_chained_ladder_pac):
+    out_path must then contain {bps}, written once per rate with the value as given, and a list of byte strings (one per
+    rate) is returned.  A ladder refuses certify.  These checks run before the file is read or a device is touched.
+    certify: a dict to fill with the sensitivity certificate of the encode (mrc_get_sensitivity: how many integer decisions
     were taken within a guard band of floating-point rounding); if any was, the file is encoded once more with the masker
     spreading evaluated operation by operation (MRC_OPT_EXACT_SPREAD) and certify["bytes_equal_exact_spread"] says whether
     the two encodes gave the same bytes.
@@ -73,6 +114,16 @@ def encode_wav(in_path, out_path=None, use_huffman=True, device_id=0, handle=Non
     bit-identical by construction (README.md, "Parity").
     The file's int16 codes go to the device as they are: the transient detector (mrc_transient_peaks_ex) and the whole
     encode loop (ONE call, mrc_encode_chained_stream_pcm16_pac) read them there; 2 bytes per sample on the host."""
+    rates = None if bits_per_sample is None else parse_bits_per_sample(bits_per_sample)
+    ladder = rates is not None and len(rates) > 1
+    if ladder and certify is not None:
+        raise ValueError("--certify takes one bit rate (the sensitivity certificate covers one encode)")
+    if ladder and out_path is not None and "{bps}" not in out_path:
+        raise ValueError("several bit rates: the output name must contain {bps} (e.g. out_{bps}.pac)")
+    if rates is not None and not ladder and handle is not None and rates[0][1] != handle.cfg.target_bits_per_sample:
+        ladder = True                    # (a caller's handle at another rate: a ladder of one, the handle stays as it is)
+        if certify is not None:
+            raise ValueError("--certify: the handle's target_bits_per_sample differs from bits_per_sample")
     rate, n_ch, num_samples, pcm = read_wav_pcm(in_path)
     if n_ch not in (1, 2):
         raise ValueError("%d-channel input: mono and stereo WAV files only (the .pac readers refuse more than two channels "
@@ -82,7 +133,8 @@ def encode_wav(in_path, out_path=None, use_huffman=True, device_id=0, handle=Non
         pacfile.header(pacfile.make_config(sample_rate=rate, **shape), n_ch, num_samples)
     except MrcError as e:
         raise ValueError("%d Hz input: outside the sample rates the reference can encode (%s)" % (rate, e))
-    h = handle if handle is not None else Handle(sample_rate=rate, device_id=device_id)
+    tbps = {} if rates is None or ladder else dict(target_bits_per_sample=rates[0][1])
+    h = handle if handle is not None else Handle(sample_rate=rate, device_id=device_id, **tbps)
     was_exact = h.get_option(1)
     was_sens = h.get_option(5)
     if exact_spread:
@@ -99,6 +151,15 @@ def encode_wav(in_path, out_path=None, use_huffman=True, device_id=0, handle=Non
             raise ValueError("file too short: fewer than two hops")
         if shapes[-1, 2] != L:
             raise ValueError("the stream must end with a long block (the reference's Close() assumes it)")
+        if ladder:
+            stream = codes[0] if n_ch == 1 else codes
+            datas = pacfile.encode_stream_ladder(h, stream, shapes, [v for (_, v) in rates], use_huffman=use_huffman,
+                                                 num_samples=num_samples)
+            if out_path:
+                for path, d in zip(ladder_paths(out_path, rates), datas):
+                    with open(path, "wb") as f:
+                        f.write(d)
+            return datas if len(rates) > 1 else datas[0]
         r = h.encode_chained_pac(codes[0][None], right, [shapes], use_huffman=use_huffman, with_flush=True,
                                  num_samples=[num_samples])
         data = r["bytes"].tobytes()
@@ -167,6 +228,9 @@ def main(argv=None):
                     help="report how many integer decisions of the encode lay within a guard band of floating-point rounding "
                          "(quantiser edges, bit-allocation ties, M/S threshold, peak test); if any did, encode again with "
                          "--exact-spread and say whether the bytes are the same")
+    ap.add_argument("--bits-per-sample", default=None, metavar="LIST",
+                    help="target bits per sample (default 2.86, the reference's); several, comma separated (e.g. 1.5,2.86,4), "
+                         "encode a rate ladder in one call, and dst must then contain {bps}")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
     if a.decode:
@@ -174,7 +238,18 @@ def main(argv=None):
         print("%s: %d channels x %d samples" % (a.dst, pcm.shape[0], pcm.shape[1]))
         return
     cert = {} if a.certify else None
-    data = encode_wav(a.src, a.dst, not a.no_huffman, a.device, exact_spread=a.exact_spread, certify=cert)
+    if a.bits_per_sample is not None and len(parse_bits_per_sample(a.bits_per_sample)) > 1:
+        rates = parse_bits_per_sample(a.bits_per_sample)
+        if cert is not None:
+            ap.error("--certify takes one bit rate")
+        if "{bps}" not in a.dst:
+            ap.error("several bit rates: dst must contain {bps} (e.g. out_{bps}.pac)")
+        datas = encode_wav(a.src, a.dst, not a.no_huffman, a.device, exact_spread=a.exact_spread, bits_per_sample=a.bits_per_sample)
+        for path, d in zip(ladder_paths(a.dst, rates), datas):
+            print("%s: %d bytes" % (path, len(d)))
+        return
+    data = encode_wav(a.src, a.dst, not a.no_huffman, a.device, exact_spread=a.exact_spread, certify=cert,
+                      bits_per_sample=a.bits_per_sample)
     print("%s: %d bytes" % (a.dst, len(data)))
     if cert is not None:
         print("certificate: %d blocks examined; decisions within a guard band of rounding: %d (quantiser edges %d, "

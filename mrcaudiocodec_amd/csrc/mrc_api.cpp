@@ -711,8 +711,8 @@ int encode_host(mrc_handle* h, int64_t n, int a, int b, const double* left, cons
         MRC_HIP(h, launch_chain_prep(S, joint, n, ws.smr.as<double>(), joint ? (const int*)(dev + oSw) : nullptr,
                                      B.ev.as<unsigned>(), B.pre.as<unsigned>(), 0, st));
         if (timing) MRC_HIP(h, hipEventRecord(h->ev[4], st));
-        MRC_HIP(h, launch_chain_phase_b(n, (const ChainGroupDev*)(dev + oDesc), (const int*)(dev + oItems),
-                                        (const long long*)(dev + oStart), (int*)(dev + oRes), nullptr, 0, h->chainThreads, st));
+        MRC_HIP(h, launch_chain_phase_b(n, 1, (const ChainGroupDev*)(dev + oDesc), (const int*)(dev + oItems),
+                                        (const long long*)(dev + oStart), (int*)(dev + oRes), nullptr, 0, 0, h->chainThreads, st));
         if (timing) MRC_HIP(h, hipEventRecord(h->ev[5], st));
         if (h->sensOn)
             MRC_HIP(h, launch_sensitivity(S, n, joint, (const double*)(dev + oLines), (const int*)(dev + oScale),

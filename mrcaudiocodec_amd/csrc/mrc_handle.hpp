@@ -83,7 +83,6 @@ struct Lane {
 };
 constexpr int kLanes = 4;          // chunk buffers in flight (mrc_encode_stream_pcm16_pac reads sizes two chunks behind)
 constexpr int kKernelEvents = 6;   // boundaries of: mdct | smr | band_stats | bitalloc | quantize
-constexpr int kChainGroups = 5;    // chained encode: the four joint block shapes + Close()'s non-joint long block
 
 // Device state of one block-shape group of the chained encode (mrc_api_chain.cpp): the reservoir-free results (phase A),
 // the sorted grant events of the bit allocation, and the outputs of the serial scan (phase B)

@@ -75,6 +75,9 @@ std::string& create_error();
 void ms_plan(const std::vector<int>& bandLo, const std::vector<int>& bandN, std::vector<int>* plan, int* nLeaves,
              int* nInternal);
 bool build_shape(const mrc_config& cfg, int a, int b, HostShape* out, std::string* err);
+// the bit budgets of a block of shape (a, b) with nb bands at target_bits_per_sample tbps (codecThem.py:299-306 mono,
+// 381-388 joint before the reservoir is added): the one copy of the float arithmetic the shape tables and the rate ladder share
+void shape_budgets(const mrc_config& cfg, double tbps, int a, int b, int nb, double* budgetMono, double* budgetJointPre);
 void free_shape(HostShape* s);
 int scale_factor_host(double v, int nScaleBits, int nMantBits);
 
@@ -190,6 +193,7 @@ hipError_t launch_pcm16_interleave(int64_t nFiles, int64_t nOut, const long long
                                    hipStream_t st);
 // mrc_kernels_chain.hip -- chained stream encode: reservoir-free preparation per block, serial scan per stream
 constexpr int kChainMaxLinesPerItem = 2 * 1024;  // coded lines one scan item holds (all its streams together)
+constexpr int kChainGroups = 5;    // chained encode: the four joint block shapes + Close()'s non-joint long block
 struct ChainGroupDev {               // what chain_phase_b_kernel knows about one block-shape group (device memory)
     int joint, nb, nTot, M, K, nEv, maxN, nScaleBits, nstream, pad_;
     double budgetMono, budgetJointPre, blkswA, blkswB;          // codecThem.py:299-308, 381-396
@@ -209,9 +213,11 @@ struct ChainGroupDev {               // what chain_phase_b_kernel knows about on
 size_t chain_events_per_block(const DevShape& S, int joint);
 hipError_t launch_chain_prep(const DevShape& S, int joint, int64_t nBlocks, const double* smr, const int* msSwitch,
                              unsigned* ev, unsigned* pre, int forceFallback, hipStream_t st);
-hipError_t launch_chain_phase_b(int64_t nStreams, const ChainGroupDev* groups, const int* items, const long long* itemStart,
-                                int* reservoir, int* resTrace, int useHuffman, int threads /* 0: chosen by stream count */,
-                                hipStream_t st);
+// one workgroup per (stream, rate): rate r reads groups[r * kChainGroups ...] and reservoir[r * nStreams + s] and writes its
+// trace at resTrace + r * traceStride; the items and phase-A data are shared by all rates
+hipError_t launch_chain_phase_b(int64_t nStreams, int nRates, const ChainGroupDev* groups, const int* items,
+                                const long long* itemStart, int* reservoir, int* resTrace, long long traceStride,
+                                int useHuffman, int threads /* 0: chosen by workgroup count */, hipStream_t st);
 hipError_t launch_chain_flush_gather(int64_t nStreams, int L, const void* pcmL, const void* pcmR /* null: mono */, int fmt, int64_t stride,
                                      const long long* tailOffset, void* out, hipStream_t st);
 hipError_t launch_chain_headers(int64_t nStreams, int hdrLen, const unsigned char* hdr, const long long* firstChunk,

@@ -15,7 +15,7 @@
 //                         6 dB periodicity (level = floor(SMR / 6) - grants, position inside a level by SMR mod 6) and
 //                         is then CHECKED against the actual keys pair by pair (a near-tie that rounding turned round
 //                         is put right by an insertion pass), so the list is exactly np.argmax's order;
-//   chain_phase_b_kernel  one workgroup per stream walks the stream's blocks in file order: budget from the reservoir
+//   chain_phase_b_kernel  one workgroup per (rate, stream) walks the stream's blocks in file order: budget from the reservoir
 //                         (codecThem.py:299-308, 381-396) -> how far down the event list the budget reaches (all
 //                         grants up to the point where fewer than max(nLines) bits are left fit for certain: one
 //                         parallel count over the list's cost prefix sums; the few events after it are walked one by
@@ -263,7 +263,8 @@ __global__ __launch_bounds__(kWave * kPrepWaves) void chain_prep_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// phase B: one workgroup per stream
+// phase B: one workgroup per stream and bit rate (a rate ladder shares phase A and the event lists; only the budgets
+// differ)
 // ------------------------------------------------------------------------------------------------------------------
 #ifdef MRC_CHAIN_PROFILE
 // profiling build only (make EXTRA=-DMRC_CHAIN_PROFILE): shader-clock cycles of wave 0 per phase of chain_phase_b_kernel
@@ -446,10 +447,14 @@ __device__ __forceinline__ unsigned mantissa32(double x, int scale, int nScaleBi
     return (x < 0.0 ? (1u << (nMantBits - 1)) : 0u) + (code >> (shift < 0 ? 0 : shift));
 }
 
-template <int NT>
+// Ladder: a grid of (stream, rate) workgroups (blockIdx.y = the rate).  A separate instance, so that the single-rate scan --
+// whose scalar registers are all in use -- keeps its code as it is.
+template <int NT, bool Ladder>
 __global__ __launch_bounds__(NT) void chain_phase_b_kernel(
-    const ChainGroupDev* __restrict__ groups, const int* __restrict__ items, const long long* __restrict__ itemStart,
-    int* __restrict__ reservoir, int* __restrict__ resTrace /* nullable: reservoir after every item */, int useHuffman) {
+    const ChainGroupDev* __restrict__ groups, const int* __restrict__ items,
+    const long long* __restrict__ itemStart, int* __restrict__ reservoir /* [nRates][nStreams] */,
+    int* __restrict__ resTrace /* nullable: reservoir after every item, [nRates][traceStride] */, long long traceStride,
+    int useHuffman) {
     constexpr int kEvPerThread = ChainDims<NT>::kEvPerThread, kUnitsPerThread = ChainDims<NT>::kUnitsPerThread;
     constexpr int kChainThreads = NT;
     __shared__ int sBits[kWave];                         // bits granted per (stream, band) while the tail is walked
@@ -466,6 +471,13 @@ __global__ __launch_bounds__(NT) void chain_phase_b_kernel(
     __shared__ int sItems[256];                          // ring of item ids (see below)
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
     const int64_t strmId = blockIdx.x;
+    if (Ladder) {
+        // rate ladder: workgroup (stream, rate) = (blockIdx.x, blockIdx.y) reads the stream's phase-A data and items through
+        // the rate's group descriptors (its budgets, its output planes) and carries a reservoir and a trace of its own
+        groups += (int64_t)blockIdx.y * kChainGroups;
+        reservoir += (int64_t)blockIdx.y * gridDim.x;
+        if (resTrace) resTrace += (int64_t)blockIdx.y * traceStride;
+    }
     for (int v = tid; v <= kLutSize; v += kChainThreads) {
         unsigned e = 0;
         if (v < kLutSize)
@@ -834,21 +846,30 @@ hipError_t launch_chain_prep(const DevShape& S, int joint, int64_t nBlocks, cons
     return hipGetLastError();
 }
 
-hipError_t launch_chain_phase_b(int64_t nStreams, const ChainGroupDev* groups, const int* items, const long long* itemStart,
-                                int* reservoir, int* resTrace, int useHuffman, int threads, hipStream_t st) {
-    if (nStreams <= 0) return hipSuccess;
-    // a workgroup per stream.  Few streams: large workgroups (the chip is idle anyway, the stream's latency is what
-    // counts); many: small ones, eight streams per CU
-    if (threads <= 0) threads = nStreams <= 512 ? 512 : 256;   // (measured on one stream: 3.7 / 3.3 / 4.3 us per block at 256 / 512 / 1024)
+template <bool Ladder>
+void launch_chain_phase_b_form(int threads, dim3 grid, const ChainGroupDev* groups, const int* items, const long long* itemStart,
+                               int* reservoir, int* resTrace, long long traceStride, int useHuffman, hipStream_t st) {
     if (threads >= 1024)
-        hipLaunchKernelGGL(chain_phase_b_kernel<1024>, dim3((unsigned)nStreams), dim3(1024), 0, st, groups, items, itemStart,
-                           reservoir, resTrace, useHuffman);
+        hipLaunchKernelGGL((chain_phase_b_kernel<1024, Ladder>), grid, dim3(1024), 0, st, groups, items, itemStart, reservoir,
+                           resTrace, traceStride, useHuffman);
     else if (threads >= 512)
-        hipLaunchKernelGGL(chain_phase_b_kernel<512>, dim3((unsigned)nStreams), dim3(512), 0, st, groups, items, itemStart,
-                           reservoir, resTrace, useHuffman);
+        hipLaunchKernelGGL((chain_phase_b_kernel<512, Ladder>), grid, dim3(512), 0, st, groups, items, itemStart, reservoir,
+                           resTrace, traceStride, useHuffman);
     else
-        hipLaunchKernelGGL(chain_phase_b_kernel<256>, dim3((unsigned)nStreams), dim3(256), 0, st, groups, items, itemStart,
-                           reservoir, resTrace, useHuffman);
+        hipLaunchKernelGGL((chain_phase_b_kernel<256, Ladder>), grid, dim3(256), 0, st, groups, items, itemStart, reservoir,
+                           resTrace, traceStride, useHuffman);
+}
+
+hipError_t launch_chain_phase_b(int64_t nStreams, int nRates, const ChainGroupDev* groups, const int* items,
+                                const long long* itemStart, int* reservoir, int* resTrace, long long traceStride,
+                                int useHuffman, int threads, hipStream_t st) {
+    if (nStreams <= 0 || nRates <= 0) return hipSuccess;
+    // a workgroup per (stream, rate).  Few of them: large workgroups (the chip is idle anyway, the stream's latency is what
+    // counts); many: small ones, eight streams per CU
+    if (threads <= 0) threads = nStreams * nRates <= 512 ? 512 : 256;   // (measured on one stream: 3.7 / 3.3 / 4.3 us per block at 256 / 512 / 1024)
+    const dim3 grid((unsigned)nStreams, (unsigned)nRates);
+    if (nRates > 1) launch_chain_phase_b_form<true>(threads, grid, groups, items, itemStart, reservoir, resTrace, traceStride, useHuffman, st);
+    else launch_chain_phase_b_form<false>(threads, grid, groups, items, itemStart, reservoir, resTrace, traceStride, useHuffman, st);
     return hipGetLastError();
 }
 

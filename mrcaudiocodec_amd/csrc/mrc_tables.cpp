@@ -186,6 +186,23 @@ void ms_plan(const std::vector<int>& bandLo, const std::vector<int>& bandN, std:
     *nInternal = (int)rec.pending.size();
 }
 
+void shape_budgets(const mrc_config& cfg, double tbps, int a, int b, int nb, double* budgetMono, double* budgetJointPre) {
+    double halfN = (a + b) / 2.;
+    double m = tbps * halfN;
+    m -= cfg.n_scale_bits * (nb + 1);
+    m -= cfg.n_mant_size_bits * nb;
+    m -= cfg.blksw_bits_a;
+    m -= cfg.blksw_bits_b;
+    *budgetMono = m;
+    double j = tbps * halfN;
+    j -= cfg.n_scale_bits * nb;
+    j -= cfg.n_mant_size_bits * nb;
+    j += j;
+    j -= nb;
+    j -= cfg.n_scale_bits * 4;
+    *budgetJointPre = j;
+}
+
 bool build_shape(const mrc_config& cfg, int a, int b, HostShape* out, std::string* err) {
     const int N = a + b;
     if (a <= 0 || b <= 0 || N % 4 != 0 || (b - a) % 4 != 0) {
@@ -221,24 +238,9 @@ bool build_shape(const mrc_config& cfg, int a, int b, HostShape* out, std::strin
         for (int k = 0; k < count[i]; ++k) bandOfLine[out->bandLo[i] + k] = (unsigned char)i;
 
     // bit budgets: codecThem.py:299-306 (mono) and 381-388 (joint, before the reservoir is added)
-    {
-        double halfN = (a + b) / 2.;
-        double m = cfg.target_bits_per_sample * halfN;
-        m -= cfg.n_scale_bits * (nb + 1);
-        m -= cfg.n_mant_size_bits * nb;
-        m -= cfg.blksw_bits_a;
-        m -= cfg.blksw_bits_b;
-        S.budgetMono = m;
-        double j = cfg.target_bits_per_sample * halfN;
-        j -= cfg.n_scale_bits * nb;
-        j -= cfg.n_mant_size_bits * nb;
-        j += j;
-        j -= nb;
-        j -= cfg.n_scale_bits * 4;
-        S.budgetJointPre = j;
-        S.blkswA = cfg.blksw_bits_a;
-        S.blkswB = cfg.blksw_bits_b;
-    }
+    shape_budgets(cfg, cfg.target_bits_per_sample, a, b, nb, &S.budgetMono, &S.budgetJointPre);
+    S.blkswA = cfg.blksw_bits_a;
+    S.blkswB = cfg.blksw_bits_b;
 
     // windows
     std::vector<double> win(N), hann(N);

@@ -8,6 +8,7 @@ with the dense arrays the GPU path returns.  Mirrors the encode half of the refe
     PACFile.JointWriteDataBlock  pacfileThem.py:793-972   -> pack_joint_blocks()
     the CLI's encode loop + Close pacfileThem.py:1159-1214, 973-984 -> encode_stereo_stream()
     ... with WriteDataBlock in place of JointWriteDataBlock (1218)  -> encode_mono_stream()
+    ... at several bit rates in one call                            -> encode_stream_ladder()
 
 Block shapes are an input here; mrcaudiocodec_amd/transient.py derives them from the audio like the reference's
 transient detector, and mrcaudiocodec_amd/cli.py strings WAV ingest, detector and this writer together.
@@ -222,6 +223,30 @@ def encode_mono_streams(handle, streams, shapes, use_huffman=True, num_samples=N
     r = handle.encode_chained_pac(streams, None, shapes, use_huffman=use_huffman, with_flush=True, num_samples=num_samples)
     data, offs = r["bytes"], r["stream_offset"]
     return [data[offs[s]:offs[s + 1]].tobytes() for s in range(nS)]
+
+
+def encode_stream_ladder(handle, stream, shapes, rates, use_huffman=True, num_samples=None):
+    """ONE stream -- stereo [2][samples], or mono [samples] / [1][samples]; float64 signed fractions or int16 PCM codes, with
+    the zero prior hop -- and its block-shape sequence, encoded at every target bit rate of `rates` (bits per sample) in one
+    library call (mrc_encode_chained_ladder_pac: the transform and the psychoacoustic model once, the serial scan per rate).
+    Returns a list of .pac byte strings, one per rate: each what encode_stereo_stream / encode_mono_stream write on a handle
+    whose target_bits_per_sample is that rate.  The handle's own rate is not used."""
+    L = handle.cfg.n_mdct_lines
+    stream = np.asarray(stream)
+    if stream.dtype != np.int16:
+        stream = stream.astype(np.float64, copy=False)
+    if stream.ndim == 1:
+        stream = stream[None]
+    if stream.ndim != 2 or stream.shape[0] not in (1, 2):
+        raise ValueError("stream must be stereo [2][samples] or mono [samples]")
+    if not len(shapes) or shapes[-1][2] != L:
+        raise ValueError("the stream must end with a long block (the reference's Close() assumes it)")
+    if num_samples is None:
+        num_samples = sum(int(b) for (_, _, b) in shapes)                 # the CLI writes the WAV's count
+    right = stream[1][None] if stream.shape[0] == 2 else None
+    rs = handle.encode_chained_pac_ladder(stream[0][None], right, [shapes], rates, use_huffman=use_huffman, with_flush=True,
+                                          num_samples=[num_samples])
+    return [r["bytes"].tobytes() for r in rs]
 
 
 def encode_mono_stream_per_block(handle, stream, shapes, use_huffman=True, num_samples=None):
