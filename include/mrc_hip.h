@@ -216,14 +216,17 @@ int mrc_stereo_masking_factor(mrc_handle* h, int64_t n, const double* mid_thresh
 int mrc_ms_switch(mrc_handle* h, int64_t n_blocks, int n_bands, const int32_t* n_lines,
                   const double* lines_left, const double* lines_right, int32_t* ms_switch);
 
-/* ---- device entry points (batch / stream mode; what bench.py and multi-GPU sharding drive) ------ */
+/* ---- device entry points (batch / stream mode; bench.py and multi-GPU sharding drive mrc_dev_encode_ex) ---- */
 
 /* Frame f of the batch reads its a+b samples at ch[offsets ? offsets[f] : f*frame_stride ...].
  * frame_stride = b  -> an overlapped PCM stream, every hop read once (pacfileThem.py:628-631);
  * frame_stride = a+b -> explicit blocks.  ch_right == NULL -> mono (nsig = 1), else joint (nsig = 4).
  * Buffers (device): lines [n][nsig][N/2] f64, overall_scale [n][nsig] i32, smr [n][nsig][nBands] f64,
  * ms_switch [n][nBands] i32 (joint only), bit_alloc/scale_factor [n][nstream][nBands] i32,
- * mantissa [n][nstream][N/2] i32, reservoir_in (may be NULL) / reservoir_out [n] i32. */
+ * mantissa [n][nstream][N/2] i32, reservoir_in (may be NULL) / reservoir_out [n] i32.
+ * The three stage calls (mrc_dev_mdct, mrc_dev_smr, mrc_dev_alloc_quant) are neither timed (mrc_set_timing) nor counted
+ * by MRC_OPT_SENSITIVITY; mrc_dev_smr computes the SMRs of all nsig signals in every band.  mrc_dev_alloc_quant keeps
+ * per-band peaks in the handle's workspace: one stream per handle at a time. */
 int mrc_dev_mdct(mrc_handle* h, int a, int b, int64_t n_frames, const double* ch_left, const double* ch_right,
                  int64_t frame_stride, const int64_t* offsets, double* lines, int32_t* overall_scale, void* stream);
 int mrc_dev_smr(mrc_handle* h, int a, int b, int64_t n_frames, const double* ch_left, const double* ch_right,
@@ -460,7 +463,8 @@ int mrc_dev_encode_chained_ladder_pac(mrc_handle* h, int n_rates, const double* 
  *                      bound exceeded 1e-13 of a line's masked intensity) -- informational: the result is then the sweep's
  *   MRC_SENS_FRAMES    blocks examined
  * A call whose first four counts are zero took no decision near an edge.  Not counted: the overall scale (a 20-bit code of
- * the block peak), the transient detector's threshold tests.  Synchronises the handle's stream. */
+ * the block peak), the transient detector's threshold tests.  Waits for the whole device (hipDeviceSynchronize), so that
+ * counting calls queued on any stream are included; a reset is complete when it returns. */
 #define MRC_SENS_QUANT 0
 #define MRC_SENS_BITALLOC 1
 #define MRC_SENS_MS 2
@@ -543,8 +547,11 @@ int mrc_decode_pac_pcm16(mrc_handle* h, int64_t n_files, const uint8_t* buf, con
  * (decode_kernel launches + interleaved pcm16), [3] device -> host copy. */
 int mrc_get_decode_ms(mrc_handle* h, double* ms /*[4]*/);
 
-/* Per-stage device time of the most recent mrc_dev_encode / stage call when timing is enabled
- * (hipEvents on the launch stream; the call then synchronises).  ms[0..2] = mdct, smr, alloc+quant. */
+/* Per-stage device time of the most recent timed call when timing is enabled (hipEvents on the launch stream; the call
+ * then synchronises).  Timed: mrc_dev_encode / mrc_dev_encode_ex and mrc_encode_mono / mrc_encode_joint (the _blocks
+ * forms: their last shape group).  Not timed: the stage calls (mrc_dev_mdct, mrc_dev_smr, mrc_dev_alloc_quant),
+ * mrc_encode_stream_pcm16* (it overlaps calls; timing stays on after it) and the chained calls (mrc_get_chain_ms).
+ * ms[0..2] = mdct, smr, alloc+quant. */
 int mrc_set_timing(mrc_handle* h, int enabled);
 /* Options.  MRC_OPT_EXACT_SPREAD = 1: evaluate the masker spreading (psychoac.py:68-78) with the
  * reference's own expression and pow() per (masker, line) instead of the factored fast form (default 0).
@@ -559,9 +566,10 @@ int mrc_set_timing(mrc_handle* h, int enabled);
 /* MRC_OPT_CHAIN_THREADS = 0 | 256 | 512 | 1024: threads of the workgroup that walks one stream in the chained encode's
  * serial scan (default 0: 512 for up to 512 streams -- the latency of the one stream counts -- else 256: eight streams per CU). */
 #define MRC_OPT_CHAIN_THREADS 4
-/* MRC_OPT_SENSITIVITY = 1: every encode call on the handle also counts the integer decisions it took within a guard band of
+/* MRC_OPT_SENSITIVITY = 1: every encode call on the handle (not the stage calls) also counts the integer decisions it took within a guard band of
  * floating-point rounding (see mrc_get_sensitivity); costs a pass over the intermediate results (~10 % of an encode).
- * = 2 (tests): the same with every guard band 10^8 times wider, so that an ordinary corpus produces counts. */
+ * = 2 (tests): the same with every guard band 10^8 times wider, so that an ordinary corpus produces counts.
+ * mrc_get_option returns the value as set (0, 1 or 2). */
 #define MRC_OPT_SENSITIVITY 5
 /* MRC_OPT_CHAIN_SLAB_BLOCKS = n: the chained encode (mrc_encode_chained_stream*_pac, mrc_dev_encode_chained_pac) cuts a call
  * into slabs of at most n blocks -- whole streams while they fit, a longer stream alone in consecutive time slabs, the bit

@@ -183,6 +183,7 @@ int mrc_set_option(mrc_handle* h, int option, int value) {
             const double scale = value == 2 ? 1e8 : 1.0;                 // slot 7: the guard scale the kernels read
             MRC_HIP(h, hipMemcpy(h->sens.as<unsigned long long>() + 7, &scale, sizeof scale, hipMemcpyHostToDevice));
         }
+        h->sensMode = value;
         h->sensOn = value != 0;
         return MRC_OK;
     }
@@ -206,7 +207,7 @@ int mrc_get_option(mrc_handle* h, int option, int32_t* value) {
         case MRC_OPT_SMR_ALL_BANDS: *value = h->smrAllBands ? 1 : 0; return MRC_OK;
         case MRC_OPT_CHAIN_FORCE_REPAIR: *value = h->chainForceFallback ? 1 : 0; return MRC_OK;
         case MRC_OPT_CHAIN_THREADS: *value = h->chainThreads; return MRC_OK;
-        case MRC_OPT_SENSITIVITY: *value = h->sensOn ? 1 : 0; return MRC_OK;
+        case MRC_OPT_SENSITIVITY: *value = h->sensMode; return MRC_OK;
         case MRC_OPT_CHAIN_SLAB_BLOCKS: *value = (int32_t)h->chainSlabBlocks; return MRC_OK;
         default: return fail(h, MRC_ERR_INVALID, "mrc_get_option: unknown option");
     }
@@ -217,11 +218,15 @@ int mrc_get_sensitivity(mrc_handle* h, int64_t* counts, int reset) {
     for (int i = 0; i < MRC_SENS_COUNT; ++i) counts[i] = 0;
     if (!h->sens.p) return MRC_OK;
     MRC_HIP(h, hipSetDevice(h->device));
-    MRC_HIP(h, hipStreamSynchronize(h->stream));
+    // the whole device, not h->stream: the counting encode calls may have been queued on any stream of the caller's
+    MRC_HIP(h, hipDeviceSynchronize());
     unsigned long long v[MRC_SENS_COUNT];
     MRC_HIP(h, hipMemcpy(v, h->sens.p, sizeof v, hipMemcpyDeviceToHost));
     for (int i = 0; i < MRC_SENS_COUNT - 1; ++i) counts[i] = (int64_t)v[i];   // (slot 7 is the guard scale)
-    if (reset) MRC_HIP(h, hipMemset(h->sens.p, 0, (MRC_SENS_COUNT - 1) * sizeof(unsigned long long)));
+    if (reset) {                                         // done before returning: no later call on any stream can race it
+        MRC_HIP(h, hipMemset(h->sens.p, 0, (MRC_SENS_COUNT - 1) * sizeof(unsigned long long)));
+        MRC_HIP(h, hipDeviceSynchronize());
+    }
     return MRC_OK;
 }
 

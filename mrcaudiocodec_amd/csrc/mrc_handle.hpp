@@ -163,6 +163,7 @@ struct mrc_handle {
     bool chainForceFallback = false; // mrc_set_option(MRC_OPT_CHAIN_FORCE_REPAIR): tests of chain_prep_kernel's repair pass
     bool sensOn = false;             // mrc_set_option(MRC_OPT_SENSITIVITY): count decisions near a rounding edge ...
     mrc::DevBuf sens;                // ... here: MRC_SENS_COUNT counters (uint64), mrc_get_sensitivity
+    int sensMode = 0;                // the option's value as set (0, 1 or 2), what mrc_get_option returns
     hipEvent_t ev[mrc::kKernelEvents] = {};
     double stageMs[3] = {0, 0, 0};
     double kernelMs[5] = {0, 0, 0, 0, 0};

@@ -150,3 +150,93 @@ def test_cli_certificate(tmp_path):
     assert data == cli.encode_wav(str(wav))                   # counting changes nothing
     assert cert["blocks_examined"] > 14 and cert["decisions_near_an_edge"] == 0
     assert "bytes_equal_exact_spread" not in cert
+
+
+def test_the_option_reads_back_the_mode_it_was_set_to(h):
+    for v in (2, 1, 0, 2):
+        h.set_option(SENS, v)
+        assert h.get_option(SENS) == v
+
+
+def _model_counts_match(h):
+    """a loose-guard (mode 2) mono encode counts exactly what the model counts with the guards 10^8 wider"""
+    from mrcaudiocodec_amd import synth
+    h.sensitivity()
+    n = 32
+    bl = _blocks(synth.c2_noise(n + 1), n)
+    h.encode_mono(bl, 1024, 1024)
+    s = h.sensitivity()
+    quant, ties = _model(fast.encode_mono_batch(bl, 1024, 1024), False, 1e8)
+    assert quant > 5 and ties > 20
+    assert s["quantiser_edges"] == quant, (s, quant)
+    assert s["bitalloc_near_ties"] == ties, (s, ties)
+    assert s["blocks_examined"] == n
+
+
+def test_a_certified_encode_gives_a_mode_2_handle_back_in_mode_2(h, tmp_path):
+    from mrcaudiocodec_amd import cli
+    rng = np.random.default_rng(4)
+    pcm = np.clip(np.rint(rng.normal(0, 0.05 * 32767, (2, 8 * 1024))), -32767, 32767).astype(np.int16)
+    wav = tmp_path / "in.wav"
+    wav.write_bytes(cli.wav_bytes(pcm, 48000))
+    h.set_option(SENS, 2)
+    cli.encode_wav(str(wav), handle=h, certify={})           # counts in mode 1, then restores the handle's mode
+    assert h.get_option(SENS) == 2
+    _model_counts_match(h)                                   # ... guard scale included
+
+
+def test_counts_of_an_encode_queued_on_the_callers_stream(h):
+    """mrc_get_sensitivity waits for the whole device, not only for the handle's stream, and its reset is done when it
+    returns.  This cannot force the race (the encode may well be finished before the counts are read); it pins the
+    contract: counts read right after an encode queued on another stream, without synchronising it, are that encode's."""
+    torch = pytest.importorskip("torch")
+    from mrcaudiocodec_amd import synth
+    n, half = 96, 1024
+    bl = _blocks(synth.c2_noise(n + 1), n)
+    dev = "cuda:0"
+    ch = torch.from_numpy(bl.reshape(-1)).to(dev)
+    osc, ro = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+    nb = len(h.bands(1024, 1024))
+    ba, sf = torch.empty(n * nb, dtype=torch.int32, device=dev), torch.empty(n * nb, dtype=torch.int32, device=dev)
+    mant = torch.empty(n * half, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    h.set_option(SENS, 1)
+    h.sensitivity()
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        for _ in range(2):                                   # the second: after the first read's reset
+            h.dev_encode_ex(1024, 1024, n, ch.data_ptr(), None, 0, 2048, None, None, osc.data_ptr(), None, ba.data_ptr(),
+                            sf.data_ptr(), mant.data_ptr(), 0, ro.data_ptr(), None, side.cuda_stream)
+            s = h.sensitivity()
+            assert s["blocks_examined"] == n, s
+    torch.cuda.synchronize()
+
+
+def test_stage_calls_count_nothing(h):
+    torch = pytest.importorskip("torch")
+    from mrcaudiocodec_amd import synth
+    h.set_option(SENS, 1)
+    h.sensitivity()
+    n, a, b = 6, 1024, 1024
+    h.encode_mono(_blocks(synth.c2_noise(5), 4), a, b)       # 4 blocks counted ...
+    xs = synth.c3_stereo(n + 1)
+    dev = "cuda:0"
+    nb = len(h.bands(a, b))
+    for chans in ([_blocks(xs[0], n)], [_blocks(xs[0], n), _blocks(xs[1], n)]):
+        joint = len(chans) == 2
+        nsig, ns = (4, 2) if joint else (1, 1)
+        ch = [torch.from_numpy(c.reshape(-1)).to(dev) for c in chans]
+        lines = torch.empty(n * nsig * 1024, dtype=torch.float64, device=dev)
+        smr = torch.empty(n * nsig * nb, dtype=torch.float64, device=dev)
+        osc = torch.empty(n * nsig, dtype=torch.int32, device=dev)
+        sw = torch.empty(n * nb, dtype=torch.int32, device=dev)
+        ba, sf = (torch.empty(n * ns * nb, dtype=torch.int32, device=dev) for _ in range(2))
+        mant = torch.empty(n * ns * 1024, dtype=torch.int32, device=dev)
+        ro = torch.empty(n, dtype=torch.int32, device=dev)
+        chr_ = ch[1].data_ptr() if joint else None
+        h.dev_mdct(a, b, n, ch[0].data_ptr(), chr_, a + b, None, lines.data_ptr(), osc.data_ptr())
+        h.dev_smr(a, b, n, ch[0].data_ptr(), chr_, a + b, None, lines.data_ptr(), osc.data_ptr(), smr.data_ptr())
+        h.dev_alloc_quant(a, b, n, joint, lines.data_ptr(), osc.data_ptr(), smr.data_ptr(), None, sw.data_ptr(),
+                          ba.data_ptr(), sf.data_ptr(), mant.data_ptr(), ro.data_ptr())
+        torch.cuda.synchronize()
+    assert h.sensitivity()["blocks_examined"] == 4           # ... and no block of the stage calls
