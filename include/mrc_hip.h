@@ -547,6 +547,46 @@ int mrc_decode_pac_pcm16(mrc_handle* h, int64_t n_files, const uint8_t* buf, con
  * (decode_kernel launches + interleaved pcm16), [3] device -> host copy. */
 int mrc_get_decode_ms(mrc_handle* h, double* ms /*[4]*/);
 
+/* mrc_pac_nmr: the noise-to-mask ratio (NMR) of n_files whole `.pac` files against the source they were coded from, in
+ * ONE call, measured with the codec's own masking model.  The files are read as mrc_decode_pac_pcm16 reads them (host
+ * memory; the same parameter checks against the handle and the same error texts; a stereo file of more than one block
+ * is joint blocks followed by Close()'s two non-joint chunks).  File f's source channel c is
+ * src[src_offset[f] + c * src_stride[f] + t] for t < src_frames[f] and zero beyond: the WAV's own samples as 16-bit
+ * codes, without the prior hop (the layout of the fixtures and of cli.read_wav_pcm).  The library cannot see how long
+ * src is: the caller must hold a channel row of src_frames[f] samples for every channel the file's header names (the
+ * Python binding checks the rows against each header).  Block i of shape (a_i, b_i)
+ * covers [p_i, p_i + a_i + b_i) of the channel's padded source (n_mdct_lines zeros, the samples, zeros),
+ * p_i = a_0 + ... + a_{i-1}.  For every entry e = (block, channel), with X the windowed MDCT lines of the source block
+ * (mrc_mdct, apply_window = 1), X^ the decoded lines of the channel before the IMDCT (dequantised, divided by the
+ * overall scale level, L / R rebuilt in M/S bands) and T the masked threshold of the source block in dB SPL
+ * (psychoac.py:134-173, the handle's MRC_OPT_EXACT_SPREAD), band j gives
+ *   noise_j = sum_k 4 (X[k] - X^[k])^2,  mask_j = sum_k 10^((T[k] - 96) / 10),  r_j = noise_j / mask_j
+ * (r_j = 0 where mask_j is +inf: the top lines from ~80 kHz on).  Per file:
+ *   nmr_max_db      10 log10 of the largest r_j over all entries and bands;
+ *   nmr_total_db    10 log10(sum_e b_e mean_j(r_j) / sum_e b_e): band-averaged ratios weighted by the block's b;
+ *   disturbed_blocks  blocks in which some channel has a band with r_j > 1;  n_blocks.
+ * A file without blocks gives -inf, -inf, 0, 0; r_j = 0 everywhere gives -inf.  Entries are ordered by file, block,
+ * channel; file f's are [entry_offset[f], entry_offset[f + 1]).  entry_shape (NULL or [entry_cap][2]: a, b) and
+ * band_noise / band_mask (both NULL or both [entry_cap][MRC_MAX_BANDS], zeros past a block's band count) return the
+ * entries.  If any of them is asked for and entry_cap is too small, the call returns MRC_ERR_NOMEM after reading only
+ * the headers and chunk lengths on the host (no device call of any kind), fills entry_offset [n_files + 1] and
+ * n_blocks [n_files] and writes nothing else.  entry_shape and the band arrays are written only by a call that succeeds.  MRC_ERR_INVALID, the text
+ * naming the file: a file the decoder refuses; a negative src_offset, src_stride or src_frames; a stride below
+ * src_frames for a stereo file; a NULL src with src_frames > 0.  Results are bit-identical from call to call and
+ * whatever other files share the call.  Device memory: ~16 bytes per source line analysed (distinct source, position
+ * and shape: the rungs of a ladder share one analysis) plus the padded int16 sources. */
+int mrc_pac_nmr(mrc_handle* h, int64_t n_files, const uint8_t* buf, const int64_t* file_offset /*[n_files+1]*/,
+                const int16_t* src, const int64_t* src_offset /*[n_files]*/, const int64_t* src_stride /*[n_files]*/,
+                const int64_t* src_frames /*[n_files]*/,
+                double* nmr_max_db, double* nmr_total_db, int64_t* disturbed_blocks, int64_t* n_blocks /*[n_files]*/,
+                int64_t* entry_offset /*[n_files+1]*/, int64_t entry_cap,
+                int32_t* entry_shape /* NULL or [entry_cap][2]: a, b */,
+                double* band_noise /* NULL or [entry_cap][MRC_MAX_BANDS] */,
+                double* band_mask /* NULL or [entry_cap][MRC_MAX_BANDS] */);
+/* Device time of the last mrc_pac_nmr call (ms): [0] host -> device copy, [1] unpack kernel, [2] source analysis
+ * (padding, MDCT and masked thresholds), [3] NMR kernels + device -> host copy. */
+int mrc_get_nmr_ms(mrc_handle* h, double* ms /*[4]*/);
+
 /* Per-stage device time of the most recent timed call when timing is enabled (hipEvents on the launch stream; the call
  * then synchronises).  Timed: mrc_dev_encode / mrc_dev_encode_ex and mrc_encode_mono / mrc_encode_joint (the _blocks
  * forms: their last shape group).  Not timed: the stage calls (mrc_dev_mdct, mrc_dev_smr, mrc_dev_alloc_quant),

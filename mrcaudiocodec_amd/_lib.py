@@ -161,6 +161,9 @@ def _load():
         "mrc_dev_unpack_blocks": (C.c_int, [H, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64] + [C.c_void_p] * 10),
         "mrc_decode_pac_pcm16": (C.c_int, [H, C.c_int64, _u8p, _i64p, C.c_void_p, C.c_int64, _i64p, _i32p]),
         "mrc_get_decode_ms": (C.c_int, [H, _f64p]),
+        "mrc_pac_nmr": (C.c_int, [H, C.c_int64, _u8p, _i64p, C.c_void_p, _i64p, _i64p, _i64p, _f64p, _f64p, _i64p, _i64p,
+                                  _i64p, C.c_int64, _i32p, _f64p, _f64p]),
+        "mrc_get_nmr_ms": (C.c_int, [H, _f64p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = the library does not export the header's symbol
@@ -192,6 +195,53 @@ def _reservoir(reservoir_in, n):
 
 def _p(a, typ):
     return None if a is None else a.ctypes.data
+
+
+def nmr_layout(bufs, sources):
+    """The host side of mrc_pac_nmr's arguments: bufs (a list of bytes-like `.pac` files) -> one byte buffer and
+    file_offset; sources (a list or tuple, one int16 [nCh][n] array per file; the same object may repeat and is then
+    staged once) -> one planar int16 buffer with src_offset / src_stride / src_frames per file.  Each source must have
+    exactly the channel count its file's header names: the library reads nCh rows of src_frames samples from the
+    address it is given and cannot see where the caller's array ends.  Also returns the number of chunks of all files
+    (the entry count of the call).  Raises ValueError before anything is read past an array."""
+    if not isinstance(sources, (list, tuple)):
+        raise ValueError("pac_nmr: sources must be a list with one int16 [nCh][n] array per file")
+    n = len(bufs)
+    if len(sources) != n:
+        raise ValueError("pac_nmr: one source per file (%d files, %d sources)" % (n, len(sources)))
+    sizes = np.fromiter((len(b) for b in bufs), dtype=np.int64, count=n)
+    file_offset = np.zeros(n + 1, np.int64)
+    np.cumsum(sizes, out=file_offset[1:])
+    data = np.frombuffer(b"".join(bytes(b) for b in bufs), np.uint8) if n else np.zeros(1, np.uint8)
+    n_entries = 0
+    planes, where = [], {}
+    src_offset = np.zeros(max(n, 1), np.int64)
+    src_stride = np.zeros(max(n, 1), np.int64)
+    src_frames = np.zeros(max(n, 1), np.int64)
+    total = 0
+    cfg, nch, ns, doff = MrcConfig(), C.c_int32(), C.c_uint32(), C.c_int64()
+    for f, s in enumerate(sources):
+        if id(s) not in where:
+            a = np.ascontiguousarray(np.asarray(s))
+            if a.ndim == 1:
+                a = a[None]
+            if a.dtype != np.int16 or a.ndim != 2:
+                raise ValueError("pac_nmr: source %d is not an int16 [nCh][n] array" % f)
+            where[id(s)] = (total, a.shape[1], a.shape[0])
+            planes.append(a.reshape(-1))
+            total += a.size
+        src_offset[f], src_frames[f], rows = where[id(s)]
+        src_stride[f] = src_frames[f]
+        raw = data[file_offset[f]:file_offset[f + 1]]
+        # (a file whose header or chunks do not read is refused by the library before it touches any source)
+        if raw.size and lib.mrc_pac_read_header(raw.ctypes.data, raw.size, C.byref(cfg), C.byref(nch), C.byref(ns),
+                                                C.byref(doff)) == 0:
+            if rows != nch.value:
+                raise ValueError("pac_nmr: file %d has %d channel(s), its source %d row(s)" % (f, nch.value, rows))
+            n_entries += max(0, int(lib.mrc_pac_scan_chunks(raw.ctypes.data, raw.size, doff.value, None, 0)))
+    # (one distinct source -- one file, or the rungs of a ladder -- is passed as it is, without a copy)
+    src = planes[0] if len(planes) == 1 else np.concatenate(planes) if planes else np.zeros(1, np.int16)
+    return data, file_offset, src, src_offset, src_stride, src_frames, n_entries
 
 
 class ChainSchedule:
@@ -778,6 +828,67 @@ class Handle:
         """device time of the last decode_pac_pcm16: H2D copy, unpack, synthesis (decode + pcm16), D2H copy (ms)"""
         ms = np.zeros(4, np.float64)
         self._check(lib.mrc_get_decode_ms(self._h, _p(ms, _f64p)))
+        return ms
+
+    def pac_nmr(self, bufs, sources, detail=False):
+        """mrc_pac_nmr: the noise-to-mask ratio of whole `.pac` files (bytes-like, one or a list) against their sources,
+        one int16 [nCh][n] array per file (the WAV's own samples, no prior hop; the same object may repeat and is then
+        uploaded once).  Returns one dict per file: nmr_max_db, nmr_total_db, disturbed_blocks, n_blocks; with
+        detail=True also shape [E, 2] (a, b per entry: block, then channel), noise and mask [E, nBands of the widest
+        block] and nmr_db = 10 log10(noise / mask) (0 ratio where mask is +inf), NaN past a block's bands."""
+        if isinstance(bufs, (bytes, bytearray, memoryview, np.ndarray)):
+            bufs = [bufs]
+            sources = [sources]
+        data, file_offset, src, src_offset, src_stride, src_frames, n_entries = nmr_layout(bufs, sources)
+        n = len(bufs)
+        mx, tot = np.zeros(max(n, 1)), np.zeros(max(n, 1))
+        dist, nblk = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
+        entry_offset = np.zeros(n + 1, np.int64)
+        cap = 0
+        shape = noise = mask = None
+
+        def call():
+            return lib.mrc_pac_nmr(self._h, n, _p(data, _u8p), _p(file_offset, _i64p), src.ctypes.data_as(C.c_void_p),
+                                   _p(src_offset, _i64p), _p(src_stride, _i64p), _p(src_frames, _i64p), _p(mx, _f64p),
+                                   _p(tot, _f64p), _p(dist, _i64p), _p(nblk, _i64p), _p(entry_offset, _i64p), cap,
+                                   _p(shape, _i32p), _p(noise, _f64p), _p(mask, _f64p))
+        if detail:
+            cap = max(1, n_entries)                # one entry per chunk (exact unless a file is refused)
+            shape = np.zeros((cap, 2), np.int32)
+            noise, mask = np.zeros((cap, MRC_MAX_BANDS)), np.zeros((cap, MRC_MAX_BANDS))
+        rc = call()
+        if detail and rc == MRC_ERR_NOMEM and int(entry_offset[n]) > cap:
+            cap = int(entry_offset[n])
+            shape = np.zeros((cap, 2), np.int32)
+            noise, mask = np.zeros((cap, MRC_MAX_BANDS)), np.zeros((cap, MRC_MAX_BANDS))
+            rc = call()
+        self._check(rc)
+        res = []
+        for f in range(n):
+            r = dict(nmr_max_db=float(mx[f]), nmr_total_db=float(tot[f]), disturbed_blocks=int(dist[f]),
+                     n_blocks=int(nblk[f]))
+            if detail:
+                e0, e1 = int(entry_offset[f]), int(entry_offset[f + 1])
+                sh = shape[e0:e1].copy()
+                keys = sh[:, 0].astype(np.int64) * 65536 + sh[:, 1]
+                uk, inv = np.unique(keys, return_inverse=True)
+                nbands = np.array([len(self.bands(int(k) // 65536, int(k) % 65536)) for k in uk], np.int64)[inv.reshape(-1)]
+                w = int(nbands.max()) if e1 > e0 else 0
+                no, ma = noise[e0:e1, :w].copy(), mask[e0:e1, :w].copy()
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    ratio = np.where(np.isinf(ma), 0.0, no / ma)
+                    db = 10.0 * np.log10(ratio)
+                past = np.arange(w)[None, :] >= nbands[:, None]
+                for a in (no, ma, db):
+                    a[past] = np.nan
+                r.update(shape=sh, noise=no, mask=ma, nmr_db=db)
+            res.append(r)
+        return res
+
+    def nmr_ms(self):
+        """device time of the last pac_nmr: H2D copy, unpack, source analysis, NMR kernels + D2H copy (ms)"""
+        ms = np.zeros(4, np.float64)
+        self._check(lib.mrc_get_nmr_ms(self._h, _p(ms, _f64p)))
         return ms
 
     def transient_peaks(self, streams, sos):

@@ -19,8 +19,16 @@ Decode direction (row f-4):  python -m mrcaudiocodec_amd.cli -d in.pac out.wav
 One library call (mrc_decode_pac_pcm16): chunk parsing and Huffman decoding, dequantise / M-S / IMDCT / window /
 overlap-add and the interleaved 16-bit PCM codes all on the GPU, then the WAV header of pcmfile.py:141-153.  The first decoded block (the MDCT's half-block delay) is dropped as in the
 reference's loop; everything after it is written, header sample count = what was decoded.
+
+Quality (mrc_pac_nmr): --nmr on an encode prints, per file written (every rung of a ladder), one JSON line with the
+noise-to-mask ratio of the file against the WAV, measured with the codec's own masking model: nmr_max_db (worst band),
+nmr_total_db (band-averaged ratio, weighted by block length), disturbed_blocks (blocks with a band whose noise exceeds
+its mask) and n_blocks.  --measure prints the same lines for existing dst file(s) against src without encoding:
+    python -m mrcaudiocodec_amd.cli in.wav out_{bps}.pac --bits-per-sample 1.5,2.86,4 --measure
 """
 import argparse
+import json
+import os
 from struct import pack, unpack
 
 import numpy as np
@@ -215,6 +223,47 @@ def decode_pac_file(pac_path, wav_path, device_id=0):
     return inter.T
 
 
+def measure_files(wav_path, pac_paths, bits_per_sample=None, device_id=0, exact_spread=False):
+    """The NMR of each `.pac` file in pac_paths against the WAV it was coded from, in one library call (mrc_pac_nmr).
+    bits_per_sample: one value per file (or None) for the report.  -> one dict per file: file, bits_per_sample and the
+    four numbers of pacfile.measure_nmr."""
+    bufs = []
+    for p in pac_paths:
+        with open(p, "rb") as fp:
+            bufs.append(fp.read())
+    rate, n_ch, num_samples, pcm = read_wav_pcm(wav_path)
+    cfg = None
+    for p, buf in zip(pac_paths, bufs):          # the WAV must be what every file was coded from: refused before any device use
+        try:
+            c, nch, _, _ = pacfile.read_header(buf)
+        except MrcError as e:
+            raise ValueError("%s: not a .pac file (%s)" % (p, e))
+        if (c.sample_rate, nch) != (rate, n_ch):
+            raise ValueError("%s holds %d channel(s) at %d Hz, %s %d channel(s) at %d Hz: not its source"
+                             % (p, nch, c.sample_rate, wav_path, n_ch, rate))
+        if cfg is None:
+            cfg = c
+    h = Handle(sample_rate=cfg.sample_rate, n_mdct_lines=cfg.n_mdct_lines, n_scale_bits=cfg.n_scale_bits,
+               n_mant_size_bits=cfg.n_mant_size_bits, device_id=device_id)
+    try:
+        if exact_spread:
+            h.set_option(1, 1)
+        res = pacfile.measure_nmr(h, bufs, np.ascontiguousarray(pcm[:, :num_samples]))
+    finally:
+        h.close()
+    bps = [None] * len(pac_paths) if bits_per_sample is None else list(bits_per_sample)
+    return [dict(file=p, bits_per_sample=b, **r) for p, b, r in zip(pac_paths, bps, res)]
+
+
+def _print_nmr(ap, a, paths, bps):
+    try:
+        res = measure_files(a.src, paths, bps, a.device, a.exact_spread)
+    except ValueError as e:
+        ap.error(str(e))
+    for r in res:
+        print(json.dumps(r))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Encode a mono or stereo 16-bit WAV to .pac (or, with -d, decode a .pac to WAV) "
                                              "on an MI355X")
@@ -231,8 +280,25 @@ def main(argv=None):
     ap.add_argument("--bits-per-sample", default=None, metavar="LIST",
                     help="target bits per sample (default 2.86, the reference's); several, comma separated (e.g. 1.5,2.86,4), "
                          "encode a rate ladder in one call, and dst must then contain {bps}")
+    ap.add_argument("--nmr", action="store_true",
+                    help="after the encode, print one JSON line per file written with its noise-to-mask ratio against src")
+    ap.add_argument("--measure", action="store_true",
+                    help="do not encode: print the noise-to-mask ratio of the existing dst file(s) against src, one JSON "
+                         "line per file (dst may hold {bps} with --bits-per-sample)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.decode and (a.nmr or a.measure):
+        ap.error("-d decodes: --nmr and --measure apply to .pac files coded from src")
+    if a.measure:
+        rates = None if a.bits_per_sample is None else parse_bits_per_sample(a.bits_per_sample)
+        if rates is not None and len(rates) > 1 and "{bps}" not in a.dst:
+            ap.error("several bit rates: dst must contain {bps} (e.g. out_{bps}.pac)")
+        paths = [a.dst] if rates is None else ladder_paths(a.dst, rates)
+        missing = [p for p in paths if not os.path.isfile(p)]
+        if missing:
+            ap.error("--measure: no such file: %s" % ", ".join(missing))
+        _print_nmr(ap, a, paths, None if rates is None else [v for (_, v) in rates])
+        return
     if a.decode:
         pcm = decode_pac_file(a.src, a.dst, a.device)
         print("%s: %d channels x %d samples" % (a.dst, pcm.shape[0], pcm.shape[1]))
@@ -247,6 +313,8 @@ def main(argv=None):
         datas = encode_wav(a.src, a.dst, not a.no_huffman, a.device, exact_spread=a.exact_spread, bits_per_sample=a.bits_per_sample)
         for path, d in zip(ladder_paths(a.dst, rates), datas):
             print("%s: %d bytes" % (path, len(d)))
+        if a.nmr:
+            _print_nmr(ap, a, ladder_paths(a.dst, rates), [v for (_, v) in rates])
         return
     data = encode_wav(a.src, a.dst, not a.no_huffman, a.device, exact_spread=a.exact_spread, certify=cert,
                       bits_per_sample=a.bits_per_sample)
@@ -258,6 +326,8 @@ def main(argv=None):
                  cert["ms_switch_near_threshold"], cert["peak_near_ties"], cert["node_chunks_sent_back"]))
         if "bytes_equal_exact_spread" in cert:
             print("  re-encoded with --exact-spread: bytes %s" % ("identical" if cert["bytes_equal_exact_spread"] else "DIFFER"))
+    if a.nmr:                            # one rate: the one given, else the one a new handle encodes at (pacfileThem.py:1108)
+        _print_nmr(ap, a, [a.dst], [2.86 if a.bits_per_sample is None else parse_bits_per_sample(a.bits_per_sample)[0][1]])
 
 
 if __name__ == "__main__":

@@ -125,6 +125,7 @@ void mrc_destroy(mrc_handle* h) {
     h->packWs.release();
     h->chain.release();
     h->dec.release();
+    h->nmr.release();
     h->ws.release();
     for (DevBuf& b : h->stage) b.release();
     h->smallBatch.release();

@@ -18,9 +18,7 @@
 
 using namespace mrc;
 
-namespace {
-
-inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
+namespace mrc {
 
 UnpackParams unpack_params(const mrc_config& c) {
     UnpackParams P;
@@ -33,29 +31,34 @@ UnpackParams unpack_params(const mrc_config& c) {
     return P;
 }
 
-// block shapes in the order of UnpackBands: (L,L), (L,S), (S,L), (S,S)
-inline void shape_ab(const mrc_config& c, int s, int* a, int* b) {
-    *a = (s & 2) ? c.n_short : c.n_mdct_lines;
-    *b = (s & 1) ? c.n_short : c.n_mdct_lines;
+// the band counts of the four shapes as the parser sees them (-1: a shape without a usable band table); host only
+void decode_band_counts(const mrc_config& c, int nBands[4], std::vector<int>* cnt /* nullable: [4] */) {
+    for (int s = 0; s < 4; ++s) {
+        int a, b;
+        shape_ab(c, s, &a, &b);
+        std::vector<int> tmp;
+        std::vector<int>& v = cnt ? cnt[s] : tmp;
+        // (a shape of more lines than n_mdct_lines would not fit mrc_unpack_blocks' fixed stride either: refused)
+        if (!band_table(c, a, b, &v) || (int)v.size() > MRC_MAX_BANDS || (a + b) / 2 > c.n_mdct_lines)
+            v.clear(), nBands[s] = -1;
+        else nBands[s] = (int)v.size();
+    }
 }
 
 // decode tables + band tables of the four shapes in device memory, once per handle
-int ensure_consts(mrc_handle* h) {
+int ensure_decode_consts(mrc_handle* h) {
     DecodeBufs& d = h->dec;
     MRC_HIP(h, hipSetDevice(h->device));
     if (d.consts.p) return MRC_OK;
     std::vector<int> cnt[4];
-    size_t bandOff[4], bytes = align_up(sizeof(UnpackTables));
+    size_t bandOff[4], bytes = align256(sizeof(UnpackTables));
+    decode_band_counts(h->cfg, d.bands.nBands, cnt);
     for (int s = 0; s < 4; ++s) {
         int a, b;
         shape_ab(h->cfg, s, &a, &b);
-        // (a shape of more lines than n_mdct_lines would not fit mrc_unpack_blocks' fixed stride either: refused)
-        if (!band_table(h->cfg, a, b, &cnt[s]) || (int)cnt[s].size() > MRC_MAX_BANDS || (a + b) / 2 > h->cfg.n_mdct_lines)
-            cnt[s].clear(), d.bands.nBands[s] = -1;
-        else d.bands.nBands[s] = (int)cnt[s].size();
         d.bands.halfN[s] = (a + b) / 2;
         bandOff[s] = bytes;
-        bytes += align_up(sizeof(int) * (cnt[s].size() + 1));
+        bytes += align256(sizeof(int) * (cnt[s].size() + 1));
     }
     std::vector<unsigned char> blob(bytes, 0);
     unpack_tables((UnpackTables*)blob.data());
@@ -70,7 +73,7 @@ int ensure_consts(mrc_handle* h) {
     return MRC_OK;
 }
 
-const char* status_text(int flag) {
+const char* unpack_status_text(int flag) {
     if (flag & (1 << kUnpackBadTable)) return "table id not in {0..3, 15}";
     if (flag & (1 << kUnpackBadAlloc)) return "bit allocation above 16";
     if (flag & (1 << kUnpackBadCode)) return "bits that are no Huffman code of the table";
@@ -79,7 +82,7 @@ const char* status_text(int flag) {
 }
 
 // err <- {0, INT_MAX} on the stream
-int reset_err(mrc_handle* h, hipStream_t st) {
+int reset_unpack_err(mrc_handle* h, hipStream_t st) {
     DecodeBufs& d = h->dec;
     MRC_HIP(h, d.err.reserve(sizeof(UnpackErr)));
     UnpackErr* e = d.err.as<UnpackErr>();
@@ -101,13 +104,123 @@ void copy_host(void* dst, const void* src, size_t n) {
     for (auto& th : pool) th.join();
 }
 
-struct FileInfo {
-    int nch = 0;
-    int64_t firstChunk = 0, nChunks = 0;   // into the call's chunk list
-    int64_t xStart = 0, extent = 0, total = 0;
-};
+// ---- host plan, pass 1: headers, chunks, block shapes, where each file's samples go
+int pac_plan_scan(mrc_handle* h, const char* fn, int64_t n_files, const uint8_t* buf, const int64_t* file_offset,
+                  PacPlan* p) {
+    const mrc_config& hc = h->cfg;
+    const UnpackParams P = unpack_params(hc);
+    int nBands[4];
+    decode_band_counts(hc, nBands, nullptr);
+    char msg[200];
+    p->files.assign((size_t)n_files, PacFilePlan{});
+    p->chunkOff.clear();
+    p->chunkShape.clear();
+    p->planeStride = 0;
+    p->anyStereo = false;
+    for (int64_t f = 0; f < n_files; ++f) {
+        const uint8_t* fb = buf + file_offset[f];
+        const int64_t flen = file_offset[f + 1] - file_offset[f];
+        mrc_config fc = hc;
+        int32_t nch = 0;
+        uint32_t ns = 0;
+        int64_t doff = 0;
+        if (mrc_pac_read_header(fb, flen, &fc, &nch, &ns, &doff) != MRC_OK) {
+            std::snprintf(msg, sizeof msg, "%s: file %lld: not a .pac header (", fn, (long long)f);
+            return fail(h, MRC_ERR_INVALID, msg + create_error() + ")");
+        }
+        const struct { const char* name; int file, handle; } par[4] = {
+            {"sample_rate", fc.sample_rate, hc.sample_rate}, {"n_mdct_lines", fc.n_mdct_lines, hc.n_mdct_lines},
+            {"n_scale_bits", fc.n_scale_bits, hc.n_scale_bits}, {"n_mant_size_bits", fc.n_mant_size_bits, hc.n_mant_size_bits}};
+        for (const auto& q : par)
+            if (q.file != q.handle) {
+                std::snprintf(msg, sizeof msg, "%s: file %lld has %s = %d, the handle was created with %d", fn,
+                              (long long)f, q.name, q.file, q.handle);
+                return fail(h, MRC_ERR_INVALID, msg);
+            }
+        PacFilePlan& fi = p->files[(size_t)f];
+        fi.nch = nch;
+        fi.firstChunk = (int64_t)p->chunkOff.size();
+        for (int64_t off = doff; off + 4 <= flen;) {       // mrc_pac_scan_chunks
+            const int64_t nBytes = unpack_u32le(fb + off);
+            if (off + 4 + nBytes > flen) {
+                std::snprintf(msg, sizeof msg, "%s: file %lld: truncated chunk at byte %lld", fn, (long long)f,
+                              (long long)off);
+                return fail(h, MRC_ERR_INVALID, msg);
+            }
+            int shape;
+            if (unpack_chunk_shape(fb + off + 4, nBytes, P, &shape) != kUnpackOk || nBands[shape] < 0) {
+                std::snprintf(msg, sizeof msg, "%s: file %lld: chunk at byte %lld has no block shape", fn, (long long)f,
+                              (long long)off);
+                return fail(h, MRC_ERR_INVALID, msg);
+            }
+            p->chunkOff.push_back(file_offset[f] - file_offset[0] + off);
+            p->chunkShape.push_back((unsigned char)shape);
+            off += 4 + nBytes;
+        }
+        fi.nChunks = (int64_t)p->chunkOff.size() - fi.firstChunk;
+        if (fi.nChunks % nch) {
+            std::snprintf(msg, sizeof msg, "%s: file %lld: %lld chunks for %d channels", fn, (long long)f,
+                          (long long)fi.nChunks, nch);
+            return fail(h, MRC_ERR_INVALID, msg);
+        }
+        int64_t start = 0;
+        for (int64_t i = 0; i < fi.nChunks / nch; ++i) {
+            const int s = p->chunkShape[(size_t)(fi.firstChunk + i * nch)];
+            if (nch == 2 && p->chunkShape[(size_t)(fi.firstChunk + i * nch + 1)] != s) {
+                std::snprintf(msg, sizeof msg, "%s: file %lld: the chunks of block %lld differ in shape", fn, (long long)f,
+                              (long long)i);
+                return fail(h, MRC_ERR_INVALID, msg);
+            }
+            int a, b;
+            shape_ab(hc, s, &a, &b);
+            fi.extent = std::max(fi.extent, start + a + b);   // (a file whose shapes do not chain still stays in its plane)
+            fi.total = start + a + b;                          // pacfile.decode_pac: last block's start + a + b
+            start += a;
+        }
+        fi.xStart = p->planeStride;
+        p->planeStride += fi.extent;
+        p->anyStereo |= nch == 2;
+    }
+    return MRC_OK;
+}
 
-}  // namespace
+// ---- pass 2: groups and slots
+int pac_plan_groups(mrc_handle* h, const char* fn, PacPlan* p) {
+    const DecodeBufs& d = h->dec;
+    for (int64_t k = 0; k < 2 * kUnpackGroups; ++k) p->nCat[k] = 0;
+    for (int g = 0; g < kUnpackGroups; ++g) p->nSlots[g] = 0;
+    for (int s = 0; s < 4; ++s) p->hs[s] = nullptr;
+    for (const PacFilePlan& fi : p->files) {
+        const int64_t nb = fi.nChunks / fi.nch, nJoint = (fi.nch == 2 && nb > 1) ? nb - 1 : 0;
+        for (int64_t i = 0; i < nb; ++i) {
+            const int s = p->chunkShape[(size_t)(fi.firstChunk + i * fi.nch)];
+            if (i < nJoint) { p->nSlots[s * 2] += 1; p->nCat[s * 4] += 1; p->nCat[s * 4 + 1] += 1; }
+            else { p->nSlots[s * 2 + 1] += fi.nch; p->nCat[s * 4 + 2] += fi.nch; }
+        }
+    }
+    for (int64_t g = 0, q = 0; g < kUnpackGroups; q += p->nSlots[g], ++g) p->slotBase[g] = q;
+    for (int s = 0; s < 4; ++s)
+        if (p->nSlots[s * 2] + p->nSlots[s * 2 + 1]) {
+            int a, b;
+            shape_ab(h->cfg, s, &a, &b);
+            MRC_TRY(get_shape(h, a, b, &p->hs[s]));
+            if (p->hs[s]->dev.nBands != d.bands.nBands[s])
+                return fail(h, MRC_ERR_INVALID, std::string(fn) + ": band tables disagree");
+        }
+    p->totalSlots = 0;
+    for (int g = 0; g < kUnpackGroups; ++g) p->totalSlots += p->nSlots[g];
+    p->gBytes = 0;
+    for (int g = 0; g < kUnpackGroups; ++g) {
+        const int s = g / 2, joint = !(g & 1), nb = std::max(d.bands.nBands[s], 0), half = d.bands.halfN[s];
+        const int64_t n = p->nSlots[g], ns = joint ? 2 : 1;
+        const size_t sz[5] = {sizeof(int) * n * (joint ? 4 : 1), joint ? sizeof(int) * n * nb : 0, sizeof(int) * n * ns * nb,
+                              sizeof(int) * n * ns * nb, sizeof(int) * n * ns * half};
+        for (int k = 0; k < 5; ++k) { p->gOff[g][k] = p->gBytes; p->gBytes += align256(sz[k]); }
+    }
+    return MRC_OK;
+}
+
+}  // namespace mrc
 
 extern "C" {
 
@@ -120,9 +233,9 @@ int mrc_dev_unpack_blocks(mrc_handle* h, int64_t n_blocks, int n_channels, int j
         n_blocks < 0 || n_channels < 1 || n_channels > 2 || (joint && (n_channels != 2 || !ms_switch)) || len < 0 ||
         c.n_mdct_lines <= 0 || c.n_scale_bits < 1 || c.n_scale_bits > 4 || c.n_mant_size_bits < 1 || c.n_mant_size_bits > 8)
         return fail(h, MRC_ERR_INVALID, "mrc_dev_unpack_blocks: bad argument");
-    MRC_TRY(ensure_consts(h));
+    MRC_TRY(ensure_decode_consts(h));
     hipStream_t st = pick_stream(h, stream);
-    MRC_TRY(reset_err(h, st));
+    MRC_TRY(reset_unpack_err(h, st));
     UnpackFixedOut O{a, b, huff_table, overall_scale, ms_switch, scale_factor, bit_alloc, mantissa};
     MRC_HIP(h, launch_unpack_fixed(unpack_params(c), h->dec.bands, h->dec.consts.as<UnpackTables>(), n_blocks, n_channels,
                                    joint ? 1 : 0, buf, len, chunk_offset, O, h->dec.err.as<UnpackErr>(), st));
@@ -131,7 +244,7 @@ int mrc_dev_unpack_blocks(mrc_handle* h, int64_t n_blocks, int n_channels, int j
     if (h->dec.pinErr->flag) {
         char msg[160];
         std::snprintf(msg, sizeof msg, "mrc_dev_unpack_blocks: chunk %d: %s", h->dec.pinErr->firstBad,
-                      status_text(h->dec.pinErr->flag));
+                      unpack_status_text(h->dec.pinErr->flag));
         return fail(h, MRC_ERR_INVALID, msg);
     }
     return MRC_OK;
@@ -142,91 +255,28 @@ int mrc_decode_pac_pcm16(mrc_handle* h, int64_t n_files, const uint8_t* buf, con
     if (!h) return MRC_ERR_INVALID;
     if (n_files < 0 || !file_offset || !sample_offset || !n_channels || out_cap < 0 || (n_files > 0 && !buf))
         return fail(h, MRC_ERR_INVALID, "mrc_decode_pac_pcm16: bad argument");
-    const mrc_config& hc = h->cfg;
-    const int L = hc.n_mdct_lines;
-    const UnpackParams P = unpack_params(hc);
+    const int L = h->cfg.n_mdct_lines;
+    const UnpackParams P = unpack_params(h->cfg);
     char msg[200];
     sample_offset[0] = 0;
     for (int64_t f = 0; f < n_files; ++f)
         if (file_offset[0] < 0 || file_offset[f + 1] < file_offset[f])
             return fail(h, MRC_ERR_INVALID, "mrc_decode_pac_pcm16: file_offset must not decrease");
     if (n_files == 0) return MRC_OK;
-    MRC_TRY(ensure_consts(h));
+    MRC_TRY(ensure_decode_consts(h));
     DecodeBufs& d = h->dec;
 
-    // ---- host plan, pass 1: headers, chunks, block shapes, where each file's samples go
+    // ---- host plan (shared with mrc_pac_nmr): headers, chunks, block shapes, where each file's samples go
     const uint8_t* base = buf + file_offset[0];
     const int64_t inBytes = file_offset[n_files] - file_offset[0];
-    std::vector<FileInfo> files((size_t)n_files);
-    std::vector<int64_t> chunkOff;                 // relative to base
-    std::vector<unsigned char> chunkShape;
-    int64_t planeStride = 0;
-    bool anyStereo = false;
+    PacPlan pl;
+    MRC_TRY(pac_plan_scan(h, "mrc_decode_pac_pcm16", n_files, buf, file_offset, &pl));
+    const int64_t planeStride = pl.planeStride;
+    const bool anyStereo = pl.anyStereo;
     for (int64_t f = 0; f < n_files; ++f) {
-        const uint8_t* fb = buf + file_offset[f];
-        const int64_t flen = file_offset[f + 1] - file_offset[f];
-        mrc_config fc = hc;
-        int32_t nch = 0;
-        uint32_t ns = 0;
-        int64_t doff = 0;
-        if (mrc_pac_read_header(fb, flen, &fc, &nch, &ns, &doff) != MRC_OK) {
-            std::snprintf(msg, sizeof msg, "mrc_decode_pac_pcm16: file %lld: not a .pac header (", (long long)f);
-            return fail(h, MRC_ERR_INVALID, msg + create_error() + ")");
-        }
-        const struct { const char* name; int file, handle; } par[4] = {
-            {"sample_rate", fc.sample_rate, hc.sample_rate}, {"n_mdct_lines", fc.n_mdct_lines, hc.n_mdct_lines},
-            {"n_scale_bits", fc.n_scale_bits, hc.n_scale_bits}, {"n_mant_size_bits", fc.n_mant_size_bits, hc.n_mant_size_bits}};
-        for (const auto& q : par)
-            if (q.file != q.handle) {
-                std::snprintf(msg, sizeof msg, "mrc_decode_pac_pcm16: file %lld has %s = %d, the handle was created with %d",
-                              (long long)f, q.name, q.file, q.handle);
-                return fail(h, MRC_ERR_INVALID, msg);
-            }
-        FileInfo& fi = files[(size_t)f];
-        fi.nch = nch;
-        fi.firstChunk = (int64_t)chunkOff.size();
-        for (int64_t off = doff; off + 4 <= flen;) {       // mrc_pac_scan_chunks
-            const int64_t nBytes = unpack_u32le(fb + off);
-            if (off + 4 + nBytes > flen) {
-                std::snprintf(msg, sizeof msg, "mrc_decode_pac_pcm16: file %lld: truncated chunk at byte %lld", (long long)f,
-                              (long long)off);
-                return fail(h, MRC_ERR_INVALID, msg);
-            }
-            int shape;
-            if (unpack_chunk_shape(fb + off + 4, nBytes, P, &shape) != kUnpackOk || d.bands.nBands[shape] < 0) {
-                std::snprintf(msg, sizeof msg, "mrc_decode_pac_pcm16: file %lld: chunk at byte %lld has no block shape",
-                              (long long)f, (long long)off);
-                return fail(h, MRC_ERR_INVALID, msg);
-            }
-            chunkOff.push_back(file_offset[f] - file_offset[0] + off);
-            chunkShape.push_back((unsigned char)shape);
-            off += 4 + nBytes;
-        }
-        fi.nChunks = (int64_t)chunkOff.size() - fi.firstChunk;
-        if (fi.nChunks % nch) {
-            std::snprintf(msg, sizeof msg, "mrc_decode_pac_pcm16: file %lld: %lld chunks for %d channels", (long long)f,
-                          (long long)fi.nChunks, nch);
-            return fail(h, MRC_ERR_INVALID, msg);
-        }
-        int64_t start = 0;
-        for (int64_t i = 0; i < fi.nChunks / nch; ++i) {
-            const int s = chunkShape[(size_t)(fi.firstChunk + i * nch)];
-            if (nch == 2 && chunkShape[(size_t)(fi.firstChunk + i * nch + 1)] != s) {
-                std::snprintf(msg, sizeof msg, "mrc_decode_pac_pcm16: file %lld: the chunks of block %lld differ in shape",
-                              (long long)f, (long long)i);
-                return fail(h, MRC_ERR_INVALID, msg);
-            }
-            int a, b;
-            shape_ab(hc, s, &a, &b);
-            fi.extent = std::max(fi.extent, start + a + b);   // (a file whose shapes do not chain still stays in its plane)
-            fi.total = start + a + b;                          // pacfile.decode_pac: last block's start + a + b
-            start += a;
-        }
-        fi.xStart = planeStride;
-        planeStride += fi.extent;
-        anyStereo |= nch == 2;
-        n_channels[f] = nch;
-        sample_offset[f + 1] = sample_offset[f] + std::max<int64_t>(0, fi.total - L) * nch;
+        const PacFilePlan& fi = pl.files[(size_t)f];
+        n_channels[f] = fi.nch;
+        sample_offset[f + 1] = sample_offset[f] + std::max<int64_t>(0, fi.total - L) * fi.nch;
     }
     const int64_t nOut = sample_offset[n_files];
     if (nOut > out_cap || (nOut > 0 && !out)) {
@@ -236,49 +286,22 @@ int mrc_decode_pac_pcm16(mrc_handle* h, int64_t n_files, const uint8_t* buf, con
     }
 
     // ---- pass 2: groups and slots; plan entries ordered by (group, joint channel) so that a wave parses one kind
-    int64_t nSlots[kUnpackGroups] = {}, nCat[2 * kUnpackGroups] = {};
-    for (const FileInfo& fi : files) {
-        const int64_t nb = fi.nChunks / fi.nch, nJoint = (fi.nch == 2 && nb > 1) ? nb - 1 : 0;
-        for (int64_t i = 0; i < nb; ++i) {
-            const int s = chunkShape[(size_t)(fi.firstChunk + i * fi.nch)];
-            if (i < nJoint) { nSlots[s * 2] += 1; nCat[s * 4] += 1; nCat[s * 4 + 1] += 1; }
-            else { nSlots[s * 2 + 1] += fi.nch; nCat[s * 4 + 2] += fi.nch; }
-        }
-    }
-    const int64_t nChunks = (int64_t)chunkOff.size();
-    int64_t catPos[2 * kUnpackGroups], slotBase[kUnpackGroups];
-    for (int64_t k = 0, p = 0; k < 2 * kUnpackGroups; p += nCat[k], ++k) catPos[k] = p;
-    for (int64_t g = 0, p = 0; g < kUnpackGroups; p += nSlots[g], ++g) slotBase[g] = p;
-    const HostShape* hs[4] = {};
-    for (int s = 0; s < 4; ++s)
-        if (nSlots[s * 2] + nSlots[s * 2 + 1]) {
-            int a, b;
-            shape_ab(hc, s, &a, &b);
-            MRC_TRY(get_shape(h, a, b, &hs[s]));
-            if (hs[s]->dev.nBands != d.bands.nBands[s]) return fail(h, MRC_ERR_INVALID, "mrc_decode_pac_pcm16: band tables disagree");
-        }
-    int64_t totalSlots = 0;
-    for (int g = 0; g < kUnpackGroups; ++g) totalSlots += nSlots[g];
+    MRC_TRY(pac_plan_groups(h, "mrc_decode_pac_pcm16", &pl));
+    const int64_t nChunks = pl.nChunks();
+    const int64_t* nSlots = pl.nSlots;
+    const int64_t* slotBase = pl.slotBase;
+    const int64_t totalSlots = pl.totalSlots;
 
     // staging layout (one H2D copy): bytes | plan | groups | block offsets | outStart [n+1] | xStart [n] | nch [n]
-    const size_t oPlan = align_up((size_t)inBytes), oGroups = oPlan + align_up(sizeof(UnpackPlanEntry) * nChunks),
-                 oOffs = oGroups + align_up(sizeof(UnpackGroupDev) * kUnpackGroups),
-                 oOutStart = oOffs + align_up(sizeof(long long) * totalSlots),
-                 oXStart = oOutStart + align_up(sizeof(long long) * (n_files + 1)),
-                 oNch = oXStart + align_up(sizeof(long long) * n_files), inTotal = oNch + align_up(sizeof(int) * n_files);
-    // device arrays of the groups
-    size_t gOff[kUnpackGroups][5], gBytes = 0;
-    for (int g = 0; g < kUnpackGroups; ++g) {
-        const int s = g / 2, joint = !(g & 1), nb = std::max(d.bands.nBands[s], 0), half = d.bands.halfN[s];
-        const int64_t n = nSlots[g], ns = joint ? 2 : 1;
-        const size_t sz[5] = {sizeof(int) * n * (joint ? 4 : 1), joint ? sizeof(int) * n * nb : 0, sizeof(int) * n * ns * nb,
-                              sizeof(int) * n * ns * nb, sizeof(int) * n * ns * half};
-        for (int k = 0; k < 5; ++k) { gOff[g][k] = gBytes; gBytes += align_up(sz[k]); }
-    }
+    const size_t oPlan = align256((size_t)inBytes), oGroups = oPlan + align256(sizeof(UnpackPlanEntry) * nChunks),
+                 oOffs = oGroups + align256(sizeof(UnpackGroupDev) * kUnpackGroups),
+                 oOutStart = oOffs + align256(sizeof(long long) * totalSlots),
+                 oXStart = oOutStart + align256(sizeof(long long) * (n_files + 1)),
+                 oNch = oXStart + align256(sizeof(long long) * n_files), inTotal = oNch + align256(sizeof(int) * n_files);
     const int64_t xDoubles = planeStride * (anyStereo ? 2 : 1);
     MRC_HIP(h, d.pinIn.reserve(inTotal));
     MRC_HIP(h, d.in.reserve(inTotal));
-    MRC_HIP(h, d.groups.reserve(std::max<size_t>(gBytes, 256)));
+    MRC_HIP(h, d.groups.reserve(std::max<size_t>(pl.gBytes, 256)));
     MRC_HIP(h, d.x.reserve(std::max<size_t>(sizeof(double) * xDoubles, 256)));
     MRC_HIP(h, d.pcm.reserve(std::max<size_t>(sizeof(int16_t) * nOut, 256)));
     MRC_HIP(h, d.pinOut.reserve(std::max<size_t>(sizeof(int16_t) * nOut, 256)));
@@ -291,46 +314,14 @@ int mrc_decode_pac_pcm16(mrc_handle* h, int64_t n_files, const uint8_t* buf, con
     long long* outStart = (long long*)(pin + oOutStart);
     long long* xStart = (long long*)(pin + oXStart);
     int* nchDev = (int*)(pin + oNch);
-    unsigned char* gBase = d.groups.as<unsigned char>();
-    for (int g = 0; g < kUnpackGroups; ++g) {
-        const int s = g / 2;
-        UnpackGroupDev& G = gd[g];
-        G.shape = s;
-        G.joint = !(g & 1);
-        G.nb = std::max(d.bands.nBands[s], 0);
-        G.halfN = d.bands.halfN[s];
-        int** ptr[5] = {&G.oscale, &G.ms, &G.sf, &G.ba, &G.mant};
-        for (int k = 0; k < 5; ++k) *ptr[k] = (int*)(gBase + gOff[g][k]);
-    }
-    int64_t slotNext[kUnpackGroups] = {};
+    pac_plan_fill(h->cfg, d, pl, plan, gd, d.groups.as<unsigned char>(),
+                  [&](int64_t f, int64_t, int g, int slot, int ch, int64_t start) {
+                      offs[slotBase[g] + slot] = ch * planeStride + pl.files[(size_t)f].xStart + start;
+                  });
     for (int64_t f = 0; f < n_files; ++f) {
-        const FileInfo& fi = files[(size_t)f];
-        const int64_t nb = fi.nChunks / fi.nch, nJoint = (fi.nch == 2 && nb > 1) ? nb - 1 : 0;
-        int64_t start = 0;
-        for (int64_t i = 0; i < nb; ++i) {
-            const int64_t c0 = fi.firstChunk + i * fi.nch;
-            const int s = chunkShape[(size_t)c0];
-            if (i < nJoint) {
-                const int g = s * 2;
-                const int slot = (int)slotNext[g]++;
-                plan[catPos[s * 4]++] = UnpackPlanEntry{chunkOff[(size_t)c0], g * 2, slot};
-                plan[catPos[s * 4 + 1]++] = UnpackPlanEntry{chunkOff[(size_t)c0 + 1], g * 2 + 1, slot};
-                offs[slotBase[g] + slot] = fi.xStart + start;
-            } else {
-                const int g = s * 2 + 1;
-                for (int ch = 0; ch < fi.nch; ++ch) {
-                    const int slot = (int)slotNext[g]++;
-                    plan[catPos[s * 4 + 2]++] = UnpackPlanEntry{chunkOff[(size_t)c0 + ch], g * 2, slot};
-                    offs[slotBase[g] + slot] = ch * planeStride + fi.xStart + start;
-                }
-            }
-            int a, b;
-            shape_ab(hc, s, &a, &b);
-            start += a;
-        }
         outStart[f] = sample_offset[f];
-        xStart[f] = fi.xStart;
-        nchDev[f] = fi.nch;
+        xStart[f] = pl.files[(size_t)f].xStart;
+        nchDev[f] = pl.files[(size_t)f].nch;
     }
     outStart[n_files] = nOut;
 
@@ -340,7 +331,7 @@ int mrc_decode_pac_pcm16(mrc_handle* h, int64_t n_files, const uint8_t* buf, con
     MRC_HIP(h, hipEventRecord(d.ev[0], st));
     MRC_HIP(h, hipMemcpyAsync(din, pin, inTotal, hipMemcpyHostToDevice, st));
     MRC_HIP(h, hipEventRecord(d.ev[1], st));
-    MRC_TRY(reset_err(h, st));
+    MRC_TRY(reset_unpack_err(h, st));
     MRC_HIP(h, launch_unpack_dense(P, d.bands, d.consts.as<UnpackTables>(), nChunks, (const UnpackPlanEntry*)(din + oPlan),
                                    din, inBytes, (const UnpackGroupDev*)(din + oGroups), d.err.as<UnpackErr>(), st));
     MRC_HIP(h, hipEventRecord(d.ev[2], st));
@@ -351,7 +342,7 @@ int mrc_decode_pac_pcm16(mrc_handle* h, int64_t n_files, const uint8_t* buf, con
         const int64_t at = c < nChunks ? plan[c].off + file_offset[0] : 0;
         const int64_t f = std::upper_bound(file_offset, file_offset + n_files + 1, at) - file_offset - 1;
         std::snprintf(msg, sizeof msg, "mrc_decode_pac_pcm16: file %lld: chunk at byte %lld: %s", (long long)f,
-                      (long long)(at - file_offset[std::max<int64_t>(f, 0)]), status_text(d.pinErr->flag));
+                      (long long)(at - file_offset[std::max<int64_t>(f, 0)]), unpack_status_text(d.pinErr->flag));
         return fail(h, MRC_ERR_INVALID, msg);
     }
     double* x = d.x.as<double>();
@@ -359,7 +350,7 @@ int mrc_decode_pac_pcm16(mrc_handle* h, int64_t n_files, const uint8_t* buf, con
     for (int g = 0; g < kUnpackGroups; ++g) {
         if (!nSlots[g]) continue;
         const UnpackGroupDev& G = gd[g];
-        MRC_HIP(h, launch_decode(hs[g / 2]->dev, nSlots[g], G.joint ? 2 : 1, G.oscale, G.joint ? G.ms : nullptr, G.sf, G.ba,
+        MRC_HIP(h, launch_decode(pl.hs[g / 2]->dev, nSlots[g], G.joint ? 2 : 1, G.oscale, G.joint ? G.ms : nullptr, G.sf, G.ba,
                                  G.mant, (const int64_t*)(din + oOffs) + slotBase[g], x, G.joint ? x + planeStride : nullptr,
                                  st));
     }

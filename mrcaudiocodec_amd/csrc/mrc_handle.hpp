@@ -132,6 +132,124 @@ struct DecodeBufs {
     }
 };
 
+// Noise-to-mask ratio of `.pac` files against their source (mrc_api_nmr.cpp): reused from call to call.  The parsing
+// tables, the error word and its page-locked copy are DecodeBufs'.
+struct NmrBufs {
+    DevBuf in;                       // one H2D copy: bytes | plan | groups | entries | analysis offsets | file table | sources
+    DevBuf groups;                   // dense per-(shape, kind) arrays of the parsed chunks
+    DevBuf planes;                   // padded int16 source planes
+    DevBuf lines, thresh, oscale, smr;   // source analysis per shape: X, T, overall scale, SMR (unused)
+    DevBuf out;                      // one D2H copy: per-file summaries | band noise | band mask
+    DevBuf stat;                     // per entry: max r_j, b * mean r_j
+    PinnedBuf pinIn, pinOut;
+    hipEvent_t ev[5] = {};           // start | copied in | unpacked | source analysed | reduced and copied out
+    double ms[4] = {0, 0, 0, 0};
+    void release() {
+        for (DevBuf* b : {&in, &groups, &planes, &lines, &thresh, &oscale, &smr, &out, &stat}) b->release();
+        pinIn.release();
+        pinOut.release();
+        for (auto& e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    }
+};
+
+// ---- the host plan of whole `.pac` files, shared by mrc_decode_pac_pcm16 and mrc_pac_nmr (mrc_api_decode.cpp)
+// Blocks are grouped exactly as pacfile.decode_pac groups them: a stereo file of more than one block is joint blocks
+// followed by the two non-joint chunks Close() wrote, every other file is non-joint blocks.  A group is a (block shape,
+// kind): group = shape * 2 + (non-joint), shapes in the order of UnpackBands: (L,L), (L,S), (S,L), (S,S).
+struct PacFilePlan {
+    int nch = 0;
+    int64_t firstChunk = 0, nChunks = 0;   // into the call's chunk list
+    int64_t xStart = 0, extent = 0, total = 0;   // where the file's decoded plane starts; its length; last start + a + b
+};
+struct PacPlan {
+    // pac_plan_scan
+    std::vector<PacFilePlan> files;
+    std::vector<int64_t> chunkOff;         // relative to the first file's first byte
+    std::vector<unsigned char> chunkShape;
+    int64_t planeStride = 0;               // sum of the files' extents
+    bool anyStereo = false;
+    // pac_plan_groups
+    int64_t nSlots[kUnpackGroups] = {}, nCat[2 * kUnpackGroups] = {}, slotBase[kUnpackGroups] = {}, totalSlots = 0;
+    const HostShape* hs[4] = {};
+    size_t gOff[kUnpackGroups][5] = {}, gBytes = 0;   // the groups' dense arrays in one device allocation
+    int64_t nChunks() const { return (int64_t)chunkOff.size(); }
+    int64_t nBlocks(int64_t f) const { return files[(size_t)f].nChunks / files[(size_t)f].nch; }
+    int64_t nJoint(int64_t f) const {
+        const PacFilePlan& fi = files[(size_t)f];
+        return (fi.nch == 2 && fi.nChunks / 2 > 1) ? fi.nChunks / 2 - 1 : 0;
+    }
+    int shape(int64_t f, int64_t i) const {
+        const PacFilePlan& fi = files[(size_t)f];
+        return chunkShape[(size_t)(fi.firstChunk + i * fi.nch)];
+    }
+};
+
+// block shapes in the order of UnpackBands: (L,L), (L,S), (S,L), (S,S)
+inline void shape_ab(const mrc_config& c, int s, int* a, int* b) {
+    *a = (s & 2) ? c.n_short : c.n_mdct_lines;
+    *b = (s & 1) ? c.n_short : c.n_mdct_lines;
+}
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+UnpackParams unpack_params(const mrc_config& c);
+int ensure_decode_consts(mrc_handle* h);           // decode tables + the four shapes' band tables, once per handle
+void decode_band_counts(const mrc_config& c, int nBands[4], std::vector<int>* cnt /* nullable: [4] */);   // host only
+int reset_unpack_err(mrc_handle* h, hipStream_t st);
+const char* unpack_status_text(int flag);
+void copy_host(void* dst, const void* src, size_t n);   // memcpy over a few host threads for large copies
+// headers, the handle's parameters, chunk scan with shape bits, block positions (host only: no device state is read or
+// touched).  fn names the entry point in errors.
+int pac_plan_scan(mrc_handle* h, const char* fn, int64_t n_files, const uint8_t* buf, const int64_t* file_offset,
+                  PacPlan* p);
+// slots per group, the shapes' tables and the layout of the groups' dense arrays
+int pac_plan_groups(mrc_handle* h, const char* fn, PacPlan* p);
+// Staging of the parse: the plan entries (ordered by (group, joint channel), so that a wave parses one kind) and the
+// group descriptors, with gBase the device address of the dense arrays.  visit(f, i, g, slot, ch, start) once per joint
+// block (ch = 0; the slot holds both channels) and once per channel of a non-joint block; start = p_i, the block's
+// position in its file.
+template <class Visit>
+void pac_plan_fill(const mrc_config& cfg, const DecodeBufs& d, const PacPlan& p, UnpackPlanEntry* plan, UnpackGroupDev* gd,
+                   unsigned char* gBase, Visit visit) {
+    int64_t catPos[2 * kUnpackGroups];
+    for (int64_t k = 0, q = 0; k < 2 * kUnpackGroups; q += p.nCat[k], ++k) catPos[k] = q;
+    for (int g = 0; g < kUnpackGroups; ++g) {
+        const int s = g / 2;
+        UnpackGroupDev& G = gd[g];
+        G.shape = s;
+        G.joint = !(g & 1);
+        G.nb = d.bands.nBands[s] > 0 ? d.bands.nBands[s] : 0;
+        G.halfN = d.bands.halfN[s];
+        int** ptr[5] = {&G.oscale, &G.ms, &G.sf, &G.ba, &G.mant};
+        for (int k = 0; k < 5; ++k) *ptr[k] = (int*)(gBase + p.gOff[g][k]);
+    }
+    int64_t slotNext[kUnpackGroups] = {};
+    for (int64_t f = 0; f < (int64_t)p.files.size(); ++f) {
+        const PacFilePlan& fi = p.files[(size_t)f];
+        const int64_t nb = p.nBlocks(f), nJoint = p.nJoint(f);
+        int64_t start = 0;
+        for (int64_t i = 0; i < nb; ++i) {
+            const int64_t c0 = fi.firstChunk + i * fi.nch;
+            const int s = p.chunkShape[(size_t)c0];
+            if (i < nJoint) {
+                const int g = s * 2;
+                const int slot = (int)slotNext[g]++;
+                plan[catPos[s * 4]++] = UnpackPlanEntry{p.chunkOff[(size_t)c0], g * 2, slot};
+                plan[catPos[s * 4 + 1]++] = UnpackPlanEntry{p.chunkOff[(size_t)c0 + 1], g * 2 + 1, slot};
+                visit(f, i, g, slot, 0, start);
+            } else {
+                const int g = s * 2 + 1;
+                for (int ch = 0; ch < fi.nch; ++ch) {
+                    const int slot = (int)slotNext[g]++;
+                    plan[catPos[s * 4 + 2]++] = UnpackPlanEntry{p.chunkOff[(size_t)c0 + ch], g * 2, slot};
+                    visit(f, i, g, slot, ch, start);
+                }
+            }
+            int a, b;
+            shape_ab(cfg, s, &a, &b);
+            start += a;
+        }
+    }
+}
+
 }  // namespace mrc
 
 struct mrc_handle {
@@ -154,6 +272,7 @@ struct mrc_handle {
     int64_t packLastChunks = 0, packLastCap = 0;   // ... of the most recent call (mrc_dev_pack_status)
     mrc::ChainBufs chain;            // mrc_encode_chained_*: see mrc_api_chain.cpp
     mrc::DecodeBufs dec;             // mrc_dev_unpack_blocks / mrc_decode_pac_pcm16: see mrc_api_decode.cpp
+    mrc::NmrBufs nmr;                // mrc_pac_nmr: see mrc_api_nmr.cpp
     double chainMs[4] = {0, 0, 0, 0};   // last chained encode: phase A, phase B, pack, whole call (host clock)
     bool timing = false;
     bool exactSpread = false;        // mrc_set_option(MRC_OPT_EXACT_SPREAD)

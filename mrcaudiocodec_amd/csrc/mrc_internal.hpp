@@ -191,6 +191,22 @@ hipError_t launch_unpack_dense(const UnpackParams& P, const UnpackBands& B, cons
 hipError_t launch_pcm16_interleave(int64_t nFiles, int64_t nOut, const long long* outStart, const long long* xStart,
                                    const int* nch, int skip, const double* x, int64_t planeStride, short* out,
                                    hipStream_t st);
+// mrc_kernels_nmr.hip -- noise-to-mask ratio of decoded blocks against their source (mrc_pac_nmr)
+struct NmrPlane { long long dst, src, frames, len; };   // padded plane: out[dst + t], t < len; samples src[src + t - L]
+struct NmrEntry {                    // one (block, channel) of a file, all of one block shape per launch
+    long long out;                   // entry index: row of the band arrays and of stat
+    long long ana;                   // row of the shape's source analysis (X, T)
+    int group, slot, ch, b;          // parsed chunk(s): UnpackGroupDev group and slot; output channel; new samples b
+};
+hipError_t launch_nmr_pad(int64_t nPlanes, const NmrPlane* planes /* device */, int64_t maxLen, int L, const short* src,
+                          short* out, hipStream_t st);
+// bandNoise / bandMask: [entries][kMaxBands] or null; stat [entries][2]: max_j r_j, b * mean_j r_j
+hipError_t launch_nmr_band(const DevShape& S, int64_t nEntries, const NmrEntry* entries, const UnpackGroupDev* groups,
+                           const double* lines, const double* thresh, double* bandNoise, double* bandMask, double* stat,
+                           hipStream_t st);
+// fileOut [nFiles][4]: max r, sum of b * mean r, disturbed blocks, 0.  File f's entries: [entryStart[f], entryStart[f + 1])
+hipError_t launch_nmr_file(int64_t nFiles, const long long* entryStart, const int* nch, const double* stat, double* fileOut,
+                           hipStream_t st);
 // mrc_kernels_chain.hip -- chained stream encode: reservoir-free preparation per block, serial scan per stream
 constexpr int kChainMaxLinesPerItem = 2 * 1024;  // coded lines one scan item holds (all its streams together)
 constexpr int kChainGroups = 5;    // chained encode: the four joint block shapes + Close()'s non-joint long block

@@ -14,28 +14,11 @@
 //
 // The reference computes the IMDCT with an N-point complex inverse FFT; like the forward transform the results
 // agree to ~1e-13 of the block's peak (tests hold 1e-12).
-#include "mrc_device.hpp"
+#include "mrc_decode_lines.hpp"
 
 namespace mrc {
 using namespace dev;
 namespace {
-
-// quantize.py:325-357 + 90-111 for one mantissa code
-__device__ __forceinline__ double dequantize_dev(int scale, int mant, int nScaleBits, int nMantBits) {
-    const int cap = (1 << nScaleBits) - 1;
-    const int nBits = cap + nMantBits;
-    const int signBit = 1 << (nMantBits - 1);
-    const bool neg = mant >= signBit;
-    const long long mag = neg ? mant - signBit : mant;
-    long long code = mag;
-    if (scale != cap) {
-        const int shift = cap - scale;
-        code = mag << shift;
-        if (shift > 0 && mag > 0) code += 1LL << (shift - 1);
-    }
-    const double sgn = neg ? -1.0 : 1.0;
-    return ((sgn * (double)code) * 2.0) / ((double)(1LL << nBits) - 1.0);
-}
 
 __global__ __launch_bounds__(kThreads) void decode_kernel(DevShape S, int nStreams, const int* __restrict__ oscale,
                                                           const int* __restrict__ msSwitch,
@@ -59,22 +42,9 @@ __global__ __launch_bounds__(kThreads) void decode_kernel(DevShape S, int nStrea
     const int* os = oscale + f * (joint ? 4 : 1);
 
     // dequantise, undo the overall scale (codecThem.py:47-51, 92-109), rebuild L / R (ms_stereo.py:33-49)
-    for (int k = tid; k < M; k += kThreads) {
-        const int band = S.bandOfLine[k];
-        double x;
-        if (!joint) {
-            const int bits = ba[band];
-            x = bits ? dequantize_dev(sf[band], mant[k], S.nScaleBits, bits) : 0.0;
-            x = ldexp(x, -os[0]);
-        } else {
-            const bool ms = msSwitch[f * nb + band] == 1;
-            const int b0 = ba[band], b1 = ba[nb + band];
-            double l1 = b0 ? ldexp(dequantize_dev(sf[band], mant[k], S.nScaleBits, b0), -(ms ? os[2] : os[0])) : 0.0;
-            double l2 = b1 ? ldexp(dequantize_dev(sf[nb + band], mant[M + k], S.nScaleBits, b1), -(ms ? os[3] : os[1])) : 0.0;
-            x = ms ? (ch == 0 ? l1 + l2 : l1 - l2) : (ch == 0 ? l1 : l2);
-        }
-        v[k] = x;
-    }
+    for (int k = tid; k < M; k += kThreads)
+        v[k] = decode_line(k, S.bandOfLine[k], ch, joint, nb, M, S.nScaleBits, os, joint ? msSwitch + f * nb : nullptr, sf,
+                           ba, mant);
     __syncthreads();
     // DCT-IV of the lines through the N/4-point FFT (same pairing and twiddles as the forward kernel)
     for (int n = tid; n < Q; n += kThreads) A[n] = cmul(make_double2(v[2 * n], v[M - 1 - 2 * n]), S.pre[n]);

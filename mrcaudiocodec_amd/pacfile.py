@@ -391,3 +391,19 @@ def decode_pac_files(handle, bufs):
     the bytes cross PCIe once, chunk parsing and Huffman decoding run on the device as well (mrc_decode_pac_pcm16).
     -> list of int16 [nCh][samples], bit-identical to decode_pac_pcm16 of each file (views of one WAV-order buffer)."""
     return handle.decode_pac_pcm16(bufs, interleaved=False)
+
+
+def measure_nmr(handle, buf_or_bufs, pcm, detail=False):
+    """The noise-to-mask ratio of `.pac` file(s) against their source, on the GPU of `handle` (created with the files'
+    parameters) in ONE call (mrc_pac_nmr).  pcm: the WAV's own int16 samples [nCh][n] (no prior hop) -- one array that
+    every file was coded from, or a list with one per file.  -> a dict (one file given as bytes) or a list of dicts:
+    nmr_max_db, nmr_total_db, disturbed_blocks, n_blocks (and, detail=True, the per-entry arrays of Handle.pac_nmr)."""
+    one = isinstance(buf_or_bufs, (bytes, bytearray, memoryview, np.ndarray))
+    bufs = [buf_or_bufs] if one else list(buf_or_bufs)
+    if isinstance(pcm, (list, tuple)):
+        sources = list(pcm)
+    else:
+        src = np.ascontiguousarray(np.atleast_2d(pcm), dtype=np.int16)
+        sources = [src] * len(bufs)            # one object: uploaded once
+    res = handle.pac_nmr(bufs, sources, detail=detail)
+    return res[0] if one else res
