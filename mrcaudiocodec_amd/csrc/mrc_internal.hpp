@@ -102,6 +102,10 @@ hipError_t launch_smr(const DevShape& S, int64_t nFrames, const void* chL, const
                       const int* msSwitch /* joint: [frames][nBands] -> only the SMRs the encoder uses are computed; null: all */,
                       bool exactSpread, hipStream_t st,
                       unsigned long long* sens = nullptr /* MRC_OPT_SENSITIVITY: counters [MRC_SENS_COUNT] on the device */);
+// launch_smr's other unit: the mono long block (mrc_kernels_smr_mono.hip)
+hipError_t launch_smr_mono_long(const DevShape& S, int64_t nFrames, const void* chL, int fmt, int64_t stride,
+                                const int64_t* offsets, const double* lines, const int* oscale, double* smr,
+                                double* bandPeak, hipStream_t st, unsigned long long* sens);
 // mrc_kernels_sens.hip: decisions within a guard band of rounding (quantiser edges, allocation ties, M/S threshold)
 hipError_t launch_sensitivity(const DevShape& S, int64_t nFrames, int joint, const double* lines, const int* oscale,
                               const double* smr, const double* bandPeak, const int* msSwitch, const int* bitAlloc,

@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU box: SQ_INSTS_VALU etc. of the bench command for each library variant given (profiling builds of
-# mrcaudiocodec_amd/csrc with EXTRA=-DMRC_PROFILE_SKIP=<mask>), outputs under gpurun_out/var_<name>.
+# mrcaudiocodec_amd/csrc with EXTRA="-DMRC_PROFILING_BUILD -DMRC_PROFILE_SKIP=<mask>"), outputs under $out/var_<name>.
 # usage: tools/collect_variants.sh <frames> <variant.so> ...
 set -e -o pipefail
 frames=$1; shift

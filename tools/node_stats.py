@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """
 Which evaluation of the upper-side spreading sum smr_kernel's long-block units / chunks take, per corpus (needs the
--DMRC_NODE_STATS build: make OUT=.../libmrc_hip_nodestats.so BUILD=build_nodestats EXTRA=-DMRC_NODE_STATS).
+-DMRC_NODE_STATS build: make OUT=.../libmrc_hip_nodestats.so BUILD=build_nodestats
+EXTRA="-DMRC_PROFILING_BUILD -DMRC_NODE_STATS").
     MRC_HIP_LIBRARY=mrcaudiocodec_amd/libmrc_hip_nodestats.so python tools/node_stats.py [frames]
 """
 import ctypes

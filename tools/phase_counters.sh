@@ -1,6 +1,6 @@
 #!/bin/bash
 # Runs on the GPU box: one SQ counter pass of the headline bench per profiling build of the library
-# (libmrc_hip_<name>.so: smr_kernel cut after phase n, without the sweep, ...): where the kernel's VALU and LDS
+# (libmrc_hip_<name>.so, e.g. smr_kernel cut after phase n: EXTRA="-DMRC_PROFILING_BUILD -DMRC_PROFILE_STOP=<n>"): where the kernel's VALU and LDS
 # instructions are.  usage: tools/phase_counters.sh <tag> <frames> <name> ...   -> gpurun_out/<tag>_<name>_pc/
 set -o pipefail
 tag=$1; frames=$2; shift 2

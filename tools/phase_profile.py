@@ -2,7 +2,7 @@
 """
 Where the time of smr_kernel goes: shader-clock cycles per kernel phase, summed over all waves, from the
 PROFILING build of the library (make -C mrcaudiocodec_amd/csrc OUT=.../libmrc_hip_prof.so BUILD=build_prof
-EXTRA=-DMRC_PROFILE_PHASES).  Run as
+EXTRA="-DMRC_PROFILING_BUILD -DMRC_PROFILE_PHASES").  Run as
     MRC_HIP_LIBRARY=mrcaudiocodec_amd/libmrc_hip_prof.so python tools/phase_profile.py [frames]
 The timers serialise each phase (s_memtime + wait), so the total is a few % above the production kernel; the
 FRACTIONS are what this is for.  Mono white noise as int16 PCM, long blocks (the bench workload).
