@@ -5,6 +5,7 @@ gfx950 device is usable `Handle()` raises -- nothing in this package computes on
 """
 import ctypes as C
 import os
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -197,6 +198,10 @@ def _p(a, typ):
     return None if a is None else a.ctypes.data
 
 
+def vp(arr):
+    return None if arr is None else arr.ctypes.data_as(C.c_void_p)
+
+
 def nmr_layout(bufs, sources):
     """The host side of mrc_pac_nmr's arguments: bufs (a list of bytes-like `.pac` files) -> one byte buffer and
     file_offset; sources (a list or tuple, one int16 [nCh][n] array per file; the same object may repeat and is then
@@ -387,21 +392,27 @@ class Handle:
                                                     _p(out["reservoir_out"], _i32p)))
         return out
 
-    def encode_stream_pcm16(self, pcm_left, pcm_right=None, reservoir_in=None, chunk_frames=0, out=None):
-        """mrc_encode_stream_pcm16: int16 PCM stream(s) [(n+1) * L] in host memory -> codes in host memory, long
-        blocks, pipelined over three HIP streams.  `out` may hold preallocated (ideally page-locked, see
-        pinned_empty) arrays to write into; the mantissa plane is uint16."""
+    def _stream_pcm16(self, pcm_left, pcm_right):
+        """int16 stream(s) [(n + 1) * L] of the encode_stream_pcm16* calls -> (left, right or None, n)"""
         L = self.cfg.n_mdct_lines
         pl = np.ascontiguousarray(pcm_left, dtype=np.int16)
         n = pl.size // L - 1
         if pl.ndim != 1 or pl.size != (n + 1) * L or n < 0:
             raise ValueError("pcm_left must be int16 [(n_frames + 1) * %d]" % L)
-        joint = pcm_right is not None
         pr = None
-        if joint:
+        if pcm_right is not None:
             pr = np.ascontiguousarray(pcm_right, dtype=np.int16)
             if pr.shape != pl.shape:
                 raise ValueError("pcm_right must match pcm_left")
+        return pl, pr, n
+
+    def encode_stream_pcm16(self, pcm_left, pcm_right=None, reservoir_in=None, chunk_frames=0, out=None):
+        """mrc_encode_stream_pcm16: int16 PCM stream(s) [(n+1) * L] in host memory -> codes in host memory, long
+        blocks, pipelined over three HIP streams.  `out` may hold preallocated (ideally page-locked, see
+        pinned_empty) arrays to write into; the mantissa plane is uint16."""
+        L = self.cfg.n_mdct_lines
+        pl, pr, n = self._stream_pcm16(pcm_left, pcm_right)
+        joint = pr is not None
         nb = len(self.bands(L, L))
         ns, nsig = (2, 4) if joint else (1, 1)
         want = dict(overall_scale=((n, nsig), np.int32), scale_factor=((n, ns, nb), np.int32),
@@ -417,7 +428,6 @@ class Handle:
                 raise ValueError("out[%r] must be a C-contiguous %s array of shape %s" % (k, np.dtype(dt).name, shape))
             res[k] = arr
         res_in = _reservoir(reservoir_in, n)
-        vp = lambda arr: None if arr is None else arr.ctypes.data_as(C.c_void_p)
         self._check(lib.mrc_encode_stream_pcm16(self._h, n, vp(pl), vp(pr), vp(res_in), vp(res["overall_scale"]),
                                                 vp(res.get("ms_switch")), vp(res["scale_factor"]), vp(res["bit_alloc"]),
                                                 vp(res["mantissa"]), vp(res["reservoir_out"]), int(chunk_frames)))
@@ -430,16 +440,8 @@ class Handle:
         a preallocated (ideally page-locked) uint8 array `bytes`; too small a buffer is retried once at the worst-case size.
         -> dict: bytes (the used prefix), block_offset [n + 1], huff_table / bits_saved [n][channels], reservoir_out [n]."""
         L = self.cfg.n_mdct_lines
-        pl = np.ascontiguousarray(pcm_left, dtype=np.int16)
-        n = pl.size // L - 1
-        if pl.ndim != 1 or pl.size != (n + 1) * L or n < 0:
-            raise ValueError("pcm_left must be int16 [(n_frames + 1) * %d]" % L)
-        joint = pcm_right is not None
-        pr = None
-        if joint:
-            pr = np.ascontiguousarray(pcm_right, dtype=np.int16)
-            if pr.shape != pl.shape:
-                raise ValueError("pcm_right must match pcm_left")
+        pl, pr, n = self._stream_pcm16(pcm_left, pcm_right)
+        joint = pr is not None
         nch = 2 if joint else 1
         bound = int(lib.mrc_pack_bound(C.byref(self.cfg), L, L, 1, 1 if joint else 0))
         buf = None if out is None else out.get("bytes")
@@ -452,7 +454,6 @@ class Handle:
         res_out = np.zeros(n, np.int32)
         res_in = _reservoir(reservoir_in, n)
         total = np.zeros(1, np.int64)
-        vp = lambda arr: None if arr is None else arr.ctypes.data_as(C.c_void_p)
         for attempt in (0, 1):
             rc = lib.mrc_encode_stream_pcm16_pac(self._h, n, vp(pl), vp(pr), vp(res_in), 1 if use_huffman else 0, vp(buf),
                                                  buf.size, vp(offs), vp(table), vp(saved), vp(res_out),
@@ -479,6 +480,40 @@ class Handle:
         return (start, np.ascontiguousarray(flat[:, 0]), np.ascontiguousarray(flat[:, 1], dtype=np.int32),
                 np.ascontiguousarray(flat[:, 2], dtype=np.int32))
 
+    def _chain_args(self, pcm_left, pcm_right, shapes, use_huffman, with_flush, num_samples, device):
+        """What encode_chained_pac and encode_chained_pac_ladder share.  -> namespace: n_streams, nch, n_blocks, n_items;
+        pcm = the arguments (left, right, sample_format, stride), from the host arrays [nStreams][stride] or from `device`;
+        head / opts = the schedule arguments in front of and behind reservoir_in; bound() = the worst-case bytes of one rate."""
+        start, off, a, b = self._chain_schedule(shapes)
+        n_streams = len(start) - 1
+        keep = None
+        if device is None:
+            mono = pcm_right is None
+            pl = np.atleast_2d(pcm_left)
+            dt = np.int16 if pl.dtype == np.int16 else np.float64
+            pl = np.ascontiguousarray(pl, dtype=dt)
+            pr = None if mono else np.ascontiguousarray(np.atleast_2d(pcm_right), dtype=dt)
+            if (not mono and pl.shape != pr.shape) or pl.ndim != 2 or pl.shape[0] != n_streams:
+                raise ValueError("pcm_left / pcm_right must be [nStreams][stride], one row per shape list")
+            keep, pcm = (pl, pr), (vp(pl), vp(pr), 1 if dt == np.int16 else 0, pl.shape[1])
+        else:
+            mono, pcm = device[1] is None, (device[0], device[1], int(device[2]), int(device[3]))
+        nch = 1 if mono else 2
+        ns = None if num_samples is None else np.ascontiguousarray(num_samples, dtype=np.uint32)
+        if ns is not None and ns.shape != (n_streams,):
+            raise ValueError("num_samples: one value per stream")
+
+        def bound():
+            v = self.chain_out_bound(start, a, b, with_flush, ns is not None, nch)
+            if v < 0:
+                raise MrcError("mrc_chain_out_bound failed (%d): block shape out of range" % v)
+            return v
+        return SimpleNamespace(n_streams=n_streams, nch=nch, n_blocks=int(off.size), pcm=pcm, bound=bound,
+                               n_items=len(off) + (nch * n_streams if with_flush else 0),
+                               head=(_p(start, _i64p), _p(off, _i64p), _p(a, _i32p), _p(b, _i32p)),
+                               opts=(1 if use_huffman else 0, 1 if with_flush else 0, vp(ns)),
+                               keep=(keep, start, off, a, b, ns))       # (the arrays behind the addresses)
+
     def encode_chained_pac(self, pcm_left, pcm_right, shapes, use_huffman=True, with_flush=True, num_samples=None,
                            reservoir_in=None, want_trace=False, device=None, stream=None, want_items=False):
         """mrc_encode_chained_stream_pac: stereo streams [nStreams][stride] -- int16 PCM codes or float64 signed fractions,
@@ -489,56 +524,33 @@ class Handle:
         (mrc_dev_encode_chained_pac; `bytes` is then None).
         -> dict: bytes (uint8), stream_offset [nStreams + 1], reservoir_out [nStreams], total, (trace), and with want_items
         item_offset [nItems + 1]: where every block's bytes start (costs a read-back of all chunk positions)."""
-        start, off, a, b = self._chain_schedule(shapes)
-        n_streams = len(shapes)
-        if device is None:
-            mono = pcm_right is None
-            pl = np.atleast_2d(pcm_left)
-            dt = np.int16 if pl.dtype == np.int16 else np.float64
-            pl = np.ascontiguousarray(pl, dtype=dt)
-            pr = None if mono else np.ascontiguousarray(np.atleast_2d(pcm_right), dtype=dt)
-            if (not mono and pl.shape != pr.shape) or pl.ndim != 2 or pl.shape[0] != n_streams:
-                raise ValueError("pcm_left / pcm_right must be [nStreams][stride], one row per shape list")
-            stride, fmt = pl.shape[1], (1 if dt == np.int16 else 0)
-        else:
-            mono = device[1] is None
-        nch = 1 if mono else 2
-        n_items = len(off) + (nch * n_streams if with_flush else 0)
-        ns = None if num_samples is None else np.ascontiguousarray(num_samples, dtype=np.uint32)
-        if ns is not None and ns.shape != (n_streams,):
-            raise ValueError("num_samples: one value per stream")
+        q = self._chain_args(pcm_left, pcm_right, shapes, use_huffman, with_flush, num_samples, device)
+        n_streams = q.n_streams
         res_in = _reservoir(reservoir_in, n_streams)
         s_off = np.zeros(n_streams + 1, np.int64)
-        i_off = np.zeros(n_items + 1, np.int64) if want_items else None
+        i_off = np.zeros(q.n_items + 1, np.int64) if want_items else None
         res_out = np.zeros(n_streams, np.int32)
-        trace = np.zeros(n_items, np.int32) if want_trace else None
+        trace = np.zeros(q.n_items, np.int32) if want_trace else None
         total = np.zeros(1, np.int64)
-        vp = lambda arr: None if arr is None else arr.ctypes.data_as(C.c_void_p)
-        sched = (_p(start, _i64p), _p(off, _i64p), _p(a, _i32p), _p(b, _i32p), _p(res_in, _i32p), 1 if use_huffman else 0,
-                 1 if with_flush else 0, vp(ns))
-        tail = (_p(s_off, _i64p), _p(i_off, _i64p), _p(res_out, _i32p), _p(trace, _i32p), total.ctypes.data_as(_i64p))
+        sched = q.head + (_p(res_in, _i32p),) + q.opts
+        tail = (_p(s_off, _i64p), _p(i_off, _i64p), _p(res_out, _i32p), _p(trace, _i32p), _p(total, _i64p))
         buf = None
         if device is not None:
-            dl, dr, fmt, stride, dout, dcap = device
-            self._check(lib.mrc_dev_encode_chained_pac(self._h, n_streams, dl, dr, int(fmt), int(stride), *sched, dout, int(dcap),
-                                                       *tail, stream))
+            self._check(lib.mrc_dev_encode_chained_pac(self._h, n_streams, *q.pcm, *sched, device[4], int(device[5]), *tail,
+                                                       stream))
         else:
-            bound = self.chain_out_bound(start, a, b, with_flush, ns is not None, nch)
-            if bound < 0:
-                raise MrcError("mrc_chain_out_bound failed (%d): block shape out of range" % bound)
+            bound = q.bound()
             # a buffer for typical content (~3 bits per sample); if the streams pack to more, the call says how much and
             # its bytes -- complete in the handle's device buffer -- are fetched into a buffer of that size (no second encode)
-            cap = min(bound, int(off.size) * 1024 + n_streams * 4096 + 4096)
+            cap = min(bound, q.n_blocks * 1024 + n_streams * 4096 + 4096)
             buf = np.empty(max(cap, 1), np.uint8)
-            rc = lib.mrc_encode_chained_stream_pac(self._h, n_streams, vp(pl), vp(pr), fmt, stride, *sched, vp(buf),
-                                                   buf.size, *tail)
+            rc = lib.mrc_encode_chained_stream_pac(self._h, n_streams, *q.pcm, *sched, vp(buf), buf.size, *tail)
             if rc == MRC_ERR_NOMEM and 0 < int(total[0]) <= bound:
                 buf = np.empty(int(total[0]), np.uint8)
-                if lib.mrc_chain_fetch_output(self._h, vp(buf), buf.size, total.ctypes.data_as(_i64p)) != 0:
+                if lib.mrc_chain_fetch_output(self._h, vp(buf), buf.size, _p(total, _i64p)) != 0:
                     # a call of several slabs keeps only its last slab on the device: encode again into a buffer of the
                     # size the first pass reported
-                    self._check(lib.mrc_encode_chained_stream_pac(self._h, n_streams, vp(pl), vp(pr), fmt, stride, *sched,
-                                                                  vp(buf), buf.size, *tail))
+                    self._check(lib.mrc_encode_chained_stream_pac(self._h, n_streams, *q.pcm, *sched, vp(buf), buf.size, *tail))
             else:
                 self._check(rc)
             buf = buf[:int(total[0])]
@@ -556,64 +568,43 @@ class Handle:
         device = (left_ptr, right_ptr or None, sample_format, stride, out_ptrs [nRates], out_caps [nRates]): PCM and outputs
         in HBM (mrc_dev_encode_chained_ladder_pac; `bytes` is then None).
         -> list of nRates dicts shaped like encode_chained_pac's."""
-        start, off, a, b = self._chain_schedule(shapes)
-        n_streams = len(start) - 1
         rates = np.ascontiguousarray(np.atleast_1d(np.asarray(rates, dtype=np.float64)))
         R = rates.size
-        if device is None:
-            mono = pcm_right is None
-            pl = np.atleast_2d(pcm_left)
-            dt = np.int16 if pl.dtype == np.int16 else np.float64
-            pl = np.ascontiguousarray(pl, dtype=dt)
-            pr = None if mono else np.ascontiguousarray(np.atleast_2d(pcm_right), dtype=dt)
-            if (not mono and pl.shape != pr.shape) or pl.ndim != 2 or pl.shape[0] != n_streams:
-                raise ValueError("pcm_left / pcm_right must be [nStreams][stride], one row per shape list")
-            stride, fmt = pl.shape[1], (1 if dt == np.int16 else 0)
-        else:
-            mono = device[1] is None
-        nch = 1 if mono else 2
-        n_items = len(off) + (nch * n_streams if with_flush else 0)
-        ns = None if num_samples is None else np.ascontiguousarray(num_samples, dtype=np.uint32)
-        if ns is not None and ns.shape != (n_streams,):
-            raise ValueError("num_samples: one value per stream")
+        q = self._chain_args(pcm_left, pcm_right, shapes, use_huffman, with_flush, num_samples, device)
+        n_streams = q.n_streams
         res_in = None
         if reservoir_in is not None:
             res_in = _i32(np.asarray(reservoir_in))
             if res_in.shape != (R, n_streams):
                 raise ValueError("reservoir_in must be [nRates][nStreams] = [%d][%d], got %s" % (R, n_streams, res_in.shape))
         s_off = np.zeros((R, n_streams + 1), np.int64)
-        i_off = np.zeros((R, n_items + 1), np.int64) if want_items else None
+        i_off = np.zeros((R, q.n_items + 1), np.int64) if want_items else None
         res_out = np.zeros((R, n_streams), np.int32)
-        trace = np.zeros((R, n_items), np.int32) if want_trace else None
+        trace = np.zeros((R, q.n_items), np.int32) if want_trace else None
         total = np.zeros(R, np.int64)
-        vp = lambda arr: None if arr is None else arr.ctypes.data_as(C.c_void_p)
-        sched = (_p(start, _i64p), _p(off, _i64p), _p(a, _i32p), _p(b, _i32p), _p(res_in, _i32p), 1 if use_huffman else 0,
-                 1 if with_flush else 0, vp(ns))
+        sched = q.head + (_p(res_in, _i32p),) + q.opts
         tail = (_p(s_off, _i64p), _p(i_off, _i64p), _p(res_out, _i32p), _p(trace, _i32p), _p(total, _i64p))
         bufs = None
         if device is not None:
-            dl, dr, fmt, stride, douts, dcaps = device
+            douts, dcaps = device[4], device[5]
             ptrs = (C.c_void_p * R)(*[int(p) if p else None for p in douts])
             caps = np.ascontiguousarray(dcaps, dtype=np.int64)
             if len(douts) != R or caps.shape != (R,):
                 raise ValueError("device: one output pointer and one capacity per rate")
-            self._check(lib.mrc_dev_encode_chained_ladder_pac(self._h, R, _p(rates, _f64p), n_streams, dl, dr, int(fmt),
-                                                              int(stride), *sched, C.cast(ptrs, C.c_void_p), _p(caps, _i64p),
-                                                              *tail, stream))
+            self._check(lib.mrc_dev_encode_chained_ladder_pac(self._h, R, _p(rates, _f64p), n_streams, *q.pcm, *sched,
+                                                              C.cast(ptrs, C.c_void_p), _p(caps, _i64p), *tail, stream))
         else:
-            bound = self.chain_out_bound(start, a, b, with_flush, ns is not None, nch)
-            if bound < 0:
-                raise MrcError("mrc_chain_out_bound failed (%d): block shape out of range" % bound)
+            bound = q.bound()
             # a buffer per rate for typical content (1.5x the rate's bits for a long block, at least 1 KB per block); if a rate
             # packs to more, the call says how much and runs again with buffers of the reported sizes (a ladder keeps no
             # output on the device)
-            per_block = [max(1024, int(1.5 * r * nch * 1024 / 8)) for r in rates]
-            bufs = [np.empty(max(min(bound, int(off.size) * pb + n_streams * 4096 + 4096), 1), np.uint8) for pb in per_block]
+            per_block = [max(1024, int(1.5 * r * q.nch * 1024 / 8)) for r in rates]
+            bufs = [np.empty(max(min(bound, q.n_blocks * pb + n_streams * 4096 + 4096), 1), np.uint8) for pb in per_block]
             for attempt in range(2):
                 ptrs = (C.c_void_p * R)(*[buf.ctypes.data for buf in bufs])
                 caps = np.array([buf.size for buf in bufs], np.int64)
-                rc = lib.mrc_encode_chained_ladder_pac(self._h, R, _p(rates, _f64p), n_streams, vp(pl), vp(pr), fmt, stride,
-                                                       *sched, C.cast(ptrs, C.c_void_p), _p(caps, _i64p), *tail)
+                rc = lib.mrc_encode_chained_ladder_pac(self._h, R, _p(rates, _f64p), n_streams, *q.pcm, *sched,
+                                                       C.cast(ptrs, C.c_void_p), _p(caps, _i64p), *tail)
                 if rc == MRC_ERR_NOMEM and attempt == 0 and 0 < int(total.max()) and int(total.max()) <= bound:
                     bufs = [buf if int(t) <= buf.size else np.empty(int(t), np.uint8) for buf, t in zip(bufs, total)]
                     continue
