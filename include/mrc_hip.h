@@ -448,6 +448,60 @@ int mrc_dev_encode_chained_ladder_pac(mrc_handle* h, int n_rates, const double* 
                                       int64_t* stream_byte_offset, int64_t* item_byte_offset, int32_t* reservoir_out,
                                       int32_t* reservoir_trace, int64_t* total_bytes, void* stream);
 
+/* ---- encode to a target noise-to-mask ratio: one source, a rate ladder, the cheapest rung that is clean enough ---------
+ * mrc_encode_chained_target_nmr_pac encodes every stream at the n_rates rates of a ladder (as
+ * mrc_encode_chained_ladder_pac does: transform and psychoacoustic model once, the serial scan per (rate, stream)), measures
+ * the noise-to-mask ratio of every rung on the device from the scan's own planes while they are resident, and returns per
+ * stream the `.pac` file of the LOWEST rung whose nmr_total_db meets the target, with the NMR numbers of every rung.
+ * The bytes of the other rungs never leave the device.
+ * Whole files only: the call always writes Close()'s flush and the headers (num_samples must not be NULL), the samples are
+ * 16-bit PCM (the NMR's source is int16), pcm_right == NULL means mono streams.
+ * The rule, per stream s: chosen[s] is the smallest r with nmr_total_db[r][s] <= target_nmr_total_db and met[s] = 1; if no
+ * rung meets it, chosen[s] = n_rates - 1 and met[s] = 0.  The comparison is made on the double dB value returned; -inf
+ * (silence) meets every target.  out[stream_byte_offset[s] .. stream_byte_offset[s + 1]) is the complete file of stream s
+ * at target_bits_per_sample[chosen[s]], byte for byte what mrc_encode_chained_ladder_pac writes for that rung and stream.
+ * The numbers: nmr_total_db[r][s], nmr_max_db[r][s], disturbed_blocks[r][s] and n_blocks[s] are the SAME doubles and counts
+ * mrc_pac_nmr returns for rung r's file of stream s against the stream's own row from sample n_mdct_lines on, with
+ * src_frames = (end of the stream's last block) - n_mdct_lines -- provided the row's first n_mdct_lines samples (the prior
+ * hop) are zero.  Every sum is kept in mrc_pac_nmr's order (the same source analysis calls, MRC_OPT_EXACT_SPREAD
+ * honoured, the same line decoder, the same band and file reductions), and the results do not depend on what shares the
+ * call or on the slab size.
+ *   MRC_ERR_INVALID, with a message naming the argument and before any device work, for: n_rates outside
+ *   1..MRC_MAX_RATES; a rate that is not finite or outside (0, 64]; rates not strictly ascending; a NaN target (+inf: rung
+ *   0, -inf: met only by silence); num_samples == NULL; MRC_OPT_SENSITIVITY on; a stream whose first block has
+ *   block_a != n_mdct_lines; a stream where block_offset[i] is not the sum of block_a of its earlier blocks (the NMR
+ *   positions blocks by that sum); a stream that does not end in a long block.
+ *   out [out_cap]: the bound is mrc_chain_out_bound_ex for ONE rate.  Too small: MRC_ERR_NOMEM with total_bytes and every
+ *   result array filled and nothing written past out_cap; the chosen bytes stay on the device for mrc_chain_fetch_output.
+ * Slabs (MRC_OPT_CHAIN_SLAB_BLOCKS) apply as for the ladder.  Whole streams of a slab are decided when the slab is done.  For
+ * a stream cut into time slabs the per-entry statistics (16 bytes per entry and rung) and the packed bytes of ALL rungs stay
+ * on the device until the stream's last slab decides: packed bytes are about 1 % of phase A's footprint per block and
+ * rung, so a stream of any length the ladder can encode fits.  The chosen files of the whole call are kept on the device
+ * (the sum of the chosen sizes) until the call returns.
+ * mrc_dev_encode_chained_target_nmr_pac: pcm_left / pcm_right and out in DEVICE memory, all other pointers host; it
+ * synchronises `stream` before it returns.
+ * mrc_get_target_ms: device time of the last call, ms: phase A + preparation, the serial scan, the NMR kernels (threshold
+ * pass and file reduction included), pack + gather. */
+int mrc_encode_chained_target_nmr_pac(mrc_handle* h, int n_rates, const double* target_bits_per_sample /*[n_rates]*/,
+                                      double target_nmr_total_db, int64_t n_streams, const int16_t* pcm_left,
+                                      const int16_t* pcm_right, int64_t stream_stride, const int64_t* block_start,
+                                      const int64_t* block_offset, const int32_t* block_a, const int32_t* block_b,
+                                      int use_huffman, const uint32_t* num_samples, uint8_t* out, int64_t out_cap,
+                                      int64_t* stream_byte_offset /*[n_streams + 1]*/, int32_t* chosen /*[n_streams]*/,
+                                      int32_t* met /*[n_streams]*/, double* nmr_total_db /*[n_rates][n_streams]*/,
+                                      double* nmr_max_db /*[n_rates][n_streams]*/,
+                                      int64_t* disturbed_blocks /*[n_rates][n_streams]*/, int64_t* n_blocks /*[n_streams]*/,
+                                      int64_t* total_bytes);
+int mrc_dev_encode_chained_target_nmr_pac(mrc_handle* h, int n_rates, const double* target_bits_per_sample,
+                                          double target_nmr_total_db, int64_t n_streams, const int16_t* pcm_left,
+                                          const int16_t* pcm_right, int64_t stream_stride, const int64_t* block_start,
+                                          const int64_t* block_offset, const int32_t* block_a, const int32_t* block_b,
+                                          int use_huffman, const uint32_t* num_samples, uint8_t* out, int64_t out_cap,
+                                          int64_t* stream_byte_offset, int32_t* chosen, int32_t* met, double* nmr_total_db,
+                                          double* nmr_max_db, int64_t* disturbed_blocks, int64_t* n_blocks,
+                                          int64_t* total_bytes, void* stream);
+int mrc_get_target_ms(mrc_handle* h, double* ms /*[4]*/);
+
 /* ---- sensitivity certificate (round 4) ----
  * Bit-identity of the integers with the reference is an empirical, counted result: each of them is a floor / compare of
  * float64 values whose last bits differ between implementations (FFT factorisation, log10 / atan / 2^x), and it can only come
@@ -475,7 +529,7 @@ int mrc_dev_encode_chained_ladder_pac(mrc_handle* h, int n_rates, const double* 
 int mrc_get_sensitivity(mrc_handle* h, int64_t* counts /*[MRC_SENS_COUNT]*/, int reset);
 /* mrc_chain_fetch_output: the bytes of the LAST mrc_encode_chained_stream[_pcm16]_pac call on this handle, which stay in the
  * handle's device buffer until the next chained call: after MRC_ERR_NOMEM ("out_cap too small") a caller allocates
- * total_bytes and fetches them -- no second encode.  After a rate ladder call nothing is held (MRC_ERR_INVALID).  The offsets / reservoirs of that call were already returned by it. */
+ * total_bytes and fetches them -- no second encode.  After mrc_encode_chained_target_nmr_pac: the chosen files of that call.  After a rate ladder call nothing is held (MRC_ERR_INVALID).  The offsets / reservoirs of that call were already returned by it. */
 int mrc_chain_fetch_output(mrc_handle* h, uint8_t* out, int64_t out_cap, int64_t* total_bytes);
 
 /* ---- decode side ("next" row f-4: the reference's decoder, pacfileThem.py:130-585 + codecThem.py:30-134) ----

@@ -130,6 +130,14 @@ def _load():
         "mrc_dev_encode_chained_ladder_pac": (C.c_int, [H, C.c_int, _f64p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64,
                                                         _i64p, _i64p, _i32p, _i32p, _i32p, C.c_int, C.c_int, C.c_void_p,
                                                         C.c_void_p, _i64p, _i64p, _i64p, _i32p, _i32p, _i64p, C.c_void_p]),
+        "mrc_encode_chained_target_nmr_pac": (C.c_int, [H, C.c_int, _f64p, C.c_double, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                                                        _i64p, _i64p, _i32p, _i32p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
+                                                        _i64p, _i32p, _i32p, _f64p, _f64p, _i64p, _i64p, _i64p]),
+        "mrc_dev_encode_chained_target_nmr_pac": (C.c_int, [H, C.c_int, _f64p, C.c_double, C.c_int64, C.c_void_p, C.c_void_p,
+                                                            C.c_int64, _i64p, _i64p, _i32p, _i32p, C.c_int, C.c_void_p, C.c_void_p,
+                                                            C.c_int64, _i64p, _i32p, _i32p, _f64p, _f64p, _i64p, _i64p, _i64p,
+                                                            C.c_void_p]),
+        "mrc_get_target_ms": (C.c_int, [H, _f64p]),
         "mrc_pac_read_header": (C.c_int, [_u8p, C.c_int64, C.POINTER(MrcConfig), _i32p, C.POINTER(C.c_uint32), _i64p]),
         "mrc_pac_scan_chunks": (C.c_int64, [_u8p, C.c_int64, C.c_int64, _i64p, C.c_int64]),
         "mrc_unpack_blocks": (C.c_int, [C.POINTER(MrcConfig), C.c_int64, C.c_int, C.c_int, _u8p, C.c_int64, _i64p] +
@@ -619,6 +627,64 @@ class Handle:
                 d["reservoir_trace"] = trace[r]
             out.append(d)
         return out
+
+    def encode_chained_pac_target_nmr(self, pcm_left, pcm_right, shapes, rates, target_db, use_huffman=True, num_samples=None,
+                                      device=None, stream=None, out_cap=None):
+        """mrc_encode_chained_target_nmr_pac: the streams of encode_chained_pac_ladder (int16 PCM codes, each row starting
+        with its zero prior hop) at every rate of `rates` (strictly ascending), the noise-to-mask ratio of every rung measured
+        on the device, and per stream the complete `.pac` file of the LOWEST rung whose nmr_total_db is <= target_db (the top
+        rung, met False, if none is).  num_samples [nStreams] is required: whole files only.
+        device = (left_ptr, right_ptr or None, stride, out_ptr, out_cap): PCM and output in HBM
+        (mrc_dev_encode_chained_target_nmr_pac; `data` is then the (start, end) bytes of the stream's file in out).
+        out_cap: the size of the host buffer (default: sized for typical content, fetched from the device if too small).
+        -> one dict per stream: data (bytes), chosen, rate, met, nmr_total_db [R], nmr_max_db [R], disturbed_blocks [R],
+        n_blocks -- the numbers pac_nmr gives for every rung's file."""
+        rates = np.ascontiguousarray(np.atleast_1d(np.asarray(rates, dtype=np.float64)))
+        R = rates.size
+        if num_samples is None:
+            raise ValueError("encode_chained_pac_target_nmr: num_samples is required (whole files only)")
+        if device is None and np.atleast_2d(pcm_left).dtype != np.int16:
+            raise ValueError("encode_chained_pac_target_nmr: int16 PCM codes only (the NMR's source is int16)")
+        dev5 = None if device is None else (device[0], device[1], 1, device[2])
+        q = self._chain_args(pcm_left, pcm_right, shapes, use_huffman, True, num_samples, dev5)
+        n = q.n_streams
+        pcm = (q.pcm[0], q.pcm[1], q.pcm[3])
+        s_off = np.zeros(n + 1, np.int64)
+        chosen, met = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        tot, mx = np.zeros((R, max(n, 1)), np.float64), np.zeros((R, max(n, 1)), np.float64)
+        dist, nblk = np.zeros((R, max(n, 1)), np.int64), np.zeros(max(n, 1), np.int64)
+        total = np.zeros(1, np.int64)
+        args = (self._h, R, _p(rates, _f64p), float(target_db), n) + pcm + q.head + (q.opts[0], q.opts[2])
+        tail = (_p(s_off, _i64p), _p(chosen, _i32p), _p(met, _i32p), _p(tot, _f64p), _p(mx, _f64p), _p(dist, _i64p),
+                _p(nblk, _i64p), _p(total, _i64p))
+        buf = None
+        if device is not None:
+            self._check(lib.mrc_dev_encode_chained_target_nmr_pac(*args, device[3], int(device[4]), *tail, stream))
+        else:
+            bound = q.bound()
+            if out_cap is None:                  # typical content at the top rate; more: fetched from the device, no second encode
+                out_cap = min(bound, q.n_blocks * max(1024, int(1.5 * rates.max() * q.nch * 1024 / 8)) + n * 4096 + 4096)
+            buf = np.empty(max(int(out_cap), 1), np.uint8)
+            rc = lib.mrc_encode_chained_target_nmr_pac(*args, vp(buf), int(out_cap), *tail)
+            if rc == MRC_ERR_NOMEM and 0 < int(total[0]) <= bound:
+                buf = np.empty(int(total[0]), np.uint8)
+                self._check(lib.mrc_chain_fetch_output(self._h, vp(buf), buf.size, _p(total, _i64p)))
+            else:
+                self._check(rc)
+        out = []
+        for s in range(n):
+            lo, hi = int(s_off[s]), int(s_off[s + 1])
+            out.append(dict(data=(lo, hi) if buf is None else buf[lo:hi].tobytes(), chosen=int(chosen[s]),
+                            rate=float(rates[chosen[s]]), met=bool(met[s]), nmr_total_db=tot[:, s].copy(),
+                            nmr_max_db=mx[:, s].copy(), disturbed_blocks=dist[:, s].copy(), n_blocks=int(nblk[s])))
+        return out
+
+    def target_ms(self):
+        """device time of the last encode_chained_pac_target_nmr: phase A + preparation, serial scan, NMR kernels
+        (threshold pass included), pack + gather (ms)"""
+        ms = np.zeros(4, np.float64)
+        self._check(lib.mrc_get_target_ms(self._h, _p(ms, _f64p)))
+        return ms
 
     def chain_out_bound(self, block_start, block_a, block_b, with_flush=True, with_headers=True, n_channels=2):
         """mrc_chain_out_bound_ex: the worst-case output bytes of a chained call on n_channels = 1 (mono) or 2 streams."""

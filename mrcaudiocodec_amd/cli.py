@@ -25,6 +25,14 @@ noise-to-mask ratio of the file against the WAV, measured with the codec's own m
 nmr_total_db (band-averaged ratio, weighted by block length), disturbed_blocks (blocks with a band whose noise exceeds
 its mask) and n_blocks.  --measure prints the same lines for existing dst file(s) against src without encoding:
     python -m mrcaudiocodec_amd.cli in.wav out_{bps}.pac --bits-per-sample 1.5,2.86,4 --measure
+
+Target quality (mrc_encode_chained_target_nmr_pac): --target-nmr DB with an ascending --bits-per-sample list of two rates or
+more encodes the ladder, measures every rung on the device and writes ONE file to dst: the lowest rate whose nmr_total_db
+is <= DB (the top rate if none is).  One JSON line says which: chosen_bits_per_sample, met, and per rung nmr_total_db,
+nmr_max_db and disturbed_blocks.  The numbers are those of pacfile.measure_nmr on each rung's file against the samples up
+to the end of the last coded block; --measure reads the whole WAV and so holds Close()'s block against the file's last hop,
+which the encoder analyses but never codes: the two agree when that hop is silent.
+    python -m mrcaudiocodec_amd.cli in.wav out.pac --bits-per-sample 1.5,2.86,4,8 --target-nmr -3
 """
 import argparse
 import json
@@ -193,6 +201,70 @@ def encode_wav(in_path, out_path=None, use_huffman=True, device_id=0, handle=Non
     return data
 
 
+def check_target_args(bits_per_sample, target_nmr, out_path=None, decode=False, certify=False, measure=False):
+    """The refusals of --target-nmr, before a file is read or a device is touched.  -> [(text, rate)], the target (float)."""
+    if decode or certify or measure:
+        raise ValueError("--target-nmr encodes one file at the rate it picks: it does not go with -d, --certify or --measure")
+    try:
+        target = float(target_nmr)
+    except (TypeError, ValueError):
+        raise ValueError("--target-nmr: %r is not a number" % (target_nmr,))
+    if np.isnan(target):
+        raise ValueError("--target-nmr: the target must not be NaN")
+    if bits_per_sample is None:
+        raise ValueError("--target-nmr needs --bits-per-sample with two rates or more to choose from")
+    rates = parse_bits_per_sample(bits_per_sample)
+    if len(rates) < 2:
+        raise ValueError("--target-nmr needs two rates or more to choose from (--bits-per-sample 1.5,2.86,4)")
+    if any(b[1] <= a[1] for a, b in zip(rates, rates[1:])):
+        raise ValueError("--target-nmr: --bits-per-sample must be strictly ascending")
+    if out_path is not None and "{bps}" in out_path:
+        raise ValueError("--target-nmr writes ONE file: dst must not contain {bps}")
+    return rates, target
+
+
+def encode_wav_target_nmr(in_path, out_path, bits_per_sample, target_nmr, use_huffman=True, device_id=0, handle=None,
+                          exact_spread=False):
+    """encode_wav at the lowest rate of the ladder bits_per_sample whose nmr_total_db against the WAV is <= target_nmr, in
+    one library call (mrc_encode_chained_target_nmr_pac).  Writes the one file to out_path (if given) and returns the
+    report: data, chosen, chosen_bits_per_sample (as written), rate, met, per-rung nmr_total_db / nmr_max_db /
+    disturbed_blocks, n_blocks.  The argument checks run before the file is read or a device is touched."""
+    rates, target = check_target_args(bits_per_sample, target_nmr, out_path)
+    rate, n_ch, num_samples, pcm = read_wav_pcm(in_path)
+    if n_ch not in (1, 2):
+        raise ValueError("%d-channel input: mono and stereo WAV files only" % n_ch)
+    shape = {} if handle is None else dict(n_mdct_lines=handle.cfg.n_mdct_lines, n_short=handle.cfg.n_short)
+    try:
+        pacfile.header(pacfile.make_config(sample_rate=rate, **shape), n_ch, num_samples)
+    except MrcError as e:
+        raise ValueError("%d Hz input: outside the sample rates the reference can encode (%s)" % (rate, e))
+    h = handle if handle is not None else Handle(sample_rate=rate, device_id=device_id)
+    was_exact = h.get_option(1)
+    if exact_spread:
+        h.set_option(1, 1)
+    try:
+        L = h.cfg.n_mdct_lines
+        codes = np.concatenate([np.zeros((n_ch, L), np.int16), pcm], axis=1)
+        shapes = transient.block_shape_array(h, codes)
+        if not len(shapes):
+            raise ValueError("file too short: fewer than two hops")
+        if shapes[-1, 2] != L:
+            raise ValueError("the stream must end with a long block (the reference's Close() assumes it)")
+        r = pacfile.encode_stream_target_nmr(h, codes[0] if n_ch == 1 else codes, shapes, [v for (_, v) in rates], target,
+                                             use_huffman=use_huffman, num_samples=num_samples)
+    finally:
+        if handle is not None:
+            h.set_option(1, was_exact)
+        else:
+            h.close()
+    r["chosen_bits_per_sample"] = rates[r["chosen"]][0]
+    r["bits_per_sample"] = [t for (t, _) in rates]
+    if out_path:
+        with open(out_path, "wb") as f:
+            f.write(r["data"])
+    return r
+
+
 def wav_header(n_ch, n_data_bytes, sample_rate):
     """pcmfile.py:141-153"""
     return pack('<4sL4s4sLHHLLHH4sL', b"RIFF", 36 + n_data_bytes, b"WAVE", b"fmt ", 16, 1, n_ch, sample_rate,
@@ -285,8 +357,24 @@ def main(argv=None):
     ap.add_argument("--measure", action="store_true",
                     help="do not encode: print the noise-to-mask ratio of the existing dst file(s) against src, one JSON "
                          "line per file (dst may hold {bps} with --bits-per-sample)")
+    ap.add_argument("--target-nmr", default=None, metavar="DB",
+                    help="with an ascending --bits-per-sample list of two rates or more: write ONE file to dst, the lowest "
+                         "rate whose nmr_total_db against src is <= DB (the top rate if none is), and print one JSON line")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.target_nmr is not None:
+        try:
+            check_target_args(a.bits_per_sample, a.target_nmr, a.dst, a.decode, a.certify, a.measure)
+            r = encode_wav_target_nmr(a.src, a.dst, a.bits_per_sample, a.target_nmr, not a.no_huffman, a.device,
+                                      exact_spread=a.exact_spread)
+        except ValueError as e:
+            ap.error(str(e))
+        print(json.dumps(dict(file=a.dst, bytes=len(r["data"]), chosen_bits_per_sample=float(r["rate"]), met=r["met"],
+                              target_nmr_total_db=float(a.target_nmr), bits_per_sample=[float(t) for t in r["bits_per_sample"]],
+                              nmr_total_db=[float(v) for v in r["nmr_total_db"]],
+                              nmr_max_db=[float(v) for v in r["nmr_max_db"]],
+                              disturbed_blocks=[int(v) for v in r["disturbed_blocks"]], n_blocks=r["n_blocks"])))
+        return
     if a.decode and (a.nmr or a.measure):
         ap.error("-d decodes: --nmr and --measure apply to .pac files coded from src")
     if a.measure:

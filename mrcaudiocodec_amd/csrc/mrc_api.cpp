@@ -126,6 +126,7 @@ void mrc_destroy(mrc_handle* h) {
     h->chain.release();
     h->dec.release();
     h->nmr.release();
+    h->target.release();
     h->ws.release();
     for (DevBuf& b : h->stage) b.release();
     h->smallBatch.release();

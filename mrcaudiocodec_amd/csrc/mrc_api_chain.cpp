@@ -14,6 +14,8 @@
 // ladder's ladder_check in front of it); chained_slabs cuts the call into slabs, each the same ChainCall with the slab's fields
 // overwritten; chained_core runs one slab: schedule_groups, phase A + prep queued, schedule_items while the device works,
 // uploads, scan, pack, headers, chain_results.  The host-memory entry points are chained_host with one or several rates.
+// mrc_encode_chained_target_nmr_pac (end of the file) is a ladder whose slabs also measure their rungs (ChainCall::nmr) and
+// whose caller receives the chosen rung alone.
 //
 // Items, in file order per stream:  stereo  one joint block (two chunks) per block shape, Close()'s two one-channel blocks
 //                                           (one chunk each);
@@ -23,6 +25,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -113,6 +116,7 @@ namespace {
 // pcm_right == nullptr: mono streams.  Every per-stream / per-item array holds n_rates rows: reservoir_in / reservoir_out
 // [R][n_streams], stream_byte_offset [R][n_streams + 1], item_byte_offset [R][n_items + 1], reservoir_trace [R][n_items],
 // total_bytes [R]; byte offsets are relative to the start of their rate's output.  Where the bytes go is the layers' own.
+struct ChainNmr;
 struct ChainCall {
     int n_rates; const double* rates;
     int64_t n_streams;
@@ -121,6 +125,7 @@ struct ChainCall {
     const int32_t* reservoir_in; int use_huffman, with_flush; const uint32_t* num_samples;
     int64_t *stream_byte_offset, *item_byte_offset; int32_t *reservoir_out, *reservoir_trace; int64_t* total_bytes;
     void* stream;
+    ChainNmr* nmr = nullptr;         // mrc_encode_chained_target_nmr_pac: every slab also measures its rungs (target_nmr_slab)
     int nch() const { return pcm_right ? 2 : 1; }
     size_t sample_bytes() const { return sample_format == MRC_SAMPLES_PCM16 ? sizeof(int16_t) : sizeof(double); }
     int64_t n_blocks() const { return block_start[n_streams] - block_start[0]; }
@@ -284,6 +289,10 @@ void chain_results(const ChainCall& c, const ChainSchedule& q, int64_t* rate_bas
     if (c.reservoir_out) std::memcpy(c.reservoir_out, q.resOut.data(), q.resOut.size() * sizeof(int32_t));
 }
 
+// mrc_encode_chained_target_nmr_pac (below): the NMR of the slab's rungs from the planes the scan just wrote, and its device time
+int target_nmr_slab(mrc_handle* h, const ChainCall& c, const ChainSchedule& q, const int64_t* count, hipStream_t st);
+int target_nmr_time(mrc_handle* h, const ChainCall& c);
+
 // One SLAB of a chained encode: all of the call's streams, every buffer sized for exactly these blocks (chained_slabs cuts a
 // call into slabs and checked that every stream has a block).  The bytes of all rates go to out [out_cap], device memory.
 int chained_core(mrc_handle* h, const ChainCall& c, uint8_t* out, int64_t out_cap, int64_t* rate_base) {
@@ -413,6 +422,7 @@ int chained_core(mrc_handle* h, const ChainCall& c, uint8_t* out, int64_t out_ca
     MRC_HIP(h, launch_chain_headers(R * nS, q.hdrLen, C.hdr.as<unsigned char>(), C.firstChunk.as<long long>(), W.pos, out,
                                     (long long)out_cap, C.streamPos.as<long long>(), st));
     MRC_HIP(h, hipEventRecord(C.evT[3], st));
+    if (c.nmr) MRC_TRY(target_nmr_slab(h, c, q, count, st));
     // ---- read back: stream starts (the position of every chunk only if the caller asked for them), total, error flag,
     // reservoirs
     if (c.item_byte_offset)
@@ -429,6 +439,7 @@ int chained_core(mrc_handle* h, const ChainCall& c, uint8_t* out, int64_t out_ca
         MRC_HIP(h, hipEventElapsedTime(&ms, C.evT[i < 3 ? i : 0], C.evT[i < 3 ? i + 1 : 3]));
         h->chainMs[i] = ms;
     }
+    if (c.nmr) MRC_TRY(target_nmr_time(h, c));
     chain_results(c, q, rate_base);
     if (q.bad & 3) return fail(h, MRC_ERR_INVALID, "mrc_encode_chained: internal error (table id / chunk size out of range)");
     if (q.total > out_cap || (q.bad & 4)) return fail(h, MRC_ERR_NOMEM, "mrc_encode_chained: out_cap too small (see total_bytes)");
@@ -484,11 +495,19 @@ int64_t ladder_slab_blocks(mrc_handle* h, int64_t cap, int n_rates, int nch) {
     return std::max<int64_t>(1, cap * (shared + perRate) / (shared + n_rates * perRate));
 }
 
+int64_t slab_cap(mrc_handle* h, int n_rates, int nch) {
+    return h->chainSlabBlocks > 0 ? ladder_slab_blocks(h, h->chainSlabBlocks, n_rates, nch) : (int64_t)1 << 40;
+}
+
+struct NoAfter { int operator()(const Slab&, const int64_t*, const int64_t*, const uint8_t*) const { return MRC_OK; } };
+
 // A chained encode cut into slabs.  out_cap[r] is the room of rate r's output.  direct_out (one rate): a device buffer of
 // out_cap[0] bytes the slabs write into in place; null: every slab packs into the handle's buffer and
-// sink(rate r, its slab bytes are at `buf` on the device, n of them, they belong at byte `at` of rate r's output) -> status
-template <class Sink>
-int chained_slabs(mrc_handle* h, const ChainCall& c, const int64_t* out_cap, uint8_t* direct_out, Sink sink) {
+// sink(rate r, its slab bytes are at `buf` on the device, n of them, they belong at byte `at` of rate r's output) -> status;
+// after(the slab, its stream_byte_offset [R][ns + 1], where each rate's bytes start in `buf`, buf) -> status, once per slab
+// behind its sinks
+template <class Sink, class After>
+int chained_slabs(mrc_handle* h, const ChainCall& c, const int64_t* out_cap, uint8_t* direct_out, Sink sink, After after) {
     const int R = c.n_rates, nch = c.nch();
     const int64_t nS = c.n_streams;
     for (int r = 0; r < R; ++r) { c.total_bytes[r] = 0; c.stream_byte_offset[r * (nS + 1)] = 0; }
@@ -496,8 +515,7 @@ int chained_slabs(mrc_handle* h, const ChainCall& c, const int64_t* out_cap, uin
     for (int64_t s = 0; s < nS; ++s)                     // (the slab plan and every size below count on it)
         if (c.block_start[s + 1] <= c.block_start[s]) return fail(h, MRC_ERR_INVALID, "mrc_encode_chained: every stream needs at least one block");
     const int64_t nItemsAll = c.n_items();
-    const int64_t cap = h->chainSlabBlocks > 0 ? ladder_slab_blocks(h, h->chainSlabBlocks, R, nch) : (int64_t)1 << 40;
-    const std::vector<Slab> slabs = plan_slabs(nS, c.block_start, cap);
+    const std::vector<Slab> slabs = plan_slabs(nS, c.block_start, slab_cap(h, R, nch));
     ChainBufs& C = h->chain;
     int64_t itemBase = 0;
     std::vector<int64_t> written((size_t)R, 0), slabTotal((size_t)R), base((size_t)R);
@@ -567,6 +585,7 @@ int chained_slabs(mrc_handle* h, const ChainCall& c, const int64_t* out_cap, uin
             }
             written[(size_t)r] += slabTotal[(size_t)r];
         }
+        MRC_TRY(after(sl, sOff.data(), base.data(), dst));
         itemBase += nItems;
     }
     for (int i = 0; i < 4; ++i) h->chainMs[i] = ms[i];
@@ -590,6 +609,7 @@ int check_call(mrc_handle* h, const char* who, const ChainCall& c, uint8_t* cons
     for (int r = 0; ok && r < c.n_rates; ++r) ok = out[r] && out_cap[r] >= 0;
     if (!ok) return fail(h, MRC_ERR_INVALID, std::string(who) + ": bad argument");
     h->chain.lastTotal = -1;
+    h->chain.lastSrc = nullptr;
     return MRC_OK;
 }
 
@@ -641,7 +661,7 @@ int chained_host(mrc_handle* h, const char* who, ChainCall c, uint8_t* const* ou
         if (n) MRC_HIP(h, hipMemcpyAsync(out[r] + at, buf, (size_t)n, hipMemcpyDeviceToHost, st));
         MRC_HIP(h, hipStreamSynchronize(st));            // (the next slab reuses the buffer)
         return (int)MRC_OK;
-    });
+    }, NoAfter{});
     if (rc == MRC_ERR_NOMEM)
         return fail(h, MRC_ERR_NOMEM, std::string(who) + (c.rates ? ": an out_cap too small (see total_bytes)"
                                                                   : ": out_cap too small (see total_bytes; mrc_chain_fetch_output)"));
@@ -662,7 +682,7 @@ int mrc_dev_encode_chained_pac(mrc_handle* h, int64_t n_streams, const void* pcm
                       block_a, block_b, reservoir_in, use_huffman, with_flush, num_samples, stream_byte_offset, item_byte_offset,
                       reservoir_out, reservoir_trace, total_bytes, stream};
     MRC_TRY(check_call(h, __func__, c, &out, &out_cap));
-    return chained_slabs(h, c, &out_cap, out, [](int, uint8_t*, int64_t, int64_t) { return (int)MRC_OK; });
+    return chained_slabs(h, c, &out_cap, out, [](int, uint8_t*, int64_t, int64_t) { return (int)MRC_OK; }, NoAfter{});
 }
 
 int mrc_encode_chained_stream_pac(mrc_handle* h, int64_t n_streams, const void* pcm_left, const void* pcm_right,
@@ -708,7 +728,7 @@ int mrc_dev_encode_chained_ladder_pac(mrc_handle* h, int n_rates, const double* 
     int rc = chained_slabs(h, c, out_cap, nullptr, [out, st, h](int r, uint8_t* buf, int64_t n, int64_t at) {
         if (n) MRC_HIP(h, hipMemcpyAsync(out[r] + at, buf, (size_t)n, hipMemcpyDeviceToDevice, st));
         return (int)MRC_OK;
-    });
+    }, NoAfter{});
     if (rc == MRC_OK || rc == MRC_ERR_NOMEM) MRC_HIP(h, hipStreamSynchronize(st));
     if (rc == MRC_ERR_NOMEM) return fail(h, MRC_ERR_NOMEM, std::string(__func__) + ": an out_cap too small (see total_bytes)");
     return rc;
@@ -721,7 +741,8 @@ int mrc_chain_fetch_output(mrc_handle* h, uint8_t* out, int64_t out_cap, int64_t
     *total_bytes = C.lastTotal;
     if (C.lastTotal > out_cap) return fail(h, MRC_ERR_NOMEM, "mrc_chain_fetch_output: out_cap too small (see total_bytes)");
     MRC_HIP(h, hipSetDevice(h->device));
-    if (C.lastTotal) MRC_HIP(h, hipMemcpyAsync(out, C.out.p, (size_t)C.lastTotal, hipMemcpyDeviceToHost, h->stream));
+    if (C.lastTotal)
+        MRC_HIP(h, hipMemcpyAsync(out, C.lastSrc ? C.lastSrc : C.out.p, (size_t)C.lastTotal, hipMemcpyDeviceToHost, h->stream));
     MRC_HIP(h, hipStreamSynchronize(h->stream));
     return MRC_OK;
 }
@@ -736,6 +757,351 @@ int mrc_encode_chained_stream_pcm16_pac(mrc_handle* h, int64_t n_streams, const 
                                          block_offset, block_a, block_b, reservoir_in, use_huffman, with_flush, num_samples,
                                          out, out_cap, stream_byte_offset, item_byte_offset, reservoir_out, reservoir_trace,
                                          total_bytes);
+}
+
+}  // extern "C"
+
+// ---- encode to a target noise-to-mask ratio (include/mrc_hip.h: mrc_encode_chained_target_nmr_pac) -----------------------
+// A rate ladder whose rungs are measured where they are made.  Every slab runs as a ladder slab (chained_core) and, while
+// the scan's planes are still in device memory, target_nmr_slab measures each (block, output channel) of each rung against
+// the source: launch_mdct and launch_smr exactly as mrc_pac_nmr calls them (mono, explicit offsets, the generic mode that
+// writes thresholds, MRC_OPT_EXACT_SPREAD honoured) on the stream's own rows and on Close()'s gathered blocks, then
+// nmr_rungs_kernel.  The streams of a slab -- or, for a stream cut into time slabs, the stream once its last slab ran -- are
+// DECIDED: nmr_file_kernel over [rungs x streams] pseudo-files, one small copy back, the dB values and the rule on the host,
+// and the chosen files gathered behind each other in TargetBufs::sel.  The caller's buffer receives that run alone.
+// (The source analysis is run again rather than taken from phase A's lines: a joint group keeps L, R, M, S rows of one block
+// side by side and comes from the four-signal kernels, mrc_pac_nmr's X from the one-signal kernels on explicit offsets; the
+// numbers must be mrc_pac_nmr's to the bit, so the calls are the same calls.)
+namespace {
+
+constexpr int64_t kTargetBatch = 16384;   // blocks of one shape analysed at a time: X and T of a batch stay below 512 MB
+
+struct TargetSeg { int r; int64_t off, n; };   // bytes of rung r of one time slab in TargetBufs::keep
+
+struct ChainNmr {
+    std::vector<Slab> plan;          // the call's slabs (chained_slabs' own plan) ...
+    size_t slab = 0;                 // ... and the one that runs
+    const int64_t* blockStart = nullptr;   // the caller's
+    int64_t unitChunks = 0;          // chunks of one rung of the streams being decided: the stride of stat's rows
+    std::vector<int64_t> flushOffs;  // Close()'s blocks in flushPcm (a queued copy reads it)
+    std::vector<TargetSeg> segs;
+    int64_t keepUsed = 0, selUsed = 0;
+    double msNmr = 0, msGather = 0;
+};
+
+// room for `need` more bytes behind the `used` bytes a buffer holds, which stay
+int grow_kept(mrc_handle* h, DevBuf& b, int64_t used, int64_t need, hipStream_t st) {
+    if ((size_t)(used + need) <= b.cap) return MRC_OK;
+    DevBuf bigger;
+    MRC_HIP(h, bigger.reserve(std::max<size_t>(2 * b.cap, (size_t)(used + need))));
+    hipError_t e = hipSuccess;
+    if (used) e = hipMemcpyAsync(bigger.p, b.p, (size_t)used, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { bigger.release(); return hip_fail(h, e, "mrc_encode_chained_target_nmr_pac: growing a device buffer"); }
+    b.release();
+    b = bigger;
+    return MRC_OK;
+}
+
+int64_t stream_chunks(const ChainCall& c, const int64_t* block_start, int64_t s) {   // blocks + Close(), a chunk per channel
+    return c.nch() * (block_start[s + 1] - block_start[s] + 1);
+}
+
+int target_nmr_slab(mrc_handle* h, const ChainCall& c, const ChainSchedule& q, const int64_t* count, hipStream_t st) {
+    ChainNmr& N = *c.nmr;
+    ChainBufs& C = h->chain;
+    TargetBufs& T = h->target;
+    const Slab& sl = N.plan[N.slab];
+    const int R = c.n_rates, nch = c.nch(), L = h->cfg.n_mdct_lines;
+    int64_t chunkBase = 0;
+    if (sl.first) {                                      // the first slab of the streams decided together: their stat rows
+        N.unitChunks = sl.timeSlab ? stream_chunks(c, N.blockStart, sl.s0) : c.n_chunks();
+        MRC_HIP(h, T.stat.reserve((size_t)(R * N.unitChunks) * 2 * sizeof(double)));
+    } else chunkBase = nch * (sl.i0 - N.blockStart[sl.s0]);
+    size_t rowBytes = 0, rows = 0;
+    for (int g = 0; g < q.nGroups; ++g) {
+        const int nOut = (g == 4 || nch == 1) ? 1 : 2;
+        const size_t n = (size_t)std::min<int64_t>(count[g], kTargetBatch) * nOut;
+        rows = std::max(rows, n);
+        rowBytes = std::max(rowBytes, n * q.hs[g]->dev.halfN * sizeof(double));
+    }
+    MRC_HIP(h, T.lines.reserve(std::max<size_t>(rowBytes, 256)));
+    MRC_HIP(h, T.thresh.reserve(std::max<size_t>(rowBytes, 256)));
+    MRC_HIP(h, T.oscale.reserve(std::max<size_t>(rows * sizeof(int), 256)));
+    MRC_HIP(h, T.smr.reserve(std::max<size_t>(rows * kMaxBands * sizeof(double), 256)));
+    if (c.with_flush) {
+        N.flushOffs.resize((size_t)count[4]);
+        for (int64_t k = 0; k < count[4]; ++k) N.flushOffs[(size_t)k] = k * 2 * (int64_t)L;
+        MRC_HIP(h, T.flushOffs.reserve(std::max<size_t>(N.flushOffs.size() * sizeof(int64_t), 256)));
+        if (count[4])
+            MRC_HIP(h, hipMemcpyAsync(T.flushOffs.p, N.flushOffs.data(), N.flushOffs.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    }
+    MRC_HIP(h, hipEventRecord(T.ev[0], st));
+    for (int g = 0; g < q.nGroups; ++g) {
+        if (!count[g]) continue;
+        const DevShape& S = q.hs[g]->dev;
+        const int joint = (g == 4 || nch == 1) ? 0 : 1, nOut = joint ? 2 : 1, M = S.halfN;
+        for (int64_t k0 = 0; k0 < count[g]; k0 += kTargetBatch) {
+            const int64_t n = std::min<int64_t>(kTargetBatch, count[g] - k0);
+            const int64_t* offs = (g == 4 ? T.flushOffs.as<int64_t>() : C.g[g].offsets.as<int64_t>()) + k0;
+            for (int ch = 0; ch < nOut; ++ch) {
+                const void* src = g == 4 ? C.flushPcm.p : (ch ? c.pcm_right : c.pcm_left);
+                double* X = T.lines.as<double>() + ch * n * M;
+                int* os = T.oscale.as<int>() + ch * n;
+                MRC_HIP(h, launch_mdct(S, n, src, nullptr, kSampleI16, 0, offs, true, X, os, st));
+                MRC_HIP(h, launch_smr(S, n, src, nullptr, kSampleI16, 0, offs, X, os, T.smr.as<double>() + ch * n * kMaxBands,
+                                      T.thresh.as<double>() + ch * n * M, nullptr, nullptr, h->exactSpread, st));
+            }
+            MRC_HIP(h, launch_nmr_rungs(S, R, joint, n, k0, C.groupDesc.as<ChainGroupDev>(), g,
+                                        C.g[g].chunkMap.as<long long>() + k0 * nOut, T.lines.as<double>(), T.thresh.as<double>(),
+                                        T.stat.as<double>(), N.unitChunks, chunkBase, st));
+        }
+    }
+    MRC_HIP(h, hipEventRecord(T.ev[1], st));
+    return MRC_OK;
+}
+
+int target_nmr_time(mrc_handle* h, const ChainCall& c) {
+    float ms = 0.f;
+    MRC_HIP(h, hipEventElapsedTime(&ms, h->target.ev[0], h->target.ev[1]));
+    c.nmr->msNmr += ms;
+    return MRC_OK;
+}
+
+// what a call returns beside the bytes
+struct TargetOut {
+    double target;
+    int64_t* stream_byte_offset; int32_t *chosen, *met;
+    double *nmr_total_db, *nmr_max_db; int64_t *disturbed_blocks, *n_blocks;
+};
+
+// The streams sl.s0 .. sl.s0 + sl.ns - 1 have all their entries in stat and all their bytes packed: reduce, decide, gather.
+// Whole-stream slab: rung r's bytes of stream s are at buf + base[r] + sOff[r][s]; time slabs: in the segments of `keep`.
+int target_decide(mrc_handle* h, const ChainCall& c, ChainNmr& N, const TargetOut& o, const Slab& sl, const int64_t* sOff,
+                  const int64_t* base, const uint8_t* buf, hipStream_t st) {
+    TargetBufs& T = h->target;
+    const int R = c.n_rates, nch = c.nch(), L = h->cfg.n_mdct_lines;
+    const int64_t nS = c.n_streams, ns = sl.ns, nFiles = R * ns;
+    // pseudo-file (r, s): entries [r * unitChunks + first chunk of s, ...), in file order
+    std::vector<long long> tab((size_t)nFiles + 1 + (size_t)(nFiles + 1) / 2 + 1);
+    int* nchTab = (int*)(tab.data() + nFiles + 1);
+    for (int r = 0; r < R; ++r) {
+        int64_t first = 0;
+        for (int64_t s = 0; s < ns; ++s) {
+            tab[(size_t)(r * ns + s)] = r * N.unitChunks + first;
+            nchTab[r * ns + s] = nch;
+            first += stream_chunks(c, N.blockStart, sl.s0 + s);
+        }
+    }
+    tab[(size_t)nFiles] = R * N.unitChunks;
+    std::vector<double> fileOut((size_t)nFiles * 4);
+    MRC_HIP(h, T.fileTab.reserve(tab.size() * sizeof(long long)));
+    MRC_HIP(h, T.fileOut.reserve(fileOut.size() * sizeof(double)));
+    DrainGuard guard{{st}};                              // (behind the vectors queued copies read and write)
+    MRC_HIP(h, hipMemcpyAsync(T.fileTab.p, tab.data(), tab.size() * sizeof(long long), hipMemcpyHostToDevice, st));
+    MRC_HIP(h, hipEventRecord(T.ev[2], st));
+    MRC_HIP(h, launch_nmr_file(nFiles, T.fileTab.as<long long>(), (const int*)(T.fileTab.as<long long>() + nFiles + 1),
+                               T.stat.as<double>(), T.fileOut.as<double>(), st));
+    MRC_HIP(h, hipEventRecord(T.ev[3], st));
+    MRC_HIP(h, hipMemcpyAsync(fileOut.data(), T.fileOut.p, fileOut.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    MRC_HIP(h, hipStreamSynchronize(st));
+    // ---- the dB values as mrc_pac_nmr forms them, and the rule
+    const double ninf = -std::numeric_limits<double>::infinity();
+    std::vector<long long> span((size_t)ns * 3);
+    int64_t maxLen = 0, selNeed = 0;
+    for (int64_t s = 0; s < ns; ++s) {
+        const int64_t gs = sl.s0 + s;
+        int64_t weight = (int64_t)L * nch;                                      // Close()'s block
+        for (int64_t i = N.blockStart[gs]; i < N.blockStart[gs + 1]; ++i) weight += (int64_t)c.block_b[i] * nch;
+        o.n_blocks[gs] = N.blockStart[gs + 1] - N.blockStart[gs] + 1;
+        int pick = R - 1, met = 0;
+        for (int r = R - 1; r >= 0; --r) {
+            const double* f = fileOut.data() + 4 * (r * ns + s);
+            const double mean = weight > 0 ? f[1] / (double)weight : 0.0;
+            const double total = mean > 0.0 ? 10.0 * std::log10(mean) : ninf;
+            o.nmr_max_db[r * nS + gs] = f[0] > 0.0 ? 10.0 * std::log10(f[0]) : ninf;
+            o.nmr_total_db[r * nS + gs] = total;
+            o.disturbed_blocks[r * nS + gs] = (int64_t)f[2];
+            if (total <= o.target) { pick = r; met = 1; }                       // (descending: the smallest r that meets it stays)
+        }
+        o.chosen[gs] = pick;
+        o.met[gs] = met;
+        o.stream_byte_offset[gs] = N.selUsed + selNeed;
+        if (!sl.timeSlab) {
+            const int64_t* so = sOff + pick * (ns + 1);
+            span[(size_t)(3 * s)] = base[pick] + so[s];
+            span[(size_t)(3 * s + 1)] = N.selUsed + selNeed;
+            span[(size_t)(3 * s + 2)] = so[s + 1] - so[s];
+            maxLen = std::max<int64_t>(maxLen, so[s + 1] - so[s]);
+            selNeed += so[s + 1] - so[s];
+        } else
+            for (const TargetSeg& g : N.segs) if (g.r == pick) selNeed += g.n;
+    }
+    // ---- the chosen files behind each other
+    MRC_TRY(grow_kept(h, T.sel, N.selUsed, std::max<int64_t>(selNeed, 1), st));
+    MRC_HIP(h, hipEventRecord(T.ev[4], st));
+    if (!sl.timeSlab) {
+        MRC_HIP(h, T.span.reserve(span.size() * sizeof(long long)));
+        MRC_HIP(h, hipMemcpyAsync(T.span.p, span.data(), span.size() * sizeof(long long), hipMemcpyHostToDevice, st));
+        MRC_HIP(h, launch_target_gather(ns, maxLen, T.span.as<long long>(), buf, T.sel.as<unsigned char>(), st));
+    } else {
+        int64_t at = N.selUsed;
+        for (const TargetSeg& g : N.segs)
+            if (g.r == o.chosen[sl.s0] && g.n) {
+                MRC_HIP(h, hipMemcpyAsync(T.sel.as<uint8_t>() + at, T.keep.as<uint8_t>() + g.off, (size_t)g.n, hipMemcpyDeviceToDevice, st));
+                at += g.n;
+            }
+        N.segs.clear();
+        N.keepUsed = 0;
+    }
+    MRC_HIP(h, hipEventRecord(T.ev[5], st));
+    MRC_HIP(h, hipStreamSynchronize(st));
+    N.selUsed += selNeed;
+    float a = 0.f, b = 0.f;
+    MRC_HIP(h, hipEventElapsedTime(&a, T.ev[2], T.ev[3]));
+    MRC_HIP(h, hipEventElapsedTime(&b, T.ev[4], T.ev[5]));
+    N.msNmr += a;
+    N.msGather += b;
+    return MRC_OK;
+}
+
+// the refusals of include/mrc_hip.h, before any device work
+int target_check(mrc_handle* h, const std::string& w, int n_rates, const double* rates, double target, int64_t n_streams,
+                 const void* pcm_left, int64_t stream_stride, const int64_t* block_start, const int64_t* block_offset,
+                 const int32_t* block_a, const int32_t* block_b, const uint32_t* num_samples, const uint8_t* out, int64_t out_cap,
+                 const TargetOut& o, const int64_t* total_bytes) {
+    if (!h) return MRC_ERR_INVALID;
+    if (n_rates < 1 || n_rates > MRC_MAX_RATES) return fail(h, MRC_ERR_INVALID, w + ": n_rates must lie in 1..MRC_MAX_RATES (16)");
+    if (!rates) return fail(h, MRC_ERR_INVALID, w + ": target_bits_per_sample must not be NULL");
+    for (int r = 0; r < n_rates; ++r) {
+        if (!std::isfinite(rates[r]) || !(rates[r] > 0.0) || rates[r] > 64.0)
+            return fail(h, MRC_ERR_INVALID, w + ": target_bits_per_sample[" + std::to_string(r) + "] must be finite and in (0, 64]");
+        if (r && !(rates[r] > rates[r - 1]))
+            return fail(h, MRC_ERR_INVALID, w + ": target_bits_per_sample must be strictly ascending (entry " + std::to_string(r) + " is not)");
+    }
+    if (std::isnan(target)) return fail(h, MRC_ERR_INVALID, w + ": target_nmr_total_db is NaN");
+    if (!num_samples) return fail(h, MRC_ERR_INVALID, w + ": num_samples must not be NULL (whole files only)");
+    if (h->sensOn)
+        return fail(h, MRC_ERR_INVALID, w + ": MRC_OPT_SENSITIVITY is on (the certificate covers one rate: encode each rate on its own)");
+    if (n_streams < 0 || !pcm_left || stream_stride <= 0 || !block_start || !block_offset || !block_a || !block_b || !out ||
+        out_cap < 0 || !o.stream_byte_offset || !o.chosen || !o.met || !o.nmr_total_db || !o.nmr_max_db || !o.disturbed_blocks ||
+        !o.n_blocks || !total_bytes)
+        return fail(h, MRC_ERR_INVALID, w + ": bad argument (a NULL pointer, a negative count or capacity)");
+    const int L = h->cfg.n_mdct_lines;
+    for (int64_t s = 0; s < n_streams; ++s) {
+        const int64_t i0 = block_start[s], i1 = block_start[s + 1];
+        const std::string which = w + ": stream " + std::to_string(s);
+        if (i1 <= i0) return fail(h, MRC_ERR_INVALID, which + ": block_start gives it no block");
+        if (block_a[i0] != L)
+            return fail(h, MRC_ERR_INVALID, which + ": block_a of its first block must be n_mdct_lines (the zero prior hop)");
+        int64_t sum = 0;
+        for (int64_t i = i0; i < i1; ++i) {
+            if (block_offset[i] != sum)
+                return fail(h, MRC_ERR_INVALID, which + ": block_offset[" + std::to_string(i) + "] must be the sum of block_a of the "
+                                                "stream's earlier blocks (" + std::to_string(sum) + "): the NMR positions blocks by it");
+            sum += block_a[i];
+        }
+        if (block_b[i1 - 1] != L)
+            return fail(h, MRC_ERR_INVALID, which + ": block_b of its last block must be n_mdct_lines (a stream must end with a long "
+                                            "block: the reference's Close() assumes it, pacfileThem.py:973-984)");
+    }
+    return MRC_OK;
+}
+
+// pcm_left / pcm_right in device memory; the chosen bytes end in TargetBufs::sel and, if they fit, in out (host or device)
+int chained_target(mrc_handle* h, const std::string& w, ChainCall c, const TargetOut& o, uint8_t* out, int64_t out_cap,
+                   bool outOnHost, int64_t* total_bytes, hipStream_t st) {
+    const int R = c.n_rates;
+    const int64_t nS = c.n_streams;
+    ChainBufs& C = h->chain;
+    TargetBufs& T = h->target;
+    for (auto& e : T.ev) if (!e) MRC_HIP(h, hipEventCreate(&e));
+    ChainNmr N;
+    N.blockStart = c.block_start;
+    N.plan = plan_slabs(nS, c.block_start, slab_cap(h, R, c.nch()));
+    std::vector<int64_t> sOff((size_t)R * (nS + 1)), totals((size_t)R), caps((size_t)R, std::numeric_limits<int64_t>::max() / 4);
+    c.stream_byte_offset = sOff.data();
+    c.total_bytes = totals.data();
+    c.nmr = &N;
+    *total_bytes = 0;
+    o.stream_byte_offset[0] = 0;
+    int rc = chained_slabs(h, c, caps.data(), nullptr,
+        [&](int r, uint8_t* buf, int64_t n, int64_t) {
+            if (!N.plan[N.slab].timeSlab) return (int)MRC_OK;        // (whole streams: gathered from the slab's buffer)
+            MRC_TRY(grow_kept(h, T.keep, N.keepUsed, std::max<int64_t>(n, 1), st));
+            if (n) MRC_HIP(h, hipMemcpyAsync(T.keep.as<uint8_t>() + N.keepUsed, buf, (size_t)n, hipMemcpyDeviceToDevice, st));
+            N.segs.push_back(TargetSeg{r, N.keepUsed, n});
+            N.keepUsed += n;
+            return (int)MRC_OK;
+        },
+        [&](const Slab& sl, const int64_t* slabOff, const int64_t* base, const uint8_t* buf) {
+            if (sl.last) MRC_TRY(target_decide(h, c, N, o, sl, slabOff, base, buf, st));
+            ++N.slab;
+            return (int)MRC_OK;
+        });
+    T.ms[0] = h->chainMs[0]; T.ms[1] = h->chainMs[1]; T.ms[2] = N.msNmr; T.ms[3] = h->chainMs[2] + N.msGather;
+    if (rc != MRC_OK) return rc;
+    const int64_t total = N.selUsed;
+    *total_bytes = total;
+    o.stream_byte_offset[nS] = total;
+    C.lastTotal = total;                                 // (mrc_chain_fetch_output: the chosen bytes, whatever out_cap was)
+    C.lastSrc = T.sel.p;
+    if (total > out_cap) return fail(h, MRC_ERR_NOMEM, w + ": out_cap too small (see total_bytes; mrc_chain_fetch_output)");
+    if (total) MRC_HIP(h, hipMemcpyAsync(out, T.sel.p, (size_t)total, outOnHost ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
+    MRC_HIP(h, hipStreamSynchronize(st));
+    return MRC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mrc_encode_chained_target_nmr_pac(mrc_handle* h, int n_rates, const double* target_bits_per_sample,
+                                      double target_nmr_total_db, int64_t n_streams, const int16_t* pcm_left,
+                                      const int16_t* pcm_right, int64_t stream_stride, const int64_t* block_start,
+                                      const int64_t* block_offset, const int32_t* block_a, const int32_t* block_b,
+                                      int use_huffman, const uint32_t* num_samples, uint8_t* out, int64_t out_cap,
+                                      int64_t* stream_byte_offset, int32_t* chosen, int32_t* met, double* nmr_total_db,
+                                      double* nmr_max_db, int64_t* disturbed_blocks, int64_t* n_blocks, int64_t* total_bytes) {
+    const TargetOut o{target_nmr_total_db, stream_byte_offset, chosen, met, nmr_total_db, nmr_max_db, disturbed_blocks, n_blocks};
+    MRC_TRY(target_check(h, __func__, n_rates, target_bits_per_sample, target_nmr_total_db, n_streams, pcm_left, stream_stride,
+                         block_start, block_offset, block_a, block_b, num_samples, out, out_cap, o, total_bytes));
+    ChainCall c{n_rates, target_bits_per_sample, n_streams, pcm_left, pcm_right, MRC_SAMPLES_PCM16, stream_stride, block_start,
+                block_offset, block_a, block_b, nullptr, use_huffman, 1, num_samples, nullptr, nullptr, nullptr, nullptr, nullptr,
+                nullptr};
+    h->chain.lastTotal = -1;
+    h->chain.lastSrc = nullptr;
+    MRC_HIP(h, hipSetDevice(h->device));
+    MRC_TRY(stage_pcm(h, c));
+    c.pcm_left = h->chain.pcmL.p;
+    if (c.pcm_right) c.pcm_right = h->chain.pcmR.p;
+    return chained_target(h, __func__, c, o, out, out_cap, true, total_bytes, h->stream);
+}
+
+int mrc_dev_encode_chained_target_nmr_pac(mrc_handle* h, int n_rates, const double* target_bits_per_sample,
+                                          double target_nmr_total_db, int64_t n_streams, const int16_t* pcm_left,
+                                          const int16_t* pcm_right, int64_t stream_stride, const int64_t* block_start,
+                                          const int64_t* block_offset, const int32_t* block_a, const int32_t* block_b,
+                                          int use_huffman, const uint32_t* num_samples, uint8_t* out, int64_t out_cap,
+                                          int64_t* stream_byte_offset, int32_t* chosen, int32_t* met, double* nmr_total_db,
+                                          double* nmr_max_db, int64_t* disturbed_blocks, int64_t* n_blocks, int64_t* total_bytes,
+                                          void* stream) {
+    const TargetOut o{target_nmr_total_db, stream_byte_offset, chosen, met, nmr_total_db, nmr_max_db, disturbed_blocks, n_blocks};
+    MRC_TRY(target_check(h, __func__, n_rates, target_bits_per_sample, target_nmr_total_db, n_streams, pcm_left, stream_stride,
+                         block_start, block_offset, block_a, block_b, num_samples, out, out_cap, o, total_bytes));
+    const ChainCall c{n_rates, target_bits_per_sample, n_streams, pcm_left, pcm_right, MRC_SAMPLES_PCM16, stream_stride, block_start,
+                      block_offset, block_a, block_b, nullptr, use_huffman, 1, num_samples, nullptr, nullptr, nullptr, nullptr,
+                      nullptr, stream};
+    h->chain.lastTotal = -1;
+    h->chain.lastSrc = nullptr;
+    MRC_HIP(h, hipSetDevice(h->device));
+    return chained_target(h, __func__, c, o, out, out_cap, false, total_bytes, pick_stream(h, stream));
+}
+
+int mrc_get_target_ms(mrc_handle* h, double* ms) {
+    if (!h || !ms) return MRC_ERR_INVALID;
+    for (int i = 0; i < 4; ++i) ms[i] = h->target.ms[i];
+    return MRC_OK;
 }
 
 }  // extern "C"

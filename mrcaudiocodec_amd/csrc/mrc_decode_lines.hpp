@@ -1,5 +1,5 @@
-// The decoded MDCT lines of one channel of one block, before the IMDCT: shared by decode_kernel (mrc_kernels_decode.hip)
-// and nmr_band_kernel (mrc_kernels_nmr.hip), so that the noise the NMR measures is that of the samples the decoder writes.
+// The decoded MDCT lines of one channel of one block, before the IMDCT: shared by decode_kernel (mrc_kernels_decode.hip),
+// nmr_band_kernel (mrc_kernels_nmr.hip) and nmr_rungs_kernel (mrc_kernels_target.hip), so that the noise the NMR measures is that of the samples the decoder writes.
 //   vDequantize (quantize.py:325-357, operation order kept: ((sign*mag)*2) / (2^R - 1), one correctly rounded division)
 //   -> divide by the overall scale level (a power of two: exact, codecThem.py:47-51, 92-109) -> ReconstructLR
 //   (ms_stereo.py:33-49; a joint block's output channel dequantises BOTH streams of the bands whose M/S switch is set).
@@ -28,10 +28,13 @@ __device__ __forceinline__ double dequantize_dev(int scale, int mant, int nScale
 
 // Line k (band `band`) of output channel ch.  Non-joint: os[0], sf / ba [nb], mant [M] of the channel's own chunk.
 // Joint: os [4] = L, R, M, S; ms [nb]; sf / ba [2][nb], mant [2][M] of the block's two streams.
+// MantT: int (the parsed chunks of decode_kernel and nmr_band_kernel) or unsigned short (the chained scan's plane,
+// nmr_rungs_kernel): the same codes.
+template <class MantT>
 __device__ __forceinline__ double decode_line(int k, int band, int ch, bool joint, int nb, int M, int nScaleBits,
                                               const int* __restrict__ os, const int* __restrict__ ms,
                                               const int* __restrict__ sf, const int* __restrict__ ba,
-                                              const int* __restrict__ mant) {
+                                              const MantT* __restrict__ mant) {
     double x;
     if (!joint) {
         const int bits = ba[band];

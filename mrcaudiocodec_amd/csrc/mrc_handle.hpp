@@ -102,12 +102,29 @@ struct ChainBufs {
         streamPos;
     hipEvent_t evT[4] = {};          // phase timing: start | phase A done | phase B done | packed
     int64_t lastTotal = -1;          // bytes the last mrc_encode_chained_stream_pac left in `out` (-1: none) -- mrc_chain_fetch_output
+    const void* lastSrc = nullptr;   // ... or, after mrc_encode_chained_target_nmr_pac, in TargetBufs::sel (null: in `out`)
     void release() {
         for (auto& x : g) x.release();
         for (DevBuf* b : {&pcmL, &pcmR, &flushPcm, &items, &itemStart, &reservoir, &groupDesc, &packWs, &out, &hdr,
                           &chunkStream, &resTrace, &firstChunk, &streamPos})
             b->release();
         for (auto& e : evT) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    }
+};
+
+// Encode to a target noise-to-mask ratio (mrc_encode_chained_target_nmr_pac, mrc_api_chain.cpp): reused from call to call
+struct TargetBufs {
+    DevBuf lines, thresh, oscale, smr;   // source analysis of one batch of blocks of one shape: X, T, overall scale, SMR (unused)
+    DevBuf flushOffs;                // where Close()'s blocks start in ChainBufs::flushPcm
+    DevBuf stat;                     // [rungs][chunks of the streams being decided][2]: max r_j, b * mean r_j
+    DevBuf fileTab, fileOut, span;   // nmr_file_kernel's pseudo-files and sums; the gather's spans
+    DevBuf keep;                     // a stream cut into time slabs: the packed bytes of all rungs until its last slab decides
+    DevBuf sel;                      // the chosen files of the call, contiguous in stream order
+    hipEvent_t ev[6] = {};           // NMR kernels of a slab | file reduction | gather, start and end each
+    double ms[4] = {0, 0, 0, 0};     // phase A + preparation | scan | NMR (threshold pass included) | pack + gather
+    void release() {
+        for (DevBuf* b : {&lines, &thresh, &oscale, &smr, &flushOffs, &stat, &fileTab, &fileOut, &span, &keep, &sel}) b->release();
+        for (auto& e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
     }
 };
 
@@ -273,6 +290,7 @@ struct mrc_handle {
     mrc::ChainBufs chain;            // mrc_encode_chained_*: see mrc_api_chain.cpp
     mrc::DecodeBufs dec;             // mrc_dev_unpack_blocks / mrc_decode_pac_pcm16: see mrc_api_decode.cpp
     mrc::NmrBufs nmr;                // mrc_pac_nmr: see mrc_api_nmr.cpp
+    mrc::TargetBufs target;          // mrc_encode_chained_target_nmr_pac: see mrc_api_chain.cpp
     double chainMs[4] = {0, 0, 0, 0};   // last chained encode: phase A, phase B, pack, whole call (host clock)
     bool timing = false;
     bool exactSpread = false;        // mrc_set_option(MRC_OPT_EXACT_SPREAD)

@@ -243,6 +243,17 @@ hipError_t launch_chain_flush_gather(int64_t nStreams, int L, const void* pcmL, 
 hipError_t launch_chain_headers(int64_t nStreams, int hdrLen, const unsigned char* hdr, const long long* firstChunk,
                                 const long long* pos, unsigned char* out, long long outCap, long long* streamPos,
                                 hipStream_t st);
+// mrc_kernels_target.hip -- the NMR of every rung of a chained ladder from the scan's planes (mrc_encode_chained_target_nmr_pac)
+// One workgroup per entry (block k0 + kb, output channel) of n blocks of group g: groups [nRates][kChainGroups] in device
+// memory, chunkMap [n * (joint ? 2 : 1)] the entry's chunk in file order, lines / thresh [(joint ? 2 : 1) * n][halfN] the
+// source analysis (a joint group: the left rows, then the right rows).  stat[2 * (r * statStride + chunkBase + chunk)] =
+// {max_j r_j, b * mean_j r_j} of rung r: launch_nmr_file's input.
+hipError_t launch_nmr_rungs(const DevShape& S, int nRates, int joint, int64_t n, int64_t k0, const ChainGroupDev* groups,
+                            int g, const long long* chunkMap, const double* lines, const double* thresh, double* stat,
+                            long long statStride, long long chunkBase, hipStream_t st);
+// span [nStreams][3] = {first byte in `in`, first byte in `out`, length}: byte copies, longest run maxLen
+hipError_t launch_target_gather(int64_t nStreams, int64_t maxLen, const long long* span, const unsigned char* in,
+                                unsigned char* out, hipStream_t st);
 // mrc_kernels_huff.hip
 hipError_t launch_huffman_gain(const DevShape& S, int64_t nFrames, int nStreams, const int* bitAlloc,
                                const int* mantissa, const int* reservoirOut, int* huffTable, int* bitsSaved,

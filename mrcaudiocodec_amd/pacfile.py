@@ -249,6 +249,43 @@ def encode_stream_ladder(handle, stream, shapes, rates, use_huffman=True, num_sa
     return [r["bytes"].tobytes() for r in rs]
 
 
+def choose_rung(nmr_total_db, target_db):
+    """The rule of mrc_encode_chained_target_nmr_pac on one stream's per-rung values: -> (chosen, met) = (the smallest r with
+    nmr_total_db[r] <= target_db, True), or (the top rung, False) if none meets it.  -inf (silence) meets every target."""
+    vals = [float(v) for v in nmr_total_db]
+    if not vals:
+        raise ValueError("choose_rung: no rungs")
+    if np.isnan(target_db):
+        raise ValueError("choose_rung: the target is NaN")
+    for r, v in enumerate(vals):
+        if v <= target_db:
+            return r, True
+    return len(vals) - 1, False
+
+
+def encode_stream_target_nmr(handle, stream, shapes, rates, target_db, use_huffman=True, num_samples=None):
+    """ONE stream of int16 PCM codes -- stereo [2][samples], or mono [samples] / [1][samples], with the zero prior hop -- and
+    its block-shape sequence, encoded at the ascending rate ladder `rates` and measured in one library call
+    (mrc_encode_chained_target_nmr_pac).  -> dict: data (the `.pac` bytes of the LOWEST rung whose nmr_total_db is <=
+    target_db; the top rung, met False, if none is), chosen, rate, met, and per rung nmr_total_db, nmr_max_db,
+    disturbed_blocks (what measure_nmr gives for encode_stream_ladder's files), n_blocks."""
+    L = handle.cfg.n_mdct_lines
+    stream = np.asarray(stream)
+    if stream.dtype != np.int16:
+        raise ValueError("the stream must hold int16 PCM codes (the NMR's source is int16)")
+    if stream.ndim == 1:
+        stream = stream[None]
+    if stream.ndim != 2 or stream.shape[0] not in (1, 2):
+        raise ValueError("stream must be stereo [2][samples] or mono [samples]")
+    if not len(shapes) or shapes[-1][2] != L:
+        raise ValueError("the stream must end with a long block (the reference's Close() assumes it)")
+    if num_samples is None:
+        num_samples = sum(int(b) for (_, _, b) in shapes)
+    right = stream[1][None] if stream.shape[0] == 2 else None
+    return handle.encode_chained_pac_target_nmr(stream[0][None], right, [shapes], rates, target_db, use_huffman=use_huffman,
+                                                num_samples=[num_samples])[0]
+
+
 def encode_mono_stream_per_block(handle, stream, shapes, use_huffman=True, num_samples=None):
     """The block-at-a-time form of encode_mono_stream: one mrc_encode_mono per block, the reservoir carried on the host
     (reservoir_out + Huffman bits_saved), C++ packer, then Close()'s block.  The cross-check of the chained mono path
