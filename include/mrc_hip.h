@@ -502,6 +502,52 @@ int mrc_dev_encode_chained_target_nmr_pac(mrc_handle* h, int n_rates, const doub
                                           int64_t* total_bytes, void* stream);
 int mrc_get_target_ms(mrc_handle* h, double* ms /*[4]*/);
 
+/* ---- constant-quality VBR: every band coded to a noise-to-mask ceiling -------------------------------------------------
+ * mrc_encode_vbr_nmr_pac encodes whole streams without a bit budget and without a reservoir: block shapes, window, MDCT,
+ * overall scales, the M/S switch, the quantiser (ScaleFactor, vMantissa) and the file format are the chained call's, but
+ * every band of every block gets the FEWEST mantissa bits (0, 2, 3, .., 2^n_mant_size_bits capped at 16, tried in that
+ * order) at which its measured noise-to-mask ratio r_j = noise_j / mask_j, as mrc_pac_nmr defines it, is <= the ceiling
+ * c = 10^(ceiling_db / 10); c is formed once on the host and returned in *ceiling_ratio.  A band that misses c even at the
+ * most bits keeps them and is counted in capped_bands[s].  In a joint block an L/R band is first-fit per coded stream
+ * against its own channel; an M/S band starts at (0, 0) and, while max(r_L, r_R) > c, raises the stream (0 -> 2, else + 1)
+ * whose own error energy is larger (a tie: stream 0), the other one when that stream is at the most bits; when both are,
+ * the band is capped (counted once).  A band without lines takes 0 bits.  DESIGN.md section 12 states the rule in full.
+ * The Huffman table of a chunk is calculateHuffmanGain's choice (15 = raw with use_huffman == 0).  A block depends on its
+ * own samples only, so one long stream encodes with the parallelism of a batch.
+ * Whole files only: headers and Close()'s flush always (num_samples must not be NULL), 16-bit PCM, pcm_right == NULL means
+ * mono streams.  out[stream_byte_offset[s] .. stream_byte_offset[s + 1]) is the complete file of stream s.
+ * The numbers: nmr_total_db[s], nmr_max_db[s], disturbed_blocks[s] and n_blocks[s] are the SAME doubles and counts
+ * mrc_pac_nmr returns for that file against the stream's own row from sample n_mdct_lines on, with src_frames = (end of the
+ * stream's last block) - n_mdct_lines, provided the row's first n_mdct_lines samples are zero (every sum in mrc_pac_nmr's
+ * order, the same source analysis calls, MRC_OPT_EXACT_SPREAD honoured); where capped_bands[s] == 0, max r <= c holds
+ * exactly.  coded_bits[s]: the payload bits of the stream's file, 8 x (its bytes - the file header - 4 per chunk).
+ * +inf ceiling: 0 bits everywhere; -inf (c = 0): met only where the noise is exactly 0.  Results do not depend on the
+ * slab size (MRC_OPT_CHAIN_SLAB_BLOCKS), on what shares the call, or on its size.
+ *   MRC_ERR_INVALID, with a message naming the argument and before any device work, for: a NaN ceiling_db; num_samples ==
+ *   NULL; MRC_OPT_SENSITIVITY on; the block layouts mrc_encode_chained_target_nmr_pac refuses (first block_a !=
+ *   n_mdct_lines, block_offset[i] not the sum of the stream's earlier block_a, no long block at the end).
+ *   out [out_cap]: the bound is mrc_chain_out_bound_ex.  Too small: MRC_ERR_NOMEM with total_bytes and every result array
+ *   filled; a call of one slab keeps its bytes on the device for mrc_chain_fetch_output, as mrc_encode_chained_stream_pac does.
+ * mrc_dev_encode_vbr_nmr_pac: pcm_left / pcm_right and out in DEVICE memory, all other pointers host; it synchronises
+ * `stream` before it returns.
+ * mrc_get_vbr_ms: device time of the last call, ms: phase A + source analysis (uploads included), the allocator kernel,
+ * pack, the sum of the three (the file reduction, a few microseconds per slab, is outside them). */
+int mrc_encode_vbr_nmr_pac(mrc_handle* h, double ceiling_db, int64_t n_streams, const int16_t* pcm_left, const int16_t* pcm_right,
+                           int64_t stream_stride, const int64_t* block_start, const int64_t* block_offset,
+                           const int32_t* block_a, const int32_t* block_b, int use_huffman, const uint32_t* num_samples,
+                           uint8_t* out, int64_t out_cap, int64_t* stream_byte_offset /*[n_streams + 1]*/,
+                           double* ceiling_ratio, int64_t* capped_bands /*[n_streams]*/, int64_t* coded_bits /*[n_streams]*/,
+                           double* nmr_total_db /*[n_streams]*/, double* nmr_max_db /*[n_streams]*/,
+                           int64_t* disturbed_blocks /*[n_streams]*/, int64_t* n_blocks /*[n_streams]*/, int64_t* total_bytes);
+int mrc_dev_encode_vbr_nmr_pac(mrc_handle* h, double ceiling_db, int64_t n_streams, const int16_t* pcm_left,
+                               const int16_t* pcm_right, int64_t stream_stride, const int64_t* block_start,
+                               const int64_t* block_offset, const int32_t* block_a, const int32_t* block_b, int use_huffman,
+                               const uint32_t* num_samples, uint8_t* out, int64_t out_cap, int64_t* stream_byte_offset,
+                               double* ceiling_ratio, int64_t* capped_bands, int64_t* coded_bits, double* nmr_total_db,
+                               double* nmr_max_db, int64_t* disturbed_blocks, int64_t* n_blocks, int64_t* total_bytes,
+                               void* stream);
+int mrc_get_vbr_ms(mrc_handle* h, double* ms /*[4]*/);
+
 /* ---- sensitivity certificate (round 4) ----
  * Bit-identity of the integers with the reference is an empirical, counted result: each of them is a floor / compare of
  * float64 values whose last bits differ between implementations (FFT factorisation, log10 / atan / 2^x), and it can only come

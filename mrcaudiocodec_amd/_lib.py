@@ -138,6 +138,13 @@ def _load():
                                                             C.c_int64, _i64p, _i32p, _i32p, _f64p, _f64p, _i64p, _i64p, _i64p,
                                                             C.c_void_p]),
         "mrc_get_target_ms": (C.c_int, [H, _f64p]),
+        "mrc_encode_vbr_nmr_pac": (C.c_int, [H, C.c_double, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, _i64p, _i64p, _i32p,
+                                             _i32p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, _i64p, _f64p, _i64p, _i64p,
+                                             _f64p, _f64p, _i64p, _i64p, _i64p]),
+        "mrc_dev_encode_vbr_nmr_pac": (C.c_int, [H, C.c_double, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, _i64p, _i64p,
+                                                 _i32p, _i32p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, _i64p, _f64p, _i64p,
+                                                 _i64p, _f64p, _f64p, _i64p, _i64p, _i64p, C.c_void_p]),
+        "mrc_get_vbr_ms": (C.c_int, [H, _f64p]),
         "mrc_pac_read_header": (C.c_int, [_u8p, C.c_int64, C.POINTER(MrcConfig), _i32p, C.POINTER(C.c_uint32), _i64p]),
         "mrc_pac_scan_chunks": (C.c_int64, [_u8p, C.c_int64, C.c_int64, _i64p, C.c_int64]),
         "mrc_unpack_blocks": (C.c_int, [C.POINTER(MrcConfig), C.c_int64, C.c_int, C.c_int, _u8p, C.c_int64, _i64p] +
@@ -684,6 +691,64 @@ class Handle:
         (threshold pass included), pack + gather (ms)"""
         ms = np.zeros(4, np.float64)
         self._check(lib.mrc_get_target_ms(self._h, _p(ms, _f64p)))
+        return ms
+
+    def encode_vbr_nmr_pac(self, pcm_left, pcm_right, shapes, ceiling_db, use_huffman=True, num_samples=None, device=None,
+                           stream=None, out_cap=None):
+        """mrc_encode_vbr_nmr_pac: constant-quality VBR.  The streams of encode_chained_pac (int16 PCM codes, each row
+        starting with its zero prior hop) coded without a bit budget: every band of every block gets the fewest mantissa
+        bits at which its measured noise-to-mask ratio is <= 10^(ceiling_db / 10).  num_samples [nStreams] is required:
+        whole files only.
+        device = (left_ptr, right_ptr or None, stride, out_ptr, out_cap): PCM and output in HBM (mrc_dev_encode_vbr_nmr_pac;
+        `data` is then the (start, end) bytes of the stream's file in out).
+        out_cap: the size of the host buffer (default: the call's bound).
+        -> one dict per stream: data (bytes), ceiling_ratio, capped_bands, coded_bits, nmr_total_db, nmr_max_db,
+        disturbed_blocks, n_blocks -- the numbers pac_nmr gives for the file."""
+        if num_samples is None:
+            raise ValueError("encode_vbr_nmr_pac: num_samples is required (whole files only)")
+        if device is None and np.atleast_2d(pcm_left).dtype != np.int16:
+            raise ValueError("encode_vbr_nmr_pac: int16 PCM codes only (the NMR's source is int16)")
+        dev5 = None if device is None else (device[0], device[1], 1, device[2])
+        q = self._chain_args(pcm_left, pcm_right, shapes, use_huffman, True, num_samples, dev5)
+        n = q.n_streams
+        pcm = (q.pcm[0], q.pcm[1], q.pcm[3])
+        s_off = np.zeros(n + 1, np.int64)
+        ratio = np.zeros(1, np.float64)
+        capped, bits = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
+        tot, mx = np.zeros(max(n, 1), np.float64), np.zeros(max(n, 1), np.float64)
+        dist, nblk = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
+        total = np.zeros(1, np.int64)
+        args = (self._h, float(ceiling_db), n) + pcm + q.head + (q.opts[0], q.opts[2])
+        tail = (_p(s_off, _i64p), _p(ratio, _f64p), _p(capped, _i64p), _p(bits, _i64p), _p(tot, _f64p), _p(mx, _f64p),
+                _p(dist, _i64p), _p(nblk, _i64p), _p(total, _i64p))
+        buf = None
+        if device is not None:
+            self._check(lib.mrc_dev_encode_vbr_nmr_pac(*args, device[3], int(device[4]), *tail, stream))
+        else:
+            bound = q.bound()
+            if out_cap is None:
+                out_cap = bound
+            buf = np.empty(max(int(out_cap), 1), np.uint8)
+            rc = lib.mrc_encode_vbr_nmr_pac(*args, vp(buf), int(out_cap), *tail)
+            if rc == MRC_ERR_NOMEM and 0 < int(total[0]) <= bound:
+                buf = np.empty(int(total[0]), np.uint8)
+                if lib.mrc_chain_fetch_output(self._h, vp(buf), buf.size, _p(total, _i64p)) != 0:
+                    # several slabs: nothing is kept on the device -- once more, into a buffer of the reported size
+                    self._check(lib.mrc_encode_vbr_nmr_pac(*args, vp(buf), buf.size, *tail))
+            else:
+                self._check(rc)
+        out = []
+        for s in range(n):
+            lo, hi = int(s_off[s]), int(s_off[s + 1])
+            out.append(dict(data=(lo, hi) if buf is None else buf[lo:hi].tobytes(), ceiling_ratio=float(ratio[0]),
+                            capped_bands=int(capped[s]), coded_bits=int(bits[s]), nmr_total_db=float(tot[s]),
+                            nmr_max_db=float(mx[s]), disturbed_blocks=int(dist[s]), n_blocks=int(nblk[s])))
+        return out
+
+    def vbr_ms(self):
+        """device time of the last encode_vbr_nmr_pac: phase A + source analysis, the allocator, pack, their sum (ms)"""
+        ms = np.zeros(4, np.float64)
+        self._check(lib.mrc_get_vbr_ms(self._h, _p(ms, _f64p)))
         return ms
 
     def chain_out_bound(self, block_start, block_a, block_b, with_flush=True, with_headers=True, n_channels=2):

@@ -26,6 +26,8 @@ nmr_total_db (band-averaged ratio, weighted by block length), disturbed_blocks (
 its mask) and n_blocks.  --measure prints the same lines for existing dst file(s) against src without encoding:
     python -m mrcaudiocodec_amd.cli in.wav out_{bps}.pac --bits-per-sample 1.5,2.86,4 --measure
 
+Constant-quality VBR (mrc_encode_vbr_nmr_pac): --vbr-nmr DB codes every band with the fewest bits that keep its noise-to-mask
+ratio <= DB; no bit rate is given, one JSON line reports bits per sample, capped bands and the NMR of the file written.
 Target quality (mrc_encode_chained_target_nmr_pac): --target-nmr DB with an ascending --bits-per-sample list of two rates or
 more encodes the ladder, measures every rung on the device and writes ONE file to dst: the lowest rate whose nmr_total_db
 is <= DB (the top rate if none is).  One JSON line says which: chosen_bits_per_sample, met, and per rung nmr_total_db,
@@ -265,6 +267,63 @@ def encode_wav_target_nmr(in_path, out_path, bits_per_sample, target_nmr, use_hu
     return r
 
 
+def check_vbr_args(vbr_nmr, bits_per_sample=None, target_nmr=None, out_path=None, decode=False, certify=False, measure=False):
+    """The refusals of --vbr-nmr, before a file is read or a device is touched.  -> the ceiling in dB (float)."""
+    if decode or certify or measure:
+        raise ValueError("--vbr-nmr encodes one file: it does not go with -d, --certify or --measure")
+    if bits_per_sample is not None or target_nmr is not None:
+        raise ValueError("--vbr-nmr has no bit rate: it does not go with --bits-per-sample or --target-nmr")
+    try:
+        ceiling = float(vbr_nmr)
+    except (TypeError, ValueError):
+        raise ValueError("--vbr-nmr: %r is not a number" % (vbr_nmr,))
+    if np.isnan(ceiling):
+        raise ValueError("--vbr-nmr: the ceiling must not be NaN")
+    if out_path is not None and "{bps}" in out_path:
+        raise ValueError("--vbr-nmr writes ONE file: dst must not contain {bps}")
+    return ceiling
+
+
+def encode_wav_vbr_nmr(in_path, out_path, vbr_nmr, use_huffman=True, device_id=0, handle=None, exact_spread=False):
+    """encode_wav as constant-quality VBR (mrc_encode_vbr_nmr_pac): every band coded with the fewest bits that keep its
+    noise-to-mask ratio <= vbr_nmr dB.  Writes the file to out_path (if given) and returns the report of
+    pacfile.encode_stream_vbr_nmr plus bits_per_sample = coded_bits / (channels x coded samples)."""
+    ceiling = check_vbr_args(vbr_nmr, out_path=out_path)
+    rate, n_ch, num_samples, pcm = read_wav_pcm(in_path)
+    if n_ch not in (1, 2):
+        raise ValueError("%d-channel input: mono and stereo WAV files only" % n_ch)
+    shape = {} if handle is None else dict(n_mdct_lines=handle.cfg.n_mdct_lines, n_short=handle.cfg.n_short)
+    try:
+        pacfile.header(pacfile.make_config(sample_rate=rate, **shape), n_ch, num_samples)
+    except MrcError as e:
+        raise ValueError("%d Hz input: outside the sample rates the reference can encode (%s)" % (rate, e))
+    h = handle if handle is not None else Handle(sample_rate=rate, device_id=device_id)
+    was_exact = h.get_option(1)
+    if exact_spread:
+        h.set_option(1, 1)
+    try:
+        L = h.cfg.n_mdct_lines
+        codes = np.concatenate([np.zeros((n_ch, L), np.int16), pcm], axis=1)
+        shapes = transient.block_shape_array(h, codes)
+        if not len(shapes):
+            raise ValueError("file too short: fewer than two hops")
+        if shapes[-1, 2] != L:
+            raise ValueError("the stream must end with a long block (the reference's Close() assumes it)")
+        r = pacfile.encode_stream_vbr_nmr(h, codes[0] if n_ch == 1 else codes, shapes, ceiling, use_huffman=use_huffman,
+                                          num_samples=num_samples)
+        coded = sum(int(b) for (_, _, b) in shapes)
+    finally:
+        if handle is not None:
+            h.set_option(1, was_exact)
+        else:
+            h.close()
+    r["bits_per_sample"] = r["coded_bits"] / float(n_ch * coded)
+    if out_path:
+        with open(out_path, "wb") as f:
+            f.write(r["data"])
+    return r
+
+
 def wav_header(n_ch, n_data_bytes, sample_rate):
     """pcmfile.py:141-153"""
     return pack('<4sL4s4sLHHLLHH4sL', b"RIFF", 36 + n_data_bytes, b"WAVE", b"fmt ", 16, 1, n_ch, sample_rate,
@@ -360,8 +419,22 @@ def main(argv=None):
     ap.add_argument("--target-nmr", default=None, metavar="DB",
                     help="with an ascending --bits-per-sample list of two rates or more: write ONE file to dst, the lowest "
                          "rate whose nmr_total_db against src is <= DB (the top rate if none is), and print one JSON line")
+    ap.add_argument("--vbr-nmr", default=None, metavar="DB",
+                    help="constant-quality VBR: no bit rate; every band gets the fewest bits that keep its noise-to-mask ratio "
+                         "<= DB.  Writes ONE file to dst and prints one JSON line (bits per sample, capped bands, NMR)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.vbr_nmr is not None:
+        try:
+            check_vbr_args(a.vbr_nmr, a.bits_per_sample, a.target_nmr, a.dst, a.decode, a.certify, a.measure)
+            r = encode_wav_vbr_nmr(a.src, a.dst, a.vbr_nmr, not a.no_huffman, a.device, exact_spread=a.exact_spread)
+        except ValueError as e:
+            ap.error(str(e))
+        print(json.dumps(dict(file=a.dst, bytes=len(r["data"]), ceiling_db=float(a.vbr_nmr), ceiling_ratio=r["ceiling_ratio"],
+                              bits_per_sample=r["bits_per_sample"], coded_bits=r["coded_bits"], capped_bands=r["capped_bands"],
+                              nmr_total_db=r["nmr_total_db"], nmr_max_db=r["nmr_max_db"],
+                              disturbed_blocks=r["disturbed_blocks"], n_blocks=r["n_blocks"])))
+        return
     if a.target_nmr is not None:
         try:
             check_target_args(a.bits_per_sample, a.target_nmr, a.dst, a.decode, a.certify, a.measure)

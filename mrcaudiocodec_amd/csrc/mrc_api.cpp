@@ -127,6 +127,7 @@ void mrc_destroy(mrc_handle* h) {
     h->dec.release();
     h->nmr.release();
     h->target.release();
+    h->vbr.release();
     h->ws.release();
     for (DevBuf& b : h->stage) b.release();
     h->smallBatch.release();

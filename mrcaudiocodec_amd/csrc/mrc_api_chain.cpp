@@ -15,7 +15,8 @@
 // overwritten; chained_core runs one slab: schedule_groups, phase A + prep queued, schedule_items while the device works,
 // uploads, scan, pack, headers, chain_results.  The host-memory entry points are chained_host with one or several rates.
 // mrc_encode_chained_target_nmr_pac (end of the file) is a ladder whose slabs also measure their rungs (ChainCall::nmr) and
-// whose caller receives the chosen rung alone.
+// whose caller receives the chosen rung alone.  mrc_encode_vbr_nmr_pac (behind it) is a one-rate call whose slabs allocate
+// per band against a noise-to-mask ceiling (ChainCall::vbr, vbr_slab) in place of the event lists and the serial scan.
 //
 // Items, in file order per stream:  stereo  one joint block (two chunks) per block shape, Close()'s two one-channel blocks
 //                                           (one chunk each);
@@ -117,6 +118,7 @@ namespace {
 // [R][n_streams], stream_byte_offset [R][n_streams + 1], item_byte_offset [R][n_items + 1], reservoir_trace [R][n_items],
 // total_bytes [R]; byte offsets are relative to the start of their rate's output.  Where the bytes go is the layers' own.
 struct ChainNmr;
+struct ChainVbr;
 struct ChainCall {
     int n_rates; const double* rates;
     int64_t n_streams;
@@ -126,6 +128,7 @@ struct ChainCall {
     int64_t *stream_byte_offset, *item_byte_offset; int32_t *reservoir_out, *reservoir_trace; int64_t* total_bytes;
     void* stream;
     ChainNmr* nmr = nullptr;         // mrc_encode_chained_target_nmr_pac: every slab also measures its rungs (target_nmr_slab)
+    ChainVbr* vbr = nullptr;         // mrc_encode_vbr_nmr_pac: no budget, no scan -- every slab allocates per band (vbr_slab)
     int nch() const { return pcm_right ? 2 : 1; }
     size_t sample_bytes() const { return sample_format == MRC_SAMPLES_PCM16 ? sizeof(int16_t) : sizeof(double); }
     int64_t n_blocks() const { return block_start[n_streams] - block_start[0]; }
@@ -292,6 +295,9 @@ void chain_results(const ChainCall& c, const ChainSchedule& q, int64_t* rate_bas
 // mrc_encode_chained_target_nmr_pac (below): the NMR of the slab's rungs from the planes the scan just wrote, and its device time
 int target_nmr_slab(mrc_handle* h, const ChainCall& c, const ChainSchedule& q, const int64_t* count, hipStream_t st);
 int target_nmr_time(mrc_handle* h, const ChainCall& c);
+// mrc_encode_vbr_nmr_pac (below): the slab's allocation in place of the scan -- source analysis, vbr_alloc_kernel -- and its time
+int vbr_slab(mrc_handle* h, const ChainCall& c, const ChainSchedule& q, const int64_t* count, hipStream_t st);
+int vbr_time(mrc_handle* h, const ChainCall& c);
 
 // One SLAB of a chained encode: all of the call's streams, every buffer sized for exactly these blocks (chained_slabs cuts a
 // call into slabs and checked that every stream has a block).  The bytes of all rates go to out [out_cap], device memory.
@@ -329,23 +335,36 @@ int chained_core(mrc_handle* h, const ChainCall& c, uint8_t* out, int64_t out_ca
             if (g != 4) MRC_TRY(upload(h, B.offsets, q.offs[g], st));
             MRC_HIP(h, B.lines.reserve((size_t)m * nsig * S.halfN * sizeof(double)));
             MRC_HIP(h, B.oscale.reserve((size_t)m * nsig * sizeof(int32_t)));
-            MRC_HIP(h, B.smr.reserve((size_t)m * nsig * S.nBands * sizeof(double)));
-            MRC_HIP(h, B.peak.reserve((size_t)m * nsig * S.nBands * sizeof(double)));
             if (joint) MRC_HIP(h, B.ms.reserve((size_t)m * S.nBands * sizeof(int32_t)));
-            MRC_HIP(h, B.ev.reserve((size_t)m * nEv * sizeof(unsigned)));
-            MRC_HIP(h, B.pre.reserve((size_t)m * (nEv + 1) * sizeof(unsigned)));
+            if (!c.vbr) {                                    // (the VBR call needs no SMRs: it allocates against measured noise)
+                MRC_HIP(h, B.smr.reserve((size_t)m * nsig * S.nBands * sizeof(double)));
+                MRC_HIP(h, B.peak.reserve((size_t)m * nsig * S.nBands * sizeof(double)));
+                MRC_HIP(h, B.ev.reserve((size_t)m * nEv * sizeof(unsigned)));
+                MRC_HIP(h, B.pre.reserve((size_t)m * (nEv + 1) * sizeof(unsigned)));
+            }
             MRC_HIP(h, B.bitAlloc.reserve((size_t)R * m * nTot * sizeof(int32_t)));          // (phase B's planes: one per rate)
             MRC_HIP(h, B.scaleFactor.reserve((size_t)R * m * nTot * sizeof(int32_t)));
             MRC_HIP(h, B.mant.reserve((size_t)R * m * nstream * S.halfN * sizeof(uint16_t)));
             MRC_HIP(h, B.table.reserve((size_t)R * m * nstream * sizeof(int32_t)));
-            if (g == 4)
+            if (c.vbr) {                                     // phase A without its last step: lines, overall scales, M/S switch
+                if (g == 4)
+                    MRC_HIP(h, launch_mdct(S, m, C.flushPcm.p, nullptr, c.sample_format, 2 * (int64_t)L, nullptr, true,
+                                           B.lines.as<double>(), B.oscale.as<int32_t>(), st));
+                else
+                    MRC_HIP(h, launch_mdct(S, m, c.pcm_left, c.pcm_right, c.sample_format, 0, B.offsets.as<int64_t>(), true,
+                                           B.lines.as<double>(), B.oscale.as<int32_t>(), st));
+                if (joint)
+                    MRC_HIP(h, launch_ms_switch(m, S.nBands, S.msLeaves, S.msInternal, S.msPlan, B.lines.as<double>(),
+                                                B.lines.as<double>() + S.halfN, 4 * (int64_t)S.halfN, S.halfN, B.ms.as<int32_t>(), st));
+            } else if (g == 4)
                 MRC_TRY(encode_phase_a(h, S, m, C.flushPcm.p, nullptr, c.sample_format, 2 * (int64_t)L, nullptr, B.lines.as<double>(),
                                        B.oscale.as<int32_t>(), nullptr, B.smr.as<double>(), B.peak.as<double>(), st, false));
             else                                             // (pcm_right == nullptr: the mono kernels, no M/S switch)
                 MRC_TRY(encode_phase_a(h, S, m, c.pcm_left, c.pcm_right, c.sample_format, 0, B.offsets.as<int64_t>(),
                                        B.lines.as<double>(), B.oscale.as<int32_t>(), joint ? B.ms.as<int32_t>() : nullptr,
                                        B.smr.as<double>(), B.peak.as<double>(), st, false));
-            MRC_HIP(h, launch_chain_prep(S, joint, m, B.smr.as<double>(), joint ? B.ms.as<int32_t>() : nullptr,
+            if (!c.vbr)
+                MRC_HIP(h, launch_chain_prep(S, joint, m, B.smr.as<double>(), joint ? B.ms.as<int32_t>() : nullptr,
                                          B.ev.as<unsigned>(), B.pre.as<unsigned>(),
                                          h->chainForceFallback ? 1 : 0, st));
         }
@@ -373,9 +392,11 @@ int chained_core(mrc_handle* h, const ChainCall& c, uint8_t* out, int64_t out_ca
     MRC_TRY(upload(h, C.groupDesc, desc, st));
     MRC_HIP(h, hipEventRecord(C.evT[1], st));
     // ---- phase B: the serial scan per stream and rate
-    MRC_HIP(h, launch_chain_phase_b(nS, R, C.groupDesc.as<ChainGroupDev>(), C.items.as<int>(), C.itemStart.as<long long>(),
-                                    C.reservoir.as<int>(), c.reservoir_trace ? C.resTrace.as<int>() : nullptr, nItems,
-                                    c.use_huffman ? 1 : 0, h->chainThreads, st));
+    if (c.vbr) MRC_TRY(vbr_slab(h, c, q, count, st));    // (no reservoir: nothing is carried from block to block)
+    else
+        MRC_HIP(h, launch_chain_phase_b(nS, R, C.groupDesc.as<ChainGroupDev>(), C.items.as<int>(), C.itemStart.as<long long>(),
+                                        C.reservoir.as<int>(), c.reservoir_trace ? C.resTrace.as<int>() : nullptr, nItems,
+                                        c.use_huffman ? 1 : 0, h->chainThreads, st));
     MRC_HIP(h, hipEventRecord(C.evT[2], st));
     if (h->sensOn)                                       // MRC_OPT_SENSITIVITY: the scan's decisions, group by group
         for (int g = 0; g < q.nGroups; ++g) {
@@ -399,7 +420,9 @@ int chained_core(mrc_handle* h, const ChainCall& c, uint8_t* out, int64_t out_ca
         if (!count[g]) continue;
         for (int r = 0; r < R; ++r) {                           // (a mono item is a one-channel block)
             const ChainGroupDev& D = desc[(size_t)r * kChainGroups + g];
-            MRC_HIP(h, launch_pack_plan(q.hs[g]->dev, P[g], tables, count[g], D.bitAlloc, D.mant, MRC_MANTISSA_I16, D.table, D.table,
+            // (the scan chose the tables; the VBR call leaves calculateHuffmanGain's choice to the packer, as independent frames do)
+            MRC_HIP(h, launch_pack_plan(q.hs[g]->dev, P[g], tables, count[g], D.bitAlloc, D.mant, MRC_MANTISSA_I16,
+                                        c.vbr ? nullptr : D.table, D.table,
                                         nullptr, W, C.g[g].chunkMap.as<long long>() + r * (q.chunkMap[g].size() / R),
                                         all_bands_non_empty(*q.hs[g]), st));
         }
@@ -440,6 +463,7 @@ int chained_core(mrc_handle* h, const ChainCall& c, uint8_t* out, int64_t out_ca
         h->chainMs[i] = ms;
     }
     if (c.nmr) MRC_TRY(target_nmr_time(h, c));
+    if (c.vbr) MRC_TRY(vbr_time(h, c));
     chain_results(c, q, rate_base);
     if (q.bad & 3) return fail(h, MRC_ERR_INVALID, "mrc_encode_chained: internal error (table id / chunk size out of range)");
     if (q.total > out_cap || (q.bad & 4)) return fail(h, MRC_ERR_NOMEM, "mrc_encode_chained: out_cap too small (see total_bytes)");
@@ -649,7 +673,8 @@ int stage_pcm(mrc_handle* h, const ChainCall& c) {
 // The host-memory entry points (the one-rate one: a ladder of one rate with rates == nullptr): the PCM staged in the handle's
 // device buffers, every slab packed into the handle's output buffer (sized for the slab's worst case), rate r's bytes copied
 // behind the previous slab's in out[r], which only has to hold what the streams really pack to.
-int chained_host(mrc_handle* h, const char* who, ChainCall c, uint8_t* const* out, const int64_t* out_cap) {
+template <class After = NoAfter>
+int chained_host(mrc_handle* h, const char* who, ChainCall c, uint8_t* const* out, const int64_t* out_cap, After after = After{}) {
     MRC_TRY(check_call(h, who, c, out, out_cap));
     MRC_HIP(h, hipSetDevice(h->device));
     MRC_TRY(stage_pcm(h, c));
@@ -661,7 +686,7 @@ int chained_host(mrc_handle* h, const char* who, ChainCall c, uint8_t* const* ou
         if (n) MRC_HIP(h, hipMemcpyAsync(out[r] + at, buf, (size_t)n, hipMemcpyDeviceToHost, st));
         MRC_HIP(h, hipStreamSynchronize(st));            // (the next slab reuses the buffer)
         return (int)MRC_OK;
-    }, NoAfter{});
+    }, after);
     if (rc == MRC_ERR_NOMEM)
         return fail(h, MRC_ERR_NOMEM, std::string(who) + (c.rates ? ": an out_cap too small (see total_bytes)"
                                                                   : ": out_cap too small (see total_bytes; mrc_chain_fetch_output)"));
@@ -965,6 +990,10 @@ int target_decide(mrc_handle* h, const ChainCall& c, ChainNmr& N, const TargetOu
     return MRC_OK;
 }
 
+// the block layout a call that measures its own output needs (the NMR positions blocks by their offsets; whole files)
+int layout_check(mrc_handle* h, const std::string& w, int64_t n_streams, const int64_t* block_start, const int64_t* block_offset,
+                 const int32_t* block_a, const int32_t* block_b);
+
 // the refusals of include/mrc_hip.h, before any device work
 int target_check(mrc_handle* h, const std::string& w, int n_rates, const double* rates, double target, int64_t n_streams,
                  const void* pcm_left, int64_t stream_stride, const int64_t* block_start, const int64_t* block_offset,
@@ -987,6 +1016,11 @@ int target_check(mrc_handle* h, const std::string& w, int n_rates, const double*
         out_cap < 0 || !o.stream_byte_offset || !o.chosen || !o.met || !o.nmr_total_db || !o.nmr_max_db || !o.disturbed_blocks ||
         !o.n_blocks || !total_bytes)
         return fail(h, MRC_ERR_INVALID, w + ": bad argument (a NULL pointer, a negative count or capacity)");
+    return layout_check(h, w, n_streams, block_start, block_offset, block_a, block_b);
+}
+
+int layout_check(mrc_handle* h, const std::string& w, int64_t n_streams, const int64_t* block_start, const int64_t* block_offset,
+                 const int32_t* block_a, const int32_t* block_b) {
     const int L = h->cfg.n_mdct_lines;
     for (int64_t s = 0; s < n_streams; ++s) {
         const int64_t i0 = block_start[s], i1 = block_start[s + 1];
@@ -1101,6 +1135,255 @@ int mrc_dev_encode_chained_target_nmr_pac(mrc_handle* h, int n_rates, const doub
 int mrc_get_target_ms(mrc_handle* h, double* ms) {
     if (!h || !ms) return MRC_ERR_INVALID;
     for (int i = 0; i < 4; ++i) ms[i] = h->target.ms[i];
+    return MRC_OK;
+}
+
+}  // extern "C"
+
+// ---- constant-quality VBR (include/mrc_hip.h: mrc_encode_vbr_nmr_pac; the rule: DESIGN.md section 12) ---------------------
+// A one-rate chained call without a budget.  chained_core runs phase A up to the M/S switch (no SMRs, no event lists), and
+// where the serial scan would run, vbr_slab analyses the source exactly as target_nmr_slab does -- launch_mdct and launch_smr
+// in the mode that writes thresholds, mono, explicit offsets, MRC_OPT_EXACT_SPREAD honoured -- and vbr_alloc_kernel writes
+// the planes the packer reads, the entries' statistics and the capped bands.  The packer chooses the Huffman tables.  The
+// streams of a slab -- a stream cut into time slabs: once its last slab ran -- are reduced by nmr_file_kernel (vbr_decide).
+// The bytes travel as the one-rate chained call's do.
+namespace {
+
+struct ChainVbr {
+    std::vector<Slab> plan;          // the call's slabs (chained_slabs' own plan) ...
+    size_t slab = 0;                 // ... and the one that runs
+    const int64_t* blockStart = nullptr;   // the caller's
+    double ceiling = 0.0;            // c, the linear ratio
+    int64_t unitChunks = 0;          // chunks of the streams being decided
+    std::vector<int64_t> flushOffs;  // Close()'s blocks in flushPcm (a queued copy reads it)
+    double msAlloc = 0;
+};
+
+struct VbrOut { int64_t *capped_bands, *coded_bits; double *nmr_total_db, *nmr_max_db; int64_t *disturbed_blocks, *n_blocks; };
+
+int vbr_slab(mrc_handle* h, const ChainCall& c, const ChainSchedule& q, const int64_t* count, hipStream_t st) {
+    ChainVbr& N = *c.vbr;
+    ChainBufs& C = h->chain;
+    TargetBufs& T = h->target;
+    VbrBufs& V = h->vbr;
+    const Slab& sl = N.plan[N.slab];
+    const int nch = c.nch(), L = h->cfg.n_mdct_lines;
+    int64_t chunkBase = 0;
+    if (sl.first) {                                      // the first slab of the streams decided together: their rows
+        N.unitChunks = sl.timeSlab ? stream_chunks(c, N.blockStart, sl.s0) : c.n_chunks();
+        MRC_HIP(h, T.stat.reserve((size_t)N.unitChunks * 2 * sizeof(double)));
+        MRC_HIP(h, V.capped.reserve((size_t)N.unitChunks * sizeof(int)));
+    } else chunkBase = nch * (sl.i0 - N.blockStart[sl.s0]);
+    size_t rowBytes = 0, rows = 0, launches = 0;
+    for (int g = 0; g < q.nGroups; ++g) {
+        const int nOut = (g == 4 || nch == 1) ? 1 : 2;
+        const size_t n = (size_t)std::min<int64_t>(count[g], kTargetBatch) * nOut;
+        rows = std::max(rows, n);
+        rowBytes = std::max(rowBytes, n * q.hs[g]->dev.halfN * sizeof(double));
+        launches += (size_t)((count[g] + kTargetBatch - 1) / kTargetBatch);
+    }
+    MRC_HIP(h, T.lines.reserve(std::max<size_t>(rowBytes, 256)));
+    MRC_HIP(h, T.thresh.reserve(std::max<size_t>(rowBytes, 256)));
+    MRC_HIP(h, T.oscale.reserve(std::max<size_t>(rows * sizeof(int), 256)));
+    MRC_HIP(h, T.smr.reserve(std::max<size_t>(rows * kMaxBands * sizeof(double), 256)));
+    while (V.ev.size() < 2 * launches) {
+        hipEvent_t e = nullptr;
+        MRC_HIP(h, hipEventCreate(&e));
+        V.ev.push_back(e);
+    }
+    V.evUsed = 0;
+    if (c.with_flush) {
+        N.flushOffs.resize((size_t)count[4]);
+        for (int64_t k = 0; k < count[4]; ++k) N.flushOffs[(size_t)k] = k * 2 * (int64_t)L;
+        MRC_HIP(h, T.flushOffs.reserve(std::max<size_t>(N.flushOffs.size() * sizeof(int64_t), 256)));
+        if (count[4])
+            MRC_HIP(h, hipMemcpyAsync(T.flushOffs.p, N.flushOffs.data(), N.flushOffs.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    }
+    for (int g = 0; g < q.nGroups; ++g) {
+        if (!count[g]) continue;
+        const DevShape& S = q.hs[g]->dev;
+        const int joint = (g == 4 || nch == 1) ? 0 : 1, nOut = joint ? 2 : 1, M = S.halfN;
+        ChainGroupBufs& B = C.g[g];
+        for (int64_t k0 = 0; k0 < count[g]; k0 += kTargetBatch) {
+            const int64_t n = std::min<int64_t>(kTargetBatch, count[g] - k0);
+            const int64_t* offs = (g == 4 ? T.flushOffs.as<int64_t>() : B.offsets.as<int64_t>()) + k0;
+            for (int ch = 0; ch < nOut; ++ch) {
+                const void* src = g == 4 ? C.flushPcm.p : (ch ? c.pcm_right : c.pcm_left);
+                double* X = T.lines.as<double>() + ch * n * M;
+                int* os = T.oscale.as<int>() + ch * n;
+                MRC_HIP(h, launch_mdct(S, n, src, nullptr, kSampleI16, 0, offs, true, X, os, st));
+                MRC_HIP(h, launch_smr(S, n, src, nullptr, kSampleI16, 0, offs, X, os, T.smr.as<double>() + ch * n * kMaxBands,
+                                      T.thresh.as<double>() + ch * n * M, nullptr, nullptr, h->exactSpread, st));
+            }
+            MRC_HIP(h, hipEventRecord(V.ev[V.evUsed++], st));
+            MRC_HIP(h, launch_vbr_alloc(S, joint, n, k0, N.ceiling, B.lines.as<double>(), B.oscale.as<int>(),
+                                        joint ? B.ms.as<int>() : nullptr, B.bitAlloc.as<int>(), B.scaleFactor.as<int>(),
+                                        B.mant.as<unsigned short>(), B.chunkMap.as<long long>() + k0 * nOut, T.lines.as<double>(),
+                                        T.thresh.as<double>(), T.stat.as<double>(), V.capped.as<int>(), chunkBase, st));
+            MRC_HIP(h, hipEventRecord(V.ev[V.evUsed++], st));
+        }
+    }
+    return MRC_OK;
+}
+
+int vbr_time(mrc_handle* h, const ChainCall& c) {
+    VbrBufs& V = h->vbr;
+    for (size_t i = 0; i + 1 < V.evUsed; i += 2) {
+        float ms = 0.f;
+        MRC_HIP(h, hipEventElapsedTime(&ms, V.ev[i], V.ev[i + 1]));
+        c.vbr->msAlloc += ms;
+    }
+    return MRC_OK;
+}
+
+// The streams sl.s0 .. sl.s0 + sl.ns - 1 have all their entries in stat: the file reduction, the dB values as mrc_pac_nmr
+// forms them, the capped bands.
+int vbr_decide(mrc_handle* h, const ChainCall& c, ChainVbr& N, const VbrOut& o, const Slab& sl, hipStream_t st) {
+    TargetBufs& T = h->target;
+    const int nch = c.nch(), L = h->cfg.n_mdct_lines;
+    const int64_t ns = sl.ns;
+    std::vector<long long> tab((size_t)ns + 1 + (size_t)(ns + 1) / 2 + 1);
+    int* nchTab = (int*)(tab.data() + ns + 1);
+    int64_t first = 0;
+    for (int64_t s = 0; s < ns; ++s) {
+        tab[(size_t)s] = first;
+        nchTab[s] = nch;
+        first += stream_chunks(c, N.blockStart, sl.s0 + s);
+    }
+    tab[(size_t)ns] = first;
+    std::vector<double> fileOut((size_t)ns * 4);
+    std::vector<int> capped((size_t)first);
+    MRC_HIP(h, T.fileTab.reserve(tab.size() * sizeof(long long)));
+    MRC_HIP(h, T.fileOut.reserve(fileOut.size() * sizeof(double)));
+    DrainGuard guard{{st}};                              // (behind the vectors queued copies read and write)
+    MRC_HIP(h, hipMemcpyAsync(T.fileTab.p, tab.data(), tab.size() * sizeof(long long), hipMemcpyHostToDevice, st));
+    MRC_HIP(h, launch_nmr_file(ns, T.fileTab.as<long long>(), (const int*)(T.fileTab.as<long long>() + ns + 1),
+                               T.stat.as<double>(), T.fileOut.as<double>(), st));
+    MRC_HIP(h, hipMemcpyAsync(fileOut.data(), T.fileOut.p, fileOut.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    MRC_HIP(h, hipMemcpyAsync(capped.data(), h->vbr.capped.p, capped.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+    MRC_HIP(h, hipStreamSynchronize(st));
+    const double ninf = -std::numeric_limits<double>::infinity();
+    for (int64_t s = 0; s < ns; ++s) {
+        const int64_t gs = sl.s0 + s;
+        int64_t weight = (int64_t)L * nch;                                      // Close()'s block
+        for (int64_t i = N.blockStart[gs]; i < N.blockStart[gs + 1]; ++i) weight += (int64_t)c.block_b[i] * nch;
+        const double* f = fileOut.data() + 4 * s;
+        const double mean = weight > 0 ? f[1] / (double)weight : 0.0;
+        o.n_blocks[gs] = N.blockStart[gs + 1] - N.blockStart[gs] + 1;
+        o.nmr_total_db[gs] = mean > 0.0 ? 10.0 * std::log10(mean) : ninf;
+        o.nmr_max_db[gs] = f[0] > 0.0 ? 10.0 * std::log10(f[0]) : ninf;
+        o.disturbed_blocks[gs] = (int64_t)f[2];
+        int64_t cap = 0;
+        for (long long k = tab[(size_t)s]; k < tab[(size_t)s + 1]; ++k) cap += capped[(size_t)k];
+        o.capped_bands[gs] = cap;
+    }
+    return MRC_OK;
+}
+
+// the refusals of include/mrc_hip.h, before any device work
+int vbr_check(mrc_handle* h, const std::string& w, double ceiling_db, int64_t n_streams, const void* pcm_left, int64_t stream_stride,
+              const int64_t* block_start, const int64_t* block_offset, const int32_t* block_a, const int32_t* block_b,
+              const uint32_t* num_samples, const uint8_t* out, int64_t out_cap, const int64_t* stream_byte_offset,
+              const double* ceiling_ratio, const VbrOut& o, const int64_t* total_bytes) {
+    if (!h) return MRC_ERR_INVALID;
+    if (std::isnan(ceiling_db)) return fail(h, MRC_ERR_INVALID, w + ": ceiling_db is NaN");
+    if (!num_samples) return fail(h, MRC_ERR_INVALID, w + ": num_samples must not be NULL (whole files only)");
+    if (h->sensOn)
+        return fail(h, MRC_ERR_INVALID, w + ": MRC_OPT_SENSITIVITY is on (the certificate covers the budgeted allocation, not this one)");
+    if (n_streams < 0 || !pcm_left || stream_stride <= 0 || !block_start || !block_offset || !block_a || !block_b || !out ||
+        out_cap < 0 || !stream_byte_offset || !ceiling_ratio || !o.capped_bands || !o.coded_bits || !o.nmr_total_db ||
+        !o.nmr_max_db || !o.disturbed_blocks || !o.n_blocks || !total_bytes)
+        return fail(h, MRC_ERR_INVALID, w + ": bad argument (a NULL pointer, a negative count or capacity)");
+    return layout_check(h, w, n_streams, block_start, block_offset, block_a, block_b);
+}
+
+// behind the slabs: the sizes as payload bits, the times
+int vbr_finish(mrc_handle* h, const ChainCall& c, const ChainVbr& N, const VbrOut& o) {
+    const int nch = c.nch();
+    uint8_t one[256];
+    int64_t hdrLen = 0;
+    if (c.n_streams && (mrc_pac_header(&h->cfg, nch, c.num_samples[0], one, sizeof(one), &hdrLen) != MRC_OK))
+        return fail(h, MRC_ERR_INVALID, "mrc_encode_vbr_nmr_pac: mrc_pac_header failed");
+    for (int64_t s = 0; s < c.n_streams; ++s)            // a chunk: a 4-byte length and its payload
+        o.coded_bits[s] = 8 * (c.stream_byte_offset[s + 1] - c.stream_byte_offset[s] - hdrLen - 4 * stream_chunks(c, N.blockStart, s));
+    VbrBufs& V = h->vbr;
+    V.ms[0] = h->chainMs[0] + h->chainMs[1] - N.msAlloc;
+    V.ms[1] = N.msAlloc;
+    V.ms[2] = h->chainMs[2];
+    V.ms[3] = h->chainMs[3];
+    return MRC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mrc_encode_vbr_nmr_pac(mrc_handle* h, double ceiling_db, int64_t n_streams, const int16_t* pcm_left, const int16_t* pcm_right,
+                           int64_t stream_stride, const int64_t* block_start, const int64_t* block_offset,
+                           const int32_t* block_a, const int32_t* block_b, int use_huffman, const uint32_t* num_samples,
+                           uint8_t* out, int64_t out_cap, int64_t* stream_byte_offset, double* ceiling_ratio,
+                           int64_t* capped_bands, int64_t* coded_bits, double* nmr_total_db, double* nmr_max_db,
+                           int64_t* disturbed_blocks, int64_t* n_blocks, int64_t* total_bytes) {
+    const VbrOut o{capped_bands, coded_bits, nmr_total_db, nmr_max_db, disturbed_blocks, n_blocks};
+    MRC_TRY(vbr_check(h, __func__, ceiling_db, n_streams, pcm_left, stream_stride, block_start, block_offset, block_a, block_b,
+                      num_samples, out, out_cap, stream_byte_offset, ceiling_ratio, o, total_bytes));
+    ChainVbr N;
+    N.blockStart = block_start;
+    N.ceiling = *ceiling_ratio = std::pow(10.0, ceiling_db / 10.0);
+    N.plan = plan_slabs(n_streams, block_start, slab_cap(h, 1, pcm_right ? 2 : 1));
+    ChainCall c{1, nullptr, n_streams, pcm_left, pcm_right, MRC_SAMPLES_PCM16, stream_stride, block_start, block_offset,
+                block_a, block_b, nullptr, use_huffman, 1, num_samples, stream_byte_offset, nullptr, nullptr, nullptr,
+                total_bytes, nullptr};
+    c.vbr = &N;
+    hipStream_t st = h->stream;
+    const int rc = chained_host(h, __func__, c, &out, &out_cap, [&](const Slab& sl, const int64_t*, const int64_t*, const uint8_t*) {
+        if (sl.last) MRC_TRY(vbr_decide(h, c, N, o, sl, st));
+        ++N.slab;
+        return (int)MRC_OK;
+    });
+    if (rc != MRC_OK && rc != MRC_ERR_NOMEM) return rc;
+    const std::string err = h->error;
+    MRC_TRY(vbr_finish(h, c, N, o));
+    if (rc != MRC_OK) h->error = err;
+    return rc;
+}
+
+int mrc_dev_encode_vbr_nmr_pac(mrc_handle* h, double ceiling_db, int64_t n_streams, const int16_t* pcm_left,
+                               const int16_t* pcm_right, int64_t stream_stride, const int64_t* block_start,
+                               const int64_t* block_offset, const int32_t* block_a, const int32_t* block_b, int use_huffman,
+                               const uint32_t* num_samples, uint8_t* out, int64_t out_cap, int64_t* stream_byte_offset,
+                               double* ceiling_ratio, int64_t* capped_bands, int64_t* coded_bits, double* nmr_total_db,
+                               double* nmr_max_db, int64_t* disturbed_blocks, int64_t* n_blocks, int64_t* total_bytes,
+                               void* stream) {
+    const VbrOut o{capped_bands, coded_bits, nmr_total_db, nmr_max_db, disturbed_blocks, n_blocks};
+    MRC_TRY(vbr_check(h, __func__, ceiling_db, n_streams, pcm_left, stream_stride, block_start, block_offset, block_a, block_b,
+                      num_samples, out, out_cap, stream_byte_offset, ceiling_ratio, o, total_bytes));
+    ChainVbr N;
+    N.blockStart = block_start;
+    N.ceiling = *ceiling_ratio = std::pow(10.0, ceiling_db / 10.0);
+    N.plan = plan_slabs(n_streams, block_start, slab_cap(h, 1, pcm_right ? 2 : 1));
+    ChainCall c{1, nullptr, n_streams, pcm_left, pcm_right, MRC_SAMPLES_PCM16, stream_stride, block_start, block_offset,
+                block_a, block_b, nullptr, use_huffman, 1, num_samples, stream_byte_offset, nullptr, nullptr, nullptr,
+                total_bytes, stream};
+    c.vbr = &N;
+    MRC_TRY(check_call(h, __func__, c, &out, &out_cap));
+    hipStream_t st = pick_stream(h, stream);
+    const int rc = chained_slabs(h, c, &out_cap, out, [](int, uint8_t*, int64_t, int64_t) { return (int)MRC_OK; },
+                                 [&](const Slab& sl, const int64_t*, const int64_t*, const uint8_t*) {
+        if (sl.last) MRC_TRY(vbr_decide(h, c, N, o, sl, st));
+        ++N.slab;
+        return (int)MRC_OK;
+    });
+    if (rc != MRC_OK && rc != MRC_ERR_NOMEM) return rc;
+    const std::string err = h->error;
+    MRC_TRY(vbr_finish(h, c, N, o));
+    if (rc != MRC_OK) h->error = err;
+    return rc;
+}
+
+int mrc_get_vbr_ms(mrc_handle* h, double* ms) {
+    if (!h || !ms) return MRC_ERR_INVALID;
+    for (int i = 0; i < 4; ++i) ms[i] = h->vbr.ms[i];
     return MRC_OK;
 }
 

@@ -128,6 +128,19 @@ struct TargetBufs {
     }
 };
 
+// Constant-quality VBR (mrc_encode_vbr_nmr_pac, mrc_api_chain.cpp).  The source analysis and the file reduction use TargetBufs.
+struct VbrBufs {
+    DevBuf capped;                   // [chunks of the streams being decided]: capped bands, at a block's first chunk
+    std::vector<hipEvent_t> ev;      // start and end of every allocator launch of a slab
+    size_t evUsed = 0;
+    double ms[4] = {0, 0, 0, 0};     // phase A + source analysis | the allocator | pack | all three
+    void release() {
+        capped.release();
+        for (auto& e : ev) if (e) (void)hipEventDestroy(e);
+        ev.clear();
+    }
+};
+
 // Device decode of whole `.pac` files (mrc_api_decode.cpp): reused from call to call
 struct DecodeBufs {
     DevBuf consts;                   // UnpackTables + the band tables of the four block shapes (built once)
@@ -291,6 +304,7 @@ struct mrc_handle {
     mrc::DecodeBufs dec;             // mrc_dev_unpack_blocks / mrc_decode_pac_pcm16: see mrc_api_decode.cpp
     mrc::NmrBufs nmr;                // mrc_pac_nmr: see mrc_api_nmr.cpp
     mrc::TargetBufs target;          // mrc_encode_chained_target_nmr_pac: see mrc_api_chain.cpp
+    mrc::VbrBufs vbr;                // mrc_encode_vbr_nmr_pac: see mrc_api_chain.cpp
     double chainMs[4] = {0, 0, 0, 0};   // last chained encode: phase A, phase B, pack, whole call (host clock)
     bool timing = false;
     bool exactSpread = false;        // mrc_set_option(MRC_OPT_EXACT_SPREAD)

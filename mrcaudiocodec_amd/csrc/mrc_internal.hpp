@@ -254,6 +254,16 @@ hipError_t launch_nmr_rungs(const DevShape& S, int nRates, int joint, int64_t n,
 // span [nStreams][3] = {first byte in `in`, first byte in `out`, length}: byte copies, longest run maxLen
 hipError_t launch_target_gather(int64_t nStreams, int64_t maxLen, const long long* span, const unsigned char* in,
                                 unsigned char* out, hipStream_t st);
+// mrc_kernels_vbr.hip -- constant-quality VBR (mrc_encode_vbr_nmr_pac): per band the fewest bits with noise / mask <= ceiling
+// One workgroup per block k0 + kb of n blocks of a group: phaseLines [blocks][joint ? 4 : 1][halfN], oscale, msSwitch are
+// phase A's (indexed by the group's block), lines / thresh / chunkMap the source analysis and file order of THIS launch's
+// blocks as launch_nmr_rungs takes them.  Writes the group's planes bitAlloc / scaleFactor [blocks][streams][nBands] and mant
+// [blocks][streams][halfN], stat[2 * (chunkBase + chunk)] = {max_j r_j, b * mean_j r_j} and capped[chunkBase + chunk] (a
+// block's capped bands at its first chunk, 0 at its second).
+hipError_t launch_vbr_alloc(const DevShape& S, int joint, int64_t n, int64_t k0, double ceiling, const double* phaseLines,
+                            const int* oscale, const int* msSwitch, int* bitAlloc, int* scaleFactor, unsigned short* mant,
+                            const long long* chunkMap, const double* lines, const double* thresh, double* stat, int* capped,
+                            long long chunkBase, hipStream_t st);
 // mrc_kernels_huff.hip
 hipError_t launch_huffman_gain(const DevShape& S, int64_t nFrames, int nStreams, const int* bitAlloc,
                                const int* mantissa, const int* reservoirOut, int* huffTable, int* bitsSaved,

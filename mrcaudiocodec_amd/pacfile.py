@@ -286,6 +286,29 @@ def encode_stream_target_nmr(handle, stream, shapes, rates, target_db, use_huffm
                                                 num_samples=[num_samples])[0]
 
 
+def encode_stream_vbr_nmr(handle, stream, shapes, ceiling_db, use_huffman=True, num_samples=None):
+    """ONE stream of int16 PCM codes -- stereo [2][samples], or mono [samples] / [1][samples], with the zero prior hop -- and
+    its block-shape sequence, coded as constant-quality VBR in one library call (mrc_encode_vbr_nmr_pac): every band gets
+    the fewest bits that keep its measured noise-to-mask ratio <= 10^(ceiling_db / 10).  -> dict: data (the `.pac` bytes),
+    ceiling_ratio, capped_bands, coded_bits, nmr_total_db, nmr_max_db, disturbed_blocks, n_blocks (what measure_nmr gives for
+    the file)."""
+    L = handle.cfg.n_mdct_lines
+    stream = np.asarray(stream)
+    if stream.dtype != np.int16:
+        raise ValueError("the stream must hold int16 PCM codes (the NMR's source is int16)")
+    if stream.ndim == 1:
+        stream = stream[None]
+    if stream.ndim != 2 or stream.shape[0] not in (1, 2):
+        raise ValueError("stream must be stereo [2][samples] or mono [samples]")
+    if not len(shapes) or shapes[-1][2] != L:
+        raise ValueError("the stream must end with a long block (the reference's Close() assumes it)")
+    if num_samples is None:
+        num_samples = sum(int(b) for (_, _, b) in shapes)
+    right = stream[1][None] if stream.shape[0] == 2 else None
+    return handle.encode_vbr_nmr_pac(stream[0][None], right, [shapes], ceiling_db, use_huffman=use_huffman,
+                                     num_samples=[num_samples])[0]
+
+
 def encode_mono_stream_per_block(handle, stream, shapes, use_huffman=True, num_samples=None):
     """The block-at-a-time form of encode_mono_stream: one mrc_encode_mono per block, the reservoir carried on the host
     (reservoir_out + Huffman bits_saved), C++ packer, then Close()'s block.  The cross-check of the chained mono path
