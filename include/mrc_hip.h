@@ -548,6 +548,60 @@ int mrc_dev_encode_vbr_nmr_pac(mrc_handle* h, double ceiling_db, int64_t n_strea
                                void* stream);
 int mrc_get_vbr_ms(mrc_handle* h, double* ms /*[4]*/);
 
+/* ---- constant-quality VBR to a file size ("two-pass VBR") ---------------------------------------------------------------
+ * mrc_encode_vbr_size_pac is mrc_encode_vbr_nmr_pac with the ceiling SEARCHED per stream: the best constant quality on a grid
+ * of ceilings whose file fits target_bytes[s] (the complete file of stream s: header and the 4-byte length of every chunk
+ * included).  Same stream arguments, whole files only, 16-bit PCM, pcm_right == NULL means mono, same outputs.
+ *   The grid: db_i = ceiling_lo_db + (double)i * ceiling_step_db (one multiply, one add, in double), i = 0 .. n_ceilings - 1,
+ *   c_i = pow(10.0, db_i / 10.0) formed on the host as mrc_encode_vbr_nmr_pac forms its c.  Index 0 is the tightest ceiling.
+ *   The rule, per stream s, with bytes(i) the size of the file mrc_encode_vbr_nmr_pac writes for it at ceiling_db = db_i,
+ *   lo = 0, hi = n_ceilings - 1:  probe hi;  bytes(hi) > target_bytes[s]: chosen = hi, met = 0, stop;  otherwise met = 1 and
+ *   while lo < hi: mid = (lo + hi) / 2, probe mid, bytes(mid) <= target_bytes[s] ? hi = mid : lo = mid + 1;  chosen = hi.
+ *   File size is not guaranteed to be monotone in the ceiling, so the contract is this rule, not "the optimum": met == 1
+ *   implies the returned file is <= target_bytes[s].
+ * out[stream_byte_offset[s] .. stream_byte_offset[s + 1]) is byte for byte the file mrc_encode_vbr_nmr_pac writes for stream
+ * s at ceiling_db = chosen_db[s]; capped_bands, coded_bits, nmr_total_db, nmr_max_db, disturbed_blocks and n_blocks are that
+ * call's values for that file.  chosen[s]: the grid index, chosen_db[s] = db_chosen, ceiling_ratio[s] = c_chosen, met[s],
+ * probes[s]: the ceilings tried (<= MRC_MAX_PROBES).  probe_index / probe_bytes: NULL or [n_streams][MRC_MAX_PROBES], the
+ * grid index and file size of every probe in order, -1 in unused entries.  Streams of one call search independently; results
+ * do not depend on what shares the call nor on MRC_OPT_CHAIN_SLAB_BLOCKS.  MRC_OPT_EXACT_SPREAD is honoured.
+ * How: the sequence of states a band walks through in mrc_encode_vbr_nmr_pac's allocator is fixed by the signal -- c only
+ * decides where the walk stops -- so it is recorded once per block (about 12 KB per joint long block, which this call's slabs
+ * make room for) and every probe is a lookup, one quantise pass and the packer's pricing: the source analysis and phase A
+ * run once per call.  DESIGN.md section 13.
+ *   MRC_ERR_INVALID, with a message naming the argument and before any device work, for: all mrc_encode_vbr_nmr_pac refuses;
+ *   a non-finite ceiling_lo_db or ceiling_step_db; ceiling_step_db <= 0; n_ceilings outside 1..MRC_MAX_CEILINGS; target_bytes
+ *   NULL or an entry negative; a stream with more blocks than a slab of this call holds (it would run in time slabs, and the
+ *   search needs all blocks of a stream resident: raise MRC_OPT_CHAIN_SLAB_BLOCKS).
+ *   out_cap too small: MRC_ERR_NOMEM as in mrc_encode_vbr_nmr_pac (every result filled, mrc_chain_fetch_output for one slab).
+ * mrc_dev_encode_vbr_size_pac: pcm_left / pcm_right and out in DEVICE memory, all other pointers host; it synchronises
+ * `stream` before it returns.
+ * mrc_get_vbr_size_ms: device time of the last call, ms: phase A + source analysis, the profile kernel, all probes (pick +
+ * pricing + size reduction + copy back), the final pick + pack, the sum. */
+#define MRC_MAX_CEILINGS 256
+#define MRC_MAX_PROBES 9
+int mrc_encode_vbr_size_pac(mrc_handle* h, double ceiling_lo_db, double ceiling_step_db, int n_ceilings,
+                            const int64_t* target_bytes /*[n_streams]*/, int64_t n_streams, const int16_t* pcm_left,
+                            const int16_t* pcm_right, int64_t stream_stride, const int64_t* block_start,
+                            const int64_t* block_offset, const int32_t* block_a, const int32_t* block_b, int use_huffman,
+                            const uint32_t* num_samples, uint8_t* out, int64_t out_cap,
+                            int64_t* stream_byte_offset /*[n_streams + 1]*/, int32_t* chosen /*[n_streams]*/,
+                            double* chosen_db /*[n_streams]*/, double* ceiling_ratio /*[n_streams]*/, int32_t* met /*[n_streams]*/,
+                            int32_t* probes /*[n_streams]*/, int32_t* probe_index /* NULL or [n_streams][MRC_MAX_PROBES] */,
+                            int64_t* probe_bytes /* NULL or [n_streams][MRC_MAX_PROBES] */, int64_t* capped_bands,
+                            int64_t* coded_bits, double* nmr_total_db, double* nmr_max_db, int64_t* disturbed_blocks,
+                            int64_t* n_blocks, int64_t* total_bytes);
+int mrc_dev_encode_vbr_size_pac(mrc_handle* h, double ceiling_lo_db, double ceiling_step_db, int n_ceilings,
+                                const int64_t* target_bytes, int64_t n_streams, const int16_t* pcm_left,
+                                const int16_t* pcm_right, int64_t stream_stride, const int64_t* block_start,
+                                const int64_t* block_offset, const int32_t* block_a, const int32_t* block_b, int use_huffman,
+                                const uint32_t* num_samples, uint8_t* out, int64_t out_cap, int64_t* stream_byte_offset,
+                                int32_t* chosen, double* chosen_db, double* ceiling_ratio, int32_t* met, int32_t* probes,
+                                int32_t* probe_index, int64_t* probe_bytes, int64_t* capped_bands, int64_t* coded_bits,
+                                double* nmr_total_db, double* nmr_max_db, int64_t* disturbed_blocks, int64_t* n_blocks,
+                                int64_t* total_bytes, void* stream);
+int mrc_get_vbr_size_ms(mrc_handle* h, double* ms /*[5]*/);
+
 /* ---- sensitivity certificate (round 4) ----
  * Bit-identity of the integers with the reference is an empirical, counted result: each of them is a floor / compare of
  * float64 values whose last bits differ between implementations (FFT factorisation, log10 / atan / 2^x), and it can only come

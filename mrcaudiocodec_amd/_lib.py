@@ -14,6 +14,8 @@ LIB_PATH = os.environ.get("MRC_HIP_LIBRARY") or os.path.join(_HERE, "libmrc_hip.
 
 MRC_MAX_BANDS = 32
 MRC_MAX_RATES = 16
+MRC_MAX_CEILINGS = 256
+MRC_MAX_PROBES = 9
 MRC_ERR_INVALID = -1
 MRC_ERR_NOMEM = -4
 # array arguments travel as plain addresses (c_void_p prototypes): numpy's typed `data_as` costs ~2.3 us per array, which
@@ -145,6 +147,15 @@ def _load():
                                                  _i32p, _i32p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, _i64p, _f64p, _i64p,
                                                  _i64p, _f64p, _f64p, _i64p, _i64p, _i64p, C.c_void_p]),
         "mrc_get_vbr_ms": (C.c_int, [H, _f64p]),
+        "mrc_encode_vbr_size_pac": (C.c_int, [H, C.c_double, C.c_double, C.c_int, _i64p, C.c_int64, C.c_void_p, C.c_void_p,
+                                              C.c_int64, _i64p, _i64p, _i32p, _i32p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
+                                              _i64p, _i32p, _f64p, _f64p, _i32p, _i32p, _i32p, _i64p, _i64p, _i64p, _f64p, _f64p,
+                                              _i64p, _i64p, _i64p]),
+        "mrc_dev_encode_vbr_size_pac": (C.c_int, [H, C.c_double, C.c_double, C.c_int, _i64p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                  C.c_int64, _i64p, _i64p, _i32p, _i32p, C.c_int, C.c_void_p, C.c_void_p,
+                                                  C.c_int64, _i64p, _i32p, _f64p, _f64p, _i32p, _i32p, _i32p, _i64p, _i64p, _i64p,
+                                                  _f64p, _f64p, _i64p, _i64p, _i64p, C.c_void_p]),
+        "mrc_get_vbr_size_ms": (C.c_int, [H, _f64p]),
         "mrc_pac_read_header": (C.c_int, [_u8p, C.c_int64, C.POINTER(MrcConfig), _i32p, C.POINTER(C.c_uint32), _i64p]),
         "mrc_pac_scan_chunks": (C.c_int64, [_u8p, C.c_int64, C.c_int64, _i64p, C.c_int64]),
         "mrc_unpack_blocks": (C.c_int, [C.POINTER(MrcConfig), C.c_int64, C.c_int, C.c_int, _u8p, C.c_int64, _i64p] +
@@ -749,6 +760,70 @@ class Handle:
         """device time of the last encode_vbr_nmr_pac: phase A + source analysis, the allocator, pack, their sum (ms)"""
         ms = np.zeros(4, np.float64)
         self._check(lib.mrc_get_vbr_ms(self._h, _p(ms, _f64p)))
+        return ms
+
+    def encode_vbr_size_pac(self, pcm_left, pcm_right, shapes, target_bytes, lo_db=-30.0, step_db=0.25, n=256, use_huffman=True,
+                            num_samples=None, device=None, stream=None, out_cap=None):
+        """mrc_encode_vbr_size_pac: constant-quality VBR to a file size.  The streams of encode_vbr_nmr_pac, each coded at the
+        tightest ceiling of the grid lo_db + i * step_db (i < n) that the bisection of pacfile.bisect_ceiling finds to fit
+        target_bytes [nStreams] (the complete file).  device / out_cap as in encode_vbr_nmr_pac.
+        -> one dict per stream: encode_vbr_nmr_pac's at the chosen ceiling plus chosen, chosen_db, met, probes, probe_index
+        and probe_bytes (the grid index and file size of every probe in order)."""
+        if num_samples is None:
+            raise ValueError("encode_vbr_size_pac: num_samples is required (whole files only)")
+        if device is None and np.atleast_2d(pcm_left).dtype != np.int16:
+            raise ValueError("encode_vbr_size_pac: int16 PCM codes only (the NMR's source is int16)")
+        dev5 = None if device is None else (device[0], device[1], 1, device[2])
+        q = self._chain_args(pcm_left, pcm_right, shapes, use_huffman, True, num_samples, dev5)
+        ns = q.n_streams
+        m = max(ns, 1)
+        target = np.ascontiguousarray(target_bytes, dtype=np.int64).reshape(-1)
+        if target.shape != (ns,):
+            raise ValueError("target_bytes: one value per stream")
+        pcm = (q.pcm[0], q.pcm[1], q.pcm[3])
+        s_off = np.zeros(ns + 1, np.int64)
+        chosen, met, probes = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.int32)
+        chosen_db, ratio = np.zeros(m, np.float64), np.zeros(m, np.float64)
+        p_idx, p_bytes = np.full((m, MRC_MAX_PROBES), -1, np.int32), np.full((m, MRC_MAX_PROBES), -1, np.int64)
+        capped, bits = np.zeros(m, np.int64), np.zeros(m, np.int64)
+        tot, mx = np.zeros(m, np.float64), np.zeros(m, np.float64)
+        dist, nblk = np.zeros(m, np.int64), np.zeros(m, np.int64)
+        total = np.zeros(1, np.int64)
+        args = (self._h, float(lo_db), float(step_db), int(n), _p(target, _i64p), ns) + pcm + q.head + (q.opts[0], q.opts[2])
+        tail = (_p(s_off, _i64p), _p(chosen, _i32p), _p(chosen_db, _f64p), _p(ratio, _f64p), _p(met, _i32p), _p(probes, _i32p),
+                _p(p_idx, _i32p), _p(p_bytes, _i64p), _p(capped, _i64p), _p(bits, _i64p), _p(tot, _f64p), _p(mx, _f64p),
+                _p(dist, _i64p), _p(nblk, _i64p), _p(total, _i64p))
+        buf = None
+        if device is not None:
+            self._check(lib.mrc_dev_encode_vbr_size_pac(*args, device[3], int(device[4]), *tail, stream))
+        else:
+            bound = q.bound()
+            if out_cap is None:
+                out_cap = bound
+            buf = np.empty(max(int(out_cap), 1), np.uint8)
+            rc = lib.mrc_encode_vbr_size_pac(*args, vp(buf), int(out_cap), *tail)
+            if rc == MRC_ERR_NOMEM and 0 < int(total[0]) <= bound:
+                buf = np.empty(int(total[0]), np.uint8)
+                if lib.mrc_chain_fetch_output(self._h, vp(buf), buf.size, _p(total, _i64p)) != 0:
+                    # several slabs: nothing is kept on the device -- once more, into a buffer of the reported size
+                    self._check(lib.mrc_encode_vbr_size_pac(*args, vp(buf), buf.size, *tail))
+            else:
+                self._check(rc)
+        out = []
+        for s in range(ns):
+            lo, hi, k = int(s_off[s]), int(s_off[s + 1]), int(probes[s])
+            out.append(dict(data=(lo, hi) if buf is None else buf[lo:hi].tobytes(), chosen=int(chosen[s]),
+                            chosen_db=float(chosen_db[s]), ceiling_ratio=float(ratio[s]), met=bool(met[s]), probes=k,
+                            probe_index=[int(v) for v in p_idx[s, :k]], probe_bytes=[int(v) for v in p_bytes[s, :k]],
+                            capped_bands=int(capped[s]), coded_bits=int(bits[s]), nmr_total_db=float(tot[s]),
+                            nmr_max_db=float(mx[s]), disturbed_blocks=int(dist[s]), n_blocks=int(nblk[s])))
+        return out
+
+    def vbr_size_ms(self):
+        """device time of the last encode_vbr_size_pac: phase A + source analysis, the profile kernel, all probes, the final
+        pick + pack, their sum (ms)"""
+        ms = np.zeros(5, np.float64)
+        self._check(lib.mrc_get_vbr_size_ms(self._h, _p(ms, _f64p)))
         return ms
 
     def chain_out_bound(self, block_start, block_a, block_b, with_flush=True, with_headers=True, n_channels=2):

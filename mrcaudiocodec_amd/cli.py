@@ -39,12 +39,13 @@ which the encoder analyses but never codes: the two agree when that hop is silen
 import argparse
 import json
 import os
+import sys
 from struct import pack, unpack
 
 import numpy as np
 
 from . import Handle, MrcError, pacfile, transient
-from ._lib import MRC_MAX_RATES
+from ._lib import MRC_MAX_CEILINGS, MRC_MAX_RATES
 
 
 def read_wav_pcm(path, hop=1024):
@@ -324,6 +325,101 @@ def encode_wav_vbr_nmr(in_path, out_path, vbr_nmr, use_huffman=True, device_id=0
     return r
 
 
+def vbr_size_target_bytes(bits_per_sample, header_bytes, coded_samples, channels, chunks):
+    """--vbr-bits-per-sample X as a file size: header + floor(X * coded_samples * channels / 8) + 4 * chunks."""
+    return int(header_bytes) + int(np.floor(float(bits_per_sample) * coded_samples * channels / 8.0)) + 4 * int(chunks)
+
+
+def check_vbr_size_args(vbr_bytes=None, vbr_bits_per_sample=None, vbr_grid=None, bits_per_sample=None, target_nmr=None,
+                        vbr_nmr=None, out_path=None, decode=False, certify=False, measure=False):
+    """The refusals of --vbr-bytes / --vbr-bits-per-sample, before a file is read or a device is touched.
+    -> (bytes or None, bits per sample or None, (lo_db, step_db, n))."""
+    which = "--vbr-bytes" if vbr_bytes is not None else "--vbr-bits-per-sample"
+    if vbr_bytes is None and vbr_bits_per_sample is None:
+        raise ValueError("--vbr-grid goes with --vbr-bytes or --vbr-bits-per-sample")
+    if vbr_bytes is not None and vbr_bits_per_sample is not None:
+        raise ValueError("--vbr-bytes and --vbr-bits-per-sample are two ways to give ONE size: take one")
+    if decode or certify or measure:
+        raise ValueError("%s encodes one file: it does not go with -d, --certify or --measure" % which)
+    if bits_per_sample is not None or target_nmr is not None or vbr_nmr is not None:
+        raise ValueError("%s searches the ceiling itself: it does not go with --bits-per-sample, --target-nmr or --vbr-nmr" % which)
+    if out_path is not None and "{bps}" in out_path:
+        raise ValueError("%s writes ONE file: dst must not contain {bps}" % which)
+    nbytes = bps = None
+    if vbr_bytes is not None:
+        try:
+            nbytes = int(vbr_bytes)
+        except (TypeError, ValueError):
+            raise ValueError("--vbr-bytes: %r is not a whole number" % (vbr_bytes,))
+        if nbytes < 0:
+            raise ValueError("--vbr-bytes: the size must not be negative")
+    else:
+        try:
+            bps = float(vbr_bits_per_sample)
+        except (TypeError, ValueError):
+            raise ValueError("--vbr-bits-per-sample: %r is not a number" % (vbr_bits_per_sample,))
+        if not np.isfinite(bps) or bps < 0:
+            raise ValueError("--vbr-bits-per-sample: the rate must be finite and not negative")
+    grid = (-30.0, 0.25, 256)
+    if vbr_grid is not None:
+        parts = str(vbr_grid).split(":")
+        try:
+            if len(parts) != 3:
+                raise ValueError
+            grid = (float(parts[0]), float(parts[1]), int(parts[2]))
+        except ValueError:
+            raise ValueError("--vbr-grid: %r is not LO:STEP:N (two numbers and a count)" % (vbr_grid,))
+        if not np.isfinite(grid[0]) or not np.isfinite(grid[1]) or not grid[1] > 0:
+            raise ValueError("--vbr-grid: LO and STEP must be finite, STEP > 0")
+        if not 1 <= grid[2] <= MRC_MAX_CEILINGS:
+            raise ValueError("--vbr-grid: N must lie in 1..%d" % MRC_MAX_CEILINGS)
+    return nbytes, bps, grid
+
+
+def encode_wav_vbr_size(in_path, out_path, vbr_bytes=None, vbr_bits_per_sample=None, vbr_grid=None, use_huffman=True, device_id=0,
+                        handle=None, exact_spread=False):
+    """encode_wav as constant-quality VBR to a size (mrc_encode_vbr_size_pac): the tightest ceiling of the grid whose file
+    is <= vbr_bytes, or <= vbr_size_target_bytes(vbr_bits_per_sample, ..).  Writes the file to out_path (if given) and
+    returns the report of pacfile.encode_stream_vbr_size plus target_bytes and bits_per_sample."""
+    nbytes, bps, grid = check_vbr_size_args(vbr_bytes, vbr_bits_per_sample, vbr_grid, out_path=out_path)
+    rate, n_ch, num_samples, pcm = read_wav_pcm(in_path)
+    if n_ch not in (1, 2):
+        raise ValueError("%d-channel input: mono and stereo WAV files only" % n_ch)
+    shape = {} if handle is None else dict(n_mdct_lines=handle.cfg.n_mdct_lines, n_short=handle.cfg.n_short)
+    try:
+        hdr = pacfile.header(pacfile.make_config(sample_rate=rate, **shape), n_ch, num_samples)
+    except MrcError as e:
+        raise ValueError("%d Hz input: outside the sample rates the reference can encode (%s)" % (rate, e))
+    h = handle if handle is not None else Handle(sample_rate=rate, device_id=device_id)
+    was_exact = h.get_option(1)
+    if exact_spread:
+        h.set_option(1, 1)
+    try:
+        L = h.cfg.n_mdct_lines
+        codes = np.concatenate([np.zeros((n_ch, L), np.int16), pcm], axis=1)
+        shapes = transient.block_shape_array(h, codes)
+        if not len(shapes):
+            raise ValueError("file too short: fewer than two hops")
+        if shapes[-1, 2] != L:
+            raise ValueError("the stream must end with a long block (the reference's Close() assumes it)")
+        coded = sum(int(b) for (_, _, b) in shapes)
+        if nbytes is None:
+            nbytes = vbr_size_target_bytes(bps, len(hdr), coded, n_ch, n_ch * (len(shapes) + 1))
+        r = pacfile.encode_stream_vbr_size(h, codes[0] if n_ch == 1 else codes, shapes, nbytes, grid[0], grid[1], grid[2],
+                                           use_huffman=use_huffman, num_samples=num_samples)
+    finally:
+        if handle is not None:
+            h.set_option(1, was_exact)
+        else:
+            h.close()
+    r["target_bytes"] = nbytes
+    r["bits_per_sample"] = r["coded_bits"] / float(n_ch * coded)
+    if out_path:
+        with open(out_path, "wb") as f:
+            f.write(r["data"])
+    return r
+
+
 def wav_header(n_ch, n_data_bytes, sample_rate):
     """pcmfile.py:141-153"""
     return pack('<4sL4s4sLHHLLHH4sL', b"RIFF", 36 + n_data_bytes, b"WAVE", b"fmt ", 16, 1, n_ch, sample_rate,
@@ -395,6 +491,22 @@ def _print_nmr(ap, a, paths, bps):
         print(json.dumps(r))
 
 
+def _join_vbr_grid(argv):
+    """argv with "--vbr-grid VALUE" written "--vbr-grid=VALUE": a grid usually starts at a negative LO, and argparse takes
+    "-30:0.25:256" (a leading minus, yet no number) for an option and never hands it to --vbr-grid as its value."""
+    argv, out, i = list(argv), [], 0
+    while i < len(argv):
+        if argv[i] == "--":
+            return out + argv[i:]
+        if argv[i] == "--vbr-grid" and i + 1 < len(argv) and ":" in argv[i + 1]:
+            out.append("--vbr-grid=" + argv[i + 1])
+            i += 2
+        else:
+            out.append(argv[i])
+            i += 1
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Encode a mono or stereo 16-bit WAV to .pac (or, with -d, decode a .pac to WAV) "
                                              "on an MI355X")
@@ -422,8 +534,31 @@ def main(argv=None):
     ap.add_argument("--vbr-nmr", default=None, metavar="DB",
                     help="constant-quality VBR: no bit rate; every band gets the fewest bits that keep its noise-to-mask ratio "
                          "<= DB.  Writes ONE file to dst and prints one JSON line (bits per sample, capped bands, NMR)")
+    ap.add_argument("--vbr-bytes", default=None, metavar="N",
+                    help="constant-quality VBR to a size: the tightest noise-to-mask ceiling of the grid whose whole file is "
+                         "<= N bytes, searched in one call.  Writes ONE file to dst and prints one JSON line (--vbr-nmr's "
+                         "plus chosen_db, met, probes)")
+    ap.add_argument("--vbr-bits-per-sample", default=None, metavar="X",
+                    help="--vbr-bytes with N = header + floor(X * coded_samples * channels / 8) + 4 * chunks")
+    ap.add_argument("--vbr-grid", default=None, metavar="LO:STEP:N",
+                    help="the ceilings --vbr-bytes / --vbr-bits-per-sample search: LO + i * STEP dB, i < N <= 256 "
+                         "(default -30:0.25:256)")
     ap.add_argument("--device", type=int, default=0)
-    a = ap.parse_args(argv)
+    a = ap.parse_args(_join_vbr_grid(sys.argv[1:] if argv is None else argv))
+    if a.vbr_bytes is not None or a.vbr_bits_per_sample is not None or a.vbr_grid is not None:
+        try:
+            check_vbr_size_args(a.vbr_bytes, a.vbr_bits_per_sample, a.vbr_grid, a.bits_per_sample, a.target_nmr, a.vbr_nmr, a.dst,
+                                a.decode, a.certify, a.measure)
+            r = encode_wav_vbr_size(a.src, a.dst, a.vbr_bytes, a.vbr_bits_per_sample, a.vbr_grid, not a.no_huffman, a.device,
+                                    exact_spread=a.exact_spread)
+        except ValueError as e:
+            ap.error(str(e))
+        print(json.dumps(dict(file=a.dst, bytes=len(r["data"]), target_bytes=r["target_bytes"], chosen_db=r["chosen_db"],
+                              met=r["met"], probes=r["probes"], ceiling_ratio=r["ceiling_ratio"],
+                              bits_per_sample=r["bits_per_sample"], coded_bits=r["coded_bits"], capped_bands=r["capped_bands"],
+                              nmr_total_db=r["nmr_total_db"], nmr_max_db=r["nmr_max_db"],
+                              disturbed_blocks=r["disturbed_blocks"], n_blocks=r["n_blocks"])))
+        return
     if a.vbr_nmr is not None:
         try:
             check_vbr_args(a.vbr_nmr, a.bits_per_sample, a.target_nmr, a.dst, a.decode, a.certify, a.measure)

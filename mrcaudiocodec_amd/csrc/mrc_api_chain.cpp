@@ -16,7 +16,9 @@
 // uploads, scan, pack, headers, chain_results.  The host-memory entry points are chained_host with one or several rates.
 // mrc_encode_chained_target_nmr_pac (end of the file) is a ladder whose slabs also measure their rungs (ChainCall::nmr) and
 // whose caller receives the chosen rung alone.  mrc_encode_vbr_nmr_pac (behind it) is a one-rate call whose slabs allocate
-// per band against a noise-to-mask ceiling (ChainCall::vbr, vbr_slab) in place of the event lists and the serial scan.
+// per band against a noise-to-mask ceiling (ChainCall::vbr, vbr_slab) in place of the event lists and the serial scan;
+// mrc_encode_vbr_size_pac is that call with the ceiling searched per stream (ChainVbr::size: the slab records every band's walk
+// once and bisects a grid of ceilings over the record, vbr_size_search).
 //
 // Items, in file order per stream:  stereo  one joint block (two chunks) per block shape, Close()'s two one-channel blocks
 //                                           (one chunk each);
@@ -129,6 +131,7 @@ struct ChainCall {
     void* stream;
     ChainNmr* nmr = nullptr;         // mrc_encode_chained_target_nmr_pac: every slab also measures its rungs (target_nmr_slab)
     ChainVbr* vbr = nullptr;         // mrc_encode_vbr_nmr_pac: no budget, no scan -- every slab allocates per band (vbr_slab)
+    int64_t slabBlocks = 0;          // the slab capacity of this call where it is not slab_cap's (mrc_encode_vbr_size_pac)
     int nch() const { return pcm_right ? 2 : 1; }
     size_t sample_bytes() const { return sample_format == MRC_SAMPLES_PCM16 ? sizeof(int16_t) : sizeof(double); }
     int64_t n_blocks() const { return block_start[n_streams] - block_start[0]; }
@@ -519,6 +522,22 @@ int64_t ladder_slab_blocks(mrc_handle* h, int64_t cap, int n_rates, int nch) {
     return std::max<int64_t>(1, cap * (shared + perRate) / (shared + n_rates * perRate));
 }
 
+// mrc_encode_vbr_size_pac keeps vbr_profile_kernel's record of every block of a slab beside phase A's data: its slab takes
+// as many blocks fewer as hold the device memory of a one-rate slab of `cap` blocks (per block of the long shape).
+int64_t vbr_size_slab_blocks(mrc_handle* h, int nch) {
+    const int64_t cap = h->chainSlabBlocks;
+    if (cap <= 0) return (int64_t)1 << 40;
+    const int L = h->cfg.n_mdct_lines;
+    const HostShape* hs = nullptr;
+    if (get_shape(h, L, L, &hs) != MRC_OK) return cap;                  // (the call itself says why)
+    const DevShape& S = hs->dev;
+    const int joint = nch == 2 ? 1 : 0, nsig = joint ? 4 : 1, nTot = nch * S.nBands;
+    const int64_t block = (int64_t)nsig * S.halfN * 8 + nsig * 4 + S.nBands * 4 + 2 * (int64_t)nTot * 4 + (int64_t)nch * S.halfN * 2 +
+                          nch * 4 + nch * 16 + mrc_pack_bound(&h->cfg, L, L, nch, joint);
+    const int64_t record = (int64_t)vbr_profile_bytes(S, joint) + (joint ? S.nBands * 4 : 0);
+    return std::max<int64_t>(1, cap * block / (block + record));
+}
+
 int64_t slab_cap(mrc_handle* h, int n_rates, int nch) {
     return h->chainSlabBlocks > 0 ? ladder_slab_blocks(h, h->chainSlabBlocks, n_rates, nch) : (int64_t)1 << 40;
 }
@@ -539,7 +558,7 @@ int chained_slabs(mrc_handle* h, const ChainCall& c, const int64_t* out_cap, uin
     for (int64_t s = 0; s < nS; ++s)                     // (the slab plan and every size below count on it)
         if (c.block_start[s + 1] <= c.block_start[s]) return fail(h, MRC_ERR_INVALID, "mrc_encode_chained: every stream needs at least one block");
     const int64_t nItemsAll = c.n_items();
-    const std::vector<Slab> slabs = plan_slabs(nS, c.block_start, slab_cap(h, R, nch));
+    const std::vector<Slab> slabs = plan_slabs(nS, c.block_start, c.slabBlocks > 0 ? c.slabBlocks : slab_cap(h, R, nch));
     ChainBufs& C = h->chain;
     int64_t itemBase = 0;
     std::vector<int64_t> written((size_t)R, 0), slabTotal((size_t)R), base((size_t)R);
@@ -1147,7 +1166,16 @@ int mrc_get_target_ms(mrc_handle* h, double* ms) {
 // the planes the packer reads, the entries' statistics and the capped bands.  The packer chooses the Huffman tables.  The
 // streams of a slab -- a stream cut into time slabs: once its last slab ran -- are reduced by nmr_file_kernel (vbr_decide).
 // The bytes travel as the one-rate chained call's do.
+// mrc_encode_vbr_size_pac: the same slab with vbr_profile_kernel in vbr_alloc_kernel's place and
+// vbr_size_search behind it; everything after it -- pack, headers, vbr_decide -- is the VBR call's.
 namespace {
+
+// mrc_encode_vbr_size_pac: the grid, the size limits and the per-stream results of the search, all the caller's
+struct VbrSize {
+    double lo, step; int n; const int64_t* target;
+    int32_t* chosen; double *chosen_db, *ceiling_ratio; int32_t *met, *probes, *probe_index; int64_t* probe_bytes;
+    double db(int i) const { return lo + (double)i * step; }
+};
 
 struct ChainVbr {
     std::vector<Slab> plan;          // the call's slabs (chained_slabs' own plan) ...
@@ -1157,9 +1185,96 @@ struct ChainVbr {
     int64_t unitChunks = 0;          // chunks of the streams being decided
     std::vector<int64_t> flushOffs;  // Close()'s blocks in flushPcm (a queued copy reads it)
     double msAlloc = 0;
+    const VbrSize* size = nullptr;   // mrc_encode_vbr_size_pac: the slab records the walk and searches the grid (vbr_size_search)
+    double msProbe = 0, msPick = 0;
 };
 
 struct VbrOut { int64_t *capped_bands, *coded_bits; double *nmr_total_db, *nmr_max_db; int64_t *disturbed_blocks, *n_blocks; };
+
+// The search of one slab's streams (include/mrc_hip.h states the rule): the record of every block is in VbrBufs::prof.  A
+// probe: vbr_pick_kernel at each stream's ceiling, the packer's plan (pricing only), the streams' file sizes, one copy back;
+// the host moves every unfinished stream's interval.  At most MRC_MAX_PROBES rounds whatever the number of streams.  It
+// leaves the planes, T.stat and V.capped at the chosen ceilings, as vbr_alloc_kernel would.
+int vbr_size_search(mrc_handle* h, const ChainCall& c, const ChainSchedule& q, const int64_t* count, hipStream_t st) {
+    ChainVbr& N = *c.vbr;
+    const VbrSize& Z = *N.size;
+    ChainBufs& C = h->chain;
+    TargetBufs& T = h->target;
+    VbrBufs& V = h->vbr;
+    const int nch = c.nch();
+    const int64_t nS = c.n_streams, nChunks = c.n_chunks(), s0 = N.plan[N.slab].s0;
+    MRC_HIP(h, V.ceilings.reserve((size_t)nS * sizeof(double)));
+    MRC_HIP(h, V.bytes.reserve((size_t)nS * sizeof(long long)));
+    MRC_HIP(h, C.packWs.reserve(pack_workspace_bytes(nChunks)));
+    const PackWs W = pack_ws_views(C.packWs.p, nChunks);
+    const PackTables& tables = host_pack_tables();
+    std::vector<int> lo((size_t)nS, 0), hi((size_t)nS, Z.n - 1), at((size_t)nS, -1);
+    std::vector<char> active((size_t)nS, 1);
+    std::vector<double> ceil((size_t)nS);
+    std::vector<long long> bytes((size_t)nS);
+    auto pick = [&]() -> int {                           // every block at the ceiling at[] of its stream
+        for (int64_t s = 0; s < nS; ++s) ceil[(size_t)s] = std::pow(10.0, Z.db(at[(size_t)s]) / 10.0);
+        MRC_HIP(h, hipMemcpyAsync(V.ceilings.p, ceil.data(), (size_t)nS * sizeof(double), hipMemcpyHostToDevice, st));
+        for (int g = 0; g < q.nGroups; ++g) {
+            const int joint = (g == 4 || nch == 1) ? 0 : 1;
+            ChainGroupBufs& B = C.g[g];
+            MRC_HIP(h, launch_vbr_pick(q.hs[g]->dev, joint, count[g], V.ceilings.as<double>(), C.chunkStream.as<int>(),
+                                       B.lines.as<double>(), B.oscale.as<int>(), joint ? B.ms.as<int>() : nullptr,
+                                       V.prof[g].as<double>(), joint ? V.profPick[g].as<unsigned>() : nullptr,
+                                       B.bitAlloc.as<int>(), B.scaleFactor.as<int>(), B.mant.as<unsigned short>(),
+                                       B.chunkMap.as<long long>(), T.stat.as<double>(), V.capped.as<int>(), st));
+        }
+        return MRC_OK;
+    };
+    MRC_HIP(h, hipEventRecord(V.evSize[0], st));
+    for (int round = 0; round < MRC_MAX_PROBES; ++round) {
+        bool any = false;
+        for (int64_t s = 0; s < nS; ++s)
+            if (active[(size_t)s]) { at[(size_t)s] = round == 0 ? hi[(size_t)s] : (lo[(size_t)s] + hi[(size_t)s]) / 2; any = true; }
+        if (!any) break;
+        MRC_TRY(pick());
+        for (int g = 0; g < q.nGroups; ++g) {
+            if (!count[g]) continue;
+            const int joint = (g == 4 || nch == 1) ? 0 : 1;
+            const DevShape& S = q.hs[g]->dev;
+            ChainGroupBufs& B = C.g[g];
+            MRC_HIP(h, launch_pack_plan(S, pack_params(h->cfg, S.a, S.b, joint ? 2 : 1, joint, c.use_huffman), tables, count[g],
+                                        B.bitAlloc.as<int>(), B.mant.as<unsigned short>(), MRC_MANTISSA_I16, nullptr,
+                                        B.table.as<int>(), nullptr, W, B.chunkMap.as<long long>(), all_bands_non_empty(*q.hs[g]), st));
+        }
+        MRC_HIP(h, launch_vbr_size_bytes(nS, nChunks, q.hdrLen, C.firstChunk.as<long long>(), W.chunkBytes, V.bytes.as<long long>(), st));
+        MRC_HIP(h, hipMemcpyAsync(bytes.data(), V.bytes.p, (size_t)nS * sizeof(long long), hipMemcpyDeviceToHost, st));
+        MRC_HIP(h, hipStreamSynchronize(st));
+        for (int64_t s = 0; s < nS; ++s) {
+            if (!active[(size_t)s]) continue;
+            const int64_t gs = s0 + s;
+            const int i = at[(size_t)s], p = Z.probes[gs]++;
+            const bool fits = bytes[(size_t)s] <= Z.target[gs];
+            if (Z.probe_index) Z.probe_index[gs * MRC_MAX_PROBES + p] = i;
+            if (Z.probe_bytes) Z.probe_bytes[gs * MRC_MAX_PROBES + p] = bytes[(size_t)s];
+            if (round == 0) {
+                Z.met[gs] = fits ? 1 : 0;
+                if (!fits) active[(size_t)s] = 0;
+            } else if (fits) hi[(size_t)s] = i;
+            else lo[(size_t)s] = i + 1;
+            if (lo[(size_t)s] >= hi[(size_t)s]) active[(size_t)s] = 0;
+        }
+    }
+    MRC_HIP(h, hipEventRecord(V.evSize[1], st));
+    bool again = false;
+    for (int64_t s = 0; s < nS; ++s) {
+        const int64_t gs = s0 + s;
+        again = again || at[(size_t)s] != hi[(size_t)s];
+        at[(size_t)s] = hi[(size_t)s];
+        Z.chosen[gs] = hi[(size_t)s];
+        Z.chosen_db[gs] = Z.db(hi[(size_t)s]);
+        Z.ceiling_ratio[gs] = std::pow(10.0, Z.chosen_db[gs] / 10.0);
+    }
+    if (again) MRC_TRY(pick());
+    MRC_HIP(h, hipEventRecord(V.evSize[2], st));
+    MRC_HIP(h, hipStreamSynchronize(st));                // (the queued copy reads ceil)
+    return MRC_OK;
+}
 
 int vbr_slab(mrc_handle* h, const ChainCall& c, const ChainSchedule& q, const int64_t* count, hipStream_t st) {
     ChainVbr& N = *c.vbr;
@@ -1192,6 +1307,14 @@ int vbr_slab(mrc_handle* h, const ChainCall& c, const ChainSchedule& q, const in
         V.ev.push_back(e);
     }
     V.evUsed = 0;
+    if (N.size) {                                        // the record of every block of the slab, group by group
+        for (auto& e : V.evSize) if (!e) MRC_HIP(h, hipEventCreate(&e));
+        for (int g = 0; g < q.nGroups; ++g) {
+            const int joint = (g == 4 || nch == 1) ? 0 : 1;
+            MRC_HIP(h, V.prof[g].reserve(std::max<size_t>((size_t)count[g] * vbr_profile_bytes(q.hs[g]->dev, joint), 256)));
+            if (joint) MRC_HIP(h, V.profPick[g].reserve(std::max<size_t>((size_t)count[g] * q.hs[g]->dev.nBands * sizeof(unsigned), 256)));
+        }
+    }
     if (c.with_flush) {
         N.flushOffs.resize((size_t)count[4]);
         for (int64_t k = 0; k < count[4]; ++k) N.flushOffs[(size_t)k] = k * 2 * (int64_t)L;
@@ -1216,13 +1339,19 @@ int vbr_slab(mrc_handle* h, const ChainCall& c, const ChainSchedule& q, const in
                                       T.thresh.as<double>() + ch * n * M, nullptr, nullptr, h->exactSpread, st));
             }
             MRC_HIP(h, hipEventRecord(V.ev[V.evUsed++], st));
-            MRC_HIP(h, launch_vbr_alloc(S, joint, n, k0, N.ceiling, B.lines.as<double>(), B.oscale.as<int>(),
-                                        joint ? B.ms.as<int>() : nullptr, B.bitAlloc.as<int>(), B.scaleFactor.as<int>(),
-                                        B.mant.as<unsigned short>(), B.chunkMap.as<long long>() + k0 * nOut, T.lines.as<double>(),
-                                        T.thresh.as<double>(), T.stat.as<double>(), V.capped.as<int>(), chunkBase, st));
+            if (N.size)
+                MRC_HIP(h, launch_vbr_profile(S, joint, n, k0, B.lines.as<double>(), B.oscale.as<int>(),
+                                              joint ? B.ms.as<int>() : nullptr, T.lines.as<double>(), T.thresh.as<double>(),
+                                              V.prof[g].as<double>(), joint ? V.profPick[g].as<unsigned>() : nullptr, st));
+            else
+                MRC_HIP(h, launch_vbr_alloc(S, joint, n, k0, N.ceiling, B.lines.as<double>(), B.oscale.as<int>(),
+                                            joint ? B.ms.as<int>() : nullptr, B.bitAlloc.as<int>(), B.scaleFactor.as<int>(),
+                                            B.mant.as<unsigned short>(), B.chunkMap.as<long long>() + k0 * nOut, T.lines.as<double>(),
+                                            T.thresh.as<double>(), T.stat.as<double>(), V.capped.as<int>(), chunkBase, st));
             MRC_HIP(h, hipEventRecord(V.ev[V.evUsed++], st));
         }
     }
+    if (N.size) MRC_TRY(vbr_size_search(h, c, q, count, st));
     return MRC_OK;
 }
 
@@ -1232,6 +1361,13 @@ int vbr_time(mrc_handle* h, const ChainCall& c) {
         float ms = 0.f;
         MRC_HIP(h, hipEventElapsedTime(&ms, V.ev[i], V.ev[i + 1]));
         c.vbr->msAlloc += ms;
+    }
+    if (c.vbr->size) {
+        float a = 0.f, b = 0.f;
+        MRC_HIP(h, hipEventElapsedTime(&a, V.evSize[0], V.evSize[1]));
+        MRC_HIP(h, hipEventElapsedTime(&b, V.evSize[1], V.evSize[2]));
+        c.vbr->msProbe += a;
+        c.vbr->msPick += b;
     }
     return MRC_OK;
 }
@@ -1311,7 +1447,71 @@ int vbr_finish(mrc_handle* h, const ChainCall& c, const ChainVbr& N, const VbrOu
     V.ms[1] = N.msAlloc;
     V.ms[2] = h->chainMs[2];
     V.ms[3] = h->chainMs[3];
+    if (N.size) {
+        V.sizeMs[0] = V.ms[0] - N.msProbe - N.msPick;
+        V.sizeMs[1] = N.msAlloc;
+        V.sizeMs[2] = N.msProbe;
+        V.sizeMs[3] = N.msPick + h->chainMs[2];
+        V.sizeMs[4] = h->chainMs[3];
+    }
     return MRC_OK;
+}
+
+// mrc_encode_vbr_size_pac's own refusals behind vbr_check's, and the trace cleared
+int vbr_size_check(mrc_handle* h, const std::string& w, const VbrSize& Z, int64_t n_streams, const int64_t* block_start, int nch) {
+    if (!std::isfinite(Z.lo)) return fail(h, MRC_ERR_INVALID, w + ": ceiling_lo_db must be finite");
+    if (!std::isfinite(Z.step) || !(Z.step > 0.0)) return fail(h, MRC_ERR_INVALID, w + ": ceiling_step_db must be finite and > 0");
+    if (Z.n < 1 || Z.n > MRC_MAX_CEILINGS) return fail(h, MRC_ERR_INVALID, w + ": n_ceilings must lie in 1..MRC_MAX_CEILINGS (256)");
+    if (!Z.target) return fail(h, MRC_ERR_INVALID, w + ": target_bytes must not be NULL");
+    if (!Z.chosen || !Z.chosen_db || !Z.met || !Z.probes)
+        return fail(h, MRC_ERR_INVALID, w + ": chosen, chosen_db, met and probes must not be NULL");
+    const int64_t cap = vbr_size_slab_blocks(h, nch);
+    for (int64_t s = 0; s < n_streams; ++s) {
+        if (Z.target[s] < 0) return fail(h, MRC_ERR_INVALID, w + ": target_bytes[" + std::to_string(s) + "] is negative");
+        if (block_start[s + 1] - block_start[s] > cap)
+            return fail(h, MRC_ERR_INVALID, w + ": stream " + std::to_string(s) + " has " + std::to_string(block_start[s + 1] - block_start[s]) +
+                                            " blocks, a slab of this call holds " + std::to_string(cap) + " (MRC_OPT_CHAIN_SLAB_BLOCKS): "
+                                            "the search needs all blocks of a stream resident at once");
+    }
+    for (int64_t s = 0; s < n_streams; ++s) {
+        Z.probes[s] = 0;
+        for (int p = 0; p < MRC_MAX_PROBES; ++p) {
+            if (Z.probe_index) Z.probe_index[s * MRC_MAX_PROBES + p] = -1;
+            if (Z.probe_bytes) Z.probe_bytes[s * MRC_MAX_PROBES + p] = -1;
+        }
+    }
+    return MRC_OK;
+}
+
+// both entry points: pcm and out in host memory (the PCM staged, the bytes copied back slab by slab) or on the device
+int vbr_size_call(mrc_handle* h, const char* who, const VbrSize& Z, ChainCall c, const VbrOut& o, uint8_t* out, int64_t out_cap,
+                  bool onHost) {
+    MRC_TRY(vbr_check(h, who, 0.0, c.n_streams, c.pcm_left, c.stream_stride, c.block_start, c.block_offset, c.block_a, c.block_b,
+                      c.num_samples, out, out_cap, c.stream_byte_offset, Z.ceiling_ratio, o, c.total_bytes));
+    MRC_TRY(vbr_size_check(h, who, Z, c.n_streams, c.block_start, c.nch()));
+    ChainVbr N;
+    N.blockStart = c.block_start;
+    N.size = &Z;
+    c.slabBlocks = vbr_size_slab_blocks(h, c.nch());
+    N.plan = plan_slabs(c.n_streams, c.block_start, c.slabBlocks);
+    c.vbr = &N;
+    hipStream_t st = onHost ? h->stream : pick_stream(h, c.stream);
+    auto after = [&](const Slab& sl, const int64_t*, const int64_t*, const uint8_t*) {
+        MRC_TRY(vbr_decide(h, c, N, o, sl, st));             // (whole streams only: every slab decides its own)
+        ++N.slab;
+        return (int)MRC_OK;
+    };
+    int rc;
+    if (onHost) rc = chained_host(h, who, c, &out, &out_cap, after);
+    else {
+        MRC_TRY(check_call(h, who, c, &out, &out_cap));
+        rc = chained_slabs(h, c, &out_cap, out, [](int, uint8_t*, int64_t, int64_t) { return (int)MRC_OK; }, after);
+    }
+    if (rc != MRC_OK && rc != MRC_ERR_NOMEM) return rc;
+    const std::string err = h->error;
+    MRC_TRY(vbr_finish(h, c, N, o));
+    if (rc != MRC_OK) h->error = err;
+    return rc;
 }
 
 }  // namespace
@@ -1379,6 +1579,46 @@ int mrc_dev_encode_vbr_nmr_pac(mrc_handle* h, double ceiling_db, int64_t n_strea
     MRC_TRY(vbr_finish(h, c, N, o));
     if (rc != MRC_OK) h->error = err;
     return rc;
+}
+
+int mrc_encode_vbr_size_pac(mrc_handle* h, double ceiling_lo_db, double ceiling_step_db, int n_ceilings, const int64_t* target_bytes,
+                            int64_t n_streams, const int16_t* pcm_left, const int16_t* pcm_right, int64_t stream_stride,
+                            const int64_t* block_start, const int64_t* block_offset, const int32_t* block_a, const int32_t* block_b,
+                            int use_huffman, const uint32_t* num_samples, uint8_t* out, int64_t out_cap, int64_t* stream_byte_offset,
+                            int32_t* chosen, double* chosen_db, double* ceiling_ratio, int32_t* met, int32_t* probes,
+                            int32_t* probe_index, int64_t* probe_bytes, int64_t* capped_bands, int64_t* coded_bits,
+                            double* nmr_total_db, double* nmr_max_db, int64_t* disturbed_blocks, int64_t* n_blocks,
+                            int64_t* total_bytes) {
+    const VbrOut o{capped_bands, coded_bits, nmr_total_db, nmr_max_db, disturbed_blocks, n_blocks};
+    const VbrSize Z{ceiling_lo_db, ceiling_step_db, n_ceilings, target_bytes, chosen, chosen_db, ceiling_ratio, met, probes,
+                    probe_index, probe_bytes};
+    const ChainCall c{1, nullptr, n_streams, pcm_left, pcm_right, MRC_SAMPLES_PCM16, stream_stride, block_start, block_offset,
+                      block_a, block_b, nullptr, use_huffman, 1, num_samples, stream_byte_offset, nullptr, nullptr, nullptr,
+                      total_bytes, nullptr};
+    return vbr_size_call(h, __func__, Z, c, o, out, out_cap, true);
+}
+
+int mrc_dev_encode_vbr_size_pac(mrc_handle* h, double ceiling_lo_db, double ceiling_step_db, int n_ceilings,
+                                const int64_t* target_bytes, int64_t n_streams, const int16_t* pcm_left, const int16_t* pcm_right,
+                                int64_t stream_stride, const int64_t* block_start, const int64_t* block_offset,
+                                const int32_t* block_a, const int32_t* block_b, int use_huffman, const uint32_t* num_samples,
+                                uint8_t* out, int64_t out_cap, int64_t* stream_byte_offset, int32_t* chosen, double* chosen_db,
+                                double* ceiling_ratio, int32_t* met, int32_t* probes, int32_t* probe_index, int64_t* probe_bytes,
+                                int64_t* capped_bands, int64_t* coded_bits, double* nmr_total_db, double* nmr_max_db,
+                                int64_t* disturbed_blocks, int64_t* n_blocks, int64_t* total_bytes, void* stream) {
+    const VbrOut o{capped_bands, coded_bits, nmr_total_db, nmr_max_db, disturbed_blocks, n_blocks};
+    const VbrSize Z{ceiling_lo_db, ceiling_step_db, n_ceilings, target_bytes, chosen, chosen_db, ceiling_ratio, met, probes,
+                    probe_index, probe_bytes};
+    const ChainCall c{1, nullptr, n_streams, pcm_left, pcm_right, MRC_SAMPLES_PCM16, stream_stride, block_start, block_offset,
+                      block_a, block_b, nullptr, use_huffman, 1, num_samples, stream_byte_offset, nullptr, nullptr, nullptr,
+                      total_bytes, stream};
+    return vbr_size_call(h, __func__, Z, c, o, out, out_cap, false);
+}
+
+int mrc_get_vbr_size_ms(mrc_handle* h, double* ms) {
+    if (!h || !ms) return MRC_ERR_INVALID;
+    for (int i = 0; i < 5; ++i) ms[i] = h->vbr.sizeMs[i];
+    return MRC_OK;
 }
 
 int mrc_get_vbr_ms(mrc_handle* h, double* ms) {

@@ -131,11 +131,20 @@ struct TargetBufs {
 // Constant-quality VBR (mrc_encode_vbr_nmr_pac, mrc_api_chain.cpp).  The source analysis and the file reduction use TargetBufs.
 struct VbrBufs {
     DevBuf capped;                   // [chunks of the streams being decided]: capped bands, at a block's first chunk
-    std::vector<hipEvent_t> ev;      // start and end of every allocator launch of a slab
+    std::vector<hipEvent_t> ev;      // start and end of every allocator (or profile) launch of a slab
     size_t evUsed = 0;
     double ms[4] = {0, 0, 0, 0};     // phase A + source analysis | the allocator | pack | all three
+    // mrc_encode_vbr_size_pac: the slab's record per block-shape group, the streams' ceilings and file sizes of a probe
+    DevBuf prof[kChainGroups], profPick[kChainGroups], ceilings, bytes;
+    hipEvent_t evSize[3] = {};       // the probes start | the final pick starts | it ended
+    double sizeMs[5] = {0, 0, 0, 0, 0};   // phase A + source analysis | profile | probes | final pick + pack | their sum
     void release() {
         capped.release();
+        for (auto& b : prof) b.release();
+        for (auto& b : profPick) b.release();
+        ceilings.release();
+        bytes.release();
+        for (auto& e : evSize) { if (e) (void)hipEventDestroy(e); e = nullptr; }
         for (auto& e : ev) if (e) (void)hipEventDestroy(e);
         ev.clear();
     }

@@ -264,6 +264,22 @@ hipError_t launch_vbr_alloc(const DevShape& S, int joint, int64_t n, int64_t k0,
                             const int* oscale, const int* msSwitch, int* bitAlloc, int* scaleFactor, unsigned short* mant,
                             const long long* chunkMap, const double* lines, const double* thresh, double* stat, int* capped,
                             long long chunkBase, hipStream_t st);
+// Encode to a size at constant quality (mrc_encode_vbr_size_pac).  launch_vbr_profile: launch_vbr_alloc's inputs without a
+// ceiling; every band walks to the end of its state sequence and its ratios go to prof [blocks of the group][nBands]
+// [vbr_profile_bytes / nBands / 8], the streams its M/S bands raised to profPick [blocks of the group][nBands] (joint only).
+// launch_vbr_pick: all n blocks of a group at the ceiling of their stream (ceilings [streams], chunkStream [chunks]) from that
+// record and phase A's data alone; it writes what launch_vbr_alloc writes (chunkBase 0).  launch_vbr_size_bytes: bytes[s] =
+// hdrLen + sum over stream s's chunks of (4 + chunkBytes), the packer's plan in chunk order.
+size_t vbr_profile_bytes(const DevShape& S, int joint);   // of one block
+hipError_t launch_vbr_profile(const DevShape& S, int joint, int64_t n, int64_t k0, const double* phaseLines, const int* oscale,
+                              const int* msSwitch, const double* lines, const double* thresh, double* prof, unsigned* profPick,
+                              hipStream_t st);
+hipError_t launch_vbr_pick(const DevShape& S, int joint, int64_t n, const double* ceilings, const int* chunkStream,
+                           const double* phaseLines, const int* oscale, const int* msSwitch, const double* prof,
+                           const unsigned* profPick, int* bitAlloc, int* scaleFactor, unsigned short* mant,
+                           const long long* chunkMap, double* stat, int* capped, hipStream_t st);
+hipError_t launch_vbr_size_bytes(int64_t nStreams, int64_t nChunks, int hdrLen, const long long* firstChunk,
+                                 const int* chunkBytes, long long* bytes, hipStream_t st);
 // mrc_kernels_huff.hip
 hipError_t launch_huffman_gain(const DevShape& S, int64_t nFrames, int nStreams, const int* bitAlloc,
                                const int* mantissa, const int* reservoirOut, int* huffTable, int* bitsSaved,

@@ -309,6 +309,55 @@ def encode_stream_vbr_nmr(handle, stream, shapes, ceiling_db, use_huffman=True, 
                                      num_samples=[num_samples])[0]
 
 
+def bisect_ceiling(sizes_by_index, target):
+    """The rule of mrc_encode_vbr_size_pac on one stream: sizes_by_index[i] = the file size at grid index i (index 0: the
+    tightest ceiling), target = the size limit.  Probe the last index; too large: (last, False).  Otherwise bisect -- mid =
+    (lo + hi) // 2, a probe that fits moves hi to mid, one that does not moves lo to mid + 1 -- until lo == hi.
+    -> (chosen, met, the indices probed in order).  Sizes need not be monotone: this rule is the contract."""
+    n = len(sizes_by_index)
+    if n < 1:
+        raise ValueError("bisect_ceiling: no ceilings")
+    lo, hi = 0, n - 1
+    probed = [hi]
+    if sizes_by_index[hi] > target:
+        return hi, False, probed
+    while lo < hi:
+        mid = (lo + hi) // 2
+        probed.append(mid)
+        if sizes_by_index[mid] <= target:
+            hi = mid
+        else:
+            lo = mid + 1
+    return hi, True, probed
+
+
+def ceiling_grid(lo_db, step_db, n):
+    """The grid of mrc_encode_vbr_size_pac in dB: lo_db + i * step_db, one multiply and one add in double."""
+    return np.float64(lo_db) + np.arange(int(n), dtype=np.float64) * np.float64(step_db)
+
+
+def encode_stream_vbr_size(handle, stream, shapes, target_bytes, lo_db=-30.0, step_db=0.25, n=256, use_huffman=True,
+                           num_samples=None):
+    """encode_stream_vbr_nmr with the ceiling searched in one library call (mrc_encode_vbr_size_pac): the tightest ceiling of
+    the grid lo_db + i * step_db (i < n) that bisect_ceiling finds to keep the whole file <= target_bytes.  -> dict:
+    encode_stream_vbr_nmr's for that ceiling plus chosen, chosen_db, met, probes, probe_index, probe_bytes."""
+    L = handle.cfg.n_mdct_lines
+    stream = np.asarray(stream)
+    if stream.dtype != np.int16:
+        raise ValueError("the stream must hold int16 PCM codes (the NMR's source is int16)")
+    if stream.ndim == 1:
+        stream = stream[None]
+    if stream.ndim != 2 or stream.shape[0] not in (1, 2):
+        raise ValueError("stream must be stereo [2][samples] or mono [samples]")
+    if not len(shapes) or shapes[-1][2] != L:
+        raise ValueError("the stream must end with a long block (the reference's Close() assumes it)")
+    if num_samples is None:
+        num_samples = sum(int(b) for (_, _, b) in shapes)
+    right = stream[1][None] if stream.shape[0] == 2 else None
+    return handle.encode_vbr_size_pac(stream[0][None], right, [shapes], [int(target_bytes)], lo_db, step_db, n,
+                                      use_huffman=use_huffman, num_samples=[num_samples])[0]
+
+
 def encode_mono_stream_per_block(handle, stream, shapes, use_huffman=True, num_samples=None):
     """The block-at-a-time form of encode_mono_stream: one mrc_encode_mono per block, the reservoir carried on the host
     (reservoir_out + Huffman bits_saved), C++ packer, then Close()'s block.  The cross-check of the chained mono path
