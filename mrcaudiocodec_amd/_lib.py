@@ -646,6 +646,62 @@ class Handle:
             out.append(d)
         return out
 
+    # ---- what the calls that measure their own output share: the preamble, the host buffer, the per-stream dicts
+
+    def _measured_begin(self, name, pcm_left, pcm_right, shapes, use_huffman, num_samples, device, rungs=None):
+        """The preamble (name: the method, for its errors) -> the call's state: q (_chain_args), n streams, m = max(n, 1)
+        (the length of a per-stream output array), the outputs every such call has -- s_off, total, and the NMR values
+        tot, mx, dist ([rungs][m] with rungs, else [m]) and nblk -- and the C arguments `common` (n_streams .. num_samples)
+        and `nmr_tail` (nmr_total_db .. total_bytes)."""
+        if num_samples is None:
+            raise ValueError("%s: num_samples is required (whole files only)" % name)
+        if device is None and np.atleast_2d(pcm_left).dtype != np.int16:
+            raise ValueError("%s: int16 PCM codes only (the NMR's source is int16)" % name)
+        dev5 = None if device is None else (device[0], device[1], 1, device[2])
+        q = self._chain_args(pcm_left, pcm_right, shapes, use_huffman, True, num_samples, dev5)
+        n, m = q.n_streams, max(q.n_streams, 1)
+        rows = (m,) if rungs is None else (rungs, m)
+        o = SimpleNamespace(q=q, n=n, m=m, rungs=rungs, s_off=np.zeros(n + 1, np.int64), total=np.zeros(1, np.int64),
+                            tot=np.zeros(rows, np.float64), mx=np.zeros(rows, np.float64), dist=np.zeros(rows, np.int64),
+                            nblk=np.zeros(m, np.int64))
+        o.common = (n, q.pcm[0], q.pcm[1], q.pcm[3]) + q.head + (q.opts[0], q.opts[2])
+        o.nmr_tail = (_p(o.tot, _f64p), _p(o.mx, _f64p), _p(o.dist, _i64p), _p(o.nblk, _i64p), _p(o.total, _i64p))
+        return o
+
+    def _measured_call(self, cname, head, tail, o, device, stream, out_cap, typical=None, encode_again=True):
+        """mrc_dev_<cname> on the caller's device buffer (-> None), or mrc_<cname> into a host buffer of out_cap bytes (None:
+        the call's bound, or `typical` if that is less) -> the bytes.  If they do not fit they are fetched from the handle's
+        device buffer; a call of several slabs keeps nothing there and, with encode_again, runs once more into a buffer of
+        the reported size."""
+        if device is not None:
+            self._check(getattr(lib, "mrc_dev_" + cname)(*head, device[3], int(device[4]), *tail, stream))
+            return None
+        call, bound = getattr(lib, "mrc_" + cname), o.q.bound()
+        if out_cap is None:
+            out_cap = bound if typical is None else min(bound, typical)
+        buf = np.empty(max(int(out_cap), 1), np.uint8)
+        rc = call(*head, vp(buf), int(out_cap), *tail)
+        if rc == MRC_ERR_NOMEM and 0 < int(o.total[0]) <= bound:
+            buf = np.empty(int(o.total[0]), np.uint8)
+            rc = lib.mrc_chain_fetch_output(self._h, vp(buf), buf.size, _p(o.total, _i64p))
+            if rc != 0 and encode_again:
+                rc = call(*head, vp(buf), buf.size, *tail)
+        self._check(rc)
+        return buf
+
+    @staticmethod
+    def _measured_results(o, buf, **own):
+        """-> one dict per stream: data (the stream's bytes; (start, end) in the caller's buffer if buf is None), the call's
+        own fields (a list with an entry per stream each), the NMR fields.  Columns are converted once, not per stream."""
+        n, off = o.n, o.s_off.tolist()
+        data = [(off[s], off[s + 1]) if buf is None else buf[off[s]:off[s + 1]].tobytes() for s in range(n)]
+        if o.rungs is None:
+            nmr = [o.tot[:n].tolist(), o.mx[:n].tolist(), o.dist[:n].tolist()]
+        else:
+            nmr = [[a[:, s].copy() for s in range(n)] for a in (o.tot, o.mx, o.dist)]
+        keys = ("data",) + tuple(own) + ("nmr_total_db", "nmr_max_db", "disturbed_blocks", "n_blocks")
+        return [dict(zip(keys, row)) for row in zip(data, *own.values(), *nmr, o.nblk[:n].tolist())]
+
     def encode_chained_pac_target_nmr(self, pcm_left, pcm_right, shapes, rates, target_db, use_huffman=True, num_samples=None,
                                       device=None, stream=None, out_cap=None):
         """mrc_encode_chained_target_nmr_pac: the streams of encode_chained_pac_ladder (int16 PCM codes, each row starting
@@ -658,44 +714,20 @@ class Handle:
         -> one dict per stream: data (bytes), chosen, rate, met, nmr_total_db [R], nmr_max_db [R], disturbed_blocks [R],
         n_blocks -- the numbers pac_nmr gives for every rung's file."""
         rates = np.ascontiguousarray(np.atleast_1d(np.asarray(rates, dtype=np.float64)))
-        R = rates.size
-        if num_samples is None:
-            raise ValueError("encode_chained_pac_target_nmr: num_samples is required (whole files only)")
-        if device is None and np.atleast_2d(pcm_left).dtype != np.int16:
-            raise ValueError("encode_chained_pac_target_nmr: int16 PCM codes only (the NMR's source is int16)")
-        dev5 = None if device is None else (device[0], device[1], 1, device[2])
-        q = self._chain_args(pcm_left, pcm_right, shapes, use_huffman, True, num_samples, dev5)
-        n = q.n_streams
-        pcm = (q.pcm[0], q.pcm[1], q.pcm[3])
-        s_off = np.zeros(n + 1, np.int64)
-        chosen, met = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
-        tot, mx = np.zeros((R, max(n, 1)), np.float64), np.zeros((R, max(n, 1)), np.float64)
-        dist, nblk = np.zeros((R, max(n, 1)), np.int64), np.zeros(max(n, 1), np.int64)
-        total = np.zeros(1, np.int64)
-        args = (self._h, R, _p(rates, _f64p), float(target_db), n) + pcm + q.head + (q.opts[0], q.opts[2])
-        tail = (_p(s_off, _i64p), _p(chosen, _i32p), _p(met, _i32p), _p(tot, _f64p), _p(mx, _f64p), _p(dist, _i64p),
-                _p(nblk, _i64p), _p(total, _i64p))
-        buf = None
-        if device is not None:
-            self._check(lib.mrc_dev_encode_chained_target_nmr_pac(*args, device[3], int(device[4]), *tail, stream))
-        else:
-            bound = q.bound()
-            if out_cap is None:                  # typical content at the top rate; more: fetched from the device, no second encode
-                out_cap = min(bound, q.n_blocks * max(1024, int(1.5 * rates.max() * q.nch * 1024 / 8)) + n * 4096 + 4096)
-            buf = np.empty(max(int(out_cap), 1), np.uint8)
-            rc = lib.mrc_encode_chained_target_nmr_pac(*args, vp(buf), int(out_cap), *tail)
-            if rc == MRC_ERR_NOMEM and 0 < int(total[0]) <= bound:
-                buf = np.empty(int(total[0]), np.uint8)
-                self._check(lib.mrc_chain_fetch_output(self._h, vp(buf), buf.size, _p(total, _i64p)))
-            else:
-                self._check(rc)
-        out = []
-        for s in range(n):
-            lo, hi = int(s_off[s]), int(s_off[s + 1])
-            out.append(dict(data=(lo, hi) if buf is None else buf[lo:hi].tobytes(), chosen=int(chosen[s]),
-                            rate=float(rates[chosen[s]]), met=bool(met[s]), nmr_total_db=tot[:, s].copy(),
-                            nmr_max_db=mx[:, s].copy(), disturbed_blocks=dist[:, s].copy(), n_blocks=int(nblk[s])))
-        return out
+        o = self._measured_begin("encode_chained_pac_target_nmr", pcm_left, pcm_right, shapes, use_huffman, num_samples, device,
+                                 rungs=rates.size)
+        chosen, met = np.zeros(o.m, np.int32), np.zeros(o.m, np.int32)
+        head = (self._h, rates.size, _p(rates, _f64p), float(target_db)) + o.common
+        tail = (_p(o.s_off, _i64p), _p(chosen, _i32p), _p(met, _i32p)) + o.nmr_tail
+        # typical content at the top rate; more: fetched from TargetBufs::sel, which holds the whole result (no second encode)
+        typical = None
+        if device is None and out_cap is None:
+            typical = o.q.n_blocks * max(1024, int(1.5 * rates.max() * o.q.nch * 1024 / 8)) + o.n * 4096 + 4096
+        buf = self._measured_call("encode_chained_target_nmr_pac", head, tail, o, device, stream, out_cap, typical,
+                                  encode_again=False)
+        chosen = chosen[:o.n]
+        return self._measured_results(o, buf, chosen=chosen.tolist(), rate=rates[chosen].tolist(),
+                                      met=met[:o.n].astype(bool).tolist())
 
     def target_ms(self):
         """device time of the last encode_chained_pac_target_nmr: phase A + preparation, serial scan, NMR kernels
@@ -715,46 +747,13 @@ class Handle:
         out_cap: the size of the host buffer (default: the call's bound).
         -> one dict per stream: data (bytes), ceiling_ratio, capped_bands, coded_bits, nmr_total_db, nmr_max_db,
         disturbed_blocks, n_blocks -- the numbers pac_nmr gives for the file."""
-        if num_samples is None:
-            raise ValueError("encode_vbr_nmr_pac: num_samples is required (whole files only)")
-        if device is None and np.atleast_2d(pcm_left).dtype != np.int16:
-            raise ValueError("encode_vbr_nmr_pac: int16 PCM codes only (the NMR's source is int16)")
-        dev5 = None if device is None else (device[0], device[1], 1, device[2])
-        q = self._chain_args(pcm_left, pcm_right, shapes, use_huffman, True, num_samples, dev5)
-        n = q.n_streams
-        pcm = (q.pcm[0], q.pcm[1], q.pcm[3])
-        s_off = np.zeros(n + 1, np.int64)
-        ratio = np.zeros(1, np.float64)
-        capped, bits = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
-        tot, mx = np.zeros(max(n, 1), np.float64), np.zeros(max(n, 1), np.float64)
-        dist, nblk = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
-        total = np.zeros(1, np.int64)
-        args = (self._h, float(ceiling_db), n) + pcm + q.head + (q.opts[0], q.opts[2])
-        tail = (_p(s_off, _i64p), _p(ratio, _f64p), _p(capped, _i64p), _p(bits, _i64p), _p(tot, _f64p), _p(mx, _f64p),
-                _p(dist, _i64p), _p(nblk, _i64p), _p(total, _i64p))
-        buf = None
-        if device is not None:
-            self._check(lib.mrc_dev_encode_vbr_nmr_pac(*args, device[3], int(device[4]), *tail, stream))
-        else:
-            bound = q.bound()
-            if out_cap is None:
-                out_cap = bound
-            buf = np.empty(max(int(out_cap), 1), np.uint8)
-            rc = lib.mrc_encode_vbr_nmr_pac(*args, vp(buf), int(out_cap), *tail)
-            if rc == MRC_ERR_NOMEM and 0 < int(total[0]) <= bound:
-                buf = np.empty(int(total[0]), np.uint8)
-                if lib.mrc_chain_fetch_output(self._h, vp(buf), buf.size, _p(total, _i64p)) != 0:
-                    # several slabs: nothing is kept on the device -- once more, into a buffer of the reported size
-                    self._check(lib.mrc_encode_vbr_nmr_pac(*args, vp(buf), buf.size, *tail))
-            else:
-                self._check(rc)
-        out = []
-        for s in range(n):
-            lo, hi = int(s_off[s]), int(s_off[s + 1])
-            out.append(dict(data=(lo, hi) if buf is None else buf[lo:hi].tobytes(), ceiling_ratio=float(ratio[0]),
-                            capped_bands=int(capped[s]), coded_bits=int(bits[s]), nmr_total_db=float(tot[s]),
-                            nmr_max_db=float(mx[s]), disturbed_blocks=int(dist[s]), n_blocks=int(nblk[s])))
-        return out
+        o = self._measured_begin("encode_vbr_nmr_pac", pcm_left, pcm_right, shapes, use_huffman, num_samples, device)
+        ratio, capped, bits = np.zeros(1, np.float64), np.zeros(o.m, np.int64), np.zeros(o.m, np.int64)
+        head = (self._h, float(ceiling_db)) + o.common
+        tail = (_p(o.s_off, _i64p), _p(ratio, _f64p), _p(capped, _i64p), _p(bits, _i64p)) + o.nmr_tail
+        buf = self._measured_call("encode_vbr_nmr_pac", head, tail, o, device, stream, out_cap)
+        return self._measured_results(o, buf, ceiling_ratio=[float(ratio[0])] * o.n, capped_bands=capped[:o.n].tolist(),
+                                      coded_bits=bits[:o.n].tolist())
 
     def vbr_ms(self):
         """device time of the last encode_vbr_nmr_pac: phase A + source analysis, the allocator, pack, their sum (ms)"""
@@ -769,55 +768,25 @@ class Handle:
         target_bytes [nStreams] (the complete file).  device / out_cap as in encode_vbr_nmr_pac.
         -> one dict per stream: encode_vbr_nmr_pac's at the chosen ceiling plus chosen, chosen_db, met, probes, probe_index
         and probe_bytes (the grid index and file size of every probe in order)."""
-        if num_samples is None:
-            raise ValueError("encode_vbr_size_pac: num_samples is required (whole files only)")
-        if device is None and np.atleast_2d(pcm_left).dtype != np.int16:
-            raise ValueError("encode_vbr_size_pac: int16 PCM codes only (the NMR's source is int16)")
-        dev5 = None if device is None else (device[0], device[1], 1, device[2])
-        q = self._chain_args(pcm_left, pcm_right, shapes, use_huffman, True, num_samples, dev5)
-        ns = q.n_streams
-        m = max(ns, 1)
+        o = self._measured_begin("encode_vbr_size_pac", pcm_left, pcm_right, shapes, use_huffman, num_samples, device)
+        ns, m = o.n, o.m
         target = np.ascontiguousarray(target_bytes, dtype=np.int64).reshape(-1)
         if target.shape != (ns,):
             raise ValueError("target_bytes: one value per stream")
-        pcm = (q.pcm[0], q.pcm[1], q.pcm[3])
-        s_off = np.zeros(ns + 1, np.int64)
         chosen, met, probes = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros(m, np.int32)
         chosen_db, ratio = np.zeros(m, np.float64), np.zeros(m, np.float64)
         p_idx, p_bytes = np.full((m, MRC_MAX_PROBES), -1, np.int32), np.full((m, MRC_MAX_PROBES), -1, np.int64)
         capped, bits = np.zeros(m, np.int64), np.zeros(m, np.int64)
-        tot, mx = np.zeros(m, np.float64), np.zeros(m, np.float64)
-        dist, nblk = np.zeros(m, np.int64), np.zeros(m, np.int64)
-        total = np.zeros(1, np.int64)
-        args = (self._h, float(lo_db), float(step_db), int(n), _p(target, _i64p), ns) + pcm + q.head + (q.opts[0], q.opts[2])
-        tail = (_p(s_off, _i64p), _p(chosen, _i32p), _p(chosen_db, _f64p), _p(ratio, _f64p), _p(met, _i32p), _p(probes, _i32p),
-                _p(p_idx, _i32p), _p(p_bytes, _i64p), _p(capped, _i64p), _p(bits, _i64p), _p(tot, _f64p), _p(mx, _f64p),
-                _p(dist, _i64p), _p(nblk, _i64p), _p(total, _i64p))
-        buf = None
-        if device is not None:
-            self._check(lib.mrc_dev_encode_vbr_size_pac(*args, device[3], int(device[4]), *tail, stream))
-        else:
-            bound = q.bound()
-            if out_cap is None:
-                out_cap = bound
-            buf = np.empty(max(int(out_cap), 1), np.uint8)
-            rc = lib.mrc_encode_vbr_size_pac(*args, vp(buf), int(out_cap), *tail)
-            if rc == MRC_ERR_NOMEM and 0 < int(total[0]) <= bound:
-                buf = np.empty(int(total[0]), np.uint8)
-                if lib.mrc_chain_fetch_output(self._h, vp(buf), buf.size, _p(total, _i64p)) != 0:
-                    # several slabs: nothing is kept on the device -- once more, into a buffer of the reported size
-                    self._check(lib.mrc_encode_vbr_size_pac(*args, vp(buf), buf.size, *tail))
-            else:
-                self._check(rc)
-        out = []
-        for s in range(ns):
-            lo, hi, k = int(s_off[s]), int(s_off[s + 1]), int(probes[s])
-            out.append(dict(data=(lo, hi) if buf is None else buf[lo:hi].tobytes(), chosen=int(chosen[s]),
-                            chosen_db=float(chosen_db[s]), ceiling_ratio=float(ratio[s]), met=bool(met[s]), probes=k,
-                            probe_index=[int(v) for v in p_idx[s, :k]], probe_bytes=[int(v) for v in p_bytes[s, :k]],
-                            capped_bands=int(capped[s]), coded_bits=int(bits[s]), nmr_total_db=float(tot[s]),
-                            nmr_max_db=float(mx[s]), disturbed_blocks=int(dist[s]), n_blocks=int(nblk[s])))
-        return out
+        head = (self._h, float(lo_db), float(step_db), int(n), _p(target, _i64p)) + o.common
+        tail = (_p(o.s_off, _i64p), _p(chosen, _i32p), _p(chosen_db, _f64p), _p(ratio, _f64p), _p(met, _i32p), _p(probes, _i32p),
+                _p(p_idx, _i32p), _p(p_bytes, _i64p), _p(capped, _i64p), _p(bits, _i64p)) + o.nmr_tail
+        buf = self._measured_call("encode_vbr_size_pac", head, tail, o, device, stream, out_cap)
+        k = probes[:ns].tolist()
+        return self._measured_results(
+            o, buf, chosen=chosen[:ns].tolist(), chosen_db=chosen_db[:ns].tolist(), ceiling_ratio=ratio[:ns].tolist(),
+            met=met[:ns].astype(bool).tolist(), probes=k, probe_index=[row[:c] for row, c in zip(p_idx.tolist(), k)],
+            probe_bytes=[row[:c] for row, c in zip(p_bytes.tolist(), k)], capped_bands=capped[:ns].tolist(),
+            coded_bits=bits[:ns].tolist())
 
     def vbr_size_ms(self):
         """device time of the last encode_vbr_size_pac: phase A + source analysis, the profile kernel, all probes, the final

@@ -412,6 +412,7 @@ int encode_phase_a(mrc_handle* h, const DevShape& S, int64_t n, const void* chL,
         MRC_HIP(h, launch_ms_switch(n, S.nBands, S.msLeaves, S.msInternal, S.msPlan, lines, lines + S.halfN,
                                     4 * (int64_t)S.halfN, S.halfN, msSwitch, st));
     if (timing) MRC_HIP(h, hipEventRecord(h->ev[2], st));
+    if (!smr) return MRC_OK;                             // (a caller that allocates without SMRs: it stops here)
     MRC_HIP(h, launch_smr(S, n, chL, chR, fmt, stride, offsets, lines, oscale, smr, nullptr, peak,
                           (joint && !h->smrAllBands) ? msSwitch : nullptr, h->exactSpread, st,
                           h->sensOn ? h->sens.as<unsigned long long>() : nullptr));

@@ -244,9 +244,7 @@ int mrc_pac_nmr(mrc_handle* h, int64_t n_files, const uint8_t* buf, const int64_
         double* T = (double*)(dThresh + anaBytes[s]);
         int* os = nb.oscale.as<int>() + row;
         const int64_t* offs = (const int64_t*)(din + oAna[s]);
-        MRC_HIP(h, launch_mdct(S, n, dPlanes, nullptr, kSampleI16, 0, offs, true, X, os, st));
-        MRC_HIP(h, launch_smr(S, n, dPlanes, nullptr, kSampleI16, 0, offs, X, os, nb.smr.as<double>() + (int64_t)row * kMaxBands,
-                              T, nullptr, nullptr, h->exactSpread, st));
+        MRC_HIP(h, launch_nmr_source(h, S, n, dPlanes, offs, X, os, nb.smr.as<double>() + (int64_t)row * kMaxBands, T, st));
     }
     MRC_HIP(h, hipEventRecord(nb.ev[3], st));
     unsigned char* dOut = nb.out.as<unsigned char>();
@@ -271,7 +269,6 @@ int mrc_pac_nmr(mrc_handle* h, int64_t n_files, const uint8_t* buf, const int64_
     // ---- results: dB on the host from the file sums
     const unsigned char* pout = (const unsigned char*)nb.pinOut.p;
     const double* fileOut = (const double*)pout;
-    const double ninf = -std::numeric_limits<double>::infinity();
     for (int64_t f = 0; f < n_files; ++f) {
         const PacFilePlan& fi = pl.files[(size_t)f];
         int64_t weight = 0;
@@ -280,11 +277,10 @@ int mrc_pac_nmr(mrc_handle* h, int64_t n_files, const uint8_t* buf, const int64_
             shape_ab(h->cfg, pl.shape(f, i), &a, &b);
             weight += (int64_t)b * fi.nch;
         }
-        const double mx = fileOut[4 * f], sum = fileOut[4 * f + 1];
-        nmr_max_db[f] = mx > 0.0 ? 10.0 * std::log10(mx) : ninf;
-        const double mean = weight > 0 ? sum / (double)weight : 0.0;
-        nmr_total_db[f] = mean > 0.0 ? 10.0 * std::log10(mean) : ninf;
-        disturbed_blocks[f] = (int64_t)fileOut[4 * f + 2];
+        const NmrFileValues v = nmr_file_values(fileOut + 4 * f, weight);
+        nmr_total_db[f] = v.nmr_total_db;
+        nmr_max_db[f] = v.nmr_max_db;
+        disturbed_blocks[f] = v.disturbed_blocks;
     }
     if (entry_shape)
         for (int64_t f = 0; f < n_files; ++f)

@@ -1,8 +1,10 @@
 // The handle behind the C ABI and the helpers every translation unit of the host glue shares (mrc_api.cpp: the per-block
-// and pipelined entry points; mrc_api_chain.cpp: the chained stream encode).  Not part of the ABI.
+// and pipelined entry points; mrc_api_chain.cpp, mrc_api_chain_measured.cpp: the chained stream encode).  Not part of the ABI.
 #pragma once
 #include "mrc_internal.hpp"
 
+#include <cmath>
+#include <limits>
 #include <map>
 #include <string>
 #include <utility>
@@ -112,7 +114,7 @@ struct ChainBufs {
     }
 };
 
-// Encode to a target noise-to-mask ratio (mrc_encode_chained_target_nmr_pac, mrc_api_chain.cpp): reused from call to call
+// Encode to a target noise-to-mask ratio (mrc_encode_chained_target_nmr_pac, mrc_api_chain_measured.cpp): reused from call to call
 struct TargetBufs {
     DevBuf lines, thresh, oscale, smr;   // source analysis of one batch of blocks of one shape: X, T, overall scale, SMR (unused)
     DevBuf flushOffs;                // where Close()'s blocks start in ChainBufs::flushPcm
@@ -128,7 +130,7 @@ struct TargetBufs {
     }
 };
 
-// Constant-quality VBR (mrc_encode_vbr_nmr_pac, mrc_api_chain.cpp).  The source analysis and the file reduction use TargetBufs.
+// Constant-quality VBR (mrc_encode_vbr_nmr_pac, mrc_api_chain_measured.cpp).  The source analysis and the file reduction use TargetBufs.
 struct VbrBufs {
     DevBuf capped;                   // [chunks of the streams being decided]: capped bands, at a block's first chunk
     std::vector<hipEvent_t> ev;      // start and end of every allocator (or profile) launch of a slab
@@ -312,8 +314,8 @@ struct mrc_handle {
     mrc::ChainBufs chain;            // mrc_encode_chained_*: see mrc_api_chain.cpp
     mrc::DecodeBufs dec;             // mrc_dev_unpack_blocks / mrc_decode_pac_pcm16: see mrc_api_decode.cpp
     mrc::NmrBufs nmr;                // mrc_pac_nmr: see mrc_api_nmr.cpp
-    mrc::TargetBufs target;          // mrc_encode_chained_target_nmr_pac: see mrc_api_chain.cpp
-    mrc::VbrBufs vbr;                // mrc_encode_vbr_nmr_pac: see mrc_api_chain.cpp
+    mrc::TargetBufs target;          // mrc_encode_chained_target_nmr_pac: see mrc_api_chain_measured.cpp
+    mrc::VbrBufs vbr;                // mrc_encode_vbr_nmr_pac: see mrc_api_chain_measured.cpp
     double chainMs[4] = {0, 0, 0, 0};   // last chained encode: phase A, phase B, pack, whole call (host clock)
     bool timing = false;
     bool exactSpread = false;        // mrc_set_option(MRC_OPT_EXACT_SPREAD)
@@ -393,9 +395,28 @@ ChainGroupDev chain_group_desc(const HostShape& hs, int joint, const double* lin
                                unsigned short* mant, int* table);
 
 // phase A of the per-block path (windowed MDCT + overall scale -> [M/S switch] -> SMRs and per-band peaks), defined in
-// mrc_api.cpp beside encode_core, which it is the first half of
+// mrc_api.cpp beside encode_core, which it is the first half of.  smr == nullptr: it stops behind the M/S switch.
 int encode_phase_a(mrc_handle* h, const DevShape& S, int64_t n, const void* chL, const void* chR, int fmt, int64_t stride,
                    const int64_t* offsets, double* lines, int32_t* oscale, int32_t* msSwitch, double* smr, double* peak,
                    hipStream_t st, bool timing);
+
+// ---- the noise-to-mask ratio's two ends, shared by mrc_pac_nmr (mrc_api_nmr.cpp) and the chained calls that measure their
+// own output (mrc_api_chain_measured.cpp): the numbers of the latter are the former's to the bit because both come from here.
+// The source analysis: n one-channel blocks of shape S at explicit offsets `offs` into the int16 samples `src` -> lines X
+// [n][halfN], overall scales os [n], masked thresholds T [n][halfN] (the generic mode of smr_kernel that writes them;
+// MRC_OPT_EXACT_SPREAD honoured), SMRs to smr [n][kMaxBands] (unused).
+inline hipError_t launch_nmr_source(mrc_handle* h, const DevShape& S, int64_t n, const void* src, const int64_t* offs, double* X,
+                                    int* os, double* smr, double* T, hipStream_t st) {
+    const hipError_t e = launch_mdct(S, n, src, nullptr, kSampleI16, 0, offs, true, X, os, st);
+    if (e != hipSuccess) return e;
+    return launch_smr(S, n, src, nullptr, kSampleI16, 0, offs, X, os, smr, T, nullptr, nullptr, h->exactSpread, st);
+}
+// The file's values from nmr_file_kernel's row f = (max r, sum of b * mean r, disturbed blocks, -) and the file's weight
+// (the sum of b over its blocks and channels): -inf where nothing was disturbed at all
+struct NmrFileValues { double nmr_total_db, nmr_max_db; int64_t disturbed_blocks; };
+inline NmrFileValues nmr_file_values(const double* f, int64_t weight) {
+    const auto db = [](double v) { return v > 0.0 ? 10.0 * std::log10(v) : -std::numeric_limits<double>::infinity(); };
+    return {db(weight > 0 ? f[1] / (double)weight : 0.0), db(f[0]), (int64_t)f[2]};
+}
 
 }  // namespace mrc

@@ -247,6 +247,37 @@ def test_device_entry_point(mono):
     assert not host[len(want[0]["data"]):].any()
 
 
+def _long_short_run():
+    """one mono stream whose (S,S) blocks do not fit one batch of the source analysis (16384 blocks of one shape):
+    (L,S), 16384 + 5 x (S,S), (S,L) -- int16 [1][n], its shapes, its sample count"""
+    S, n_ss = 128, 16384 + 5
+    a = np.array([HOP] + [S] * (n_ss + 1), np.int64)
+    b = np.array([S] * (n_ss + 1) + [HOP], np.int64)
+    off = np.concatenate([[0], np.cumsum(a)[:-1]])
+    shapes = np.stack([off, a, b], axis=1)
+    hops = -(-int(off[-1] + a[-1] + b[-1]) // HOP)
+    return _clicks(hops, 11, True), shapes, int(b.sum())
+
+
+def test_second_batch_of_one_shape_equals_single_batch_slabs():
+    """Inside a slab the blocks of one shape are analysed 16384 at a time.  4096-block slabs: time slabs of one batch each,
+    the path of every other test; the default slab: one slab whose (S,S) group is a full batch and a batch of five."""
+    h = _handle()
+    pcm, shapes, ns = _long_short_run()
+    rates = (2.86, 8.0)
+    run = lambda: h.encode_chained_pac_target_nmr(pcm, None, [shapes], rates, 0.0, num_samples=[ns])
+    try:
+        h.set_option(6, 4096)
+        want = run()
+        h.set_option(6, 131072)
+        got = run()
+    finally:
+        h.set_option(6, 131072)
+    assert want[0]["n_blocks"] == len(shapes) + 1 and len(want[0]["data"]) > 0
+    _same(got, want)
+    assert got[0]["rate"] == want[0]["rate"]
+
+
 def _raw(h, c, rates, target, out_cap=None, num_samples=True, start=None, off=None, a=None, b=None):
     """the C entry point itself -> (rc, out, total, results...)"""
     from mrcaudiocodec_amd import _lib

@@ -262,6 +262,35 @@ def test_independent_of_slabs_batching_and_entry_point():
         assert not host[total:].any()
 
 
+def _long_short_run():
+    """one mono stream whose (S,S) blocks do not fit one batch of the source analysis (16384 blocks of one shape):
+    (L,S), 16384 + 5 x (S,S), (S,L) -- int16 [1][n], its shapes, its sample count"""
+    S, n_ss = 128, 16384 + 5
+    a = np.array([HOP] + [S] * (n_ss + 1), np.int64)
+    b = np.array([S] * (n_ss + 1) + [HOP], np.int64)
+    off = np.concatenate([[0], np.cumsum(a)[:-1]])
+    shapes = np.stack([off, a, b], axis=1)
+    hops = -(-int(off[-1] + a[-1] + b[-1]) // HOP)
+    return _clicks(hops, 11, True), shapes, int(b.sum())
+
+
+def test_second_batch_of_one_shape_equals_single_batch_slabs():
+    """Inside a slab the blocks of one shape are analysed 16384 at a time.  4096-block slabs: time slabs of one batch each,
+    the path of every other test; the default slab: one slab whose (S,S) group is a full batch and a batch of five."""
+    h = _handle()
+    pcm, shapes, ns = _long_short_run()
+    run = lambda: h.encode_vbr_nmr_pac(pcm, None, [shapes], -6.0, num_samples=[ns])[0]
+    try:
+        h.set_option(6, 4096)
+        want = run()
+        h.set_option(6, 131072)
+        got = run()
+    finally:
+        h.set_option(6, 131072)
+    assert want["n_blocks"] == len(shapes) + 1 and len(want["data"]) > 0
+    _same(got, want)
+
+
 def test_exact_spreading_mode():
     from mrcaudiocodec_amd import pacfile
     s = _stream("exact")

@@ -254,6 +254,32 @@ def test_decodes_to_the_same_pcm():
     assert a.shape == b.shape and a.shape[0] == 2 and np.array_equal(a, b)
 
 
+def test_second_batch_of_one_shape_equals_the_existing_call_in_single_batch_slabs():
+    """Inside a slab the blocks of one shape are recorded 16384 at a time.  One mono stream of (L,S), 16384 + 5 x (S,S), (S,L):
+    the search keeps it in one slab (the default capacity, less the record, still holds its 16391 blocks), so its (S,S) group
+    is a full batch and a batch of five; the existing call under 4096-block slabs runs single batches only."""
+    S, n_ss = 128, 16384 + 5
+    a = np.array([HOP] + [S] * (n_ss + 1), np.int64)
+    b = np.array([S] * (n_ss + 1) + [HOP], np.int64)
+    off = np.concatenate([[0], np.cumsum(a)[:-1]])
+    shapes = np.stack([off, a, b], axis=1)
+    pcm = _clicks(-(-int(off[-1] + a[-1] + b[-1]) // HOP), 11, True)
+    ns, db = int(b.sum()), -6.0
+    h = _handle()
+    try:
+        h.set_option(SLAB_OPT, 4096)
+        want = h.encode_vbr_nmr_pac(pcm, None, [shapes], db, num_samples=[ns])[0]
+    finally:
+        h.set_option(SLAB_OPT, SLAB_DEFAULT)
+    target = len(want["data"])
+    got = h.encode_vbr_size_pac(pcm, None, [shapes], [target], db, 1.0, 1, num_samples=[ns])[0]
+    assert got["met"] and (got["chosen"], got["chosen_db"], got["probes"]) == (0, db, 1)
+    assert got["probe_index"] == [0] and got["probe_bytes"] == [target]
+    assert got["data"] == want["data"] and got["n_blocks"] == len(shapes) + 1
+    for k in NUMBERS:
+        assert got[k] == want[k], (k, got[k], want[k])
+
+
 def _raw(s, target, lo=LO, step=STEP, n=N, out_cap=None, num_samples=True, off=None, a=None, b=None, no_target=False,
          trace=True):
     """the C entry point itself -> (rc, out, results)"""
