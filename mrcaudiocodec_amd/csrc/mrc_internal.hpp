@@ -38,6 +38,11 @@ struct DevShape {
     int winSymmetric;                // win[n] == win[N - 1 - n] bit for bit (true for a = b)
     const double* hann;              // [N] window.py:28-45
     const double2* pre;              // [Q] exp(-i pi (4n+1)/(4M)), M = N/2
+    // [halfN] zb, quiet, lowE and the band of a line side by side (smr_kernel's sweep).  Between two pointers that smr_kernel
+    // does not read: next to loLine / hiLine / linesPerHz the compiler fetched the four with one 32-byte scalar load for the masker
+    // table and kept -- and, at its scalar-register limit, reloaded from a spill lane in every chunk -- all eight registers for
+    // the sake of this one pointer.
+    const struct LineConstants* lineC;
     const double2* post;             // [Q] exp(-i pi k / M)
     const double2* wQ;               // [Q] exp(-2 pi i t/Q)
     const double2* wH;               // [H] exp(-2 pi i t/H)
@@ -49,7 +54,6 @@ struct DevShape {
     const int* bandLo;               // [nBands]
     const int* bandN;                // [nBands]
     const unsigned char* bandOfLine; // [halfN]
-    const struct LineConstants* lineC;  // [halfN] zb, quiet, lowE and the band of a line side by side (smr_kernel's sweep)
     const unsigned short* loLine;    // [halfN] first line j with zb[j] - zb[k] >= -1/2 (search hint)
     const unsigned short* hiLine;    // [halfN] first line j with zb[j] - zb[k] > 1/2, halfN if none (search hint)
     double linesPerHz;               // N / sampleRate

@@ -142,6 +142,8 @@ __device__ __forceinline__ void smr_body(DevShape S, int nsigArg, const SampleT*
             else if (n < H) A[n] = make_double2(e[u] * he[u], o[u] * ho[u]);
         }
     }
+    // (the unit's scale is first used in the sweep: requested here, it arrives under the wait for the samples)
+    const int scale = oscale[unit];
     const double xiInv = 1.0 / S.xiDen;
     // Constants that are only needed after the FFT are requested BEFORE it (their LDS homes are FFT scratch until
     // then): the loads complete under the FFT's barriers instead of adding a memory round trip of their own.
@@ -404,7 +406,6 @@ __device__ __forceinline__ void smr_body(DevShape S, int nsigArg, const SampleT*
     // psychoac.py:214-217: SMR of a band = max over its lines of (SPL of the line - masked threshold),
     // accumulated with LDS integer max-atomics on an order-preserving key (initialised by the table
     // build's barrier below)
-    const int scale = oscale[unit];
     const double* X = lines + (int64_t)unit * M;
 
     if (EXACT) {
@@ -450,6 +451,31 @@ __device__ __forceinline__ void smr_body(DevShape S, int nsigArg, const SampleT*
         double* sc = xi;                                 // xi is dead (all peak reads happened before the barrier)
         if (TAB != kExpTab) smem[4 * H + kTabLongOff + tid] = e2Pre;      // (NT = 256 = TAB: an entry per thread)
         const int waveU = __builtin_amdgcn_readfirstlane(wave);          // (uniform: chunk indices stay in SGPRs)
+        // The sweep (below) walks 64-line chunks; a wave's i-th chunk:
+        const int nChunks = (M + kWave - 1) / kWave;
+        const int nWaves = NT / kWave;
+        // the per-line constants of the NEXT chunk are loaded while this one is computed (loop-carried, so the
+        // global-load latency is never exposed between the loops of a chunk)
+        struct LineConst { double z, quiet, lowE, x; int bnd; };
+        auto chunk_of = [&](int i) { return i * nWaves + ((i & 1) ? (nWaves - 1 - waveU) : waveU); };
+        auto load_consts = [&](int i) {
+            // (byte offsets as 32-bit unsigned values: scalar base + vector offset addressing, no 64-bit address arithmetic)
+            const unsigned kc = (unsigned)min(chunk_of(i) * kWave + lane, M - 1);
+            const char* lc = reinterpret_cast<const char*>(S.lineC) + kc * (unsigned)sizeof(LineConstants);
+            const double2 a = *reinterpret_cast<const double2*>(lc);
+            // (lowE and the band, not the entry's padding: a register that is loaded and never read is free for the next
+            // value at once, and whoever gets it first has to wait for this load -- in the loop that issued it as a prefetch)
+            const double lowE = *reinterpret_cast<const double*>(lc + 16);
+            const int bnd = *reinterpret_cast<const int*>(lc + 24);
+            const double x = *reinterpret_cast<const double*>(reinterpret_cast<const char*>(X) + kc * 8u);
+            return LineConst{a.x, a.y, lowE, x, bnd};
+        };
+        // ... and those of the wave's FIRST chunk here, two barriers ahead of the sweep: the MDCT lines were written by the
+        // kernel before this one and come from HBM, a round trip that the node terms and the scans cover.  (Long blocks: the
+        // other shapes are short of registers or of a phase long enough to hide it in.)
+        constexpr bool kFirstEarly = LONG && NT == 256;
+        [[maybe_unused]] LineConst first{};
+        if constexpr (kFirstEarly) first = load_consts(0);
         // ---- which evaluation of the upper-side sum the frame takes (wave-uniform): slope nodes (see kNodeR) when its
         // maskers are many and their slopes lie within reach of R nodes, else the sorted sweep.  Long blocks only.
         constexpr bool kNodes = (DIM == 1024 || DIM == 576) && NT == 256;      // (576: 156 of a transition block's <= 237 maskers)
@@ -691,21 +717,6 @@ __device__ __forceinline__ void smr_body(DevShape S, int nsigArg, const SampleT*
         // split into [0, nUp): more than 1/2 Bark below the line (upper slope, needs 2^x),
         // [nUp, cnt): within +-1/2 Bark (contributes exactly I_m), [cnt, P): more than 1/2 Bark above
         // (lower slope, served by the suffix sums).
-        const int nChunks = (M + kWave - 1) / kWave;
-        const int nWaves = NT / kWave;
-        // the per-line constants of the NEXT chunk are loaded while this one is computed (loop-carried, so the
-        // global-load latency is never exposed between the loops of a chunk)
-        struct LineConst { double z, quiet, lowE, x; int bnd; };
-        auto chunk_of = [&](int i) { return i * nWaves + ((i & 1) ? (nWaves - 1 - waveU) : waveU); };
-        auto load_consts = [&](int i) {
-            // (byte offsets as 32-bit unsigned values: scalar base + vector offset addressing, no 64-bit address arithmetic)
-            const unsigned kc = (unsigned)min(chunk_of(i) * kWave + lane, M - 1);
-            const char* lc = reinterpret_cast<const char*>(S.lineC) + kc * (unsigned)sizeof(LineConstants);
-            const double2 a = *reinterpret_cast<const double2*>(lc);
-            const double2 b = *reinterpret_cast<const double2*>(lc + 16);
-            const double x = *reinterpret_cast<const double*>(reinterpret_cast<const char*>(X) + kc * 8u);
-            return LineConst{a.x, a.y, b.x, x, __double2loint(b.y)};
-        };
         // in-band maskers [from, cnt) and the lower side on top of `tot` (quiet threshold + upper side): the line's masked intensity
         auto tail_sum = [&](double tot, int cnt, int from, double lowE) {
             if (cnt > from) {
@@ -796,13 +807,13 @@ __device__ __forceinline__ void smr_body(DevShape S, int nsigArg, const SampleT*
                 return NodeEval{tail_sum(cur.quiet + up, cnt, nUp, cur.lowE), errBound, cnt, nUp};
             };
             unsigned setAside = 0;                       // (wave-uniform)
-            LineConst nxt = load_consts(0);
+            LineConst nxt = kFirstEarly ? first : load_consts(0);
             for (int i = 0; chunk_of(i) < nChunks; ++i) {
                 const int k = chunk_of(i) * kWave + lane;
                 const LineConst cur = nxt;
                 nxt = load_consts(i + 1);
                 if (haveSwitch && !__any(needBand[cur.bnd])) continue;                           // (see needBand)
-                MRC_PHASE(6);
+                MRC_PHASE(i == 0 ? 25 : 6);                     // (25: the wave's first chunk -- its loads are `first`, not the loop's prefetch)
                 const NodeEval ev = node_chunk(cur, min(k, M - 1));
                 MRC_PHASE(8);
                 const bool odd = !(ev.bound <= kNodeTol * ev.t) || line_plain(line_a2(cur), ev.t);
@@ -860,7 +871,7 @@ __device__ __forceinline__ void smr_body(DevShape S, int nsigArg, const SampleT*
         MRC_PHASE(7);
         // ---- pass 2
         __builtin_amdgcn_s_setprio(0);
-        LineConst nxt = load_consts(i0);
+        LineConst nxt = (kFirstEarly && i0 == 0) ? first : load_consts(i0);
         for (int u = 0; u < 4; ++u) {
             const int i = i0 + u;
             const int c = chunk_of(i);

@@ -16,7 +16,7 @@ for l in sys.stdin:
     cur[k] = v
     if k.startswith("LDS Size"):
         d = subprocess.run(["c++filt", cur["name"]], capture_output=True, text=True).stdout.strip()
-        d = re.sub(r"\(.*", "", d).replace("mrc::(anonymous namespace)::", "").replace("void ", "")
-        print("%-52s VGPR %3s AGPR %3s spill %3s scratch %5s occ %s LDS %6s" % (
-            d[:52], cur.get("VGPRs"), cur.get("AGPRs"), cur.get("VGPRs Spill"), cur.get("ScratchSize [bytes/lane]"),
-            cur.get("Occupancy [waves/SIMD]"), v))
+        d = re.sub(r"\(.*", "", d.replace("mrc::(anonymous namespace)::", "").replace("void ", ""))
+        print("%-52s VGPR %3s AGPR %3s spill %3s SGPR %3s spill %3s scratch %5s occ %s LDS %6s" % (
+            d[:52], cur.get("VGPRs"), cur.get("AGPRs"), cur.get("VGPRs Spill"), cur.get("TotalSGPRs"), cur.get("SGPRs Spill"),
+            cur.get("ScratchSize [bytes/lane]"), cur.get("Occupancy [waves/SIMD]"), v))

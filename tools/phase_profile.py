@@ -23,7 +23,8 @@ NAMES = ["0 samples + Hann (wait for the loads)", "1 fft", "2 real split -> barr
          "12 masker table -> barrier", "13 decision (slope range, node spacing)", "14 node terms", "15 node terms -> barrier",
          "16 prologue (arguments, unit, keys)", "17 peak flags + count", "18 counts -> barrier", "19 compaction + histogram zeroing",
          "20 real split + intensity", "21 masker: peak bin + its three intensities", "22 masker: level, frequency, Bark, intensity, constants",
-         "23 masker: search hints (global)", "24 masker: the two walks + histogram"] + ["-"] * 7
+         "23 masker: search hints (global)", "24 masker: the two walks + histogram",
+         "25 chunk set-up, first chunk of a wave (node frames)"] + ["-"] * 6
 
 F = int(sys.argv[1]) if len(sys.argv) > 1 else 16384
 dev = torch.device("cuda", 0)
