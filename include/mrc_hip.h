@@ -614,7 +614,10 @@ int mrc_get_vbr_size_ms(mrc_handle* h, double* ms /*[5]*/);
  *   MRC_SENS_MS        bands whose M/S test is within 1e-12 (relative) of its 0.8 threshold (ms_stereo.py:5-27)
  *   MRC_SENS_PEAK      spectral bins within 1e-11 (relative) of a neighbour they have to beat strictly (psychoac.py:162)
  *   MRC_SENS_NODES     64-line chunks the slope-node evaluation of the masking sum sent back to the sorted sweep (its error
- *                      bound exceeded 1e-13 of a line's masked intensity) -- informational: the result is then the sweep's
+ *                      bound exceeded 1e-13 of a line's masked intensity) -- informational: the result is then the sweep's.
+ *                      Mono long blocks evaluate only the lines that can be their band's maximum: there a chunk is sent
+ *                      back, and counted, when the bound fails on one of THOSE lines -- or on any line of a chunk that is
+ *                      evaluated whole (a line at the SPL floor; a wave with more than 64 such lines)
  *   MRC_SENS_FRAMES    blocks examined
  * A call whose first four counts are zero took no decision near an edge.  Not counted: the overall scale (a 20-bit code of
  * the block peak), the transient detector's threshold tests.  Waits for the whole device (hipDeviceSynchronize), so that

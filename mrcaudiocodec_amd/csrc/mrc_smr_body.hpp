@@ -458,9 +458,8 @@ __device__ __forceinline__ void smr_body(DevShape S, int nsigArg, const SampleT*
         // global-load latency is never exposed between the loops of a chunk)
         struct LineConst { double z, quiet, lowE, x; int bnd; };
         auto chunk_of = [&](int i) { return i * nWaves + ((i & 1) ? (nWaves - 1 - waveU) : waveU); };
-        auto load_consts = [&](int i) {
+        auto load_line = [&](unsigned kc) {               // the constants of line kc < M
             // (byte offsets as 32-bit unsigned values: scalar base + vector offset addressing, no 64-bit address arithmetic)
-            const unsigned kc = (unsigned)min(chunk_of(i) * kWave + lane, M - 1);
             const char* lc = reinterpret_cast<const char*>(S.lineC) + kc * (unsigned)sizeof(LineConstants);
             const double2 a = *reinterpret_cast<const double2*>(lc);
             // (lowE and the band, not the entry's padding: a register that is loaded and never read is free for the next
@@ -470,6 +469,20 @@ __device__ __forceinline__ void smr_body(DevShape S, int nsigArg, const SampleT*
             const double x = *reinterpret_cast<const double*>(reinterpret_cast<const char*>(X) + kc * 8u);
             return LineConst{a.x, a.y, lowE, x, bnd};
         };
+        auto load_consts = [&](int i) { return load_line((unsigned)min(chunk_of(i) * kWave + lane, M - 1)); };
+        // ---- band contenders (mono long blocks through the slope nodes; see the sweep): per wave, a lower bound of every
+        // band's best ratio among the wave's lines, and the lines that can still reach it.  Both sit in the spectrum area
+        // behind the 2^(j/256) table: the spectrum is dead with the barrier above, sc takes < kTabLongOff doubles.
+        constexpr bool kContend = LONG && NT == 256 && !EXACT && MODE == 1;
+        constexpr int kContCap = kWave;                 // contenders a wave evaluates: one gathered chunk
+        constexpr int kContLbOff = kTabLongOff + kExpTabLong, kContIdxOff = kContLbOff + (NT / kWave) * kMaxBands;
+        static_assert(!kContend || kContIdxOff + (NT / kWave) * kContCap / 4 <= DIM - 100 + 1, "contender areas: inside the spectrum");
+        [[maybe_unused]] unsigned long long* const lbKey =
+            reinterpret_cast<unsigned long long*>(smem + 4 * H + kContLbOff) + wave * kMaxBands;
+        [[maybe_unused]] unsigned short* const contIdx =
+            reinterpret_cast<unsigned short*>(smem + 4 * H + kContIdxOff) + wave * kContCap;
+        if constexpr (kContend)
+            if (lane < kMaxBands) lbKey[lane] = 0ull;    // (the wave's own: read and written by nobody else, no barrier)
         // ... and those of the wave's FIRST chunk here, two barriers ahead of the sweep: the MDCT lines were written by the
         // kernel before this one and come from HBM, a round trip that the node terms and the scans cover.  (Long blocks: the
         // other shapes are short of registers or of a phase long enough to hide it in.)
@@ -808,6 +821,88 @@ __device__ __forceinline__ void smr_body(DevShape S, int nsigArg, const SampleT*
             };
             unsigned setAside = 0;                       // (wave-uniform)
             LineConst nxt = kFirstEarly ? first : load_consts(0);
+            if constexpr (kContend) {
+                // ---- band contenders.  A band's SMR is the maximum of a2 / t over its lines, and t = quiet + in-band + lower
+                // side + upper side with every term positive.  What tail_sum adds to the quiet threshold alone is a lower
+                // bound t_lb of t; with E0 times the row's column R + 1 (sum of Lambda_m I_m 2^(-sigma_0 z_m), Lambda_m >= 1,
+                // sigma_0 >= every slope, over at least the maskers below the line) on top it is an upper bound t_ub.  The wave
+                // takes, per band, L = max of a2 / t_ub over ITS lines -- a ratio one of them reaches in the evaluation -- and
+                // evaluates only the lines with a2 >= L t_lb, gathered into one chunk.  The margins (1 - 2^-30, twice) cover
+                // the roundings of either bound, of recip_nr and the node tolerance: a line left out is strictly below a line
+                // that is evaluated, by the same arithmetic as before, so the integer maxima end as they did.
+                // Chunks with a line near the SPL floor go through the set-aside path whole, as before; so does the original
+                // chunk of a contender whose error bound fails, and all four when the contenders do not fit.
+                constexpr double kShrink = 1.0 - 0x1p-30, kFloorHi = kSplFloorGuard * (1.0 + 0x1p-30);
+                static_assert(NT / kWave == 4 && DIM / kWave == 16, "a wave's chunks: four, the i-th in lines [256 i, 256 i + 256)");
+                double a2s[4], tlb[4];
+                int bnds[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int k = chunk_of(i) * kWave + lane;
+                    const LineConst cur = nxt;
+                    if (i < 3) nxt = load_consts(i + 1);
+                    MRC_PHASE(i == 0 ? 25 : 6);
+                    const int cnt = cntArr[k], nUp = nUpArr[k];
+                    const double a2 = line_a2(cur);
+                    const double tl = tail_sum(cur.quiet, cnt, nUp, cur.lowE);
+                    const int bnd = cur.bnd;
+                    const bool oneBand = __all(bnd == __builtin_amdgcn_readfirstlane(bnd));
+                    const bool rowHead = (lane & 15) == 0;
+                    const bool whole = __any(!(a2 >= kFloorHi && tl >= kFloorHi));
+                    a2s[i] = a2; tlb[i] = tl; bnds[i] = bnd;
+                    double lb = 0.0;
+                    if (whole) setAside |= 1u << i;
+                    else {
+                        const double E0 = exp2_tab64<TAB>(nodeS0, cur.z - 0.5, e2tab);
+                        const double tub = fma(E0, nodeQ[((nUp + kNodeC - 1) >> 2) * kNodeCols + kNodeR + 1], tl);
+                        lb = (a2 * recip_nr(tub)) * kShrink;
+                    }
+                    // (every line's |X| goes into the band peaks here; the band's bound from the lines of this chunk)
+                    if (oneBand) {
+                        const double pk = row_max(fabs(cur.x));
+                        if (rowHead) atomicMax(&peakKey[bnd], (unsigned long long)__double_as_longlong(pk));
+                        if (!whole) {
+                            const double best = row_max(lb);
+                            if (rowHead) atomicMax(&lbKey[bnd], (unsigned long long)__double_as_longlong(best));
+                        }
+                    } else {
+                        atomicMax(&peakKey[bnd], (unsigned long long)__double_as_longlong(fabs(cur.x)));
+                        if (!whole) atomicMax(&lbKey[bnd], (unsigned long long)__double_as_longlong(lb));
+                    }
+                    MRC_PHASE(8);
+                }
+                // (the wave's lanes read what other lanes of it wrote, here and below: ordered within the wavefront)
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                int nCont = 0;                           // (wave-uniform)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    if ((setAside >> i) & 1u) continue;
+                    const double L = __longlong_as_double((long long)lbKey[bnds[i]]);
+                    const bool in = !(a2s[i] < (L * tlb[i]) * kShrink);
+                    const unsigned long long m = __ballot(in);
+                    const int pos = nCont + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+                    if (in && pos < kContCap) contIdx[pos] = (unsigned short)(chunk_of(i) * kWave + lane);
+                    nCont += __popcll(m);
+                }
+                if (nCont > kContCap) { setAside = 0xFu; nCont = 0; }
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                if (nCont > 0) {
+                    const int k = contIdx[min(lane, nCont - 1)];       // (lanes past the end repeat the last one: maxima unchanged)
+                    const LineConst cur = load_line((unsigned)k);
+                    const NodeEval ev = node_chunk(cur, k);
+                    const bool bad = !(ev.bound <= kNodeTol * ev.t);
+                    if (__any(bad)) {                     // (rare) the contender's own chunk goes to the sorted sweep: none of
+#pragma unroll                                            // its lines counts here
+                        for (int i = 0; i < 4; ++i)
+                            if (__any(bad && (k >> 8) == i)) setAside |= 1u << i;
+                    }
+                    MRC_NODE_COUNT(2);
+                    const bool live = !((setAside >> (k >> 8)) & 1u);
+                    const double q = live ? line_ratio(line_a2(cur), ev.t) : 0.0;
+                    atomicMax(&ratioKey[cur.bnd], (unsigned long long)__double_as_longlong(q));
+                    MRC_PHASE(10);
+                }
+            } else
             for (int i = 0; chunk_of(i) < nChunks; ++i) {
                 const int k = chunk_of(i) * kWave + lane;
                 const LineConst cur = nxt;
