@@ -29,15 +29,12 @@ int get_shape(mrc_handle* h, int a, int b, const HostShape** out) {
         // is refused here rather than at its first launch.  (smr_kernel's layout is the largest for every shape that gets
         // near the limit; the packer's per-chunk buffers and the bit allocation's stay below it.)  smr_kernel also scans
         // a block's peaks in a fixed number of slots: at most (N/2 - 101) / 2 peaks, N/2 <= 1123 lines.
-        if (!smr_peaks_fit(hs.dev)) {
-            free_shape(&hs);
+        if (!smr_peaks_fit(hs.dev))
             return fail(h, MRC_ERR_INVALID, "block shape too long for the masking model's peak scan (N/2 <= 1123 lines)");
-        }
         int ldsMax = 0;
         MRC_HIP(h, hipDeviceGetAttribute(&ldsMax, hipDeviceAttributeMaxSharedMemoryPerBlock, h->device));
         const size_t need = std::max(smr_generic_lds_bytes(hs.dev), mdct_generic_lds_bytes(hs.dev));
         if (need > (size_t)ldsMax) {
-            free_shape(&hs);
             char msg[160];
             std::snprintf(msg, sizeof msg, "block shape (%d,%d) needs %zu bytes of LDS per workgroup, the device allows %d",
                           a, b, need, ldsMax);
@@ -94,11 +91,11 @@ int mrc_create(const mrc_config* cfg, mrc_handle** out) {
     if (!h) return fail(nullptr, MRC_ERR_NOMEM, "mrc_create: out of host memory");
     h->cfg = *cfg;
     h->device = cfg->device_id;
-    if ((e = hipSetDevice(h->device)) != hipSuccess || (e = hipStreamCreate(&h->stream)) != hipSuccess) {
+    if ((e = hipSetDevice(h->device)) != hipSuccess || (e = h->stream.create()) != hipSuccess) {
         delete h;
         return hip_fail(nullptr, e, "hipSetDevice/hipStreamCreate");
     }
-    for (auto& ev : h->ev) (void)hipEventCreate(&ev);
+    (void)h->ev.create();
     // the four shapes of the reference's block switching (pacfileThem.py:1192-1210)
     const int L = cfg->n_mdct_lines, Sh = cfg->n_short;
     const int shapes[4][2] = {{L, L}, {Sh, Sh}, {L, Sh}, {Sh, L}};
@@ -113,28 +110,6 @@ int mrc_create(const mrc_config* cfg, mrc_handle** out) {
 
 void mrc_destroy(mrc_handle* h) {
     if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (auto& kv : h->shapes) free_shape(&kv.second);
-    for (hipStream_t* st : {&h->stIn, &h->stOut}) {
-        if (*st) { (void)hipStreamSynchronize(*st); (void)hipStreamDestroy(*st); }
-        *st = nullptr;
-    }
-    for (auto& lane : h->lanes) lane.release();
-    h->wsPipe.release();
-    h->packWs.release();
-    h->chain.release();
-    h->dec.release();
-    h->nmr.release();
-    h->target.release();
-    h->vbr.release();
-    h->ws.release();
-    for (DevBuf& b : h->stage) b.release();
-    h->smallBatch.release();
-    h->sos.release();
-    h->sens.release();
-    for (auto& ev : h->ev) if (ev) (void)hipEventDestroy(ev);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
 
@@ -285,7 +260,7 @@ int mrc_dev_alloc_quant(mrc_handle* h, int a, int b, int64_t n_frames, int joint
     MRC_HIP(h, h->ws.peak.reserve(alloc_workspace_bytes(hs->dev, n_frames, joint)));
     MRC_HIP(h, launch_alloc_quant(hs->dev, n_frames, joint, lines, overall_scale, smr, reservoir_in, ms_switch,
                                   bit_alloc, scale_factor, mantissa, MRC_MANTISSA_I32, reservoir_out,
-                                  h->ws.peak.as<double>(), false, false, nullptr, pick_stream(h, stream)));
+                                  h->ws.peak.as<double>(), false, false, nullptr, nullptr, pick_stream(h, stream)));
     return MRC_OK;
 }
 
@@ -428,11 +403,7 @@ namespace {
 // (few blocks: the scan kernel) | 5; reported order (mrc_get_kernel_ms): mdct, smr, ms_switch, bitalloc, quantize
 int collect_kernel_ms(mrc_handle* h) {
     static const int from[5] = {0, 2, 1, 3, 4}, to[5] = {1, 3, 2, 4, 5};
-    for (int i = 0; i < 5; ++i) {
-        float ms = 0.f;
-        MRC_HIP(h, hipEventElapsedTime(&ms, h->ev[from[i]], h->ev[to[i]]));
-        h->kernelMs[i] = ms;
-    }
+    for (int i = 0; i < 5; ++i) MRC_HIP(h, h->ev.elapsed(from[i], to[i], &h->kernelMs[i]));
     h->stageMs[0] = h->kernelMs[0];
     h->stageMs[1] = h->kernelMs[1];
     h->stageMs[2] = h->kernelMs[2] + h->kernelMs[3] + h->kernelMs[4];
@@ -460,7 +431,8 @@ int encode_core(mrc_handle* h, const DevShape& S, int64_t n, const void* chL, co
     MRC_TRY(encode_phase_a(h, S, n, chL, chR, fmt, stride, offsets, lines, oscale, msSwitch, smr, ws.peak.as<double>(), st,
                            timing));
     MRC_HIP(h, launch_alloc_quant(S, n, joint, lines, oscale, smr, resIn, msSwitch, bitAlloc, scaleFactor, mantissa,
-                                  mantFmt, resOut, ws.peak.as<double>(), true, true, timing ? &h->ev[3] : nullptr, st));
+                                  mantFmt, resOut, ws.peak.as<double>(), true, true, timing ? h->ev[3] : nullptr,
+                                  timing ? h->ev[4] : nullptr, st));
     if (h->sensOn)                                       // (after the timed kernels; outside their events)
         MRC_HIP(h, launch_sensitivity(S, n, joint, lines, oscale, smr, ws.peak.as<double>(), msSwitch, bitAlloc, scaleFactor,
                                       h->sens.as<unsigned long long>(), nullptr, st));
@@ -577,13 +549,11 @@ int encode_pcm16_chunks(mrc_handle* h, const DevShape& S, int64_t n_frames, cons
         for (chunk = 32768; chunk > 8192 && n_frames < 6 * chunk;) chunk /= 2;
     if (chunk > n_frames) chunk = n_frames;
     // streams, events and chunk buffers: created on first use, buffers sized for one chunk (+ the one-hop halo in front)
-    for (hipStream_t* st : {&h->stIn, &h->stOut})
-        if (!*st) MRC_HIP(h, hipStreamCreateWithFlags(st, hipStreamNonBlocking));
+    for (Stream* st : {&h->stIn, &h->stOut}) MRC_HIP(h, st->create(hipStreamNonBlocking));
     const hipStream_t stK = h->stream;
     const size_t szPcm = (size_t)(chunk + 1) * L * sizeof(int16_t);
     for (auto& lane : h->lanes) {
-        for (hipEvent_t* e : {&lane.evIn, &lane.evK, &lane.evOut})
-            if (!*e) MRC_HIP(h, hipEventCreateWithFlags(e, hipEventDisableTiming));
+        for (Event* e : {&lane.evIn, &lane.evK, &lane.evOut}) MRC_HIP(h, e->create(hipEventDisableTiming));
         MRC_HIP(h, lane.pcmL.reserve(szPcm));
         if (joint) MRC_HIP(h, lane.pcmR.reserve(szPcm));
         MRC_HIP(h, lane.resIn.reserve((size_t)chunk * sizeof(int32_t)));
@@ -639,7 +609,7 @@ int encode_pcm16_chunks(mrc_handle* h, const DevShape& S, int64_t n_frames, cons
     }
     h->timing = wasTiming;
     if (rc != MRC_OK) return rc;
-    for (hipStream_t st : {h->stIn, stK, h->stOut}) MRC_HIP(h, hipStreamSynchronize(st));
+    for (hipStream_t st : drain.st) MRC_HIP(h, hipStreamSynchronize(st));
     return MRC_OK;
 }
 
@@ -858,7 +828,7 @@ int mrc_encode_stream_pcm16_pac(mrc_handle* h, int64_t n_frames, const int16_t* 
             base.assign((size_t)((n_frames + chunk - 1) / chunk) + 1, 0);
             for (auto& lane : h->lanes) {
                 if (!lane.pacTotal) {
-                    MRC_HIP(h, hipHostMalloc(reinterpret_cast<void**>(&lane.pacTotal), 2 * sizeof(long long), hipHostMallocDefault));
+                    MRC_HIP(h, pinned_alloc(&lane.pacTotal, 2 * sizeof(long long)));
                     lane.pacTotal[0] = lane.pacTotal[1] = 0;
                 }
                 MRC_HIP(h, lane.pacBytes.reserve(pacCap));
@@ -875,7 +845,7 @@ int mrc_encode_stream_pcm16_pac(mrc_handle* h, int64_t n_frames, const int16_t* 
                                    lane.pacTable.as<int32_t>(), lane.pacSaved.as<int32_t>(), lane.pacBytes.as<unsigned char>(),
                                    (long long)pacCap, lane.pacOffs.as<long long>(), h->packWs.p, (int)(bound - 4),
                                    all_bands_non_empty(*hs), h->stream));
-            MRC_HIP(h, launch_pack_export(h->packWs.p, n * nch, lane.pacTotal, h->stream));   // 16 bytes, written by a kernel: no copy command
+            MRC_HIP(h, launch_pack_export(h->packWs.p, n * nch, lane.pacTotal.get(), h->stream));   // 16 bytes, written by a kernel: no copy command
             return MRC_OK;
         },
         // copies chunk c's packed form out, once its size is known

@@ -259,7 +259,7 @@ int chained_core(mrc_handle* h, const ChainCall& c, uint8_t* out, int64_t out_ca
     MRC_HIP(h, hipSetDevice(h->device));
     hipStream_t st = pick_stream(h, c.stream);
     ChainBufs& C = h->chain;
-    for (auto& e : C.evT) if (!e) MRC_HIP(h, hipEventCreate(&e));
+    MRC_HIP(h, C.evT.create());
     DrainGuard guard{{st}};                              // (declared behind q and desc: they outlive every queued copy)
     MRC_HIP(h, hipEventRecord(C.evT[0], st));
     if (c.with_flush) {
@@ -396,11 +396,8 @@ int chained_core(mrc_handle* h, const ChainCall& c, uint8_t* out, int64_t out_ca
     if (c.reservoir_trace)
         MRC_HIP(h, hipMemcpyAsync(c.reservoir_trace, C.resTrace.p, (size_t)(R * nItems) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     MRC_HIP(h, hipStreamSynchronize(st));
-    for (int i = 0; i < 4; ++i) {                        // phase A + prep | scan | pack | all three
-        float ms = 0.f;
-        MRC_HIP(h, hipEventElapsedTime(&ms, C.evT[i < 3 ? i : 0], C.evT[i < 3 ? i + 1 : 3]));
-        h->chainMs[i] = ms;
-    }
+    for (int i = 0; i < 4; ++i)                          // phase A + prep | scan | pack | all three
+        MRC_HIP(h, C.evT.elapsed(i < 3 ? i : 0, i < 3 ? i + 1 : 3, &h->chainMs[i]));
     if (c.measure) MRC_TRY(c.measure->read_events(h));
     chain_results(c, q, rate_base);
     if (q.bad & 3) return fail(h, MRC_ERR_INVALID, "mrc_encode_chained: internal error (table id / chunk size out of range)");

@@ -103,7 +103,7 @@ int source_analysis(mrc_handle* h, const ChainCall& c, ChainMeasure& N, const Ch
 // The streams sl.s0 .. sl.s0 + sl.ns - 1 have all their entries in stat, `rungs` rows of N.unitChunks: pseudo-file (r, s) is
 // the entries [r * unitChunks + first chunk of s, ...) in file order.  -> start [ns + 1]: the first chunk of every stream
 // inside a row; fileOut [rungs * ns][4]: nmr_file_kernel's sums.  ev (if any): recorded around the kernel.  Synchronises.
-int reduce_files(mrc_handle* h, const ChainCall& c, const ChainMeasure& N, const Slab& sl, int rungs, const hipEvent_t* ev,
+int reduce_files(mrc_handle* h, const ChainCall& c, const ChainMeasure& N, const Slab& sl, int rungs, const Event* ev,
                  hipStream_t st, std::vector<long long>* start, std::vector<double>* fileOut) {
     TargetBufs& T = h->target;
     const int64_t ns = sl.ns, nFiles = rungs * ns;
@@ -200,8 +200,8 @@ struct TargetMeasure : ChainMeasure {
         return MRC_OK;
     }
     int read_events(mrc_handle* h) override {
-        float ms = 0.f;
-        MRC_HIP(h, hipEventElapsedTime(&ms, h->target.ev[0], h->target.ev[1]));
+        double ms = 0;
+        MRC_HIP(h, h->target.ev.elapsed(0, 1, &ms));
         msMeasure += ms;
         return MRC_OK;
     }
@@ -215,9 +215,8 @@ int grow_kept(mrc_handle* h, DevBuf& b, int64_t used, int64_t need, hipStream_t 
     hipError_t e = hipSuccess;
     if (used) e = hipMemcpyAsync(bigger.p, b.p, (size_t)used, hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { bigger.release(); return hip_fail(h, e, "mrc_encode_chained_target_nmr_pac: growing a device buffer"); }
-    b.release();
-    b = bigger;
+    if (e != hipSuccess) return hip_fail(h, e, "mrc_encode_chained_target_nmr_pac: growing a device buffer");
+    b = std::move(bigger);                               // (which leaves with b's old allocation and frees it)
     return MRC_OK;
 }
 
@@ -237,7 +236,7 @@ int target_decide(mrc_handle* h, const ChainCall& c, TargetMeasure& N, const Tar
     const int64_t nS = c.n_streams, ns = sl.ns;
     std::vector<long long> start, span((size_t)ns * 3);
     std::vector<double> fileOut;
-    MRC_TRY(reduce_files(h, c, N, sl, R, T.ev + 2, st, &start, &fileOut));
+    MRC_TRY(reduce_files(h, c, N, sl, R, &T.ev.ev[2], st, &start, &fileOut));
     // ---- the rule
     int64_t maxLen = 0, selNeed = 0;
     for (int64_t s = 0; s < ns; ++s) {
@@ -285,9 +284,9 @@ int target_decide(mrc_handle* h, const ChainCall& c, TargetMeasure& N, const Tar
     MRC_HIP(h, hipEventRecord(T.ev[5], st));
     MRC_HIP(h, hipStreamSynchronize(st));
     N.selUsed += selNeed;
-    float a = 0.f, b = 0.f;
-    MRC_HIP(h, hipEventElapsedTime(&a, T.ev[2], T.ev[3]));
-    MRC_HIP(h, hipEventElapsedTime(&b, T.ev[4], T.ev[5]));
+    double a = 0, b = 0;
+    MRC_HIP(h, T.ev.elapsed(2, 3, &a));
+    MRC_HIP(h, T.ev.elapsed(4, 5, &b));
     N.msMeasure += a;
     N.msGather += b;
     return MRC_OK;
@@ -322,7 +321,7 @@ int target_call(mrc_handle* h, const std::string& w, ChainCall c, const TargetOu
     const int64_t nS = c.n_streams;
     ChainBufs& C = h->chain;
     TargetBufs& T = h->target;
-    for (auto& e : T.ev) if (!e) MRC_HIP(h, hipEventCreate(&e));
+    MRC_HIP(h, T.ev.create());
     TargetMeasure N;
     N.blockStart = c.block_start;
     std::vector<int64_t> sOff((size_t)R * (nS + 1)), totals((size_t)R), caps((size_t)R, std::numeric_limits<int64_t>::max() / 4);
@@ -474,13 +473,13 @@ int VbrMeasure::in_place_of_scan(mrc_handle* h, const ChainCall& c, const ChainS
     size_t launches = 0;
     for (int g = 0; g < q.nGroups; ++g) launches += (size_t)((count[g] + kTargetBatch - 1) / kTargetBatch);
     while (V.ev.size() < 2 * launches) {
-        hipEvent_t e = nullptr;
-        MRC_HIP(h, hipEventCreate(&e));
-        V.ev.push_back(e);
+        Event e;
+        MRC_HIP(h, e.create());
+        V.ev.push_back(std::move(e));
     }
     V.evUsed = 0;
     if (size) {                                          // the record of every block of the slab, group by group
-        for (auto& e : V.evSize) if (!e) MRC_HIP(h, hipEventCreate(&e));
+        MRC_HIP(h, V.evSize.create());
         for (int g = 0; g < q.nGroups; ++g) {
             const int joint = (g == 4 || nch == 1) ? 0 : 1;
             MRC_HIP(h, V.prof[g].reserve(std::max<size_t>((size_t)count[g] * vbr_profile_bytes(q.hs[g]->dev, joint), 256)));
@@ -510,14 +509,14 @@ int VbrMeasure::in_place_of_scan(mrc_handle* h, const ChainCall& c, const ChainS
 int VbrMeasure::read_events(mrc_handle* h) {
     VbrBufs& V = h->vbr;
     for (size_t i = 0; i + 1 < V.evUsed; i += 2) {
-        float ms = 0.f;
-        MRC_HIP(h, hipEventElapsedTime(&ms, V.ev[i], V.ev[i + 1]));
+        double ms = 0;
+        MRC_HIP(h, V.ev[i].ms_until(V.ev[i + 1], &ms));
         msMeasure += ms;
     }
     if (size) {
-        float a = 0.f, b = 0.f;
-        MRC_HIP(h, hipEventElapsedTime(&a, V.evSize[0], V.evSize[1]));
-        MRC_HIP(h, hipEventElapsedTime(&b, V.evSize[1], V.evSize[2]));
+        double a = 0, b = 0;
+        MRC_HIP(h, V.evSize.elapsed(0, 1, &a));
+        MRC_HIP(h, V.evSize.elapsed(1, 2, &b));
         msProbe += a;
         msPick += b;
     }

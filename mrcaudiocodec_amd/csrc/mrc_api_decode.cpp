@@ -67,9 +67,8 @@ int ensure_decode_consts(mrc_handle* h) {
     MRC_HIP(h, d.consts.reserve(bytes));
     MRC_HIP(h, hipMemcpy(d.consts.p, blob.data(), bytes, hipMemcpyHostToDevice));
     for (int s = 0; s < 4; ++s) d.bands.bandN[s] = (const int*)(d.consts.as<unsigned char>() + bandOff[s]);
-    if (!d.pinErr) MRC_HIP(h, hipHostMalloc((void**)&d.pinErr, sizeof(UnpackErr), hipHostMallocDefault));
-    for (auto& e : d.ev)
-        if (!e) MRC_HIP(h, hipEventCreate(&e));
+    if (!d.pinErr) MRC_HIP(h, pinned_alloc(&d.pinErr, sizeof(UnpackErr)));
+    MRC_HIP(h, d.ev.create());
     return MRC_OK;
 }
 
@@ -239,7 +238,7 @@ int mrc_dev_unpack_blocks(mrc_handle* h, int64_t n_blocks, int n_channels, int j
     UnpackFixedOut O{a, b, huff_table, overall_scale, ms_switch, scale_factor, bit_alloc, mantissa};
     MRC_HIP(h, launch_unpack_fixed(unpack_params(c), h->dec.bands, h->dec.consts.as<UnpackTables>(), n_blocks, n_channels,
                                    joint ? 1 : 0, buf, len, chunk_offset, O, h->dec.err.as<UnpackErr>(), st));
-    MRC_HIP(h, hipMemcpyAsync(h->dec.pinErr, h->dec.err.p, sizeof(UnpackErr), hipMemcpyDeviceToHost, st));
+    MRC_HIP(h, hipMemcpyAsync(h->dec.pinErr.get(), h->dec.err.p, sizeof(UnpackErr), hipMemcpyDeviceToHost, st));
     MRC_HIP(h, hipStreamSynchronize(st));
     if (h->dec.pinErr->flag) {
         char msg[160];
@@ -335,7 +334,7 @@ int mrc_decode_pac_pcm16(mrc_handle* h, int64_t n_files, const uint8_t* buf, con
     MRC_HIP(h, launch_unpack_dense(P, d.bands, d.consts.as<UnpackTables>(), nChunks, (const UnpackPlanEntry*)(din + oPlan),
                                    din, inBytes, (const UnpackGroupDev*)(din + oGroups), d.err.as<UnpackErr>(), st));
     MRC_HIP(h, hipEventRecord(d.ev[2], st));
-    MRC_HIP(h, hipMemcpyAsync(d.pinErr, d.err.p, sizeof(UnpackErr), hipMemcpyDeviceToHost, st));
+    MRC_HIP(h, hipMemcpyAsync(d.pinErr.get(), d.err.p, sizeof(UnpackErr), hipMemcpyDeviceToHost, st));
     MRC_HIP(h, hipStreamSynchronize(st));
     if (d.pinErr->flag) {
         const int64_t c = d.pinErr->firstBad;
@@ -361,11 +360,7 @@ int mrc_decode_pac_pcm16(mrc_handle* h, int64_t n_files, const uint8_t* buf, con
     if (nOut) MRC_HIP(h, hipMemcpyAsync(d.pinOut.p, pcm, sizeof(int16_t) * nOut, hipMemcpyDeviceToHost, st));
     MRC_HIP(h, hipEventRecord(d.ev[4], st));
     MRC_HIP(h, hipStreamSynchronize(st));
-    for (int i = 0; i < 4; ++i) {
-        float ms = 0;
-        MRC_HIP(h, hipEventElapsedTime(&ms, d.ev[i], d.ev[i + 1]));
-        d.ms[i] = ms;
-    }
+    for (int i = 0; i < 4; ++i) MRC_HIP(h, d.ev.elapsed(i, i + 1, &d.ms[i]));
     if (nOut) copy_host(out, d.pinOut.p, sizeof(int16_t) * nOut);
     return MRC_OK;
 }

@@ -100,8 +100,7 @@ int mrc_pac_nmr(mrc_handle* h, int64_t n_files, const uint8_t* buf, const int64_
     MRC_TRY(ensure_decode_consts(h));
     DecodeBufs& d = h->dec;
     NmrBufs& nb = h->nmr;
-    for (auto& e : nb.ev)
-        if (!e) MRC_HIP(h, hipEventCreate(&e));
+    MRC_HIP(h, nb.ev.create());
     MRC_TRY(pac_plan_groups(h, "mrc_pac_nmr", &pl));
     const int64_t nChunks = pl.nChunks();
 
@@ -220,7 +219,7 @@ int mrc_pac_nmr(mrc_handle* h, int64_t n_files, const uint8_t* buf, const int64_
     MRC_HIP(h, launch_unpack_dense(P, d.bands, d.consts.as<UnpackTables>(), nChunks, (const UnpackPlanEntry*)(din + oPlan),
                                    din, inBytes, (const UnpackGroupDev*)(din + oGroups), d.err.as<UnpackErr>(), st));
     MRC_HIP(h, hipEventRecord(nb.ev[2], st));
-    MRC_HIP(h, hipMemcpyAsync(d.pinErr, d.err.p, sizeof(UnpackErr), hipMemcpyDeviceToHost, st));
+    MRC_HIP(h, hipMemcpyAsync(d.pinErr.get(), d.err.p, sizeof(UnpackErr), hipMemcpyDeviceToHost, st));
     MRC_HIP(h, hipStreamSynchronize(st));
     if (d.pinErr->flag) {
         const UnpackPlanEntry* plan = (const UnpackPlanEntry*)(pin + oPlan);
@@ -260,11 +259,7 @@ int mrc_pac_nmr(mrc_handle* h, int64_t n_files, const uint8_t* buf, const int64_
     MRC_HIP(h, hipMemcpyAsync(nb.pinOut.p, dOut, outTotal, hipMemcpyDeviceToHost, st));
     MRC_HIP(h, hipEventRecord(nb.ev[4], st));
     MRC_HIP(h, hipStreamSynchronize(st));
-    for (int i = 0; i < 4; ++i) {
-        float ms = 0;
-        MRC_HIP(h, hipEventElapsedTime(&ms, nb.ev[i], nb.ev[i + 1]));
-        nb.ms[i] = ms;
-    }
+    for (int i = 0; i < 4; ++i) MRC_HIP(h, nb.ev.elapsed(i, i + 1, &nb.ms[i]));
 
     // ---- results: dB on the host from the file sums
     const unsigned char* pout = (const unsigned char*)nb.pinOut.p;

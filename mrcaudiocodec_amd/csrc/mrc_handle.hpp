@@ -1,48 +1,127 @@
 // The handle behind the C ABI and the helpers every translation unit of the host glue shares (mrc_api.cpp: the per-block
 // and pipelined entry points; mrc_api_chain.cpp, mrc_api_chain_measured.cpp: the chained stream encode).  Not part of the ABI.
+// Who frees what: every device buffer, page-locked buffer, event and stream is a member of an owning type below and goes
+// with the handle (mrc_destroy deletes it); nothing here is freed by name.
 #pragma once
 #include "mrc_internal.hpp"
 
 #include <cmath>
 #include <limits>
 #include <map>
+#include <memory>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
 namespace mrc {
 
-struct DevBuf {
+// ---- Owning types.  Every device resource of a handle is a member of one of these: move-only, freed by its destructor,
+// so a struct that gains a buffer or an event needs no list that frees it.  mrc_handle's destructor drains the streams
+// first.  None of them may be declared at namespace or static scope: its destructor would run after the HIP runtime
+// has gone.
+
+// A buffer that only grows: reserve() keeps what it has when that is enough, else frees it and allocates with headroom
+// (the old contents are lost).  Mem: how to allocate, how to free, how much headroom.
+template <class Mem>
+struct GrowBuf {
     void* p = nullptr;
     size_t cap = 0;
+    GrowBuf() = default;
+    GrowBuf(GrowBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+    GrowBuf& operator=(GrowBuf&& o) noexcept {           // o leaves with what this held and frees it
+        std::swap(p, o.p);
+        std::swap(cap, o.cap);
+        return *this;
+    }
+    ~GrowBuf() { reset(); }
     hipError_t reserve(size_t bytes) {
         if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        size_t want = bytes + bytes / 8 + 256;
-        hipError_t e = hipMalloc(&p, want);
+        reset();
+        const size_t want = Mem::headroom(bytes);
+        hipError_t e = Mem::alloc(&p, want);
         if (e == hipSuccess) cap = want;
         return e;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
     template <class T> T* as() { return (T*)p; }
+
+  private:
+    void reset() {
+        if (p) typename Mem::Free{}(p);
+        p = nullptr; cap = 0;
+    }
+};
+struct HostFree { void operator()(void* p) const { (void)hipHostFree(p); } };
+struct DevMem {
+    using Free = DevFree;
+    static hipError_t alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+    static size_t headroom(size_t bytes) { return bytes + bytes / 8 + 256; }
+};
+struct PinnedMem {
+    using Free = HostFree;
+    static hipError_t alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+    static size_t headroom(size_t bytes) { return bytes + bytes / 4 + 4096; }
+};
+using DevBuf = GrowBuf<DevMem>;
+// page-locked host staging of the small-batch host entry points (one copy each way instead of one per array)
+using PinnedBuf = GrowBuf<PinnedMem>;
+// one page-locked object (or array) the device writes and the host reads
+template <class T> using PinnedPtr = std::unique_ptr<T, HostFree>;
+template <class P> hipError_t pinned_alloc(P* out, size_t bytes) {
+    void* p = nullptr;
+    const hipError_t e = PinnedMem::alloc(&p, bytes);
+    if (e == hipSuccess) out->reset((typename P::pointer)p);
+    return e;
+}
+
+// An event / a stream: created on first use (create() on one that exists does nothing), used as the raw handle
+struct Event {
+    struct Destroy { void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); } };
+    std::unique_ptr<std::remove_pointer_t<hipEvent_t>, Destroy> e;
+    hipError_t create(unsigned flags = hipEventDefault) {
+        if (e) return hipSuccess;
+        hipEvent_t raw = nullptr;
+        const hipError_t rc = hipEventCreateWithFlags(&raw, flags);
+        if (rc == hipSuccess) e.reset(raw);
+        return rc;
+    }
+    operator hipEvent_t() const { return e.get(); }
+    hipError_t ms_until(hipEvent_t later, double* ms) const {   // both have completed
+        float f = 0.f;
+        const hipError_t rc = hipEventElapsedTime(&f, e.get(), later);
+        if (rc == hipSuccess) *ms = f;
+        return rc;
+    }
+};
+struct Stream {
+    struct Destroy { void operator()(hipStream_t s) const { (void)hipStreamDestroy(s); } };
+    std::unique_ptr<std::remove_pointer_t<hipStream_t>, Destroy> s;
+    hipError_t create(unsigned flags = hipStreamDefault) {
+        if (s) return hipSuccess;
+        hipStream_t raw = nullptr;
+        const hipError_t rc = hipStreamCreateWithFlags(&raw, flags);
+        if (rc == hipSuccess) s.reset(raw);
+        return rc;
+    }
+    operator hipStream_t() const { return s.get(); }
+};
+// The events of a timed call: create() before the first record, ev[i] to record, elapsed(i, j) once both have completed
+template <int N>
+struct EventSet {
+    Event ev[N];
+    hipError_t create() {
+        for (Event& e : ev)
+            if (hipError_t rc = e.create(); rc != hipSuccess) return rc;
+        return hipSuccess;
+    }
+    hipEvent_t operator[](int i) const { return ev[i]; }
+    hipError_t elapsed(int i, int j, double* ms) const { return ev[i].ms_until(ev[j], ms); }
 };
 
-// page-locked host staging of the small-batch host entry points (one copy each way instead of one per array)
-struct PinnedBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t reserve(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr; cap = 0;
-        const size_t want = bytes + bytes / 4 + 4096;
-        hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
-};
+static_assert(!std::is_copy_constructible_v<DevBuf> && std::is_nothrow_move_constructible_v<DevBuf>);
+static_assert(!std::is_copy_constructible_v<PinnedBuf> && std::is_nothrow_move_constructible_v<PinnedBuf>);
+static_assert(!std::is_copy_constructible_v<Event> && std::is_nothrow_move_constructible_v<Event>);
+static_assert(!std::is_copy_constructible_v<Stream> && std::is_nothrow_move_constructible_v<Stream>);
 
 // encode_host with few blocks (the per-block seam): one device layout, one page-locked copy each way (see encode_host)
 struct SmallBatchBufs {
@@ -50,17 +129,11 @@ struct SmallBatchBufs {
     DevBuf ev, pre;                  // chain_prep_kernel's grant events and the bits spent before each
     DevBuf table;                    // the scan's table ids (all 15: no pricing)
     PinnedBuf pinIn, pinOut;
-    void release() {
-        for (DevBuf* b : {&layout, &ev, &pre, &table}) b->release();
-        pinIn.release();
-        pinOut.release();
-    }
 };
 
 // intermediate results of one encode call (lines, SMRs, band peaks); one set per stream that encodes concurrently
 struct Workspace {
     DevBuf lines, smr, peak;
-    void release() { lines.release(); smr.release(); peak.release(); }
 };
 
 // The pipelined host entry point runs THREE streams -- one that only copies in, one that only launches kernels, one that
@@ -70,18 +143,8 @@ struct Workspace {
 struct Lane {
     DevBuf pcmL, pcmR, resIn, oScale, ms, ba, sf, mant, resOut;
     DevBuf pacBytes, pacOffs, pacTable, pacSaved;                // mrc_encode_stream_pcm16_pac: the chunk's packed form
-    long long* pacTotal = nullptr;                               // page-locked: the chunk's byte count, read by the host
-    hipEvent_t evIn = nullptr, evK = nullptr, evOut = nullptr;   // chunk copied in / encoded / copied out
-    void release() {
-        for (DevBuf* b : {&pcmL, &pcmR, &resIn, &oScale, &ms, &ba, &sf, &mant, &resOut, &pacBytes, &pacOffs, &pacTable, &pacSaved})
-            b->release();
-        if (pacTotal) (void)hipHostFree(pacTotal);
-        pacTotal = nullptr;
-        for (hipEvent_t* e : {&evIn, &evK, &evOut}) {
-            if (*e) (void)hipEventDestroy(*e);
-            *e = nullptr;
-        }
-    }
+    PinnedPtr<long long[]> pacTotal;                             // page-locked: the chunk's byte count, read by the host
+    Event evIn, evK, evOut;                                      // chunk copied in / encoded / copied out (no timing)
 };
 constexpr int kLanes = 4;          // chunk buffers in flight (mrc_encode_stream_pcm16_pac reads sizes two chunks behind)
 constexpr int kKernelEvents = 6;   // boundaries of: mdct | smr | band_stats | bitalloc | quantize
@@ -92,26 +155,14 @@ struct ChainGroupBufs {
     DevBuf offsets, lines, oscale, smr, peak, ms;                // phase A
     DevBuf ev, pre;                                              // prepared for phase B
     DevBuf bitAlloc, scaleFactor, mant, table, chunkMap;         // phase B outputs, packer inputs
-    void release() {
-        for (DevBuf* b : {&offsets, &lines, &oscale, &smr, &peak, &ms, &ev, &pre, &bitAlloc, &scaleFactor, &mant, &table,
-                          &chunkMap})
-            b->release();
-    }
 };
 struct ChainBufs {
     ChainGroupBufs g[kChainGroups];
     DevBuf pcmL, pcmR, flushPcm, items, itemStart, reservoir, groupDesc, packWs, out, hdr, chunkStream, resTrace, firstChunk,
         streamPos;
-    hipEvent_t evT[4] = {};          // phase timing: start | phase A done | phase B done | packed
+    EventSet<4> evT;                 // phase timing: start | phase A done | phase B done | packed
     int64_t lastTotal = -1;          // bytes the last mrc_encode_chained_stream_pac left in `out` (-1: none) -- mrc_chain_fetch_output
     const void* lastSrc = nullptr;   // ... or, after mrc_encode_chained_target_nmr_pac, in TargetBufs::sel (null: in `out`)
-    void release() {
-        for (auto& x : g) x.release();
-        for (DevBuf* b : {&pcmL, &pcmR, &flushPcm, &items, &itemStart, &reservoir, &groupDesc, &packWs, &out, &hdr,
-                          &chunkStream, &resTrace, &firstChunk, &streamPos})
-            b->release();
-        for (auto& e : evT) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    }
 };
 
 // Encode to a target noise-to-mask ratio (mrc_encode_chained_target_nmr_pac, mrc_api_chain_measured.cpp): reused from call to call
@@ -122,34 +173,20 @@ struct TargetBufs {
     DevBuf fileTab, fileOut, span;   // nmr_file_kernel's pseudo-files and sums; the gather's spans
     DevBuf keep;                     // a stream cut into time slabs: the packed bytes of all rungs until its last slab decides
     DevBuf sel;                      // the chosen files of the call, contiguous in stream order
-    hipEvent_t ev[6] = {};           // NMR kernels of a slab | file reduction | gather, start and end each
+    EventSet<6> ev;                  // NMR kernels of a slab | file reduction | gather, start and end each
     double ms[4] = {0, 0, 0, 0};     // phase A + preparation | scan | NMR (threshold pass included) | pack + gather
-    void release() {
-        for (DevBuf* b : {&lines, &thresh, &oscale, &smr, &flushOffs, &stat, &fileTab, &fileOut, &span, &keep, &sel}) b->release();
-        for (auto& e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    }
 };
 
 // Constant-quality VBR (mrc_encode_vbr_nmr_pac, mrc_api_chain_measured.cpp).  The source analysis and the file reduction use TargetBufs.
 struct VbrBufs {
     DevBuf capped;                   // [chunks of the streams being decided]: capped bands, at a block's first chunk
-    std::vector<hipEvent_t> ev;      // start and end of every allocator (or profile) launch of a slab
+    std::vector<Event> ev;           // start and end of every allocator (or profile) launch of a slab
     size_t evUsed = 0;
     double ms[4] = {0, 0, 0, 0};     // phase A + source analysis | the allocator | pack | all three
     // mrc_encode_vbr_size_pac: the slab's record per block-shape group, the streams' ceilings and file sizes of a probe
     DevBuf prof[kChainGroups], profPick[kChainGroups], ceilings, bytes;
-    hipEvent_t evSize[3] = {};       // the probes start | the final pick starts | it ended
+    EventSet<3> evSize;              // the probes start | the final pick starts | it ended
     double sizeMs[5] = {0, 0, 0, 0, 0};   // phase A + source analysis | profile | probes | final pick + pack | their sum
-    void release() {
-        capped.release();
-        for (auto& b : prof) b.release();
-        for (auto& b : profPick) b.release();
-        ceilings.release();
-        bytes.release();
-        for (auto& e : evSize) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-        for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-        ev.clear();
-    }
 };
 
 // Device decode of whole `.pac` files (mrc_api_decode.cpp): reused from call to call
@@ -160,17 +197,9 @@ struct DecodeBufs {
     DevBuf groups;                   // dense per-(shape, kind) arrays decode_kernel reads
     DevBuf x, pcm, err;              // decoded planes (float64), interleaved int16, UnpackErr
     PinnedBuf pinIn, pinOut;
-    UnpackErr* pinErr = nullptr;     // page-locked copy of err
-    hipEvent_t ev[5] = {};           // start | copied in | unpacked | synthesised | copied out
+    PinnedPtr<UnpackErr> pinErr;     // page-locked copy of err
+    EventSet<5> ev;                  // start | copied in | unpacked | synthesised | copied out
     double ms[4] = {0, 0, 0, 0};
-    void release() {
-        for (DevBuf* b : {&consts, &in, &groups, &x, &pcm, &err}) b->release();
-        pinIn.release();
-        pinOut.release();
-        if (pinErr) (void)hipHostFree(pinErr);
-        pinErr = nullptr;
-        for (auto& e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    }
 };
 
 // Noise-to-mask ratio of `.pac` files against their source (mrc_api_nmr.cpp): reused from call to call.  The parsing
@@ -183,14 +212,8 @@ struct NmrBufs {
     DevBuf out;                      // one D2H copy: per-file summaries | band noise | band mask
     DevBuf stat;                     // per entry: max r_j, b * mean r_j
     PinnedBuf pinIn, pinOut;
-    hipEvent_t ev[5] = {};           // start | copied in | unpacked | source analysed | reduced and copied out
+    EventSet<5> ev;                  // start | copied in | unpacked | source analysed | reduced and copied out
     double ms[4] = {0, 0, 0, 0};
-    void release() {
-        for (DevBuf* b : {&in, &groups, &planes, &lines, &thresh, &oscale, &smr, &out, &stat}) b->release();
-        pinIn.release();
-        pinOut.release();
-        for (auto& e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    }
 };
 
 // ---- the host plan of whole `.pac` files, shared by mrc_decode_pac_pcm16 and mrc_pac_nmr (mrc_api_decode.cpp)
@@ -296,12 +319,12 @@ void pac_plan_fill(const mrc_config& cfg, const DecodeBufs& d, const PacPlan& p,
 struct mrc_handle {
     mrc_config cfg{};
     int device = 0;
-    hipStream_t stream = nullptr;
+    mrc::Stream stream;
     std::map<std::pair<int, int>, mrc::HostShape> shapes;
     std::string error;
     mrc::Workspace ws;               // workspace of mrc_dev_encode* (calls on one handle are serialised)
     mrc::Lane lanes[mrc::kLanes];    // mrc_encode_stream_pcm16: chunk buffers ...
-    hipStream_t stIn = nullptr, stOut = nullptr;   // ... and its copy-in / copy-out streams; the kernels of all chunks run
+    mrc::Stream stIn, stOut;         // ... and its copy-in / copy-out streams; the kernels of all chunks run
     mrc::Workspace wsPipe;           //     on `stream`, one after the other: one workspace.  (No third stream of its own:
                                      //     the runtime multiplexes streams onto 4 hardware queues by default -- with the
                                      //     null stream and `stream` that is exactly four; a fifth would share a queue with
@@ -326,9 +349,16 @@ struct mrc_handle {
     bool sensOn = false;             // mrc_set_option(MRC_OPT_SENSITIVITY): count decisions near a rounding edge ...
     mrc::DevBuf sens;                // ... here: MRC_SENS_COUNT counters (uint64), mrc_get_sensitivity
     int sensMode = 0;                // the option's value as set (0, 1 or 2), what mrc_get_option returns
-    hipEvent_t ev[mrc::kKernelEvents] = {};
+    mrc::EventSet<mrc::kKernelEvents> ev;   // per-kernel timing: see collect_kernel_ms (mrc_api.cpp)
     double stageMs[3] = {0, 0, 0};
     double kernelMs[5] = {0, 0, 0, 0, 0};
+    // The members free themselves, on the handle's device and once nothing queued can still touch them: that is said
+    // here, not left to the order of the declarations above.
+    ~mrc_handle() {
+        (void)hipSetDevice(device);
+        for (hipStream_t st : {(hipStream_t)stream, (hipStream_t)stIn, (hipStream_t)stOut})
+            if (st) (void)hipStreamSynchronize(st);
+    }
 };
 
 namespace mrc {

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <vector>
 #include "mrc_hip.h"
@@ -63,10 +64,14 @@ struct DevShape {
     int msLeaves, msInternal;
 };
 
+// one device allocation, freed with its owner (the rule for every owning type: mrc_handle.hpp)
+struct DevFree { void operator()(void* p) const { (void)hipFree(p); } };
+using DevPtr = std::unique_ptr<void, DevFree>;
+
 struct HostShape {
     DevShape dev{};                  // device view (pointers valid on the device)
     std::vector<int> bandN, bandLo;  // host copies
-    void* blob = nullptr;            // device allocation backing dev.*
+    DevPtr blob;                     // device allocation backing dev.*
 };
 
 // mrc_tables.cpp
@@ -82,7 +87,6 @@ bool build_shape(const mrc_config& cfg, int a, int b, HostShape* out, std::strin
 // the bit budgets of a block of shape (a, b) with nb bands at target_bits_per_sample tbps (codecThem.py:299-306 mono,
 // 381-388 joint before the reservoir is added): the one copy of the float arithmetic the shape tables and the rate ladder share
 void shape_budgets(const mrc_config& cfg, double tbps, int a, int b, int nb, double* budgetMono, double* budgetJointPre);
-void free_shape(HostShape* s);
 int scale_factor_host(double v, int nScaleBits, int nMantBits);
 
 // mrc_kernels.hip -- launchers (enqueue only)
@@ -120,7 +124,8 @@ hipError_t launch_alloc_quant(const DevShape& S, int64_t nFrames, int joint, con
                               int* resOut, double* bandPeakWs,
                               bool peaksReady /* bandPeakWs already filled by launch_smr */,
                               bool msReady /* msSwitch already filled (launch_ms_switch ran before launch_smr) */,
-                              hipEvent_t* ev /* null or 2 events: after band_stats, after bitalloc */, hipStream_t st);
+                              hipEvent_t evStats, hipEvent_t evAlloc /* recorded after band_stats / after bitalloc; null: not */,
+                              hipStream_t st);
 hipError_t launch_pcm_to_float(int64_t n, const short* pcm, double* out, hipStream_t st);
 hipError_t launch_quantize_uniform(int64_t n, int nBits, const double* x, long long* out, hipStream_t st);
 hipError_t launch_bark(int64_t n, const double* f, double* out, hipStream_t st);

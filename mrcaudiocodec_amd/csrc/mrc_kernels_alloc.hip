@@ -332,7 +332,8 @@ size_t alloc_workspace_bytes(const DevShape& S, int64_t nFrames, int joint) {
 hipError_t launch_alloc_quant(const DevShape& S, int64_t nFrames, int joint, const double* lines, const int* oscale,
                               const double* smr, const int* resIn, int* msSwitch, int* bitAlloc, int* scaleFactor,
                               void* mantissa, int mantFmt, int* resOut, double* bandPeakWs, bool peaksReady, bool msReady,
-                              hipEvent_t* ev /* null, or 2 events: after band_stats, after bitalloc */, hipStream_t st) {
+                              hipEvent_t evStats, hipEvent_t evAlloc /* recorded after band_stats / after bitalloc; null: not */,
+                              hipStream_t st) {
     if (nFrames <= 0) return hipSuccess;
     const int nTot = (joint ? 2 : 1) * S.nBands;
     // the per-band peaks come from smr_kernel on the full path; band_stats_kernel only serves the stage entry points
@@ -344,7 +345,7 @@ hipError_t launch_alloc_quant(const DevShape& S, int64_t nFrames, int joint, con
                                         4 * (int64_t)S.halfN, S.halfN, msSwitch, st);
         if (e != hipSuccess) return e;
     }
-    if (ev) (void)hipEventRecord(ev[0], st);
+    if (evStats) (void)hipEventRecord(evStats, st);
     // frames per wave.  Spreading a launch over more, emptier waves (fpw = 8 .. 32) was tried to hide the latency of the
     // loop's dependent LDS reads: 2-3x SLOWER (mono 0.16 -> 0.30 ms, joint 0.52 -> 1.51 ms per 131 072 / 65 536 frames) --
     // the loop is bound by instruction issue, not by latency, so full waves it is.
@@ -358,7 +359,7 @@ hipError_t launch_alloc_quant(const DevShape& S, int64_t nFrames, int joint, con
     else if (nTot == 25) hipLaunchKernelGGL(bitalloc_kernel<25>, bgrid, dim3(kWave), lds, st, S, joint, nFrames, fpw, smr, msSwitch, resIn, bitAlloc, resOut);
     else if (nTot == 50) hipLaunchKernelGGL(bitalloc_kernel<50>, bgrid, dim3(kWave), lds, st, S, joint, nFrames, fpw, smr, msSwitch, resIn, bitAlloc, resOut);
     else hipLaunchKernelGGL(bitalloc_kernel<0>, bgrid, dim3(kWave), lds, st, S, joint, nFrames, fpw, smr, msSwitch, resIn, bitAlloc, resOut);
-    if (ev) (void)hipEventRecord(ev[1], st);
+    if (evAlloc) (void)hipEventRecord(evAlloc, st);
     const int vecOk = !((reinterpret_cast<uintptr_t>(lines) | reinterpret_cast<uintptr_t>(mantissa)) & 15);
     const dim3 qgrid((unsigned)(nFrames * (joint ? 2 : 1)));
     const int longj = (S.halfN == 1024 && vecOk) ? (joint ? 1 : 0) : -1;

@@ -320,8 +320,8 @@ bool build_shape(const mrc_config& cfg, int a, int b, HostShape* out, std::strin
     size_t oLineC = bw.put(lineC), oFftTw = bw.put(fftTw);
     void* blob = nullptr;
     if (hipMalloc(&blob, bw.bytes.size()) != hipSuccess) { *err = "hipMalloc(shape tables) failed"; return false; }
+    out->blob.reset(blob);
     if (hipMemcpy(blob, bw.bytes.data(), bw.bytes.size(), hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(blob);
         *err = "hipMemcpy(shape tables) failed";
         return false;
     }
@@ -339,13 +339,7 @@ bool build_shape(const mrc_config& cfg, int a, int b, HostShape* out, std::strin
     S.msPlan = (const int*)(base + oMsPlan);
     S.lineC = (const LineConstants*)(base + oLineC);
     S.fftTw = fftTw.empty() ? nullptr : (const double2*)(base + oFftTw);
-    out->blob = blob;
     return true;
-}
-
-void free_shape(HostShape* s) {
-    if (s->blob) (void)hipFree(s->blob);
-    s->blob = nullptr;
 }
 
 }  // namespace mrc
