@@ -40,6 +40,8 @@ import argparse
 import json
 import os
 import sys
+from collections import namedtuple
+from contextlib import contextmanager
 from struct import pack, unpack
 
 import numpy as np
@@ -118,6 +120,54 @@ def ladder_paths(out_path, rates):
     return [out_path.replace("{bps}", t) for (t, _) in rates]
 
 
+_Wav = namedtuple("_Wav", "h n_ch num_samples rate codes shapes header")
+
+
+@contextmanager
+def _wav_on_handle(in_path, handle, device_id, exact_spread, new_handle=None, options=None):
+    """What every encode of a WAV file starts and ends with.  Reads in_path (1 or 2 channels, a sample rate the reference can
+    encode), takes the caller's handle or creates one (new_handle: further keyword arguments of Handle), sets
+    MRC_OPT_EXACT_SPREAD if asked and the options {option: value} besides, prepends the zero prior hop
+    (pacfileThem.py:615-618) and runs the transient detector.
+    Yields (h, n_ch, num_samples, rate, codes int16 [n_ch][n], shapes, the file's header bytes).  On exit a caller's handle
+    gets back option 1 and those of `options` as it came with them, whatever the body set; a handle created here is closed."""
+    rate, n_ch, num_samples, pcm = read_wav_pcm(in_path)
+    if n_ch not in (1, 2):
+        raise ValueError("%d-channel input: mono and stereo WAV files only (the .pac readers refuse more than two channels "
+                         "and the reference's Close() flushes at most two)" % n_ch)
+    shape = {} if handle is None else dict(n_mdct_lines=handle.cfg.n_mdct_lines, n_short=handle.cfg.n_short)
+    try:                                 # (the rate decides the band tables: below ~31 kHz the reference's raise IndexError)
+        header = pacfile.header(pacfile.make_config(sample_rate=rate, **shape), n_ch, num_samples)
+    except MrcError as e:
+        raise ValueError("%d Hz input: outside the sample rates the reference can encode (%s)" % (rate, e))
+    h = handle if handle is not None else Handle(sample_rate=rate, device_id=device_id, **(new_handle or {}))
+    options = {**(options or {}), **({1: 1} if exact_spread else {})}
+    came_with = {opt: h.get_option(opt) for opt in {1, *options}}
+    try:
+        for opt, value in options.items():
+            h.set_option(opt, value)
+        L = h.cfg.n_mdct_lines
+        codes = np.concatenate([np.zeros((n_ch, L), np.int16), pcm], axis=1)
+        shapes = transient.block_shape_array(h, codes)
+        if not len(shapes):
+            raise ValueError("file too short: fewer than two hops")
+        if shapes[-1, 2] != L:
+            raise ValueError("the stream must end with a long block (the reference's Close() assumes it)")
+        yield _Wav(h, n_ch, num_samples, rate, codes, shapes, header)
+    finally:
+        if handle is None:
+            h.close()
+        else:
+            for opt, value in came_with.items():
+                h.set_option(opt, value)
+
+
+def _write(out_path, data):
+    if out_path:
+        with open(out_path, "wb") as f:
+            f.write(data)
+
+
 def encode_wav(in_path, out_path=None, use_huffman=True, device_id=0, handle=None, exact_spread=False, certify=None,
                bits_per_sample=None):
     """bits_per_sample: None -- the handle's rate (a new handle: the reference's 2.86); one value -- that target bit rate;
@@ -143,75 +193,55 @@ def encode_wav(in_path, out_path=None, use_huffman=True, device_id=0, handle=Non
         ladder = True                    # (a caller's handle at another rate: a ladder of one, the handle stays as it is)
         if certify is not None:
             raise ValueError("--certify: the handle's target_bits_per_sample differs from bits_per_sample")
-    rate, n_ch, num_samples, pcm = read_wav_pcm(in_path)
-    if n_ch not in (1, 2):
-        raise ValueError("%d-channel input: mono and stereo WAV files only (the .pac readers refuse more than two channels "
-                         "and the reference's Close() flushes at most two)" % n_ch)
-    shape = {} if handle is None else dict(n_mdct_lines=handle.cfg.n_mdct_lines, n_short=handle.cfg.n_short)
-    try:                                 # (the rate decides the band tables: below ~31 kHz the reference's raise IndexError)
-        pacfile.header(pacfile.make_config(sample_rate=rate, **shape), n_ch, num_samples)
-    except MrcError as e:
-        raise ValueError("%d Hz input: outside the sample rates the reference can encode (%s)" % (rate, e))
     tbps = {} if rates is None or ladder else dict(target_bits_per_sample=rates[0][1])
-    h = handle if handle is not None else Handle(sample_rate=rate, device_id=device_id, **tbps)
-    was_exact = h.get_option(1)
-    was_sens = h.get_option(5)
-    if exact_spread:
-        h.set_option(1, 1)
-    if certify is not None:
-        h.set_option(5, 1)
-        h.sensitivity()
-    try:
-        L = h.cfg.n_mdct_lines
-        codes = np.concatenate([np.zeros((n_ch, L), np.int16), pcm], axis=1)   # the zero prior hop (pacfileThem.py:615-618)
-        right = None if n_ch == 1 else codes[1][None]                          # (None: mono streams)
-        shapes = transient.block_shape_array(h, codes)
-        if not len(shapes):
-            raise ValueError("file too short: fewer than two hops")
-        if shapes[-1, 2] != L:
-            raise ValueError("the stream must end with a long block (the reference's Close() assumes it)")
+    sens = {} if certify is None else {5: 1}
+    if certify is not None and handle is not None:
+        handle.sensitivity()             # (counts a caller's handle still holds are not this encode's)
+    with _wav_on_handle(in_path, handle, device_id, exact_spread, new_handle=tbps, options=sens) as w:
         if ladder:
-            stream = codes[0] if n_ch == 1 else codes
-            datas = pacfile.encode_stream_ladder(h, stream, shapes, [v for (_, v) in rates], use_huffman=use_huffman,
-                                                 num_samples=num_samples)
+            datas = pacfile.encode_stream_ladder(w.h, w.codes, w.shapes, [v for (_, v) in rates], use_huffman=use_huffman,
+                                                 num_samples=w.num_samples)
             if out_path:
                 for path, d in zip(ladder_paths(out_path, rates), datas):
-                    with open(path, "wb") as f:
-                        f.write(d)
+                    _write(path, d)
             return datas if len(rates) > 1 else datas[0]
-        r = h.encode_chained_pac(codes[0][None], right, [shapes], use_huffman=use_huffman, with_flush=True,
-                                 num_samples=[num_samples])
-        data = r["bytes"].tobytes()
+        right = None if w.n_ch == 1 else w.codes[1][None]                      # (None: mono streams)
+        once = lambda: w.h.encode_chained_pac(w.codes[0][None], right, [w.shapes], use_huffman=use_huffman, with_flush=True,
+                                              num_samples=[w.num_samples])["bytes"].tobytes()
+        data = once()
         if certify is not None:
-            certify.update(h.sensitivity())
+            certify.update(w.h.sensitivity())
             near = sum(certify[k] for k in ("quantiser_edges", "bitalloc_near_ties", "ms_switch_near_threshold", "peak_near_ties"))
             certify["decisions_near_an_edge"] = near
             if near and not exact_spread:
-                h.set_option(5, 0)
-                h.set_option(1, 1)
-                again = h.encode_chained_pac(codes[0][None], right, [shapes], use_huffman=use_huffman, with_flush=True,
-                                             num_samples=[num_samples])
-                certify["bytes_equal_exact_spread"] = again["bytes"].tobytes() == data
-    finally:
-        if handle is not None:
-            h.set_option(1, was_exact)           # (a caller's handle gets back the settings it came with)
-            h.set_option(5, was_sens)
-        if handle is None:
-            h.close()
-    if out_path:
-        with open(out_path, "wb") as f:
-            f.write(data)
+                w.h.set_option(5, 0)
+                w.h.set_option(1, 1)
+                certify["bytes_equal_exact_spread"] = once() == data
+    _write(out_path, data)
     return data
+
+
+def _only_encodes(what, decode, certify, measure):
+    if decode or certify or measure:
+        raise ValueError("%s: it does not go with -d, --certify or --measure" % what)
+
+
+def _writes_one_file(flag, out_path):
+    if out_path is not None and "{bps}" in out_path:
+        raise ValueError("%s writes ONE file: dst must not contain {bps}" % flag)
+
+
+def _number(flag, value, kind=float, what="a number"):
+    try:
+        return kind(value)
+    except (TypeError, ValueError):
+        raise ValueError("%s: %r is not %s" % (flag, value, what))
 
 
 def check_target_args(bits_per_sample, target_nmr, out_path=None, decode=False, certify=False, measure=False):
     """The refusals of --target-nmr, before a file is read or a device is touched.  -> [(text, rate)], the target (float)."""
-    if decode or certify or measure:
-        raise ValueError("--target-nmr encodes one file at the rate it picks: it does not go with -d, --certify or --measure")
-    try:
-        target = float(target_nmr)
-    except (TypeError, ValueError):
-        raise ValueError("--target-nmr: %r is not a number" % (target_nmr,))
+    _only_encodes("--target-nmr encodes one file at the rate it picks", decode, certify, measure)
+    target = _number("--target-nmr", target_nmr)
     if np.isnan(target):
         raise ValueError("--target-nmr: the target must not be NaN")
     if bits_per_sample is None:
@@ -221,8 +251,7 @@ def check_target_args(bits_per_sample, target_nmr, out_path=None, decode=False, 
         raise ValueError("--target-nmr needs two rates or more to choose from (--bits-per-sample 1.5,2.86,4)")
     if any(b[1] <= a[1] for a, b in zip(rates, rates[1:])):
         raise ValueError("--target-nmr: --bits-per-sample must be strictly ascending")
-    if out_path is not None and "{bps}" in out_path:
-        raise ValueError("--target-nmr writes ONE file: dst must not contain {bps}")
+    _writes_one_file("--target-nmr", out_path)
     return rates, target
 
 
@@ -233,56 +262,29 @@ def encode_wav_target_nmr(in_path, out_path, bits_per_sample, target_nmr, use_hu
     report: data, chosen, chosen_bits_per_sample (as written), rate, met, per-rung nmr_total_db / nmr_max_db /
     disturbed_blocks, n_blocks.  The argument checks run before the file is read or a device is touched."""
     rates, target = check_target_args(bits_per_sample, target_nmr, out_path)
-    rate, n_ch, num_samples, pcm = read_wav_pcm(in_path)
-    if n_ch not in (1, 2):
-        raise ValueError("%d-channel input: mono and stereo WAV files only" % n_ch)
-    shape = {} if handle is None else dict(n_mdct_lines=handle.cfg.n_mdct_lines, n_short=handle.cfg.n_short)
-    try:
-        pacfile.header(pacfile.make_config(sample_rate=rate, **shape), n_ch, num_samples)
-    except MrcError as e:
-        raise ValueError("%d Hz input: outside the sample rates the reference can encode (%s)" % (rate, e))
-    h = handle if handle is not None else Handle(sample_rate=rate, device_id=device_id)
-    was_exact = h.get_option(1)
-    if exact_spread:
-        h.set_option(1, 1)
-    try:
-        L = h.cfg.n_mdct_lines
-        codes = np.concatenate([np.zeros((n_ch, L), np.int16), pcm], axis=1)
-        shapes = transient.block_shape_array(h, codes)
-        if not len(shapes):
-            raise ValueError("file too short: fewer than two hops")
-        if shapes[-1, 2] != L:
-            raise ValueError("the stream must end with a long block (the reference's Close() assumes it)")
-        r = pacfile.encode_stream_target_nmr(h, codes[0] if n_ch == 1 else codes, shapes, [v for (_, v) in rates], target,
-                                             use_huffman=use_huffman, num_samples=num_samples)
-    finally:
-        if handle is not None:
-            h.set_option(1, was_exact)
-        else:
-            h.close()
+    with _wav_on_handle(in_path, handle, device_id, exact_spread) as w:
+        r = pacfile.encode_stream_target_nmr(w.h, w.codes, w.shapes, [v for (_, v) in rates], target, use_huffman=use_huffman,
+                                             num_samples=w.num_samples)
     r["chosen_bits_per_sample"] = rates[r["chosen"]][0]
     r["bits_per_sample"] = [t for (t, _) in rates]
-    if out_path:
-        with open(out_path, "wb") as f:
-            f.write(r["data"])
+    _write(out_path, r["data"])
     return r
 
 
 def check_vbr_args(vbr_nmr, bits_per_sample=None, target_nmr=None, out_path=None, decode=False, certify=False, measure=False):
     """The refusals of --vbr-nmr, before a file is read or a device is touched.  -> the ceiling in dB (float)."""
-    if decode or certify or measure:
-        raise ValueError("--vbr-nmr encodes one file: it does not go with -d, --certify or --measure")
+    _only_encodes("--vbr-nmr encodes one file", decode, certify, measure)
     if bits_per_sample is not None or target_nmr is not None:
         raise ValueError("--vbr-nmr has no bit rate: it does not go with --bits-per-sample or --target-nmr")
-    try:
-        ceiling = float(vbr_nmr)
-    except (TypeError, ValueError):
-        raise ValueError("--vbr-nmr: %r is not a number" % (vbr_nmr,))
+    ceiling = _number("--vbr-nmr", vbr_nmr)
     if np.isnan(ceiling):
         raise ValueError("--vbr-nmr: the ceiling must not be NaN")
-    if out_path is not None and "{bps}" in out_path:
-        raise ValueError("--vbr-nmr writes ONE file: dst must not contain {bps}")
+    _writes_one_file("--vbr-nmr", out_path)
     return ceiling
+
+
+def _coded_samples(shapes):
+    return sum(int(b) for (_, _, b) in shapes)
 
 
 def encode_wav_vbr_nmr(in_path, out_path, vbr_nmr, use_huffman=True, device_id=0, handle=None, exact_spread=False):
@@ -290,38 +292,10 @@ def encode_wav_vbr_nmr(in_path, out_path, vbr_nmr, use_huffman=True, device_id=0
     noise-to-mask ratio <= vbr_nmr dB.  Writes the file to out_path (if given) and returns the report of
     pacfile.encode_stream_vbr_nmr plus bits_per_sample = coded_bits / (channels x coded samples)."""
     ceiling = check_vbr_args(vbr_nmr, out_path=out_path)
-    rate, n_ch, num_samples, pcm = read_wav_pcm(in_path)
-    if n_ch not in (1, 2):
-        raise ValueError("%d-channel input: mono and stereo WAV files only" % n_ch)
-    shape = {} if handle is None else dict(n_mdct_lines=handle.cfg.n_mdct_lines, n_short=handle.cfg.n_short)
-    try:
-        pacfile.header(pacfile.make_config(sample_rate=rate, **shape), n_ch, num_samples)
-    except MrcError as e:
-        raise ValueError("%d Hz input: outside the sample rates the reference can encode (%s)" % (rate, e))
-    h = handle if handle is not None else Handle(sample_rate=rate, device_id=device_id)
-    was_exact = h.get_option(1)
-    if exact_spread:
-        h.set_option(1, 1)
-    try:
-        L = h.cfg.n_mdct_lines
-        codes = np.concatenate([np.zeros((n_ch, L), np.int16), pcm], axis=1)
-        shapes = transient.block_shape_array(h, codes)
-        if not len(shapes):
-            raise ValueError("file too short: fewer than two hops")
-        if shapes[-1, 2] != L:
-            raise ValueError("the stream must end with a long block (the reference's Close() assumes it)")
-        r = pacfile.encode_stream_vbr_nmr(h, codes[0] if n_ch == 1 else codes, shapes, ceiling, use_huffman=use_huffman,
-                                          num_samples=num_samples)
-        coded = sum(int(b) for (_, _, b) in shapes)
-    finally:
-        if handle is not None:
-            h.set_option(1, was_exact)
-        else:
-            h.close()
-    r["bits_per_sample"] = r["coded_bits"] / float(n_ch * coded)
-    if out_path:
-        with open(out_path, "wb") as f:
-            f.write(r["data"])
+    with _wav_on_handle(in_path, handle, device_id, exact_spread) as w:
+        r = pacfile.encode_stream_vbr_nmr(w.h, w.codes, w.shapes, ceiling, use_huffman=use_huffman, num_samples=w.num_samples)
+    r["bits_per_sample"] = r["coded_bits"] / float(w.n_ch * _coded_samples(w.shapes))
+    _write(out_path, r["data"])
     return r
 
 
@@ -339,25 +313,17 @@ def check_vbr_size_args(vbr_bytes=None, vbr_bits_per_sample=None, vbr_grid=None,
         raise ValueError("--vbr-grid goes with --vbr-bytes or --vbr-bits-per-sample")
     if vbr_bytes is not None and vbr_bits_per_sample is not None:
         raise ValueError("--vbr-bytes and --vbr-bits-per-sample are two ways to give ONE size: take one")
-    if decode or certify or measure:
-        raise ValueError("%s encodes one file: it does not go with -d, --certify or --measure" % which)
+    _only_encodes("%s encodes one file" % which, decode, certify, measure)
     if bits_per_sample is not None or target_nmr is not None or vbr_nmr is not None:
         raise ValueError("%s searches the ceiling itself: it does not go with --bits-per-sample, --target-nmr or --vbr-nmr" % which)
-    if out_path is not None and "{bps}" in out_path:
-        raise ValueError("%s writes ONE file: dst must not contain {bps}" % which)
+    _writes_one_file(which, out_path)
     nbytes = bps = None
     if vbr_bytes is not None:
-        try:
-            nbytes = int(vbr_bytes)
-        except (TypeError, ValueError):
-            raise ValueError("--vbr-bytes: %r is not a whole number" % (vbr_bytes,))
+        nbytes = _number("--vbr-bytes", vbr_bytes, int, "a whole number")
         if nbytes < 0:
             raise ValueError("--vbr-bytes: the size must not be negative")
     else:
-        try:
-            bps = float(vbr_bits_per_sample)
-        except (TypeError, ValueError):
-            raise ValueError("--vbr-bits-per-sample: %r is not a number" % (vbr_bits_per_sample,))
+        bps = _number("--vbr-bits-per-sample", vbr_bits_per_sample)
         if not np.isfinite(bps) or bps < 0:
             raise ValueError("--vbr-bits-per-sample: the rate must be finite and not negative")
     grid = (-30.0, 0.25, 256)
@@ -382,41 +348,15 @@ def encode_wav_vbr_size(in_path, out_path, vbr_bytes=None, vbr_bits_per_sample=N
     is <= vbr_bytes, or <= vbr_size_target_bytes(vbr_bits_per_sample, ..).  Writes the file to out_path (if given) and
     returns the report of pacfile.encode_stream_vbr_size plus target_bytes and bits_per_sample."""
     nbytes, bps, grid = check_vbr_size_args(vbr_bytes, vbr_bits_per_sample, vbr_grid, out_path=out_path)
-    rate, n_ch, num_samples, pcm = read_wav_pcm(in_path)
-    if n_ch not in (1, 2):
-        raise ValueError("%d-channel input: mono and stereo WAV files only" % n_ch)
-    shape = {} if handle is None else dict(n_mdct_lines=handle.cfg.n_mdct_lines, n_short=handle.cfg.n_short)
-    try:
-        hdr = pacfile.header(pacfile.make_config(sample_rate=rate, **shape), n_ch, num_samples)
-    except MrcError as e:
-        raise ValueError("%d Hz input: outside the sample rates the reference can encode (%s)" % (rate, e))
-    h = handle if handle is not None else Handle(sample_rate=rate, device_id=device_id)
-    was_exact = h.get_option(1)
-    if exact_spread:
-        h.set_option(1, 1)
-    try:
-        L = h.cfg.n_mdct_lines
-        codes = np.concatenate([np.zeros((n_ch, L), np.int16), pcm], axis=1)
-        shapes = transient.block_shape_array(h, codes)
-        if not len(shapes):
-            raise ValueError("file too short: fewer than two hops")
-        if shapes[-1, 2] != L:
-            raise ValueError("the stream must end with a long block (the reference's Close() assumes it)")
-        coded = sum(int(b) for (_, _, b) in shapes)
+    with _wav_on_handle(in_path, handle, device_id, exact_spread) as w:
+        coded = _coded_samples(w.shapes)
         if nbytes is None:
-            nbytes = vbr_size_target_bytes(bps, len(hdr), coded, n_ch, n_ch * (len(shapes) + 1))
-        r = pacfile.encode_stream_vbr_size(h, codes[0] if n_ch == 1 else codes, shapes, nbytes, grid[0], grid[1], grid[2],
-                                           use_huffman=use_huffman, num_samples=num_samples)
-    finally:
-        if handle is not None:
-            h.set_option(1, was_exact)
-        else:
-            h.close()
+            nbytes = vbr_size_target_bytes(bps, len(w.header), coded, w.n_ch, w.n_ch * (len(w.shapes) + 1))
+        r = pacfile.encode_stream_vbr_size(w.h, w.codes, w.shapes, nbytes, grid[0], grid[1], grid[2], use_huffman=use_huffman,
+                                           num_samples=w.num_samples)
     r["target_bytes"] = nbytes
-    r["bits_per_sample"] = r["coded_bits"] / float(n_ch * coded)
-    if out_path:
-        with open(out_path, "wb") as f:
-            f.write(r["data"])
+    r["bits_per_sample"] = r["coded_bits"] / float(w.n_ch * coded)
+    _write(out_path, r["data"])
     return r
 
 
@@ -491,6 +431,18 @@ def _print_nmr(ap, a, paths, bps):
         print(json.dumps(r))
 
 
+def _nmr_fields(r):
+    """the NMR tail of a report's JSON line: one number each, or (a ladder's report) one per rung"""
+    plain = lambda v, typ: [typ(x) for x in v] if np.ndim(v) else v
+    return dict(nmr_total_db=plain(r["nmr_total_db"], float), nmr_max_db=plain(r["nmr_max_db"], float),
+                disturbed_blocks=plain(r["disturbed_blocks"], int), n_blocks=r["n_blocks"])
+
+
+def _vbr_fields(r):
+    return dict(ceiling_ratio=r["ceiling_ratio"], bits_per_sample=r["bits_per_sample"], coded_bits=r["coded_bits"],
+                capped_bands=r["capped_bands"], **_nmr_fields(r))
+
+
 def _join_vbr_grid(argv):
     """argv with "--vbr-grid VALUE" written "--vbr-grid=VALUE": a grid usually starts at a negative LO, and argparse takes
     "-30:0.25:256" (a leading minus, yet no number) for an option and never hands it to --vbr-grid as its value."""
@@ -554,10 +506,7 @@ def main(argv=None):
         except ValueError as e:
             ap.error(str(e))
         print(json.dumps(dict(file=a.dst, bytes=len(r["data"]), target_bytes=r["target_bytes"], chosen_db=r["chosen_db"],
-                              met=r["met"], probes=r["probes"], ceiling_ratio=r["ceiling_ratio"],
-                              bits_per_sample=r["bits_per_sample"], coded_bits=r["coded_bits"], capped_bands=r["capped_bands"],
-                              nmr_total_db=r["nmr_total_db"], nmr_max_db=r["nmr_max_db"],
-                              disturbed_blocks=r["disturbed_blocks"], n_blocks=r["n_blocks"])))
+                              met=r["met"], probes=r["probes"], **_vbr_fields(r))))
         return
     if a.vbr_nmr is not None:
         try:
@@ -565,10 +514,7 @@ def main(argv=None):
             r = encode_wav_vbr_nmr(a.src, a.dst, a.vbr_nmr, not a.no_huffman, a.device, exact_spread=a.exact_spread)
         except ValueError as e:
             ap.error(str(e))
-        print(json.dumps(dict(file=a.dst, bytes=len(r["data"]), ceiling_db=float(a.vbr_nmr), ceiling_ratio=r["ceiling_ratio"],
-                              bits_per_sample=r["bits_per_sample"], coded_bits=r["coded_bits"], capped_bands=r["capped_bands"],
-                              nmr_total_db=r["nmr_total_db"], nmr_max_db=r["nmr_max_db"],
-                              disturbed_blocks=r["disturbed_blocks"], n_blocks=r["n_blocks"])))
+        print(json.dumps(dict(file=a.dst, bytes=len(r["data"]), ceiling_db=float(a.vbr_nmr), **_vbr_fields(r))))
         return
     if a.target_nmr is not None:
         try:
@@ -579,9 +525,7 @@ def main(argv=None):
             ap.error(str(e))
         print(json.dumps(dict(file=a.dst, bytes=len(r["data"]), chosen_bits_per_sample=float(r["rate"]), met=r["met"],
                               target_nmr_total_db=float(a.target_nmr), bits_per_sample=[float(t) for t in r["bits_per_sample"]],
-                              nmr_total_db=[float(v) for v in r["nmr_total_db"]],
-                              nmr_max_db=[float(v) for v in r["nmr_max_db"]],
-                              disturbed_blocks=[int(v) for v in r["disturbed_blocks"]], n_blocks=r["n_blocks"])))
+                              **_nmr_fields(r))))
         return
     if a.decode and (a.nmr or a.measure):
         ap.error("-d decodes: --nmr and --measure apply to .pac files coded from src")

@@ -127,6 +127,44 @@ def pack_joint_blocks(cfg, a, b, overall_scale, ms_switch, scale_factor, bit_all
     return _pack(cfg, a, b, 1, overall_scale, ms_switch, scale_factor, bit_alloc, mantissa, use_huffman, huff_table)
 
 
+def _covered(shapes):
+    """the samples a block-shape sequence covers: what the header says when the caller names no count"""
+    return sum(int(b) for (_, _, b) in shapes)
+
+
+def _one_stream(handle, stream, shapes, num_samples, int16_only=False):
+    """The arguments of a chained call for ONE stream: stereo [2][samples], or mono [samples] / [1][samples]; int16 PCM codes,
+    or (unless int16_only) anything float64 holds.  The shapes must end with a long block; num_samples defaults to the samples
+    they cover.  -> (left [1][n], right [1][n] or None, [shapes], [num_samples])."""
+    stream = np.asarray(stream)
+    if stream.dtype != np.int16:
+        if int16_only:
+            raise ValueError("the stream must hold int16 PCM codes (the NMR's source is int16)")
+        stream = stream.astype(np.float64, copy=False)
+    if stream.ndim == 1:
+        stream = stream[None]
+    if stream.ndim != 2 or stream.shape[0] not in (1, 2):
+        raise ValueError("stream must be stereo [2][samples] or mono [samples]")
+    if not len(shapes) or shapes[-1][2] != handle.cfg.n_mdct_lines:
+        raise ValueError("the stream must end with a long block (the reference's Close() assumes it)")
+    if num_samples is None:
+        num_samples = _covered(shapes)                                    # the CLI writes the WAV's count
+    return stream[0][None], (stream[1][None] if stream.shape[0] == 2 else None), [shapes], [num_samples]
+
+
+def _encode_streams(handle, left, right, shapes, use_huffman, num_samples):
+    """MANY streams (left / right [nStreams][samples], right None: mono) through the one-rate chained call, each ending with a
+    long block; num_samples[s] defaults to the samples stream s's blocks cover.  -> one .pac byte string per stream."""
+    for sh in shapes:
+        if not len(sh) or sh[-1][2] != handle.cfg.n_mdct_lines:
+            raise ValueError("every stream must end with a long block (the reference's Close() assumes it)")
+    if num_samples is None:
+        num_samples = [_covered(sh) for sh in shapes]                     # the CLI writes the WAV's count
+    r = handle.encode_chained_pac(left, right, shapes, use_huffman=use_huffman, with_flush=True, num_samples=num_samples)
+    data, offs = r["bytes"], r["stream_offset"]
+    return [data[offs[s]:offs[s + 1]].tobytes() for s in range(len(shapes))]
+
+
 def encode_stereo_stream(handle, stream, shapes, use_huffman=True, num_samples=None):
     """The encode half of the reference CLI for ONE stereo stream [2][samples] (float64 signed fractions or int16 PCM
     codes) that starts with the zero prior hop and a given block-shape sequence [(offset, a, b)]: header, one joint block
@@ -144,22 +182,13 @@ def encode_stereo_streams(handle, streams, shapes, use_huffman=True, num_samples
     sequence of stream s, num_samples[s] (optional) = the header's sample count (default: the samples the blocks
     cover).  Returns a list of .pac byte strings, each identical to what the reference's driver writes for that
     stream alone."""
-    L = handle.cfg.n_mdct_lines
     streams = np.asarray(streams)
     if streams.dtype != np.int16:
         streams = streams.astype(np.float64, copy=False)
     nS = streams.shape[0]
     if streams.ndim != 3 or streams.shape[1] != 2 or len(shapes) != nS:
         raise ValueError("streams [nStreams][2][samples] and one shape list per stream expected")
-    for sh in shapes:
-        if not len(sh) or sh[-1][2] != L:
-            raise ValueError("every stream must end with a long block (the reference's Close() assumes it)")
-    if num_samples is None:
-        num_samples = [sum(int(b) for (_, _, b) in sh) for sh in shapes]       # the CLI writes the WAV's count
-    r = handle.encode_chained_pac(streams[:, 0], streams[:, 1], shapes, use_huffman=use_huffman, with_flush=True,
-                                  num_samples=num_samples)
-    data, offs = r["bytes"], r["stream_offset"]
-    return [data[offs[s]:offs[s + 1]].tobytes() for s in range(nS)]
+    return _encode_streams(handle, streams[:, 0], streams[:, 1], shapes, use_huffman, num_samples)
 
 
 def encode_stereo_stream_per_block(handle, stream, shapes, use_huffman=True, num_samples=None):
@@ -206,7 +235,6 @@ def encode_mono_stream(handle, stream, shapes, use_huffman=True, num_samples=Non
 def encode_mono_streams(handle, streams, shapes, use_huffman=True, num_samples=None):
     """encode_mono_stream for MANY mono streams at once: streams [nStreams][samples] (or [nStreams][1][samples]), shapes[s]
     and num_samples[s] as in encode_stereo_streams.  Returns a list of .pac byte strings."""
-    L = handle.cfg.n_mdct_lines
     streams = np.asarray(streams)
     if streams.ndim == 3 and streams.shape[1] == 1:
         streams = streams[:, 0]
@@ -215,14 +243,7 @@ def encode_mono_streams(handle, streams, shapes, use_huffman=True, num_samples=N
     nS = streams.shape[0]
     if streams.ndim != 2 or len(shapes) != nS:
         raise ValueError("streams [nStreams][samples] and one shape list per stream expected")
-    for sh in shapes:
-        if not len(sh) or sh[-1][2] != L:
-            raise ValueError("every stream must end with a long block (the reference's Close() assumes it)")
-    if num_samples is None:
-        num_samples = [sum(int(b) for (_, _, b) in sh) for sh in shapes]
-    r = handle.encode_chained_pac(streams, None, shapes, use_huffman=use_huffman, with_flush=True, num_samples=num_samples)
-    data, offs = r["bytes"], r["stream_offset"]
-    return [data[offs[s]:offs[s + 1]].tobytes() for s in range(nS)]
+    return _encode_streams(handle, streams, None, shapes, use_huffman, num_samples)
 
 
 def encode_stream_ladder(handle, stream, shapes, rates, use_huffman=True, num_samples=None):
@@ -231,21 +252,9 @@ def encode_stream_ladder(handle, stream, shapes, rates, use_huffman=True, num_sa
     library call (mrc_encode_chained_ladder_pac: the transform and the psychoacoustic model once, the serial scan per rate).
     Returns a list of .pac byte strings, one per rate: each what encode_stereo_stream / encode_mono_stream write on a handle
     whose target_bits_per_sample is that rate.  The handle's own rate is not used."""
-    L = handle.cfg.n_mdct_lines
-    stream = np.asarray(stream)
-    if stream.dtype != np.int16:
-        stream = stream.astype(np.float64, copy=False)
-    if stream.ndim == 1:
-        stream = stream[None]
-    if stream.ndim != 2 or stream.shape[0] not in (1, 2):
-        raise ValueError("stream must be stereo [2][samples] or mono [samples]")
-    if not len(shapes) or shapes[-1][2] != L:
-        raise ValueError("the stream must end with a long block (the reference's Close() assumes it)")
-    if num_samples is None:
-        num_samples = sum(int(b) for (_, _, b) in shapes)                 # the CLI writes the WAV's count
-    right = stream[1][None] if stream.shape[0] == 2 else None
-    rs = handle.encode_chained_pac_ladder(stream[0][None], right, [shapes], rates, use_huffman=use_huffman, with_flush=True,
-                                          num_samples=[num_samples])
+    left, right, shapes, num_samples = _one_stream(handle, stream, shapes, num_samples)
+    rs = handle.encode_chained_pac_ladder(left, right, shapes, rates, use_huffman=use_huffman, with_flush=True,
+                                          num_samples=num_samples)
     return [r["bytes"].tobytes() for r in rs]
 
 
@@ -269,21 +278,9 @@ def encode_stream_target_nmr(handle, stream, shapes, rates, target_db, use_huffm
     (mrc_encode_chained_target_nmr_pac).  -> dict: data (the `.pac` bytes of the LOWEST rung whose nmr_total_db is <=
     target_db; the top rung, met False, if none is), chosen, rate, met, and per rung nmr_total_db, nmr_max_db,
     disturbed_blocks (what measure_nmr gives for encode_stream_ladder's files), n_blocks."""
-    L = handle.cfg.n_mdct_lines
-    stream = np.asarray(stream)
-    if stream.dtype != np.int16:
-        raise ValueError("the stream must hold int16 PCM codes (the NMR's source is int16)")
-    if stream.ndim == 1:
-        stream = stream[None]
-    if stream.ndim != 2 or stream.shape[0] not in (1, 2):
-        raise ValueError("stream must be stereo [2][samples] or mono [samples]")
-    if not len(shapes) or shapes[-1][2] != L:
-        raise ValueError("the stream must end with a long block (the reference's Close() assumes it)")
-    if num_samples is None:
-        num_samples = sum(int(b) for (_, _, b) in shapes)
-    right = stream[1][None] if stream.shape[0] == 2 else None
-    return handle.encode_chained_pac_target_nmr(stream[0][None], right, [shapes], rates, target_db, use_huffman=use_huffman,
-                                                num_samples=[num_samples])[0]
+    left, right, shapes, num_samples = _one_stream(handle, stream, shapes, num_samples, int16_only=True)
+    return handle.encode_chained_pac_target_nmr(left, right, shapes, rates, target_db, use_huffman=use_huffman,
+                                                num_samples=num_samples)[0]
 
 
 def encode_stream_vbr_nmr(handle, stream, shapes, ceiling_db, use_huffman=True, num_samples=None):
@@ -292,21 +289,8 @@ def encode_stream_vbr_nmr(handle, stream, shapes, ceiling_db, use_huffman=True, 
     the fewest bits that keep its measured noise-to-mask ratio <= 10^(ceiling_db / 10).  -> dict: data (the `.pac` bytes),
     ceiling_ratio, capped_bands, coded_bits, nmr_total_db, nmr_max_db, disturbed_blocks, n_blocks (what measure_nmr gives for
     the file)."""
-    L = handle.cfg.n_mdct_lines
-    stream = np.asarray(stream)
-    if stream.dtype != np.int16:
-        raise ValueError("the stream must hold int16 PCM codes (the NMR's source is int16)")
-    if stream.ndim == 1:
-        stream = stream[None]
-    if stream.ndim != 2 or stream.shape[0] not in (1, 2):
-        raise ValueError("stream must be stereo [2][samples] or mono [samples]")
-    if not len(shapes) or shapes[-1][2] != L:
-        raise ValueError("the stream must end with a long block (the reference's Close() assumes it)")
-    if num_samples is None:
-        num_samples = sum(int(b) for (_, _, b) in shapes)
-    right = stream[1][None] if stream.shape[0] == 2 else None
-    return handle.encode_vbr_nmr_pac(stream[0][None], right, [shapes], ceiling_db, use_huffman=use_huffman,
-                                     num_samples=[num_samples])[0]
+    left, right, shapes, num_samples = _one_stream(handle, stream, shapes, num_samples, int16_only=True)
+    return handle.encode_vbr_nmr_pac(left, right, shapes, ceiling_db, use_huffman=use_huffman, num_samples=num_samples)[0]
 
 
 def bisect_ceiling(sizes_by_index, target):
@@ -341,21 +325,9 @@ def encode_stream_vbr_size(handle, stream, shapes, target_bytes, lo_db=-30.0, st
     """encode_stream_vbr_nmr with the ceiling searched in one library call (mrc_encode_vbr_size_pac): the tightest ceiling of
     the grid lo_db + i * step_db (i < n) that bisect_ceiling finds to keep the whole file <= target_bytes.  -> dict:
     encode_stream_vbr_nmr's for that ceiling plus chosen, chosen_db, met, probes, probe_index, probe_bytes."""
-    L = handle.cfg.n_mdct_lines
-    stream = np.asarray(stream)
-    if stream.dtype != np.int16:
-        raise ValueError("the stream must hold int16 PCM codes (the NMR's source is int16)")
-    if stream.ndim == 1:
-        stream = stream[None]
-    if stream.ndim != 2 or stream.shape[0] not in (1, 2):
-        raise ValueError("stream must be stereo [2][samples] or mono [samples]")
-    if not len(shapes) or shapes[-1][2] != L:
-        raise ValueError("the stream must end with a long block (the reference's Close() assumes it)")
-    if num_samples is None:
-        num_samples = sum(int(b) for (_, _, b) in shapes)
-    right = stream[1][None] if stream.shape[0] == 2 else None
-    return handle.encode_vbr_size_pac(stream[0][None], right, [shapes], [int(target_bytes)], lo_db, step_db, n,
-                                      use_huffman=use_huffman, num_samples=[num_samples])[0]
+    left, right, shapes, num_samples = _one_stream(handle, stream, shapes, num_samples, int16_only=True)
+    return handle.encode_vbr_size_pac(left, right, shapes, [int(target_bytes)], lo_db, step_db, n,
+                                      use_huffman=use_huffman, num_samples=num_samples)[0]
 
 
 def encode_mono_stream_per_block(handle, stream, shapes, use_huffman=True, num_samples=None):

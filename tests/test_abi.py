@@ -10,15 +10,14 @@ import types
 import numpy as np
 import pytest
 
+import chain_kit as kit
 from oracle import codec as ocodec, huffman_tables as otables
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _header_functions():
-    text = open(os.path.join(ROOT, "include", "mrc_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(mrc_[a-z_0-9]+)\s*\(", text)))
+    return sorted(set(re.findall(r"\b(mrc_[a-z_0-9]+)\s*\(", kit.header_text())))
 
 
 def test_library_exports_every_header_symbol():
@@ -31,6 +30,15 @@ def test_library_exports_every_header_symbol():
         assert hasattr(raw, n), "libmrc_hip.so does not export %s" % n
         assert n in _lib.EXPORTS, "ctypes binding does not declare %s" % n
     assert _lib.lib.mrc_version() == 300
+
+
+def test_binding_matches_the_header():
+    """every declaration of include/mrc_hip.h against the hand-written prototype of _lib.py: a wrong argument count there
+    is silent memory corruption, not an error"""
+    from mrcaudiocodec_amd import _lib
+    declared = sorted(kit.header_declarations())
+    assert declared == _header_functions() == sorted(_lib.EXPORTS)
+    kit.check_binding(declared)
 
 
 def test_no_cpu_fallback_without_gpu():

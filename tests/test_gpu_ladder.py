@@ -10,27 +10,17 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import chain_kit as kit
+from chain_kit import HOP, handles_closed_after_module as _close_handles  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 RATES = (1.0, 2.0, 2.86, 4.0, 6.5)
-HOP = 1024
-_HANDLES = {}
 
 
 def _handle(tbps):
     """a handle at target_bits_per_sample = tbps (kept for the module: the one-rate reference calls)"""
-    from mrcaudiocodec_amd import Handle
-    if tbps not in _HANDLES:
-        _HANDLES[tbps] = Handle(device_id=0, target_bits_per_sample=tbps)
-    return _HANDLES[tbps]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _close_handles():
-    yield
-    for hd in _HANDLES.values():
-        hd.close()
-    _HANDLES.clear()
+    return kit.handle(target_bits_per_sample=tbps)
 
 
 @pytest.fixture(scope="module")
@@ -41,17 +31,14 @@ def h():
 def _switched(h, hops, seed, mono=False):
     """int16 PCM codes [nCh][(hops + 1) * HOP] (zero prior hop) with bursts, and the detector's shapes [n][3] up to the last
     long block (Close() needs one)"""
-    from mrcaudiocodec_amd import synth, transient
+    from mrcaudiocodec_amd import synth
     x, _ = synth.c4_transients(hops, seed=seed, period=7)
     tone = synth.c1_sine(hops, freq=440.0 + seed, amp=0.2)
     g = synth.c2_noise(hops, seed=seed + 1, sigma=0.03)[:len(x)]
     left = x + tone
     chans = [left] if mono else [left, 0.7 * x + 0.8 * tone + g]
-    pcm = np.clip(np.rint(np.stack(chans) * 32767.5), -32767, 32767).astype(np.int16)
-    pcm[:, :HOP] = 0
-    shapes = transient.block_shape_array(h, pcm)
-    last = np.nonzero(shapes[:, 2] == HOP)[0][-1]
-    return pcm, shapes[:last + 1]
+    pcm = kit.to_pcm(np.stack(chans))
+    return pcm, kit.shapes_to_last_long(h, pcm)
 
 
 def _four_shapes(shapes):
@@ -88,12 +75,7 @@ def test_ladder_equals_one_call_per_rate(h, mono, huff):
 def _four_streams(h):
     """4 stereo streams of different lengths [4][stride] and their shape lists (the first one switched through all shapes)"""
     parts = [_switched(h, n, seed=s) for (n, s) in ((37, 11), (12, 12), (25, 13), (6, 14))]
-    stride = max(p.shape[1] for (p, _) in parts)
-    left = np.zeros((4, stride), np.int16)
-    right = np.zeros((4, stride), np.int16)
-    for i, (p, _) in enumerate(parts):
-        left[i, :p.shape[1]] = p[0]
-        right[i, :p.shape[1]] = p[1]
+    left, right, _ = kit.rows([p for (p, _) in parts])
     assert _four_shapes(parts[0][1])
     return left, right, [sh for (_, sh) in parts]
 
@@ -284,18 +266,11 @@ def test_ladder_memory_stays_within_twice_one_rate():
     assert used[1] < 2 * used[0] and used[1] < 8e9, [u / 1e9 for u in used]
 
 
-def _wav(tmp_path, name, pcm):
-    from mrcaudiocodec_amd import cli
-    p = tmp_path / name
-    p.write_bytes(cli.wav_bytes(pcm, 48000))
-    return str(p)
-
-
 @pytest.mark.parametrize("mono", [False, True])
 def test_cli_ladder(h, tmp_path, mono):
     from mrcaudiocodec_amd import cli
     pcm, _ = _switched(h, 25, seed=17, mono=mono)
-    src = _wav(tmp_path, "in.wav", pcm[:, HOP:])
+    src = kit.write_wav(tmp_path / "in.wav", pcm[:, HOP:])
     cli.main([src, str(tmp_path / "plain.pac")])
     cli.main([src, str(tmp_path / "out_{bps}.pac"), "--bits-per-sample", "2,2.86,4"])
     files = {v: (tmp_path / ("out_%s.pac" % v)).read_bytes() for v in ("2", "2.86", "4")}

@@ -10,7 +10,9 @@ import os
 import numpy as np
 import pytest
 
+import chain_kit as kit
 import mono_oracle as MO
+from chain_kit import handles_closed_after_module as _close_handles  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -29,14 +31,8 @@ def _cases():
     return [str(c) for c in np.load(FIXTURE)["cases"]] if os.path.exists(FIXTURE) else ["missing"]
 
 
-_HANDLES = {}
-
-
 def _handle(rate=48000):
-    from mrcaudiocodec_amd import Handle
-    if rate not in _HANDLES:
-        _HANDLES[rate] = Handle(sample_rate=rate, device_id=0)
-    return _HANDLES[rate]
+    return kit.handle(rate=rate)
 
 
 def _write_wav(tmp_path, pcm, rate, name="in.wav"):

@@ -14,29 +14,18 @@ import os
 import numpy as np
 import pytest
 
+import chain_kit as kit
 import nmr_restatement as nr
+from chain_kit import HOP, handles_closed_after_module as _close_handles  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-HOP = 1024
 EPS = 1e-12
-_HANDLES = {}
 
 
 def _handle(rate=48000):
-    from mrcaudiocodec_amd import Handle
-    if rate not in _HANDLES:
-        _HANDLES[rate] = Handle(sample_rate=int(rate), device_id=0)
-    return _HANDLES[rate]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _close_handles():
-    yield
-    for hd in _HANDLES.values():
-        hd.close()
-    _HANDLES.clear()
+    return kit.handle(rate=rate)
 
 
 def _golden_cases():
@@ -121,15 +110,12 @@ def test_reference_files_against_restatement(name, key, case):
 def _switched(h, hops, seed, mono=False):
     """int16 codes [nCh][(hops + 1) * HOP] with the zero prior hop, bursts as synth.c4_transients builds them (two seeds
     for stereo), and the detector's shapes up to the last long block"""
-    from mrcaudiocodec_amd import synth, transient
+    from mrcaudiocodec_amd import synth
     x, _ = synth.c4_transients(hops, seed=seed, period=6)
     chans = [x] if mono else [x, synth.c4_transients(hops, seed=seed + 1, period=6)[0]]
     tone = synth.c1_sine(hops, freq=440.0 + seed, amp=0.1)[:len(x)]
-    pcm = np.clip(np.rint((np.stack(chans) + tone) * 32767.5), -32767, 32767).astype(np.int16)
-    pcm[:, :HOP] = 0
-    shapes = transient.block_shape_array(h, pcm)
-    last = np.nonzero(shapes[:, 2] == HOP)[0][-1]
-    return pcm, shapes[:last + 1]
+    pcm = kit.to_pcm(np.stack(chans) + tone)
+    return pcm, kit.shapes_to_last_long(h, pcm)
 
 
 def _encode(h, pcm, shapes, rates):
@@ -326,19 +312,10 @@ def test_stereo_stride_below_frames_is_refused(streams):
     assert b"file 0" in _lib.lib.mrc_last_error(h._h)
 
 
-def _write_wav(path, pcm, rate=48000):
-    from mrcaudiocodec_amd import cli
-    data = np.ascontiguousarray(pcm.T).astype("<i2").tobytes()
-    with open(path, "wb") as f:
-        f.write(cli.wav_header(pcm.shape[0], len(data), rate))
-        f.write(data)
-
-
 def test_cli_nmr_and_measure(tmp_path, capsys, streams):
     from mrcaudiocodec_amd import cli, pacfile
     src, _ = streams[False]
-    wav = str(tmp_path / "in.wav")
-    _write_wav(wav, src[:, :12 * HOP + 321])
+    wav = kit.write_wav(tmp_path / "in.wav", src[:, :12 * HOP + 321])
     dst = str(tmp_path / "out_{bps}.pac")
     cli.main([wav, dst, "--bits-per-sample", "1.5,2.86,4", "--nmr"])
     lines = [json.loads(x) for x in capsys.readouterr().out.splitlines() if x.startswith("{")]

@@ -13,48 +13,11 @@ import math
 import numpy as np
 import pytest
 
+import chain_kit as kit
+from chain_kit import HOP, handle as _handle, handles_closed_after_module as _close_handles  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-HOP = 1024
 RATES = (1.5, 2.86, 4.0, 8.0)
-_HANDLES = {}
-
-
-def _handle(exact=False):
-    from mrcaudiocodec_amd import Handle
-    if exact not in _HANDLES:
-        _HANDLES[exact] = Handle(sample_rate=48000, device_id=0)
-        if exact:
-            _HANDLES[exact].set_option(1, 1)
-    return _HANDLES[exact]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _close_handles():
-    yield
-    for hd in _HANDLES.values():
-        hd.close()
-    _HANDLES.clear()
-
-
-def _to_pcm(x):
-    pcm = np.clip(np.rint(np.atleast_2d(x) * 32767.5), -32767, 32767).astype(np.int16)
-    pcm[:, :HOP] = 0
-    return pcm
-
-
-def _shapes(h, pcm):
-    from mrcaudiocodec_amd import transient
-    shapes = transient.block_shape_array(h, pcm)
-    last = np.nonzero(shapes[:, 2] == HOP)[0][-1]
-    return shapes[:last + 1]
-
-
-def _clicks(hops, seed, mono, period=6):
-    """noise floor + bursts (synth.c4_transients, a seed per channel) + a tone: int16 [nCh][(hops + 1) * HOP]"""
-    from mrcaudiocodec_amd import synth
-    chans = [synth.c4_transients(hops, seed=seed + c, period=period)[0] for c in range(1 if mono else 2)]
-    tone = synth.c1_sine(hops, freq=440.0 + seed, amp=0.1)[:len(chans[0])]
-    return _to_pcm(np.stack(chans) + tone)
 
 
 def _kinds(hops, mono):
@@ -65,7 +28,7 @@ def _kinds(hops, mono):
     noise = np.stack([synth.c2_noise(hops, seed=5 + c, sigma=0.25) for c in range(nch)])
     tones = np.stack([synth.c1_sine(hops, freq=523.0 + 100 * c, amp=0.004) + synth.c1_sine(hops, freq=659.0, amp=0.003)
                       for c in range(nch)])
-    return [_to_pcm(noise), _to_pcm(tones), np.zeros((nch, n), np.int16), _clicks(hops, 31, mono, period=5)]
+    return [kit.to_pcm(noise), kit.to_pcm(tones), np.zeros((nch, n), np.int16), kit.clicks(hops, 31, mono, period=5)]
 
 
 class Case:
@@ -75,7 +38,7 @@ class Case:
         from mrcaudiocodec_amd import pacfile
         self.h, self.pcms, self.rates, self.huff = h, pcms, rates, use_huffman
         self.mono = pcms[0].shape[0] == 1
-        self.shapes = [_shapes(h, p) for p in pcms]
+        self.shapes = [kit.shapes_to_last_long(h, p) for p in pcms]
         self.ns = [len(sh) * HOP for sh in self.shapes]
         self.left = np.stack([p[0] for p in pcms])
         self.right = None if self.mono else np.stack([p[1] for p in pcms])
@@ -134,7 +97,7 @@ def _case(mono, huff=True, exact=False):
     key = (mono, huff, exact)
     if key not in _CASES:
         h = _handle(exact)
-        pcm = _clicks(30, 11, mono)
+        pcm = kit.clicks(30, 11, mono, period=6)
         c = Case(h, [pcm], use_huffman=huff)
         assert len({(int(a), int(b)) for (_, a, b) in c.shapes[0]}) == 4, "all four block shapes"
         assert all(w["n_blocks"] == len(c.shapes[0]) + 1 for w in (c.nmr[r][0] for r in range(4))), "Close()'s block"
@@ -193,7 +156,7 @@ def test_many_streams_choose_different_rungs(mono):
 def test_slabs_do_not_change_anything():
     h = _handle()
     try:
-        long = Case(h, [_clicks(40, 17, False)])
+        long = Case(h, [kit.clicks(40, 17, False, period=6)])
         tot = long.totals(0)
         t = 0.5 * (tot[1] + tot[2])
         want = long.run(t)
@@ -203,7 +166,7 @@ def test_slabs_do_not_change_anything():
         _same(long.run(t), want)
         h.set_option(6, 131072)
         from mrcaudiocodec_amd import synth
-        short = Case(h, [_to_pcm(np.stack([synth.c2_noise(8, seed=70 + 2 * s + c, sigma=0.02 * (s + 1)) for c in range(2)]))
+        short = Case(h, [kit.to_pcm(np.stack([synth.c2_noise(8, seed=70 + 2 * s + c, sigma=0.02 * (s + 1)) for c in range(2)]))
                          for s in range(6)])
         cands = sorted(v for s in range(6) for v in short.totals(s))
         t = cands[len(cands) // 2]
@@ -247,23 +210,11 @@ def test_device_entry_point(mono):
     assert not host[len(want[0]["data"]):].any()
 
 
-def _long_short_run():
-    """one mono stream whose (S,S) blocks do not fit one batch of the source analysis (16384 blocks of one shape):
-    (L,S), 16384 + 5 x (S,S), (S,L) -- int16 [1][n], its shapes, its sample count"""
-    S, n_ss = 128, 16384 + 5
-    a = np.array([HOP] + [S] * (n_ss + 1), np.int64)
-    b = np.array([S] * (n_ss + 1) + [HOP], np.int64)
-    off = np.concatenate([[0], np.cumsum(a)[:-1]])
-    shapes = np.stack([off, a, b], axis=1)
-    hops = -(-int(off[-1] + a[-1] + b[-1]) // HOP)
-    return _clicks(hops, 11, True), shapes, int(b.sum())
-
-
 def test_second_batch_of_one_shape_equals_single_batch_slabs():
     """Inside a slab the blocks of one shape are analysed 16384 at a time.  4096-block slabs: time slabs of one batch each,
     the path of every other test; the default slab: one slab whose (S,S) group is a full batch and a batch of five."""
     h = _handle()
-    pcm, shapes, ns = _long_short_run()
+    pcm, shapes, ns = kit.long_short_run(period=6)
     rates = (2.86, 8.0)
     run = lambda: h.encode_chained_pac_target_nmr(pcm, None, [shapes], rates, 0.0, num_samples=[ns])
     try:
@@ -377,11 +328,9 @@ def test_cli_target_nmr(tmp_path, capsys):
     from mrcaudiocodec_amd import synth
     # the file ends in long blocks and in two silent hops: mrc_pac_nmr measures Close()'s block against the samples that
     # follow the last coded block, the call against the zeros Close() coded -- the same thing when the WAV ends in silence
-    tail = _to_pcm(np.stack([synth.c1_sine(3, freq=440.0, amp=0.05)] * 2))[:, HOP:]
-    pcm = np.concatenate([_clicks(22, 23, False)[:, HOP:], tail, np.zeros((2, 2 * HOP), np.int16)], axis=1)
-    wav = str(tmp_path / "in.wav")
-    with open(wav, "wb") as f:
-        f.write(cli.wav_bytes(pcm, 48000))
+    tail = kit.to_pcm(np.stack([synth.c1_sine(3, freq=440.0, amp=0.05)] * 2))[:, HOP:]
+    pcm = np.concatenate([kit.clicks(22, 23, False, period=6)[:, HOP:], tail, np.zeros((2, 2 * HOP), np.int16)], axis=1)
+    wav = kit.write_wav(tmp_path / "in.wav", pcm)
     lad = cli.encode_wav(wav, None, bits_per_sample="1.5,2.86,4,8")
     dst = str(tmp_path / "out.pac")
     probe = cli.encode_wav_target_nmr(wav, None, "1.5,2.86,4,8", "inf")

@@ -14,58 +14,13 @@ import math
 import numpy as np
 import pytest
 
+import chain_kit as kit
 import nmr_restatement as nr
 import vbr_restatement as vr
+from chain_kit import HOP, handle as _handle, handles_closed_after_module as _close_handles  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-HOP = 1024
 CEILINGS = (6.0, 0.0, -6.0, -60.0)
-_HANDLES = {}
-
-
-def _handle(exact=False, rate=48000):
-    from mrcaudiocodec_amd import Handle
-    if (exact, rate) not in _HANDLES:
-        _HANDLES[(exact, rate)] = Handle(sample_rate=rate, device_id=0)
-        if exact:
-            _HANDLES[(exact, rate)].set_option(1, 1)
-    return _HANDLES[(exact, rate)]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _close_handles():
-    yield
-    for hd in _HANDLES.values():
-        hd.close()
-    _HANDLES.clear()
-
-
-def _to_pcm(x):
-    pcm = np.clip(np.rint(np.atleast_2d(x) * 32767.5), -32767, 32767).astype(np.int16)
-    pcm[:, :HOP] = 0
-    return pcm
-
-
-def _clicks(hops, seed, mono, period=5, fs=48000):
-    """config C4 content -- noise floor + bursts (synth.c4_transients, a seed per channel) -- and a tone common to the
-    channels, so that M/S bands occur beside L/R bands: int16 [nCh][(hops + 1) * HOP]"""
-    from mrcaudiocodec_amd import synth
-    chans = [synth.c4_transients(hops, seed=seed + c, period=period)[0] for c in range(1 if mono else 2)]
-    tone = synth.c1_sine(hops, freq=440.0 + seed, amp=0.1, fs=fs)[:len(chans[0])]
-    return _to_pcm(np.stack(chans) + tone)
-
-
-def _shapes(h, pcm):
-    from mrcaudiocodec_amd import transient
-    shapes = transient.block_shape_array(h, pcm)
-    last = np.nonzero(shapes[:, 2] == HOP)[0][-1]
-    return shapes[:last + 1]
-
-
-def _noise(hops, seed, fs):
-    from mrcaudiocodec_amd import synth
-    return _to_pcm(np.stack([synth.c2_noise(hops, seed=seed + c, sigma=0.05) for c in range(2)]) +
-                   synth.c1_sine(hops, freq=3000.0, amp=0.2, fs=fs))
 
 
 class Stream:
@@ -76,7 +31,7 @@ class Stream:
         if long_blocks:
             self.shapes = np.array([(i * HOP, HOP, HOP) for i in range(pcm.shape[1] // HOP - 1)], np.int64)
         else:
-            self.shapes = _shapes(self.h, pcm)
+            self.shapes = kit.shapes_to_last_long(self.h, pcm)
         self.ns = len(self.shapes) * HOP
         self.src = vr.source_of(pcm, self.shapes, HOP)
         self._got, self._want = {}, {}
@@ -102,18 +57,18 @@ _STREAMS = {}
 def _stream(name):
     if name not in _STREAMS:
         if name == "stereo":
-            s = Stream(_clicks(12, 11, False))
+            s = Stream(kit.clicks(12, 11, False, period=5))
             assert len({(int(a), int(b)) for (_, a, b) in s.shapes}) == 4, "all four block shapes"
         elif name == "mono":
-            s = Stream(_clicks(12, 11, True))
+            s = Stream(kit.clicks(12, 11, True, period=5))
             assert len({(int(a), int(b)) for (_, a, b) in s.shapes}) == 4, "all four block shapes"
         elif name == "hi96":
-            s = Stream(_noise(6, 3, 96000), rate=96000, long_blocks=True)
+            s = Stream(kit.noise(6, 3, 96000), rate=96000, long_blocks=True)
         elif name == "exact":
-            s = Stream(_clicks(12, 11, False), exact=True)
+            s = Stream(kit.clicks(12, 11, False, period=5), exact=True)
         else:                                            # "s<k>": the streams of the 5-stream call, 4 .. 12 hops
             k = int(name[1:])
-            s = Stream(_clicks(4 + 2 * k, 40 + 3 * k, bool(k & 1)))
+            s = Stream(kit.clicks(4 + 2 * k, 40 + 3 * k, bool(k & 1), period=5))
         _STREAMS[name] = s
     return _STREAMS[name]
 
@@ -224,13 +179,7 @@ def test_independent_of_slabs_batching_and_entry_point():
     # one call of the three stereo streams, one of the two mono streams, rows padded to one stride
     for mono in (False, True):
         sel = [s for s in streams if s.mono == mono]
-        stride = max(s.pcm.shape[1] for s in sel)
-        left = np.zeros((len(sel), stride), np.int16)
-        right = None if mono else np.zeros((len(sel), stride), np.int16)
-        for i, s in enumerate(sel):
-            left[i, :s.pcm.shape[1]] = s.pcm[0]
-            if not mono:
-                right[i, :s.pcm.shape[1]] = s.pcm[1]
+        left, right, stride = kit.rows([s.pcm for s in sel])
         shapes, ns = [s.shapes for s in sel], [s.ns for s in sel]
         many = h.encode_vbr_nmr_pac(left, right, shapes, db, num_samples=ns)
         for s, m in zip(sel, many):
@@ -262,23 +211,11 @@ def test_independent_of_slabs_batching_and_entry_point():
         assert not host[total:].any()
 
 
-def _long_short_run():
-    """one mono stream whose (S,S) blocks do not fit one batch of the source analysis (16384 blocks of one shape):
-    (L,S), 16384 + 5 x (S,S), (S,L) -- int16 [1][n], its shapes, its sample count"""
-    S, n_ss = 128, 16384 + 5
-    a = np.array([HOP] + [S] * (n_ss + 1), np.int64)
-    b = np.array([S] * (n_ss + 1) + [HOP], np.int64)
-    off = np.concatenate([[0], np.cumsum(a)[:-1]])
-    shapes = np.stack([off, a, b], axis=1)
-    hops = -(-int(off[-1] + a[-1] + b[-1]) // HOP)
-    return _clicks(hops, 11, True), shapes, int(b.sum())
-
-
 def test_second_batch_of_one_shape_equals_single_batch_slabs():
     """Inside a slab the blocks of one shape are analysed 16384 at a time.  4096-block slabs: time slabs of one batch each,
     the path of every other test; the default slab: one slab whose (S,S) group is a full batch and a batch of five."""
     h = _handle()
-    pcm, shapes, ns = _long_short_run()
+    pcm, shapes, ns = kit.long_short_run(period=5)
     run = lambda: h.encode_vbr_nmr_pac(pcm, None, [shapes], -6.0, num_samples=[ns])[0]
     try:
         h.set_option(6, 4096)
@@ -385,8 +322,7 @@ def test_cli_vbr_nmr(tmp_path, capsys):
     # the WAV: the stream without its prior hop, up to the end of its last block, and one more hop the encoder never codes
     pcm = np.concatenate([s.src, np.zeros((2, HOP), np.int16)], axis=1)
     wav, dst, back = str(tmp_path / "in.wav"), str(tmp_path / "out.pac"), str(tmp_path / "back.wav")
-    with open(wav, "wb") as f:
-        f.write(cli.wav_bytes(pcm, 48000))
+    kit.write_wav(wav, pcm)
     capsys.readouterr()
     cli.main([wav, dst, "--vbr-nmr", "0"])
     line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])

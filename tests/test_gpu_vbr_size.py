@@ -5,7 +5,7 @@ Handle.encode_vbr_size_pac, pacfile.encode_stream_vbr_size, cli --vbr-bytes).
 The reference of every assertion is the EXISTING call, Handle.encode_vbr_nmr_pac, never the new one: per stream the file at
 every ceiling of a small grid gives the table bytes(i); the targets are taken from that table when the test runs; the search
 the new call reports must be pacfile.bisect_ceiling over the table, its file and numbers the existing call's at the chosen
-ceiling.  Every comparison is equality.  The content is that of tests/test_gpu_vbr.py (the generator parameters are copied).
+ceiling.  Every comparison is equality.  The content is that of tests/test_gpu_vbr.py (the same generators and parameters).
 """
 import ctypes as C
 import json
@@ -14,58 +14,20 @@ import math
 import numpy as np
 import pytest
 
+import chain_kit as kit
+from chain_kit import HOP, handle as _handle
+
 pytestmark = pytest.mark.gpu
-HOP = 1024
 LO, STEP, N = -12.0, 3.0, 8
 SLAB_OPT, SLAB_DEFAULT = 6, 131072
 NUMBERS = ("ceiling_ratio", "capped_bands", "coded_bits", "nmr_total_db", "nmr_max_db", "disturbed_blocks", "n_blocks")
-_HANDLES = {}
-
-
-def _handle(exact=False, rate=48000):
-    from mrcaudiocodec_amd import Handle
-    if (exact, rate) not in _HANDLES:
-        _HANDLES[(exact, rate)] = Handle(sample_rate=rate, device_id=0)
-        if exact:
-            _HANDLES[(exact, rate)].set_option(1, 1)
-    return _HANDLES[(exact, rate)]
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _close_handles():
     yield
-    for hd in _HANDLES.values():
-        hd.close()
-    _HANDLES.clear()
+    kit.close_handles()
     _STREAMS.clear()
-
-
-def _to_pcm(x):
-    pcm = np.clip(np.rint(np.atleast_2d(x) * 32767.5), -32767, 32767).astype(np.int16)
-    pcm[:, :HOP] = 0
-    return pcm
-
-
-def _clicks(hops, seed, mono, period=5, fs=48000):
-    """noise floor + bursts (synth.c4_transients, a seed per channel) and a tone common to the channels, so that M/S bands
-    occur beside L/R bands: int16 [nCh][(hops + 1) * HOP]"""
-    from mrcaudiocodec_amd import synth
-    chans = [synth.c4_transients(hops, seed=seed + c, period=period)[0] for c in range(1 if mono else 2)]
-    tone = synth.c1_sine(hops, freq=440.0 + seed, amp=0.1, fs=fs)[:len(chans[0])]
-    return _to_pcm(np.stack(chans) + tone)
-
-
-def _noise(hops, seed, fs):
-    from mrcaudiocodec_amd import synth
-    return _to_pcm(np.stack([synth.c2_noise(hops, seed=seed + c, sigma=0.05) for c in range(2)]) +
-                   synth.c1_sine(hops, freq=3000.0, amp=0.2, fs=fs))
-
-
-def _shapes(h, pcm):
-    from mrcaudiocodec_amd import transient
-    shapes = transient.block_shape_array(h, pcm)
-    last = np.nonzero(shapes[:, 2] == HOP)[0][-1]
-    return shapes[:last + 1]
 
 
 def _grid_db(i, lo=LO, step=STEP):
@@ -80,7 +42,7 @@ class Stream:
         if long_blocks:
             self.shapes = np.array([(i * HOP, HOP, HOP) for i in range(pcm.shape[1] // HOP - 1)], np.int64)
         else:
-            self.shapes = _shapes(self.h, pcm)
+            self.shapes = kit.shapes_to_last_long(self.h, pcm)
         self.ns = len(self.shapes) * HOP
         self._ref = {}
 
@@ -109,13 +71,13 @@ _STREAMS = {}
 def _stream(name):
     if name not in _STREAMS:
         if name in ("stereo", "mono", "raw", "exact"):
-            s = Stream(_clicks(12, 11, name == "mono"), exact=name == "exact", huffman=name != "raw")
+            s = Stream(kit.clicks(12, 11, name == "mono", period=5), exact=name == "exact", huffman=name != "raw")
             assert len({(int(a), int(b)) for (_, a, b) in s.shapes}) == 4, "all four block shapes"
         elif name == "hi96":
-            s = Stream(_noise(6, 3, 96000), rate=96000, long_blocks=True)
+            s = Stream(kit.noise(6, 3, 96000), rate=96000, long_blocks=True)
         else:                                            # "s<k>" stereo, "m<k>" mono: the many-stream calls, 4 .. 12 hops
             k = int(name[1:])
-            s = Stream(_clicks(4 + 2 * k, 40 + 3 * k, name[0] == "m"))
+            s = Stream(kit.clicks(4 + 2 * k, 40 + 3 * k, name[0] == "m", period=5))
         _STREAMS[name] = s
     return _STREAMS[name]
 
@@ -168,18 +130,6 @@ def test_the_content_has_ms_bands_lr_bands_and_capped_bands():
     assert tight["data"] == want["data"]
 
 
-def _rows(sel):
-    stride = max(s.pcm.shape[1] for s in sel)
-    mono = sel[0].mono
-    left = np.zeros((len(sel), stride), np.int16)
-    right = None if mono else np.zeros((len(sel), stride), np.int16)
-    for i, s in enumerate(sel):
-        left[i, :s.pcm.shape[1]] = s.pcm[0]
-        if not mono:
-            right[i, :s.pcm.shape[1]] = s.pcm[1]
-    return left, right, stride
-
-
 def _many(prefix, count):
     """`count` streams of one kind, each with its table and a target of its own: stream i aims at bytes(1 + i mod (N - 2))"""
     sel = [_stream("%s%d" % (prefix, k)) for k in range(count)]
@@ -193,7 +143,7 @@ def test_streams_of_one_call_search_independently_whatever_the_slabs(prefix, cou
     sel, tables, targets = _many(prefix, count)
     h = sel[0].h
     assert len({len(s.shapes) for s in sel}) == count, "different lengths"
-    left, right, _ = _rows(sel)
+    left, right, _ = kit.rows([s.pcm for s in sel])
     shapes, ns = [s.shapes for s in sel], [s.ns for s in sel]
     many = h.encode_vbr_size_pac(left, right, shapes, targets, LO, STEP, N, num_samples=ns)
     for s, m, t, tab in zip(sel, many, targets, tables):
@@ -218,7 +168,7 @@ def test_device_entry_point():
     import torch
     sel, tables, targets = _many("s", 5)
     h = sel[0].h
-    left, right, stride = _rows(sel)
+    left, right, stride = kit.rows([s.pcm for s in sel])
     shapes, ns = [s.shapes for s in sel], [s.ns for s in sel]
     host = h.encode_vbr_size_pac(left, right, shapes, targets, LO, STEP, N, num_samples=ns)
     dev = torch.device("cuda", 0)
@@ -258,13 +208,8 @@ def test_second_batch_of_one_shape_equals_the_existing_call_in_single_batch_slab
     """Inside a slab the blocks of one shape are recorded 16384 at a time.  One mono stream of (L,S), 16384 + 5 x (S,S), (S,L):
     the search keeps it in one slab (the default capacity, less the record, still holds its 16391 blocks), so its (S,S) group
     is a full batch and a batch of five; the existing call under 4096-block slabs runs single batches only."""
-    S, n_ss = 128, 16384 + 5
-    a = np.array([HOP] + [S] * (n_ss + 1), np.int64)
-    b = np.array([S] * (n_ss + 1) + [HOP], np.int64)
-    off = np.concatenate([[0], np.cumsum(a)[:-1]])
-    shapes = np.stack([off, a, b], axis=1)
-    pcm = _clicks(-(-int(off[-1] + a[-1] + b[-1]) // HOP), 11, True)
-    ns, db = int(b.sum()), -6.0
+    pcm, shapes, ns = kit.long_short_run(period=5)
+    db = -6.0
     h = _handle()
     try:
         h.set_option(SLAB_OPT, 4096)
@@ -413,8 +358,7 @@ def test_cli_vbr_bytes(tmp_path, capsys):
     # the WAV: the stream without its prior hop, up to the end of its last block, and one more (silent) hop that is never coded
     pcm = np.concatenate([s.pcm[:, HOP:HOP + s.ns], np.zeros((2, HOP), np.int16)], axis=1)
     wav, dst = str(tmp_path / "in.wav"), str(tmp_path / "out.pac")
-    with open(wav, "wb") as f:
-        f.write(cli.wav_bytes(pcm, 48000))
+    kit.write_wav(wav, pcm)
     h = s.h
     codes = np.concatenate([np.zeros((2, HOP), np.int16), pcm], axis=1)
     from mrcaudiocodec_amd import transient

@@ -3,43 +3,18 @@ CPU-side checks of the encode to a target noise-to-mask ratio: the library expor
 declares them with the header's argument lists, the rule helper on hand-written tables, and the command line's refusals,
 which come before a file is read or a device is touched.  No kernel is launched here.
 """
-import ctypes as C
 import math
-import os
-import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from chain_kit import check_binding, header_args
+
 NAMES = ("mrc_encode_chained_target_nmr_pac", "mrc_dev_encode_chained_target_nmr_pac", "mrc_get_target_ms")
 
 
-def _header_args(name):
-    text = open(os.path.join(ROOT, "include", "mrc_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    m = re.search(r"\bint\s+%s\s*\((.*?)\)\s*;" % name, text, flags=re.S)
-    assert m, name
-    return [" ".join(a.split()) for a in m.group(1).split(",")]
-
-
 def test_binding_matches_the_header():
-    from mrcaudiocodec_amd import _lib
-    raw = C.CDLL(_lib.LIB_PATH)
-    for name in NAMES:
-        assert hasattr(raw, name) and name in _lib.EXPORTS
-        fn = getattr(_lib.lib, name)
-        args = _header_args(name)
-        assert fn.restype is C.c_int and len(fn.argtypes) == len(args), (name, len(fn.argtypes), len(args))
-        for decl, typ in zip(args, fn.argtypes):
-            if "*" in decl:
-                assert typ is C.c_void_p or issubclass(typ, C._Pointer), (name, decl, typ)
-            elif decl.startswith("double"):
-                assert typ is C.c_double, (name, decl)
-            elif decl.startswith("int64_t"):
-                assert typ is C.c_int64, (name, decl)
-            else:
-                assert decl.startswith("int ") and typ is C.c_int, (name, decl)
-    host, dev = _header_args(NAMES[0]), _header_args(NAMES[1])
+    check_binding(NAMES)
+    host, dev = header_args(NAMES[0]), header_args(NAMES[1])
     assert dev[:-1] == host and dev[-1] == "void* stream"
     assert host[3] == "double target_nmr_total_db" and host[-1] == "int64_t* total_bytes"
     from mrcaudiocodec_amd import Handle, pacfile

@@ -4,58 +4,25 @@ the header's argument lists; the NumPy restatement of the rule (tests/vbr_restat
 parser and the oracle's decoder read, every band of them is first-fit, and the measure of the file stays under the ceiling;
 the command line's refusals come before a file is read or a device is touched.  No kernel is launched here.
 """
-import ctypes as C
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 
 import nmr_restatement as nr
 import vbr_restatement as vr
+from chain_kit import HOP, check_binding, header_args, to_pcm as _to_pcm
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("mrc_encode_vbr_nmr_pac", "mrc_dev_encode_vbr_nmr_pac", "mrc_get_vbr_ms")
-HOP = 1024
-
-
-def _header_args(name):
-    text = open(os.path.join(ROOT, "include", "mrc_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    m = re.search(r"\bint\s+%s\s*\((.*?)\)\s*;" % name, text, flags=re.S)
-    assert m, name
-    return [" ".join(a.split()) for a in m.group(1).split(",")]
 
 
 def test_binding_matches_the_header():
-    from mrcaudiocodec_amd import _lib
-    raw = C.CDLL(_lib.LIB_PATH)
-    for name in NAMES:
-        assert hasattr(raw, name) and name in _lib.EXPORTS
-        fn = getattr(_lib.lib, name)
-        args = _header_args(name)
-        assert fn.restype is C.c_int and len(fn.argtypes) == len(args), (name, len(fn.argtypes), len(args))
-        for decl, typ in zip(args, fn.argtypes):
-            if "*" in decl:
-                assert typ is C.c_void_p or issubclass(typ, C._Pointer), (name, decl, typ)
-            elif decl.startswith("double"):
-                assert typ is C.c_double, (name, decl)
-            elif decl.startswith("int64_t"):
-                assert typ is C.c_int64, (name, decl)
-            else:
-                assert decl.startswith("int ") and typ is C.c_int, (name, decl)
-    host, dev = _header_args(NAMES[0]), _header_args(NAMES[1])
+    check_binding(NAMES)
+    host, dev = header_args(NAMES[0]), header_args(NAMES[1])
     assert dev[:-1] == host and dev[-1] == "void* stream"
     assert host[1] == "double ceiling_db" and host[-1] == "int64_t* total_bytes"
     from mrcaudiocodec_amd import Handle, pacfile
     assert callable(Handle.encode_vbr_nmr_pac) and callable(pacfile.encode_stream_vbr_nmr)
-
-
-def _to_pcm(x):
-    pcm = np.clip(np.rint(np.atleast_2d(x) * 32767.5), -32767, 32767).astype(np.int16)
-    pcm[:, :HOP] = 0
-    return pcm
 
 
 def _stream(mono, hops=10, seed=11):

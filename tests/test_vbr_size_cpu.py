@@ -4,53 +4,27 @@ points and the binding declares them with the header's argument lists; pacfile.b
 host and is held against hand-made size tables; the grid is lo + i * step in double; the command line's refusals come before
 a file is read or a device is touched, and --vbr-bits-per-sample becomes bytes by the stated formula.  No kernel is launched.
 """
-import ctypes as C
-import os
 import re
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from chain_kit import check_binding, header_args, header_text
+
 NAMES = ("mrc_encode_vbr_size_pac", "mrc_dev_encode_vbr_size_pac", "mrc_get_vbr_size_ms")
-
-
-def _header_text():
-    text = open(os.path.join(ROOT, "include", "mrc_hip.h")).read()
-    return text, re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-
-
-def _header_args(name):
-    m = re.search(r"\bint\s+%s\s*\((.*?)\)\s*;" % name, _header_text()[1], flags=re.S)
-    assert m, name
-    return [" ".join(a.split()) for a in m.group(1).split(",")]
 
 
 def test_binding_matches_the_header():
     from mrcaudiocodec_amd import _lib
-    raw = C.CDLL(_lib.LIB_PATH)
-    for name in NAMES:
-        assert hasattr(raw, name) and name in _lib.EXPORTS
-        fn = getattr(_lib.lib, name)
-        args = _header_args(name)
-        assert fn.restype is C.c_int and len(fn.argtypes) == len(args), (name, len(fn.argtypes), len(args))
-        for decl, typ in zip(args, fn.argtypes):
-            if "*" in decl:
-                assert typ is C.c_void_p or issubclass(typ, C._Pointer), (name, decl, typ)
-            elif decl.startswith("double"):
-                assert typ is C.c_double, (name, decl)
-            elif decl.startswith("int64_t"):
-                assert typ is C.c_int64, (name, decl)
-            else:
-                assert decl.startswith("int ") and typ is C.c_int, (name, decl)
-    host, dev = _header_args(NAMES[0]), _header_args(NAMES[1])
+    check_binding(NAMES)
+    host, dev = header_args(NAMES[0]), header_args(NAMES[1])
     assert dev[:-1] == host and dev[-1] == "void* stream"
     assert host[1:5] == ["double ceiling_lo_db", "double ceiling_step_db", "int n_ceilings", "const int64_t* target_bytes"]
     assert host[-1] == "int64_t* total_bytes"
     # behind the grid and the targets: the VBR call's stream arguments, in its order
-    vbr = _header_args("mrc_encode_vbr_nmr_pac")
+    vbr = header_args("mrc_encode_vbr_nmr_pac")
     assert host[5:5 + 13] == vbr[2:2 + 13]
-    text = _header_text()[0]
+    text = header_text(comments=True)
     assert re.search(r"#define\s+MRC_MAX_CEILINGS\s+256\b", text) and re.search(r"#define\s+MRC_MAX_PROBES\s+9\b", text)
     assert (_lib.MRC_MAX_CEILINGS, _lib.MRC_MAX_PROBES) == (256, 9)
     from mrcaudiocodec_amd import Handle, pacfile
