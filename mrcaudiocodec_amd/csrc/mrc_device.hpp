@@ -29,13 +29,22 @@ __device__ __forceinline__ double pcm16_to_frac(int c) {
 // one sample of a channel held as float64 signed fractions or as int16 PCM codes
 __device__ __forceinline__ double sample_of(const double* __restrict__ p, int64_t i) { return p[i]; }
 __device__ __forceinline__ double sample_of(const short* __restrict__ p, int64_t i) { return pcm16_to_frac(p[i]); }
-// an (even, odd) sample pair at an EVEN index: one 16-byte / 4-byte load
-__device__ __forceinline__ double2 pair_of(const double* __restrict__ p, int64_t i) {
-    return *reinterpret_cast<const double2*>(p + i);
+// An (even, odd) sample pair in two steps, so that a caller can request the raw words of many pairs before it converts
+// the first: raw_pair is the load and nothing else (ALIGNED -- even index, base aligned to the pair size: one 16-byte /
+// 4-byte load; else one load per sample), pair_value the conversion of what it returned.
+template <bool ALIGNED>
+__device__ __forceinline__ double2 raw_pair(const double* __restrict__ p, int64_t i) {
+    if constexpr (ALIGNED) return *reinterpret_cast<const double2*>(p + i);
+    else return make_double2(p[i], p[i + 1]);
 }
-__device__ __forceinline__ double2 pair_of(const short* __restrict__ p, int64_t i) {
-    const int v = *reinterpret_cast<const int*>(p + i);
-    return make_double2(pcm16_to_frac((short)(v & 0xffff)), pcm16_to_frac(v >> 16));
+template <bool ALIGNED>
+__device__ __forceinline__ int raw_pair(const short* __restrict__ p, int64_t i) {
+    if constexpr (ALIGNED) return *reinterpret_cast<const int*>(p + i);
+    else return (int)(unsigned short)p[i] | ((int)p[i + 1] << 16);
+}
+__device__ __forceinline__ double2 pair_value(double2 raw) { return raw; }
+__device__ __forceinline__ double2 pair_value(int raw) {
+    return make_double2(pcm16_to_frac((short)(raw & 0xffff)), pcm16_to_frac(raw >> 16));
 }
 
 // The four signals of a joint block: L, R, M=(L+R)/2, S=(L-R)/2 (codecThem.py:363-364).
@@ -46,18 +55,6 @@ __device__ __forceinline__ double load_signal(const T* __restrict__ L, const T* 
     double l = sample_of(L, i), r = sample_of(R, i);
     return sig == 2 ? (l + r) / 2.0 : (l - r) / 2.0;
 }
-// ... as (even, odd) pairs; `aligned`: index even and base aligned to the pair size (wave-uniform)
-template <class T>
-__device__ __forceinline__ double2 load_signal_pair(const T* __restrict__ L, const T* __restrict__ R, int64_t i, int sig,
-                                                    bool aligned) {
-    if (!aligned)
-        return make_double2(load_signal(L, R, i, sig), load_signal(L, R, i + 1, sig));
-    if (sig == 0) return pair_of(L, i);
-    if (sig == 1) return pair_of(R, i);
-    const double2 l = pair_of(L, i), r = pair_of(R, i);
-    return sig == 2 ? make_double2((l.x + r.x) / 2.0, (l.y + r.y) / 2.0) : make_double2((l.x - r.x) / 2.0, (l.y - r.y) / 2.0);
-}
-
 // MI355X: 8 XCDs, consecutive workgroup ids go to consecutive XCDs.  Maps hardware block id b of a 1-D grid of g
 // blocks to a work unit such that XCD x (the blocks with b % 8 == x) gets a contiguous range of units.  A bijection
 // for every g.

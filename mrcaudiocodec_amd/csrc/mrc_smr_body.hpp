@@ -111,8 +111,9 @@ __device__ __forceinline__ void smr_body(DevShape S, int nsigArg, const SampleT*
     unsigned long long* ratioKey = reinterpret_cast<unsigned long long*>(smem + 2 * H - kExpTab - kMaxBands);
     const double* logTabLds = smem + lay.logOff;
     const double* logTab = logTabLds;
-    // Hann window (window.py:28-45) and real FFT through an H = N/2 point complex FFT.  All global loads of a
-    // thread are issued before the first use: one memory round trip per phase instead of one per iteration.
+    // Hann window (window.py:28-45) and real FFT through an H = N/2 point complex FFT.  The raw words of a thread's
+    // kPre sample pairs and their Hann values are all requested before the first of them is converted (`front` below;
+    // the long block is one such group): one memory round trip per group instead of one per pair.
     constexpr int kPre = 4;
     // (even, odd) sample pairs come as ONE load each when the block starts at an even sample of an aligned channel
     const bool pairAligned = !(off & 1) && !(reinterpret_cast<uintptr_t>(chL) & (2 * sizeof(SampleT) - 1)) &&
@@ -124,24 +125,44 @@ __device__ __forceinline__ void smr_body(DevShape S, int nsigArg, const SampleT*
     [[maybe_unused]] double2 fftIn[4];
     [[maybe_unused]] Tw3 fftW1;
     if constexpr (kFftRegs) fftW1 = fft1024_twiddles(S.fftTw, 1, tid);
-    for (int n0 = tid; n0 < H; n0 += NT * kPre) {
-        double e[kPre], o[kPre], he[kPre], ho[kPre];
+    // One arm per (alignment, signal kind), chosen once per unit (both are wave-uniform): decided per pair, each pair's
+    // load ended up in a basic block of its own with a full wait behind it -- four dependent round trips for int16 PCM.
+    // MS: the M / S signals, which read both channels; else the one channel of L or R.
+    auto front = [&](auto alignedC, auto msC) {
+        constexpr bool AL = decltype(alignedC)::value, MS = decltype(msC)::value;
+        const SampleT* const one = MS ? chL : (sig == 1 ? chR : chL);
+        for (int n0 = tid; n0 < H; n0 += NT * kPre) {
+            decltype(raw_pair<AL>(one, 0)) rawL[kPre];
+            [[maybe_unused]] decltype(raw_pair<AL>(one, 0)) rawR[kPre];
+            double2 hn[kPre];
 #pragma unroll
-        for (int u = 0; u < kPre; ++u) {
-            const int n = min(n0 + u * NT, H - 1);
-            const double2 eo = load_signal_pair(chL, chR, off + 2 * n, sig, pairAligned);
-            e[u] = eo.x;
-            o[u] = eo.y;
-            he[u] = S.hann[2 * n];
-            ho[u] = S.hann[2 * n + 1];
-        }
+            for (int u = 0; u < kPre; ++u) {
+                const int n = min(n0 + u * NT, H - 1);
+                rawL[u] = raw_pair<AL>(one, off + 2 * n);
+                if constexpr (MS) rawR[u] = raw_pair<AL>(chR, off + 2 * n);
+                hn[u] = make_double2(S.hann[2 * n], S.hann[2 * n + 1]);
+            }
 #pragma unroll
-        for (int u = 0; u < kPre; ++u) {
-            const int n = n0 + u * NT;
-            if constexpr (kFftRegs) fftIn[u] = make_double2(e[u] * he[u], o[u] * ho[u]);
-            else if (n < H) A[n] = make_double2(e[u] * he[u], o[u] * ho[u]);
+            for (int u = 0; u < kPre; ++u) {
+                const int n = n0 + u * NT;
+                double2 eo = pair_value(rawL[u]);
+                if constexpr (MS) {                      // codecThem.py:363-364
+                    const double2 r = pair_value(rawR[u]);
+                    eo = sig == 2 ? make_double2((eo.x + r.x) / 2.0, (eo.y + r.y) / 2.0)
+                                  : make_double2((eo.x - r.x) / 2.0, (eo.y - r.y) / 2.0);
+                }
+                if constexpr (kFftRegs) fftIn[u] = make_double2(eo.x * hn[u].x, eo.y * hn[u].y);
+                else if (n < H) A[n] = make_double2(eo.x * hn[u].x, eo.y * hn[u].y);
+            }
         }
-    }
+    };
+    auto front_kind = [&](auto alignedC) {
+        if constexpr (MODE == 1) front(alignedC, std::false_type{});
+        else if (sig >= 2) front(alignedC, std::true_type{});
+        else front(alignedC, std::false_type{});
+    };
+    if (pairAligned) front_kind(std::true_type{});
+    else front_kind(std::false_type{});
     // (the unit's scale is first used in the sweep: requested here, it arrives under the wait for the samples)
     const int scale = oscale[unit];
     const double xiInv = 1.0 / S.xiDen;

@@ -14,6 +14,7 @@
 #include "mrc_smr_math.hpp"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace mrc {
 using namespace dev;
@@ -111,13 +112,39 @@ __global__ __launch_bounds__(kWave * kShortWaves) __attribute__((amdgpu_waves_pe
         const int64_t off = offsets ? offsets[f] : f * stride;
         const bool pairAligned = !(off & 1) && !(reinterpret_cast<uintptr_t>(chL) & (2 * sizeof(SampleT) - 1)) &&
                                  (!chR || !(reinterpret_cast<uintptr_t>(chR) & (2 * sizeof(SampleT) - 1)));
-        // Hann window (window.py:28-45), real FFT through a 128-point complex FFT
+        // Hann window (window.py:28-45), real FFT through a 128-point complex FFT.  One arm per (alignment, signal kind),
+        // both wave-uniform: the raw words of the lane's two pairs are requested before the first is converted (decided
+        // per pair, each load had a branch and a full wait of its own: see smr_body's front end)
+        auto front = [&](auto alignedC, auto msC) {
+            constexpr bool AL = decltype(alignedC)::value, MS = decltype(msC)::value;
+            const SampleT* const one = MS ? chL : (sig == 1 ? chR : chL);
+            decltype(raw_pair<AL>(one, 0)) rawL[2];
+            [[maybe_unused]] decltype(raw_pair<AL>(one, 0)) rawR[2];
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int n = lane + kWave * j;
-            const double2 eo = load_signal_pair(chL, chR, off + 2 * n, sig, pairAligned);
-            A[n] = make_double2(eo.x * he[j], eo.y * ho[j]);
-        }
+            for (int j = 0; j < 2; ++j) {
+                const int n = lane + kWave * j;
+                rawL[j] = raw_pair<AL>(one, off + 2 * n);
+                if constexpr (MS) rawR[j] = raw_pair<AL>(chR, off + 2 * n);
+            }
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int n = lane + kWave * j;
+                double2 eo = pair_value(rawL[j]);
+                if constexpr (MS) {                      // codecThem.py:363-364
+                    const double2 r = pair_value(rawR[j]);
+                    eo = sig == 2 ? make_double2((eo.x + r.x) / 2.0, (eo.y + r.y) / 2.0)
+                                  : make_double2((eo.x - r.x) / 2.0, (eo.y - r.y) / 2.0);
+                }
+                A[n] = make_double2(eo.x * he[j], eo.y * ho[j]);
+            }
+        };
+        auto front_kind = [&](auto alignedC) {
+            if constexpr (MODE == 1) front(alignedC, std::false_type{});
+            else if (sig >= 2) front(alignedC, std::true_type{});
+            else front(alignedC, std::false_type{});
+        };
+        if (pairAligned) front_kind(std::true_type{});
+        else front_kind(std::false_type{});
         if (lane < 32) { ratioKey[lane] = 0ull; bandKey[lane] = 0ull; peakKey[lane] = 0ull; }
         const int scale = oscale[unit];
         const double* X = lines + unit * M;
