@@ -744,6 +744,70 @@ int mrc_pac_nmr(mrc_handle* h, int64_t n_files, const uint8_t* buf, const int64_
  * (padding, MDCT and masked thresholds), [3] NMR kernels + device -> host copy. */
 int mrc_get_nmr_ms(mrc_handle* h, double* ms /*[4]*/);
 
+/* ---- resident `.pac` store: sample windows of many files, decoded into device tensors ----
+ * Upload the files once, then cut windows from them for ever: no file byte crosses PCIe again, a call parses and
+ * synthesises only the blocks its windows overlap, and the result is written where the caller wants it on the device, in the
+ * format the caller wants.
+ *
+ * mrc_pac_index (host only: no GPU, no handle): headers, chunk lengths and each chunk's block-switch bits of ONE `.pac` file
+ * -> where every block lies.  cfg: n_short and blksw_bits_a / _b are read from it; sample_rate, n_mdct_lines, n_scale_bits
+ * and n_mant_size_bits must equal the file's (MRC_ERR_INVALID naming the parameter, as mrc_decode_pac_pcm16 words it).
+ * Block i: block_start[i] = a_0 + .. + a_{i-1} (its position in the padded plane: n_mdct_lines zeros, the samples, zeros),
+ * block_a / block_b [i], chunk_offset[i * n_channels + c] (byte offset of the chunk's 4-byte length in buf).
+ * n_samples = max(0, block_start[last] + a_last + b_last - n_mdct_lines): what mrc_decode_pac_pcm16 returns per channel.
+ * block_cap too small (or an array NULL while the file has blocks): MRC_ERR_NOMEM with n_channels, n_blocks and n_samples
+ * filled and the arrays untouched.  Refusals (MRC_ERR_INVALID, the text from mrc_last_error(NULL)) are exactly those of
+ * mrc_decode_pac_pcm16's host plan: no header, a truncated chunk, a chunk without a block shape, a chunk count that is no
+ * multiple of the channels, a block whose chunks differ in shape. */
+int mrc_pac_index(const mrc_config* cfg, const uint8_t* buf, int64_t len, int32_t* n_channels, int64_t* n_blocks,
+                  int64_t* n_samples, int64_t block_cap, int64_t* block_start, int32_t* block_a, int32_t* block_b,
+                  int64_t* chunk_offset);
+
+typedef struct mrc_pac_store mrc_pac_store;
+#define MRC_WINDOW_PCM16 0   /* int16: the codes mrc_decode_pac_pcm16 writes */
+#define MRC_WINDOW_F32   1   /* (float) of the F64 value, round to nearest even */
+#define MRC_WINDOW_F64   2   /* the overlap-added signed fraction before the PCM quantiser */
+
+/* mrc_pac_store_create: n_files whole `.pac` files, file f = buf[file_offset[f], file_offset[f + 1]) in host memory, checked
+ * exactly as mrc_decode_pac_pcm16 checks them (the same refusals and texts, under this function's name), copied to the
+ * handle's device ONCE and indexed on the host as mrc_pac_index does.  No chunk payload is parsed.  The store belongs to h
+ * and must be destroyed before it: after mrc_destroy(h) every call on the store except mrc_pac_store_destroy returns
+ * MRC_ERR_INVALID (text from mrc_last_error(NULL)), its device memory having gone with the handle.  Calls on one handle,
+ * those on its stores included, are serialised by the caller.  Errors of the store's calls are read with mrc_last_error(h).
+ * mrc_pac_store_destroy(NULL) does nothing.
+ * mrc_pac_store_info: the file count, per file (each array NULL or [n_files]) its channels, samples per channel and
+ * blocks, and the device memory the store holds. */
+int mrc_pac_store_create(mrc_handle* h, int64_t n_files, const uint8_t* buf, const int64_t* file_offset /*[n_files+1]*/,
+                         mrc_pac_store** out);
+void mrc_pac_store_destroy(mrc_pac_store* s);
+int mrc_pac_store_info(mrc_pac_store* s, int64_t* n_files, int32_t* n_channels /*NULL or [n_files]*/,
+                       int64_t* n_samples /*NULL or [n_files]*/, int64_t* n_blocks /*NULL or [n_files]*/,
+                       int64_t* device_bytes);
+/* mrc_pac_store_decode_window: out[i][c][t] (DEVICE memory, [n_items][n_channels_out][window] of the format's type) = sample
+ * start[i] + t of channel c of file file[i], in the coordinates of mrc_decode_pac_pcm16's output (the MDCT's first
+ * n_mdct_lines samples already dropped), and exactly +0.0 / 0 where start[i] + t lies outside [0, n_samples): start may be
+ * negative or past the end.  MRC_WINDOW_PCM16 values are bit-identical to that slice of mrc_decode_pac_pcm16's output,
+ * MRC_WINDOW_F64 values to the same slice of the overlap-added plane the 16-bit codes are taken from (each sample is the
+ * same at most two contributions added to zero), MRC_WINDOW_F32 is that value converted once.  A file of n_channels_out
+ * channels maps one to one, a mono file in a two-channel call is written to both channels, a stereo file in a one-channel
+ * call is refused.  An item's result does not depend on what shares the call, on the order of the items or on the slab size.
+ * Work follows the windows, not the files: only the chunks of blocks that overlap a window are parsed -- block i of a file
+ * iff block_start[i] < start + window + n_mdct_lines and block_start[i] + a_i + b_i > start + n_mdct_lines -- so a damaged
+ * chunk inside a window gives MRC_ERR_INVALID (file, byte offset in the file, what the parser met; out is then unspecified)
+ * while a damaged chunk outside every window of the call is never read and never reported.  An item that needs no block is
+ * zeros.  MRC_ERR_INVALID naming the argument, before any device work: file[i] outside the store, window < 0,
+ * n_channels_out not 1 or 2, an unknown format, out == NULL with n_items * window > 0, a stereo file in a one-channel call
+ * (the item is named).  window == 0 or n_items == 0: MRC_OK, nothing written.  The call enqueues on `stream` (NULL: the
+ * handle's) and synchronises it before it returns, because the parser's error word comes back.  A call is cut into slabs
+ * of whole items (MRC_OPT_STORE_SLAB_SAMPLES); the workspace is the handle's, sized by the slab and reused.
+ * mrc_pac_store_stats, for the store's last mrc_pac_store_decode_window: stats = chunks parsed, decode_kernel launches,
+ * slabs, bytes of plan uploaded (no file bytes among them); ms = device time of the plan upload, the unpack kernel, the
+ * synthesis (zeroing the planes + decode_kernel launches) and window_out_kernel, summed over the slabs. */
+int mrc_pac_store_decode_window(mrc_pac_store* s, int64_t n_items, const int64_t* file /*[n_items]*/,
+                                const int64_t* start /*[n_items]*/, int64_t window, int n_channels_out, int format,
+                                void* out /* DEVICE [n_items][n_channels_out][window] */, void* stream);
+int mrc_pac_store_stats(mrc_pac_store* s, int64_t* stats /*[4]*/, double* ms /*[4]*/);
+
 /* Per-stage device time of the most recent timed call when timing is enabled (hipEvents on the launch stream; the call
  * then synchronises).  Timed: mrc_dev_encode / mrc_dev_encode_ex and mrc_encode_mono / mrc_encode_joint (the _blocks
  * forms: their last shape group).  Not timed: the stage calls (mrc_dev_mdct, mrc_dev_smr, mrc_dev_alloc_quant),
@@ -775,6 +839,11 @@ int mrc_set_timing(mrc_handle* h, int enabled);
  * slab costs ~0.25 ms of host work between its neighbours: 8 192 streams x 12 blocks run 5 % slower in two slabs than in
  * one); 65 536: < 4 GB; 0: one slab.  The bytes do not depend on it. */
 #define MRC_OPT_CHAIN_SLAB_BLOCKS 6
+/* MRC_OPT_STORE_SLAB_SAMPLES = n: mrc_pac_store_decode_window cuts a call into slabs, runs of whole items whose windows sum
+ * to at most n samples per channel (an item larger than n runs alone), so that its device memory is bounded by the slab
+ * whatever the size of the call: 16 bytes per sample of margin planes and about as much of parsed chunks for stereo.
+ * Default 2^24 (~270 MB of planes); 0: one slab.  The results do not depend on it. */
+#define MRC_OPT_STORE_SLAB_SAMPLES 7
 int mrc_set_option(mrc_handle* h, int option, int value);
 int mrc_get_option(mrc_handle* h, int option, int32_t* value);
 int mrc_get_stage_ms(mrc_handle* h, double* ms /*[3]*/);

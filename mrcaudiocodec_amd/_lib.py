@@ -18,6 +18,8 @@ MRC_MAX_CEILINGS = 256
 MRC_MAX_PROBES = 9
 MRC_ERR_INVALID = -1
 MRC_ERR_NOMEM = -4
+MRC_WINDOW_PCM16, MRC_WINDOW_F32, MRC_WINDOW_F64 = 0, 1, 2      # mrc_pac_store_decode_window's formats
+MRC_OPT_STORE_SLAB_SAMPLES = 7
 # array arguments travel as plain addresses (c_void_p prototypes): numpy's typed `data_as` costs ~2.3 us per array, which
 # at thirteen arrays per call was a third of a one-block call through the drop-in seam; the names say what the C side expects
 _i32p = _i64p = _f64p = _u8p = C.c_void_p
@@ -191,6 +193,14 @@ def _load():
         "mrc_pac_nmr": (C.c_int, [H, C.c_int64, _u8p, _i64p, C.c_void_p, _i64p, _i64p, _i64p, _f64p, _f64p, _i64p, _i64p,
                                   _i64p, C.c_int64, _i32p, _f64p, _f64p]),
         "mrc_get_nmr_ms": (C.c_int, [H, _f64p]),
+        "mrc_pac_index": (C.c_int, [C.POINTER(MrcConfig), _u8p, C.c_int64, _i32p, _i64p, _i64p, C.c_int64, _i64p, _i32p, _i32p,
+                                    _i64p]),
+        "mrc_pac_store_create": (C.c_int, [H, C.c_int64, _u8p, _i64p, C.POINTER(C.c_void_p)]),
+        "mrc_pac_store_destroy": (None, [C.c_void_p]),
+        "mrc_pac_store_info": (C.c_int, [C.c_void_p, _i64p, _i32p, _i64p, _i64p, _i64p]),
+        "mrc_pac_store_decode_window": (C.c_int, [C.c_void_p, C.c_int64, _i64p, _i64p, C.c_int64, C.c_int, C.c_int, C.c_void_p,
+                                                  C.c_void_p]),
+        "mrc_pac_store_stats": (C.c_int, [C.c_void_p, _i64p, _f64p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = the library does not export the header's symbol

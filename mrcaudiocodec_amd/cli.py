@@ -19,6 +19,9 @@ Decode direction (row f-4):  python -m mrcaudiocodec_amd.cli -d in.pac out.wav
 One library call (mrc_decode_pac_pcm16): chunk parsing and Huffman decoding, dequantise / M-S / IMDCT / window /
 overlap-add and the interleaved 16-bit PCM codes all on the GPU, then the WAV header of pcmfile.py:141-153.  The first decoded block (the MDCT's half-block delay) is dropped as in the
 reference's loop; everything after it is written, header sample count = what was decoded.
+An excerpt:  python -m mrcaudiocodec_amd.cli -d in.pac out.wav --start S --samples N  decodes N samples from sample S of that
+output on through a one-file resident store (mrc_pac_store_decode_window): only the blocks the excerpt overlaps are parsed
+and synthesised.  --start defaults to 0, --samples to the rest of the file; what lies outside the file is silence.
 
 Quality (mrc_pac_nmr): --nmr on an encode prints, per file written (every rung of a ladder), one JSON line with the
 noise-to-mask ratio of the file against the WAV, measured with the codec's own masking model: nmr_max_db (worst band),
@@ -373,14 +376,37 @@ def wav_bytes(pcm, sample_rate):
     return wav_header(n_ch, len(data), sample_rate) + data
 
 
-def decode_pac_file(pac_path, wav_path, device_id=0):
+def check_excerpt_args(start, samples, decode):
+    """--start / --samples as given (None: not given) -> (start, samples or None for "to the end"), or None when neither was
+    given.  They cut an excerpt out of a decode: refused without -d, and a negative sample count is refused."""
+    if start is None and samples is None:
+        return None
+    if not decode:
+        raise ValueError("--start and --samples cut an excerpt out of a decode: they need -d")
+    if samples is not None and samples < 0:
+        raise ValueError("--samples: %d is negative" % samples)
+    return (0 if start is None else int(start)), (None if samples is None else int(samples))
+
+
+def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None):
+    """excerpt: None (the whole file, mrc_decode_pac_pcm16) or (start, samples): that many samples from sample `start` on
+    (samples None: to the end of the file), decoded through a one-file PacStore -- only the blocks the excerpt overlaps are
+    parsed and synthesised; what lies outside the file is silence.  -> int16 [nCh][samples] as written."""
     with open(pac_path, "rb") as fp:
         buf = fp.read()
     cfg, _, _, _ = pacfile.read_header(buf)
     h = Handle(sample_rate=cfg.sample_rate, n_mdct_lines=cfg.n_mdct_lines, n_scale_bits=cfg.n_scale_bits,
                n_mant_size_bits=cfg.n_mant_size_bits, device_id=device_id)
     try:
-        inter = h.decode_pac_pcm16(buf)[0]          # [samples][nCh] in WAV order, parsed and decoded on the device
+        if excerpt is None:
+            inter = h.decode_pac_pcm16(buf)[0]      # [samples][nCh] in WAV order, parsed and decoded on the device
+        else:
+            from .store import PacStore
+            with PacStore(h, [buf]) as store:
+                start, samples = excerpt
+                if samples is None:
+                    samples = max(0, int(store.n_samples[0]) - start)
+                inter = np.ascontiguousarray(store.decode_window([0], [start], samples)[0].cpu().numpy().T)
     finally:
         h.close()
     data = inter.astype("<i2", copy=False)
@@ -495,8 +521,16 @@ def main(argv=None):
     ap.add_argument("--vbr-grid", default=None, metavar="LO:STEP:N",
                     help="the ceilings --vbr-bytes / --vbr-bits-per-sample search: LO + i * STEP dB, i < N <= 256 "
                          "(default -30:0.25:256)")
+    ap.add_argument("--start", type=int, default=None, metavar="S",
+                    help="with -d: decode an excerpt that starts at sample S of the decoded file (default 0)")
+    ap.add_argument("--samples", type=int, default=None, metavar="N",
+                    help="with -d: decode an excerpt of N samples (default: to the end of the file)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(_join_vbr_grid(sys.argv[1:] if argv is None else argv))
+    try:
+        excerpt = check_excerpt_args(a.start, a.samples, a.decode)
+    except ValueError as e:
+        ap.error(str(e))
     if a.vbr_bytes is not None or a.vbr_bits_per_sample is not None or a.vbr_grid is not None:
         try:
             check_vbr_size_args(a.vbr_bytes, a.vbr_bits_per_sample, a.vbr_grid, a.bits_per_sample, a.target_nmr, a.vbr_nmr, a.dst,
@@ -540,7 +574,7 @@ def main(argv=None):
         _print_nmr(ap, a, paths, None if rates is None else [v for (_, v) in rates])
         return
     if a.decode:
-        pcm = decode_pac_file(a.src, a.dst, a.device)
+        pcm = decode_pac_file(a.src, a.dst, a.device, excerpt)
         print("%s: %d channels x %d samples" % (a.dst, pcm.shape[0], pcm.shape[1]))
         return
     cert = {} if a.certify else None

@@ -104,91 +104,99 @@ void copy_host(void* dst, const void* src, size_t n) {
 }
 
 // ---- host plan, pass 1: headers, chunks, block shapes, where each file's samples go
-int pac_plan_scan(mrc_handle* h, const char* fn, int64_t n_files, const uint8_t* buf, const int64_t* file_offset,
-                  PacPlan* p) {
-    const mrc_config& hc = h->cfg;
+// ONE file: header, the caller's parameters against the file's (`owner` words who named them), chunk scan with shape
+// bits, block positions.  Appends the file's chunks (offsets + base) and fills fi except xStart.  h == nullptr: the
+// text goes to mrc_last_error(NULL).
+int pac_scan_file(mrc_handle* h, const mrc_config& hc, const char* fn, const char* owner, int64_t f, const uint8_t* fb,
+                  int64_t flen, int64_t base, std::vector<int64_t>* chunkOff, std::vector<unsigned char>* chunkShape,
+                  PacFilePlan* out) {
     const UnpackParams P = unpack_params(hc);
     int nBands[4];
     decode_band_counts(hc, nBands, nullptr);
     char msg[200];
+    mrc_config fc = hc;
+    int32_t nch = 0;
+    uint32_t ns = 0;
+    int64_t doff = 0;
+    if (mrc_pac_read_header(fb, flen, &fc, &nch, &ns, &doff) != MRC_OK) {
+        std::snprintf(msg, sizeof msg, "%s: file %lld: not a .pac header (", fn, (long long)f);
+        return fail(h, MRC_ERR_INVALID, msg + create_error() + ")");
+    }
+    const struct { const char* name; int file, handle; } par[4] = {
+        {"sample_rate", fc.sample_rate, hc.sample_rate}, {"n_mdct_lines", fc.n_mdct_lines, hc.n_mdct_lines},
+        {"n_scale_bits", fc.n_scale_bits, hc.n_scale_bits}, {"n_mant_size_bits", fc.n_mant_size_bits, hc.n_mant_size_bits}};
+    for (const auto& q : par)
+        if (q.file != q.handle) {
+            std::snprintf(msg, sizeof msg, "%s: file %lld has %s = %d, %s %d", fn, (long long)f, q.name, q.file, owner,
+                          q.handle);
+            return fail(h, MRC_ERR_INVALID, msg);
+        }
+    PacFilePlan& fi = *out;
+    fi.nch = nch;
+    fi.firstChunk = (int64_t)chunkOff->size();
+    for (int64_t off = doff; off + 4 <= flen;) {       // mrc_pac_scan_chunks
+        const int64_t nBytes = unpack_u32le(fb + off);
+        if (off + 4 + nBytes > flen) {
+            std::snprintf(msg, sizeof msg, "%s: file %lld: truncated chunk at byte %lld", fn, (long long)f,
+                          (long long)off);
+            return fail(h, MRC_ERR_INVALID, msg);
+        }
+        int shape;
+        if (unpack_chunk_shape(fb + off + 4, nBytes, P, &shape) != kUnpackOk || nBands[shape] < 0) {
+            std::snprintf(msg, sizeof msg, "%s: file %lld: chunk at byte %lld has no block shape", fn, (long long)f,
+                          (long long)off);
+            return fail(h, MRC_ERR_INVALID, msg);
+        }
+        chunkOff->push_back(base + off);
+        chunkShape->push_back((unsigned char)shape);
+        off += 4 + nBytes;
+    }
+    fi.nChunks = (int64_t)chunkOff->size() - fi.firstChunk;
+    if (fi.nChunks % nch) {
+        std::snprintf(msg, sizeof msg, "%s: file %lld: %lld chunks for %d channels", fn, (long long)f,
+                      (long long)fi.nChunks, nch);
+        return fail(h, MRC_ERR_INVALID, msg);
+    }
+    int64_t start = 0;
+    for (int64_t i = 0; i < fi.nChunks / nch; ++i) {
+        const int s = (*chunkShape)[(size_t)(fi.firstChunk + i * nch)];
+        if (nch == 2 && (*chunkShape)[(size_t)(fi.firstChunk + i * nch + 1)] != s) {
+            std::snprintf(msg, sizeof msg, "%s: file %lld: the chunks of block %lld differ in shape", fn, (long long)f,
+                          (long long)i);
+            return fail(h, MRC_ERR_INVALID, msg);
+        }
+        int a, b;
+        shape_ab(hc, s, &a, &b);
+        fi.extent = std::max(fi.extent, start + a + b);   // (a file whose shapes do not chain still stays in its plane)
+        fi.total = start + a + b;                          // pacfile.decode_pac: last block's start + a + b
+        start += a;
+    }
+    return MRC_OK;
+}
+
+int pac_plan_scan(mrc_handle* h, const char* fn, int64_t n_files, const uint8_t* buf, const int64_t* file_offset,
+                  PacPlan* p) {
     p->files.assign((size_t)n_files, PacFilePlan{});
     p->chunkOff.clear();
     p->chunkShape.clear();
     p->planeStride = 0;
     p->anyStereo = false;
     for (int64_t f = 0; f < n_files; ++f) {
-        const uint8_t* fb = buf + file_offset[f];
-        const int64_t flen = file_offset[f + 1] - file_offset[f];
-        mrc_config fc = hc;
-        int32_t nch = 0;
-        uint32_t ns = 0;
-        int64_t doff = 0;
-        if (mrc_pac_read_header(fb, flen, &fc, &nch, &ns, &doff) != MRC_OK) {
-            std::snprintf(msg, sizeof msg, "%s: file %lld: not a .pac header (", fn, (long long)f);
-            return fail(h, MRC_ERR_INVALID, msg + create_error() + ")");
-        }
-        const struct { const char* name; int file, handle; } par[4] = {
-            {"sample_rate", fc.sample_rate, hc.sample_rate}, {"n_mdct_lines", fc.n_mdct_lines, hc.n_mdct_lines},
-            {"n_scale_bits", fc.n_scale_bits, hc.n_scale_bits}, {"n_mant_size_bits", fc.n_mant_size_bits, hc.n_mant_size_bits}};
-        for (const auto& q : par)
-            if (q.file != q.handle) {
-                std::snprintf(msg, sizeof msg, "%s: file %lld has %s = %d, the handle was created with %d", fn,
-                              (long long)f, q.name, q.file, q.handle);
-                return fail(h, MRC_ERR_INVALID, msg);
-            }
         PacFilePlan& fi = p->files[(size_t)f];
-        fi.nch = nch;
-        fi.firstChunk = (int64_t)p->chunkOff.size();
-        for (int64_t off = doff; off + 4 <= flen;) {       // mrc_pac_scan_chunks
-            const int64_t nBytes = unpack_u32le(fb + off);
-            if (off + 4 + nBytes > flen) {
-                std::snprintf(msg, sizeof msg, "%s: file %lld: truncated chunk at byte %lld", fn, (long long)f,
-                              (long long)off);
-                return fail(h, MRC_ERR_INVALID, msg);
-            }
-            int shape;
-            if (unpack_chunk_shape(fb + off + 4, nBytes, P, &shape) != kUnpackOk || nBands[shape] < 0) {
-                std::snprintf(msg, sizeof msg, "%s: file %lld: chunk at byte %lld has no block shape", fn, (long long)f,
-                              (long long)off);
-                return fail(h, MRC_ERR_INVALID, msg);
-            }
-            p->chunkOff.push_back(file_offset[f] - file_offset[0] + off);
-            p->chunkShape.push_back((unsigned char)shape);
-            off += 4 + nBytes;
-        }
-        fi.nChunks = (int64_t)p->chunkOff.size() - fi.firstChunk;
-        if (fi.nChunks % nch) {
-            std::snprintf(msg, sizeof msg, "%s: file %lld: %lld chunks for %d channels", fn, (long long)f,
-                          (long long)fi.nChunks, nch);
-            return fail(h, MRC_ERR_INVALID, msg);
-        }
-        int64_t start = 0;
-        for (int64_t i = 0; i < fi.nChunks / nch; ++i) {
-            const int s = p->chunkShape[(size_t)(fi.firstChunk + i * nch)];
-            if (nch == 2 && p->chunkShape[(size_t)(fi.firstChunk + i * nch + 1)] != s) {
-                std::snprintf(msg, sizeof msg, "%s: file %lld: the chunks of block %lld differ in shape", fn, (long long)f,
-                              (long long)i);
-                return fail(h, MRC_ERR_INVALID, msg);
-            }
-            int a, b;
-            shape_ab(hc, s, &a, &b);
-            fi.extent = std::max(fi.extent, start + a + b);   // (a file whose shapes do not chain still stays in its plane)
-            fi.total = start + a + b;                          // pacfile.decode_pac: last block's start + a + b
-            start += a;
-        }
+        MRC_TRY(pac_scan_file(h, h->cfg, fn, "the handle was created with", f, buf + file_offset[f],
+                              file_offset[f + 1] - file_offset[f], file_offset[f] - file_offset[0], &p->chunkOff,
+                              &p->chunkShape, &fi));
         fi.xStart = p->planeStride;
         p->planeStride += fi.extent;
-        p->anyStereo |= nch == 2;
+        p->anyStereo |= fi.nch == 2;
     }
     return MRC_OK;
 }
 
 // ---- pass 2: groups and slots
 int pac_plan_groups(mrc_handle* h, const char* fn, PacPlan* p) {
-    const DecodeBufs& d = h->dec;
     for (int64_t k = 0; k < 2 * kUnpackGroups; ++k) p->nCat[k] = 0;
     for (int g = 0; g < kUnpackGroups; ++g) p->nSlots[g] = 0;
-    for (int s = 0; s < 4; ++s) p->hs[s] = nullptr;
     for (const PacFilePlan& fi : p->files) {
         const int64_t nb = fi.nChunks / fi.nch, nJoint = (fi.nch == 2 && nb > 1) ? nb - 1 : 0;
         for (int64_t i = 0; i < nb; ++i) {
@@ -197,7 +205,14 @@ int pac_plan_groups(mrc_handle* h, const char* fn, PacPlan* p) {
             else { p->nSlots[s * 2 + 1] += fi.nch; p->nCat[s * 4 + 2] += fi.nch; }
         }
     }
+    return pac_plan_layout(h, fn, p);
+}
+
+// ... the part that follows from nSlots alone (mrc_pac_store_decode_window counts the slots of its windows itself)
+int pac_plan_layout(mrc_handle* h, const char* fn, PacPlan* p) {
+    const DecodeBufs& d = h->dec;
     for (int64_t g = 0, q = 0; g < kUnpackGroups; q += p->nSlots[g], ++g) p->slotBase[g] = q;
+    for (int s = 0; s < 4; ++s) p->hs[s] = nullptr;
     for (int s = 0; s < 4; ++s)
         if (p->nSlots[s * 2] + p->nSlots[s * 2 + 1]) {
             int a, b;
@@ -362,6 +377,35 @@ int mrc_decode_pac_pcm16(mrc_handle* h, int64_t n_files, const uint8_t* buf, con
     MRC_HIP(h, hipStreamSynchronize(st));
     for (int i = 0; i < 4; ++i) MRC_HIP(h, d.ev.elapsed(i, i + 1, &d.ms[i]));
     if (nOut) copy_host(out, d.pinOut.p, sizeof(int16_t) * nOut);
+    return MRC_OK;
+}
+
+int mrc_pac_index(const mrc_config* cfg, const uint8_t* buf, int64_t len, int32_t* n_channels, int64_t* n_blocks,
+                  int64_t* n_samples, int64_t block_cap, int64_t* block_start, int32_t* block_a, int32_t* block_b,
+                  int64_t* chunk_offset) {
+    if (!cfg || !buf || len < 0 || !n_channels || !n_blocks || !n_samples || block_cap < 0)
+        return fail(nullptr, MRC_ERR_INVALID, "mrc_pac_index: bad argument");
+    std::vector<int64_t> chunkOff;
+    std::vector<unsigned char> chunkShape;
+    PacFilePlan fi;
+    MRC_TRY(pac_scan_file(nullptr, *cfg, "mrc_pac_index", "cfg has", 0, buf, len, 0, &chunkOff, &chunkShape, &fi));
+    const int64_t nb = fi.nChunks / fi.nch;
+    *n_channels = fi.nch;
+    *n_blocks = nb;
+    *n_samples = std::max<int64_t>(0, fi.total - cfg->n_mdct_lines);
+    if (nb > block_cap || (nb > 0 && (!block_start || !block_a || !block_b || !chunk_offset)))
+        return fail(nullptr, MRC_ERR_NOMEM, "mrc_pac_index: the file has " + std::to_string(nb) + " blocks, block_cap is " +
+                                                std::to_string(block_cap));
+    int64_t start = 0;
+    for (int64_t i = 0; i < nb; ++i) {
+        int a, b;
+        shape_ab(*cfg, chunkShape[(size_t)(i * fi.nch)], &a, &b);
+        block_start[i] = start;
+        block_a[i] = a;
+        block_b[i] = b;
+        start += a;
+    }
+    std::copy(chunkOff.begin(), chunkOff.end(), chunk_offset);
     return MRC_OK;
 }
 

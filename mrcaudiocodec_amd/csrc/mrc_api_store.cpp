@@ -1,0 +1,299 @@
+// C ABI, resident `.pac` store (include/mrc_hip.h: mrc_pac_store_*): files uploaded once, sample windows decoded into the
+// caller's device memory.
+//
+// create: pac_plan_scan -- the host plan of mrc_decode_pac_pcm16, one scan in the tree -- gives every file's chunks, block
+// shapes and positions; the bytes go to the device in one copy and never cross PCIe again.
+//
+// decode_window, per slab of whole items:
+//   needed blocks   block i of the item's file iff p_i < start + window + L and p_i + a_i + b_i > start + L (p_i its position
+//                   in the padded plane, L = n_mdct_lines): positions increase, so the end is a binary search, and as
+//                   a + b <= 2 L so is a point before which no block can reach the window; the few blocks behind it are
+//                   tested one by one.
+//   margin planes   each item that needs a block gets a float64 plane of window + 4 L samples per decoded channel, the
+//                   window at [2 L, 2 L + window): a needed block starts at 2 L + p_i - (start + L), which lies in
+//                   (2 L - (a + b), 2 L + window), so every needed block fits with decode_kernel unchanged.  Each window
+//                   sample receives exactly the contributions it receives in the whole-file decode (a block that
+//                   contributes to it overlaps the window, hence is needed), added to zero: the same bits.
+//   groups          the needed (block, channel)s of ALL items of the slab are slots of at most eight (shape, kind) groups:
+//                   one unpack_dense_kernel launch, at most eight decode_kernel launches.  A block's kind is its position
+//                   in its file: joint for all but the last block of a stereo file of more than one block.
+//   window_out_kernel  planes -> out [item][channel][t] in the caller's format (mrc_kernels_store.hip).
+// The plan entries point into the resident bytes; what is uploaded per slab is the plan alone.
+#include "mrc_handle.hpp"
+
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+
+using namespace mrc;
+
+namespace {
+
+const char* const kWin = "mrc_pac_store_decode_window";
+
+int store_alive(mrc_pac_store* s, const char* fn) {
+    if (!s) return fail(nullptr, MRC_ERR_INVALID, std::string(fn) + ": null store");
+    if (!s->h) return fail(nullptr, MRC_ERR_INVALID, std::string(fn) + ": the store's handle has been destroyed");
+    return MRC_OK;
+}
+
+struct Need { int64_t item, file, block; };          // item: index in the slab
+
+// the blocks of file f that a window of `window` samples at `start` overlaps, appended to out as (item, f, block)
+void needed_blocks(const mrc_pac_store& s, const mrc_config& cfg, int64_t item, int64_t f, int64_t start, int64_t window,
+                   std::vector<Need>* out) {
+    const int64_t L = cfg.n_mdct_lines, nb = s.index.nBlocks(f);
+    // no block reaches past the file's extent or before 0 (compared without forming start + window where start is extreme)
+    if (nb == 0 || start >= s.index.files[(size_t)f].extent - L || (start < 0 && -(start + 1) >= window + L - 1)) return;
+    const int64_t* p = s.blockStart.data() + s.firstBlock[(size_t)f];
+    const int64_t lo = start + L, hi = start + window + L;
+    const int64_t first = std::upper_bound(p, p + nb, lo - 2 * L) - p, end = std::lower_bound(p, p + nb, hi) - p;
+    for (int64_t i = first; i < end; ++i) {
+        int a, b;
+        shape_ab(cfg, s.index.shape(f, i), &a, &b);
+        if (p[i] + a + b > lo) out->push_back(Need{item, f, i});
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int mrc_pac_store_create(mrc_handle* h, int64_t n_files, const uint8_t* buf, const int64_t* file_offset,
+                         mrc_pac_store** out) {
+    if (!h) return MRC_ERR_INVALID;
+    if (out) *out = nullptr;
+    if (n_files < 0 || !file_offset || !out || (n_files > 0 && !buf))
+        return fail(h, MRC_ERR_INVALID, "mrc_pac_store_create: bad argument");
+    for (int64_t f = 0; f < n_files; ++f)
+        if (file_offset[0] < 0 || file_offset[f + 1] < file_offset[f])
+            return fail(h, MRC_ERR_INVALID, "mrc_pac_store_create: file_offset must not decrease");
+    std::unique_ptr<mrc_pac_store> s(new (std::nothrow) mrc_pac_store());
+    if (!s) return fail(h, MRC_ERR_NOMEM, "mrc_pac_store_create: out of host memory");
+    MRC_TRY(pac_plan_scan(h, "mrc_pac_store_create", n_files, buf, file_offset, &s->index));
+    s->firstBlock.assign((size_t)n_files + 1, 0);
+    s->fileBase.assign((size_t)n_files + 1, 0);
+    for (int64_t f = 0; f < n_files; ++f) {
+        int64_t start = 0;
+        for (int64_t i = 0; i < s->index.nBlocks(f); ++i) {
+            int a, b;
+            shape_ab(h->cfg, s->index.shape(f, i), &a, &b);
+            s->blockStart.push_back(start);
+            start += a;
+        }
+        s->firstBlock[(size_t)f + 1] = (int64_t)s->blockStart.size();
+        s->fileBase[(size_t)f + 1] = file_offset[f + 1] - file_offset[0];
+    }
+    s->nBytes = n_files ? file_offset[n_files] - file_offset[0] : 0;
+    MRC_TRY(ensure_decode_consts(h));
+    MRC_HIP(h, s->bytes.reserve(std::max<size_t>((size_t)s->nBytes, 256)));
+    if (s->nBytes) MRC_HIP(h, hipMemcpy(s->bytes.p, buf + file_offset[0], (size_t)s->nBytes, hipMemcpyHostToDevice));
+    s->h = h;
+    h->stores.push_back(s.get());
+    *out = s.release();
+    return MRC_OK;
+}
+
+void mrc_pac_store_destroy(mrc_pac_store* s) {
+    if (!s) return;
+    if (mrc_handle* h = s->h) {
+        h->stores.erase(std::remove(h->stores.begin(), h->stores.end(), s), h->stores.end());
+        (void)hipSetDevice(h->device);
+        if (h->stream) (void)hipStreamSynchronize(h->stream);
+    }
+    delete s;
+}
+
+int mrc_pac_store_info(mrc_pac_store* s, int64_t* n_files, int32_t* n_channels, int64_t* n_samples, int64_t* n_blocks,
+                       int64_t* device_bytes) {
+    MRC_TRY(store_alive(s, "mrc_pac_store_info"));
+    const int64_t n = (int64_t)s->index.files.size(), L = s->h->cfg.n_mdct_lines;
+    if (n_files) *n_files = n;
+    for (int64_t f = 0; f < n; ++f) {
+        const PacFilePlan& fi = s->index.files[(size_t)f];
+        if (n_channels) n_channels[f] = fi.nch;
+        if (n_samples) n_samples[f] = std::max<int64_t>(0, fi.total - L);
+        if (n_blocks) n_blocks[f] = s->index.nBlocks(f);
+    }
+    if (device_bytes) *device_bytes = (int64_t)s->bytes.cap;
+    return MRC_OK;
+}
+
+int mrc_pac_store_decode_window(mrc_pac_store* s, int64_t n_items, const int64_t* file, const int64_t* start, int64_t window,
+                                int n_channels_out, int format, void* out, void* stream) {
+    MRC_TRY(store_alive(s, kWin));
+    mrc_handle* h = s->h;
+    const mrc_config& cfg = h->cfg;
+    const int64_t nFiles = (int64_t)s->index.files.size(), L = cfg.n_mdct_lines;
+    const std::string w = kWin;
+    for (int i = 0; i < 4; ++i) { s->stats[i] = 0; s->ms[i] = 0.0; }
+    if (n_items < 0) return fail(h, MRC_ERR_INVALID, w + ": n_items < 0");
+    if (window < 0 || window > ((int64_t)1 << 40)) return fail(h, MRC_ERR_INVALID, w + ": window must lie in [0, 2^40]");
+    if (n_channels_out != 1 && n_channels_out != 2) return fail(h, MRC_ERR_INVALID, w + ": n_channels_out must be 1 or 2");
+    if (format != MRC_WINDOW_PCM16 && format != MRC_WINDOW_F32 && format != MRC_WINDOW_F64)
+        return fail(h, MRC_ERR_INVALID, w + ": unknown format " + std::to_string(format));
+    if (n_items > 0 && (!file || !start)) return fail(h, MRC_ERR_INVALID, w + ": file or start is NULL");
+    if (n_items > 0 && window > 0 && !out) return fail(h, MRC_ERR_INVALID, w + ": out is NULL");
+    for (int64_t k = 0; k < n_items; ++k) {
+        if (file[k] < 0 || file[k] >= nFiles)
+            return fail(h, MRC_ERR_INVALID, w + ": file[" + std::to_string(k) + "] = " + std::to_string(file[k]) + " is outside the store's " +
+                                                std::to_string(nFiles) + " files");
+        if (s->index.files[(size_t)file[k]].nch > n_channels_out)
+            return fail(h, MRC_ERR_INVALID, w + ": item " + std::to_string(k) + ": file " + std::to_string(file[k]) +
+                                                " is stereo, the call asks for one channel");
+    }
+    if (n_items == 0 || window == 0) return MRC_OK;
+
+    MRC_TRY(ensure_decode_consts(h));
+    DecodeBufs& d = h->dec;
+    StoreBufs& b = h->store;
+    MRC_HIP(h, b.ev.create());
+    const UnpackParams P = unpack_params(cfg);
+    hipStream_t st = pick_stream(h, stream);
+    DrainGuard drain{{st, nullptr, nullptr}};
+    const size_t elem = format == MRC_WINDOW_PCM16 ? 2 : format == MRC_WINDOW_F32 ? 4 : 8;
+    const int64_t planeLen = window + 4 * L, tiles = (window + 255) / 256;
+    const int64_t slab = h->storeSlabSamples, itemCap = std::max<int64_t>(1, 0x7fffffffLL / (tiles * n_channels_out));
+    char msg[240];
+
+    std::vector<Need> needs;
+    std::vector<WindowItem> items;
+    std::vector<int64_t> planFile;
+    PacPlan pl;                                              // (its group fields: the slab's slots)
+    for (int64_t first = 0, last; first < n_items; first = last) {
+        last = first + 1;
+        while (last < n_items && last - first < itemCap && (slab == 0 || (last - first + 1) * window <= slab)) ++last;
+        const int64_t nSlab = last - first;
+        unsigned char* outSlab = (unsigned char*)out + (size_t)first * n_channels_out * window * elem;
+        s->stats[2] += 1;
+
+        // ---- the slab's needed blocks, its items and planes
+        needs.clear();
+        items.assign((size_t)nSlab, WindowItem{0, 0, 0, 1, 0});
+        int64_t planeDoubles = 0;
+        for (int64_t k = 0; k < nSlab; ++k) {
+            const int64_t f = file[first + k];
+            const size_t before = needs.size();
+            needed_blocks(*s, cfg, k, f, start[first + k], window, &needs);
+            if (needs.size() == before) continue;            // all zeros: its plane does not exist
+            const PacFilePlan& fi = s->index.files[(size_t)f];
+            items[(size_t)k] = WindowItem{planeDoubles, start[first + k], std::max<int64_t>(0, fi.total - L), fi.nch, 0};
+            planeDoubles += fi.nch * planeLen;
+        }
+        if (needs.empty()) {                                 // nothing to decode: zeros, no launch
+            MRC_HIP(h, hipMemsetAsync(outSlab, 0, (size_t)nSlab * n_channels_out * window * elem, st));
+            continue;
+        }
+        for (int64_t k = 0; k < 2 * kUnpackGroups; ++k) pl.nCat[k] = 0;
+        for (int g = 0; g < kUnpackGroups; ++g) pl.nSlots[g] = 0;
+        for (const Need& n : needs) {
+            const int nch = s->index.files[(size_t)n.file].nch, sh = s->index.shape(n.file, n.block);
+            if (n.block < s->index.nJoint(n.file)) { pl.nSlots[sh * 2] += 1; pl.nCat[sh * 4] += 1; pl.nCat[sh * 4 + 1] += 1; }
+            else { pl.nSlots[sh * 2 + 1] += nch; pl.nCat[sh * 4 + 2] += nch; }
+        }
+        MRC_TRY(pac_plan_layout(h, kWin, &pl));
+        int64_t nChunks = 0;
+        for (int64_t k = 0; k < 2 * kUnpackGroups; ++k) nChunks += pl.nCat[k];
+
+        // ---- staging (one H2D copy): plan | groups | block offsets | items
+        const size_t oGroups = align256(sizeof(UnpackPlanEntry) * nChunks),
+                     oOffs = oGroups + align256(sizeof(UnpackGroupDev) * kUnpackGroups),
+                     oItems = oOffs + align256(sizeof(long long) * pl.totalSlots),
+                     inTotal = oItems + align256(sizeof(WindowItem) * nSlab);
+        MRC_HIP(h, b.pinIn.reserve(inTotal));
+        MRC_HIP(h, b.in.reserve(inTotal));
+        MRC_HIP(h, b.groups.reserve(std::max<size_t>(pl.gBytes, 256)));
+        MRC_HIP(h, b.planes.reserve(sizeof(double) * (size_t)planeDoubles));
+        unsigned char* pin = (unsigned char*)b.pinIn.p;
+        UnpackPlanEntry* plan = (UnpackPlanEntry*)pin;
+        UnpackGroupDev* gd = (UnpackGroupDev*)(pin + oGroups);
+        long long* offs = (long long*)(pin + oOffs);
+        std::memcpy(pin + oItems, items.data(), sizeof(WindowItem) * nSlab);
+        pac_plan_group_descs(d, pl, gd, b.groups.as<unsigned char>());
+        planFile.assign((size_t)nChunks, 0);
+        int64_t catPos[2 * kUnpackGroups], slotNext[kUnpackGroups] = {};
+        for (int64_t k = 0, q = 0; k < 2 * kUnpackGroups; q += pl.nCat[k], ++k) catPos[k] = q;
+        for (const Need& n : needs) {
+            const PacFilePlan& fi = s->index.files[(size_t)n.file];
+            const WindowItem& it = items[(size_t)n.item];
+            const int64_t c0 = fi.firstChunk + n.block * fi.nch;
+            const int sh = s->index.chunkShape[(size_t)c0];
+            // the block's place in the item's plane: its position in the file's padded plane, the window's start at 2 L
+            const int64_t at = it.plane + 2 * L + s->blockStart[(size_t)(s->firstBlock[(size_t)n.file] + n.block)] - (it.start + L);
+            if (n.block < s->index.nJoint(n.file)) {
+                const int g = sh * 2, slot = (int)slotNext[g]++;
+                for (int ch = 0; ch < 2; ++ch) {
+                    planFile[(size_t)catPos[sh * 4 + ch]] = n.file;
+                    plan[catPos[sh * 4 + ch]++] = UnpackPlanEntry{s->index.chunkOff[(size_t)c0 + ch], g * 2 + ch, slot};
+                }
+                offs[pl.slotBase[g] + slot] = at;
+            } else {
+                const int g = sh * 2 + 1;
+                for (int ch = 0; ch < fi.nch; ++ch) {
+                    const int slot = (int)slotNext[g]++;
+                    planFile[(size_t)catPos[sh * 4 + 2]] = n.file;
+                    plan[catPos[sh * 4 + 2]++] = UnpackPlanEntry{s->index.chunkOff[(size_t)c0 + ch], g * 2, slot};
+                    offs[pl.slotBase[g] + slot] = at + ch * planeLen;
+                }
+            }
+        }
+        s->stats[0] += nChunks;
+        s->stats[3] += (int64_t)inTotal;
+
+        // ---- device
+        unsigned char* din = b.in.as<unsigned char>();
+        MRC_HIP(h, hipEventRecord(b.ev[0], st));
+        MRC_HIP(h, hipMemcpyAsync(din, pin, inTotal, hipMemcpyHostToDevice, st));
+        MRC_HIP(h, hipEventRecord(b.ev[1], st));
+        MRC_TRY(reset_unpack_err(h, st));
+        MRC_HIP(h, launch_unpack_dense(P, d.bands, d.consts.as<UnpackTables>(), nChunks, (const UnpackPlanEntry*)din,
+                                       s->bytes.as<uint8_t>(), s->nBytes, (const UnpackGroupDev*)(din + oGroups),
+                                       d.err.as<UnpackErr>(), st));
+        MRC_HIP(h, hipEventRecord(b.ev[2], st));
+        MRC_HIP(h, hipMemcpyAsync(d.pinErr.get(), d.err.p, sizeof(UnpackErr), hipMemcpyDeviceToHost, st));
+        MRC_HIP(h, hipStreamSynchronize(st));
+        if (d.pinErr->flag) {
+            const int64_t c = d.pinErr->firstBad;
+            const int64_t f = c < nChunks ? planFile[(size_t)c] : 0;
+            const int64_t at = c < nChunks ? plan[c].off - s->fileBase[(size_t)f] : 0;
+            std::snprintf(msg, sizeof msg, "%s: file %lld: chunk at byte %lld: %s", kWin, (long long)f, (long long)at,
+                          unpack_status_text(d.pinErr->flag));
+            return fail(h, MRC_ERR_INVALID, msg);
+        }
+        double* x = b.planes.as<double>();
+        MRC_HIP(h, hipEventRecord(b.ev[3], st));
+        MRC_HIP(h, hipMemsetAsync(x, 0, sizeof(double) * (size_t)planeDoubles, st));
+        for (int g = 0; g < kUnpackGroups; ++g) {
+            if (!pl.nSlots[g]) continue;
+            const UnpackGroupDev& G = gd[g];
+            MRC_HIP(h, launch_decode(pl.hs[g / 2]->dev, pl.nSlots[g], G.joint ? 2 : 1, G.oscale, G.joint ? G.ms : nullptr, G.sf,
+                                     G.ba, G.mant, (const int64_t*)(din + oOffs) + pl.slotBase[g], x,
+                                     G.joint ? x + planeLen : nullptr, st));
+            s->stats[1] += 1;
+        }
+        MRC_HIP(h, hipEventRecord(b.ev[4], st));
+        MRC_HIP(h, launch_window_out(nSlab, (const WindowItem*)(din + oItems), window, n_channels_out, format, (int)L, x,
+                                     outSlab, st));
+        MRC_HIP(h, hipEventRecord(b.ev[5], st));
+        MRC_HIP(h, hipStreamSynchronize(st));                // (the staging is written again by the next slab)
+        const int span[4][2] = {{0, 1}, {1, 2}, {3, 4}, {4, 5}};
+        for (int i = 0; i < 4; ++i) {
+            double ms = 0.0;
+            MRC_HIP(h, b.ev.elapsed(span[i][0], span[i][1], &ms));
+            s->ms[i] += ms;
+        }
+    }
+    MRC_HIP(h, hipStreamSynchronize(st));
+    return MRC_OK;
+}
+
+int mrc_pac_store_stats(mrc_pac_store* s, int64_t* stats, double* ms) {
+    MRC_TRY(store_alive(s, "mrc_pac_store_stats"));
+    for (int i = 0; i < 4; ++i) {
+        if (stats) stats[i] = s->stats[i];
+        if (ms) ms[i] = s->ms[i];
+    }
+    return MRC_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,6 @@
 // The handle behind the C ABI and the helpers every translation unit of the host glue shares (mrc_api.cpp: the per-block
-// and pipelined entry points; mrc_api_chain.cpp, mrc_api_chain_measured.cpp: the chained stream encode).  Not part of the ABI.
+// and pipelined entry points; mrc_api_chain.cpp, mrc_api_chain_measured.cpp: the chained stream encode; mrc_api_decode.cpp,
+// mrc_api_nmr.cpp, mrc_api_store.cpp: the decode side).  Not part of the ABI.
 // Who frees what: every device buffer, page-locked buffer, event and stream is a member of an owning type below and goes
 // with the handle (mrc_destroy deletes it); nothing here is freed by name.
 #pragma once
@@ -216,6 +217,16 @@ struct NmrBufs {
     double ms[4] = {0, 0, 0, 0};
 };
 
+// Windows of resident `.pac` files (mrc_pac_store_decode_window, mrc_api_store.cpp): the workspace of one slab, reused from
+// slab to slab and from call to call.  The parsing tables, the error word and its page-locked copy are DecodeBufs'.
+struct StoreBufs {
+    DevBuf in;                       // one H2D copy per slab: plan | group descriptors | block offsets | items
+    DevBuf groups;                   // dense per-(shape, kind) arrays of the parsed chunks
+    DevBuf planes;                   // float64, window + 4 n_mdct_lines samples per item and decoded channel
+    PinnedBuf pinIn;                 // written again only after the slab that read it has been synchronised
+    EventSet<6> ev;                  // start | plan uploaded | unpacked ; synthesis starts | planes done | windows written
+};
+
 // ---- the host plan of whole `.pac` files, shared by mrc_decode_pac_pcm16 and mrc_pac_nmr (mrc_api_decode.cpp)
 // Blocks are grouped exactly as pacfile.decode_pac groups them: a stereo file of more than one block is joint blocks
 // followed by the two non-joint chunks Close() wrote, every other file is non-joint blocks.  A group is a (block shape,
@@ -264,17 +275,18 @@ void copy_host(void* dst, const void* src, size_t n);   // memcpy over a few hos
 // touched).  fn names the entry point in errors.
 int pac_plan_scan(mrc_handle* h, const char* fn, int64_t n_files, const uint8_t* buf, const int64_t* file_offset,
                   PacPlan* p);
-// slots per group, the shapes' tables and the layout of the groups' dense arrays
+// ... one file of it, also behind mrc_pac_index (h == nullptr, hc the caller's cfg, owner = who named hc's values in the
+// refusal of a file with other parameters): appends the file's chunks, their offsets counted from `base` bytes before the
+// file, and fills *fi except xStart
+int pac_scan_file(mrc_handle* h, const mrc_config& hc, const char* fn, const char* owner, int64_t f, const uint8_t* fb,
+                  int64_t flen, int64_t base, std::vector<int64_t>* chunkOff, std::vector<unsigned char>* chunkShape,
+                  PacFilePlan* fi);
+// slots per group (pac_plan_groups: of whole files), then the shapes' tables and the layout of the groups' dense arrays
+// (pac_plan_layout: from nSlots / nCat as they stand)
 int pac_plan_groups(mrc_handle* h, const char* fn, PacPlan* p);
-// Staging of the parse: the plan entries (ordered by (group, joint channel), so that a wave parses one kind) and the
-// group descriptors, with gBase the device address of the dense arrays.  visit(f, i, g, slot, ch, start) once per joint
-// block (ch = 0; the slot holds both channels) and once per channel of a non-joint block; start = p_i, the block's
-// position in its file.
-template <class Visit>
-void pac_plan_fill(const mrc_config& cfg, const DecodeBufs& d, const PacPlan& p, UnpackPlanEntry* plan, UnpackGroupDev* gd,
-                   unsigned char* gBase, Visit visit) {
-    int64_t catPos[2 * kUnpackGroups];
-    for (int64_t k = 0, q = 0; k < 2 * kUnpackGroups; q += p.nCat[k], ++k) catPos[k] = q;
+int pac_plan_layout(mrc_handle* h, const char* fn, PacPlan* p);
+// the group descriptors, with gBase the device address of the dense arrays
+inline void pac_plan_group_descs(const DecodeBufs& d, const PacPlan& p, UnpackGroupDev* gd, unsigned char* gBase) {
     for (int g = 0; g < kUnpackGroups; ++g) {
         const int s = g / 2;
         UnpackGroupDev& G = gd[g];
@@ -285,6 +297,16 @@ void pac_plan_fill(const mrc_config& cfg, const DecodeBufs& d, const PacPlan& p,
         int** ptr[5] = {&G.oscale, &G.ms, &G.sf, &G.ba, &G.mant};
         for (int k = 0; k < 5; ++k) *ptr[k] = (int*)(gBase + p.gOff[g][k]);
     }
+}
+// Staging of the parse of whole files: the plan entries (ordered by (group, joint channel), so that a wave parses one kind)
+// and the group descriptors.  visit(f, i, g, slot, ch, start) once per joint block (ch = 0; the slot holds both channels)
+// and once per channel of a non-joint block; start = p_i, the block's position in its file.
+template <class Visit>
+void pac_plan_fill(const mrc_config& cfg, const DecodeBufs& d, const PacPlan& p, UnpackPlanEntry* plan, UnpackGroupDev* gd,
+                   unsigned char* gBase, Visit visit) {
+    int64_t catPos[2 * kUnpackGroups];
+    for (int64_t k = 0, q = 0; k < 2 * kUnpackGroups; q += p.nCat[k], ++k) catPos[k] = q;
+    pac_plan_group_descs(d, p, gd, gBase);
     int64_t slotNext[kUnpackGroups] = {};
     for (int64_t f = 0; f < (int64_t)p.files.size(); ++f) {
         const PacFilePlan& fi = p.files[(size_t)f];
@@ -316,6 +338,21 @@ void pac_plan_fill(const mrc_config& cfg, const DecodeBufs& d, const PacPlan& p,
 
 }  // namespace mrc
 
+// A resident store (mrc_pac_store_create): the files' bytes on the handle's device, their index on the host.  It belongs to
+// its handle, whose destructor takes the bytes back and clears `h`: what is left is a husk that refuses every call until
+// mrc_pac_store_destroy deletes it.
+struct mrc_pac_store {
+    mrc_handle* h = nullptr;
+    mrc::DevBuf bytes;               // the files back to back, as the caller passed them
+    int64_t nBytes = 0;
+    mrc::PacPlan index;              // pac_plan_scan's: files, chunk offsets into `bytes`, chunk shapes
+    std::vector<int64_t> blockStart; // per block of every file, file after file: a_0 + .. + a_{i-1}
+    std::vector<int64_t> firstBlock; // [files + 1] into blockStart
+    std::vector<int64_t> fileBase;   // [files + 1]: where each file's bytes start in `bytes`
+    int64_t stats[4] = {0, 0, 0, 0}; // last decode_window: chunks parsed, decode_kernel launches, slabs, plan bytes uploaded
+    double ms[4] = {0, 0, 0, 0};     // ... plan upload | unpack | synthesis | window_out_kernel
+};
+
 struct mrc_handle {
     mrc_config cfg{};
     int device = 0;
@@ -339,6 +376,9 @@ struct mrc_handle {
     mrc::NmrBufs nmr;                // mrc_pac_nmr: see mrc_api_nmr.cpp
     mrc::TargetBufs target;          // mrc_encode_chained_target_nmr_pac: see mrc_api_chain_measured.cpp
     mrc::VbrBufs vbr;                // mrc_encode_vbr_nmr_pac: see mrc_api_chain_measured.cpp
+    mrc::StoreBufs store;            // mrc_pac_store_decode_window: see mrc_api_store.cpp
+    std::vector<mrc_pac_store*> stores;   // the live stores of this handle (not owned: mrc_pac_store_destroy deletes them)
+    int64_t storeSlabSamples = (int64_t)1 << 24;   // mrc_set_option(MRC_OPT_STORE_SLAB_SAMPLES)
     double chainMs[4] = {0, 0, 0, 0};   // last chained encode: phase A, phase B, pack, whole call (host clock)
     bool timing = false;
     bool exactSpread = false;        // mrc_set_option(MRC_OPT_EXACT_SPREAD)
@@ -358,6 +398,10 @@ struct mrc_handle {
         (void)hipSetDevice(device);
         for (hipStream_t st : {(hipStream_t)stream, (hipStream_t)stIn, (hipStream_t)stOut})
             if (st) (void)hipStreamSynchronize(st);
+        for (mrc_pac_store* s : stores) {
+            s->bytes = mrc::DevBuf();
+            s->h = nullptr;
+        }
     }
 };
 

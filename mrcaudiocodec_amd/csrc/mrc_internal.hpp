@@ -220,6 +220,17 @@ hipError_t launch_nmr_band(const DevShape& S, int64_t nEntries, const NmrEntry* 
 // fileOut [nFiles][4]: max r, sum of b * mean r, disturbed blocks, 0.  File f's entries: [entryStart[f], entryStart[f + 1])
 hipError_t launch_nmr_file(int64_t nFiles, const long long* entryStart, const int* nch, const double* stat, double* fileOut,
                            hipStream_t st);
+// mrc_kernels_store.hip -- windows of resident `.pac` files (mrc_pac_store_decode_window)
+struct WindowItem {                  // one item of a slab
+    long long plane;                 // where its first decoded channel's plane starts in the slab's planes (doubles)
+    long long start;                 // the window's first sample, in the coordinates of mrc_decode_pac_pcm16's output
+    long long nSamples;              // the file's length in those coordinates; 0: the item needs no block, its plane is not read
+    int nch, pad_;                   // decoded channels: planes at plane + c * (window + 4 L)
+};
+// out [nItems][nchOut][window] in `format` (MRC_WINDOW_*) <- planes[item.plane + c * (window + 4 L) + 2 L + t], zero where
+// start + t lies outside [0, nSamples); a one-channel item fills every output channel
+hipError_t launch_window_out(int64_t nItems, const WindowItem* items /* device */, int64_t window, int nchOut, int format,
+                             int L, const double* planes, void* out, hipStream_t st);
 // mrc_kernels_chain.hip -- chained stream encode: reservoir-free preparation per block, serial scan per stream
 constexpr int kChainMaxLinesPerItem = 2 * 1024;  // coded lines one scan item holds (all its streams together)
 constexpr int kChainGroups = 5;    // chained encode: the four joint block shapes + Close()'s non-joint long block

@@ -376,6 +376,32 @@ def scan_chunks(buf, data_offset):
     return offs[:n]
 
 
+def index(buf, cfg=None):
+    """mrc_pac_index: where every block of ONE `.pac` byte string lies, from its header, chunk lengths and block-switch bits
+    alone (host only).  cfg: the codec parameters to hold the file against; None: the file's own header with the default
+    n_short and block-switch bits.  -> dict: n_channels, n_blocks, n_samples (per channel, as decode_pac_pcm16 returns
+    them), block_start [n] (position in the padded plane: a_0 + .. + a_{i-1}), block_a, block_b [n], chunk_offset
+    [n][n_channels] (byte offset of each chunk's length field)."""
+    raw = np.ascontiguousarray(np.frombuffer(buf, dtype=np.uint8))
+    if cfg is None:
+        cfg = read_header(buf)[0]
+    nch, nb, ns = C.c_int32(), C.c_int64(), C.c_int64()
+    arrays = lambda n: (np.zeros(n, np.int64), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(2 * n, np.int64))
+    cap = max(1, raw.size // 64)
+    start, a, b, offs = arrays(cap)
+    call = lambda: lib.mrc_pac_index(C.byref(cfg), raw.ctypes.data, raw.size, C.byref(nch), C.byref(nb), C.byref(ns), cap,
+                                     start.ctypes.data, a.ctypes.data, b.ctypes.data, offs.ctypes.data)
+    rc = call()
+    if rc == _lib.MRC_ERR_NOMEM and nb.value > cap:
+        cap = nb.value
+        start, a, b, offs = arrays(cap)
+        rc = call()
+    _check(rc, "mrc_pac_index", reason=True)
+    n = nb.value
+    return dict(n_channels=nch.value, n_blocks=n, n_samples=ns.value, block_start=start[:n].copy(), block_a=a[:n].copy(),
+                block_b=b[:n].copy(), chunk_offset=offs[:n * nch.value].reshape(n, nch.value).copy())
+
+
 def unpack_blocks(cfg, buf, chunk_offsets, n_channels, joint):
     """The parsing half of (Joint)ReadDataBlock for the blocks whose chunks start at chunk_offsets
     [n * n_channels] -> dict of fixed-stride arrays (see mrc_unpack_blocks)."""

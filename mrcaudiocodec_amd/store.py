@@ -1,0 +1,117 @@
+"""
+PacStore: `.pac` files resident on the device of a Handle (mrc_pac_store_*), sample windows of them decoded straight into
+torch tensors [item][channel][time] on that device.  Upload once, crop for ever: a call parses and synthesises only the
+blocks its windows overlap, and no file byte crosses PCIe again.
+
+    with PacStore(handle, bufs) as store:
+        x = store.decode_window(files, starts, 48000, dtype=torch.float32)     # [len(files)][channels][48000], on the GPU
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import lib
+
+STAT_NAMES = ("chunks_parsed", "decode_launches", "slabs", "plan_bytes_uploaded")
+MS_NAMES = ("plan_upload", "unpack", "synthesis", "window_out")
+
+
+def _formats():
+    import torch
+    return {torch.int16: _lib.MRC_WINDOW_PCM16, torch.float32: _lib.MRC_WINDOW_F32, torch.float64: _lib.MRC_WINDOW_F64}
+
+
+class PacStore:
+    """bufs: a list of bytes-like `.pac` files carrying the handle's codec parameters, mono and stereo mixed at will.
+    .n_channels, .n_samples (per channel, as Handle.decode_pac_pcm16 returns them), .n_blocks: one NumPy value per file;
+    .device_bytes: the device memory the store holds.  Close the store before its handle: a store whose handle has been
+    closed refuses every call (MrcError)."""
+
+    def __init__(self, handle, bufs):
+        if isinstance(bufs, (bytes, bytearray, memoryview, np.ndarray)):
+            bufs = [bufs]
+        n = len(bufs)
+        sizes = np.fromiter((len(b) for b in bufs), dtype=np.int64, count=n)
+        file_offset = np.zeros(n + 1, np.int64)
+        np.cumsum(sizes, out=file_offset[1:])
+        data = np.frombuffer(b"".join(bytes(b) for b in bufs), np.uint8) if n else np.zeros(1, np.uint8)
+        if not data.size:
+            data = np.zeros(1, np.uint8)
+        self._handle = handle
+        self._s = C.c_void_p()
+        handle._check(lib.mrc_pac_store_create(handle._h, n, data.ctypes.data, file_offset.ctypes.data, C.byref(self._s)))
+        self.n_channels = np.zeros(n, np.int32)
+        self.n_samples = np.zeros(n, np.int64)
+        self.n_blocks = np.zeros(n, np.int64)
+        nf, dev_bytes = C.c_int64(), C.c_int64()
+        pad = lambda a: a.ctypes.data if n else None
+        handle._check(lib.mrc_pac_store_info(self._s, C.byref(nf), pad(self.n_channels), pad(self.n_samples),
+                                             pad(self.n_blocks), C.byref(dev_bytes)))
+        self.device_bytes = dev_bytes.value
+
+    def close(self):
+        if getattr(self, "_s", None):
+            lib.mrc_pac_store_destroy(self._s)
+            self._s = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return len(self.n_channels)
+
+    def decode_window(self, files, starts, window, channels=None, dtype=None, out=None, stream=None):
+        """Item i = samples [starts[i], starts[i] + window) of file files[i], zeros where that leaves the file (starts may be
+        negative or past the end) -> a torch tensor [n][channels][window] on the handle's device.  dtype: torch.int16 (the
+        default: the codes Handle.decode_pac_pcm16 writes, bit for bit), torch.float64 (the overlap-added signal before the
+        PCM quantiser, bit for bit) or torch.float32 (that value converted once).  channels: 1 or 2; None: the largest channel
+        count among the items' files.  A mono file fills both channels of a two-channel call; a stereo file in a one-channel
+        call is refused.  out: a contiguous tensor of that shape, dtype and device to write into (else ValueError, before any
+        library call).  stream: a raw stream; None: torch's current stream on the device.  The call returns when the result
+        is there."""
+        import torch
+        files = np.ascontiguousarray(np.asarray(files, dtype=np.int64).reshape(-1))
+        starts = np.ascontiguousarray(np.asarray(starts, dtype=np.int64).reshape(-1))
+        if files.shape != starts.shape:
+            raise ValueError("decode_window: one start per file index (%d files, %d starts)" % (files.size, starts.size))
+        n, window = files.size, int(window)
+        if dtype is None:
+            dtype = torch.int16 if out is None else out.dtype
+        fmt = _formats().get(dtype)
+        if fmt is None:
+            raise ValueError("decode_window: dtype must be torch.int16, torch.float32 or torch.float64, got %s" % (dtype,))
+        if channels is None:
+            inside = files[(files >= 0) & (files < len(self))]
+            channels = int(self.n_channels[inside].max()) if inside.size else 1
+        channels = int(channels)
+        dev = torch.device("cuda", self._handle.cfg.device_id)
+        shape = (n, channels, max(window, 0))
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=dev)
+        elif not isinstance(out, torch.Tensor) or out.dtype != dtype or tuple(out.shape) != shape or out.device != dev \
+                or not out.is_contiguous():
+            raise ValueError("decode_window: out must be a contiguous %s tensor of shape %s on %s" % (dtype, shape, dev))
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        self._handle._check(lib.mrc_pac_store_decode_window(self._s, n, files.ctypes.data, starts.ctypes.data, window, channels,
+                                                            fmt, out.data_ptr() if out.numel() else None, stream or None))
+        return out
+
+    def stats(self):
+        """of the last decode_window: chunks_parsed, decode_launches, slabs, plan_bytes_uploaded, and ms: the device time of
+        the plan upload, the unpack kernel, the synthesis and window_out_kernel, summed over the slabs"""
+        st, ms = np.zeros(4, np.int64), np.zeros(4, np.float64)
+        self._handle._check(lib.mrc_pac_store_stats(self._s, st.ctypes.data, ms.ctypes.data))
+        r = {k: int(v) for k, v in zip(STAT_NAMES, st)}
+        r["ms"] = {k: float(v) for k, v in zip(MS_NAMES, ms)}
+        return r
