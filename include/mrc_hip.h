@@ -640,7 +640,11 @@ int mrc_chain_fetch_output(mrc_handle* h, uint8_t* out, int64_t out_cap, int64_t
  * reconstruction -> IMDCT -> transition window -> overlap-and-add, and the 16-bit PCM codes. */
 
 /* pacfileThem.py:130-158.  Fills sample_rate, n_mdct_lines, n_scale_bits, n_mant_size_bits of *cfg (other fields
- * untouched); data_offset = first chunk. */
+ * untouched); data_offset = first chunk.  The header is untrusted input; accepted is what mrc_pac_header and a handle can
+ * write: 1 or 2 channels, a positive rate, 1..4 scale bits, 1..8 allocation-field bits, and 16 <= n_mdct_lines <= 8192 that
+ * is even and has no prime factor but 2 and 3 (mrc_create's rule for the long block: N/4 and N/2 factor into 2s and 3s --
+ * 1024, 768, 576, 512, 384, ...), for which the rate has a band table.  Anything else: MRC_ERR_INVALID, "header field out of
+ * range" (or the band table's own text) in mrc_last_error(NULL). */
 int mrc_pac_read_header(const uint8_t* buf, int64_t len, mrc_config* cfg, int32_t* n_channels, uint32_t* num_samples,
                         int64_t* data_offset);
 /* Offsets of the `<L nBytes` + payload chunks after the header; returns their number (chunk_offset may be NULL /
@@ -651,7 +655,9 @@ int64_t mrc_pac_scan_chunks(const uint8_t* buf, int64_t len, int64_t data_offset
  * records with raw or Huffman-coded mantissas (prefix decoding by table; ids in sorted-name order).  Fixed strides
  * because the shape varies from block to block: overall_scale [n][joint ? 4 : n_channels], ms_switch
  * [n][MRC_MAX_BANDS], huff_table [n][n_channels], scale_factor / bit_alloc [n][n_channels][MRC_MAX_BANDS], mantissa
- * [n][n_channels][n_mdct_lines] dense.  chunk_offset [n * n_channels]. */
+ * [n][n_channels][n_mdct_lines] dense.  chunk_offset [n * n_channels].  A refusal (MRC_ERR_INVALID) names the first chunk
+ * refused and why in mrc_last_error(NULL), "mrc_unpack_blocks: chunk at byte <offset>: <reason>", the reason in the words
+ * mrc_decode_pac_pcm16, the store and mrc_pac_nmr use for the same chunk. */
 int mrc_unpack_blocks(const mrc_config* cfg, int64_t n_blocks, int n_channels, int joint, const uint8_t* buf, int64_t len,
                       const int64_t* chunk_offset, int32_t* a, int32_t* b, int32_t* huff_table, int32_t* overall_scale,
                       int32_t* ms_switch, int32_t* scale_factor, int32_t* bit_alloc, int32_t* mantissa);

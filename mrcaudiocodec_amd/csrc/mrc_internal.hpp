@@ -180,6 +180,7 @@ const int* pack_error_flag(const void* ws, int64_t nChunks);          // device 
 const long long* pack_total_bytes(const void* ws, int64_t nChunks);
 // mrc_kernels_unpack.hip -- `.pac` chunk parsing on the device (the parser itself: mrc_unpack.hpp)
 void unpack_tables(UnpackTables* out);                      // host, from the table data in mrc_pack.cpp
+const char* unpack_status_text(int flag);                   // the words for a set of (1 << UnpackStatus) bits (mrc_api_decode.cpp)
 struct UnpackErr { int flag; int firstBad; };               // first bad chunk (lowest index) and its UnpackStatus
 // layout of mrc_unpack_blocks: chunk c = blk * nch + ch, buf / chunkOffset / outputs in device memory
 hipError_t launch_unpack_fixed(const UnpackParams& P, const UnpackBands& B, const UnpackTables* T /* device */,

@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <mutex>
 #include <thread>
 
 namespace {
@@ -549,8 +550,10 @@ int mrc_pac_read_header(const uint8_t* buf, int64_t len, mrc_config* cfg, int32_
     const uint32_t nBands = get_u32le(buf + 22);
     if (nBands > 4096 || 26 + 2 * (int64_t)nBands > len) return refuse("mrc_pac_read_header: band count out of range");
     // the header is untrusted input and sizes every later allocation: refuse what no encoder writes
+    // (block length: the rule of build_shape for the long block -- N/4 = L/2 and N/2 = L factor into 2s and 3s)
+    auto smooth = [](int n) { while (n % 2 == 0) n /= 2; while (n % 3 == 0) n /= 3; return n == 1; };
     if (cfg->sample_rate <= 0 || *n_channels < 1 || *n_channels > 2 || cfg->n_mdct_lines < 16 ||
-        cfg->n_mdct_lines > 8192 || (cfg->n_mdct_lines & (cfg->n_mdct_lines - 1)) != 0 || cfg->n_scale_bits < 1 ||
+        cfg->n_mdct_lines > 8192 || cfg->n_mdct_lines % 2 != 0 || !smooth(cfg->n_mdct_lines) || cfg->n_scale_bits < 1 ||
         cfg->n_scale_bits > 4 || cfg->n_mant_size_bits < 1 || cfg->n_mant_size_bits > 8)
         return refuse("mrc_pac_read_header: header field out of range");
     // the band table itself is implied by rate and block length: a rate the reference could not have encoded at is refused
@@ -583,23 +586,34 @@ int mrc_unpack_blocks(const mrc_config* cfg, int64_t n_blocks, int n_channels, i
         !shape_ok(cfg, cfg->n_mdct_lines, cfg->n_mdct_lines))
         return MRC_ERR_INVALID;
     const int L = cfg->n_mdct_lines, nOs = joint ? 4 : n_channels;
-    std::atomic<int> bad{0};
+    // the first chunk refused (lowest index) and why, in the words of the device paths (unpack_status_text)
+    std::mutex badLock;
+    int64_t badChunk = -1;
+    int badWhy = 0;
+    auto refuse_chunk = [&](int64_t chunk, int why) {
+        std::lock_guard<std::mutex> g(badLock);
+        if (badChunk < 0 || chunk < badChunk) { badChunk = chunk; badWhy = why; }
+    };
     parallel_for(n_blocks, [&](int64_t blk) {
         std::vector<int> bandN;
         for (int ch = 0; ch < n_channels; ++ch) {
-            const int64_t off = chunk_offset[blk * n_channels + ch];
-            if (off < 0 || off + 4 > len) { bad = 1; return; }
+            const int64_t chunk = blk * n_channels + ch;
+            const int64_t off = chunk_offset[chunk];
+            if (off < 0 || off + 4 > len) { refuse_chunk(chunk, mrc::kUnpackTruncated); return; }
             const int64_t nBytes = get_u32le(buf + off);
-            if (off + 4 + nBytes > len) { bad = 1; return; }
+            if (off + 4 + nBytes > len) { refuse_chunk(chunk, mrc::kUnpackTruncated); return; }
             BitReader r(buf + off + 4, nBytes);
             const int table = (int)r.get(4);
-            if (table != kRawTable && table > 3) { bad = 1; return; }
+            if (table != kRawTable && table > 3) { refuse_chunk(chunk, mrc::kUnpackBadTable); return; }
             const int swA = (int)r.get(cfg->blksw_bits_a), swB = (int)r.get(cfg->blksw_bits_b);
             const int a = swA ? cfg->n_short : L, b = swB ? cfg->n_short : L;      // pacfileThem.py:206-207
             if (ch == 0) { a_out[blk] = a; b_out[blk] = b; }
-            else if (a != a_out[blk] || b != b_out[blk]) { bad = 1; return; }
-            if (!mrc::band_table(*cfg, a, b, &bandN) || (int)bandN.size() > MRC_MAX_BANDS) { bad = 1; return; }
-            huff_table[blk * n_channels + ch] = table;
+            else if (a != a_out[blk] || b != b_out[blk]) { refuse_chunk(chunk, mrc::kUnpackBadShape); return; }
+            if (!mrc::band_table(*cfg, a, b, &bandN) || (int)bandN.size() > MRC_MAX_BANDS) {
+                refuse_chunk(chunk, mrc::kUnpackBadShape);
+                return;
+            }
+            huff_table[chunk] = table;
             if (joint) {
                 if (ch == 0) {
                     for (int i = 0; i < 4; ++i) overall_scale[blk * 4 + i] = (int32_t)r.get(cfg->n_scale_bits);
@@ -609,16 +623,36 @@ int mrc_unpack_blocks(const mrc_config* cfg, int64_t n_blocks, int n_channels, i
             } else {
                 overall_scale[blk * nOs + ch] = (int32_t)r.get(cfg->n_scale_bits);
             }
-            int32_t* sf = scale_factor + (blk * n_channels + ch) * MRC_MAX_BANDS;
-            int32_t* ba = bit_alloc + (blk * n_channels + ch) * MRC_MAX_BANDS;
-            int32_t* m = mantissa + (blk * n_channels + ch) * (int64_t)L;
+            int32_t* sf = scale_factor + chunk * MRC_MAX_BANDS;
+            int32_t* ba = bit_alloc + chunk * MRC_MAX_BANDS;
+            int32_t* m = mantissa + chunk * (int64_t)L;
             std::memset(sf, 0, sizeof(int32_t) * MRC_MAX_BANDS);
             std::memset(ba, 0, sizeof(int32_t) * MRC_MAX_BANDS);
             std::memset(m, 0, sizeof(int32_t) * L);
-            if (!read_band_records(r, *cfg, table, bandN, sf, ba, m)) { bad = 1; return; }
+            if (!read_band_records(r, *cfg, table, bandN, sf, ba, m)) {
+                // why: the portable parser (mrc_unpack.hpp, what the device runs) on the same chunk names it
+                static const mrc::UnpackTables* T = [] { auto* t = new mrc::UnpackTables; mrc::unpack_tables(t); return t; }();
+                const int shape = (swA ? 2 : 0) + (swB ? 1 : 0);
+                mrc::UnpackParams P{cfg->n_scale_bits, cfg->n_mant_size_bits, cfg->blksw_bits_a, cfg->blksw_bits_b, cfg->n_short, L};
+                mrc::UnpackBands B;
+                for (int q = 0; q < 4; ++q) { B.nBands[q] = -1; B.halfN[q] = 0; B.bandN[q] = nullptr; }
+                B.nBands[shape] = (int)bandN.size();
+                B.halfN[shape] = (a + b) / 2;
+                B.bandN[shape] = bandN.data();
+                mrc::UnpackDst D{nullptr, nullptr, nullptr, sf, ba, m, MRC_MAX_BANDS, L};
+                int got = 0;
+                const int why = mrc::unpack_chunk(buf + off + 4, nBytes, P, B, T->lut, T->escape, joint, ch, -1, &got, D);
+                refuse_chunk(chunk, why != mrc::kUnpackOk ? why : (int)mrc::kUnpackTruncated);
+                return;
+            }
         }
     });
-    return bad.load() ? MRC_ERR_INVALID : MRC_OK;
+    if (badChunk >= 0) {
+        const int64_t at = chunk_offset[badChunk];
+        return refuse("mrc_unpack_blocks: chunk at byte " + std::to_string((long long)at) + ": " +
+                      mrc::unpack_status_text(1 << badWhy));
+    }
+    return MRC_OK;
 }
 
 }  // extern "C"

@@ -416,7 +416,7 @@ def unpack_blocks(cfg, buf, chunk_offsets, n_channels, joint):
     p = lambda k: out[k].ctypes.data_as(_i32p)
     _check(lib.mrc_unpack_blocks(C.byref(cfg), n, n_channels, int(bool(joint)), raw.ctypes.data_as(_u8p), raw.size,
                                  offs.ctypes.data_as(_i64p), p("a"), p("b"), p("huff_table"), p("overall_scale"),
-                                 p("ms_switch"), p("scale_factor"), p("bit_alloc"), p("mantissa")), "mrc_unpack_blocks")
+                                 p("ms_switch"), p("scale_factor"), p("bit_alloc"), p("mantissa")), "mrc_unpack_blocks", reason=True)
     return out
 
 

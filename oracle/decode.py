@@ -138,8 +138,9 @@ class BitReader:
         return v
 
 
-def read_header(buf):
-    """pacfileThem.py:130-158 -> (CodingParams, offset of the first chunk)."""
+def read_header(buf, n_short=128, blksw_bits=(1, 1)):
+    """pacfileThem.py:130-158 -> (CodingParams, offset of the first chunk).  The short block length and the widths of the two
+    block-switch fields are not in the file (the reference has them as literals): n_short, blksw_bits name another codec's."""
     if buf[:4] != b"PAC ":
         raise ValueError("not a PAC file")
     fmt = '<LHLLHH'
@@ -154,9 +155,9 @@ def read_header(buf):
     cp.nMDCTLines = cp.nSamplesPerBlock = nMDCTLines
     cp.nScaleBits, cp.nMantSizeBits = nScaleBits, nMantSizeBits
     cp.sfBands = ScaleFactorBands(nLines)
-    cp.nSamplesShort = 128
+    cp.nSamplesShort = int(n_short)
     cp.a = cp.b = nMDCTLines
-    cp.blkswBitA = cp.blkswBitB = 1
+    cp.blkswBitA, cp.blkswBitB = int(blksw_bits[0]), int(blksw_bits[1])
     return cp, off
 
 
@@ -183,8 +184,9 @@ def _read_prefix(pb, cp):
     """huffTable, block-switch bits -> cp.a, cp.b, cp.sfBands (pacfileThem.py:196-216)."""
     huffTable = pb.ReadBits(4)
     swA, swB = pb.ReadBits(cp.blkswBitA), pb.ReadBits(cp.blkswBitB)
-    cp.a = (1 - swA) * cp.nMDCTLines + swA * 128
-    cp.b = (1 - swB) * cp.nMDCTLines + swB * 128
+    swA, swB = int(swA != 0), int(swB != 0)             # any set bit of a wider field: short (pacfileThem.py:206-207)
+    cp.a = (1 - swA) * cp.nMDCTLines + swA * cp.nSamplesShort
+    cp.b = (1 - swB) * cp.nMDCTLines + swB * cp.nSamplesShort
     half = (cp.a + cp.b) // 2
     if cp.a + cp.b == 2 * cp.nMDCTLines:
         cp.sfBands = ScaleFactorBands(AssignMDCTLinesFromFreqLimits(half, cp.sampleRate))
@@ -246,11 +248,11 @@ def parse_joint_block(chunk0, chunk1, cp):
                 bitAlloc=[ba0, ba1], mantissa=[m0, m1])
 
 
-def decode_pac(buf):
-    """Decode a whole `.pac` byte string -> (cp, float64 [nCh][samples]): the concatenation of what successive
+def decode_pac(buf, n_short=128, blksw_bits=(1, 1)):
+    """Decode a whole `.pac` byte string (n_short, blksw_bits: as read_header) -> (cp, float64 [nCh][samples]): the concatenation of what successive
     (Joint)ReadDataBlock calls return, final overlap-and-add tail included.  The first block's output is the
     half-block delay of the MDCT (zeros overlap) and is kept here; pcm16() drops it like the reference's loop."""
-    cp, off = read_header(buf)
+    cp, off = read_header(buf, n_short, blksw_bits)
     chunks = split_chunks(buf, off)
     nCh = cp.nChannels
     if len(chunks) % nCh:

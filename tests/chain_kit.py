@@ -7,6 +7,7 @@ The seeds the GPU tests pass to the generators were picked so that the NumPy res
 to what a generator returns for given arguments changes what those tests run on.
 """
 import ctypes as C
+import math
 import os
 import re
 
@@ -106,6 +107,63 @@ def write_wav(path, pcm, rate=48000):
     with open(str(path), "wb") as f:
         f.write(cli.wav_bytes(pcm, rate))
     return str(path)
+
+
+# ------------------------------------------------------------------ mrc_pac_nmr against its restatement
+NMR_EPS = 1e-12
+
+
+def check_nmr_against_restatement(got, buf, pcm, n_short=128, blksw_bits=(1, 1)):
+    """one file's detailed Handle.pac_nmr result against tests/nmr_restatement.restate (the bars: tests/test_gpu_nmr.py)"""
+    import nmr_restatement as nr
+    want = nr.restate(buf, pcm, n_short, blksw_bits)
+    assert got["n_blocks"] == want["n_blocks"]
+    assert np.array_equal(got["shape"], want["shape"])
+    near_one = 0
+    for e, w in enumerate(want["entries"]):
+        nb = len(w["noise"])
+        gn, gm = got["noise"][e, :nb], got["mask"][e, :nb]
+        assert np.all(np.isnan(got["noise"][e, nb:]))
+        assert np.array_equal(np.isinf(gm), np.isinf(w["mask"])), e
+        fin = np.isfinite(w["mask"])
+        assert np.all(np.abs(gm[fin] - w["mask"][fin]) <= 1e-9 * w["mask"][fin]), e
+        n_j = np.asarray(w["n_lines"], np.float64)
+        P = w["peak"]
+        tol = 2.0 * (4 * NMR_EPS * P * np.sqrt(n_j * w["noise"]) + 4 * n_j * NMR_EPS ** 2 * P ** 2)
+        assert np.all(np.abs(gn - w["noise"]) <= tol), (e, np.max(np.abs(gn - w["noise"]) - tol))
+        big = (w["noise"] >= 1e6 * tol) & (w["noise"] > 0) & fin
+        gdb = got["nmr_db"][e, :nb]
+        with np.errstate(divide="ignore"):
+            wdb = 10 * np.log10(w["r"])
+        assert np.all(np.abs(gdb[big] - wdb[big]) <= 1e-5), e
+        # disturbed: the restatement's deciding ratio may lie within the tolerance of 1
+        rtol = np.where(fin, (tol + 1e-9 * w["noise"]) / np.maximum(w["mask"], 1e-300), 0.0)
+        near_one += int(np.any(np.abs(w["r"] - 1.0) <= rtol + 1e-9))
+    assert abs(got["disturbed_blocks"] - want["disturbed_blocks"]) <= near_one
+    return want
+
+
+def check_nmr_summaries(got):
+    """the four numbers from the returned band arrays, in NumPy"""
+    noise, mask, shape = got["noise"], got["mask"], got["shape"]
+    E = len(shape)
+    if E == 0:
+        assert got["nmr_max_db"] == -math.inf and got["nmr_total_db"] == -math.inf and got["disturbed_blocks"] == 0
+        return
+    nch = E // got["n_blocks"]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.where(np.isinf(mask), 0.0, noise / mask)
+    rmax = np.nanmax(r)
+    db = (lambda v: 10.0 * math.log10(v) if v > 0 else -math.inf)
+    assert got["nmr_max_db"] == db(float(rmax))
+    emax = np.nanmax(r, axis=1)
+    assert got["disturbed_blocks"] == int(np.sum(np.any(emax.reshape(-1, nch) > 1.0, axis=1)))
+    mean = np.nanmean(r, axis=1)
+    total = float(np.sum(shape[:, 1] * mean) / np.sum(shape[:, 1]))
+    if total > 0:
+        assert abs(got["nmr_total_db"] - db(total)) <= 1e-12 * abs(db(total)) + 1e-11
+    else:
+        assert got["nmr_total_db"] == -math.inf
 
 
 # ------------------------------------------------------------------ the binding against the header

@@ -77,9 +77,9 @@ def entry_from_parsed(seg, cp, Xhat, sample_rate):
     return dict(noise=noise, mask=mask, r=r, peak=float(np.abs(X).max()), X=X, n_lines=np.asarray(cp.sfBands.nLines))
 
 
-def parse_file(buf):
-    """-> (cp, nCh, [(a, b, joint, parsed block)])"""
-    cp, off = odec.read_header(buf)
+def parse_file(buf, n_short=128, blksw_bits=(1, 1)):
+    """-> (cp, nCh, [(a, b, joint, parsed block)]); n_short, blksw_bits: as oracle.decode.read_header"""
+    cp, off = odec.read_header(buf, n_short, blksw_bits)
     chunks = odec.split_chunks(buf, off)
     nCh = cp.nChannels
     nBlocks = len(chunks) // nCh
@@ -95,9 +95,10 @@ def parse_file(buf):
     return cp, nCh, blocks
 
 
-def restate(buf, pcm):
-    """One file against its source (int16 [nCh][n], no prior hop) -> dict(entries=[...], shape [E, 2], summaries)."""
-    cp, nCh, blocks = parse_file(buf)
+def restate(buf, pcm, n_short=128, blksw_bits=(1, 1)):
+    """One file against its source (int16 [nCh][n], no prior hop) -> dict(entries=[...], shape [E, 2], summaries).
+    n_short, blksw_bits: as oracle.decode.read_header."""
+    cp, nCh, blocks = parse_file(buf, n_short, blksw_bits)
     L = cp.nMDCTLines
     rate = cp.sampleRate
     pcm = np.atleast_2d(pcm)

@@ -44,10 +44,11 @@ def _close_handles():
     _HANDLES.clear()
 
 
-def _dev_parse(case):
-    """Handle.dev_unpack_blocks on device copies of the case -> dict of host arrays, or None if refused"""
+def _dev_parse(case, hd=None):
+    """Handle.dev_unpack_blocks on device copies of the case -> dict of host arrays, or None if refused (hd: the handle to
+    parse on; None: one of the case's rate and allocation-field width)"""
     from mrcaudiocodec_amd import MrcError
-    hd = _handle_for(case["cfg"])
+    hd = hd if hd is not None else _handle_for(case["cfg"])
     dev = torch.device("cuda", 0)
     nch, joint, L = case["nch"], case["joint"], case["cfg"].n_mdct_lines
     offs = np.ascontiguousarray(case["offsets"], np.int64)
@@ -67,10 +68,10 @@ def _dev_parse(case):
     return {k: v.cpu().numpy() for k, v in out.items()}
 
 
-def _compare(cases):
+def _compare(cases, hd=None):
     n_acc = n_rej = 0
     for c in cases:
-        want, got = UC.host_parse(c), _dev_parse(c)
+        want, got = UC.host_parse(c), _dev_parse(c, hd)
         if want is None:
             assert got is None, "%s: the host parser refuses, the device accepts" % c["label"]
             n_rej += 1

@@ -17,11 +17,11 @@ import pytest
 import chain_kit as kit
 import nmr_restatement as nr
 from chain_kit import HOP, handles_closed_after_module as _close_handles  # noqa: F401
+from chain_kit import check_nmr_against_restatement as _check_against_restatement, check_nmr_summaries as _check_summaries
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-EPS = 1e-12
 
 
 def _handle(rate=48000):
@@ -43,57 +43,6 @@ def _golden_cases():
 def _load(name, key, case):
     d = np.load(os.path.join(GOLDEN, name))
     return d[key].tobytes(), np.ascontiguousarray(d[case + "_pcm"]), int(d[case + "_rate"])
-
-
-def _check_against_restatement(got, buf, pcm):
-    want = nr.restate(buf, pcm)
-    assert got["n_blocks"] == want["n_blocks"]
-    assert np.array_equal(got["shape"], want["shape"])
-    near_one = 0
-    for e, w in enumerate(want["entries"]):
-        nb = len(w["noise"])
-        gn, gm = got["noise"][e, :nb], got["mask"][e, :nb]
-        assert np.all(np.isnan(got["noise"][e, nb:]))
-        assert np.array_equal(np.isinf(gm), np.isinf(w["mask"])), e
-        fin = np.isfinite(w["mask"])
-        assert np.all(np.abs(gm[fin] - w["mask"][fin]) <= 1e-9 * w["mask"][fin]), e
-        n_j = np.asarray(w["n_lines"], np.float64)
-        P = w["peak"]
-        tol = 2.0 * (4 * EPS * P * np.sqrt(n_j * w["noise"]) + 4 * n_j * EPS ** 2 * P ** 2)
-        assert np.all(np.abs(gn - w["noise"]) <= tol), (e, np.max(np.abs(gn - w["noise"]) - tol))
-        big = (w["noise"] >= 1e6 * tol) & (w["noise"] > 0) & fin
-        gdb = got["nmr_db"][e, :nb]
-        with np.errstate(divide="ignore"):
-            wdb = 10 * np.log10(w["r"])
-        assert np.all(np.abs(gdb[big] - wdb[big]) <= 1e-5), e
-        # disturbed: the restatement's deciding ratio may lie within the tolerance of 1
-        rtol = np.where(fin, (tol + 1e-9 * w["noise"]) / np.maximum(w["mask"], 1e-300), 0.0)
-        near_one += int(np.any(np.abs(w["r"] - 1.0) <= rtol + 1e-9))
-    assert abs(got["disturbed_blocks"] - want["disturbed_blocks"]) <= near_one
-    return want
-
-
-def _check_summaries(got):
-    """the four numbers from the returned band arrays, in NumPy"""
-    noise, mask, shape = got["noise"], got["mask"], got["shape"]
-    E = len(shape)
-    if E == 0:
-        assert got["nmr_max_db"] == -math.inf and got["nmr_total_db"] == -math.inf and got["disturbed_blocks"] == 0
-        return
-    nch = E // got["n_blocks"]
-    with np.errstate(divide="ignore", invalid="ignore"):
-        r = np.where(np.isinf(mask), 0.0, noise / mask)
-    rmax = np.nanmax(r)
-    db = (lambda v: 10.0 * math.log10(v) if v > 0 else -math.inf)
-    assert got["nmr_max_db"] == db(float(rmax))
-    emax = np.nanmax(r, axis=1)
-    assert got["disturbed_blocks"] == int(np.sum(np.any(emax.reshape(-1, nch) > 1.0, axis=1)))
-    mean = np.nanmean(r, axis=1)
-    total = float(np.sum(shape[:, 1] * mean) / np.sum(shape[:, 1]))
-    if total > 0:
-        assert abs(got["nmr_total_db"] - db(total)) <= 1e-12 * abs(db(total)) + 1e-11
-    else:
-        assert got["nmr_total_db"] == -math.inf
 
 
 @pytest.mark.parametrize("name,key,case", _golden_cases())

@@ -195,14 +195,18 @@ def _huff(m, ba, cp, huffman):
     return t, codes
 
 
-def encode(pcm, shapes, c, sample_rate=48000, huffman=True, num_samples=None):
+def encode(pcm, shapes, c, sample_rate=48000, huffman=True, num_samples=None, cp=None):
     """pcm int16 [nCh][n], every row starting with its zero prior hop; shapes [(offset, a, b)] ending in a long block; c the
     linear ceiling -> dict(data = the `.pac` bytes, capped, edges, blocks = [dict per block, Close()'s blocks (one per
-    channel) last])."""
+    channel) last]).  cp: the oracle CodingParams of another codec setting (block lengths, field widths; its rate and
+    channel count are used), else the defaults at sample_rate."""
     pcm = np.atleast_2d(pcm)
     nch = pcm.shape[0]
     x = nmr.pcm_to_float(pcm)
-    cp = codec.default_params(sampleRate=sample_rate, nChannels=nch)
+    if cp is None:
+        cp = codec.default_params(sampleRate=sample_rate, nChannels=nch)
+    sample_rate = cp.sampleRate
+    assert cp.nChannels == nch
     L = cp.nMDCTLines
     shapes = [(int(o), int(a), int(b)) for (o, a, b) in shapes]
     assert shapes[-1][2] == L and shapes[0][1] == L
