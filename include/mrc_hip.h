@@ -854,7 +854,9 @@ int mrc_set_option(mrc_handle* h, int option, int value);
 int mrc_get_option(mrc_handle* h, int option, int32_t* value);
 int mrc_get_stage_ms(mrc_handle* h, double* ms /*[3]*/);
 /* ... and per kernel: ms[0..4] = MDCT, smr_kernel, band_stats_kernel (joint only, else ~0), bitalloc_kernel,
- * quantize_kernel. */
+ * quantize_kernel.  Long blocks (1024 lines, 25 bands, 16-byte aligned planes) run the last two as one kernel,
+ * alloc_quant_long_kernel: ms[3] is then the gap between two event records (a few microseconds, no kernel) and ms[4] the
+ * fused kernel's time. */
 int mrc_get_kernel_ms(mrc_handle* h, double* ms /*[5]*/);
 
 #ifdef __cplusplus

@@ -124,7 +124,8 @@ hipError_t launch_alloc_quant(const DevShape& S, int64_t nFrames, int joint, con
                               int* resOut, double* bandPeakWs,
                               bool peaksReady /* bandPeakWs already filled by launch_smr */,
                               bool msReady /* msSwitch already filled (launch_ms_switch ran before launch_smr) */,
-                              hipEvent_t evStats, hipEvent_t evAlloc /* recorded after band_stats / after bitalloc; null: not */,
+                              hipEvent_t evStats, hipEvent_t evAlloc /* recorded after band_stats / after bitalloc (in front of the fused
+                              long-block kernel); null: not */,
                               hipStream_t st);
 hipError_t launch_pcm_to_float(int64_t n, const short* pcm, double* out, hipStream_t st);
 hipError_t launch_quantize_uniform(int64_t n, int nBits, const double* x, long long* out, hipStream_t st);

@@ -8,6 +8,12 @@
 //   quantize_kernel     quantize.py:114-146 (per-band scale factor with nMantBits = allocation) and
 //                       quantize.py:294-322 (mantissas), codecThem.py:335-350 / 510-559 -- one wavefront per
 //                       (frame, stream), 16 lines per lane, coalesced int32 stores
+//   alloc_quant_long_kernel   both of them for the long block (1024 lines, 25 bands, 16-byte aligned planes) in one kernel:
+//                       64 frames per workgroup of four waves; wave 0 runs the greedy loop, then all four quantise.  The
+//                       workgroups of a CU drift apart, so the serial loops of some overlap the line streaming of others.
+//                       Every other shape, band count and alignment takes bitalloc_kernel + quantize_kernel.
+// Timing mode (mrc_get_kernel_ms): where the fused kernel runs, the event between the two slots is recorded in front of it --
+// the bit allocation reports the gap between two event records (microseconds) and the quantiser's slot holds the fused kernel.
 // Integer-deciding float64 arithmetic keeps the reference's operation order (file built with
 // -ffp-contract=off).
 #include "mrc_device.hpp"
@@ -227,10 +233,8 @@ __global__ __launch_bounds__(kWave) void bitalloc_cases_kernel(int64_t nCases, i
 // ------------------------------------------------------------------------------------------------
 // scale factors + mantissas: one wavefront per (frame, stream)
 // ------------------------------------------------------------------------------------------------
-// LONGJ: -1 any shape, joint or not at run time; 0 / 1: the long block (1024 lines), independent / joint channels fixed at
-// compile time (the four iterations of the line loop unroll, the stream arithmetic folds)
-template <class OutT, int LONGJ>                       // int32 plane, or uint16 (codes are at most 16 bits wide: codecThem.py:292-293)
-__global__ __launch_bounds__(kWave) void quantize_kernel(DevShape S, int jointArg, const double* __restrict__ lines,
+template <class OutT>                                  // int32 plane, or uint16 (codes are at most 16 bits wide: codecThem.py:292-293)
+__global__ __launch_bounds__(kWave) void quantize_kernel(DevShape S, int joint, const double* __restrict__ lines,
                                                          const int* __restrict__ oscale,
                                                          const double* __restrict__ bandPeak,
                                                          const int* __restrict__ msSwitch,
@@ -240,11 +244,10 @@ __global__ __launch_bounds__(kWave) void quantize_kernel(DevShape S, int jointAr
     __shared__ unsigned int sInfo[kMaxBands];            // per band: bits | scale factor << 8 | overall scale << 16 | signal << 24
     __shared__ __attribute__((aligned(4))) unsigned char sBand[kBandLds];   // band of every line (copy of S.bandOfLine)
     const int lane = threadIdx.x;
-    const int joint = LONGJ < 0 ? jointArg : LONGJ;
     const int nstream = joint ? 2 : 1, nsig = joint ? 4 : 1;
     const int64_t f = blockIdx.x / nstream;
     const int strm = blockIdx.x % nstream;
-    const int M = LONGJ < 0 ? S.halfN : 1024, nb = S.nBands;
+    const int M = S.halfN, nb = S.nBands;
     const double* X = lines + f * nsig * M;
     const int* osc = oscale + f * nsig;
     // the line -> band map goes to LDS with the other per-band values: the loop below then has ONE global round
@@ -270,7 +273,7 @@ __global__ __launch_bounds__(kWave) void quantize_kernel(DevShape S, int jointAr
         const int ba = (int)(info & 0xff);
         return (OutT)(ba ? mantissa_dev(ldexp(x, (int)((info >> 16) & 0xff)), (int)((info >> 8) & 0xff), S.nScaleBits, ba) : 0);
     };
-    if ((LONGJ >= 0 || vecOk) && bandInLds && !(M & 3)) {       // (LONGJ: the launcher has checked the alignment)
+    if (vecOk && bandInLds && !(M & 3)) {
         // a lane takes FOUR CONSECUTIVE lines: one LDS word for their bands, 32 contiguous bytes of lines (one signal: the
         // four lines of a lane lie in one band almost always), one 8- or 16-byte store of the four codes
         for (int k = 4 * lane; k < M; k += 4 * kWave) {
@@ -323,6 +326,211 @@ __global__ __launch_bounds__(kWave) void quantize_kernel(DevShape S, int jointAr
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// the long block (1024 lines, 25 bands, 16-byte aligned planes): bit allocation, scale factors and mantissas of 64 frames in
+// ONE workgroup of four waves.  bitalloc_kernel keeps one wave busy per 17 KB of LDS and leaves HBM idle; quantize_kernel
+// streams HBM and has next to no arithmetic.  Here the workgroups of a CU fall out of step after their first round, so
+// that some run the serial loop (phase 1) while others stream lines (phase 2).
+//   stage in   all four waves: the selected SMRs, coalesced, into run[][] ([band][lane], as bitalloc_kernel lays it out), the
+//              line -> band map once per workgroup.  Here and below only the signal the M/S switch selects is ever read:
+//              smr_kernel leaves the others' SMRs and peaks unwritten.
+//   phase 1    wave 0: bitalloc_lane<NTOT>, one lane per frame; reservoir_out
+//   between    all 256 threads: band peaks in, scale factors, bit_alloc and scale_factor out (coalesced), info words into
+//              LDS over run[]
+//   phase 2    each wave: every fourth (frame, stream), quantize_kernel's four-lines-per-lane loop with all the loads of
+//              fused_depth() units requested before the first line is coded
+// ------------------------------------------------------------------------------------------------
+constexpr int kFusedWaves = 4, kFusedThreads = kFusedWaves * kWave;
+// (frame, stream) units whose line loads a wave has in flight.  Joint: LDS allows four workgroups per CU, which leaves each
+// wave 128 registers -- two units.  Mono: eight workgroups per CU need 64 registers or fewer -- one unit (sixteen loads of
+// 8 bytes per lane); two units (92 registers, five workgroups per CU) measured the same step time.
+__host__ __device__ constexpr int fused_depth(int nTot) { return nTot == 50 ? 2 : 1; }
+__host__ __device__ inline size_t fused_lds_bytes(int nTot) { return alloc_lds_bytes(nTot, kWave) + 1024; }
+
+template <int NTOT, class OutT>
+__global__ __launch_bounds__(kFusedThreads) void alloc_quant_long_kernel(DevShape S, int64_t nFrames,
+                                                                          const double* __restrict__ lines,
+                                                                          const int* __restrict__ oscale,
+                                                                          const double* __restrict__ smr,
+                                                                          const double* __restrict__ bandPeak,
+                                                                          const int* __restrict__ msSwitch,
+                                                                          const int* __restrict__ resIn,
+                                                                          int* __restrict__ bitAlloc,
+                                                                          int* __restrict__ scaleFactor,
+                                                                          OutT* __restrict__ mantissa,
+                                                                          int* __restrict__ resOut) {
+    static_assert(NTOT == 25 || NTOT == 50, "25 bands, one or two streams");
+    constexpr int nb = 25, M = 1024;
+    constexpr bool joint = NTOT == 50;
+    constexpr int nstream = joint ? 2 : 1, nsig = joint ? 4 : 1;
+    constexpr int kElems = kWave * NTOT;                 // (frame, stream, band) triples of the workgroup
+    constexpr int kPer = (kElems + kFusedThreads - 1) / kFusedThreads;
+    constexpr int kFusedDepth = fused_depth(NTOT);
+    extern __shared__ double lds[];
+    const AllocSlabs A = alloc_slabs(lds, NTOT, kWave);
+    unsigned int* sBand = reinterpret_cast<unsigned int*>(reinterpret_cast<unsigned char*>(lds) + alloc_lds_bytes(NTOT, kWave));
+    unsigned int* sInfo = reinterpret_cast<unsigned int*>(A.run);   // [frame][stream][band], after phase 1 (run[] is dead then)
+    const int tid = threadIdx.x, lane = tid & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(tid / kWave);      // (uniform: the unit loop of phase 2 runs on scalars)
+    const int64_t f0 = (int64_t)blockIdx.x * kWave;
+    const int nValid = (int)(nFrames - f0 < kWave ? nFrames - f0 : kWave);
+
+    // triple e = [frame][stream][band] of the workgroup -> the signal the encoder codes there and where its SMR and peak lie.
+    // stream 0 = Mid-or-Left, stream 1 = Side-or-Right (ms_stereo.py:70-81, codecThem.py:485,524-551)
+    struct Sel { int64_t osIdx, src; int sig; };
+    auto selected = [&](int e) -> Sel {
+        const int fl = e / NTOT, i = e - fl * NTOT;
+        const int64_t f = f0 + fl;
+        const int band = i % nb, strm = i / nb;
+        const int sig = joint ? (msSwitch[f * nb + band] ? 2 + strm : strm) : 0;
+        return Sel{f * nsig + sig, (f * nsig + sig) * nb + band, sig};
+    };
+
+    // ---- stage in.  (Here and between the phases a thread's loads are unconditional -- a triple beyond the last frame reads the
+    // last valid one's -- so that all of them go out before the first is used: one round trip, not one per triple.)
+    const int lastElem = nValid * NTOT - 1;
+    const bool active = wave == 0 && lane < nValid;       // phase 1: lane <-> frame
+    double r;
+    {
+        double v[kPer];
+#pragma unroll
+        for (int j = 0; j < kPer; ++j) v[j] = smr[selected(min(tid + j * kFusedThreads, lastElem)).src];
+        const unsigned int bandWord = reinterpret_cast<const unsigned int*>(S.bandOfLine)[tid];
+        const int nLinesOfBand = S.bandN[tid % nb];
+        r = (active && resIn) ? (double)resIn[f0 + lane] : 0.0;
+        sBand[tid] = bandWord;
+        if (tid < NTOT) A.nLines[tid] = nLinesOfBand;
+#pragma unroll
+        for (int j = 0; j < kPer; ++j) {
+            const int e = tid + j * kFusedThreads;
+            if (e < kElems) {
+                const int fl = e / NTOT, i = e - fl * NTOT;
+                A.run[i * kWave + fl] = e <= lastElem ? v[j] : 0.0;
+                A.bits[i * kWave + fl] = 0;
+            }
+        }
+    }
+    __syncthreads();
+
+    // ---- phase 1: the greedy loop, one lane per frame
+    if (wave == 0) {
+        double budget;
+        if (joint) { budget = S.budgetJointPre + r; budget -= S.blkswA; budget -= S.blkswB; }   // codecThem.py:390-396
+        else budget = S.budgetMono + r;                                                           // codecThem.py:308
+        const double left = bitalloc_lane<NTOT>(A, NTOT, S.maxMantBits, budget, lane, active);
+        if (active) resOut[f0 + lane] = (int)left;                // int(bitsLeft): truncation toward zero (bitalloc.py:155)
+    }
+    __syncthreads();
+
+    // ---- between the phases: codecThem.py:346-347, ScaleFactor(max |scaled line| of the band, nScaleBits, nMantBits = bitAlloc)
+    // (the peaks are loaded here and not ahead of phase 1: held across the loop they cost wave 0 a third more registers,
+    // which is workgroups per CU.  Scaling by 2^overallScale is exact, so max and scale commute.)
+    // (tidB: the triples' indices and addresses are worked out again, not carried through phase 1 in registers)
+    int tidB = tid;
+    asm volatile("" : "+v"(tidB));
+    double peak[kPer];
+    int os[kPer], sig[kPer];
+#pragma unroll
+    for (int j = 0; j < kPer; ++j) {
+        const Sel s = selected(min(tidB + j * kFusedThreads, lastElem));
+        os[j] = oscale[s.osIdx];
+        peak[j] = bandPeak[s.src];
+        sig[j] = s.sig;
+    }
+#pragma unroll
+    for (int j = 0; j < kPer; ++j) {
+        const int e = tidB + j * kFusedThreads;
+        if (e <= lastElem) {
+            const int fl = e / NTOT, i = e - fl * NTOT;
+            const int ba = A.bits[i * kWave + fl];
+            const int sf = scale_factor_dev(ldexp(peak[j], os[j]), S.nScaleBits, ba);
+            // (sf is -1 for a band without bits when nScaleBits = 1: kept inside its byte, or it would overwrite the signal)
+            sInfo[e] = (unsigned)ba | (((unsigned)sf & 0xffu) << 8) | ((unsigned)os[j] << 16) | ((unsigned)sig[j] << 24);
+            bitAlloc[f0 * NTOT + e] = ba;                // [frame][stream][band]: the workgroup's triples are contiguous
+            scaleFactor[f0 * NTOT + e] = sf;
+        }
+    }
+    __syncthreads();
+
+    // ---- phase 2: a lane takes FOUR CONSECUTIVE lines, as in quantize_kernel
+    unsigned bands[4];
+#pragma unroll
+    for (int it = 0; it < 4; ++it) bands[it] = sBand[lane + it * kWave];
+    auto infos = [&](const unsigned int* sI, int it, unsigned (&info)[4]) {
+        // (the four band numbers are taken out of their word at every use: hoisted out of the unit loop as sixteen LDS
+        // offsets they cost registers, which is workgroups per CU)
+        unsigned b = bands[it];
+        asm volatile("" : "+v"(b));
+#pragma unroll
+        for (int u = 0; u < 4; ++u) info[u] = sI[(b >> (8 * u)) & 0xff];
+    };
+    auto code_of = [&](double x, unsigned info) -> OutT {   // codecThem.py:348-349
+        const int ba = (int)(info & 0xff);
+        return (OutT)(ba ? mantissa_dev(ldexp(x, (int)((info >> 16) & 0xff)), (int)((info >> 8) & 0xff), S.nScaleBits, ba) : 0);
+    };
+    const int nUnits = nValid * nstream;
+    for (int u0 = wave; u0 < nUnits; u0 += kFusedWaves * kFusedDepth) {
+        double x[kFusedDepth][4][4];
+#pragma unroll
+        for (int d = 0; d < kFusedDepth; ++d) {
+            const int unit = u0 + d * kFusedWaves;
+            if (unit < nUnits) {
+                const int fl = unit / nstream, strm = unit % nstream;
+                const unsigned int* sI = sInfo + fl * NTOT + strm * nb;
+                const double* X = lines + (f0 + fl) * nsig * M;
+#pragma unroll
+                for (int it = 0; it < 4; ++it) {
+                    const int k = 4 * lane + it * 4 * kWave;
+                    unsigned info[4];
+                    infos(sI, it, info);
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) x[d][it][u] = 0.0;
+                    const bool anyBits = ((info[0] | info[1] | info[2] | info[3]) & 0xff) != 0;   // lines of bands without bits are not read
+                    const bool oneSignal = ((info[0] ^ info[3]) >> 24) == 0 && ((info[1] ^ info[2]) >> 24) == 0 && ((info[0] ^ info[1]) >> 24) == 0;
+                    if (anyBits) {
+                        if (oneSignal) {
+                            const double* src = X + (int64_t)(info[0] >> 24) * M + k;
+                            const double2 p = *reinterpret_cast<const double2*>(src), q = *reinterpret_cast<const double2*>(src + 2);
+                            x[d][it][0] = p.x; x[d][it][1] = p.y; x[d][it][2] = q.x; x[d][it][3] = q.y;
+                        } else {
+#pragma unroll
+                            for (int u = 0; u < 4; ++u) x[d][it][u] = X[(int64_t)(info[u] >> 24) * M + k + u];
+                        }
+                    }
+                }
+            }
+        }
+        // the info words are read from LDS again below, not carried in registers next to the lines in flight
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int d = 0; d < kFusedDepth; ++d) {
+            const int unit = u0 + d * kFusedWaves;
+            if (unit < nUnits) {
+                const int fl = unit / nstream, strm = unit % nstream;
+                const unsigned int* sI = sInfo + fl * NTOT + strm * nb;
+                OutT* out = mantissa + ((f0 + fl) * nstream + strm) * M;
+#pragma unroll
+                for (int it = 0; it < 4; ++it) {
+                    const int k = 4 * lane + it * 4 * kWave;
+                    unsigned info[4];
+                    infos(sI, it, info);
+                    OutT c[4];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) c[u] = code_of(x[d][it][u], info[u]);
+                    if (sizeof(OutT) == 2) {
+                        uint2 w;
+                        w.x = (unsigned)(unsigned short)c[0] | ((unsigned)(unsigned short)c[1] << 16);
+                        w.y = (unsigned)(unsigned short)c[2] | ((unsigned)(unsigned short)c[3] << 16);
+                        *reinterpret_cast<uint2*>(out + k) = w;
+                    } else {
+                        *reinterpret_cast<int4*>(out + k) = make_int4((int)c[0], (int)c[1], (int)c[2], (int)c[3]);
+                    }
+                }
+            }
+        }
+    }
+}
+
 }  // namespace
 
 size_t alloc_workspace_bytes(const DevShape& S, int64_t nFrames, int joint) {
@@ -332,7 +540,8 @@ size_t alloc_workspace_bytes(const DevShape& S, int64_t nFrames, int joint) {
 hipError_t launch_alloc_quant(const DevShape& S, int64_t nFrames, int joint, const double* lines, const int* oscale,
                               const double* smr, const int* resIn, int* msSwitch, int* bitAlloc, int* scaleFactor,
                               void* mantissa, int mantFmt, int* resOut, double* bandPeakWs, bool peaksReady, bool msReady,
-                              hipEvent_t evStats, hipEvent_t evAlloc /* recorded after band_stats / after bitalloc; null: not */,
+                              hipEvent_t evStats, hipEvent_t evAlloc /* recorded after band_stats / after bitalloc (in front of the fused
+                              long-block kernel); null: not */,
                               hipStream_t st) {
     if (nFrames <= 0) return hipSuccess;
     const int nTot = (joint ? 2 : 1) * S.nBands;
@@ -346,31 +555,38 @@ hipError_t launch_alloc_quant(const DevShape& S, int64_t nFrames, int joint, con
         if (e != hipSuccess) return e;
     }
     if (evStats) (void)hipEventRecord(evStats, st);
+    const int vecOk = !((reinterpret_cast<uintptr_t>(lines) | reinterpret_cast<uintptr_t>(mantissa)) & 15);
+    if (S.halfN == 1024 && S.nBands == 25 && vecOk) {
+        // the long block: one kernel for both.  evAlloc goes in front of it, so that a timed call reports no kernel time for the
+        // bit allocation and the fused kernel's time in the quantiser's slot
+        if (evAlloc) (void)hipEventRecord(evAlloc, st);
+        const dim3 fgrid((unsigned)((nFrames + kWave - 1) / kWave));
+#define MRC_F_LAUNCH(NT, TY)                                                                                         \
+    hipLaunchKernelGGL((alloc_quant_long_kernel<NT, TY>), fgrid, dim3(kFusedThreads), fused_lds_bytes(NT), st, S,    \
+                       nFrames, lines, oscale, smr, bandPeakWs, msSwitch, resIn, bitAlloc, scaleFactor, (TY*)mantissa, resOut)
+        if (mantFmt == MRC_MANTISSA_I16) { if (joint) MRC_F_LAUNCH(50, unsigned short); else MRC_F_LAUNCH(25, unsigned short); }
+        else { if (joint) MRC_F_LAUNCH(50, int); else MRC_F_LAUNCH(25, int); }
+#undef MRC_F_LAUNCH
+        return hipGetLastError();
+    }
     // frames per wave.  Spreading a launch over more, emptier waves (fpw = 8 .. 32) was tried to hide the latency of the
     // loop's dependent LDS reads: 2-3x SLOWER (mono 0.16 -> 0.30 ms, joint 0.52 -> 1.51 ms per 131 072 / 65 536 frames) --
     // the loop is bound by instruction issue, not by latency, so full waves it is.
     const int fpw = kWave;
     const size_t lds = alloc_lds_bytes(nTot, fpw);
     const dim3 bgrid((unsigned)((nFrames + fpw - 1) / fpw));
-    // the common band counts (25 bands of a long block at 44.1 / 48 kHz, one or two streams) as compile-time constants
-    // (9 / 18: the short and transition blocks)
+    // the band counts of the short and transition blocks (9 bands, one or two streams) as compile-time constants; a long
+    // block that comes here (another sample rate's band count, planes that are not 16-byte aligned) takes the generic form
     if (nTot == 9) hipLaunchKernelGGL(bitalloc_kernel<9>, bgrid, dim3(kWave), lds, st, S, joint, nFrames, fpw, smr, msSwitch, resIn, bitAlloc, resOut);
     else if (nTot == 18) hipLaunchKernelGGL(bitalloc_kernel<18>, bgrid, dim3(kWave), lds, st, S, joint, nFrames, fpw, smr, msSwitch, resIn, bitAlloc, resOut);
-    else if (nTot == 25) hipLaunchKernelGGL(bitalloc_kernel<25>, bgrid, dim3(kWave), lds, st, S, joint, nFrames, fpw, smr, msSwitch, resIn, bitAlloc, resOut);
-    else if (nTot == 50) hipLaunchKernelGGL(bitalloc_kernel<50>, bgrid, dim3(kWave), lds, st, S, joint, nFrames, fpw, smr, msSwitch, resIn, bitAlloc, resOut);
     else hipLaunchKernelGGL(bitalloc_kernel<0>, bgrid, dim3(kWave), lds, st, S, joint, nFrames, fpw, smr, msSwitch, resIn, bitAlloc, resOut);
     if (evAlloc) (void)hipEventRecord(evAlloc, st);
-    const int vecOk = !((reinterpret_cast<uintptr_t>(lines) | reinterpret_cast<uintptr_t>(mantissa)) & 15);
     const dim3 qgrid((unsigned)(nFrames * (joint ? 2 : 1)));
-    const int longj = (S.halfN == 1024 && vecOk) ? (joint ? 1 : 0) : -1;
-#define MRC_Q_LAUNCH(TY, LJ)                                                                                         \
-    hipLaunchKernelGGL((quantize_kernel<TY, LJ>), qgrid, dim3(kWave), 0, st, S, joint, lines, oscale, bandPeakWs,    \
-                       msSwitch, bitAlloc, scaleFactor, (TY*)mantissa, vecOk)
-#define MRC_Q_PICK(TY) do { if (longj == 0) MRC_Q_LAUNCH(TY, 0); else if (longj == 1) MRC_Q_LAUNCH(TY, 1);            \
-                            else MRC_Q_LAUNCH(TY, -1); } while (0)
-    if (mantFmt == MRC_MANTISSA_I16) MRC_Q_PICK(unsigned short);
-    else MRC_Q_PICK(int);
-#undef MRC_Q_PICK
+#define MRC_Q_LAUNCH(TY)                                                                                             \
+    hipLaunchKernelGGL((quantize_kernel<TY>), qgrid, dim3(kWave), 0, st, S, joint, lines, oscale, bandPeakWs, msSwitch, \
+                       bitAlloc, scaleFactor, (TY*)mantissa, vecOk)
+    if (mantFmt == MRC_MANTISSA_I16) MRC_Q_LAUNCH(unsigned short);
+    else MRC_Q_LAUNCH(int);
 #undef MRC_Q_LAUNCH
     return hipGetLastError();
 }
