@@ -806,13 +806,41 @@ int mrc_pac_store_info(mrc_pac_store* s, int64_t* n_files, int32_t* n_channels /
  * (the item is named).  window == 0 or n_items == 0: MRC_OK, nothing written.  The call enqueues on `stream` (NULL: the
  * handle's) and synchronises it before it returns, because the parser's error word comes back.  A call is cut into slabs
  * of whole items (MRC_OPT_STORE_SLAB_SAMPLES); the workspace is the handle's, sized by the slab and reused.
- * mrc_pac_store_stats, for the store's last mrc_pac_store_decode_window: stats = chunks parsed, decode_kernel launches,
+ * mrc_pac_store_stats, for the store's last mrc_pac_store_decode_window(_reduced): stats = chunks parsed, decode_kernel launches,
  * slabs, bytes of plan uploaded (no file bytes among them); ms = device time of the plan upload, the unpack kernel, the
  * synthesis (zeroing the planes + decode_kernel launches) and window_out_kernel, summed over the slabs. */
 int mrc_pac_store_decode_window(mrc_pac_store* s, int64_t n_items, const int64_t* file /*[n_items]*/,
                                 const int64_t* start /*[n_items]*/, int64_t window, int n_channels_out, int format,
                                 void* out /* DEVICE [n_items][n_channels_out][window] */, void* stream);
 int mrc_pac_store_stats(mrc_pac_store* s, int64_t* stats /*[4]*/, double* ms /*[4]*/);
+/* mrc_pac_store_decode_window_reduced: mrc_pac_store_decode_window at 1 / rate_divisor of the files' sample rate, straight
+ * from the MDCT lines: of every block the first 1 / D of the lines go through an inverse transform D times shorter, shape
+ * (a, b) / D with the codec's own transition window (KBD, alpha 4) at those lengths, so the synthesis does 1 / D of the work
+ * and the planes and the output take 1 / D of the bytes.  The result is the decoded signal band-limited to the new Nyquist
+ * frequency by a cut on MDCT lines -- no resampling filter runs; content right next to the cut-off is attenuated and aliased
+ * within a few lines of it, as such a cut does -- and it is NOT scaled.
+ * rate_divisor D is 1, 2 or 4.  D = 1 is mrc_pac_store_decode_window exactly (the same kernels, the same bits).  Anything
+ * else, or a D for which one of the handle's four block shapes (L,L), (L,S), (S,S), (S,L) has no reduced synthesis shape --
+ * a / D and b / D whole and positive, their sum and difference divisible by 4, (a + b) / (4 D) and (a + b) / (2 D) products of
+ * 2s and 3s -- is MRC_ERR_INVALID naming D and the shape, before any device work.
+ * start and window count REDUCED samples.  Reduced sample m of a file is the band-limited signal at time D m + (D - 1) / 2
+ * in the coordinates of mrc_decode_pac_pcm16's output: it lies (D - 1) / 2 full-rate samples AFTER full-rate sample D m
+ * (half a sample at D = 2, one and a half at D = 4).  The MDCT's first n_mdct_lines / D samples are dropped as the first
+ * n_mdct_lines are at full rate; a file has n_samples / D reduced samples (exact: every block length is a multiple of
+ * n_short, which D divides), and samples outside [0, n_samples / D) are exactly +0.0 / 0.  Block i of a file is parsed iff
+ * block_start[i] / D < start + window + n_mdct_lines / D and (block_start[i] + a_i + b_i) / D > start + n_mdct_lines / D; the
+ * whole chunk of such a block is parsed (its bits are sequential).  MRC_WINDOW_F64 is the overlap-added reduced plane,
+ * MRC_WINDOW_F32 that value converted once, MRC_WINDOW_PCM16 the 16-bit code of it (pcmfile.py:163-172).  Everything else --
+ * the channel map, the refusals, damage inside and outside a window, the independence of item order and slab size, slabs by
+ * MRC_OPT_STORE_SLAB_SAMPLES (counting reduced samples), the stream, mrc_pac_store_stats -- is mrc_pac_store_decode_window's. */
+int mrc_pac_store_decode_window_reduced(mrc_pac_store* s, int rate_divisor, int64_t n_items, const int64_t* file /*[n_items]*/,
+                                        const int64_t* start /*[n_items]*/, int64_t window, int n_channels_out, int format,
+                                        void* out /* DEVICE [n_items][n_channels_out][window] */, void* stream);
+/* mrc_synthesis_shape: the rule above for one block shape (a, b) and divisor, on the host alone (no handle, no device):
+ * MRC_OK if blocks of shape (a, b) have a synthesis shape (a, b) / rate_divisor, else MRC_ERR_INVALID with the reason, the
+ * divisor and the shape in mrc_last_error(NULL).  rate_divisor is any positive number here: 1 asks whether (a, b) itself
+ * has an inverse transform. */
+int mrc_synthesis_shape(int a, int b, int rate_divisor);
 
 /* Per-stage device time of the most recent timed call when timing is enabled (hipEvents on the launch stream; the call
  * then synchronises).  Timed: mrc_dev_encode / mrc_dev_encode_ex and mrc_encode_mono / mrc_encode_joint (the _blocks

@@ -200,6 +200,9 @@ def _load():
         "mrc_pac_store_info": (C.c_int, [C.c_void_p, _i64p, _i32p, _i64p, _i64p, _i64p]),
         "mrc_pac_store_decode_window": (C.c_int, [C.c_void_p, C.c_int64, _i64p, _i64p, C.c_int64, C.c_int, C.c_int, C.c_void_p,
                                                   C.c_void_p]),
+        "mrc_pac_store_decode_window_reduced": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, _i64p, _i64p, C.c_int64, C.c_int,
+                                                          C.c_int, C.c_void_p, C.c_void_p]),
+        "mrc_synthesis_shape": (C.c_int, [C.c_int, C.c_int, C.c_int]),
         "mrc_pac_store_stats": (C.c_int, [C.c_void_p, _i64p, _f64p]),
     }
     for name, (res, args) in sig.items():

@@ -22,6 +22,9 @@ reference's loop; everything after it is written, header sample count = what was
 An excerpt:  python -m mrcaudiocodec_amd.cli -d in.pac out.wav --start S --samples N  decodes N samples from sample S of that
 output on through a one-file resident store (mrc_pac_store_decode_window): only the blocks the excerpt overlaps are parsed
 and synthesised.  --start defaults to 0, --samples to the rest of the file; what lies outside the file is silence.
+At half or quarter rate:  python -m mrcaudiocodec_amd.cli -d in.pac out.wav --rate-divisor 2  (or 4) decodes through the same
+store straight from the MDCT lines (mrc_pac_store_decode_window_reduced): the WAV's header carries sample_rate // D, and
+--start / --samples then count samples at that rate.  Refused when D does not divide the file's sample rate.
 
 Quality (mrc_pac_nmr): --nmr on an encode prints, per file written (every rung of a ladder), one JSON line with the
 noise-to-mask ratio of the file against the WAV, measured with the codec's own masking model: nmr_max_db (worst band),
@@ -388,13 +391,32 @@ def check_excerpt_args(start, samples, decode):
     return (0 if start is None else int(start)), (None if samples is None else int(samples))
 
 
-def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None):
+def check_rate_divisor_args(rate_divisor, decode):
+    """--rate-divisor as given (None: not given) -> the divisor (1 when not given).  It decodes at a fraction of the sample
+    rate: refused without -d, and anything but 1, 2 or 4 is refused."""
+    if rate_divisor is None:
+        return 1
+    if not decode:
+        raise ValueError("--rate-divisor decodes at a fraction of the sample rate: it needs -d")
+    if isinstance(rate_divisor, bool) or not isinstance(rate_divisor, (int, np.integer)) or int(rate_divisor) not in (1, 2, 4):
+        raise ValueError("--rate-divisor: %r is not 1, 2 or 4" % (rate_divisor,))
+    return int(rate_divisor)
+
+
+def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=1):
     """excerpt: None (the whole file, mrc_decode_pac_pcm16) or (start, samples): that many samples from sample `start` on
     (samples None: to the end of the file), decoded through a one-file PacStore -- only the blocks the excerpt overlaps are
-    parsed and synthesised; what lies outside the file is silence.  -> int16 [nCh][samples] as written."""
+    parsed and synthesised; what lies outside the file is silence.  rate_divisor 2 or 4: at that fraction of the sample rate,
+    through the store as well (excerpt None: the whole file); start and samples count samples at the reduced rate, which the
+    WAV's header carries.  -> int16 [nCh][samples] as written."""
     with open(pac_path, "rb") as fp:
         buf = fp.read()
     cfg, _, _, _ = pacfile.read_header(buf)
+    rate_divisor = check_rate_divisor_args(rate_divisor, True)
+    if cfg.sample_rate % rate_divisor:
+        raise ValueError("--rate-divisor %d does not divide the file's sample rate, %d Hz" % (rate_divisor, cfg.sample_rate))
+    if rate_divisor != 1 and excerpt is None:
+        excerpt = (0, None)
     h = Handle(sample_rate=cfg.sample_rate, n_mdct_lines=cfg.n_mdct_lines, n_scale_bits=cfg.n_scale_bits,
                n_mant_size_bits=cfg.n_mant_size_bits, device_id=device_id)
     try:
@@ -405,13 +427,13 @@ def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None):
             with PacStore(h, [buf]) as store:
                 start, samples = excerpt
                 if samples is None:
-                    samples = max(0, int(store.n_samples[0]) - start)
-                inter = np.ascontiguousarray(store.decode_window([0], [start], samples)[0].cpu().numpy().T)
+                    samples = max(0, int(store.n_samples_at(rate_divisor)[0]) - start)
+                inter = np.ascontiguousarray(store.decode_window([0], [start], samples, rate_divisor=rate_divisor)[0].cpu().numpy().T)
     finally:
         h.close()
     data = inter.astype("<i2", copy=False)
     with open(wav_path, "wb") as fp:
-        fp.write(wav_header(inter.shape[1], data.nbytes, cfg.sample_rate))
+        fp.write(wav_header(inter.shape[1], data.nbytes, cfg.sample_rate // rate_divisor))
         fp.write(data.tobytes())
     return inter.T
 
@@ -525,10 +547,14 @@ def main(argv=None):
                     help="with -d: decode an excerpt that starts at sample S of the decoded file (default 0)")
     ap.add_argument("--samples", type=int, default=None, metavar="N",
                     help="with -d: decode an excerpt of N samples (default: to the end of the file)")
+    ap.add_argument("--rate-divisor", type=int, default=None, metavar="D",
+                    help="with -d: decode at 1/D of the sample rate (D = 2 or 4) straight from the MDCT lines; the WAV says "
+                         "sample_rate // D, and --start / --samples count samples at that rate")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(_join_vbr_grid(sys.argv[1:] if argv is None else argv))
     try:
         excerpt = check_excerpt_args(a.start, a.samples, a.decode)
+        rate_divisor = check_rate_divisor_args(a.rate_divisor, a.decode)
     except ValueError as e:
         ap.error(str(e))
     if a.vbr_bytes is not None or a.vbr_bits_per_sample is not None or a.vbr_grid is not None:
@@ -574,7 +600,10 @@ def main(argv=None):
         _print_nmr(ap, a, paths, None if rates is None else [v for (_, v) in rates])
         return
     if a.decode:
-        pcm = decode_pac_file(a.src, a.dst, a.device, excerpt)
+        try:
+            pcm = decode_pac_file(a.src, a.dst, a.device, excerpt, rate_divisor)
+        except ValueError as e:
+            ap.error(str(e))
         print("%s: %d channels x %d samples" % (a.dst, pcm.shape[0], pcm.shape[1]))
         return
     cert = {} if a.certify else None

@@ -46,6 +46,31 @@ int get_shape(mrc_handle* h, int a, int b, const HostShape** out) {
     return MRC_OK;
 }
 
+std::string synth_shape_refusal(int a, int b, int D) {
+    std::string why;
+    if (D <= 0 || a % D || b % D) why = "its lengths are no multiples of the divisor";
+    else if (synth_shape_rule(a / D, b / D, &why)) return std::string();
+    char msg[320];
+    std::snprintf(msg, sizeof msg, "rate_divisor %d: block shape (%d,%d) has no reduced synthesis shape: %s", D, a, b, why.c_str());
+    return msg;
+}
+
+int get_synth_shape(mrc_handle* h, int a, int b, int D, const HostShape** out) {
+    MRC_HIP(h, hipSetDevice(h->device));
+    const auto key = std::make_tuple(a, b, D);
+    auto it = h->synthShapes.find(key);
+    if (it == h->synthShapes.end()) {
+        const std::string refusal = synth_shape_refusal(a, b, D);
+        if (!refusal.empty()) return fail(h, MRC_ERR_INVALID, refusal);
+        HostShape hs;
+        std::string err;
+        if (!build_synth_shape(a / D, b / D, &hs, &err)) return fail(h, MRC_ERR_INVALID, err);
+        it = h->synthShapes.emplace(key, std::move(hs)).first;      // (its LDS: less than the full shape's, checked by get_shape)
+    }
+    *out = &it->second;
+    return MRC_OK;
+}
+
 }  // namespace mrc
 
 extern "C" {

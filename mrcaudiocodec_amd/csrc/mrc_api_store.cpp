@@ -19,6 +19,13 @@
 //                   in its file: joint for all but the last block of a stereo file of more than one block.
 //   window_out_kernel  planes -> out [item][channel][t] in the caller's format (mrc_kernels_store.hip).
 // The plan entries point into the resident bytes; what is uploaded per slab is the plan alone.
+//
+// decode_window_reduced, rate divisor D = 2 or 4 (D = 1: the call above): the same plan with every length divided by D --
+// L / D, p_i / D, (a_i + b_i) / D, planes of window + 4 L / D, start and window in reduced samples -- exact, because every
+// block length and position is a multiple of n_short and D divides n_short (else the shapes have no reduced form and the
+// call is refused).  The parser is untouched (a chunk's bits are sequential: every mantissa is parsed); decode_reduced_kernel
+// dequantises the first 1 / D of a block's lines and runs the inverse transform of the shape (a, b) / D.  One function,
+// decode_windows, holds the arithmetic for every D.
 #include "mrc_handle.hpp"
 
 #include <algorithm>
@@ -30,6 +37,7 @@ using namespace mrc;
 namespace {
 
 const char* const kWin = "mrc_pac_store_decode_window";
+const char* const kWinReduced = "mrc_pac_store_decode_window_reduced";
 
 int store_alive(mrc_pac_store* s, const char* fn) {
     if (!s) return fail(nullptr, MRC_ERR_INVALID, std::string(fn) + ": null store");
@@ -39,15 +47,18 @@ int store_alive(mrc_pac_store* s, const char* fn) {
 
 struct Need { int64_t item, file, block; };          // item: index in the slab
 
-// the blocks of file f that a window of `window` samples at `start` overlaps, appended to out as (item, f, block)
-void needed_blocks(const mrc_pac_store& s, const mrc_config& cfg, int64_t item, int64_t f, int64_t start, int64_t window,
+// the blocks of file f that a window of `window` samples at `start` overlaps, appended to out as (item, f, block); start
+// and window count samples at 1 / D of the file's rate, where block i covers [p_i / D, (p_i + a_i + b_i) / D)
+void needed_blocks(const mrc_pac_store& s, const mrc_config& cfg, int D, int64_t item, int64_t f, int64_t start, int64_t window,
                    std::vector<Need>* out) {
-    const int64_t L = cfg.n_mdct_lines, nb = s.index.nBlocks(f);
+    const int64_t L = cfg.n_mdct_lines / D, nb = s.index.nBlocks(f);
     // no block reaches past the file's extent or before 0 (compared without forming start + window where start is extreme)
-    if (nb == 0 || start >= s.index.files[(size_t)f].extent - L || (start < 0 && -(start + 1) >= window + L - 1)) return;
+    if (nb == 0 || start >= (s.index.files[(size_t)f].extent - cfg.n_mdct_lines) / D ||
+        (start < 0 && -(start + 1) >= window + L - 1))
+        return;
     const int64_t* p = s.blockStart.data() + s.firstBlock[(size_t)f];
-    const int64_t lo = start + L, hi = start + window + L;
-    const int64_t first = std::upper_bound(p, p + nb, lo - 2 * L) - p, end = std::lower_bound(p, p + nb, hi) - p;
+    const int64_t lo = (start + L) * D, hi = (start + window + L) * D;      // in the file's own samples: p_i is a multiple of D
+    const int64_t first = std::upper_bound(p, p + nb, lo - 2 * L * D) - p, end = std::lower_bound(p, p + nb, hi) - p;
     for (int64_t i = first; i < end; ++i) {
         int a, b;
         shape_ab(cfg, s.index.shape(f, i), &a, &b);
@@ -119,14 +130,26 @@ int mrc_pac_store_info(mrc_pac_store* s, int64_t* n_files, int32_t* n_channels, 
     return MRC_OK;
 }
 
-int mrc_pac_store_decode_window(mrc_pac_store* s, int64_t n_items, const int64_t* file, const int64_t* start, int64_t window,
-                                int n_channels_out, int format, void* out, void* stream) {
-    MRC_TRY(store_alive(s, kWin));
+}  // extern "C"
+
+namespace {
+
+// both decode_window calls: fn the entry point's name, D the rate divisor (1: full rate, decode_kernel)
+int decode_windows(mrc_pac_store* s, const char* fn, int D, int64_t n_items, const int64_t* file, const int64_t* start,
+                   int64_t window, int n_channels_out, int format, void* out, void* stream) {
+    MRC_TRY(store_alive(s, fn));
     mrc_handle* h = s->h;
     const mrc_config& cfg = h->cfg;
-    const int64_t nFiles = (int64_t)s->index.files.size(), L = cfg.n_mdct_lines;
-    const std::string w = kWin;
+    const std::string w = fn;
     for (int i = 0; i < 4; ++i) { s->stats[i] = 0; s->ms[i] = 0.0; }
+    if (D != 1 && D != 2 && D != 4) return fail(h, MRC_ERR_INVALID, w + ": rate_divisor " + std::to_string(D) + " is not 1, 2 or 4");
+    for (int sh = 0; D > 1 && sh < 4; ++sh) {
+        int a, b;
+        shape_ab(cfg, sh, &a, &b);
+        const std::string refusal = synth_shape_refusal(a, b, D);
+        if (!refusal.empty()) return fail(h, MRC_ERR_INVALID, w + ": " + refusal);
+    }
+    const int64_t nFiles = (int64_t)s->index.files.size(), L = cfg.n_mdct_lines / D;      // L: the margin unit, reduced samples
     if (n_items < 0) return fail(h, MRC_ERR_INVALID, w + ": n_items < 0");
     if (window < 0 || window > ((int64_t)1 << 40)) return fail(h, MRC_ERR_INVALID, w + ": window must lie in [0, 2^40]");
     if (n_channels_out != 1 && n_channels_out != 2) return fail(h, MRC_ERR_INVALID, w + ": n_channels_out must be 1 or 2");
@@ -174,10 +197,10 @@ int mrc_pac_store_decode_window(mrc_pac_store* s, int64_t n_items, const int64_t
         for (int64_t k = 0; k < nSlab; ++k) {
             const int64_t f = file[first + k];
             const size_t before = needs.size();
-            needed_blocks(*s, cfg, k, f, start[first + k], window, &needs);
+            needed_blocks(*s, cfg, D, k, f, start[first + k], window, &needs);
             if (needs.size() == before) continue;            // all zeros: its plane does not exist
             const PacFilePlan& fi = s->index.files[(size_t)f];
-            items[(size_t)k] = WindowItem{planeDoubles, start[first + k], std::max<int64_t>(0, fi.total - L), fi.nch, 0};
+            items[(size_t)k] = WindowItem{planeDoubles, start[first + k], std::max<int64_t>(0, fi.total - cfg.n_mdct_lines) / D, fi.nch, 0};
             planeDoubles += fi.nch * planeLen;
         }
         if (needs.empty()) {                                 // nothing to decode: zeros, no launch
@@ -191,7 +214,10 @@ int mrc_pac_store_decode_window(mrc_pac_store* s, int64_t n_items, const int64_t
             if (n.block < s->index.nJoint(n.file)) { pl.nSlots[sh * 2] += 1; pl.nCat[sh * 4] += 1; pl.nCat[sh * 4 + 1] += 1; }
             else { pl.nSlots[sh * 2 + 1] += nch; pl.nCat[sh * 4 + 2] += nch; }
         }
-        MRC_TRY(pac_plan_layout(h, kWin, &pl));
+        MRC_TRY(pac_plan_layout(h, fn, &pl));
+        const HostShape* reduced[4] = {};
+        for (int sh = 0; D > 1 && sh < 4; ++sh)
+            if (pl.hs[sh]) MRC_TRY(get_synth_shape(h, pl.hs[sh]->dev.a, pl.hs[sh]->dev.b, D, &reduced[sh]));
         int64_t nChunks = 0;
         for (int64_t k = 0; k < 2 * kUnpackGroups; ++k) nChunks += pl.nCat[k];
 
@@ -219,7 +245,7 @@ int mrc_pac_store_decode_window(mrc_pac_store* s, int64_t n_items, const int64_t
             const int64_t c0 = fi.firstChunk + n.block * fi.nch;
             const int sh = s->index.chunkShape[(size_t)c0];
             // the block's place in the item's plane: its position in the file's padded plane, the window's start at 2 L
-            const int64_t at = it.plane + 2 * L + s->blockStart[(size_t)(s->firstBlock[(size_t)n.file] + n.block)] - (it.start + L);
+            const int64_t at = it.plane + 2 * L + s->blockStart[(size_t)(s->firstBlock[(size_t)n.file] + n.block)] / D - (it.start + L);
             if (n.block < s->index.nJoint(n.file)) {
                 const int g = sh * 2, slot = (int)slotNext[g]++;
                 for (int ch = 0; ch < 2; ++ch) {
@@ -256,7 +282,7 @@ int mrc_pac_store_decode_window(mrc_pac_store* s, int64_t n_items, const int64_t
             const int64_t c = d.pinErr->firstBad;
             const int64_t f = c < nChunks ? planFile[(size_t)c] : 0;
             const int64_t at = c < nChunks ? plan[c].off - s->fileBase[(size_t)f] : 0;
-            std::snprintf(msg, sizeof msg, "%s: file %lld: chunk at byte %lld: %s", kWin, (long long)f, (long long)at,
+            std::snprintf(msg, sizeof msg, "%s: file %lld: chunk at byte %lld: %s", fn, (long long)f, (long long)at,
                           unpack_status_text(d.pinErr->flag));
             return fail(h, MRC_ERR_INVALID, msg);
         }
@@ -266,9 +292,14 @@ int mrc_pac_store_decode_window(mrc_pac_store* s, int64_t n_items, const int64_t
         for (int g = 0; g < kUnpackGroups; ++g) {
             if (!pl.nSlots[g]) continue;
             const UnpackGroupDev& G = gd[g];
-            MRC_HIP(h, launch_decode(pl.hs[g / 2]->dev, pl.nSlots[g], G.joint ? 2 : 1, G.oscale, G.joint ? G.ms : nullptr, G.sf,
-                                     G.ba, G.mant, (const int64_t*)(din + oOffs) + pl.slotBase[g], x,
-                                     G.joint ? x + planeLen : nullptr, st));
+            const int64_t* offsDev = (const int64_t*)(din + oOffs) + pl.slotBase[g];
+            if (D == 1)
+                MRC_HIP(h, launch_decode(pl.hs[g / 2]->dev, pl.nSlots[g], G.joint ? 2 : 1, G.oscale, G.joint ? G.ms : nullptr, G.sf,
+                                         G.ba, G.mant, offsDev, x, G.joint ? x + planeLen : nullptr, st));
+            else
+                MRC_HIP(h, launch_decode_reduced(pl.hs[g / 2]->dev, reduced[g / 2]->dev, pl.nSlots[g], G.joint ? 2 : 1, G.oscale,
+                                                 G.joint ? G.ms : nullptr, G.sf, G.ba, G.mant, offsDev, x,
+                                                 G.joint ? x + planeLen : nullptr, st));
             s->stats[1] += 1;
         }
         MRC_HIP(h, hipEventRecord(b.ev[4], st));
@@ -285,6 +316,26 @@ int mrc_pac_store_decode_window(mrc_pac_store* s, int64_t n_items, const int64_t
     }
     MRC_HIP(h, hipStreamSynchronize(st));
     return MRC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mrc_pac_store_decode_window(mrc_pac_store* s, int64_t n_items, const int64_t* file, const int64_t* start, int64_t window,
+                                int n_channels_out, int format, void* out, void* stream) {
+    return decode_windows(s, kWin, 1, n_items, file, start, window, n_channels_out, format, out, stream);
+}
+
+int mrc_pac_store_decode_window_reduced(mrc_pac_store* s, int rate_divisor, int64_t n_items, const int64_t* file,
+                                        const int64_t* start, int64_t window, int n_channels_out, int format, void* out,
+                                        void* stream) {
+    return decode_windows(s, kWinReduced, rate_divisor, n_items, file, start, window, n_channels_out, format, out, stream);
+}
+
+int mrc_synthesis_shape(int a, int b, int rate_divisor) {
+    const std::string refusal = synth_shape_refusal(a, b, rate_divisor);
+    return refusal.empty() ? MRC_OK : fail(nullptr, MRC_ERR_INVALID, "mrc_synthesis_shape: " + refusal);
 }
 
 int mrc_pac_store_stats(mrc_pac_store* s, int64_t* stats, double* ms) {

@@ -11,6 +11,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <tuple>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -358,6 +359,7 @@ struct mrc_handle {
     int device = 0;
     mrc::Stream stream;
     std::map<std::pair<int, int>, mrc::HostShape> shapes;
+    std::map<std::tuple<int, int, int>, mrc::HostShape> synthShapes;   // (a, b, D): synthesis-only shape (a / D, b / D), get_synth_shape
     std::string error;
     mrc::Workspace ws;               // workspace of mrc_dev_encode* (calls on one handle are serialised)
     mrc::Lane lanes[mrc::kLanes];    // mrc_encode_stream_pcm16: chunk buffers ...
@@ -439,6 +441,10 @@ struct DrainGuard {
 // every entry point that launches comes through here first: the launches, the tables and the caller's pointers all
 // belong to the handle's device, whatever the calling thread's current device was
 int get_shape(mrc_handle* h, int a, int b, const HostShape** out);
+// the synthesis-only shape (a / D, b / D) of the reduced-rate store decode (build_synth_shape), cached per (a, b, D);
+// synth_shape_refusal: why there is none, D and the shape named -- empty if there is one (host only)
+std::string synth_shape_refusal(int a, int b, int D);
+int get_synth_shape(mrc_handle* h, int a, int b, int D, const HostShape** out);
 inline bool all_bands_non_empty(const HostShape& hs) {
     for (int n : hs.bandN) if (n <= 0) return false;
     return true;

@@ -84,6 +84,11 @@ std::string& create_error();
 void ms_plan(const std::vector<int>& bandLo, const std::vector<int>& bandN, std::vector<int>* plan, int* nLeaves,
              int* nInternal);
 bool build_shape(const mrc_config& cfg, int a, int b, HostShape* out, std::string* err);
+// Synthesis only: the fields decode_kernel reads of a shape (a, b, N, halfN, Q, shift, radQ / nRadQ / wQ, pre / post, win),
+// by build_shape's own expressions, and nothing else -- no band table, no masking model, so no lower limit on the length.
+// The rule is the transform's: a, b > 0, a + b and b - a divisible by 4, N/4 and N/2 products of 2s and 3s.
+bool synth_shape_rule(int a, int b, std::string* err);                              // host only
+bool build_synth_shape(int a, int b, HostShape* out, std::string* err);
 // the bit budgets of a block of shape (a, b) with nb bands at target_bits_per_sample tbps (codecThem.py:299-306 mono,
 // 381-388 joint before the reservoir is added): the one copy of the float arithmetic the shape tables and the rate ladder share
 void shape_budgets(const mrc_config& cfg, double tbps, int a, int b, int nb, double* budgetMono, double* budgetJointPre);
@@ -136,6 +141,12 @@ hipError_t launch_decode(const DevShape& S, int64_t nBlocks, int nStreams, const
                          const int* scaleFactor, const int* bitAlloc, const int* mantissa, const int64_t* outOffset,
                          double* outL, double* outR, hipStream_t st);
 hipError_t launch_pcm16(int64_t n, const double* x, short* out, hipStream_t st);
+// launch_decode at a reduced sample rate: the parsed arrays, bands and line stride are those of the block's FULL shape F,
+// of which the first R.halfN lines are dequantised; the inverse transform, window and overlap-add are R's (a synthesis
+// shape, build_synth_shape, of F's (a, b) / D), and outOffset counts reduced samples
+hipError_t launch_decode_reduced(const DevShape& F, const DevShape& R, int64_t nBlocks, int nStreams, const int* oscale,
+                                 const int* msSwitch, const int* scaleFactor, const int* bitAlloc, const int* mantissa,
+                                 const int64_t* outOffset, double* outL, double* outR, hipStream_t st);
 // mrc_kernels_pack.hip -- `.pac` chunk packing on the device
 constexpr int kPackLutSize = 65;     // the largest value in any Huffman table is 64
 constexpr int kPackRawTable = 15;    // codecThem.py:149
@@ -225,12 +236,14 @@ hipError_t launch_nmr_file(int64_t nFiles, const long long* entryStart, const in
 // mrc_kernels_store.hip -- windows of resident `.pac` files (mrc_pac_store_decode_window)
 struct WindowItem {                  // one item of a slab
     long long plane;                 // where its first decoded channel's plane starts in the slab's planes (doubles)
-    long long start;                 // the window's first sample, in the coordinates of mrc_decode_pac_pcm16's output
+    long long start;                 // the window's first sample, in the coordinates of mrc_decode_pac_pcm16's output (divided
+                                     // by the rate divisor: mrc_pac_store_decode_window_reduced)
     long long nSamples;              // the file's length in those coordinates; 0: the item needs no block, its plane is not read
     int nch, pad_;                   // decoded channels: planes at plane + c * (window + 4 L)
 };
 // out [nItems][nchOut][window] in `format` (MRC_WINDOW_*) <- planes[item.plane + c * (window + 4 L) + 2 L + t], zero where
-// start + t lies outside [0, nSamples); a one-channel item fills every output channel
+// start + t lies outside [0, nSamples); a one-channel item fills every output channel.  (L: the planes' margin unit --
+// n_mdct_lines, divided by the rate divisor where there is one.)
 hipError_t launch_window_out(int64_t nItems, const WindowItem* items /* device */, int64_t window, int nchOut, int format,
                              int L, const double* planes, void* out, hipStream_t st);
 // mrc_kernels_chain.hip -- chained stream encode: reservoir-free preparation per block, serial scan per stream

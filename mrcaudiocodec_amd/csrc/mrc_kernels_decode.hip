@@ -10,6 +10,8 @@
 //     an unfold) -> transition window (window.py:104-121) -> atomic add into the output stream at the block's
 //     offset.  Every output sample receives at most two contributions and a + b == b + a, so the result does not
 //     depend on the order in which blocks finish.
+//   decode_reduced_kernel   the same block at 1 / D of its sample rate: its first halfN / D lines through the inverse
+//     transform of the shape (a, b) / D (the resident store's reduced windows, mrc_api_store.cpp).
 //   pcm16_kernel    |x| -> 16-bit magnitude code (quantize.py:61-87) with the sign re-applied as 2's complement.
 //
 // The reference computes the IMDCT with an N-point complex inverse FFT; like the forward transform the results
@@ -20,16 +22,17 @@ namespace mrc {
 using namespace dev;
 namespace {
 
-__global__ __launch_bounds__(kThreads) void decode_kernel(DevShape S, int nStreams, const int* __restrict__ oscale,
-                                                          const int* __restrict__ msSwitch,
-                                                          const int* __restrict__ scaleFactor,
-                                                          const int* __restrict__ bitAlloc,
-                                                          const int* __restrict__ mantissa,
-                                                          const int64_t* __restrict__ outOffset,
-                                                          double* __restrict__ outL, double* __restrict__ outR) {
-    extern __shared__ double smem[];
+// One (block, output channel).  S: the shape whose transform, window and LDS layout are used; the parsed arrays are those
+// of a block of nb bands and lineStride lines per stream with the band table bandOfLine, of which the first S.halfN lines
+// are dequantised.  decode_kernel: all of them S's own.  decode_reduced_kernel: the block's full shape, S its reduced one.
+__device__ __forceinline__ void decode_block(const DevShape& S, const unsigned char* __restrict__ bandOfLine, int nb,
+                                             int lineStride, int nScaleBits, int nStreams, const int* __restrict__ oscale,
+                                             const int* __restrict__ msSwitch, const int* __restrict__ scaleFactor,
+                                             const int* __restrict__ bitAlloc, const int* __restrict__ mantissa,
+                                             const int64_t* __restrict__ outOffset, double* __restrict__ outL,
+                                             double* __restrict__ outR, double* smem) {
     const int tid = threadIdx.x;
-    const int N = S.N, M = S.halfN, Q = S.Q, nb = S.nBands;
+    const int N = S.N, M = S.halfN, Q = S.Q;
     const int64_t f = blockIdx.x / nStreams;
     const int ch = blockIdx.x % nStreams;
     double* v = smem;                                   // [M] lines, later the DCT-IV output; [M, N) unused
@@ -38,12 +41,12 @@ __global__ __launch_bounds__(kThreads) void decode_kernel(DevShape S, int nStrea
     const bool joint = nStreams == 2;
     const int* sf = scaleFactor + f * nStreams * nb;
     const int* ba = bitAlloc + f * nStreams * nb;
-    const int* mant = mantissa + f * nStreams * (int64_t)M;
+    const int* mant = mantissa + f * nStreams * (int64_t)lineStride;
     const int* os = oscale + f * (joint ? 4 : 1);
 
     // dequantise, undo the overall scale (codecThem.py:47-51, 92-109), rebuild L / R (ms_stereo.py:33-49)
     for (int k = tid; k < M; k += kThreads)
-        v[k] = decode_line(k, S.bandOfLine[k], ch, joint, nb, M, S.nScaleBits, os, joint ? msSwitch + f * nb : nullptr, sf,
+        v[k] = decode_line(k, bandOfLine[k], ch, joint, nb, lineStride, nScaleBits, os, joint ? msSwitch + f * nb : nullptr, sf,
                            ba, mant);
     __syncthreads();
     // DCT-IV of the lines through the N/4-point FFT (same pairing and twiddles as the forward kernel)
@@ -74,6 +77,38 @@ __global__ __launch_bounds__(kThreads) void decode_kernel(DevShape S, int nStrea
     }
 }
 
+__global__ __launch_bounds__(kThreads) void decode_kernel(DevShape S, int nStreams, const int* __restrict__ oscale,
+                                                          const int* __restrict__ msSwitch,
+                                                          const int* __restrict__ scaleFactor,
+                                                          const int* __restrict__ bitAlloc,
+                                                          const int* __restrict__ mantissa,
+                                                          const int64_t* __restrict__ outOffset,
+                                                          double* __restrict__ outL, double* __restrict__ outR) {
+    extern __shared__ double smem[];
+    decode_block(S, S.bandOfLine, S.nBands, S.halfN, S.nScaleBits, nStreams, oscale, msSwitch, scaleFactor, bitAlloc, mantissa,
+                 outOffset, outL, outR, smem);
+}
+
+// The block at 1 / D of its sample rate (the store's reduced windows): the first R.halfN = halfN / D of its lines through
+// the inverse transform of the shape R = (a, b) / D.  With n = D m + (D - 1) / 2 the phase (n + n0)(k + 1/2) / N of the
+// full block's line k at sample n is (m + n0')(k + 1/2) / N' of R's line k at sample m, and the inverse carries no factor
+// that depends on N: the result is the block's signal band-limited to the new Nyquist at those times, unscaled.  The bands,
+// the bit allocation and the dense mantissa planes (stride fullLines) stay the full shape's; a band that straddles the
+// cut is dequantised on its lines below it.
+__global__ __launch_bounds__(kThreads) void decode_reduced_kernel(DevShape R, const unsigned char* __restrict__ bandOfLine,
+                                                                  int nb, int fullLines, int nScaleBits, int nStreams,
+                                                                  const int* __restrict__ oscale,
+                                                                  const int* __restrict__ msSwitch,
+                                                                  const int* __restrict__ scaleFactor,
+                                                                  const int* __restrict__ bitAlloc,
+                                                                  const int* __restrict__ mantissa,
+                                                                  const int64_t* __restrict__ outOffset,
+                                                                  double* __restrict__ outL, double* __restrict__ outR) {
+    extern __shared__ double smem[];
+    decode_block(R, bandOfLine, nb, fullLines, nScaleBits, nStreams, oscale, msSwitch, scaleFactor, bitAlloc, mantissa, outOffset,
+                 outL, outR, smem);
+}
+
 // pcmfile.py:163-172
 __global__ void pcm16_kernel(int64_t n, const double* __restrict__ x, short* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -93,6 +128,18 @@ hipError_t launch_decode(const DevShape& S, int64_t nBlocks, int nStreams, const
     const size_t lds = mdct_generic_lds_bytes(S);          // (the same [2N] doubles as mdct_kernel)
     hipLaunchKernelGGL(decode_kernel, dim3((unsigned)(nBlocks * nStreams)), dim3(kThreads), lds, st, S, nStreams, oscale,
                        msSwitch, scaleFactor, bitAlloc, mantissa, outOffset, outL, outR);
+    return hipGetLastError();
+}
+
+hipError_t launch_decode_reduced(const DevShape& F, const DevShape& R, int64_t nBlocks, int nStreams, const int* oscale,
+                                 const int* msSwitch, const int* scaleFactor, const int* bitAlloc, const int* mantissa,
+                                 const int64_t* outOffset, double* outL, double* outR, hipStream_t st) {
+    if (nBlocks <= 0) return hipSuccess;
+    if (R.halfN <= 0 || R.halfN > F.halfN) return hipErrorInvalidValue;
+    const size_t lds = mdct_generic_lds_bytes(R);
+    hipLaunchKernelGGL(decode_reduced_kernel, dim3((unsigned)(nBlocks * nStreams)), dim3(kThreads), lds, st, R, F.bandOfLine,
+                       F.nBands, F.halfN, F.nScaleBits, nStreams, oscale, msSwitch, scaleFactor, bitAlloc, mantissa, outOffset,
+                       outL, outR);
     return hipGetLastError();
 }
 

@@ -100,6 +100,48 @@ std::vector<double2> unit_circle(int n, long double scale /* angle = -scale * t 
     return w;
 }
 
+// window.py:104-121 -- the transition window of a block (a, b): the rising half of the KBD window of length 2a, the falling
+// half of the one of length 2b
+std::vector<double> transition_window(int a, int b) {
+    std::vector<double> win((size_t)a + b);
+    std::vector<double> ka = kbd_table(2 * a), kb = (a == b) ? ka : kbd_table(2 * b);
+    for (int n = 0; n < a; ++n) win[n] = ka[n];
+    for (int i = 0; i < b; ++i) win[a + i] = kb[b + i];
+    return win;
+}
+
+// the DCT-IV's twiddles around the N/4-point FFT: pre[n] = exp(-i pi (4n+1)/(4M)), post[n] = exp(-i pi n/M), M = N/2
+void dct4_twiddles(int Q, int M, std::vector<double2>* pre, std::vector<double2>* post) {
+    pre->resize(Q);
+    post->resize(Q);
+    for (int n = 0; n < Q; ++n) {
+        long double ang = -kPiL * (4.0L * n + 1.0L) / (4.0L * M);
+        (*pre)[n] = make_double2((double)cosl(ang), (double)sinl(ang));
+        long double ang2 = -kPiL * (long double)n / (long double)M;
+        (*post)[n] = make_double2((double)cosl(ang2), (double)sinl(ang2));
+    }
+}
+
+// what the transform itself asks of a block shape, and the fields that follow from (a, b) alone
+bool transform_shape(int a, int b, DevShape* S, std::string* err) {
+    const int N = a + b;
+    if (a <= 0 || b <= 0 || N % 4 != 0 || (b - a) % 4 != 0) {
+        *err = "block shape (a,b) must be positive with a+b and b-a divisible by 4";
+        return false;
+    }
+    *S = DevShape{};
+    S->a = a; S->b = b; S->N = N; S->halfN = N / 2; S->Q = N / 4; S->H = N / 2;
+    S->shift = (b - a) / 4;
+    return true;
+}
+bool transform_radices(DevShape* S, std::string* err) {
+    if (!factor(S->Q, S->radQ, &S->nRadQ) || !factor(S->H, S->radH, &S->nRadH)) {
+        *err = "block length must factor into 2s and 3s";
+        return false;
+    }
+    return true;
+}
+
 }  // namespace
 
 // quantize.py:114-146 on the host (used for validation of configs only; the device has its own copy).
@@ -204,21 +246,12 @@ void shape_budgets(const mrc_config& cfg, double tbps, int a, int b, int nb, dou
 }
 
 bool build_shape(const mrc_config& cfg, int a, int b, HostShape* out, std::string* err) {
-    const int N = a + b;
-    if (a <= 0 || b <= 0 || N % 4 != 0 || (b - a) % 4 != 0) {
-        *err = "block shape (a,b) must be positive with a+b and b-a divisible by 4";
-        return false;
-    }
     DevShape& S = out->dev;
-    S = DevShape{};
-    S.a = a; S.b = b; S.N = N; S.halfN = N / 2; S.Q = N / 4; S.H = N / 2;
-    S.shift = (b - a) / 4;
+    if (!transform_shape(a, b, &S, err)) return false;
+    const int N = S.N;
     S.peakLast = N / 2 - 100;
     if (S.peakLast < 3) { *err = "block too short for the peak search (N/2-100 < 3)"; return false; }
-    if (!factor(S.Q, S.radQ, &S.nRadQ) || !factor(S.H, S.radH, &S.nRadH)) {
-        *err = "block length must factor into 2s and 3s";
-        return false;
-    }
+    if (!transform_radices(&S, err)) return false;
     S.nScaleBits = cfg.n_scale_bits;
     S.maxMantBits = (1 << cfg.n_mant_size_bits) > 16 ? 16 : (1 << cfg.n_mant_size_bits);   // codecThem.py:292-293
     S.twoOverN = 2.0 / N;
@@ -243,11 +276,8 @@ bool build_shape(const mrc_config& cfg, int a, int b, HostShape* out, std::strin
     S.blkswB = cfg.blksw_bits_b;
 
     // windows
-    std::vector<double> win(N), hann(N);
+    std::vector<double> win = transition_window(a, b), hann(N);
     {
-        std::vector<double> ka = kbd_table(2 * a), kb = (a == b) ? ka : kbd_table(2 * b);
-        for (int n = 0; n < a; ++n) win[n] = ka[n];
-        for (int i = 0; i < b; ++i) win[a + i] = kb[b + i];
         for (int n = 0; n < N; ++n)                      // window.py:38-42
             hann[n] = 0.5 + (-0.5 * std::cos(((2.0 * M_PI) / N) * (n + 0.5)));
         // a = b: the two halves are built from the same running sums in the same order, so win[n] == win[N - 1 - n] bit for
@@ -258,13 +288,8 @@ bool build_shape(const mrc_config& cfg, int a, int b, HostShape* out, std::strin
     }
     // twiddles
     const int M = S.halfN;
-    std::vector<double2> pre(S.Q), post(S.Q);
-    for (int n = 0; n < S.Q; ++n) {
-        long double ang = -kPiL * (4.0L * n + 1.0L) / (4.0L * M);
-        pre[n] = make_double2((double)cosl(ang), (double)sinl(ang));
-        long double ang2 = -kPiL * (long double)n / (long double)M;
-        post[n] = make_double2((double)cosl(ang2), (double)sinl(ang2));
-    }
+    std::vector<double2> pre, post;
+    dct4_twiddles(S.Q, M, &pre, &post);
     std::vector<double2> wQ = unit_circle(S.Q, 2.0L * kPiL / S.Q);
     std::vector<double2> wH = unit_circle(S.H, 2.0L * kPiL / S.H);
     std::vector<double2> wN = unit_circle(S.H, 2.0L * kPiL / N);
@@ -339,6 +364,36 @@ bool build_shape(const mrc_config& cfg, int a, int b, HostShape* out, std::strin
     S.msPlan = (const int*)(base + oMsPlan);
     S.lineC = (const LineConstants*)(base + oLineC);
     S.fftTw = fftTw.empty() ? nullptr : (const double2*)(base + oFftTw);
+    return true;
+}
+
+// What decode_kernel reads of a shape and nothing else: the transform's sizes and FFT plan, its twiddles and the
+// transition window.  No band table, no psychoacoustic constant and no peak search: a shape too short for build_shape
+// (the reduced-rate synthesis of the store, a block of (a, b) / D) still has an inverse transform.
+bool synth_shape_rule(int a, int b, std::string* err) {
+    DevShape S;
+    return transform_shape(a, b, &S, err) && transform_radices(&S, err);
+}
+
+bool build_synth_shape(int a, int b, HostShape* out, std::string* err) {
+    DevShape& S = out->dev;
+    if (!transform_shape(a, b, &S, err) || !transform_radices(&S, err)) return false;
+    std::vector<double2> pre, post;
+    dct4_twiddles(S.Q, S.halfN, &pre, &post);
+    BlobWriter bw;
+    const size_t oWin = bw.put(transition_window(a, b)), oPre = bw.put(pre), oPost = bw.put(post),
+                 oWQ = bw.put(unit_circle(S.Q, 2.0L * kPiL / S.Q));
+    void* blob = nullptr;
+    if (hipMalloc(&blob, bw.bytes.size()) != hipSuccess) { *err = "hipMalloc(shape tables) failed"; return false; }
+    out->blob.reset(blob);
+    if (hipMemcpy(blob, bw.bytes.data(), bw.bytes.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        *err = "hipMemcpy(shape tables) failed";
+        return false;
+    }
+    unsigned char* base = (unsigned char*)blob;
+    S.win = (const double*)(base + oWin);
+    S.pre = (const double2*)(base + oPre);      S.post = (const double2*)(base + oPost);
+    S.wQ = (const double2*)(base + oWQ);
     return true;
 }
 

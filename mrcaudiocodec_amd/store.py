@@ -5,6 +5,12 @@ blocks its windows overlap, and no file byte crosses PCIe again.
 
     with PacStore(handle, bufs) as store:
         x = store.decode_window(files, starts, 48000, dtype=torch.float32)     # [len(files)][channels][48000], on the GPU
+        y = store.decode_window(files, starts, 12000, dtype=torch.float32, rate_divisor=4)   # the same second at 1/4 rate
+
+rate_divisor = 2 or 4 (mrc_pac_store_decode_window_reduced) decodes at half or quarter sample rate straight from the MDCT
+lines: the first 1/D of each block's lines through an inverse transform D times shorter.  starts and window then count
+reduced samples; reduced sample m is the signal, band-limited to the new Nyquist frequency, at full-rate time
+D m + (D - 1) / 2 -- (D - 1) / 2 full-rate samples after full-rate sample D m.
 """
 import ctypes as C
 
@@ -15,6 +21,14 @@ from ._lib import lib
 
 STAT_NAMES = ("chunks_parsed", "decode_launches", "slabs", "plan_bytes_uploaded")
 MS_NAMES = ("plan_upload", "unpack", "synthesis", "window_out")
+RATE_DIVISORS = (1, 2, 4)
+
+
+def check_rate_divisor(rate_divisor, what="decode_window"):
+    """rate_divisor as an int in RATE_DIVISORS, else ValueError (a bool or a float is not an int)"""
+    if isinstance(rate_divisor, bool) or not isinstance(rate_divisor, (int, np.integer)) or int(rate_divisor) not in RATE_DIVISORS:
+        raise ValueError("%s: rate_divisor must be an int in {1, 2, 4}, got %r" % (what, rate_divisor))
+    return int(rate_divisor)
 
 
 def _formats():
@@ -70,7 +84,12 @@ class PacStore:
     def __len__(self):
         return len(self.n_channels)
 
-    def decode_window(self, files, starts, window, channels=None, dtype=None, out=None, stream=None):
+    def n_samples_at(self, rate_divisor):
+        """.n_samples at 1 / rate_divisor of the sample rate: n_samples // rate_divisor per file (exact for every divisor the
+        library accepts for the handle's block lengths)"""
+        return self.n_samples // check_rate_divisor(rate_divisor, "n_samples_at")
+
+    def decode_window(self, files, starts, window, channels=None, dtype=None, out=None, stream=None, rate_divisor=1):
         """Item i = samples [starts[i], starts[i] + window) of file files[i], zeros where that leaves the file (starts may be
         negative or past the end) -> a torch tensor [n][channels][window] on the handle's device.  dtype: torch.int16 (the
         default: the codes Handle.decode_pac_pcm16 writes, bit for bit), torch.float64 (the overlap-added signal before the
@@ -78,8 +97,13 @@ class PacStore:
         count among the items' files.  A mono file fills both channels of a two-channel call; a stereo file in a one-channel
         call is refused.  out: a contiguous tensor of that shape, dtype and device to write into (else ValueError, before any
         library call).  stream: a raw stream; None: torch's current stream on the device.  The call returns when the result
-        is there."""
+        is there.
+        rate_divisor: 1, 2 or 4 (else ValueError, before any library call).  2 or 4: starts and window count samples at that
+        fraction of the sample rate (n_samples_at), sample m being the band-limited signal at full-rate time
+        D m + (D - 1) / 2; torch.float64 is then the reduced overlap-added signal, torch.float32 and torch.int16 its
+        conversions.  A divisor the handle's block shapes do not divide by is refused by the library (MrcError)."""
         import torch
+        rate_divisor = check_rate_divisor(rate_divisor)
         files = np.ascontiguousarray(np.asarray(files, dtype=np.int64).reshape(-1))
         starts = np.ascontiguousarray(np.asarray(starts, dtype=np.int64).reshape(-1))
         if files.shape != starts.shape:
@@ -103,8 +127,12 @@ class PacStore:
             raise ValueError("decode_window: out must be a contiguous %s tensor of shape %s on %s" % (dtype, shape, dev))
         if stream is None:
             stream = torch.cuda.current_stream(dev).cuda_stream
-        self._handle._check(lib.mrc_pac_store_decode_window(self._s, n, files.ctypes.data, starts.ctypes.data, window, channels,
-                                                            fmt, out.data_ptr() if out.numel() else None, stream or None))
+        tail = (n, files.ctypes.data, starts.ctypes.data, window, channels, fmt, out.data_ptr() if out.numel() else None,
+                stream or None)
+        if rate_divisor == 1:
+            self._handle._check(lib.mrc_pac_store_decode_window(self._s, *tail))
+        else:
+            self._handle._check(lib.mrc_pac_store_decode_window_reduced(self._s, rate_divisor, *tail))
         return out
 
     def stats(self):
