@@ -1,6 +1,7 @@
 // Device-side helpers shared by the gfx950 kernels (included by the .hip files only).
 #pragma once
 #include "mrc_internal.hpp"
+#include "mrc_wave.hpp"
 
 namespace mrc {
 namespace dev {
@@ -65,88 +66,44 @@ __device__ __forceinline__ unsigned xcd_contiguous(unsigned b, unsigned g) {
     return x * base + (x < rem ? x : rem) + q;
 }
 
-// ---- cross-lane reductions that stay in registers (no ds_bpermute: the LDS pipe is busy enough).  All 64 lanes
-// must be active.  Within a 16-lane row: DPP quad permutes, half mirror, rotate by 8.  Across rows: gfx950's
-// v_permlane16_swap / v_permlane32_swap exchange the odd rows (upper half) of one register with the even rows
-// (lower half) of another; swapping a value with itself leaves {even, even} and {odd, odd} copies to combine.
-typedef unsigned int uint2v __attribute__((ext_vector_type(2)));
-template <int CTRL>
-__device__ __forceinline__ double dpp_move(double v) {
-    // every lane has a valid source for the controls used here, so no "old" value has to be prepared
-    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-template <int DIST, class Op>
-__device__ __forceinline__ double rows_combine(double v, Op op) {
-    static_assert(DIST == 32 || DIST == 16, "swap distance");
-    const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
-    const uint2v l = DIST == 32 ? __builtin_amdgcn_permlane32_swap(lo, lo, false, false)
-                                : __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
-    const uint2v h = DIST == 32 ? __builtin_amdgcn_permlane32_swap(hi, hi, false, false)
-                                : __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
-    return op(__hiloint2double((int)h.x, (int)l.x), __hiloint2double((int)h.y, (int)l.y));
-}
-template <class Op>
-__device__ __forceinline__ double wave_allreduce(double v, Op op) {
-    v = op(v, dpp_move<0xB1>(v));                       // quad_perm [1,0,3,2]
-    v = op(v, dpp_move<0x4E>(v));                       // quad_perm [2,3,0,1]
-    v = op(v, dpp_move<0x141>(v));                      // row_half_mirror: the other quad of the 8-lane group
-    v = op(v, dpp_move<0x128>(v));                      // row_ror:8: the other half of the row
-    v = rows_combine<16>(v, op);
-    return rows_combine<32>(v, op);
-}
-__device__ __forceinline__ double wave_max(double v) {
-    return wave_allreduce(v, [](double a, double b) { return fmax(a, b); });
-}
-// v_max_f64 as it is: fmax() makes the compiler canonicalise operands that come out of a lane exchange (a second
-// v_max_f64 x, x per operand, against signalling NaNs); the values reduced with this are ratios and magnitudes
-__device__ __forceinline__ double max_raw(double a, double b) {
-    double r;
-    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-// maximum over each 16-lane row, in every lane of the row
-__device__ __forceinline__ double row_max(double v) {
-    v = max_raw(v, dpp_move<0xB1>(v));
-    v = max_raw(v, dpp_move<0x4E>(v));
-    v = max_raw(v, dpp_move<0x141>(v));
-    return max_raw(v, dpp_move<0x128>(v));
-}
-__device__ __forceinline__ double wave_sum(double v) {
-    return wave_allreduce(v, [](double a, double b) { return a + b; });
-}
-
 // psychoac.py:8-12
 __device__ __forceinline__ double spl_db(double intensity) {
     return fmax(96 + 10 * log10(intensity), -30.0);
 }
 
-// quantize.py:12-38 magnitude code for |x| (R = nBits)
-__device__ __forceinline__ long long mag_code(double mag, int nBits) {
-    if (mag >= 1.0) return (1LL << (nBits - 1)) - 1;
-    return (long long)((((double)((1LL << nBits) - 1)) * mag + 1.0) / 2.0);
+// quantize.py:12-38 magnitude code for |x| (R = nBits).  The quantiser is a template on the integer type of the code:
+// long long for every width mrc_quantize_uniform accepts (up to 62 bits); unsigned for code widths of at most 31 bits (the
+// encoder's: 2^nScaleBits - 1 + bits <= 15 + 16) -- the same expressions, the truncation done by the 32-bit conversion
+// instead of the emulated 64-bit one.
+template <class Code = long long>
+__device__ __forceinline__ Code mag_code(double mag, int nBits) {
+    if (mag >= 1.0) return (Code(1) << (nBits - 1)) - Code(1);
+    return (Code)((((double)((Code(1) << nBits) - Code(1))) * mag + 1.0) / 2.0);
 }
+__device__ __forceinline__ int top_bit(long long code) { return 63 - __clzll(code); }
+__device__ __forceinline__ int top_bit(unsigned code) { return 31 - __clz((int)code); }
 
 // quantize.py:114-146
+template <class Code = long long>
 __device__ __forceinline__ int scale_factor_dev(double v, int nScaleBits, int nMantBits) {
     const int cap = (1 << nScaleBits) - 1;
     const int nBits = cap + nMantBits;
-    long long code = mag_code(fabs(v), nBits);
-    int top = code > 0 ? 63 - __clzll(code) : 0;
-    int lz = (nBits - 2) - top;
+    const Code code = mag_code<Code>(fabs(v), nBits);
+    const int top = code > 0 ? top_bit(code) : 0;
+    const int lz = (nBits - 2) - top;
     return lz < cap ? lz : cap;
 }
 
 // quantize.py:294-322 (one element)
+template <class Code = long long>
 __device__ __forceinline__ int mantissa_dev(double x, int scale, int nScaleBits, int nMantBits) {
     const int cap = (1 << nScaleBits) - 1;
     const int nBits = cap + nMantBits;
-    long long code = mag_code(fabs(x), nBits);
+    const Code code = mag_code<Code>(fabs(x), nBits);
     int shift = cap - scale;
     if (shift < 0) shift = 0;
-    long long m = code >> shift;
-    return (int)((x < 0.0 ? (1LL << (nMantBits - 1)) : 0LL) + m);
+    const Code m = code >> shift;
+    return (int)((x < 0.0 ? (Code(1) << (nMantBits - 1)) : Code(0)) + m);
 }
 
 // ------------------------------------------------------------------------------------------------

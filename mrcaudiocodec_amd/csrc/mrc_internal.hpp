@@ -160,7 +160,7 @@ struct PackParams {
     int nScaleBits, nMantSizeBits, blkBitsA, blkBitsB;      // field widths
     unsigned bitA, bitB;                                    // block-switching bits of this shape (pacfileThem.py:720-723)
 };
-void pack_tables(PackTables* out);                          // host, from the table data in mrc_pack.cpp
+void pack_tables(PackTables* out);                          // host (mrc_pack.cpp), from mrc_huffman_tables.hpp
 size_t pack_workspace_bytes(int64_t nChunks);
 hipError_t launch_pack(const DevShape& S, const PackParams& P, const PackTables& T, int64_t nBlocks, const int* oscale,
                        const int* msSwitch, const int* scaleFactor, const int* bitAlloc, const void* mant, int mantFmt,
@@ -191,7 +191,7 @@ hipError_t launch_pack_export(const void* ws, int64_t nChunks, long long* hostOu
 const int* pack_error_flag(const void* ws, int64_t nChunks);          // device addresses inside ws
 const long long* pack_total_bytes(const void* ws, int64_t nChunks);
 // mrc_kernels_unpack.hip -- `.pac` chunk parsing on the device (the parser itself: mrc_unpack.hpp)
-void unpack_tables(UnpackTables* out);                      // host, from the table data in mrc_pack.cpp
+void unpack_tables(UnpackTables* out);                      // host (mrc_pack.cpp), from mrc_huffman_tables.hpp
 const char* unpack_status_text(int flag);                   // the words for a set of (1 << UnpackStatus) bits (mrc_api_decode.cpp)
 struct UnpackErr { int flag; int firstBad; };               // first bad chunk (lowest index) and its UnpackStatus
 // layout of mrc_unpack_blocks: chunk c = blk * nch + ch, buf / chunkOffset / outputs in device memory

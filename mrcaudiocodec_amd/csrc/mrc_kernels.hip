@@ -100,13 +100,6 @@ struct TwLds {
     const double2* w;                                   // LDS, [n]
     __device__ __forceinline__ double2 operator()(int t, int /*nq*/) const { return w[t]; }
 };
-// LDS traffic between lanes of ONE wave: order the wave's own DS operations and keep the compiler from moving LDS accesses
-// across this point
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 // one Stockham pass of radix R over U transforms of Q points each (P = product of the radices already done), a butterfly
 // per lane and round
 template <int R, int Q, int P, int U>
@@ -155,33 +148,6 @@ __device__ __forceinline__ double2* wave_fft(double2* A, double2* B, const doubl
     wave_pass<3, Q, 96, U>(B, A, wl, lane);
     wave_sync();
     return A;
-}
-
-// Four per-lane partial maxima (one per unit of a group) -> every lane of row r (lanes 16 r .. 16 r + 15) ends with the
-// wave-wide maximum of value r: two rounds of permlane swaps fold the four registers into one whose rows belong to the four
-// values, then one reduction inside the rows -- a quarter of four separate wave reductions.
-__device__ __forceinline__ double wave_max4(double p0, double p1, double p2, double p3) {
-    auto swap = [](double a, double b, bool half, double* x, double* y) {
-        const unsigned al = (unsigned)__double2loint(a), ah = (unsigned)__double2hiint(a);
-        const unsigned bl = (unsigned)__double2loint(b), bh = (unsigned)__double2hiint(b);
-        const uint2v l = half ? __builtin_amdgcn_permlane32_swap(al, bl, false, false)
-                              : __builtin_amdgcn_permlane16_swap(al, bl, false, false);
-        const uint2v h = half ? __builtin_amdgcn_permlane32_swap(ah, bh, false, false)
-                              : __builtin_amdgcn_permlane16_swap(ah, bh, false, false);
-        *x = __hiloint2double((int)h.x, (int)l.x);
-        *y = __hiloint2double((int)h.y, (int)l.y);
-    };
-    double x, y;
-    swap(p0, p2, true, &x, &y);                         // x = {p0 lower half, p2 lower half}, y = {p0 upper, p2 upper}
-    const double m02 = fmax(x, y);                      // lanes 0-31: value 0 over both halves; lanes 32-63: value 2
-    swap(p1, p3, true, &x, &y);
-    const double m13 = fmax(x, y);                      // lanes 0-31: value 1; lanes 32-63: value 3
-    swap(m02, m13, false, &x, &y);                      // x = {m02 row 0, m13 row 0, m02 row 2, m13 row 2}, y = the odd rows
-    double q = fmax(x, y);                              // row r: value r
-    q = fmax(q, dpp_move<0xB1>(q));
-    q = fmax(q, dpp_move<0x4E>(q));
-    q = fmax(q, dpp_move<0x141>(q));
-    return fmax(q, dpp_move<0x128>(q));
 }
 
 constexpr int kMdctWaves = 4;                           // waves per workgroup, each with its own groups of units
@@ -362,7 +328,8 @@ __global__ __launch_bounds__(kWave * kMdctWaves, K64 ? 3 : 2) void mdct_wave_ker
                 if (u0 + uu < nUnits) *reinterpret_cast<double2*>(lines + (u0 + uu) * M + 2 * lane) = x;
                 pk[uu] = fmax(fabs(x.x), fabs(x.y));
             }
-            const double peak = wave_max4(pk[0], pk[1], pk[2], pk[3]);
+            // row r of the wave: the maximum of unit r
+            const double peak = wave_fold4(pk[0], pk[1], pk[2], pk[3], [](double a, double b) { return fmax(a, b); });
             const int r = lane >> 4;
             if ((lane & 15) == 0 && u0 + r < nUnits) oscale[u0 + r] = scale_factor_dev(peak, S.nScaleBits, 5);
         } else
@@ -562,10 +529,6 @@ __global__ void stereo_masking_kernel(int64_t n, const double* __restrict__ mid,
 // run over registers in NumPy's order, and the only LDS is the 64 node sums per wave: 0.25 ms.
 constexpr int kMsWaves = 4;
 constexpr int kMsMaxSteps = 16, kMsRounds = 8;          // leaf <= 128 lines; <= 64 leaves, eight per round
-template <int CTRL> __device__ __forceinline__ double dpp_from(double v) {           // lane i reads lane i + (CTRL - 0x100) of its row
-    return __hiloint2double(__builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false),
-                            __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false));
-}
 __global__ __launch_bounds__(kWave * kMsWaves) void ms_switch_direct_kernel(int64_t nBlocks, int nBands, int nLeaves,
                                                                              int nInternal, const int* __restrict__ plan,
                                                                              const double* __restrict__ L,
@@ -620,7 +583,7 @@ __global__ __launch_bounds__(kWave * kMsWaves) void ms_switch_direct_kernel(int6
         const double dt = dOf(lt, rt), st = sOf(lt, rt);
 #define MRC_MS_TAIL(T)                                                                  \
         {                                                                               \
-            const double a = T ? dpp_from<0x100 + (T ? T : 1)>(dt) : dt, b = T ? dpp_from<0x100 + (T ? T : 1)>(st) : st;   \
+            const double a = T ? dpp_move<0x100 + (T ? T : 1)>(dt) : dt, b = T ? dpp_move<0x100 + (T ? T : 1)>(st) : st;   \
             if (T < tail) { d += a; sg += b; }                                          \
         }
         MRC_MS_TAIL(0) MRC_MS_TAIL(1) MRC_MS_TAIL(2) MRC_MS_TAIL(3) MRC_MS_TAIL(4) MRC_MS_TAIL(5) MRC_MS_TAIL(6)

@@ -29,87 +29,18 @@
 // float64 for every value the loop can reach (|bitsLeft| <= |budget|, both multiples of ulp(budget)), so
 // `nLines <= bitsLeft` is `nLines + spent <= floor(budget)` and `bitsLeft > 0` is `spent < ceil(budget)`.
 #include "mrc_device.hpp"
+#include "mrc_huffman_tables.hpp"
 
 namespace mrc {
 using namespace dev;
 namespace {
 
 constexpr int kMaxEvents = 64 * 15;                   // bands (x streams) <= 64, grants per band <= maxMantBits - 1 <= 15
-constexpr int kLutSize = 65;                          // largest value in any Huffman table is 64 (index 65: any other)
 
-// code length per value (0 = not in the table); rows: percussive, silence, speech, tonal (sorted names; the table data
-// of mrc_pack.cpp / mrc_kernels_huff.hip)
-__constant__ unsigned char kChainCodeLen[4][kLutSize] = {
-    {1, 4, 3, 6, 3, 4, 6, 8, 5, 6, 7, 7, 7, 9, 9, 0, 6},
-    {2, 3, 3, 5, 2, 4, 6, 0, 5, 5, 6, 4},
-    {2, 4, 3, 6, 2, 4, 6, 4, 4, 5, 6, 7, 7, 0, 0, 0, 6, 7, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 7},
-    {1, 5, 3, 7, 3, 7, 8, 4, 4, 7, 8, 0, 0, 0, 0, 0, 5, 7, 8, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 6,
-     0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 8}};
-__constant__ int kChainEscape[4] = {16, 11, 7, 7};
+// code length per value (0 = not in the table) and escape value of the four trained tables
+__constant__ HuffLens kChainCodeLen = make_huff_lens();
+__constant__ int kChainEscape[4] = {kHuffTables[0].escape, kHuffTables[1].escape, kHuffTables[2].escape, kHuffTables[3].escape};
 
-__device__ __forceinline__ int wave_sum_i(int v) {
-    v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false);      // quad_perm [1,0,3,2]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, false);      // quad_perm [2,3,0,1]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, false);     // row_half_mirror
-    v += __builtin_amdgcn_update_dpp(0, v, 0x128, 0xf, 0xf, false);     // row_ror:8
-    const uint2v r16 = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
-    v = (int)(r16.x + r16.y);
-    const uint2v r32 = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
-    return (int)(r32.x + r32.y);
-}
-// Four per-lane partial sums -> every lane of row r (lanes 16 r .. 16 r + 15) ends with the wave-wide sum of value r: two
-// rounds of permlane swaps fold the four registers into one whose rows belong to the four values, then one reduction inside
-// the rows (10 instead of 32 instructions for four separate sums)
-__device__ __forceinline__ unsigned wave_sum4_u(unsigned a, unsigned b, unsigned c, unsigned d) {
-    uint2v t = __builtin_amdgcn_permlane32_swap(a, c, false, false);    // x = {a lower half, c lower half}, y = the upper halves
-    const unsigned ac = t.x + t.y;                                      // lanes 0-31: a over both halves; lanes 32-63: c
-    t = __builtin_amdgcn_permlane32_swap(b, d, false, false);
-    const unsigned bd = t.x + t.y;
-    t = __builtin_amdgcn_permlane16_swap(ac, bd, false, false);         // x = {ac row 0, bd row 0, ac row 2, bd row 2}, y = the odd rows
-    int q = (int)(t.x + t.y);                                           // row r: value r
-    q += __builtin_amdgcn_update_dpp(0, q, 0xB1, 0xf, 0xf, false);
-    q += __builtin_amdgcn_update_dpp(0, q, 0x4E, 0xf, 0xf, false);
-    q += __builtin_amdgcn_update_dpp(0, q, 0x141, 0xf, 0xf, false);
-    q += __builtin_amdgcn_update_dpp(0, q, 0x128, 0xf, 0xf, false);
-    return (unsigned)q;
-}
-// ... two values: lanes 0-31 end with the sum of a, lanes 32-63 with the sum of b
-__device__ __forceinline__ int wave_sum2_i(int a, int b) {
-    uint2v t = __builtin_amdgcn_permlane32_swap((unsigned)a, (unsigned)b, false, false);
-    int q = (int)(t.x + t.y);
-    q += __builtin_amdgcn_update_dpp(0, q, 0xB1, 0xf, 0xf, false);
-    q += __builtin_amdgcn_update_dpp(0, q, 0x4E, 0xf, 0xf, false);
-    q += __builtin_amdgcn_update_dpp(0, q, 0x141, 0xf, 0xf, false);
-    q += __builtin_amdgcn_update_dpp(0, q, 0x128, 0xf, 0xf, false);
-    t = __builtin_amdgcn_permlane16_swap((unsigned)q, (unsigned)q, false, false);
-    return (int)(t.x + t.y);
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xf, 0xf, false));
-    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xf, 0xf, false));
-    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x141, 0xf, 0xf, false));
-    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x128, 0xf, 0xf, false));
-    const uint2v r16 = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
-    v = max((int)r16.x, (int)r16.y);
-    const uint2v r32 = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
-    return max((int)r32.x, (int)r32.y);
-}
-// inclusive prefix sum over the 64 lanes (Kogge-Stone in 16-lane rows by DPP shifts, row totals by row_bcast)
-__device__ __forceinline__ int wave_scan_i(int v) {
-    v += __builtin_amdgcn_mov_dpp(v, 0x111, 0xf, 0xf, true);            // row_shr:1 (bound_ctrl: 0 shifted in)
-    v += __builtin_amdgcn_mov_dpp(v, 0x112, 0xf, 0xf, true);
-    v += __builtin_amdgcn_mov_dpp(v, 0x114, 0xf, 0xf, true);
-    v += __builtin_amdgcn_mov_dpp(v, 0x118, 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);     // row_bcast:15 into rows 1 and 3
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);     // row_bcast:31 into rows 2 and 3
-    return v;
-}
-// LDS traffic between the lanes of ONE wave
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 // the order np.argmax serves grant attempts in: larger key first, equal keys by band index
 __device__ __forceinline__ bool event_before(double ka, int ba, double kb, int bb) {
     return ka > kb || (ka == kb && ba < bb);
@@ -195,7 +126,7 @@ __global__ __launch_bounds__(kWave * kPrepWaves) void chain_prep_kernel(
         const unsigned long long mask = __ballot(has);
         const int off = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
         const int cost = has ? (k == 0 ? 2 * nB : nB) : 0;  // bitalloc.py:137-138, 144-145
-        const int incl = wave_scan_i(cost);
+        const int incl = wave_incl_scan(cost);
         if (has) {
             const int p = base + off;
             sEv[p] = (unsigned)band | ((unsigned)(k + 2) << 6) | ((unsigned)nB << 11);
@@ -426,27 +357,6 @@ __device__ __forceinline__ void item_load(const LoadView& G, int64_t idx, int ti
     }
 }
 
-// quantize.py:12-38 for code widths of at most 31 bits (the encoder's: 2^nScaleBits - 1 + bits <= 15 + 16): the same
-// expression as dev::mag_code, the truncation done by the 32-bit conversion instead of the emulated 64-bit one
-__device__ __forceinline__ unsigned mag_code32(double mag, int nBits) {
-    if (mag >= 1.0) return (1u << (nBits - 1)) - 1u;
-    return (unsigned)((((double)((1u << nBits) - 1u)) * mag + 1.0) / 2.0);
-}
-__device__ __forceinline__ int scale_factor32(double v, int nScaleBits, int nMantBits) {      // quantize.py:114-146
-    const int cap = (1 << nScaleBits) - 1;
-    const int nBits = cap + nMantBits;
-    const unsigned code = mag_code32(fabs(v), nBits);
-    const int top = code ? 31 - __clz((int)code) : 0;
-    const int lz = (nBits - 2) - top;
-    return lz < cap ? lz : cap;
-}
-__device__ __forceinline__ unsigned mantissa32(double x, int scale, int nScaleBits, int nMantBits) {   // quantize.py:294-322
-    const int cap = (1 << nScaleBits) - 1;
-    const unsigned code = mag_code32(fabs(x), cap + nMantBits);
-    const int shift = cap - scale;
-    return (x < 0.0 ? (1u << (nMantBits - 1)) : 0u) + (code >> (shift < 0 ? 0 : shift));
-}
-
 // Ladder: a grid of (stream, rate) workgroups (blockIdx.y = the rate).  A separate instance, so that the single-rate scan --
 // whose scalar registers are all in use -- keeps its code as it is.
 template <int NT, bool Ladder>
@@ -464,7 +374,7 @@ __global__ __launch_bounds__(NT) void chain_phase_b_kernel(
     __shared__ int sOsc[2][4];                           // overall scale of signal q, likewise
     __shared__ unsigned sInfo[kWave];                    // per (stream, band): bits | scale factor << 8
     __shared__ unsigned sEsc[kWave];                     // per (stream, band): bits + escape code length of each table, 8 bits each
-    __shared__ unsigned sLut[kLutSize + 1];              // per value: the four code lengths, 8 bits each (0: not in the table)
+    __shared__ unsigned sLut[kPackLutSize + 1];              // per value: the four code lengths, 8 bits each (0: not in the table)
     __shared__ int sCtl[4];                              // remaining bits, raw bits of stream 0 / 1
     __shared__ int sCut;                                 // events that are certain grants (counted by all waves)
     __shared__ unsigned sAcc[2][4];                      // Huffman prices of the block, summed over the waves (LDS atomics); by item parity
@@ -478,14 +388,14 @@ __global__ __launch_bounds__(NT) void chain_phase_b_kernel(
         reservoir += (int64_t)blockIdx.y * gridDim.x;
         if (resTrace) resTrace += (int64_t)blockIdx.y * traceStride;
     }
-    for (int v = tid; v <= kLutSize; v += kChainThreads) {
+    for (int v = tid; v <= kPackLutSize; v += kChainThreads) {
         unsigned e = 0;
-        if (v < kLutSize)
-            for (int t = 0; t < 4; ++t) e |= (unsigned)kChainCodeLen[t][v] << (8 * t);
+        if (v < kPackLutSize)
+            for (int t = 0; t < 4; ++t) e |= (unsigned)kChainCodeLen.len[t][v] << (8 * t);
         sLut[v] = e;
     }
     unsigned escLen4 = 0;                                // the escape code's length in each table
-    for (int t = 0; t < 4; ++t) escLen4 |= (unsigned)kChainCodeLen[t][kChainEscape[t]] << (8 * t);
+    for (int t = 0; t < 4; ++t) escLen4 |= (unsigned)kChainCodeLen.len[t][kChainEscape[t]] << (8 * t);
     // the reservoir travels in a register of EVERY thread: each wave works the table decision out for itself from the block's
     // price sums, so that no barrier stands between the decision and the next item's budget
     int resReg = reservoir[strmId];
@@ -652,7 +562,7 @@ __global__ __launch_bounds__(NT) void chain_phase_b_kernel(
                 while (pending != 0ull && !done) {
                     const bool live = ((pending >> lane) & 1ull) && ((alive >> evBand) & 1ull);
                     const int cst = live ? evCost : 0;
-                    const int incl = wave_scan_i(cst);
+                    const int incl = wave_incl_scan(cst);
                     const int before = spent + incl - cst;
                     // bitalloc.py:131,134: the loop goes on while bits are left, and only nLines is tested (also for the
                     // two-bit grant)
@@ -677,11 +587,12 @@ __global__ __launch_bounds__(NT) void chain_phase_b_kernel(
 #endif
             // ---- scale factors (codecThem.py:346-347), raw size of each stream (codecThem.py:141-146)
             const int rawMine = myBits * myN;
-            const int raw01 = wave_sum2_i((valid && lane < nb) ? rawMine : 0, (valid && lane >= nb) ? rawMine : 0);
+            const int raw01 = wave_fold2((valid && lane < nb) ? rawMine : 0, (valid && lane >= nb) ? rawMine : 0,
+                                         [](int a, int b) { return a + b; });
             if (valid) {
                 // codecThem.py:346-347: the scale factor comes from max |scaled line| of the band; scaling by 2^overallScale
                 // is exact, so maximum and scaling commute
-                const int sf = scale_factor32(ldexp(peakCur, oscCur), G.nScaleBits, myBits);
+                const int sf = scale_factor_dev<unsigned>(ldexp(peakCur, oscCur), G.nScaleBits, myBits);
                 sInfo[lane] = (unsigned)myBits | ((unsigned)sf << 8);
                 sEsc[lane] = escLen4 + (unsigned)myBits * 0x01010101u;
                 G.bitAlloc[idx * nTot + lane] = myBits;
@@ -721,8 +632,8 @@ __global__ __launch_bounds__(NT) void chain_phase_b_kernel(
                         const int ba = (int)(info & 0xffu);
                         unsigned cdv = 0u;
                         if (ba) {
-                            cdv = mantissa32(x[j], (int)(info >> 8), nScaleBits, ba);
-                            const unsigned lens = sLut[cdv < (unsigned)kLutSize ? cdv : (unsigned)kLutSize];
+                            cdv = mantissa_dev<unsigned>(x[j], (int)(info >> 8), nScaleBits, ba);
+                            const unsigned lens = sLut[cdv < (unsigned)kPackLutSize ? cdv : (unsigned)kPackLutSize];
                             // a value without a code (length byte 0) costs the escape code + the raw mantissa; the escape
                             // VALUE itself is priced as its code alone (codecThem.py:169-172)
                             unsigned z = (lens & 0x7f7f7f7fu) + 0x7f7f7f7fu;
@@ -742,7 +653,8 @@ __global__ __launch_bounds__(NT) void chain_phase_b_kernel(
         }
         {
             // bytes -> 16-bit fields (per table at most 25 bits x 1024 lines): tables 0 | 2 and 1 | 3 of each stream
-            const unsigned w = wave_sum4_u(accA & 0x00ff00ffu, (accA >> 8) & 0x00ff00ffu, accB & 0x00ff00ffu, (accB >> 8) & 0x00ff00ffu);
+            const unsigned w = wave_fold4(accA & 0x00ff00ffu, (accA >> 8) & 0x00ff00ffu, accB & 0x00ff00ffu, (accB >> 8) & 0x00ff00ffu,
+                                          [](unsigned a, unsigned b) { return a + b; });
             if ((lane & 15) == 0) atomicAdd(&sAcc[par][lane >> 4], w);         // row r of the wave: field pair r
         }
         MRC_CP(8);

@@ -8,32 +8,15 @@
 // One wavefront per (frame, stream); lanes stride over the lines.  The reference's pricing quirk is kept: a
 // mantissa equal to the table's escape VALUE is priced as its code alone (codecThem.py:169-172).
 #include "mrc_device.hpp"
+#include "mrc_huffman_tables.hpp"
 
 namespace mrc {
 using namespace dev;
 namespace {
 
-constexpr int kLutSize = 65;                           // largest value in any table is 64
-// code length per value (0 = not in the table); rows: percussive, silence, speech, tonal (sorted names)
-__constant__ unsigned char kCodeLen[4][kLutSize] = {
-    {1, 4, 3, 6, 3, 4, 6, 8, 5, 6, 7, 7, 7, 9, 9, 0, 6},
-    {2, 3, 3, 5, 2, 4, 6, 0, 5, 5, 6, 4},
-    {2, 4, 3, 6, 2, 4, 6, 4, 4, 5, 6, 7, 7, 0, 0, 0, 6, 7, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 7},
-    {1, 5, 3, 7, 3, 7, 8, 4, 4, 7, 8, 0, 0, 0, 0, 0, 5, 7, 8, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 6,
-     0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 8}};
-__constant__ int kEscape[4] = {16, 11, 7, 7};
-
-// sum over the 64 lanes, in registers (DPP inside a 16-lane row, gfx950 permlane swaps across rows); all lanes active
-__device__ __forceinline__ int wave_sum_int(int v) {
-    v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false);      // quad_perm [1,0,3,2]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, false);      // quad_perm [2,3,0,1]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, false);     // row_half_mirror
-    v += __builtin_amdgcn_update_dpp(0, v, 0x128, 0xf, 0xf, false);     // row_ror:8
-    const uint2v r16 = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
-    v = (int)(r16.x + r16.y);
-    const uint2v r32 = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
-    return (int)(r32.x + r32.y);
-}
+// code length per value (0 = not in the table) and escape value of the four trained tables
+__constant__ HuffLens kCodeLen = make_huff_lens();
+__constant__ int kEscape[4] = {kHuffTables[0].escape, kHuffTables[1].escape, kHuffTables[2].escape, kHuffTables[3].escape};
 
 // grid: nFrames blocks of nStreams waves.  reservoirNext (may be null): reservoirOut[f] + sum over the frame's
 // streams of bits_saved -- the value the NEXT block of the same stream starts from (codecThem.py:274).
@@ -55,16 +38,16 @@ __global__ void huffman_gain_kernel(DevShape S, int nStreams, const int* __restr
             raw += b;
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
-                const int len = (v >= 0 && v < kLutSize) ? kCodeLen[t][v] : 0;
-                cost[t] += len ? len : b + kCodeLen[t][kEscape[t]];
+                const int len = (v >= 0 && v < kPackLutSize) ? kCodeLen.len[t][v] : 0;
+                cost[t] += len ? len : b + kCodeLen.len[t][kEscape[t]];
             }
         }
     }
-    raw = wave_sum_int(raw);
-    int best = raw, table = 15;
+    raw = wave_sum_i(raw);
+    int best = raw, table = kPackRawTable;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-        const int c = wave_sum_int(cost[t]);
+        const int c = wave_sum_i(cost[t]);
         if (c < best) { best = c; table = t; }               // strictly less: the first table wins ties, raw wins ties
     }
     if (lane == 0) {

@@ -46,6 +46,8 @@ constexpr int kWaveLds = 1152;                       // doubles per wave (9 KiB)
 constexpr int kRun = 16;                             // units per wave (<= 64: a lane per unit holds its offset; 8 and 32 measured no faster)
 
 using dev::cmul;
+using dev::wave_max;
+using dev::wave_sync;
 __device__ __forceinline__ double2 cadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
 __device__ __forceinline__ double2 csub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
 __device__ __forceinline__ double2 mul_mi(double2 a) { return make_double2(a.y, -a.x); }     // a * (-i)
@@ -56,14 +58,6 @@ template <int R> __device__ __forceinline__ double2 mul_w32(double2 a) {
                              0.70710678118654752440, 0.55557023301960222474, 0.38268343236508977173,
                              0.19509032201612826785};
     return cmul(a, make_double2(c[R], -c[8 - R]));                   // sin(2 pi R/32) = cos(2 pi (8-R)/32)
-}
-
-// LDS traffic between lanes of ONE wave: order the wave's own DS operations and stop the compiler from
-// moving LDS accesses across this point.  No other wave is involved.
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
 // 4-point DFT (forward): v -> natural order
@@ -86,39 +80,6 @@ __device__ __forceinline__ void dft8(double2* u) {
     b3 = make_double2(h * (b3.y - b3.x), -h * (b3.x + b3.y));         // * (-1 - i)/sqrt2
     dft4(a0, a1, a2, a3, &u[0], &u[2], &u[4], &u[6]);
     dft4(b0, b1, b2, b3, &u[1], &u[3], &u[5], &u[7]);
-}
-
-// max over the 64 lanes, in registers (DPP inside a 16-lane row, gfx950 permlane swaps across rows; same scheme as
-// dev::wave_allreduce in mrc_device.hpp, which this self-contained file does not include); all lanes active
-template <int CTRL> __device__ __forceinline__ double dpp_move(double v) {
-    return __hiloint2double(__builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false),
-                            __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false));
-}
-typedef unsigned int uint2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ double wave_max(double v) {
-    v = fmax(v, dpp_move<0xB1>(v));
-    v = fmax(v, dpp_move<0x4E>(v));
-    v = fmax(v, dpp_move<0x141>(v));
-    v = fmax(v, dpp_move<0x128>(v));
-    {
-        const uint2v l = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(v), (unsigned)__double2loint(v), false, false);
-        const uint2v h = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(v), (unsigned)__double2hiint(v), false, false);
-        v = fmax(__hiloint2double((int)h.x, (int)l.x), __hiloint2double((int)h.y, (int)l.y));
-    }
-    const uint2v l = __builtin_amdgcn_permlane32_swap((unsigned)__double2loint(v), (unsigned)__double2loint(v), false, false);
-    const uint2v h = __builtin_amdgcn_permlane32_swap((unsigned)__double2hiint(v), (unsigned)__double2hiint(v), false, false);
-    return fmax(__hiloint2double((int)h.x, (int)l.x), __hiloint2double((int)h.y, (int)l.y));
-}
-
-__device__ __forceinline__ int scale_factor20(double v, int nScaleBits) {        // quantize.py:114-146, nMantBits = 5
-    const int cap = (1 << nScaleBits) - 1;
-    const int nBits = cap + 5;
-    double mag = fabs(v);
-    long long code = mag >= 1.0 ? (1LL << (nBits - 1)) - 1
-                                : (long long)((((double)((1LL << nBits) - 1)) * mag + 1.0) / 2.0);
-    int top = code > 0 ? 63 - __clzll(code) : 0;
-    int lz = (nBits - 2) - top;
-    return lz < cap ? lz : cap;
 }
 
 // One raw sample as it sits in memory -- an int16 PCM code or a float64 signed fraction -- loaded now, converted when
@@ -386,7 +347,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock, MRC_MDCT_WG_PER_CU) void md
             if (!(MRC_MDCT_PROFILE & 1) || xE[i] == 1.2345e300) *reinterpret_cast<double2*>(dst + 2 * i) = make_double2(xE[i], xO[i]);
         }
         peak = wave_max(peak);
-        if (lane == 0) oscale[unit] = scale_factor20(peak, S.nScaleBits);    // codecThem.py:321-322
+        if (lane == 0) oscale[unit] = dev::scale_factor_dev(peak, S.nScaleBits, 5);    // codecThem.py:321-322
         wave_sync();               // output staging read before the next unit overwrites the region
     }
 }

@@ -28,33 +28,6 @@ namespace {
 constexpr int kWavesPerGroup = 4;
 constexpr int kScanTile = 1024;                      // chunks per workgroup of the position scan
 
-__device__ __forceinline__ int wave_sum_i(int v) {
-    v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false);      // quad_perm [1,0,3,2]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, false);      // quad_perm [2,3,0,1]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, false);     // row_half_mirror
-    v += __builtin_amdgcn_update_dpp(0, v, 0x128, 0xf, 0xf, false);     // row_ror:8
-    const uint2v r16 = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
-    v = (int)(r16.x + r16.y);
-    const uint2v r32 = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
-    return (int)(r32.x + r32.y);
-}
-// inclusive prefix sum over the 64 lanes (Kogge-Stone in 16-lane rows by DPP shifts, row totals by row_bcast)
-__device__ __forceinline__ int wave_scan_i(int v) {
-    v += __builtin_amdgcn_mov_dpp(v, 0x111, 0xf, 0xf, true);            // row_shr:1 (bound_ctrl: 0 shifted in)
-    v += __builtin_amdgcn_mov_dpp(v, 0x112, 0xf, 0xf, true);
-    v += __builtin_amdgcn_mov_dpp(v, 0x114, 0xf, 0xf, true);
-    v += __builtin_amdgcn_mov_dpp(v, 0x118, 0xf, 0xf, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);     // row_bcast:15 into rows 1 and 3
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);     // row_bcast:31 into rows 2 and 3
-    return v;
-}
-// LDS traffic between the lanes of ONE wave: order this wave's DS operations (no other wave is involved)
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
 __device__ __forceinline__ unsigned lut_index(int v) { return (unsigned)v < (unsigned)kPackLutSize ? (unsigned)v : (unsigned)kPackLutSize; }
 
 // what the writer emits for one mantissa under `table` (pacfileThem.py:685-703, 742-760): -> (bits, length)
@@ -189,7 +162,7 @@ __global__ __launch_bounds__(256) void pack_scan_apply_kernel(int64_t n, int nch
     int v[4], s = 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) { v[j] = base + j < n ? 4 + chunkBytes[base + j] : 0; s += v[j]; }
-    const int incl = wave_scan_i(s);
+    const int incl = wave_incl_scan(s);
     if ((threadIdx.x & 63) == 63) sWave[threadIdx.x >> 6] = incl;
     __syncthreads();
     long long run = tileSum[blockIdx.x] + (incl - s);
@@ -314,7 +287,7 @@ __global__ __launch_bounds__(kWave * kWavesPerGroup) void pack_write_kernel(
             if (b) code_of(sEmit, tbl, v[j], b, &bits[j], &len[j]);
             run += len[j];
         }
-        const int base = wave_scan_i(run) - run;
+        const int base = wave_incl_scan(run) - run;
         int at = base;
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
@@ -348,7 +321,7 @@ __global__ __launch_bounds__(kWave * kWavesPerGroup) void pack_write_kernel(
         int run = 0;
         const int k0 = lane * lpl, k1 = min(k0 + lpl, M);
         for (int k = k0; k < k1; ++k) { const int t = pref[pad16(k)]; pref[pad16(k)] = run; run += t; }
-        const int incl = wave_scan_i(run);
+        const int incl = wave_incl_scan(run);
         laneBase[lane] = incl - run;
         if (lane == kWave - 1) pref[pad16(M) + 1] = incl;            // the total: the prefix of a band that starts at M
     }

@@ -8,7 +8,7 @@
 //   chunk payloads                pacfileThem.py:716-781, 892-963; bit order of bitpack.py:36-101
 //   file header                   pacfileThem.py:586-613
 // Table ids: sorted table names (percussive 0, silence 1, speech 2, tonal 3), 15 = raw; see DESIGN.md.
-#include "mrc_internal.hpp"
+#include "mrc_huffman_tables.hpp"
 
 #include <sched.h>
 
@@ -21,55 +21,30 @@
 
 namespace {
 
-struct HuffTable {
-    int escape;
-    int nCodes;
-    struct { int value; const char* code; } codes[16];
-};
-
-// training_data/*_table.pkl of the reference, as data (tools/check_huffman_tables.py)
-const HuffTable kTables[4] = {
-    {16, 16, {{0, "0"}, {1, "1110"}, {2, "110"}, {3, "111101"}, {4, "101"}, {5, "1000"}, {6, "111100"},
-              {7, "11111100"}, {8, "10010"}, {9, "111110"}, {10, "1111111"}, {11, "1001101"}, {12, "1001100"},
-              {13, "111111011"}, {14, "111111010"}, {16, "100111"}}},
-    {11, 11, {{0, "11"}, {1, "000"}, {2, "100"}, {3, "00101"}, {4, "01"}, {5, "0011"}, {6, "101101"},
-              {8, "10111"}, {9, "00100"}, {10, "101100"}, {11, "1010"}}},
-    {7, 16, {{0, "11"}, {1, "1001"}, {2, "101"}, {3, "100011"}, {4, "00"}, {5, "0100"}, {6, "100000"},
-             {7, "0101"}, {8, "0111"}, {9, "01101"}, {10, "100001"}, {11, "1000101"}, {12, "0110000"},
-             {16, "011001"}, {17, "1000100"}, {32, "0110001"}}},
-    {7, 16, {{0, "0"}, {1, "11110"}, {2, "110"}, {3, "1111101"}, {4, "101"}, {5, "1001011"}, {6, "11111101"},
-             {7, "1000"}, {8, "1110"}, {9, "1111111"}, {10, "10010100"}, {16, "10011"}, {17, "1111100"},
-             {18, "11111100"}, {32, "100100"}, {64, "10010101"}}},
-};
-constexpr int kRawTable = 15;       // codecThem.py:149
-constexpr int kLutSize = 65;        // largest table value is 64
+using mrc::kHuffTables;
+using mrc::kPackLutSize;
+using mrc::kPackRawTable;
 
 struct Lut {
-    unsigned char len[4][kLutSize];
-    unsigned short bits[4][kLutSize];
+    unsigned char len[4][kPackLutSize];
+    unsigned short bits[4][kPackLutSize];
     // Pricing all four tables in ONE pass over the mantissas: per value two 64-bit words of four 16-bit fields
     // (field t = table t): lenSum[v] = code length, 0 where the table has no code for v; miss[v] = 1 there.
-    // A band's sums stay below 2^16 (<= 1024 lines x 9 bits).  Index kLutSize = "any larger value": in no table.
-    uint64_t lenSum[kLutSize + 1], miss[kLutSize + 1];
+    // A band's sums stay below 2^16 (<= 1024 lines x 9 bits).  Index kPackLutSize = "any larger value": in no table.
+    uint64_t lenSum[kPackLutSize + 1], miss[kPackLutSize + 1];
     // Emission: emit[t][v] = code | length << 16 | (1 << 31 where the raw mantissa follows: escape value / no code)
-    uint32_t emit[4][kLutSize + 1];
+    uint32_t emit[4][kPackLutSize + 1];
     Lut() {
-        std::memset(len, 0, sizeof(len));
-        std::memset(bits, 0, sizeof(bits));
         for (int t = 0; t < 4; ++t)
-            for (int i = 0; i < kTables[t].nCodes; ++i) {
-                const char* c = kTables[t].codes[i].code;
-                unsigned v = 0;
-                int n = 0;
-                for (; c[n]; ++n) v = (v << 1) | (unsigned)(c[n] - '0');
-                len[t][kTables[t].codes[i].value] = (unsigned char)n;
-                bits[t][kTables[t].codes[i].value] = (unsigned short)v;
+            for (int v = 0; v < kPackLutSize; ++v) {
+                len[t][v] = (unsigned char)mrc::huff_code_len(t, v);
+                bits[t][v] = (unsigned short)mrc::huff_code_bits(t, v);
             }
-        for (int v = 0; v <= kLutSize; ++v) {
+        for (int v = 0; v <= kPackLutSize; ++v) {
             lenSum[v] = miss[v] = 0;
             for (int t = 0; t < 4; ++t) {
-                const int esc = kTables[t].escape;
-                const int n = v < kLutSize ? len[t][v] : 0;
+                const int esc = kHuffTables[t].escape;
+                const int n = v < kPackLutSize ? len[t][v] : 0;
                 lenSum[v] |= (uint64_t)n << (16 * t);
                 miss[v] |= (uint64_t)(n == 0) << (16 * t);
                 if (n != 0 && v != esc) emit[t][v] = bits[t][v] | ((uint32_t)n << 16);
@@ -79,7 +54,7 @@ struct Lut {
     }
 };
 const Lut kLut;
-inline unsigned lut_index(int32_t v) { return (uint32_t)v < (uint32_t)kLutSize ? (unsigned)v : (unsigned)kLutSize; }
+inline unsigned lut_index(int32_t v) { return (uint32_t)v < (uint32_t)kPackLutSize ? (unsigned)v : (unsigned)kPackLutSize; }
 
 // MSB-first writer, same byte image as bitpack.py:36-101 (zero-initialised buffer, bits OR-ed in)
 struct BitWriter {
@@ -143,9 +118,9 @@ ChannelPlan plan_channel(const int32_t* ba, const MantT* mant, const std::vector
     int64_t raw = 0;
     for (int b = 0; b < nb; ++b)
         if (ba[b]) raw += (int64_t)ba[b] * nLines[b];
-    ChannelPlan plan{kRawTable, raw, 0};
+    ChannelPlan plan{kPackRawTable, raw, 0};
     if (givenTable >= 0) {                           // the table was chosen elsewhere (huffman_gain_kernel): no pricing
-        if (givenTable != kRawTable) { plan.table = givenTable; plan.mantBits = written_bits(ba, mant, nLines, givenTable); }
+        if (givenTable != kPackRawTable) { plan.table = givenTable; plan.mantBits = written_bits(ba, mant, nLines, givenTable); }
         return plan;
     }
     if (!useHuffman) return plan;
@@ -162,14 +137,14 @@ ChannelPlan plan_channel(const int32_t* ba, const MantT* mant, const std::vector
             }
             for (int t = 0; t < 4; ++t)
                 priced[t] += (int64_t)((lens >> (16 * t)) & 0xffffu) +
-                             (int64_t)((misses >> (16 * t)) & 0xffffu) * (ba[b] + kLut.len[t][kTables[t].escape]);
+                             (int64_t)((misses >> (16 * t)) & 0xffffu) * (ba[b] + kLut.len[t][kHuffTables[t].escape]);
         }
         k += n;
     }
     int64_t best = raw;
     for (int t = 0; t < 4; ++t)
         if (priced[t] < best) { best = priced[t]; plan.table = t; }
-    if (plan.table != kRawTable) plan.mantBits = written_bits(ba, mant, nLines, plan.table);
+    if (plan.table != kPackRawTable) plan.mantBits = written_bits(ba, mant, nLines, plan.table);
     plan.bitsSaved = (int)(raw - best);
     return plan;
 }
@@ -187,7 +162,7 @@ void write_band_records(BitWriter& w, const mrc_config& cfg, const int32_t* sf, 
         const int n = nLines[b];
         if (bits) {
             const MantT* m = mant + k;
-            if (table == kRawTable) {
+            if (table == kPackRawTable) {
                 for (int i = 0; i < n; ++i) w.put((uint32_t)m[i], bits);
             } else {
                 const uint32_t* emit = kLut.emit[table];
@@ -259,8 +234,8 @@ struct DecLut {
         std::memset(len, 0, sizeof(len));
         std::memset(value, 0, sizeof(value));
         for (int t = 0; t < 4; ++t)
-            for (int i = 0; i < kTables[t].nCodes; ++i) {
-                const int v = kTables[t].codes[i].value, n = kLut.len[t][v];
+            for (int i = 0; i < kHuffTables[t].nCodes; ++i) {
+                const int v = kHuffTables[t].codes[i].value, n = kLut.len[t][v];
                 const unsigned head = (unsigned)kLut.bits[t][v] << (kPeekBits - n);
                 for (unsigned tail = 0; tail < (1u << (kPeekBits - n)); ++tail) {
                     value[t][head | tail] = (short)v;
@@ -305,7 +280,7 @@ bool read_band_records(BitReader& r, const mrc_config& cfg, int table, const std
         sf[band] = (int32_t)r.get(cfg.n_scale_bits);
         if (bits) {
             for (int j = 0; j < bandN[band]; ++j) {
-                if (table == kRawTable) {
+                if (table == kPackRawTable) {
                     mant[line + j] = (int32_t)r.get(bits);
                 } else {
                     const unsigned w = r.peek(kPeekBits);
@@ -313,7 +288,7 @@ bool read_band_records(BitReader& r, const mrc_config& cfg, int table, const std
                     if (!n) return false;
                     r.get(n);
                     const int v = kDecLut.value[table][w];
-                    mant[line + j] = (v == kTables[table].escape) ? (int32_t)r.get(bits) : v;
+                    mant[line + j] = (v == kHuffTables[table].escape) ? (int32_t)r.get(bits) : v;
                 }
             }
         }
@@ -329,18 +304,17 @@ inline uint32_t get_u16le(const uint8_t* p) { return p[0] | (p[1] << 8); }
 
 namespace mrc {
 void pack_tables(PackTables* out) {
-    static_assert(kPackLutSize == kLutSize && kPackRawTable == kRawTable, "device and host packer tables");
     for (int t = 0; t < 4; ++t) {
-        for (int v = 0; v <= kLutSize; ++v) out->emit[t * (kLutSize + 1) + v] = kLut.emit[t][v];
-        out->escape[t] = kTables[t].escape;
+        for (int v = 0; v <= kPackLutSize; ++v) out->emit[t * (kPackLutSize + 1) + v] = kLut.emit[t][v];
+        out->escape[t] = kHuffTables[t].escape;
     }
 }
 void unpack_tables(UnpackTables* out) {
-    static_assert(kUnpackPeekBits == kPeekBits && kUnpackRawTable == kRawTable, "device and host parser tables");
+    static_assert(kUnpackPeekBits == kPeekBits && kUnpackRawTable == kPackRawTable, "device and host parser tables");
     for (int t = 0; t < 4; ++t) {
         for (int w = 0; w < (1 << kPeekBits); ++w)
             out->lut[t * (1 << kPeekBits) + w] = (unsigned short)((unsigned)kDecLut.value[t][w] | (unsigned)kDecLut.len[t][w] << 8);
-        out->escape[t] = kTables[t].escape;
+        out->escape[t] = kHuffTables[t].escape;
     }
 }
 }  // namespace mrc
@@ -425,7 +399,7 @@ static int pack_blocks(const mrc_config* cfg, int64_t n, int nch, int a, int b, 
         int given = -1;
         if (huff_table_in) {
             given = huff_table_in[c];
-            if (given != kRawTable && (given < 0 || given > 3)) { badTable.store(1); given = kRawTable; }
+            if (given != kPackRawTable && (given < 0 || given > 3)) { badTable.store(1); given = kPackRawTable; }
         }
         const ChannelPlan plan = plan_channel(bit_alloc + c * nb, mantissa + c * (int64_t)half, nLines, use_huffman, given);
         int64_t bits = 4 + cfg->blksw_bits_a + cfg->blksw_bits_b + (int64_t)nb * (cfg->n_mant_size_bits + cfg->n_scale_bits) +
@@ -604,7 +578,7 @@ int mrc_unpack_blocks(const mrc_config* cfg, int64_t n_blocks, int n_channels, i
             if (off + 4 + nBytes > len) { refuse_chunk(chunk, mrc::kUnpackTruncated); return; }
             BitReader r(buf + off + 4, nBytes);
             const int table = (int)r.get(4);
-            if (table != kRawTable && table > 3) { refuse_chunk(chunk, mrc::kUnpackBadTable); return; }
+            if (table != kPackRawTable && table > 3) { refuse_chunk(chunk, mrc::kUnpackBadTable); return; }
             const int swA = (int)r.get(cfg->blksw_bits_a), swB = (int)r.get(cfg->blksw_bits_b);
             const int a = swA ? cfg->n_short : L, b = swB ? cfg->n_short : L;      // pacfileThem.py:206-207
             if (ch == 0) { a_out[blk] = a; b_out[blk] = b; }

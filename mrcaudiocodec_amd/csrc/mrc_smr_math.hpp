@@ -1,5 +1,5 @@
 // fp64 and wavefront helpers of the masking kernels (mrc_kernels_smr*.hip): order-preserving keys, 2^x by polynomial and by
-// table, double-double sums, wave-wide sums and prefix scans in registers, 1/x, atan, and the table-driven SPL conversion
+// table, double-double sums, wave-wide sums of blocks of values in registers, 1/x, atan, and the table-driven SPL conversion
 // with the two device tables every masking kernel stages (2^(j/64), log10).
 #pragma once
 #include "mrc_device.hpp"
@@ -123,14 +123,9 @@ __device__ __forceinline__ void dd_add(double* hi, double* lo, double xh, double
 //   distance 8, 4, 2, 1: DPP row rotate / half mirror / quad permutes.
 template <int DIST>
 __device__ __forceinline__ double wave_xchg_add(double a, double b) {
-    static_assert(DIST == 32 || DIST == 16, "swap distance");
-    const unsigned alo = (unsigned)__double2loint(a), ahi = (unsigned)__double2hiint(a);
-    const unsigned blo = (unsigned)__double2loint(b), bhi = (unsigned)__double2hiint(b);
-    const uint2v lo = DIST == 32 ? __builtin_amdgcn_permlane32_swap(alo, blo, false, false)
-                                 : __builtin_amdgcn_permlane16_swap(alo, blo, false, false);
-    const uint2v hi = DIST == 32 ? __builtin_amdgcn_permlane32_swap(ahi, bhi, false, false)
-                                 : __builtin_amdgcn_permlane16_swap(ahi, bhi, false, false);
-    return __hiloint2double((int)hi.x, (int)lo.x) + __hiloint2double((int)hi.y, (int)lo.y);
+    double x, y;
+    rows_swap<DIST>(a, b, &x, &y);
+    return x + y;
 }
 // Sum each of 8 per-lane values over the 64 lanes of the wave and leave the 8 totals in every lane (wave-uniform).
 // Transposing butterfly: at distances 32, 16, 8 a lane hands HALF of its remaining values to its partner and adds
@@ -225,31 +220,6 @@ __device__ __attribute__((noinline)) double excess_plain(double t, double a2, in
     const double thr = spl_db_tab(t, tab);
     *thrOut = thr;
     return (spl_db_tab(a2, tab) - 6. * scale) - thr;
-}
-
-// inclusive prefix sum over the 64 lanes, in registers: Kogge-Stone inside each 16-lane row with DPP row shifts (lanes
-// that would read across the row's start get 0), then the row totals are passed on with row_bcast:15 / row_bcast:31
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ int dpp_shift_or_zero(int v) {
-    // all rows enabled: bound_ctrl supplies the zero of lanes without a source; a partial row mask leaves the other
-    // rows' lanes to the prepared zero
-    if (ROW_MASK == 0xf) return __builtin_amdgcn_mov_dpp(v, CTRL, 0xf, 0xf, true);
-    return __builtin_amdgcn_update_dpp(0, v, CTRL, ROW_MASK, 0xf, false);
-}
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_shift_or_zero(double v) {
-    return __hiloint2double(dpp_shift_or_zero<CTRL, ROW_MASK>(__double2hiint(v)),
-                            dpp_shift_or_zero<CTRL, ROW_MASK>(__double2loint(v)));
-}
-template <class T>                                      // int or double
-__device__ __forceinline__ T wave_incl_scan(T v) {
-    v += dpp_shift_or_zero<0x111, 0xf>(v);              // row_shr:1
-    v += dpp_shift_or_zero<0x112, 0xf>(v);              // row_shr:2
-    v += dpp_shift_or_zero<0x114, 0xf>(v);              // row_shr:4
-    v += dpp_shift_or_zero<0x118, 0xf>(v);              // row_shr:8
-    v += dpp_shift_or_zero<0x142, 0xa>(v);              // row_bcast:15 into rows 1 and 3
-    v += dpp_shift_or_zero<0x143, 0xc>(v);              // row_bcast:31 into rows 2 and 3
-    return v;
 }
 
 }  // namespace

@@ -20,14 +20,6 @@ namespace mrc {
 using namespace dev;
 namespace {
 
-// LDS traffic between lanes of ONE wave: order the wave's own DS operations, keep the compiler from
-// moving LDS accesses across this point
-__device__ __forceinline__ void wave_sync_lds() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
 // One masker's table entry {I, z, upper slope in 1/64 bit per Bark} from the sum of its three bins and the numerator of its
 // centre frequency.  OUT OF LINE on purpose: it runs once per unit on at most 13 lanes, and inlined its ~60 polynomial
 // constants would sit in registers across the whole unit loop (145 registers instead of ~100: a wave per SIMD less).
@@ -149,15 +141,15 @@ __global__ __launch_bounds__(kWave * kShortWaves) __attribute__((amdgpu_waves_pe
         const int scale = oscale[unit];
         const double* X = lines + unit * M;
         const double x0 = X[lane], x1 = X[lane + kWave];        // (in flight under the FFT)
-        wave_sync_lds();
+        wave_sync();
         fft_pass<4, true, TwQuarter, kWave>(A, B, H, 1, W, lane);
-        wave_sync_lds();
+        wave_sync();
         fft_pass<4, true, TwQuarter, kWave>(B, A, H, 4, W, lane);
-        wave_sync_lds();
+        wave_sync();
         fft_pass<4, true, TwQuarter, kWave>(A, B, H, 16, W, lane);
-        wave_sync_lds();
+        wave_sync();
         fft_pass<2, true, TwQuarter, kWave>(B, A, H, 64, W, lane);
-        wave_sync_lds();
+        wave_sync();
         if (lane < last) {                               // psychoac.py:147-151: intensity of bins 0 .. 27
             const int k = lane;
             const double2 zz = A[k];
@@ -170,7 +162,7 @@ __global__ __launch_bounds__(kWave * kShortWaves) __attribute__((amdgpu_waves_pe
             Xk.x += ev.x; Xk.y += ev.y;
             xi[k] = (4. * (Xk.x * Xk.x + Xk.y * Xk.y)) * xiInv;
         }
-        wave_sync_lds();
+        wave_sync();
         // tonal maskers: strict 3-point peaks at bins 1 .. 26, in increasing bin order (psychoac.py:160-165)
         const int p = lane;
         double y0 = 0.0, y1 = 0.0, y2 = 0.0;
@@ -184,7 +176,7 @@ __global__ __launch_bounds__(kWave * kShortWaves) __attribute__((amdgpu_waves_pe
             const double fnum = S.binHz * (((p - 1) * y0 + p * y1) + (p + 1) * y2);
             short_masker(s3, fnum, logTab, mt + 4 * idx);
         }
-        wave_sync_lds();
+        wave_sync();
         // psychoac.py:155,166-173: quiet threshold + every masker's spread intensity, in masker order
         double tot0 = qk[0], tot1 = qk[1];
         for (int m = 0; m < nPeaks; ++m) {
@@ -210,14 +202,14 @@ __global__ __launch_bounds__(kWave * kShortWaves) __attribute__((amdgpu_waves_pe
             }
             atomicMax(&peakKey[bnd], (unsigned long long)__double_as_longlong(fabs(x)));
         }
-        wave_sync_lds();
+        wave_sync();
         if (lane < nb) {
             double v = bandKey[lane] ? order_value(bandKey[lane]) : -1e300;
             if (ratioKey[lane]) v = fmax(v, short_band_db(__longlong_as_double((long long)ratioKey[lane]), scale, logTab));
             smr[unit * nb + lane] = v;
             bandPeak[unit * nb + lane] = __longlong_as_double((long long)peakKey[lane]);
         }
-        wave_sync_lds();                                // keys read before the next unit clears them
+        wave_sync();                                // keys read before the next unit clears them
     }
 }
 

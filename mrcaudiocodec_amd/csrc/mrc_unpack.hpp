@@ -40,7 +40,7 @@ enum UnpackStatus : int {
     kUnpackBadShape = 5,        // shape without a band table, or not the shape the caller expects / the block's other chunk has
 };
 
-// Decode tables: derived from the table data of mrc_pack.cpp (mrc::unpack_tables)
+// Decode tables: derived from mrc_huffman_tables.hpp by mrc_pack.cpp (mrc::unpack_tables)
 struct UnpackTables {
     unsigned short lut[kUnpackLutEntries];
     int escape[4];
