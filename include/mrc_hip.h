@@ -806,7 +806,7 @@ int mrc_pac_store_info(mrc_pac_store* s, int64_t* n_files, int32_t* n_channels /
  * (the item is named).  window == 0 or n_items == 0: MRC_OK, nothing written.  The call enqueues on `stream` (NULL: the
  * handle's) and synchronises it before it returns, because the parser's error word comes back.  A call is cut into slabs
  * of whole items (MRC_OPT_STORE_SLAB_SAMPLES); the workspace is the handle's, sized by the slab and reused.
- * mrc_pac_store_stats, for the store's last mrc_pac_store_decode_window(_reduced): stats = chunks parsed, decode_kernel launches,
+ * mrc_pac_store_stats, for the store's last mrc_pac_store_decode_window(_reduced, _mix): stats = chunks parsed, decode_kernel launches,
  * slabs, bytes of plan uploaded (no file bytes among them); ms = device time of the plan upload, the unpack kernel, the
  * synthesis (zeroing the planes + decode_kernel launches) and window_out_kernel, summed over the slabs. */
 int mrc_pac_store_decode_window(mrc_pac_store* s, int64_t n_items, const int64_t* file /*[n_items]*/,
@@ -836,6 +836,33 @@ int mrc_pac_store_stats(mrc_pac_store* s, int64_t* stats /*[4]*/, double* ms /*[
 int mrc_pac_store_decode_window_reduced(mrc_pac_store* s, int rate_divisor, int64_t n_items, const int64_t* file /*[n_items]*/,
                                         const int64_t* start /*[n_items]*/, int64_t window, int n_channels_out, int format,
                                         void* out /* DEVICE [n_items][n_channels_out][window] */, void* stream);
+/* mrc_pac_store_decode_window_mix: ONE channel of every item, whatever its file's channel count -- out[i][0][t] -- at
+ * 1 / rate_divisor of the sample rate.  Everything not named here is mrc_pac_store_decode_window_reduced's under this
+ * function's name: coordinates, rate_divisor 1 / 2 / 4 and its shape refusals, zeros outside the file, the overlap rule,
+ * damage inside or outside a window, slabs, the stream, the three formats, mrc_pac_store_stats.
+ * A mono file gives its one channel for every mix: the bits of the one-channel call at that divisor.
+ * MRC_MIX_LEFT / MRC_MIX_RIGHT of a stereo file: bit-identical, in all three formats, to channel 0 / 1 of the two-channel
+ * call at that divisor (each sample is the same at most two contributions added to zero).
+ * MRC_MIX_MID of a stereo file is defined on the MDCT lines, before the inverse transform.  With l1, l2 the two streams'
+ * dequantised lines of a joint block, each divided by its overall scale level: line k of the mid is l1 where the band's M/S
+ * switch is set (the first stream IS (L + R) / 2; the side stream of such a band is not dequantised) and 0.5 * (l1 + l2)
+ * where it is not; for the file's last block, whose two chunks are not joint, 0.5 * (x0 + x1) of the two channels' lines.
+ * One inverse transform, window and overlap-add per block follow: MRC_WINDOW_F64 is that plane -- the mean of the two
+ * channels' planes up to rounding, the transform being linear -- MRC_WINDOW_F32 and MRC_WINDOW_PCM16 conversions of it (the
+ * 16-bit code is that of the float64 mid, not the mean of two codes).  An item's result does not depend on its company,
+ * the order, the slab size or how a window is cut.
+ * Work per needed block of a stereo file: one synthesis workgroup, not two; one margin plane per item.  A joint block has
+ * both chunks parsed for every mix (the M/S switches and both streams are needed even for left); the last block of a
+ * stereo file has two chunks parsed for MRC_MIX_MID and ONE for left / right -- the other channel's chunk is not in the
+ * plan, so damage in it goes unnoticed.  chunks_parsed counts accordingly.
+ * mix outside {0, 1, 2}: MRC_ERR_INVALID naming mix and its value, before any device work (out untouched).  The refusal
+ * of a stereo file in a one-channel call of the two calls above is theirs alone and stays. */
+#define MRC_MIX_MID   0   /* (L + R) / 2 */
+#define MRC_MIX_LEFT  1
+#define MRC_MIX_RIGHT 2
+int mrc_pac_store_decode_window_mix(mrc_pac_store* s, int rate_divisor, int mix, int64_t n_items, const int64_t* file /*[n_items]*/,
+                                    const int64_t* start /*[n_items]*/, int64_t window, int format,
+                                    void* out /* DEVICE [n_items][1][window] */, void* stream);
 /* mrc_synthesis_shape: the rule above for one block shape (a, b) and divisor, on the host alone (no handle, no device):
  * MRC_OK if blocks of shape (a, b) have a synthesis shape (a, b) / rate_divisor, else MRC_ERR_INVALID with the reason, the
  * divisor and the shape in mrc_last_error(NULL).  rate_divisor is any positive number here: 1 asks whether (a, b) itself

@@ -25,6 +25,10 @@ and synthesised.  --start defaults to 0, --samples to the rest of the file; what
 At half or quarter rate:  python -m mrcaudiocodec_amd.cli -d in.pac out.wav --rate-divisor 2  (or 4) decodes through the same
 store straight from the MDCT lines (mrc_pac_store_decode_window_reduced): the WAV's header carries sample_rate // D, and
 --start / --samples then count samples at that rate.  Refused when D does not divide the file's sample rate.
+One channel:  python -m mrcaudiocodec_amd.cli -d in.pac out.wav --mix mid  (or left, right) writes a one-channel WAV through
+the same store (mrc_pac_store_decode_window_mix): the mid (L + R) / 2 of a stereo file, formed on the MDCT lines before the
+one inverse transform, or its left or right channel; a mono file gives its channel.  Composes with --rate-divisor, --start
+and --samples.
 
 Quality (mrc_pac_nmr): --nmr on an encode prints, per file written (every rung of a ladder), one JSON line with the
 noise-to-mask ratio of the file against the WAV, measured with the codec's own masking model: nmr_max_db (worst band),
@@ -403,19 +407,33 @@ def check_rate_divisor_args(rate_divisor, decode):
     return int(rate_divisor)
 
 
-def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=1):
+def check_mix_args(mix, decode):
+    """--mix as given (None: not given) -> "mid", "left", "right" or None.  It picks one channel of a decode: refused
+    without -d, and any other word is refused."""
+    if mix is None:
+        return None
+    if not decode:
+        raise ValueError("--mix decodes one channel of a stereo file: it needs -d")
+    if mix not in ("mid", "left", "right"):
+        raise ValueError("--mix: %r is not mid, left or right" % (mix,))
+    return mix
+
+
+def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=1, mix=None):
     """excerpt: None (the whole file, mrc_decode_pac_pcm16) or (start, samples): that many samples from sample `start` on
     (samples None: to the end of the file), decoded through a one-file PacStore -- only the blocks the excerpt overlaps are
     parsed and synthesised; what lies outside the file is silence.  rate_divisor 2 or 4: at that fraction of the sample rate,
     through the store as well (excerpt None: the whole file); start and samples count samples at the reduced rate, which the
-    WAV's header carries.  -> int16 [nCh][samples] as written."""
+    WAV's header carries.  mix "mid", "left" or "right": a one-channel WAV of that channel (mid: (L + R) / 2, formed on the
+    MDCT lines), through the store as well.  -> int16 [nCh][samples] as written."""
     with open(pac_path, "rb") as fp:
         buf = fp.read()
     cfg, _, _, _ = pacfile.read_header(buf)
     rate_divisor = check_rate_divisor_args(rate_divisor, True)
     if cfg.sample_rate % rate_divisor:
         raise ValueError("--rate-divisor %d does not divide the file's sample rate, %d Hz" % (rate_divisor, cfg.sample_rate))
-    if rate_divisor != 1 and excerpt is None:
+    mix = check_mix_args(mix, True)
+    if (rate_divisor != 1 or mix is not None) and excerpt is None:
         excerpt = (0, None)
     h = Handle(sample_rate=cfg.sample_rate, n_mdct_lines=cfg.n_mdct_lines, n_scale_bits=cfg.n_scale_bits,
                n_mant_size_bits=cfg.n_mant_size_bits, device_id=device_id)
@@ -428,7 +446,7 @@ def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=
                 start, samples = excerpt
                 if samples is None:
                     samples = max(0, int(store.n_samples_at(rate_divisor)[0]) - start)
-                inter = np.ascontiguousarray(store.decode_window([0], [start], samples, rate_divisor=rate_divisor)[0].cpu().numpy().T)
+                inter = np.ascontiguousarray(store.decode_window([0], [start], samples, rate_divisor=rate_divisor, mix=mix)[0].cpu().numpy().T)
     finally:
         h.close()
     data = inter.astype("<i2", copy=False)
@@ -550,11 +568,15 @@ def main(argv=None):
     ap.add_argument("--rate-divisor", type=int, default=None, metavar="D",
                     help="with -d: decode at 1/D of the sample rate (D = 2 or 4) straight from the MDCT lines; the WAV says "
                          "sample_rate // D, and --start / --samples count samples at that rate")
+    ap.add_argument("--mix", default=None, metavar="CH",
+                    help="with -d: write a one-channel WAV, CH = mid ((L + R) / 2 of a stereo file, formed on the MDCT lines), "
+                         "left or right; composes with --rate-divisor, --start and --samples")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(_join_vbr_grid(sys.argv[1:] if argv is None else argv))
     try:
         excerpt = check_excerpt_args(a.start, a.samples, a.decode)
         rate_divisor = check_rate_divisor_args(a.rate_divisor, a.decode)
+        mix = check_mix_args(a.mix, a.decode)
     except ValueError as e:
         ap.error(str(e))
     if a.vbr_bytes is not None or a.vbr_bits_per_sample is not None or a.vbr_grid is not None:
@@ -601,7 +623,7 @@ def main(argv=None):
         return
     if a.decode:
         try:
-            pcm = decode_pac_file(a.src, a.dst, a.device, excerpt, rate_divisor)
+            pcm = decode_pac_file(a.src, a.dst, a.device, excerpt, rate_divisor, mix)
         except ValueError as e:
             ap.error(str(e))
         print("%s: %d channels x %d samples" % (a.dst, pcm.shape[0], pcm.shape[1]))

@@ -26,6 +26,13 @@
 // call is refused).  The parser is untouched (a chunk's bits are sequential: every mantissa is parsed); decode_reduced_kernel
 // dequantises the first 1 / D of a block's lines and runs the inverse transform of the shape (a, b) / D.  One function,
 // decode_windows, holds the arithmetic for every D.
+//
+// decode_window_mix, one channel of every item (left, right or the mid (L + R) / 2): the same plan with ONE plane per item
+// and one workgroup per needed block (decode_mix_kernel, its selector an argument).  A joint block keeps its slot of two
+// chunks -- the M/S switches and both streams are needed even for left.  The non-joint last block of a stereo file is one
+// single slot for left / right (the other channel's chunk is not in the plan) and for mid a PAIR: two neighbouring slots
+// of the non-joint group, which laid side by side are one slot of two streams, the group's pairs in front of its single
+// slots so that a workgroup finds its slot from its index alone.  pac_plan_layout sees slot counts as ever.
 #include "mrc_handle.hpp"
 
 #include <algorithm>
@@ -38,6 +45,8 @@ namespace {
 
 const char* const kWin = "mrc_pac_store_decode_window";
 const char* const kWinReduced = "mrc_pac_store_decode_window_reduced";
+const char* const kWinMix = "mrc_pac_store_decode_window_mix";
+constexpr int kNoMix = -1;                           // decode_windows: every channel of a file into a plane of its own
 
 int store_alive(mrc_pac_store* s, const char* fn) {
     if (!s) return fail(nullptr, MRC_ERR_INVALID, std::string(fn) + ": null store");
@@ -134,14 +143,18 @@ int mrc_pac_store_info(mrc_pac_store* s, int64_t* n_files, int32_t* n_channels, 
 
 namespace {
 
-// both decode_window calls: fn the entry point's name, D the rate divisor (1: full rate, decode_kernel)
-int decode_windows(mrc_pac_store* s, const char* fn, int D, int64_t n_items, const int64_t* file, const int64_t* start,
+// all decode_window calls: fn the entry point's name, D the rate divisor (1: full rate, decode_kernel), mixArg null or the
+// caller's MRC_MIX_* (one plane per item, decode_mix_kernel; n_channels_out is then 1)
+int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, int64_t n_items, const int64_t* file, const int64_t* start,
                    int64_t window, int n_channels_out, int format, void* out, void* stream) {
     MRC_TRY(store_alive(s, fn));
     mrc_handle* h = s->h;
     const mrc_config& cfg = h->cfg;
     const std::string w = fn;
     for (int i = 0; i < 4; ++i) { s->stats[i] = 0; s->ms[i] = 0.0; }
+    const int mix = mixArg ? *mixArg : kNoMix;
+    if (mixArg && mix != MRC_MIX_MID && mix != MRC_MIX_LEFT && mix != MRC_MIX_RIGHT)
+        return fail(h, MRC_ERR_INVALID, w + ": mix " + std::to_string(mix) + " is not MRC_MIX_MID (0), MRC_MIX_LEFT (1) or MRC_MIX_RIGHT (2)");
     if (D != 1 && D != 2 && D != 4) return fail(h, MRC_ERR_INVALID, w + ": rate_divisor " + std::to_string(D) + " is not 1, 2 or 4");
     for (int sh = 0; D > 1 && sh < 4; ++sh) {
         int a, b;
@@ -161,7 +174,7 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, int64_t n_items, con
         if (file[k] < 0 || file[k] >= nFiles)
             return fail(h, MRC_ERR_INVALID, w + ": file[" + std::to_string(k) + "] = " + std::to_string(file[k]) + " is outside the store's " +
                                                 std::to_string(nFiles) + " files");
-        if (s->index.files[(size_t)file[k]].nch > n_channels_out)
+        if (mix == kNoMix && s->index.files[(size_t)file[k]].nch > n_channels_out)
             return fail(h, MRC_ERR_INVALID, w + ": item " + std::to_string(k) + ": file " + std::to_string(file[k]) +
                                                 " is stereo, the call asks for one channel");
     }
@@ -182,6 +195,8 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, int64_t n_items, con
     std::vector<Need> needs;
     std::vector<WindowItem> items;
     std::vector<int64_t> planFile;
+    // chunks of a needed non-joint block that are parsed: all of the file's, but under left / right the one asked for
+    const auto lastChunks = [mix](int nch) { return mix == MRC_MIX_LEFT || mix == MRC_MIX_RIGHT ? 1 : nch; };
     PacPlan pl;                                              // (its group fields: the slab's slots)
     for (int64_t first = 0, last; first < n_items; first = last) {
         last = first + 1;
@@ -200,8 +215,9 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, int64_t n_items, con
             needed_blocks(*s, cfg, D, k, f, start[first + k], window, &needs);
             if (needs.size() == before) continue;            // all zeros: its plane does not exist
             const PacFilePlan& fi = s->index.files[(size_t)f];
-            items[(size_t)k] = WindowItem{planeDoubles, start[first + k], std::max<int64_t>(0, fi.total - cfg.n_mdct_lines) / D, fi.nch, 0};
-            planeDoubles += fi.nch * planeLen;
+            const int nPlanes = mix == kNoMix ? fi.nch : 1;
+            items[(size_t)k] = WindowItem{planeDoubles, start[first + k], std::max<int64_t>(0, fi.total - cfg.n_mdct_lines) / D, nPlanes, 0};
+            planeDoubles += nPlanes * planeLen;
         }
         if (needs.empty()) {                                 // nothing to decode: zeros, no launch
             MRC_HIP(h, hipMemsetAsync(outSlab, 0, (size_t)nSlab * n_channels_out * window * elem, st));
@@ -209,10 +225,17 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, int64_t n_items, con
         }
         for (int64_t k = 0; k < 2 * kUnpackGroups; ++k) pl.nCat[k] = 0;
         for (int g = 0; g < kUnpackGroups; ++g) pl.nSlots[g] = 0;
+        // mid: the two chunks of a stereo file's last block are a PAIR of neighbouring slots of the non-joint group, the
+        // pairs in front of the group's single slots (launch_decode_mix)
+        int64_t nPairs[kUnpackGroups] = {};
         for (const Need& n : needs) {
-            const int nch = s->index.files[(size_t)n.file].nch, sh = s->index.shape(n.file, n.block);
+            const int nch = lastChunks(s->index.files[(size_t)n.file].nch), sh = s->index.shape(n.file, n.block);
             if (n.block < s->index.nJoint(n.file)) { pl.nSlots[sh * 2] += 1; pl.nCat[sh * 4] += 1; pl.nCat[sh * 4 + 1] += 1; }
-            else { pl.nSlots[sh * 2 + 1] += nch; pl.nCat[sh * 4 + 2] += nch; }
+            else {
+                pl.nSlots[sh * 2 + 1] += nch;
+                pl.nCat[sh * 4 + 2] += nch;
+                if (mix == MRC_MIX_MID && nch == 2) nPairs[sh * 2 + 1] += 1;
+            }
         }
         MRC_TRY(pac_plan_layout(h, fn, &pl));
         const HostShape* reduced[4] = {};
@@ -237,8 +260,9 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, int64_t n_items, con
         std::memcpy(pin + oItems, items.data(), sizeof(WindowItem) * nSlab);
         pac_plan_group_descs(d, pl, gd, b.groups.as<unsigned char>());
         planFile.assign((size_t)nChunks, 0);
-        int64_t catPos[2 * kUnpackGroups], slotNext[kUnpackGroups] = {};
+        int64_t catPos[2 * kUnpackGroups], slotNext[kUnpackGroups] = {}, pairNext[kUnpackGroups] = {};
         for (int64_t k = 0, q = 0; k < 2 * kUnpackGroups; q += pl.nCat[k], ++k) catPos[k] = q;
+        for (int g = 0; g < kUnpackGroups; ++g) slotNext[g] = 2 * nPairs[g];      // (joint groups, and every group without mid: 0)
         for (const Need& n : needs) {
             const PacFilePlan& fi = s->index.files[(size_t)n.file];
             const WindowItem& it = items[(size_t)n.item];
@@ -254,12 +278,15 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, int64_t n_items, con
                 }
                 offs[pl.slotBase[g] + slot] = at;
             } else {
-                const int g = sh * 2 + 1;
-                for (int ch = 0; ch < fi.nch; ++ch) {
-                    const int slot = (int)slotNext[g]++;
+                const int g = sh * 2 + 1, nParsed = lastChunks(fi.nch), ch0 = fi.nch == 2 && mix == MRC_MIX_RIGHT ? 1 : 0;
+                const bool pair = mix == MRC_MIX_MID && fi.nch == 2;
+                if (pair) offs[pl.slotBase[g] + pairNext[g] / 2] = at;
+                for (int ch = ch0; ch < ch0 + nParsed; ++ch) {
+                    const int slot = (int)(pair ? pairNext[g]++ : slotNext[g]++);
                     planFile[(size_t)catPos[sh * 4 + 2]] = n.file;
                     plan[catPos[sh * 4 + 2]++] = UnpackPlanEntry{s->index.chunkOff[(size_t)c0 + ch], g * 2, slot};
-                    offs[pl.slotBase[g] + slot] = at + ch * planeLen;
+                    // a single slot's workgroup comes after the group's pairs; without a mix a channel has a plane of its own
+                    if (!pair) offs[pl.slotBase[g] + slot - nPairs[g]] = at + (mix == kNoMix ? ch * planeLen : 0);
                 }
             }
         }
@@ -293,7 +320,11 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, int64_t n_items, con
             if (!pl.nSlots[g]) continue;
             const UnpackGroupDev& G = gd[g];
             const int64_t* offsDev = (const int64_t*)(din + oOffs) + pl.slotBase[g];
-            if (D == 1)
+            if (mix != kNoMix)
+                MRC_HIP(h, launch_decode_mix(pl.hs[g / 2]->dev, D == 1 ? nullptr : &reduced[g / 2]->dev, pl.nSlots[g] - nPairs[g], G.joint,
+                                             mix == MRC_MIX_MID ? 2 : mix == MRC_MIX_LEFT ? 0 : 1, nPairs[g], G.oscale,
+                                             G.joint ? G.ms : nullptr, G.sf, G.ba, G.mant, offsDev, x, st));
+            else if (D == 1)
                 MRC_HIP(h, launch_decode(pl.hs[g / 2]->dev, pl.nSlots[g], G.joint ? 2 : 1, G.oscale, G.joint ? G.ms : nullptr, G.sf,
                                          G.ba, G.mant, offsDev, x, G.joint ? x + planeLen : nullptr, st));
             else
@@ -324,13 +355,18 @@ extern "C" {
 
 int mrc_pac_store_decode_window(mrc_pac_store* s, int64_t n_items, const int64_t* file, const int64_t* start, int64_t window,
                                 int n_channels_out, int format, void* out, void* stream) {
-    return decode_windows(s, kWin, 1, n_items, file, start, window, n_channels_out, format, out, stream);
+    return decode_windows(s, kWin, 1, nullptr, n_items, file, start, window, n_channels_out, format, out, stream);
 }
 
 int mrc_pac_store_decode_window_reduced(mrc_pac_store* s, int rate_divisor, int64_t n_items, const int64_t* file,
                                         const int64_t* start, int64_t window, int n_channels_out, int format, void* out,
                                         void* stream) {
-    return decode_windows(s, kWinReduced, rate_divisor, n_items, file, start, window, n_channels_out, format, out, stream);
+    return decode_windows(s, kWinReduced, rate_divisor, nullptr, n_items, file, start, window, n_channels_out, format, out, stream);
+}
+
+int mrc_pac_store_decode_window_mix(mrc_pac_store* s, int rate_divisor, int mix, int64_t n_items, const int64_t* file,
+                                    const int64_t* start, int64_t window, int format, void* out, void* stream) {
+    return decode_windows(s, kWinMix, rate_divisor, &mix, n_items, file, start, window, 1, format, out, stream);
 }
 
 int mrc_synthesis_shape(int a, int b, int rate_divisor) {

@@ -50,5 +50,20 @@ __device__ __forceinline__ double decode_line(int k, int band, int ch, bool join
     return x;
 }
 
+// Line k of the MID (L + R) / 2 of a joint block (the store's mix windows, decode_mix_kernel): where the band's M/S switch
+// is set the first stream IS the mid and the side stream is not dequantised at all; elsewhere 0.5 * (l1 + l2), l1 and l2
+// as above.  (By linearity the inverse transform of these lines is the mean of the two channels' signals.)
+__device__ __forceinline__ double decode_line_mid(int k, int band, int nb, int M, int nScaleBits, const int* __restrict__ os,
+                                                  const int* __restrict__ ms, const int* __restrict__ sf,
+                                                  const int* __restrict__ ba, const int* __restrict__ mant) {
+    const bool isMs = ms[band] == 1;
+    const int b0 = ba[band];
+    const double l1 = b0 ? ldexp(dequantize_dev(sf[band], mant[k], nScaleBits, b0), -(isMs ? os[2] : os[0])) : 0.0;
+    if (isMs) return l1;
+    const int b1 = ba[nb + band];
+    const double l2 = b1 ? ldexp(dequantize_dev(sf[nb + band], mant[M + k], nScaleBits, b1), -os[1]) : 0.0;
+    return 0.5 * (l1 + l2);
+}
+
 }  // namespace dev
 }  // namespace mrc

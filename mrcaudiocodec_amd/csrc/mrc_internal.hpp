@@ -147,6 +147,14 @@ hipError_t launch_pcm16(int64_t n, const double* x, short* out, hipStream_t st);
 hipError_t launch_decode_reduced(const DevShape& F, const DevShape& R, int64_t nBlocks, int nStreams, const int* oscale,
                                  const int* msSwitch, const int* scaleFactor, const int* bitAlloc, const int* mantissa,
                                  const int64_t* outOffset, double* outL, double* outR, hipStream_t st);
+// One output plane per block instead of one per channel (mrc_pac_store_decode_window_mix): one workgroup per joint slot
+// writes its L (mixSel 0), R (1) or mid (L + R) / 2 (2; formed on the lines, decode_line_mid).  A non-joint group holds
+// nPairs pairs of slots first -- slots 2 w, 2 w + 1 are the two channels of a stereo file's last block, workgroup w writes
+// their mid -- and single slots after them, nWorkgroups - nPairs of them, each written as it is.  R: the reduced shape of
+// launch_decode_reduced, null at full rate.  outOffset [nWorkgroups]: per workgroup, not per slot.
+hipError_t launch_decode_mix(const DevShape& F, const DevShape* R, int64_t nWorkgroups, int joint, int mixSel, int64_t nPairs,
+                             const int* oscale, const int* msSwitch, const int* scaleFactor, const int* bitAlloc,
+                             const int* mantissa, const int64_t* outOffset, double* out, hipStream_t st);
 // mrc_kernels_pack.hip -- `.pac` chunk packing on the device
 constexpr int kPackLutSize = 65;     // the largest value in any Huffman table is 64
 constexpr int kPackRawTable = 15;    // codecThem.py:149

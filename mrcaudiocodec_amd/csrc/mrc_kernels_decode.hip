@@ -10,6 +10,8 @@
 //     an unfold) -> transition window (window.py:104-121) -> atomic add into the output stream at the block's
 //     offset.  Every output sample receives at most two contributions and a + b == b + a, so the result does not
 //     depend on the order in which blocks finish.
+//   decode_mix_kernel, decode_reduced_mix_kernel   one workgroup per block into ONE plane: its left or right channel, or
+//     the mid (L + R) / 2 formed on the lines before the one inverse transform (decode_line_mid; the store's mix windows).
 //   decode_reduced_kernel   the same block at 1 / D of its sample rate: its first halfN / D lines through the inverse
 //     transform of the shape (a, b) / D (the resident store's reduced windows, mrc_api_store.cpp).
 //   pcm16_kernel    |x| -> 16-bit magnitude code (quantize.py:61-87) with the sign re-applied as 2's complement.
@@ -22,32 +24,49 @@ namespace mrc {
 using namespace dev;
 namespace {
 
-// One (block, output channel).  S: the shape whose transform, window and LDS layout are used; the parsed arrays are those
+// One block into one output plane.  S: the shape whose transform, window and LDS layout are used; the parsed arrays are those
 // of a block of nb bands and lineStride lines per stream with the band table bandOfLine, of which the first S.halfN lines
 // are dequantised.  decode_kernel: all of them S's own.  decode_reduced_kernel: the block's full shape, S its reduced one.
+// f: the block's slot in the parsed arrays (joint: two streams per slot, else one).  sel: what the plane receives --
+// 0 / 1: output channel L / R (a non-joint slot has one channel: itself); kSelMid: (L + R) / 2 on the lines, which for a
+// non-joint slot means the PAIR of slots f, f + 1, a stereo file's last block (its two chunks side by side are laid out
+// as one slot of two streams, each with its own overall scale).  out: the plane, at the block's first sample.
+// kMix false: sel is a channel, and the two-plane kernels hold no code for the mid.
+constexpr int kSelMid = 2;
+template <bool kMix>
 __device__ __forceinline__ void decode_block(const DevShape& S, const unsigned char* __restrict__ bandOfLine, int nb,
-                                             int lineStride, int nScaleBits, int nStreams, const int* __restrict__ oscale,
-                                             const int* __restrict__ msSwitch, const int* __restrict__ scaleFactor,
-                                             const int* __restrict__ bitAlloc, const int* __restrict__ mantissa,
-                                             const int64_t* __restrict__ outOffset, double* __restrict__ outL,
-                                             double* __restrict__ outR, double* smem) {
+                                             int lineStride, int nScaleBits, bool joint, int64_t f, int sel,
+                                             const int* __restrict__ oscale, const int* __restrict__ msSwitch,
+                                             const int* __restrict__ scaleFactor, const int* __restrict__ bitAlloc,
+                                             const int* __restrict__ mantissa, double* __restrict__ out, double* smem) {
     const int tid = threadIdx.x;
     const int N = S.N, M = S.halfN, Q = S.Q;
-    const int64_t f = blockIdx.x / nStreams;
-    const int ch = blockIdx.x % nStreams;
+    const int nStreams = joint ? 2 : 1;
     double* v = smem;                                   // [M] lines, later the DCT-IV output; [M, N) unused
     double2* A = (double2*)(smem + N);                  // [Q]
     double2* B = A + Q;                                 // [Q]
-    const bool joint = nStreams == 2;
     const int* sf = scaleFactor + f * nStreams * nb;
     const int* ba = bitAlloc + f * nStreams * nb;
     const int* mant = mantissa + f * nStreams * (int64_t)lineStride;
     const int* os = oscale + f * (joint ? 4 : 1);
+    const int* ms = joint ? msSwitch + f * nb : nullptr;
 
-    // dequantise, undo the overall scale (codecThem.py:47-51, 92-109), rebuild L / R (ms_stereo.py:33-49)
-    for (int k = tid; k < M; k += kThreads)
-        v[k] = decode_line(k, bandOfLine[k], ch, joint, nb, lineStride, nScaleBits, os, joint ? msSwitch + f * nb : nullptr, sf,
-                           ba, mant);
+    // dequantise, undo the overall scale (codecThem.py:47-51, 92-109), rebuild L / R (ms_stereo.py:33-49) or the mid
+    if (!kMix || sel != kSelMid) {
+        for (int k = tid; k < M; k += kThreads)
+            v[k] = decode_line(k, bandOfLine[k], sel, joint, nb, lineStride, nScaleBits, os, ms, sf, ba, mant);
+    } else if (joint) {
+        for (int k = tid; k < M; k += kThreads)
+            v[k] = decode_line_mid(k, bandOfLine[k], nb, lineStride, nScaleBits, os, ms, sf, ba, mant);
+    } else {
+        for (int k = tid; k < M; k += kThreads) {
+            const int band = bandOfLine[k];
+            const double x0 = decode_line(k, band, 0, false, nb, lineStride, nScaleBits, os, nullptr, sf, ba, mant);
+            const double x1 = decode_line(k, band, 0, false, nb, lineStride, nScaleBits, os + 1, nullptr, sf + nb, ba + nb,
+                                          mant + lineStride);
+            v[k] = 0.5 * (x0 + x1);
+        }
+    }
     __syncthreads();
     // DCT-IV of the lines through the N/4-point FFT (same pairing and twiddles as the forward kernel)
     for (int n = tid; n < Q; n += kThreads) A[n] = cmul(make_double2(v[2 * n], v[M - 1 - 2 * n]), S.pre[n]);
@@ -61,7 +80,6 @@ __device__ __forceinline__ void decode_block(const DevShape& S, const unsigned c
     __syncthreads();
     // unfold M -> N (transpose of the forward fold), undo the signed circular shift, x = 2 y (mdct.py:121 scales by N
     // what its normalised inverse FFT divided by N; the remaining factor is the 2 of the definition), window, add
-    double* out = (ch == 0 ? outL : outR) + outOffset[f];
     const int h = Q;
     for (int i = tid; i < N; i += kThreads) {
         int m = i + S.shift;
@@ -77,6 +95,21 @@ __device__ __forceinline__ void decode_block(const DevShape& S, const unsigned c
     }
 }
 
+// workgroup -> (block, output channel) of the two-plane launches: one workgroup per stream of every slot
+struct BlockChannel { int64_t f; int ch; };
+__device__ __forceinline__ BlockChannel block_channel(int nStreams) {
+    return BlockChannel{(int64_t)(blockIdx.x / nStreams), (int)(blockIdx.x % nStreams)};
+}
+// workgroup w -> slot of the one-plane (mix) launches.  Joint group: slot w.  Non-joint group: its first 2 nPairs slots are
+// the pairs (workgroup w < nPairs: slots 2 w, 2 w + 1, their mid), the rest single slots (a mono file's block, or the one
+// parsed channel of a stereo file's last block).  outOffset is indexed by the workgroup.
+__device__ __forceinline__ void mix_slot(bool joint, int mixSel, int64_t nPairs, int64_t* f, int* sel) {
+    const int64_t w = blockIdx.x;
+    if (joint) { *f = w; *sel = mixSel; }
+    else if (w < nPairs) { *f = 2 * w; *sel = kSelMid; }
+    else { *f = w + nPairs; *sel = 0; }
+}
+
 __global__ __launch_bounds__(kThreads) void decode_kernel(DevShape S, int nStreams, const int* __restrict__ oscale,
                                                           const int* __restrict__ msSwitch,
                                                           const int* __restrict__ scaleFactor,
@@ -85,8 +118,26 @@ __global__ __launch_bounds__(kThreads) void decode_kernel(DevShape S, int nStrea
                                                           const int64_t* __restrict__ outOffset,
                                                           double* __restrict__ outL, double* __restrict__ outR) {
     extern __shared__ double smem[];
-    decode_block(S, S.bandOfLine, S.nBands, S.halfN, S.nScaleBits, nStreams, oscale, msSwitch, scaleFactor, bitAlloc, mantissa,
-                 outOffset, outL, outR, smem);
+    const BlockChannel bc = block_channel(nStreams);
+    decode_block<false>(S, S.bandOfLine, S.nBands, S.halfN, S.nScaleBits, nStreams == 2, bc.f, bc.ch, oscale, msSwitch, scaleFactor,
+                 bitAlloc, mantissa, (bc.ch == 0 ? outL : outR) + outOffset[bc.f], smem);
+}
+
+// ... one plane per item (the store's mix windows): one workgroup per joint slot, pair or single slot (mix_slot)
+__global__ __launch_bounds__(kThreads) void decode_mix_kernel(DevShape S, int joint, int mixSel, int64_t nPairs,
+                                                              const int* __restrict__ oscale,
+                                                              const int* __restrict__ msSwitch,
+                                                              const int* __restrict__ scaleFactor,
+                                                              const int* __restrict__ bitAlloc,
+                                                              const int* __restrict__ mantissa,
+                                                              const int64_t* __restrict__ outOffset,
+                                                              double* __restrict__ out) {
+    extern __shared__ double smem[];
+    int64_t f;
+    int sel;
+    mix_slot(joint != 0, mixSel, nPairs, &f, &sel);
+    decode_block<true>(S, S.bandOfLine, S.nBands, S.halfN, S.nScaleBits, joint != 0, f, sel, oscale, msSwitch, scaleFactor, bitAlloc,
+                 mantissa, out + outOffset[blockIdx.x], smem);
 }
 
 // The block at 1 / D of its sample rate (the store's reduced windows): the first R.halfN = halfN / D of its lines through
@@ -105,8 +156,27 @@ __global__ __launch_bounds__(kThreads) void decode_reduced_kernel(DevShape R, co
                                                                   const int64_t* __restrict__ outOffset,
                                                                   double* __restrict__ outL, double* __restrict__ outR) {
     extern __shared__ double smem[];
-    decode_block(R, bandOfLine, nb, fullLines, nScaleBits, nStreams, oscale, msSwitch, scaleFactor, bitAlloc, mantissa, outOffset,
-                 outL, outR, smem);
+    const BlockChannel bc = block_channel(nStreams);
+    decode_block<false>(R, bandOfLine, nb, fullLines, nScaleBits, nStreams == 2, bc.f, bc.ch, oscale, msSwitch, scaleFactor, bitAlloc,
+                 mantissa, (bc.ch == 0 ? outL : outR) + outOffset[bc.f], smem);
+}
+
+__global__ __launch_bounds__(kThreads) void decode_reduced_mix_kernel(DevShape R, const unsigned char* __restrict__ bandOfLine,
+                                                                      int nb, int fullLines, int nScaleBits, int joint,
+                                                                      int mixSel, int64_t nPairs,
+                                                                      const int* __restrict__ oscale,
+                                                                      const int* __restrict__ msSwitch,
+                                                                      const int* __restrict__ scaleFactor,
+                                                                      const int* __restrict__ bitAlloc,
+                                                                      const int* __restrict__ mantissa,
+                                                                      const int64_t* __restrict__ outOffset,
+                                                                      double* __restrict__ out) {
+    extern __shared__ double smem[];
+    int64_t f;
+    int sel;
+    mix_slot(joint != 0, mixSel, nPairs, &f, &sel);
+    decode_block<true>(R, bandOfLine, nb, fullLines, nScaleBits, joint != 0, f, sel, oscale, msSwitch, scaleFactor, bitAlloc, mantissa,
+                 out + outOffset[blockIdx.x], smem);
 }
 
 // pcmfile.py:163-172
@@ -140,6 +210,27 @@ hipError_t launch_decode_reduced(const DevShape& F, const DevShape& R, int64_t n
     hipLaunchKernelGGL(decode_reduced_kernel, dim3((unsigned)(nBlocks * nStreams)), dim3(kThreads), lds, st, R, F.bandOfLine,
                        F.nBands, F.halfN, F.nScaleBits, nStreams, oscale, msSwitch, scaleFactor, bitAlloc, mantissa, outOffset,
                        outL, outR);
+    return hipGetLastError();
+}
+
+// One plane: F the block's full shape, R its reduced one (null: full rate, decode_mix_kernel).  nWorkgroups: the joint
+// group's slots, or the non-joint group's nPairs pairs + single slots (2 nPairs + singles slots in all); mixSel: 0 / 1 / 2 =
+// L / R / mid of a joint slot.  outOffset [nWorkgroups].
+hipError_t launch_decode_mix(const DevShape& F, const DevShape* R, int64_t nWorkgroups, int joint, int mixSel, int64_t nPairs,
+                             const int* oscale, const int* msSwitch, const int* scaleFactor, const int* bitAlloc,
+                             const int* mantissa, const int64_t* outOffset, double* out, hipStream_t st) {
+    if (nWorkgroups <= 0) return hipSuccess;
+    if (mixSel < 0 || mixSel > kSelMid || nPairs < 0 || nPairs > nWorkgroups || (joint && nPairs) || nWorkgroups > 0x7fffffffLL)
+        return hipErrorInvalidValue;
+    if (!R) {
+        hipLaunchKernelGGL(decode_mix_kernel, dim3((unsigned)nWorkgroups), dim3(kThreads), mdct_generic_lds_bytes(F), st, F, joint,
+                           mixSel, nPairs, oscale, msSwitch, scaleFactor, bitAlloc, mantissa, outOffset, out);
+        return hipGetLastError();
+    }
+    if (R->halfN <= 0 || R->halfN > F.halfN) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(decode_reduced_mix_kernel, dim3((unsigned)nWorkgroups), dim3(kThreads), mdct_generic_lds_bytes(*R), st, *R,
+                       F.bandOfLine, F.nBands, F.halfN, F.nScaleBits, joint, mixSel, nPairs, oscale, msSwitch, scaleFactor,
+                       bitAlloc, mantissa, outOffset, out);
     return hipGetLastError();
 }
 

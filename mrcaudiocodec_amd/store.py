@@ -6,11 +6,16 @@ blocks its windows overlap, and no file byte crosses PCIe again.
     with PacStore(handle, bufs) as store:
         x = store.decode_window(files, starts, 48000, dtype=torch.float32)     # [len(files)][channels][48000], on the GPU
         y = store.decode_window(files, starts, 12000, dtype=torch.float32, rate_divisor=4)   # the same second at 1/4 rate
+        m = store.decode_window(files, starts, 24000, dtype=torch.float32, rate_divisor=2, mix="mid")   # [len(files)][1][24000]
 
 rate_divisor = 2 or 4 (mrc_pac_store_decode_window_reduced) decodes at half or quarter sample rate straight from the MDCT
 lines: the first 1/D of each block's lines through an inverse transform D times shorter.  starts and window then count
 reduced samples; reduced sample m is the signal, band-limited to the new Nyquist frequency, at full-rate time
 D m + (D - 1) / 2 -- (D - 1) / 2 full-rate samples after full-rate sample D m.
+
+mix = "mid", "left" or "right" (mrc_pac_store_decode_window_mix) gives ONE channel of every file, stereo or mono: left and
+right are the bits of that channel of the two-channel call; mid is (L + R) / 2 formed on the MDCT lines, where most bands
+of a stereo file hold it already, so that a stereo block costs one inverse transform, one plane and one output row.
 """
 import ctypes as C
 
@@ -22,6 +27,7 @@ from ._lib import lib
 STAT_NAMES = ("chunks_parsed", "decode_launches", "slabs", "plan_bytes_uploaded")
 MS_NAMES = ("plan_upload", "unpack", "synthesis", "window_out")
 RATE_DIVISORS = (1, 2, 4)
+MIXES = {"mid": _lib.MRC_MIX_MID, "left": _lib.MRC_MIX_LEFT, "right": _lib.MRC_MIX_RIGHT}
 
 
 def check_rate_divisor(rate_divisor, what="decode_window"):
@@ -29,6 +35,17 @@ def check_rate_divisor(rate_divisor, what="decode_window"):
     if isinstance(rate_divisor, bool) or not isinstance(rate_divisor, (int, np.integer)) or int(rate_divisor) not in RATE_DIVISORS:
         raise ValueError("%s: rate_divisor must be an int in {1, 2, 4}, got %r" % (what, rate_divisor))
     return int(rate_divisor)
+
+
+def check_mix(mix, channels=None, what="decode_window"):
+    """mix (None: no mix) with the channels asked for beside it -> its MRC_MIX_* value or None, else ValueError"""
+    if mix is None:
+        return None
+    if not isinstance(mix, str) or mix not in MIXES:
+        raise ValueError('%s: mix must be None, "mid", "left" or "right", got %r' % (what, mix))
+    if channels is not None and (isinstance(channels, bool) or not isinstance(channels, (int, np.integer)) or int(channels) != 1):
+        raise ValueError("%s: mix=%r gives one channel, channels must be None or 1, got %r" % (what, mix, channels))
+    return MIXES[mix]
 
 
 def _formats():
@@ -89,7 +106,8 @@ class PacStore:
         library accepts for the handle's block lengths)"""
         return self.n_samples // check_rate_divisor(rate_divisor, "n_samples_at")
 
-    def decode_window(self, files, starts, window, channels=None, dtype=None, out=None, stream=None, rate_divisor=1):
+    def decode_window(self, files, starts, window, channels=None, dtype=None, out=None, stream=None, rate_divisor=1,
+                      mix=None):
         """Item i = samples [starts[i], starts[i] + window) of file files[i], zeros where that leaves the file (starts may be
         negative or past the end) -> a torch tensor [n][channels][window] on the handle's device.  dtype: torch.int16 (the
         default: the codes Handle.decode_pac_pcm16 writes, bit for bit), torch.float64 (the overlap-added signal before the
@@ -101,9 +119,16 @@ class PacStore:
         rate_divisor: 1, 2 or 4 (else ValueError, before any library call).  2 or 4: starts and window count samples at that
         fraction of the sample rate (n_samples_at), sample m being the band-limited signal at full-rate time
         D m + (D - 1) / 2; torch.float64 is then the reduced overlap-added signal, torch.float32 and torch.int16 its
-        conversions.  A divisor the handle's block shapes do not divide by is refused by the library (MrcError)."""
+        conversions.  A divisor the handle's block shapes do not divide by is refused by the library (MrcError).
+        mix: None, or "mid", "left" or "right": one channel of every item, [n][1][window], a stereo file's left or right
+        channel (the bits of that channel of the two-channel call) or its mid (L + R) / 2, formed on the MDCT lines before
+        the one inverse transform (torch.float64: that plane; the other dtypes its conversions); a mono file gives its
+        channel.  channels must then be None or 1, and any other mix is a ValueError, before any library call."""
         import torch
         rate_divisor = check_rate_divisor(rate_divisor)
+        mix = check_mix(mix, channels)
+        if mix is not None:
+            channels = 1
         files = np.ascontiguousarray(np.asarray(files, dtype=np.int64).reshape(-1))
         starts = np.ascontiguousarray(np.asarray(starts, dtype=np.int64).reshape(-1))
         if files.shape != starts.shape:
@@ -129,7 +154,9 @@ class PacStore:
             stream = torch.cuda.current_stream(dev).cuda_stream
         tail = (n, files.ctypes.data, starts.ctypes.data, window, channels, fmt, out.data_ptr() if out.numel() else None,
                 stream or None)
-        if rate_divisor == 1:
+        if mix is not None:
+            self._handle._check(lib.mrc_pac_store_decode_window_mix(self._s, rate_divisor, mix, *tail[:4], *tail[5:]))
+        elif rate_divisor == 1:
             self._handle._check(lib.mrc_pac_store_decode_window(self._s, *tail))
         else:
             self._handle._check(lib.mrc_pac_store_decode_window_reduced(self._s, rate_divisor, *tail))
