@@ -31,58 +31,12 @@ import pytest
 
 from oracle import fast
 import smr_contenders_restatement as R
+from smr_content import content_noise, content_tone, content_softtone, content_silence, content_step, content_sparse
 
 HOP = 1024
 N_FRAMES = 9
 COUNTS = (1, 2, 9)
 INT_KEYS = ("overall_scale", "bit_alloc", "scale_factor", "mantissa", "reservoir_out")
-
-
-def _noise(seed, n, sigma):
-    g = np.random.default_rng(seed).normal(0.0, sigma * 32767, n)
-    return np.clip(np.rint(g), -32767, 32767)
-
-
-def content_noise():
-    return np.concatenate([np.zeros(HOP), _noise(77, N_FRAMES * HOP, 0.1)]).astype(np.int16)
-
-
-def _tone(amp):
-    n = np.arange((N_FRAMES + 1) * HOP)
-    x = amp * 32767 * np.sin(2 * np.pi * 997.0 * n / 48000.0) + _noise(5, len(n), 1e-3)
-    return np.clip(np.rint(x), -32767, 32767).astype(np.int16)
-
-
-def content_tone():
-    return _tone(0.5)
-
-
-def content_softtone():
-    return _tone(0.015)
-
-
-def _gated(seed, on):
-    x = _noise(seed, (N_FRAMES + 1) * HOP, 0.1)
-    x[~np.repeat(np.array(on, dtype=bool), HOP)] = 0
-    return x.astype(np.int16)
-
-
-def content_silence():
-    return _gated(11, [1, 0, 0, 1, 0, 1, 1, 0, 0, 1])
-
-
-def content_step():
-    n = (N_FRAMES + 1) * HOP
-    spec = np.fft.rfft(np.random.default_rng(21).normal(0.0, 0.1 * 32767, n))
-    spec[np.fft.rfftfreq(n, 1.0 / 48000.0) >= 6000.0] *= 0.01
-    return np.clip(np.rint(np.fft.irfft(spec, n)), -32767, 32767).astype(np.int16)
-
-
-def content_sparse():
-    x = np.zeros((N_FRAMES + 1) * HOP)
-    x[HOP + 300::2 * HOP] = 20000                                  # (every second hop: a block sees one pair)
-    x[HOP + 340::2 * HOP] = -12000
-    return x.astype(np.int16)
 
 
 CONTENTS = dict(noise=content_noise, tone=content_tone, softtone=content_softtone, silence=content_silence,
