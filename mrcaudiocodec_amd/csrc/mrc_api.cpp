@@ -680,14 +680,13 @@ int encode_host(mrc_handle* h, int64_t n, int a, int b, const double* left, cons
         //     remainder as the reservoir; the savings are the caller's, 224,274).
         DrainGuard drain{{h->stream}};
         SmallBatchBufs& B = h->smallBatch;
-        auto al = [](size_t v) { return (v + 15) & ~(size_t)15; };
         const int nEv = (int)chain_events_per_block(S, joint);
-        const size_t szDesc = sizeof(ChainGroupDev), szItems = (size_t)n * sizeof(int32_t), szStart = (size_t)(n + 1) * sizeof(long long);
         const size_t szMant16 = (size_t)n * nstream * S.halfN * sizeof(uint16_t);
-        const size_t oR = al(inBytes), oDesc = oR + (joint ? al(inBytes) : 0), oItems = oDesc + al(szDesc),
-                     oStart = oItems + al(szItems), oRes = oStart + al(szStart), oScale = oRes + al(szRes),
-                     oSw = oScale + al(szScale), oSf = oSw + al(joint ? szSw : 0), oBa = oSf + al(szBand), oMant = oBa + al(szBand),
-                     oLines = oMant + al(szMant16), total = oLines + al(szLines);
+        StageLayout lay(16);
+        const size_t oL = lay.add(inBytes), oR = lay.add(joint ? inBytes : 0), oDesc = lay.add<ChainGroupDev>(1),
+                     oItems = lay.add<int32_t>((size_t)n), oStart = lay.add<long long>((size_t)n + 1), oRes = lay.add(szRes),
+                     oScale = lay.add(szScale), oSw = lay.add(joint ? szSw : 0), oSf = lay.add(szBand), oBa = lay.add(szBand),
+                     oMant = lay.add(szMant16), oLines = lay.add(szLines), total = lay.total();
         MRC_HIP(h, B.pinIn.reserve(oScale));
         MRC_HIP(h, B.pinOut.reserve(total - oRes));
         MRC_HIP(h, B.layout.reserve(total));
@@ -699,7 +698,7 @@ int encode_host(mrc_handle* h, int64_t n, int a, int b, const double* left, cons
         MRC_HIP(h, ws.peak.reserve(alloc_workspace_bytes(S, n, joint)));
         char* pin = (char*)B.pinIn.p;
         char* dev = (char*)B.layout.p;
-        std::memcpy(pin, left, inBytes);
+        std::memcpy(pin + oL, left, inBytes);
         if (joint) std::memcpy(pin + oR, right, inBytes);
         const ChainGroupDev D = chain_group_desc(*hs, joint, (const double*)(dev + oLines), ws.peak.as<double>(),
                                                  (const int*)(dev + oScale), (const int*)(dev + oSw), B.ev.as<unsigned>(),
@@ -715,7 +714,7 @@ int encode_host(mrc_handle* h, int64_t n, int a, int b, const double* left, cons
         hipStream_t st = h->stream;
         MRC_HIP(h, hipMemcpyAsync(dev, pin, oScale, hipMemcpyHostToDevice, st));
         const bool timing = h->timing;
-        MRC_TRY(encode_phase_a(h, S, n, dev, joint ? dev + oR : nullptr, kSampleF64, S.N, nullptr, (double*)(dev + oLines),
+        MRC_TRY(encode_phase_a(h, S, n, dev + oL, joint ? dev + oR : nullptr, kSampleF64, S.N, nullptr, (double*)(dev + oLines),
                                (int32_t*)(dev + oScale), joint ? (int32_t*)(dev + oSw) : nullptr, ws.smr.as<double>(),
                                ws.peak.as<double>(), st, timing));
         MRC_HIP(h, launch_chain_prep(S, joint, n, ws.smr.as<double>(), joint ? (const int*)(dev + oSw) : nullptr,

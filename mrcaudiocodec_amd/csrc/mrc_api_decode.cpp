@@ -9,6 +9,12 @@
 // A group is a (block shape, kind): one decode_kernel launch each, over all files of the call.  The output planes hold
 // every file one after the other, channel 1 one plane stride behind channel 0; each output sample receives at most two
 // atomic contributions, so the order of the blocks does not change a bit of the result.
+//
+// Also here, for mrc_api_nmr.cpp and mrc_api_store.cpp as well: the host plan (pac_plan_scan / pac_plan_groups /
+// pac_plan_layout), the preamble of a call that takes a list of files (check_file_list) and the parse step (pac_parse: staging
+// copy, unpack_dense_kernel, verdict, a bad chunk named by file and byte).  Their pure parts -- the staging layout, the chunk
+// locator, the slots a block takes -- are in mrc_pac_stage.hpp; the walk over the groups that have slots (decode_groups) is in
+// mrc_handle.hpp.
 #include "mrc_handle.hpp"
 
 #include <algorithm>
@@ -51,15 +57,17 @@ int ensure_decode_consts(mrc_handle* h) {
     MRC_HIP(h, hipSetDevice(h->device));
     if (d.consts.p) return MRC_OK;
     std::vector<int> cnt[4];
-    size_t bandOff[4], bytes = align256(sizeof(UnpackTables));
+    StageLayout lay(256);                                // UnpackTables | the four band tables
+    size_t bandOff[4];
+    lay.add<UnpackTables>(1);
     decode_band_counts(h->cfg, d.bands.nBands, cnt);
     for (int s = 0; s < 4; ++s) {
         int a, b;
         shape_ab(h->cfg, s, &a, &b);
         d.bands.halfN[s] = (a + b) / 2;
-        bandOff[s] = bytes;
-        bytes += align256(sizeof(int) * (cnt[s].size() + 1));
+        bandOff[s] = lay.add<int>(cnt[s].size() + 1);
     }
+    const size_t bytes = lay.total();
     std::vector<unsigned char> blob(bytes, 0);
     unpack_tables((UnpackTables*)blob.data());
     for (int s = 0; s < 4; ++s)
@@ -87,6 +95,45 @@ int reset_unpack_err(mrc_handle* h, hipStream_t st) {
     UnpackErr* e = d.err.as<UnpackErr>();
     MRC_HIP(h, hipMemsetAsync(&e->flag, 0, sizeof(int), st));
     MRC_HIP(h, hipMemsetD32Async((hipDeviceptr_t)&e->firstBad, 0x7fffffff, 1, st));
+    return MRC_OK;
+}
+
+int read_unpack_err(mrc_handle* h, hipStream_t st, const UnpackErr** bad) {
+    DecodeBufs& d = h->dec;
+    MRC_HIP(h, hipMemcpyAsync(d.pinErr.get(), d.err.p, sizeof(UnpackErr), hipMemcpyDeviceToHost, st));
+    MRC_HIP(h, hipStreamSynchronize(st));
+    *bad = d.pinErr->flag ? d.pinErr.get() : nullptr;
+    return MRC_OK;
+}
+
+int pac_parse(mrc_handle* h, const char* fn, const std::vector<int64_t>& fileBase, const PacParse& p) {
+    DecodeBufs& d = h->dec;
+    const unsigned char* dev = (const unsigned char*)p.dev;
+    MRC_HIP(h, hipEventRecord(p.ev[0], p.st));
+    MRC_HIP(h, hipMemcpyAsync(p.dev, p.pin, p.total, hipMemcpyHostToDevice, p.st));
+    MRC_HIP(h, hipEventRecord(p.ev[1], p.st));
+    MRC_TRY(reset_unpack_err(h, p.st));
+    MRC_HIP(h, launch_unpack_dense(unpack_params(h->cfg), d.bands, d.consts.as<UnpackTables>(), p.nChunks,
+                                   (const UnpackPlanEntry*)(dev + p.oPlan), p.bytes, p.nBytes,
+                                   (const UnpackGroupDev*)(dev + p.oGroups), d.err.as<UnpackErr>(), p.st));
+    MRC_HIP(h, hipEventRecord(p.ev[2], p.st));
+    const UnpackErr* bad;
+    MRC_TRY(read_unpack_err(h, p.st, &bad));
+    if (!bad) return MRC_OK;
+    // (firstBad is the minimum over the flagged chunks, so it names one; were it not to, the answer is file 0, byte 0)
+    const UnpackPlanEntry* plan = (const UnpackPlanEntry*)((const unsigned char*)p.pin + p.oPlan);
+    const ChunkPlace at = bad->firstBad < p.nChunks ? pac_locate_chunk(fileBase, plan[bad->firstBad].off) : ChunkPlace{0, 0};
+    char msg[240];
+    std::snprintf(msg, sizeof msg, "%s: file %lld: chunk at byte %lld: %s", fn, (long long)at.file, (long long)at.byte,
+                  unpack_status_text(bad->flag));
+    return fail(h, MRC_ERR_INVALID, msg);
+}
+
+int check_file_list(mrc_handle* h, const char* fn, int64_t n_files, const uint8_t* buf, const int64_t* file_offset) {
+    if (n_files < 0 || !file_offset || (n_files > 0 && !buf)) return fail(h, MRC_ERR_INVALID, std::string(fn) + ": bad argument");
+    for (int64_t f = 0; f < n_files; ++f)
+        if (file_offset[0] < 0 || file_offset[f + 1] < file_offset[f])
+            return fail(h, MRC_ERR_INVALID, std::string(fn) + ": file_offset must not decrease");
     return MRC_OK;
 }
 
@@ -177,6 +224,7 @@ int pac_scan_file(mrc_handle* h, const mrc_config& hc, const char* fn, const cha
 int pac_plan_scan(mrc_handle* h, const char* fn, int64_t n_files, const uint8_t* buf, const int64_t* file_offset,
                   PacPlan* p) {
     p->files.assign((size_t)n_files, PacFilePlan{});
+    p->fileBase = pac_file_bases(file_offset, n_files);
     p->chunkOff.clear();
     p->chunkShape.clear();
     p->planeStride = 0;
@@ -184,7 +232,7 @@ int pac_plan_scan(mrc_handle* h, const char* fn, int64_t n_files, const uint8_t*
     for (int64_t f = 0; f < n_files; ++f) {
         PacFilePlan& fi = p->files[(size_t)f];
         MRC_TRY(pac_scan_file(h, h->cfg, fn, "the handle was created with", f, buf + file_offset[f],
-                              file_offset[f + 1] - file_offset[f], file_offset[f] - file_offset[0], &p->chunkOff,
+                              file_offset[f + 1] - file_offset[f], p->fileBase[(size_t)f], &p->chunkOff,
                               &p->chunkShape, &fi));
         fi.xStart = p->planeStride;
         p->planeStride += fi.extent;
@@ -195,16 +243,9 @@ int pac_plan_scan(mrc_handle* h, const char* fn, int64_t n_files, const uint8_t*
 
 // ---- pass 2: groups and slots
 int pac_plan_groups(mrc_handle* h, const char* fn, PacPlan* p) {
-    for (int64_t k = 0; k < 2 * kUnpackGroups; ++k) p->nCat[k] = 0;
-    for (int g = 0; g < kUnpackGroups; ++g) p->nSlots[g] = 0;
-    for (const PacFilePlan& fi : p->files) {
-        const int64_t nb = fi.nChunks / fi.nch, nJoint = (fi.nch == 2 && nb > 1) ? nb - 1 : 0;
-        for (int64_t i = 0; i < nb; ++i) {
-            const int s = p->chunkShape[(size_t)(fi.firstChunk + i * fi.nch)];
-            if (i < nJoint) { p->nSlots[s * 2] += 1; p->nCat[s * 4] += 1; p->nCat[s * 4 + 1] += 1; }
-            else { p->nSlots[s * 2 + 1] += fi.nch; p->nCat[s * 4 + 2] += fi.nch; }
-        }
-    }
+    p->clear_counts();
+    for (int64_t f = 0; f < (int64_t)p->files.size(); ++f)
+        for (int64_t i = 0; i < p->nBlocks(f); ++i) p->add_block(p->shape(f, i), i < p->nJoint(f), p->files[(size_t)f].nch);
     return pac_plan_layout(h, fn, p);
 }
 
@@ -221,16 +262,15 @@ int pac_plan_layout(mrc_handle* h, const char* fn, PacPlan* p) {
             if (p->hs[s]->dev.nBands != d.bands.nBands[s])
                 return fail(h, MRC_ERR_INVALID, std::string(fn) + ": band tables disagree");
         }
-    p->totalSlots = 0;
-    for (int g = 0; g < kUnpackGroups; ++g) p->totalSlots += p->nSlots[g];
-    p->gBytes = 0;
+    StageLayout lay(256);
     for (int g = 0; g < kUnpackGroups; ++g) {
         const int s = g / 2, joint = !(g & 1), nb = std::max(d.bands.nBands[s], 0), half = d.bands.halfN[s];
         const int64_t n = p->nSlots[g], ns = joint ? 2 : 1;
         const size_t sz[5] = {sizeof(int) * n * (joint ? 4 : 1), joint ? sizeof(int) * n * nb : 0, sizeof(int) * n * ns * nb,
                               sizeof(int) * n * ns * nb, sizeof(int) * n * ns * half};
-        for (int k = 0; k < 5; ++k) { p->gOff[g][k] = p->gBytes; p->gBytes += align256(sz[k]); }
+        for (int k = 0; k < 5; ++k) p->gOff[g][k] = lay.add(sz[k]);
     }
+    p->gBytes = lay.total();
     return MRC_OK;
 }
 
@@ -253,12 +293,11 @@ int mrc_dev_unpack_blocks(mrc_handle* h, int64_t n_blocks, int n_channels, int j
     UnpackFixedOut O{a, b, huff_table, overall_scale, ms_switch, scale_factor, bit_alloc, mantissa};
     MRC_HIP(h, launch_unpack_fixed(unpack_params(c), h->dec.bands, h->dec.consts.as<UnpackTables>(), n_blocks, n_channels,
                                    joint ? 1 : 0, buf, len, chunk_offset, O, h->dec.err.as<UnpackErr>(), st));
-    MRC_HIP(h, hipMemcpyAsync(h->dec.pinErr.get(), h->dec.err.p, sizeof(UnpackErr), hipMemcpyDeviceToHost, st));
-    MRC_HIP(h, hipStreamSynchronize(st));
-    if (h->dec.pinErr->flag) {
+    const UnpackErr* bad;
+    MRC_TRY(read_unpack_err(h, st, &bad));
+    if (bad) {
         char msg[160];
-        std::snprintf(msg, sizeof msg, "mrc_dev_unpack_blocks: chunk %d: %s", h->dec.pinErr->firstBad,
-                      unpack_status_text(h->dec.pinErr->flag));
+        std::snprintf(msg, sizeof msg, "mrc_dev_unpack_blocks: chunk %d: %s", bad->firstBad, unpack_status_text(bad->flag));
         return fail(h, MRC_ERR_INVALID, msg);
     }
     return MRC_OK;
@@ -267,26 +306,21 @@ int mrc_dev_unpack_blocks(mrc_handle* h, int64_t n_blocks, int n_channels, int j
 int mrc_decode_pac_pcm16(mrc_handle* h, int64_t n_files, const uint8_t* buf, const int64_t* file_offset, int16_t* out,
                          int64_t out_cap, int64_t* sample_offset, int32_t* n_channels) {
     if (!h) return MRC_ERR_INVALID;
-    if (n_files < 0 || !file_offset || !sample_offset || !n_channels || out_cap < 0 || (n_files > 0 && !buf))
-        return fail(h, MRC_ERR_INVALID, "mrc_decode_pac_pcm16: bad argument");
+    const char* const fn = "mrc_decode_pac_pcm16";
+    if (!sample_offset || !n_channels || out_cap < 0) return fail(h, MRC_ERR_INVALID, "mrc_decode_pac_pcm16: bad argument");
+    MRC_TRY(check_file_list(h, fn, n_files, buf, file_offset));
     const int L = h->cfg.n_mdct_lines;
-    const UnpackParams P = unpack_params(h->cfg);
     char msg[200];
     sample_offset[0] = 0;
-    for (int64_t f = 0; f < n_files; ++f)
-        if (file_offset[0] < 0 || file_offset[f + 1] < file_offset[f])
-            return fail(h, MRC_ERR_INVALID, "mrc_decode_pac_pcm16: file_offset must not decrease");
     if (n_files == 0) return MRC_OK;
     MRC_TRY(ensure_decode_consts(h));
     DecodeBufs& d = h->dec;
 
     // ---- host plan (shared with mrc_pac_nmr): headers, chunks, block shapes, where each file's samples go
-    const uint8_t* base = buf + file_offset[0];
     const int64_t inBytes = file_offset[n_files] - file_offset[0];
     PacPlan pl;
-    MRC_TRY(pac_plan_scan(h, "mrc_decode_pac_pcm16", n_files, buf, file_offset, &pl));
+    MRC_TRY(pac_plan_scan(h, fn, n_files, buf, file_offset, &pl));
     const int64_t planeStride = pl.planeStride;
-    const bool anyStereo = pl.anyStereo;
     for (int64_t f = 0; f < n_files; ++f) {
         const PacFilePlan& fi = pl.files[(size_t)f];
         n_channels[f] = fi.nch;
@@ -300,19 +334,15 @@ int mrc_decode_pac_pcm16(mrc_handle* h, int64_t n_files, const uint8_t* buf, con
     }
 
     // ---- pass 2: groups and slots; plan entries ordered by (group, joint channel) so that a wave parses one kind
-    MRC_TRY(pac_plan_groups(h, "mrc_decode_pac_pcm16", &pl));
-    const int64_t nChunks = pl.nChunks();
-    const int64_t* nSlots = pl.nSlots;
-    const int64_t* slotBase = pl.slotBase;
-    const int64_t totalSlots = pl.totalSlots;
+    MRC_TRY(pac_plan_groups(h, fn, &pl));
 
     // staging layout (one H2D copy): bytes | plan | groups | block offsets | outStart [n+1] | xStart [n] | nch [n]
-    const size_t oPlan = align256((size_t)inBytes), oGroups = oPlan + align256(sizeof(UnpackPlanEntry) * nChunks),
-                 oOffs = oGroups + align256(sizeof(UnpackGroupDev) * kUnpackGroups),
-                 oOutStart = oOffs + align256(sizeof(long long) * totalSlots),
-                 oXStart = oOutStart + align256(sizeof(long long) * (n_files + 1)),
-                 oNch = oXStart + align256(sizeof(long long) * n_files), inTotal = oNch + align256(sizeof(int) * n_files);
-    const int64_t xDoubles = planeStride * (anyStereo ? 2 : 1);
+    StageLayout lay(256);
+    const size_t oBytes = lay.add((size_t)inBytes), oPlan = lay.add<UnpackPlanEntry>(pl.nChunks()),
+                 oGroups = lay.add<UnpackGroupDev>(kUnpackGroups), oOffs = lay.add<long long>(pl.totalSlots),
+                 oOutStart = lay.add<long long>(n_files + 1), oXStart = lay.add<long long>(n_files),
+                 oNch = lay.add<int>(n_files), inTotal = lay.total();
+    const int64_t xDoubles = planeStride * (pl.anyStereo ? 2 : 1);
     MRC_HIP(h, d.pinIn.reserve(inTotal));
     MRC_HIP(h, d.in.reserve(inTotal));
     MRC_HIP(h, d.groups.reserve(std::max<size_t>(pl.gBytes, 256)));
@@ -321,16 +351,15 @@ int mrc_decode_pac_pcm16(mrc_handle* h, int64_t n_files, const uint8_t* buf, con
     MRC_HIP(h, d.pinOut.reserve(std::max<size_t>(sizeof(int16_t) * nOut, 256)));
 
     unsigned char* pin = (unsigned char*)d.pinIn.p;
-    copy_host(pin, base, (size_t)inBytes);
-    UnpackPlanEntry* plan = (UnpackPlanEntry*)(pin + oPlan);
+    copy_host(pin + oBytes, buf + file_offset[0], (size_t)inBytes);
     UnpackGroupDev* gd = (UnpackGroupDev*)(pin + oGroups);
     long long* offs = (long long*)(pin + oOffs);
     long long* outStart = (long long*)(pin + oOutStart);
     long long* xStart = (long long*)(pin + oXStart);
     int* nchDev = (int*)(pin + oNch);
-    pac_plan_fill(h->cfg, d, pl, plan, gd, d.groups.as<unsigned char>(),
+    pac_plan_fill(h->cfg, d, pl, (UnpackPlanEntry*)(pin + oPlan), gd, d.groups.as<unsigned char>(),
                   [&](int64_t f, int64_t, int g, int slot, int ch, int64_t start) {
-                      offs[slotBase[g] + slot] = ch * planeStride + pl.files[(size_t)f].xStart + start;
+                      offs[pl.slotBase[g] + slot] = ch * planeStride + pl.files[(size_t)f].xStart + start;
                   });
     for (int64_t f = 0; f < n_files; ++f) {
         outStart[f] = sample_offset[f];
@@ -339,35 +368,14 @@ int mrc_decode_pac_pcm16(mrc_handle* h, int64_t n_files, const uint8_t* buf, con
     }
     outStart[n_files] = nOut;
 
-    // ---- device
+    // ---- device: the parse step (the plan entries point into the staging's own bytes), synthesis, interleave
     hipStream_t st = h->stream;
     unsigned char* din = d.in.as<unsigned char>();
-    MRC_HIP(h, hipEventRecord(d.ev[0], st));
-    MRC_HIP(h, hipMemcpyAsync(din, pin, inTotal, hipMemcpyHostToDevice, st));
-    MRC_HIP(h, hipEventRecord(d.ev[1], st));
-    MRC_TRY(reset_unpack_err(h, st));
-    MRC_HIP(h, launch_unpack_dense(P, d.bands, d.consts.as<UnpackTables>(), nChunks, (const UnpackPlanEntry*)(din + oPlan),
-                                   din, inBytes, (const UnpackGroupDev*)(din + oGroups), d.err.as<UnpackErr>(), st));
-    MRC_HIP(h, hipEventRecord(d.ev[2], st));
-    MRC_HIP(h, hipMemcpyAsync(d.pinErr.get(), d.err.p, sizeof(UnpackErr), hipMemcpyDeviceToHost, st));
-    MRC_HIP(h, hipStreamSynchronize(st));
-    if (d.pinErr->flag) {
-        const int64_t c = d.pinErr->firstBad;
-        const int64_t at = c < nChunks ? plan[c].off + file_offset[0] : 0;
-        const int64_t f = std::upper_bound(file_offset, file_offset + n_files + 1, at) - file_offset - 1;
-        std::snprintf(msg, sizeof msg, "mrc_decode_pac_pcm16: file %lld: chunk at byte %lld: %s", (long long)f,
-                      (long long)(at - file_offset[std::max<int64_t>(f, 0)]), unpack_status_text(d.pinErr->flag));
-        return fail(h, MRC_ERR_INVALID, msg);
-    }
+    MRC_TRY(pac_parse(h, fn, pl.fileBase, PacParse{pin, din, inTotal, oPlan, oGroups, pl.nChunks(), din + oBytes, inBytes,
+                                                   {d.ev[0], d.ev[1], d.ev[2]}, st}));
     double* x = d.x.as<double>();
     MRC_HIP(h, hipMemsetAsync(x, 0, sizeof(double) * xDoubles, st));
-    for (int g = 0; g < kUnpackGroups; ++g) {
-        if (!nSlots[g]) continue;
-        const UnpackGroupDev& G = gd[g];
-        MRC_HIP(h, launch_decode(pl.hs[g / 2]->dev, nSlots[g], G.joint ? 2 : 1, G.oscale, G.joint ? G.ms : nullptr, G.sf, G.ba,
-                                 G.mant, (const int64_t*)(din + oOffs) + slotBase[g], x, G.joint ? x + planeStride : nullptr,
-                                 st));
-    }
+    MRC_TRY(decode_groups(h, pl, gd, (const int64_t*)(din + oOffs), x, planeStride, st));
     short* pcm = d.pcm.as<short>();
     MRC_HIP(h, launch_pcm16_interleave(n_files, nOut, (const long long*)(din + oOutStart), (const long long*)(din + oXStart),
                                        (const int*)(din + oNch), L, x, planeStride, pcm, st));

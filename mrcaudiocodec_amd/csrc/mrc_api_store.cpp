@@ -18,7 +18,10 @@
 //                   one unpack_dense_kernel launch, at most eight decode_kernel launches.  A block's kind is its position
 //                   in its file: joint for all but the last block of a stereo file of more than one block.
 //   window_out_kernel  planes -> out [item][channel][t] in the caller's format (mrc_kernels_store.hip).
-// The plan entries point into the resident bytes; what is uploaded per slab is the plan alone.
+// The plan entries point into the resident bytes; what is uploaded per slab is the plan alone.  Staging offsets, slot counts,
+// the parse step and the walk over the groups are the whole-file decode's (StageLayout, PacGroupCounts::add_block, pac_parse with
+// the resident bytes as what the entries point into, pac_for_groups / decode_groups); a bad chunk's file is found from the
+// index's file bases like everywhere else.
 //
 // decode_window_reduced, rate divisor D = 2 or 4 (D = 1: the call above): the same plan with every length divided by D --
 // L / D, p_i / D, (a_i + b_i) / D, planes of window + 4 L / D, start and window in reduced samples -- exact, because every
@@ -83,16 +86,12 @@ int mrc_pac_store_create(mrc_handle* h, int64_t n_files, const uint8_t* buf, con
                          mrc_pac_store** out) {
     if (!h) return MRC_ERR_INVALID;
     if (out) *out = nullptr;
-    if (n_files < 0 || !file_offset || !out || (n_files > 0 && !buf))
-        return fail(h, MRC_ERR_INVALID, "mrc_pac_store_create: bad argument");
-    for (int64_t f = 0; f < n_files; ++f)
-        if (file_offset[0] < 0 || file_offset[f + 1] < file_offset[f])
-            return fail(h, MRC_ERR_INVALID, "mrc_pac_store_create: file_offset must not decrease");
+    if (!out) return fail(h, MRC_ERR_INVALID, "mrc_pac_store_create: bad argument");
+    MRC_TRY(check_file_list(h, "mrc_pac_store_create", n_files, buf, file_offset));
     std::unique_ptr<mrc_pac_store> s(new (std::nothrow) mrc_pac_store());
     if (!s) return fail(h, MRC_ERR_NOMEM, "mrc_pac_store_create: out of host memory");
     MRC_TRY(pac_plan_scan(h, "mrc_pac_store_create", n_files, buf, file_offset, &s->index));
     s->firstBlock.assign((size_t)n_files + 1, 0);
-    s->fileBase.assign((size_t)n_files + 1, 0);
     for (int64_t f = 0; f < n_files; ++f) {
         int64_t start = 0;
         for (int64_t i = 0; i < s->index.nBlocks(f); ++i) {
@@ -102,7 +101,6 @@ int mrc_pac_store_create(mrc_handle* h, int64_t n_files, const uint8_t* buf, con
             start += a;
         }
         s->firstBlock[(size_t)f + 1] = (int64_t)s->blockStart.size();
-        s->fileBase[(size_t)f + 1] = file_offset[f + 1] - file_offset[0];
     }
     s->nBytes = n_files ? file_offset[n_files] - file_offset[0] : 0;
     MRC_TRY(ensure_decode_consts(h));
@@ -184,17 +182,14 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
     DecodeBufs& d = h->dec;
     StoreBufs& b = h->store;
     MRC_HIP(h, b.ev.create());
-    const UnpackParams P = unpack_params(cfg);
     hipStream_t st = pick_stream(h, stream);
     DrainGuard drain{{st, nullptr, nullptr}};
     const size_t elem = format == MRC_WINDOW_PCM16 ? 2 : format == MRC_WINDOW_F32 ? 4 : 8;
     const int64_t planeLen = window + 4 * L, tiles = (window + 255) / 256;
     const int64_t slab = h->storeSlabSamples, itemCap = std::max<int64_t>(1, 0x7fffffffLL / (tiles * n_channels_out));
-    char msg[240];
 
     std::vector<Need> needs;
     std::vector<WindowItem> items;
-    std::vector<int64_t> planFile;
     // chunks of a needed non-joint block that are parsed: all of the file's, but under left / right the one asked for
     const auto lastChunks = [mix](int nch) { return mix == MRC_MIX_LEFT || mix == MRC_MIX_RIGHT ? 1 : nch; };
     PacPlan pl;                                              // (its group fields: the slab's slots)
@@ -223,43 +218,36 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
             MRC_HIP(h, hipMemsetAsync(outSlab, 0, (size_t)nSlab * n_channels_out * window * elem, st));
             continue;
         }
-        for (int64_t k = 0; k < 2 * kUnpackGroups; ++k) pl.nCat[k] = 0;
-        for (int g = 0; g < kUnpackGroups; ++g) pl.nSlots[g] = 0;
+        pl.clear_counts();
         // mid: the two chunks of a stereo file's last block are a PAIR of neighbouring slots of the non-joint group, the
         // pairs in front of the group's single slots (launch_decode_mix)
         int64_t nPairs[kUnpackGroups] = {};
         for (const Need& n : needs) {
             const int nch = lastChunks(s->index.files[(size_t)n.file].nch), sh = s->index.shape(n.file, n.block);
-            if (n.block < s->index.nJoint(n.file)) { pl.nSlots[sh * 2] += 1; pl.nCat[sh * 4] += 1; pl.nCat[sh * 4 + 1] += 1; }
-            else {
-                pl.nSlots[sh * 2 + 1] += nch;
-                pl.nCat[sh * 4 + 2] += nch;
-                if (mix == MRC_MIX_MID && nch == 2) nPairs[sh * 2 + 1] += 1;
-            }
+            const bool joint = n.block < s->index.nJoint(n.file);
+            pl.add_block(sh, joint, nch);
+            if (!joint && mix == MRC_MIX_MID && nch == 2) nPairs[sh * 2 + 1] += 1;
         }
         MRC_TRY(pac_plan_layout(h, fn, &pl));
         const HostShape* reduced[4] = {};
         for (int sh = 0; D > 1 && sh < 4; ++sh)
             if (pl.hs[sh]) MRC_TRY(get_synth_shape(h, pl.hs[sh]->dev.a, pl.hs[sh]->dev.b, D, &reduced[sh]));
-        int64_t nChunks = 0;
-        for (int64_t k = 0; k < 2 * kUnpackGroups; ++k) nChunks += pl.nCat[k];
+        const int64_t nChunks = pl.nEntries();
 
         // ---- staging (one H2D copy): plan | groups | block offsets | items
-        const size_t oGroups = align256(sizeof(UnpackPlanEntry) * nChunks),
-                     oOffs = oGroups + align256(sizeof(UnpackGroupDev) * kUnpackGroups),
-                     oItems = oOffs + align256(sizeof(long long) * pl.totalSlots),
-                     inTotal = oItems + align256(sizeof(WindowItem) * nSlab);
+        StageLayout lay(256);
+        const size_t oPlan = lay.add<UnpackPlanEntry>(nChunks), oGroups = lay.add<UnpackGroupDev>(kUnpackGroups),
+                     oOffs = lay.add<long long>(pl.totalSlots), oItems = lay.add<WindowItem>(nSlab), inTotal = lay.total();
         MRC_HIP(h, b.pinIn.reserve(inTotal));
         MRC_HIP(h, b.in.reserve(inTotal));
         MRC_HIP(h, b.groups.reserve(std::max<size_t>(pl.gBytes, 256)));
         MRC_HIP(h, b.planes.reserve(sizeof(double) * (size_t)planeDoubles));
         unsigned char* pin = (unsigned char*)b.pinIn.p;
-        UnpackPlanEntry* plan = (UnpackPlanEntry*)pin;
+        UnpackPlanEntry* plan = (UnpackPlanEntry*)(pin + oPlan);
         UnpackGroupDev* gd = (UnpackGroupDev*)(pin + oGroups);
         long long* offs = (long long*)(pin + oOffs);
         std::memcpy(pin + oItems, items.data(), sizeof(WindowItem) * nSlab);
         pac_plan_group_descs(d, pl, gd, b.groups.as<unsigned char>());
-        planFile.assign((size_t)nChunks, 0);
         int64_t catPos[2 * kUnpackGroups], slotNext[kUnpackGroups] = {}, pairNext[kUnpackGroups] = {};
         for (int64_t k = 0, q = 0; k < 2 * kUnpackGroups; q += pl.nCat[k], ++k) catPos[k] = q;
         for (int g = 0; g < kUnpackGroups; ++g) slotNext[g] = 2 * nPairs[g];      // (joint groups, and every group without mid: 0)
@@ -272,10 +260,8 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
             const int64_t at = it.plane + 2 * L + s->blockStart[(size_t)(s->firstBlock[(size_t)n.file] + n.block)] / D - (it.start + L);
             if (n.block < s->index.nJoint(n.file)) {
                 const int g = sh * 2, slot = (int)slotNext[g]++;
-                for (int ch = 0; ch < 2; ++ch) {
-                    planFile[(size_t)catPos[sh * 4 + ch]] = n.file;
+                for (int ch = 0; ch < 2; ++ch)
                     plan[catPos[sh * 4 + ch]++] = UnpackPlanEntry{s->index.chunkOff[(size_t)c0 + ch], g * 2 + ch, slot};
-                }
                 offs[pl.slotBase[g] + slot] = at;
             } else {
                 const int g = sh * 2 + 1, nParsed = lastChunks(fi.nch), ch0 = fi.nch == 2 && mix == MRC_MIX_RIGHT ? 1 : 0;
@@ -283,7 +269,6 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
                 if (pair) offs[pl.slotBase[g] + pairNext[g] / 2] = at;
                 for (int ch = ch0; ch < ch0 + nParsed; ++ch) {
                     const int slot = (int)(pair ? pairNext[g]++ : slotNext[g]++);
-                    planFile[(size_t)catPos[sh * 4 + 2]] = n.file;
                     plan[catPos[sh * 4 + 2]++] = UnpackPlanEntry{s->index.chunkOff[(size_t)c0 + ch], g * 2, slot};
                     // a single slot's workgroup comes after the group's pairs; without a mix a channel has a plane of its own
                     if (!pair) offs[pl.slotBase[g] + slot - nPairs[g]] = at + (mix == kNoMix ? ch * planeLen : 0);
@@ -293,46 +278,28 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
         s->stats[0] += nChunks;
         s->stats[3] += (int64_t)inTotal;
 
-        // ---- device
+        // ---- device: the parse step (the plan entries point into the resident bytes), then one launch per group with slots
         unsigned char* din = b.in.as<unsigned char>();
-        MRC_HIP(h, hipEventRecord(b.ev[0], st));
-        MRC_HIP(h, hipMemcpyAsync(din, pin, inTotal, hipMemcpyHostToDevice, st));
-        MRC_HIP(h, hipEventRecord(b.ev[1], st));
-        MRC_TRY(reset_unpack_err(h, st));
-        MRC_HIP(h, launch_unpack_dense(P, d.bands, d.consts.as<UnpackTables>(), nChunks, (const UnpackPlanEntry*)din,
-                                       s->bytes.as<uint8_t>(), s->nBytes, (const UnpackGroupDev*)(din + oGroups),
-                                       d.err.as<UnpackErr>(), st));
-        MRC_HIP(h, hipEventRecord(b.ev[2], st));
-        MRC_HIP(h, hipMemcpyAsync(d.pinErr.get(), d.err.p, sizeof(UnpackErr), hipMemcpyDeviceToHost, st));
-        MRC_HIP(h, hipStreamSynchronize(st));
-        if (d.pinErr->flag) {
-            const int64_t c = d.pinErr->firstBad;
-            const int64_t f = c < nChunks ? planFile[(size_t)c] : 0;
-            const int64_t at = c < nChunks ? plan[c].off - s->fileBase[(size_t)f] : 0;
-            std::snprintf(msg, sizeof msg, "%s: file %lld: chunk at byte %lld: %s", fn, (long long)f, (long long)at,
-                          unpack_status_text(d.pinErr->flag));
-            return fail(h, MRC_ERR_INVALID, msg);
-        }
+        MRC_TRY(pac_parse(h, fn, s->index.fileBase,
+                          PacParse{pin, din, inTotal, oPlan, oGroups, nChunks, s->bytes.as<uint8_t>(), s->nBytes,
+                                   {b.ev[0], b.ev[1], b.ev[2]}, st}));
         double* x = b.planes.as<double>();
         MRC_HIP(h, hipEventRecord(b.ev[3], st));
         MRC_HIP(h, hipMemsetAsync(x, 0, sizeof(double) * (size_t)planeDoubles, st));
-        for (int g = 0; g < kUnpackGroups; ++g) {
-            if (!pl.nSlots[g]) continue;
-            const UnpackGroupDev& G = gd[g];
-            const int64_t* offsDev = (const int64_t*)(din + oOffs) + pl.slotBase[g];
-            if (mix != kNoMix)
-                MRC_HIP(h, launch_decode_mix(pl.hs[g / 2]->dev, D == 1 ? nullptr : &reduced[g / 2]->dev, pl.nSlots[g] - nPairs[g], G.joint,
+        const int64_t* offsDev = (const int64_t*)(din + oOffs);
+        if (mix == kNoMix && D == 1) MRC_TRY(decode_groups(h, pl, gd, offsDev, x, planeLen, st));
+        else
+            MRC_TRY(pac_for_groups(h, pl, gd, offsDev, [&](int g, const UnpackGroupDev& G, const int64_t* o) {
+                const DevShape& F = pl.hs[g / 2]->dev;
+                if (mix != kNoMix)
+                    return launch_decode_mix(F, D == 1 ? nullptr : &reduced[g / 2]->dev, pl.nSlots[g] - nPairs[g], G.joint,
                                              mix == MRC_MIX_MID ? 2 : mix == MRC_MIX_LEFT ? 0 : 1, nPairs[g], G.oscale,
-                                             G.joint ? G.ms : nullptr, G.sf, G.ba, G.mant, offsDev, x, st));
-            else if (D == 1)
-                MRC_HIP(h, launch_decode(pl.hs[g / 2]->dev, pl.nSlots[g], G.joint ? 2 : 1, G.oscale, G.joint ? G.ms : nullptr, G.sf,
-                                         G.ba, G.mant, offsDev, x, G.joint ? x + planeLen : nullptr, st));
-            else
-                MRC_HIP(h, launch_decode_reduced(pl.hs[g / 2]->dev, reduced[g / 2]->dev, pl.nSlots[g], G.joint ? 2 : 1, G.oscale,
-                                                 G.joint ? G.ms : nullptr, G.sf, G.ba, G.mant, offsDev, x,
-                                                 G.joint ? x + planeLen : nullptr, st));
-            s->stats[1] += 1;
-        }
+                                             G.joint ? G.ms : nullptr, G.sf, G.ba, G.mant, o, x, st);
+                return launch_decode_reduced(F, reduced[g / 2]->dev, pl.nSlots[g], G.joint ? 2 : 1, G.oscale,
+                                             G.joint ? G.ms : nullptr, G.sf, G.ba, G.mant, o, x,
+                                             G.joint ? x + planeLen : nullptr, st);
+            }));
+        s->stats[1] += pl.groupsUsed();
         MRC_HIP(h, hipEventRecord(b.ev[4], st));
         MRC_HIP(h, launch_window_out(nSlab, (const WindowItem*)(din + oItems), window, n_channels_out, format, (int)L, x,
                                      outSlab, st));

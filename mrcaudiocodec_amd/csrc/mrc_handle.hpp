@@ -5,6 +5,7 @@
 // with the handle (mrc_destroy deletes it); nothing here is freed by name.
 #pragma once
 #include "mrc_internal.hpp"
+#include "mrc_pac_stage.hpp"
 
 #include <cmath>
 #include <limits>
@@ -197,21 +198,21 @@ struct DecodeBufs {
     UnpackBands bands{};             // ... with device pointers into consts
     DevBuf in;                       // one H2D copy: bytes | plan | group descriptors | block offsets | file tables
     DevBuf groups;                   // dense per-(shape, kind) arrays decode_kernel reads
-    DevBuf x, pcm, err;              // decoded planes (float64), interleaved int16, UnpackErr
+    DevBuf x, pcm, err;              // decoded planes (float64), interleaved int16, UnpackErr (reset_unpack_err)
     PinnedBuf pinIn, pinOut;
-    PinnedPtr<UnpackErr> pinErr;     // page-locked copy of err
+    PinnedPtr<UnpackErr> pinErr;     // page-locked copy of err (read_unpack_err)
     EventSet<5> ev;                  // start | copied in | unpacked | synthesised | copied out
     double ms[4] = {0, 0, 0, 0};
 };
 
 // Noise-to-mask ratio of `.pac` files against their source (mrc_api_nmr.cpp): reused from call to call.  The parsing
-// tables, the error word and its page-locked copy are DecodeBufs'.
+// tables, the error word and its page-locked copy are DecodeBufs' (pac_parse).
 struct NmrBufs {
-    DevBuf in;                       // one H2D copy: bytes | plan | groups | entries | analysis offsets | file table | sources
+    DevBuf in;                       // one H2D copy (NmrStage): bytes | plan | groups | entries | analyses | file table | sources
     DevBuf groups;                   // dense per-(shape, kind) arrays of the parsed chunks
     DevBuf planes;                   // padded int16 source planes
     DevBuf lines, thresh, oscale, smr;   // source analysis per shape: X, T, overall scale, SMR (unused)
-    DevBuf out;                      // one D2H copy: per-file summaries | band noise | band mask
+    DevBuf out;                      // one D2H copy (NmrStage): per-file summaries | band noise | band mask
     DevBuf stat;                     // per entry: max r_j, b * mean r_j
     PinnedBuf pinIn, pinOut;
     EventSet<5> ev;                  // start | copied in | unpacked | source analysed | reduced and copied out
@@ -219,9 +220,9 @@ struct NmrBufs {
 };
 
 // Windows of resident `.pac` files (mrc_pac_store_decode_window, mrc_api_store.cpp): the workspace of one slab, reused from
-// slab to slab and from call to call.  The parsing tables, the error word and its page-locked copy are DecodeBufs'.
+// slab to slab and from call to call.  The parsing tables, the error word and its page-locked copy are DecodeBufs' (pac_parse).
 struct StoreBufs {
-    DevBuf in;                       // one H2D copy per slab: plan | group descriptors | block offsets | items
+    DevBuf in;                       // one H2D copy per slab (a StageLayout): plan | group descriptors | block offsets | items
     DevBuf groups;                   // dense per-(shape, kind) arrays of the parsed chunks
     DevBuf planes;                   // float64, window + 4 n_mdct_lines samples per item and decoded channel
     PinnedBuf pinIn;                 // written again only after the slab that read it has been synchronised
@@ -231,21 +232,24 @@ struct StoreBufs {
 // ---- the host plan of whole `.pac` files, shared by mrc_decode_pac_pcm16 and mrc_pac_nmr (mrc_api_decode.cpp)
 // Blocks are grouped exactly as pacfile.decode_pac groups them: a stereo file of more than one block is joint blocks
 // followed by the two non-joint chunks Close() wrote, every other file is non-joint blocks.  A group is a (block shape,
-// kind): group = shape * 2 + (non-joint), shapes in the order of UnpackBands: (L,L), (L,S), (S,L), (S,S).
+// kind): group = shape * 2 + (non-joint), shapes in the order of UnpackBands: (L,L), (L,S), (S,L), (S,S).  The slots and plan
+// entries a block takes are PacGroupCounts::add_block's (mrc_pac_stage.hpp).
+static_assert(kPacGroups == kUnpackGroups);
 struct PacFilePlan {
     int nch = 0;
     int64_t firstChunk = 0, nChunks = 0;   // into the call's chunk list
     int64_t xStart = 0, extent = 0, total = 0;   // where the file's decoded plane starts; its length; last start + a + b
 };
-struct PacPlan {
+struct PacPlan : PacGroupCounts {
     // pac_plan_scan
     std::vector<PacFilePlan> files;
+    std::vector<int64_t> fileBase;         // [files]: where each file starts, relative to the first file's first byte
     std::vector<int64_t> chunkOff;         // relative to the first file's first byte
     std::vector<unsigned char> chunkShape;
     int64_t planeStride = 0;               // sum of the files' extents
     bool anyStereo = false;
-    // pac_plan_groups
-    int64_t nSlots[kUnpackGroups] = {}, nCat[2 * kUnpackGroups] = {}, slotBase[kUnpackGroups] = {}, totalSlots = 0;
+    // pac_plan_groups: nSlots, nCat, totalSlots (PacGroupCounts), then pac_plan_layout
+    int64_t slotBase[kUnpackGroups] = {};
     const HostShape* hs[4] = {};
     size_t gOff[kUnpackGroups][5] = {}, gBytes = 0;   // the groups' dense arrays in one device allocation
     int64_t nChunks() const { return (int64_t)chunkOff.size(); }
@@ -265,12 +269,17 @@ inline void shape_ab(const mrc_config& c, int s, int* a, int* b) {
     *a = (s & 2) ? c.n_short : c.n_mdct_lines;
     *b = (s & 1) ? c.n_short : c.n_mdct_lines;
 }
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 UnpackParams unpack_params(const mrc_config& c);
 int ensure_decode_consts(mrc_handle* h);           // decode tables + the four shapes' band tables, once per handle
 void decode_band_counts(const mrc_config& c, int nBands[4], std::vector<int>* cnt /* nullable: [4] */);   // host only
+// The error word of a parse: err <- {0, INT_MAX} on the stream before the unpack kernel; behind it, the copy back and the
+// wait: *bad = null when every chunk parsed, else the word (why, and the lowest bad chunk).  Shared by pac_parse and
+// mrc_dev_unpack_blocks, which differ in how they name the chunk.
 int reset_unpack_err(mrc_handle* h, hipStream_t st);
+int read_unpack_err(mrc_handle* h, hipStream_t st, const UnpackErr** bad);
 const char* unpack_status_text(int flag);
+// the preamble of every call that takes a list of files: offsets that do not decrease, bytes where there are files
+int check_file_list(mrc_handle* h, const char* fn, int64_t n_files, const uint8_t* buf, const int64_t* file_offset);
 void copy_host(void* dst, const void* src, size_t n);   // memcpy over a few host threads for large copies
 // headers, the handle's parameters, chunk scan with shape bits, block positions (host only: no device state is read or
 // touched).  fn names the entry point in errors.
@@ -346,10 +355,9 @@ struct mrc_pac_store {
     mrc_handle* h = nullptr;
     mrc::DevBuf bytes;               // the files back to back, as the caller passed them
     int64_t nBytes = 0;
-    mrc::PacPlan index;              // pac_plan_scan's: files, chunk offsets into `bytes`, chunk shapes
+    mrc::PacPlan index;              // pac_plan_scan's: files and where they start in `bytes`, chunk offsets into it, chunk shapes
     std::vector<int64_t> blockStart; // per block of every file, file after file: a_0 + .. + a_{i-1}
     std::vector<int64_t> firstBlock; // [files + 1] into blockStart
-    std::vector<int64_t> fileBase;   // [files + 1]: where each file's bytes start in `bytes`
     int64_t stats[4] = {0, 0, 0, 0}; // last decode_window: chunks parsed, decode_kernel launches, slabs, plan bytes uploaded
     double ms[4] = {0, 0, 0, 0};     // ... plan upload | unpack | synthesis | window_out_kernel
 };
@@ -430,6 +438,40 @@ inline int hip_fail(mrc_handle* h, hipError_t e, const char* what) {
         int rc_ = (expr);          \
         if (rc_ != MRC_OK) return rc_; \
     } while (0)
+
+// THE parse step of the `.pac` readers: event, the staging copy to the device, event, unpack_dense_kernel over the plan,
+// event, the verdict.  The caller says where its staging lives and where the plan entries and group descriptors sit in
+// it, and which device bytes the entries point into: the staging itself (whole-file decode, NMR) or a store's resident
+// bytes.  A bad chunk is refused as "<fn>: file F: chunk at byte B: <reason>", F and B from pac_locate_chunk over
+// fileBase (PacPlan::fileBase of the files the offsets count in).
+struct PacParse {
+    const void* pin;                 // the staging: page-locked host copy, device copy, bytes
+    void* dev;
+    size_t total, oPlan, oGroups;    // ... and where its plan entries [nChunks] and group descriptors [kUnpackGroups] sit
+    int64_t nChunks;
+    const uint8_t* bytes;            // device: what the entries' offsets point into, and its length
+    int64_t nBytes;
+    hipEvent_t ev[3];                // recorded: before the copy | copied | unpacked
+    hipStream_t st;
+};
+int pac_parse(mrc_handle* h, const char* fn, const std::vector<int64_t>& fileBase, const PacParse& p);
+
+// Every group of the plan that has slots: launch(g, its descriptor, its slots' offsets on the device).  gd: the host copy
+// of the descriptors, offs: the device offsets of all slots, group after group (slotBase).
+template <class Launch>
+int pac_for_groups(mrc_handle* h, const PacPlan& pl, const UnpackGroupDev* gd, const int64_t* offs, Launch launch) {
+    for (int g = 0; g < kUnpackGroups; ++g)
+        if (pl.nSlots[g]) MRC_HIP(h, launch(g, gd[g], offs + pl.slotBase[g]));
+    return MRC_OK;
+}
+// ... decode_kernel for each (full rate, a plane per channel): channel 0 into x, channel 1 of a joint slot planeStride behind
+inline int decode_groups(mrc_handle* h, const PacPlan& pl, const UnpackGroupDev* gd, const int64_t* offs, double* x,
+                         int64_t planeStride, hipStream_t st) {
+    return pac_for_groups(h, pl, gd, offs, [&](int g, const UnpackGroupDev& G, const int64_t* o) {
+        return launch_decode(pl.hs[g / 2]->dev, pl.nSlots[g], G.joint ? 2 : 1, G.oscale, G.joint ? G.ms : nullptr, G.sf, G.ba,
+                             G.mant, o, x, G.joint ? x + planeStride : nullptr, st);
+    });
+}
 
 // Whichever way a function is left, nothing it queued on these streams still touches the caller's memory or the host
 // temporaries declared before the guard.  (Null entries are skipped.)
