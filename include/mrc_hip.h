@@ -808,7 +808,8 @@ int mrc_pac_store_info(mrc_pac_store* s, int64_t* n_files, int32_t* n_channels /
  * of whole items (MRC_OPT_STORE_SLAB_SAMPLES); the workspace is the handle's, sized by the slab and reused.
  * mrc_pac_store_stats, for the store's last mrc_pac_store_decode_window(_reduced, _mix): stats = chunks parsed, decode_kernel launches,
  * slabs, bytes of plan uploaded (no file bytes among them); ms = device time of the plan upload, the unpack kernel, the
- * synthesis (zeroing the planes + decode_kernel launches) and window_out_kernel, summed over the slabs. */
+ * synthesis (zeroing the planes + decode_kernel launches) and window_out_kernel, summed over the slabs.  After
+ * mrc_pac_store_block_energy the same slots describe that call (see there). */
 int mrc_pac_store_decode_window(mrc_pac_store* s, int64_t n_items, const int64_t* file /*[n_items]*/,
                                 const int64_t* start /*[n_items]*/, int64_t window, int n_channels_out, int format,
                                 void* out /* DEVICE [n_items][n_channels_out][window] */, void* stream);
@@ -863,6 +864,43 @@ int mrc_pac_store_decode_window_reduced(mrc_pac_store* s, int rate_divisor, int6
 int mrc_pac_store_decode_window_mix(mrc_pac_store* s, int rate_divisor, int mix, int64_t n_items, const int64_t* file /*[n_items]*/,
                                     const int64_t* start /*[n_items]*/, int64_t window, int format,
                                     void* out /* DEVICE [n_items][1][window] */, void* stream);
+/* mrc_pac_store_block_energy: how much of the decoded signal's energy each block of the selected files holds, from the MDCT
+ * lines alone -- no inverse transform, no plane, no output tensor.  The windowed MDCT with the codec's transition windows is
+ * an orthogonal lapped transform (mdct.py: forward factor 2 / N, inverse factor 2), so with x^ a block's decoded lines
+ *   sum_t x[t]^2 = sum_i (a_i + b_i) sum_k x^_i[k]^2
+ * over the whole overlap-added plane of a channel (the MDCT's first n_mdct_lines samples included), and the reduced plane of
+ * mrc_pac_store_decode_window_reduced obeys the same identity with the lines it keeps.  An entry is a (block, channel of the
+ * file) under MRC_MIX_EACH and a block under MRC_MIX_MID:
+ *   energy = ((a + b) / D) * sum_{k < (a + b) / (2 D)} x^[k]^2
+ * x^[k] the line mrc_pac_store_decode_window(_reduced) transforms for that channel (dequantised, divided by the overall
+ * scale, L / R rebuilt in M/S bands; the full shape's bands, a band that straddles the cut counted on its lines below it),
+ * or the mid's line as mrc_pac_store_decode_window_mix defines it; a mono file under MRC_MIX_MID gives its own channel.
+ * Where the energy lies in time is for the caller to say: block i is centred on its overlap halves, so it is usually
+ * spread over [block_start + a / 2, block_start + a + b / 2) of the padded plane (mrcaudiocodec_amd/levels.py).
+ * file [n_sel]: indices into the store, in any order, repeats allowed; NULL with n_sel = the store's file count: every file
+ * in order.  Entries are ordered by selected file, block, channel; selection k's are [entry_offset[k], entry_offset[k + 1]).
+ * entry_block (NULL or [entry_cap][3]): block_start, a, b of each entry's block at full rate, block_start in the padded plane
+ * as mrc_pac_index counts it.  energy: HOST memory [entry_cap].
+ * The order of every sum is fixed (lane l of a wave adds lines l, l + 64, ... in ascending order, then one fixed tree over
+ * the 64 lanes, then one multiplication; no atomics): results are bit-identical from call to call and do not depend on the
+ * order of the selection, on which files share the call or on the slab size.
+ * MRC_ERR_INVALID naming the argument, before any device work: mix not MRC_MIX_EACH or MRC_MIX_MID; rate_divisor not 1, 2
+ * or 4, or one of the handle's block shapes without a reduced shape (the refusal of mrc_pac_store_decode_window_reduced
+ * under this function's name); a file index outside the store; file NULL with another n_sel; entry_offset NULL.
+ * entry_cap below the entry count: MRC_ERR_NOMEM with entry_offset filled, nothing else written and no device work.
+ * ALL chunks of the selected files are parsed: a damaged chunk gives MRC_ERR_INVALID with file (its index in the store), byte
+ * offset and what the parser met, as a window over that block does; energy and entry_block are then unspecified.
+ * The call runs in slabs of whole blocks, in entry order, whose b / D sum to at most MRC_OPT_STORE_SLAB_SAMPLES (at least one
+ * block; 0: one slab), in the handle's workspace, and synchronises `stream` (NULL: the handle's) after each slab, because
+ * the parser's error word comes back.  mrc_pac_store_stats then describes this call: stats = chunks parsed,
+ * block_energy_kernel launches (one per slab and (shape, kind) group with blocks), slabs, bytes of plan uploaded; ms = plan
+ * upload, unpack kernel, block_energy_kernel, 0. */
+#define MRC_MIX_EACH  3   /* mrc_pac_store_block_energy only: every channel of the file, an entry each */
+int mrc_pac_store_block_energy(mrc_pac_store* s, int rate_divisor, int mix, int64_t n_sel,
+                               const int64_t* file /* [n_sel], NULL: every file in order */,
+                               int64_t* entry_offset /* [n_sel + 1] */, int64_t entry_cap,
+                               int64_t* entry_block /* NULL or [entry_cap][3]: block_start, a, b (full rate, padded plane) */,
+                               double* energy /* HOST [entry_cap] */, void* stream);
 /* mrc_synthesis_shape: the rule above for one block shape (a, b) and divisor, on the host alone (no handle, no device):
  * MRC_OK if blocks of shape (a, b) have a synthesis shape (a, b) / rate_divisor, else MRC_ERR_INVALID with the reason, the
  * divisor and the shape in mrc_last_error(NULL).  rate_divisor is any positive number here: 1 asks whether (a, b) itself

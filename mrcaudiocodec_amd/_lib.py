@@ -20,6 +20,7 @@ MRC_ERR_INVALID = -1
 MRC_ERR_NOMEM = -4
 MRC_WINDOW_PCM16, MRC_WINDOW_F32, MRC_WINDOW_F64 = 0, 1, 2      # mrc_pac_store_decode_window's formats
 MRC_MIX_MID, MRC_MIX_LEFT, MRC_MIX_RIGHT = 0, 1, 2               # mrc_pac_store_decode_window_mix's channels
+MRC_MIX_EACH = 3                                                 # mrc_pac_store_block_energy: every channel of the file
 MRC_OPT_STORE_SLAB_SAMPLES = 7
 # array arguments travel as plain addresses (c_void_p prototypes): numpy's typed `data_as` costs ~2.3 us per array, which
 # at thirteen arrays per call was a third of a one-block call through the drop-in seam; the names say what the C side expects
@@ -205,6 +206,8 @@ def _load():
                                                           C.c_int, C.c_void_p, C.c_void_p]),
         "mrc_pac_store_decode_window_mix": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, _i64p, _i64p, C.c_int64, C.c_int,
                                                       C.c_void_p, C.c_void_p]),
+        "mrc_pac_store_block_energy": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, _i64p, _i64p, C.c_int64, _i64p, _f64p,
+                                                 C.c_void_p]),
         "mrc_synthesis_shape": (C.c_int, [C.c_int, C.c_int, C.c_int]),
         "mrc_pac_store_stats": (C.c_int, [C.c_void_p, _i64p, _f64p]),
     }

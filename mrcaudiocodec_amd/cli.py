@@ -29,6 +29,10 @@ One channel:  python -m mrcaudiocodec_amd.cli -d in.pac out.wav --mix mid  (or l
 the same store (mrc_pac_store_decode_window_mix): the mid (L + R) / 2 of a stereo file, formed on the MDCT lines before the
 one inverse transform, or its left or right channel; a mono file gives its channel.  Composes with --rate-divisor, --start
 and --samples.
+Levels:  python -m mrcaudiocodec_amd.cli --levels a.pac [b.pac ...] [--levels-window N]  decodes nothing and writes nothing: per
+file one JSON line with its channels, samples, RMS level per channel (dB re full scale) and its loudest and quietest window of
+N samples (default one second) on the short-block grid with their starts, from the energies of the blocks' MDCT lines
+(mrc_pac_store_block_energy, levels.LevelMap).  Composes with --rate-divisor and --mix mid; refuses every other flag.
 
 Quality (mrc_pac_nmr): --nmr on an encode prints, per file written (every rung of a ladder), one JSON line with the
 noise-to-mask ratio of the file against the WAV, measured with the codec's own masking model: nmr_max_db (worst band),
@@ -419,6 +423,71 @@ def check_mix_args(mix, decode):
     return mix
 
 
+LEVELS_REFUSES = ("src", "dst", "-d", "--no-huffman", "--exact-spread", "--certify", "--bits-per-sample", "--nmr", "--measure",
+                  "--target-nmr", "--vbr-nmr", "--vbr-bytes", "--vbr-bits-per-sample", "--vbr-grid", "--start", "--samples")
+
+
+def check_levels_args(levels, levels_window, given):
+    """--levels as given (None: not given) with --levels-window -> (paths, window or None), or None without --levels.  It
+    reads `.pac` files and writes nothing: given (flag -> whether it was given, for LEVELS_REFUSES) must be empty of
+    positional files and of every encode, decode, excerpt and measure flag; --levels-window needs --levels and is >= 1."""
+    if levels is None:
+        if levels_window is not None:
+            raise ValueError("--levels-window is the window of --levels: it needs --levels")
+        return None
+    for flag in LEVELS_REFUSES:
+        if given.get(flag):
+            raise ValueError("--levels prints the levels of .pac files and nothing else: it does not go with %s%s"
+                             % (flag, " (name the files behind --levels)" if flag in ("src", "dst") else ""))
+    if levels_window is not None and (isinstance(levels_window, bool) or not isinstance(levels_window, (int, np.integer))
+                                      or int(levels_window) < 1):
+        raise ValueError("--levels-window: %r is not a positive number of samples" % (levels_window,))
+    return list(levels), (None if levels_window is None else int(levels_window))
+
+
+def levels_of_files(pac_paths, window=None, device_id=0, rate_divisor=1, mix=None):
+    """One dict per `.pac` file from its block energies (PacStore.levels: no file is decoded): file, channels, samples,
+    rms_db (per channel, over the whole file), window, and the loudest and quietest window of that many samples on the n_short
+    grid with their starts (None for a file shorter than the window).  window None: one second.  rate_divisor 2 or 4: all of
+    it at that fraction of the sample rate; mix "mid": of the mid (L + R) / 2, one channel."""
+    from .store import PacStore, check_levels_mix
+    rate_divisor = check_rate_divisor_args(rate_divisor, True)
+    check_levels_mix(mix, "--mix")
+    bufs, groups = [], {}
+    for i, p in enumerate(pac_paths):
+        with open(p, "rb") as fp:
+            bufs.append(fp.read())
+        try:
+            c, _, _, _ = pacfile.read_header(bufs[-1])
+        except MrcError as e:
+            raise ValueError("%s: not a .pac file (%s)" % (p, e))
+        if c.sample_rate % rate_divisor:
+            raise ValueError("--rate-divisor %d does not divide the sample rate of %s, %d Hz" % (rate_divisor, p, c.sample_rate))
+        groups.setdefault((c.sample_rate, c.n_mdct_lines, c.n_scale_bits, c.n_mant_size_bits), []).append(i)
+    out = [None] * len(pac_paths)
+    for (rate, lines, scale_bits, mant_bits), members in groups.items():
+        h = Handle(sample_rate=rate, n_mdct_lines=lines, n_scale_bits=scale_bits, n_mant_size_bits=mant_bits, device_id=device_id)
+        try:
+            with PacStore(h, [bufs[i] for i in members]) as store:
+                m = store.levels(rate_divisor, mix)
+                for k, i in enumerate(members):
+                    n = int(store.n_samples_at(rate_divisor)[k])
+                    w = rate // rate_divisor if window is None else window
+                    nch = 1 if mix == "mid" else int(store.n_channels[k])
+                    r = dict(file=pac_paths[i], channels=nch, samples=n, window=w,
+                             rms_db=[float(v) for v in m.window_rms_db([k], [0], n)[0, :nch]] if n else [float("-inf")] * nch,
+                             loudest_db=None, loudest_start=None, quietest_db=None, quietest_start=None)
+                    starts, db = m.grid_levels(k, w)
+                    if starts.size:
+                        hi, lo = int(np.argmax(db)), int(np.argmin(db))
+                        r.update(loudest_db=float(db[hi]), loudest_start=int(starts[hi]), quietest_db=float(db[lo]),
+                                 quietest_start=int(starts[lo]))
+                    out[i] = r
+        finally:
+            h.close()
+    return out
+
+
 def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=1, mix=None):
     """excerpt: None (the whole file, mrc_decode_pac_pcm16) or (start, samples): that many samples from sample `start` on
     (samples None: to the end of the file), decoded through a one-file PacStore -- only the blocks the excerpt overlaps are
@@ -528,8 +597,8 @@ def _join_vbr_grid(argv):
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Encode a mono or stereo 16-bit WAV to .pac (or, with -d, decode a .pac to WAV) "
                                              "on an MI355X")
-    ap.add_argument("src")
-    ap.add_argument("dst")
+    ap.add_argument("src", nargs="?", default=None)
+    ap.add_argument("dst", nargs="?", default=None)
     ap.add_argument("-d", "--decode", action="store_true")
     ap.add_argument("--no-huffman", action="store_true")
     ap.add_argument("--exact-spread", action="store_true",
@@ -571,14 +640,38 @@ def main(argv=None):
     ap.add_argument("--mix", default=None, metavar="CH",
                     help="with -d: write a one-channel WAV, CH = mid ((L + R) / 2 of a stereo file, formed on the MDCT lines), "
                          "left or right; composes with --rate-divisor, --start and --samples")
+    ap.add_argument("--levels", nargs="+", default=None, metavar="PAC",
+                    help="no src, no dst: print one JSON line per .pac file with its channels, samples, RMS level per channel "
+                         "(dB re full scale) and its loudest and quietest window on the short-block grid, from the block "
+                         "energies of the MDCT lines (nothing is decoded); composes with --rate-divisor and --mix mid")
+    ap.add_argument("--levels-window", type=int, default=None, metavar="N",
+                    help="with --levels: the window in samples (default: one second)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(_join_vbr_grid(sys.argv[1:] if argv is None else argv))
     try:
+        levels = check_levels_args(a.levels, a.levels_window, {
+            "src": a.src is not None, "dst": a.dst is not None, "-d": a.decode, "--no-huffman": a.no_huffman,
+            "--exact-spread": a.exact_spread, "--certify": a.certify, "--bits-per-sample": a.bits_per_sample is not None,
+            "--nmr": a.nmr, "--measure": a.measure, "--target-nmr": a.target_nmr is not None, "--vbr-nmr": a.vbr_nmr is not None,
+            "--vbr-bytes": a.vbr_bytes is not None, "--vbr-bits-per-sample": a.vbr_bits_per_sample is not None,
+            "--vbr-grid": a.vbr_grid is not None, "--start": a.start is not None, "--samples": a.samples is not None})
+        if levels is None and (a.src is None or a.dst is None):
+            raise ValueError("the following arguments are required: src, dst")
         excerpt = check_excerpt_args(a.start, a.samples, a.decode)
-        rate_divisor = check_rate_divisor_args(a.rate_divisor, a.decode)
-        mix = check_mix_args(a.mix, a.decode)
+        rate_divisor = check_rate_divisor_args(a.rate_divisor, a.decode or levels is not None)
+        mix = check_mix_args(a.mix, a.decode or levels is not None)
+        if levels is not None:
+            from .store import check_levels_mix
+            check_levels_mix(mix, "--mix")
     except ValueError as e:
         ap.error(str(e))
+    if levels is not None:
+        try:
+            for r in levels_of_files(levels[0], levels[1], a.device, rate_divisor, mix):
+                print(json.dumps(r))
+        except ValueError as e:
+            ap.error(str(e))
+        return
     if a.vbr_bytes is not None or a.vbr_bits_per_sample is not None or a.vbr_grid is not None:
         try:
             check_vbr_size_args(a.vbr_bytes, a.vbr_bits_per_sample, a.vbr_grid, a.bits_per_sample, a.target_nmr, a.vbr_nmr, a.dst,

@@ -36,6 +36,10 @@
 // single slot for left / right (the other channel's chunk is not in the plan) and for mid a PAIR: two neighbouring slots
 // of the non-joint group, which laid side by side are one slot of two streams, the group's pairs in front of its single
 // slots so that a workgroup finds its slot from its index alone.  pac_plan_layout sees slot counts as ever.
+//
+// block_energy, ((a + b) / D) * the sum of squares of a block's first 1 / D decoded lines, per channel or for the mid, for
+// every block of the selected files: the same slab plan (stage_slab, parse_slab) over runs of whole blocks instead of the
+// blocks of windows, then block_energy_kernel per group (mrc_kernels_store.hip) in place of planes, synthesis and output.
 #include "mrc_handle.hpp"
 
 #include <algorithm>
@@ -76,6 +80,99 @@ void needed_blocks(const mrc_pac_store& s, const mrc_config& cfg, int D, int64_t
         shape_ab(cfg, s.index.shape(f, i), &a, &b);
         if (p[i] + a + b > lo) out->push_back(Need{item, f, i});
     }
+}
+
+// rate_divisor of every call that takes one: 1, 2 or 4, and a reduced shape for each of the handle's four block shapes
+int check_divisor(mrc_handle* h, const std::string& w, int D) {
+    if (D != 1 && D != 2 && D != 4) return fail(h, MRC_ERR_INVALID, w + ": rate_divisor " + std::to_string(D) + " is not 1, 2 or 4");
+    for (int sh = 0; D > 1 && sh < 4; ++sh) {
+        int a, b;
+        shape_ab(h->cfg, sh, &a, &b);
+        const std::string refusal = synth_shape_refusal(a, b, D);
+        if (!refusal.empty()) return fail(h, MRC_ERR_INVALID, w + ": " + refusal);
+    }
+    return MRC_OK;
+}
+
+// The host side of one slab's parse, shared by decode_windows and block_energy: `needs`, the slab's blocks, become slots of
+// the (shape, kind) groups and plan entries that point into the resident bytes.
+//   slots    a joint block is one slot of two streams.  Any other block is one slot per chunk parsed: all of the file's, or
+//            under MRC_MIX_LEFT / _RIGHT the one asked for.  Under MRC_MIX_MID the two chunks of a stereo file's last block
+//            are a PAIR of neighbouring slots, the group's pairs in front of its single slots (nPairs per group).
+//   staging  plan | group descriptors | whatever more(&lay) adds once the slots are counted (pl holds them);
+//            StoreBufs' pinIn, in and groups are reserved for it, the descriptors and the plan entries written.
+//   visit(need, g, slot, ch, pair)   once per joint block (ch 0) and once per parsed chunk of any other block, in the
+//            order of `needs`: the caller's per-slot fields (pin is valid by then).
+// Counts the chunks and the staging's bytes into the store's stats.  What follows is pac_parse over the same fields.
+struct SlabStage {
+    size_t oPlan = 0, oGroups = 0, total = 0;
+    int64_t nChunks = 0, nPairs[kUnpackGroups] = {};
+    unsigned char* pin = nullptr;
+    UnpackGroupDev* gd = nullptr;                    // (in pin)
+};
+template <class More, class Visit>
+int stage_slab(mrc_pac_store* s, const char* fn, int mix, const std::vector<Need>& needs, PacPlan* plp, SlabStage* S, More more,
+               Visit visit) {
+    mrc_handle* h = s->h;
+    StoreBufs& b = h->store;
+    PacPlan& pl = *plp;
+    // chunks of a needed non-joint block that are parsed
+    const auto lastChunks = [mix](int nch) { return mix == MRC_MIX_LEFT || mix == MRC_MIX_RIGHT ? 1 : nch; };
+    pl.clear_counts();
+    *S = SlabStage{};
+    for (const Need& n : needs) {
+        const int nch = lastChunks(s->index.files[(size_t)n.file].nch), sh = s->index.shape(n.file, n.block);
+        const bool joint = n.block < s->index.nJoint(n.file);
+        pl.add_block(sh, joint, nch);
+        if (!joint && mix == MRC_MIX_MID && nch == 2) S->nPairs[sh * 2 + 1] += 1;
+    }
+    MRC_TRY(pac_plan_layout(h, fn, &pl));
+    S->nChunks = pl.nEntries();
+
+    StageLayout lay(256);
+    S->oPlan = lay.add<UnpackPlanEntry>(S->nChunks);
+    S->oGroups = lay.add<UnpackGroupDev>(kUnpackGroups);
+    more(&lay);
+    S->total = lay.total();
+    MRC_HIP(h, b.pinIn.reserve(S->total));
+    MRC_HIP(h, b.in.reserve(S->total));
+    MRC_HIP(h, b.groups.reserve(std::max<size_t>(pl.gBytes, 256)));
+    S->pin = (unsigned char*)b.pinIn.p;
+    S->gd = (UnpackGroupDev*)(S->pin + S->oGroups);
+    UnpackPlanEntry* plan = (UnpackPlanEntry*)(S->pin + S->oPlan);
+    pac_plan_group_descs(h->dec, pl, S->gd, b.groups.as<unsigned char>());
+    int64_t catPos[2 * kUnpackGroups], slotNext[kUnpackGroups] = {}, pairNext[kUnpackGroups] = {};
+    for (int64_t k = 0, q = 0; k < 2 * kUnpackGroups; q += pl.nCat[k], ++k) catPos[k] = q;
+    for (int g = 0; g < kUnpackGroups; ++g) slotNext[g] = 2 * S->nPairs[g];      // (joint groups, and every group without mid: 0)
+    for (const Need& n : needs) {
+        const PacFilePlan& fi = s->index.files[(size_t)n.file];
+        const int64_t c0 = fi.firstChunk + n.block * fi.nch;
+        const int sh = s->index.chunkShape[(size_t)c0];
+        if (n.block < s->index.nJoint(n.file)) {
+            const int g = sh * 2, slot = (int)slotNext[g]++;
+            for (int ch = 0; ch < 2; ++ch)
+                plan[catPos[sh * 4 + ch]++] = UnpackPlanEntry{s->index.chunkOff[(size_t)c0 + ch], g * 2 + ch, slot};
+            visit(n, g, slot, 0, false);
+        } else {
+            const int g = sh * 2 + 1, nParsed = lastChunks(fi.nch), ch0 = fi.nch == 2 && mix == MRC_MIX_RIGHT ? 1 : 0;
+            const bool pair = mix == MRC_MIX_MID && fi.nch == 2;
+            for (int ch = ch0; ch < ch0 + nParsed; ++ch) {
+                const int slot = (int)(pair ? pairNext[g]++ : slotNext[g]++);
+                plan[catPos[sh * 4 + 2]++] = UnpackPlanEntry{s->index.chunkOff[(size_t)c0 + ch], g * 2, slot};
+                visit(n, g, slot, ch, pair);
+            }
+        }
+    }
+    s->stats[0] += S->nChunks;
+    s->stats[3] += (int64_t)S->total;
+    return MRC_OK;
+}
+// ... and its device side: the staging to the device, unpack_dense_kernel over the plan, the parser's verdict (pac_parse)
+int parse_slab(mrc_pac_store* s, const char* fn, const SlabStage& S, hipStream_t st) {
+    StoreBufs& b = s->h->store;
+    return pac_parse(s->h, fn, s->index.fileBase,
+                     PacParse{S.pin, b.in.p, S.total, S.oPlan, S.oGroups, S.nChunks, s->bytes.as<uint8_t>(), s->nBytes,
+                              {b.ev[0], b.ev[1], b.ev[2]}, st});
 }
 
 }  // namespace
@@ -153,13 +250,7 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
     const int mix = mixArg ? *mixArg : kNoMix;
     if (mixArg && mix != MRC_MIX_MID && mix != MRC_MIX_LEFT && mix != MRC_MIX_RIGHT)
         return fail(h, MRC_ERR_INVALID, w + ": mix " + std::to_string(mix) + " is not MRC_MIX_MID (0), MRC_MIX_LEFT (1) or MRC_MIX_RIGHT (2)");
-    if (D != 1 && D != 2 && D != 4) return fail(h, MRC_ERR_INVALID, w + ": rate_divisor " + std::to_string(D) + " is not 1, 2 or 4");
-    for (int sh = 0; D > 1 && sh < 4; ++sh) {
-        int a, b;
-        shape_ab(cfg, sh, &a, &b);
-        const std::string refusal = synth_shape_refusal(a, b, D);
-        if (!refusal.empty()) return fail(h, MRC_ERR_INVALID, w + ": " + refusal);
-    }
+    MRC_TRY(check_divisor(h, w, D));
     const int64_t nFiles = (int64_t)s->index.files.size(), L = cfg.n_mdct_lines / D;      // L: the margin unit, reduced samples
     if (n_items < 0) return fail(h, MRC_ERR_INVALID, w + ": n_items < 0");
     if (window < 0 || window > ((int64_t)1 << 40)) return fail(h, MRC_ERR_INVALID, w + ": window must lie in [0, 2^40]");
@@ -179,7 +270,6 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
     if (n_items == 0 || window == 0) return MRC_OK;
 
     MRC_TRY(ensure_decode_consts(h));
-    DecodeBufs& d = h->dec;
     StoreBufs& b = h->store;
     MRC_HIP(h, b.ev.create());
     hipStream_t st = pick_stream(h, stream);
@@ -190,8 +280,6 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
 
     std::vector<Need> needs;
     std::vector<WindowItem> items;
-    // chunks of a needed non-joint block that are parsed: all of the file's, but under left / right the one asked for
-    const auto lastChunks = [mix](int nch) { return mix == MRC_MIX_LEFT || mix == MRC_MIX_RIGHT ? 1 : nch; };
     PacPlan pl;                                              // (its group fields: the slab's slots)
     for (int64_t first = 0, last; first < n_items; first = last) {
         last = first + 1;
@@ -218,71 +306,36 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
             MRC_HIP(h, hipMemsetAsync(outSlab, 0, (size_t)nSlab * n_channels_out * window * elem, st));
             continue;
         }
-        pl.clear_counts();
-        // mid: the two chunks of a stereo file's last block are a PAIR of neighbouring slots of the non-joint group, the
-        // pairs in front of the group's single slots (launch_decode_mix)
-        int64_t nPairs[kUnpackGroups] = {};
-        for (const Need& n : needs) {
-            const int nch = lastChunks(s->index.files[(size_t)n.file].nch), sh = s->index.shape(n.file, n.block);
-            const bool joint = n.block < s->index.nJoint(n.file);
-            pl.add_block(sh, joint, nch);
-            if (!joint && mix == MRC_MIX_MID && nch == 2) nPairs[sh * 2 + 1] += 1;
-        }
-        MRC_TRY(pac_plan_layout(h, fn, &pl));
+        // ---- staging (one H2D copy): plan | groups | block offsets | items; a slot's offset is its block's place in the item's
+        // plane: the block's position in the file's padded plane, the window's start at 2 L
+        size_t oOffs = 0, oItems = 0;
+        SlabStage S;
+        MRC_TRY(stage_slab(
+            s, fn, mix, needs, &pl, &S,
+            [&](StageLayout* lay) {
+                oOffs = lay->add<long long>(pl.totalSlots);
+                oItems = lay->add<WindowItem>(nSlab);
+            },
+            [&](const Need& n, int g, int slot, int ch, bool pair) {
+                const WindowItem& it = items[(size_t)n.item];
+                long long* offs = (long long*)(S.pin + oOffs) + pl.slotBase[g];
+                const int64_t at = it.plane + 2 * L + s->blockStart[(size_t)(s->firstBlock[(size_t)n.file] + n.block)] / D - (it.start + L);
+                // a pair's workgroup is its index among the pairs; a single slot's comes after the group's pairs; without a
+                // mix a channel has a plane of its own
+                if (pair) offs[slot / 2] = at;
+                else offs[slot - S.nPairs[g]] = at + (mix == kNoMix ? ch * planeLen : 0);
+            }));
+        const int64_t* nPairs = S.nPairs;
+        const UnpackGroupDev* gd = S.gd;
+        std::memcpy(S.pin + oItems, items.data(), sizeof(WindowItem) * nSlab);
         const HostShape* reduced[4] = {};
         for (int sh = 0; D > 1 && sh < 4; ++sh)
             if (pl.hs[sh]) MRC_TRY(get_synth_shape(h, pl.hs[sh]->dev.a, pl.hs[sh]->dev.b, D, &reduced[sh]));
-        const int64_t nChunks = pl.nEntries();
-
-        // ---- staging (one H2D copy): plan | groups | block offsets | items
-        StageLayout lay(256);
-        const size_t oPlan = lay.add<UnpackPlanEntry>(nChunks), oGroups = lay.add<UnpackGroupDev>(kUnpackGroups),
-                     oOffs = lay.add<long long>(pl.totalSlots), oItems = lay.add<WindowItem>(nSlab), inTotal = lay.total();
-        MRC_HIP(h, b.pinIn.reserve(inTotal));
-        MRC_HIP(h, b.in.reserve(inTotal));
-        MRC_HIP(h, b.groups.reserve(std::max<size_t>(pl.gBytes, 256)));
         MRC_HIP(h, b.planes.reserve(sizeof(double) * (size_t)planeDoubles));
-        unsigned char* pin = (unsigned char*)b.pinIn.p;
-        UnpackPlanEntry* plan = (UnpackPlanEntry*)(pin + oPlan);
-        UnpackGroupDev* gd = (UnpackGroupDev*)(pin + oGroups);
-        long long* offs = (long long*)(pin + oOffs);
-        std::memcpy(pin + oItems, items.data(), sizeof(WindowItem) * nSlab);
-        pac_plan_group_descs(d, pl, gd, b.groups.as<unsigned char>());
-        int64_t catPos[2 * kUnpackGroups], slotNext[kUnpackGroups] = {}, pairNext[kUnpackGroups] = {};
-        for (int64_t k = 0, q = 0; k < 2 * kUnpackGroups; q += pl.nCat[k], ++k) catPos[k] = q;
-        for (int g = 0; g < kUnpackGroups; ++g) slotNext[g] = 2 * nPairs[g];      // (joint groups, and every group without mid: 0)
-        for (const Need& n : needs) {
-            const PacFilePlan& fi = s->index.files[(size_t)n.file];
-            const WindowItem& it = items[(size_t)n.item];
-            const int64_t c0 = fi.firstChunk + n.block * fi.nch;
-            const int sh = s->index.chunkShape[(size_t)c0];
-            // the block's place in the item's plane: its position in the file's padded plane, the window's start at 2 L
-            const int64_t at = it.plane + 2 * L + s->blockStart[(size_t)(s->firstBlock[(size_t)n.file] + n.block)] / D - (it.start + L);
-            if (n.block < s->index.nJoint(n.file)) {
-                const int g = sh * 2, slot = (int)slotNext[g]++;
-                for (int ch = 0; ch < 2; ++ch)
-                    plan[catPos[sh * 4 + ch]++] = UnpackPlanEntry{s->index.chunkOff[(size_t)c0 + ch], g * 2 + ch, slot};
-                offs[pl.slotBase[g] + slot] = at;
-            } else {
-                const int g = sh * 2 + 1, nParsed = lastChunks(fi.nch), ch0 = fi.nch == 2 && mix == MRC_MIX_RIGHT ? 1 : 0;
-                const bool pair = mix == MRC_MIX_MID && fi.nch == 2;
-                if (pair) offs[pl.slotBase[g] + pairNext[g] / 2] = at;
-                for (int ch = ch0; ch < ch0 + nParsed; ++ch) {
-                    const int slot = (int)(pair ? pairNext[g]++ : slotNext[g]++);
-                    plan[catPos[sh * 4 + 2]++] = UnpackPlanEntry{s->index.chunkOff[(size_t)c0 + ch], g * 2, slot};
-                    // a single slot's workgroup comes after the group's pairs; without a mix a channel has a plane of its own
-                    if (!pair) offs[pl.slotBase[g] + slot - nPairs[g]] = at + (mix == kNoMix ? ch * planeLen : 0);
-                }
-            }
-        }
-        s->stats[0] += nChunks;
-        s->stats[3] += (int64_t)inTotal;
 
         // ---- device: the parse step (the plan entries point into the resident bytes), then one launch per group with slots
         unsigned char* din = b.in.as<unsigned char>();
-        MRC_TRY(pac_parse(h, fn, s->index.fileBase,
-                          PacParse{pin, din, inTotal, oPlan, oGroups, nChunks, s->bytes.as<uint8_t>(), s->nBytes,
-                                   {b.ev[0], b.ev[1], b.ev[2]}, st}));
+        MRC_TRY(parse_slab(s, fn, S, st));
         double* x = b.planes.as<double>();
         MRC_HIP(h, hipEventRecord(b.ev[3], st));
         MRC_HIP(h, hipMemsetAsync(x, 0, sizeof(double) * (size_t)planeDoubles, st));
@@ -316,6 +369,135 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
     return MRC_OK;
 }
 
+// mrc_pac_store_block_energy: every block of the selected files through the slab's parse (stage_slab, parse_slab: the
+// planner of decode_windows) and block_energy_kernel, one launch per group with slots; no plane, no inverse transform.
+// A slab is a run of whole blocks, in the order of the entries, whose b / D sum to at most MRC_OPT_STORE_SLAB_SAMPLES (one
+// block at least): its entries are consecutive, so its energies come back in one copy.
+int block_energy(mrc_pac_store* s, int D, int mixArg, int64_t n_sel, const int64_t* file, int64_t* entry_offset, int64_t entry_cap,
+                 int64_t* entry_block, double* energy, void* stream) {
+    const char* const fn = "mrc_pac_store_block_energy";
+    MRC_TRY(store_alive(s, fn));
+    mrc_handle* h = s->h;
+    const mrc_config& cfg = h->cfg;
+    const std::string w = fn;
+    for (int i = 0; i < 4; ++i) { s->stats[i] = 0; s->ms[i] = 0.0; }
+    if (mixArg != MRC_MIX_EACH && mixArg != MRC_MIX_MID)
+        return fail(h, MRC_ERR_INVALID, w + ": mix " + std::to_string(mixArg) + " is not MRC_MIX_EACH (3) or MRC_MIX_MID (0)");
+    const int mix = mixArg == MRC_MIX_MID ? MRC_MIX_MID : kNoMix;
+    MRC_TRY(check_divisor(h, w, D));
+    const int64_t nFiles = (int64_t)s->index.files.size();
+    if (n_sel < 0) return fail(h, MRC_ERR_INVALID, w + ": n_sel < 0");
+    if (!file && n_sel != nFiles)
+        return fail(h, MRC_ERR_INVALID, w + ": file is NULL (every file in order) but n_sel = " + std::to_string(n_sel) + " is not the store's " +
+                                            std::to_string(nFiles) + " files");
+    if (!entry_offset) return fail(h, MRC_ERR_INVALID, w + ": entry_offset is NULL");
+    if (entry_cap < 0) return fail(h, MRC_ERR_INVALID, w + ": entry_cap < 0");
+    const auto fileOf = [file](int64_t k) { return file ? file[k] : k; };
+    for (int64_t k = 0; k < n_sel; ++k)
+        if (fileOf(k) < 0 || fileOf(k) >= nFiles)
+            return fail(h, MRC_ERR_INVALID, w + ": file[" + std::to_string(k) + "] = " + std::to_string(fileOf(k)) + " is outside the store's " +
+                                                std::to_string(nFiles) + " files");
+    const auto columns = [&](int64_t f) { return mix == kNoMix ? s->index.files[(size_t)f].nch : 1; };
+    entry_offset[0] = 0;
+    for (int64_t k = 0; k < n_sel; ++k) entry_offset[k + 1] = entry_offset[k] + s->index.nBlocks(fileOf(k)) * columns(fileOf(k));
+    const int64_t nEntries = entry_offset[n_sel];
+    if (nEntries > entry_cap)
+        return fail(h, MRC_ERR_NOMEM, w + ": entry_cap = " + std::to_string(entry_cap) + " is too small for " + std::to_string(nEntries) + " entries");
+    if (nEntries == 0) return MRC_OK;
+    if (!energy) return fail(h, MRC_ERR_INVALID, w + ": energy is NULL");
+
+    MRC_TRY(ensure_decode_consts(h));
+    StoreBufs& b = h->store;
+    MRC_HIP(h, b.ev.create());
+    hipStream_t st = pick_stream(h, stream);
+    DrainGuard drain{{st, nullptr, nullptr}};
+    const int64_t slab = h->storeSlabSamples, blockCap = (int64_t)1 << 28;      // (entries and slots of a launch stay below 2^31)
+
+    std::vector<Need> needs;
+    std::vector<EnergyEntry> entries[kUnpackGroups];
+    PacPlan pl;                                              // (its group fields: the slab's slots)
+    int64_t k = 0, blk = 0;                                  // the next block: block blk of selection k
+    while (k < n_sel && s->index.nBlocks(fileOf(k)) == 0) ++k;
+    while (k < n_sel) {
+        // ---- the slab's blocks, from (k, blk) on
+        needs.clear();
+        const int64_t firstEntry = entry_offset[k] + blk * columns(fileOf(k));
+        int64_t nSlabEntries = 0;
+        for (int64_t samples = 0; k < n_sel;) {
+            const int64_t f = fileOf(k);
+            int a, bb;
+            shape_ab(cfg, s->index.shape(f, blk), &a, &bb);
+            if (!needs.empty() && ((slab != 0 && samples + bb / D > slab) || (int64_t)needs.size() >= blockCap)) break;
+            samples += bb / D;
+            needs.push_back(Need{k, f, blk});
+            nSlabEntries += columns(f);
+            if (entry_block) {
+                const int64_t p = s->blockStart[(size_t)(s->firstBlock[(size_t)f] + blk)];
+                for (int64_t e = entry_offset[k] + blk * columns(f), c = 0; c < columns(f); ++c, ++e) {
+                    entry_block[3 * e] = p;
+                    entry_block[3 * e + 1] = a;
+                    entry_block[3 * e + 2] = bb;
+                }
+            }
+            if (++blk == s->index.nBlocks(f)) {
+                blk = 0;
+                do ++k; while (k < n_sel && s->index.nBlocks(fileOf(k)) == 0);
+            }
+        }
+        s->stats[2] += 1;
+
+        // ---- staging (one H2D copy): plan | groups | entries, group after group
+        for (auto& v : entries) v.clear();
+        size_t oEntries = 0;
+        SlabStage S;
+        MRC_TRY(stage_slab(
+            s, fn, mix, needs, &pl, &S, [&](StageLayout* lay) { oEntries = lay->add<EnergyEntry>(nSlabEntries); },
+            [&](const Need& n, int g, int slot, int ch, bool pair) {
+                const long long out = entry_offset[n.item] + n.block * columns(n.file) - firstEntry;
+                const bool joint = !(g & 1);
+                if (mix == MRC_MIX_MID) {                    // one entry per block: a joint slot, a pair (at its first slot) or a mono slot
+                    if (!pair || ch == 0) entries[g].push_back(EnergyEntry{out, slot, joint || pair ? kEnergyMid : 0});
+                } else if (joint) {
+                    for (int c = 0; c < 2; ++c) entries[g].push_back(EnergyEntry{out + c, slot, c});
+                } else {
+                    entries[g].push_back(EnergyEntry{out + ch, slot, 0});
+                }
+            }));
+        int64_t entryBase[kUnpackGroups], q = 0;
+        for (int g = 0; g < kUnpackGroups; ++g) {
+            entryBase[g] = q;
+            if (!entries[g].empty())
+                std::memcpy(S.pin + oEntries + sizeof(EnergyEntry) * (size_t)q, entries[g].data(), sizeof(EnergyEntry) * entries[g].size());
+            q += (int64_t)entries[g].size();
+        }
+        if (q != nSlabEntries) return fail(h, MRC_ERR_INVALID, w + ": internal error: a slab's entries do not add up");
+        MRC_HIP(h, b.planes.reserve(sizeof(double) * (size_t)nSlabEntries));
+
+        // ---- device: the parse step, one block_energy_kernel launch per group with slots, the energies back
+        MRC_TRY(parse_slab(s, fn, S, st));
+        double* e = b.planes.as<double>();
+        const EnergyEntry* entDev = (const EnergyEntry*)(b.in.as<unsigned char>() + oEntries);
+        MRC_HIP(h, hipEventRecord(b.ev[3], st));
+        for (int g = 0; g < kUnpackGroups; ++g) {
+            if (entries[g].empty()) continue;
+            const UnpackGroupDev& G = S.gd[g];
+            MRC_HIP(h, launch_block_energy(pl.hs[g / 2]->dev, D, G.joint, (int64_t)entries[g].size(), entDev + entryBase[g], G.oscale,
+                                           G.joint ? G.ms : nullptr, G.sf, G.ba, G.mant, e, st));
+            s->stats[1] += 1;
+        }
+        MRC_HIP(h, hipEventRecord(b.ev[4], st));
+        MRC_HIP(h, hipMemcpyAsync(energy + firstEntry, e, sizeof(double) * (size_t)nSlabEntries, hipMemcpyDeviceToHost, st));
+        MRC_HIP(h, hipStreamSynchronize(st));                // (the staging is written again by the next slab)
+        const int span[3][2] = {{0, 1}, {1, 2}, {3, 4}};
+        for (int i = 0; i < 3; ++i) {
+            double ms = 0.0;
+            MRC_HIP(h, b.ev.elapsed(span[i][0], span[i][1], &ms));
+            s->ms[i] += ms;
+        }
+    }
+    return MRC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -334,6 +516,11 @@ int mrc_pac_store_decode_window_reduced(mrc_pac_store* s, int rate_divisor, int6
 int mrc_pac_store_decode_window_mix(mrc_pac_store* s, int rate_divisor, int mix, int64_t n_items, const int64_t* file,
                                     const int64_t* start, int64_t window, int format, void* out, void* stream) {
     return decode_windows(s, kWinMix, rate_divisor, &mix, n_items, file, start, window, 1, format, out, stream);
+}
+
+int mrc_pac_store_block_energy(mrc_pac_store* s, int rate_divisor, int mix, int64_t n_sel, const int64_t* file,
+                               int64_t* entry_offset, int64_t entry_cap, int64_t* entry_block, double* energy, void* stream) {
+    return block_energy(s, rate_divisor, mix, n_sel, file, entry_offset, entry_cap, entry_block, energy, stream);
 }
 
 int mrc_synthesis_shape(int a, int b, int rate_divisor) {

@@ -360,6 +360,7 @@ struct mrc_pac_store {
     std::vector<int64_t> firstBlock; // [files + 1] into blockStart
     int64_t stats[4] = {0, 0, 0, 0}; // last decode_window: chunks parsed, decode_kernel launches, slabs, plan bytes uploaded
     double ms[4] = {0, 0, 0, 0};     // ... plan upload | unpack | synthesis | window_out_kernel
+                                     // (after block_energy: block_energy_kernel launches in [1]; ms: upload | unpack | that kernel | 0)
 };
 
 struct mrc_handle {

@@ -254,6 +254,14 @@ struct WindowItem {                  // one item of a slab
 // n_mdct_lines, divided by the rate divisor where there is one.)
 hipError_t launch_window_out(int64_t nItems, const WindowItem* items /* device */, int64_t window, int nchOut, int format,
                              int L, const double* planes, void* out, hipStream_t st);
+// One entry of mrc_pac_store_block_energy: a channel of a block, or its mid.  sel 0 / 1: output channel L / R of a joint
+// slot (a non-joint slot has one channel, itself: 0); kEnergyMid: the mid (L + R) / 2 on the lines -- of a joint slot, or of
+// the PAIR of non-joint slots slot, slot + 1 (a stereo file's last block).
+constexpr int kEnergyMid = 2;
+struct EnergyEntry { long long out; int slot, sel; };   // out: where its energy goes
+hipError_t launch_block_energy(const DevShape& F, int D, int joint, int64_t nEntries, const EnergyEntry* entries /* device */,
+                               const int* oscale, const int* msSwitch, const int* scaleFactor, const int* bitAlloc,
+                               const int* mantissa, double* energy, hipStream_t st);
 // mrc_kernels_chain.hip -- chained stream encode: reservoir-free preparation per block, serial scan per stream
 constexpr int kChainMaxLinesPerItem = 2 * 1024;  // coded lines one scan item holds (all its streams together)
 constexpr int kChainGroups = 5;    // chained encode: the four joint block shapes + Close()'s non-joint long block

@@ -16,6 +16,15 @@ D m + (D - 1) / 2 -- (D - 1) / 2 full-rate samples after full-rate sample D m.
 mix = "mid", "left" or "right" (mrc_pac_store_decode_window_mix) gives ONE channel of every file, stereo or mono: left and
 right are the bits of that channel of the two-channel call; mid is (L + R) / 2 formed on the MDCT lines, where most bands
 of a stereo file hold it already, so that a stereo block costs one inverse transform, one plane and one output row.
+
+levels (mrc_pac_store_block_energy) answers how loud every stretch of every file is without decoding it: the sum of squares
+of each block's decoded MDCT lines IS the energy the block adds to the signal (Parseval on the orthogonal lapped transform),
+and levels.LevelMap turns those numbers into window levels, admissible crop starts, reproducible draws and gains:
+
+        m = store.levels()                                                     # every file, per channel; cached
+        starts = m.sample_starts(files, 48000, -40.0, np.random.default_rng(0))   # crops at or above -40 dB RMS
+        x = store.decode_window(files, starts, 48000, dtype=torch.float32)
+        x *= torch.from_numpy(m.gains_to(-20.0, files, starts, 48000)).to(x)[:, None, None]
 """
 import ctypes as C
 
@@ -48,6 +57,18 @@ def check_mix(mix, channels=None, what="decode_window"):
     return MIXES[mix]
 
 
+def check_levels_mix(mix, what="levels"):
+    """mix of PacStore.levels -> MRC_MIX_EACH (None: every channel) or MRC_MIX_MID, else ValueError"""
+    if mix is None:
+        return _lib.MRC_MIX_EACH
+    if isinstance(mix, str) and mix in ("left", "right"):
+        raise ValueError('%s: mix=%r is a column of mix=None (every channel): ask for that and take channel %d'
+                         % (what, mix, ("left", "right").index(mix)))
+    if not isinstance(mix, str) or mix != "mid":
+        raise ValueError('%s: mix must be None or "mid", got %r' % (what, mix))
+    return _lib.MRC_MIX_MID
+
+
 def _formats():
     import torch
     return {torch.int16: _lib.MRC_WINDOW_PCM16, torch.float32: _lib.MRC_WINDOW_F32, torch.float64: _lib.MRC_WINDOW_F64}
@@ -70,6 +91,7 @@ class PacStore:
         if not data.size:
             data = np.zeros(1, np.uint8)
         self._handle = handle
+        self._levels = {}                # levels() of every file, per (rate_divisor, mix)
         self._s = C.c_void_p()
         handle._check(lib.mrc_pac_store_create(handle._h, n, data.ctypes.data, file_offset.ctypes.data, C.byref(self._s)))
         self.n_channels = np.zeros(n, np.int32)
@@ -162,9 +184,61 @@ class PacStore:
             self._handle._check(lib.mrc_pac_store_decode_window_reduced(self._s, rate_divisor, *tail))
         return out
 
+    def block_energy(self, rate_divisor=1, mix=None, files=None):
+        """mrc_pac_store_block_energy -> (entry_offset [n + 1], blocks [entries][3] (block_start, a, b), energy [entries]):
+        one entry per block and channel of every selected file (files: indices into the store; None: every file in order), or
+        per block with mix="mid"; selection k's entries are [entry_offset[k], entry_offset[k + 1]), ordered by block, then
+        channel.  Every chunk of the selected files is parsed; nothing is synthesised."""
+        rate_divisor = check_rate_divisor(rate_divisor, "levels")
+        mix = check_levels_mix(mix)
+        if files is None:
+            sel, n = None, len(self)
+            counts = self.n_blocks * (1 if mix == _lib.MRC_MIX_MID else self.n_channels)
+        else:
+            sel = np.ascontiguousarray(np.asarray(files, dtype=np.int64).reshape(-1))
+            n = sel.size
+            if n and (sel.min() < 0 or sel.max() >= len(self)):
+                raise ValueError("levels: files must be indices into the store's %d files, got %r" % (len(self), files))
+            counts = (self.n_blocks * (1 if mix == _lib.MRC_MIX_MID else self.n_channels))[sel]
+        cap = int(np.sum(counts))
+        entry_offset = np.zeros(n + 1, np.int64)
+        blocks, energy = np.zeros((max(cap, 1), 3), np.int64), np.zeros(max(cap, 1), np.float64)
+        self._handle._check(lib.mrc_pac_store_block_energy(self._s, rate_divisor, mix, n, None if sel is None else sel.ctypes.data,
+                                                           entry_offset.ctypes.data, cap, blocks.ctypes.data, energy.ctypes.data,
+                                                           None))
+        return entry_offset, blocks[:cap], energy[:cap]
+
+    def levels(self, rate_divisor=1, mix=None, files=None):
+        """-> a levels.LevelMap of the selected files (files: indices into the store, map file k = files[k]; None: every file,
+        and the map is cached per (rate_divisor, mix)) at 1 / rate_divisor of the sample rate, in the coordinates of
+        decode_window at that divisor: per channel (mix=None) or of the mid (mix="mid": one channel per file, a mono file its
+        own).  "left" and "right" are columns of mix=None and are refused, like every other argument error, with a ValueError
+        before any library call.  One call parses every chunk of the selected files once (block_energy_kernel: the sum of
+        squares of each block's decoded lines, no inverse transform)."""
+        from .levels import LevelMap
+        rate_divisor = check_rate_divisor(rate_divisor, "levels")
+        check_levels_mix(mix)
+        if files is None and (rate_divisor, mix) in self._levels:
+            return self._levels[(rate_divisor, mix)]
+        entry_offset, blocks, energy = self.block_energy(rate_divisor, mix, files)
+        sel = np.arange(len(self)) if files is None else np.asarray(files, dtype=np.int64).reshape(-1)
+        cfg = self._handle.cfg
+        per_file = []
+        for k, f in enumerate(sel):
+            lo, hi = int(entry_offset[k]), int(entry_offset[k + 1])
+            nch = 1 if mix == "mid" else int(self.n_channels[f])
+            per_file.append(dict(blocks=blocks[lo:hi:nch], energy=energy[lo:hi].reshape(-1, nch),
+                                 n_samples=int(self.n_samples[f]) // rate_divisor))
+        m = LevelMap(per_file, cfg.n_mdct_lines, rate_divisor, cfg.n_short)
+        if files is None:
+            self._levels[(rate_divisor, mix)] = m
+        return m
+
     def stats(self):
         """of the last decode_window: chunks_parsed, decode_launches, slabs, plan_bytes_uploaded, and ms: the device time of
-        the plan upload, the unpack kernel, the synthesis and window_out_kernel, summed over the slabs"""
+        the plan upload, the unpack kernel, the synthesis and window_out_kernel, summed over the slabs.  After levels() or
+        block_energy(): decode_launches counts block_energy_kernel launches, ms["synthesis"] is that kernel's time and
+        ms["window_out"] is 0."""
         st, ms = np.zeros(4, np.int64), np.zeros(4, np.float64)
         self._handle._check(lib.mrc_pac_store_stats(self._s, st.ctypes.data, ms.ctypes.data))
         r = {k: int(v) for k, v in zip(STAT_NAMES, st)}
