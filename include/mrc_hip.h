@@ -895,7 +895,7 @@ int mrc_pac_store_decode_window_mix(mrc_pac_store* s, int rate_divisor, int mix,
  * the parser's error word comes back.  mrc_pac_store_stats then describes this call: stats = chunks parsed,
  * block_energy_kernel launches (one per slab and (shape, kind) group with blocks), slabs, bytes of plan uploaded; ms = plan
  * upload, unpack kernel, block_energy_kernel, 0. */
-#define MRC_MIX_EACH  3   /* mrc_pac_store_block_energy only: every channel of the file, an entry each */
+#define MRC_MIX_EACH  3   /* mrc_pac_store_block_energy, _band_energy_window: every channel of the file, an entry each */
 int mrc_pac_store_block_energy(mrc_pac_store* s, int rate_divisor, int mix, int64_t n_sel,
                                const int64_t* file /* [n_sel], NULL: every file in order */,
                                int64_t* entry_offset /* [n_sel + 1] */, int64_t entry_cap,
@@ -906,6 +906,50 @@ int mrc_pac_store_block_energy(mrc_pac_store* s, int rate_divisor, int mix, int6
  * divisor and the shape in mrc_last_error(NULL).  rate_divisor is any positive number here: 1 asks whether (a, b) itself
  * has an inverse transform. */
 int mrc_synthesis_shape(int a, int b, int rate_divisor);
+/* mrc_band_line_ranges: which MDCT lines of a block of shape (a, b) a set of frequency bands holds, on the host alone (no
+ * handle, no device).  With halfN = (a + b) / 2, line k lies at f_k = (k + 0.5) * ((sample_rate / halfN) / 2.) -- the
+ * reference's own expression, in float64 (psychoac.py:94) -- and line_lo[q] is the number of lines with f_k < edge_hz[q]
+ * (its comparison, psychoac.py:99).  Band q, [edge_hz[q], edge_hz[q + 1]), holds lines [line_lo[q], line_lo[q + 1]), which
+ * may be none: a short block has few lines, and a band narrower than its line spacing that no line centre falls into is
+ * empty there.  Lines below edge_hz[0] or at or above edge_hz[n_bands] belong to no band.  MRC_ERR_INVALID naming the
+ * argument (mrc_last_error(NULL)): n_bands outside 1..MRC_MAX_STORE_BANDS, an edge that is not finite, edge_hz[0] < 0,
+ * edges not strictly increasing, a shape mrc_synthesis_shape(a, b, 1) refuses. */
+#define MRC_MAX_STORE_BANDS 256
+int mrc_band_line_ranges(double sample_rate, int a, int b, int n_bands, const double* edge_hz /*[n_bands+1]*/,
+                         int32_t* line_lo /*[n_bands+1]*/);
+/* mrc_pac_store_band_energy_window: a band-energy spectrogram of every item, from the MDCT lines alone -- no inverse
+ * transform, no plane, no STFT.  out[i][c][q][j] (DEVICE memory, [n_items][n_channels_out][n_bands][n_frames], float or
+ * double) is the energy of band q that frame j = [start[i] + j hop, start[i] + (j + 1) hop) of file file[i] holds, in the
+ * full-rate coordinates of mrc_pac_store_decode_window:
+ *   B_n[c][q]       = sum of x^_n,c[k]^2 over the lines k of band q (mrc_band_line_ranges for block n's shape, the
+ *                     handle's sample rate), x^ the lines mrc_pac_store_block_energy squares;
+ *   tile_n          = [p_n + a_n / 2 - L, p_n + a_n + b_n / 2 - L), L = n_mdct_lines: tiles abut and partition time;
+ *   out[i][c][q][j] = sum_n ov2(n, j) * B_n[c][q],   ov2 = 2 |tile_n and frame j|, an exact integer on doubled coordinates:
+ * a block's (a + b) B spread evenly over its (a + b) / 2 samples is 2 B per sample.  Summed over bands [0, fs / 2] and over
+ * frames that cover every tile this is the decoded signal's sum of squares (mrc_pac_store_block_energy's identity); a
+ * frame's value is local to within the blocks it cuts, and a band carries its neighbours' window leakage as any
+ * spectrogram does.  A band that holds no line of a block's shape reads 0 there.  A frame outside every tile is +0.0.
+ * mix: MRC_MIX_EACH with n_channels_out 1 or 2 (the channel map and the stereo-in-one-channel refusal of
+ * mrc_pac_store_decode_window), or MRC_MIX_MID / _LEFT / _RIGHT with n_channels_out 1 (the lines of
+ * mrc_pac_store_decode_window_mix; a mono file gives its own channel).  format: MRC_WINDOW_F32 or MRC_WINDOW_F64.
+ * Every bit is defined.  B is a left fold from +0.0 over k ascending, each square rounded once, then added (no fused
+ * multiply-add).  A frame's value is a left fold from +0.0, over the item's blocks in ascending order with ov2 > 0, of
+ * (double)ov2 * B; MRC_WINDOW_F32 is one conversion of it.  No atomics: results do not depend on the order of the items,
+ * on what shares the call, on the slab size or on the launch grid.
+ * Block n of an item is parsed iff its tile overlaps [start, start + n_frames hop) -- fewer blocks than a window of that
+ * length decodes; nothing is synthesised.  Damage inside such a block gives MRC_ERR_INVALID with file, byte offset and
+ * the parser's words; damage elsewhere is never read.  n_items = 0 or n_frames = 0: MRC_OK, nothing written.
+ * MRC_ERR_INVALID naming the argument, before any device work: a mix outside the four, n_channels_out wrong for the mix, a
+ * format other than F32 / F64, n_frames < 0, hop < 1, n_frames hop above 2^62, the refusals of mrc_band_line_ranges, a
+ * file index outside the store, out NULL with output to write, a stereo file in a one-channel MRC_MIX_EACH call.
+ * Slabs are whole items whose n_frames hop sum to at most MRC_OPT_STORE_SLAB_SAMPLES (one item at least; 0: one slab);
+ * `stream` (NULL: the handle's) is synchronised after each.  mrc_pac_store_stats then describes this call: stats = chunks
+ * parsed, band_energy_kernel launches (one per slab and (shape, kind) group with blocks), slabs, bytes of plan uploaded;
+ * ms = plan upload, unpack kernel, band sums (band_energy_kernel), frame assembly (band_frames_kernel). */
+int mrc_pac_store_band_energy_window(mrc_pac_store* s, int mix, int64_t n_items, const int64_t* file /*[n_items]*/,
+                                     const int64_t* start /*[n_items]*/, int64_t n_frames, int64_t hop, int n_bands,
+                                     const double* edge_hz /*[n_bands+1]*/, int n_channels_out, int format,
+                                     void* out /* DEVICE [n_items][n_channels_out][n_bands][n_frames] */, void* stream);
 
 /* Per-stage device time of the most recent timed call when timing is enabled (hipEvents on the launch stream; the call
  * then synchronises).  Timed: mrc_dev_encode / mrc_dev_encode_ex and mrc_encode_mono / mrc_encode_joint (the _blocks

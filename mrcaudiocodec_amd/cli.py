@@ -33,6 +33,10 @@ Levels:  python -m mrcaudiocodec_amd.cli --levels a.pac [b.pac ...] [--levels-wi
 file one JSON line with its channels, samples, RMS level per channel (dB re full scale) and its loudest and quietest window of
 N samples (default one second) on the short-block grid with their starts, from the energies of the blocks' MDCT lines
 (mrc_pac_store_block_energy, levels.LevelMap).  Composes with --rate-divisor and --mix mid; refuses every other flag.
+Band energies:  python -m mrcaudiocodec_amd.cli --band-energies in.pac out.npy --hop N [--band-edges f0,f1,...] [--mix CH]
+decodes nothing: out.npy holds float32 [channels][bands][frames], the energy of each band in frame [j N, (j + 1) N) of the
+file from its MDCT lines (mrc_pac_store_band_energy_window); default bands: the codec's critical bands.  Refuses every
+encode, decode and levels flag.
 
 Quality (mrc_pac_nmr): --nmr on an encode prints, per file written (every rung of a ladder), one JSON line with the
 noise-to-mask ratio of the file against the WAV, measured with the codec's own masking model: nmr_max_db (worst band),
@@ -488,6 +492,63 @@ def levels_of_files(pac_paths, window=None, device_id=0, rate_divisor=1, mix=Non
     return out
 
 
+BAND_ENERGIES_REFUSES = tuple(f for f in LEVELS_REFUSES if f not in ("src", "dst")) + ("--levels", "--levels-window", "--rate-divisor")
+
+
+def check_band_energies_args(band_energies, hop, band_edges, given):
+    """--band-energies as given with --hop and --band-edges -> (hop, edges as float64 or None: the critical bands), or None
+    without --band-energies.  It reads src, a `.pac` file, and writes dst, a .npy file: given (flag -> whether it was given, for
+    BAND_ENERGIES_REFUSES) must be empty of every encode, decode, excerpt, measure and levels flag; --hop is needed and >= 1;
+    --hop and --band-edges need --band-energies."""
+    if not band_energies:
+        for flag, v in (("--hop", hop), ("--band-edges", band_edges)):
+            if v is not None:
+                raise ValueError("%s belongs to --band-energies: it needs --band-energies" % flag)
+        return None
+    for flag in BAND_ENERGIES_REFUSES:
+        if given.get(flag):
+            raise ValueError("--band-energies writes the band energies of a .pac file and nothing else: it does not go with %s" % flag)
+    if hop is None or isinstance(hop, bool) or not isinstance(hop, (int, np.integer)) or int(hop) < 1:
+        raise ValueError("--band-energies needs --hop N, a positive number of samples, got %r" % (hop,))
+    edges = None
+    if band_edges is not None:
+        from .store import check_band_edges
+        try:
+            values = [float(v) for v in str(band_edges).split(",")]
+        except ValueError:
+            raise ValueError("--band-edges: %r is not a comma-separated list of frequencies in Hz" % (band_edges,))
+        edges = check_band_edges(values, "--band-edges")
+    return int(hop), edges
+
+
+def band_energies_of_file(pac_path, npy_path, hop, band_edges_hz=None, device_id=0, mix=None):
+    """The whole file's band energies (PacStore.band_energy_window: nothing is decoded) -> float32 [channels][bands][frames],
+    written to npy_path as a .npy file: frame j is samples [j hop, (j + 1) hop) of the decoded file, ceil(samples / hop)
+    frames; band_edges_hz None: store.critical_band_edges of the file's sample rate; mix "mid", "left" or "right": one
+    channel."""
+    import torch
+    from .store import PacStore, check_mix, critical_band_edges
+    check_mix(mix, None, "--mix")
+    with open(pac_path, "rb") as fp:
+        buf = fp.read()
+    try:
+        c, _, _, _ = pacfile.read_header(buf)
+    except MrcError as e:
+        raise ValueError("%s: not a .pac file (%s)" % (pac_path, e))
+    edges = critical_band_edges(c.sample_rate) if band_edges_hz is None else band_edges_hz
+    h = Handle(sample_rate=c.sample_rate, n_mdct_lines=c.n_mdct_lines, n_scale_bits=c.n_scale_bits,
+               n_mant_size_bits=c.n_mant_size_bits, device_id=device_id)
+    try:
+        with PacStore(h, [buf]) as store:
+            n_frames = -(-int(store.n_samples[0]) // hop)
+            e = store.band_energy_window([0], [0], n_frames, hop, edges, dtype=torch.float32, mix=mix)[0].cpu().numpy()
+    finally:
+        h.close()
+    with open(npy_path, "wb") as fp:
+        np.save(fp, e)
+    return e
+
+
 def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=1, mix=None):
     """excerpt: None (the whole file, mrc_decode_pac_pcm16) or (start, samples): that many samples from sample `start` on
     (samples None: to the end of the file), decoded through a one-file PacStore -- only the blocks the excerpt overlaps are
@@ -646,25 +707,43 @@ def main(argv=None):
                          "energies of the MDCT lines (nothing is decoded); composes with --rate-divisor and --mix mid")
     ap.add_argument("--levels-window", type=int, default=None, metavar="N",
                     help="with --levels: the window in samples (default: one second)")
+    ap.add_argument("--band-energies", action="store_true",
+                    help="src is a .pac file, dst a .npy file: write the whole file's band energies, float32 "
+                         "[channels][bands][frames], frame j = samples [j N, (j + 1) N) for --hop N, from the MDCT lines (nothing "
+                         "is decoded); composes with --band-edges and --mix")
+    ap.add_argument("--hop", type=int, default=None, metavar="N", help="with --band-energies: the frame length in samples")
+    ap.add_argument("--band-edges", default=None, metavar="F0,F1,...",
+                    help="with --band-energies: the band edges in Hz, increasing (default: 0, the codec's critical-band "
+                         "limits below Nyquist, Nyquist)")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(_join_vbr_grid(sys.argv[1:] if argv is None else argv))
     try:
-        levels = check_levels_args(a.levels, a.levels_window, {
+        given = {
             "src": a.src is not None, "dst": a.dst is not None, "-d": a.decode, "--no-huffman": a.no_huffman,
             "--exact-spread": a.exact_spread, "--certify": a.certify, "--bits-per-sample": a.bits_per_sample is not None,
             "--nmr": a.nmr, "--measure": a.measure, "--target-nmr": a.target_nmr is not None, "--vbr-nmr": a.vbr_nmr is not None,
             "--vbr-bytes": a.vbr_bytes is not None, "--vbr-bits-per-sample": a.vbr_bits_per_sample is not None,
-            "--vbr-grid": a.vbr_grid is not None, "--start": a.start is not None, "--samples": a.samples is not None})
+            "--vbr-grid": a.vbr_grid is not None, "--start": a.start is not None, "--samples": a.samples is not None}
+        bands = check_band_energies_args(a.band_energies, a.hop, a.band_edges, dict(
+            given, **{"--levels": a.levels is not None, "--levels-window": a.levels_window is not None,
+                      "--rate-divisor": a.rate_divisor is not None}))
+        levels = check_levels_args(a.levels, a.levels_window, given)
         if levels is None and (a.src is None or a.dst is None):
             raise ValueError("the following arguments are required: src, dst")
         excerpt = check_excerpt_args(a.start, a.samples, a.decode)
         rate_divisor = check_rate_divisor_args(a.rate_divisor, a.decode or levels is not None)
-        mix = check_mix_args(a.mix, a.decode or levels is not None)
+        mix = check_mix_args(a.mix, a.decode or levels is not None or bands is not None)
         if levels is not None:
             from .store import check_levels_mix
             check_levels_mix(mix, "--mix")
     except ValueError as e:
         ap.error(str(e))
+    if bands is not None:
+        try:
+            band_energies_of_file(a.src, a.dst, bands[0], bands[1], a.device, mix)
+        except ValueError as e:
+            ap.error(str(e))
+        return
     if levels is not None:
         try:
             for r in levels_of_files(levels[0], levels[1], a.device, rate_divisor, mix):

@@ -40,9 +40,17 @@
 // block_energy, ((a + b) / D) * the sum of squares of a block's first 1 / D decoded lines, per channel or for the mid, for
 // every block of the selected files: the same slab plan (stage_slab, parse_slab) over runs of whole blocks instead of the
 // blocks of windows, then block_energy_kernel per group (mrc_kernels_store.hip) in place of planes, synthesis and output.
+//
+// band_energy_window, those sums split by frequency band and laid on a frame grid: the same slab plan over the blocks whose
+// TILE [p + a / 2 - L, p + a + b / 2 - L) the item's frames overlap (tiles abut, so the needed blocks are one run found by two
+// binary searches in the file's edges, kept doubled so that half samples are integers), band_energy_kernel per group into
+// B [row][band] of the store workspace -- a row per needed block and decoded channel, an item's rows together -- then
+// band_frames_kernel over the slab's output; per item one descriptor and its run of edges go up with the plan, per shape
+// the band's line ranges (mrc_band_line_ranges, no handle and no device).
 #include "mrc_handle.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 
@@ -190,13 +198,16 @@ int mrc_pac_store_create(mrc_handle* h, int64_t n_files, const uint8_t* buf, con
     MRC_TRY(pac_plan_scan(h, "mrc_pac_store_create", n_files, buf, file_offset, &s->index));
     s->firstBlock.assign((size_t)n_files + 1, 0);
     for (int64_t f = 0; f < n_files; ++f) {
-        int64_t start = 0;
+        int64_t start = 0, tileEnd = 0;
         for (int64_t i = 0; i < s->index.nBlocks(f); ++i) {
             int a, b;
             shape_ab(h->cfg, s->index.shape(f, i), &a, &b);
             s->blockStart.push_back(start);
+            s->tileEdge.push_back(2 * start + a - 2 * (int64_t)h->cfg.n_mdct_lines);
+            tileEnd = 2 * start + 2 * a + b - 2 * (int64_t)h->cfg.n_mdct_lines;
             start += a;
         }
+        s->tileEdge.push_back(tileEnd);                      // (a file's edges: its blocks' + 1, from firstBlock[f] + f on)
         s->firstBlock[(size_t)f + 1] = (int64_t)s->blockStart.size();
     }
     s->nBytes = n_files ? file_offset[n_files] - file_offset[0] : 0;
@@ -498,9 +509,211 @@ int block_energy(mrc_pac_store* s, int D, int mixArg, int64_t n_sel, const int64
     return MRC_OK;
 }
 
+// mrc_band_line_ranges' rule; the refusal's words (the caller puts its own name in front), empty if there is none
+std::string band_line_ranges(double sampleRate, int a, int b, int nBands, const double* edge, int32_t* lineLo) {
+    if (nBands < 1 || nBands > MRC_MAX_STORE_BANDS)
+        return "n_bands " + std::to_string(nBands) + " is outside 1.." + std::to_string(MRC_MAX_STORE_BANDS);
+    if (!edge || !lineLo) return "edge_hz or line_lo is NULL";
+    for (int q = 0; q <= nBands; ++q)
+        if (!std::isfinite(edge[q])) return "edge_hz[" + std::to_string(q) + "] is not finite";
+    if (edge[0] < 0) return "edge_hz[0] < 0";
+    for (int q = 0; q < nBands; ++q)
+        if (!(edge[q] < edge[q + 1])) return "edge_hz is not strictly increasing at [" + std::to_string(q + 1) + "]";
+    if (!(sampleRate > 0) || !std::isfinite(sampleRate)) return "sample_rate is not a positive number";
+    const std::string refusal = synth_shape_refusal(a, b, 1);
+    if (!refusal.empty()) return refusal;
+    const int halfN = (a + b) / 2;
+    int k = 0;                                               // f_k does not decrease with k: one pass over lines and edges
+    for (int q = 0; q <= nBands; ++q) {
+        while (k < halfN && (k + 0.5) * ((sampleRate / halfN) / 2.) < edge[q]) ++k;      // psychoac.py:94, 99
+        lineLo[q] = k;
+    }
+    return std::string();
+}
+
+// mrc_pac_store_band_energy_window: the slab's parse (stage_slab, parse_slab) over the blocks whose TILES the items' frames
+// overlap, band_energy_kernel per group with slots into B [rows][n_bands] in the store workspace, band_frames_kernel
+// over the slab's output.  An item's rows are its needed blocks in file order, a row per decoded channel.
+int band_energy_window(mrc_pac_store* s, int mixArg, int64_t n_items, const int64_t* file, const int64_t* start, int64_t n_frames,
+                       int64_t hop, int n_bands, const double* edge_hz, int n_channels_out, int format, void* out, void* stream) {
+    const char* const fn = "mrc_pac_store_band_energy_window";
+    MRC_TRY(store_alive(s, fn));
+    mrc_handle* h = s->h;
+    const mrc_config& cfg = h->cfg;
+    const std::string w = fn;
+    for (int i = 0; i < 4; ++i) { s->stats[i] = 0; s->ms[i] = 0.0; }
+    if (mixArg != MRC_MIX_EACH && mixArg != MRC_MIX_MID && mixArg != MRC_MIX_LEFT && mixArg != MRC_MIX_RIGHT)
+        return fail(h, MRC_ERR_INVALID, w + ": mix " + std::to_string(mixArg) +
+                                            " is not MRC_MIX_EACH (3), MRC_MIX_MID (0), MRC_MIX_LEFT (1) or MRC_MIX_RIGHT (2)");
+    const int mix = mixArg == MRC_MIX_EACH ? kNoMix : mixArg;
+    if (mix == kNoMix ? n_channels_out != 1 && n_channels_out != 2 : n_channels_out != 1)
+        return fail(h, MRC_ERR_INVALID, w + (mix == kNoMix ? ": n_channels_out must be 1 or 2" : ": n_channels_out must be 1 under a mix of one channel"));
+    if (format != MRC_WINDOW_F32 && format != MRC_WINDOW_F64)
+        return fail(h, MRC_ERR_INVALID, w + ": format " + std::to_string(format) + " is not MRC_WINDOW_F32 (1) or MRC_WINDOW_F64 (2)");
+    if (n_items < 0) return fail(h, MRC_ERR_INVALID, w + ": n_items < 0");
+    if (n_frames < 0) return fail(h, MRC_ERR_INVALID, w + ": n_frames < 0");
+    if (hop < 1) return fail(h, MRC_ERR_INVALID, w + ": hop < 1");
+    if (n_frames > ((int64_t)1 << 62) / hop) return fail(h, MRC_ERR_INVALID, w + ": n_frames * hop is above 2^62");
+    int32_t lineLo[4][MRC_MAX_STORE_BANDS + 1];
+    for (int sh = 0; sh < 4; ++sh) {
+        int a, b;
+        shape_ab(cfg, sh, &a, &b);
+        const std::string refusal = band_line_ranges((double)cfg.sample_rate, a, b, n_bands, edge_hz, lineLo[sh]);
+        if (!refusal.empty()) return fail(h, MRC_ERR_INVALID, w + ": " + refusal);
+    }
+    const int64_t nFiles = (int64_t)s->index.files.size(), span = n_frames * hop;
+    if (n_items > 0 && (!file || !start)) return fail(h, MRC_ERR_INVALID, w + ": file or start is NULL");
+    if (n_items > 0 && n_frames > 0 && !out) return fail(h, MRC_ERR_INVALID, w + ": out is NULL");
+    for (int64_t k = 0; k < n_items; ++k) {
+        if (file[k] < 0 || file[k] >= nFiles)
+            return fail(h, MRC_ERR_INVALID, w + ": file[" + std::to_string(k) + "] = " + std::to_string(file[k]) + " is outside the store's " +
+                                                std::to_string(nFiles) + " files");
+        if (mix == kNoMix && s->index.files[(size_t)file[k]].nch > n_channels_out)
+            return fail(h, MRC_ERR_INVALID, w + ": item " + std::to_string(k) + ": file " + std::to_string(file[k]) +
+                                                " is stereo, the call asks for one channel");
+    }
+    if (n_items == 0 || n_frames == 0) return MRC_OK;
+
+    MRC_TRY(ensure_decode_consts(h));
+    StoreBufs& b = h->store;
+    MRC_HIP(h, b.ev.create());
+    hipStream_t st = pick_stream(h, stream);
+    DrainGuard drain{{st, nullptr, nullptr}};
+    const size_t elem = format == MRC_WINDOW_F32 ? 4 : 8;
+    const int64_t rowLen = (int64_t)n_channels_out * n_bands * n_frames;     // one item's output values
+    const int64_t slab = h->storeSlabSamples, itemCap = std::max<int64_t>(1, ((int64_t)1 << 38) / rowLen);   // (a launch's grid below 2^31)
+    const auto floorHalf = [](int64_t v) { return v >= 0 ? v / 2 : -((-v + 1) / 2); };
+
+    std::vector<Need> needs;
+    std::vector<BandItem> items;
+    std::vector<int64_t> firstTile;                          // per item: its first needed block
+    std::vector<EnergyEntry> entries[kUnpackGroups];
+    PacPlan pl;                                              // (its group fields: the slab's slots)
+    for (int64_t first = 0, last; first < n_items; first = last) {
+        last = first + 1;
+        while (last < n_items && last - first < itemCap && (slab == 0 || span <= slab / (last - first + 1))) ++last;
+        const int64_t nSlab = last - first;
+        unsigned char* outSlab = (unsigned char*)out + (size_t)first * (size_t)rowLen * elem;
+        s->stats[2] += 1;
+
+        // ---- the slab's items: the run of blocks whose tile overlaps [start, start + span), in doubled samples
+        // [2 start, 2 (start + span)) against the file's ascending edges; compared without doubling an extreme start
+        needs.clear();
+        items.assign((size_t)nSlab, BandItem{0, 0, 0, 0, 0, 0, 1});
+        firstTile.assign((size_t)nSlab, 0);
+        int64_t nRows = 0, nEdges = 0;
+        for (int64_t k = 0; k < nSlab; ++k) {
+            const int64_t f = file[first + k], nb = s->index.nBlocks(f), at = start[first + k];
+            if (nb == 0) continue;
+            const int64_t* E = s->tileEdge.data() + s->firstBlock[(size_t)f] + f;
+            const int64_t lo = floorHalf(E[0]), hi = floorHalf(E[nb]) + 1;       // lo <= E / 2 <= hi for every edge
+            if (at >= hi || (at < lo && lo - at >= span)) continue;              // behind the last tile, or ends before the first
+            const int64_t s2 = 2 * std::max(at, lo), e2 = 2 * std::min(at + span, hi);      // (at < hi: at + span fits)
+            const int64_t b0 = std::upper_bound(E + 1, E + nb + 1, s2) - (E + 1);           // first tile that ends behind s2
+            const int64_t b1 = std::lower_bound(E, E + nb, e2) - E;                         // first tile that starts at or behind e2
+            if (b0 >= b1) continue;
+            const int cols = mix == kNoMix ? s->index.files[(size_t)f].nch : 1;
+            items[(size_t)k] = BandItem{nEdges, nRows, at, lo, hi, (int)(b1 - b0), cols};
+            firstTile[(size_t)k] = b0;
+            for (int64_t i = b0; i < b1; ++i) needs.push_back(Need{k, f, i});
+            nRows += (b1 - b0) * cols;
+            nEdges += b1 - b0 + 1;
+        }
+        if (needs.empty()) {                                 // no tile under any frame: zeros, no launch
+            MRC_HIP(h, hipMemsetAsync(outSlab, 0, (size_t)nSlab * (size_t)rowLen * elem, st));
+            continue;
+        }
+        // ---- staging (one H2D copy): plan | groups | entries, group after group | line tables | tile edges | items
+        for (auto& v : entries) v.clear();
+        size_t oEntries = 0, oLines = 0, oEdges = 0, oItems = 0;
+        int64_t nSlabEntries = 0;
+        SlabStage S;
+        MRC_TRY(stage_slab(
+            s, fn, mix, needs, &pl, &S,
+            [&](StageLayout* lay) {
+                for (const Need& n : needs) nSlabEntries += mix == kNoMix ? s->index.files[(size_t)n.file].nch : 1;
+                oEntries = lay->add<EnergyEntry>(nSlabEntries);
+                oLines = lay->add<int32_t>(4 * (MRC_MAX_STORE_BANDS + 1));
+                oEdges = lay->add<long long>(nEdges);
+                oItems = lay->add<BandItem>(nSlab);
+            },
+            [&](const Need& n, int g, int slot, int ch, bool pair) {
+                const BandItem& it = items[(size_t)n.item];
+                const long long row = it.row0 + (n.block - firstTile[(size_t)n.item]) * it.nch;
+                const bool joint = !(g & 1);
+                if (mix == MRC_MIX_MID) {                    // one entry per block: a joint slot, a pair (at its first slot) or a mono slot
+                    if (!pair || ch == 0) entries[g].push_back(EnergyEntry{row, slot, joint || pair ? kEnergyMid : 0});
+                } else if (joint) {
+                    if (mix == kNoMix) for (int c = 0; c < 2; ++c) entries[g].push_back(EnergyEntry{row + c, slot, c});
+                    else entries[g].push_back(EnergyEntry{row, slot, mix == MRC_MIX_LEFT ? 0 : 1});
+                } else {
+                    entries[g].push_back(EnergyEntry{row + (mix == kNoMix ? ch : 0), slot, 0});
+                }
+            }));
+        int64_t entryBase[kUnpackGroups], q = 0;
+        for (int g = 0; g < kUnpackGroups; ++g) {
+            entryBase[g] = q;
+            if (!entries[g].empty())
+                std::memcpy(S.pin + oEntries + sizeof(EnergyEntry) * (size_t)q, entries[g].data(), sizeof(EnergyEntry) * entries[g].size());
+            q += (int64_t)entries[g].size();
+        }
+        if (q != nSlabEntries || q != nRows) return fail(h, MRC_ERR_INVALID, w + ": internal error: a slab's entries do not add up");
+        std::memcpy(S.pin + oLines, lineLo, sizeof lineLo);
+        long long* edges = (long long*)(S.pin + oEdges);
+        for (int64_t k = 0; k < nSlab; ++k) {
+            const BandItem& it = items[(size_t)k];
+            if (it.nTiles == 0) continue;
+            const int64_t f = file[first + k];
+            const int64_t* E = s->tileEdge.data() + s->firstBlock[(size_t)f] + f + firstTile[(size_t)k];
+            for (int64_t i = 0; i <= it.nTiles; ++i) edges[it.edge0 + i] = E[i];
+        }
+        std::memcpy(S.pin + oItems, items.data(), sizeof(BandItem) * (size_t)nSlab);
+        MRC_HIP(h, b.planes.reserve(sizeof(double) * (size_t)nRows * (size_t)n_bands));
+
+        // ---- device: the parse step, one band_energy_kernel launch per group with slots, the frames
+        MRC_TRY(parse_slab(s, fn, S, st));
+        unsigned char* din = b.in.as<unsigned char>();
+        double* B = b.planes.as<double>();
+        const EnergyEntry* entDev = (const EnergyEntry*)(din + oEntries);
+        MRC_HIP(h, hipEventRecord(b.ev[3], st));
+        for (int g = 0; g < kUnpackGroups; ++g) {
+            if (entries[g].empty()) continue;
+            const UnpackGroupDev& G = S.gd[g];
+            MRC_HIP(h, launch_band_energy(pl.hs[g / 2]->dev, G.joint, n_bands, (const int*)(din + oLines) + (g / 2) * (MRC_MAX_STORE_BANDS + 1),
+                                          (int64_t)entries[g].size(), entDev + entryBase[g], G.oscale, G.joint ? G.ms : nullptr, G.sf,
+                                          G.ba, G.mant, B, st));
+            s->stats[1] += 1;
+        }
+        MRC_HIP(h, hipEventRecord(b.ev[4], st));
+        MRC_HIP(h, launch_band_frames(nSlab, (const BandItem*)(din + oItems), (const long long*)(din + oEdges), n_frames, hop, n_bands,
+                                      n_channels_out, format, B, outSlab, st));
+        MRC_HIP(h, hipEventRecord(b.ev[5], st));
+        MRC_HIP(h, hipStreamSynchronize(st));                // (the staging is written again by the next slab)
+        const int span4[4][2] = {{0, 1}, {1, 2}, {3, 4}, {4, 5}};
+        for (int i = 0; i < 4; ++i) {
+            double ms = 0.0;
+            MRC_HIP(h, b.ev.elapsed(span4[i][0], span4[i][1], &ms));
+            s->ms[i] += ms;
+        }
+    }
+    MRC_HIP(h, hipStreamSynchronize(st));
+    return MRC_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int mrc_band_line_ranges(double sample_rate, int a, int b, int n_bands, const double* edge_hz, int32_t* line_lo) {
+    const std::string refusal = band_line_ranges(sample_rate, a, b, n_bands, edge_hz, line_lo);
+    return refusal.empty() ? MRC_OK : fail(nullptr, MRC_ERR_INVALID, "mrc_band_line_ranges: " + refusal);
+}
+
+int mrc_pac_store_band_energy_window(mrc_pac_store* s, int mix, int64_t n_items, const int64_t* file, const int64_t* start,
+                                     int64_t n_frames, int64_t hop, int n_bands, const double* edge_hz, int n_channels_out,
+                                     int format, void* out, void* stream) {
+    return band_energy_window(s, mix, n_items, file, start, n_frames, hop, n_bands, edge_hz, n_channels_out, format, out, stream);
+}
 
 int mrc_pac_store_decode_window(mrc_pac_store* s, int64_t n_items, const int64_t* file, const int64_t* start, int64_t window,
                                 int n_channels_out, int format, void* out, void* stream) {

@@ -358,9 +358,12 @@ struct mrc_pac_store {
     mrc::PacPlan index;              // pac_plan_scan's: files and where they start in `bytes`, chunk offsets into it, chunk shapes
     std::vector<int64_t> blockStart; // per block of every file, file after file: a_0 + .. + a_{i-1}
     std::vector<int64_t> firstBlock; // [files + 1] into blockStart
+    std::vector<int64_t> tileEdge;   // file f with blocks: nBlocks(f) + 1 edges from firstBlock[f] + f on, in DOUBLED output samples:
+                                     // block i's tile is [2 p_i + a_i - 2 L, 2 p_i + 2 a_i + b_i - 2 L), and tiles abut
     int64_t stats[4] = {0, 0, 0, 0}; // last decode_window: chunks parsed, decode_kernel launches, slabs, plan bytes uploaded
     double ms[4] = {0, 0, 0, 0};     // ... plan upload | unpack | synthesis | window_out_kernel
-                                     // (after block_energy: block_energy_kernel launches in [1]; ms: upload | unpack | that kernel | 0)
+                                     // (after block_energy: block_energy_kernel launches in [1]; ms: upload | unpack | that kernel | 0;
+                                     // after band_energy_window: band_energy_kernel launches; upload | unpack | band sums | frames)
 };
 
 struct mrc_handle {

@@ -262,6 +262,22 @@ struct EnergyEntry { long long out; int slot, sel; };   // out: where its energy
 hipError_t launch_block_energy(const DevShape& F, int D, int joint, int64_t nEntries, const EnergyEntry* entries /* device */,
                                const int* oscale, const int* msSwitch, const int* scaleFactor, const int* bitAlloc,
                                const int* mantissa, double* energy, hipStream_t st);
+// mrc_pac_store_band_energy_window.  band_energy_kernel: B[entry.out][q] = the sum of the squares of the entry's decoded
+// lines lineLo[q] <= k < lineLo[q + 1], a left fold from +0.0 in ascending k (entries as launch_block_energy's; lineLo
+// (device) [nBands + 1], the shape's table of mrc_band_line_ranges).
+hipError_t launch_band_energy(const DevShape& F, int joint, int nBands, const int* lineLo /* device */, int64_t nEntries,
+                              const EnergyEntry* entries /* device */, const int* oscale, const int* msSwitch,
+                              const int* scaleFactor, const int* bitAlloc, const int* mantissa, double* bandSums, hipStream_t st);
+// One item of band_frames_kernel: its needed blocks are tiles [edge[edge0 + t], edge[edge0 + t + 1]), t < nTiles, in DOUBLED
+// output samples, ascending and abutting; tile t's band sums of decoded channel c are row row0 + t * nch + c of B.  lo and
+// hi: output samples at or before the first and at or behind the last tile edge -- a frame's ends are clamped to them
+// before they are doubled, which changes no overlap and keeps every start, however extreme, inside 64 bits.
+struct BandItem { long long edge0, row0, start, lo, hi; int nTiles, nch; };
+// out [nItems][nchOut][nBands][nFrames] (MRC_WINDOW_F32 / _F64) <- frame j = [start + j hop, start + (j + 1) hop): the left
+// fold from +0.0 over the item's tiles in ascending order, of (double)(doubled overlap) * B, where the overlap is positive
+hipError_t launch_band_frames(int64_t nItems, const BandItem* items /* device */, const long long* edges /* device */,
+                              int64_t nFrames, int64_t hop, int nBands, int nchOut, int format, const double* bandSums,
+                              void* out, hipStream_t st);
 // mrc_kernels_chain.hip -- chained stream encode: reservoir-free preparation per block, serial scan per stream
 constexpr int kChainMaxLinesPerItem = 2 * 1024;  // coded lines one scan item holds (all its streams together)
 constexpr int kChainGroups = 5;    // chained encode: the four joint block shapes + Close()'s non-joint long block

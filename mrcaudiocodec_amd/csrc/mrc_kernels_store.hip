@@ -29,6 +29,28 @@
 //     step adds two values that hold the same kind of partial sum, and a + b == b + a, so every lane ends with the same
 //     bits), and lane 0 multiplies once by (a + b) / D, an integer.  Lanes past n contribute +0.0.  Nothing depends on
 //     the grid, on which entries share the launch, on their order or on the slab.  No floating-point atomics.
+//
+//   band_energy_kernel   block_energy_kernel's sum split by frequency band (mrc_pac_store_band_energy_window):
+//       B[entry][q] = sum of x^[k]^2 over lineLo[q] <= k < lineLo[q + 1],
+//     x^ the same lines, lineLo the shape's table of mrc_band_line_ranges.  The CONTRACT is the order: each band is a left
+//     fold from +0.0 over k ascending, every square rounded once, then added (no fused multiply-add) -- so a band cannot be
+//     spread over lanes, and the parallelism lies across bands and entries.  One workgroup of 256 threads per entry, in two
+//     phases per chunk of kBandChunk = 512 lines: all threads dequantise and square lines k = t, t + 256, ... into LDS (a
+//     wave reads 64 consecutive mantissa codes per step, as block_energy_kernel does; a line is decoded once, whatever
+//     the bands), then thread q continues band q's fold over the part of [lineLo[q], lineLo[q + 1]) inside the chunk,
+//     its sum in a register from chunk to chunk, reading eight squares ahead of their additions (the additions keep their
+//     order; without that every line costs an LDS round trip in the longest band's chain, 363 lines of a long block's
+//     last critical band, which every other thread of the workgroup waits for).  A long block of 1024 lines is two
+//     chunks, one of 8192 lines sixteen, in 4 KiB of LDS whatever the shape.  An empty band is +0.0; lines outside
+//     every band are decoded and not read.  Nothing depends on the grid, on which entries share the launch or on their
+//     order.
+//
+//   band_frames_kernel   B laid on the call's frame grid.  One thread per output value, frames fastest -- the flat index
+//     is the output's own, so a wave stores 64 consecutive values -- and a row is (item, output channel, band).  The
+//     item's needed blocks are abutting tiles in DOUBLED output samples (a tile edge is a half sample); the thread finds
+//     the first tile that ends behind its frame's start by bisection, then folds forward from +0.0 while tiles start
+//     before the frame's end: acc += (double)ov2 * B, ov2 = 2 |tile and frame| > 0 an exact integer.  A frame that meets
+//     no tile is +0.0.  MRC_WINDOW_F32 converts acc once.  No atomics; nothing depends on the grid or the slab.
 #include "mrc_decode_lines.hpp"
 
 namespace mrc {
@@ -65,6 +87,34 @@ __global__ __launch_bounds__(kWindowThreads) void window_out_kernel(const Window
 
 constexpr int kEnergyThreads = 256, kEnergyWave = 64;
 
+// The parsed arrays of one EnergyEntry and line k as the entry selects it: a channel's decode_line, the mid's
+// decode_line_mid, or for the pair of non-joint slots of a stereo file's last block 0.5 * (x0 + x1) as in decode_block.
+struct EntryLines {
+    const unsigned char* bandOfLine;
+    const int *os, *ms, *sf, *ba, *mant;
+    int nb, fullLines, nScaleBits, sel;
+    bool joint;
+    __device__ EntryLines(const EnergyEntry& e, const unsigned char* bandOfLine_, int nb_, int fullLines_, int nScaleBits_, int joint_,
+                          const int* oscale, const int* msSwitch, const int* scaleFactor, const int* bitAlloc, const int* mantissa)
+        : bandOfLine(bandOfLine_), nb(nb_), fullLines(fullLines_), nScaleBits(nScaleBits_), sel(e.sel), joint(joint_ != 0) {
+        const int64_t f = e.slot;
+        const int nStreams = joint ? 2 : 1;
+        sf = scaleFactor + f * nStreams * nb;
+        ba = bitAlloc + f * nStreams * nb;
+        mant = mantissa + f * nStreams * (int64_t)fullLines;
+        os = oscale + f * (joint ? 4 : 1);
+        ms = joint ? msSwitch + f * nb : nullptr;
+    }
+    __device__ double line(int k) const {
+        const int band = bandOfLine[k];
+        if (sel != kEnergyMid) return decode_line(k, band, sel, joint, nb, fullLines, nScaleBits, os, ms, sf, ba, mant);
+        if (joint) return decode_line_mid(k, band, nb, fullLines, nScaleBits, os, ms, sf, ba, mant);
+        const double x0 = decode_line(k, band, 0, false, nb, fullLines, nScaleBits, os, nullptr, sf, ba, mant);
+        const double x1 = decode_line(k, band, 0, false, nb, fullLines, nScaleBits, os + 1, nullptr, sf + nb, ba + nb, mant + fullLines);
+        return 0.5 * (x0 + x1);
+    }
+};
+
 __global__ __launch_bounds__(kEnergyThreads) void block_energy_kernel(const unsigned char* __restrict__ bandOfLine, int nb,
                                                                      int fullLines, int nScaleBits, int joint, int nLines,
                                                                      double factor, int64_t nEntries,
@@ -79,36 +129,93 @@ __global__ __launch_bounds__(kEnergyThreads) void block_energy_kernel(const unsi
     const int64_t w = (int64_t)blockIdx.x * (kEnergyThreads / kEnergyWave) + threadIdx.x / kEnergyWave;
     if (w >= nEntries) return;                                       // (the whole wave)
     const EnergyEntry e = entries[w];
-    const int64_t f = e.slot;
-    const int nStreams = joint ? 2 : 1;
-    const int* sf = scaleFactor + f * nStreams * nb;
-    const int* ba = bitAlloc + f * nStreams * nb;
-    const int* mant = mantissa + f * nStreams * (int64_t)fullLines;
-    const int* os = oscale + f * (joint ? 4 : 1);
-    const int* ms = joint ? msSwitch + f * nb : nullptr;
+    const EntryLines L(e, bandOfLine, nb, fullLines, nScaleBits, joint, oscale, msSwitch, scaleFactor, bitAlloc, mantissa);
     double acc = 0.0;
-    if (e.sel != kEnergyMid) {
-        for (int k = lane; k < nLines; k += kEnergyWave) {
-            const double x = decode_line(k, bandOfLine[k], e.sel, joint != 0, nb, fullLines, nScaleBits, os, ms, sf, ba, mant);
-            acc += x * x;
-        }
-    } else if (joint) {
-        for (int k = lane; k < nLines; k += kEnergyWave) {
-            const double x = decode_line_mid(k, bandOfLine[k], nb, fullLines, nScaleBits, os, ms, sf, ba, mant);
-            acc += x * x;
-        }
-    } else {                                                         // slots f, f + 1: the two channels of a stereo file's last block
-        for (int k = lane; k < nLines; k += kEnergyWave) {
-            const int band = bandOfLine[k];
-            const double x0 = decode_line(k, band, 0, false, nb, fullLines, nScaleBits, os, nullptr, sf, ba, mant);
-            const double x1 = decode_line(k, band, 0, false, nb, fullLines, nScaleBits, os + 1, nullptr, sf + nb, ba + nb,
-                                          mant + fullLines);
-            const double x = 0.5 * (x0 + x1);
-            acc += x * x;
-        }
+    for (int k = lane; k < nLines; k += kEnergyWave) {
+        const double x = L.line(k);
+        acc += x * x;
     }
     acc = wave_sum(acc);
     if (lane == 0) energy[e.out] = factor * acc;
+}
+
+constexpr int kBandThreads = 256, kBandChunk = 512;
+
+__global__ __launch_bounds__(kBandThreads) void band_energy_kernel(const unsigned char* __restrict__ bandOfLine, int nb,
+                                                                  int fullLines, int nScaleBits, int joint, int nBands,
+                                                                  const int* __restrict__ lineLo, int64_t nEntries,
+                                                                  const EnergyEntry* __restrict__ entries,
+                                                                  const int* __restrict__ oscale,
+                                                                  const int* __restrict__ msSwitch,
+                                                                  const int* __restrict__ scaleFactor,
+                                                                  const int* __restrict__ bitAlloc,
+                                                                  const int* __restrict__ mantissa,
+                                                                  double* __restrict__ bandSums) {
+    __shared__ double sq[kBandChunk];
+    const int t = threadIdx.x;
+    const EnergyEntry e = entries[blockIdx.x];
+    const EntryLines L(e, bandOfLine, nb, fullLines, nScaleBits, joint, oscale, msSwitch, scaleFactor, bitAlloc, mantissa);
+    // thread t folds band t (nBands <= MRC_MAX_STORE_BANDS = kBandThreads: the launcher refuses more)
+    const int lo = t < nBands ? lineLo[t] : 0, hi = t < nBands ? lineLo[t + 1] : 0;
+    double acc = 0.0;
+    for (int c0 = 0; c0 < fullLines; c0 += kBandChunk) {
+        const int c1 = min(c0 + kBandChunk, fullLines);
+        if (c0) __syncthreads();                                     // (the folds of the chunk before are done with sq)
+        for (int k = c0 + t; k < c1; k += kBandThreads) {
+            const double x = L.line(k);
+            sq[k - c0] = x * x;
+        }
+        __syncthreads();
+        // the fold, in order; eight squares are read ahead of their additions (one LDS round trip per eight, not per line)
+        int k = max(lo, c0);
+        const int kEnd = min(hi, c1);
+        for (; k + 8 <= kEnd; k += 8) {
+            double v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = sq[k - c0 + u];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) acc += v[u];
+        }
+        for (; k < kEnd; ++k) acc += sq[k - c0];
+    }
+    if (t < nBands) bandSums[e.out * nBands + t] = acc;
+}
+
+constexpr int kFrameThreads = 256;
+
+__global__ __launch_bounds__(kFrameThreads) void band_frames_kernel(const BandItem* __restrict__ items,
+                                                                   const long long* __restrict__ edges, int64_t total,
+                                                                   int64_t nFrames, int64_t hop, int nBands, int nchOut,
+                                                                   int format, const double* __restrict__ bandSums,
+                                                                   void* __restrict__ out) {
+    const int64_t o = (int64_t)blockIdx.x * kFrameThreads + threadIdx.x;      // out's own index: [item][channel][band][frame]
+    if (o >= total) return;
+    const int64_t row = o / nFrames, j = o - row * nFrames;
+    const int64_t ic = row / nBands;
+    const int q = (int)(row - ic * nBands);
+    const int64_t i = ic / nchOut;
+    const BandItem it = items[i];
+    const int c = it.nch == 2 ? (int)(ic - i * nchOut) : 0;
+    double acc = 0.0;
+    if (it.nTiles > 0) {
+        // the frame in doubled samples, its ends clamped to the item's tiles first (lo <= every edge / 2 <= hi)
+        const int64_t s = it.start + j * hop;                        // (start + nFrames hop was checked to fit)
+        const int64_t s2 = 2 * min(max(s, (int64_t)it.lo), (int64_t)it.hi), e2 = 2 * min(max(s + hop, (int64_t)it.lo), (int64_t)it.hi);
+        const long long* E = edges + it.edge0;
+        int a = 0, b = it.nTiles;                                    // the first tile with E[t + 1] > s2, or nTiles
+        while (a < b) {
+            const int m = (a + b) >> 1;
+            if (E[m + 1] > s2) b = m;
+            else a = m + 1;
+        }
+        const double* B = bandSums + (it.row0 + c) * nBands + q;
+        for (int tl = a; tl < it.nTiles && E[tl] < e2; ++tl) {
+            const int64_t ov2 = min((int64_t)E[tl + 1], e2) - max((int64_t)E[tl], s2);
+            if (ov2 > 0) acc += (double)ov2 * B[(int64_t)tl * it.nch * nBands];
+        }
+    }
+    if (format == MRC_WINDOW_F64) ((double*)out)[o] = acc;
+    else ((float*)out)[o] = (float)acc;
 }
 
 }  // namespace
@@ -136,6 +243,27 @@ hipError_t launch_block_energy(const DevShape& F, int D, int joint, int64_t nEnt
     hipLaunchKernelGGL(block_energy_kernel, dim3((unsigned)blocks), dim3(kEnergyThreads), 0, st, F.bandOfLine, F.nBands, F.halfN,
                        F.nScaleBits, joint, F.halfN / D, (double)(F.N / D), nEntries, entries, oscale, msSwitch, scaleFactor,
                        bitAlloc, mantissa, energy);
+    return hipGetLastError();
+}
+
+hipError_t launch_band_energy(const DevShape& F, int joint, int nBands, const int* lineLo, int64_t nEntries,
+                              const EnergyEntry* entries, const int* oscale, const int* msSwitch, const int* scaleFactor,
+                              const int* bitAlloc, const int* mantissa, double* bandSums, hipStream_t st) {
+    if (nEntries <= 0) return hipSuccess;
+    if (nBands < 1 || nBands > kBandThreads || nEntries > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(band_energy_kernel, dim3((unsigned)nEntries), dim3(kBandThreads), 0, st, F.bandOfLine, F.nBands, F.halfN,
+                       F.nScaleBits, joint, nBands, lineLo, nEntries, entries, oscale, msSwitch, scaleFactor, bitAlloc, mantissa,
+                       bandSums);
+    return hipGetLastError();
+}
+
+hipError_t launch_band_frames(int64_t nItems, const BandItem* items, const long long* edges, int64_t nFrames, int64_t hop,
+                              int nBands, int nchOut, int format, const double* bandSums, void* out, hipStream_t st) {
+    if (nItems <= 0 || nFrames <= 0) return hipSuccess;
+    const int64_t total = nItems * nchOut * nBands * nFrames, blocks = (total + kFrameThreads - 1) / kFrameThreads;
+    if (blocks > 0x7fffffffLL || (format != MRC_WINDOW_F32 && format != MRC_WINDOW_F64)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(band_frames_kernel, dim3((unsigned)blocks), dim3(kFrameThreads), 0, st, items, edges, total, nFrames, hop,
+                       nBands, nchOut, format, bandSums, out);
     return hipGetLastError();
 }
 

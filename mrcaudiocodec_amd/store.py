@@ -25,6 +25,13 @@ and levels.LevelMap turns those numbers into window levels, admissible crop star
         starts = m.sample_starts(files, 48000, -40.0, np.random.default_rng(0))   # crops at or above -40 dB RMS
         x = store.decode_window(files, starts, 48000, dtype=torch.float32)
         x *= torch.from_numpy(m.gains_to(-20.0, files, starts, 48000)).to(x)[:, None, None]
+
+band_energy_window (mrc_pac_store_band_energy_window) is the time-frequency feature that usually follows a crop, taken from
+the same sums split by frequency band and laid on a frame grid -- the coded file already is a time-frequency representation:
+
+        edges = critical_band_edges(48000)                                     # 0, 100, 200, ... 15500, 24000
+        e = store.band_energy_window(files, starts, 94, 512, edges)            # [len(files)][channels][25][94], on the GPU
+        logspec = torch.log10(e.clamp_min(1e-12))
 """
 import ctypes as C
 
@@ -67,6 +74,49 @@ def check_levels_mix(mix, what="levels"):
     if not isinstance(mix, str) or mix != "mid":
         raise ValueError('%s: mix must be None or "mid", got %r' % (what, mix))
     return _lib.MRC_MIX_MID
+
+
+MAX_BANDS = 256                          # MRC_MAX_STORE_BANDS
+# the codec's critical-band limits below the last (psychoac.py:82-84; the last band takes what is left, up to Nyquist)
+CRITICAL_BAND_LIMITS_HZ = (100, 200, 300, 400, 510, 630, 770, 920, 1080, 1270, 1480, 1720, 2000, 2320, 2700, 3150, 3700, 4400,
+                           5300, 6400, 7700, 9500, 12000, 15500)
+
+
+def critical_band_edges(sample_rate):
+    """0, the codec's 24 critical-band limits below Nyquist, Nyquist -> float64 [bands + 1]: at 48 kHz the 25 bands of a long
+    block's scale-factor table"""
+    nyquist = float(sample_rate) / 2.0
+    if not np.isfinite(nyquist) or nyquist <= 0:
+        raise ValueError("critical_band_edges: sample_rate must be a positive number, got %r" % (sample_rate,))
+    return np.array([0.0] + [float(f) for f in CRITICAL_BAND_LIMITS_HZ if f < nyquist] + [nyquist])
+
+
+def check_band_edges(band_edges_hz, what="band_energy_window"):
+    """band edges in Hz -> float64 [bands + 1], else ValueError: 1 to MAX_BANDS bands, finite, from 0 up, strictly increasing"""
+    try:
+        edges = np.ascontiguousarray(np.asarray(band_edges_hz, dtype=np.float64).reshape(-1))
+    except (TypeError, ValueError):
+        raise ValueError("%s: band_edges_hz must be a sequence of frequencies in Hz, got %r" % (what, band_edges_hz))
+    if not 2 <= edges.size <= MAX_BANDS + 1:
+        raise ValueError("%s: band_edges_hz must hold 2 to %d edges (1 to %d bands), got %d" % (what, MAX_BANDS + 1, MAX_BANDS, edges.size))
+    if not np.all(np.isfinite(edges)):
+        raise ValueError("%s: band_edges_hz must be finite, got %r" % (what, band_edges_hz))
+    if edges[0] < 0 or not np.all(np.diff(edges) > 0):
+        raise ValueError("%s: band_edges_hz must start at or above 0 and increase strictly, got %r" % (what, band_edges_hz))
+    return edges
+
+
+def band_line_ranges(sample_rate, a, b, band_edges_hz):
+    """mrc_band_line_ranges -> int32 [bands + 1]: band q of a block of shape (a, b) holds MDCT lines [r[q], r[q + 1]), line k
+    lying at (k + 0.5) * ((sample_rate / ((a + b) / 2)) / 2.).  No handle, no GPU.  MrcError where the library refuses."""
+    edges = np.ascontiguousarray(np.asarray(band_edges_hz, dtype=np.float64).reshape(-1))
+    lo = np.zeros(max(edges.size, 1), np.int32)
+    rc = lib.mrc_band_line_ranges(float(sample_rate), int(a), int(b), int(edges.size) - 1, edges.ctypes.data, lo.ctypes.data)
+    if rc:
+        err = _lib.MrcError("libmrc_hip error %d: %s" % (rc, lib.mrc_last_error(None).decode()))
+        err.code = rc
+        raise err
+    return lo
 
 
 def _formats():
@@ -184,6 +234,63 @@ class PacStore:
             self._handle._check(lib.mrc_pac_store_decode_window_reduced(self._s, rate_divisor, *tail))
         return out
 
+    def band_energy_window(self, files, starts, n_frames, hop, band_edges_hz, channels=None, dtype=None, out=None, stream=None,
+                           mix=None):
+        """mrc_pac_store_band_energy_window -> a torch tensor [n][channels][n_bands][n_frames] on the handle's device: the
+        energy that band q = [band_edges_hz[q], band_edges_hz[q + 1]) holds in frame j = samples [starts[i] + j hop,
+        starts[i] + (j + 1) hop) of file files[i] (decode_window's full-rate coordinates; starts may be negative or past the
+        end, a frame outside the file's blocks is 0), from the MDCT lines alone: each block's sum of squares per band, spread
+        evenly over the block's tile (levels.LevelMap's), so that bands [0, fs / 2] and frames over the whole file add up to
+        the decoded signal's sum of squares.  Only the blocks whose tile a frame touches are parsed; nothing is synthesised.
+        band_edges_hz: 2 to 257 increasing frequencies from 0 up (critical_band_edges(sample_rate): the codec's own bands);
+        a band narrower than a short block's line spacing may hold no line of such a block and then reads 0 there.
+        dtype: torch.float32 (the default) or torch.float64 (every bit defined: see the header).  channels, out, stream: as
+        decode_window's; mix: None (every channel), "mid", "left" or "right" (one channel, channels None or 1).  Argument
+        errors are ValueErrors before any library call."""
+        import torch
+        what = "band_energy_window"
+        mix = check_mix(mix, channels, what)
+        if mix is not None:
+            channels = 1
+        files = np.ascontiguousarray(np.asarray(files, dtype=np.int64).reshape(-1))
+        starts = np.ascontiguousarray(np.asarray(starts, dtype=np.int64).reshape(-1))
+        if files.shape != starts.shape:
+            raise ValueError("%s: one start per file index (%d files, %d starts)" % (what, files.size, starts.size))
+        for name, v, least in (("n_frames", n_frames, 0), ("hop", hop, 1)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < least:
+                raise ValueError("%s: %s must be an int >= %d, got %r" % (what, name, least, v))
+        n, n_frames, hop = files.size, int(n_frames), int(hop)
+        if n_frames * hop > 1 << 62:
+            raise ValueError("%s: n_frames * hop must not exceed 2^62, got %d * %d" % (what, n_frames, hop))
+        edges = check_band_edges(band_edges_hz, what)
+        if dtype is None:
+            dtype = torch.float32 if out is None else out.dtype
+        if dtype not in (torch.float32, torch.float64):
+            raise ValueError("%s: dtype must be torch.float32 or torch.float64, got %s" % (what, dtype))
+        if channels is None:
+            inside = files[(files >= 0) & (files < len(self))]
+            channels = int(self.n_channels[inside].max()) if inside.size else 1
+        if isinstance(channels, bool) or not isinstance(channels, (int, np.integer)) or int(channels) not in (1, 2):
+            raise ValueError("%s: channels must be None, 1 or 2, got %r" % (what, channels))
+        channels = int(channels)
+        if n and (files.min() < 0 or files.max() >= len(self)):
+            raise ValueError("%s: files must be indices into the store's %d files, got %r" % (what, len(self), files.tolist()))
+        if mix is None and n and int(self.n_channels[files].max()) > channels:
+            raise ValueError("%s: a stereo file in a one-channel call (channels=1): ask for 2 channels or a mix" % what)
+        dev = torch.device("cuda", self._handle.cfg.device_id)
+        shape = (n, channels, edges.size - 1, n_frames)
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=dev)
+        elif not isinstance(out, torch.Tensor) or out.dtype != dtype or tuple(out.shape) != shape or out.device != dev \
+                or not out.is_contiguous():
+            raise ValueError("%s: out must be a contiguous %s tensor of shape %s on %s" % (what, dtype, shape, dev))
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        self._handle._check(lib.mrc_pac_store_band_energy_window(
+            self._s, _lib.MRC_MIX_EACH if mix is None else mix, n, files.ctypes.data, starts.ctypes.data, n_frames, hop,
+            edges.size - 1, edges.ctypes.data, channels, _formats()[dtype], out.data_ptr() if out.numel() else None, stream or None))
+        return out
+
     def block_energy(self, rate_divisor=1, mix=None, files=None):
         """mrc_pac_store_block_energy -> (entry_offset [n + 1], blocks [entries][3] (block_start, a, b), energy [entries]):
         one entry per block and channel of every selected file (files: indices into the store; None: every file in order), or
@@ -238,7 +345,8 @@ class PacStore:
         """of the last decode_window: chunks_parsed, decode_launches, slabs, plan_bytes_uploaded, and ms: the device time of
         the plan upload, the unpack kernel, the synthesis and window_out_kernel, summed over the slabs.  After levels() or
         block_energy(): decode_launches counts block_energy_kernel launches, ms["synthesis"] is that kernel's time and
-        ms["window_out"] is 0."""
+        ms["window_out"] is 0.  After band_energy_window(): decode_launches counts band_energy_kernel launches,
+        ms["synthesis"] is the band sums' time (that kernel) and ms["window_out"] the frame assembly's (band_frames_kernel)."""
         st, ms = np.zeros(4, np.int64), np.zeros(4, np.float64)
         self._handle._check(lib.mrc_pac_store_stats(self._s, st.ctypes.data, ms.ctypes.data))
         r = {k: int(v) for k, v in zip(STAT_NAMES, st)}
