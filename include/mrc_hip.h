@@ -950,6 +950,48 @@ int mrc_pac_store_band_energy_window(mrc_pac_store* s, int mix, int64_t n_items,
                                      const int64_t* start /*[n_items]*/, int64_t n_frames, int64_t hop, int n_bands,
                                      const double* edge_hz /*[n_bands+1]*/, int n_channels_out, int format,
                                      void* out /* DEVICE [n_items][n_channels_out][n_bands][n_frames] */, void* stream);
+/* mrc_resample_taps: the filter of mrc_pac_store_decode_window_resampled, on the host alone (no handle, no device).
+ * up / down is the output rate over the input rate; the library reduces it by the gcd.  After reduction 1 <= up, down <= 1024,
+ * up != down, down <= 8 up and up <= 8 down; zeros in [1, 64]; rolloff in [0.5, 1]; anything else is MRC_ERR_INVALID naming
+ * the argument (mrc_last_error(NULL)).
+ *   base = min(1, up / down) * rolloff        the cut-off as a fraction of the input's Nyquist frequency
+ *   W    = ceil(zeros / base)                 (both in double) written to *half_width (NULL: not wanted)
+ *   taps [up][2 W] (NULL: W alone is wanted): for phase p and tap j, with d = (j - W + 1) - p / up and t = base * d,
+ *     taps[p][j] = base * sinc(t) * cos^2(pi t / (2 zeros))  for |t| < zeros, else 0;  sinc(t) = sin(pi t) / (pi t), 1 at t = 0
+ * -- a Hann-windowed sinc with `zeros` zero crossings a side, the shape torchaudio.functional.resample uses -- evaluated in
+ * long double and rounded to double once.  d is where input sample j of the row lies relative to the output sample, so
+ * taps[p][j] = taps[up - p][2 W - 1 - j] for 0 < p < up and row 0 is symmetric about j = W - 1.  The limits keep a row at or
+ * below 2048 taps and a table at or below 16 MiB. */
+int mrc_resample_taps(int up, int down, int zeros, double rolloff, int32_t* half_width, double* taps /* NULL or [up][2 W] */);
+/* mrc_pac_store_decode_window_resampled: the windows of mrc_pac_store_decode_window_reduced / _mix at up / down of THAT
+ * call's rate -- 48 kHz files at 16 kHz: rate_divisor 2, up / down = 2 / 3 -- through a polyphase filter that reads the
+ * float64 overlap-added planes and writes the caller's tensor; no window at the intermediate rate is written or read back.
+ * mix: MRC_MIX_EACH (every channel, as mrc_pac_store_decode_window_reduced gives them, n_channels_out 1 or 2) or
+ * MRC_MIX_MID / _LEFT / _RIGHT (mrc_pac_store_decode_window_mix's one channel; n_channels_out must be 1).  rate_divisor as in
+ * those calls.  up, down, zeros, rolloff: mrc_resample_taps' arguments and refusals.  start and window count OUTPUT samples.
+ * The intermediate signal y[m], m any integer, is the float64 signal of the existing call at that rate_divisor and mix: the
+ * plane's value for 0 <= m < n_samples / rate_divisor, +0.0 everywhere else -- what MRC_WINDOW_F64 of that call gives.
+ * Output sample n sits at intermediate time n down / up (full-rate time D n down / up + (D - 1) / 2).  With
+ * q = floor(n down / up) and p = n down mod up (floored: n may be negative), W and taps those of mrc_resample_taps,
+ *   v[n] = the left fold from +0.0 over j = 0 .. 2 W - 1 ascending of taps[p][j] * y[q - W + 1 + j],
+ * every product rounded once, then added -- no fused multiply-add.  MRC_WINDOW_F64 is v, MRC_WINDOW_F32 (float) v,
+ * MRC_WINDOW_PCM16 the 16-bit code of v (pcmfile.py:163-172).  Every bit is defined: nothing depends on the launch grid, on
+ * the order of the items, on which items share the call or on the slab size.  A file has ceil(n_samples / D * up / down)
+ * output samples that lie inside it; the filter's tails reach W up / down samples beyond either end, then all is +0.0.
+ * Work follows the windows: an item needs intermediate samples floor(start down / up) - W + 1 up to and including
+ * floor((start + window - 1) down / up) + W, and the blocks parsed and synthesised are those the existing call parses for
+ * a window over exactly that span; an item whose span meets no block is zeros.  Slabs are whole items whose spans, each
+ * counted as ceil((window - 1) down / up) + 2 W plane samples, sum to at most MRC_OPT_STORE_SLAB_SAMPLES (one item at least).
+ * All arithmetic on n down is 64-bit; window <= 2^40; a start beyond +-2^52 lies beyond every file and gives zeros.
+ * MRC_ERR_INVALID naming the argument, before any device work: a mix outside the four, n_channels_out other than 1 under a
+ * one-channel mix, the refusals of mrc_resample_taps, and every refusal of the existing calls (rate_divisor, file indices,
+ * window, format, out, a stereo file in a one-channel MRC_MIX_EACH call).  The stream, damage inside and outside a span and
+ * mrc_pac_store_stats are the existing calls'; ms[3] is resample_out_kernel's time.  The filter is computed and uploaded once
+ * per handle and (up, down, zeros, rolloff). */
+int mrc_pac_store_decode_window_resampled(mrc_pac_store* s, int rate_divisor, int mix, int up, int down, int zeros, double rolloff,
+                                          int64_t n_items, const int64_t* file /*[n_items]*/, const int64_t* start /*[n_items]*/,
+                                          int64_t window, int n_channels_out, int format,
+                                          void* out /* DEVICE [n_items][n_channels_out][window] */, void* stream);
 
 /* Per-stage device time of the most recent timed call when timing is enabled (hipEvents on the launch stream; the call
  * then synchronises).  Timed: mrc_dev_encode / mrc_dev_encode_ex and mrc_encode_mono / mrc_encode_joint (the _blocks

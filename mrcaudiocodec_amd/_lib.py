@@ -212,6 +212,10 @@ def _load():
         "mrc_band_line_ranges": (C.c_int, [C.c_double, C.c_int, C.c_int, C.c_int, _f64p, _i32p]),
         "mrc_pac_store_band_energy_window": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, _i64p, _i64p, C.c_int64, C.c_int64, C.c_int,
                                                        _f64p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+        "mrc_resample_taps": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, _i32p, _f64p]),
+        "mrc_pac_store_decode_window_resampled": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                                            C.c_int64, _i64p, _i64p, C.c_int64, C.c_int, C.c_int, C.c_void_p,
+                                                            C.c_void_p]),
         "mrc_pac_store_stats": (C.c_int, [C.c_void_p, _i64p, _f64p]),
     }
     for name, (res, args) in sig.items():

@@ -29,6 +29,11 @@ One channel:  python -m mrcaudiocodec_amd.cli -d in.pac out.wav --mix mid  (or l
 the same store (mrc_pac_store_decode_window_mix): the mid (L + R) / 2 of a stereo file, formed on the MDCT lines before the
 one inverse transform, or its left or right channel; a mono file gives its channel.  Composes with --rate-divisor, --start
 and --samples.
+At any rate:  python -m mrcaudiocodec_amd.cli -d in.pac out.wav --sample-rate 16000  decodes through the same store at the
+largest rate divisor that still holds the band and a polyphase resampler on the device for the rest
+(mrc_pac_store_decode_window_resampled, store.resample_plan: 48 kHz -> 16 kHz is half-rate synthesis, then 2 / 3): the WAV's
+header carries HZ, and --start / --samples count samples at HZ.  Composes with --mix, --start and --samples; refused together
+with --rate-divisor.
 Levels:  python -m mrcaudiocodec_amd.cli --levels a.pac [b.pac ...] [--levels-window N]  decodes nothing and writes nothing: per
 file one JSON line with its channels, samples, RMS level per channel (dB re full scale) and its loudest and quietest window of
 N samples (default one second) on the short-block grid with their starts, from the energies of the blocks' MDCT lines
@@ -415,6 +420,20 @@ def check_rate_divisor_args(rate_divisor, decode):
     return int(rate_divisor)
 
 
+def check_sample_rate_args(sample_rate, decode, rate_divisor_given=False):
+    """--sample-rate as given (None: not given) -> the rate in Hz or None.  It decodes at that rate: refused without -d,
+    together with --rate-divisor (it picks the divisor itself), and when it is not a positive whole number."""
+    if sample_rate is None:
+        return None
+    if not decode:
+        raise ValueError("--sample-rate decodes at another sample rate: it needs -d")
+    if rate_divisor_given:
+        raise ValueError("--sample-rate picks the rate divisor itself: it does not go with --rate-divisor")
+    if isinstance(sample_rate, bool) or not isinstance(sample_rate, (int, np.integer)) or int(sample_rate) < 1:
+        raise ValueError("--sample-rate: %r is not a positive number of Hz" % (sample_rate,))
+    return int(sample_rate)
+
+
 def check_mix_args(mix, decode):
     """--mix as given (None: not given) -> "mid", "left", "right" or None.  It picks one channel of a decode: refused
     without -d, and any other word is refused."""
@@ -428,7 +447,8 @@ def check_mix_args(mix, decode):
 
 
 LEVELS_REFUSES = ("src", "dst", "-d", "--no-huffman", "--exact-spread", "--certify", "--bits-per-sample", "--nmr", "--measure",
-                  "--target-nmr", "--vbr-nmr", "--vbr-bytes", "--vbr-bits-per-sample", "--vbr-grid", "--start", "--samples")
+                  "--target-nmr", "--vbr-nmr", "--vbr-bytes", "--vbr-bits-per-sample", "--vbr-grid", "--start", "--samples",
+                  "--sample-rate")
 
 
 def check_levels_args(levels, levels_window, given):
@@ -549,13 +569,15 @@ def band_energies_of_file(pac_path, npy_path, hop, band_edges_hz=None, device_id
     return e
 
 
-def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=1, mix=None):
+def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=1, mix=None, sample_rate=None):
     """excerpt: None (the whole file, mrc_decode_pac_pcm16) or (start, samples): that many samples from sample `start` on
     (samples None: to the end of the file), decoded through a one-file PacStore -- only the blocks the excerpt overlaps are
     parsed and synthesised; what lies outside the file is silence.  rate_divisor 2 or 4: at that fraction of the sample rate,
     through the store as well (excerpt None: the whole file); start and samples count samples at the reduced rate, which the
     WAV's header carries.  mix "mid", "left" or "right": a one-channel WAV of that channel (mid: (L + R) / 2, formed on the
-    MDCT lines), through the store as well.  -> int16 [nCh][samples] as written."""
+    MDCT lines), through the store as well.  sample_rate: None or the rate in Hz to decode at, through the store as well
+    (store.resample_plan picks the divisor and the fraction; rate_divisor must be 1): start and samples count samples at
+    that rate, which the WAV's header carries.  -> int16 [nCh][samples] as written."""
     with open(pac_path, "rb") as fp:
         buf = fp.read()
     cfg, _, _, _ = pacfile.read_header(buf)
@@ -563,7 +585,12 @@ def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=
     if cfg.sample_rate % rate_divisor:
         raise ValueError("--rate-divisor %d does not divide the file's sample rate, %d Hz" % (rate_divisor, cfg.sample_rate))
     mix = check_mix_args(mix, True)
-    if (rate_divisor != 1 or mix is not None) and excerpt is None:
+    resample = None
+    if check_sample_rate_args(sample_rate, True, rate_divisor != 1) is not None:
+        from .store import resample_plan
+        rate_divisor, up, down = resample_plan(cfg.sample_rate, int(sample_rate))
+        resample = None if up == down else (up, down)
+    if (rate_divisor != 1 or mix is not None or resample is not None) and excerpt is None:
         excerpt = (0, None)
     h = Handle(sample_rate=cfg.sample_rate, n_mdct_lines=cfg.n_mdct_lines, n_scale_bits=cfg.n_scale_bits,
                n_mant_size_bits=cfg.n_mant_size_bits, device_id=device_id)
@@ -575,13 +602,15 @@ def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=
             with PacStore(h, [buf]) as store:
                 start, samples = excerpt
                 if samples is None:
-                    samples = max(0, int(store.n_samples_at(rate_divisor)[0]) - start)
-                inter = np.ascontiguousarray(store.decode_window([0], [start], samples, rate_divisor=rate_divisor, mix=mix)[0].cpu().numpy().T)
+                    n = store.n_samples_at(rate_divisor) if resample is None else store.n_samples_resampled(*resample, rate_divisor)
+                    samples = max(0, int(n[0]) - start)
+                inter = np.ascontiguousarray(store.decode_window([0], [start], samples, rate_divisor=rate_divisor, mix=mix,
+                                                                 resample=resample)[0].cpu().numpy().T)
     finally:
         h.close()
     data = inter.astype("<i2", copy=False)
     with open(wav_path, "wb") as fp:
-        fp.write(wav_header(inter.shape[1], data.nbytes, cfg.sample_rate // rate_divisor))
+        fp.write(wav_header(inter.shape[1], data.nbytes, cfg.sample_rate // rate_divisor if sample_rate is None else int(sample_rate)))
         fp.write(data.tobytes())
     return inter.T
 
@@ -698,6 +727,10 @@ def main(argv=None):
     ap.add_argument("--rate-divisor", type=int, default=None, metavar="D",
                     help="with -d: decode at 1/D of the sample rate (D = 2 or 4) straight from the MDCT lines; the WAV says "
                          "sample_rate // D, and --start / --samples count samples at that rate")
+    ap.add_argument("--sample-rate", type=int, default=None, metavar="HZ",
+                    help="with -d: decode at HZ samples per second (16000 from a 48 kHz file: half-rate synthesis, then a 2 / 3 "
+                         "polyphase resampler on the device); the WAV says HZ, and --start / --samples count samples at HZ; "
+                         "does not go with --rate-divisor")
     ap.add_argument("--mix", default=None, metavar="CH",
                     help="with -d: write a one-channel WAV, CH = mid ((L + R) / 2 of a stereo file, formed on the MDCT lines), "
                          "left or right; composes with --rate-divisor, --start and --samples")
@@ -723,7 +756,8 @@ def main(argv=None):
             "--exact-spread": a.exact_spread, "--certify": a.certify, "--bits-per-sample": a.bits_per_sample is not None,
             "--nmr": a.nmr, "--measure": a.measure, "--target-nmr": a.target_nmr is not None, "--vbr-nmr": a.vbr_nmr is not None,
             "--vbr-bytes": a.vbr_bytes is not None, "--vbr-bits-per-sample": a.vbr_bits_per_sample is not None,
-            "--vbr-grid": a.vbr_grid is not None, "--start": a.start is not None, "--samples": a.samples is not None}
+            "--vbr-grid": a.vbr_grid is not None, "--start": a.start is not None, "--samples": a.samples is not None,
+            "--sample-rate": a.sample_rate is not None}
         bands = check_band_energies_args(a.band_energies, a.hop, a.band_edges, dict(
             given, **{"--levels": a.levels is not None, "--levels-window": a.levels_window is not None,
                       "--rate-divisor": a.rate_divisor is not None}))
@@ -733,6 +767,7 @@ def main(argv=None):
         excerpt = check_excerpt_args(a.start, a.samples, a.decode)
         rate_divisor = check_rate_divisor_args(a.rate_divisor, a.decode or levels is not None)
         mix = check_mix_args(a.mix, a.decode or levels is not None or bands is not None)
+        sample_rate = check_sample_rate_args(a.sample_rate, a.decode, a.rate_divisor is not None)
         if levels is not None:
             from .store import check_levels_mix
             check_levels_mix(mix, "--mix")
@@ -795,7 +830,7 @@ def main(argv=None):
         return
     if a.decode:
         try:
-            pcm = decode_pac_file(a.src, a.dst, a.device, excerpt, rate_divisor, mix)
+            pcm = decode_pac_file(a.src, a.dst, a.device, excerpt, rate_divisor, mix, sample_rate)
         except ValueError as e:
             ap.error(str(e))
         print("%s: %d channels x %d samples" % (a.dst, pcm.shape[0], pcm.shape[1]))

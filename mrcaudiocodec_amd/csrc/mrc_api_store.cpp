@@ -37,6 +37,12 @@
 // of the non-joint group, which laid side by side are one slot of two streams, the group's pairs in front of its single
 // slots so that a workgroup finds its slot from its index alone.  pac_plan_layout sees slot counts as ever.
 //
+// decode_window_resampled, the windows at up / down of the rate 1 / D: decode_windows with two coordinate systems.  start and
+// window count output samples; what is planned, staged, parsed and synthesised is each item's span of INTERMEDIATE samples
+// (everything the filter reads for the item's outputs), and resample_out_kernel folds the planes into the caller's tensor
+// where window_out_kernel copies them.  The filter (mrc_resample_taps.hpp: host only) goes up once per handle and
+// (up, down, zeros, rolloff).
+//
 // block_energy, ((a + b) / D) * the sum of squares of a block's first 1 / D decoded lines, per channel or for the mid, for
 // every block of the selected files: the same slab plan (stage_slab, parse_slab) over runs of whole blocks instead of the
 // blocks of windows, then block_energy_kernel per group (mrc_kernels_store.hip) in place of planes, synthesis and output.
@@ -48,6 +54,7 @@
 // band_frames_kernel over the slab's output; per item one descriptor and its run of edges go up with the plan, per shape
 // the band's line ranges (mrc_band_line_ranges, no handle and no device).
 #include "mrc_handle.hpp"
+#include "mrc_resample_taps.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -61,6 +68,7 @@ namespace {
 const char* const kWin = "mrc_pac_store_decode_window";
 const char* const kWinReduced = "mrc_pac_store_decode_window_reduced";
 const char* const kWinMix = "mrc_pac_store_decode_window_mix";
+const char* const kWinResampled = "mrc_pac_store_decode_window_resampled";
 constexpr int kNoMix = -1;                           // decode_windows: every channel of a file into a plane of its own
 
 int store_alive(mrc_pac_store* s, const char* fn) {
@@ -249,10 +257,45 @@ int mrc_pac_store_info(mrc_pac_store* s, int64_t* n_files, int32_t* n_channels, 
 
 namespace {
 
+int64_t floor_div(int64_t a, int64_t b) {             // b > 0
+    const int64_t q = a / b;
+    return (a % b != 0 && a < 0) ? q - 1 : q;
+}
+
+// the device table of a filter, computed and uploaded on its first use on this handle
+int get_resample_table(mrc_handle* h, const ResampleSpec& r, const ResampleTable** out) {
+    auto& tables = h->store.resample;
+    const auto key = std::make_tuple(r.up, r.down, r.zeros, r.rolloff);
+    auto it = tables.find(key);
+    if (it == tables.end()) {
+        if (tables.size() >= 16) tables.clear();             // (a sweep over ratios: no call is in flight between calls)
+        const size_t nTaps = 2 * (size_t)r.W, n = nTaps * (size_t)r.up;
+        std::vector<double> byPhase(n), byTap(n);
+        resample_taps(r, byPhase.data());
+        for (size_t p = 0; p < (size_t)r.up; ++p)
+            for (size_t j = 0; j < nTaps; ++j) byTap[j * (size_t)r.up + p] = byPhase[p * nTaps + j];
+        ResampleTable t;
+        t.W = r.W;
+        int g = 1;
+        resample_lds_layout(r.up, r.down, &g, &t.skew);
+        t.evenOdd = g == 2;
+        MRC_HIP(h, t.taps.reserve(sizeof(double) * n));
+        MRC_HIP(h, hipMemcpy(t.taps.p, byTap.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+        it = tables.emplace(key, std::move(t)).first;
+    }
+    *out = &it->second;
+    return MRC_OK;
+}
+
 // all decode_window calls: fn the entry point's name, D the rate divisor (1: full rate, decode_kernel), mixArg null or the
-// caller's MRC_MIX_* (one plane per item, decode_mix_kernel; n_channels_out is then 1)
+// caller's MRC_MIX_* (one plane per item, decode_mix_kernel; n_channels_out is then 1).
+// rs (mrc_pac_store_decode_window_resampled) null or the filter: start and window then count OUTPUT samples, at up / down of
+// the rate 1 / D.  Item k reads the intermediate samples [lo, hi], lo = floor(start down / up) - W + 1, hi =
+// floor((start + window - 1) down / up) + W: that span is what is planned, staged, parsed and synthesised exactly as a
+// window of the other calls -- into planes of span + 4 L samples, span = ceil((window - 1) down / up) + 2 W the one bound on
+// hi - lo + 1 -- and resample_out_kernel stands where window_out_kernel stands.  A slab counts plane samples (spans).
 int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, int64_t n_items, const int64_t* file, const int64_t* start,
-                   int64_t window, int n_channels_out, int format, void* out, void* stream) {
+                   int64_t window, int n_channels_out, int format, void* out, void* stream, const ResampleSpec* rs = nullptr) {
     MRC_TRY(store_alive(s, fn));
     mrc_handle* h = s->h;
     const mrc_config& cfg = h->cfg;
@@ -286,7 +329,12 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
     hipStream_t st = pick_stream(h, stream);
     DrainGuard drain{{st, nullptr, nullptr}};
     const size_t elem = format == MRC_WINDOW_PCM16 ? 2 : format == MRC_WINDOW_F32 ? 4 : 8;
-    const int64_t planeLen = window + 4 * L, tiles = (window + 255) / 256;
+    const ResampleTable* table = nullptr;
+    if (rs) MRC_TRY(get_resample_table(h, *rs, &table));
+    const int64_t up = rs ? rs->up : 1, down = rs ? rs->down : 1, W = rs ? rs->W : 0;
+    const int64_t span = rs ? ((window - 1) * down + up - 1) / up + 2 * W : window;     // plane samples an item takes at most
+    const int64_t far = (int64_t)1 << 52;                    // an output start beyond it is beyond every file: (start + window) * down fits
+    const int64_t planeLen = span + 4 * L, tiles = (window + 255) / 256;
     const int64_t slab = h->storeSlabSamples, itemCap = std::max<int64_t>(1, 0x7fffffffLL / (tiles * n_channels_out));
 
     std::vector<Need> needs;
@@ -294,7 +342,7 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
     PacPlan pl;                                              // (its group fields: the slab's slots)
     for (int64_t first = 0, last; first < n_items; first = last) {
         last = first + 1;
-        while (last < n_items && last - first < itemCap && (slab == 0 || (last - first + 1) * window <= slab)) ++last;
+        while (last < n_items && last - first < itemCap && (slab == 0 || (last - first + 1) * span <= slab)) ++last;
         const int64_t nSlab = last - first;
         unsigned char* outSlab = (unsigned char*)out + (size_t)first * n_channels_out * window * elem;
         s->stats[2] += 1;
@@ -306,11 +354,17 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
         for (int64_t k = 0; k < nSlab; ++k) {
             const int64_t f = file[first + k];
             const size_t before = needs.size();
-            needed_blocks(*s, cfg, D, k, f, start[first + k], window, &needs);
+            int64_t at = start[first + k], len = window;     // the samples the planes must hold: [at, at + len)
+            if (rs) {
+                if (at > far || at < -far) continue;
+                at = floor_div(at * down, up) - W + 1;
+                len = floor_div((start[first + k] + window - 1) * down, up) + W - at + 1;
+            }
+            needed_blocks(*s, cfg, D, k, f, at, len, &needs);
             if (needs.size() == before) continue;            // all zeros: its plane does not exist
             const PacFilePlan& fi = s->index.files[(size_t)f];
             const int nPlanes = mix == kNoMix ? fi.nch : 1;
-            items[(size_t)k] = WindowItem{planeDoubles, start[first + k], std::max<int64_t>(0, fi.total - cfg.n_mdct_lines) / D, nPlanes, 0};
+            items[(size_t)k] = WindowItem{planeDoubles, at, std::max<int64_t>(0, fi.total - cfg.n_mdct_lines) / D, nPlanes, 0};
             planeDoubles += nPlanes * planeLen;
         }
         if (needs.empty()) {                                 // nothing to decode: zeros, no launch
@@ -319,13 +373,14 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
         }
         // ---- staging (one H2D copy): plan | groups | block offsets | items; a slot's offset is its block's place in the item's
         // plane: the block's position in the file's padded plane, the window's start at 2 L
-        size_t oOffs = 0, oItems = 0;
+        size_t oOffs = 0, oItems = 0, oOutStart = 0;
         SlabStage S;
         MRC_TRY(stage_slab(
             s, fn, mix, needs, &pl, &S,
             [&](StageLayout* lay) {
                 oOffs = lay->add<long long>(pl.totalSlots);
                 oItems = lay->add<WindowItem>(nSlab);
+                if (rs) oOutStart = lay->add<long long>(nSlab);
             },
             [&](const Need& n, int g, int slot, int ch, bool pair) {
                 const WindowItem& it = items[(size_t)n.item];
@@ -339,6 +394,7 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
         const int64_t* nPairs = S.nPairs;
         const UnpackGroupDev* gd = S.gd;
         std::memcpy(S.pin + oItems, items.data(), sizeof(WindowItem) * nSlab);
+        if (rs) std::memcpy(S.pin + oOutStart, start + first, sizeof(long long) * nSlab);
         const HostShape* reduced[4] = {};
         for (int sh = 0; D > 1 && sh < 4; ++sh)
             if (pl.hs[sh]) MRC_TRY(get_synth_shape(h, pl.hs[sh]->dev.a, pl.hs[sh]->dev.b, D, &reduced[sh]));
@@ -365,8 +421,13 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
             }));
         s->stats[1] += pl.groupsUsed();
         MRC_HIP(h, hipEventRecord(b.ev[4], st));
-        MRC_HIP(h, launch_window_out(nSlab, (const WindowItem*)(din + oItems), window, n_channels_out, format, (int)L, x,
-                                     outSlab, st));
+        if (rs)
+            MRC_HIP(h, launch_resample_out(nSlab, (const WindowItem*)(din + oItems), (const long long*)(din + oOutStart), window,
+                                           n_channels_out, format, (int)L, planeLen, rs->up, rs->down, rs->W, table->evenOdd,
+                                           table->skew, (const double*)table->taps.p, x, outSlab, st));
+        else
+            MRC_HIP(h, launch_window_out(nSlab, (const WindowItem*)(din + oItems), window, n_channels_out, format, (int)L, x,
+                                         outSlab, st));
         MRC_HIP(h, hipEventRecord(b.ev[5], st));
         MRC_HIP(h, hipStreamSynchronize(st));                // (the staging is written again by the next slab)
         const int span[4][2] = {{0, 1}, {1, 2}, {3, 4}, {4, 5}};
@@ -729,6 +790,33 @@ int mrc_pac_store_decode_window_reduced(mrc_pac_store* s, int rate_divisor, int6
 int mrc_pac_store_decode_window_mix(mrc_pac_store* s, int rate_divisor, int mix, int64_t n_items, const int64_t* file,
                                     const int64_t* start, int64_t window, int format, void* out, void* stream) {
     return decode_windows(s, kWinMix, rate_divisor, &mix, n_items, file, start, window, 1, format, out, stream);
+}
+
+int mrc_resample_taps(int up, int down, int zeros, double rolloff, int32_t* half_width, double* taps) {
+    ResampleSpec r;
+    const std::string refusal = resample_spec(up, down, zeros, rolloff, &r);
+    if (!refusal.empty()) return fail(nullptr, MRC_ERR_INVALID, "mrc_resample_taps: " + refusal);
+    if (half_width) *half_width = r.W;
+    if (taps) resample_taps(r, taps);
+    return MRC_OK;
+}
+
+int mrc_pac_store_decode_window_resampled(mrc_pac_store* s, int rate_divisor, int mix, int up, int down, int zeros, double rolloff,
+                                          int64_t n_items, const int64_t* file, const int64_t* start, int64_t window,
+                                          int n_channels_out, int format, void* out, void* stream) {
+    MRC_TRY(store_alive(s, kWinResampled));
+    mrc_handle* h = s->h;
+    const std::string w = kWinResampled;
+    if (mix != MRC_MIX_EACH && mix != MRC_MIX_MID && mix != MRC_MIX_LEFT && mix != MRC_MIX_RIGHT)
+        return fail(h, MRC_ERR_INVALID, w + ": mix " + std::to_string(mix) +
+                                            " is not MRC_MIX_EACH (3), MRC_MIX_MID (0), MRC_MIX_LEFT (1) or MRC_MIX_RIGHT (2)");
+    if (mix != MRC_MIX_EACH && n_channels_out != 1)
+        return fail(h, MRC_ERR_INVALID, w + ": n_channels_out must be 1 under a mix of one channel");
+    ResampleSpec r;
+    const std::string refusal = resample_spec(up, down, zeros, rolloff, &r);
+    if (!refusal.empty()) return fail(h, MRC_ERR_INVALID, w + ": " + refusal);
+    return decode_windows(s, kWinResampled, rate_divisor, mix == MRC_MIX_EACH ? nullptr : &mix, n_items, file, start, window,
+                          n_channels_out, format, out, stream, &r);
 }
 
 int mrc_pac_store_block_energy(mrc_pac_store* s, int rate_divisor, int mix, int64_t n_sel, const int64_t* file,

@@ -221,8 +221,14 @@ struct NmrBufs {
 
 // Windows of resident `.pac` files (mrc_pac_store_decode_window, mrc_api_store.cpp): the workspace of one slab, reused from
 // slab to slab and from call to call.  The parsing tables, the error word and its page-locked copy are DecodeBufs' (pac_parse).
+struct ResampleTable {               // the filter of one (up, down, zeros, rolloff), uploaded once (mrc_resample_taps.hpp)
+    DevBuf taps;                     // [2 W][up]
+    int W = 0, evenOdd = 0, skew = 0;   // half width; resample_out_kernel's LDS layout (resample_lds_layout)
+};
 struct StoreBufs {
+    std::map<std::tuple<int, int, int, double>, ResampleTable> resample;   // mrc_pac_store_decode_window_resampled's filters
     DevBuf in;                       // one H2D copy per slab (a StageLayout): plan | group descriptors | block offsets | items
+                                     // (| the items' output starts: decode_window_resampled)
     DevBuf groups;                   // dense per-(shape, kind) arrays of the parsed chunks
     DevBuf planes;                   // float64, window + 4 n_mdct_lines samples per item and decoded channel
     PinnedBuf pinIn;                 // written again only after the slab that read it has been synchronised
@@ -361,7 +367,7 @@ struct mrc_pac_store {
     std::vector<int64_t> tileEdge;   // file f with blocks: nBlocks(f) + 1 edges from firstBlock[f] + f on, in DOUBLED output samples:
                                      // block i's tile is [2 p_i + a_i - 2 L, 2 p_i + 2 a_i + b_i - 2 L), and tiles abut
     int64_t stats[4] = {0, 0, 0, 0}; // last decode_window: chunks parsed, decode_kernel launches, slabs, plan bytes uploaded
-    double ms[4] = {0, 0, 0, 0};     // ... plan upload | unpack | synthesis | window_out_kernel
+    double ms[4] = {0, 0, 0, 0};     // ... plan upload | unpack | synthesis | window_out_kernel (resampled: resample_out_kernel)
                                      // (after block_energy: block_energy_kernel launches in [1]; ms: upload | unpack | that kernel | 0;
                                      // after band_energy_window: band_energy_kernel launches; upload | unpack | band sums | frames)
 };

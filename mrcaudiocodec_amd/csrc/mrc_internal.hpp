@@ -254,6 +254,13 @@ struct WindowItem {                  // one item of a slab
 // n_mdct_lines, divided by the rate divisor where there is one.)
 hipError_t launch_window_out(int64_t nItems, const WindowItem* items /* device */, int64_t window, int nchOut, int format,
                              int L, const double* planes, void* out, hipStream_t st);
+// mrc_pac_store_decode_window_resampled: out [nItems][nchOut][window] <- the polyphase fold of the items' planes, which hold
+// INTERMEDIATE samples (item.start, item.nSamples in those; planes of planeLen doubles, sample m at 2 L + m - item.start).
+// Output t of item k is output sample n = outStart[k] + t; taps (device) [2 W][up]; evenOdd, skew: the LDS layout
+// (resample_lds_layout).  Refuses a run of more than 4089 intermediate samples per 256 outputs.
+hipError_t launch_resample_out(int64_t nItems, const WindowItem* items /* device */, const long long* outStart /* device */,
+                               int64_t window, int nchOut, int format, int L, int64_t planeLen, int up, int down, int W,
+                               int evenOdd, int skew, const double* taps, const double* planes, void* out, hipStream_t st);
 // One entry of mrc_pac_store_block_energy: a channel of a block, or its mid.  sel 0 / 1: output channel L / R of a joint
 // slot (a non-joint slot has one channel, itself: 0); kEnergyMid: the mid (L + R) / 2 on the lines -- of a joint slot, or of
 // the PAIR of non-joint slots slot, slot + 1 (a stereo file's last block).

@@ -11,6 +11,27 @@
 //       MRC_WINDOW_F32    (float) of it, one conversion, round to nearest even;
 //       MRC_WINDOW_PCM16  pcmfile.py:163-172 exactly as pcm16_kernel (mrc_kernels_decode.hip) has it.
 //
+//   resample_out_kernel   window_out_kernel's place in mrc_pac_store_decode_window_resampled: the planes hold the items'
+//     INTERMEDIATE samples y (the signal at 1 / D of the file's rate), out the signal at up / down of that rate.  Output n of a
+//     row sits at intermediate time n down / up; with q = floor(n down / up), p = n down mod up
+//       v[n] = the left fold from +0.0 over j = 0 .. 2 W - 1 ascending of taps[p][j] * y[q - W + 1 + j],
+//     every product rounded once, then added (__dmul_rn, __dadd_rn: no fused multiply-add), y +0.0 outside [0, nSamples).
+//     A row is one (item, output channel); a workgroup of 256 threads takes 256 consecutive n of it.  What they read is one
+//     run of at most 255 down / up + 2 W + 1 <= 4089 intermediate samples: all threads stage it into LDS with consecutive
+//     loads of the plane (the file mask applied there, so the plane is not read outside the file), then each thread folds
+//     from LDS, eight taps and samples read ahead of their additions.  The taps lie [tap][phase] in device memory, so that at
+//     tap j a wave's 64 reads fall into one row of `up` doubles; for up == 1 and up == 2 the row is read at addresses the
+//     whole wave shares (scalar loads) and each lane picks its phase's tap, in instantiations of their own.
+//     LDS layout: at tap j lane k of a half wave reads run[o + floor((p0 + k down) / up)] with a 64-bit read, 32 lanes over
+//     32 banks of a double.  down <= up, or down / up an odd whole number: 32 different banks, nothing to do.  Otherwise two
+//     remedies, chosen per ratio on the host by counting (resample_lds_layout, mrc_resample_taps.hpp): skew -- double i
+//     kept at i + (i >> 5), one double of padding per bank row, which takes the 2-, 4- and 8-way conflicts of the strides 2,
+//     4 and 8 to under two cycles a read -- and evenOdd -- a wave's first half takes the even, its second half the odd of
+//     its 64 outputs, so that a half's stride is 2 down / up: 3 / 2 becomes the odd stride 3, conflict-free.  Ratios like
+//     441 / 160 keep their two cycles a read under all four layouts (DESIGN.md has the table).  A wave's stores are the
+//     same 64 consecutive values either way.
+//     Nothing depends on the grid, on the order of the items, on which items share the launch or on the slab.
+//
 //   block_energy_kernel   the energy a block adds to the decoded signal, from its MDCT lines alone
 //     (mrc_pac_store_block_energy).  The windowed MDCT with the codec's transition windows is an orthogonal lapped
 //     transform; with the reference's scaling (mdct.py: forward 2 / N, inverse 2) a block of shape (a, b) holds
@@ -59,6 +80,19 @@ namespace {
 
 constexpr int kWindowThreads = 256;
 
+// out[o] = v in the caller's format (MRC_WINDOW_*)
+__device__ inline void store_window_value(void* __restrict__ out, int64_t o, int format, double v) {
+    if (format == MRC_WINDOW_F64) {
+        ((double*)out)[o] = v;
+    } else if (format == MRC_WINDOW_F32) {
+        ((float*)out)[o] = (float)v;
+    } else {
+        const double mag = fabs(v);
+        const int code = mag == 0.0 ? 0 : (int)mag_code(mag, 16);
+        ((short*)out)[o] = (short)(signbit(v) ? -code : code);
+    }
+}
+
 __global__ __launch_bounds__(kWindowThreads) void window_out_kernel(const WindowItem* __restrict__ items, int64_t window,
                                                                     int64_t tiles, int nchOut, int format, int L,
                                                                     const double* __restrict__ planes,
@@ -73,16 +107,93 @@ __global__ __launch_bounds__(kWindowThreads) void window_out_kernel(const Window
     double v = 0.0;
     if (pos >= 0 && pos < it.nSamples)
         v = planes[it.plane + (int64_t)(it.nch == 2 ? c : 0) * (window + 4 * (int64_t)L) + 2 * (int64_t)L + t];
-    const int64_t o = row * window + t;
-    if (format == MRC_WINDOW_F64) {
-        ((double*)out)[o] = v;
-    } else if (format == MRC_WINDOW_F32) {
-        ((float*)out)[o] = (float)v;
-    } else {
-        const double mag = fabs(v);
-        const int code = mag == 0.0 ? 0 : (int)mag_code(mag, 16);
-        ((short*)out)[o] = (short)(signbit(v) ? -code : code);
+    store_window_value(out, row * window + t, format, v);
+}
+
+constexpr int kResampleThreads = 256, kResampleWave = 64;
+constexpr int kResampleRun = 4089;                                   // doubles a workgroup stages at most: 255 * 8 + 2 * 1024 + 1
+constexpr int kResampleLds = kResampleRun + kResampleRun / 32 + 1;   // ... with one double of padding per 32 (skew)
+
+__device__ inline int64_t floor_div(int64_t a, int64_t b) {         // b > 0
+    const int64_t q = a / b;
+    return (a % b != 0 && a < 0) ? q - 1 : q;
+}
+
+// v = the left fold from +0.0 over j ascending of taps[j][p] * run[first + j], every product rounded once, then added.
+// kUp: 1 or 2 -- `up` itself: a tap's row is read at addresses the whole wave shares (scalar loads) and the lane picks its
+// phase's -- or 0: any `up`, each lane loads taps[j][p].  kSkew: the run's layout.  Eight taps and samples are read ahead of
+// their eight additions.
+template <int kUp, bool kSkew>
+__device__ inline double resample_fold(const double* __restrict__ taps, int up, int p, const double* run, int first, int nTaps) {
+    const auto tap = [&](int j) {
+        if (kUp == 1) return taps[j];
+        if (kUp == 2) {
+            const double c0 = taps[2 * j], c1 = taps[2 * j + 1];
+            return p ? c1 : c0;
+        }
+        return taps[(int64_t)j * up + p];
+    };
+    const auto at = [](int i) { return kSkew ? i + (i >> 5) : i; };
+    double acc = 0.0;
+    int j = 0;
+    for (; j + 8 <= nTaps; j += 8) {
+        double c[8], y[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            c[u] = tap(j + u);
+            y[u] = run[at(first + j + u)];
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) acc = __dadd_rn(acc, __dmul_rn(c[u], y[u]));
     }
+    for (; j < nTaps; ++j) acc = __dadd_rn(acc, __dmul_rn(tap(j), run[at(first + j)]));
+    return acc;
+}
+template <bool kSkew>
+__device__ inline double resample_fold_up(const double* __restrict__ taps, int up, int p, const double* run, int first, int nTaps) {
+    return up == 1 ? resample_fold<1, kSkew>(taps, up, p, run, first, nTaps)
+         : up == 2 ? resample_fold<2, kSkew>(taps, up, p, run, first, nTaps)
+                   : resample_fold<0, kSkew>(taps, up, p, run, first, nTaps);
+}
+
+__global__ __launch_bounds__(kResampleThreads) void resample_out_kernel(const WindowItem* __restrict__ items,
+                                                                        const long long* __restrict__ outStart, int64_t window,
+                                                                        int64_t tiles, int nchOut, int format, int L,
+                                                                        int64_t planeLen, int up, int down, int W, int evenOdd,
+                                                                        int skew, const double* __restrict__ taps,
+                                                                        const double* __restrict__ planes,
+                                                                        void* __restrict__ out) {
+    __shared__ double run[kResampleLds];
+    const int64_t row = (int64_t)blockIdx.x / tiles;                 // item * nchOut + channel
+    const int64_t t0 = ((int64_t)blockIdx.x - row * tiles) * kResampleThreads;
+    const int64_t k = row / nchOut;
+    const int c = (int)(row - k * nchOut);
+    const WindowItem it = items[k];
+    // the thread's output: lane l of a wave takes output l of the wave's 64, or (evenOdd) its first half the even and its
+    // second half the odd ones -- a wave's stores cover the same 64 consecutive values either way
+    const int lane = threadIdx.x % kResampleWave, wave = threadIdx.x / kResampleWave;
+    const int64_t t = t0 + wave * kResampleWave + (evenOdd ? 2 * (lane & 31) + (lane >> 5) : lane);
+    if (it.nSamples == 0) {                                          // (the whole workgroup) no plane: every y is +0.0
+        if (t < window) store_window_value(out, row * window + t, format, 0.0);
+        return;
+    }
+    // the run of intermediate samples the tile's outputs read: [qFirst, qFirst + len)
+    const int64_t n0 = outStart[k] + t0, nLast = n0 + min((int64_t)kResampleThreads, window - t0) - 1;
+    const int64_t qFirst = floor_div(n0 * down, up) - W + 1;
+    const int len = (int)(floor_div(nLast * down, up) + W - qFirst + 1);       // <= kResampleRun (the launcher's check)
+    const double* plane = planes + it.plane + (int64_t)(it.nch == 2 ? c : 0) * planeLen;
+    for (int i = threadIdx.x; i < len; i += kResampleThreads) {
+        const int64_t m = qFirst + i, at = 2 * (int64_t)L + (m - it.start);   // y[m] is plane[2 L + m - start] inside the file
+        double v = 0.0;
+        if (m >= 0 && m < it.nSamples && at >= 0 && at < planeLen) v = plane[at];
+        run[i + skew * (i >> 5)] = v;
+    }
+    __syncthreads();
+    if (t >= window) return;
+    const int64_t nd = (outStart[k] + t) * down, q = floor_div(nd, up);
+    const int p = (int)(nd - q * up), first = (int)(q - W + 1 - qFirst);
+    const double v = skew ? resample_fold_up<true>(taps, up, p, run, first, 2 * W) : resample_fold_up<false>(taps, up, p, run, first, 2 * W);
+    store_window_value(out, row * window + t, format, v);
 }
 
 constexpr int kEnergyThreads = 256, kEnergyWave = 64;
@@ -228,6 +339,20 @@ hipError_t launch_window_out(int64_t nItems, const WindowItem* items, int64_t wi
     if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;          // (the caller cuts such a call into slabs)
     hipLaunchKernelGGL(window_out_kernel, dim3((unsigned)blocks), dim3(kWindowThreads), 0, st, items, window, tiles, nchOut,
                        format, L, planes, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_resample_out(int64_t nItems, const WindowItem* items, const long long* outStart, int64_t window, int nchOut,
+                               int format, int L, int64_t planeLen, int up, int down, int W, int evenOdd, int skew,
+                               const double* taps, const double* planes, void* out, hipStream_t st) {
+    if (nItems <= 0 || window <= 0) return hipSuccess;
+    const int64_t tiles = (window + kResampleThreads - 1) / kResampleThreads;
+    const int64_t blocks = tiles * nItems * nchOut;
+    if (blocks > 0x7fffffffLL || up < 1 || down < 1 || W < 1 ||
+        ((int64_t)(kResampleThreads - 1) * down + up - 1) / up + 2 * (int64_t)W + 1 > kResampleRun)
+        return hipErrorInvalidValue;                                 // (a run that would not fit the workgroup's LDS)
+    hipLaunchKernelGGL(resample_out_kernel, dim3((unsigned)blocks), dim3(kResampleThreads), 0, st, items, outStart, window, tiles,
+                       nchOut, format, L, planeLen, up, down, W, evenOdd, skew, taps, planes, out);
     return hipGetLastError();
 }
 

@@ -17,6 +17,13 @@ mix = "mid", "left" or "right" (mrc_pac_store_decode_window_mix) gives ONE chann
 right are the bits of that channel of the two-channel call; mid is (L + R) / 2 formed on the MDCT lines, where most bands
 of a stereo file hold it already, so that a stereo block costs one inverse transform, one plane and one output row.
 
+resample = (up, down) (mrc_pac_store_decode_window_resampled) gives the window at up / down of the rate_divisor's rate -- any
+rational rate, 16 kHz from 48 kHz files among them -- through a polyphase Hann-windowed sinc that reads the float64 planes
+on the device; starts and window then count output samples:
+
+        d, up, down = resample_plan(48000, 16000)                              # (2, 2, 3): half-rate synthesis, then 2 / 3
+        z = store.decode_window(files, starts, 16000, dtype=torch.float32, rate_divisor=d, resample=(up, down))
+
 levels (mrc_pac_store_block_energy) answers how loud every stretch of every file is without decoding it: the sum of squares
 of each block's decoded MDCT lines IS the energy the block adds to the signal (Parseval on the orthogonal lapped transform),
 and levels.LevelMap turns those numbers into window levels, admissible crop starts, reproducible draws and gains:
@@ -62,6 +69,78 @@ def check_mix(mix, channels=None, what="decode_window"):
     if channels is not None and (isinstance(channels, bool) or not isinstance(channels, (int, np.integer)) or int(channels) != 1):
         raise ValueError("%s: mix=%r gives one channel, channels must be None or 1, got %r" % (what, mix, channels))
     return MIXES[mix]
+
+
+RESAMPLE_ZEROS, RESAMPLE_ROLLOFF = 16, 0.9475     # the defaults of resample_taps
+RESAMPLE_MAX_TERM, RESAMPLE_MAX_RATIO, RESAMPLE_MAX_ZEROS = 1024, 8, 64
+
+
+def _is_int(v):
+    return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+
+
+def check_resample(resample, what="decode_window"):
+    """resample as (up, down) or (up, down, zeros, rolloff) -> (up, down, zeros, rolloff) with up / down reduced, or None
+    for None and for a ratio of 1; else ValueError: mrc_resample_taps' rule, checked before any library call"""
+    if resample is None:
+        return None
+    if not isinstance(resample, (tuple, list)) or len(resample) not in (2, 4):
+        raise ValueError("%s: resample must be None, (up, down) or (up, down, zeros, rolloff), got %r" % (what, resample))
+    up, down = resample[0], resample[1]
+    zeros, rolloff = (RESAMPLE_ZEROS, RESAMPLE_ROLLOFF) if len(resample) == 2 else resample[2:]
+    for name, v in (("up", up), ("down", down)):
+        if not _is_int(v) or int(v) < 1:
+            raise ValueError("%s: resample: %s must be a positive int, got %r" % (what, name, v))
+    g = int(np.gcd(int(up), int(down)))
+    up, down = int(up) // g, int(down) // g
+    for name, v in (("up", up), ("down", down)):
+        if v > RESAMPLE_MAX_TERM:
+            raise ValueError("%s: resample: %s = %d (of %d / %d, reduced) is above %d" % (what, name, v, up, down, RESAMPLE_MAX_TERM))
+    if down > RESAMPLE_MAX_RATIO * up or up > RESAMPLE_MAX_RATIO * down:
+        raise ValueError("%s: resample: up / down = %d / %d is outside [1 / %d, %d]" % (what, up, down, RESAMPLE_MAX_RATIO, RESAMPLE_MAX_RATIO))
+    if not _is_int(zeros) or not 1 <= int(zeros) <= RESAMPLE_MAX_ZEROS:
+        raise ValueError("%s: resample: zeros must be an int in 1..%d, got %r" % (what, RESAMPLE_MAX_ZEROS, zeros))
+    if isinstance(rolloff, bool) or not isinstance(rolloff, (int, float, np.integer, np.floating)) or not 0.5 <= float(rolloff) <= 1.0:
+        raise ValueError("%s: resample: rolloff must be a number in [0.5, 1], got %r" % (what, rolloff))
+    if up == down:
+        return None
+    return up, down, int(zeros), float(rolloff)
+
+
+def resample_taps(up, down, zeros=RESAMPLE_ZEROS, rolloff=RESAMPLE_ROLLOFF):
+    """mrc_resample_taps -> (W, float64 [up][2 W]) with up / down reduced: the Hann-windowed sinc of
+    PacStore.decode_window(resample=), phase p and tap j at d = (j - W + 1) - p / up input samples from the output sample.
+    No handle, no GPU.  MrcError where the library refuses."""
+    def call(w, taps):
+        rc = lib.mrc_resample_taps(int(up), int(down), int(zeros), float(rolloff), w.ctypes.data, taps)
+        if rc:
+            err = _lib.MrcError("libmrc_hip error %d: %s" % (rc, lib.mrc_last_error(None).decode()))
+            err.code = rc
+            raise err
+    w = np.zeros(1, np.int32)
+    call(w, None)
+    g = int(np.gcd(int(up), int(down)))
+    taps = np.zeros((int(up) // g, 2 * int(w[0])), np.float64)
+    call(w, taps.ctypes.data)
+    return int(w[0]), taps
+
+
+def resample_plan(rate_in, rate_out, divisors=RATE_DIVISORS):
+    """How to read files of rate_in Hz at rate_out Hz -> (rate_divisor, up, down): the largest divisor D of `divisors` that
+    divides rate_in with rate_in / D >= rate_out -- the cheapest synthesis that still holds the band -- and up / down =
+    rate_out / (rate_in / D), reduced (1, 1: that divisor alone gives the rate).  48000 -> 16000: (2, 2, 3); 44100 -> 16000:
+    (2, 320, 441); a rate_out above rate_in: divisor 1 (44100 -> 48000: (1, 160, 147)).  ValueError for rates that are not
+    positive ints and for a fraction outside what decode_window(resample=) takes."""
+    for name, v in (("rate_in", rate_in), ("rate_out", rate_out)):
+        if not _is_int(v) or int(v) < 1:
+            raise ValueError("resample_plan: %s must be a positive int, got %r" % (name, v))
+    rate_in, rate_out = int(rate_in), int(rate_out)
+    fits = [check_rate_divisor(d, "resample_plan") for d in divisors]
+    d = max([d for d in fits if rate_in % d == 0 and rate_in // d >= rate_out] or [1])     # (a rate above the file's: full rate)
+    g = int(np.gcd(rate_out, rate_in // d))
+    up, down = rate_out // g, rate_in // d // g
+    check_resample((up, down), "resample_plan")
+    return d, up, down
 
 
 def check_levels_mix(mix, what="levels"):
@@ -178,8 +257,17 @@ class PacStore:
         library accepts for the handle's block lengths)"""
         return self.n_samples // check_rate_divisor(rate_divisor, "n_samples_at")
 
+    def n_samples_resampled(self, up, down, rate_divisor=1):
+        """the output samples of decode_window(resample=(up, down), rate_divisor=) that lie inside each file:
+        ceil(n_samples_at(rate_divisor) * up / down)"""
+        n = self.n_samples_at(rate_divisor)
+        for name, v in (("up", up), ("down", down)):
+            if not _is_int(v) or int(v) < 1:
+                raise ValueError("n_samples_resampled: %s must be a positive int, got %r" % (name, v))
+        return -((-n * int(up)) // int(down))
+
     def decode_window(self, files, starts, window, channels=None, dtype=None, out=None, stream=None, rate_divisor=1,
-                      mix=None):
+                      mix=None, resample=None):
         """Item i = samples [starts[i], starts[i] + window) of file files[i], zeros where that leaves the file (starts may be
         negative or past the end) -> a torch tensor [n][channels][window] on the handle's device.  dtype: torch.int16 (the
         default: the codes Handle.decode_pac_pcm16 writes, bit for bit), torch.float64 (the overlap-added signal before the
@@ -195,10 +283,19 @@ class PacStore:
         mix: None, or "mid", "left" or "right": one channel of every item, [n][1][window], a stereo file's left or right
         channel (the bits of that channel of the two-channel call) or its mid (L + R) / 2, formed on the MDCT lines before
         the one inverse transform (torch.float64: that plane; the other dtypes its conversions); a mono file gives its
-        channel.  channels must then be None or 1, and any other mix is a ValueError, before any library call."""
+        channel.  channels must then be None or 1, and any other mix is a ValueError, before any library call.
+        resample: None, or (up, down) or (up, down, zeros, rolloff) (mrc_pac_store_decode_window_resampled): the signal of
+        this call at that rate_divisor and mix, at up / down of its rate through a Hann-windowed sinc (resample_taps; zeros
+        16, rolloff 0.9475 unless given) that reads the float64 planes on the device -- 48 kHz files at 16 kHz:
+        rate_divisor=2, resample=(2, 3), which resample_plan(48000, 16000) says.  starts and window then count OUTPUT
+        samples, output n at time n down / up of the rate_divisor signal (n_samples_resampled of them lie inside a file);
+        torch.float64 is the fold defined in the header, bit for bit, the other dtypes its conversions.  A ratio of 1 after
+        reduction is the call without resample.  A ratio outside [1 / 8, 8], terms above 1024 after reduction, zeros outside
+        1..64 and rolloff outside [0.5, 1] are ValueErrors, before any library call."""
         import torch
         rate_divisor = check_rate_divisor(rate_divisor)
         mix = check_mix(mix, channels)
+        resample = check_resample(resample)
         if mix is not None:
             channels = 1
         files = np.ascontiguousarray(np.asarray(files, dtype=np.int64).reshape(-1))
@@ -226,7 +323,10 @@ class PacStore:
             stream = torch.cuda.current_stream(dev).cuda_stream
         tail = (n, files.ctypes.data, starts.ctypes.data, window, channels, fmt, out.data_ptr() if out.numel() else None,
                 stream or None)
-        if mix is not None:
+        if resample is not None:
+            self._handle._check(lib.mrc_pac_store_decode_window_resampled(
+                self._s, rate_divisor, _lib.MRC_MIX_EACH if mix is None else mix, *resample, *tail))
+        elif mix is not None:
             self._handle._check(lib.mrc_pac_store_decode_window_mix(self._s, rate_divisor, mix, *tail[:4], *tail[5:]))
         elif rate_divisor == 1:
             self._handle._check(lib.mrc_pac_store_decode_window(self._s, *tail))
@@ -343,7 +443,8 @@ class PacStore:
 
     def stats(self):
         """of the last decode_window: chunks_parsed, decode_launches, slabs, plan_bytes_uploaded, and ms: the device time of
-        the plan upload, the unpack kernel, the synthesis and window_out_kernel, summed over the slabs.  After levels() or
+        the plan upload, the unpack kernel, the synthesis and window_out_kernel (with resample=: resample_out_kernel, and the
+        counts are those of the intermediate spans), summed over the slabs.  After levels() or
         block_energy(): decode_launches counts block_energy_kernel launches, ms["synthesis"] is that kernel's time and
         ms["window_out"] is 0.  After band_energy_window(): decode_launches counts band_energy_kernel launches,
         ms["synthesis"] is the band sums' time (that kernel) and ms["window_out"] the frame assembly's (band_frames_kernel)."""

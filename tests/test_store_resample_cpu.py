@@ -1,0 +1,240 @@
+"""
+The store's rational-rate windows (mrc_resample_taps, mrc_pac_store_decode_window_resampled, PacStore.decode_window(resample=),
+store.resample_plan, cli -d --sample-rate) as far as a CPU reaches: the taps against the header's formula in NumPy float64 and
+their shape; the library's refusals with the argument named; the plan for pairs of rates; the Python-side refusals, raised
+before any library call; the command line's refusals; the binding; and the host-only header of the filter compiled into a
+stand-alone program (tests/resample_taps_check.cpp) under AddressSanitizer and UndefinedBehaviorSanitizer where g++ has them.
+"""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import chain_kit as kit
+import resample_restatement as RS
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RATIOS = ((1, 3), (2, 3), (3, 2), (160, 441), (320, 441), (147, 160), (160, 147), (1, 8), (8, 1))
+ROLLOFF = 0.9475
+SUM_BAR = {6: 1e-3, 16: 1e-4}                        # the NumPy formula alone: at most 6.1e-4 and 3.7e-5 over RATIOS
+
+
+def _formula(up, down, zeros, rolloff):
+    base = min(1.0, up / down) * rolloff
+    W = int(np.ceil(zeros / base))
+    j, p = np.arange(2 * W)[None, :], np.arange(up)[:, None]
+    t = base * ((j - W + 1) - p / up)
+    return W, np.where(np.abs(t) < zeros, base * np.sinc(t) * np.cos(np.pi * t / (2 * zeros)) ** 2, 0.0)
+
+
+@pytest.mark.parametrize("zeros", [6, 16])
+@pytest.mark.parametrize("up,down", RATIOS)
+def test_taps_are_the_formula_and_have_its_shape(up, down, zeros):
+    from mrcaudiocodec_amd.store import resample_taps
+    W, taps = resample_taps(up, down, zeros, ROLLOFF)
+    W_ref, ref = _formula(up, down, zeros, ROLLOFF)
+    assert W == W_ref and taps.shape == (up, 2 * W) and taps.dtype == np.float64
+    # 1e-14 absolute: taps are at most 1, and sin's argument reaches 64 pi, whose rounding alone moves sin by about 2e-14
+    # before the division by pi t -- a tighter bar would test NumPy's libm
+    err = np.abs(taps - ref).max()
+    print("%d / %d zeros %d: W = %d, max |delta| = %.3g, max |row sum - 1| = %.3g" % (up, down, zeros, W, err, np.abs(taps.sum(1) - 1).max()))
+    assert err <= 1e-14
+    assert np.abs(taps).max() <= 1.0
+    assert np.abs(taps.sum(axis=1) - 1.0).max() <= SUM_BAR[zeros]
+    assert np.abs(_formula(up, down, zeros, ROLLOFF)[1].sum(axis=1) - 1.0).max() <= SUM_BAR[zeros]
+    # symmetry.  d(p, j) = (j - W + 1) - p / up, so -d(p, j) = d(up - p, 2 W - 1 - j) for 0 < p < up, and -d(0, j) = d(0, 2 W - 2 - j):
+    # row 0 is symmetric about j = W - 1, and phase p mirrors phase up - p about the gap between taps W - 1 and W
+    assert np.array_equal(taps[0, :2 * W - 1], taps[0, :2 * W - 1][::-1])
+    for p in range(1, up):
+        assert np.abs(taps[p] - taps[up - p][::-1]).max() <= 1e-14
+
+
+def test_gcd_reduction_gives_the_same_bits():
+    from mrcaudiocodec_amd.store import resample_taps
+    W, a = resample_taps(4, 6, 16, ROLLOFF)
+    W2, b = resample_taps(2, 3, 16, ROLLOFF)
+    assert W == W2 and a.shape == b.shape == (2, 2 * W) and np.array_equal(a, b)
+    W3, c = resample_taps(441 * 5, 160 * 5, 6, 0.8)
+    assert np.array_equal(c, resample_taps(441, 160, 6, 0.8)[1]) and c.shape == (441, 2 * W3)
+
+
+def test_half_width_alone():
+    from mrcaudiocodec_amd import _lib
+    w = np.zeros(1, np.int32)
+    assert _lib.lib.mrc_resample_taps(2, 3, 16, ROLLOFF, w.ctypes.data, None) == 0 and w[0] == 26
+    assert _lib.lib.mrc_resample_taps(1, 8, 64, 0.5, w.ctypes.data, None) == 0 and w[0] == 1024       # the widest row: 2048 taps
+    assert _lib.lib.mrc_resample_taps(2, 3, 16, ROLLOFF, None, None) == 0
+
+
+@pytest.mark.parametrize("args,names", [
+    ((0, 3, 16, 0.9), ("up 0",)), ((-2, 3, 16, 0.9), ("up -2",)), ((2, 0, 16, 0.9), ("down 0",)),
+    ((1025, 1024, 16, 0.9), ("up 1025", "1024")), ((1024, 1025, 16, 0.9), ("down 1025", "1024")),
+    ((5, 5, 16, 0.9), ("up", "down", "is 1")), ((48000, 48000, 16, 0.9), ("up", "down", "is 1")),
+    ((1, 9, 16, 0.9), ("down 9", "8 * up")), ((9, 1, 16, 0.9), ("up 9", "8 * down")), ((100, 801, 16, 0.9), ("down 801", "8 * up")),
+    ((2, 3, 0, 0.9), ("zeros 0",)), ((2, 3, 65, 0.9), ("zeros 65",)), ((2, 3, -1, 0.9), ("zeros -1",)),
+    ((2, 3, 16, 0.4999), ("rolloff",)), ((2, 3, 16, 1.0001), ("rolloff",)), ((2, 3, 16, float("nan")), ("rolloff",)),
+])
+def test_the_library_refuses_and_names_the_argument(args, names):
+    from mrcaudiocodec_amd import MrcError, _lib
+    from mrcaudiocodec_amd.store import resample_taps
+    w, t = np.full(1, -5, np.int32), np.full(8, 7.0)
+    assert _lib.lib.mrc_resample_taps(*args, w.ctypes.data, t.ctypes.data) == _lib.MRC_ERR_INVALID
+    text = _lib.lib.mrc_last_error(None).decode()
+    assert text.startswith("mrc_resample_taps: ") and all(n in text for n in names), text
+    assert w[0] == -5 and (t == 7.0).all()
+    with pytest.raises(MrcError, match="mrc_resample_taps") as e:
+        resample_taps(*args)
+    assert e.value.code == -1
+
+
+def test_the_limits_themselves_are_accepted():
+    from mrcaudiocodec_amd.store import resample_taps
+    for args in ((1, 8, 1, 0.5), (8, 1, 64, 1.0), (1024, 1023, 1, 1.0), (128, 1024, 2, 0.5)):
+        W, taps = resample_taps(*args)
+        g = int(np.gcd(args[0], args[1]))
+        assert taps.shape == (args[0] // g, 2 * W) and 2 * W <= 2048 and taps.nbytes <= 16 << 20 and np.isfinite(taps).all()
+
+
+def test_resample_plan():
+    from mrcaudiocodec_amd.store import resample_plan
+    assert resample_plan(48000, 16000) == (2, 2, 3)
+    assert resample_plan(44100, 16000) == (2, 320, 441)
+    assert resample_plan(48000, 48000) == (1, 1, 1)
+    assert resample_plan(48000, 24000) == (2, 1, 1) and resample_plan(48000, 12000) == (4, 1, 1)
+    assert resample_plan(48000, 32000) == (1, 2, 3) and resample_plan(48000, 22050) == (2, 147, 160)
+    assert resample_plan(48000, 8000) == (4, 2, 3) and resample_plan(44100, 48000) == (1, 160, 147)
+    assert resample_plan(48000, 16000, divisors=(1,)) == (1, 1, 3) and resample_plan(48000, 16000, divisors=(1, 2)) == (2, 2, 3)
+    for (up, down) in RATIOS:                                   # the pairs of the taps test as rates: the fraction comes back reduced
+        d, u, w = resample_plan(down * 100, up * 100, divisors=(1,))
+        assert (d, u, w) == (1, up, down)
+    # the largest divisor whose rate still holds the output's band
+    for (rate_in, rate_out) in ((48000, 16000), (44100, 16000), (48000, 11025), (96000, 16000), (32000, 16000), (48000, 44100)):
+        d, up, down = resample_plan(rate_in, rate_out)
+        assert rate_in % d == 0 and rate_in // d >= rate_out and (d == 4 or rate_in % (2 * d) or rate_in // (2 * d) < rate_out)
+        assert np.gcd(up, down) == 1 and up * (rate_in // d) == down * rate_out
+    with pytest.raises(ValueError, match="above 1024"):
+        resample_plan(48000, 47999)
+    for bad in ((0, 16000), (48000, 0), (48000.0, 16000), (48000, "16000"), (True, 16000)):
+        with pytest.raises(ValueError, match="resample_plan"):
+            resample_plan(*bad)
+    with pytest.raises(ValueError, match="rate_divisor"):
+        resample_plan(48000, 16000, divisors=(1, 3))
+
+
+def test_restatement_fold_on_a_signal_it_can_be_checked_on():
+    """a tone well inside the pass band, resampled by the restatement with the library's taps, is the tone at the new rate"""
+    from mrcaudiocodec_amd.store import resample_taps
+    for (up, down) in ((2, 3), (1, 3), (3, 2), (160, 441)):
+        W, taps = resample_taps(up, down)
+        f = 0.05                                                 # cycles per intermediate sample
+        first, last = RS.span(-40, 300, up, down, W)
+        assert last - first + 1 <= RS.span_bound(300, up, down, W)
+        y = np.cos(2 * np.pi * f * np.arange(first, last + 1))
+        v = RS.fold(y, first, -40, 300, up, down, W, taps)
+        want = np.cos(2 * np.pi * f * (np.arange(-40, 260) * down / up))
+        assert np.abs(v - want).max() < 2e-4, (up, down, np.abs(v - want).max())
+    assert RS.span(0, 1, 2, 3, 26) == (-25, 26) and RS.span(-1, 2, 2, 3, 26) == (-27, 26) and RS.floor_div(-3, 2) == -2
+
+
+# ------------------------------------------------------------------ Python-side checks
+class _NoLibrary:
+    """in place of the library: any call through it fails the test"""
+
+    def __getattr__(self, name):
+        raise AssertionError("the library was reached: %s" % name)
+
+
+def _husk(monkeypatch):
+    from mrcaudiocodec_amd import store
+    monkeypatch.setattr(store, "lib", _NoLibrary())
+    s = store.PacStore.__new__(store.PacStore)
+    s._handle, s._s = None, None
+    s.n_channels, s.n_samples = np.array([2], np.int32), np.array([6144], np.int64)
+    return s
+
+
+@pytest.mark.parametrize("bad,text", [
+    ((2,), "resample must be None"), ((2, 3, 16), "resample must be None"), ("2/3", "resample must be None"), (2, "resample must be None"),
+    ((0, 3), "up must be a positive int"), ((2, -3), "down must be a positive int"), ((2.0, 3), "up must be a positive int"),
+    ((True, 3), "up must be a positive int"), ((2, "3"), "down must be a positive int"),
+    ((1025, 1024), r"up = 1025 .* above 1024"), ((3, 2050), r"down = 2050 .* above 1024"),
+    ((1, 9), r"1 / 9 is outside \[1 / 8, 8\]"), ((18, 2), r"9 / 1 is outside"),
+    ((2, 3, 0, 0.9), "zeros must be an int in 1..64"), ((2, 3, 65, 0.9), "zeros"), ((2, 3, 16.0, 0.9), "zeros"),
+    ((2, 3, 16, 0.3), r"rolloff must be a number in \[0.5, 1\]"), ((2, 3, 16, 1.5), "rolloff"), ((2, 3, 16, "0.9"), "rolloff"),
+    ((2, 3, 16, float("nan")), "rolloff"),
+])
+def test_bad_resample_is_refused_before_any_library_call(monkeypatch, bad, text):
+    s = _husk(monkeypatch)
+    with pytest.raises(ValueError, match="decode_window: .*" + text):
+        s.decode_window([0], [0], 16, resample=bad)
+    with pytest.raises(ValueError, match="rate_divisor"):
+        s.decode_window([0], [0], 16, resample=(2, 3), rate_divisor=3)
+    with pytest.raises(ValueError, match="mix must be"):
+        s.decode_window([0], [0], 16, resample=(2, 3), mix="side")
+
+
+def test_check_resample_and_n_samples_resampled(monkeypatch):
+    from mrcaudiocodec_amd import store
+    assert store.check_resample(None) is None and store.check_resample((3, 3)) is None and store.check_resample((6, 6, 8, 0.7)) is None
+    assert store.check_resample((4, 6)) == (2, 3, 16, 0.9475) and store.check_resample([441, 160, 6, 1]) == (441, 160, 6, 1.0)
+    assert store.check_resample((np.int64(2), np.int32(3), np.int64(6), np.float32(0.5))) == (2, 3, 6, 0.5)
+    s = _husk(monkeypatch)
+    assert s.n_samples_resampled(2, 3).tolist() == [4096] and s.n_samples_resampled(2, 3, 2).tolist() == [2048]
+    assert s.n_samples_resampled(160, 441, 4).tolist() == [-(-1536 * 160 // 441)] and s.n_samples_resampled(3, 2).tolist() == [9216]
+    for bad in ((0, 3), (2, 3.0)):
+        with pytest.raises(ValueError, match="n_samples_resampled"):
+            s.n_samples_resampled(*bad)
+    with pytest.raises(ValueError, match="rate_divisor"):
+        s.n_samples_resampled(2, 3, 3)
+
+
+# ------------------------------------------------------------------ the command line
+def test_check_sample_rate_args():
+    from mrcaudiocodec_amd import cli
+    assert cli.check_sample_rate_args(None, False) is None and cli.check_sample_rate_args(None, True, True) is None
+    assert cli.check_sample_rate_args(16000, True) == 16000
+    with pytest.raises(ValueError, match="--sample-rate.*needs -d"):
+        cli.check_sample_rate_args(16000, False)
+    with pytest.raises(ValueError, match="--sample-rate.*--rate-divisor"):
+        cli.check_sample_rate_args(16000, True, True)
+    for bad in (0, -16000, 16000.0, True, "16000"):
+        with pytest.raises(ValueError, match="--sample-rate"):
+            cli.check_sample_rate_args(bad, True)
+
+
+@pytest.mark.parametrize("argv,text", [
+    (["in.wav", "out.pac", "--sample-rate", "16000"], "--sample-rate decodes at another sample rate: it needs -d"),
+    (["-d", "in.pac", "out.wav", "--sample-rate", "16000", "--rate-divisor", "2"], "does not go with --rate-divisor"),
+    (["-d", "in.pac", "out.wav", "--sample-rate", "0"], "is not a positive number of Hz"),
+    (["--levels", "a.pac", "--sample-rate", "16000"], "--sample-rate"),
+    (["--band-energies", "a.pac", "b.npy", "--hop", "512", "--sample-rate", "16000"], "--sample-rate"),
+])
+def test_cli_refuses_a_sample_rate_that_makes_no_sense(argv, text, capsys):
+    from mrcaudiocodec_amd import cli
+    with pytest.raises(SystemExit) as e:
+        cli.main(argv)
+    assert e.value.code == 2 and text in capsys.readouterr().err
+
+
+# ------------------------------------------------------------------ the binding and the host-only header
+def test_binding_of_the_resample_calls():
+    kit.check_binding(("mrc_resample_taps", "mrc_pac_store_decode_window_resampled"))
+    args = kit.header_args("mrc_pac_store_decode_window_resampled")
+    assert args[1:7] == ["int rate_divisor", "int mix", "int up", "int down", "int zeros", "double rolloff"]
+    assert len(args) == len(kit.header_args("mrc_pac_store_decode_window_reduced")) + 5
+    assert kit.header_args("mrc_resample_taps")[:4] == ["int up", "int down", "int zeros", "double rolloff"]
+
+
+def test_filter_header_alone_under_sanitizers(tmp_path):
+    src = os.path.join(ROOT, "tests", "resample_taps_check.cpp")
+    exe = str(tmp_path / "resample_taps_check")
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]
+    probe = subprocess.run(["g++", "-x", "c++", "-", "-o", str(tmp_path / "probe")] + san,
+                           input=b"int main() { return 0; }\n", capture_output=True)
+    flags = san if probe.returncode == 0 else []
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra"] + flags +
+                          ["-I", os.path.join(ROOT, "mrcaudiocodec_amd", "csrc"), src, "-o", exe])
+    run = subprocess.run([exe], capture_output=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+    assert run.returncode == 0 and not run.stderr, run.stderr.decode(errors="replace")[-3000:]
+    print("sanitizers %s" % ("on" if flags else "not available"))
