@@ -232,6 +232,13 @@ int mrc_dev_mdct(mrc_handle* h, int a, int b, int64_t n_frames, const double* ch
 int mrc_dev_smr(mrc_handle* h, int a, int b, int64_t n_frames, const double* ch_left, const double* ch_right,
                 int64_t frame_stride, const int64_t* offsets, const double* lines, const int32_t* overall_scale,
                 double* smr, double* thresh /*nullable*/, void* stream);
+/* Everything of the encode that does not depend on the bit reservoir, as the encode calls launch it (the same kernel
+ * instantiations, MRC_OPT_SENSITIVITY counted), with the masking kernel's own outputs handed out: smr and band_peak
+ * [n][nsig][nBands] f64 (band_peak: max |line| of the band, unscaled).  Joint frames get the SMRs and peaks of the signals
+ * the M/S switch selects per band; units that no band selects stay unwritten.  ms_switch: joint only. */
+int mrc_dev_masking(mrc_handle* h, int a, int b, int64_t n_frames, const void* ch_left, const void* ch_right,
+                    int sample_format, int64_t frame_stride, const int64_t* offsets, double* lines, int32_t* overall_scale,
+                    int32_t* ms_switch, double* smr, double* band_peak, void* stream);
 int mrc_dev_alloc_quant(mrc_handle* h, int a, int b, int64_t n_frames, int joint,
                         const double* lines, const int32_t* overall_scale, const double* smr,
                         const int32_t* reservoir_in, int32_t* ms_switch, int32_t* bit_alloc,

@@ -93,6 +93,8 @@ def _load():
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
         "mrc_dev_smr": (C.c_int, [H, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "mrc_dev_masking": (C.c_int, [H, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64] +
+                            [C.c_void_p] * 7),
         "mrc_dev_alloc_quant": (C.c_int, [H, C.c_int, C.c_int, C.c_int64, C.c_int] + [C.c_void_p] * 10),
         "mrc_dev_encode": (C.c_int, [H, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64] +
                            [C.c_void_p] * 10),
@@ -1146,6 +1148,11 @@ class Handle:
                 thresh=None, stream=None):
         self._check(lib.mrc_dev_smr(self._h, a, b, n_frames, ch_left, ch_right, frame_stride, offsets, lines,
                                     overall_scale, smr, thresh, stream))
+
+    def dev_masking(self, a, b, n_frames, ch_left, ch_right, sample_format, frame_stride, offsets, lines, overall_scale,
+                    ms_switch, smr, band_peak, stream=None):
+        self._check(lib.mrc_dev_masking(self._h, a, b, n_frames, ch_left, ch_right, int(sample_format), frame_stride,
+                                        offsets, lines, overall_scale, ms_switch, smr, band_peak, stream))
 
     def dev_alloc_quant(self, a, b, n_frames, joint, lines, overall_scale, smr, reservoir_in, ms_switch, bit_alloc,
                         scale_factor, mantissa, reservoir_out, stream=None):

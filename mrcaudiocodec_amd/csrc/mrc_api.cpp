@@ -278,6 +278,21 @@ int mrc_dev_smr(mrc_handle* h, int a, int b, int64_t n_frames, const double* ch_
     return MRC_OK;
 }
 
+int mrc_dev_masking(mrc_handle* h, int a, int b, int64_t n_frames, const void* ch_left, const void* ch_right,
+                    int sample_format, int64_t frame_stride, const int64_t* offsets, double* lines, int32_t* overall_scale,
+                    int32_t* ms_switch, double* smr, double* band_peak, void* stream) {
+    if (!h || !ch_left || !lines || !overall_scale || !smr || !band_peak || n_frames < 0 || (ch_right && !ms_switch) ||
+        (sample_format != MRC_SAMPLES_F64 && sample_format != MRC_SAMPLES_PCM16))
+        return fail(h, MRC_ERR_INVALID, "mrc_dev_masking: bad argument");
+    const HostShape* hs;
+    int rc = get_shape(h, a, b, &hs);
+    if (rc) return rc;
+    if (!n_frames) return MRC_OK;
+    MRC_HIP(h, hipSetDevice(h->device));
+    return mrc::encode_phase_a(h, hs->dev, n_frames, ch_left, ch_right, sample_format, frame_stride, offsets, lines,
+                               overall_scale, ms_switch, smr, band_peak, pick_stream(h, stream), false);
+}
+
 int mrc_dev_alloc_quant(mrc_handle* h, int a, int b, int64_t n_frames, int joint, const double* lines,
                         const int32_t* overall_scale, const double* smr, const int32_t* reservoir_in,
                         int32_t* ms_switch, int32_t* bit_alloc, int32_t* scale_factor, int32_t* mantissa,

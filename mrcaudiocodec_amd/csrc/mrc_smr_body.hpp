@@ -848,12 +848,29 @@ __device__ __forceinline__ void smr_body(DevShape S, int nsigArg, const SampleT*
                 // bound t_lb of t; with E0 times the row's column R + 1 (sum of Lambda_m I_m 2^(-sigma_0 z_m), Lambda_m >= 1,
                 // sigma_0 >= every slope, over at least the maskers below the line) on top it is an upper bound t_ub.  The wave
                 // takes, per band, L = max of a2 / t_ub over ITS lines -- a ratio one of them reaches in the evaluation -- and
-                // evaluates only the lines with a2 >= L t_lb, gathered into one chunk.  The margins (1 - 2^-30, twice) cover
-                // the roundings of either bound, of recip_nr and the node tolerance: a line left out is strictly below a line
-                // that is evaluated, by the same arithmetic as before, so the integer maxima end as they did.
+                // evaluates only the lines with a2 >= L t_lb, gathered into one chunk.  The margins (kShrinkLb on L, kShrink
+                // on the comparison) cover the roundings of either bound, of the reciprocal and the node tolerance: a line
+                // left out is strictly below a line that is evaluated, by the same arithmetic as before, so the integer
+                // maxima end as they did.
                 // Chunks with a line near the SPL floor go through the set-aside path whole, as before; so does the original
                 // chunk of a contender whose error bound fails, and all four when the contenders do not fit.
+                // The bounds themselves only have to be SAFE, so the pass that forms them for all 1024 lines does without the
+                // accuracy the evaluation needs.  With mu = 2^-50 piH[cnt] (>= 4 ulp of either prefix sum) and d = fl(piH[cnt] -
+                // piH[nUp]) of the high parts alone, and t the sum that the evaluation's value stands for (it lies within the node
+                // tolerance, 1e-13, of it; 2^-30 and 2^-13 below have room for that):
+                //   in-band sum S as tail_sum forms it:  d - mu <= S <= d + mu   (the two low parts are each below half an ulp
+                //       of their high part, d's own rounding is another half; S >= 0)
+                //   t_lb = quiet + max(d - mu, 0) + lowE sc[cnt]   <= t (1 + 2^-50)      (three roundings)
+                //   E0'  = exp2_tab_above (the table entry above the exponent)  >= E0 (1 - 2^-52), at most 0.41 % above it
+                //   t_ub = t_lb + 2 mu + E0' col[R + 1]            >= t (1 - 2^-50)
+                //   r    = v_rcp_f64(t_ub) without a Newton step: within kRcpRel of 1 / t_ub.  recip_nr reaches its 2^-52
+                //       after two steps, each of which squares the error, from an estimate within 2^-13; twice that is taken.
+                //   lb   = a2 r kShrinkLb  <  a2 / t_ub (1 - 2^-13)  <  a2 recip_nr(t)   (kShrinkLb = 1 - 2 kRcpRel)
+                // so the band's L = max lb stays strictly below the ratio its line reaches in the evaluation, and a line with
+                // a2 < L t_lb kShrink has a2 recip_nr(t) < L (1 - 2^-31): strictly below that line, as before.  A looser bound
+                // only lets more lines through to the evaluation, which is tail_sum, node_chunk and line_ratio untouched.
                 constexpr double kShrink = 1.0 - 0x1p-30, kFloorHi = kSplFloorGuard * (1.0 + 0x1p-30);
+                constexpr double kRcpRel = 0x1p-12, kShrinkLb = 1.0 - 2 * kRcpRel, kInBandMargin = 0x1p-50;
                 static_assert(NT / kWave == 4 && DIM / kWave == 16, "a wave's chunks: four, the i-th in lines [256 i, 256 i + 256)");
                 double a2s[4], tlb[4];
                 int bnds[4];
@@ -865,7 +882,9 @@ __device__ __forceinline__ void smr_body(DevShape S, int nsigArg, const SampleT*
                     MRC_PHASE(i == 0 ? 25 : 6);
                     const int cnt = cntArr[k], nUp = nUpArr[k];
                     const double a2 = line_a2(cur);
-                    const double tl = tail_sum(cur.quiet, cnt, nUp, cur.lowE);
+                    const double ah = piH[cnt];
+                    const double d = ah - piH[nUp], mu = ah * kInBandMargin;
+                    const double tl = fma(cur.lowE, sc[cnt], cur.quiet + fmax(d - mu, 0.0));
                     const int bnd = cur.bnd;
                     const bool oneBand = __all(bnd == __builtin_amdgcn_readfirstlane(bnd));
                     const bool rowHead = (lane & 15) == 0;
@@ -874,9 +893,9 @@ __device__ __forceinline__ void smr_body(DevShape S, int nsigArg, const SampleT*
                     double lb = 0.0;
                     if (whole) setAside |= 1u << i;
                     else {
-                        const double E0 = exp2_tab64<TAB>(nodeS0, cur.z - 0.5, e2tab);
-                        const double tub = fma(E0, nodeQ[((nUp + kNodeC - 1) >> 2) * kNodeCols + kNodeR + 1], tl);
-                        lb = (a2 * recip_nr(tub)) * kShrink;
+                        const double E0 = exp2_tab_above<TAB>(nodeS0, cur.z - 0.5, e2tab);
+                        const double tub = fma(E0, nodeQ[((nUp + kNodeC - 1) >> 2) * kNodeCols + kNodeR + 1], tl + (mu + mu));
+                        lb = (a2 * __builtin_amdgcn_rcp(tub)) * kShrinkLb;
                     }
                     // (every line's |X| goes into the band peaks here; the band's bound from the lines of this chunk)
                     if (oneBand) {

@@ -79,6 +79,15 @@ __device__ __forceinline__ double exp2_tab64(double sT, double u, const double* 
     return ldexp(p * tab[n & (kExpTab - 1)], n >> kExpTabShift);
 }
 
+// An UPPER BOUND of the same 2^(sT*u/T) from the table alone: with n = rint(sT*u), sT*u <= n + 1/2 < n + 1, so entry n + 1
+// (correctly rounded: within 2^-53 of 2^((n+1)/T)) is above it, by at most 2^(3/(2T)) - 1 (T = 256: 0.41 %).  No polynomial.
+template <int T>
+__device__ __forceinline__ double exp2_tab_above(double sT, double u, const double* __restrict__ tab) {
+    static_assert(T == kExpTab || T == kExpTabLong, "the tables staged in LDS");
+    const int n = __double2loint(fma(sT, u, 0x1.8p52)) + 1;
+    return ldexp(tab[n & (T - 1)], n >> (T == kExpTabLong ? 8 : kExpTabShift));
+}
+
 // 2^(j/64), j = 0..63, correctly rounded
 __constant__ double kExp2Tab[kExpTab] = {
     0x1.0000000000000p+0, 0x1.02c9a3e778061p+0, 0x1.059b0d3158574p+0, 0x1.0874518759bc8p+0,

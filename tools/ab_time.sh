@@ -1,9 +1,10 @@
 #!/bin/bash
 # smr_kernel time (hipEvents, headline bench workload) of several library builds in one gpurun call (profiling builds
-# give wrong results: only the kernel times are read).  usage: tools/ab_time.sh <out-prefix> <name> ...
+# give wrong results: only the kernel times are read).  usage: [ROUNDS=3] tools/ab_time.sh <out-prefix> <name> ...
+# (interleaved rounds: every build once per round, in the order given)
 pre=$1; shift
 repo=$PWD
-for round in 1 2; do
+for round in $(seq 1 ${ROUNDS:-3}); do
     for v in default "$@"; do
         lib=$repo/mrcaudiocodec_amd/libmrc_hip.so
         [ "$v" != default ] && lib=$repo/mrcaudiocodec_amd/libmrc_hip_$v.so
