@@ -243,6 +243,22 @@ int mrc_dev_alloc_quant(mrc_handle* h, int a, int b, int64_t n_frames, int joint
                         const double* lines, const int32_t* overall_scale, const double* smr,
                         const int32_t* reservoir_in, int32_t* ms_switch, int32_t* bit_alloc,
                         int32_t* scale_factor, int32_t* mantissa, int32_t* reservoir_out, void* stream);
+/* mrc_dev_alloc_quant through the CHAINED back end (the sorted grant events and the serial scan of the chained encodes, which
+ * mrc_encode_mono / mrc_encode_joint also take for 64 blocks or fewer), with the reservoir carried from block to block:
+ * consecutive runs of blocks_per_stream (>= 1, dividing n_frames) blocks form a stream; reservoir_in (NULL: zeros) and
+ * reservoir_out have one entry per STREAM, reservoir_trace (nullable) [n_frames] the reservoir behind every block.  With
+ * use_huffman the cheapest of the four tables is priced per block and channel and its saving goes into the reservoir
+ * (codecThem.py:136-180,224,274); huff_table (nullable) [n_frames][nstream] receives the ids (15: raw).  The M/S switch and
+ * the band peaks are computed as mrc_dev_alloc_quant computes them.  The mantissa plane is the back end's own:
+ * mantissa16 [n][nstream][N/2] uint16 (MRC_MANTISSA_I16), 8-byte aligned; lines 16-byte aligned.  MRC_OPT_CHAIN_THREADS and
+ * MRC_OPT_CHAIN_FORCE_REPAIR are honoured.  MRC_ERR_INVALID: a shape outside the chained back end (more than 64 coded bands,
+ * more than 2048 coded lines per block, lines not a multiple of 4), a NULL output, a bad blocks_per_stream, a misaligned
+ * plane.  Not timed, not counted; workspace in the handle: one stream per handle at a time. */
+int mrc_dev_alloc_quant_chained(mrc_handle* h, int a, int b, int64_t n_frames, int joint, int64_t blocks_per_stream,
+                                int use_huffman, const double* lines, const int32_t* overall_scale, const double* smr,
+                                const int32_t* reservoir_in, int32_t* ms_switch, int32_t* bit_alloc, int32_t* scale_factor,
+                                uint16_t* mantissa16, int32_t* huff_table, int32_t* reservoir_out, int32_t* reservoir_trace,
+                                void* stream);
 /* The three stages back to back, intermediates in the handle's workspace (grown on demand, never
  * inside a timed loop once warm).  lines_out may be NULL. */
 int mrc_dev_encode(mrc_handle* h, int a, int b, int64_t n_frames, const double* ch_left, const double* ch_right,

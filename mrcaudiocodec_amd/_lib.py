@@ -96,6 +96,8 @@ def _load():
         "mrc_dev_masking": (C.c_int, [H, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64] +
                             [C.c_void_p] * 7),
         "mrc_dev_alloc_quant": (C.c_int, [H, C.c_int, C.c_int, C.c_int64, C.c_int] + [C.c_void_p] * 10),
+        "mrc_dev_alloc_quant_chained": (C.c_int, [H, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int] +
+                                        [C.c_void_p] * 12),
         "mrc_dev_encode": (C.c_int, [H, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64] +
                            [C.c_void_p] * 10),
         "mrc_dev_encode_ex": (C.c_int, [H, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64] +
@@ -1159,6 +1161,16 @@ class Handle:
         self._check(lib.mrc_dev_alloc_quant(self._h, a, b, n_frames, int(joint), lines, overall_scale, smr,
                                             reservoir_in, ms_switch, bit_alloc, scale_factor, mantissa,
                                             reservoir_out, stream))
+
+    def dev_alloc_quant_chained(self, a, b, n_frames, joint, blocks_per_stream, use_huffman, lines, overall_scale, smr,
+                                reservoir_in, ms_switch, bit_alloc, scale_factor, mantissa16, huff_table, reservoir_out,
+                                reservoir_trace=None, stream=None):
+        """mrc_dev_alloc_quant through the chained back end: streams of blocks_per_stream consecutive blocks, reservoirs
+        per stream, the mantissa plane uint16"""
+        self._check(lib.mrc_dev_alloc_quant_chained(self._h, a, b, n_frames, int(joint), int(blocks_per_stream),
+                                                    int(bool(use_huffman)), lines, overall_scale, smr, reservoir_in,
+                                                    ms_switch, bit_alloc, scale_factor, mantissa16, huff_table,
+                                                    reservoir_out, reservoir_trace, stream))
 
     def set_option(self, option, value):
         self._check(lib.mrc_set_option(self._h, int(option), int(value)))

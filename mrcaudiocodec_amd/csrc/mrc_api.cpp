@@ -719,13 +719,9 @@ int encode_host(mrc_handle* h, int64_t n, int a, int b, const double* left, cons
                                                  (const int*)(dev + oScale), (const int*)(dev + oSw), B.ev.as<unsigned>(),
                                                  B.pre.as<unsigned>(), (int*)(dev + oBa), (int*)(dev + oSf),
                                                  (unsigned short*)(dev + oMant), B.table.as<int32_t>());
-        std::memcpy(pin + oDesc, &D, sizeof D);
-        for (int64_t i = 0; i < n; ++i) {
-            reinterpret_cast<int32_t*>(pin + oItems)[i] = (int32_t)i;                  // group 0, block i
-            reinterpret_cast<long long*>(pin + oStart)[i] = i;
-            reinterpret_cast<int32_t*>(pin + oRes)[i] = reservoir_in ? reservoir_in[i] : 0;
-        }
-        reinterpret_cast<long long*>(pin + oStart)[n] = n;
+        chain_one_group(D, n, 1, reinterpret_cast<ChainGroupDev*>(pin + oDesc), reinterpret_cast<int32_t*>(pin + oItems),
+                        reinterpret_cast<long long*>(pin + oStart));                   // every block a stream of its own
+        for (int64_t i = 0; i < n; ++i) reinterpret_cast<int32_t*>(pin + oRes)[i] = reservoir_in ? reservoir_in[i] : 0;
         hipStream_t st = h->stream;
         MRC_HIP(h, hipMemcpyAsync(dev, pin, oScale, hipMemcpyHostToDevice, st));
         const bool timing = h->timing;

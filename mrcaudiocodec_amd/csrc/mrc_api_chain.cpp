@@ -58,6 +58,13 @@ ChainGroupDev chain_group_desc(const HostShape& hs, int joint, const double* lin
     return D;
 }
 
+void chain_one_group(const ChainGroupDev& D, int64_t n, int64_t blocksPerStream, ChainGroupDev* desc, int32_t* items,
+                     long long* itemStart) {
+    *desc = D;
+    for (int64_t i = 0; i < n; ++i) items[i] = (int32_t)i;                             // group 0, block i
+    for (int64_t s = 0; s * blocksPerStream <= n; ++s) itemStart[s] = s * blocksPerStream;
+}
+
 }  // namespace mrc
 
 namespace {
@@ -106,6 +113,71 @@ int64_t mrc_chain_out_bound_ex(mrc_handle* h, int n_channels, int64_t n_streams,
 int64_t mrc_chain_out_bound(mrc_handle* h, int64_t n_streams, const int64_t* block_start, const int32_t* block_a,
                             const int32_t* block_b, int with_flush, int with_headers) {
     return mrc_chain_out_bound_ex(h, 2, n_streams, block_start, block_a, block_b, with_flush, with_headers);
+}
+
+// The chained back end on the caller's lines and SMRs: what encode_host's few-block path launches behind encode_phase_a,
+// with band_stats_kernel and ms_switch_kernel in place of the masking kernel's peaks and switch (as mrc_dev_alloc_quant).
+int mrc_dev_alloc_quant_chained(mrc_handle* h, int a, int b, int64_t n_frames, int joint, int64_t blocks_per_stream,
+                                int use_huffman, const double* lines, const int32_t* overall_scale, const double* smr,
+                                const int32_t* reservoir_in, int32_t* ms_switch, int32_t* bit_alloc, int32_t* scale_factor,
+                                uint16_t* mantissa16, int32_t* huff_table, int32_t* reservoir_out, int32_t* reservoir_trace,
+                                void* stream) {
+    if (!h || !lines || !overall_scale || !smr || !bit_alloc || !scale_factor || !mantissa16 || !reservoir_out ||
+        (joint && !ms_switch) || n_frames < 0)
+        return fail(h, MRC_ERR_INVALID, "mrc_dev_alloc_quant_chained: null argument or negative frame count");
+    if (blocks_per_stream < 1 || n_frames % blocks_per_stream)
+        return fail(h, MRC_ERR_INVALID, "mrc_dev_alloc_quant_chained: n_frames must be a multiple of blocks_per_stream >= 1");
+    if (n_frames >= ((int64_t)1 << 28)) return fail(h, MRC_ERR_INVALID, "mrc_dev_alloc_quant_chained: too many blocks");
+    if ((reinterpret_cast<uintptr_t>(lines) & 15) || (reinterpret_cast<uintptr_t>(mantissa16) & 7))
+        return fail(h, MRC_ERR_INVALID, "mrc_dev_alloc_quant_chained: lines must be 16-byte aligned, mantissa16 8-byte aligned");
+    const HostShape* hs;
+    MRC_TRY(get_shape(h, a, b, &hs));
+    const DevShape& S = hs->dev;
+    joint = joint ? 1 : 0;
+    const int nstream = joint ? 2 : 1;
+    if (const char* why = chain_shape_misfit(S, nstream))
+        return fail(h, MRC_ERR_INVALID, std::string("mrc_dev_alloc_quant_chained: ") + why);
+    const int64_t n = n_frames, nStreams = n / blocks_per_stream;
+    if (n == 0) return MRC_OK;
+    MRC_HIP(h, hipSetDevice(h->device));
+    hipStream_t st = pick_stream(h, stream);
+    SmallBatchBufs& B = h->smallBatch;
+    const size_t nEv = chain_events_per_block(S, joint);
+    StageLayout lay(16);
+    const size_t oDesc = lay.add<ChainGroupDev>(1), oItems = lay.add<int32_t>((size_t)n),
+                 oStart = lay.add<long long>((size_t)nStreams + 1), total = lay.total();
+    MRC_HIP(h, B.ctl.reserve(total));
+    MRC_HIP(h, B.ev.reserve((size_t)n * nEv * sizeof(unsigned)));
+    MRC_HIP(h, B.pre.reserve((size_t)n * (nEv + 1) * sizeof(unsigned)));
+    if (!huff_table) MRC_HIP(h, B.table.reserve((size_t)n * nstream * sizeof(int32_t)));
+    MRC_HIP(h, h->ws.peak.reserve(alloc_workspace_bytes(S, n, joint)));
+    double* peak = h->ws.peak.as<double>();
+    char* dev = (char*)B.ctl.p;
+    // page-locked staging, copied on the caller's stream: the previous call's copy must have read it before it is refilled
+    MRC_HIP(h, B.ctlCopied.create(hipEventDisableTiming));
+    MRC_HIP(h, hipEventSynchronize(B.ctlCopied));
+    MRC_HIP(h, B.ctlPin.reserve(total));
+    char* host = (char*)B.ctlPin.p;
+    chain_one_group(chain_group_desc(*hs, joint, lines, peak, overall_scale, ms_switch, B.ev.as<unsigned>(),
+                                     B.pre.as<unsigned>(), bit_alloc, scale_factor, mantissa16,
+                                     huff_table ? huff_table : B.table.as<int32_t>()),
+                    n, blocks_per_stream, reinterpret_cast<ChainGroupDev*>(host + oDesc),
+                    reinterpret_cast<int32_t*>(host + oItems), reinterpret_cast<long long*>(host + oStart));
+    MRC_HIP(h, hipMemcpyAsync(dev, host, total, hipMemcpyHostToDevice, st));
+    MRC_HIP(h, hipEventRecord(B.ctlCopied, st));
+    if (!reservoir_in) MRC_HIP(h, hipMemsetAsync(reservoir_out, 0, (size_t)nStreams * sizeof(int32_t), st));
+    else if (reservoir_in != reservoir_out)
+        MRC_HIP(h, hipMemcpyAsync(reservoir_out, reservoir_in, (size_t)nStreams * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    MRC_HIP(h, launch_band_peaks(S, n, joint, lines, peak, st));
+    if (joint)                                                      // on the UNSCALED L / R lines (codecThem.py:436)
+        MRC_HIP(h, launch_ms_switch(n, S.nBands, S.msLeaves, S.msInternal, S.msPlan, lines, lines + S.halfN,
+                                    4 * (int64_t)S.halfN, S.halfN, ms_switch, st));
+    MRC_HIP(h, launch_chain_prep(S, joint, n, smr, joint ? ms_switch : nullptr, B.ev.as<unsigned>(), B.pre.as<unsigned>(),
+                                 h->chainForceFallback ? 1 : 0, st));
+    MRC_HIP(h, launch_chain_phase_b(nStreams, 1, (const ChainGroupDev*)(dev + oDesc), (const int*)(dev + oItems),
+                                    (const long long*)(dev + oStart), reservoir_out, reservoir_trace, n,
+                                    use_huffman ? 1 : 0, h->chainThreads, st));
+    return MRC_OK;
 }
 
 }  // extern "C"

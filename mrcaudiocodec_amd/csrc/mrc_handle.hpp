@@ -131,6 +131,9 @@ struct SmallBatchBufs {
     DevBuf layout;                   // inputs, scan descriptor, reservoirs and results of the call, back to back
     DevBuf ev, pre;                  // chain_prep_kernel's grant events and the bits spent before each
     DevBuf table;                    // the scan's table ids (all 15: no pricing)
+    DevBuf ctl;                      // mrc_dev_alloc_quant_chained: scan descriptor, items, item starts ...
+    PinnedBuf ctlPin;                // ... their page-locked staging ...
+    Event ctlCopied;                 // ... and the copy between the two, waited for before the staging is refilled
     PinnedBuf pinIn, pinOut;
 };
 
@@ -525,6 +528,11 @@ const char* chain_shape_misfit(const DevShape& S, int nstream);
 ChainGroupDev chain_group_desc(const HostShape& hs, int joint, const double* lines, const double* peak, const int* oscale,
                                const int* ms, const unsigned* ev, const unsigned* pre, int* bitAlloc, int* scaleFactor,
                                unsigned short* mant, int* table);
+// The scan's control data for n blocks of ONE group, cut into streams of blocksPerStream consecutive blocks (n a multiple of
+// it): the descriptor, item i = block i of group 0, stream s = items [s blocksPerStream, (s + 1) blocksPerStream).  Host
+// memory: desc [1], items [n], itemStart [n / blocksPerStream + 1].
+void chain_one_group(const ChainGroupDev& D, int64_t n, int64_t blocksPerStream, ChainGroupDev* desc, int32_t* items,
+                     long long* itemStart);
 
 // phase A of the per-block path (windowed MDCT + overall scale -> [M/S switch] -> SMRs and per-band peaks), defined in
 // mrc_api.cpp beside encode_core, which it is the first half of.  smr == nullptr: it stops behind the M/S switch.

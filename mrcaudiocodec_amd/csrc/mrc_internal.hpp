@@ -136,6 +136,10 @@ hipError_t launch_pcm_to_float(int64_t n, const short* pcm, double* out, hipStre
 hipError_t launch_quantize_uniform(int64_t n, int nBits, const double* x, long long* out, hipStream_t st);
 hipError_t launch_bark(int64_t n, const double* f, double* out, hipStream_t st);
 size_t alloc_workspace_bytes(const DevShape& S, int64_t nFrames, int joint);   // bandPeakWs size
+// band_stats_kernel alone: bandPeak [n][nsig][nBands] = max |line| of every band of every signal (what the stage entry points
+// have in place of smr_kernel's peaks)
+hipError_t launch_band_peaks(const DevShape& S, int64_t nFrames, int joint, const double* lines, double* bandPeak,
+                             hipStream_t st);
 // mrc_kernels_decode.hip
 hipError_t launch_decode(const DevShape& S, int64_t nBlocks, int nStreams, const int* oscale, const int* msSwitch,
                          const int* scaleFactor, const int* bitAlloc, const int* mantissa, const int64_t* outOffset,

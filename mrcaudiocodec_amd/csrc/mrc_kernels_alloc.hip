@@ -537,6 +537,14 @@ size_t alloc_workspace_bytes(const DevShape& S, int64_t nFrames, int joint) {
     return (size_t)nFrames * (joint ? 4 : 1) * S.nBands * sizeof(double);
 }
 
+hipError_t launch_band_peaks(const DevShape& S, int64_t nFrames, int joint, const double* lines, double* bandPeak,
+                             hipStream_t st) {
+    if (nFrames <= 0) return hipSuccess;
+    hipLaunchKernelGGL(band_stats_kernel, dim3((unsigned)nFrames), dim3(kWave), 0, st, S, joint, 1, lines, (int*)nullptr,
+                       bandPeak);
+    return hipGetLastError();
+}
+
 hipError_t launch_alloc_quant(const DevShape& S, int64_t nFrames, int joint, const double* lines, const int* oscale,
                               const double* smr, const int* resIn, int* msSwitch, int* bitAlloc, int* scaleFactor,
                               void* mantissa, int mantFmt, int* resOut, double* bandPeakWs, bool peaksReady, bool msReady,
@@ -546,9 +554,7 @@ hipError_t launch_alloc_quant(const DevShape& S, int64_t nFrames, int joint, con
     if (nFrames <= 0) return hipSuccess;
     const int nTot = (joint ? 2 : 1) * S.nBands;
     // the per-band peaks come from smr_kernel on the full path; band_stats_kernel only serves the stage entry points
-    if (!peaksReady)
-        hipLaunchKernelGGL(band_stats_kernel, dim3((unsigned)nFrames), dim3(kWave), 0, st, S, joint, 1, lines, msSwitch,
-                           bandPeakWs);
+    if (!peaksReady) (void)launch_band_peaks(S, nFrames, joint, lines, bandPeakWs, st);
     if (joint && !msReady) {                             // on the UNSCALED L / R lines (codecThem.py:436)
         hipError_t e = launch_ms_switch(nFrames, S.nBands, S.msLeaves, S.msInternal, S.msPlan, lines, lines + S.halfN,
                                         4 * (int64_t)S.halfN, S.halfN, msSwitch, st);
