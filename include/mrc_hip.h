@@ -259,6 +259,39 @@ int mrc_dev_alloc_quant_chained(mrc_handle* h, int a, int b, int64_t n_frames, i
                                 const int32_t* reservoir_in, int32_t* ms_switch, int32_t* bit_alloc, int32_t* scale_factor,
                                 uint16_t* mantissa16, int32_t* huff_table, int32_t* reservoir_out, int32_t* reservoir_trace,
                                 void* stream);
+/* The three kernels of the constant-quality VBR calls (mrc_encode_vbr_nmr_pac, mrc_encode_vbr_size_pac) on the caller's
+ * planes: n_frames independent blocks of shape (a, b), all mono or all joint, through exactly the launches those calls make
+ * (first block 0, chunks in block order, every block a stream of its own).  All pointers are device memory.
+ *   inputs   lines [n][nsig][N/2] f64 phase A's UNSCALED lines (joint: L, R, M, S); overall_scale [n][nsig] i32;
+ *            ms_switch [n][nBands] i32 (joint only, else nullable); source_lines / source_thresh [nstream][n][N/2] f64: the
+ *            source analysis X and T (dB) per output channel -- all left rows, then all right rows; ceiling: LINEAR (the
+ *            calls' pow(10, dB / 10)), +inf and 0 allowed.
+ *   outputs  bit_alloc / scale_factor [n][nstream][nBands] i32; mantissa16 [n][nstream][N/2] uint16; stat [n][nstream][2]
+ *            f64 = {max_j r_j, b * mean_j r_j} of the output channel; capped [n][nstream] i32: the block's capped bands at
+ *            its first entry, 0 at its second.
+ * mrc_dev_vbr_profile hands out the record of the walk without a ceiling: ratios [n][nBands][W] f64, W =
+ * mrc_vbr_record_width(joint), first filled with NaN by the entry so that the states the walk wrote can be told; picks
+ * [n][nBands] u32 (joint only, else nullable).  Mono band: r at state i (0, 2, 3, .. bits) in [i].  Joint L/R band: stream
+ * s's in [s * W / 2 + i].  M/S band: {r_L, r_R} of step i in [2 i], [2 i + 1], bit i of the pick word the stream raised
+ * behind step i.  mrc_dev_vbr_pick takes such a record and ceilings [n] f64 (one per block) and leaves what
+ * mrc_dev_vbr_alloc leaves at that ceiling.  The planes need their types' natural alignment only.
+ * MRC_ERR_INVALID (with a message naming the argument): a NULL plane; a NaN ceiling; n_frames < 0; a shape the handle does
+ * not have, one outside the chained back end (more than 2048 coded lines per block, lines not a multiple of 4) or one whose
+ * walk the kernels cannot hold (more than MRC_MAX_BANDS bands, more than 60 KB of LDS).  n_frames == 0 returns MRC_OK and
+ * writes nothing.  Not timed, not counted; workspace in the handle: one stream per handle
+ * at a time. */
+int mrc_vbr_record_width(int joint);
+int mrc_dev_vbr_alloc(mrc_handle* h, int a, int b, int64_t n_frames, int joint, double ceiling, const double* lines,
+                      const int32_t* overall_scale, const int32_t* ms_switch, const double* source_lines,
+                      const double* source_thresh, int32_t* bit_alloc, int32_t* scale_factor, uint16_t* mantissa16,
+                      double* stat, int32_t* capped, void* stream);
+int mrc_dev_vbr_profile(mrc_handle* h, int a, int b, int64_t n_frames, int joint, const double* lines,
+                        const int32_t* overall_scale, const int32_t* ms_switch, const double* source_lines,
+                        const double* source_thresh, double* ratios, uint32_t* picks, void* stream);
+int mrc_dev_vbr_pick(mrc_handle* h, int a, int b, int64_t n_frames, int joint, const double* ceilings, const double* lines,
+                     const int32_t* overall_scale, const int32_t* ms_switch, const double* ratios, const uint32_t* picks,
+                     int32_t* bit_alloc, int32_t* scale_factor, uint16_t* mantissa16, double* stat, int32_t* capped,
+                     void* stream);
 /* The three stages back to back, intermediates in the handle's workspace (grown on demand, never
  * inside a timed loop once warm).  lines_out may be NULL. */
 int mrc_dev_encode(mrc_handle* h, int a, int b, int64_t n_frames, const double* ch_left, const double* ch_right,

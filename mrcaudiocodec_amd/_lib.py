@@ -98,6 +98,10 @@ def _load():
         "mrc_dev_alloc_quant": (C.c_int, [H, C.c_int, C.c_int, C.c_int64, C.c_int] + [C.c_void_p] * 10),
         "mrc_dev_alloc_quant_chained": (C.c_int, [H, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int] +
                                         [C.c_void_p] * 12),
+        "mrc_vbr_record_width": (C.c_int, [C.c_int]),
+        "mrc_dev_vbr_alloc": (C.c_int, [H, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_double] + [C.c_void_p] * 11),
+        "mrc_dev_vbr_profile": (C.c_int, [H, C.c_int, C.c_int, C.c_int64, C.c_int] + [C.c_void_p] * 8),
+        "mrc_dev_vbr_pick": (C.c_int, [H, C.c_int, C.c_int, C.c_int64, C.c_int] + [C.c_void_p] * 12),
         "mrc_dev_encode": (C.c_int, [H, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64] +
                            [C.c_void_p] * 10),
         "mrc_dev_encode_ex": (C.c_int, [H, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64] +
@@ -1171,6 +1175,31 @@ class Handle:
                                                     int(bool(use_huffman)), lines, overall_scale, smr, reservoir_in,
                                                     ms_switch, bit_alloc, scale_factor, mantissa16, huff_table,
                                                     reservoir_out, reservoir_trace, stream))
+
+    @staticmethod
+    def vbr_record_width(joint):
+        """ratios per band of a VBR record (dev_vbr_profile / dev_vbr_pick)"""
+        return int(lib.mrc_vbr_record_width(int(bool(joint))))
+
+    def dev_vbr_alloc(self, a, b, n_frames, joint, ceiling, lines, overall_scale, ms_switch, source_lines, source_thresh,
+                      bit_alloc, scale_factor, mantissa16, stat, capped, stream=None):
+        """vbr_alloc_kernel on caller-made planes at the LINEAR ceiling (include/mrc_hip.h: mrc_dev_vbr_alloc)"""
+        self._check(lib.mrc_dev_vbr_alloc(self._h, a, b, n_frames, int(bool(joint)), float(ceiling), lines, overall_scale,
+                                          ms_switch, source_lines, source_thresh, bit_alloc, scale_factor, mantissa16, stat,
+                                          capped, stream))
+
+    def dev_vbr_profile(self, a, b, n_frames, joint, lines, overall_scale, ms_switch, source_lines, source_thresh, ratios,
+                        picks, stream=None):
+        """vbr_profile_kernel on caller-made planes: the record ratios [n][nBands][vbr_record_width(joint)] (NaN where the
+        walk wrote nothing) and picks [n][nBands] (joint)"""
+        self._check(lib.mrc_dev_vbr_profile(self._h, a, b, n_frames, int(bool(joint)), lines, overall_scale, ms_switch,
+                                            source_lines, source_thresh, ratios, picks, stream))
+
+    def dev_vbr_pick(self, a, b, n_frames, joint, ceilings, lines, overall_scale, ms_switch, ratios, picks, bit_alloc,
+                     scale_factor, mantissa16, stat, capped, stream=None):
+        """vbr_pick_kernel on a record of dev_vbr_profile, one linear ceiling per block"""
+        self._check(lib.mrc_dev_vbr_pick(self._h, a, b, n_frames, int(bool(joint)), ceilings, lines, overall_scale, ms_switch,
+                                         ratios, picks, bit_alloc, scale_factor, mantissa16, stat, capped, stream))
 
     def set_option(self, option, value):
         self._check(lib.mrc_set_option(self._h, int(option), int(value)))

@@ -630,6 +630,50 @@ int vbr_call(mrc_handle* h, const std::string& w, double ceiling_db, const VbrSi
     return rc;
 }
 
+// The stage entries of the VBR kernels (mrc_dev_vbr_alloc, _profile, _pick): n independent blocks of one shape on the caller's
+// planes.  File order as the launches take it: the chunks of block k are ns k, ns k + 1 (chunkMap the identity, chunkBase
+// 0), and every block is a stream of its own (chunkStream [chunk] = chunk / ns), so that a pick has one ceiling per block.
+struct VbrStage {
+    const HostShape* hs = nullptr;
+    int joint = 0, ns = 1;
+    hipStream_t st = nullptr;
+    const long long* chunkMap = nullptr;
+    const int* chunkStream = nullptr;
+};
+
+int vbr_stage(mrc_handle* h, const std::string& who, int a, int b, int64_t n, int joint, void* stream, VbrStage* v) {
+    if (n < 0 || n >= ((int64_t)1 << 28)) return fail(h, MRC_ERR_INVALID, who + ": n_frames negative or too large");
+    MRC_TRY(get_shape(h, a, b, &v->hs));
+    const DevShape& S = v->hs->dev;
+    v->joint = joint ? 1 : 0;
+    v->ns = joint ? 2 : 1;
+    if (const char* why = chain_shape_misfit(S, v->ns)) return fail(h, MRC_ERR_INVALID, who + ": " + why);
+    if (S.nBands > kMaxBands || vbr_lds_bytes(S, v->joint) > 60 * 1024)
+        return fail(h, MRC_ERR_INVALID, who + ": block shape (a, b) outside what the VBR kernels hold in LDS");
+    if (n == 0) return MRC_OK;
+    MRC_HIP(h, hipSetDevice(h->device));
+    v->st = pick_stream(h, stream);
+    VbrBufs& V = h->vbr;
+    const size_t chunks = (size_t)n * v->ns;
+    StageLayout lay(16);
+    const size_t oMap = lay.add<long long>(chunks), oStream = lay.add<int>(chunks), total = lay.total();
+    MRC_HIP(h, V.stageMap.reserve(total));
+    // page-locked staging, copied on the caller's stream: the previous call's copy must have read it before it is refilled
+    MRC_HIP(h, V.stageCopied.create(hipEventDisableTiming));
+    MRC_HIP(h, hipEventSynchronize(V.stageCopied));
+    MRC_HIP(h, V.stagePin.reserve(total));
+    char* host = (char*)V.stagePin.p;
+    for (size_t c = 0; c < chunks; ++c) {
+        reinterpret_cast<long long*>(host + oMap)[c] = (long long)c;
+        reinterpret_cast<int*>(host + oStream)[c] = (int)(c / v->ns);
+    }
+    MRC_HIP(h, hipMemcpyAsync(V.stageMap.p, host, total, hipMemcpyHostToDevice, v->st));
+    MRC_HIP(h, hipEventRecord(V.stageCopied, v->st));
+    v->chunkMap = reinterpret_cast<const long long*>((char*)V.stageMap.p + oMap);
+    v->chunkStream = reinterpret_cast<const int*>((char*)V.stageMap.p + oStream);
+    return MRC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -739,6 +783,64 @@ int mrc_get_vbr_size_ms(mrc_handle* h, double* ms) {
 int mrc_get_vbr_ms(mrc_handle* h, double* ms) {
     if (!h || !ms) return MRC_ERR_INVALID;
     for (int i = 0; i < 4; ++i) ms[i] = h->vbr.ms[i];
+    return MRC_OK;
+}
+
+int mrc_vbr_record_width(int joint) {
+    DevShape one{};
+    one.nBands = 1;
+    return (int)(vbr_profile_bytes(one, joint ? 1 : 0) / sizeof(double));
+}
+
+int mrc_dev_vbr_alloc(mrc_handle* h, int a, int b, int64_t n_frames, int joint, double ceiling, const double* lines,
+                      const int32_t* overall_scale, const int32_t* ms_switch, const double* source_lines,
+                      const double* source_thresh, int32_t* bit_alloc, int32_t* scale_factor, uint16_t* mantissa16,
+                      double* stat, int32_t* capped, void* stream) {
+    if (!h) return MRC_ERR_INVALID;
+    if (!lines || !overall_scale || (joint && !ms_switch) || !source_lines || !source_thresh)
+        return fail(h, MRC_ERR_INVALID, "mrc_dev_vbr_alloc: null input (lines, overall_scale, ms_switch, source_lines or source_thresh)");
+    if (!bit_alloc || !scale_factor || !mantissa16 || !stat || !capped)
+        return fail(h, MRC_ERR_INVALID, "mrc_dev_vbr_alloc: null output (bit_alloc, scale_factor, mantissa16, stat or capped)");
+    if (std::isnan(ceiling)) return fail(h, MRC_ERR_INVALID, "mrc_dev_vbr_alloc: ceiling is NaN");
+    VbrStage v;
+    MRC_TRY(vbr_stage(h, __func__, a, b, n_frames, joint, stream, &v));
+    if (n_frames == 0) return MRC_OK;
+    MRC_HIP(h, launch_vbr_alloc(v.hs->dev, v.joint, n_frames, 0, ceiling, lines, overall_scale, ms_switch, bit_alloc,
+                                scale_factor, mantissa16, v.chunkMap, source_lines, source_thresh, stat, capped, 0, v.st));
+    return MRC_OK;
+}
+
+int mrc_dev_vbr_profile(mrc_handle* h, int a, int b, int64_t n_frames, int joint, const double* lines,
+                        const int32_t* overall_scale, const int32_t* ms_switch, const double* source_lines,
+                        const double* source_thresh, double* ratios, uint32_t* picks, void* stream) {
+    if (!h) return MRC_ERR_INVALID;
+    if (!lines || !overall_scale || (joint && !ms_switch) || !source_lines || !source_thresh)
+        return fail(h, MRC_ERR_INVALID, "mrc_dev_vbr_profile: null input (lines, overall_scale, ms_switch, source_lines or source_thresh)");
+    if (!ratios || (joint && !picks)) return fail(h, MRC_ERR_INVALID, "mrc_dev_vbr_profile: null output (ratios or picks)");
+    VbrStage v;
+    MRC_TRY(vbr_stage(h, __func__, a, b, n_frames, joint, stream, &v));
+    if (n_frames == 0) return MRC_OK;
+    // states that the walk never reaches stay NaN (every byte 0xff)
+    MRC_HIP(h, hipMemsetAsync(ratios, 0xff, (size_t)n_frames * vbr_profile_bytes(v.hs->dev, v.joint), v.st));
+    MRC_HIP(h, launch_vbr_profile(v.hs->dev, v.joint, n_frames, 0, lines, overall_scale, ms_switch, source_lines, source_thresh,
+                                  ratios, v.joint ? picks : nullptr, v.st));
+    return MRC_OK;
+}
+
+int mrc_dev_vbr_pick(mrc_handle* h, int a, int b, int64_t n_frames, int joint, const double* ceilings, const double* lines,
+                     const int32_t* overall_scale, const int32_t* ms_switch, const double* ratios, const uint32_t* picks,
+                     int32_t* bit_alloc, int32_t* scale_factor, uint16_t* mantissa16, double* stat, int32_t* capped,
+                     void* stream) {
+    if (!h) return MRC_ERR_INVALID;
+    if (!ceilings || !lines || !overall_scale || (joint && !ms_switch) || !ratios || (joint && !picks))
+        return fail(h, MRC_ERR_INVALID, "mrc_dev_vbr_pick: null input (ceilings, lines, overall_scale, ms_switch, ratios or picks)");
+    if (!bit_alloc || !scale_factor || !mantissa16 || !stat || !capped)
+        return fail(h, MRC_ERR_INVALID, "mrc_dev_vbr_pick: null output (bit_alloc, scale_factor, mantissa16, stat or capped)");
+    VbrStage v;
+    MRC_TRY(vbr_stage(h, __func__, a, b, n_frames, joint, stream, &v));
+    if (n_frames == 0) return MRC_OK;
+    MRC_HIP(h, launch_vbr_pick(v.hs->dev, v.joint, n_frames, ceilings, v.chunkStream, lines, overall_scale, ms_switch, ratios,
+                               v.joint ? picks : nullptr, bit_alloc, scale_factor, mantissa16, v.chunkMap, stat, capped, v.st));
     return MRC_OK;
 }
 

@@ -193,6 +193,11 @@ struct VbrBufs {
     DevBuf prof[kChainGroups], profPick[kChainGroups], ceilings, bytes;
     EventSet<3> evSize;              // the probes start | the final pick starts | it ended
     double sizeMs[5] = {0, 0, 0, 0, 0};   // phase A + source analysis | profile | probes | final pick + pack | their sum
+    // mrc_dev_vbr_alloc / _profile / _pick: the identity chunk map and the chunks' streams, their page-locked staging and the
+    // copy between the two (waited for before the staging is refilled)
+    DevBuf stageMap;
+    PinnedBuf stagePin;
+    Event stageCopied;
 };
 
 // Device decode of whole `.pac` files (mrc_api_decode.cpp): reused from call to call

@@ -349,6 +349,7 @@ hipError_t launch_vbr_alloc(const DevShape& S, int joint, int64_t n, int64_t k0,
 // record and phase A's data alone; it writes what launch_vbr_alloc writes (chunkBase 0).  launch_vbr_size_bytes: bytes[s] =
 // hdrLen + sum over stream s's chunks of (4 + chunkBytes), the packer's plan in chunk order.
 size_t vbr_profile_bytes(const DevShape& S, int joint);   // of one block
+size_t vbr_lds_bytes(const DevShape& S, int joint);       // launch_vbr_alloc / _profile refuse more than 60 KB
 hipError_t launch_vbr_profile(const DevShape& S, int joint, int64_t n, int64_t k0, const double* phaseLines, const int* oscale,
                               const int* msSwitch, const double* lines, const double* thresh, double* prof, unsigned* profPick,
                               hipStream_t st);
