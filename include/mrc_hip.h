@@ -1048,6 +1048,46 @@ int mrc_pac_store_decode_window_resampled(mrc_pac_store* s, int rate_divisor, in
                                           int64_t n_items, const int64_t* file /*[n_items]*/, const int64_t* start /*[n_items]*/,
                                           int64_t window, int n_channels_out, int format,
                                           void* out /* DEVICE [n_items][n_channels_out][window] */, void* stream);
+/* mrc_pac_store_decode_window_sum: windows that are weighted sums of crops -- speech over noise at a drawn SNR, an event placed
+ * inside a background, two utterances overlapped -- folded from the float64 overlap-added planes straight into the caller's
+ * tensor; no per-term window is written.
+ * Terms: item i's terms are k in [term_offset[i], term_offset[i + 1]), n_terms = term_offset[n_items]; file, start and gain are
+ * [n_terms].  An item may have no terms: its row is then +0.0 / 0.
+ * One term's signal: v_k[c][t] is the MRC_WINDOW_F64 value the existing call gives for (file[k], start[k]), channel c, sample
+ * t, at this rate_divisor and mix.  up == down (ratio 1; zeros and rolloff are ignored): that call is
+ * mrc_pac_store_decode_window_reduced under MRC_MIX_EACH and mrc_pac_store_decode_window_mix otherwise.  up != down: it is
+ * mrc_pac_store_decode_window_resampled with these up, down, zeros, rolloff; start and window then count OUTPUT samples,
+ * exactly as in that call.  A start may be negative or past the end (+0.0 outside the file), so "this event begins 0.3 s into
+ * that background" is a start and nothing more.
+ * The sum: out[i][c][t] = the left fold from +0.0, over the item's terms IN THE ORDER GIVEN, of gain[k] * v_k[c][t]; every
+ * product is rounded once, then added (__dmul_rn, __dadd_rn: no fused multiply-add).  MRC_WINDOW_F64 is that sum,
+ * MRC_WINDOW_F32 one conversion of it, MRC_WINDOW_PCM16 the 16-bit code of it (pcmfile.py:163-172, saturating at full scale
+ * as that map does).  Every bit is defined: nothing depends on the launch grid, on the order of the ITEMS, on what shares the
+ * call or on the slab size; the order of an item's TERMS is part of the definition (floating-point addition does not
+ * associate).
+ * Single-term identity: a one-term item with gain 1.0 equals the existing call in all three formats -- +0.0 + 1.0 * v is v
+ * for every v but -0.0, and the planes and the resample fold never hold -0.0: they are sums that start from +0.0.
+ * Channel map: MRC_MIX_EACH takes n_channels_out 1 or 2; a mono file's term adds to both channels of a two-channel call, a
+ * stereo file's term in a one-channel call is refused, the refusal naming the term.  MRC_MIX_MID / _LEFT / _RIGHT take
+ * n_channels_out == 1, with the lines of mrc_pac_store_decode_window_mix.
+ * Work follows the windows, per term: a term's blocks are those the existing call parses for that (file, start, window); a
+ * term that meets no block has no plane and adds nothing; a zero gain is not special, the term is parsed like any other.
+ * Damage inside a term's span gives MRC_ERR_INVALID (file, byte offset, the parser's words); damage elsewhere is never read.
+ * MRC_ERR_INVALID naming the argument, before any device work and with `out` untouched: every refusal of the existing calls
+ * (rate_divisor and the block shapes, mix, mrc_resample_taps' arguments when up != down, file indices, window, format, out
+ * NULL with output to write); term_offset NULL, term_offset[0] != 0 or term_offset decreasing; file, start or gain NULL with
+ * terms present; a gain that is not finite (the term is named); up or down < 1.  n_items == 0 or window == 0: MRC_OK, nothing
+ * written.
+ * Slabs are runs of whole items whose TERMS' plane spans -- window, or ceil((window - 1) down / up) + 2 W when resampling, per
+ * term -- sum to at most MRC_OPT_STORE_SLAB_SAMPLES (one item at least; 0: one slab), and of at most (2^31 - 1) /
+ * (n_channels_out * ceil(window / 256)) items; `stream` (NULL: the handle's) is synchronised after each.
+ * mrc_pac_store_stats describes the call as it does the others, the chunks those of all terms; ms[3] is sum_out_kernel's
+ * time, or resample_sum_out_kernel's. */
+int mrc_pac_store_decode_window_sum(mrc_pac_store* s, int rate_divisor, int mix, int up, int down, int zeros, double rolloff,
+                                    int64_t n_items, const int64_t* term_offset /*[n_items+1]*/, const int64_t* file /*[n_terms]*/,
+                                    const int64_t* start /*[n_terms]*/, const double* gain /*[n_terms]*/, int64_t window,
+                                    int n_channels_out, int format, void* out /* DEVICE [n_items][n_channels_out][window] */,
+                                    void* stream);
 
 /* Per-stage device time of the most recent timed call when timing is enabled (hipEvents on the launch stream; the call
  * then synchronises).  Timed: mrc_dev_encode / mrc_dev_encode_ex and mrc_encode_mono / mrc_encode_joint (the _blocks

@@ -34,6 +34,12 @@ largest rate divisor that still holds the band and a polyphase resampler on the 
 (mrc_pac_store_decode_window_resampled, store.resample_plan: 48 kHz -> 16 kHz is half-rate synthesis, then 2 / 3): the WAV's
 header carries HZ, and --start / --samples count samples at HZ.  Composes with --mix, --start and --samples; refused together
 with --rate-divisor.
+A mixture:  python -m mrcaudiocodec_amd.cli -d in.pac out.wav --overlay other.pac --snr-db DB [--overlay-start N]  puts both files
+into one store and writes in.pac + g * other.pac in ONE call of two terms (mrc_pac_store_decode_window_sum), g the factor that
+puts in.pac DB above other.pac over the excerpt (levels.LevelMap.gains_for_snr, from the block energies; printed).  N is the
+overlay's sample under the excerpt's first; a negative N starts the overlay that far into the excerpt.  Codec settings that
+differ between the files are refused, the parameter named.  Composes with --start, --samples, --mix, --rate-divisor and
+--sample-rate.
 Levels:  python -m mrcaudiocodec_amd.cli --levels a.pac [b.pac ...] [--levels-window N]  decodes nothing and writes nothing: per
 file one JSON line with its channels, samples, RMS level per channel (dB re full scale) and its loudest and quietest window of
 N samples (default one second) on the short-block grid with their starts, from the energies of the blocks' MDCT lines
@@ -446,6 +452,27 @@ def check_mix_args(mix, decode):
     return mix
 
 
+def check_overlay_args(overlay, snr_db, overlay_start, decode):
+    """--overlay, --snr-db and --overlay-start as given (None: not given) -> (path, SNR in dB, the overlay's start), or None
+    without --overlay.  --overlay adds a second file under a decode at a signal-to-noise ratio: refused without -d and
+    without --snr-db; --snr-db and --overlay-start are refused without --overlay; the SNR is a finite number of dB."""
+    if overlay is None:
+        for flag, v in (("--snr-db", snr_db), ("--overlay-start", overlay_start)):
+            if v is not None:
+                raise ValueError("%s belongs to --overlay: it needs --overlay" % flag)
+        return None
+    if not decode:
+        raise ValueError("--overlay adds a second .pac file under a decode: it needs -d")
+    if snr_db is None:
+        raise ValueError("--overlay needs --snr-db: the level of src over the overlay in dB")
+    snr = _number("--snr-db", snr_db)
+    if not np.isfinite(snr):
+        raise ValueError("--snr-db: %r is not a finite number of dB" % (snr_db,))
+    if overlay_start is not None and (isinstance(overlay_start, bool) or not isinstance(overlay_start, (int, np.integer))):
+        raise ValueError("--overlay-start: %r is not a whole number of samples" % (overlay_start,))
+    return str(overlay), snr, (0 if overlay_start is None else int(overlay_start))
+
+
 LEVELS_REFUSES = ("src", "dst", "-d", "--no-huffman", "--exact-spread", "--certify", "--bits-per-sample", "--nmr", "--measure",
                   "--target-nmr", "--vbr-nmr", "--vbr-bytes", "--vbr-bits-per-sample", "--vbr-grid", "--start", "--samples",
                   "--sample-rate")
@@ -569,7 +596,25 @@ def band_energies_of_file(pac_path, npy_path, hop, band_edges_hz=None, device_id
     return e
 
 
-def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=1, mix=None, sample_rate=None):
+CODEC_SETTINGS = ("sample_rate", "n_mdct_lines", "n_scale_bits", "n_mant_size_bits")   # what a .pac header says of its codec
+
+
+def _levels_of_mix(store, rate_divisor, mix):
+    """the LevelMap of the channels decode_window gives under mix: every channel, the mid, or the left / right column of the
+    per-channel energies (a mono file its own)"""
+    if mix not in ("left", "right"):
+        return store.levels(rate_divisor, mix)
+    from .levels import LevelMap
+    entry_offset, blocks, energy = store.block_energy(rate_divisor, None)
+    cfg, per_file = store._handle.cfg, []
+    for f in range(len(store)):
+        lo, hi, nch = int(entry_offset[f]), int(entry_offset[f + 1]), int(store.n_channels[f])
+        per_file.append(dict(blocks=blocks[lo:hi:nch], energy=energy[lo:hi].reshape(-1, nch)[:, min(("left", "right").index(mix), nch - 1)],
+                             n_samples=int(store.n_samples[f]) // rate_divisor))
+    return LevelMap(per_file, cfg.n_mdct_lines, rate_divisor, cfg.n_short)
+
+
+def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=1, mix=None, sample_rate=None, overlay=None):
     """excerpt: None (the whole file, mrc_decode_pac_pcm16) or (start, samples): that many samples from sample `start` on
     (samples None: to the end of the file), decoded through a one-file PacStore -- only the blocks the excerpt overlaps are
     parsed and synthesised; what lies outside the file is silence.  rate_divisor 2 or 4: at that fraction of the sample rate,
@@ -577,10 +622,26 @@ def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=
     WAV's header carries.  mix "mid", "left" or "right": a one-channel WAV of that channel (mid: (L + R) / 2, formed on the
     MDCT lines), through the store as well.  sample_rate: None or the rate in Hz to decode at, through the store as well
     (store.resample_plan picks the divisor and the fraction; rate_divisor must be 1): start and samples count samples at
-    that rate, which the WAV's header carries.  -> int16 [nCh][samples] as written."""
+    that rate, which the WAV's header carries.  overlay: None or (path, snr_db, start): a second `.pac` file of the same codec
+    settings added under the excerpt in ONE PacStore.decode_window_sum call of two terms -- the file at 1.0 and the overlay,
+    from its sample `start` on (negative: it begins that far into the excerpt), at the factor that puts the excerpt snr_db
+    above it (levels.LevelMap.gains_for_snr over the excerpt, from the block energies; the factor is printed).
+    -> int16 [nCh][samples] as written."""
     with open(pac_path, "rb") as fp:
         buf = fp.read()
     cfg, _, _, _ = pacfile.read_header(buf)
+    bufs = [buf]
+    if overlay is not None:
+        with open(overlay[0], "rb") as fp:
+            bufs.append(fp.read())
+        try:
+            other, _, _, _ = pacfile.read_header(bufs[1])
+        except MrcError as e:
+            raise ValueError("--overlay: %s: not a .pac file (%s)" % (overlay[0], e))
+        for name in CODEC_SETTINGS:
+            if getattr(other, name) != getattr(cfg, name):
+                raise ValueError("--overlay: %s differs: %s has %d, %s has %d"
+                                 % (name, pac_path, getattr(cfg, name), overlay[0], getattr(other, name)))
     rate_divisor = check_rate_divisor_args(rate_divisor, True)
     if cfg.sample_rate % rate_divisor:
         raise ValueError("--rate-divisor %d does not divide the file's sample rate, %d Hz" % (rate_divisor, cfg.sample_rate))
@@ -590,7 +651,7 @@ def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=
         from .store import resample_plan
         rate_divisor, up, down = resample_plan(cfg.sample_rate, int(sample_rate))
         resample = None if up == down else (up, down)
-    if (rate_divisor != 1 or mix is not None or resample is not None) and excerpt is None:
+    if (rate_divisor != 1 or mix is not None or resample is not None or overlay is not None) and excerpt is None:
         excerpt = (0, None)
     h = Handle(sample_rate=cfg.sample_rate, n_mdct_lines=cfg.n_mdct_lines, n_scale_bits=cfg.n_scale_bits,
                n_mant_size_bits=cfg.n_mant_size_bits, device_id=device_id)
@@ -599,13 +660,24 @@ def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=
             inter = h.decode_pac_pcm16(buf)[0]      # [samples][nCh] in WAV order, parsed and decoded on the device
         else:
             from .store import PacStore
-            with PacStore(h, [buf]) as store:
+            with PacStore(h, bufs) as store:
                 start, samples = excerpt
                 if samples is None:
                     n = store.n_samples_at(rate_divisor) if resample is None else store.n_samples_resampled(*resample, rate_divisor)
                     samples = max(0, int(n[0]) - start)
-                inter = np.ascontiguousarray(store.decode_window([0], [start], samples, rate_divisor=rate_divisor, mix=mix,
-                                                                 resample=resample)[0].cpu().numpy().T)
+                if overlay is None:
+                    got = store.decode_window([0], [start], samples, rate_divisor=rate_divisor, mix=mix, resample=resample)
+                else:
+                    # the levels live at the rate divisor's rate: the excerpt's span there (the whole of it, rounded outwards)
+                    up, down = resample if resample is not None else (1, 1)
+                    at = lambda v: v * down // up
+                    span = max(1, -(-(start + samples) * down // up) - at(start))
+                    gain = float(_levels_of_mix(store, rate_divisor, mix).gains_for_snr(
+                        overlay[1], [0], [at(start)], [1], [at(overlay[2])], span)[0]) if samples else 1.0
+                    print("overlay: %s at a factor of %.9g (%g dB under the excerpt)" % (overlay[0], gain, overlay[1]))
+                    got = store.decode_window_sum([[0, 1]], [[start, overlay[2]]], [[1.0, gain]], samples, rate_divisor=rate_divisor,
+                                                  mix=mix, resample=resample)
+                inter = np.ascontiguousarray(got[0].cpu().numpy().T)
     finally:
         h.close()
     data = inter.astype("<i2", copy=False)
@@ -734,6 +806,14 @@ def main(argv=None):
     ap.add_argument("--mix", default=None, metavar="CH",
                     help="with -d: write a one-channel WAV, CH = mid ((L + R) / 2 of a stereo file, formed on the MDCT lines), "
                          "left or right; composes with --rate-divisor, --start and --samples")
+    ap.add_argument("--overlay", default=None, metavar="PAC",
+                    help="with -d: add a second .pac file of the same codec settings under the decode, src at 1.0 and PAC at the "
+                         "factor that puts src --snr-db above it over the excerpt (from the block energies), in one call on the "
+                         "device; composes with --start, --samples, --mix, --rate-divisor and --sample-rate")
+    ap.add_argument("--snr-db", default=None, metavar="DB", help="with --overlay: the level of src over the overlay in dB")
+    ap.add_argument("--overlay-start", type=int, default=None, metavar="N",
+                    help="with --overlay: the overlay's sample that falls on the excerpt's first (default 0; negative: the "
+                         "overlay begins that many samples into the excerpt)")
     ap.add_argument("--levels", nargs="+", default=None, metavar="PAC",
                     help="no src, no dst: print one JSON line per .pac file with its channels, samples, RMS level per channel "
                          "(dB re full scale) and its loudest and quietest window on the short-block grid, from the block "
@@ -768,6 +848,7 @@ def main(argv=None):
         rate_divisor = check_rate_divisor_args(a.rate_divisor, a.decode or levels is not None)
         mix = check_mix_args(a.mix, a.decode or levels is not None or bands is not None)
         sample_rate = check_sample_rate_args(a.sample_rate, a.decode, a.rate_divisor is not None)
+        overlay = check_overlay_args(a.overlay, a.snr_db, a.overlay_start, a.decode)
         if levels is not None:
             from .store import check_levels_mix
             check_levels_mix(mix, "--mix")
@@ -830,7 +911,7 @@ def main(argv=None):
         return
     if a.decode:
         try:
-            pcm = decode_pac_file(a.src, a.dst, a.device, excerpt, rate_divisor, mix, sample_rate)
+            pcm = decode_pac_file(a.src, a.dst, a.device, excerpt, rate_divisor, mix, sample_rate, overlay)
         except ValueError as e:
             ap.error(str(e))
         print("%s: %d channels x %d samples" % (a.dst, pcm.shape[0], pcm.shape[1]))

@@ -43,6 +43,12 @@
 // where window_out_kernel copies them.  The filter (mrc_resample_taps.hpp: host only) goes up once per handle and
 // (up, down, zeros, rolloff).
 //
+// decode_window_sum, rows that are weighted sums of windows: decode_windows with the TERM as its planning unit.  Each term is
+// planned, staged, parsed and synthesised as an item of the calls above, into planes of its own; a slab is a run of whole
+// rows counted by its terms' spans, and sum_out_kernel / resample_sum_out_kernel fold a row's terms with their gains, in the
+// order given, into the caller's tensor.  The term records (WindowItem, gain, output start) and the rows' term offsets go up
+// with the plan.  No per-term window is written.
+//
 // block_energy, ((a + b) / D) * the sum of squares of a block's first 1 / D decoded lines, per channel or for the mid, for
 // every block of the selected files: the same slab plan (stage_slab, parse_slab) over runs of whole blocks instead of the
 // blocks of windows, then block_energy_kernel per group (mrc_kernels_store.hip) in place of planes, synthesis and output.
@@ -69,6 +75,7 @@ const char* const kWin = "mrc_pac_store_decode_window";
 const char* const kWinReduced = "mrc_pac_store_decode_window_reduced";
 const char* const kWinMix = "mrc_pac_store_decode_window_mix";
 const char* const kWinResampled = "mrc_pac_store_decode_window_resampled";
+const char* const kWinSum = "mrc_pac_store_decode_window_sum";
 constexpr int kNoMix = -1;                           // decode_windows: every channel of a file into a plane of its own
 
 int store_alive(mrc_pac_store* s, const char* fn) {
@@ -294,8 +301,18 @@ int get_resample_table(mrc_handle* h, const ResampleSpec& r, const ResampleTable
 // floor((start + window - 1) down / up) + W: that span is what is planned, staged, parsed and synthesised exactly as a
 // window of the other calls -- into planes of span + 4 L samples, span = ceil((window - 1) down / up) + 2 W the one bound on
 // hi - lo + 1 -- and resample_out_kernel stands where window_out_kernel stands.  A slab counts plane samples (spans).
+// sum (mrc_pac_store_decode_window_sum) null or the rows of that call: what is planned, staged, parsed and synthesised -- the
+// UNIT, (file[k], start[k]) -- is then a TERM of row i, k in [termOffset[i], termOffset[i + 1]), n_items the number of terms;
+// a slab is a run of whole rows, counted by its terms' spans, and sum_out_kernel / resample_sum_out_kernel fold a row's
+// terms with their gains where the other calls copy or fold one unit per row.  Without it a row is its one unit.
+struct SumSpec {
+    int64_t nRows;
+    const int64_t* termOffset;                               // [nRows + 1], checked by the caller
+    const double* gain;                                      // [n_items]
+};
 int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, int64_t n_items, const int64_t* file, const int64_t* start,
-                   int64_t window, int n_channels_out, int format, void* out, void* stream, const ResampleSpec* rs = nullptr) {
+                   int64_t window, int n_channels_out, int format, void* out, void* stream, const ResampleSpec* rs = nullptr,
+                   const SumSpec* sum = nullptr) {
     MRC_TRY(store_alive(s, fn));
     mrc_handle* h = s->h;
     const mrc_config& cfg = h->cfg;
@@ -312,16 +329,17 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
     if (format != MRC_WINDOW_PCM16 && format != MRC_WINDOW_F32 && format != MRC_WINDOW_F64)
         return fail(h, MRC_ERR_INVALID, w + ": unknown format " + std::to_string(format));
     if (n_items > 0 && (!file || !start)) return fail(h, MRC_ERR_INVALID, w + ": file or start is NULL");
-    if (n_items > 0 && window > 0 && !out) return fail(h, MRC_ERR_INVALID, w + ": out is NULL");
+    const int64_t nRows = sum ? sum->nRows : n_items;
+    if (nRows > 0 && window > 0 && !out) return fail(h, MRC_ERR_INVALID, w + ": out is NULL");
     for (int64_t k = 0; k < n_items; ++k) {
         if (file[k] < 0 || file[k] >= nFiles)
             return fail(h, MRC_ERR_INVALID, w + ": file[" + std::to_string(k) + "] = " + std::to_string(file[k]) + " is outside the store's " +
                                                 std::to_string(nFiles) + " files");
         if (mix == kNoMix && s->index.files[(size_t)file[k]].nch > n_channels_out)
-            return fail(h, MRC_ERR_INVALID, w + ": item " + std::to_string(k) + ": file " + std::to_string(file[k]) +
+            return fail(h, MRC_ERR_INVALID, w + (sum ? ": term " : ": item ") + std::to_string(k) + ": file " + std::to_string(file[k]) +
                                                 " is stereo, the call asks for one channel");
     }
-    if (n_items == 0 || window == 0) return MRC_OK;
+    if (nRows == 0 || window == 0) return MRC_OK;
 
     MRC_TRY(ensure_decode_consts(h));
     StoreBufs& b = h->store;
@@ -340,10 +358,11 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
     std::vector<Need> needs;
     std::vector<WindowItem> items;
     PacPlan pl;                                              // (its group fields: the slab's slots)
-    for (int64_t first = 0, last; first < n_items; first = last) {
+    const auto unitsBefore = [sum](int64_t row) { return sum ? sum->termOffset[row] : row; };
+    for (int64_t first = 0, last; first < nRows; first = last) {  // rows [first, last), their units [u0, u0 + nSlab)
         last = first + 1;
-        while (last < n_items && last - first < itemCap && (slab == 0 || (last - first + 1) * span <= slab)) ++last;
-        const int64_t nSlab = last - first;
+        while (last < nRows && last - first < itemCap && (slab == 0 || (unitsBefore(last + 1) - unitsBefore(first)) * span <= slab)) ++last;
+        const int64_t nSlabRows = last - first, u0 = unitsBefore(first), nSlab = unitsBefore(last) - u0;
         unsigned char* outSlab = (unsigned char*)out + (size_t)first * n_channels_out * window * elem;
         s->stats[2] += 1;
 
@@ -352,13 +371,13 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
         items.assign((size_t)nSlab, WindowItem{0, 0, 0, 1, 0});
         int64_t planeDoubles = 0;
         for (int64_t k = 0; k < nSlab; ++k) {
-            const int64_t f = file[first + k];
+            const int64_t f = file[u0 + k];
             const size_t before = needs.size();
-            int64_t at = start[first + k], len = window;     // the samples the planes must hold: [at, at + len)
+            int64_t at = start[u0 + k], len = window;        // the samples the planes must hold: [at, at + len)
             if (rs) {
                 if (at > far || at < -far) continue;
                 at = floor_div(at * down, up) - W + 1;
-                len = floor_div((start[first + k] + window - 1) * down, up) + W - at + 1;
+                len = floor_div((start[u0 + k] + window - 1) * down, up) + W - at + 1;
             }
             needed_blocks(*s, cfg, D, k, f, at, len, &needs);
             if (needs.size() == before) continue;            // all zeros: its plane does not exist
@@ -368,19 +387,25 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
             planeDoubles += nPlanes * planeLen;
         }
         if (needs.empty()) {                                 // nothing to decode: zeros, no launch
-            MRC_HIP(h, hipMemsetAsync(outSlab, 0, (size_t)nSlab * n_channels_out * window * elem, st));
+            MRC_HIP(h, hipMemsetAsync(outSlab, 0, (size_t)nSlabRows * n_channels_out * window * elem, st));
             continue;
         }
-        // ---- staging (one H2D copy): plan | groups | block offsets | items; a slot's offset is its block's place in the item's
-        // plane: the block's position in the file's padded plane, the window's start at 2 L
+        // ---- staging (one H2D copy): plan | groups | block offsets | items (a sum: term records | the rows' term offsets);
+        // a slot's offset is its block's place in the item's plane: the block's position in the file's padded plane, the
+        // window's start at 2 L
         size_t oOffs = 0, oItems = 0, oOutStart = 0;
         SlabStage S;
         MRC_TRY(stage_slab(
             s, fn, mix, needs, &pl, &S,
             [&](StageLayout* lay) {
                 oOffs = lay->add<long long>(pl.totalSlots);
-                oItems = lay->add<WindowItem>(nSlab);
-                if (rs) oOutStart = lay->add<long long>(nSlab);
+                if (sum) {
+                    oItems = lay->add<SumTerm>(nSlab);
+                    oOutStart = lay->add<long long>(nSlabRows + 1);      // (the rows' term offsets, from the slab's first term)
+                } else {
+                    oItems = lay->add<WindowItem>(nSlab);
+                    if (rs) oOutStart = lay->add<long long>(nSlab);
+                }
             },
             [&](const Need& n, int g, int slot, int ch, bool pair) {
                 const WindowItem& it = items[(size_t)n.item];
@@ -393,8 +418,15 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
             }));
         const int64_t* nPairs = S.nPairs;
         const UnpackGroupDev* gd = S.gd;
-        std::memcpy(S.pin + oItems, items.data(), sizeof(WindowItem) * nSlab);
-        if (rs) std::memcpy(S.pin + oOutStart, start + first, sizeof(long long) * nSlab);
+        if (sum) {
+            SumTerm* terms = (SumTerm*)(S.pin + oItems);
+            for (int64_t k = 0; k < nSlab; ++k) terms[k] = SumTerm{items[(size_t)k], sum->gain[u0 + k], rs ? start[u0 + k] : 0};
+            long long* rowTerms = (long long*)(S.pin + oOutStart);
+            for (int64_t r = 0; r <= nSlabRows; ++r) rowTerms[r] = sum->termOffset[first + r] - u0;
+        } else {
+            std::memcpy(S.pin + oItems, items.data(), sizeof(WindowItem) * nSlab);
+            if (rs) std::memcpy(S.pin + oOutStart, start + first, sizeof(long long) * nSlab);
+        }
         const HostShape* reduced[4] = {};
         for (int sh = 0; D > 1 && sh < 4; ++sh)
             if (pl.hs[sh]) MRC_TRY(get_synth_shape(h, pl.hs[sh]->dev.a, pl.hs[sh]->dev.b, D, &reduced[sh]));
@@ -421,7 +453,14 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
             }));
         s->stats[1] += pl.groupsUsed();
         MRC_HIP(h, hipEventRecord(b.ev[4], st));
-        if (rs)
+        if (sum && rs)
+            MRC_HIP(h, launch_resample_sum_out(nSlabRows, (const SumTerm*)(din + oItems), (const long long*)(din + oOutStart), window,
+                                               n_channels_out, format, (int)L, planeLen, rs->up, rs->down, rs->W, table->evenOdd,
+                                               table->skew, (const double*)table->taps.p, x, outSlab, st));
+        else if (sum)
+            MRC_HIP(h, launch_sum_out(nSlabRows, (const SumTerm*)(din + oItems), (const long long*)(din + oOutStart), window,
+                                      n_channels_out, format, (int)L, x, outSlab, st));
+        else if (rs)
             MRC_HIP(h, launch_resample_out(nSlab, (const WindowItem*)(din + oItems), (const long long*)(din + oOutStart), window,
                                            n_channels_out, format, (int)L, planeLen, rs->up, rs->down, rs->W, table->evenOdd,
                                            table->skew, (const double*)table->taps.p, x, outSlab, st));
@@ -817,6 +856,39 @@ int mrc_pac_store_decode_window_resampled(mrc_pac_store* s, int rate_divisor, in
     if (!refusal.empty()) return fail(h, MRC_ERR_INVALID, w + ": " + refusal);
     return decode_windows(s, kWinResampled, rate_divisor, mix == MRC_MIX_EACH ? nullptr : &mix, n_items, file, start, window,
                           n_channels_out, format, out, stream, &r);
+}
+
+int mrc_pac_store_decode_window_sum(mrc_pac_store* s, int rate_divisor, int mix, int up, int down, int zeros, double rolloff,
+                                    int64_t n_items, const int64_t* term_offset, const int64_t* file, const int64_t* start,
+                                    const double* gain, int64_t window, int n_channels_out, int format, void* out, void* stream) {
+    MRC_TRY(store_alive(s, kWinSum));
+    mrc_handle* h = s->h;
+    const std::string w = kWinSum;
+    if (mix != MRC_MIX_EACH && mix != MRC_MIX_MID && mix != MRC_MIX_LEFT && mix != MRC_MIX_RIGHT)
+        return fail(h, MRC_ERR_INVALID, w + ": mix " + std::to_string(mix) +
+                                            " is not MRC_MIX_EACH (3), MRC_MIX_MID (0), MRC_MIX_LEFT (1) or MRC_MIX_RIGHT (2)");
+    if (mix != MRC_MIX_EACH && n_channels_out != 1)
+        return fail(h, MRC_ERR_INVALID, w + ": n_channels_out must be 1 under a mix of one channel");
+    if (up < 1 || down < 1)
+        return fail(h, MRC_ERR_INVALID, w + ": " + (up < 1 ? "up " + std::to_string(up) : "down " + std::to_string(down)) + " is below 1");
+    ResampleSpec r;
+    if (up != down) {                                        // (up == down: ratio 1, zeros and rolloff are not looked at)
+        const std::string refusal = resample_spec(up, down, zeros, rolloff, &r);
+        if (!refusal.empty()) return fail(h, MRC_ERR_INVALID, w + ": " + refusal);
+    }
+    if (n_items < 0) return fail(h, MRC_ERR_INVALID, w + ": n_items < 0");
+    if (!term_offset) return fail(h, MRC_ERR_INVALID, w + ": term_offset is NULL");
+    if (term_offset[0] != 0) return fail(h, MRC_ERR_INVALID, w + ": term_offset[0] = " + std::to_string(term_offset[0]) + " is not 0");
+    for (int64_t i = 0; i < n_items; ++i)
+        if (term_offset[i + 1] < term_offset[i])
+            return fail(h, MRC_ERR_INVALID, w + ": term_offset decreases at [" + std::to_string(i + 1) + "]");
+    const int64_t nTerms = term_offset[n_items];
+    if (nTerms > 0 && (!file || !start || !gain)) return fail(h, MRC_ERR_INVALID, w + ": file, start or gain is NULL");
+    for (int64_t k = 0; k < nTerms; ++k)
+        if (!std::isfinite(gain[k])) return fail(h, MRC_ERR_INVALID, w + ": gain of term " + std::to_string(k) + " is not finite");
+    const SumSpec sum{n_items, term_offset, gain};
+    return decode_windows(s, kWinSum, rate_divisor, mix == MRC_MIX_EACH ? nullptr : &mix, nTerms, file, start, window, n_channels_out,
+                          format, out, stream, up != down ? &r : nullptr, &sum);
 }
 
 int mrc_pac_store_block_energy(mrc_pac_store* s, int rate_divisor, int mix, int64_t n_sel, const int64_t* file,

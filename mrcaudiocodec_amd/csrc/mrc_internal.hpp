@@ -265,6 +265,22 @@ hipError_t launch_window_out(int64_t nItems, const WindowItem* items /* device *
 hipError_t launch_resample_out(int64_t nItems, const WindowItem* items /* device */, const long long* outStart /* device */,
                                int64_t window, int nchOut, int format, int L, int64_t planeLen, int up, int down, int W,
                                int evenOdd, int skew, const double* taps, const double* planes, void* out, hipStream_t st);
+// mrc_pac_store_decode_window_sum: one term of an item, the planning unit of that call -- the WindowItem of the other calls,
+// the factor its signal is multiplied by and, when the call resamples, its first OUTPUT sample (else 0).
+struct SumTerm {
+    WindowItem w;
+    double gain;
+    long long outStart;
+};
+// out [nRows][nchOut][window] in `format` <- the left fold from +0.0, over terms [termOffset[i], termOffset[i + 1]) of item i in
+// that order, of gain * (window_out_kernel's value of the term): every product rounded once, then added.  An item without
+// terms is +0.0.  terms, termOffset [nRows + 1]: device.
+hipError_t launch_sum_out(int64_t nRows, const SumTerm* terms, const long long* termOffset, int64_t window, int nchOut,
+                          int format, int L, const double* planes, void* out, hipStream_t st);
+// ... and the same fold of gain * (resample_out_kernel's value of the term, output t at output sample term.outStart + t)
+hipError_t launch_resample_sum_out(int64_t nRows, const SumTerm* terms, const long long* termOffset, int64_t window, int nchOut,
+                                   int format, int L, int64_t planeLen, int up, int down, int W, int evenOdd, int skew,
+                                   const double* taps, const double* planes, void* out, hipStream_t st);
 // One entry of mrc_pac_store_block_energy: a channel of a block, or its mid.  sel 0 / 1: output channel L / R of a joint
 // slot (a non-joint slot has one channel, itself: 0); kEnergyMid: the mid (L + R) / 2 on the lines -- of a joint slot, or of
 // the PAIR of non-joint slots slot, slot + 1 (a stereo file's last block).

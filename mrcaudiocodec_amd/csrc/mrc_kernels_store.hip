@@ -32,6 +32,21 @@
 //     same 64 consecutive values either way.
 //     Nothing depends on the grid, on the order of the items, on which items share the launch or on the slab.
 //
+//   sum_out_kernel, resample_sum_out_kernel   the two kernels above where a row is a weighted sum of windows
+//     (mrc_pac_store_decode_window_sum).  Item i owns the term records [termOffset[i], termOffset[i + 1]): a WindowItem (the
+//     term's plane, start and file length), its gain and, when resampling, its first output sample.  With v_k[t] what
+//     window_out_kernel / resample_out_kernel would write as float64 for term k alone,
+//       out[t] = the left fold from +0.0 over the item's terms IN THEIR ORDER of gain_k * v_k[t],
+//     every product rounded once, then added (__dmul_rn, __dadd_rn); the caller's format is taken from the sum.  Rows, tiles
+//     and the lane-to-output map are those of the kernel each stands for.  The term records are read at addresses made of
+//     the workgroup's index and the loop counter alone: the same for every lane, so they stay in scalar registers.
+//     sum_out_kernel loads four terms' samples ahead of their four additions (the additions keep their order; otherwise a
+//     row of K terms is K HBM round trips one after the other), a wave reading 64 consecutive doubles of each plane; no LDS.
+//     resample_sum_out_kernel stages one term's run of intermediate samples at a time (the file mask applied there), folds it
+//     with resample_fold_up -- phase and first tap differ per term -- and adds gain * v between two barriers, the second
+//     because the next term's run overwrites this one's; a term without a plane skips both, the whole workgroup together.
+//     No atomics; nothing depends on the grid, on the order of the items, on what shares the launch or on the slab.
+//
 //   block_energy_kernel   the energy a block adds to the decoded signal, from its MDCT lines alone
 //     (mrc_pac_store_block_energy).  The windowed MDCT with the codec's transition windows is an orthogonal lapped
 //     transform; with the reference's scaling (mdct.py: forward 2 / N, inverse 2) a block of shape (a, b) holds
@@ -196,6 +211,86 @@ __global__ __launch_bounds__(kResampleThreads) void resample_out_kernel(const Wi
     store_window_value(out, row * window + t, format, v);
 }
 
+// window_out_kernel's value of one term at sample t of channel c: the plane's, +0.0 outside the file or without a plane
+__device__ inline double sum_term_sample(const SumTerm& tm, int c, int64_t t, int64_t planeLen, int L,
+                                         const double* __restrict__ planes) {
+    const int64_t pos = tm.w.start + t;
+    double y = 0.0;
+    if (pos >= 0 && pos < tm.w.nSamples) y = planes[tm.w.plane + (int64_t)(tm.w.nch == 2 ? c : 0) * planeLen + 2 * (int64_t)L + t];
+    return y;
+}
+
+constexpr int kSumAhead = 4;                                         // terms whose samples are loaded ahead of their additions
+
+__global__ __launch_bounds__(kWindowThreads) void sum_out_kernel(const SumTerm* __restrict__ terms,
+                                                                 const long long* __restrict__ termOffset, int64_t window,
+                                                                 int64_t tiles, int nchOut, int format, int L,
+                                                                 const double* __restrict__ planes, void* __restrict__ out) {
+    const int64_t row = (int64_t)blockIdx.x / tiles;                 // item * nchOut + channel
+    const int64_t t = ((int64_t)blockIdx.x - row * tiles) * kWindowThreads + threadIdx.x;
+    const int64_t k = row / nchOut;
+    const int c = (int)(row - k * nchOut);
+    // the item's terms: the same for the whole workgroup (indexed from blockIdx and the loop counter alone)
+    const int64_t jEnd = termOffset[k + 1], planeLen = window + 4 * (int64_t)L;
+    int64_t j = termOffset[k];
+    if (t >= window) return;
+    double acc = 0.0;
+    for (; j + kSumAhead <= jEnd; j += kSumAhead) {
+        double g[kSumAhead], y[kSumAhead];
+#pragma unroll
+        for (int u = 0; u < kSumAhead; ++u) {
+            g[u] = terms[j + u].gain;
+            y[u] = sum_term_sample(terms[j + u], c, t, planeLen, L, planes);
+        }
+#pragma unroll
+        for (int u = 0; u < kSumAhead; ++u) acc = __dadd_rn(acc, __dmul_rn(g[u], y[u]));
+    }
+    for (; j < jEnd; ++j) acc = __dadd_rn(acc, __dmul_rn(terms[j].gain, sum_term_sample(terms[j], c, t, planeLen, L, planes)));
+    store_window_value(out, row * window + t, format, acc);
+}
+
+__global__ __launch_bounds__(kResampleThreads) void resample_sum_out_kernel(const SumTerm* __restrict__ terms,
+                                                                            const long long* __restrict__ termOffset,
+                                                                            int64_t window, int64_t tiles, int nchOut, int format,
+                                                                            int L, int64_t planeLen, int up, int down, int W,
+                                                                            int evenOdd, int skew, const double* __restrict__ taps,
+                                                                            const double* __restrict__ planes,
+                                                                            void* __restrict__ out) {
+    __shared__ double run[kResampleLds];
+    const int64_t row = (int64_t)blockIdx.x / tiles;                 // item * nchOut + channel
+    const int64_t t0 = ((int64_t)blockIdx.x - row * tiles) * kResampleThreads;
+    const int64_t k = row / nchOut;
+    const int c = (int)(row - k * nchOut);
+    const int lane = threadIdx.x % kResampleWave, wave = threadIdx.x / kResampleWave;      // (resample_out_kernel's map)
+    const int64_t t = t0 + wave * kResampleWave + (evenOdd ? 2 * (lane & 31) + (lane >> 5) : lane);
+    const int64_t jEnd = termOffset[k + 1];
+    double acc = 0.0;
+    for (int64_t j = termOffset[k]; j < jEnd; ++j) {                 // (every branch on the term: the whole workgroup)
+        const SumTerm tm = terms[j];
+        if (tm.w.nSamples == 0) continue;                            // no plane: every y is +0.0, the term adds nothing
+        // the term's run of intermediate samples under the tile's outputs: [qFirst, qFirst + len)
+        const int64_t n0 = tm.outStart + t0, nLast = n0 + min((int64_t)kResampleThreads, window - t0) - 1;
+        const int64_t qFirst = floor_div(n0 * down, up) - W + 1;
+        const int len = (int)(floor_div(nLast * down, up) + W - qFirst + 1);   // <= kResampleRun (the launcher's check)
+        const double* plane = planes + tm.w.plane + (int64_t)(tm.w.nch == 2 ? c : 0) * planeLen;
+        for (int i = threadIdx.x; i < len; i += kResampleThreads) {
+            const int64_t m = qFirst + i, at = 2 * (int64_t)L + (m - tm.w.start);
+            double v = 0.0;
+            if (m >= 0 && m < tm.w.nSamples && at >= 0 && at < planeLen) v = plane[at];
+            run[i + skew * (i >> 5)] = v;
+        }
+        __syncthreads();
+        if (t < window) {
+            const int64_t nd = (tm.outStart + t) * down, q = floor_div(nd, up);
+            const int p = (int)(nd - q * up), first = (int)(q - W + 1 - qFirst);
+            const double v = skew ? resample_fold_up<true>(taps, up, p, run, first, 2 * W) : resample_fold_up<false>(taps, up, p, run, first, 2 * W);
+            acc = __dadd_rn(acc, __dmul_rn(tm.gain, v));
+        }
+        __syncthreads();                                             // (the next term's run goes over this one)
+    }
+    if (t < window) store_window_value(out, row * window + t, format, acc);
+}
+
 constexpr int kEnergyThreads = 256, kEnergyWave = 64;
 
 // The parsed arrays of one EnergyEntry and line k as the entry selects it: a channel's decode_line, the mid's
@@ -353,6 +448,31 @@ hipError_t launch_resample_out(int64_t nItems, const WindowItem* items, const lo
         return hipErrorInvalidValue;                                 // (a run that would not fit the workgroup's LDS)
     hipLaunchKernelGGL(resample_out_kernel, dim3((unsigned)blocks), dim3(kResampleThreads), 0, st, items, outStart, window, tiles,
                        nchOut, format, L, planeLen, up, down, W, evenOdd, skew, taps, planes, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_sum_out(int64_t nRows, const SumTerm* terms, const long long* termOffset, int64_t window, int nchOut,
+                          int format, int L, const double* planes, void* out, hipStream_t st) {
+    if (nRows <= 0 || window <= 0) return hipSuccess;
+    const int64_t tiles = (window + kWindowThreads - 1) / kWindowThreads;
+    const int64_t blocks = tiles * nRows * nchOut;
+    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;          // (the caller cuts such a call into slabs)
+    hipLaunchKernelGGL(sum_out_kernel, dim3((unsigned)blocks), dim3(kWindowThreads), 0, st, terms, termOffset, window, tiles,
+                       nchOut, format, L, planes, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_resample_sum_out(int64_t nRows, const SumTerm* terms, const long long* termOffset, int64_t window, int nchOut,
+                                   int format, int L, int64_t planeLen, int up, int down, int W, int evenOdd, int skew,
+                                   const double* taps, const double* planes, void* out, hipStream_t st) {
+    if (nRows <= 0 || window <= 0) return hipSuccess;
+    const int64_t tiles = (window + kResampleThreads - 1) / kResampleThreads;
+    const int64_t blocks = tiles * nRows * nchOut;
+    if (blocks > 0x7fffffffLL || up < 1 || down < 1 || W < 1 ||
+        ((int64_t)(kResampleThreads - 1) * down + up - 1) / up + 2 * (int64_t)W + 1 > kResampleRun)
+        return hipErrorInvalidValue;                                 // (a run that would not fit the workgroup's LDS)
+    hipLaunchKernelGGL(resample_sum_out_kernel, dim3((unsigned)blocks), dim3(kResampleThreads), 0, st, terms, termOffset, window,
+                       tiles, nchOut, format, L, planeLen, up, down, W, evenOdd, skew, taps, planes, out);
     return hipGetLastError();
 }
 

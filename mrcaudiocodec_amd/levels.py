@@ -1,7 +1,8 @@
 """
 LevelMap: how loud every stretch of a set of `.pac` files is, from one number per block and channel -- the block energies of
 mrc_pac_store_block_energy (PacStore.levels) -- and what a crop loader asks of it: the energy and RMS level of any window,
-the starts whose window is loud enough, a reproducible draw among them, the gain that brings a crop to a target level.
+the starts whose window is loud enough, a reproducible draw among them, the gain that brings a crop to a target level, the
+gain that puts one crop at a given SNR under another.
 Pure NumPy: no GPU, no library call.
 
 The windowed MDCT of the codec is an orthogonal lapped transform, so block i of shape (a_i, b_i) at position p_i of the padded
@@ -171,4 +172,17 @@ class LevelMap:
         gain = np.ones(energy.size)
         loud = energy > 0.0
         gain[loud] = 10.0 ** ((float(target_rms_db) - _db(energy[loud] / window)) / 20.0)
+        return gain
+
+    def gains_for_snr(self, snr_db, files_a, starts_a, files_b, starts_b, window):
+        """-> [n] linear factors g for the b windows such that a + g * b has the a window snr_db above the b window: with E the
+        window energy summed over the channels, g = sqrt(E_a / (E_b * 10 ** (snr_db / 10))).  1.0 where either window is
+        silent: no SNR is defined there.  The factors PacStore.decode_window_sum takes for the b terms, the a terms at 1.0."""
+        e_a = self.window_energy(files_a, starts_a, window).sum(axis=1)
+        e_b = self.window_energy(files_b, starts_b, window).sum(axis=1)
+        if e_a.shape != e_b.shape:
+            raise ValueError("gains_for_snr: one b window per a window (%d and %d)" % (e_a.size, e_b.size))
+        gain = np.ones(e_a.size)
+        both = (e_a > 0.0) & (e_b > 0.0)
+        gain[both] = np.sqrt(e_a[both] / (e_b[both] * 10.0 ** (float(snr_db) / 10.0)))
         return gain

@@ -33,6 +33,14 @@ and levels.LevelMap turns those numbers into window levels, admissible crop star
         x = store.decode_window(files, starts, 48000, dtype=torch.float32)
         x *= torch.from_numpy(m.gains_to(-20.0, files, starts, 48000)).to(x)[:, None, None]
 
+decode_window_sum (mrc_pac_store_decode_window_sum) gives windows that are weighted sums of crops -- speech over noise at a drawn
+SNR, an event placed inside a background (a term's start may be negative: it reads zeros there), mixup -- folded from the
+float64 planes in one call, every bit defined, no per-term window written:
+
+        g = m.gains_for_snr(10.0, speech, s_starts, noise, n_starts, 48000)   # the noise 10 dB below the speech
+        x = store.decode_window_sum(np.stack([speech, noise], 1), np.stack([s_starts, n_starts], 1),
+                                    np.stack([np.ones_like(g), g], 1), 48000, dtype=torch.float32)
+
 band_energy_window (mrc_pac_store_band_energy_window) is the time-frequency feature that usually follows a crop, taken from
 the same sums split by frequency band and laid on a frame grid -- the coded file already is a time-frequency representation:
 
@@ -266,6 +274,31 @@ class PacStore:
                 raise ValueError("n_samples_resampled: %s must be a positive int, got %r" % (name, v))
         return -((-n * int(up)) // int(down))
 
+    def _window_out(self, what, n, files, window, channels, dtype, out, stream):
+        """the output side of decode_window and decode_window_sum -> (format, channels, out, stream): dtype (None: int16, or
+        out's), channels (None: the largest channel count among the files named), the tensor [n][channels][window] (given: it
+        must be that, else ValueError) and the stream (None: torch's current one)"""
+        import torch
+        if dtype is None:
+            dtype = torch.int16 if out is None else out.dtype
+        fmt = _formats().get(dtype)
+        if fmt is None:
+            raise ValueError("%s: dtype must be torch.int16, torch.float32 or torch.float64, got %s" % (what, dtype))
+        if channels is None:
+            inside = files[(files >= 0) & (files < len(self))]
+            channels = int(self.n_channels[inside].max()) if inside.size else 1
+        channels = int(channels)
+        dev = torch.device("cuda", self._handle.cfg.device_id)
+        shape = (n, channels, max(window, 0))
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=dev)
+        elif not isinstance(out, torch.Tensor) or out.dtype != dtype or tuple(out.shape) != shape or out.device != dev \
+                or not out.is_contiguous():
+            raise ValueError("%s: out must be a contiguous %s tensor of shape %s on %s" % (what, dtype, shape, dev))
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        return fmt, channels, out, stream
+
     def decode_window(self, files, starts, window, channels=None, dtype=None, out=None, stream=None, rate_divisor=1,
                       mix=None, resample=None):
         """Item i = samples [starts[i], starts[i] + window) of file files[i], zeros where that leaves the file (starts may be
@@ -292,7 +325,6 @@ class PacStore:
         torch.float64 is the fold defined in the header, bit for bit, the other dtypes its conversions.  A ratio of 1 after
         reduction is the call without resample.  A ratio outside [1 / 8, 8], terms above 1024 after reduction, zeros outside
         1..64 and rolloff outside [0.5, 1] are ValueErrors, before any library call."""
-        import torch
         rate_divisor = check_rate_divisor(rate_divisor)
         mix = check_mix(mix, channels)
         resample = check_resample(resample)
@@ -303,24 +335,7 @@ class PacStore:
         if files.shape != starts.shape:
             raise ValueError("decode_window: one start per file index (%d files, %d starts)" % (files.size, starts.size))
         n, window = files.size, int(window)
-        if dtype is None:
-            dtype = torch.int16 if out is None else out.dtype
-        fmt = _formats().get(dtype)
-        if fmt is None:
-            raise ValueError("decode_window: dtype must be torch.int16, torch.float32 or torch.float64, got %s" % (dtype,))
-        if channels is None:
-            inside = files[(files >= 0) & (files < len(self))]
-            channels = int(self.n_channels[inside].max()) if inside.size else 1
-        channels = int(channels)
-        dev = torch.device("cuda", self._handle.cfg.device_id)
-        shape = (n, channels, max(window, 0))
-        if out is None:
-            out = torch.empty(shape, dtype=dtype, device=dev)
-        elif not isinstance(out, torch.Tensor) or out.dtype != dtype or tuple(out.shape) != shape or out.device != dev \
-                or not out.is_contiguous():
-            raise ValueError("decode_window: out must be a contiguous %s tensor of shape %s on %s" % (dtype, shape, dev))
-        if stream is None:
-            stream = torch.cuda.current_stream(dev).cuda_stream
+        fmt, channels, out, stream = self._window_out("decode_window", n, files, window, channels, dtype, out, stream)
         tail = (n, files.ctypes.data, starts.ctypes.data, window, channels, fmt, out.data_ptr() if out.numel() else None,
                 stream or None)
         if resample is not None:
@@ -332,6 +347,56 @@ class PacStore:
             self._handle._check(lib.mrc_pac_store_decode_window(self._s, *tail))
         else:
             self._handle._check(lib.mrc_pac_store_decode_window_reduced(self._s, rate_divisor, *tail))
+        return out
+
+    def decode_window_sum(self, files, starts, gains, window, item_offsets=None, channels=None, dtype=None, out=None, stream=None,
+                          rate_divisor=1, mix=None, resample=None):
+        """mrc_pac_store_decode_window_sum -> a torch tensor [n][channels][window] on the handle's device: item i is the sum
+        over its terms k, IN THE ORDER GIVEN, of gains[k] * (the float64 window decode_window gives for files[k], starts[k]
+        at this rate_divisor, mix and resample), folded from +0.0 with every product rounded once, then added -- speech over
+        noise, an event inside a background, mixup -- in one call that writes no per-term window.  torch.float64 is that sum,
+        bit for bit; torch.float32 and torch.int16 (the default, saturating at full scale) are conversions of it.
+        files, starts, gains: 2-D [n][K] (every item has K terms), or 1-D [terms] with item_offsets [n + 1] (item i's terms are
+        [item_offsets[i], item_offsets[i + 1]); an item without terms is zeros).  A start may be negative or past the end:
+        the term reads zeros there, which is how a term is placed inside the window.  levels.LevelMap.gains_for_snr and
+        .gains_to give factors without decoding anything.  A one-term item with gain 1.0 is decode_window's window.
+        window, channels, dtype, out, stream, rate_divisor, mix, resample: as decode_window's (with resample, starts and window
+        count output samples).  Shapes that do not agree, offsets that do not start at 0 or that decrease and gains that are
+        not finite are ValueErrors, like decode_window's argument errors, before any library call."""
+        what = "decode_window_sum"
+        rate_divisor = check_rate_divisor(rate_divisor, what)
+        mix = check_mix(mix, channels, what)
+        resample = check_resample(resample, what)
+        if mix is not None:
+            channels = 1
+        files, starts = np.asarray(files, dtype=np.int64), np.asarray(starts, dtype=np.int64)
+        gains = np.asarray(gains, dtype=np.float64)
+        if not (files.shape == starts.shape == gains.shape):
+            raise ValueError("%s: files, starts and gains must have one shape, got %s, %s and %s"
+                             % (what, files.shape, starts.shape, gains.shape))
+        if item_offsets is None:
+            if files.ndim != 2:
+                raise ValueError("%s: files, starts and gains must be [n][K], or 1-D with item_offsets; got shape %s" % (what, files.shape))
+            offsets = np.arange(files.shape[0] + 1, dtype=np.int64) * files.shape[1]
+        else:
+            if files.ndim != 1:
+                raise ValueError("%s: with item_offsets, files, starts and gains must be 1-D; got shape %s" % (what, files.shape))
+            offsets = np.ascontiguousarray(np.asarray(item_offsets, dtype=np.int64))
+            if offsets.ndim != 1 or offsets.size < 1 or offsets[0] != 0 or np.any(np.diff(offsets) < 0):
+                raise ValueError("%s: item_offsets must be [n + 1], start at 0 and not decrease, got %r" % (what, item_offsets))
+            if offsets[-1] != files.size:
+                raise ValueError("%s: item_offsets end at %d, there are %d terms" % (what, int(offsets[-1]), files.size))
+        files, starts, gains = (np.ascontiguousarray(a.reshape(-1)) for a in (files, starts, gains))
+        bad = np.flatnonzero(~np.isfinite(gains))
+        if bad.size:
+            raise ValueError("%s: gains must be finite, got %r at term %d" % (what, float(gains[bad[0]]), int(bad[0])))
+        n, window = offsets.size - 1, int(window)
+        fmt, channels, out, stream = self._window_out(what, n, files, window, channels, dtype, out, stream)
+        up, down, zeros, rolloff = resample if resample is not None else (1, 1, RESAMPLE_ZEROS, RESAMPLE_ROLLOFF)
+        pad = lambda a: a.ctypes.data if a.size else None
+        self._handle._check(lib.mrc_pac_store_decode_window_sum(
+            self._s, rate_divisor, _lib.MRC_MIX_EACH if mix is None else mix, up, down, zeros, rolloff, n, offsets.ctypes.data,
+            pad(files), pad(starts), pad(gains), window, channels, fmt, out.data_ptr() if out.numel() else None, stream or None))
         return out
 
     def band_energy_window(self, files, starts, n_frames, hop, band_edges_hz, channels=None, dtype=None, out=None, stream=None,
@@ -444,7 +509,8 @@ class PacStore:
     def stats(self):
         """of the last decode_window: chunks_parsed, decode_launches, slabs, plan_bytes_uploaded, and ms: the device time of
         the plan upload, the unpack kernel, the synthesis and window_out_kernel (with resample=: resample_out_kernel, and the
-        counts are those of the intermediate spans), summed over the slabs.  After levels() or
+        counts are those of the intermediate spans), summed over the slabs.  After decode_window_sum(): the same, the counts
+        those of all terms and ms["window_out"] the time of sum_out_kernel (resample_sum_out_kernel).  After levels() or
         block_energy(): decode_launches counts block_energy_kernel launches, ms["synthesis"] is that kernel's time and
         ms["window_out"] is 0.  After band_energy_window(): decode_launches counts band_energy_kernel launches,
         ms["synthesis"] is the band sums' time (that kernel) and ms["window_out"] the frame assembly's (band_frames_kernel)."""
