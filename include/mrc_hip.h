@@ -239,6 +239,62 @@ int mrc_dev_smr(mrc_handle* h, int a, int b, int64_t n_frames, const double* ch_
 int mrc_dev_masking(mrc_handle* h, int a, int b, int64_t n_frames, const void* ch_left, const void* ch_right,
                     int sample_format, int64_t frame_stride, const int64_t* offsets, double* lines, int32_t* overall_scale,
                     int32_t* ms_switch, double* smr, double* band_peak, void* stream);
+/* One __device__ helper of the kernels (cross-lane primitives, 2^x, 1/x, atan, SPL conversion, quantiser templates), called
+ * unchanged by a small kernel of its own on the caller's inputs: how the tests hold each helper to its documented bound
+ * (tests/test_gpu_helper_probes.py).  All arrays are DEVICE arrays of 8-byte words, word k of element j at [k * n + j]: doubles
+ * as their bits, signed integers as int64, unsigned 32-bit values zero-extended.  Words per element of in0, in1, in2 -> out:
+ *   MOVES_I32 / _U32 / _F64  a | b -> dpp_move 0xB1, 0x4E, 0x141, 0x128 of a; x, y of rows_swap<16>(a, b); x, y of rows_swap<32>
+ *   SUM_F64       1 -> wave_sum, row_reduce(+)          MAX_F64  1 -> wave_max          ROW_MAX  1 -> row_max
+ *   REDUCE_I32    1 -> wave_sum_i, wave_max_i, row_reduce(+), row_reduce(max)
+ *   FOLD4_F64     4 -> wave_fold4(fmax)                 FOLD4_U32  4 -> wave_fold4(+)
+ *   FOLD2         2 (int) | 2 (double) -> wave_fold2(+) of the ints, of the doubles
+ *   SUM_BLOCK8    8 -> wave_sum_block<8>                SUM_ALL9 / 16 / 17  N -> wave_sum_all<N>
+ *   SCAN_I32 / SCAN_F64  1 -> wave_incl_scan            ORDER_KEY  1 -> order_key, order_value of that key
+ *   XCD           b | g -> xcd_contiguous(b, g)         RCP  1 -> the bare hardware reciprocal, recip_nr
+ *   LINE_RATIO    a2 | t -> line_ratio                  EXP2_POLY  1 -> exp2_poly
+ *   EXP2_TAB      sT | u -> exp2_tab64<64>, <256>, exp2_tab_above<64>, <256>, tables staged in LDS as the masking kernels do
+ *   TABLES        none -> element j: entry j mod 64 / 256 of the two staged 2^x tables, kAtanQ[j mod 22], word j mod 128 of the
+ *                 staged log10 table
+ *   EXP2_DD       hi | lo -> exp2_dd                    DD_ADD  hi, lo | xh, xl -> hi, lo behind dd_add
+ *   ATAN_POS      1 -> atan_pos
+ *   SPL           x | a2 -> spl_db_tab(x), spl_db(x), log10_tab32(x), excess_plain(x, a2, scale 3) and the threshold it hands out
+ *   MAG_CODE      mag | nBits (1..31) -> mag_code<unsigned>, mag_code<long long>
+ *   SCALE_MANT    x | scale + (nScaleBits << 8) + (nMantBits << 16)  (1..4, 2..16) -> scale_factor_dev<unsigned>, <long long>,
+ *                 mantissa_dev<unsigned>, <long long>
+ * threads: the workgroup size, 64, 128 or 256; whole workgroups cover n, a thread past the end computes on element n - 1 and
+ * stores nothing.  out_words: the words `out` holds (at least n times the probe's output words).  MRC_ERR_INVALID: an unknown
+ * probe, n outside 1 .. 65536, another workgroup size, out too small, a NULL array the probe needs. */
+#define MRC_PROBE_MOVES_I32 1
+#define MRC_PROBE_MOVES_U32 2
+#define MRC_PROBE_MOVES_F64 3
+#define MRC_PROBE_SUM_F64 4
+#define MRC_PROBE_MAX_F64 5
+#define MRC_PROBE_ROW_MAX 6
+#define MRC_PROBE_REDUCE_I32 7
+#define MRC_PROBE_FOLD4_F64 8
+#define MRC_PROBE_FOLD4_U32 9
+#define MRC_PROBE_FOLD2 10
+#define MRC_PROBE_SUM_BLOCK8 11
+#define MRC_PROBE_SUM_ALL9 12
+#define MRC_PROBE_SUM_ALL16 13
+#define MRC_PROBE_SUM_ALL17 14
+#define MRC_PROBE_SCAN_I32 15
+#define MRC_PROBE_SCAN_F64 16
+#define MRC_PROBE_ORDER_KEY 17
+#define MRC_PROBE_XCD 18
+#define MRC_PROBE_RCP 19
+#define MRC_PROBE_LINE_RATIO 20
+#define MRC_PROBE_EXP2_POLY 21
+#define MRC_PROBE_EXP2_TAB 22
+#define MRC_PROBE_TABLES 23
+#define MRC_PROBE_EXP2_DD 24
+#define MRC_PROBE_DD_ADD 25
+#define MRC_PROBE_ATAN_POS 26
+#define MRC_PROBE_SPL 27
+#define MRC_PROBE_MAG_CODE 28
+#define MRC_PROBE_SCALE_MANT 29
+int mrc_dev_helper_probe(mrc_handle* h, int probe, const void* in0, const void* in1, const void* in2, void* out,
+                         int64_t out_words, int64_t n, int threads, void* stream);
 int mrc_dev_alloc_quant(mrc_handle* h, int a, int b, int64_t n_frames, int joint,
                         const double* lines, const int32_t* overall_scale, const double* smr,
                         const int32_t* reservoir_in, int32_t* ms_switch, int32_t* bit_alloc,

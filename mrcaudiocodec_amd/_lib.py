@@ -22,6 +22,18 @@ MRC_WINDOW_PCM16, MRC_WINDOW_F32, MRC_WINDOW_F64 = 0, 1, 2      # mrc_pac_store_
 MRC_MIX_MID, MRC_MIX_LEFT, MRC_MIX_RIGHT = 0, 1, 2               # mrc_pac_store_decode_window_mix's channels
 MRC_MIX_EACH = 3                                                 # mrc_pac_store_block_energy: every channel of the file
 MRC_OPT_STORE_SLAB_SAMPLES = 7
+# mrc_dev_helper_probe: name -> (MRC_PROBE_ id, words per element of in0 / in1 / in2, words per element of out)
+PROBES = {
+    "MOVES_I32": (1, (1, 1, 0), 8), "MOVES_U32": (2, (1, 1, 0), 8), "MOVES_F64": (3, (1, 1, 0), 8),
+    "SUM_F64": (4, (1, 0, 0), 2), "MAX_F64": (5, (1, 0, 0), 1), "ROW_MAX": (6, (1, 0, 0), 1),
+    "REDUCE_I32": (7, (1, 0, 0), 4), "FOLD4_F64": (8, (4, 0, 0), 1), "FOLD4_U32": (9, (4, 0, 0), 1),
+    "FOLD2": (10, (2, 2, 0), 2), "SUM_BLOCK8": (11, (8, 0, 0), 8), "SUM_ALL9": (12, (9, 0, 0), 9),
+    "SUM_ALL16": (13, (16, 0, 0), 16), "SUM_ALL17": (14, (17, 0, 0), 17), "SCAN_I32": (15, (1, 0, 0), 1),
+    "SCAN_F64": (16, (1, 0, 0), 1), "ORDER_KEY": (17, (1, 0, 0), 2), "XCD": (18, (1, 1, 0), 1), "RCP": (19, (1, 0, 0), 2),
+    "LINE_RATIO": (20, (1, 1, 0), 1), "EXP2_POLY": (21, (1, 0, 0), 1), "EXP2_TAB": (22, (1, 1, 0), 4),
+    "TABLES": (23, (0, 0, 0), 4), "EXP2_DD": (24, (1, 1, 0), 1), "DD_ADD": (25, (2, 2, 0), 2), "ATAN_POS": (26, (1, 0, 0), 1),
+    "SPL": (27, (1, 1, 0), 5), "MAG_CODE": (28, (1, 1, 0), 2), "SCALE_MANT": (29, (1, 1, 0), 4),
+}
 # array arguments travel as plain addresses (c_void_p prototypes): numpy's typed `data_as` costs ~2.3 us per array, which
 # at thirteen arrays per call was a third of a one-block call through the drop-in seam; the names say what the C side expects
 _i32p = _i64p = _f64p = _u8p = C.c_void_p
@@ -95,6 +107,7 @@ def _load():
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
         "mrc_dev_masking": (C.c_int, [H, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int64] +
                             [C.c_void_p] * 7),
+        "mrc_dev_helper_probe": (C.c_int, [H, C.c_int] + [C.c_void_p] * 4 + [C.c_int64, C.c_int64, C.c_int, C.c_void_p]),
         "mrc_dev_alloc_quant": (C.c_int, [H, C.c_int, C.c_int, C.c_int64, C.c_int] + [C.c_void_p] * 10),
         "mrc_dev_alloc_quant_chained": (C.c_int, [H, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int] +
                                         [C.c_void_p] * 12),
@@ -1162,6 +1175,12 @@ class Handle:
                     ms_switch, smr, band_peak, stream=None):
         self._check(lib.mrc_dev_masking(self._h, a, b, n_frames, ch_left, ch_right, int(sample_format), frame_stride,
                                         offsets, lines, overall_scale, ms_switch, smr, band_peak, stream))
+
+    def dev_helper_probe(self, probe, in0, in1, in2, out, out_words, n, threads=64, stream=None):
+        """one __device__ helper on device arrays of 8-byte words (include/mrc_hip.h: mrc_dev_helper_probe; PROBES names the
+        probes and their words per element)"""
+        self._check(lib.mrc_dev_helper_probe(self._h, int(probe), in0, in1, in2, out, int(out_words), int(n), int(threads),
+                                             stream))
 
     def dev_alloc_quant(self, a, b, n_frames, joint, lines, overall_scale, smr, reservoir_in, ms_switch, bit_alloc,
                         scale_factor, mantissa, reservoir_out, stream=None):

@@ -293,6 +293,22 @@ int mrc_dev_masking(mrc_handle* h, int a, int b, int64_t n_frames, const void* c
                                overall_scale, ms_switch, smr, band_peak, pick_stream(h, stream), false);
 }
 
+int mrc_dev_helper_probe(mrc_handle* h, int probe, const void* in0, const void* in1, const void* in2, void* out,
+                         int64_t out_words, int64_t n, int threads, void* stream) {
+    if (!h) return fail(h, MRC_ERR_INVALID, "mrc_dev_helper_probe: null handle");
+    int w0, w1, w2, wout;
+    if (!probe_words(probe, &w0, &w1, &w2, &wout)) return fail(h, MRC_ERR_INVALID, "mrc_dev_helper_probe: unknown probe");
+    if (n < 1 || n > 65536) return fail(h, MRC_ERR_INVALID, "mrc_dev_helper_probe: n outside 1 .. 65536");
+    if (threads != 64 && threads != 128 && threads != 256)
+        return fail(h, MRC_ERR_INVALID, "mrc_dev_helper_probe: workgroup size not 64, 128 or 256");
+    if (!out || out_words < n * wout) return fail(h, MRC_ERR_INVALID, "mrc_dev_helper_probe: out is NULL or too small");
+    if ((w0 && !in0) || (w1 && !in1) || (w2 && !in2))
+        return fail(h, MRC_ERR_INVALID, "mrc_dev_helper_probe: an input array the probe reads is NULL");
+    MRC_HIP(h, hipSetDevice(h->device));
+    MRC_HIP(h, launch_probe(probe, in0, in1, in2, out, (int)n, threads, pick_stream(h, stream)));
+    return MRC_OK;
+}
+
 int mrc_dev_alloc_quant(mrc_handle* h, int a, int b, int64_t n_frames, int joint, const double* lines,
                         const int32_t* overall_scale, const double* smr, const int32_t* reservoir_in,
                         int32_t* ms_switch, int32_t* bit_alloc, int32_t* scale_factor, int32_t* mantissa,

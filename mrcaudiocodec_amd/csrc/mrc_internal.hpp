@@ -119,6 +119,11 @@ hipError_t launch_smr(const DevShape& S, int64_t nFrames, const void* chL, const
 hipError_t launch_smr_mono_long(const DevShape& S, int64_t nFrames, const void* chL, int fmt, int64_t stride,
                                 const int64_t* offsets, const double* lines, const int* oscale, double* smr,
                                 double* bandPeak, hipStream_t st, unsigned long long* sens);
+// mrc_kernels_probe.hip: one __device__ helper on the caller's words (mrc_dev_helper_probe).  probe_words: the words per element
+// of the three inputs and the output, false for an unknown probe
+bool probe_words(int probe, int* w0, int* w1, int* w2, int* wout);
+hipError_t launch_probe(int probe, const void* in0, const void* in1, const void* in2, void* out, int n, int threads,
+                        hipStream_t st);
 // mrc_kernels_sens.hip: decisions within a guard band of rounding (quantiser edges, allocation ties, M/S threshold)
 hipError_t launch_sensitivity(const DevShape& S, int64_t nFrames, int joint, const double* lines, const int* oscale,
                               const double* smr, const double* bandPeak, const int* msSwitch, const int* bitAlloc,

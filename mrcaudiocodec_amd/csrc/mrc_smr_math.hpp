@@ -45,8 +45,10 @@ __device__ __forceinline__ double exp2_poly(double f) {
 
 // 2^(sT*u/T) for the spreading loop, table driven (T = kExpTab entries per octave, sT = slope in 1/T bit per Bark):
 // n = rint(sT*u) splits into k = n / T (exponent), j = n mod T (entry of the 2^(j/T) table in LDS) and a remainder
-// g = sT*u - n in [-1/2, 1/2] (exact, by fma) whose 2^(g/T) = exp(g ln2/T) is a Taylor polynomial (T = 64: degree 5,
-// remainder < 3.5e-17).  sT*u == 0 gives exactly 1 (a line inside +-1/2 Bark
+// g = sT*u - n in [-1/2, 1/2] (one rounding, by fma) whose 2^(g/T) = exp(g ln2/T) is a Taylor polynomial (T = 64: degree 5,
+// remainder |x|^6/6! e^|x| < 3.53e-17 of the value at |x| <= ln2/128).  With the correctly rounded table entry, the last fma
+// of the chain and the product, one rounding each, the result is within 3.70e-16 (T = 256: 3.73e-16) of 2^(sT*u/T); derived
+// and held on the device by tests/test_gpu_helper_probes.py.  sT*u == 0 gives exactly 1 (a line inside +-1/2 Bark
 // gets exactly the masker's intensity).  Requires |sT*u| < 2^31 (here it is < 16000).
 constexpr int kExpTab = 64;
 constexpr int kExpTabShift = 6;
@@ -176,7 +178,9 @@ __device__ __forceinline__ void wave_sum_all(double* v, int lane) {
 
 // 1/x for a finite positive normal x: hardware estimate + two Newton steps (relative error ~2^-52; NOT the correctly
 // rounded quotient -- used by the fast spreading mode only, where one more rounding per masker / line is inside what the
-// FFT in front of it already differs from the reference's by; the EXACT mode divides like the reference)
+// FFT in front of it already differs from the reference's by; the EXACT mode divides like the reference).  The 2^-52 is for
+// x <= 2^1022: beyond it 1/x is subnormal, on a grid of 2^-1074 that no result can beat, and the last step's rounding leaves
+// the result within 1.5 x 2^-1074 of 1/x.  The thresholds it divides by end far below that or at +inf (line_ratio).
 __device__ __forceinline__ double recip_nr(double x) {
     double r = __builtin_amdgcn_rcp(x);
     r = fma(fma(-x, r, 1.0), r, r);

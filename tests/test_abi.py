@@ -41,6 +41,23 @@ def test_binding_matches_the_header():
     kit.check_binding(declared)
 
 
+def test_helper_probe_table_matches_header_and_kernels():
+    """mrc_dev_helper_probe: the ids and words per element of _lib.PROBES against the MRC_PROBE_ constants of the header and
+    the shapes csrc/mrc_kernels_probe.hip launches with -- a wrong count there is an out-of-bounds access on the device"""
+    from mrcaudiocodec_amd import _lib
+    ids = {n: int(v) for n, v in re.findall(r"#define\s+MRC_PROBE_([A-Z0-9_]+)\s+(\d+)", kit.header_text())}
+    assert ids == {n: p[0] for n, p in _lib.PROBES.items()} and len(set(ids.values())) == len(ids)
+    src = open(os.path.join(ROOT, "mrcaudiocodec_amd", "csrc", "mrc_kernels_probe.hip")).read()
+    shapes = {}
+    for m in re.finditer(r"((?:case MRC_PROBE_[A-Z0-9_]+:\s*)+)return \{(\d+), (\d+), (\d+), (\d+), (?:true|false)\};", src):
+        for n in re.findall(r"MRC_PROBE_([A-Z0-9_]+)", m.group(1)):
+            shapes[n] = (tuple(int(m.group(k)) for k in (2, 3, 4)), int(m.group(5)))
+    assert shapes == {n: (p[1], p[2]) for n, p in _lib.PROBES.items()}
+    for n in ids:                                                      # every probe is launched somewhere
+        assert "MRC_PROBE_CASE(MRC_PROBE_%s)" % n in src, n
+    assert max(max(p[1]) for p in _lib.PROBES.values()) <= 17 and max(p[2] for p in _lib.PROBES.values()) <= 17
+
+
 def test_no_cpu_fallback_without_gpu():
     from mrcaudiocodec_amd import Handle, MrcError, _lib
     if _lib.lib.mrc_device_count() > 0:
