@@ -1144,6 +1144,43 @@ int mrc_pac_store_decode_window_sum(mrc_pac_store* s, int rate_divisor, int mix,
                                     const int64_t* start /*[n_terms]*/, const double* gain /*[n_terms]*/, int64_t window,
                                     int n_channels_out, int format, void* out /* DEVICE [n_items][n_channels_out][window] */,
                                     void* stream);
+/* mrc_pac_store_decode_window_shaped: the rows of mrc_pac_store_decode_window_sum with the spectrum of every term changed on
+ * its MDCT lines -- a telephone band for the speech term, an EQ tilt per item, frequency masks, a per-item low-pass -- one
+ * multiplication per line between the dequantiser and the inverse transform that runs anyway.
+ * Bands: n_bands in 1..MRC_MAX_STORE_BANDS, edge_hz [n_bands + 1] under mrc_band_line_ranges' rule (its words in the refusal),
+ * band_gain [n_terms][n_bands], finite; zero and negative gains are allowed.  For a block of full shape (a, b), band q holds the
+ * lines [r[q], r[q + 1]) that mrc_band_line_ranges(sample_rate, a, b, ...) gives: the FULL shape's line frequencies at every
+ * rate_divisor.  At D = 2 or 4 only the first 1 / D of the lines exist; bands above them are ignored.
+ * The gain: let x[k] be the line the existing call transforms for a plane -- a channel's line after ReconstructLR, or the
+ * mid's line as mrc_pac_store_decode_window_mix defines it (for the non-joint last block of a stereo file under the mid,
+ * 0.5 * (x0 + x1)).  This call transforms __dmul_rn(band_gain[u][q], x[k]) instead, u the term the block is decoded for and q
+ * the line's band: one product, rounded once.  A line that lies in no band (below edge_hz[0], or at or above
+ * edge_hz[n_bands]) is not multiplied at all.  All channels of a term share its row of gains.
+ * Everything after the lines is mrc_pac_store_decode_window_sum's, unchanged: inverse transform, window, overlap-add into the
+ * float64 planes, the fold of a row's terms with `gain` (with or without the resampling filter), the three formats, zeros
+ * outside the file, slabs, stats, damage rules, term order, channel map, single-term identity.  Hence:
+ *   All band gains 1.0: every format equals mrc_pac_store_decode_window_sum bit for bit (x * 1.0 is x).
+ *   All band gains of a term the same power of two 2^e: the term's float64 window is 2^e times its unshaped float64 window, bit
+ *   for bit -- scaling by a power of two commutes with every rounding of the transform as long as nothing goes subnormal
+ *   (checked on the host for D = 1, 2, 4 and 0.25, -2, 2^-20 on every block shape; a coded file's smallest nonzero line is of
+ *   the order of 1e-10).
+ *   The planes never hold -0.0: they remain sums that start from +0.0.
+ * Not a filter in the LTI sense: per-line gains on a lapped transform leave the time-domain aliasing of adjacent blocks
+ * uncancelled where neighbouring lines get different gains.  Smooth gain curves are clean; a brick-wall edge leaves a small
+ * aliasing residue near the edge frequency (DESIGN.md has measured figures).
+ * MRC_ERR_INVALID naming the argument, before any device work and with `out` untouched: every refusal of
+ * mrc_pac_store_decode_window_sum; n_bands out of range; mrc_band_line_ranges' refusals of edge_hz; edge_hz or band_gain NULL
+ * with terms present; a band gain that is not finite (the term and the band are named).
+ * Per slab the line-to-band tables (a uint16 per line of each block shape), the slab's rows of band_gain and one term index per
+ * decoded block go up with the plan: no further copy, no further synchronisation.  The existing entry points do not come
+ * through the shaped kernels. */
+int mrc_pac_store_decode_window_shaped(mrc_pac_store* s, int rate_divisor, int mix, int up, int down, int zeros, double rolloff,
+                                       int n_bands, const double* edge_hz /*[n_bands+1]*/,
+                                       const double* band_gain /*[n_terms][n_bands]*/, int64_t n_items,
+                                       const int64_t* term_offset /*[n_items+1]*/, const int64_t* file /*[n_terms]*/,
+                                       const int64_t* start /*[n_terms]*/, const double* gain /*[n_terms]*/, int64_t window,
+                                       int n_channels_out, int format, void* out /* DEVICE [n_items][n_channels_out][window] */,
+                                       void* stream);
 
 /* Per-stage device time of the most recent timed call when timing is enabled (hipEvents on the launch stream; the call
  * then synchronises).  Timed: mrc_dev_encode / mrc_dev_encode_ex and mrc_encode_mono / mrc_encode_joint (the _blocks

@@ -40,6 +40,11 @@ puts in.pac DB above other.pac over the excerpt (levels.LevelMap.gains_for_snr, 
 overlay's sample under the excerpt's first; a negative N starts the overlay that far into the excerpt.  Codec settings that
 differ between the files are refused, the parameter named.  Composes with --start, --samples, --mix, --rate-divisor and
 --sample-rate.
+A changed spectrum:  python -m mrcaudiocodec_amd.cli -d in.pac out.wav --band-gains-db "0-300:-inf,3400-24000:-inf"  multiplies
+the file's MDCT lines between LO and HI Hz by DB decibels (-inf: zero) before the inverse transform, through the same store
+(mrc_pac_store_decode_window_shaped): bands ascend and do not overlap, a gap stays at 0 dB.  Composes with --start, --samples,
+--rate-divisor, --mix, --sample-rate and --overlay (the overlay is left as it is); refused without -d and with --band-energies.
+Per-line gains are not an LTI filter: a brick-wall edge leaves a small aliasing residue near the edge frequency.
 Levels:  python -m mrcaudiocodec_amd.cli --levels a.pac [b.pac ...] [--levels-window N]  decodes nothing and writes nothing: per
 file one JSON line with its channels, samples, RMS level per channel (dB re full scale) and its loudest and quietest window of
 N samples (default one second) on the short-block grid with their starts, from the energies of the blocks' MDCT lines
@@ -539,7 +544,8 @@ def levels_of_files(pac_paths, window=None, device_id=0, rate_divisor=1, mix=Non
     return out
 
 
-BAND_ENERGIES_REFUSES = tuple(f for f in LEVELS_REFUSES if f not in ("src", "dst")) + ("--levels", "--levels-window", "--rate-divisor")
+BAND_ENERGIES_REFUSES = tuple(f for f in LEVELS_REFUSES if f not in ("src", "dst")) + ("--levels", "--levels-window", "--rate-divisor",
+                                                                                        "--band-gains-db")
 
 
 def check_band_energies_args(band_energies, hop, band_edges, given):
@@ -596,6 +602,42 @@ def band_energies_of_file(pac_path, npy_path, hop, band_edges_hz=None, device_id
     return e
 
 
+def check_band_gains_db_args(band_gains_db, decode):
+    """--band-gains-db as given (None: not given), "LO-HI:DB[,LO-HI:DB...]" -> (edges in Hz float64 [bands + 1], gains float64
+    [bands]) for PacStore.decode_window(band_gains=, band_edges_hz=), or None.  LO and HI are frequencies in Hz, 0 <= LO < HI,
+    the bands ascending and not overlapping; DB is a number of decibels or -inf.  A gap between two bands becomes a band of
+    its own at 0 dB (factor 1.0); what lies below the first LO and at or above the last HI is left alone.  It changes the
+    spectrum of a decode: refused without -d."""
+    if band_gains_db is None:
+        return None
+    if not decode:
+        raise ValueError("--band-gains-db changes the spectrum of a decode: it needs -d")
+    from .store import MAX_BANDS, gains_from_db
+    edges, db = [], []
+    for part in str(band_gains_db).split(","):
+        try:
+            span, level = part.split(":")
+            lo, hi = span.split("-")                     # (frequencies are not negative: the one '-' separates them)
+            lo, hi, level = float(lo), float(hi), float(level)
+        except ValueError:
+            raise ValueError("--band-gains-db: %r is not LO-HI:DB (frequencies in Hz, decibels or -inf)" % (part,))
+        if not (np.isfinite(lo) and np.isfinite(hi) and 0 <= lo < hi):
+            raise ValueError("--band-gains-db: %r: the band must be 0 <= LO < HI, finite" % (part,))
+        if np.isnan(level) or level == np.inf:
+            raise ValueError("--band-gains-db: %r: DB must be a finite number of decibels or -inf" % (part,))
+        if edges and lo < edges[-1]:
+            raise ValueError("--band-gains-db: %r starts below the end of the band before it: bands ascend and do not overlap" % (part,))
+        if edges and lo > edges[-1]:
+            db.append(0.0)                               # the gap: a band at 0 dB
+        if not edges or lo > edges[-1]:
+            edges.append(lo)
+        edges.append(hi)
+        db.append(level)
+    if len(db) > MAX_BANDS:
+        raise ValueError("--band-gains-db: %d bands (gaps included) are more than %d" % (len(db), MAX_BANDS))
+    return np.array(edges, np.float64), gains_from_db(db)
+
+
 CODEC_SETTINGS = ("sample_rate", "n_mdct_lines", "n_scale_bits", "n_mant_size_bits")   # what a .pac header says of its codec
 
 
@@ -614,7 +656,8 @@ def _levels_of_mix(store, rate_divisor, mix):
     return LevelMap(per_file, cfg.n_mdct_lines, rate_divisor, cfg.n_short)
 
 
-def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=1, mix=None, sample_rate=None, overlay=None):
+def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=1, mix=None, sample_rate=None, overlay=None,
+                    band_gains=None):
     """excerpt: None (the whole file, mrc_decode_pac_pcm16) or (start, samples): that many samples from sample `start` on
     (samples None: to the end of the file), decoded through a one-file PacStore -- only the blocks the excerpt overlaps are
     parsed and synthesised; what lies outside the file is silence.  rate_divisor 2 or 4: at that fraction of the sample rate,
@@ -626,6 +669,9 @@ def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=
     settings added under the excerpt in ONE PacStore.decode_window_sum call of two terms -- the file at 1.0 and the overlay,
     from its sample `start` on (negative: it begins that far into the excerpt), at the factor that puts the excerpt snr_db
     above it (levels.LevelMap.gains_for_snr over the excerpt, from the block energies; the factor is printed).
+    band_gains: None or (edges in Hz, gains) of check_band_gains_db_args: the file's MDCT lines multiplied band by band before
+    the inverse transform (PacStore.decode_window(band_gains=)), through the store as well; the overlay is left as it is, and
+    its level is set against the unshaped excerpt.
     -> int16 [nCh][samples] as written."""
     with open(pac_path, "rb") as fp:
         buf = fp.read()
@@ -651,7 +697,8 @@ def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=
         from .store import resample_plan
         rate_divisor, up, down = resample_plan(cfg.sample_rate, int(sample_rate))
         resample = None if up == down else (up, down)
-    if (rate_divisor != 1 or mix is not None or resample is not None or overlay is not None) and excerpt is None:
+    if (rate_divisor != 1 or mix is not None or resample is not None or overlay is not None or band_gains is not None) \
+            and excerpt is None:
         excerpt = (0, None)
     h = Handle(sample_rate=cfg.sample_rate, n_mdct_lines=cfg.n_mdct_lines, n_scale_bits=cfg.n_scale_bits,
                n_mant_size_bits=cfg.n_mant_size_bits, device_id=device_id)
@@ -665,8 +712,11 @@ def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=
                 if samples is None:
                     n = store.n_samples_at(rate_divisor) if resample is None else store.n_samples_resampled(*resample, rate_divisor)
                     samples = max(0, int(n[0]) - start)
+                shaped = {} if band_gains is None else dict(band_edges_hz=band_gains[0])
                 if overlay is None:
-                    got = store.decode_window([0], [start], samples, rate_divisor=rate_divisor, mix=mix, resample=resample)
+                    if band_gains is not None:
+                        shaped["band_gains"] = band_gains[1]
+                    got = store.decode_window([0], [start], samples, rate_divisor=rate_divisor, mix=mix, resample=resample, **shaped)
                 else:
                     # the levels live at the rate divisor's rate: the excerpt's span there (the whole of it, rounded outwards)
                     up, down = resample if resample is not None else (1, 1)
@@ -675,8 +725,10 @@ def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=
                     gain = float(_levels_of_mix(store, rate_divisor, mix).gains_for_snr(
                         overlay[1], [0], [at(start)], [1], [at(overlay[2])], span)[0]) if samples else 1.0
                     print("overlay: %s at a factor of %.9g (%g dB under the excerpt)" % (overlay[0], gain, overlay[1]))
+                    if band_gains is not None:           # (the overlay's row: ones)
+                        shaped["band_gains"] = np.stack([band_gains[1], np.ones_like(band_gains[1])])[None]
                     got = store.decode_window_sum([[0, 1]], [[start, overlay[2]]], [[1.0, gain]], samples, rate_divisor=rate_divisor,
-                                                  mix=mix, resample=resample)
+                                                  mix=mix, resample=resample, **shaped)
                 inter = np.ascontiguousarray(got[0].cpu().numpy().T)
     finally:
         h.close()
@@ -814,6 +866,11 @@ def main(argv=None):
     ap.add_argument("--overlay-start", type=int, default=None, metavar="N",
                     help="with --overlay: the overlay's sample that falls on the excerpt's first (default 0; negative: the "
                          "overlay begins that many samples into the excerpt)")
+    ap.add_argument("--band-gains-db", default=None, metavar="LO-HI:DB,...",
+                    help="with -d: multiply the MDCT lines between LO and HI Hz by DB decibels (-inf: silence them) before the "
+                         "inverse transform, e.g. 0-300:-inf,3400-24000:-inf for a telephone band; bands ascend and do not "
+                         "overlap, gaps stay at 0 dB; composes with --start, --samples, --rate-divisor, --mix, --sample-rate and "
+                         "--overlay (the overlay is left as it is)")
     ap.add_argument("--levels", nargs="+", default=None, metavar="PAC",
                     help="no src, no dst: print one JSON line per .pac file with its channels, samples, RMS level per channel "
                          "(dB re full scale) and its loudest and quietest window on the short-block grid, from the block "
@@ -840,7 +897,7 @@ def main(argv=None):
             "--sample-rate": a.sample_rate is not None}
         bands = check_band_energies_args(a.band_energies, a.hop, a.band_edges, dict(
             given, **{"--levels": a.levels is not None, "--levels-window": a.levels_window is not None,
-                      "--rate-divisor": a.rate_divisor is not None}))
+                      "--rate-divisor": a.rate_divisor is not None, "--band-gains-db": a.band_gains_db is not None}))
         levels = check_levels_args(a.levels, a.levels_window, given)
         if levels is None and (a.src is None or a.dst is None):
             raise ValueError("the following arguments are required: src, dst")
@@ -849,6 +906,7 @@ def main(argv=None):
         mix = check_mix_args(a.mix, a.decode or levels is not None or bands is not None)
         sample_rate = check_sample_rate_args(a.sample_rate, a.decode, a.rate_divisor is not None)
         overlay = check_overlay_args(a.overlay, a.snr_db, a.overlay_start, a.decode)
+        band_gains = check_band_gains_db_args(a.band_gains_db, a.decode)
         if levels is not None:
             from .store import check_levels_mix
             check_levels_mix(mix, "--mix")
@@ -911,7 +969,7 @@ def main(argv=None):
         return
     if a.decode:
         try:
-            pcm = decode_pac_file(a.src, a.dst, a.device, excerpt, rate_divisor, mix, sample_rate, overlay)
+            pcm = decode_pac_file(a.src, a.dst, a.device, excerpt, rate_divisor, mix, sample_rate, overlay, band_gains)
         except ValueError as e:
             ap.error(str(e))
         print("%s: %d channels x %d samples" % (a.dst, pcm.shape[0], pcm.shape[1]))

@@ -49,6 +49,12 @@
 // order given, into the caller's tensor.  The term records (WindowItem, gain, output start) and the rows' term offsets go up
 // with the plan.  No per-term window is written.
 //
+// decode_window_shaped, those rows with a band gain on every decoded MDCT line: decode_windows with a shaping spec beside the
+// filter and the rows.  Per call one uint16 line-to-band table per block shape (band_line_ranges over the FULL shape, at every
+// D); per slab, in the same staging copy as the plan, those tables, the slab's rows of gains and one unit index per slot or
+// workgroup laid out as the block offsets are; the shaped launches (mrc_kernels_decode.hip) multiply once per line between
+// the dequantiser and the inverse transform.  Calls without gains never come here.
+//
 // block_energy, ((a + b) / D) * the sum of squares of a block's first 1 / D decoded lines, per channel or for the mid, for
 // every block of the selected files: the same slab plan (stage_slab, parse_slab) over runs of whole blocks instead of the
 // blocks of windows, then block_energy_kernel per group (mrc_kernels_store.hip) in place of planes, synthesis and output.
@@ -76,6 +82,7 @@ const char* const kWinReduced = "mrc_pac_store_decode_window_reduced";
 const char* const kWinMix = "mrc_pac_store_decode_window_mix";
 const char* const kWinResampled = "mrc_pac_store_decode_window_resampled";
 const char* const kWinSum = "mrc_pac_store_decode_window_sum";
+const char* const kWinShaped = "mrc_pac_store_decode_window_shaped";
 constexpr int kNoMix = -1;                           // decode_windows: every channel of a file into a plane of its own
 
 int store_alive(mrc_pac_store* s, const char* fn) {
@@ -305,14 +312,25 @@ int get_resample_table(mrc_handle* h, const ResampleSpec& r, const ResampleTable
 // UNIT, (file[k], start[k]) -- is then a TERM of row i, k in [termOffset[i], termOffset[i + 1]), n_items the number of terms;
 // a slab is a run of whole rows, counted by its terms' spans, and sum_out_kernel / resample_sum_out_kernel fold a row's
 // terms with their gains where the other calls copy or fold one unit per row.  Without it a row is its one unit.
+// shape (mrc_pac_store_decode_window_shaped) null or the band gains of that call, one row per unit: each needed block is then
+// synthesised by the shaped launches, its line k multiplied once by the unit's gain of the band that
+// band_line_ranges(sample rate, the block's FULL shape) puts it in, whatever D.  Per call: lineBand, a uint16 per line of each
+// block shape (kNoLineBand: in no band).  Per slab, in the one staging copy: those tables, the slab's rows of gains, and one
+// unit index per slot or workgroup laid out as the block offsets are.
 struct SumSpec {
     int64_t nRows;
     const int64_t* termOffset;                               // [nRows + 1], checked by the caller
     const double* gain;                                      // [n_items]
 };
+struct ShapeSpec {
+    int nBands;
+    const double* bandGain;                                  // [n_items][nBands], checked by the caller
+    std::vector<uint16_t> lineBand;                          // the band of every line of the four block shapes, shape after shape
+    int64_t lineOff[4];                                      // ... shape sh from lineOff[sh] on, (a + b) / 2 values
+};
 int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, int64_t n_items, const int64_t* file, const int64_t* start,
                    int64_t window, int n_channels_out, int format, void* out, void* stream, const ResampleSpec* rs = nullptr,
-                   const SumSpec* sum = nullptr) {
+                   const SumSpec* sum = nullptr, const ShapeSpec* shape = nullptr) {
     MRC_TRY(store_alive(s, fn));
     mrc_handle* h = s->h;
     const mrc_config& cfg = h->cfg;
@@ -393,7 +411,7 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
         // ---- staging (one H2D copy): plan | groups | block offsets | items (a sum: term records | the rows' term offsets);
         // a slot's offset is its block's place in the item's plane: the block's position in the file's padded plane, the
         // window's start at 2 L
-        size_t oOffs = 0, oItems = 0, oOutStart = 0;
+        size_t oOffs = 0, oItems = 0, oOutStart = 0, oLineBand = 0, oBandGain = 0, oUnit = 0;
         SlabStage S;
         MRC_TRY(stage_slab(
             s, fn, mix, needs, &pl, &S,
@@ -406,6 +424,11 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
                     oItems = lay->add<WindowItem>(nSlab);
                     if (rs) oOutStart = lay->add<long long>(nSlab);
                 }
+                if (shape) {
+                    oLineBand = lay->add<uint16_t>((int64_t)shape->lineBand.size());
+                    oBandGain = lay->add<double>(nSlab * shape->nBands);
+                    oUnit = lay->add<int>(pl.totalSlots);    // (indexed as the offsets are: a pair's workgroup, a single slot)
+                }
             },
             [&](const Need& n, int g, int slot, int ch, bool pair) {
                 const WindowItem& it = items[(size_t)n.item];
@@ -413,8 +436,9 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
                 const int64_t at = it.plane + 2 * L + s->blockStart[(size_t)(s->firstBlock[(size_t)n.file] + n.block)] / D - (it.start + L);
                 // a pair's workgroup is its index among the pairs; a single slot's comes after the group's pairs; without a
                 // mix a channel has a plane of its own
-                if (pair) offs[slot / 2] = at;
-                else offs[slot - S.nPairs[g]] = at + (mix == kNoMix ? ch * planeLen : 0);
+                const int64_t wg = pair ? slot / 2 : slot - S.nPairs[g];
+                offs[wg] = pair ? at : at + (mix == kNoMix ? ch * planeLen : 0);
+                if (shape) ((int*)(S.pin + oUnit))[pl.slotBase[g] + wg] = (int)n.item;
             }));
         const int64_t* nPairs = S.nPairs;
         const UnpackGroupDev* gd = S.gd;
@@ -426,6 +450,10 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
         } else {
             std::memcpy(S.pin + oItems, items.data(), sizeof(WindowItem) * nSlab);
             if (rs) std::memcpy(S.pin + oOutStart, start + first, sizeof(long long) * nSlab);
+        }
+        if (shape) {
+            std::memcpy(S.pin + oLineBand, shape->lineBand.data(), sizeof(uint16_t) * shape->lineBand.size());
+            std::memcpy(S.pin + oBandGain, shape->bandGain + u0 * shape->nBands, sizeof(double) * (size_t)(nSlab * shape->nBands));
         }
         const HostShape* reduced[4] = {};
         for (int sh = 0; D > 1 && sh < 4; ++sh)
@@ -439,7 +467,21 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
         MRC_HIP(h, hipEventRecord(b.ev[3], st));
         MRC_HIP(h, hipMemsetAsync(x, 0, sizeof(double) * (size_t)planeDoubles, st));
         const int64_t* offsDev = (const int64_t*)(din + oOffs);
-        if (mix == kNoMix && D == 1) MRC_TRY(decode_groups(h, pl, gd, offsDev, x, planeLen, st));
+        if (shape)
+            MRC_TRY(pac_for_groups(h, pl, gd, offsDev, [&](int g, const UnpackGroupDev& G, const int64_t* o) {
+                const DevShape& F = pl.hs[g / 2]->dev;
+                const DevShape* R = D == 1 ? nullptr : &reduced[g / 2]->dev;
+                const uint16_t* lineBand = (const uint16_t*)(din + oLineBand) + shape->lineOff[g / 2];
+                const double* bandGain = (const double*)(din + oBandGain);
+                const int* unit = (const int*)(din + oUnit) + (o - offsDev);
+                if (mix != kNoMix)
+                    return launch_decode_shaped_mix(F, R, lineBand, bandGain, unit, shape->nBands, pl.nSlots[g] - nPairs[g], G.joint,
+                                                    mix == MRC_MIX_MID ? 2 : mix == MRC_MIX_LEFT ? 0 : 1, nPairs[g], G.oscale,
+                                                    G.joint ? G.ms : nullptr, G.sf, G.ba, G.mant, o, x, st);
+                return launch_decode_shaped(F, R, lineBand, bandGain, unit, shape->nBands, pl.nSlots[g], G.joint ? 2 : 1, G.oscale,
+                                            G.joint ? G.ms : nullptr, G.sf, G.ba, G.mant, o, x, G.joint ? x + planeLen : nullptr, st);
+            }));
+        else if (mix == kNoMix && D == 1) MRC_TRY(decode_groups(h, pl, gd, offsDev, x, planeLen, st));
         else
             MRC_TRY(pac_for_groups(h, pl, gd, offsDev, [&](int g, const UnpackGroupDev& G, const int64_t* o) {
                 const DevShape& F = pl.hs[g / 2]->dev;
@@ -858,12 +900,19 @@ int mrc_pac_store_decode_window_resampled(mrc_pac_store* s, int rate_divisor, in
                           n_channels_out, format, out, stream, &r);
 }
 
-int mrc_pac_store_decode_window_sum(mrc_pac_store* s, int rate_divisor, int mix, int up, int down, int zeros, double rolloff,
-                                    int64_t n_items, const int64_t* term_offset, const int64_t* file, const int64_t* start,
-                                    const double* gain, int64_t window, int n_channels_out, int format, void* out, void* stream) {
-    MRC_TRY(store_alive(s, kWinSum));
+}  // extern "C"
+
+namespace {
+
+// mrc_pac_store_decode_window_sum and, with bands (n_bands, edge_hz, band_gain: the caller's, unchecked),
+// mrc_pac_store_decode_window_shaped: the checks of the rows and of the bands, then decode_windows
+struct BandArgs { int nBands; const double* edgeHz; const double* bandGain; };
+int decode_window_rows(mrc_pac_store* s, const char* fn, int rate_divisor, int mix, int up, int down, int zeros, double rolloff,
+                       const BandArgs* bands, int64_t n_items, const int64_t* term_offset, const int64_t* file, const int64_t* start,
+                       const double* gain, int64_t window, int n_channels_out, int format, void* out, void* stream) {
+    MRC_TRY(store_alive(s, fn));
     mrc_handle* h = s->h;
-    const std::string w = kWinSum;
+    const std::string w = fn;
     if (mix != MRC_MIX_EACH && mix != MRC_MIX_MID && mix != MRC_MIX_LEFT && mix != MRC_MIX_RIGHT)
         return fail(h, MRC_ERR_INVALID, w + ": mix " + std::to_string(mix) +
                                             " is not MRC_MIX_EACH (3), MRC_MIX_MID (0), MRC_MIX_LEFT (1) or MRC_MIX_RIGHT (2)");
@@ -886,9 +935,54 @@ int mrc_pac_store_decode_window_sum(mrc_pac_store* s, int rate_divisor, int mix,
     if (nTerms > 0 && (!file || !start || !gain)) return fail(h, MRC_ERR_INVALID, w + ": file, start or gain is NULL");
     for (int64_t k = 0; k < nTerms; ++k)
         if (!std::isfinite(gain[k])) return fail(h, MRC_ERR_INVALID, w + ": gain of term " + std::to_string(k) + " is not finite");
+    ShapeSpec shape;
+    if (bands) {
+        const int nb = bands->nBands;
+        if (nb < 1 || nb > MRC_MAX_STORE_BANDS)
+            return fail(h, MRC_ERR_INVALID, w + ": n_bands " + std::to_string(nb) + " is outside 1.." + std::to_string(MRC_MAX_STORE_BANDS));
+        if (nTerms > 0 && (!bands->edgeHz || !bands->bandGain)) return fail(h, MRC_ERR_INVALID, w + ": edge_hz or band_gain is NULL");
+        shape.nBands = nb;
+        shape.bandGain = bands->bandGain;
+        int32_t lineLo[MRC_MAX_STORE_BANDS + 1];
+        for (int sh = 0; bands->edgeHz && sh < 4; ++sh) {
+            int a, b;
+            shape_ab(h->cfg, sh, &a, &b);
+            const std::string refusal = band_line_ranges((double)h->cfg.sample_rate, a, b, nb, bands->edgeHz, lineLo);
+            if (!refusal.empty()) return fail(h, MRC_ERR_INVALID, w + ": " + refusal);
+            shape.lineOff[sh] = (int64_t)shape.lineBand.size();
+            shape.lineBand.resize(shape.lineBand.size() + (size_t)((a + b) / 2), kNoLineBand);
+            uint16_t* lb = shape.lineBand.data() + shape.lineOff[sh];
+            for (int q = 0; q < nb; ++q)
+                for (int k = lineLo[q]; k < lineLo[q + 1]; ++k) lb[k] = (uint16_t)q;
+        }
+        for (int64_t k = 0; k < nTerms; ++k)
+            for (int q = 0; q < nb; ++q)
+                if (!std::isfinite(bands->bandGain[k * nb + q]))
+                    return fail(h, MRC_ERR_INVALID, w + ": band_gain of term " + std::to_string(k) + ", band " + std::to_string(q) + " is not finite");
+    }
     const SumSpec sum{n_items, term_offset, gain};
-    return decode_windows(s, kWinSum, rate_divisor, mix == MRC_MIX_EACH ? nullptr : &mix, nTerms, file, start, window, n_channels_out,
-                          format, out, stream, up != down ? &r : nullptr, &sum);
+    return decode_windows(s, fn, rate_divisor, mix == MRC_MIX_EACH ? nullptr : &mix, nTerms, file, start, window, n_channels_out,
+                          format, out, stream, up != down ? &r : nullptr, &sum, bands ? &shape : nullptr);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mrc_pac_store_decode_window_sum(mrc_pac_store* s, int rate_divisor, int mix, int up, int down, int zeros, double rolloff,
+                                    int64_t n_items, const int64_t* term_offset, const int64_t* file, const int64_t* start,
+                                    const double* gain, int64_t window, int n_channels_out, int format, void* out, void* stream) {
+    return decode_window_rows(s, kWinSum, rate_divisor, mix, up, down, zeros, rolloff, nullptr, n_items, term_offset, file, start, gain,
+                              window, n_channels_out, format, out, stream);
+}
+
+int mrc_pac_store_decode_window_shaped(mrc_pac_store* s, int rate_divisor, int mix, int up, int down, int zeros, double rolloff,
+                                       int n_bands, const double* edge_hz, const double* band_gain, int64_t n_items,
+                                       const int64_t* term_offset, const int64_t* file, const int64_t* start, const double* gain,
+                                       int64_t window, int n_channels_out, int format, void* out, void* stream) {
+    const BandArgs bands{n_bands, edge_hz, band_gain};
+    return decode_window_rows(s, kWinShaped, rate_divisor, mix, up, down, zeros, rolloff, &bands, n_items, term_offset, file, start,
+                              gain, window, n_channels_out, format, out, stream);
 }
 
 int mrc_pac_store_block_energy(mrc_pac_store* s, int rate_divisor, int mix, int64_t n_sel, const int64_t* file,

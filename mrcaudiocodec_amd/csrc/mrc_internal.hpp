@@ -164,6 +164,19 @@ hipError_t launch_decode_reduced(const DevShape& F, const DevShape& R, int64_t n
 hipError_t launch_decode_mix(const DevShape& F, const DevShape* R, int64_t nWorkgroups, int joint, int mixSel, int64_t nPairs,
                              const int* oscale, const int* msSwitch, const int* scaleFactor, const int* bitAlloc,
                              const int* mantissa, const int64_t* outOffset, double* out, hipStream_t st);
+// launch_decode (R null) / launch_decode_reduced and launch_decode_mix with one band gain per line between the dequantiser
+// and the inverse transform (mrc_pac_store_decode_window_shaped): line k of a block is multiplied once by
+// gain[unit[i]][lineBand[k]] unless lineBand[k] is kNoLineBand.  lineBand [F.halfN] counts the lines of the FULL shape at every
+// rate; unit is indexed as outOffset is (per slot, per workgroup); all three DEVICE.
+constexpr unsigned short kNoLineBand = 0xffff;      // lineBand: the line lies in no band
+hipError_t launch_decode_shaped(const DevShape& F, const DevShape* R, const unsigned short* lineBand, const double* gain,
+                                const int* unit, int nBands, int64_t nBlocks, int nStreams, const int* oscale, const int* msSwitch,
+                                const int* scaleFactor, const int* bitAlloc, const int* mantissa, const int64_t* outOffset,
+                                double* outL, double* outR, hipStream_t st);
+hipError_t launch_decode_shaped_mix(const DevShape& F, const DevShape* R, const unsigned short* lineBand, const double* gain,
+                                    const int* unit, int nBands, int64_t nWorkgroups, int joint, int mixSel, int64_t nPairs,
+                                    const int* oscale, const int* msSwitch, const int* scaleFactor, const int* bitAlloc,
+                                    const int* mantissa, const int64_t* outOffset, double* out, hipStream_t st);
 // mrc_kernels_pack.hip -- `.pac` chunk packing on the device
 constexpr int kPackLutSize = 65;     // the largest value in any Huffman table is 64
 constexpr int kPackRawTable = 15;    // codecThem.py:149

@@ -14,6 +14,9 @@
 //     the mid (L + R) / 2 formed on the lines before the one inverse transform (decode_line_mid; the store's mix windows).
 //   decode_reduced_kernel   the same block at 1 / D of its sample rate: its first halfN / D lines through the inverse
 //     transform of the shape (a, b) / D (the resident store's reduced windows, mrc_api_store.cpp).
+//   decode_shaped_kernel, decode_shaped_mix_kernel, decode_reduced_shaped_kernel, decode_reduced_shaped_mix_kernel   the four
+//     store launches above with one band gain per line between the dequantiser and the inverse transform
+//     (mrc_pac_store_decode_window_shaped): decode_block<.., true>, the unshaped instantiations keep their code.
 //   pcm16_kernel    |x| -> 16-bit magnitude code (quantize.py:61-87) with the sign re-applied as 2's complement.
 //
 // The reference computes the IMDCT with an N-point complex inverse FFT; like the forward transform the results
@@ -32,13 +35,28 @@ namespace {
 // non-joint slot means the PAIR of slots f, f + 1, a stereo file's last block (its two chunks side by side are laid out
 // as one slot of two streams, each with its own overall scale).  out: the plane, at the block's first sample.
 // kMix false: sel is a channel, and the two-plane kernels hold no code for the mid.
+// kShaped (mrc_pac_store_decode_window_shaped): line k, as the unshaped block transforms it, is multiplied once by
+// gainRow[lineBand[k]] -- lineBand the uint16 band of every line of the block's FULL shape (coalesced), kNoLineBand where the
+// line lies in no band and is left as it is; gainRow the unit's row of band gains (at most 2 KB, read by every lane of the
+// workgroup: it stays in cache).  No LDS beyond the unshaped block's.
 constexpr int kSelMid = 2;
-template <bool kMix>
+template <bool kShaped>
+__device__ __forceinline__ double shape_line(double x, int k, const unsigned short* __restrict__ lineBand,
+                                             const double* __restrict__ gainRow) {
+    if (kShaped) {
+        const unsigned short q = lineBand[k];
+        if (q != kNoLineBand) x = __dmul_rn(gainRow[q], x);
+    }
+    return x;
+}
+template <bool kMix, bool kShaped = false>
 __device__ __forceinline__ void decode_block(const DevShape& S, const unsigned char* __restrict__ bandOfLine, int nb,
                                              int lineStride, int nScaleBits, bool joint, int64_t f, int sel,
                                              const int* __restrict__ oscale, const int* __restrict__ msSwitch,
                                              const int* __restrict__ scaleFactor, const int* __restrict__ bitAlloc,
-                                             const int* __restrict__ mantissa, double* __restrict__ out, double* smem) {
+                                             const int* __restrict__ mantissa, double* __restrict__ out, double* smem,
+                                             const unsigned short* __restrict__ lineBand = nullptr,
+                                             const double* __restrict__ gainRow = nullptr) {
     const int tid = threadIdx.x;
     const int N = S.N, M = S.halfN, Q = S.Q;
     const int nStreams = joint ? 2 : 1;
@@ -54,17 +72,19 @@ __device__ __forceinline__ void decode_block(const DevShape& S, const unsigned c
     // dequantise, undo the overall scale (codecThem.py:47-51, 92-109), rebuild L / R (ms_stereo.py:33-49) or the mid
     if (!kMix || sel != kSelMid) {
         for (int k = tid; k < M; k += kThreads)
-            v[k] = decode_line(k, bandOfLine[k], sel, joint, nb, lineStride, nScaleBits, os, ms, sf, ba, mant);
+            v[k] = shape_line<kShaped>(decode_line(k, bandOfLine[k], sel, joint, nb, lineStride, nScaleBits, os, ms, sf, ba, mant), k,
+                                       lineBand, gainRow);
     } else if (joint) {
         for (int k = tid; k < M; k += kThreads)
-            v[k] = decode_line_mid(k, bandOfLine[k], nb, lineStride, nScaleBits, os, ms, sf, ba, mant);
+            v[k] = shape_line<kShaped>(decode_line_mid(k, bandOfLine[k], nb, lineStride, nScaleBits, os, ms, sf, ba, mant), k, lineBand,
+                                       gainRow);
     } else {
         for (int k = tid; k < M; k += kThreads) {
             const int band = bandOfLine[k];
             const double x0 = decode_line(k, band, 0, false, nb, lineStride, nScaleBits, os, nullptr, sf, ba, mant);
             const double x1 = decode_line(k, band, 0, false, nb, lineStride, nScaleBits, os + 1, nullptr, sf + nb, ba + nb,
                                           mant + lineStride);
-            v[k] = 0.5 * (x0 + x1);
+            v[k] = shape_line<kShaped>(0.5 * (x0 + x1), k, lineBand, gainRow);
         }
     }
     __syncthreads();
@@ -179,6 +199,82 @@ __global__ __launch_bounds__(kThreads) void decode_reduced_mix_kernel(DevShape R
                  out + outOffset[blockIdx.x], smem);
 }
 
+// The four store launches with band gains (mrc_pac_store_decode_window_shaped).  Sh: lineBand, the band of every line of the
+// block's full shape; gain [units][nBands]; unit, the row of gains per slot (two-plane launches) or per workgroup (one-plane
+// launches) -- indexed exactly as outOffset is.
+struct ShapeDev {
+    const unsigned short* lineBand;
+    const double* gain;
+    const int* unit;
+    int nBands;
+};
+__device__ __forceinline__ const double* gain_row(const ShapeDev& Sh, int64_t at) { return Sh.gain + (int64_t)Sh.unit[at] * Sh.nBands; }
+
+__global__ __launch_bounds__(kThreads) void decode_shaped_kernel(DevShape S, ShapeDev Sh, int nStreams,
+                                                                 const int* __restrict__ oscale,
+                                                                 const int* __restrict__ msSwitch,
+                                                                 const int* __restrict__ scaleFactor,
+                                                                 const int* __restrict__ bitAlloc,
+                                                                 const int* __restrict__ mantissa,
+                                                                 const int64_t* __restrict__ outOffset,
+                                                                 double* __restrict__ outL, double* __restrict__ outR) {
+    extern __shared__ double smem[];
+    const BlockChannel bc = block_channel(nStreams);
+    decode_block<false, true>(S, S.bandOfLine, S.nBands, S.halfN, S.nScaleBits, nStreams == 2, bc.f, bc.ch, oscale, msSwitch,
+                              scaleFactor, bitAlloc, mantissa, (bc.ch == 0 ? outL : outR) + outOffset[bc.f], smem, Sh.lineBand,
+                              gain_row(Sh, bc.f));
+}
+
+__global__ __launch_bounds__(kThreads) void decode_shaped_mix_kernel(DevShape S, ShapeDev Sh, int joint, int mixSel, int64_t nPairs,
+                                                                     const int* __restrict__ oscale,
+                                                                     const int* __restrict__ msSwitch,
+                                                                     const int* __restrict__ scaleFactor,
+                                                                     const int* __restrict__ bitAlloc,
+                                                                     const int* __restrict__ mantissa,
+                                                                     const int64_t* __restrict__ outOffset,
+                                                                     double* __restrict__ out) {
+    extern __shared__ double smem[];
+    int64_t f;
+    int sel;
+    mix_slot(joint != 0, mixSel, nPairs, &f, &sel);
+    decode_block<true, true>(S, S.bandOfLine, S.nBands, S.halfN, S.nScaleBits, joint != 0, f, sel, oscale, msSwitch, scaleFactor,
+                             bitAlloc, mantissa, out + outOffset[blockIdx.x], smem, Sh.lineBand, gain_row(Sh, blockIdx.x));
+}
+
+__global__ __launch_bounds__(kThreads) void decode_reduced_shaped_kernel(DevShape R, ShapeDev Sh,
+                                                                         const unsigned char* __restrict__ bandOfLine, int nb,
+                                                                         int fullLines, int nScaleBits, int nStreams,
+                                                                         const int* __restrict__ oscale,
+                                                                         const int* __restrict__ msSwitch,
+                                                                         const int* __restrict__ scaleFactor,
+                                                                         const int* __restrict__ bitAlloc,
+                                                                         const int* __restrict__ mantissa,
+                                                                         const int64_t* __restrict__ outOffset,
+                                                                         double* __restrict__ outL, double* __restrict__ outR) {
+    extern __shared__ double smem[];
+    const BlockChannel bc = block_channel(nStreams);
+    decode_block<false, true>(R, bandOfLine, nb, fullLines, nScaleBits, nStreams == 2, bc.f, bc.ch, oscale, msSwitch, scaleFactor,
+                              bitAlloc, mantissa, (bc.ch == 0 ? outL : outR) + outOffset[bc.f], smem, Sh.lineBand, gain_row(Sh, bc.f));
+}
+
+__global__ __launch_bounds__(kThreads) void decode_reduced_shaped_mix_kernel(DevShape R, ShapeDev Sh,
+                                                                             const unsigned char* __restrict__ bandOfLine, int nb,
+                                                                             int fullLines, int nScaleBits, int joint, int mixSel,
+                                                                             int64_t nPairs, const int* __restrict__ oscale,
+                                                                             const int* __restrict__ msSwitch,
+                                                                             const int* __restrict__ scaleFactor,
+                                                                             const int* __restrict__ bitAlloc,
+                                                                             const int* __restrict__ mantissa,
+                                                                             const int64_t* __restrict__ outOffset,
+                                                                             double* __restrict__ out) {
+    extern __shared__ double smem[];
+    int64_t f;
+    int sel;
+    mix_slot(joint != 0, mixSel, nPairs, &f, &sel);
+    decode_block<true, true>(R, bandOfLine, nb, fullLines, nScaleBits, joint != 0, f, sel, oscale, msSwitch, scaleFactor, bitAlloc,
+                             mantissa, out + outOffset[blockIdx.x], smem, Sh.lineBand, gain_row(Sh, blockIdx.x));
+}
+
 // pcmfile.py:163-172
 __global__ void pcm16_kernel(int64_t n, const double* __restrict__ x, short* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -230,6 +326,50 @@ hipError_t launch_decode_mix(const DevShape& F, const DevShape* R, int64_t nWork
     if (R->halfN <= 0 || R->halfN > F.halfN) return hipErrorInvalidValue;
     hipLaunchKernelGGL(decode_reduced_mix_kernel, dim3((unsigned)nWorkgroups), dim3(kThreads), mdct_generic_lds_bytes(*R), st, *R,
                        F.bandOfLine, F.nBands, F.halfN, F.nScaleBits, joint, mixSel, nPairs, oscale, msSwitch, scaleFactor,
+                       bitAlloc, mantissa, outOffset, out);
+    return hipGetLastError();
+}
+
+// launch_decode / launch_decode_reduced (R null: full rate) with band gains: one gain per line of the block's full shape F
+// before the inverse transform.  lineBand [F.halfN] (kNoLineBand: the line is left alone), gain [units][nBands],
+// unit [nBlocks] (a slot's row of gain, indexed as outOffset), all DEVICE.
+hipError_t launch_decode_shaped(const DevShape& F, const DevShape* R, const unsigned short* lineBand, const double* gain,
+                                const int* unit, int nBands, int64_t nBlocks, int nStreams, const int* oscale, const int* msSwitch,
+                                const int* scaleFactor, const int* bitAlloc, const int* mantissa, const int64_t* outOffset,
+                                double* outL, double* outR, hipStream_t st) {
+    if (nBlocks <= 0) return hipSuccess;
+    if (!lineBand || !gain || !unit || nBands < 1) return hipErrorInvalidValue;
+    const ShapeDev Sh{lineBand, gain, unit, nBands};
+    if (!R) {
+        hipLaunchKernelGGL(decode_shaped_kernel, dim3((unsigned)(nBlocks * nStreams)), dim3(kThreads), mdct_generic_lds_bytes(F), st,
+                           F, Sh, nStreams, oscale, msSwitch, scaleFactor, bitAlloc, mantissa, outOffset, outL, outR);
+        return hipGetLastError();
+    }
+    if (R->halfN <= 0 || R->halfN > F.halfN) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(decode_reduced_shaped_kernel, dim3((unsigned)(nBlocks * nStreams)), dim3(kThreads), mdct_generic_lds_bytes(*R),
+                       st, *R, Sh, F.bandOfLine, F.nBands, F.halfN, F.nScaleBits, nStreams, oscale, msSwitch, scaleFactor, bitAlloc,
+                       mantissa, outOffset, outL, outR);
+    return hipGetLastError();
+}
+
+// launch_decode_mix with band gains; unit [nWorkgroups], per workgroup as outOffset is.
+hipError_t launch_decode_shaped_mix(const DevShape& F, const DevShape* R, const unsigned short* lineBand, const double* gain,
+                                    const int* unit, int nBands, int64_t nWorkgroups, int joint, int mixSel, int64_t nPairs,
+                                    const int* oscale, const int* msSwitch, const int* scaleFactor, const int* bitAlloc,
+                                    const int* mantissa, const int64_t* outOffset, double* out, hipStream_t st) {
+    if (nWorkgroups <= 0) return hipSuccess;
+    if (mixSel < 0 || mixSel > kSelMid || nPairs < 0 || nPairs > nWorkgroups || (joint && nPairs) || nWorkgroups > 0x7fffffffLL)
+        return hipErrorInvalidValue;
+    if (!lineBand || !gain || !unit || nBands < 1) return hipErrorInvalidValue;
+    const ShapeDev Sh{lineBand, gain, unit, nBands};
+    if (!R) {
+        hipLaunchKernelGGL(decode_shaped_mix_kernel, dim3((unsigned)nWorkgroups), dim3(kThreads), mdct_generic_lds_bytes(F), st, F, Sh,
+                           joint, mixSel, nPairs, oscale, msSwitch, scaleFactor, bitAlloc, mantissa, outOffset, out);
+        return hipGetLastError();
+    }
+    if (R->halfN <= 0 || R->halfN > F.halfN) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(decode_reduced_shaped_mix_kernel, dim3((unsigned)nWorkgroups), dim3(kThreads), mdct_generic_lds_bytes(*R), st,
+                       *R, Sh, F.bandOfLine, F.nBands, F.halfN, F.nScaleBits, joint, mixSel, nPairs, oscale, msSwitch, scaleFactor,
                        bitAlloc, mantissa, outOffset, out);
     return hipGetLastError();
 }

@@ -41,6 +41,17 @@ float64 planes in one call, every bit defined, no per-term window written:
         x = store.decode_window_sum(np.stack([speech, noise], 1), np.stack([s_starts, n_starts], 1),
                                     np.stack([np.ones_like(g), g], 1), 48000, dtype=torch.float32)
 
+band_gains= (mrc_pac_store_decode_window_shaped) changes the spectrum of a crop, or of a term of a sum, where it is cheapest: one
+multiplication per decoded MDCT line, between the dequantiser and the inverse transform that runs anyway -- a telephone band
+for the speech term, an EQ tilt per item, frequency masks, a per-item low-pass.  Per-line gains on a lapped transform are not
+an LTI filter: smooth curves are clean, a brick-wall edge leaves a small aliasing residue near the edge frequency:
+
+        tilt = gains_from_db(np.linspace(3.0, -9.0, 25))                       # one row for every item, the codec's 25 bands
+        x = store.decode_window(files, starts, 48000, dtype=torch.float32, band_gains=tilt)
+        masks = band_mask_gains(len(files), 25, np.random.default_rng(0), n_masks=2, max_width=4)
+        y = store.decode_window(files, starts, 48000, dtype=torch.float32, band_gains=masks)
+        z = store.decode_window(files, starts, 48000, band_gains=[0.0, 1.0, 0.0], band_edges_hz=[0, 300, 3400, 24000])   # telephone band
+
 band_energy_window (mrc_pac_store_band_energy_window) is the time-frequency feature that usually follows a crop, taken from
 the same sums split by frequency band and laid on a frame grid -- the coded file already is a time-frequency representation:
 
@@ -193,6 +204,75 @@ def check_band_edges(band_edges_hz, what="band_energy_window"):
     return edges
 
 
+def check_band_gains(band_gains, unit_shape, n_bands, what="decode_window", band_edges_hz=None):
+    """band_gains of decode_window / decode_window_sum -> float64 [units][n_bands], contiguous (None: None), else ValueError:
+    unit_shape is the shape of the call's units ((n,) items, or the shape of decode_window_sum's files), band_gains that shape
+    plus a last axis [n_bands], or [n_bands] alone for every unit; numbers, finite (zero and negative gains are allowed).
+    band_edges_hz is looked at only to refuse it without band_gains."""
+    if band_gains is None:
+        if band_edges_hz is not None:
+            raise ValueError("%s: band_edges_hz is given without band_gains" % what)
+        return None
+    unit_shape = tuple(int(v) for v in unit_shape)
+    try:
+        g = np.asarray(band_gains)
+        if g.dtype == object or g.dtype.kind not in "fiu":
+            raise TypeError
+        g = g.astype(np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("%s: band_gains must be numbers, got %r" % (what, band_gains))
+    if g.shape == (n_bands,):
+        g = np.broadcast_to(g, unit_shape + (n_bands,))
+    if g.shape != unit_shape + (n_bands,):
+        raise ValueError("%s: band_gains must have shape %s or (%d,) (%d bands), got %s"
+                         % (what, unit_shape + (n_bands,), n_bands, n_bands, np.shape(band_gains)))
+    g = np.ascontiguousarray(g.reshape(-1, n_bands))
+    bad = np.argwhere(~np.isfinite(g))
+    if bad.size:
+        raise ValueError("%s: band_gains must be finite, got %r at unit %d, band %d"
+                         % (what, float(g[tuple(bad[0])]), int(bad[0][0]), int(bad[0][1])))
+    return g
+
+
+def gains_from_db(db):
+    """decibels -> float64 factors 10^(db / 20), any shape: -inf gives 0.0; +inf and NaN are ValueErrors.  No handle, no GPU."""
+    try:
+        d = np.asarray(db, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("gains_from_db: db must be numbers, got %r" % (db,))
+    if np.any(np.isnan(d)) or np.any(d == np.inf):
+        raise ValueError("gains_from_db: db must be finite or -inf, got %r" % (db,))
+    with np.errstate(over="raise"):
+        try:
+            return np.where(np.isneginf(d), 0.0, 10.0 ** (np.where(np.isneginf(d), 0.0, d) / 20.0))
+        except FloatingPointError:
+            raise ValueError("gains_from_db: 10^(db / 20) overflows for %r" % (db,))
+
+
+def band_mask_gains(n_items, n_bands, rng, n_masks=1, max_width=8, floor=0.0):
+    """SpecAugment-style frequency masks -> float64 [n_items][n_bands] of ones in which, per item, n_masks runs of bands are set
+    to `floor`: mask j of item i has width = rng.integers(0, min(max_width, n_bands) + 1) bands from first =
+    rng.integers(0, n_bands - width + 1), the draws made item by item, mask by mask, width before first -- reproducible from rng
+    (a numpy.random.Generator) alone.  Runs may overlap; a width of 0 masks nothing.  No handle, no GPU."""
+    for name, v, least in (("n_items", n_items, 0), ("n_bands", n_bands, 1), ("n_masks", n_masks, 0), ("max_width", max_width, 0)):
+        if not _is_int(v) or int(v) < least:
+            raise ValueError("band_mask_gains: %s must be an int >= %d, got %r" % (name, least, v))
+    if int(n_bands) > MAX_BANDS:
+        raise ValueError("band_mask_gains: n_bands must not exceed %d, got %r" % (MAX_BANDS, n_bands))
+    if isinstance(floor, bool) or not isinstance(floor, (int, float, np.integer, np.floating)) or not np.isfinite(floor):
+        raise ValueError("band_mask_gains: floor must be a finite number, got %r" % (floor,))
+    if not isinstance(rng, np.random.Generator):
+        raise ValueError("band_mask_gains: rng must be a numpy.random.Generator, got %r" % (rng,))
+    n_items, n_bands, widest = int(n_items), int(n_bands), min(int(max_width), int(n_bands))
+    g = np.ones((n_items, n_bands), np.float64)
+    for i in range(n_items):
+        for _ in range(int(n_masks)):
+            width = int(rng.integers(0, widest + 1))
+            first = int(rng.integers(0, n_bands - width + 1))
+            g[i, first:first + width] = float(floor)
+    return g
+
+
 def band_line_ranges(sample_rate, a, b, band_edges_hz):
     """mrc_band_line_ranges -> int32 [bands + 1]: band q of a block of shape (a, b) holds MDCT lines [r[q], r[q + 1]), line k
     lying at (k + 0.5) * ((sample_rate / ((a + b) / 2)) / 2.).  No handle, no GPU.  MrcError where the library refuses."""
@@ -299,8 +379,17 @@ class PacStore:
             stream = torch.cuda.current_stream(dev).cuda_stream
         return fmt, channels, out, stream
 
+    def _band_args(self, what, band_gains, band_edges_hz, unit_shape):
+        """band_gains / band_edges_hz of a window call -> None, or (edges float64 [n_bands + 1], gains float64 [units][n_bands]);
+        ValueError as check_band_edges and check_band_gains raise it"""
+        if band_gains is None:
+            check_band_gains(None, unit_shape, 0, what, band_edges_hz)
+            return None
+        edges = critical_band_edges(self._handle.cfg.sample_rate) if band_edges_hz is None else check_band_edges(band_edges_hz, what)
+        return edges, check_band_gains(band_gains, unit_shape, edges.size - 1, what)
+
     def decode_window(self, files, starts, window, channels=None, dtype=None, out=None, stream=None, rate_divisor=1,
-                      mix=None, resample=None):
+                      mix=None, resample=None, band_gains=None, band_edges_hz=None):
         """Item i = samples [starts[i], starts[i] + window) of file files[i], zeros where that leaves the file (starts may be
         negative or past the end) -> a torch tensor [n][channels][window] on the handle's device.  dtype: torch.int16 (the
         default: the codes Handle.decode_pac_pcm16 writes, bit for bit), torch.float64 (the overlap-added signal before the
@@ -324,7 +413,20 @@ class PacStore:
         samples, output n at time n down / up of the rate_divisor signal (n_samples_resampled of them lie inside a file);
         torch.float64 is the fold defined in the header, bit for bit, the other dtypes its conversions.  A ratio of 1 after
         reduction is the call without resample.  A ratio outside [1 / 8, 8], terms above 1024 after reduction, zeros outside
-        1..64 and rolloff outside [0.5, 1] are ValueErrors, before any library call."""
+        1..64 and rolloff outside [0.5, 1] are ValueErrors, before any library call.
+        band_gains: None, or float64 [n][n_bands] ([n_bands]: the same row for every item): the spectrum of item i changed on its
+        MDCT lines (mrc_pac_store_decode_window_shaped, as one-term rows at gain 1.0) -- every decoded line whose frequency lies
+        in band q = [band_edges_hz[q], band_edges_hz[q + 1]) is multiplied once by band_gains[i][q] before the inverse
+        transform that runs anyway; lines outside every band are left alone; all channels of an item share its row.  Zero
+        and negative gains are allowed (a telephone band, an EQ tilt from gains_from_db, masks from band_mask_gains).
+        band_edges_hz: 2 to 257 increasing frequencies from 0 up; None: critical_band_edges(sample_rate), the codec's own
+        bands.  The line frequencies are the full-rate block's at every rate_divisor (bands above the reduced Nyquist are
+        ignored), and everything else of the call -- mix, resample, dtype, zeros outside the file -- is unchanged: gains of
+        1.0 give the bits of the call without band_gains, gains that are all one power of two that multiple of its float64
+        window.  Not an LTI filter: where neighbouring lines get different gains the time-domain aliasing of adjacent blocks
+        no longer cancels exactly -- smooth gain curves are clean, a brick-wall edge leaves a small aliasing residue near the
+        edge frequency (DESIGN.md has figures).  A wrong shape, values that are not finite numbers and band_edges_hz without
+        band_gains are ValueErrors, before any library call."""
         rate_divisor = check_rate_divisor(rate_divisor)
         mix = check_mix(mix, channels)
         resample = check_resample(resample)
@@ -335,7 +437,12 @@ class PacStore:
         if files.shape != starts.shape:
             raise ValueError("decode_window: one start per file index (%d files, %d starts)" % (files.size, starts.size))
         n, window = files.size, int(window)
+        bands = self._band_args("decode_window", band_gains, band_edges_hz, (n,))
         fmt, channels, out, stream = self._window_out("decode_window", n, files, window, channels, dtype, out, stream)
+        if bands is not None:
+            offsets, ones = np.arange(n + 1, dtype=np.int64), np.ones(n, np.float64)
+            self._shaped(rate_divisor, mix, resample, bands, n, offsets, files, starts, ones, window, channels, fmt, out, stream)
+            return out
         tail = (n, files.ctypes.data, starts.ctypes.data, window, channels, fmt, out.data_ptr() if out.numel() else None,
                 stream or None)
         if resample is not None:
@@ -349,8 +456,18 @@ class PacStore:
             self._handle._check(lib.mrc_pac_store_decode_window_reduced(self._s, rate_divisor, *tail))
         return out
 
+    def _shaped(self, rate_divisor, mix, resample, bands, n, offsets, files, starts, gains, window, channels, fmt, out, stream):
+        """mrc_pac_store_decode_window_shaped over checked arguments; bands = (edges, gains [terms][n_bands])"""
+        up, down, zeros, rolloff = resample if resample is not None else (1, 1, RESAMPLE_ZEROS, RESAMPLE_ROLLOFF)
+        pad = lambda a: a.ctypes.data if a.size else None
+        edges, band_gains = bands
+        self._handle._check(lib.mrc_pac_store_decode_window_shaped(
+            self._s, rate_divisor, _lib.MRC_MIX_EACH if mix is None else mix, up, down, zeros, rolloff, edges.size - 1,
+            edges.ctypes.data, pad(band_gains), n, offsets.ctypes.data, pad(files), pad(starts), pad(gains), window, channels, fmt,
+            out.data_ptr() if out.numel() else None, stream or None))
+
     def decode_window_sum(self, files, starts, gains, window, item_offsets=None, channels=None, dtype=None, out=None, stream=None,
-                          rate_divisor=1, mix=None, resample=None):
+                          rate_divisor=1, mix=None, resample=None, band_gains=None, band_edges_hz=None):
         """mrc_pac_store_decode_window_sum -> a torch tensor [n][channels][window] on the handle's device: item i is the sum
         over its terms k, IN THE ORDER GIVEN, of gains[k] * (the float64 window decode_window gives for files[k], starts[k]
         at this rate_divisor, mix and resample), folded from +0.0 with every product rounded once, then added -- speech over
@@ -362,7 +479,11 @@ class PacStore:
         .gains_to give factors without decoding anything.  A one-term item with gain 1.0 is decode_window's window.
         window, channels, dtype, out, stream, rate_divisor, mix, resample: as decode_window's (with resample, starts and window
         count output samples).  Shapes that do not agree, offsets that do not start at 0 or that decrease and gains that are
-        not finite are ValueErrors, like decode_window's argument errors, before any library call."""
+        not finite are ValueErrors, like decode_window's argument errors, before any library call.
+        band_gains, band_edges_hz: as decode_window's, PER TERM: band_gains has the shape of files plus a last axis [n_bands]
+        ([n_bands] alone: every term), and term k's lines are multiplied by its row before its inverse transform
+        (mrc_pac_store_decode_window_shaped) -- a telephone band for the speech term and none for the noise is a row of gains
+        and a row of ones.  The fold over the terms is unchanged."""
         what = "decode_window_sum"
         rate_divisor = check_rate_divisor(rate_divisor, what)
         mix = check_mix(mix, channels, what)
@@ -374,6 +495,7 @@ class PacStore:
         if not (files.shape == starts.shape == gains.shape):
             raise ValueError("%s: files, starts and gains must have one shape, got %s, %s and %s"
                              % (what, files.shape, starts.shape, gains.shape))
+        bands = self._band_args(what, band_gains, band_edges_hz, files.shape)
         if item_offsets is None:
             if files.ndim != 2:
                 raise ValueError("%s: files, starts and gains must be [n][K], or 1-D with item_offsets; got shape %s" % (what, files.shape))
@@ -392,6 +514,9 @@ class PacStore:
             raise ValueError("%s: gains must be finite, got %r at term %d" % (what, float(gains[bad[0]]), int(bad[0])))
         n, window = offsets.size - 1, int(window)
         fmt, channels, out, stream = self._window_out(what, n, files, window, channels, dtype, out, stream)
+        if bands is not None:
+            self._shaped(rate_divisor, mix, resample, bands, n, offsets, files, starts, gains, window, channels, fmt, out, stream)
+            return out
         up, down, zeros, rolloff = resample if resample is not None else (1, 1, RESAMPLE_ZEROS, RESAMPLE_ROLLOFF)
         pad = lambda a: a.ctypes.data if a.size else None
         self._handle._check(lib.mrc_pac_store_decode_window_sum(
