@@ -1181,6 +1181,52 @@ int mrc_pac_store_decode_window_shaped(mrc_pac_store* s, int rate_divisor, int m
                                        const int64_t* start /*[n_terms]*/, const double* gain /*[n_terms]*/, int64_t window,
                                        int n_channels_out, int format, void* out /* DEVICE [n_items][n_channels_out][window] */,
                                        void* stream);
+/* mrc_pac_store_decode_window_speeds: the rows of mrc_pac_store_decode_window_shaped (rows of terms, optional band gains) in
+ * which every term is read at a ratio of its own, chosen from a short list the call carries -- speed perturbation (each
+ * utterance at 0.9x, 1.0x or 1.1x, drawn per item) in one call, and mixtures whose speech term is sped up and whose noise term
+ * is not.  Term k is read at ratio r = ratio_of[k]: ratio_up[r] / ratio_down[r] of the rate 1 / rate_divisor; zeros and
+ * rolloff are shared by every non-unit ratio of the list.
+ * One term's signal: v_k[c][t] is the MRC_WINDOW_F64 value the EXISTING call gives for (file[k], start[k]), channel c, sample
+ * t, at this rate_divisor and mix, made with that term's ratio.  A ratio that does not reduce to 1: that call is
+ * mrc_pac_store_decode_window_resampled with (ratio_up[r], ratio_down[r], zeros, rolloff).  A ratio that reduces to 1: it is the
+ * call without a filter, mrc_pac_store_decode_window_reduced under MRC_MIX_EACH and mrc_pac_store_decode_window_mix otherwise
+ * (zeros and rolloff are not looked at if every ratio is such).  With band gains (n_bands > 0) v_k is the value of
+ * mrc_pac_store_decode_window_shaped's one-term row at gain 1.0 with band_gain's row k and that ratio.  start[k] and window
+ * count output samples AT THE TERM'S OWN RATIO, exactly as in those calls: a term at 10 / 11 of the rate (speed 1.1) covers
+ * 1.1 times the source time that a unit term of the same window covers.
+ * The row is mrc_pac_store_decode_window_sum's fold: out[i][c][t] = the left fold from +0.0, over the item's terms in the order
+ * given, of gain[k] * v_k[c][t], every product rounded once, then added (__dmul_rn, __dadd_rn); MRC_WINDOW_F32 and
+ * MRC_WINDOW_PCM16 are conversions of that sum; channel map, zeros outside the file and damage rules are unchanged.  Hence,
+ * bit for bit: a one-term row at gain 1.0 equals the existing single-ratio call in all three formats; a call whose terms all
+ * name one ratio equals mrc_pac_store_decode_window_sum / _shaped with that ratio, whatever else the list holds; nothing
+ * depends on the launch grid, on the order of the items, on what shares the call or on the slab size.
+ * n_bands == 0: no band gains, edge_hz and band_gain must be NULL.
+ * MRC_ERR_INVALID naming the argument, before any device work and with `out` untouched: every refusal of
+ * mrc_pac_store_decode_window_shaped (of mrc_pac_store_decode_window_sum when n_bands == 0); n_bands == 0 with edge_hz or
+ * band_gain not NULL; n_ratios outside 1..MRC_MAX_STORE_RATIOS; ratio_up, ratio_down or ratio_of NULL with terms present; for
+ * each ratio that does not reduce to 1, mrc_resample_taps' own words behind "ratio <index>: " -- the list is checked wherever
+ * ratio_up and ratio_down are given, also in a call without terms; ratio_of[k] outside the list (the term is named).  n_items == 0 or window == 0: MRC_OK, nothing written.
+ * Work follows the spans, per term: a unit-ratio term parses the blocks of [start, start + window), any other the blocks of
+ * the intermediate span its filter reads; the chunks parsed are the sum of the existing calls' over the terms.
+ * Slabs: every term's planes have ONE length per call, S + 4 n_mdct_lines / rate_divisor, S the largest span bound among the
+ * ratios that the call's terms name (window for the unit ratio, ceil((window - 1) down / up) + 2 W otherwise); a slab is a run
+ * of whole rows whose terms, EACH COUNTED AT S, sum to at most MRC_OPT_STORE_SLAB_SAMPLES (one row at least; 0: one slab), and
+ * of at most (2^31 - 1) / (n_channels_out * ceil(window / 256)) rows.  Per slab the terms' ratio indices and the table of the
+ * ratios go up with the plan: no further copy, no further synchronisation.
+ * mrc_pac_store_stats then describes this call: stats = chunks parsed over all terms, synthesis launches, slabs, plan bytes
+ * uploaded (the indices and the table included); ms[3] is resample_multi_sum_out_kernel's time.
+ * All filters of the list are resolved before any is used; the handle's cache of filters (16) is emptied before the first if
+ * the missing ones would not fit, never between two of one call. */
+#define MRC_MAX_STORE_RATIOS 8
+int mrc_pac_store_decode_window_speeds(mrc_pac_store* s, int rate_divisor, int mix, int n_ratios,
+                                       const int32_t* ratio_up /*[n_ratios]*/, const int32_t* ratio_down /*[n_ratios]*/, int zeros,
+                                       double rolloff, int n_bands /* 0: no band gains */, const double* edge_hz /*[n_bands+1]*/,
+                                       const double* band_gain /*[n_terms][n_bands]*/, int64_t n_items,
+                                       const int64_t* term_offset /*[n_items+1]*/, const int64_t* file /*[n_terms]*/,
+                                       const int64_t* start /*[n_terms]*/, const double* gain /*[n_terms]*/,
+                                       const int32_t* ratio_of /*[n_terms]: index into the list*/, int64_t window,
+                                       int n_channels_out, int format, void* out /* DEVICE [n_items][n_channels_out][window] */,
+                                       void* stream);
 
 /* Per-stage device time of the most recent timed call when timing is enabled (hipEvents on the launch stream; the call
  * then synchronises).  Timed: mrc_dev_encode / mrc_dev_encode_ex and mrc_encode_mono / mrc_encode_joint (the _blocks

@@ -243,6 +243,9 @@ def _load():
         "mrc_pac_store_decode_window_shaped": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
                                                          _f64p, _f64p, C.c_int64, _i64p, _i64p, _i64p, _f64p, C.c_int64, C.c_int,
                                                          C.c_int, C.c_void_p, C.c_void_p]),
+        "mrc_pac_store_decode_window_speeds": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, C.c_int, C.c_double,
+                                                         C.c_int, _f64p, _f64p, C.c_int64, _i64p, _i64p, _i64p, _f64p, _i32p,
+                                                         C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
         "mrc_pac_store_stats": (C.c_int, [C.c_void_p, _i64p, _f64p]),
     }
     for name, (res, args) in sig.items():

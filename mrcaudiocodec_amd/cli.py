@@ -45,6 +45,12 @@ the file's MDCT lines between LO and HI Hz by DB decibels (-inf: zero) before th
 (mrc_pac_store_decode_window_shaped): bands ascend and do not overlap, a gap stays at 0 dB.  Composes with --start, --samples,
 --rate-divisor, --mix, --sample-rate and --overlay (the overlay is left as it is); refused without -d and with --band-energies.
 Per-line gains are not an LTI filter: a brick-wall edge leaves a small aliasing residue near the edge frequency.
+At another speed:  python -m mrcaudiocodec_amd.cli -d in.pac out.wav --speed 11/10  plays the file NUM/DEN times as fast (pitch and
+tempo together, the speed perturbation of speech recipes) through the same store (mrc_pac_store_decode_window_speeds): the
+file is read at the output rate's ratio divided by the speed, the WAV's header carries the output rate unchanged, and
+--start / --samples count output samples -- the whole file is n_samples_resampled of the combined ratio.  Composes with
+--sample-rate, --rate-divisor, --mix, --band-gains-db and --overlay; the overlay stays at speed 1, in the same one call.
+Refused without -d and with --band-energies.
 Levels:  python -m mrcaudiocodec_amd.cli --levels a.pac [b.pac ...] [--levels-window N]  decodes nothing and writes nothing: per
 file one JSON line with its channels, samples, RMS level per channel (dB re full scale) and its loudest and quietest window of
 N samples (default one second) on the short-block grid with their starts, from the energies of the blocks' MDCT lines
@@ -545,7 +551,7 @@ def levels_of_files(pac_paths, window=None, device_id=0, rate_divisor=1, mix=Non
 
 
 BAND_ENERGIES_REFUSES = tuple(f for f in LEVELS_REFUSES if f not in ("src", "dst")) + ("--levels", "--levels-window", "--rate-divisor",
-                                                                                        "--band-gains-db")
+                                                                                        "--band-gains-db", "--speed")
 
 
 def check_band_energies_args(band_energies, hop, band_edges, given):
@@ -638,6 +644,23 @@ def check_band_gains_db_args(band_gains_db, decode):
     return np.array(edges, np.float64), gains_from_db(db)
 
 
+def check_speed_args(speed, decode):
+    """--speed as given (None: not given), "NUM/DEN" or "NUM" -> (num, den), positive ints, or None.  It plays a decode faster
+    or slower: refused without -d."""
+    if speed is None:
+        return None
+    if not decode:
+        raise ValueError("--speed plays a decode faster or slower: it needs -d")
+    try:
+        parts = str(speed).split("/")
+        num, den = (int(parts[0]), 1) if len(parts) == 1 else (int(parts[0]), int(parts[1]))
+        if len(parts) > 2 or num < 1 or den < 1:
+            raise ValueError
+    except ValueError:
+        raise ValueError("--speed: %r is not NUM/DEN, two positive whole numbers" % (speed,))
+    return num, den
+
+
 CODEC_SETTINGS = ("sample_rate", "n_mdct_lines", "n_scale_bits", "n_mant_size_bits")   # what a .pac header says of its codec
 
 
@@ -657,7 +680,7 @@ def _levels_of_mix(store, rate_divisor, mix):
 
 
 def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=1, mix=None, sample_rate=None, overlay=None,
-                    band_gains=None):
+                    band_gains=None, speed=None):
     """excerpt: None (the whole file, mrc_decode_pac_pcm16) or (start, samples): that many samples from sample `start` on
     (samples None: to the end of the file), decoded through a one-file PacStore -- only the blocks the excerpt overlaps are
     parsed and synthesised; what lies outside the file is silence.  rate_divisor 2 or 4: at that fraction of the sample rate,
@@ -672,6 +695,10 @@ def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=
     band_gains: None or (edges in Hz, gains) of check_band_gains_db_args: the file's MDCT lines multiplied band by band before
     the inverse transform (PacStore.decode_window(band_gains=)), through the store as well; the overlay is left as it is, and
     its level is set against the unshaped excerpt.
+    speed: None or (num, den): the file read num / den times as fast (PacStore.decode_window(speed_factors=)), through the store
+    as well: start and samples count output samples, the whole file is n_samples_resampled of the combined ratio, the WAV's
+    header carries the output rate unchanged; the overlay stays at speed 1, a second term of the same one call, its level set
+    against the stretch of source under the excerpt (PacStore.source_spans).
     -> int16 [nCh][samples] as written."""
     with open(pac_path, "rb") as fp:
         buf = fp.read()
@@ -697,8 +724,15 @@ def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=
         from .store import resample_plan
         rate_divisor, up, down = resample_plan(cfg.sample_rate, int(sample_rate))
         resample = None if up == down else (up, down)
-    if (rate_divisor != 1 or mix is not None or resample is not None or overlay is not None or band_gains is not None) \
-            and excerpt is None:
+    ratio = None
+    if speed is not None:
+        from .store import speed_ratios
+        try:
+            ratio = speed_ratios(resample, [speed])[0]
+        except ValueError as e:
+            raise ValueError("--speed: %s" % e)
+    if (rate_divisor != 1 or mix is not None or resample is not None or overlay is not None or band_gains is not None
+            or speed is not None) and excerpt is None:
         excerpt = (0, None)
     h = Handle(sample_rate=cfg.sample_rate, n_mdct_lines=cfg.n_mdct_lines, n_scale_bits=cfg.n_scale_bits,
                n_mant_size_bits=cfg.n_mant_size_bits, device_id=device_id)
@@ -710,9 +744,12 @@ def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=
             with PacStore(h, bufs) as store:
                 start, samples = excerpt
                 if samples is None:
-                    n = store.n_samples_at(rate_divisor) if resample is None else store.n_samples_resampled(*resample, rate_divisor)
+                    n = store.n_samples_resampled(*ratio, rate_divisor) if ratio is not None else \
+                        store.n_samples_at(rate_divisor) if resample is None else store.n_samples_resampled(*resample, rate_divisor)
                     samples = max(0, int(n[0]) - start)
                 shaped = {} if band_gains is None else dict(band_edges_hz=band_gains[0])
+                if speed is not None:                    # the file at its speed; the overlay, a second term, at speed 1
+                    shaped.update(speed_factors=[speed, (1, 1)], speed_index=[0] if overlay is None else [[0, 1]])
                 if overlay is None:
                     if band_gains is not None:
                         shaped["band_gains"] = band_gains[1]
@@ -721,9 +758,12 @@ def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=
                     # the levels live at the rate divisor's rate: the excerpt's span there (the whole of it, rounded outwards)
                     up, down = resample if resample is not None else (1, 1)
                     at = lambda v: v * down // up
-                    span = max(1, -(-(start + samples) * down // up) - at(start))
+                    first, span = at(start), max(1, -(-(start + samples) * down // up) - at(start))
+                    if ratio is not None:                # the stretch of source under the sped-up excerpt
+                        first, span = (int(v[0]) for v in store.source_spans([start], samples, [ratio], [0], rate_divisor))
+                        span = max(1, span)
                     gain = float(_levels_of_mix(store, rate_divisor, mix).gains_for_snr(
-                        overlay[1], [0], [at(start)], [1], [at(overlay[2])], span)[0]) if samples else 1.0
+                        overlay[1], [0], [first], [1], [at(overlay[2])], span)[0]) if samples else 1.0
                     print("overlay: %s at a factor of %.9g (%g dB under the excerpt)" % (overlay[0], gain, overlay[1]))
                     if band_gains is not None:           # (the overlay's row: ones)
                         shaped["band_gains"] = np.stack([band_gains[1], np.ones_like(band_gains[1])])[None]
@@ -871,6 +911,10 @@ def main(argv=None):
                          "inverse transform, e.g. 0-300:-inf,3400-24000:-inf for a telephone band; bands ascend and do not "
                          "overlap, gaps stay at 0 dB; composes with --start, --samples, --rate-divisor, --mix, --sample-rate and "
                          "--overlay (the overlay is left as it is)")
+    ap.add_argument("--speed", default=None, metavar="NUM/DEN",
+                    help="with -d: play the file NUM/DEN times as fast (11/10: speed perturbation) through the resident store; the "
+                         "WAV's rate is unchanged, --start / --samples count output samples; composes with --sample-rate, "
+                         "--rate-divisor, --mix, --band-gains-db and --overlay (the overlay stays at speed 1)")
     ap.add_argument("--levels", nargs="+", default=None, metavar="PAC",
                     help="no src, no dst: print one JSON line per .pac file with its channels, samples, RMS level per channel "
                          "(dB re full scale) and its loudest and quietest window on the short-block grid, from the block "
@@ -897,7 +941,8 @@ def main(argv=None):
             "--sample-rate": a.sample_rate is not None}
         bands = check_band_energies_args(a.band_energies, a.hop, a.band_edges, dict(
             given, **{"--levels": a.levels is not None, "--levels-window": a.levels_window is not None,
-                      "--rate-divisor": a.rate_divisor is not None, "--band-gains-db": a.band_gains_db is not None}))
+                      "--rate-divisor": a.rate_divisor is not None, "--band-gains-db": a.band_gains_db is not None,
+                      "--speed": a.speed is not None}))
         levels = check_levels_args(a.levels, a.levels_window, given)
         if levels is None and (a.src is None or a.dst is None):
             raise ValueError("the following arguments are required: src, dst")
@@ -907,6 +952,7 @@ def main(argv=None):
         sample_rate = check_sample_rate_args(a.sample_rate, a.decode, a.rate_divisor is not None)
         overlay = check_overlay_args(a.overlay, a.snr_db, a.overlay_start, a.decode)
         band_gains = check_band_gains_db_args(a.band_gains_db, a.decode)
+        speed = check_speed_args(a.speed, a.decode)
         if levels is not None:
             from .store import check_levels_mix
             check_levels_mix(mix, "--mix")
@@ -969,7 +1015,7 @@ def main(argv=None):
         return
     if a.decode:
         try:
-            pcm = decode_pac_file(a.src, a.dst, a.device, excerpt, rate_divisor, mix, sample_rate, overlay, band_gains)
+            pcm = decode_pac_file(a.src, a.dst, a.device, excerpt, rate_divisor, mix, sample_rate, overlay, band_gains, speed)
         except ValueError as e:
             ap.error(str(e))
         print("%s: %d channels x %d samples" % (a.dst, pcm.shape[0], pcm.shape[1]))

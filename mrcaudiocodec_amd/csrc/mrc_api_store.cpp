@@ -55,6 +55,11 @@
 // workgroup laid out as the block offsets are; the shaped launches (mrc_kernels_decode.hip) multiply once per line between
 // the dequantiser and the inverse transform.  Calls without gains never come here.
 //
+// decode_window_speeds, those rows with a ratio per term: decode_windows with a list of filters beside the rows.  Each term's
+// span is its own ratio's; the planes have one length per call, the largest span among the ratios named plus 4 L, so the
+// synthesis launches and their second plane at x + planeLen stay as they are.  The terms' ratio indices and the table of
+// the ratios (SpeedRatio) ride in the slab's staging copy; SumTerm and WindowItem are the other calls', unchanged.
+//
 // block_energy, ((a + b) / D) * the sum of squares of a block's first 1 / D decoded lines, per channel or for the mid, for
 // every block of the selected files: the same slab plan (stage_slab, parse_slab) over runs of whole blocks instead of the
 // blocks of windows, then block_energy_kernel per group (mrc_kernels_store.hip) in place of planes, synthesis and output.
@@ -83,6 +88,7 @@ const char* const kWinMix = "mrc_pac_store_decode_window_mix";
 const char* const kWinResampled = "mrc_pac_store_decode_window_resampled";
 const char* const kWinSum = "mrc_pac_store_decode_window_sum";
 const char* const kWinShaped = "mrc_pac_store_decode_window_shaped";
+const char* const kWinSpeeds = "mrc_pac_store_decode_window_speeds";
 constexpr int kNoMix = -1;                           // decode_windows: every channel of a file into a plane of its own
 
 int store_alive(mrc_pac_store* s, const char* fn) {
@@ -293,11 +299,30 @@ int get_resample_table(mrc_handle* h, const ResampleSpec& r, const ResampleTable
         int g = 1;
         resample_lds_layout(r.up, r.down, &g, &t.skew);
         t.evenOdd = g == 2;
+        t.skewNatural = resample_lds_cycles(r.up, r.down, 1, 1) < resample_lds_cycles(r.up, r.down, 1, 0);
         MRC_HIP(h, t.taps.reserve(sizeof(double) * n));
         MRC_HIP(h, hipMemcpy(t.taps.p, byTap.data(), sizeof(double) * n, hipMemcpyHostToDevice));
         it = tables.emplace(key, std::move(t)).first;
     }
     *out = &it->second;
+    return MRC_OK;
+}
+
+// mrc_pac_store_decode_window_speeds: the tables of all the call's filters, none evicted while a later one is resolved -- the
+// cache is emptied BEFORE the first when the missing ones would not fit beside what it holds (get_resample_table then never
+// finds it full)
+int get_resample_tables(mrc_handle* h, int n, const ResampleSpec* r, const ResampleTable** out) {
+    auto& tables = h->store.resample;
+    std::map<std::tuple<int, int, int, double>, int> missing;
+    for (int i = 0; i < n; ++i) {
+        const auto key = std::make_tuple(r[i].up, r[i].down, r[i].zeros, r[i].rolloff);
+        if (r[i].W && tables.find(key) == tables.end()) missing[key] = 1;
+    }
+    if (tables.size() + missing.size() > 16) tables.clear();
+    for (int i = 0; i < n; ++i) {
+        out[i] = nullptr;
+        if (r[i].W) MRC_TRY(get_resample_table(h, r[i], &out[i]));
+    }
     return MRC_OK;
 }
 
@@ -312,6 +337,11 @@ int get_resample_table(mrc_handle* h, const ResampleSpec& r, const ResampleTable
 // UNIT, (file[k], start[k]) -- is then a TERM of row i, k in [termOffset[i], termOffset[i + 1]), n_items the number of terms;
 // a slab is a run of whole rows, counted by its terms' spans, and sum_out_kernel / resample_sum_out_kernel fold a row's
 // terms with their gains where the other calls copy or fold one unit per row.  Without it a row is its one unit.
+// speeds (mrc_pac_store_decode_window_speeds; with sum, without rs) null or the ratios of that call: term k is planned over the
+// span of ITS ratio -- the unit ratio's is [start, start + window), any other's the intermediate span above with that ratio's
+// up, down and W -- into planes of ONE length, the largest span bound among the ratios the call's terms name plus 4 L, which a
+// slab counts each term at.  Per slab, in the one staging copy: the ratio index of every term and the table of the ratios
+// (SpeedRatio); resample_multi_sum_out_kernel folds.
 // shape (mrc_pac_store_decode_window_shaped) null or the band gains of that call, one row per unit: each needed block is then
 // synthesised by the shaped launches, its line k multiplied once by the unit's gain of the band that
 // band_line_ranges(sample rate, the block's FULL shape) puts it in, whatever D.  Per call: lineBand, a uint16 per line of each
@@ -322,6 +352,11 @@ struct SumSpec {
     const int64_t* termOffset;                               // [nRows + 1], checked by the caller
     const double* gain;                                      // [n_items]
 };
+struct SpeedSpec {
+    int nRatios;
+    ResampleSpec r[MRC_MAX_STORE_RATIOS];                    // reduced; W == 0: the unit ratio, no filter
+    const int32_t* ratioOf;                                  // [n_items], checked by the caller
+};
 struct ShapeSpec {
     int nBands;
     const double* bandGain;                                  // [n_items][nBands], checked by the caller
@@ -330,7 +365,7 @@ struct ShapeSpec {
 };
 int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, int64_t n_items, const int64_t* file, const int64_t* start,
                    int64_t window, int n_channels_out, int format, void* out, void* stream, const ResampleSpec* rs = nullptr,
-                   const SumSpec* sum = nullptr, const ShapeSpec* shape = nullptr) {
+                   const SumSpec* sum = nullptr, const ShapeSpec* shape = nullptr, const SpeedSpec* speeds = nullptr) {
     MRC_TRY(store_alive(s, fn));
     mrc_handle* h = s->h;
     const mrc_config& cfg = h->cfg;
@@ -368,7 +403,21 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
     const ResampleTable* table = nullptr;
     if (rs) MRC_TRY(get_resample_table(h, *rs, &table));
     const int64_t up = rs ? rs->up : 1, down = rs ? rs->down : 1, W = rs ? rs->W : 0;
-    const int64_t span = rs ? ((window - 1) * down + up - 1) / up + 2 * W : window;     // plane samples an item takes at most
+    int64_t span = rs ? ((window - 1) * down + up - 1) / up + 2 * W : window;           // plane samples an item takes at most
+    const ResampleTable* tables[MRC_MAX_STORE_RATIOS] = {};
+    SpeedRatio ratios[MRC_MAX_STORE_RATIOS] = {};
+    if (speeds) {                                            // every filter first, then the largest span among the ratios named
+        MRC_TRY(get_resample_tables(h, speeds->nRatios, speeds->r, tables));
+        for (int i = 0; i < speeds->nRatios; ++i) {
+            const ResampleSpec& r = speeds->r[i];
+            ratios[i] = SpeedRatio{r.up, r.down, r.W, r.W ? tables[i]->skewNatural : 0, r.W ? (const double*)tables[i]->taps.p : nullptr};
+        }
+        span = 0;
+        for (int64_t k = 0; k < n_items; ++k) {
+            const ResampleSpec& r = speeds->r[speeds->ratioOf[k]];
+            span = std::max<int64_t>(span, r.W ? ((window - 1) * r.down + r.up - 1) / r.up + 2 * r.W : window);
+        }
+    }
     const int64_t far = (int64_t)1 << 52;                    // an output start beyond it is beyond every file: (start + window) * down fits
     const int64_t planeLen = span + 4 * L, tiles = (window + 255) / 256;
     const int64_t slab = h->storeSlabSamples, itemCap = std::max<int64_t>(1, 0x7fffffffLL / (tiles * n_channels_out));
@@ -396,6 +445,11 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
                 if (at > far || at < -far) continue;
                 at = floor_div(at * down, up) - W + 1;
                 len = floor_div((start[u0 + k] + window - 1) * down, up) + W - at + 1;
+            } else if (speeds && speeds->r[speeds->ratioOf[u0 + k]].W) {
+                const ResampleSpec& r = speeds->r[speeds->ratioOf[u0 + k]];
+                if (at > far || at < -far) continue;
+                at = floor_div(at * r.down, r.up) - r.W + 1;
+                len = floor_div((start[u0 + k] + window - 1) * r.down, r.up) + r.W - at + 1;
             }
             needed_blocks(*s, cfg, D, k, f, at, len, &needs);
             if (needs.size() == before) continue;            // all zeros: its plane does not exist
@@ -411,7 +465,7 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
         // ---- staging (one H2D copy): plan | groups | block offsets | items (a sum: term records | the rows' term offsets);
         // a slot's offset is its block's place in the item's plane: the block's position in the file's padded plane, the
         // window's start at 2 L
-        size_t oOffs = 0, oItems = 0, oOutStart = 0, oLineBand = 0, oBandGain = 0, oUnit = 0;
+        size_t oOffs = 0, oItems = 0, oOutStart = 0, oLineBand = 0, oBandGain = 0, oUnit = 0, oRatioOf = 0, oRatios = 0;
         SlabStage S;
         MRC_TRY(stage_slab(
             s, fn, mix, needs, &pl, &S,
@@ -429,6 +483,10 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
                     oBandGain = lay->add<double>(nSlab * shape->nBands);
                     oUnit = lay->add<int>(pl.totalSlots);    // (indexed as the offsets are: a pair's workgroup, a single slot)
                 }
+                if (speeds) {
+                    oRatioOf = lay->add<int>(nSlab);
+                    oRatios = lay->add<SpeedRatio>(speeds->nRatios);
+                }
             },
             [&](const Need& n, int g, int slot, int ch, bool pair) {
                 const WindowItem& it = items[(size_t)n.item];
@@ -444,12 +502,18 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
         const UnpackGroupDev* gd = S.gd;
         if (sum) {
             SumTerm* terms = (SumTerm*)(S.pin + oItems);
-            for (int64_t k = 0; k < nSlab; ++k) terms[k] = SumTerm{items[(size_t)k], sum->gain[u0 + k], rs ? start[u0 + k] : 0};
+            const auto resampled = [&](int64_t k) { return rs || (speeds && speeds->r[speeds->ratioOf[u0 + k]].W); };
+            for (int64_t k = 0; k < nSlab; ++k) terms[k] = SumTerm{items[(size_t)k], sum->gain[u0 + k], resampled(k) ? start[u0 + k] : 0};
             long long* rowTerms = (long long*)(S.pin + oOutStart);
             for (int64_t r = 0; r <= nSlabRows; ++r) rowTerms[r] = sum->termOffset[first + r] - u0;
         } else {
             std::memcpy(S.pin + oItems, items.data(), sizeof(WindowItem) * nSlab);
             if (rs) std::memcpy(S.pin + oOutStart, start + first, sizeof(long long) * nSlab);
+        }
+        if (speeds) {
+            int* ratioOf = (int*)(S.pin + oRatioOf);
+            for (int64_t k = 0; k < nSlab; ++k) ratioOf[k] = speeds->ratioOf[u0 + k];
+            std::memcpy(S.pin + oRatios, ratios, sizeof(SpeedRatio) * (size_t)speeds->nRatios);
         }
         if (shape) {
             std::memcpy(S.pin + oLineBand, shape->lineBand.data(), sizeof(uint16_t) * shape->lineBand.size());
@@ -495,7 +559,12 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
             }));
         s->stats[1] += pl.groupsUsed();
         MRC_HIP(h, hipEventRecord(b.ev[4], st));
-        if (sum && rs)
+        if (speeds)
+            MRC_HIP(h, launch_resample_multi_sum_out(nSlabRows, (const SumTerm*)(din + oItems), (const int*)(din + oRatioOf),
+                                                     (const SpeedRatio*)(din + oRatios), ratios, speeds->nRatios,
+                                                     (const long long*)(din + oOutStart), window, n_channels_out, format, (int)L,
+                                                     planeLen, x, outSlab, st));
+        else if (sum && rs)
             MRC_HIP(h, launch_resample_sum_out(nSlabRows, (const SumTerm*)(din + oItems), (const long long*)(din + oOutStart), window,
                                                n_channels_out, format, (int)L, planeLen, rs->up, rs->down, rs->W, table->evenOdd,
                                                table->skew, (const double*)table->taps.p, x, outSlab, st));
@@ -906,10 +975,14 @@ namespace {
 
 // mrc_pac_store_decode_window_sum and, with bands (n_bands, edge_hz, band_gain: the caller's, unchecked),
 // mrc_pac_store_decode_window_shaped: the checks of the rows and of the bands, then decode_windows
+// ... and, with ratios (mrc_pac_store_decode_window_speeds: up and down are then not looked at), the checks of the list and of
+// the terms' indices into it
 struct BandArgs { int nBands; const double* edgeHz; const double* bandGain; };
+struct RatioArgs { int nRatios; const int32_t* up; const int32_t* down; const int32_t* ratioOf; };
 int decode_window_rows(mrc_pac_store* s, const char* fn, int rate_divisor, int mix, int up, int down, int zeros, double rolloff,
                        const BandArgs* bands, int64_t n_items, const int64_t* term_offset, const int64_t* file, const int64_t* start,
-                       const double* gain, int64_t window, int n_channels_out, int format, void* out, void* stream) {
+                       const double* gain, int64_t window, int n_channels_out, int format, void* out, void* stream,
+                       const RatioArgs* ratios = nullptr) {
     MRC_TRY(store_alive(s, fn));
     mrc_handle* h = s->h;
     const std::string w = fn;
@@ -918,6 +991,11 @@ int decode_window_rows(mrc_pac_store* s, const char* fn, int rate_divisor, int m
                                             " is not MRC_MIX_EACH (3), MRC_MIX_MID (0), MRC_MIX_LEFT (1) or MRC_MIX_RIGHT (2)");
     if (mix != MRC_MIX_EACH && n_channels_out != 1)
         return fail(h, MRC_ERR_INVALID, w + ": n_channels_out must be 1 under a mix of one channel");
+    if (ratios) {
+        up = down = 1;
+        if (ratios->nRatios < 1 || ratios->nRatios > MRC_MAX_STORE_RATIOS)
+            return fail(h, MRC_ERR_INVALID, w + ": n_ratios " + std::to_string(ratios->nRatios) + " is outside 1.." + std::to_string(MRC_MAX_STORE_RATIOS));
+    }
     if (up < 1 || down < 1)
         return fail(h, MRC_ERR_INVALID, w + ": " + (up < 1 ? "up " + std::to_string(up) : "down " + std::to_string(down)) + " is below 1");
     ResampleSpec r;
@@ -935,6 +1013,28 @@ int decode_window_rows(mrc_pac_store* s, const char* fn, int rate_divisor, int m
     if (nTerms > 0 && (!file || !start || !gain)) return fail(h, MRC_ERR_INVALID, w + ": file, start or gain is NULL");
     for (int64_t k = 0; k < nTerms; ++k)
         if (!std::isfinite(gain[k])) return fail(h, MRC_ERR_INVALID, w + ": gain of term " + std::to_string(k) + " is not finite");
+    SpeedSpec speeds;
+    if (ratios && nTerms > 0 && (!ratios->up || !ratios->down || !ratios->ratioOf))
+        return fail(h, MRC_ERR_INVALID, w + ": ratio_up, ratio_down or ratio_of is NULL");
+    if (ratios && ratios->up && ratios->down) {              // the list is checked wherever it is given, terms or none
+        speeds.nRatios = ratios->nRatios;
+        speeds.ratioOf = ratios->ratioOf;
+        for (int i = 0; i < ratios->nRatios; ++i) {
+            const int u = ratios->up[i], d = ratios->down[i];
+            const std::string at = "ratio " + std::to_string(i) + ": ";
+            if (u < 1 || d < 1)
+                return fail(h, MRC_ERR_INVALID, w + ": " + at + (u < 1 ? "up " + std::to_string(u) : "down " + std::to_string(d)) + " is not positive");
+            speeds.r[i] = ResampleSpec{1, 1, 0, 0.0, 0};     // (u == d: the unit ratio, zeros and rolloff are not looked at)
+            if (u != d) {
+                const std::string refusal = resample_spec(u, d, zeros, rolloff, &speeds.r[i]);
+                if (!refusal.empty()) return fail(h, MRC_ERR_INVALID, w + ": " + at + refusal);
+            }
+        }
+        for (int64_t k = 0; k < nTerms; ++k)                 // (terms present: ratio_of is not NULL)
+            if (ratios->ratioOf[k] < 0 || ratios->ratioOf[k] >= ratios->nRatios)
+                return fail(h, MRC_ERR_INVALID, w + ": ratio_of of term " + std::to_string(k) + " = " + std::to_string(ratios->ratioOf[k]) +
+                                                    " is outside the list of " + std::to_string(ratios->nRatios) + " ratios");
+    }
     ShapeSpec shape;
     if (bands) {
         const int nb = bands->nBands;
@@ -962,7 +1062,8 @@ int decode_window_rows(mrc_pac_store* s, const char* fn, int rate_divisor, int m
     }
     const SumSpec sum{n_items, term_offset, gain};
     return decode_windows(s, fn, rate_divisor, mix == MRC_MIX_EACH ? nullptr : &mix, nTerms, file, start, window, n_channels_out,
-                          format, out, stream, up != down ? &r : nullptr, &sum, bands ? &shape : nullptr);
+                          format, out, stream, up != down ? &r : nullptr, &sum, bands ? &shape : nullptr,
+                          ratios && nTerms > 0 ? &speeds : nullptr);
 }
 
 }  // namespace
@@ -983,6 +1084,20 @@ int mrc_pac_store_decode_window_shaped(mrc_pac_store* s, int rate_divisor, int m
     const BandArgs bands{n_bands, edge_hz, band_gain};
     return decode_window_rows(s, kWinShaped, rate_divisor, mix, up, down, zeros, rolloff, &bands, n_items, term_offset, file, start,
                               gain, window, n_channels_out, format, out, stream);
+}
+
+int mrc_pac_store_decode_window_speeds(mrc_pac_store* s, int rate_divisor, int mix, int n_ratios, const int32_t* ratio_up,
+                                       const int32_t* ratio_down, int zeros, double rolloff, int n_bands, const double* edge_hz,
+                                       const double* band_gain, int64_t n_items, const int64_t* term_offset, const int64_t* file,
+                                       const int64_t* start, const double* gain, const int32_t* ratio_of, int64_t window,
+                                       int n_channels_out, int format, void* out, void* stream) {
+    MRC_TRY(store_alive(s, kWinSpeeds));
+    if (n_bands == 0 && (edge_hz || band_gain))
+        return fail(s->h, MRC_ERR_INVALID, std::string(kWinSpeeds) + ": n_bands is 0 (no band gains) but edge_hz or band_gain is not NULL");
+    const BandArgs bands{n_bands, edge_hz, band_gain};
+    const RatioArgs ratios{n_ratios, ratio_up, ratio_down, ratio_of};
+    return decode_window_rows(s, kWinSpeeds, rate_divisor, mix, 1, 1, zeros, rolloff, n_bands == 0 ? nullptr : &bands, n_items, term_offset,
+                              file, start, gain, window, n_channels_out, format, out, stream, &ratios);
 }
 
 int mrc_pac_store_block_energy(mrc_pac_store* s, int rate_divisor, int mix, int64_t n_sel, const int64_t* file,

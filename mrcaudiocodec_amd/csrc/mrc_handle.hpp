@@ -232,6 +232,7 @@ struct NmrBufs {
 struct ResampleTable {               // the filter of one (up, down, zeros, rolloff), uploaded once (mrc_resample_taps.hpp)
     DevBuf taps;                     // [2 W][up]
     int W = 0, evenOdd = 0, skew = 0;   // half width; resample_out_kernel's LDS layout (resample_lds_layout)
+    int skewNatural = 0;             // the better skew under the natural lane map (resample_multi_sum_out_kernel)
 };
 struct StoreBufs {
     std::map<std::tuple<int, int, int, double>, ResampleTable> resample;   // mrc_pac_store_decode_window_resampled's filters

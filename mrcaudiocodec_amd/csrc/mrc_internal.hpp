@@ -299,6 +299,21 @@ hipError_t launch_sum_out(int64_t nRows, const SumTerm* terms, const long long* 
 hipError_t launch_resample_sum_out(int64_t nRows, const SumTerm* terms, const long long* termOffset, int64_t window, int nchOut,
                                    int format, int L, int64_t planeLen, int up, int down, int W, int evenOdd, int skew,
                                    const double* taps, const double* planes, void* out, hipStream_t st);
+// mrc_pac_store_decode_window_speeds: one ratio of the call's list as resample_multi_sum_out_kernel reads it.  W == 0: the
+// unit ratio -- no filter, the term's value is sum_out_kernel's.  Else up / down reduced, the half width, the run's LDS layout
+// under the natural lane map (skew: the better of resample_lds_cycles(up, down, 1, 0 | 1)) and the taps (device) [2 W][up].
+struct SpeedRatio {
+    int up, down, W, skew;
+    const double* taps;
+};
+// ... the same fold with the ratio read per term: term j is read at ratios[ratioOf[j]] (ratioOf [terms], ratios [nRatios]:
+// device; ratiosHost: the same records on the host, for the check of the run that the other resampling launchers make).
+// A term of a non-unit ratio keeps its planes as launch_resample_sum_out's terms do, one of the unit ratio as
+// launch_sum_out's; both kinds at the one planeLen.
+hipError_t launch_resample_multi_sum_out(int64_t nRows, const SumTerm* terms, const int* ratioOf, const SpeedRatio* ratios,
+                                         const SpeedRatio* ratiosHost, int nRatios, const long long* termOffset, int64_t window,
+                                         int nchOut, int format, int L, int64_t planeLen, const double* planes, void* out,
+                                         hipStream_t st);
 // One entry of mrc_pac_store_block_energy: a channel of a block, or its mid.  sel 0 / 1: output channel L / R of a joint
 // slot (a non-joint slot has one channel, itself: 0); kEnergyMid: the mid (L + R) / 2 on the lines -- of a joint slot, or of
 // the PAIR of non-joint slots slot, slot + 1 (a stereo file's last block).

@@ -47,6 +47,21 @@
 //     because the next term's run overwrites this one's; a term without a plane skips both, the whole workgroup together.
 //     No atomics; nothing depends on the grid, on the order of the items, on what shares the launch or on the slab.
 //
+//   resample_multi_sum_out_kernel   resample_sum_out_kernel with the ratio read per term (mrc_pac_store_decode_window_speeds):
+//     term j is read at ratios[ratioOf[j]], a SpeedRatio (up, down, W, skew, taps) at an address made of the workgroup's index
+//     and the loop counter alone, so the record stays in scalar registers like the term's and every branch on it is taken by
+//     the whole workgroup.  A non-unit ratio stages its run with that ratio's skew and folds it with resample_fold_up between
+//     the two barriers, exactly as above; the unit ratio (W == 0) has no run: its value is sum_term_sample's, the plane at
+//     2 L + t, and the workgroup skips both barriers together.  A thread's accumulator belongs to ONE output over all terms
+//     of its row, so the lane-to-output map is the launch's, not the ratio's: the natural one (lane l takes output l), and each
+//     ratio's skew is chosen for that map on the host.  A fold's order is per output, so the bits are those of the
+//     single-ratio kernels whatever the map; only the LDS cycles of ratios that would take evenOdd (3 / 2) differ.
+//     The taps pointer is read out of the record, where the single-ratio kernels have it as a kernel argument: a pointer out
+//     of memory is a generic one to the compiler, and the fold's tap loads would become flat vector loads, one per lane, also
+//     for up == 1 and up == 2.  So the fold takes its pointer type as a template argument and this kernel hands it a pointer
+//     to the global address space (GlobalTaps): tap rows of up == 1 and up == 2 are scalar loads again, the general case
+//     global loads -- the same mix of loads as resample_sum_out_kernel has.
+//
 //   block_energy_kernel   the energy a block adds to the decoded signal, from its MDCT lines alone
 //     (mrc_pac_store_block_energy).  The windowed MDCT with the codec's transition windows is an orthogonal lapped
 //     transform; with the reference's scaling (mdct.py: forward 2 / N, inverse 2) a block of shape (a, b) holds
@@ -134,12 +149,16 @@ __device__ inline int64_t floor_div(int64_t a, int64_t b) {         // b > 0
     return (a % b != 0 && a < 0) ? q - 1 : q;
 }
 
+// (Taps: a pointer to const double -- the kernel argument of the single-ratio kernels, or GlobalTaps where the pointer was read
+// out of memory and the compiler has to be told the address space that it sees for itself in a kernel argument)
+using GlobalTaps = const __attribute__((address_space(1))) double*;
+
 // v = the left fold from +0.0 over j ascending of taps[j][p] * run[first + j], every product rounded once, then added.
 // kUp: 1 or 2 -- `up` itself: a tap's row is read at addresses the whole wave shares (scalar loads) and the lane picks its
 // phase's -- or 0: any `up`, each lane loads taps[j][p].  kSkew: the run's layout.  Eight taps and samples are read ahead of
 // their eight additions.
-template <int kUp, bool kSkew>
-__device__ inline double resample_fold(const double* __restrict__ taps, int up, int p, const double* run, int first, int nTaps) {
+template <int kUp, bool kSkew, class Taps>
+__device__ inline double resample_fold(Taps __restrict__ taps, int up, int p, const double* run, int first, int nTaps) {
     const auto tap = [&](int j) {
         if (kUp == 1) return taps[j];
         if (kUp == 2) {
@@ -164,8 +183,8 @@ __device__ inline double resample_fold(const double* __restrict__ taps, int up, 
     for (; j < nTaps; ++j) acc = __dadd_rn(acc, __dmul_rn(tap(j), run[at(first + j)]));
     return acc;
 }
-template <bool kSkew>
-__device__ inline double resample_fold_up(const double* __restrict__ taps, int up, int p, const double* run, int first, int nTaps) {
+template <bool kSkew, class Taps>
+__device__ inline double resample_fold_up(Taps __restrict__ taps, int up, int p, const double* run, int first, int nTaps) {
     return up == 1 ? resample_fold<1, kSkew>(taps, up, p, run, first, nTaps)
          : up == 2 ? resample_fold<2, kSkew>(taps, up, p, run, first, nTaps)
                    : resample_fold<0, kSkew>(taps, up, p, run, first, nTaps);
@@ -268,6 +287,57 @@ __global__ __launch_bounds__(kResampleThreads) void resample_sum_out_kernel(cons
     for (int64_t j = termOffset[k]; j < jEnd; ++j) {                 // (every branch on the term: the whole workgroup)
         const SumTerm tm = terms[j];
         if (tm.w.nSamples == 0) continue;                            // no plane: every y is +0.0, the term adds nothing
+        // the term's run of intermediate samples under the tile's outputs: [qFirst, qFirst + len)
+        const int64_t n0 = tm.outStart + t0, nLast = n0 + min((int64_t)kResampleThreads, window - t0) - 1;
+        const int64_t qFirst = floor_div(n0 * down, up) - W + 1;
+        const int len = (int)(floor_div(nLast * down, up) + W - qFirst + 1);   // <= kResampleRun (the launcher's check)
+        const double* plane = planes + tm.w.plane + (int64_t)(tm.w.nch == 2 ? c : 0) * planeLen;
+        for (int i = threadIdx.x; i < len; i += kResampleThreads) {
+            const int64_t m = qFirst + i, at = 2 * (int64_t)L + (m - tm.w.start);
+            double v = 0.0;
+            if (m >= 0 && m < tm.w.nSamples && at >= 0 && at < planeLen) v = plane[at];
+            run[i + skew * (i >> 5)] = v;
+        }
+        __syncthreads();
+        if (t < window) {
+            const int64_t nd = (tm.outStart + t) * down, q = floor_div(nd, up);
+            const int p = (int)(nd - q * up), first = (int)(q - W + 1 - qFirst);
+            const double v = skew ? resample_fold_up<true>(taps, up, p, run, first, 2 * W) : resample_fold_up<false>(taps, up, p, run, first, 2 * W);
+            acc = __dadd_rn(acc, __dmul_rn(tm.gain, v));
+        }
+        __syncthreads();                                             // (the next term's run goes over this one)
+    }
+    if (t < window) store_window_value(out, row * window + t, format, acc);
+}
+
+__global__ __launch_bounds__(kResampleThreads) void resample_multi_sum_out_kernel(const SumTerm* __restrict__ terms,
+                                                                                  const int* __restrict__ ratioOf,
+                                                                                  const SpeedRatio* __restrict__ ratios,
+                                                                                  const long long* __restrict__ termOffset,
+                                                                                  int64_t window, int64_t tiles, int nchOut,
+                                                                                  int format, int L, int64_t planeLen,
+                                                                                  const double* __restrict__ planes,
+                                                                                  void* __restrict__ out) {
+    __shared__ double run[kResampleLds];
+    const int64_t row = (int64_t)blockIdx.x / tiles;                 // item * nchOut + channel
+    const int64_t t0 = ((int64_t)blockIdx.x - row * tiles) * kResampleThreads;
+    const int64_t k = row / nchOut;
+    const int c = (int)(row - k * nchOut);
+    const int64_t t = t0 + threadIdx.x;                              // the natural map: the accumulator's output, whatever the term
+    const int64_t jEnd = termOffset[k + 1];
+    double acc = 0.0;
+    for (int64_t j = termOffset[k]; j < jEnd; ++j) {                 // (every branch on the term or its ratio: the whole workgroup)
+        const SumTerm tm = terms[j];
+        if (tm.w.nSamples == 0) continue;                            // no plane: every y is +0.0, the term adds nothing
+        const SpeedRatio r = ratios[ratioOf[j]];                     // (blockIdx and the loop counter alone: scalar)
+        if (r.W == 0) {                                              // the unit ratio: sum_out_kernel's term, no LDS, no barrier
+            if (t < window) acc = __dadd_rn(acc, __dmul_rn(tm.gain, sum_term_sample(tm, c, t, planeLen, L, planes)));
+            continue;
+        }
+        const int up = r.up, down = r.down, W = r.W, skew = r.skew;
+        // the taps pointer comes out of memory: said to be a global one, as a kernel argument is known to be, so that the
+        // up == 1 and up == 2 folds read their tap rows with scalar loads and the general one with global loads
+        const GlobalTaps taps = (GlobalTaps)r.taps;
         // the term's run of intermediate samples under the tile's outputs: [qFirst, qFirst + len)
         const int64_t n0 = tm.outStart + t0, nLast = n0 + min((int64_t)kResampleThreads, window - t0) - 1;
         const int64_t qFirst = floor_div(n0 * down, up) - W + 1;
@@ -473,6 +543,26 @@ hipError_t launch_resample_sum_out(int64_t nRows, const SumTerm* terms, const lo
         return hipErrorInvalidValue;                                 // (a run that would not fit the workgroup's LDS)
     hipLaunchKernelGGL(resample_sum_out_kernel, dim3((unsigned)blocks), dim3(kResampleThreads), 0, st, terms, termOffset, window,
                        tiles, nchOut, format, L, planeLen, up, down, W, evenOdd, skew, taps, planes, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_resample_multi_sum_out(int64_t nRows, const SumTerm* terms, const int* ratioOf, const SpeedRatio* ratios,
+                                         const SpeedRatio* ratiosHost, int nRatios, const long long* termOffset, int64_t window,
+                                         int nchOut, int format, int L, int64_t planeLen, const double* planes, void* out,
+                                         hipStream_t st) {
+    if (nRows <= 0 || window <= 0) return hipSuccess;
+    const int64_t tiles = (window + kResampleThreads - 1) / kResampleThreads;
+    const int64_t blocks = tiles * nRows * nchOut;
+    if (blocks > 0x7fffffffLL || nRatios < 1 || !ratiosHost) return hipErrorInvalidValue;
+    for (int i = 0; i < nRatios; ++i) {
+        const SpeedRatio& r = ratiosHost[i];
+        if (r.W == 0) continue;                                      // the unit ratio: no run
+        if (r.up < 1 || r.down < 1 || r.W < 1 || !r.taps ||
+            ((int64_t)(kResampleThreads - 1) * r.down + r.up - 1) / r.up + 2 * (int64_t)r.W + 1 > kResampleRun)
+            return hipErrorInvalidValue;                             // (a run that would not fit the workgroup's LDS)
+    }
+    hipLaunchKernelGGL(resample_multi_sum_out_kernel, dim3((unsigned)blocks), dim3(kResampleThreads), 0, st, terms, ratioOf, ratios,
+                       termOffset, window, tiles, nchOut, format, L, planeLen, planes, out);
     return hipGetLastError();
 }
 

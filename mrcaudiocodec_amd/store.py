@@ -52,6 +52,25 @@ an LTI filter: smooth curves are clean, a brick-wall edge leaves a small aliasin
         y = store.decode_window(files, starts, 48000, dtype=torch.float32, band_gains=masks)
         z = store.decode_window(files, starts, 48000, band_gains=[0.0, 1.0, 0.0], band_edges_hz=[0, 300, 3400, 24000])   # telephone band
 
+speed_factors=, speed_index= (mrc_pac_store_decode_window_speeds) read every item, or every term of a sum, at a speed of its own
+drawn from a short list -- the speed perturbation of speech recipes (0.9x, 1.0x, 1.1x per utterance) in one call, one plan and
+one output kernel, each unit bit for bit what decode_window(resample=its ratio) gives.  Speech at a drawn speed over noise at
+speed 1 at a drawn SNR, at 16 kHz from 48 kHz files; source_spans says which stretch of the half-rate signal a sped-up term
+lies over, which is what the levels are asked about:
+
+        speeds = [(9, 10), (1, 1), (11, 10)]                                   # the term's ratio: 2 / 3 divided by its speed
+        ratios = speed_ratios((2, 3), speeds)                                  # [(20, 27), (2, 3), (20, 33)]
+        pick = rng.integers(0, 3, len(speech))
+        first, length = store.source_spans(s_starts, 16000, ratios, pick, rate_divisor=2)
+        n_first, _ = store.source_spans(n_starts, 16000, [(2, 3)], np.zeros_like(pick), rate_divisor=2)
+        m, g = store.levels(2, "mid"), np.ones(len(speech))
+        for r in range(3):                                                     # (one window length per question)
+            k = pick == r
+            g[k] = m.gains_for_snr(rng.uniform(0, 20), speech[k], first[k], noise[k], n_first[k], int(length[k][0])) if k.any() else 1.0
+        x = store.decode_window_sum(np.stack([speech, noise], 1), np.stack([s_starts, n_starts], 1), np.stack([np.ones_like(g), g], 1),
+                                    16000, dtype=torch.float32, rate_divisor=2, mix="mid", resample=(2, 3),
+                                    speed_factors=speeds, speed_index=np.stack([pick, np.ones_like(pick)], 1))   # the noise: speed 1
+
 band_energy_window (mrc_pac_store_band_energy_window) is the time-frequency feature that usually follows a crop, taken from
 the same sums split by frequency band and laid on a frame grid -- the coded file already is a time-frequency representation:
 
@@ -160,6 +179,63 @@ def resample_plan(rate_in, rate_out, divisors=RATE_DIVISORS):
     up, down = rate_out // g, rate_in // d // g
     check_resample((up, down), "resample_plan")
     return d, up, down
+
+
+MAX_RATIOS = 8                           # MRC_MAX_STORE_RATIOS
+
+
+def _speed_list(resample, speed_factors, what):
+    """-> ([(up, down)] reduced, zeros, rolloff): resample's base ratio (None: 1 / 1) divided by every speed; ValueError as
+    speed_ratios describes it"""
+    checked = check_resample(resample, what)
+    zeros, rolloff = (RESAMPLE_ZEROS, RESAMPLE_ROLLOFF) if resample is None or len(resample) == 2 else (int(resample[2]), float(resample[3]))
+    base_up, base_down = (1, 1) if resample is None else (int(resample[0]), int(resample[1]))
+    if checked is not None:
+        base_up, base_down = checked[0], checked[1]
+    if not isinstance(speed_factors, (tuple, list)) or not 1 <= len(speed_factors) <= MAX_RATIOS:
+        raise ValueError("%s: speed_factors must be a list of 1 to %d (num, den) pairs, got %r" % (what, MAX_RATIOS, speed_factors))
+    ratios = []
+    for i, f in enumerate(speed_factors):
+        if not isinstance(f, (tuple, list)) or len(f) != 2 or not all(_is_int(v) and int(v) >= 1 for v in f):
+            raise ValueError("%s: speed_factors[%d] must be a pair of positive ints (num, den), got %r" % (what, i, f))
+        num, den = int(f[0]), int(f[1])
+        up, down = base_up * den, base_down * num
+        g = int(np.gcd(up, down))
+        up, down = up // g, down // g
+        if max(up, down) >= 1 << 31:
+            raise ValueError("%s: speed_factors[%d] = %d / %d: the combined ratio %d / %d does not fit an int" % (what, i, num, den, up, down))
+        check_resample((up, down, zeros, rolloff), "%s: speed_factors[%d] = %d / %d on %d / %d" % (what, i, num, den, base_up, base_down))
+        ratios.append((up, down))
+    return ratios, zeros, rolloff
+
+
+def speed_ratios(resample, speed_factors):
+    """The ratios at which decode_window(resample=, speed_factors=) reads its units -> [(up, down)], reduced, one per factor:
+    resample's base ratio (None: 1 / 1) divided by the speed num / den -- a speed above 1 plays faster, so fewer output
+    samples cover the same source.  48 kHz files at 16 kHz (rate_divisor 2, resample (2, 3)) at 9/10, 1, 11/10:
+    [(20, 27), (2, 3), (20, 33)].  No handle, no GPU.  ValueError for a list that is not 1 to 8 pairs of positive ints and for
+    a combined ratio outside what check_resample takes, named with its reduced terms (320 / 441 at 11 / 10 is 3200 / 4851)."""
+    return _speed_list(resample, speed_factors, "speed_ratios")[0]
+
+
+def check_speed_index(speed_index, unit_shape, n_ratios, what="decode_window"):
+    """speed_index of a window call -> int32 [units], contiguous, else ValueError: ints, the shape of the call's units, every
+    value an index into the list of n_ratios"""
+    unit_shape = tuple(int(v) for v in unit_shape)
+    try:
+        idx = np.asarray(speed_index)
+        if idx.dtype == object or idx.dtype.kind not in "iu":
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError("%s: speed_index must be ints, got %r" % (what, speed_index))
+    if idx.shape != unit_shape:
+        raise ValueError("%s: speed_index must have shape %s, got %s" % (what, unit_shape, idx.shape))
+    idx = idx.reshape(-1)
+    bad = np.flatnonzero((idx < 0) | (idx >= n_ratios))
+    if bad.size:
+        raise ValueError("%s: speed_index must lie in 0..%d (the speed_factors given), got %d at unit %d"
+                         % (what, n_ratios - 1, int(idx[bad[0]]), int(bad[0])))
+    return np.ascontiguousarray(idx.astype(np.int32))
 
 
 def check_levels_mix(mix, what="levels"):
@@ -388,8 +464,54 @@ class PacStore:
         edges = critical_band_edges(self._handle.cfg.sample_rate) if band_edges_hz is None else check_band_edges(band_edges_hz, what)
         return edges, check_band_gains(band_gains, unit_shape, edges.size - 1, what)
 
+    def _speed_args(self, what, resample, speed_factors, speed_index, unit_shape):
+        """speed_factors / speed_index of a window call -> None, or (ratios [(up, down)], zeros, rolloff, index int32 [units]);
+        ValueError as speed_ratios and check_speed_index raise it, and for one of the two given without the other"""
+        if speed_factors is None and speed_index is None:
+            return None
+        if speed_factors is None or speed_index is None:
+            raise ValueError("%s: speed_factors and speed_index go together, got only %s"
+                             % (what, "speed_index" if speed_factors is None else "speed_factors"))
+        ratios, zeros, rolloff = _speed_list(resample, speed_factors, what)
+        return ratios, zeros, rolloff, check_speed_index(speed_index, unit_shape, len(ratios), what)
+
+    def _speeds(self, rate_divisor, mix, speeds, bands, n, offsets, files, starts, gains, window, channels, fmt, out, stream):
+        """mrc_pac_store_decode_window_speeds over checked arguments; speeds = (ratios, zeros, rolloff, index [terms]), bands
+        None or (edges, gains [terms][n_bands])"""
+        ratios, zeros, rolloff, index = speeds
+        ups = np.ascontiguousarray([r[0] for r in ratios], dtype=np.int32)
+        downs = np.ascontiguousarray([r[1] for r in ratios], dtype=np.int32)
+        pad = lambda a: a.ctypes.data if a.size else None
+        edges, band_gains = bands if bands is not None else (None, None)
+        self._handle._check(lib.mrc_pac_store_decode_window_speeds(
+            self._s, rate_divisor, _lib.MRC_MIX_EACH if mix is None else mix, len(ratios), ups.ctypes.data, downs.ctypes.data, zeros,
+            rolloff, 0 if bands is None else edges.size - 1, None if bands is None else edges.ctypes.data,
+            None if bands is None else pad(band_gains), n, offsets.ctypes.data, pad(files), pad(starts), pad(gains), pad(index), window,
+            channels, fmt, out.data_ptr() if out.numel() else None, stream or None))
+
+    def source_spans(self, starts, window, ratios, index, rate_divisor=1):
+        """Where the units of decode_window(speed_factors=, speed_index=) lie in the signal at 1 / rate_divisor of the sample
+        rate -> (first, length), int64 arrays of starts' shape: unit k, read at ratios[index[k]] = (up, down) (speed_ratios
+        gives the list), has its `window` outputs over the intermediate samples [first, first + length), first =
+        floor(starts[k] down / up) and length = ceil(window down / up) -- without the filter's tails.  Those are the
+        coordinates of levels(rate_divisor): LevelMap.gains_for_snr, .gains_to and .sample_starts can be asked about a sped-up
+        term with (first, length) in place of (start, window).  No library call.  ValueError for ratios that are not pairs
+        of positive ints, an index outside the list or of another shape, a negative window."""
+        what = "source_spans"
+        check_rate_divisor(rate_divisor, what)
+        starts = np.asarray(starts, dtype=np.int64)
+        if not isinstance(ratios, (tuple, list)) or not ratios or \
+                not all(isinstance(r, (tuple, list)) and len(r) == 2 and all(_is_int(v) and int(v) >= 1 for v in r) for r in ratios):
+            raise ValueError("%s: ratios must be a list of (up, down) pairs of positive ints, got %r" % (what, ratios))
+        if not _is_int(window) or int(window) < 0:
+            raise ValueError("%s: window must be an int >= 0, got %r" % (what, window))
+        idx = check_speed_index(index, starts.shape, len(ratios), what).reshape(starts.shape)
+        up = np.array([int(r[0]) for r in ratios], np.int64)[idx]
+        down = np.array([int(r[1]) for r in ratios], np.int64)[idx]
+        return np.floor_divide(starts * down, up), -np.floor_divide(-int(window) * down, up)
+
     def decode_window(self, files, starts, window, channels=None, dtype=None, out=None, stream=None, rate_divisor=1,
-                      mix=None, resample=None, band_gains=None, band_edges_hz=None):
+                      mix=None, resample=None, band_gains=None, band_edges_hz=None, speed_factors=None, speed_index=None):
         """Item i = samples [starts[i], starts[i] + window) of file files[i], zeros where that leaves the file (starts may be
         negative or past the end) -> a torch tensor [n][channels][window] on the handle's device.  dtype: torch.int16 (the
         default: the codes Handle.decode_pac_pcm16 writes, bit for bit), torch.float64 (the overlap-added signal before the
@@ -426,10 +548,18 @@ class PacStore:
         window.  Not an LTI filter: where neighbouring lines get different gains the time-domain aliasing of adjacent blocks
         no longer cancels exactly -- smooth gain curves are clean, a brick-wall edge leaves a small aliasing residue near the
         edge frequency (DESIGN.md has figures).  A wrong shape, values that are not finite numbers and band_edges_hz without
-        band_gains are ValueErrors, before any library call."""
+        band_gains are ValueErrors, before any library call.
+        speed_factors, speed_index: None, or a list of 1 to 8 (num, den) pairs and an int array [n] of indices into it
+        (mrc_pac_store_decode_window_speeds, as one-term rows at gain 1.0): item i is read at speed num / den -- above 1 plays
+        faster -- that is at resample's base ratio (None: 1 / 1) divided by its speed, reduced (speed_ratios gives the list).
+        Item i is then, bit for bit, what decode_window(resample=that ratio) gives for it: starts and window count output
+        samples at the item's OWN ratio, and a ratio of 1 is the call without a filter.  Speed perturbation of a batch --
+        0.9x, 1.0x, 1.1x drawn per item -- is one call, one plan and one output kernel.  Only one of the two given, a wrong
+        shape, an index outside the list, a factor that is not a pair of positive ints and a combined ratio outside what
+        resample takes (named with its reduced terms) are ValueErrors, before any library call."""
         rate_divisor = check_rate_divisor(rate_divisor)
         mix = check_mix(mix, channels)
-        resample = check_resample(resample)
+        resample_arg, resample = resample, check_resample(resample)
         if mix is not None:
             channels = 1
         files = np.ascontiguousarray(np.asarray(files, dtype=np.int64).reshape(-1))
@@ -438,7 +568,12 @@ class PacStore:
             raise ValueError("decode_window: one start per file index (%d files, %d starts)" % (files.size, starts.size))
         n, window = files.size, int(window)
         bands = self._band_args("decode_window", band_gains, band_edges_hz, (n,))
+        speeds = self._speed_args("decode_window", resample_arg, speed_factors, speed_index, (n,))
         fmt, channels, out, stream = self._window_out("decode_window", n, files, window, channels, dtype, out, stream)
+        if speeds is not None:
+            offsets, ones = np.arange(n + 1, dtype=np.int64), np.ones(n, np.float64)
+            self._speeds(rate_divisor, mix, speeds, bands, n, offsets, files, starts, ones, window, channels, fmt, out, stream)
+            return out
         if bands is not None:
             offsets, ones = np.arange(n + 1, dtype=np.int64), np.ones(n, np.float64)
             self._shaped(rate_divisor, mix, resample, bands, n, offsets, files, starts, ones, window, channels, fmt, out, stream)
@@ -467,7 +602,8 @@ class PacStore:
             out.data_ptr() if out.numel() else None, stream or None))
 
     def decode_window_sum(self, files, starts, gains, window, item_offsets=None, channels=None, dtype=None, out=None, stream=None,
-                          rate_divisor=1, mix=None, resample=None, band_gains=None, band_edges_hz=None):
+                          rate_divisor=1, mix=None, resample=None, band_gains=None, band_edges_hz=None, speed_factors=None,
+                          speed_index=None):
         """mrc_pac_store_decode_window_sum -> a torch tensor [n][channels][window] on the handle's device: item i is the sum
         over its terms k, IN THE ORDER GIVEN, of gains[k] * (the float64 window decode_window gives for files[k], starts[k]
         at this rate_divisor, mix and resample), folded from +0.0 with every product rounded once, then added -- speech over
@@ -483,11 +619,15 @@ class PacStore:
         band_gains, band_edges_hz: as decode_window's, PER TERM: band_gains has the shape of files plus a last axis [n_bands]
         ([n_bands] alone: every term), and term k's lines are multiplied by its row before its inverse transform
         (mrc_pac_store_decode_window_shaped) -- a telephone band for the speech term and none for the noise is a row of gains
-        and a row of ones.  The fold over the terms is unchanged."""
+        and a row of ones.  The fold over the terms is unchanged.
+        speed_factors, speed_index: as decode_window's, PER TERM (mrc_pac_store_decode_window_speeds): speed_index has the shape
+        of files, and term k is the float64 window decode_window gives at ITS ratio -- the speech term at a drawn speed over a
+        noise term at speed 1 is one call.  starts and window count output samples at the term's own ratio;
+        source_spans says where a term lies in the source, for LevelMap's gains.  Per-term band_gains still apply."""
         what = "decode_window_sum"
         rate_divisor = check_rate_divisor(rate_divisor, what)
         mix = check_mix(mix, channels, what)
-        resample = check_resample(resample, what)
+        resample_arg, resample = resample, check_resample(resample, what)
         if mix is not None:
             channels = 1
         files, starts = np.asarray(files, dtype=np.int64), np.asarray(starts, dtype=np.int64)
@@ -496,6 +636,7 @@ class PacStore:
             raise ValueError("%s: files, starts and gains must have one shape, got %s, %s and %s"
                              % (what, files.shape, starts.shape, gains.shape))
         bands = self._band_args(what, band_gains, band_edges_hz, files.shape)
+        speeds = self._speed_args(what, resample_arg, speed_factors, speed_index, files.shape)
         if item_offsets is None:
             if files.ndim != 2:
                 raise ValueError("%s: files, starts and gains must be [n][K], or 1-D with item_offsets; got shape %s" % (what, files.shape))
@@ -514,6 +655,9 @@ class PacStore:
             raise ValueError("%s: gains must be finite, got %r at term %d" % (what, float(gains[bad[0]]), int(bad[0])))
         n, window = offsets.size - 1, int(window)
         fmt, channels, out, stream = self._window_out(what, n, files, window, channels, dtype, out, stream)
+        if speeds is not None:
+            self._speeds(rate_divisor, mix, speeds, bands, n, offsets, files, starts, gains, window, channels, fmt, out, stream)
+            return out
         if bands is not None:
             self._shaped(rate_divisor, mix, resample, bands, n, offsets, files, starts, gains, window, channels, fmt, out, stream)
             return out
@@ -635,7 +779,10 @@ class PacStore:
         """of the last decode_window: chunks_parsed, decode_launches, slabs, plan_bytes_uploaded, and ms: the device time of
         the plan upload, the unpack kernel, the synthesis and window_out_kernel (with resample=: resample_out_kernel, and the
         counts are those of the intermediate spans), summed over the slabs.  After decode_window_sum(): the same, the counts
-        those of all terms and ms["window_out"] the time of sum_out_kernel (resample_sum_out_kernel).  After levels() or
+        those of all terms and ms["window_out"] the time of sum_out_kernel (resample_sum_out_kernel).  With speed_factors=:
+        chunks_parsed is the sum over the units of what the single-ratio call parses for each at its own ratio, slabs counts
+        runs of rows whose units, each at the call's largest span, fit MRC_OPT_STORE_SLAB_SAMPLES, plan_bytes_uploaded includes
+        the units' ratio indices and the table of ratios, and ms["window_out"] is resample_multi_sum_out_kernel's.  After levels() or
         block_energy(): decode_launches counts block_energy_kernel launches, ms["synthesis"] is that kernel's time and
         ms["window_out"] is 0.  After band_energy_window(): decode_launches counts band_energy_kernel launches,
         ms["synthesis"] is the band sums' time (that kernel) and ms["window_out"] the frame assembly's (band_frames_kernel)."""
