@@ -1062,6 +1062,49 @@ int mrc_pac_store_band_energy_window(mrc_pac_store* s, int mix, int64_t n_items,
                                      const int64_t* start /*[n_items]*/, int64_t n_frames, int64_t hop, int n_bands,
                                      const double* edge_hz /*[n_bands+1]*/, int n_channels_out, int format,
                                      void* out /* DEVICE [n_items][n_channels_out][n_bands][n_frames] */, void* stream);
+/* mrc_filterbank_line_weights: the weights with which the MDCT lines of a block of shape (a, b) enter a bank of triangular
+ * filters (mel, Bark, ERB, ...), on the host alone (no handle, no device).  n_filters in 1..MRC_MAX_STORE_BANDS; point_hz
+ * [n_filters + 2] finite, point_hz[0] >= 0, strictly increasing (points above Nyquist are allowed).  Filter q is the
+ * triangle with feet p0 = point_hz[q], p2 = point_hz[q + 2] and peak 1 at p1 = point_hz[q + 1]; norm is
+ * MRC_FILTER_NORM_NONE or MRC_FILTER_NORM_SLANEY, which multiplies every weight of filter q by 2.0 / (p2 - p0).
+ * With halfN = (a + b) / 2 and d = (sample_rate / halfN) / 2., line k occupies [e_k, e_{k+1}), e_k = k * d (its centre is
+ * mrc_band_line_ranges' f_k), and its weight is the triangle's MEAN over that interval, so that a filter narrower than a
+ * block's line spacing still reads its share of the line it lies in -- no filter is empty below the last line's upper edge:
+ *   line_lo[q] = #{k < halfN : e_{k+1} <= p0},  line_hi[q] = #{k < halfN : e_k < p2};  for line_lo[q] <= k < line_hi[q],
+ *   with f0 = e_k and f1 = e_{k+1}, in float64 and exactly this order of operations (no fused multiply-add):
+ *     u0 = max(f0, p0); u1 = min(f1, p1); rise = u1 > u0 ? ((0.5 * (u0 + u1) - p0) / (p1 - p0)) * (u1 - u0) : 0.0
+ *     v0 = max(f0, p1); v1 = min(f1, p2); fall = v1 > v0 ? ((p2 - 0.5 * (v0 + v1)) / (p2 - p1)) * (v1 - v0) : 0.0
+ *     w  = (rise + fall) / d;             MRC_FILTER_NORM_SLANEY:  w = w * (2.0 / (p2 - p0))
+ * weight holds the rows one after the other, filter 0's line_hi[0] - line_lo[0] weights first; *n_weights is their number.
+ * weight NULL: sizes only (line_lo, line_hi and *n_weights are written, weight_cap is not looked at).
+ * MRC_ERR_INVALID naming the argument (mrc_last_error(NULL)): n_filters outside 1..MRC_MAX_STORE_BANDS, a point that is
+ * not finite, point_hz[0] < 0, points not strictly increasing (with the index), norm outside {0, 1}, a shape
+ * mrc_synthesis_shape(a, b, 1) refuses, weight_cap below *n_weights with weight given. */
+#define MRC_FILTER_NORM_NONE 0
+#define MRC_FILTER_NORM_SLANEY 1
+int mrc_filterbank_line_weights(double sample_rate, int a, int b, int n_filters, const double* point_hz /*[n_filters+2]*/,
+                                int norm, int32_t* line_lo /*[n_filters]*/, int32_t* line_hi /*[n_filters]*/,
+                                int64_t weight_cap, double* weight /* rows one after the other; NULL: sizes only */,
+                                int64_t* n_weights);
+/* mrc_pac_store_filterbank_window: mrc_pac_store_band_energy_window with a bank of triangular filters in place of the
+ * rectangular bands -- a mel (Bark, ERB) spectrogram of every item from the MDCT lines alone.  out[i][c][q][j] (DEVICE
+ * memory, [n_items][n_channels_out][n_filters][n_frames]):
+ *   F_n[c][q]       = the left fold from +0.0 over k = line_lo[q] .. line_hi[q] - 1 ascending of w_q[k] * (x^[k] * x^[k]),
+ *                     w_q, line_lo and line_hi those of mrc_filterbank_line_weights for block n's shape and the handle's
+ *                     sample rate, x^ the lines mrc_pac_store_band_energy_window squares: the square is rounded once, the
+ *                     product is rounded once, then it is added (no fused multiply-add);
+ *   out[i][c][q][j] = sum_n (double)ov2(n, j) * F_n[c][q], the band call's frames, tiles and fold with F in B's place.
+ * Items, frames, mixes, channels, formats, extreme starts, damage, the "nothing to write" cases, slabs and
+ * mrc_pac_store_stats are the band call's: stats[1] counts filterbank_energy_kernel launches, ms[2] is that kernel's time.
+ * Every bit is defined; results do not depend on the order of the items, on what shares the call, on the slab size or on
+ * the launch grid.  This is not an STFT mel spectrogram: its time resolution is the block tile's and its frequency
+ * resolution the block's line spacing.  Log compression is the caller's.
+ * MRC_ERR_INVALID naming the argument, before any device work (out untouched): the band call's own refusals with the
+ * refusals of mrc_filterbank_line_weights in the place of mrc_band_line_ranges'. */
+int mrc_pac_store_filterbank_window(mrc_pac_store* s, int mix, int64_t n_items, const int64_t* file /*[n_items]*/,
+                                    const int64_t* start /*[n_items]*/, int64_t n_frames, int64_t hop, int n_filters,
+                                    const double* point_hz /*[n_filters+2]*/, int norm, int n_channels_out, int format,
+                                    void* out /* DEVICE [n_items][n_channels_out][n_filters][n_frames] */, void* stream);
 /* mrc_resample_taps: the filter of mrc_pac_store_decode_window_resampled, on the host alone (no handle, no device).
  * up / down is the output rate over the input rate; the library reduces it by the gcd.  After reduction 1 <= up, down <= 1024,
  * up != down, down <= 8 up and up <= 8 down; zeros in [1, 64]; rolloff in [0.5, 1]; anything else is MRC_ERR_INVALID naming

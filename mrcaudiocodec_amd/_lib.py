@@ -21,6 +21,7 @@ MRC_ERR_NOMEM = -4
 MRC_WINDOW_PCM16, MRC_WINDOW_F32, MRC_WINDOW_F64 = 0, 1, 2      # mrc_pac_store_decode_window's formats
 MRC_MIX_MID, MRC_MIX_LEFT, MRC_MIX_RIGHT = 0, 1, 2               # mrc_pac_store_decode_window_mix's channels
 MRC_MIX_EACH = 3                                                 # mrc_pac_store_block_energy: every channel of the file
+MRC_FILTER_NORM_NONE, MRC_FILTER_NORM_SLANEY = 0, 1              # mrc_filterbank_line_weights' norms
 MRC_OPT_STORE_SLAB_SAMPLES = 7
 # mrc_dev_helper_probe: name -> (MRC_PROBE_ id, words per element of in0 / in1 / in2, words per element of out)
 PROBES = {
@@ -233,6 +234,10 @@ def _load():
         "mrc_band_line_ranges": (C.c_int, [C.c_double, C.c_int, C.c_int, C.c_int, _f64p, _i32p]),
         "mrc_pac_store_band_energy_window": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, _i64p, _i64p, C.c_int64, C.c_int64, C.c_int,
                                                        _f64p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+        "mrc_filterbank_line_weights": (C.c_int, [C.c_double, C.c_int, C.c_int, C.c_int, _f64p, C.c_int, _i32p, _i32p, C.c_int64,
+                                                  _f64p, _i64p]),
+        "mrc_pac_store_filterbank_window": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, _i64p, _i64p, C.c_int64, C.c_int64, C.c_int,
+                                                      _f64p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
         "mrc_resample_taps": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, _i32p, _f64p]),
         "mrc_pac_store_decode_window_resampled": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
                                                             C.c_int64, _i64p, _i64p, C.c_int64, C.c_int, C.c_int, C.c_void_p,

@@ -59,6 +59,12 @@ Band energies:  python -m mrcaudiocodec_amd.cli --band-energies in.pac out.npy -
 decodes nothing: out.npy holds float32 [channels][bands][frames], the energy of each band in frame [j N, (j + 1) N) of the
 file from its MDCT lines (mrc_pac_store_band_energy_window); default bands: the codec's critical bands.  Refuses every
 encode, decode and levels flag.
+Filter-bank energies:  python -m mrcaudiocodec_amd.cli --filterbank-energies in.pac out.npy --hop N (--mel N [--f-min HZ]
+[--f-max HZ] [--mel-scale htk|slaney] | --filter-points f0,f1,...) [--filter-norm slaney] [--mix CH]  is the same with a bank
+of overlapping triangular filters (mrc_pac_store_filterbank_window): out.npy holds float32 [channels][filters][frames].  --mel N
+spaces N filters equally in mel from --f-min (default 0) to --f-max (default Nyquist); --filter-points names the filters'
+points itself.  A filter narrower than a block's line spacing reads its share of the line it lies in: no row is empty.
+Refuses every encode, decode, levels and band-energy flag.
 
 Quality (mrc_pac_nmr): --nmr on an encode prints, per file written (every rung of a ladder), one JSON line with the
 noise-to-mask ratio of the file against the WAV, measured with the codec's own masking model: nmr_max_db (worst band),
@@ -580,13 +586,10 @@ def check_band_energies_args(band_energies, hop, band_edges, given):
     return int(hop), edges
 
 
-def band_energies_of_file(pac_path, npy_path, hop, band_edges_hz=None, device_id=0, mix=None):
-    """The whole file's band energies (PacStore.band_energy_window: nothing is decoded) -> float32 [channels][bands][frames],
-    written to npy_path as a .npy file: frame j is samples [j hop, (j + 1) hop) of the decoded file, ceil(samples / hop)
-    frames; band_edges_hz None: store.critical_band_edges of the file's sample rate; mix "mid", "left" or "right": one
-    channel."""
-    import torch
-    from .store import PacStore, check_mix, critical_band_edges
+def _whole_file_energies(pac_path, npy_path, hop, device_id, mix, call):
+    """--band-energies and --filterbank-energies: call(store, sample_rate, n_frames) over the whole file from sample 0,
+    ceil(samples / hop) frames -> float32 [channels][rows][frames], written to npy_path as a .npy file"""
+    from .store import PacStore, check_mix
     check_mix(mix, None, "--mix")
     with open(pac_path, "rb") as fp:
         buf = fp.read()
@@ -594,18 +597,110 @@ def band_energies_of_file(pac_path, npy_path, hop, band_edges_hz=None, device_id
         c, _, _, _ = pacfile.read_header(buf)
     except MrcError as e:
         raise ValueError("%s: not a .pac file (%s)" % (pac_path, e))
-    edges = critical_band_edges(c.sample_rate) if band_edges_hz is None else band_edges_hz
     h = Handle(sample_rate=c.sample_rate, n_mdct_lines=c.n_mdct_lines, n_scale_bits=c.n_scale_bits,
                n_mant_size_bits=c.n_mant_size_bits, device_id=device_id)
     try:
         with PacStore(h, [buf]) as store:
             n_frames = -(-int(store.n_samples[0]) // hop)
-            e = store.band_energy_window([0], [0], n_frames, hop, edges, dtype=torch.float32, mix=mix)[0].cpu().numpy()
+            e = call(store, c.sample_rate, n_frames)[0].cpu().numpy()
     finally:
         h.close()
     with open(npy_path, "wb") as fp:
         np.save(fp, e)
     return e
+
+
+def band_energies_of_file(pac_path, npy_path, hop, band_edges_hz=None, device_id=0, mix=None):
+    """The whole file's band energies (PacStore.band_energy_window: nothing is decoded) -> float32 [channels][bands][frames],
+    written to npy_path as a .npy file: frame j is samples [j hop, (j + 1) hop) of the decoded file, ceil(samples / hop)
+    frames; band_edges_hz None: store.critical_band_edges of the file's sample rate; mix "mid", "left" or "right": one
+    channel."""
+    import torch
+    from .store import critical_band_edges
+
+    def call(store, sample_rate, n_frames):
+        edges = critical_band_edges(sample_rate) if band_edges_hz is None else band_edges_hz
+        return store.band_energy_window([0], [0], n_frames, hop, edges, dtype=torch.float32, mix=mix)
+    return _whole_file_energies(pac_path, npy_path, hop, device_id, mix, call)
+
+
+FILTERBANK_ENERGIES_REFUSES = BAND_ENERGIES_REFUSES + ("--band-energies", "--band-edges")
+FILTERBANK_FLAGS = ("--mel", "--f-min", "--f-max", "--mel-scale", "--filter-points", "--filter-norm")
+
+
+def check_filterbank_energies_args(filterbank_energies, hop, mel, f_min, f_max, mel_scale, filter_points, filter_norm, given):
+    """--filterbank-energies as given with --hop and its filter flags -> (hop, bank), or None without it.  bank is
+    dict(points=float64 points or None, mel=(n, f_min, f_max or None: Nyquist, scale) or None, norm=None or "slaney"): exactly
+    one of --mel N and --filter-points; --f-min, --f-max and --mel-scale go with --mel.  Like --band-energies it reads src, a
+    `.pac` file, and writes dst, a .npy file: given (flag -> whether it was given, for FILTERBANK_ENERGIES_REFUSES) must be
+    empty of every encode, decode, excerpt, measure, levels and band-energy flag; --hop is needed and >= 1; the filter flags
+    need --filterbank-energies."""
+    flags = dict(zip(FILTERBANK_FLAGS, (mel, f_min, f_max, mel_scale, filter_points, filter_norm)))
+    if not filterbank_energies:
+        for flag, v in flags.items():
+            if v is not None:
+                raise ValueError("%s belongs to --filterbank-energies: it needs --filterbank-energies" % flag)
+        return None
+    for flag in FILTERBANK_ENERGIES_REFUSES:
+        if given.get(flag):
+            raise ValueError("--filterbank-energies writes the filter-bank energies of a .pac file and nothing else: it does not "
+                             "go with %s" % flag)
+    if hop is None or isinstance(hop, bool) or not isinstance(hop, (int, np.integer)) or int(hop) < 1:
+        raise ValueError("--filterbank-energies needs --hop N, a positive number of samples, got %r" % (hop,))
+    from .store import MAX_BANDS, MEL_SCALES, check_filter_norm, check_filter_points, mel_points
+    if (mel is None) == (filter_points is None):
+        raise ValueError("--filterbank-energies needs exactly one of --mel N and --filter-points f0,f1,...")
+    bank = dict(points=None, mel=None, norm=filter_norm)
+    try:
+        check_filter_norm(filter_norm, "--filter-norm")
+    except ValueError:
+        raise ValueError("--filter-norm: the one norm is slaney, got %r" % (filter_norm,))
+    if filter_points is not None:
+        for flag in ("--f-min", "--f-max", "--mel-scale"):
+            if flags[flag] is not None:
+                raise ValueError("%s goes with --mel, not with --filter-points" % flag)
+        try:
+            values = [float(v) for v in str(filter_points).split(",")]
+        except ValueError:
+            raise ValueError("--filter-points: %r is not a comma-separated list of frequencies in Hz" % (filter_points,))
+        bank["points"] = check_filter_points(values, "--filter-points")
+        return int(hop), bank
+    if isinstance(mel, bool) or not isinstance(mel, (int, np.integer)) or not 1 <= int(mel) <= MAX_BANDS:
+        raise ValueError("--mel: the number of filters is an int in 1..%d, got %r" % (MAX_BANDS, mel))
+    scale = "htk" if mel_scale is None else mel_scale
+    if scale not in MEL_SCALES:
+        raise ValueError("--mel-scale is htk or slaney, got %r" % (mel_scale,))
+    lo = 0.0 if f_min is None else f_min
+    for flag, v in (("--f-min", lo), ("--f-max", f_max)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v)
+                              or v < 0):
+            raise ValueError("%s: a frequency in Hz at or above 0, got %r" % (flag, v))
+    if f_max is not None:
+        try:
+            mel_points(int(mel), float(lo), float(f_max), scale)
+        except ValueError as e:
+            raise ValueError("--f-min, --f-max: %s" % e)
+    bank["mel"] = (int(mel), float(lo), None if f_max is None else float(f_max), scale)
+    return int(hop), bank
+
+
+def filterbank_energies_of_file(pac_path, npy_path, hop, bank, device_id=0, mix=None):
+    """The whole file's filter-bank energies (PacStore.filterbank_window: nothing is decoded) -> float32
+    [channels][filters][frames], written to npy_path as a .npy file, frames as band_energies_of_file's; bank as
+    check_filterbank_energies_args gives it (mel with f_max None: up to the file's Nyquist frequency)."""
+    import torch
+    from .store import mel_points
+
+    def call(store, sample_rate, n_frames):
+        points = bank["points"]
+        if points is None:
+            n, f_min, f_max, scale = bank["mel"]
+            try:
+                points = mel_points(n, f_min, sample_rate / 2.0 if f_max is None else f_max, scale)
+            except ValueError as e:
+                raise ValueError("--mel: %s" % e)
+        return store.filterbank_window([0], [0], n_frames, hop, points, norm=bank["norm"], dtype=torch.float32, mix=mix)
+    return _whole_file_energies(pac_path, npy_path, hop, device_id, mix, call)
 
 
 def check_band_gains_db_args(band_gains_db, decode):
@@ -929,6 +1024,20 @@ def main(argv=None):
     ap.add_argument("--band-edges", default=None, metavar="F0,F1,...",
                     help="with --band-energies: the band edges in Hz, increasing (default: 0, the codec's critical-band "
                          "limits below Nyquist, Nyquist)")
+    ap.add_argument("--filterbank-energies", action="store_true",
+                    help="src is a .pac file, dst a .npy file: write the whole file's energies in a bank of triangular filters, "
+                         "float32 [channels][filters][frames], frames as --band-energies' (--hop N), from the MDCT lines (nothing "
+                         "is decoded); needs --mel N or --filter-points; composes with --filter-norm and --mix")
+    ap.add_argument("--mel", type=int, default=None, metavar="N",
+                    help="with --filterbank-energies: N mel filters from --f-min (default 0) to --f-max (default Nyquist)")
+    ap.add_argument("--f-min", type=float, default=None, metavar="HZ", help="with --mel: the first filter's lower foot")
+    ap.add_argument("--f-max", type=float, default=None, metavar="HZ", help="with --mel: the last filter's upper foot")
+    ap.add_argument("--mel-scale", default=None, metavar="htk|slaney", help="with --mel: the mel scale (default htk)")
+    ap.add_argument("--filter-points", default=None, metavar="F0,F1,...",
+                    help="with --filterbank-energies: the filters' points in Hz, increasing; filter q is the triangle over "
+                         "points q, q + 1, q + 2")
+    ap.add_argument("--filter-norm", default=None, metavar="slaney",
+                    help="with --filterbank-energies: slaney divides every filter by half its width in Hz")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(_join_vbr_grid(sys.argv[1:] if argv is None else argv))
     try:
@@ -939,16 +1048,20 @@ def main(argv=None):
             "--vbr-bytes": a.vbr_bytes is not None, "--vbr-bits-per-sample": a.vbr_bits_per_sample is not None,
             "--vbr-grid": a.vbr_grid is not None, "--start": a.start is not None, "--samples": a.samples is not None,
             "--sample-rate": a.sample_rate is not None}
-        bands = check_band_energies_args(a.band_energies, a.hop, a.band_edges, dict(
+        given_energies = dict(
             given, **{"--levels": a.levels is not None, "--levels-window": a.levels_window is not None,
                       "--rate-divisor": a.rate_divisor is not None, "--band-gains-db": a.band_gains_db is not None,
-                      "--speed": a.speed is not None}))
+                      "--speed": a.speed is not None})
+        bank = check_filterbank_energies_args(a.filterbank_energies, a.hop, a.mel, a.f_min, a.f_max, a.mel_scale, a.filter_points,
+                                              a.filter_norm, dict(given_energies, **{"--band-energies": a.band_energies,
+                                                                                     "--band-edges": a.band_edges is not None}))
+        bands = check_band_energies_args(a.band_energies, a.hop if bank is None else None, a.band_edges, given_energies)
         levels = check_levels_args(a.levels, a.levels_window, given)
         if levels is None and (a.src is None or a.dst is None):
             raise ValueError("the following arguments are required: src, dst")
         excerpt = check_excerpt_args(a.start, a.samples, a.decode)
         rate_divisor = check_rate_divisor_args(a.rate_divisor, a.decode or levels is not None)
-        mix = check_mix_args(a.mix, a.decode or levels is not None or bands is not None)
+        mix = check_mix_args(a.mix, a.decode or levels is not None or bands is not None or bank is not None)
         sample_rate = check_sample_rate_args(a.sample_rate, a.decode, a.rate_divisor is not None)
         overlay = check_overlay_args(a.overlay, a.snr_db, a.overlay_start, a.decode)
         band_gains = check_band_gains_db_args(a.band_gains_db, a.decode)
@@ -961,6 +1074,12 @@ def main(argv=None):
     if bands is not None:
         try:
             band_energies_of_file(a.src, a.dst, bands[0], bands[1], a.device, mix)
+        except ValueError as e:
+            ap.error(str(e))
+        return
+    if bank is not None:
+        try:
+            filterbank_energies_of_file(a.src, a.dst, bank[0], bank[1], a.device, mix)
         except ValueError as e:
             ap.error(str(e))
         return

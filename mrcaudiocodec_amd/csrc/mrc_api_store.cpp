@@ -70,6 +70,11 @@
 // B [row][band] of the store workspace -- a row per needed block and decoded channel, an item's rows together -- then
 // band_frames_kernel over the slab's output; per item one descriptor and its run of edges go up with the plan, per shape
 // the band's line ranges (mrc_band_line_ranges, no handle and no device).
+//
+// filterbank_window, the same call with a bank of triangular filters in place of the rectangular bands: one body
+// (energy_frames_window) serves both, and what differs is an EnergyTable -- the words that go up per slab beside the items
+// and edges, and the launcher called per group.  The filter call's table is, per shape, lo, hi and a row offset per filter
+// and the rows of mrc_filterbank_line_weights (host float64, no handle and no device), computed once per call.
 #include "mrc_handle.hpp"
 #include "mrc_resample_taps.hpp"
 
@@ -77,6 +82,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 
 using namespace mrc;
 
@@ -742,12 +748,71 @@ std::string band_line_ranges(double sampleRate, int a, int b, int nBands, const 
     return std::string();
 }
 
-// mrc_pac_store_band_energy_window: the slab's parse (stage_slab, parse_slab) over the blocks whose TILES the items' frames
-// overlap, band_energy_kernel per group with slots into B [rows][n_bands] in the store workspace, band_frames_kernel
-// over the slab's output.  An item's rows are its needed blocks in file order, a row per decoded channel.
-int band_energy_window(mrc_pac_store* s, int mixArg, int64_t n_items, const int64_t* file, const int64_t* start, int64_t n_frames,
-                       int64_t hop, int n_bands, const double* edge_hz, int n_channels_out, int format, void* out, void* stream) {
-    const char* const fn = "mrc_pac_store_band_energy_window";
+// mrc_filterbank_line_weights' rule; rows (may be null: sizes only) receives the weights, filter after filter.  The
+// refusal's words as band_line_ranges gives them.  Host float64 in the header's order of operations (-ffp-contract=off).
+std::string filterbank_line_weights(double sampleRate, int a, int b, int nFilters, const double* p, int norm, int32_t* lineLo,
+                                    int32_t* lineHi, std::vector<double>* rows, int64_t* nWeights) {
+    if (nFilters < 1 || nFilters > MRC_MAX_STORE_BANDS)
+        return "n_filters " + std::to_string(nFilters) + " is outside 1.." + std::to_string(MRC_MAX_STORE_BANDS);
+    if (!p || !lineLo || !lineHi || !nWeights) return "point_hz, line_lo, line_hi or n_weights is NULL";
+    for (int q = 0; q < nFilters + 2; ++q)
+        if (!std::isfinite(p[q])) return "point_hz[" + std::to_string(q) + "] is not finite";
+    if (p[0] < 0) return "point_hz[0] < 0";
+    for (int q = 0; q < nFilters + 1; ++q)
+        if (!(p[q] < p[q + 1])) return "point_hz is not strictly increasing at [" + std::to_string(q + 1) + "]";
+    if (norm != MRC_FILTER_NORM_NONE && norm != MRC_FILTER_NORM_SLANEY)
+        return "norm " + std::to_string(norm) + " is not MRC_FILTER_NORM_NONE (0) or MRC_FILTER_NORM_SLANEY (1)";
+    if (!(sampleRate > 0) || !std::isfinite(sampleRate)) return "sample_rate is not a positive number";
+    const std::string refusal = synth_shape_refusal(a, b, 1);
+    if (!refusal.empty()) return refusal;
+    const int halfN = (a + b) / 2;
+    const double d = (sampleRate / halfN) / 2.;
+    int kl = 0, kh = 0;                                      // e_k does not decrease with k, nor the points with q: one pass
+    int64_t total = 0;
+    for (int q = 0; q < nFilters; ++q) {
+        const double p0 = p[q], p1 = p[q + 1], p2 = p[q + 2];
+        while (kl < halfN && (double)(kl + 1) * d <= p0) ++kl;
+        while (kh < halfN && (double)kh * d < p2) ++kh;
+        lineLo[q] = kl;
+        lineHi[q] = std::max(kl, kh);                        // (kl <= kh: line kl starts at or below p0 < p2, or kl is halfN)
+        total += lineHi[q] - lineLo[q];
+        if (!rows) continue;
+        for (int k = lineLo[q]; k < lineHi[q]; ++k) {
+            const double f0 = (double)k * d, f1 = (double)(k + 1) * d;
+            const double u0 = std::max(f0, p0), u1 = std::min(f1, p1);
+            const double rise = u1 > u0 ? ((0.5 * (u0 + u1) - p0) / (p1 - p0)) * (u1 - u0) : 0.0;
+            const double v0 = std::max(f0, p1), v1 = std::min(f1, p2);
+            const double fall = v1 > v0 ? ((p2 - 0.5 * (v0 + v1)) / (p2 - p1)) * (v1 - v0) : 0.0;
+            double w = (rise + fall) / d;
+            if (norm == MRC_FILTER_NORM_SLANEY) w = w * (2.0 / (p2 - p0));
+            rows->push_back(w);
+        }
+    }
+    *nWeights = total;
+    return std::string();
+}
+
+// What differs between mrc_pac_store_band_energy_window and mrc_pac_store_filterbank_window: the per-shape table, which
+// rides in every slab's staging copy as 8-byte words, and the launcher called per (shape, kind) group.
+struct EnergyTable {
+    const char* fn;                                          // the entry point's name, in front of every refusal
+    int nOut;                                                // bands or filters: the rows of an output channel
+    // fills words for the handle's four shapes, once per call; the refusal's words, empty if there is none
+    std::function<std::string(const mrc_config&)> build;
+    std::vector<int64_t> words;
+    // sums[entry.out][nOut] of one group's entries; table: words on the device
+    std::function<hipError_t(int shape, const DevShape& F, const UnpackGroupDev& G, const int64_t* table, int64_t nEntries,
+                             const EnergyEntry* entries, double* sums, hipStream_t st)> launch;
+};
+
+// mrc_pac_store_band_energy_window and mrc_pac_store_filterbank_window: the slab's parse (stage_slab, parse_slab) over the
+// blocks whose TILES the items' frames overlap, the table's kernel per group with slots into B [rows][nOut] in the store
+// workspace, band_frames_kernel over the slab's output.  An item's rows are its needed blocks in file order, a row per
+// decoded channel.
+int energy_frames_window(mrc_pac_store* s, EnergyTable& T, int mixArg, int64_t n_items, const int64_t* file, const int64_t* start,
+                         int64_t n_frames, int64_t hop, int n_channels_out, int format, void* out, void* stream) {
+    const char* const fn = T.fn;
+    const int n_bands = T.nOut;
     MRC_TRY(store_alive(s, fn));
     mrc_handle* h = s->h;
     const mrc_config& cfg = h->cfg;
@@ -765,11 +830,8 @@ int band_energy_window(mrc_pac_store* s, int mixArg, int64_t n_items, const int6
     if (n_frames < 0) return fail(h, MRC_ERR_INVALID, w + ": n_frames < 0");
     if (hop < 1) return fail(h, MRC_ERR_INVALID, w + ": hop < 1");
     if (n_frames > ((int64_t)1 << 62) / hop) return fail(h, MRC_ERR_INVALID, w + ": n_frames * hop is above 2^62");
-    int32_t lineLo[4][MRC_MAX_STORE_BANDS + 1];
-    for (int sh = 0; sh < 4; ++sh) {
-        int a, b;
-        shape_ab(cfg, sh, &a, &b);
-        const std::string refusal = band_line_ranges((double)cfg.sample_rate, a, b, n_bands, edge_hz, lineLo[sh]);
+    {
+        const std::string refusal = T.build(cfg);
         if (!refusal.empty()) return fail(h, MRC_ERR_INVALID, w + ": " + refusal);
     }
     const int64_t nFiles = (int64_t)s->index.files.size(), span = n_frames * hop;
@@ -844,7 +906,7 @@ int band_energy_window(mrc_pac_store* s, int mixArg, int64_t n_items, const int6
             [&](StageLayout* lay) {
                 for (const Need& n : needs) nSlabEntries += mix == kNoMix ? s->index.files[(size_t)n.file].nch : 1;
                 oEntries = lay->add<EnergyEntry>(nSlabEntries);
-                oLines = lay->add<int32_t>(4 * (MRC_MAX_STORE_BANDS + 1));
+                oLines = lay->add<int64_t>(T.words.size());
                 oEdges = lay->add<long long>(nEdges);
                 oItems = lay->add<BandItem>(nSlab);
             },
@@ -869,7 +931,7 @@ int band_energy_window(mrc_pac_store* s, int mixArg, int64_t n_items, const int6
             q += (int64_t)entries[g].size();
         }
         if (q != nSlabEntries || q != nRows) return fail(h, MRC_ERR_INVALID, w + ": internal error: a slab's entries do not add up");
-        std::memcpy(S.pin + oLines, lineLo, sizeof lineLo);
+        std::memcpy(S.pin + oLines, T.words.data(), sizeof(int64_t) * T.words.size());
         long long* edges = (long long*)(S.pin + oEdges);
         for (int64_t k = 0; k < nSlab; ++k) {
             const BandItem& it = items[(size_t)k];
@@ -881,7 +943,7 @@ int band_energy_window(mrc_pac_store* s, int mixArg, int64_t n_items, const int6
         std::memcpy(S.pin + oItems, items.data(), sizeof(BandItem) * (size_t)nSlab);
         MRC_HIP(h, b.planes.reserve(sizeof(double) * (size_t)nRows * (size_t)n_bands));
 
-        // ---- device: the parse step, one band_energy_kernel launch per group with slots, the frames
+        // ---- device: the parse step, one launch of the table's kernel per group with slots, the frames
         MRC_TRY(parse_slab(s, fn, S, st));
         unsigned char* din = b.in.as<unsigned char>();
         double* B = b.planes.as<double>();
@@ -890,9 +952,8 @@ int band_energy_window(mrc_pac_store* s, int mixArg, int64_t n_items, const int6
         for (int g = 0; g < kUnpackGroups; ++g) {
             if (entries[g].empty()) continue;
             const UnpackGroupDev& G = S.gd[g];
-            MRC_HIP(h, launch_band_energy(pl.hs[g / 2]->dev, G.joint, n_bands, (const int*)(din + oLines) + (g / 2) * (MRC_MAX_STORE_BANDS + 1),
-                                          (int64_t)entries[g].size(), entDev + entryBase[g], G.oscale, G.joint ? G.ms : nullptr, G.sf,
-                                          G.ba, G.mant, B, st));
+            MRC_HIP(h, T.launch(g / 2, pl.hs[g / 2]->dev, G, (const int64_t*)(din + oLines), (int64_t)entries[g].size(),
+                                entDev + entryBase[g], B, st));
             s->stats[1] += 1;
         }
         MRC_HIP(h, hipEventRecord(b.ev[4], st));
@@ -911,9 +972,104 @@ int band_energy_window(mrc_pac_store* s, int mixArg, int64_t n_items, const int6
     return MRC_OK;
 }
 
+// the band call's table: int32 [4][MRC_MAX_STORE_BANDS + 1], a shape's line ranges (514 words)
+int band_energy_window(mrc_pac_store* s, int mix, int64_t n_items, const int64_t* file, const int64_t* start, int64_t n_frames,
+                       int64_t hop, int n_bands, const double* edge_hz, int n_channels_out, int format, void* out, void* stream) {
+    constexpr int kRow = MRC_MAX_STORE_BANDS + 1;
+    EnergyTable T;
+    T.fn = "mrc_pac_store_band_energy_window";
+    T.nOut = n_bands;
+    T.build = [&](const mrc_config& cfg) {
+        T.words.assign((4 * kRow * sizeof(int32_t) + 7) / 8, 0);
+        for (int sh = 0; sh < 4; ++sh) {
+            int a, b;
+            shape_ab(cfg, sh, &a, &b);
+            const std::string refusal = band_line_ranges((double)cfg.sample_rate, a, b, n_bands, edge_hz, (int32_t*)T.words.data() + sh * kRow);
+            if (!refusal.empty()) return refusal;
+        }
+        return std::string();
+    };
+    T.launch = [&](int sh, const DevShape& F, const UnpackGroupDev& G, const int64_t* table, int64_t nEntries,
+                   const EnergyEntry* entries, double* sums, hipStream_t st) {
+        return launch_band_energy(F, G.joint, n_bands, (const int*)table + sh * kRow, nEntries, entries, G.oscale,
+                                  G.joint ? G.ms : nullptr, G.sf, G.ba, G.mant, sums, st);
+    };
+    return energy_frames_window(s, T, mix, n_items, file, start, n_frames, hop, n_channels_out, format, out, stream);
+}
+
+// the filter call's table: int32 [4][3][n_filters] (a shape's lo, hi and row offsets, the offsets counted from the shape's
+// first weight), then the four shapes' rows of float64 weights one after the other
+int filterbank_window(mrc_pac_store* s, int mix, int64_t n_items, const int64_t* file, const int64_t* start, int64_t n_frames,
+                      int64_t hop, int n_filters, const double* point_hz, int norm, int n_channels_out, int format, void* out,
+                      void* stream) {
+    EnergyTable T;
+    T.fn = "mrc_pac_store_filterbank_window";
+    T.nOut = n_filters;
+    size_t rowWord[4] = {0, 0, 0, 0};                        // where a shape's weights start in words
+    T.build = [&](const mrc_config& cfg) {
+        std::vector<int32_t> lo[4], hi[4];
+        std::vector<double> rows[4];
+        for (int sh = 0; sh < 4; ++sh) {
+            int a, b;
+            shape_ab(cfg, sh, &a, &b);
+            lo[sh].assign((size_t)std::max(n_filters, 1), 0);
+            hi[sh].assign((size_t)std::max(n_filters, 1), 0);
+            int64_t n = 0;
+            const std::string refusal = filterbank_line_weights((double)cfg.sample_rate, a, b, n_filters, point_hz, norm,
+                                                                lo[sh].data(), hi[sh].data(), &rows[sh], &n);
+            if (!refusal.empty()) return refusal;
+        }
+        const size_t nf = (size_t)n_filters;
+        size_t at = (12 * nf * sizeof(int32_t) + 7) / 8;
+        for (int sh = 0; sh < 4; ++sh) { rowWord[sh] = at; at += rows[sh].size(); }
+        T.words.assign(at, 0);
+        int32_t* ints = (int32_t*)T.words.data();
+        for (int sh = 0; sh < 4; ++sh) {
+            int32_t off = 0;
+            for (size_t q = 0; q < nf; ++q) {
+                ints[(3 * sh + 0) * nf + q] = lo[sh][q];
+                ints[(3 * sh + 1) * nf + q] = hi[sh][q];
+                ints[(3 * sh + 2) * nf + q] = off;
+                off += hi[sh][q] - lo[sh][q];
+            }
+            if (!rows[sh].empty()) std::memcpy(T.words.data() + rowWord[sh], rows[sh].data(), sizeof(double) * rows[sh].size());
+        }
+        return std::string();
+    };
+    T.launch = [&](int sh, const DevShape& F, const UnpackGroupDev& G, const int64_t* table, int64_t nEntries,
+                   const EnergyEntry* entries, double* sums, hipStream_t st) {
+        return launch_filterbank_energy(F, G.joint, n_filters, (const int*)table + (size_t)3 * sh * n_filters,
+                                        (const double*)(table + rowWord[sh]), nEntries, entries, G.oscale, G.joint ? G.ms : nullptr,
+                                        G.sf, G.ba, G.mant, sums, st);
+    };
+    return energy_frames_window(s, T, mix, n_items, file, start, n_frames, hop, n_channels_out, format, out, stream);
+}
+
 }  // namespace
 
 extern "C" {
+
+int mrc_filterbank_line_weights(double sample_rate, int a, int b, int n_filters, const double* point_hz, int norm,
+                                int32_t* line_lo, int32_t* line_hi, int64_t weight_cap, double* weight, int64_t* n_weights) {
+    const char* const fn = "mrc_filterbank_line_weights: ";
+    std::vector<double> rows;
+    const std::string refusal = filterbank_line_weights(sample_rate, a, b, n_filters, point_hz, norm, line_lo, line_hi,
+                                                        weight ? &rows : nullptr, n_weights);
+    if (!refusal.empty()) return fail(nullptr, MRC_ERR_INVALID, fn + refusal);
+    if (!weight) return MRC_OK;
+    if (weight_cap < (int64_t)rows.size())
+        return fail(nullptr, MRC_ERR_INVALID, fn + ("weight_cap " + std::to_string(weight_cap) + " is below the " +
+                                                    std::to_string(rows.size()) + " weights of the rows"));
+    if (!rows.empty()) std::memcpy(weight, rows.data(), sizeof(double) * rows.size());
+    return MRC_OK;
+}
+
+int mrc_pac_store_filterbank_window(mrc_pac_store* s, int mix, int64_t n_items, const int64_t* file, const int64_t* start,
+                                    int64_t n_frames, int64_t hop, int n_filters, const double* point_hz, int norm,
+                                    int n_channels_out, int format, void* out, void* stream) {
+    return filterbank_window(s, mix, n_items, file, start, n_frames, hop, n_filters, point_hz, norm, n_channels_out, format, out,
+                             stream);
+}
 
 int mrc_band_line_ranges(double sample_rate, int a, int b, int n_bands, const double* edge_hz, int32_t* line_lo) {
     const std::string refusal = band_line_ranges(sample_rate, a, b, n_bands, edge_hz, line_lo);

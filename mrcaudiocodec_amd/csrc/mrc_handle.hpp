@@ -378,7 +378,8 @@ struct mrc_pac_store {
     int64_t stats[4] = {0, 0, 0, 0}; // last decode_window: chunks parsed, decode_kernel launches, slabs, plan bytes uploaded
     double ms[4] = {0, 0, 0, 0};     // ... plan upload | unpack | synthesis | window_out_kernel (resampled: resample_out_kernel)
                                      // (after block_energy: block_energy_kernel launches in [1]; ms: upload | unpack | that kernel | 0;
-                                     // after band_energy_window: band_energy_kernel launches; upload | unpack | band sums | frames)
+                                     // after band_energy_window: band_energy_kernel launches; upload | unpack | band sums | frames;
+                                     // after filterbank_window: the same with filterbank_energy_kernel and the filter sums)
 };
 
 struct mrc_handle {

@@ -328,6 +328,14 @@ hipError_t launch_block_energy(const DevShape& F, int D, int joint, int64_t nEnt
 hipError_t launch_band_energy(const DevShape& F, int joint, int nBands, const int* lineLo /* device */, int64_t nEntries,
                               const EnergyEntry* entries /* device */, const int* oscale, const int* msSwitch,
                               const int* scaleFactor, const int* bitAlloc, const int* mantissa, double* bandSums, hipStream_t st);
+// mrc_pac_store_filterbank_window.  filterbank_energy_kernel: F[entry.out][q] = the left fold from +0.0 over k = lo[q] ..
+// hi[q] - 1 ascending of w * x^[k]^2, the square and the product each rounded once (entries as launch_block_energy's; tab
+// (device) int32 [3][nFilters]: the shape's lo, hi and the offset of each filter's row in weight (device), whose entry
+// offset + (k - lo) is line k's weight -- mrc_filterbank_line_weights' rows; hi <= F.halfN).
+hipError_t launch_filterbank_energy(const DevShape& F, int joint, int nFilters, const int* tab /* device */,
+                                    const double* weight /* device */, int64_t nEntries, const EnergyEntry* entries /* device */,
+                                    const int* oscale, const int* msSwitch, const int* scaleFactor, const int* bitAlloc,
+                                    const int* mantissa, double* filterSums, hipStream_t st);
 // One item of band_frames_kernel: its needed blocks are tiles [edge[edge0 + t], edge[edge0 + t + 1]), t < nTiles, in DOUBLED
 // output samples, ascending and abutting; tile t's band sums of decoded channel c are row row0 + t * nch + c of B.  lo and
 // hi: output samples at or before the first and at or behind the last tile edge -- a frame's ends are clamped to them

@@ -96,6 +96,23 @@
 //     every band are decoded and not read.  Nothing depends on the grid, on which entries share the launch or on their
 //     order.
 //
+//   filterbank_energy_kernel   band_energy_kernel with a weight per line and filter (mrc_pac_store_filterbank_window):
+//       F[entry][q] = sum of w_q[k] * x^[k]^2 over lo[q] <= k < hi[q],
+//     the filters triangles that overlap, w_q, lo and hi the shape's table of mrc_filterbank_line_weights (host float64).
+//     The CONTRACT is again the order: a left fold from +0.0 over k ascending, the square rounded once, the product rounded
+//     once, then added (__dmul_rn, __dadd_rn: no fused multiply-add) -- a filter cannot be spread over lanes.  The band
+//     kernel's shape: one workgroup of 256 threads per entry, the chunk's squares staged in LDS (a line is decoded once
+//     however many filters it feeds: two inside a bank, more where filters are narrower than a line), thread q continuing
+//     filter q's fold through the chunk with its sum in a register, eight squares AND eight weights read ahead of their
+//     additions.  The weights are not staged: thread q walks its own row in global memory, weight[off[q] + (k - lo[q])], eight
+//     consecutive doubles per step.  A shape's rows are under 20 KiB (at most 2 halfN + 2 nFilters weights), the same for
+//     every workgroup of the launch, so after the first they come from L2; neighbouring threads' addresses lie a row
+//     apart, which costs a cache line per thread and step where LDS staging would cost a second barrier pair and, for
+//     overlapping rows, an LDS layout per chunk.  Rows are short (89 lines at most for 80 mel filters on 1024 lines, the band
+//     kernel's longest chain is 363), so the fold is shorter than the band kernel's however the weights arrive.  tab is
+//     int32 [3][nFilters]: lo, hi, off.  An empty row (a filter wholly above the last line) is +0.0.  Nothing depends on
+//     the grid, on which entries share the launch or on their order.
+//
 //   band_frames_kernel   B laid on the call's frame grid.  One thread per output value, frames fastest -- the flat index
 //     is the output's own, so a wave stores 64 consecutive values -- and a row is (item, output channel, band).  The
 //     item's needed blocks are abutting tiles in DOUBLED output samples (a tile edge is a half sample); the thread finds
@@ -457,6 +474,55 @@ __global__ __launch_bounds__(kBandThreads) void band_energy_kernel(const unsigne
     if (t < nBands) bandSums[e.out * nBands + t] = acc;
 }
 
+// tab: the shape's int32 [3][nFilters] -- lo, hi and the offset of filter q's row in weight; weight[offset + (k - lo)] is
+// line k's weight in filter q (mrc_filterbank_line_weights).  hi <= fullLines.
+__global__ __launch_bounds__(kBandThreads) void filterbank_energy_kernel(const unsigned char* __restrict__ bandOfLine, int nb,
+                                                                        int fullLines, int nScaleBits, int joint, int nFilters,
+                                                                        const int* __restrict__ tab,
+                                                                        const double* __restrict__ weight, int64_t nEntries,
+                                                                        const EnergyEntry* __restrict__ entries,
+                                                                        const int* __restrict__ oscale,
+                                                                        const int* __restrict__ msSwitch,
+                                                                        const int* __restrict__ scaleFactor,
+                                                                        const int* __restrict__ bitAlloc,
+                                                                        const int* __restrict__ mantissa,
+                                                                        double* __restrict__ filterSums) {
+    __shared__ double sq[kBandChunk];
+    const int t = threadIdx.x;
+    const EnergyEntry e = entries[blockIdx.x];
+    const EntryLines L(e, bandOfLine, nb, fullLines, nScaleBits, joint, oscale, msSwitch, scaleFactor, bitAlloc, mantissa);
+    // thread t folds filter t (nFilters <= MRC_MAX_STORE_BANDS = kBandThreads: the launcher refuses more)
+    const bool mine = t < nFilters;
+    const int lo = mine ? tab[t] : 0, hi = mine ? min(tab[nFilters + t], fullLines) : 0;
+    const int rel = (mine ? tab[2 * nFilters + t] : 0) - lo;         // weight[rel + k]: line k's weight
+    double acc = 0.0;
+    for (int c0 = 0; c0 < fullLines; c0 += kBandChunk) {
+        const int c1 = min(c0 + kBandChunk, fullLines);
+        if (c0) __syncthreads();                                     // (the folds of the chunk before are done with sq)
+        for (int k = c0 + t; k < c1; k += kBandThreads) {
+            const double x = L.line(k);
+            sq[k - c0] = x * x;
+        }
+        __syncthreads();
+        // the fold, in order: the product rounded once, then added; eight squares and eight weights are read ahead of their
+        // additions (one LDS and one memory round trip per eight lines, not per line)
+        int k = max(lo, c0);
+        const int kEnd = min(hi, c1);
+        for (; k + 8 <= kEnd; k += 8) {
+            double v[8], wt[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                v[u] = sq[k - c0 + u];
+                wt[u] = weight[rel + k + u];
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) acc = __dadd_rn(acc, __dmul_rn(wt[u], v[u]));
+        }
+        for (; k < kEnd; ++k) acc = __dadd_rn(acc, __dmul_rn(weight[rel + k], sq[k - c0]));
+    }
+    if (mine) filterSums[e.out * nFilters + t] = acc;
+}
+
 constexpr int kFrameThreads = 256;
 
 __global__ __launch_bounds__(kFrameThreads) void band_frames_kernel(const BandItem* __restrict__ items,
@@ -589,6 +655,18 @@ hipError_t launch_band_energy(const DevShape& F, int joint, int nBands, const in
     hipLaunchKernelGGL(band_energy_kernel, dim3((unsigned)nEntries), dim3(kBandThreads), 0, st, F.bandOfLine, F.nBands, F.halfN,
                        F.nScaleBits, joint, nBands, lineLo, nEntries, entries, oscale, msSwitch, scaleFactor, bitAlloc, mantissa,
                        bandSums);
+    return hipGetLastError();
+}
+
+hipError_t launch_filterbank_energy(const DevShape& F, int joint, int nFilters, const int* tab, const double* weight,
+                                    int64_t nEntries, const EnergyEntry* entries, const int* oscale, const int* msSwitch,
+                                    const int* scaleFactor, const int* bitAlloc, const int* mantissa, double* filterSums,
+                                    hipStream_t st) {
+    if (nEntries <= 0) return hipSuccess;
+    if (nFilters < 1 || nFilters > kBandThreads || nEntries > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(filterbank_energy_kernel, dim3((unsigned)nEntries), dim3(kBandThreads), 0, st, F.bandOfLine, F.nBands,
+                       F.halfN, F.nScaleBits, joint, nFilters, tab, weight, nEntries, entries, oscale, msSwitch, scaleFactor,
+                       bitAlloc, mantissa, filterSums);
     return hipGetLastError();
 }
 

@@ -77,6 +77,15 @@ the same sums split by frequency band and laid on a frame grid -- the coded file
         edges = critical_band_edges(48000)                                     # 0, 100, 200, ... 15500, 24000
         e = store.band_energy_window(files, starts, 94, 512, edges)            # [len(files)][channels][25][94], on the GPU
         logspec = torch.log10(e.clamp_min(1e-12))
+
+filterbank_window (mrc_pac_store_filterbank_window) is that call with overlapping triangular filters in place of the
+rectangular bands -- a mel front end without a decode or an STFT.  A line's weight in a filter is the triangle's mean over the
+line's own frequency interval, so a filter narrower than a short block's line spacing is never empty and the log needs no
+-inf guard beyond digital silence:
+
+        points = mel_points(80, 0.0, 24000.0)                                  # 82 points: HTK mel, 80 filters
+        e = store.filterbank_window(files, starts, 100, 480, points)           # [len(files)][channels][80][100], on the GPU
+        logmel = torch.log(e.clamp_min(1e-10))
 """
 import ctypes as C
 
@@ -360,6 +369,96 @@ def band_line_ranges(sample_rate, a, b, band_edges_hz):
         err.code = rc
         raise err
     return lo
+
+
+MEL_SCALES = ("htk", "slaney")
+FILTER_NORMS = {None: _lib.MRC_FILTER_NORM_NONE, "slaney": _lib.MRC_FILTER_NORM_SLANEY}
+
+
+def hz_to_mel(f, scale="htk"):
+    """"htk": 2595 log10(1 + f / 700).  "slaney": f / (200 / 3) below 1000 Hz, 15 + 27 ln(f / 1000) / ln 6.4 above.  float64"""
+    f = np.asarray(f, dtype=np.float64)
+    if scale == "htk":
+        return 2595.0 * np.log10(1.0 + f / 700.0)
+    return np.where(f < 1000.0, f / (200.0 / 3.0), 15.0 + 27.0 * np.log(np.maximum(f, 1000.0) / 1000.0) / np.log(6.4))
+
+
+def mel_to_hz(m, scale="htk"):
+    """hz_to_mel's inverse"""
+    m = np.asarray(m, dtype=np.float64)
+    if scale == "htk":
+        return 700.0 * (10.0 ** (m / 2595.0) - 1.0)
+    return np.where(m < 15.0, m * (200.0 / 3.0), 1000.0 * np.exp(np.maximum(m - 15.0, 0.0) * (np.log(6.4) / 27.0)))
+
+
+def mel_points(n_filters, f_min, f_max, scale="htk"):
+    """the points of a mel filter bank for filterbank_window -> float64 [n_filters + 2]: equally spaced in mel from f_min to
+    f_max (scale "htk" or "slaney": hz_to_mel), the first and the last set to f_min and f_max exactly; filter q is the
+    triangle over points q, q + 1, q + 2.  NumPy only.  ValueError for arguments that make no bank."""
+    if not _is_int(n_filters) or not 1 <= int(n_filters) <= MAX_BANDS:
+        raise ValueError("mel_points: n_filters must be an int in 1..%d, got %r" % (MAX_BANDS, n_filters))
+    if not isinstance(scale, str) or scale not in MEL_SCALES:
+        raise ValueError('mel_points: scale must be "htk" or "slaney", got %r' % (scale,))
+    for name, v in (("f_min", f_min), ("f_max", f_max)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise ValueError("mel_points: %s must be a finite number, got %r" % (name, v))
+    f_min, f_max = float(f_min), float(f_max)
+    if f_min < 0 or not f_min < f_max:
+        raise ValueError("mel_points: 0 <= f_min < f_max is required, got %r and %r" % (f_min, f_max))
+    points = mel_to_hz(np.linspace(float(hz_to_mel(f_min, scale)), float(hz_to_mel(f_max, scale)), int(n_filters) + 2), scale)
+    points[0], points[-1] = f_min, f_max
+    if not np.all(np.diff(points) > 0):
+        raise ValueError("mel_points: %d filters from %r to %r Hz are too close to tell apart in float64" % (n_filters, f_min, f_max))
+    return points
+
+
+def check_filter_points(points_hz, what="filterbank_window"):
+    """filter points in Hz -> float64 [filters + 2], else ValueError: 1 to MAX_BANDS filters, finite, from 0 up, strictly
+    increasing"""
+    try:
+        points = np.ascontiguousarray(np.asarray(points_hz, dtype=np.float64).reshape(-1))
+    except (TypeError, ValueError):
+        raise ValueError("%s: points_hz must be a sequence of frequencies in Hz, got %r" % (what, points_hz))
+    if not 3 <= points.size <= MAX_BANDS + 2:
+        raise ValueError("%s: points_hz must hold 3 to %d points (1 to %d filters), got %d" % (what, MAX_BANDS + 2, MAX_BANDS, points.size))
+    if not np.all(np.isfinite(points)):
+        raise ValueError("%s: points_hz must be finite, got %r" % (what, points_hz))
+    if points[0] < 0 or not np.all(np.diff(points) > 0):
+        raise ValueError("%s: points_hz must start at or above 0 and increase strictly, got %r" % (what, points_hz))
+    return points
+
+
+def check_filter_norm(norm, what="filterbank_window"):
+    """norm (None or "slaney") -> its MRC_FILTER_NORM_* value, else ValueError"""
+    if norm is not None and not (isinstance(norm, str) and norm in FILTER_NORMS):
+        raise ValueError('%s: norm must be None or "slaney", got %r' % (what, norm))
+    return FILTER_NORMS[norm]
+
+
+def filterbank_line_weights(sample_rate, a, b, points_hz, norm=None):
+    """mrc_filterbank_line_weights -> (lo int32 [filters], hi int32 [filters], [row arrays]): filter q of a block of shape
+    (a, b) reads MDCT lines [lo[q], hi[q]) with the float64 weights rows[q], the triangle's mean over each line's interval
+    [k d, (k + 1) d), d = (sample_rate / ((a + b) / 2)) / 2.  No handle, no GPU.  ValueError for a norm that is none;
+    MrcError where the library refuses."""
+    norm = check_filter_norm(norm, "filterbank_line_weights")
+    points = np.ascontiguousarray(np.asarray(points_hz, dtype=np.float64).reshape(-1))
+    n = int(points.size) - 2
+    lo, hi = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+    count = np.zeros(1, np.int64)
+
+    def call(cap, weight):
+        rc = lib.mrc_filterbank_line_weights(float(sample_rate), int(a), int(b), n, points.ctypes.data, norm, lo.ctypes.data,
+                                             hi.ctypes.data, cap, weight, count.ctypes.data)
+        if rc:
+            err = _lib.MrcError("libmrc_hip error %d: %s" % (rc, lib.mrc_last_error(None).decode()))
+            err.code = rc
+            raise err
+
+    call(0, None)                                                   # sizes only
+    weight = np.zeros(max(int(count[0]), 1), np.float64)
+    call(int(count[0]), weight.ctypes.data)
+    at = np.concatenate([[0], np.cumsum(hi[:n] - lo[:n])])
+    return lo[:n], hi[:n], [weight[at[q]:at[q + 1]] for q in range(n)]
 
 
 def _formats():
@@ -668,21 +767,12 @@ class PacStore:
             pad(files), pad(starts), pad(gains), window, channels, fmt, out.data_ptr() if out.numel() else None, stream or None))
         return out
 
-    def band_energy_window(self, files, starts, n_frames, hop, band_edges_hz, channels=None, dtype=None, out=None, stream=None,
-                           mix=None):
-        """mrc_pac_store_band_energy_window -> a torch tensor [n][channels][n_bands][n_frames] on the handle's device: the
-        energy that band q = [band_edges_hz[q], band_edges_hz[q + 1]) holds in frame j = samples [starts[i] + j hop,
-        starts[i] + (j + 1) hop) of file files[i] (decode_window's full-rate coordinates; starts may be negative or past the
-        end, a frame outside the file's blocks is 0), from the MDCT lines alone: each block's sum of squares per band, spread
-        evenly over the block's tile (levels.LevelMap's), so that bands [0, fs / 2] and frames over the whole file add up to
-        the decoded signal's sum of squares.  Only the blocks whose tile a frame touches are parsed; nothing is synthesised.
-        band_edges_hz: 2 to 257 increasing frequencies from 0 up (critical_band_edges(sample_rate): the codec's own bands);
-        a band narrower than a short block's line spacing may hold no line of such a block and then reads 0 there.
-        dtype: torch.float32 (the default) or torch.float64 (every bit defined: see the header).  channels, out, stream: as
-        decode_window's; mix: None (every channel), "mid", "left" or "right" (one channel, channels None or 1).  Argument
-        errors are ValueErrors before any library call."""
+    def _energy_window(self, what, table, launch, files, starts, n_frames, hop, channels, dtype, out, stream, mix):
+        """band_energy_window and filterbank_window: the checks in the one order, the output tensor, the call.  table() checks
+        the call's bands or filters where the band call always has and -> (what launch receives for them, the rows of an
+        output channel); launch(mix, n, files, starts, n_frames, hop, table, channels, format, out, stream) -> the library's
+        return code."""
         import torch
-        what = "band_energy_window"
         mix = check_mix(mix, channels, what)
         if mix is not None:
             channels = 1
@@ -696,7 +786,7 @@ class PacStore:
         n, n_frames, hop = files.size, int(n_frames), int(hop)
         if n_frames * hop > 1 << 62:
             raise ValueError("%s: n_frames * hop must not exceed 2^62, got %d * %d" % (what, n_frames, hop))
-        edges = check_band_edges(band_edges_hz, what)
+        table, n_rows = table()
         if dtype is None:
             dtype = torch.float32 if out is None else out.dtype
         if dtype not in (torch.float32, torch.float64):
@@ -712,7 +802,7 @@ class PacStore:
         if mix is None and n and int(self.n_channels[files].max()) > channels:
             raise ValueError("%s: a stereo file in a one-channel call (channels=1): ask for 2 channels or a mix" % what)
         dev = torch.device("cuda", self._handle.cfg.device_id)
-        shape = (n, channels, edges.size - 1, n_frames)
+        shape = (n, channels, n_rows, n_frames)
         if out is None:
             out = torch.empty(shape, dtype=dtype, device=dev)
         elif not isinstance(out, torch.Tensor) or out.dtype != dtype or tuple(out.shape) != shape or out.device != dev \
@@ -720,10 +810,49 @@ class PacStore:
             raise ValueError("%s: out must be a contiguous %s tensor of shape %s on %s" % (what, dtype, shape, dev))
         if stream is None:
             stream = torch.cuda.current_stream(dev).cuda_stream
-        self._handle._check(lib.mrc_pac_store_band_energy_window(
-            self._s, _lib.MRC_MIX_EACH if mix is None else mix, n, files.ctypes.data, starts.ctypes.data, n_frames, hop,
-            edges.size - 1, edges.ctypes.data, channels, _formats()[dtype], out.data_ptr() if out.numel() else None, stream or None))
+        self._handle._check(launch(_lib.MRC_MIX_EACH if mix is None else mix, n, files.ctypes.data, starts.ctypes.data, n_frames, hop,
+                                   table, channels, _formats()[dtype], out.data_ptr() if out.numel() else None, stream or None))
         return out
+
+    def band_energy_window(self, files, starts, n_frames, hop, band_edges_hz, channels=None, dtype=None, out=None, stream=None,
+                           mix=None):
+        """mrc_pac_store_band_energy_window -> a torch tensor [n][channels][n_bands][n_frames] on the handle's device: the
+        energy that band q = [band_edges_hz[q], band_edges_hz[q + 1]) holds in frame j = samples [starts[i] + j hop,
+        starts[i] + (j + 1) hop) of file files[i] (decode_window's full-rate coordinates; starts may be negative or past the
+        end, a frame outside the file's blocks is 0), from the MDCT lines alone: each block's sum of squares per band, spread
+        evenly over the block's tile (levels.LevelMap's), so that bands [0, fs / 2] and frames over the whole file add up to
+        the decoded signal's sum of squares.  Only the blocks whose tile a frame touches are parsed; nothing is synthesised.
+        band_edges_hz: 2 to 257 increasing frequencies from 0 up (critical_band_edges(sample_rate): the codec's own bands);
+        a band narrower than a short block's line spacing may hold no line of such a block and then reads 0 there.
+        dtype: torch.float32 (the default) or torch.float64 (every bit defined: see the header).  channels, out, stream: as
+        decode_window's; mix: None (every channel), "mid", "left" or "right" (one channel, channels None or 1).  Argument
+        errors are ValueErrors before any library call."""
+        def edges():
+            e = check_band_edges(band_edges_hz, "band_energy_window")
+            return e, e.size - 1
+        launch = lambda mix, n, files, starts, n_frames, hop, e, channels, fmt, out, stream: lib.mrc_pac_store_band_energy_window(
+            self._s, mix, n, files, starts, n_frames, hop, e.size - 1, e.ctypes.data, channels, fmt, out, stream)
+        return self._energy_window("band_energy_window", edges, launch, files, starts, n_frames, hop, channels, dtype, out, stream, mix)
+
+    def filterbank_window(self, files, starts, n_frames, hop, points_hz, norm=None, channels=None, dtype=None, out=None,
+                          stream=None, mix=None):
+        """mrc_pac_store_filterbank_window -> a torch tensor [n][channels][n_filters][n_frames] on the handle's device:
+        band_energy_window with a bank of overlapping triangular filters in place of the rectangular bands -- a mel spectrogram
+        from the MDCT lines alone.  points_hz: n_filters + 2 increasing frequencies from 0 up (mel_points(80, 0, fs / 2)); filter
+        q rises from points_hz[q] to 1 at points_hz[q + 1] and falls to points_hz[q + 2].  A line's weight is the triangle's mean
+        over the line's own frequency interval (filterbank_line_weights), so a filter narrower than a short block's line
+        spacing still reads its share of the line it lies in: no filter is empty, no frame inside the file reads 0 for want
+        of a line.  norm: None, or "slaney" (every filter times 2 / its width in Hz).  Frames, starts, channels, mix, dtype
+        (torch.float32 by default; torch.float64: every bit defined, see the header), out and stream are
+        band_energy_window's, and so is what the estimate resolves: a block's tile in time, a block's line spacing in
+        frequency -- this is not an STFT.  Log compression is the caller's: torch.log(e.clamp_min(1e-10)).  Argument errors
+        are ValueErrors before any library call."""
+        def table():
+            points = check_filter_points(points_hz, "filterbank_window")
+            return (points, check_filter_norm(norm, "filterbank_window")), points.size - 2
+        launch = lambda mix, n, files, starts, n_frames, hop, t, channels, fmt, out, stream: lib.mrc_pac_store_filterbank_window(
+            self._s, mix, n, files, starts, n_frames, hop, t[0].size - 2, t[0].ctypes.data, t[1], channels, fmt, out, stream)
+        return self._energy_window("filterbank_window", table, launch, files, starts, n_frames, hop, channels, dtype, out, stream, mix)
 
     def block_energy(self, rate_divisor=1, mix=None, files=None):
         """mrc_pac_store_block_energy -> (entry_offset [n + 1], blocks [entries][3] (block_start, a, b), energy [entries]):
@@ -785,7 +914,8 @@ class PacStore:
         the units' ratio indices and the table of ratios, and ms["window_out"] is resample_multi_sum_out_kernel's.  After levels() or
         block_energy(): decode_launches counts block_energy_kernel launches, ms["synthesis"] is that kernel's time and
         ms["window_out"] is 0.  After band_energy_window(): decode_launches counts band_energy_kernel launches,
-        ms["synthesis"] is the band sums' time (that kernel) and ms["window_out"] the frame assembly's (band_frames_kernel)."""
+        ms["synthesis"] is the band sums' time (that kernel) and ms["window_out"] the frame assembly's (band_frames_kernel);
+        after filterbank_window() the same with filterbank_energy_kernel in band_energy_kernel's place."""
         st, ms = np.zeros(4, np.int64), np.zeros(4, np.float64)
         self._handle._check(lib.mrc_pac_store_stats(self._s, st.ctypes.data, ms.ctypes.data))
         r = {k: int(v) for k, v in zip(STAT_NAMES, st)}
