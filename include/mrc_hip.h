@@ -1271,6 +1271,67 @@ int mrc_pac_store_decode_window_speeds(mrc_pac_store* s, int rate_divisor, int m
                                        int n_channels_out, int format, void* out /* DEVICE [n_items][n_channels_out][window] */,
                                        void* stream);
 
+/* Reverberation: window terms convolved with room impulse responses before they are mixed (speech through a room over dry
+ * noise), in the call that reads them -- no per-term tensor, no torch.fft.
+ * THE BANK.  mrc_pac_store_set_irs gives the store a bank of n_irs impulse responses: response j is the host float64 taps
+ * [ir_offset[j], ir_offset[j + 1]), ir_offset[0] == 0, each of 1..MRC_MAX_STORE_IR_TAPS finite taps (2^17: 2.7 s at 48 kHz),
+ * SAMPLED AT THE OUTPUT RATE OF THE TERMS that will name it (after the rate divisor and the resample or speed ratio: the rate
+ * the model sees, and the physical order -- speed, then room).  The call replaces the previous bank; n_irs == 0 drops it.  The
+ * transforms of the bank's partitions (MRC_STORE_REVERB_BLOCK taps each) are computed once, on the device, by the forward
+ * kernel the signal uses, and stay resident: 32 bytes of device memory per tap, a response's length rounded up to whole
+ * partitions (plus the allocator's headroom of one eighth).  MRC_ERR_INVALID naming the argument, the previous bank kept:
+ * n_irs < 0, ir_offset or taps NULL with responses present, ir_offset[0] != 0, a length outside the range (the response is
+ * named), a tap that is not finite (its index is named).  A failed allocation is MRC_ERR_NOMEM and leaves the store WITHOUT a
+ * bank.  Synchronises the handle's stream.  mrc_pac_store_ir_info: the count and (ir_len, nullable, [n_irs]) the lengths.
+ *
+ * THE CALL.  mrc_pac_store_decode_window_reverb takes every argument of mrc_pac_store_decode_window_speeds and ir_of [n_terms]:
+ * -1, the term is not convolved, or the index of a response of the bank.
+ *   Lpre     (the longest response that the call's terms name) - 1
+ *   w_k      term k's dry signal: the MRC_WINDOW_F64 window the speeds call's one-term row at gain 1.0 gives for (file[k],
+ *            start[k] - Lpre, window + Lpre) at the term's rate divisor, mix, ratio and band gains.  Those windows are functions
+ *            of the absolute output index, so a slice of w_k is the existing window bit for bit.
+ *   y_k[t]   = sum over j of h[j] * w_k[Lpre + t - j], 0 <= t < window: the wet signal of a convolved term.  Outside the file the
+ *            dry signal is zero as ever, so the wet signal rings len(h) - 1 samples past the file's end, and a window placed in
+ *            that tail reads it.
+ *   row i    the left fold from +0.0, over its terms in the order given, of gain[k] * (y_k | the dry window), every product
+ *            rounded once, then added: mrc_pac_store_decode_window_sum's rule.  MRC_WINDOW_F32 / _PCM16 convert that sum.
+ * Bit for bit: a term with ir_of -1 contributes its existing window; a row none of whose terms is convolved equals
+ * mrc_pac_store_decode_window_speeds on the same arguments in all three formats (a call without any convolved term IS that
+ * call).  A convolved term is computed by overlap-save in float64 -- a hop of B = MRC_STORE_REVERB_BLOCK samples, transforms of
+ * N = 2 B points, the segments anchored at the term's own window start -- and is defined to a tolerance, the transform's
+ * rounding being the implementation's: |error| <= K 2^-52 log2(N) sum|h| max|w_k| per term, times |gain|, K measured in
+ * tests/test_gpu_store_reverb.py.  But to the bit it does not depend on the order of the items, on what shares the call, on
+ * the slab size, on the response's index or company in the bank, and repeats from call to call.  A two-channel term's channels
+ * ride as the real and imaginary part of one transform (h is real); a one-channel term leaves the imaginary part zero.
+ * MRC_ERR_INVALID naming the argument, before any device work and with `out` untouched: every refusal of the speeds call;
+ * ir_of NULL with terms present; an index below -1 or outside the bank (the term is named); an index >= 0 while the store has
+ * no bank; window + Lpre beyond 2^40.  n_items == 0 or window == 0: MRC_OK, nothing written.
+ * Slabs: a run of whole rows whose terms, each counted at window + Lpre, sum to at most MRC_OPT_STORE_SLAB_SAMPLES (one row at
+ * least; 0: one slab).  Per slab the existing machinery decodes the terms, in one slab of its own whatever their intermediate
+ * spans (planes of up to `down / up` times the slab under a resample ratio), into a scratch buffer the handle owns (8 bytes per
+ * sample and output channel), then reverb_forward_kernel and reverb_fold_kernel run on it on the same stream; the spectra
+ * of the convolved terms' segments take 32 bytes per sample of window + len(h) rounded up to whole blocks.
+ * mrc_pac_store_stats then describes the whole call (the chunks are those of the lengthened spans; ms[3] includes the two
+ * reverb kernels); mrc_pac_store_reverb_ms gives those two apart: ms[0] reverb_forward_kernel, ms[1] reverb_fold_kernel (zeros
+ * after a call without a convolved term). */
+#ifndef MRC_STORE_REVERB_BLOCK   /* (a build-time experiment may set 2048: transforms of 4096 points, 144 KiB of LDS) */
+#define MRC_STORE_REVERB_BLOCK 1024
+#endif
+#define MRC_MAX_STORE_IR_TAPS (1 << 17)
+int mrc_pac_store_set_irs(mrc_pac_store* s, int64_t n_irs, const int64_t* ir_offset /*[n_irs+1]*/, const double* taps /* HOST */);
+int mrc_pac_store_ir_info(mrc_pac_store* s, int64_t* n_irs, int64_t* ir_len /*[n_irs], nullable*/);
+int mrc_pac_store_decode_window_reverb(mrc_pac_store* s, int rate_divisor, int mix, int n_ratios,
+                                       const int32_t* ratio_up /*[n_ratios]*/, const int32_t* ratio_down /*[n_ratios]*/, int zeros,
+                                       double rolloff, int n_bands /* 0: no band gains */, const double* edge_hz /*[n_bands+1]*/,
+                                       const double* band_gain /*[n_terms][n_bands]*/, int64_t n_items,
+                                       const int64_t* term_offset /*[n_items+1]*/, const int64_t* file /*[n_terms]*/,
+                                       const int64_t* start /*[n_terms]*/, const double* gain /*[n_terms]*/,
+                                       const int32_t* ratio_of /*[n_terms]: index into the list*/,
+                                       const int32_t* ir_of /*[n_terms]: -1 or index into the bank*/, int64_t window,
+                                       int n_channels_out, int format, void* out /* DEVICE [n_items][n_channels_out][window] */,
+                                       void* stream);
+int mrc_pac_store_reverb_ms(mrc_pac_store* s, double* ms /*[2]*/);
+
 /* Per-stage device time of the most recent timed call when timing is enabled (hipEvents on the launch stream; the call
  * then synchronises).  Timed: mrc_dev_encode / mrc_dev_encode_ex and mrc_encode_mono / mrc_encode_joint (the _blocks
  * forms: their last shape group).  Not timed: the stage calls (mrc_dev_mdct, mrc_dev_smr, mrc_dev_alloc_quant),

@@ -51,6 +51,11 @@ file is read at the output rate's ratio divided by the speed, the WAV's header c
 --start / --samples count output samples -- the whole file is n_samples_resampled of the combined ratio.  Composes with
 --sample-rate, --rate-divisor, --mix, --band-gains-db and --overlay; the overlay stays at speed 1, in the same one call.
 Refused without -d and with --band-energies.
+Through a room:  python -m mrcaudiocodec_amd.cli -d in.pac out.wav --ir room.npy  (or a mono 16-bit room.wav) convolves the file
+with that impulse response through the same store (mrc_pac_store_decode_window_reverb), last of all: at the output rate, after
+the speed.  A .npy array is taken as sampled at the output rate; a WAV is brought there from its own rate (store.ir_at_rate).
+Composes with --sample-rate, --rate-divisor, --speed, --mix, --band-gains-db, --start, --samples and --overlay; the overlay
+stays dry, in the same one call.  Refused without -d.
 Levels:  python -m mrcaudiocodec_amd.cli --levels a.pac [b.pac ...] [--levels-window N]  decodes nothing and writes nothing: per
 file one JSON line with its channels, samples, RMS level per channel (dB re full scale) and its loudest and quietest window of
 N samples (default one second) on the short-block grid with their starts, from the energies of the blocks' MDCT lines
@@ -756,6 +761,40 @@ def check_speed_args(speed, decode):
     return num, den
 
 
+def check_ir_args(ir, decode):
+    """--ir as given (None: not given) -> the path or None.  It reverberates a decode: refused without -d."""
+    if ir is not None and not decode:
+        raise ValueError("--ir reverberates a decode with an impulse response: it needs -d")
+    return ir
+
+
+def read_ir(path, rate_out):
+    """the impulse response of --ir -> float64 [taps] at rate_out Hz.  A .npy file holds a 1-D array of numbers that is taken as
+    it is (it carries no rate: it must be sampled at the output rate); anything else is a mono 16-bit PCM WAV, read with
+    read_wav and brought from its own rate to rate_out by store.ir_at_rate."""
+    from .store import check_impulse_responses, ir_at_rate
+    if str(path).lower().endswith(".npy"):
+        try:
+            taps = np.load(path, allow_pickle=False)
+        except (OSError, ValueError) as e:
+            raise ValueError("--ir: %s: %s" % (path, e))
+        try:
+            return check_impulse_responses([taps], "--ir")[1]
+        except ValueError as e:
+            raise ValueError("%s (%s)" % (e, path))
+    try:
+        rate, n_ch, num_samples, x = read_wav(path, 1)
+    except (OSError, ValueError) as e:
+        raise ValueError("--ir: %s: %s" % (path, e))
+    if n_ch != 1 or num_samples < 1:
+        raise ValueError("--ir: %s: a WAV impulse response must have one channel and at least one sample, got %d x %d"
+                         % (path, n_ch, num_samples))
+    try:
+        return ir_at_rate(x[0, :num_samples], int(rate), int(rate_out))
+    except ValueError as e:
+        raise ValueError("--ir: %s: %s" % (path, e))
+
+
 CODEC_SETTINGS = ("sample_rate", "n_mdct_lines", "n_scale_bits", "n_mant_size_bits")   # what a .pac header says of its codec
 
 
@@ -775,7 +814,7 @@ def _levels_of_mix(store, rate_divisor, mix):
 
 
 def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=1, mix=None, sample_rate=None, overlay=None,
-                    band_gains=None, speed=None):
+                    band_gains=None, speed=None, ir=None):
     """excerpt: None (the whole file, mrc_decode_pac_pcm16) or (start, samples): that many samples from sample `start` on
     (samples None: to the end of the file), decoded through a one-file PacStore -- only the blocks the excerpt overlaps are
     parsed and synthesised; what lies outside the file is silence.  rate_divisor 2 or 4: at that fraction of the sample rate,
@@ -794,6 +833,9 @@ def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=
     as well: start and samples count output samples, the whole file is n_samples_resampled of the combined ratio, the WAV's
     header carries the output rate unchanged; the overlay stays at speed 1, a second term of the same one call, its level set
     against the stretch of source under the excerpt (PacStore.source_spans).
+    ir: None or the path of an impulse response (read_ir: a .npy array at the output rate, or a mono 16-bit WAV brought to it):
+    the file convolved with it through the store as well (PacStore.decode_window(ir_index=)), last of all -- at the output rate,
+    after the speed; the overlay stays dry, the same one call.  The output keeps the length it has without --ir.
     -> int16 [nCh][samples] as written."""
     with open(pac_path, "rb") as fp:
         buf = fp.read()
@@ -827,8 +869,9 @@ def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=
         except ValueError as e:
             raise ValueError("--speed: %s" % e)
     if (rate_divisor != 1 or mix is not None or resample is not None or overlay is not None or band_gains is not None
-            or speed is not None) and excerpt is None:
+            or speed is not None or ir is not None) and excerpt is None:
         excerpt = (0, None)
+    taps = None if ir is None else read_ir(ir, cfg.sample_rate // rate_divisor if sample_rate is None else int(sample_rate))
     h = Handle(sample_rate=cfg.sample_rate, n_mdct_lines=cfg.n_mdct_lines, n_scale_bits=cfg.n_scale_bits,
                n_mant_size_bits=cfg.n_mant_size_bits, device_id=device_id)
     try:
@@ -845,6 +888,9 @@ def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=
                 shaped = {} if band_gains is None else dict(band_edges_hz=band_gains[0])
                 if speed is not None:                    # the file at its speed; the overlay, a second term, at speed 1
                     shaped.update(speed_factors=[speed, (1, 1)], speed_index=[0] if overlay is None else [[0, 1]])
+                if taps is not None:                     # the file through the room; the overlay dry
+                    store.set_impulse_responses([taps])
+                    shaped.update(ir_index=[0] if overlay is None else [[0, -1]])
                 if overlay is None:
                     if band_gains is not None:
                         shaped["band_gains"] = band_gains[1]
@@ -1010,6 +1056,10 @@ def main(argv=None):
                     help="with -d: play the file NUM/DEN times as fast (11/10: speed perturbation) through the resident store; the "
                          "WAV's rate is unchanged, --start / --samples count output samples; composes with --sample-rate, "
                          "--rate-divisor, --mix, --band-gains-db and --overlay (the overlay stays at speed 1)")
+    ap.add_argument("--ir", default=None, metavar="FILE",
+                    help="with -d: convolve the decoded file with the impulse response in FILE, a .npy float array sampled at the "
+                         "output rate or a mono 16-bit WAV (brought to the output rate), through the resident store on the device; "
+                         "composes with --sample-rate, --speed, --mix, --overlay (the overlay stays dry), --start and --samples")
     ap.add_argument("--levels", nargs="+", default=None, metavar="PAC",
                     help="no src, no dst: print one JSON line per .pac file with its channels, samples, RMS level per channel "
                          "(dB re full scale) and its loudest and quietest window on the short-block grid, from the block "
@@ -1051,7 +1101,7 @@ def main(argv=None):
         given_energies = dict(
             given, **{"--levels": a.levels is not None, "--levels-window": a.levels_window is not None,
                       "--rate-divisor": a.rate_divisor is not None, "--band-gains-db": a.band_gains_db is not None,
-                      "--speed": a.speed is not None})
+                      "--speed": a.speed is not None, "--ir": a.ir is not None})
         bank = check_filterbank_energies_args(a.filterbank_energies, a.hop, a.mel, a.f_min, a.f_max, a.mel_scale, a.filter_points,
                                               a.filter_norm, dict(given_energies, **{"--band-energies": a.band_energies,
                                                                                      "--band-edges": a.band_edges is not None}))
@@ -1066,6 +1116,7 @@ def main(argv=None):
         overlay = check_overlay_args(a.overlay, a.snr_db, a.overlay_start, a.decode)
         band_gains = check_band_gains_db_args(a.band_gains_db, a.decode)
         speed = check_speed_args(a.speed, a.decode)
+        ir = check_ir_args(a.ir, a.decode)
         if levels is not None:
             from .store import check_levels_mix
             check_levels_mix(mix, "--mix")
@@ -1134,7 +1185,7 @@ def main(argv=None):
         return
     if a.decode:
         try:
-            pcm = decode_pac_file(a.src, a.dst, a.device, excerpt, rate_divisor, mix, sample_rate, overlay, band_gains, speed)
+            pcm = decode_pac_file(a.src, a.dst, a.device, excerpt, rate_divisor, mix, sample_rate, overlay, band_gains, speed, ir)
         except ValueError as e:
             ap.error(str(e))
         print("%s: %d channels x %d samples" % (a.dst, pcm.shape[0], pcm.shape[1]))

@@ -60,6 +60,11 @@
 // synthesis launches and their second plane at x + planeLen stay as they are.  The terms' ratio indices and the table of
 // the ratios (SpeedRatio) ride in the slab's staging copy; SumTerm and WindowItem are the other calls', unchanged.
 //
+// decode_window_reverb, those rows with a room impulse response per term: NOT another spec of decode_windows but a slab loop
+// around the rows call, which decodes every term of a slab over its span lengthened by the pre-roll into a float64 scratch
+// buffer; reverb_forward_kernel and reverb_fold_kernel (mrc_kernels_reverb.hip: partitioned overlap-save) then make the rows.
+// The bank's partition spectra live in the store (set_irs), made once by the same forward kernel.
+//
 // block_energy, ((a + b) / D) * the sum of squares of a block's first 1 / D decoded lines, per channel or for the mid, for
 // every block of the selected files: the same slab plan (stage_slab, parse_slab) over runs of whole blocks instead of the
 // blocks of windows, then block_energy_kernel per group (mrc_kernels_store.hip) in place of planes, synthesis and output.
@@ -1254,6 +1259,264 @@ int mrc_pac_store_decode_window_speeds(mrc_pac_store* s, int rate_divisor, int m
     const RatioArgs ratios{n_ratios, ratio_up, ratio_down, ratio_of};
     return decode_window_rows(s, kWinSpeeds, rate_divisor, mix, 1, 1, zeros, rolloff, n_bands == 0 ? nullptr : &bands, n_items, term_offset,
                               file, start, gain, window, n_channels_out, format, out, stream, &ratios);
+}
+
+}  // extern "C"
+
+namespace {
+
+// mrc_pac_store_decode_window_reverb: a slab loop AROUND the rows call.  Per slab of whole rows the existing machinery decodes
+// every term as a one-term row at gain 1.0 over (start - Lpre, window + Lpre) in MRC_WINDOW_F64 into StoreBufs::reverbDry --
+// 0.0 + 1.0 * v is v (and a -0.0 becomes +0.0, which no fold from +0.0 can tell apart) -- then reverb_forward_kernel
+// transforms the convolved terms' segments and reverb_fold_kernel folds the rows (mrc_kernels_reverb.hip), on the same stream.
+// The term and source records of a slab go up in one copy.
+const char* const kWinReverb = "mrc_pac_store_decode_window_reverb";
+const char* const kSetIrs = "mrc_pac_store_set_irs";
+constexpr int64_t kRevB = MRC_STORE_REVERB_BLOCK, kRevN = 2 * kRevB;
+
+// the first quadrant of exp(-2 pi i t / N), rounded from long double, on the device once per handle
+int ensure_reverb_twiddles(mrc_handle* h) {
+    StoreBufs& b = h->store;
+    if (b.reverbTw.p) return MRC_OK;
+    std::vector<double2> w((size_t)(kRevN / 4));
+    const long double step = 2.0L * acosl(-1.0L) / (long double)kRevN;
+    for (int64_t t = 0; t < kRevN / 4; ++t) w[(size_t)t] = make_double2((double)cosl(step * t), (double)-sinl(step * t));
+    DevBuf tw;
+    MRC_HIP(h, tw.reserve(sizeof(double2) * w.size()));
+    MRC_HIP(h, hipMemcpy(tw.p, w.data(), sizeof(double2) * w.size(), hipMemcpyHostToDevice));
+    b.reverbTw = std::move(tw);
+    return MRC_OK;
+}
+
+int set_irs(mrc_pac_store* s, int64_t n_irs, const int64_t* ir_offset, const double* taps) {
+    MRC_TRY(store_alive(s, kSetIrs));
+    mrc_handle* h = s->h;
+    const std::string w = kSetIrs;
+    if (n_irs < 0) return fail(h, MRC_ERR_INVALID, w + ": n_irs < 0");
+    if (n_irs > 0 && (!ir_offset || !taps)) return fail(h, MRC_ERR_INVALID, w + ": ir_offset or taps is NULL");
+    if (n_irs > 0 && ir_offset[0] != 0) return fail(h, MRC_ERR_INVALID, w + ": ir_offset[0] = " + std::to_string(ir_offset[0]) + " is not 0");
+    for (int64_t j = 0; j < n_irs; ++j) {
+        const int64_t len = ir_offset[j + 1] - ir_offset[j];
+        if (len < 1 || len > MRC_MAX_STORE_IR_TAPS)
+            return fail(h, MRC_ERR_INVALID, w + ": impulse response " + std::to_string(j) + " has " + std::to_string(len) +
+                                                " taps, outside 1.." + std::to_string(MRC_MAX_STORE_IR_TAPS));
+    }
+    for (int64_t j = 0; j < n_irs; ++j)
+        for (int64_t i = ir_offset[j]; i < ir_offset[j + 1]; ++i)
+            if (!std::isfinite(taps[i]))
+                return fail(h, MRC_ERR_INVALID, w + ": taps[" + std::to_string(i) + "] (impulse response " + std::to_string(j) + ") is not finite");
+    MRC_HIP(h, hipSetDevice(h->device));
+    hipStream_t st = pick_stream(h, nullptr);
+    MRC_HIP(h, hipStreamSynchronize(st));
+    s->irBank = DevBuf();                                    // the call replaces the bank; a failure below leaves none
+    s->irLen.clear();
+    s->irPart.clear();
+    if (n_irs == 0) return MRC_OK;
+
+    std::vector<int64_t> len((size_t)n_irs), part((size_t)n_irs);
+    std::vector<ReverbSource> src((size_t)n_irs);
+    int64_t nPart = 0, maxSeg = 0;
+    for (int64_t j = 0; j < n_irs; ++j) {
+        len[(size_t)j] = ir_offset[j + 1] - ir_offset[j];
+        part[(size_t)j] = nPart;
+        const int64_t P = (len[(size_t)j] + kRevB - 1) / kRevB;
+        src[(size_t)j] = ReverbSource{ir_offset[j], -1, 0, 0, len[(size_t)j], nPart, (int)P, (int)kRevB};
+        nPart += P;
+        maxSeg = std::max(maxSeg, P);
+    }
+    const size_t nTaps = (size_t)ir_offset[n_irs];
+    DevBuf bank, tapsDev, srcDev;
+    for (auto need : {std::make_pair(&bank, sizeof(double2) * (size_t)(nPart * kRevN)), std::make_pair(&tapsDev, sizeof(double) * nTaps),
+                      std::make_pair(&srcDev, sizeof(ReverbSource) * src.size())})
+        if (need.first->reserve(need.second) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, MRC_ERR_NOMEM, w + ": out of device memory for " + std::to_string(nPart) + " partitions of " +
+                                              std::to_string(kRevN) + " bins; the store has no impulse responses now");
+        }
+    MRC_TRY(ensure_reverb_twiddles(h));
+    MRC_HIP(h, hipMemcpy(tapsDev.p, taps, sizeof(double) * nTaps, hipMemcpyHostToDevice));
+    MRC_HIP(h, hipMemcpy(srcDev.p, src.data(), sizeof(ReverbSource) * src.size(), hipMemcpyHostToDevice));
+    MRC_HIP(h, launch_reverb_forward(n_irs, maxSeg, srcDev.as<ReverbSource>(), tapsDev.as<double>(), h->store.reverbTw.as<double2>(),
+                                     bank.as<double2>(), st));
+    MRC_HIP(h, hipStreamSynchronize(st));
+    s->irBank = std::move(bank);
+    s->irLen = std::move(len);
+    s->irPart = std::move(part);
+    return MRC_OK;
+}
+
+int decode_window_reverb(mrc_pac_store* s, int rate_divisor, int mix, int n_ratios, const int32_t* ratio_up, const int32_t* ratio_down,
+                         int zeros, double rolloff, int n_bands, const double* edge_hz, const double* band_gain, int64_t n_items,
+                         const int64_t* term_offset, const int64_t* file, const int64_t* start, const double* gain,
+                         const int32_t* ratio_of, const int32_t* ir_of, int64_t window, int n_channels_out, int format, void* out,
+                         void* stream) {
+    const char* const fn = kWinReverb;
+    MRC_TRY(store_alive(s, fn));
+    mrc_handle* h = s->h;
+    const std::string w = fn;
+    s->reverbMs[0] = s->reverbMs[1] = 0.0;
+    if (n_bands == 0 && (edge_hz || band_gain))
+        return fail(h, MRC_ERR_INVALID, w + ": n_bands is 0 (no band gains) but edge_hz or band_gain is not NULL");
+    if (window < 0 || window > ((int64_t)1 << 40)) return fail(h, MRC_ERR_INVALID, w + ": window must lie in [0, 2^40]");
+    // every check of the rows call, made by that call at window 0: nothing is launched
+    const BandArgs bands{n_bands, edge_hz, band_gain};
+    const RatioArgs ratios{n_ratios, ratio_up, ratio_down, ratio_of};
+    MRC_TRY(decode_window_rows(s, fn, rate_divisor, mix, 1, 1, zeros, rolloff, n_bands == 0 ? nullptr : &bands, n_items, term_offset, file,
+                               start, gain, 0, n_channels_out, format, out, stream, &ratios));
+    const int64_t nTerms = term_offset[n_items], nIrs = (int64_t)s->irLen.size();
+    if (nTerms > 0 && !ir_of) return fail(h, MRC_ERR_INVALID, w + ": ir_of is NULL");
+    int64_t Lpre = 0;
+    bool anyConvolved = false;
+    for (int64_t k = 0; k < nTerms; ++k) {
+        const int64_t v = ir_of[k];
+        if (v == -1) continue;
+        if (v >= 0 && nIrs == 0)
+            return fail(h, MRC_ERR_INVALID, w + ": ir_of of term " + std::to_string(k) + " = " + std::to_string(v) +
+                                                " but the store has no impulse responses (mrc_pac_store_set_irs)");
+        if (v < 0 || v >= nIrs)
+            return fail(h, MRC_ERR_INVALID, w + ": ir_of of term " + std::to_string(k) + " = " + std::to_string(v) +
+                                                " is neither -1 nor inside the bank of " + std::to_string(nIrs) + " impulse responses");
+        Lpre = std::max(Lpre, s->irLen[(size_t)v] - 1);
+        anyConvolved = true;
+    }
+    if (!anyConvolved)                                       // the speeds call's path, unchanged
+        return decode_window_rows(s, fn, rate_divisor, mix, 1, 1, zeros, rolloff, n_bands == 0 ? nullptr : &bands, n_items, term_offset,
+                                  file, start, gain, window, n_channels_out, format, out, stream, &ratios);
+    const int64_t Wd = window + Lpre;
+    if (Wd > ((int64_t)1 << 40))
+        return fail(h, MRC_ERR_INVALID, w + ": window + the longest impulse response named - 1 = " + std::to_string(Wd) + " exceeds 2^40");
+    if (n_items == 0 || window == 0) return MRC_OK;
+    if (!out) return fail(h, MRC_ERR_INVALID, w + ": out is NULL");
+
+    MRC_HIP(h, hipSetDevice(h->device));
+    MRC_TRY(ensure_reverb_twiddles(h));
+    StoreBufs& b = h->store;
+    MRC_HIP(h, b.reverbEv.create());
+    hipStream_t st = pick_stream(h, stream);
+    DrainGuard drain{{st, nullptr, nullptr}};
+    const size_t elem = format == MRC_WINDOW_PCM16 ? 2 : format == MRC_WINDOW_F32 ? 4 : 8;
+    const int nch = n_channels_out;
+    const int64_t M = (window + kRevB - 1) / kRevB, slab = h->storeSlabSamples, rowCap = std::max<int64_t>(1, 0x7fffffffLL / M);
+    int64_t stats[4] = {0, 0, 0, 0};
+    double ms[4] = {0, 0, 0, 0}, reverbMs[2] = {0, 0};
+    std::vector<int64_t> ident, starts;
+    std::vector<double> ones;
+    for (int64_t first = 0, last; first < n_items; first = last) {   // rows [first, last), their terms [u0, u0 + nT)
+        last = first + 1;
+        while (last < n_items && last - first < rowCap && (slab == 0 || (term_offset[last + 1] - term_offset[first]) * Wd <= slab)) ++last;
+        const int64_t nRows = last - first, u0 = term_offset[first], nT = term_offset[last] - u0;
+        unsigned char* outSlab = (unsigned char*)out + (size_t)first * nch * window * elem;
+        if (nT == 0) {                                       // rows without terms: +0.0
+            MRC_HIP(h, hipMemsetAsync(outSlab, 0, (size_t)nRows * nch * window * elem, st));
+            stats[2] += 1;
+            continue;
+        }
+        // ---- the dry terms, by the existing machinery
+        MRC_HIP(h, b.reverbDry.reserve(sizeof(double) * (size_t)(nT * nch * Wd)));
+        ident.resize((size_t)nT + 1);
+        starts.resize((size_t)nT);
+        ones.assign((size_t)nT, 1.0);
+        for (int64_t k = 0; k <= nT; ++k) ident[(size_t)k] = k;
+        for (int64_t k = 0; k < nT; ++k)                     // (a start that far down is below every file with or without the pre-roll)
+            starts[(size_t)k] = start[u0 + k] < INT64_MIN + Lpre ? INT64_MIN : start[u0 + k] - Lpre;
+        const BandArgs slabBands{n_bands, edge_hz, band_gain ? band_gain + u0 * n_bands : nullptr};
+        const RatioArgs slabRatios{n_ratios, ratio_up, ratio_down, ratio_of + u0};
+        // (the slab is cut here, by output samples: the inner call does not cut it again by its intermediate spans, which
+        // would leave a short second slab behind every full one)
+        struct OneSlab {
+            mrc_handle* h;
+            int64_t was;
+            ~OneSlab() { h->storeSlabSamples = was; }
+        } oneSlab{h, h->storeSlabSamples};
+        h->storeSlabSamples = 0;
+        MRC_TRY(decode_window_rows(s, fn, rate_divisor, mix, 1, 1, zeros, rolloff, n_bands == 0 ? nullptr : &slabBands, nT, ident.data(),
+                                   file + u0, starts.data(), ones.data(), Wd, nch, MRC_WINDOW_F64, b.reverbDry.p, stream, &slabRatios));
+        for (int i = 0; i < 4; ++i) { stats[i] += s->stats[i]; ms[i] += s->ms[i]; }
+
+        // ---- the records (one H2D copy): terms | the rows' term offsets | sources
+        int64_t nConv = 0, nSpec = 0, maxSeg = 0;
+        for (int64_t k = 0; k < nT; ++k)
+            if (ir_of[u0 + k] >= 0) {
+                const int64_t nSeg = M + (s->irLen[(size_t)ir_of[u0 + k]] + kRevB - 1) / kRevB - 1;
+                nConv += 1;
+                nSpec += nSeg;
+                maxSeg = std::max(maxSeg, nSeg);
+            }
+        StageLayout lay(256);
+        const size_t oTerms = lay.add<ReverbTerm>(nT), oRows = lay.add<long long>(nRows + 1), oSrc = lay.add<ReverbSource>(nConv);
+        MRC_HIP(h, b.reverbPin.reserve(lay.total()));
+        MRC_HIP(h, b.reverbIn.reserve(lay.total()));
+        MRC_HIP(h, b.reverbSpec.reserve(std::max<size_t>(sizeof(double2) * (size_t)(nSpec * kRevN), 256)));
+        unsigned char* pin = (unsigned char*)b.reverbPin.p;
+        ReverbTerm* terms = (ReverbTerm*)(pin + oTerms);
+        long long* rowTerms = (long long*)(pin + oRows);
+        ReverbSource* src = (ReverbSource*)(pin + oSrc);
+        for (int64_t r = 0; r <= nRows; ++r) rowTerms[r] = term_offset[first + r] - u0;
+        for (int64_t k = 0, c = 0, spec = 0; k < nT; ++k) {
+            const int64_t base = k * nch * Wd, v = ir_of[u0 + k];
+            if (v < 0) {
+                terms[k] = ReverbTerm{base + Lpre, -1, 0, 0, 0, gain[u0 + k]};
+                continue;
+            }
+            const int64_t len = s->irLen[(size_t)v], P = (len + kRevB - 1) / kRevB, nSeg = M + P - 1;
+            terms[k] = ReverbTerm{base + Lpre, spec, s->irPart[(size_t)v], (int)P, 0, gain[u0 + k]};
+            src[c++] = ReverbSource{base, nch == 2 ? base + Wd : -1, Lpre - P * kRevB, Lpre - (len - 1), Wd, spec, (int)nSeg, (int)kRevN};
+            spec += nSeg;
+        }
+        // ---- device: forward transforms of the convolved terms' segments, then the rows
+        unsigned char* din = b.reverbIn.as<unsigned char>();
+        MRC_HIP(h, hipMemcpyAsync(din, pin, lay.total(), hipMemcpyHostToDevice, st));
+        MRC_HIP(h, hipEventRecord(b.reverbEv[0], st));
+        MRC_HIP(h, launch_reverb_forward(nConv, maxSeg, (const ReverbSource*)(din + oSrc), b.reverbDry.as<double>(),
+                                         b.reverbTw.as<double2>(), b.reverbSpec.as<double2>(), st));
+        MRC_HIP(h, hipEventRecord(b.reverbEv[1], st));
+        MRC_HIP(h, launch_reverb_fold(nRows, (const ReverbTerm*)(din + oTerms), (const long long*)(din + oRows), window, nch, format, Wd,
+                                      b.reverbDry.as<double>(), b.reverbSpec.as<double2>(), s->irBank.as<double2>(),
+                                      b.reverbTw.as<double2>(), outSlab, st));
+        MRC_HIP(h, hipEventRecord(b.reverbEv[2], st));
+        MRC_HIP(h, hipStreamSynchronize(st));                // (the staging is written again by the next slab)
+        for (int i = 0; i < 2; ++i) {
+            double t = 0.0;
+            MRC_HIP(h, b.reverbEv.elapsed(i, i + 1, &t));
+            reverbMs[i] += t;
+        }
+    }
+    MRC_HIP(h, hipStreamSynchronize(st));
+    for (int i = 0; i < 4; ++i) { s->stats[i] = stats[i]; s->ms[i] = ms[i]; }
+    s->ms[3] += reverbMs[0] + reverbMs[1];
+    s->reverbMs[0] = reverbMs[0];
+    s->reverbMs[1] = reverbMs[1];
+    return MRC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mrc_pac_store_set_irs(mrc_pac_store* s, int64_t n_irs, const int64_t* ir_offset, const double* taps) {
+    return set_irs(s, n_irs, ir_offset, taps);
+}
+
+int mrc_pac_store_ir_info(mrc_pac_store* s, int64_t* n_irs, int64_t* ir_len) {
+    MRC_TRY(store_alive(s, "mrc_pac_store_ir_info"));
+    if (n_irs) *n_irs = (int64_t)s->irLen.size();
+    for (size_t j = 0; ir_len && j < s->irLen.size(); ++j) ir_len[j] = s->irLen[j];
+    return MRC_OK;
+}
+
+int mrc_pac_store_decode_window_reverb(mrc_pac_store* s, int rate_divisor, int mix, int n_ratios, const int32_t* ratio_up,
+                                       const int32_t* ratio_down, int zeros, double rolloff, int n_bands, const double* edge_hz,
+                                       const double* band_gain, int64_t n_items, const int64_t* term_offset, const int64_t* file,
+                                       const int64_t* start, const double* gain, const int32_t* ratio_of, const int32_t* ir_of,
+                                       int64_t window, int n_channels_out, int format, void* out, void* stream) {
+    return decode_window_reverb(s, rate_divisor, mix, n_ratios, ratio_up, ratio_down, zeros, rolloff, n_bands, edge_hz, band_gain, n_items,
+                                term_offset, file, start, gain, ratio_of, ir_of, window, n_channels_out, format, out, stream);
+}
+
+int mrc_pac_store_reverb_ms(mrc_pac_store* s, double* ms) {
+    MRC_TRY(store_alive(s, "mrc_pac_store_reverb_ms"));
+    if (ms) { ms[0] = s->reverbMs[0]; ms[1] = s->reverbMs[1]; }
+    return MRC_OK;
 }
 
 int mrc_pac_store_block_energy(mrc_pac_store* s, int rate_divisor, int mix, int64_t n_sel, const int64_t* file,

@@ -106,6 +106,19 @@ __device__ __forceinline__ int mantissa_dev(double x, int scale, int nScaleBits,
     return (int)((x < 0.0 ? (Code(1) << (nMantBits - 1)) : Code(0)) + m);
 }
 
+// out[o] = v in the caller's format (MRC_WINDOW_*): the store's output kernels (mrc_kernels_store.hip, mrc_kernels_reverb.hip)
+__device__ inline void store_window_value(void* __restrict__ out, int64_t o, int format, double v) {
+    if (format == MRC_WINDOW_F64) {
+        ((double*)out)[o] = v;
+    } else if (format == MRC_WINDOW_F32) {
+        ((float*)out)[o] = (float)v;
+    } else {
+        const double mag = fabs(v);
+        const int code = mag == 0.0 ? 0 : (int)mag_code(mag, 16);
+        ((short*)out)[o] = (short)(signbit(v) ? -code : code);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // mixed-radix Stockham autosort FFT in LDS (forward, e^{-i...}); all threads of the block take part
 // ------------------------------------------------------------------------------------------------

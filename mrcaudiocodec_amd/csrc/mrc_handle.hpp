@@ -242,6 +242,12 @@ struct StoreBufs {
     DevBuf planes;                   // float64, window + 4 n_mdct_lines samples per item and decoded channel
     PinnedBuf pinIn;                 // written again only after the slab that read it has been synchronised
     EventSet<6> ev;                  // start | plan uploaded | unpacked ; synthesis starts | planes done | windows written
+    // mrc_pac_store_decode_window_reverb: a slab's dry terms [term][channel][window + pre-roll] (float64, written by the
+    // existing calls), the spectra of its convolved terms' segments, the term and source records (one H2D copy per slab from
+    // their page-locked staging), the twiddle quadrant of the N-point transform (once per handle)
+    DevBuf reverbDry, reverbSpec, reverbIn, reverbTw;
+    PinnedBuf reverbPin;
+    EventSet<3> reverbEv;            // forward transforms start | fold starts | windows written
 };
 
 // ---- the host plan of whole `.pac` files, shared by mrc_decode_pac_pcm16 and mrc_pac_nmr (mrc_api_decode.cpp)
@@ -375,6 +381,11 @@ struct mrc_pac_store {
     std::vector<int64_t> firstBlock; // [files + 1] into blockStart
     std::vector<int64_t> tileEdge;   // file f with blocks: nBlocks(f) + 1 edges from firstBlock[f] + f on, in DOUBLED output samples:
                                      // block i's tile is [2 p_i + a_i - 2 L, 2 p_i + 2 a_i + b_i - 2 L), and tiles abut
+    // mrc_pac_store_set_irs: the bank's partition spectra, response after response (N double2 per partition of B taps:
+    // 32 bytes per tap, rounded up to whole partitions), and per response its length and first partition
+    mrc::DevBuf irBank;
+    std::vector<int64_t> irLen, irPart;
+    double reverbMs[2] = {0, 0};     // last decode_window_reverb: reverb_forward_kernel | reverb_fold_kernel
     int64_t stats[4] = {0, 0, 0, 0}; // last decode_window: chunks parsed, decode_kernel launches, slabs, plan bytes uploaded
     double ms[4] = {0, 0, 0, 0};     // ... plan upload | unpack | synthesis | window_out_kernel (resampled: resample_out_kernel)
                                      // (after block_energy: block_energy_kernel launches in [1]; ms: upload | unpack | that kernel | 0;
@@ -430,6 +441,7 @@ struct mrc_handle {
             if (st) (void)hipStreamSynchronize(st);
         for (mrc_pac_store* s : stores) {
             s->bytes = mrc::DevBuf();
+            s->irBank = mrc::DevBuf();
             s->h = nullptr;
         }
     }

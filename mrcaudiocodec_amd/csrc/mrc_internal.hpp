@@ -314,6 +314,31 @@ hipError_t launch_resample_multi_sum_out(int64_t nRows, const SumTerm* terms, co
                                          const SpeedRatio* ratiosHost, int nRatios, const long long* termOffset, int64_t window,
                                          int nchOut, int format, int L, int64_t planeLen, const double* planes, void* out,
                                          hipStream_t st);
+// mrc_pac_store_decode_window_reverb (mrc_kernels_reverb.hip): overlap-save at a hop of B = MRC_STORE_REVERB_BLOCK samples and
+// transforms of N = 2 B points.  A source of forward transforms: sample i < take of segment seg < nSeg is g = first + seg B + i,
+// its value samples[re + g] + i samples[im + g] (im < 0: no imaginary part) where lo <= g < hi and zero elsewhere; the
+// segment's N bins go to spectra[(spec + seg) N ..).  A term's dry signal (take = N) and a response of the bank, whose
+// segments are its partitions of B taps (take = B), are both sources.
+struct ReverbSource {
+    long long re, im, first, lo, hi, spec;
+    int nSeg, take;
+};
+// sources, samples, twiddle (the first quadrant of exp(-2 pi i t / N), N / 4 values), spectra: device
+hipError_t launch_reverb_forward(int64_t nSources, int64_t maxSeg /* the largest nSeg */, const ReverbSource* sources,
+                                 const double* samples, const double2* twiddle, double2* spectra, hipStream_t st);
+// One term of a row: its dry samples of channel c at dry[dry + c chStride + t], t counted from the term's window start; spec < 0:
+// not convolved, else the term's first spectrum (segment s = -(nPart - 1), segment s at spec + s + nPart - 1) and ir, the
+// first of the response's nPart partitions in the bank.
+struct ReverbTerm {
+    long long dry, spec, ir;
+    int nPart, pad_;
+    double gain;
+};
+// out [nRows][nchOut][window] in `format` <- the left fold from +0.0, over terms [termOffset[i], termOffset[i + 1]) of row i in
+// that order, of gain * (the dry sample | the term's convolution with its response), every product rounded once, then added.
+hipError_t launch_reverb_fold(int64_t nRows, const ReverbTerm* terms /* device */, const long long* termOffset /* device */,
+                              int64_t window, int nchOut, int format, int64_t chStride, const double* dry, const double2* spectra,
+                              const double2* bank, const double2* twiddle, void* out, hipStream_t st);
 // One entry of mrc_pac_store_block_energy: a channel of a block, or its mid.  sel 0 / 1: output channel L / R of a joint
 // slot (a non-joint slot has one channel, itself: 0); kEnergyMid: the mid (L + R) / 2 on the lines -- of a joint slot, or of
 // the PAIR of non-joint slots slot, slot + 1 (a stereo file's last block).

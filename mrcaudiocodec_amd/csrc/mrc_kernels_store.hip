@@ -127,18 +127,7 @@ namespace {
 
 constexpr int kWindowThreads = 256;
 
-// out[o] = v in the caller's format (MRC_WINDOW_*)
-__device__ inline void store_window_value(void* __restrict__ out, int64_t o, int format, double v) {
-    if (format == MRC_WINDOW_F64) {
-        ((double*)out)[o] = v;
-    } else if (format == MRC_WINDOW_F32) {
-        ((float*)out)[o] = (float)v;
-    } else {
-        const double mag = fabs(v);
-        const int code = mag == 0.0 ? 0 : (int)mag_code(mag, 16);
-        ((short*)out)[o] = (short)(signbit(v) ? -code : code);
-    }
-}
+// (store_window_value, out[o] = v in the caller's format: mrc_device.hpp, shared with mrc_kernels_reverb.hip)
 
 __global__ __launch_bounds__(kWindowThreads) void window_out_kernel(const WindowItem* __restrict__ items, int64_t window,
                                                                     int64_t tiles, int nchOut, int format, int L,

@@ -71,6 +71,15 @@ lies over, which is what the levels are asked about:
                                     16000, dtype=torch.float32, rate_divisor=2, mix="mid", resample=(2, 3),
                                     speed_factors=speeds, speed_index=np.stack([pick, np.ones_like(pick)], 1))   # the noise: speed 1
 
+ir_index= (mrc_pac_store_decode_window_reverb) sends an item, or a term of a sum, through a room: the store keeps a bank of impulse
+responses (set_impulse_responses; ir_at_rate brings a recorded one to the rate the terms are read at), and a term is convolved
+with the response it names, last of all, in float64 overlap-save on the device -- speech through a room over dry noise:
+
+        store.set_impulse_responses([ir_at_rate(h, 48000, 16000) for h in rooms])
+        x = store.decode_window_sum(np.stack([speech, noise], 1), np.stack([s_starts, n_starts], 1), np.stack([np.ones_like(g), g], 1),
+                                    16000, dtype=torch.float32, rate_divisor=2, mix="mid", resample=(2, 3),
+                                    ir_index=np.stack([rng.integers(0, len(rooms), len(speech)), np.full(len(speech), -1)], 1))
+
 band_energy_window (mrc_pac_store_band_energy_window) is the time-frequency feature that usually follows a crop, taken from
 the same sums split by frequency band and laid on a frame grid -- the coded file already is a time-frequency representation:
 
@@ -245,6 +254,94 @@ def check_speed_index(speed_index, unit_shape, n_ratios, what="decode_window"):
         raise ValueError("%s: speed_index must lie in 0..%d (the speed_factors given), got %d at unit %d"
                          % (what, n_ratios - 1, int(idx[bad[0]]), int(bad[0])))
     return np.ascontiguousarray(idx.astype(np.int32))
+
+
+REVERB_BLOCK = _lib.MRC_STORE_REVERB_BLOCK          # the overlap-save hop B of ir_index= (transforms of 2 B points)
+MAX_IR_TAPS = _lib.MRC_MAX_STORE_IR_TAPS
+
+
+def check_impulse_responses(irs, what="set_impulse_responses"):
+    """a bank for PacStore.set_impulse_responses -> (offsets int64 [n + 1], taps float64, back to back), else ValueError: a
+    list of 1-D arrays of 1..MAX_IR_TAPS finite numbers each; None or an empty list: no bank, (offsets [0], no taps)"""
+    if irs is None:
+        irs = []
+    if isinstance(irs, np.ndarray) or not isinstance(irs, (tuple, list)):
+        raise ValueError("%s: the bank must be a list of 1-D arrays (or None), got %r" % (what, type(irs).__name__))
+    rows = []
+    for j, ir in enumerate(irs):
+        try:
+            a = np.asarray(ir)
+            if a.dtype == object or a.dtype.kind not in "fiu":
+                raise TypeError
+            a = a.astype(np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("%s: impulse response %d must be numbers, got %r" % (what, j, ir))
+        if a.ndim != 1 or not 1 <= a.size <= MAX_IR_TAPS:
+            raise ValueError("%s: impulse response %d must be 1-D with 1 to %d taps, got shape %s" % (what, j, MAX_IR_TAPS, a.shape))
+        bad = np.flatnonzero(~np.isfinite(a))
+        if bad.size:
+            raise ValueError("%s: impulse response %d must be finite, got %r at tap %d" % (what, j, float(a[bad[0]]), int(bad[0])))
+        rows.append(a)
+    offsets = np.zeros(len(rows) + 1, np.int64)
+    np.cumsum([r.size for r in rows], out=offsets[1:])
+    taps = np.ascontiguousarray(np.concatenate(rows)) if rows else np.zeros(0, np.float64)
+    return offsets, taps
+
+
+def check_ir_index(ir_index, unit_shape, n_irs, what="decode_window"):
+    """ir_index of a window call -> int32 [units], contiguous, else ValueError: ints, the shape of the call's units, every value
+    -1 (not convolved) or an index into the store's bank of n_irs impulse responses"""
+    unit_shape = tuple(int(v) for v in unit_shape)
+    try:
+        idx = np.asarray(ir_index)
+        if idx.dtype == object or idx.dtype.kind not in "iu":
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError("%s: ir_index must be ints, got %r" % (what, ir_index))
+    if idx.shape != unit_shape:
+        raise ValueError("%s: ir_index must have shape %s, got %s" % (what, unit_shape, idx.shape))
+    idx = idx.reshape(-1)
+    bad = np.flatnonzero((idx < -1) | (idx >= n_irs))
+    if bad.size:
+        if n_irs == 0:
+            raise ValueError("%s: ir_index names impulse response %d at unit %d, but the store has none (set_impulse_responses)"
+                             % (what, int(idx[bad[0]]), int(bad[0])))
+        raise ValueError("%s: ir_index must be -1 or lie in 0..%d (the store's impulse responses), got %d at unit %d"
+                         % (what, n_irs - 1, int(idx[bad[0]]), int(bad[0])))
+    return np.ascontiguousarray(idx.astype(np.int32))
+
+
+def ir_at_rate(ir, rate_in, rate_out):
+    """A recorded room impulse response at the rate the terms are read at -> float64 [ceil(len(ir) * rate_out / rate_in)].  Host
+    NumPy over the library's own polyphase filter (resample_taps(up, down), up / down = rate_out / rate_in reduced): output n
+    is the fold over j = 0 .. 2 W - 1 of taps[p][j] * ir[q - W + 1 + j] (zero outside the response), q = n down // up and p =
+    n down % up -- decode_window(resample=)'s rule -- times down / up, the factor that keeps the DC gain sum(ir) of the
+    convolution at the new rate; where that nominal result's sum lies within one half of sum(ir) != 0 it is rescaled so that
+    the two sums agree.  Equal rates: a float64 copy.  ValueError for rates that are not positive ints, a response that is not
+    1-D finite numbers, and a ratio outside what decode_window(resample=) takes."""
+    what = "ir_at_rate"
+    for name, v in (("rate_in", rate_in), ("rate_out", rate_out)):
+        if not _is_int(v) or int(v) < 1:
+            raise ValueError("%s: %s must be a positive int, got %r" % (what, name, v))
+    _, taps_in = check_impulse_responses([ir], what)
+    g = int(np.gcd(int(rate_in), int(rate_out)))
+    up, down = int(rate_out) // g, int(rate_in) // g
+    if up == down:
+        return taps_in.copy()
+    check_resample((up, down), what)
+    W, taps = resample_taps(up, down)
+    n_out = -((-taps_in.size * up) // down)
+    nd = np.arange(n_out, dtype=np.int64) * down
+    q, p = nd // up, nd % up
+    padded = np.concatenate([np.zeros(W, np.float64), taps_in, np.zeros(W + 1, np.float64)])
+    out = np.zeros(n_out, np.float64)
+    for j in range(2 * W):                                   # ir[q - W + 1 + j] is padded[q + 1 + j]
+        out += taps[p, j] * padded[q + 1 + j]
+    out *= down / up
+    s_in, s_out = float(taps_in.sum()), float(out.sum())
+    if s_in != 0.0 and s_out != 0.0 and abs(s_out - s_in) <= 0.5 * abs(s_in):
+        out *= s_in / s_out
+    return out
 
 
 def check_levels_mix(mix, what="levels"):
@@ -484,6 +581,7 @@ class PacStore:
             data = np.zeros(1, np.uint8)
         self._handle = handle
         self._levels = {}                # levels() of every file, per (rate_divisor, mix)
+        self._ir_lengths = np.zeros(0, np.int64)   # set_impulse_responses: the bank's lengths (mrc_pac_store_ir_info)
         self._s = C.c_void_p()
         handle._check(lib.mrc_pac_store_create(handle._h, n, data.ctypes.data, file_offset.ctypes.data, C.byref(self._s)))
         self.n_channels = np.zeros(n, np.int32)
@@ -574,6 +672,52 @@ class PacStore:
         ratios, zeros, rolloff = _speed_list(resample, speed_factors, what)
         return ratios, zeros, rolloff, check_speed_index(speed_index, unit_shape, len(ratios), what)
 
+    def set_impulse_responses(self, irs):
+        """mrc_pac_store_set_irs: the store's bank of room impulse responses for ir_index= -- a list of 1-D arrays of 1 to
+        MAX_IR_TAPS finite taps each, SAMPLED AT THE OUTPUT RATE of the terms that will name them (ir_at_rate brings a recorded
+        response there).  The call replaces the previous bank; None or [] drops it.  The partitions' transforms are computed
+        once on the device and stay resident (32 bytes per tap, lengths rounded up to REVERB_BLOCK).  A bank that is not such
+        a list is a ValueError before any library call; a failed allocation (MrcError) leaves the store without a bank."""
+        offsets, taps = check_impulse_responses(irs)
+        n = offsets.size - 1
+        try:
+            self._handle._check(lib.mrc_pac_store_set_irs(self._s, n, offsets.ctypes.data, taps.ctypes.data if n else None))
+        finally:
+            count = C.c_int64()
+            self._handle._check(lib.mrc_pac_store_ir_info(self._s, C.byref(count), None))
+            lengths = np.zeros(count.value, np.int64)
+            self._handle._check(lib.mrc_pac_store_ir_info(self._s, None, lengths.ctypes.data if count.value else None))
+            self._ir_lengths = lengths
+
+    @property
+    def impulse_response_lengths(self):
+        """the taps of every impulse response of the bank, int64 [n_irs] (mrc_pac_store_ir_info); empty without a bank"""
+        return self._ir_lengths.copy()
+
+    def reverb_ms(self):
+        """mrc_pac_store_reverb_ms: the device time of the last ir_index= call's two kernels, summed over its slabs"""
+        ms = np.zeros(2, np.float64)
+        self._handle._check(lib.mrc_pac_store_reverb_ms(self._s, ms.ctypes.data))
+        return {"forward": float(ms[0]), "fold": float(ms[1])}
+
+    def _reverb(self, rate_divisor, mix, resample, speeds, bands, ir_index, n, offsets, files, starts, gains, window, channels, fmt,
+                out, stream):
+        """mrc_pac_store_decode_window_reverb over checked arguments; speeds None (every term at resample's ratio, None: 1 / 1)
+        or (ratios, zeros, rolloff, index [terms]), bands None or (edges, gains [terms][n_bands]), ir_index int32 [terms]"""
+        if speeds is None:
+            up, down, zeros, rolloff = resample if resample is not None else (1, 1, RESAMPLE_ZEROS, RESAMPLE_ROLLOFF)
+            speeds = ([(up, down)], zeros, rolloff, np.zeros(files.size, np.int32))
+        ratios, zeros, rolloff, index = speeds
+        ups = np.ascontiguousarray([r[0] for r in ratios], dtype=np.int32)
+        downs = np.ascontiguousarray([r[1] for r in ratios], dtype=np.int32)
+        pad = lambda a: a.ctypes.data if a.size else None
+        edges, band_gains = bands if bands is not None else (None, None)
+        self._handle._check(lib.mrc_pac_store_decode_window_reverb(
+            self._s, rate_divisor, _lib.MRC_MIX_EACH if mix is None else mix, len(ratios), ups.ctypes.data, downs.ctypes.data, zeros,
+            rolloff, 0 if bands is None else edges.size - 1, None if bands is None else edges.ctypes.data,
+            None if bands is None else pad(band_gains), n, offsets.ctypes.data, pad(files), pad(starts), pad(gains), pad(index),
+            pad(ir_index), window, channels, fmt, out.data_ptr() if out.numel() else None, stream or None))
+
     def _speeds(self, rate_divisor, mix, speeds, bands, n, offsets, files, starts, gains, window, channels, fmt, out, stream):
         """mrc_pac_store_decode_window_speeds over checked arguments; speeds = (ratios, zeros, rolloff, index [terms]), bands
         None or (edges, gains [terms][n_bands])"""
@@ -610,7 +754,8 @@ class PacStore:
         return np.floor_divide(starts * down, up), -np.floor_divide(-int(window) * down, up)
 
     def decode_window(self, files, starts, window, channels=None, dtype=None, out=None, stream=None, rate_divisor=1,
-                      mix=None, resample=None, band_gains=None, band_edges_hz=None, speed_factors=None, speed_index=None):
+                      mix=None, resample=None, band_gains=None, band_edges_hz=None, speed_factors=None, speed_index=None,
+                      ir_index=None):
         """Item i = samples [starts[i], starts[i] + window) of file files[i], zeros where that leaves the file (starts may be
         negative or past the end) -> a torch tensor [n][channels][window] on the handle's device.  dtype: torch.int16 (the
         default: the codes Handle.decode_pac_pcm16 writes, bit for bit), torch.float64 (the overlap-added signal before the
@@ -655,7 +800,14 @@ class PacStore:
         samples at the item's OWN ratio, and a ratio of 1 is the call without a filter.  Speed perturbation of a batch --
         0.9x, 1.0x, 1.1x drawn per item -- is one call, one plan and one output kernel.  Only one of the two given, a wrong
         shape, an index outside the list, a factor that is not a pair of positive ints and a combined ratio outside what
-        resample takes (named with its reduced terms) are ValueErrors, before any library call."""
+        resample takes (named with its reduced terms) are ValueErrors, before any library call.
+        ir_index: None (this call as it always was), or an int array [n]: item i convolved with impulse response ir_index[i] of
+        the store's bank (set_impulse_responses), -1 for none (mrc_pac_store_decode_window_reverb, as one-term rows at gain
+        1.0).  The response is sampled at the item's OUTPUT rate and applied last: y[t] = sum_j h[j] x[t - j] over the
+        signal this call gives otherwise, which is zero outside the file -- so the item rings len(h) - 1 samples past the
+        file's end.  An item with -1 is this call's window bit for bit; a convolved item is float64 overlap-save within the
+        tolerance the header states, and independent to the bit of the batch it is in.  A wrong shape and an index that is
+        neither -1 nor inside the bank are ValueErrors, before any library call."""
         rate_divisor = check_rate_divisor(rate_divisor)
         mix = check_mix(mix, channels)
         resample_arg, resample = resample, check_resample(resample)
@@ -668,7 +820,13 @@ class PacStore:
         n, window = files.size, int(window)
         bands = self._band_args("decode_window", band_gains, band_edges_hz, (n,))
         speeds = self._speed_args("decode_window", resample_arg, speed_factors, speed_index, (n,))
+        irs = None if ir_index is None else check_ir_index(ir_index, (n,), self._ir_lengths.size)
         fmt, channels, out, stream = self._window_out("decode_window", n, files, window, channels, dtype, out, stream)
+        if irs is not None:
+            offsets, ones = np.arange(n + 1, dtype=np.int64), np.ones(n, np.float64)
+            self._reverb(rate_divisor, mix, resample, speeds, bands, irs, n, offsets, files, starts, ones, window, channels, fmt, out,
+                         stream)
+            return out
         if speeds is not None:
             offsets, ones = np.arange(n + 1, dtype=np.int64), np.ones(n, np.float64)
             self._speeds(rate_divisor, mix, speeds, bands, n, offsets, files, starts, ones, window, channels, fmt, out, stream)
@@ -702,7 +860,7 @@ class PacStore:
 
     def decode_window_sum(self, files, starts, gains, window, item_offsets=None, channels=None, dtype=None, out=None, stream=None,
                           rate_divisor=1, mix=None, resample=None, band_gains=None, band_edges_hz=None, speed_factors=None,
-                          speed_index=None):
+                          speed_index=None, ir_index=None):
         """mrc_pac_store_decode_window_sum -> a torch tensor [n][channels][window] on the handle's device: item i is the sum
         over its terms k, IN THE ORDER GIVEN, of gains[k] * (the float64 window decode_window gives for files[k], starts[k]
         at this rate_divisor, mix and resample), folded from +0.0 with every product rounded once, then added -- speech over
@@ -722,7 +880,11 @@ class PacStore:
         speed_factors, speed_index: as decode_window's, PER TERM (mrc_pac_store_decode_window_speeds): speed_index has the shape
         of files, and term k is the float64 window decode_window gives at ITS ratio -- the speech term at a drawn speed over a
         noise term at speed 1 is one call.  starts and window count output samples at the term's own ratio;
-        source_spans says where a term lies in the source, for LevelMap's gains.  Per-term band_gains still apply."""
+        source_spans says where a term lies in the source, for LevelMap's gains.  Per-term band_gains still apply.
+        ir_index: as decode_window's, PER TERM (mrc_pac_store_decode_window_reverb): it has the shape of files, and term k is
+        convolved with impulse response ir_index[k] of the store's bank before it is weighted and added, -1 for none -- speech
+        through a room over dry noise is one call.  It composes with resample, speed_factors / speed_index, band_gains, mix
+        and rate_divisor: the response acts last, at the term's output rate.  None: this call as it always was."""
         what = "decode_window_sum"
         rate_divisor = check_rate_divisor(rate_divisor, what)
         mix = check_mix(mix, channels, what)
@@ -736,6 +898,7 @@ class PacStore:
                              % (what, files.shape, starts.shape, gains.shape))
         bands = self._band_args(what, band_gains, band_edges_hz, files.shape)
         speeds = self._speed_args(what, resample_arg, speed_factors, speed_index, files.shape)
+        irs = None if ir_index is None else check_ir_index(ir_index, files.shape, self._ir_lengths.size, what)
         if item_offsets is None:
             if files.ndim != 2:
                 raise ValueError("%s: files, starts and gains must be [n][K], or 1-D with item_offsets; got shape %s" % (what, files.shape))
@@ -754,6 +917,10 @@ class PacStore:
             raise ValueError("%s: gains must be finite, got %r at term %d" % (what, float(gains[bad[0]]), int(bad[0])))
         n, window = offsets.size - 1, int(window)
         fmt, channels, out, stream = self._window_out(what, n, files, window, channels, dtype, out, stream)
+        if irs is not None:
+            self._reverb(rate_divisor, mix, resample, speeds, bands, irs, n, offsets, files, starts, gains, window, channels, fmt, out,
+                         stream)
+            return out
         if speeds is not None:
             self._speeds(rate_divisor, mix, speeds, bands, n, offsets, files, starts, gains, window, channels, fmt, out, stream)
             return out
