@@ -1332,6 +1332,60 @@ int mrc_pac_store_decode_window_reverb(mrc_pac_store* s, int rate_divisor, int m
                                        void* stream);
 int mrc_pac_store_reverb_ms(mrc_pac_store* s, double* ms /*[2]*/);
 
+/* Short-time Fourier transforms of rows: the features a pretrained front end expects (torch.stft's numbers: 400-point Hann at
+ * hop 160 with 80 mel filters at 16 kHz; 25 ms frames padded to 512 points; 1024 points at hop 480 at 48 kHz) of ANY row the store
+ * can make, in the call that reads it -- no waveform tensor, no torch.stft, no mel matmul.
+ * THE ROW.  mrc_pac_store_stft_window takes every argument of mrc_pac_store_decode_window_reverb up to and including ir_of,
+ * unchanged in order and meaning.  Row i's signal x_i[c][t], 0 <= t < L = (n_frames - 1) hop + n_fft, is the MRC_WINDOW_F64 row
+ * that call gives on the same row arguments with window = L, bit for bit: terms, gains, ratios, band gains, rooms, the channel
+ * map and zeros outside the file all hold as they do there.  There is no padding mode: start is sample 0 of frame 0.  A
+ * caller who wants centred frames starts n_fft / 2 earlier and reads REAL signal there (zeros before the file's start), where
+ * torch.stft(center=True) reflects the crop at its own ends: the two differ in the first and last frames that reach past a crop.
+ * THE TRANSFORM.  X[m][k] = sum over n < n_fft of g[n] x[m hop + n] e^{-2 pi i k n / n_fft}, 0 <= k <= n_fft / 2, g = frame_window
+ * as given (the caller builds Hann, Hamming, or 400 taps padded to 512: the library holds no window types); the product g x is
+ * rounded once.  The transform's rounding is the implementation's (one complex transform of n_fft / 2 points per frame in
+ * float64, radices 4, 2, 3, 5, twiddles rounded once from long double): |X - exact| <= K 2^-52 log2(n_fft) ||g x_m||_2 per
+ * bin, K measured in tests/test_gpu_store_stft.py.
+ *   MRC_STFT_COMPLEX  out[i][c][k][m][2] = (re, im) of X.
+ *   MRC_STFT_POWER    out[i][c][k][m] = P = re re + im im, each product rounded once, then added, no FMA: given X, bit-defined.
+ *   MRC_STFT_BANK     out[i][c][q][m] = E: row q of bank [n_filters][n_fft / 2 + 1] is used on its support [lo_q, hi_q), its
+ *                     first to its last nonzero entry; E is the left fold from +0.0, in ascending k, of bank[q][k] P[m][k],
+ *                     each product rounded once, then added (__dmul_rn, __dadd_rn); a row of zeros gives +0.0.  Given P,
+ *                     bit-defined.  The caller's matrix is taken as it is (torchaudio's, librosa's, a model's own).
+ * MRC_WINDOW_F64 is the value, MRC_WINDOW_F32 one conversion of it.  n_fft: even, 16..MRC_MAX_STFT_POINTS, no prime factor other
+ * than 2, 3 and 5.  hop >= 1 with no upper bound: frames may leave gaps.
+ * To the bit a result does not depend on the order of the rows, on what else shares the call, on the slab size, on the launch
+ * grid nor, for the filter values, on which filters share the call (their index and their number), and it repeats from call to
+ * call: frame m of a row is computed from that frame's n_fft samples alone (no two frames share a transform).  No atomics.
+ * MRC_ERR_INVALID naming the argument, before any device work and with `out` untouched: every refusal of
+ * mrc_pac_store_decode_window_reverb (under this call's name); n_fft outside the rule; frame_window NULL or with a tap that is
+ * not finite (its index is named); n_frames < 0; hop < 1; L, or L + the longest response named - 1, beyond 2^40; an unknown mode; a format other than MRC_WINDOW_F32 /
+ * _F64; mode MRC_STFT_BANK with n_filters outside 1..MRC_MAX_STORE_BANDS, a NULL bank or an entry that is not finite (named);
+ * any other mode with n_filters != 0 or a bank.  n_items == 0 or n_frames == 0: MRC_OK, nothing written.
+ * Slabs: runs of whole rows whose L sum to at most MRC_OPT_STORE_SLAB_SAMPLES (one row at least; 0: one slab).  Per slab the
+ * reverb entry writes the rows as MRC_WINDOW_F64, in one slab of its own, into a scratch buffer the handle owns (8 bytes per
+ * sample and output channel, apart from that entry's own scratch), then stft_kernel runs on the same stream.  The frame
+ * window, the bank's supports and weights and the twiddle table go up once per call, before the slabs.
+ * mrc_pac_store_stats then describes the whole call as the reverb call's does, ms[3] including stft_kernel;
+ * mrc_pac_store_stft_ms gives that kernel apart, summed over the slabs (mrc_pac_store_reverb_ms: the reverb kernels likewise). */
+#define MRC_STFT_COMPLEX 0   /* out[i][c][k][m][2]  (re, im)            */
+#define MRC_STFT_POWER   1   /* out[i][c][k][m]     re^2 + im^2         */
+#define MRC_STFT_BANK    2   /* out[i][c][q][m]     sum_k W[q][k] P[k]  */
+#define MRC_MAX_STFT_POINTS 2048
+int mrc_pac_store_stft_window(mrc_pac_store* s, int rate_divisor, int mix, int n_ratios,
+                              const int32_t* ratio_up /*[n_ratios]*/, const int32_t* ratio_down /*[n_ratios]*/, int zeros,
+                              double rolloff, int n_bands /* 0: no band gains */, const double* edge_hz /*[n_bands+1]*/,
+                              const double* band_gain /*[n_terms][n_bands]*/, int64_t n_items,
+                              const int64_t* term_offset /*[n_items+1]*/, const int64_t* file /*[n_terms]*/,
+                              const int64_t* start /*[n_terms]*/, const double* gain /*[n_terms]*/,
+                              const int32_t* ratio_of /*[n_terms]: index into the list*/,
+                              const int32_t* ir_of /*[n_terms]: -1 or index into the bank*/, int n_fft,
+                              const double* frame_window /* HOST [n_fft] */, int64_t n_frames, int64_t hop, int mode, int n_filters,
+                              const double* bank /* HOST [n_filters][n_fft/2+1], mode MRC_STFT_BANK only, else NULL and 0 */,
+                              int n_channels_out, int format /* MRC_WINDOW_F32 | MRC_WINDOW_F64 */, void* out /* DEVICE */,
+                              void* stream);
+int mrc_pac_store_stft_ms(mrc_pac_store* s, double* ms /*[1]: stft_kernel of the last call */);
+
 /* Per-stage device time of the most recent timed call when timing is enabled (hipEvents on the launch stream; the call
  * then synchronises).  Timed: mrc_dev_encode / mrc_dev_encode_ex and mrc_encode_mono / mrc_encode_joint (the _blocks
  * forms: their last shape group).  Not timed: the stage calls (mrc_dev_mdct, mrc_dev_smr, mrc_dev_alloc_quant),

@@ -25,6 +25,8 @@ MRC_FILTER_NORM_NONE, MRC_FILTER_NORM_SLANEY = 0, 1              # mrc_filterban
 MRC_OPT_STORE_SLAB_SAMPLES = 7
 MRC_STORE_REVERB_BLOCK = 1024                                    # mrc_pac_store_decode_window_reverb: the overlap-save hop B (N = 2 B)
 MRC_MAX_STORE_IR_TAPS = 1 << 17                                  # mrc_pac_store_set_irs: taps of one impulse response
+MRC_STFT_COMPLEX, MRC_STFT_POWER, MRC_STFT_BANK = 0, 1, 2        # mrc_pac_store_stft_window's modes
+MRC_MAX_STFT_POINTS = 2048                                       # ... and its largest n_fft
 # mrc_dev_helper_probe: name -> (MRC_PROBE_ id, words per element of in0 / in1 / in2, words per element of out)
 PROBES = {
     "MOVES_I32": (1, (1, 1, 0), 8), "MOVES_U32": (2, (1, 1, 0), 8), "MOVES_F64": (3, (1, 1, 0), 8),
@@ -260,6 +262,11 @@ def _load():
                                                          C.c_int, _f64p, _f64p, C.c_int64, _i64p, _i64p, _i64p, _f64p, _i32p, _i32p,
                                                          C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
         "mrc_pac_store_reverb_ms": (C.c_int, [C.c_void_p, _f64p]),
+        "mrc_pac_store_stft_window": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, C.c_int, C.c_double,
+                                                C.c_int, _f64p, _f64p, C.c_int64, _i64p, _i64p, _i64p, _f64p, _i32p, _i32p,
+                                                C.c_int, _f64p, C.c_int64, C.c_int64, C.c_int, C.c_int, _f64p, C.c_int, C.c_int,
+                                                C.c_void_p, C.c_void_p]),
+        "mrc_pac_store_stft_ms": (C.c_int, [C.c_void_p, _f64p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = the library does not export the header's symbol

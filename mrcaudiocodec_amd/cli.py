@@ -70,6 +70,13 @@ of overlapping triangular filters (mrc_pac_store_filterbank_window): out.npy hol
 spaces N filters equally in mel from --f-min (default 0) to --f-max (default Nyquist); --filter-points names the filters'
 points itself.  A filter narrower than a block's line spacing reads its share of the line it lies in: no row is empty.
 Refuses every encode, decode, levels and band-energy flag.
+STFT energies:  python -m mrcaudiocodec_amd.cli --stft-energies in.pac out.npy --n-fft N --hop H [--win-length W] [--mel N [--f-min HZ]
+[--f-max HZ] [--mel-scale htk|slaney] [--filter-norm slaney]] [--complex]  writes the short-time Fourier transform of the row that
+-d would decode (mrc_pac_store_stft_window): float32 power [channels][N / 2 + 1][frames], with --mel the totals of N mel filters
+on the bins (store.mel_bin_weights: torchaudio's rule), with --complex the complex64 bins.  The frame window is the periodic
+Hann of W taps (default N) centred in N points; frame j is samples [j H, j H + N) of the row, and --samples is rounded down to
+whole frames.  It composes with the flags -d takes for a row: --start, --samples, --rate-divisor, --sample-rate, --mix, --speed,
+--ir, --band-gains-db, --overlay, --snr-db; it refuses -d itself and every encode, levels and line-energy flag.
 
 Quality (mrc_pac_nmr): --nmr on an encode prints, per file written (every rung of a ladder), one JSON line with the
 noise-to-mask ratio of the file against the WAV, measured with the codec's own masking model: nmr_max_db (worst band),
@@ -708,6 +715,70 @@ def filterbank_energies_of_file(pac_path, npy_path, hop, bank, device_id=0, mix=
     return _whole_file_energies(pac_path, npy_path, hop, device_id, mix, call)
 
 
+STFT_ENERGIES_REFUSES = ("-d", "--no-huffman", "--exact-spread", "--certify", "--bits-per-sample", "--nmr", "--measure", "--target-nmr",
+                         "--vbr-nmr", "--vbr-bytes", "--vbr-bits-per-sample", "--vbr-grid", "--levels", "--levels-window",
+                         "--band-energies", "--band-edges", "--filterbank-energies", "--filter-points")
+STFT_FLAGS = ("--n-fft", "--win-length", "--complex")
+
+
+def check_stft_energies_args(stft_energies, n_fft, hop, win_length, mel, f_min, f_max, mel_scale, filter_norm, complex_bins, given):
+    """--stft-energies as given with its flags -> dict(n_fft, hop, window float64 [n_fft], mel=(n, f_min, f_max or None: the
+    output's Nyquist, scale) or None, norm, complex), or None without it.  It reads src, a `.pac` file, and writes dst, a .npy
+    file, through PacStore.stft_window on the row -d would decode: given (flag -> whether it was given) must be empty of
+    STFT_ENERGIES_REFUSES; --n-fft (store.stft_points_ok's rule) and --hop >= 1 are needed; --win-length W in 1..n_fft: the
+    periodic Hann of W taps centred in n_fft points; --f-min, --f-max, --mel-scale and --filter-norm go with --mel; --complex
+    does not go with --mel; --n-fft, --win-length and --complex need --stft-energies."""
+    if not stft_energies:
+        for flag, v in zip(STFT_FLAGS, (n_fft, win_length, complex_bins or None)):
+            if v is not None:
+                raise ValueError("%s belongs to --stft-energies: it needs --stft-energies" % flag)
+        return None
+    for flag in STFT_ENERGIES_REFUSES:
+        if given.get(flag):
+            raise ValueError("--stft-energies writes the short-time Fourier transform of a decoded row and nothing else: it does "
+                             "not go with %s" % flag)
+    from .store import MAX_BANDS, MEL_SCALES, check_filter_norm, check_stft, hann_window, mel_points, padded_window
+    if n_fft is None:
+        raise ValueError("--stft-energies needs --n-fft N, the points of a frame")
+    if hop is None:
+        raise ValueError("--stft-energies needs --hop H, the samples between two frames")
+    try:
+        check_stft(n_fft, hop, 0, what="--stft-energies")
+    except ValueError as e:
+        raise ValueError(str(e).replace("stft_window", "--stft-energies"))
+    if win_length is not None and not 1 <= int(win_length) <= int(n_fft):
+        raise ValueError("--win-length: the frame window holds 1 to --n-fft = %d taps, got %r" % (n_fft, win_length))
+    window = padded_window(hann_window(int(n_fft) if win_length is None else int(win_length)), int(n_fft))
+    spec = dict(n_fft=int(n_fft), hop=int(hop), window=window, mel=None, norm=filter_norm, complex=bool(complex_bins))
+    if mel is None:
+        for flag, v in (("--f-min", f_min), ("--f-max", f_max), ("--mel-scale", mel_scale), ("--filter-norm", filter_norm)):
+            if v is not None:
+                raise ValueError("%s goes with --mel" % flag)
+        return spec
+    if complex_bins:
+        raise ValueError("--complex writes the bins themselves: it does not go with --mel")
+    if isinstance(mel, bool) or not isinstance(mel, (int, np.integer)) or not 1 <= int(mel) <= MAX_BANDS:
+        raise ValueError("--mel: the number of filters is an int in 1..%d, got %r" % (MAX_BANDS, mel))
+    try:
+        check_filter_norm(filter_norm, "--filter-norm")
+    except ValueError:
+        raise ValueError("--filter-norm: the one norm is slaney, got %r" % (filter_norm,))
+    scale = "htk" if mel_scale is None else mel_scale
+    if scale not in MEL_SCALES:
+        raise ValueError("--mel-scale is htk or slaney, got %r" % (mel_scale,))
+    lo = 0.0 if f_min is None else f_min
+    for flag, v in (("--f-min", lo), ("--f-max", f_max)):
+        if v is not None and (not np.isfinite(v) or v < 0):
+            raise ValueError("%s: a frequency in Hz at or above 0, got %r" % (flag, v))
+    if f_max is not None:
+        try:
+            mel_points(int(mel), float(lo), float(f_max), scale)
+        except ValueError as e:
+            raise ValueError("--f-min, --f-max: %s" % e)
+    spec["mel"] = (int(mel), float(lo), None if f_max is None else float(f_max), scale)
+    return spec
+
+
 def check_band_gains_db_args(band_gains_db, decode):
     """--band-gains-db as given (None: not given), "LO-HI:DB[,LO-HI:DB...]" -> (edges in Hz float64 [bands + 1], gains float64
     [bands]) for PacStore.decode_window(band_gains=, band_edges_hz=), or None.  LO and HI are frequencies in Hz, 0 <= LO < HI,
@@ -814,7 +885,7 @@ def _levels_of_mix(store, rate_divisor, mix):
 
 
 def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=1, mix=None, sample_rate=None, overlay=None,
-                    band_gains=None, speed=None, ir=None):
+                    band_gains=None, speed=None, ir=None, stft=None):
     """excerpt: None (the whole file, mrc_decode_pac_pcm16) or (start, samples): that many samples from sample `start` on
     (samples None: to the end of the file), decoded through a one-file PacStore -- only the blocks the excerpt overlaps are
     parsed and synthesised; what lies outside the file is silence.  rate_divisor 2 or 4: at that fraction of the sample rate,
@@ -836,10 +907,18 @@ def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=
     ir: None or the path of an impulse response (read_ir: a .npy array at the output rate, or a mono 16-bit WAV brought to it):
     the file convolved with it through the store as well (PacStore.decode_window(ir_index=)), last of all -- at the output rate,
     after the speed; the overlay stays dry, the same one call.  The output keeps the length it has without --ir.
+    stft: None, or check_stft_energies_args' dict: wav_path is then a .npy file and receives PacStore.stft_window of the very row
+    the other arguments describe, (samples - n_fft) // hop + 1 whole frames of it (none: an empty array), in place of the WAV
+    -> the array as written.
     -> int16 [nCh][samples] as written."""
     with open(pac_path, "rb") as fp:
         buf = fp.read()
-    cfg, _, _, _ = pacfile.read_header(buf)
+    try:
+        cfg, _, _, _ = pacfile.read_header(buf)
+    except MrcError as e:
+        if stft is None:
+            raise
+        raise ValueError("%s: not a .pac file (%s)" % (pac_path, e))
     bufs = [buf]
     if overlay is not None:
         with open(overlay[0], "rb") as fp:
@@ -869,7 +948,7 @@ def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=
         except ValueError as e:
             raise ValueError("--speed: %s" % e)
     if (rate_divisor != 1 or mix is not None or resample is not None or overlay is not None or band_gains is not None
-            or speed is not None or ir is not None) and excerpt is None:
+            or speed is not None or ir is not None or stft is not None) and excerpt is None:
         excerpt = (0, None)
     taps = None if ir is None else read_ir(ir, cfg.sample_rate // rate_divisor if sample_rate is None else int(sample_rate))
     h = Handle(sample_rate=cfg.sample_rate, n_mdct_lines=cfg.n_mdct_lines, n_scale_bits=cfg.n_scale_bits,
@@ -891,10 +970,27 @@ def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=
                 if taps is not None:                     # the file through the room; the overlay dry
                     store.set_impulse_responses([taps])
                     shaped.update(ir_index=[0] if overlay is None else [[0, -1]])
+                if stft is not None:                     # the same row, framed and transformed instead of written
+                    from .store import mel_bin_weights, mel_points
+                    rate_out = cfg.sample_rate // rate_divisor if sample_rate is None else int(sample_rate)
+                    frames = max(0, (samples - stft["n_fft"]) // stft["hop"] + 1)
+                    spectrum = dict(frame_window=stft["window"], output="complex" if stft["complex"] else "power")
+                    if stft["mel"] is not None:
+                        n_mel, f_min, f_max, scale = stft["mel"]
+                        try:
+                            points = mel_points(n_mel, f_min, rate_out / 2.0 if f_max is None else f_max, scale)
+                        except ValueError as e:
+                            raise ValueError("--mel: %s" % e)
+                        spectrum.update(output="bank", bank=mel_bin_weights(stft["n_fft"], rate_out, points, stft["norm"]))
+                    window = lambda files, starts, _samples, **kw: store.stft_window(files, starts, frames, stft["hop"], stft["n_fft"],
+                                                                                     **spectrum, **kw)
+                    window_sum = lambda files, starts, gains, _samples, **kw: window(files, starts, _samples, gains=gains, **kw)
+                else:
+                    window, window_sum = store.decode_window, store.decode_window_sum
                 if overlay is None:
                     if band_gains is not None:
                         shaped["band_gains"] = band_gains[1]
-                    got = store.decode_window([0], [start], samples, rate_divisor=rate_divisor, mix=mix, resample=resample, **shaped)
+                    got = window([0], [start], samples, rate_divisor=rate_divisor, mix=mix, resample=resample, **shaped)
                 else:
                     # the levels live at the rate divisor's rate: the excerpt's span there (the whole of it, rounded outwards)
                     up, down = resample if resample is not None else (1, 1)
@@ -908,11 +1004,15 @@ def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=
                     print("overlay: %s at a factor of %.9g (%g dB under the excerpt)" % (overlay[0], gain, overlay[1]))
                     if band_gains is not None:           # (the overlay's row: ones)
                         shaped["band_gains"] = np.stack([band_gains[1], np.ones_like(band_gains[1])])[None]
-                    got = store.decode_window_sum([[0, 1]], [[start, overlay[2]]], [[1.0, gain]], samples, rate_divisor=rate_divisor,
-                                                  mix=mix, resample=resample, **shaped)
-                inter = np.ascontiguousarray(got[0].cpu().numpy().T)
+                    got = window_sum([[0, 1]], [[start, overlay[2]]], [[1.0, gain]], samples, rate_divisor=rate_divisor,
+                                     mix=mix, resample=resample, **shaped)
+                inter = got[0].cpu().numpy() if stft is not None else np.ascontiguousarray(got[0].cpu().numpy().T)
     finally:
         h.close()
+    if stft is not None:
+        with open(wav_path, "wb") as fp:
+            np.save(fp, inter)
+        return inter
     data = inter.astype("<i2", copy=False)
     with open(wav_path, "wb") as fp:
         fp.write(wav_header(inter.shape[1], data.nbytes, cfg.sample_rate // rate_divisor if sample_rate is None else int(sample_rate)))
@@ -1088,6 +1188,17 @@ def main(argv=None):
                          "points q, q + 1, q + 2")
     ap.add_argument("--filter-norm", default=None, metavar="slaney",
                     help="with --filterbank-energies: slaney divides every filter by half its width in Hz")
+    ap.add_argument("--stft-energies", action="store_true",
+                    help="src is a .pac file, dst a .npy file: write the short-time Fourier transform of the row -d would decode, "
+                         "float32 power [channels][N / 2 + 1][frames] for --n-fft N --hop H (frame j: samples [j H, j H + N), "
+                         "--samples rounded down to whole frames); --mel N: the totals of N mel filters on the bins; --complex: "
+                         "the complex64 bins; composes with --start, --samples, --rate-divisor, --sample-rate, --mix, --speed, "
+                         "--ir, --band-gains-db, --overlay and --snr-db")
+    ap.add_argument("--n-fft", type=int, default=None, metavar="N",
+                    help="with --stft-energies: the points of a frame, even, 16..2048, factors 2, 3 and 5 only")
+    ap.add_argument("--win-length", type=int, default=None, metavar="W",
+                    help="with --stft-energies: the periodic Hann window's taps, centred in the N points (default N)")
+    ap.add_argument("--complex", action="store_true", help="with --stft-energies: write the complex bins, not their power")
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(_join_vbr_grid(sys.argv[1:] if argv is None else argv))
     try:
@@ -1102,26 +1213,42 @@ def main(argv=None):
             given, **{"--levels": a.levels is not None, "--levels-window": a.levels_window is not None,
                       "--rate-divisor": a.rate_divisor is not None, "--band-gains-db": a.band_gains_db is not None,
                       "--speed": a.speed is not None, "--ir": a.ir is not None})
-        bank = check_filterbank_energies_args(a.filterbank_energies, a.hop, a.mel, a.f_min, a.f_max, a.mel_scale, a.filter_points,
-                                              a.filter_norm, dict(given_energies, **{"--band-energies": a.band_energies,
-                                                                                     "--band-edges": a.band_edges is not None}))
-        bands = check_band_energies_args(a.band_energies, a.hop if bank is None else None, a.band_edges, given_energies)
+        stft = check_stft_energies_args(a.stft_energies, a.n_fft, a.hop, a.win_length, a.mel, a.f_min, a.f_max, a.mel_scale, a.filter_norm,
+                                        a.complex, dict(given_energies, **{"--band-energies": a.band_energies,
+                                                                           "--band-edges": a.band_edges is not None,
+                                                                           "--filterbank-energies": a.filterbank_energies,
+                                                                           "--filter-points": a.filter_points is not None}))
+        # (--hop and the mel flags are --stft-energies' when it is given: the line-energy checks do not see them)
+        mel_flags = (None,) * 4 if stft is not None else (a.mel, a.f_min, a.f_max, a.mel_scale)
+        bank = check_filterbank_energies_args(a.filterbank_energies, a.hop, *mel_flags, a.filter_points,
+                                              None if stft is not None else a.filter_norm,
+                                              dict(given_energies, **{"--band-energies": a.band_energies,
+                                                                      "--band-edges": a.band_edges is not None}))
+        bands = check_band_energies_args(a.band_energies, a.hop if bank is None and stft is None else None, a.band_edges, given_energies)
+        row = a.decode or stft is not None                   # the flags that describe a decoded row
         levels = check_levels_args(a.levels, a.levels_window, given)
         if levels is None and (a.src is None or a.dst is None):
             raise ValueError("the following arguments are required: src, dst")
-        excerpt = check_excerpt_args(a.start, a.samples, a.decode)
-        rate_divisor = check_rate_divisor_args(a.rate_divisor, a.decode or levels is not None)
-        mix = check_mix_args(a.mix, a.decode or levels is not None or bands is not None or bank is not None)
-        sample_rate = check_sample_rate_args(a.sample_rate, a.decode, a.rate_divisor is not None)
-        overlay = check_overlay_args(a.overlay, a.snr_db, a.overlay_start, a.decode)
-        band_gains = check_band_gains_db_args(a.band_gains_db, a.decode)
-        speed = check_speed_args(a.speed, a.decode)
-        ir = check_ir_args(a.ir, a.decode)
+        excerpt = check_excerpt_args(a.start, a.samples, row)
+        rate_divisor = check_rate_divisor_args(a.rate_divisor, row or levels is not None)
+        mix = check_mix_args(a.mix, row or levels is not None or bands is not None or bank is not None)
+        sample_rate = check_sample_rate_args(a.sample_rate, row, a.rate_divisor is not None)
+        overlay = check_overlay_args(a.overlay, a.snr_db, a.overlay_start, row)
+        band_gains = check_band_gains_db_args(a.band_gains_db, row)
+        speed = check_speed_args(a.speed, row)
+        ir = check_ir_args(a.ir, row)
         if levels is not None:
             from .store import check_levels_mix
             check_levels_mix(mix, "--mix")
     except ValueError as e:
         ap.error(str(e))
+    if stft is not None:
+        try:
+            spectrum = decode_pac_file(a.src, a.dst, a.device, excerpt, rate_divisor, mix, sample_rate, overlay, band_gains, speed, ir, stft)
+        except ValueError as e:
+            ap.error(str(e))
+        print("%s: %s %s" % (a.dst, " x ".join(str(v) for v in spectrum.shape), spectrum.dtype))
+        return
     if bands is not None:
         try:
             band_energies_of_file(a.src, a.dst, bands[0], bands[1], a.device, mix)

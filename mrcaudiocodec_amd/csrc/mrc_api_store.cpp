@@ -1345,12 +1345,23 @@ int set_irs(mrc_pac_store* s, int64_t n_irs, const int64_t* ir_offset, const dou
     return MRC_OK;
 }
 
+// The handle's slab size read as "one slab" by the calls made in its scope, for a caller that has cut the slab itself.  The one
+// place that sets handle state aside: never nested (decode_window_reverb holds one at a time; stft_window holds none).
+struct OneSlabScope {
+    mrc_handle* h;
+    int64_t was;
+    explicit OneSlabScope(mrc_handle* handle) : h(handle), was(handle->storeSlabSamples) { h->storeSlabSamples = 0; }
+    ~OneSlabScope() { h->storeSlabSamples = was; }
+    OneSlabScope(const OneSlabScope&) = delete;
+    OneSlabScope& operator=(const OneSlabScope&) = delete;
+};
+
+// fn: who is named in a refusal; oneSlab: the caller (stft_window) has cut the slab already and the call runs as one
 int decode_window_reverb(mrc_pac_store* s, int rate_divisor, int mix, int n_ratios, const int32_t* ratio_up, const int32_t* ratio_down,
                          int zeros, double rolloff, int n_bands, const double* edge_hz, const double* band_gain, int64_t n_items,
                          const int64_t* term_offset, const int64_t* file, const int64_t* start, const double* gain,
                          const int32_t* ratio_of, const int32_t* ir_of, int64_t window, int n_channels_out, int format, void* out,
-                         void* stream) {
-    const char* const fn = kWinReverb;
+                         void* stream, const char* fn = kWinReverb, bool oneSlab = false) {
     MRC_TRY(store_alive(s, fn));
     mrc_handle* h = s->h;
     const std::string w = fn;
@@ -1379,9 +1390,14 @@ int decode_window_reverb(mrc_pac_store* s, int rate_divisor, int mix, int n_rati
         Lpre = std::max(Lpre, s->irLen[(size_t)v] - 1);
         anyConvolved = true;
     }
-    if (!anyConvolved)                                       // the speeds call's path, unchanged
+    if (!anyConvolved) {                                     // the speeds call's path, unchanged
+        if (!oneSlab)
+            return decode_window_rows(s, fn, rate_divisor, mix, 1, 1, zeros, rolloff, n_bands == 0 ? nullptr : &bands, n_items, term_offset,
+                                      file, start, gain, window, n_channels_out, format, out, stream, &ratios);
+        OneSlabScope scope(h);
         return decode_window_rows(s, fn, rate_divisor, mix, 1, 1, zeros, rolloff, n_bands == 0 ? nullptr : &bands, n_items, term_offset,
                                   file, start, gain, window, n_channels_out, format, out, stream, &ratios);
+    }
     const int64_t Wd = window + Lpre;
     if (Wd > ((int64_t)1 << 40))
         return fail(h, MRC_ERR_INVALID, w + ": window + the longest impulse response named - 1 = " + std::to_string(Wd) + " exceeds 2^40");
@@ -1396,7 +1412,7 @@ int decode_window_reverb(mrc_pac_store* s, int rate_divisor, int mix, int n_rati
     DrainGuard drain{{st, nullptr, nullptr}};
     const size_t elem = format == MRC_WINDOW_PCM16 ? 2 : format == MRC_WINDOW_F32 ? 4 : 8;
     const int nch = n_channels_out;
-    const int64_t M = (window + kRevB - 1) / kRevB, slab = h->storeSlabSamples, rowCap = std::max<int64_t>(1, 0x7fffffffLL / M);
+    const int64_t M = (window + kRevB - 1) / kRevB, slab = oneSlab ? 0 : h->storeSlabSamples, rowCap = std::max<int64_t>(1, 0x7fffffffLL / M);
     int64_t stats[4] = {0, 0, 0, 0};
     double ms[4] = {0, 0, 0, 0}, reverbMs[2] = {0, 0};
     std::vector<int64_t> ident, starts;
@@ -1423,12 +1439,7 @@ int decode_window_reverb(mrc_pac_store* s, int rate_divisor, int mix, int n_rati
         const RatioArgs slabRatios{n_ratios, ratio_up, ratio_down, ratio_of + u0};
         // (the slab is cut here, by output samples: the inner call does not cut it again by its intermediate spans, which
         // would leave a short second slab behind every full one)
-        struct OneSlab {
-            mrc_handle* h;
-            int64_t was;
-            ~OneSlab() { h->storeSlabSamples = was; }
-        } oneSlab{h, h->storeSlabSamples};
-        h->storeSlabSamples = 0;
+        OneSlabScope scope(h);
         MRC_TRY(decode_window_rows(s, fn, rate_divisor, mix, 1, 1, zeros, rolloff, n_bands == 0 ? nullptr : &slabBands, nT, ident.data(),
                                    file + u0, starts.data(), ones.data(), Wd, nch, MRC_WINDOW_F64, b.reverbDry.p, stream, &slabRatios));
         for (int i = 0; i < 4; ++i) { stats[i] += s->stats[i]; ms[i] += s->ms[i]; }
@@ -1489,6 +1500,155 @@ int decode_window_reverb(mrc_pac_store* s, int rate_divisor, int mix, int n_rati
     return MRC_OK;
 }
 
+// mrc_pac_store_stft_window: a slab loop AROUND the reverb entry.  Per slab of whole rows that entry writes the rows as
+// MRC_WINDOW_F64 over L = (n_frames - 1) hop + n_fft samples into StoreBufs::stftRows (its own dry-term scratch is in use
+// underneath), then stft_kernel (mrc_kernels_stft.hip) frames and transforms them on the same stream.  The twiddles, the frame
+// window and the bank's supports and weights go up once per call.
+const char* const kStft = "mrc_pac_store_stft_window";
+
+// exp(-2 pi i t / n) for 0 <= t < n from long double, the quadrant taken out first: the axes are exact
+void stft_twiddles(int n, double2* w) {
+    const long double halfPi = acosl(-1.0L) / 2.0L;
+    for (int t = 0; t < n; ++t) {
+        const int q = (int)((4LL * t) / n);
+        const long double th = halfPi * (long double)(4LL * t - (long long)q * n) / (long double)n;
+        const double c = (double)cosl(th), sn = (double)sinl(th);
+        w[t] = q == 0 ? make_double2(c, -sn) : q == 1 ? make_double2(-sn, -c) : q == 2 ? make_double2(-c, sn) : make_double2(sn, c);
+    }
+}
+
+int stft_window(mrc_pac_store* s, int rate_divisor, int mix, int n_ratios, const int32_t* ratio_up, const int32_t* ratio_down, int zeros,
+                double rolloff, int n_bands, const double* edge_hz, const double* band_gain, int64_t n_items,
+                const int64_t* term_offset, const int64_t* file, const int64_t* start, const double* gain, const int32_t* ratio_of,
+                const int32_t* ir_of, int n_fft, const double* frame_window, int64_t n_frames, int64_t hop, int mode, int n_filters,
+                const double* bank, int n_channels_out, int format, void* out, void* stream) {
+    const char* const fn = kStft;
+    MRC_TRY(store_alive(s, fn));
+    mrc_handle* h = s->h;
+    const std::string w = fn;
+    s->stftMs = 0.0;
+    // ---- this call's own arguments
+    int nRad = 0;
+    if (n_fft < 16 || n_fft > MRC_MAX_STFT_POINTS || (n_fft & 1) || stft_radices(n_fft / 2, &nRad) == 0)
+        return fail(h, MRC_ERR_INVALID, w + ": n_fft " + std::to_string(n_fft) + " must be even, in 16.." +
+                                            std::to_string(MRC_MAX_STFT_POINTS) + " and a product of 2s, 3s and 5s");
+    const unsigned long long radices = stft_radices(n_fft / 2, &nRad);
+    if (!frame_window) return fail(h, MRC_ERR_INVALID, w + ": frame_window is NULL");
+    for (int i = 0; i < n_fft; ++i)
+        if (!std::isfinite(frame_window[i])) return fail(h, MRC_ERR_INVALID, w + ": frame_window[" + std::to_string(i) + "] is not finite");
+    if (n_frames < 0) return fail(h, MRC_ERR_INVALID, w + ": n_frames < 0");
+    if (hop < 1) return fail(h, MRC_ERR_INVALID, w + ": hop < 1");
+    const int64_t kMaxL = (int64_t)1 << 40;
+    if (n_frames > 0 && (hop > kMaxL || n_frames - 1 > (kMaxL - n_fft) / hop))
+        return fail(h, MRC_ERR_INVALID, w + ": L = (n_frames - 1) hop + n_fft exceeds 2^40");
+    if (mode != MRC_STFT_COMPLEX && mode != MRC_STFT_POWER && mode != MRC_STFT_BANK)
+        return fail(h, MRC_ERR_INVALID, w + ": mode " + std::to_string(mode) + " is none of MRC_STFT_COMPLEX, _POWER, _BANK");
+    if (format != MRC_WINDOW_F32 && format != MRC_WINDOW_F64)
+        return fail(h, MRC_ERR_INVALID, w + ": format " + std::to_string(format) + " is neither MRC_WINDOW_F32 nor MRC_WINDOW_F64");
+    const int nBins = n_fft / 2 + 1;
+    if (mode == MRC_STFT_BANK) {
+        if (n_filters < 1 || n_filters > MRC_MAX_STORE_BANDS)
+            return fail(h, MRC_ERR_INVALID, w + ": n_filters " + std::to_string(n_filters) + " outside 1.." + std::to_string(MRC_MAX_STORE_BANDS));
+        if (!bank) return fail(h, MRC_ERR_INVALID, w + ": bank is NULL");
+        for (int64_t i = 0; i < (int64_t)n_filters * nBins; ++i)
+            if (!std::isfinite(bank[i]))
+                return fail(h, MRC_ERR_INVALID, w + ": bank[" + std::to_string(i / nBins) + "][" + std::to_string(i % nBins) + "] is not finite");
+    } else if (n_filters != 0 || bank) {
+        return fail(h, MRC_ERR_INVALID, w + ": n_filters must be 0 and bank NULL unless mode is MRC_STFT_BANK");
+    }
+    // ---- every check of the reverb entry, made by that entry at window 0: nothing is launched
+    MRC_TRY(decode_window_reverb(s, rate_divisor, mix, n_ratios, ratio_up, ratio_down, zeros, rolloff, n_bands, edge_hz, band_gain, n_items,
+                                 term_offset, file, start, gain, ratio_of, ir_of, 0, n_channels_out, MRC_WINDOW_F64, out, stream, fn));
+    if (n_items == 0 || n_frames == 0) return MRC_OK;
+    if (!out) return fail(h, MRC_ERR_INVALID, w + ": out is NULL");
+    const int64_t L = (n_frames - 1) * hop + n_fft;
+    // the reverb entry's bound on window + pre-roll, which its call at window 0 cannot reach (ir_of has been checked by it)
+    int64_t Lpre = 0;
+    for (int64_t k = 0; k < term_offset[n_items]; ++k)
+        if (ir_of[k] >= 0) Lpre = std::max(Lpre, s->irLen[(size_t)ir_of[k]] - 1);
+    if (L + Lpre > kMaxL)
+        return fail(h, MRC_ERR_INVALID, w + ": L + the longest impulse response named - 1 = " + std::to_string(L + Lpre) + " exceeds 2^40");
+
+    MRC_HIP(h, hipSetDevice(h->device));
+    StoreBufs& b = h->store;
+    MRC_HIP(h, b.stftEv.create());
+    hipStream_t st = pick_stream(h, stream);
+    DrainGuard drain{{st, nullptr, nullptr}};
+    // ---- the tables (one copy): twiddles | frame window | weights on the supports | lo, hi, offset per filter
+    const int nF = mode == MRC_STFT_BANK ? n_filters : 0;
+    std::vector<int32_t> tab((size_t)(3 * nF));
+    std::vector<double> weights;
+    for (int q = 0; q < nF; ++q) {
+        const double* row = bank + (size_t)q * nBins;
+        int lo = 0, hi = nBins;
+        while (lo < nBins && row[lo] == 0.0) ++lo;
+        while (hi > lo && row[hi - 1] == 0.0) --hi;
+        if (lo == nBins) lo = hi = 0;
+        tab[(size_t)q] = lo;
+        tab[(size_t)(nF + q)] = hi;
+        tab[(size_t)(2 * nF + q)] = (int32_t)weights.size();
+        weights.insert(weights.end(), row + lo, row + hi);
+    }
+    StageLayout lay(256);
+    const size_t oTw = lay.add<double2>(n_fft), oWin = lay.add<double>(n_fft), oW = lay.add<double>((int64_t)weights.size()),
+                 oTab = lay.add<int32_t>((int64_t)tab.size());
+    std::vector<unsigned char> host(lay.total());
+    stft_twiddles(n_fft, (double2*)(host.data() + oTw));
+    memcpy(host.data() + oWin, frame_window, sizeof(double) * (size_t)n_fft);
+    if (!weights.empty()) memcpy(host.data() + oW, weights.data(), sizeof(double) * weights.size());
+    if (!tab.empty()) memcpy(host.data() + oTab, tab.data(), sizeof(int32_t) * tab.size());
+    MRC_HIP(h, hipStreamSynchronize(st));                    // (an earlier call's kernel may still read the tables)
+    MRC_HIP(h, b.stftTab.reserve(lay.total()));
+    MRC_HIP(h, hipMemcpy(b.stftTab.p, host.data(), lay.total(), hipMemcpyHostToDevice));
+    const unsigned char* dtab = b.stftTab.as<unsigned char>();
+
+    StftParams P{};
+    P.win = (const double*)(dtab + oWin);
+    P.tw = (const double2*)(dtab + oTw);
+    P.bankTab = (const int*)(dtab + oTab);
+    P.bankW = (const double*)(dtab + oW);
+    P.L = L; P.nFrames = n_frames; P.hop = hop; P.radices = radices;
+    P.nch = n_channels_out; P.nFft = n_fft; P.nRad = nRad; P.mode = mode; P.format = format; P.nFilters = nF;
+    const int nch = n_channels_out;
+    const int64_t nOut = mode == MRC_STFT_BANK ? n_filters : nBins;
+    const size_t rowBytes = (size_t)nch * (size_t)nOut * (size_t)n_frames * (format == MRC_WINDOW_F32 ? 4 : 8) * (mode == MRC_STFT_COMPLEX ? 2 : 1);
+    const int64_t slab = h->storeSlabSamples, rowCap = std::max<int64_t>(1, 0x7fffffffLL / (nch * n_frames));
+    int64_t stats[4] = {0, 0, 0, 0};
+    double ms[4] = {0, 0, 0, 0}, reverbMs[2] = {0, 0}, stftMs = 0.0;
+    std::vector<int64_t> offs;
+    for (int64_t first = 0, last; first < n_items; first = last) {   // rows [first, last), their terms from u0
+        last = first + 1;
+        while (last < n_items && last - first < rowCap && (slab == 0 || (last + 1 - first) * L <= slab)) ++last;
+        const int64_t nRows = last - first, u0 = term_offset[first];
+        MRC_HIP(h, b.stftRows.reserve(sizeof(double) * (size_t)(nRows * nch * L)));
+        offs.resize((size_t)nRows + 1);
+        for (int64_t r = 0; r <= nRows; ++r) offs[(size_t)r] = term_offset[first + r] - u0;
+        // (the slab is cut here, by the rows' samples: the inner entry is told to run it as one slab of its own)
+        MRC_TRY(decode_window_reverb(s, rate_divisor, mix, n_ratios, ratio_up, ratio_down, zeros, rolloff, n_bands, edge_hz,
+                                     band_gain ? band_gain + u0 * n_bands : nullptr, nRows, offs.data(), file ? file + u0 : nullptr,
+                                     start ? start + u0 : nullptr, gain ? gain + u0 : nullptr, ratio_of ? ratio_of + u0 : nullptr,
+                                     ir_of ? ir_of + u0 : nullptr, L, nch, MRC_WINDOW_F64, b.stftRows.p, stream, fn, true));
+        for (int i = 0; i < 4; ++i) { stats[i] += s->stats[i]; ms[i] += s->ms[i]; }
+        for (int i = 0; i < 2; ++i) reverbMs[i] += s->reverbMs[i];
+        P.rows = b.stftRows.as<double>();
+        P.out = (unsigned char*)out + (size_t)first * rowBytes;
+        P.nRows = (int)nRows;
+        MRC_HIP(h, hipEventRecord(b.stftEv[0], st));
+        MRC_HIP(h, launch_stft(P, st));
+        MRC_HIP(h, hipEventRecord(b.stftEv[1], st));
+        MRC_HIP(h, hipStreamSynchronize(st));
+        double t = 0.0;
+        MRC_HIP(h, b.stftEv.elapsed(0, 1, &t));
+        stftMs += t;
+    }
+    for (int i = 0; i < 4; ++i) { s->stats[i] = stats[i]; s->ms[i] = ms[i]; }
+    s->ms[3] += stftMs;
+    s->reverbMs[0] = reverbMs[0];
+    s->reverbMs[1] = reverbMs[1];
+    s->stftMs = stftMs;
+    return MRC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1516,6 +1676,23 @@ int mrc_pac_store_decode_window_reverb(mrc_pac_store* s, int rate_divisor, int m
 int mrc_pac_store_reverb_ms(mrc_pac_store* s, double* ms) {
     MRC_TRY(store_alive(s, "mrc_pac_store_reverb_ms"));
     if (ms) { ms[0] = s->reverbMs[0]; ms[1] = s->reverbMs[1]; }
+    return MRC_OK;
+}
+
+int mrc_pac_store_stft_window(mrc_pac_store* s, int rate_divisor, int mix, int n_ratios, const int32_t* ratio_up,
+                              const int32_t* ratio_down, int zeros, double rolloff, int n_bands, const double* edge_hz,
+                              const double* band_gain, int64_t n_items, const int64_t* term_offset, const int64_t* file,
+                              const int64_t* start, const double* gain, const int32_t* ratio_of, const int32_t* ir_of, int n_fft,
+                              const double* frame_window, int64_t n_frames, int64_t hop, int mode, int n_filters, const double* bank,
+                              int n_channels_out, int format, void* out, void* stream) {
+    return stft_window(s, rate_divisor, mix, n_ratios, ratio_up, ratio_down, zeros, rolloff, n_bands, edge_hz, band_gain, n_items,
+                       term_offset, file, start, gain, ratio_of, ir_of, n_fft, frame_window, n_frames, hop, mode, n_filters, bank,
+                       n_channels_out, format, out, stream);
+}
+
+int mrc_pac_store_stft_ms(mrc_pac_store* s, double* ms) {
+    MRC_TRY(store_alive(s, "mrc_pac_store_stft_ms"));
+    if (ms) ms[0] = s->stftMs;
     return MRC_OK;
 }
 

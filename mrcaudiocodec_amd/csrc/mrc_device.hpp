@@ -151,6 +151,23 @@ template <> __device__ __forceinline__ void butterfly<4>(double2* u) {
     u[3] = make_double2(b.x - d.y, b.y + d.x);
 }
 
+// radix 5 (stft_kernel only): y_q = sum_r u_r e^{-2 pi i q r / 5}, through the sums and differences of the pairs (1, 4), (2, 3)
+template <> __device__ __forceinline__ void butterfly<5>(double2* u) {
+    const double c1 = 0.30901699437494742410, c2 = -0.80901699437494742410;    // cos(2 pi / 5), cos(4 pi / 5)
+    const double s1 = 0.95105651629515357212, s2 = 0.58778525229247312917;     // sin(2 pi / 5), sin(4 pi / 5)
+    const double2 t1 = make_double2(u[1].x + u[4].x, u[1].y + u[4].y), t2 = make_double2(u[2].x + u[3].x, u[2].y + u[3].y);
+    const double2 t3 = make_double2(u[1].x - u[4].x, u[1].y - u[4].y), t4 = make_double2(u[2].x - u[3].x, u[2].y - u[3].y);
+    const double2 a1 = make_double2(u[0].x + (c1 * t1.x + c2 * t2.x), u[0].y + (c1 * t1.y + c2 * t2.y));
+    const double2 a2 = make_double2(u[0].x + (c2 * t1.x + c1 * t2.x), u[0].y + (c2 * t1.y + c1 * t2.y));
+    const double2 b1 = make_double2(s1 * t3.x + s2 * t4.x, s1 * t3.y + s2 * t4.y);
+    const double2 b2 = make_double2(s2 * t3.x - s1 * t4.x, s2 * t3.y - s1 * t4.y);
+    u[0] = make_double2(u[0].x + (t1.x + t2.x), u[0].y + (t1.y + t2.y));
+    u[1] = make_double2(a1.x + b1.y, a1.y - b1.x);                             // a1 - i b1
+    u[2] = make_double2(a2.x + b2.y, a2.y - b2.x);
+    u[3] = make_double2(a2.x - b2.y, a2.y + b2.x);
+    u[4] = make_double2(a1.x - b1.y, a1.y + b1.x);
+}
+
 template <> __device__ __forceinline__ void butterfly<8>(double2* u) {
     const double h = 0.70710678118654752440;
     auto add = [](double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); };
@@ -235,6 +252,25 @@ __device__ __forceinline__ double2* fft_lds(double2* A, double2* B, int n, const
         p *= R;
     }
     return A;
+}
+// One pass of radix R = 2, 3, 4 or 5 chosen at run time (stft_kernel: n = 2^a 3^b 5^c; fft_lds above keeps its own list, so
+// the kernels that use it are compiled as they were).  The caller places the barrier between two passes.
+template <class TW, int NT>
+__device__ __forceinline__ void fft_pass_2345(int R, const double2* in, double2* out, int n, int p, const TW& W, int tid) {
+    const bool pow2 = (p & (p - 1)) == 0;
+    if (R == 4) {
+        if (pow2) fft_pass<4, true, TW, NT>(in, out, n, p, W, tid);
+        else fft_pass<4, false, TW, NT>(in, out, n, p, W, tid);
+    } else if (R == 2) {
+        if (pow2) fft_pass<2, true, TW, NT>(in, out, n, p, W, tid);
+        else fft_pass<2, false, TW, NT>(in, out, n, p, W, tid);
+    } else if (R == 3) {
+        if (pow2) fft_pass<3, true, TW, NT>(in, out, n, p, W, tid);
+        else fft_pass<3, false, TW, NT>(in, out, n, p, W, tid);
+    } else {
+        if (pow2) fft_pass<5, true, TW, NT>(in, out, n, p, W, tid);
+        else fft_pass<5, false, TW, NT>(in, out, n, p, W, tid);
+    }
 }
 // n a power of two (radix 4 / 2 passes only), twiddles from the LDS quadrant
 template <int NT = kThreads>

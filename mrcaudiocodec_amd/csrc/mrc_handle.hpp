@@ -248,6 +248,10 @@ struct StoreBufs {
     DevBuf reverbDry, reverbSpec, reverbIn, reverbTw;
     PinnedBuf reverbPin;
     EventSet<3> reverbEv;            // forward transforms start | fold starts | windows written
+    // mrc_pac_store_stft_window: a slab's rows [row][channel][L] (float64, written by the reverb entry, whose own scratch is
+    // in use underneath), and the call's tables in one allocation: twiddles | frame window | bank weights | bank supports
+    DevBuf stftRows, stftTab;
+    EventSet<2> stftEv;              // stft_kernel starts | ended
 };
 
 // ---- the host plan of whole `.pac` files, shared by mrc_decode_pac_pcm16 and mrc_pac_nmr (mrc_api_decode.cpp)
@@ -386,6 +390,7 @@ struct mrc_pac_store {
     mrc::DevBuf irBank;
     std::vector<int64_t> irLen, irPart;
     double reverbMs[2] = {0, 0};     // last decode_window_reverb: reverb_forward_kernel | reverb_fold_kernel
+    double stftMs = 0;               // last stft_window: stft_kernel, summed over the slabs
     int64_t stats[4] = {0, 0, 0, 0}; // last decode_window: chunks parsed, decode_kernel launches, slabs, plan bytes uploaded
     double ms[4] = {0, 0, 0, 0};     // ... plan upload | unpack | synthesis | window_out_kernel (resampled: resample_out_kernel)
                                      // (after block_energy: block_energy_kernel launches in [1]; ms: upload | unpack | that kernel | 0;

@@ -339,6 +339,25 @@ struct ReverbTerm {
 hipError_t launch_reverb_fold(int64_t nRows, const ReverbTerm* terms /* device */, const long long* termOffset /* device */,
                               int64_t window, int nchOut, int format, int64_t chStride, const double* dry, const double2* spectra,
                               const double2* bank, const double2* twiddle, void* out, hipStream_t st);
+// mrc_pac_store_stft_window (mrc_kernels_stft.hip).  rows (device) float64 [nRows][nch][L], L = (nFrames - 1) hop + nFft;
+// win (device) [nFft]; tw (device) exp(-2 pi i t / nFft) for 0 <= t < nFft; radices: the passes of the nFft / 2 point complex
+// transform, four bits each from the lowest (stft_radices); mode MRC_STFT_*, format MRC_WINDOW_F32 | _F64.  MRC_STFT_BANK:
+// bankTab (device) int32 [3][nFilters] -- lo, hi, and the offset of filter q's weights in bankW (device), whose entry
+// offset + (k - lo) is bin k's weight.  out [nRows][nch][nFft / 2 + 1 | nFilters][nFrames] ([2] under MRC_STFT_COMPLEX).
+struct StftParams {
+    const double* rows;
+    const double* win;
+    const double2* tw;
+    const int* bankTab;
+    const double* bankW;
+    void* out;
+    long long L, nFrames, hop;
+    unsigned long long radices;
+    int nRows, nch, nFft, nRad, mode, format, nFilters;
+};
+// 0 where n is not 2^a 3^b 5^c or takes more than 16 passes; else the radices, fours first, then 2, 3 and 5; *nRad their number
+unsigned long long stft_radices(int n, int* nRad);
+hipError_t launch_stft(const StftParams& P, hipStream_t st);
 // One entry of mrc_pac_store_block_energy: a channel of a block, or its mid.  sel 0 / 1: output channel L / R of a joint
 // slot (a non-joint slot has one channel, itself: 0); kEnergyMid: the mid (L + R) / 2 on the lines -- of a joint slot, or of
 // the PAIR of non-joint slots slot, slot + 1 (a stereo file's last block).

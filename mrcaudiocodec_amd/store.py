@@ -95,6 +95,14 @@ line's own frequency interval, so a filter narrower than a short block's line sp
         points = mel_points(80, 0.0, 24000.0)                                  # 82 points: HTK mel, 80 filters
         e = store.filterbank_window(files, starts, 100, 480, points)           # [len(files)][channels][80][100], on the GPU
         logmel = torch.log(e.clamp_min(1e-10))
+
+stft_window (mrc_pac_store_stft_window) is the STFT itself -- torch.stft's numbers, for a pretrained front end -- of any row
+decode_window_sum can make (mixtures, speeds, band gains, rooms), with the caller's frame window and mel matrix, and no
+waveform tensor in between:
+
+        bank = mel_bin_weights(400, 16000, mel_points(80, 0.0, 8000.0))        # [80][201], torchaudio's melscale_fbanks rule
+        e = store.stft_window(files, starts, 98, 160, 400, bank=bank, output="bank", rate_divisor=2, mix="mid", resample=(2, 3))
+        logmel = torch.log(e.clamp_min(1e-10))                                 # [len(files)][1][80][98]
 """
 import ctypes as C
 
@@ -558,6 +566,119 @@ def filterbank_line_weights(sample_rate, a, b, points_hz, norm=None):
     return lo[:n], hi[:n], [weight[at[q]:at[q + 1]] for q in range(n)]
 
 
+MAX_STFT_POINTS = _lib.MRC_MAX_STFT_POINTS
+STFT_OUTPUTS = {"complex": _lib.MRC_STFT_COMPLEX, "power": _lib.MRC_STFT_POWER, "bank": _lib.MRC_STFT_BANK}
+
+
+def stft_points_ok(n_fft):
+    """the library's rule for n_fft: an even int in 16..MAX_STFT_POINTS with no prime factor other than 2, 3 and 5"""
+    if not _is_int(n_fft) or not 16 <= int(n_fft) <= MAX_STFT_POINTS or int(n_fft) % 2:
+        return False
+    n = int(n_fft)
+    for p in (2, 3, 5):
+        while n % p == 0:
+            n //= p
+    return n == 1
+
+
+def hann_window(n, periodic=True):
+    """float64 [n]: 0.5 - 0.5 cos(2 pi k / n) (periodic: what torch.hann_window(n) gives) or cos(2 pi k / (n - 1))
+    (symmetric).  n an int >= 1, else ValueError"""
+    if not _is_int(n) or int(n) < 1:
+        raise ValueError("hann_window: n must be an int >= 1, got %r" % (n,))
+    n = int(n)
+    den = n if periodic else n - 1
+    if den == 0:
+        return np.ones(1, np.float64)
+    return 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n, dtype=np.float64) / den)
+
+
+def padded_window(win, n_fft):
+    """a window shorter than n_fft centred in n_fft points, as torch.stft(win_length=len(win)) does: (n_fft - len(win)) // 2
+    zeros in front, the rest behind -> float64 [n_fft].  ValueError for a window that is not 1-D, empty or longer than n_fft"""
+    try:
+        w = np.asarray(win, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("padded_window: win must be a 1-D array of taps, got %r" % (win,))
+    if not _is_int(n_fft) or w.ndim != 1 or not 1 <= w.size <= int(n_fft):
+        raise ValueError("padded_window: win must hold 1 to n_fft = %r taps in one dimension, got shape %s" % (n_fft, w.shape))
+    out = np.zeros(int(n_fft), np.float64)
+    left = (int(n_fft) - w.size) // 2
+    out[left:left + w.size] = w
+    return out
+
+
+def mel_bin_weights(n_fft, sample_rate, points_hz, norm=None):
+    """The matrix of a triangular filter bank on STFT bins -> float64 [n_filters][n_fft // 2 + 1] for stft_window(bank=):
+    filter q is the triangle over points_hz[q], [q + 1], [q + 2] (mel_points gives them) sampled AT the bin centre
+    frequencies f_k = k sample_rate / n_fft: max(0, min((f_k - a) / (b - a), (c - f_k) / (c - b))).  norm="slaney": each
+    filter times 2 / (c - a).  This is the rule of torchaudio's melscale_fbanks written out.  Unlike the line-based
+    filterbank_line_weights it samples and does not average: a filter narrower than a bin may hold no bin at all and then
+    reads 0 -- the STFT's own behaviour.  NumPy only.  ValueError as check_filter_points and check_filter_norm raise it, for
+    an n_fft that is no even int >= 2 and a sample rate that is not a positive finite number."""
+    what = "mel_bin_weights"
+    points = check_filter_points(points_hz, what)
+    slaney = check_filter_norm(norm, what) == _lib.MRC_FILTER_NORM_SLANEY
+    if not _is_int(n_fft) or int(n_fft) < 2 or int(n_fft) % 2:
+        raise ValueError("%s: n_fft must be an even int >= 2, got %r" % (what, n_fft))
+    if isinstance(sample_rate, bool) or not isinstance(sample_rate, (int, float, np.integer, np.floating)) or \
+            not np.isfinite(sample_rate) or not sample_rate > 0:
+        raise ValueError("%s: sample_rate must be a positive finite number, got %r" % (what, sample_rate))
+    f = np.arange(int(n_fft) // 2 + 1, dtype=np.float64) * float(sample_rate) / float(int(n_fft))
+    a, b, c = points[:-2, None], points[1:-1, None], points[2:, None]
+    w = np.maximum(0.0, np.minimum((f[None, :] - a) / (b - a), (c - f[None, :]) / (c - b)))
+    if slaney:
+        w = w * (2.0 / (c - a))
+    return np.ascontiguousarray(w)
+
+
+def check_stft(n_fft, hop, n_frames, frame_window=None, bank=None, output="power", what="stft_window"):
+    """the STFT arguments of stft_window -> (n_fft, hop, n_frames, window float64 [n_fft], bank float64 [filters][bins] or
+    None, MRC_STFT_* mode), else ValueError: n_fft under stft_points_ok's rule; hop an int >= 1; n_frames an int >= 0 with
+    (n_frames - 1) hop + n_fft <= 2^40; frame_window None (the periodic Hann) or n_fft finite taps; output "power",
+    "complex" or "bank"; bank a finite [1..MAX_BANDS][n_fft // 2 + 1] matrix with output="bank" and None otherwise"""
+    if not stft_points_ok(n_fft):
+        raise ValueError("%s: n_fft must be an even int in 16..%d with no prime factor other than 2, 3 and 5, got %r"
+                         % (what, MAX_STFT_POINTS, n_fft))
+    n_fft = int(n_fft)
+    for name, v, least in (("n_frames", n_frames, 0), ("hop", hop, 1)):
+        if not _is_int(v) or int(v) < least:
+            raise ValueError("%s: %s must be an int >= %d, got %r" % (what, name, least, v))
+    hop, n_frames = int(hop), int(n_frames)
+    if n_frames and (n_frames - 1) * hop + n_fft > 1 << 40:
+        raise ValueError("%s: (n_frames - 1) * hop + n_fft must not exceed 2^40, got %d frames at hop %d" % (what, n_frames, hop))
+    if not isinstance(output, str) or output not in STFT_OUTPUTS:
+        raise ValueError('%s: output must be "power", "complex" or "bank", got %r' % (what, output))
+    if frame_window is None:
+        window = hann_window(n_fft)
+    else:
+        try:
+            window = np.ascontiguousarray(np.asarray(frame_window, dtype=np.float64))
+        except (TypeError, ValueError):
+            raise ValueError("%s: frame_window must be %d float taps, got %r" % (what, n_fft, frame_window))
+        if window.shape != (n_fft,):
+            raise ValueError("%s: frame_window must hold n_fft = %d taps (padded_window centres a shorter one), got shape %s"
+                             % (what, n_fft, window.shape))
+        if not np.all(np.isfinite(window)):
+            raise ValueError("%s: frame_window must be finite, tap %d is not" % (what, int(np.flatnonzero(~np.isfinite(window))[0])))
+    if output != "bank":
+        if bank is not None:
+            raise ValueError('%s: bank goes with output="bank", got output=%r' % (what, output))
+        return n_fft, hop, n_frames, window, None, STFT_OUTPUTS[output]
+    if bank is None:
+        raise ValueError('%s: output="bank" needs a bank [filters][%d] (mel_bin_weights)' % (what, n_fft // 2 + 1))
+    try:
+        matrix = np.ascontiguousarray(np.asarray(bank, dtype=np.float64))
+    except (TypeError, ValueError):
+        raise ValueError("%s: bank must be a float matrix [filters][%d], got %r" % (what, n_fft // 2 + 1, bank))
+    if matrix.ndim != 2 or not 1 <= matrix.shape[0] <= MAX_BANDS or matrix.shape[1] != n_fft // 2 + 1:
+        raise ValueError("%s: bank must be [1..%d filters][n_fft // 2 + 1 = %d bins], got shape %s"
+                         % (what, MAX_BANDS, n_fft // 2 + 1, matrix.shape))
+    if not np.all(np.isfinite(matrix)):
+        raise ValueError("%s: bank must be finite" % what)
+    return n_fft, hop, n_frames, window, matrix, STFT_OUTPUTS[output]
+
+
 def _formats():
     import torch
     return {torch.int16: _lib.MRC_WINDOW_PCM16, torch.float32: _lib.MRC_WINDOW_F32, torch.float64: _lib.MRC_WINDOW_F64}
@@ -886,6 +1007,33 @@ class PacStore:
         through a room over dry noise is one call.  It composes with resample, speed_factors / speed_index, band_gains, mix
         and rate_divisor: the response acts last, at the term's output rate.  None: this call as it always was."""
         what = "decode_window_sum"
+        rate_divisor, mix, resample, channels, bands, speeds, irs, offsets, files, starts, gains = self._sum_rows(
+            what, files, starts, gains, item_offsets, channels, rate_divisor, mix, resample, band_gains, band_edges_hz, speed_factors,
+            speed_index, ir_index)
+        n, window = offsets.size - 1, int(window)
+        fmt, channels, out, stream = self._window_out(what, n, files, window, channels, dtype, out, stream)
+        if irs is not None:
+            self._reverb(rate_divisor, mix, resample, speeds, bands, irs, n, offsets, files, starts, gains, window, channels, fmt, out,
+                         stream)
+            return out
+        if speeds is not None:
+            self._speeds(rate_divisor, mix, speeds, bands, n, offsets, files, starts, gains, window, channels, fmt, out, stream)
+            return out
+        if bands is not None:
+            self._shaped(rate_divisor, mix, resample, bands, n, offsets, files, starts, gains, window, channels, fmt, out, stream)
+            return out
+        up, down, zeros, rolloff = resample if resample is not None else (1, 1, RESAMPLE_ZEROS, RESAMPLE_ROLLOFF)
+        pad = lambda a: a.ctypes.data if a.size else None
+        self._handle._check(lib.mrc_pac_store_decode_window_sum(
+            self._s, rate_divisor, _lib.MRC_MIX_EACH if mix is None else mix, up, down, zeros, rolloff, n, offsets.ctypes.data,
+            pad(files), pad(starts), pad(gains), window, channels, fmt, out.data_ptr() if out.numel() else None, stream or None))
+        return out
+
+    def _sum_rows(self, what, files, starts, gains, item_offsets, channels, rate_divisor, mix, resample, band_gains, band_edges_hz,
+                  speed_factors, speed_index, ir_index):
+        """the row arguments of decode_window_sum and stft_window, checked in the one order -> (rate_divisor, mix, resample,
+        channels, bands, speeds, irs, offsets int64 [n + 1], files, starts, gains flat and contiguous); ValueError as
+        decode_window_sum documents"""
         rate_divisor = check_rate_divisor(rate_divisor, what)
         mix = check_mix(mix, channels, what)
         resample_arg, resample = resample, check_resample(resample, what)
@@ -915,24 +1063,98 @@ class PacStore:
         bad = np.flatnonzero(~np.isfinite(gains))
         if bad.size:
             raise ValueError("%s: gains must be finite, got %r at term %d" % (what, float(gains[bad[0]]), int(bad[0])))
-        n, window = offsets.size - 1, int(window)
-        fmt, channels, out, stream = self._window_out(what, n, files, window, channels, dtype, out, stream)
-        if irs is not None:
-            self._reverb(rate_divisor, mix, resample, speeds, bands, irs, n, offsets, files, starts, gains, window, channels, fmt, out,
-                         stream)
-            return out
-        if speeds is not None:
-            self._speeds(rate_divisor, mix, speeds, bands, n, offsets, files, starts, gains, window, channels, fmt, out, stream)
-            return out
-        if bands is not None:
-            self._shaped(rate_divisor, mix, resample, bands, n, offsets, files, starts, gains, window, channels, fmt, out, stream)
-            return out
-        up, down, zeros, rolloff = resample if resample is not None else (1, 1, RESAMPLE_ZEROS, RESAMPLE_ROLLOFF)
+        return rate_divisor, mix, resample, channels, bands, speeds, irs, offsets, files, starts, gains
+
+    def stft_window(self, files, starts, n_frames, hop, n_fft, frame_window=None, bank=None, output="power", center=False,
+                    gains=None, item_offsets=None, channels=None, dtype=None, out=None, stream=None, rate_divisor=1, mix=None,
+                    resample=None, band_gains=None, band_edges_hz=None, speed_factors=None, speed_index=None, ir_index=None):
+        """mrc_pac_store_stft_window -> a torch tensor [n][channels][n_fft // 2 + 1 | filters][n_frames] on the handle's device:
+        the short-time Fourier transform of the rows decode_window_sum gives on the same row arguments, without the rows ever
+        being written out.  Row i is that call's float64 row over (n_frames - 1) hop + n_fft samples from its terms' starts;
+        frame m is samples [m hop, m hop + n_fft) of it times frame_window (float64 [n_fft]; None: hann_window(n_fft), which
+        is torch.hann_window(n_fft); padded_window centres a shorter one as torch.stft(win_length=) does), transformed in
+        float64: X[k] = sum_n g[n] x[m hop + n] e^{-2 pi i k n / n_fft}.
+        output: "power" (|X|^2, given X every bit defined), "complex" (a complex tensor, torch.view_as_complex of (re, im)), or
+        "bank": bank [filters][n_fft // 2 + 1] times the power, each filter a left fold over its support in ascending bin
+        (mel_bin_weights builds torchaudio's matrix; any matrix of 1 to MAX_BANDS rows is taken as it is).
+        n_fft: even, 16..MAX_STFT_POINTS, factors 2, 3 and 5 only.  hop >= 1.  There is no padding: starts is sample 0 of frame
+        0.  center=True subtracts n_fft // 2 from every term's start and does nothing else -- frame m is then centred on sample
+        m hop of the row and reads REAL signal around the crop (zeros outside the file), where torch.stft(center=True) reflects
+        the crop at its own ends.
+        gains=None: one term per item at gain 1.0 (files and starts 1-D); else files, starts, gains and item_offsets as
+        decode_window_sum's.  channels, stream, rate_divisor, mix, resample, band_gains, band_edges_hz, speed_factors,
+        speed_index, ir_index: decode_window_sum's, unchanged.  dtype: torch.float32 (the default) or torch.float64 (complex64
+        or complex128 for output="complex"); out: a contiguous tensor of the result's shape and dtype.  Argument errors are
+        ValueErrors before any library call."""
+        import torch
+        what = "stft_window"
+        n_fft, hop, n_frames, window, matrix, mode = check_stft(n_fft, hop, n_frames, frame_window, bank, output, what)
+        if gains is None:
+            files = np.asarray(files, dtype=np.int64).reshape(-1)
+            starts = np.asarray(starts, dtype=np.int64).reshape(-1)
+            if files.shape != starts.shape:
+                raise ValueError("%s: one start per file index (%d files, %d starts)" % (what, files.size, starts.size))
+            if item_offsets is not None:
+                raise ValueError("%s: item_offsets goes with gains" % what)
+            gains, item_offsets = np.ones(files.size, np.float64), np.arange(files.size + 1, dtype=np.int64)
+        rate_divisor, mix, resample, channels, bands, speeds, irs, offsets, files, starts, gains = self._sum_rows(
+            what, files, starts, gains, item_offsets, channels, rate_divisor, mix, resample, band_gains, band_edges_hz, speed_factors,
+            speed_index, ir_index)
+        if not isinstance(center, (bool, np.bool_)):
+            raise ValueError("%s: center must be True or False, got %r" % (what, center))
+        if center:
+            starts = starts - n_fft // 2
+        n = offsets.size - 1
+        is_complex = mode == _lib.MRC_STFT_COMPLEX
+        real = {torch.float32: torch.float32, torch.float64: torch.float64, torch.complex64: torch.float32,
+                torch.complex128: torch.float64}
+        if dtype is None:
+            dtype = out.dtype if isinstance(out, torch.Tensor) else torch.float32
+        if dtype not in real or (dtype.is_complex and not is_complex):
+            raise ValueError("%s: dtype must be torch.float32 or torch.float64%s, got %s"
+                             % (what, " (or complex64 / complex128)" if is_complex else "", dtype))
+        real_dtype = real[dtype]
+        result_dtype = {torch.float32: torch.complex64, torch.float64: torch.complex128}[real_dtype] if is_complex else real_dtype
+        if channels is None:
+            inside = files[(files >= 0) & (files < len(self))]
+            channels = int(self.n_channels[inside].max()) if inside.size else 1
+        if not _is_int(channels) or int(channels) not in (1, 2):
+            raise ValueError("%s: channels must be None, 1 or 2, got %r" % (what, channels))
+        channels = int(channels)
+        rows = matrix.shape[0] if matrix is not None else n_fft // 2 + 1
+        dev = torch.device("cuda", self._handle.cfg.device_id)
+        shape = (n, channels, rows, n_frames)
+        if out is None:
+            out = torch.empty(shape, dtype=result_dtype, device=dev)
+        elif not isinstance(out, torch.Tensor) or out.dtype != result_dtype or tuple(out.shape) != shape or out.device != dev \
+                or not out.is_contiguous():
+            raise ValueError("%s: out must be a contiguous %s tensor of shape %s on %s" % (what, result_dtype, shape, dev))
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+        if speeds is None:
+            up, down, zeros, rolloff = resample if resample is not None else (1, 1, RESAMPLE_ZEROS, RESAMPLE_ROLLOFF)
+            speeds = ([(up, down)], zeros, rolloff, np.zeros(files.size, np.int32))
+        ratios, zeros, rolloff, index = speeds
+        if irs is None:
+            irs = np.full(files.size, -1, np.int32)
+        ups = np.ascontiguousarray([r[0] for r in ratios], dtype=np.int32)
+        downs = np.ascontiguousarray([r[1] for r in ratios], dtype=np.int32)
         pad = lambda a: a.ctypes.data if a.size else None
-        self._handle._check(lib.mrc_pac_store_decode_window_sum(
-            self._s, rate_divisor, _lib.MRC_MIX_EACH if mix is None else mix, up, down, zeros, rolloff, n, offsets.ctypes.data,
-            pad(files), pad(starts), pad(gains), window, channels, fmt, out.data_ptr() if out.numel() else None, stream or None))
+        edges, band_rows = bands if bands is not None else (None, None)
+        self._handle._check(lib.mrc_pac_store_stft_window(
+            self._s, rate_divisor, _lib.MRC_MIX_EACH if mix is None else mix, len(ratios), ups.ctypes.data, downs.ctypes.data, zeros,
+            rolloff, 0 if bands is None else edges.size - 1, None if bands is None else edges.ctypes.data,
+            None if bands is None else pad(band_rows), n, offsets.ctypes.data, pad(files), pad(starts), pad(gains), pad(index), pad(irs),
+            n_fft, window.ctypes.data, n_frames, hop, mode, 0 if matrix is None else matrix.shape[0],
+            None if matrix is None else matrix.ctypes.data, channels, _formats()[real_dtype], out.data_ptr() if out.numel() else None,
+            stream or None))
         return out
+
+    def stft_ms(self):
+        """mrc_pac_store_stft_ms: the device time of the last stft_window's stft_kernel, summed over its slabs"""
+        ms = np.zeros(1, np.float64)
+        self._handle._check(lib.mrc_pac_store_stft_ms(self._s, ms.ctypes.data))
+        return float(ms[0])
 
     def _energy_window(self, what, table, launch, files, starts, n_frames, hop, channels, dtype, out, stream, mix):
         """band_energy_window and filterbank_window: the checks in the one order, the output tensor, the call.  table() checks
