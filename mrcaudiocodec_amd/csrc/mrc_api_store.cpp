@@ -4,7 +4,23 @@
 // create: pac_plan_scan -- the host plan of mrc_decode_pac_pcm16, one scan in the tree -- gives every file's chunks, block
 // shapes and positions; the bytes go to the device in one copy and never cross PCIe again.
 //
-// decode_window, per slab of whole items:
+// The window calls (decode_window and its eight kin, stft_window) are one path:
+//   request   every extern "C" entry fills a WindowRequest -- what the widest entry takes, the caller's arrays as they came --
+//             and does nothing else.
+//   check     check_windows turns it into a CheckedWindows once per public call: the internal mix, the one filter or the list
+//             of them, the line-to-band tables, the term count, the longest pre-roll.  Every refusal of every entry is there,
+//             in the order the entry gives them; no loop checks an argument again.
+//   loops     units_loop decodes units (items or terms) into rows; reverb_loop has it decode a slab's terms dry and convolves
+//             and folds them; stft_loop has reverb_loop make a slab's rows and transforms them.  Each takes the checked
+//             request and a WindowRun: a row range, the window, format and output of that range, and the slab limit -- 0 when
+//             the caller has cut the slab itself.  An outer loop hands the inner one a range; the arrays are indexed by the
+//             call's own row and term numbers throughout and no temporary ones are built.
+//   totals    the store's stats, ms, reverbMs and stftMs are the accumulator: the entry zeroes them, the slabs add to them.
+// block_energy, band_energy_window and filterbank_window are families of their own over the same slab plan (stage_slab,
+// parse_slab); the mix check, the file check, the elapsed-time sums and the copy of the energy entries have one definition
+// for all three families.
+//
+// units_loop, per slab of whole rows (an item call's row is its one unit):
 //   needed blocks   block i of the item's file iff p_i < start + window + L and p_i + a_i + b_i > start + L (p_i its position
 //                   in the padded plane, L = n_mdct_lines): positions increase, so the end is a binary search, and as
 //                   a + b <= 2 L so is a point before which no block can reach the window; the few blocks behind it are
@@ -27,8 +43,8 @@
 // L / D, p_i / D, (a_i + b_i) / D, planes of window + 4 L / D, start and window in reduced samples -- exact, because every
 // block length and position is a multiple of n_short and D divides n_short (else the shapes have no reduced form and the
 // call is refused).  The parser is untouched (a chunk's bits are sequential: every mantissa is parsed); decode_reduced_kernel
-// dequantises the first 1 / D of a block's lines and runs the inverse transform of the shape (a, b) / D.  One function,
-// decode_windows, holds the arithmetic for every D.
+// dequantises the first 1 / D of a block's lines and runs the inverse transform of the shape (a, b) / D.  The one loop holds
+// the arithmetic for every D.
 //
 // decode_window_mix, one channel of every item (left, right or the mid (L + R) / 2): the same plan with ONE plane per item
 // and one workgroup per needed block (decode_mix_kernel, its selector an argument).  A joint block keeps its slot of two
@@ -37,33 +53,37 @@
 // of the non-joint group, which laid side by side are one slot of two streams, the group's pairs in front of its single
 // slots so that a workgroup finds its slot from its index alone.  pac_plan_layout sees slot counts as ever.
 //
-// decode_window_resampled, the windows at up / down of the rate 1 / D: decode_windows with two coordinate systems.  start and
+// decode_window_resampled, the windows at up / down of the rate 1 / D: the units loop with two coordinate systems.  start and
 // window count output samples; what is planned, staged, parsed and synthesised is each item's span of INTERMEDIATE samples
 // (everything the filter reads for the item's outputs), and resample_out_kernel folds the planes into the caller's tensor
 // where window_out_kernel copies them.  The filter (mrc_resample_taps.hpp: host only) goes up once per handle and
 // (up, down, zeros, rolloff).
 //
-// decode_window_sum, rows that are weighted sums of windows: decode_windows with the TERM as its planning unit.  Each term is
+// decode_window_sum, rows that are weighted sums of windows: the units loop with the TERM as its planning unit.  Each term is
 // planned, staged, parsed and synthesised as an item of the calls above, into planes of its own; a slab is a run of whole
 // rows counted by its terms' spans, and sum_out_kernel / resample_sum_out_kernel fold a row's terms with their gains, in the
 // order given, into the caller's tensor.  The term records (WindowItem, gain, output start) and the rows' term offsets go up
 // with the plan.  No per-term window is written.
 //
-// decode_window_shaped, those rows with a band gain on every decoded MDCT line: decode_windows with a shaping spec beside the
+// decode_window_shaped, those rows with a band gain on every decoded MDCT line: the units loop with a shaping spec beside the
 // filter and the rows.  Per call one uint16 line-to-band table per block shape (band_line_ranges over the FULL shape, at every
 // D); per slab, in the same staging copy as the plan, those tables, the slab's rows of gains and one unit index per slot or
 // workgroup laid out as the block offsets are; the shaped launches (mrc_kernels_decode.hip) multiply once per line between
 // the dequantiser and the inverse transform.  Calls without gains never come here.
 //
-// decode_window_speeds, those rows with a ratio per term: decode_windows with a list of filters beside the rows.  Each term's
+// decode_window_speeds, those rows with a ratio per term: the units loop with a list of filters beside the rows.  Each term's
 // span is its own ratio's; the planes have one length per call, the largest span among the ratios named plus 4 L, so the
 // synthesis launches and their second plane at x + planeLen stay as they are.  The terms' ratio indices and the table of
 // the ratios (SpeedRatio) ride in the slab's staging copy; SumTerm and WindowItem are the other calls', unchanged.
 //
-// decode_window_reverb, those rows with a room impulse response per term: NOT another spec of decode_windows but a slab loop
-// around the rows call, which decodes every term of a slab over its span lengthened by the pre-roll into a float64 scratch
-// buffer; reverb_forward_kernel and reverb_fold_kernel (mrc_kernels_reverb.hip: partitioned overlap-save) then make the rows.
-// The bank's partition spectra live in the store (set_irs), made once by the same forward kernel.
+// decode_window_reverb, those rows with a room impulse response per term: NOT another spec of the units loop but a loop of
+// its own (reverb_loop), which has the units loop decode every term of a slab, as a row of its own, over its span lengthened
+// by the pre-roll into a float64 scratch buffer; reverb_forward_kernel and reverb_fold_kernel (mrc_kernels_reverb.hip:
+// partitioned overlap-save) then make the rows.  The bank's partition spectra live in the store (set_irs), made once by the
+// same forward kernel.
+//
+// stft_window, the short-time Fourier transform of those rows: stft_loop has reverb_loop write a slab's rows as float64 into
+// a second scratch buffer and stft_kernel (mrc_kernels_stft.hip) frames and transforms them.
 //
 // block_energy, ((a + b) / D) * the sum of squares of a block's first 1 / D decoded lines, per channel or for the mid, for
 // every block of the selected files: the same slab plan (stage_slab, parse_slab) over runs of whole blocks instead of the
@@ -100,7 +120,7 @@ const char* const kWinResampled = "mrc_pac_store_decode_window_resampled";
 const char* const kWinSum = "mrc_pac_store_decode_window_sum";
 const char* const kWinShaped = "mrc_pac_store_decode_window_shaped";
 const char* const kWinSpeeds = "mrc_pac_store_decode_window_speeds";
-constexpr int kNoMix = -1;                           // decode_windows: every channel of a file into a plane of its own
+constexpr int kNoMix = -1;                           // the internal mix: every channel of a file into a plane of its own
 
 int store_alive(mrc_pac_store* s, const char* fn) {
     if (!s) return fail(nullptr, MRC_ERR_INVALID, std::string(fn) + ": null store");
@@ -108,7 +128,7 @@ int store_alive(mrc_pac_store* s, const char* fn) {
     return MRC_OK;
 }
 
-struct Need { int64_t item, file, block; };          // item: index in the slab
+using Need = StoreNeed;                              // (item: index in the slab)
 
 // the blocks of file f that a window of `window` samples at `start` overlaps, appended to out as (item, f, block); start
 // and window count samples at 1 / D of the file's rate, where block i covers [p_i / D, (p_i + a_i + b_i) / D)
@@ -141,8 +161,54 @@ int check_divisor(mrc_handle* h, const std::string& w, int D) {
     return MRC_OK;
 }
 
-// The host side of one slab's parse, shared by decode_windows and block_energy: `needs`, the slab's blocks, become slots of
-// the (shape, kind) groups and plan entries that point into the resident bytes.
+// mix of every call that takes one: a member of `allowed`, a set of bits 1 << MRC_MIX_*; the refusal names the set
+constexpr unsigned kMixEachOrMid = 1u << MRC_MIX_EACH | 1u << MRC_MIX_MID, kMixOfOne = 1u << MRC_MIX_MID | 1u << MRC_MIX_LEFT | 1u << MRC_MIX_RIGHT,
+                   kMixAny = kMixOfOne | 1u << MRC_MIX_EACH;
+int check_mix(mrc_handle* h, const std::string& w, int mix, unsigned allowed) {
+    if (mix >= 0 && mix < 4 && (allowed >> mix & 1)) return MRC_OK;
+    const struct { int v; const char* name; } all[4] = {{MRC_MIX_EACH, "MRC_MIX_EACH (3)"}, {MRC_MIX_MID, "MRC_MIX_MID (0)"},
+                                                       {MRC_MIX_LEFT, "MRC_MIX_LEFT (1)"}, {MRC_MIX_RIGHT, "MRC_MIX_RIGHT (2)"}};
+    std::string names;
+    for (int i = 0, left = __builtin_popcount(allowed); i < 4; ++i)
+        if (allowed >> all[i].v & 1) names += std::string(all[i].name) + (--left > 1 ? ", " : left == 1 ? " or " : "");
+    return fail(h, MRC_ERR_INVALID, w + ": mix " + std::to_string(mix) + " is not " + names);
+}
+
+// file[k] (null: k itself) of every k < n is a file of the store, and -- maxChannels 1 or 2; 0: not looked at -- has no more
+// channels than that; `unit` is what k counts in the second refusal ("item", "term")
+int check_files(mrc_pac_store* s, const std::string& w, int64_t n, const int64_t* file, int maxChannels, const char* unit) {
+    const int64_t nFiles = (int64_t)s->index.files.size();
+    for (int64_t k = 0; k < n; ++k) {
+        const int64_t f = file ? file[k] : k;
+        if (f < 0 || f >= nFiles)
+            return fail(s->h, MRC_ERR_INVALID, w + ": file[" + std::to_string(k) + "] = " + std::to_string(f) + " is outside the store's " +
+                                                   std::to_string(nFiles) + " files");
+        if (maxChannels && s->index.files[(size_t)f].nch > maxChannels)
+            return fail(s->h, MRC_ERR_INVALID, w + ": " + unit + " " + std::to_string(k) + ": file " + std::to_string(f) +
+                                                   " is stereo, the call asks for one channel");
+    }
+    return MRC_OK;
+}
+
+// The statistics of a call are kept in the store itself: the entry point zeroes them, every slab of every loop adds to them
+// (stage_slab its chunks and bytes), and nothing is saved, summed or restored on the way.
+void reset_stats(mrc_pac_store* s) {
+    for (int i = 0; i < 4; ++i) { s->stats[i] = 0; s->ms[i] = 0.0; }
+}
+// ms[i] += the time between events pair[i][0] and pair[i][1] of a slab that has been synchronised
+constexpr int kSlabSpans[4][2] = {{0, 1}, {1, 2}, {3, 4}, {4, 5}};      // StoreBufs::ev: upload | unpack | synthesis | output
+template <class Events>
+int add_elapsed(mrc_handle* h, const Events& ev, const int (*pair)[2], int n, double* ms) {
+    for (int i = 0; i < n; ++i) {
+        double t = 0.0;
+        MRC_HIP(h, ev.elapsed(pair[i][0], pair[i][1], &t));
+        ms[i] += t;
+    }
+    return MRC_OK;
+}
+
+// The host side of one slab's parse, shared by units_loop, block_energy and energy_frames_window: `needs`, the slab's blocks,
+// become slots of the (shape, kind) groups and plan entries that point into the resident bytes.
 //   slots    a joint block is one slot of two streams.  Any other block is one slot per chunk parsed: all of the file's, or
 //            under MRC_MIX_LEFT / _RIGHT the one asked for.  Under MRC_MIX_MID the two chunks of a stereo file's last block
 //            are a PAIR of neighbouring slots, the group's pairs in front of its single slots (nPairs per group).
@@ -337,84 +403,114 @@ int get_resample_tables(mrc_handle* h, int n, const ResampleSpec* r, const Resam
     return MRC_OK;
 }
 
-// all decode_window calls: fn the entry point's name, D the rate divisor (1: full rate, decode_kernel), mixArg null or the
-// caller's MRC_MIX_* (one plane per item, decode_mix_kernel; n_channels_out is then 1).
-// rs (mrc_pac_store_decode_window_resampled) null or the filter: start and window then count OUTPUT samples, at up / down of
-// the rate 1 / D.  Item k reads the intermediate samples [lo, hi], lo = floor(start down / up) - W + 1, hi =
-// floor((start + window - 1) down / up) + W: that span is what is planned, staged, parsed and synthesised exactly as a
-// window of the other calls -- into planes of span + 4 L samples, span = ceil((window - 1) down / up) + 2 W the one bound on
-// hi - lo + 1 -- and resample_out_kernel stands where window_out_kernel stands.  A slab counts plane samples (spans).
-// sum (mrc_pac_store_decode_window_sum) null or the rows of that call: what is planned, staged, parsed and synthesised -- the
-// UNIT, (file[k], start[k]) -- is then a TERM of row i, k in [termOffset[i], termOffset[i + 1]), n_items the number of terms;
-// a slab is a run of whole rows, counted by its terms' spans, and sum_out_kernel / resample_sum_out_kernel fold a row's
-// terms with their gains where the other calls copy or fold one unit per row.  Without it a row is its one unit.
-// speeds (mrc_pac_store_decode_window_speeds; with sum, without rs) null or the ratios of that call: term k is planned over the
-// span of ITS ratio -- the unit ratio's is [start, start + window), any other's the intermediate span above with that ratio's
-// up, down and W -- into planes of ONE length, the largest span bound among the ratios the call's terms name plus 4 L, which a
-// slab counts each term at.  Per slab, in the one staging copy: the ratio index of every term and the table of the ratios
-// (SpeedRatio); resample_multi_sum_out_kernel folds.
-// shape (mrc_pac_store_decode_window_shaped) null or the band gains of that call, one row per unit: each needed block is then
-// synthesised by the shaped launches, its line k multiplied once by the unit's gain of the band that
-// band_line_ranges(sample rate, the block's FULL shape) puts it in, whatever D.  Per call: lineBand, a uint16 per line of each
-// block shape (kNoLineBand: in no band).  Per slab, in the one staging copy: those tables, the slab's rows of gains, and one
-// unit index per slot or workgroup laid out as the block offsets are.
-struct SumSpec {
-    int64_t nRows;
-    const int64_t* termOffset;                               // [nRows + 1], checked by the caller
-    const double* gain;                                      // [n_items]
+// ---- the window calls: one request, checked once, run by three loops over row ranges (see the head of the file)
+// What the widest entry takes, without the STFT's own arguments.  Every extern "C" window entry fills one and nothing else.
+struct WindowRequest {
+    enum Kind { kItems, kRows, kReverb, kStft };             // which checks are made and in what order (check_windows)
+    const char* fn;                                          // the entry point's name, in front of every refusal
+    Kind kind;
+    int rateDivisor = 1;
+    int mix = MRC_MIX_EACH;                                  // the caller's MRC_MIX_*, one of mixAllowed
+    unsigned mixAllowed = kMixAny;
+    // the ratio: none, one (up, down) -- an item call's must differ from 1, a rows call's may be 1 -- or a list with ratioOf
+    bool resampled = false;
+    int up = 1, down = 1;
+    bool ratioList = false;
+    int nRatios = 0;
+    const int32_t *ratioUp = nullptr, *ratioDown = nullptr, *ratioOf = nullptr;
+    int zeros = 0;
+    double rolloff = 0.0;
+    bool banded = false;                                     // band gains on the MDCT lines (with a ratio list: n_bands != 0)
+    int nBands = 0;
+    const double *edgeHz = nullptr, *bandGain = nullptr;
+    int64_t nItems = 0;                                      // rows; an item call's rows are its units
+    const int64_t *termOffset = nullptr, *file = nullptr, *start = nullptr;
+    const double* gain = nullptr;
+    const int32_t* irOf = nullptr;
+    int nChannelsOut = 1;
+    void* stream = nullptr;
+    bool rows() const { return kind != kItems; }
 };
 struct SpeedSpec {
     int nRatios;
     ResampleSpec r[MRC_MAX_STORE_RATIOS];                    // reduced; W == 0: the unit ratio, no filter
-    const int32_t* ratioOf;                                  // [n_items], checked by the caller
 };
 struct ShapeSpec {
-    int nBands;
-    const double* bandGain;                                  // [n_items][nBands], checked by the caller
     std::vector<uint16_t> lineBand;                          // the band of every line of the four block shapes, shape after shape
     int64_t lineOff[4];                                      // ... shape sh from lineOff[sh] on, (a + b) / 2 values
 };
-int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, int64_t n_items, const int64_t* file, const int64_t* start,
-                   int64_t window, int n_channels_out, int format, void* out, void* stream, const ResampleSpec* rs = nullptr,
-                   const SumSpec* sum = nullptr, const ShapeSpec* shape = nullptr, const SpeedSpec* speeds = nullptr) {
-    MRC_TRY(store_alive(s, fn));
+// What check_windows makes of a request, once per public call: the arrays stay the request's, indexed by the call's own
+// row and term numbers in every loop -- no loop re-bases them.
+struct CheckedWindows {
+    WindowRequest q;
+    int mix = kNoMix;                                        // kNoMix or MRC_MIX_MID / _LEFT / _RIGHT
+    int64_t nTerms = 0;                                      // the units: terms of a rows call, items of an item call
+    bool filtered = false, speedy = false, shaped = false;   // which of the three specs below is in use
+    ResampleSpec rs;                                         // one ratio other than 1 for every unit
+    SpeedSpec speeds;                                        // a ratio per term (only where there are terms)
+    ShapeSpec shape;
+    int64_t maxPreRoll = 0;                                  // the longest response named by any term - 1
+    bool empty = false;                                      // no row or no sample: nothing to launch
+};
+// What a loop is asked to run: rows [first, last) of the checked request into `out`, which is row first's.
+struct WindowRun {
+    int64_t first, last;
+    int64_t window;
+    int format;
+    void* out;
+    int64_t slab;                                            // the slab limit in samples; 0: the range is one slab (a caller cut it)
+    int64_t preRoll = 0;                                     // units_loop: every start moved down by it, saturating at INT64_MIN
+    bool termRows = false;                                   // units_loop: first and last count TERMS, each a row of its own at gain 1.0
+};
+
+// The units loop: D the rate divisor (1: full rate, decode_kernel), c.mix kNoMix or one channel of every unit (one plane per
+// unit, decode_mix_kernel; n_channels_out is then 1).  What is planned, staged, parsed and synthesised is the UNIT,
+// (file[k], start[k]): an item, or with rows a TERM of row i, k in [termOffset[i], termOffset[i + 1]).  A slab is a run of
+// whole rows, counted by its units' spans; sum_out_kernel / resample_sum_out_kernel fold a row's terms with their gains
+// where the item calls copy or fold one unit per row.
+// c.filtered (one ratio): start and window count OUTPUT samples, at up / down of the rate 1 / D.  Unit k reads the
+// intermediate samples [lo, hi], lo = floor(start down / up) - W + 1, hi = floor((start + window - 1) down / up) + W: that
+// span is what is planned, staged, parsed and synthesised exactly as a window of the other calls -- into planes of span + 4 L
+// samples, span = ceil((window - 1) down / up) + 2 W the one bound on hi - lo + 1 -- and resample_out_kernel stands where
+// window_out_kernel stands.  A slab counts plane samples (spans).
+// c.speedy (a ratio per term): term k is planned over the span of ITS ratio -- the unit ratio's is [start, start + window) --
+// into planes of ONE length, the largest span bound among the ratios the range's terms name plus 4 L, which a slab counts
+// each term at.  Per slab, in the one staging copy: the ratio index of every term and the table of the ratios (SpeedRatio);
+// resample_multi_sum_out_kernel folds.
+// c.shaped (band gains, one row per unit): each needed block is synthesised by the shaped launches, its line k multiplied
+// once by the unit's gain of the band that band_line_ranges(sample rate, the block's FULL shape) puts it in, whatever D.  Per
+// slab, in the one staging copy: the line-to-band tables, the slab's rows of gains, and one unit index per slot or workgroup
+// laid out as the block offsets are.
+// run.termRows and run.preRoll are the reverb loop's: the terms [first, last) as rows of one term each at gain 1.0, read
+// from start - preRoll.  They go through the sum kernels with SumTerm records like any row: 0.0 + 1.0 * v is v, and a -0.0
+// becomes +0.0, which no fold from +0.0 can tell apart.
+int units_loop(mrc_pac_store* s, const CheckedWindows& c, const WindowRun& run) {
+    const WindowRequest& q = c.q;
     mrc_handle* h = s->h;
     const mrc_config& cfg = h->cfg;
-    const std::string w = fn;
-    for (int i = 0; i < 4; ++i) { s->stats[i] = 0; s->ms[i] = 0.0; }
-    const int mix = mixArg ? *mixArg : kNoMix;
-    if (mixArg && mix != MRC_MIX_MID && mix != MRC_MIX_LEFT && mix != MRC_MIX_RIGHT)
-        return fail(h, MRC_ERR_INVALID, w + ": mix " + std::to_string(mix) + " is not MRC_MIX_MID (0), MRC_MIX_LEFT (1) or MRC_MIX_RIGHT (2)");
-    MRC_TRY(check_divisor(h, w, D));
-    const int64_t nFiles = (int64_t)s->index.files.size(), L = cfg.n_mdct_lines / D;      // L: the margin unit, reduced samples
-    if (n_items < 0) return fail(h, MRC_ERR_INVALID, w + ": n_items < 0");
-    if (window < 0 || window > ((int64_t)1 << 40)) return fail(h, MRC_ERR_INVALID, w + ": window must lie in [0, 2^40]");
-    if (n_channels_out != 1 && n_channels_out != 2) return fail(h, MRC_ERR_INVALID, w + ": n_channels_out must be 1 or 2");
-    if (format != MRC_WINDOW_PCM16 && format != MRC_WINDOW_F32 && format != MRC_WINDOW_F64)
-        return fail(h, MRC_ERR_INVALID, w + ": unknown format " + std::to_string(format));
-    if (n_items > 0 && (!file || !start)) return fail(h, MRC_ERR_INVALID, w + ": file or start is NULL");
-    const int64_t nRows = sum ? sum->nRows : n_items;
-    if (nRows > 0 && window > 0 && !out) return fail(h, MRC_ERR_INVALID, w + ": out is NULL");
-    for (int64_t k = 0; k < n_items; ++k) {
-        if (file[k] < 0 || file[k] >= nFiles)
-            return fail(h, MRC_ERR_INVALID, w + ": file[" + std::to_string(k) + "] = " + std::to_string(file[k]) + " is outside the store's " +
-                                                std::to_string(nFiles) + " files");
-        if (mix == kNoMix && s->index.files[(size_t)file[k]].nch > n_channels_out)
-            return fail(h, MRC_ERR_INVALID, w + (sum ? ": term " : ": item ") + std::to_string(k) + ": file " + std::to_string(file[k]) +
-                                                " is stereo, the call asks for one channel");
-    }
-    if (nRows == 0 || window == 0) return MRC_OK;
+    const char* const fn = q.fn;
+    const int D = q.rateDivisor, mix = c.mix, n_channels_out = q.nChannelsOut, format = run.format;
+    const int64_t* const file = q.file;
+    const int64_t window = run.window, L = cfg.n_mdct_lines / D;             // L: the margin unit, reduced samples
+    const bool sum = q.rows();
+    const ResampleSpec* const rs = c.filtered ? &c.rs : nullptr;
+    const SpeedSpec* const speeds = c.speedy ? &c.speeds : nullptr;
+    const ShapeSpec* const shape = c.shaped ? &c.shape : nullptr;
+    const int64_t* const rowTerms = sum && !run.termRows ? q.termOffset : nullptr;
+    const auto unitsBefore = [rowTerms](int64_t row) { return rowTerms ? rowTerms[row] : row; };
+    // (a start that far down is below every file with or without the pre-roll)
+    const auto startOf = [&](int64_t k) { return q.start[k] < INT64_MIN + run.preRoll ? INT64_MIN : q.start[k] - run.preRoll; };
 
     MRC_TRY(ensure_decode_consts(h));
     StoreBufs& b = h->store;
     MRC_HIP(h, b.ev.create());
-    hipStream_t st = pick_stream(h, stream);
+    hipStream_t st = pick_stream(h, q.stream);
     DrainGuard drain{{st, nullptr, nullptr}};
     const size_t elem = format == MRC_WINDOW_PCM16 ? 2 : format == MRC_WINDOW_F32 ? 4 : 8;
     const ResampleTable* table = nullptr;
     if (rs) MRC_TRY(get_resample_table(h, *rs, &table));
     const int64_t up = rs ? rs->up : 1, down = rs ? rs->down : 1, W = rs ? rs->W : 0;
-    int64_t span = rs ? ((window - 1) * down + up - 1) / up + 2 * W : window;           // plane samples an item takes at most
+    int64_t span = rs ? ((window - 1) * down + up - 1) / up + 2 * W : window;           // plane samples a unit takes at most
     const ResampleTable* tables[MRC_MAX_STORE_RATIOS] = {};
     SpeedRatio ratios[MRC_MAX_STORE_RATIOS] = {};
     if (speeds) {                                            // every filter first, then the largest span among the ratios named
@@ -424,24 +520,23 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
             ratios[i] = SpeedRatio{r.up, r.down, r.W, r.W ? tables[i]->skewNatural : 0, r.W ? (const double*)tables[i]->taps.p : nullptr};
         }
         span = 0;
-        for (int64_t k = 0; k < n_items; ++k) {
-            const ResampleSpec& r = speeds->r[speeds->ratioOf[k]];
+        for (int64_t k = unitsBefore(run.first); k < unitsBefore(run.last); ++k) {
+            const ResampleSpec& r = speeds->r[q.ratioOf[k]];
             span = std::max<int64_t>(span, r.W ? ((window - 1) * r.down + r.up - 1) / r.up + 2 * r.W : window);
         }
     }
     const int64_t far = (int64_t)1 << 52;                    // an output start beyond it is beyond every file: (start + window) * down fits
     const int64_t planeLen = span + 4 * L, tiles = (window + 255) / 256;
-    const int64_t slab = h->storeSlabSamples, itemCap = std::max<int64_t>(1, 0x7fffffffLL / (tiles * n_channels_out));
+    const int64_t slab = run.slab, itemCap = std::max<int64_t>(1, 0x7fffffffLL / (tiles * n_channels_out));
 
-    std::vector<Need> needs;
-    std::vector<WindowItem> items;
+    std::vector<Need>& needs = b.needs;                      // (the planner's scratch: StoreBufs)
+    std::vector<WindowItem>& items = b.items;
     PacPlan pl;                                              // (its group fields: the slab's slots)
-    const auto unitsBefore = [sum](int64_t row) { return sum ? sum->termOffset[row] : row; };
-    for (int64_t first = 0, last; first < nRows; first = last) {  // rows [first, last), their units [u0, u0 + nSlab)
+    for (int64_t first = run.first, last; first < run.last; first = last) {  // rows [first, last), their units [u0, u0 + nSlab)
         last = first + 1;
-        while (last < nRows && last - first < itemCap && (slab == 0 || (unitsBefore(last + 1) - unitsBefore(first)) * span <= slab)) ++last;
+        while (last < run.last && last - first < itemCap && (slab == 0 || (unitsBefore(last + 1) - unitsBefore(first)) * span <= slab)) ++last;
         const int64_t nSlabRows = last - first, u0 = unitsBefore(first), nSlab = unitsBefore(last) - u0;
-        unsigned char* outSlab = (unsigned char*)out + (size_t)first * n_channels_out * window * elem;
+        unsigned char* outSlab = (unsigned char*)run.out + (size_t)(first - run.first) * n_channels_out * window * elem;
         s->stats[2] += 1;
 
         // ---- the slab's needed blocks, its items and planes
@@ -451,16 +546,17 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
         for (int64_t k = 0; k < nSlab; ++k) {
             const int64_t f = file[u0 + k];
             const size_t before = needs.size();
-            int64_t at = start[u0 + k], len = window;        // the samples the planes must hold: [at, at + len)
+            const int64_t outStart = startOf(u0 + k);
+            int64_t at = outStart, len = window;             // the samples the planes must hold: [at, at + len)
             if (rs) {
                 if (at > far || at < -far) continue;
                 at = floor_div(at * down, up) - W + 1;
-                len = floor_div((start[u0 + k] + window - 1) * down, up) + W - at + 1;
-            } else if (speeds && speeds->r[speeds->ratioOf[u0 + k]].W) {
-                const ResampleSpec& r = speeds->r[speeds->ratioOf[u0 + k]];
+                len = floor_div((outStart + window - 1) * down, up) + W - at + 1;
+            } else if (speeds && speeds->r[q.ratioOf[u0 + k]].W) {
+                const ResampleSpec& r = speeds->r[q.ratioOf[u0 + k]];
                 if (at > far || at < -far) continue;
                 at = floor_div(at * r.down, r.up) - r.W + 1;
-                len = floor_div((start[u0 + k] + window - 1) * r.down, r.up) + r.W - at + 1;
+                len = floor_div((outStart + window - 1) * r.down, r.up) + r.W - at + 1;
             }
             needed_blocks(*s, cfg, D, k, f, at, len, &needs);
             if (needs.size() == before) continue;            // all zeros: its plane does not exist
@@ -491,7 +587,7 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
                 }
                 if (shape) {
                     oLineBand = lay->add<uint16_t>((int64_t)shape->lineBand.size());
-                    oBandGain = lay->add<double>(nSlab * shape->nBands);
+                    oBandGain = lay->add<double>(nSlab * q.nBands);
                     oUnit = lay->add<int>(pl.totalSlots);    // (indexed as the offsets are: a pair's workgroup, a single slot)
                 }
                 if (speeds) {
@@ -513,22 +609,23 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
         const UnpackGroupDev* gd = S.gd;
         if (sum) {
             SumTerm* terms = (SumTerm*)(S.pin + oItems);
-            const auto resampled = [&](int64_t k) { return rs || (speeds && speeds->r[speeds->ratioOf[u0 + k]].W); };
-            for (int64_t k = 0; k < nSlab; ++k) terms[k] = SumTerm{items[(size_t)k], sum->gain[u0 + k], resampled(k) ? start[u0 + k] : 0};
-            long long* rowTerms = (long long*)(S.pin + oOutStart);
-            for (int64_t r = 0; r <= nSlabRows; ++r) rowTerms[r] = sum->termOffset[first + r] - u0;
+            const auto resampled = [&](int64_t k) { return rs || (speeds && speeds->r[q.ratioOf[u0 + k]].W); };
+            for (int64_t k = 0; k < nSlab; ++k)
+                terms[k] = SumTerm{items[(size_t)k], run.termRows ? 1.0 : q.gain[u0 + k], resampled(k) ? startOf(u0 + k) : 0};
+            long long* slabTerms = (long long*)(S.pin + oOutStart);
+            for (int64_t r = 0; r <= nSlabRows; ++r) slabTerms[r] = unitsBefore(first + r) - u0;
         } else {
             std::memcpy(S.pin + oItems, items.data(), sizeof(WindowItem) * nSlab);
-            if (rs) std::memcpy(S.pin + oOutStart, start + first, sizeof(long long) * nSlab);
+            if (rs) std::memcpy(S.pin + oOutStart, q.start + first, sizeof(long long) * nSlab);
         }
         if (speeds) {
             int* ratioOf = (int*)(S.pin + oRatioOf);
-            for (int64_t k = 0; k < nSlab; ++k) ratioOf[k] = speeds->ratioOf[u0 + k];
+            for (int64_t k = 0; k < nSlab; ++k) ratioOf[k] = q.ratioOf[u0 + k];
             std::memcpy(S.pin + oRatios, ratios, sizeof(SpeedRatio) * (size_t)speeds->nRatios);
         }
         if (shape) {
             std::memcpy(S.pin + oLineBand, shape->lineBand.data(), sizeof(uint16_t) * shape->lineBand.size());
-            std::memcpy(S.pin + oBandGain, shape->bandGain + u0 * shape->nBands, sizeof(double) * (size_t)(nSlab * shape->nBands));
+            std::memcpy(S.pin + oBandGain, q.bandGain + u0 * q.nBands, sizeof(double) * (size_t)(nSlab * q.nBands));
         }
         const HostShape* reduced[4] = {};
         for (int sh = 0; D > 1 && sh < 4; ++sh)
@@ -550,10 +647,10 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
                 const double* bandGain = (const double*)(din + oBandGain);
                 const int* unit = (const int*)(din + oUnit) + (o - offsDev);
                 if (mix != kNoMix)
-                    return launch_decode_shaped_mix(F, R, lineBand, bandGain, unit, shape->nBands, pl.nSlots[g] - nPairs[g], G.joint,
+                    return launch_decode_shaped_mix(F, R, lineBand, bandGain, unit, q.nBands, pl.nSlots[g] - nPairs[g], G.joint,
                                                     mix == MRC_MIX_MID ? 2 : mix == MRC_MIX_LEFT ? 0 : 1, nPairs[g], G.oscale,
                                                     G.joint ? G.ms : nullptr, G.sf, G.ba, G.mant, o, x, st);
-                return launch_decode_shaped(F, R, lineBand, bandGain, unit, shape->nBands, pl.nSlots[g], G.joint ? 2 : 1, G.oscale,
+                return launch_decode_shaped(F, R, lineBand, bandGain, unit, q.nBands, pl.nSlots[g], G.joint ? 2 : 1, G.oscale,
                                             G.joint ? G.ms : nullptr, G.sf, G.ba, G.mant, o, x, G.joint ? x + planeLen : nullptr, st);
             }));
         else if (mix == kNoMix && D == 1) MRC_TRY(decode_groups(h, pl, gd, offsDev, x, planeLen, st));
@@ -591,31 +688,50 @@ int decode_windows(mrc_pac_store* s, const char* fn, int D, const int* mixArg, i
                                          outSlab, st));
         MRC_HIP(h, hipEventRecord(b.ev[5], st));
         MRC_HIP(h, hipStreamSynchronize(st));                // (the staging is written again by the next slab)
-        const int span[4][2] = {{0, 1}, {1, 2}, {3, 4}, {4, 5}};
-        for (int i = 0; i < 4; ++i) {
-            double ms = 0.0;
-            MRC_HIP(h, b.ev.elapsed(span[i][0], span[i][1], &ms));
-            s->ms[i] += ms;
-        }
+        MRC_TRY(add_elapsed(h, b.ev, kSlabSpans, 4, s->ms));
     }
     MRC_HIP(h, hipStreamSynchronize(st));
     return MRC_OK;
 }
 
+// the per-group entries of a slab into its staging at dst, group after group; entryBase[g]: where group g's start -> their number
+int64_t copy_entries(const std::vector<EnergyEntry>* entries, unsigned char* dst, int64_t* entryBase) {
+    int64_t q = 0;
+    for (int g = 0; g < kUnpackGroups; ++g) {
+        entryBase[g] = q;
+        if (!entries[g].empty())
+            std::memcpy(dst + sizeof(EnergyEntry) * (size_t)q, entries[g].data(), sizeof(EnergyEntry) * entries[g].size());
+        q += (int64_t)entries[g].size();
+    }
+    return q;
+}
+
 // mrc_pac_store_block_energy: every block of the selected files through the slab's parse (stage_slab, parse_slab: the
-// planner of decode_windows) and block_energy_kernel, one launch per group with slots; no plane, no inverse transform.
+// planner of units_loop) and block_energy_kernel, one launch per group with slots; no plane, no inverse transform.
 // A slab is a run of whole blocks, in the order of the entries, whose b / D sum to at most MRC_OPT_STORE_SLAB_SAMPLES (one
 // block at least): its entries are consecutive, so its energies come back in one copy.
-int block_energy(mrc_pac_store* s, int D, int mixArg, int64_t n_sel, const int64_t* file, int64_t* entry_offset, int64_t entry_cap,
-                 int64_t* entry_block, double* energy, void* stream) {
+struct BlockEnergyRequest {                                  // the entry's arguments, as the header names them
+    int rate_divisor, mix;
+    int64_t n_sel;
+    const int64_t* file;
+    int64_t* entry_offset;
+    int64_t entry_cap;
+    int64_t* entry_block;
+    double* energy;
+    void* stream;
+};
+int block_energy(mrc_pac_store* s, const BlockEnergyRequest& r) {
     const char* const fn = "mrc_pac_store_block_energy";
+    const int D = r.rate_divisor, mixArg = r.mix;
+    const int64_t n_sel = r.n_sel, entry_cap = r.entry_cap, *const file = r.file;
+    int64_t *const entry_offset = r.entry_offset, *const entry_block = r.entry_block;
+    double* const energy = r.energy;
     MRC_TRY(store_alive(s, fn));
     mrc_handle* h = s->h;
     const mrc_config& cfg = h->cfg;
     const std::string w = fn;
-    for (int i = 0; i < 4; ++i) { s->stats[i] = 0; s->ms[i] = 0.0; }
-    if (mixArg != MRC_MIX_EACH && mixArg != MRC_MIX_MID)
-        return fail(h, MRC_ERR_INVALID, w + ": mix " + std::to_string(mixArg) + " is not MRC_MIX_EACH (3) or MRC_MIX_MID (0)");
+    reset_stats(s);
+    MRC_TRY(check_mix(h, w, mixArg, kMixEachOrMid));
     const int mix = mixArg == MRC_MIX_MID ? MRC_MIX_MID : kNoMix;
     MRC_TRY(check_divisor(h, w, D));
     const int64_t nFiles = (int64_t)s->index.files.size();
@@ -626,10 +742,7 @@ int block_energy(mrc_pac_store* s, int D, int mixArg, int64_t n_sel, const int64
     if (!entry_offset) return fail(h, MRC_ERR_INVALID, w + ": entry_offset is NULL");
     if (entry_cap < 0) return fail(h, MRC_ERR_INVALID, w + ": entry_cap < 0");
     const auto fileOf = [file](int64_t k) { return file ? file[k] : k; };
-    for (int64_t k = 0; k < n_sel; ++k)
-        if (fileOf(k) < 0 || fileOf(k) >= nFiles)
-            return fail(h, MRC_ERR_INVALID, w + ": file[" + std::to_string(k) + "] = " + std::to_string(fileOf(k)) + " is outside the store's " +
-                                                std::to_string(nFiles) + " files");
+    MRC_TRY(check_files(s, w, n_sel, file, 0, "item"));
     const auto columns = [&](int64_t f) { return mix == kNoMix ? s->index.files[(size_t)f].nch : 1; };
     entry_offset[0] = 0;
     for (int64_t k = 0; k < n_sel; ++k) entry_offset[k + 1] = entry_offset[k] + s->index.nBlocks(fileOf(k)) * columns(fileOf(k));
@@ -642,12 +755,12 @@ int block_energy(mrc_pac_store* s, int D, int mixArg, int64_t n_sel, const int64
     MRC_TRY(ensure_decode_consts(h));
     StoreBufs& b = h->store;
     MRC_HIP(h, b.ev.create());
-    hipStream_t st = pick_stream(h, stream);
+    hipStream_t st = pick_stream(h, r.stream);
     DrainGuard drain{{st, nullptr, nullptr}};
     const int64_t slab = h->storeSlabSamples, blockCap = (int64_t)1 << 28;      // (entries and slots of a launch stay below 2^31)
 
-    std::vector<Need> needs;
-    std::vector<EnergyEntry> entries[kUnpackGroups];
+    std::vector<Need>& needs = b.needs;                      // (the planner's scratch: StoreBufs)
+    std::vector<EnergyEntry>(&entries)[kUnpackGroups] = b.entries;
     PacPlan pl;                                              // (its group fields: the slab's slots)
     int64_t k = 0, blk = 0;                                  // the next block: block blk of selection k
     while (k < n_sel && s->index.nBlocks(fileOf(k)) == 0) ++k;
@@ -696,14 +809,9 @@ int block_energy(mrc_pac_store* s, int D, int mixArg, int64_t n_sel, const int64
                     entries[g].push_back(EnergyEntry{out + ch, slot, 0});
                 }
             }));
-        int64_t entryBase[kUnpackGroups], q = 0;
-        for (int g = 0; g < kUnpackGroups; ++g) {
-            entryBase[g] = q;
-            if (!entries[g].empty())
-                std::memcpy(S.pin + oEntries + sizeof(EnergyEntry) * (size_t)q, entries[g].data(), sizeof(EnergyEntry) * entries[g].size());
-            q += (int64_t)entries[g].size();
-        }
-        if (q != nSlabEntries) return fail(h, MRC_ERR_INVALID, w + ": internal error: a slab's entries do not add up");
+        int64_t entryBase[kUnpackGroups];
+        if (copy_entries(entries, S.pin + oEntries, entryBase) != nSlabEntries)
+            return fail(h, MRC_ERR_INVALID, w + ": internal error: a slab's entries do not add up");
         MRC_HIP(h, b.planes.reserve(sizeof(double) * (size_t)nSlabEntries));
 
         // ---- device: the parse step, one block_energy_kernel launch per group with slots, the energies back
@@ -721,12 +829,7 @@ int block_energy(mrc_pac_store* s, int D, int mixArg, int64_t n_sel, const int64
         MRC_HIP(h, hipEventRecord(b.ev[4], st));
         MRC_HIP(h, hipMemcpyAsync(energy + firstEntry, e, sizeof(double) * (size_t)nSlabEntries, hipMemcpyDeviceToHost, st));
         MRC_HIP(h, hipStreamSynchronize(st));                // (the staging is written again by the next slab)
-        const int span[3][2] = {{0, 1}, {1, 2}, {3, 4}};
-        for (int i = 0; i < 3; ++i) {
-            double ms = 0.0;
-            MRC_HIP(h, b.ev.elapsed(span[i][0], span[i][1], &ms));
-            s->ms[i] += ms;
-        }
+        MRC_TRY(add_elapsed(h, b.ev, kSlabSpans, 3, s->ms));
     }
     return MRC_OK;
 }
@@ -755,8 +858,11 @@ std::string band_line_ranges(double sampleRate, int a, int b, int nBands, const 
 
 // mrc_filterbank_line_weights' rule; rows (may be null: sizes only) receives the weights, filter after filter.  The
 // refusal's words as band_line_ranges gives them.  Host float64 in the header's order of operations (-ffp-contract=off).
-std::string filterbank_line_weights(double sampleRate, int a, int b, int nFilters, const double* p, int norm, int32_t* lineLo,
-                                    int32_t* lineHi, std::vector<double>* rows, int64_t* nWeights) {
+struct FilterPoints { double sampleRate; int nFilters; const double* p; int norm; };
+std::string filterbank_line_weights(const FilterPoints& bank, int a, int b, int32_t* lineLo, int32_t* lineHi, std::vector<double>* rows,
+                                    int64_t* nWeights) {
+    const double sampleRate = bank.sampleRate, *p = bank.p;
+    const int nFilters = bank.nFilters, norm = bank.norm;
     if (nFilters < 1 || nFilters > MRC_MAX_STORE_BANDS)
         return "n_filters " + std::to_string(nFilters) + " is outside 1.." + std::to_string(MRC_MAX_STORE_BANDS);
     if (!p || !lineLo || !lineHi || !nWeights) return "point_hz, line_lo, line_hi or n_weights is NULL";
@@ -814,18 +920,25 @@ struct EnergyTable {
 // blocks whose TILES the items' frames overlap, the table's kernel per group with slots into B [rows][nOut] in the store
 // workspace, band_frames_kernel over the slab's output.  An item's rows are its needed blocks in file order, a row per
 // decoded channel.
-int energy_frames_window(mrc_pac_store* s, EnergyTable& T, int mixArg, int64_t n_items, const int64_t* file, const int64_t* start,
-                         int64_t n_frames, int64_t hop, int n_channels_out, int format, void* out, void* stream) {
+struct FramesRequest {                                       // the arguments the two entries share, as the header names them
+    int mix;
+    int64_t n_items;
+    const int64_t *file, *start;
+    int64_t n_frames, hop;
+    int n_channels_out, format;
+    void *out, *stream;
+};
+int energy_frames_window(mrc_pac_store* s, EnergyTable& T, const FramesRequest& r) {
     const char* const fn = T.fn;
-    const int n_bands = T.nOut;
+    const int n_bands = T.nOut, mixArg = r.mix, n_channels_out = r.n_channels_out, format = r.format;
+    const int64_t n_items = r.n_items, n_frames = r.n_frames, hop = r.hop, *file = r.file, *start = r.start;
+    void *const out = r.out, *const stream = r.stream;
     MRC_TRY(store_alive(s, fn));
     mrc_handle* h = s->h;
     const mrc_config& cfg = h->cfg;
     const std::string w = fn;
-    for (int i = 0; i < 4; ++i) { s->stats[i] = 0; s->ms[i] = 0.0; }
-    if (mixArg != MRC_MIX_EACH && mixArg != MRC_MIX_MID && mixArg != MRC_MIX_LEFT && mixArg != MRC_MIX_RIGHT)
-        return fail(h, MRC_ERR_INVALID, w + ": mix " + std::to_string(mixArg) +
-                                            " is not MRC_MIX_EACH (3), MRC_MIX_MID (0), MRC_MIX_LEFT (1) or MRC_MIX_RIGHT (2)");
+    reset_stats(s);
+    MRC_TRY(check_mix(h, w, mixArg, kMixAny));
     const int mix = mixArg == MRC_MIX_EACH ? kNoMix : mixArg;
     if (mix == kNoMix ? n_channels_out != 1 && n_channels_out != 2 : n_channels_out != 1)
         return fail(h, MRC_ERR_INVALID, w + (mix == kNoMix ? ": n_channels_out must be 1 or 2" : ": n_channels_out must be 1 under a mix of one channel"));
@@ -839,17 +952,10 @@ int energy_frames_window(mrc_pac_store* s, EnergyTable& T, int mixArg, int64_t n
         const std::string refusal = T.build(cfg);
         if (!refusal.empty()) return fail(h, MRC_ERR_INVALID, w + ": " + refusal);
     }
-    const int64_t nFiles = (int64_t)s->index.files.size(), span = n_frames * hop;
+    const int64_t span = n_frames * hop;
     if (n_items > 0 && (!file || !start)) return fail(h, MRC_ERR_INVALID, w + ": file or start is NULL");
     if (n_items > 0 && n_frames > 0 && !out) return fail(h, MRC_ERR_INVALID, w + ": out is NULL");
-    for (int64_t k = 0; k < n_items; ++k) {
-        if (file[k] < 0 || file[k] >= nFiles)
-            return fail(h, MRC_ERR_INVALID, w + ": file[" + std::to_string(k) + "] = " + std::to_string(file[k]) + " is outside the store's " +
-                                                std::to_string(nFiles) + " files");
-        if (mix == kNoMix && s->index.files[(size_t)file[k]].nch > n_channels_out)
-            return fail(h, MRC_ERR_INVALID, w + ": item " + std::to_string(k) + ": file " + std::to_string(file[k]) +
-                                                " is stereo, the call asks for one channel");
-    }
+    MRC_TRY(check_files(s, w, n_items, file, mix == kNoMix ? n_channels_out : 0, "item"));
     if (n_items == 0 || n_frames == 0) return MRC_OK;
 
     MRC_TRY(ensure_decode_consts(h));
@@ -862,10 +968,10 @@ int energy_frames_window(mrc_pac_store* s, EnergyTable& T, int mixArg, int64_t n
     const int64_t slab = h->storeSlabSamples, itemCap = std::max<int64_t>(1, ((int64_t)1 << 38) / rowLen);   // (a launch's grid below 2^31)
     const auto floorHalf = [](int64_t v) { return v >= 0 ? v / 2 : -((-v + 1) / 2); };
 
-    std::vector<Need> needs;
-    std::vector<BandItem> items;
-    std::vector<int64_t> firstTile;                          // per item: its first needed block
-    std::vector<EnergyEntry> entries[kUnpackGroups];
+    std::vector<Need>& needs = b.needs;                      // (the planner's scratch: StoreBufs)
+    std::vector<BandItem>& items = b.bandItems;
+    std::vector<int64_t>& firstTile = b.firstTile;           // per item: its first needed block
+    std::vector<EnergyEntry>(&entries)[kUnpackGroups] = b.entries;
     PacPlan pl;                                              // (its group fields: the slab's slots)
     for (int64_t first = 0, last; first < n_items; first = last) {
         last = first + 1;
@@ -928,13 +1034,8 @@ int energy_frames_window(mrc_pac_store* s, EnergyTable& T, int mixArg, int64_t n
                     entries[g].push_back(EnergyEntry{row + (mix == kNoMix ? ch : 0), slot, 0});
                 }
             }));
-        int64_t entryBase[kUnpackGroups], q = 0;
-        for (int g = 0; g < kUnpackGroups; ++g) {
-            entryBase[g] = q;
-            if (!entries[g].empty())
-                std::memcpy(S.pin + oEntries + sizeof(EnergyEntry) * (size_t)q, entries[g].data(), sizeof(EnergyEntry) * entries[g].size());
-            q += (int64_t)entries[g].size();
-        }
+        int64_t entryBase[kUnpackGroups];
+        const int64_t q = copy_entries(entries, S.pin + oEntries, entryBase);
         if (q != nSlabEntries || q != nRows) return fail(h, MRC_ERR_INVALID, w + ": internal error: a slab's entries do not add up");
         std::memcpy(S.pin + oLines, T.words.data(), sizeof(int64_t) * T.words.size());
         long long* edges = (long long*)(S.pin + oEdges);
@@ -966,20 +1067,14 @@ int energy_frames_window(mrc_pac_store* s, EnergyTable& T, int mixArg, int64_t n
                                       n_channels_out, format, B, outSlab, st));
         MRC_HIP(h, hipEventRecord(b.ev[5], st));
         MRC_HIP(h, hipStreamSynchronize(st));                // (the staging is written again by the next slab)
-        const int span4[4][2] = {{0, 1}, {1, 2}, {3, 4}, {4, 5}};
-        for (int i = 0; i < 4; ++i) {
-            double ms = 0.0;
-            MRC_HIP(h, b.ev.elapsed(span4[i][0], span4[i][1], &ms));
-            s->ms[i] += ms;
-        }
+        MRC_TRY(add_elapsed(h, b.ev, kSlabSpans, 4, s->ms));
     }
     MRC_HIP(h, hipStreamSynchronize(st));
     return MRC_OK;
 }
 
 // the band call's table: int32 [4][MRC_MAX_STORE_BANDS + 1], a shape's line ranges (514 words)
-int band_energy_window(mrc_pac_store* s, int mix, int64_t n_items, const int64_t* file, const int64_t* start, int64_t n_frames,
-                       int64_t hop, int n_bands, const double* edge_hz, int n_channels_out, int format, void* out, void* stream) {
+int band_energy_window(mrc_pac_store* s, const FramesRequest& r, int n_bands, const double* edge_hz) {
     constexpr int kRow = MRC_MAX_STORE_BANDS + 1;
     EnergyTable T;
     T.fn = "mrc_pac_store_band_energy_window";
@@ -999,14 +1094,12 @@ int band_energy_window(mrc_pac_store* s, int mix, int64_t n_items, const int64_t
         return launch_band_energy(F, G.joint, n_bands, (const int*)table + sh * kRow, nEntries, entries, G.oscale,
                                   G.joint ? G.ms : nullptr, G.sf, G.ba, G.mant, sums, st);
     };
-    return energy_frames_window(s, T, mix, n_items, file, start, n_frames, hop, n_channels_out, format, out, stream);
+    return energy_frames_window(s, T, r);
 }
 
 // the filter call's table: int32 [4][3][n_filters] (a shape's lo, hi and row offsets, the offsets counted from the shape's
 // first weight), then the four shapes' rows of float64 weights one after the other
-int filterbank_window(mrc_pac_store* s, int mix, int64_t n_items, const int64_t* file, const int64_t* start, int64_t n_frames,
-                      int64_t hop, int n_filters, const double* point_hz, int norm, int n_channels_out, int format, void* out,
-                      void* stream) {
+int filterbank_window(mrc_pac_store* s, const FramesRequest& r, int n_filters, const double* point_hz, int norm) {
     EnergyTable T;
     T.fn = "mrc_pac_store_filterbank_window";
     T.nOut = n_filters;
@@ -1020,7 +1113,7 @@ int filterbank_window(mrc_pac_store* s, int mix, int64_t n_items, const int64_t*
             lo[sh].assign((size_t)std::max(n_filters, 1), 0);
             hi[sh].assign((size_t)std::max(n_filters, 1), 0);
             int64_t n = 0;
-            const std::string refusal = filterbank_line_weights((double)cfg.sample_rate, a, b, n_filters, point_hz, norm,
+            const std::string refusal = filterbank_line_weights(FilterPoints{(double)cfg.sample_rate, n_filters, point_hz, norm}, a, b,
                                                                 lo[sh].data(), hi[sh].data(), &rows[sh], &n);
             if (!refusal.empty()) return refusal;
         }
@@ -1047,7 +1140,7 @@ int filterbank_window(mrc_pac_store* s, int mix, int64_t n_items, const int64_t*
                                         (const double*)(table + rowWord[sh]), nEntries, entries, G.oscale, G.joint ? G.ms : nullptr,
                                         G.sf, G.ba, G.mant, sums, st);
     };
-    return energy_frames_window(s, T, mix, n_items, file, start, n_frames, hop, n_channels_out, format, out, stream);
+    return energy_frames_window(s, T, r);
 }
 
 }  // namespace
@@ -1058,7 +1151,7 @@ int mrc_filterbank_line_weights(double sample_rate, int a, int b, int n_filters,
                                 int32_t* line_lo, int32_t* line_hi, int64_t weight_cap, double* weight, int64_t* n_weights) {
     const char* const fn = "mrc_filterbank_line_weights: ";
     std::vector<double> rows;
-    const std::string refusal = filterbank_line_weights(sample_rate, a, b, n_filters, point_hz, norm, line_lo, line_hi,
+    const std::string refusal = filterbank_line_weights(FilterPoints{sample_rate, n_filters, point_hz, norm}, a, b, line_lo, line_hi,
                                                         weight ? &rows : nullptr, n_weights);
     if (!refusal.empty()) return fail(nullptr, MRC_ERR_INVALID, fn + refusal);
     if (!weight) return MRC_OK;
@@ -1072,8 +1165,8 @@ int mrc_filterbank_line_weights(double sample_rate, int a, int b, int n_filters,
 int mrc_pac_store_filterbank_window(mrc_pac_store* s, int mix, int64_t n_items, const int64_t* file, const int64_t* start,
                                     int64_t n_frames, int64_t hop, int n_filters, const double* point_hz, int norm,
                                     int n_channels_out, int format, void* out, void* stream) {
-    return filterbank_window(s, mix, n_items, file, start, n_frames, hop, n_filters, point_hz, norm, n_channels_out, format, out,
-                             stream);
+    return filterbank_window(s, FramesRequest{mix, n_items, file, start, n_frames, hop, n_channels_out, format, out, stream}, n_filters,
+                             point_hz, norm);
 }
 
 int mrc_band_line_ranges(double sample_rate, int a, int b, int n_bands, const double* edge_hz, int32_t* line_lo) {
@@ -1084,23 +1177,8 @@ int mrc_band_line_ranges(double sample_rate, int a, int b, int n_bands, const do
 int mrc_pac_store_band_energy_window(mrc_pac_store* s, int mix, int64_t n_items, const int64_t* file, const int64_t* start,
                                      int64_t n_frames, int64_t hop, int n_bands, const double* edge_hz, int n_channels_out,
                                      int format, void* out, void* stream) {
-    return band_energy_window(s, mix, n_items, file, start, n_frames, hop, n_bands, edge_hz, n_channels_out, format, out, stream);
-}
-
-int mrc_pac_store_decode_window(mrc_pac_store* s, int64_t n_items, const int64_t* file, const int64_t* start, int64_t window,
-                                int n_channels_out, int format, void* out, void* stream) {
-    return decode_windows(s, kWin, 1, nullptr, n_items, file, start, window, n_channels_out, format, out, stream);
-}
-
-int mrc_pac_store_decode_window_reduced(mrc_pac_store* s, int rate_divisor, int64_t n_items, const int64_t* file,
-                                        const int64_t* start, int64_t window, int n_channels_out, int format, void* out,
-                                        void* stream) {
-    return decode_windows(s, kWinReduced, rate_divisor, nullptr, n_items, file, start, window, n_channels_out, format, out, stream);
-}
-
-int mrc_pac_store_decode_window_mix(mrc_pac_store* s, int rate_divisor, int mix, int64_t n_items, const int64_t* file,
-                                    const int64_t* start, int64_t window, int format, void* out, void* stream) {
-    return decode_windows(s, kWinMix, rate_divisor, &mix, n_items, file, start, window, 1, format, out, stream);
+    return band_energy_window(s, FramesRequest{mix, n_items, file, start, n_frames, hop, n_channels_out, format, out, stream}, n_bands,
+                              edge_hz);
 }
 
 int mrc_resample_taps(int up, int down, int zeros, double rolloff, int32_t* half_width, double* taps) {
@@ -1112,164 +1190,139 @@ int mrc_resample_taps(int up, int down, int zeros, double rolloff, int32_t* half
     return MRC_OK;
 }
 
-int mrc_pac_store_decode_window_resampled(mrc_pac_store* s, int rate_divisor, int mix, int up, int down, int zeros, double rolloff,
-                                          int64_t n_items, const int64_t* file, const int64_t* start, int64_t window,
-                                          int n_channels_out, int format, void* out, void* stream) {
-    MRC_TRY(store_alive(s, kWinResampled));
-    mrc_handle* h = s->h;
-    const std::string w = kWinResampled;
-    if (mix != MRC_MIX_EACH && mix != MRC_MIX_MID && mix != MRC_MIX_LEFT && mix != MRC_MIX_RIGHT)
-        return fail(h, MRC_ERR_INVALID, w + ": mix " + std::to_string(mix) +
-                                            " is not MRC_MIX_EACH (3), MRC_MIX_MID (0), MRC_MIX_LEFT (1) or MRC_MIX_RIGHT (2)");
-    if (mix != MRC_MIX_EACH && n_channels_out != 1)
-        return fail(h, MRC_ERR_INVALID, w + ": n_channels_out must be 1 under a mix of one channel");
-    ResampleSpec r;
-    const std::string refusal = resample_spec(up, down, zeros, rolloff, &r);
-    if (!refusal.empty()) return fail(h, MRC_ERR_INVALID, w + ": " + refusal);
-    return decode_windows(s, kWinResampled, rate_divisor, mix == MRC_MIX_EACH ? nullptr : &mix, n_items, file, start, window,
-                          n_channels_out, format, out, stream, &r);
-}
-
 }  // extern "C"
 
 namespace {
 
-// mrc_pac_store_decode_window_sum and, with bands (n_bands, edge_hz, band_gain: the caller's, unchecked),
-// mrc_pac_store_decode_window_shaped: the checks of the rows and of the bands, then decode_windows
-// ... and, with ratios (mrc_pac_store_decode_window_speeds: up and down are then not looked at), the checks of the list and of
-// the terms' indices into it
-struct BandArgs { int nBands; const double* edgeHz; const double* bandGain; };
-struct RatioArgs { int nRatios; const int32_t* up; const int32_t* down; const int32_t* ratioOf; };
-int decode_window_rows(mrc_pac_store* s, const char* fn, int rate_divisor, int mix, int up, int down, int zeros, double rolloff,
-                       const BandArgs* bands, int64_t n_items, const int64_t* term_offset, const int64_t* file, const int64_t* start,
-                       const double* gain, int64_t window, int n_channels_out, int format, void* out, void* stream,
-                       const RatioArgs* ratios = nullptr) {
-    MRC_TRY(store_alive(s, fn));
+// The one check of every window call, made once per public call: every refusal the entries give, under the entry's name and in
+// the order each entry has always given them -- the request's own arguments (mix, ratios, rows, bands), the divisor, window,
+// channels, format and files, then the bank indices of a reverb or STFT call.  window, format and out are the call's; an STFT
+// call passes its row length L (0 without frames) and MRC_WINDOW_F64.  The kinds differ only in where window and out are
+// looked at: a reverb call refuses a bad window before its rows and a NULL out last of all, an STFT call has refused its own
+// arguments before it comes here and names L in its bound on the pre-roll.
+constexpr int64_t kMaxWindow = (int64_t)1 << 40;
+int check_windows(mrc_pac_store* s, const WindowRequest& q, int64_t window, int format, void* out, CheckedWindows* c) {
     mrc_handle* h = s->h;
-    const std::string w = fn;
-    if (mix != MRC_MIX_EACH && mix != MRC_MIX_MID && mix != MRC_MIX_LEFT && mix != MRC_MIX_RIGHT)
-        return fail(h, MRC_ERR_INVALID, w + ": mix " + std::to_string(mix) +
-                                            " is not MRC_MIX_EACH (3), MRC_MIX_MID (0), MRC_MIX_LEFT (1) or MRC_MIX_RIGHT (2)");
-    if (mix != MRC_MIX_EACH && n_channels_out != 1)
-        return fail(h, MRC_ERR_INVALID, w + ": n_channels_out must be 1 under a mix of one channel");
-    if (ratios) {
-        up = down = 1;
-        if (ratios->nRatios < 1 || ratios->nRatios > MRC_MAX_STORE_RATIOS)
-            return fail(h, MRC_ERR_INVALID, w + ": n_ratios " + std::to_string(ratios->nRatios) + " is outside 1.." + std::to_string(MRC_MAX_STORE_RATIOS));
-    }
-    if (up < 1 || down < 1)
-        return fail(h, MRC_ERR_INVALID, w + ": " + (up < 1 ? "up " + std::to_string(up) : "down " + std::to_string(down)) + " is below 1");
-    ResampleSpec r;
-    if (up != down) {                                        // (up == down: ratio 1, zeros and rolloff are not looked at)
-        const std::string refusal = resample_spec(up, down, zeros, rolloff, &r);
-        if (!refusal.empty()) return fail(h, MRC_ERR_INVALID, w + ": " + refusal);
-    }
-    if (n_items < 0) return fail(h, MRC_ERR_INVALID, w + ": n_items < 0");
-    if (!term_offset) return fail(h, MRC_ERR_INVALID, w + ": term_offset is NULL");
-    if (term_offset[0] != 0) return fail(h, MRC_ERR_INVALID, w + ": term_offset[0] = " + std::to_string(term_offset[0]) + " is not 0");
-    for (int64_t i = 0; i < n_items; ++i)
-        if (term_offset[i + 1] < term_offset[i])
-            return fail(h, MRC_ERR_INVALID, w + ": term_offset decreases at [" + std::to_string(i + 1) + "]");
-    const int64_t nTerms = term_offset[n_items];
-    if (nTerms > 0 && (!file || !start || !gain)) return fail(h, MRC_ERR_INVALID, w + ": file, start or gain is NULL");
-    for (int64_t k = 0; k < nTerms; ++k)
-        if (!std::isfinite(gain[k])) return fail(h, MRC_ERR_INVALID, w + ": gain of term " + std::to_string(k) + " is not finite");
-    SpeedSpec speeds;
-    if (ratios && nTerms > 0 && (!ratios->up || !ratios->down || !ratios->ratioOf))
-        return fail(h, MRC_ERR_INVALID, w + ": ratio_up, ratio_down or ratio_of is NULL");
-    if (ratios && ratios->up && ratios->down) {              // the list is checked wherever it is given, terms or none
-        speeds.nRatios = ratios->nRatios;
-        speeds.ratioOf = ratios->ratioOf;
-        for (int i = 0; i < ratios->nRatios; ++i) {
-            const int u = ratios->up[i], d = ratios->down[i];
-            const std::string at = "ratio " + std::to_string(i) + ": ";
-            if (u < 1 || d < 1)
-                return fail(h, MRC_ERR_INVALID, w + ": " + at + (u < 1 ? "up " + std::to_string(u) : "down " + std::to_string(d)) + " is not positive");
-            speeds.r[i] = ResampleSpec{1, 1, 0, 0.0, 0};     // (u == d: the unit ratio, zeros and rolloff are not looked at)
-            if (u != d) {
-                const std::string refusal = resample_spec(u, d, zeros, rolloff, &speeds.r[i]);
-                if (!refusal.empty()) return fail(h, MRC_ERR_INVALID, w + ": " + at + refusal);
-            }
+    const std::string w = q.fn;
+    const auto refuse = [&](const std::string& what) { return fail(h, MRC_ERR_INVALID, w + ": " + what); };
+    const bool rows = q.rows(), banked = q.kind == WindowRequest::kReverb || q.kind == WindowRequest::kStft;
+    const bool windowOk = window >= 0 && window <= kMaxWindow;
+    c->q = q;
+    if (q.ratioList && q.nBands == 0 && (q.edgeHz || q.bandGain))
+        return refuse("n_bands is 0 (no band gains) but edge_hz or band_gain is not NULL");
+    if (q.kind == WindowRequest::kReverb && !windowOk) return refuse("window must lie in [0, 2^40]");
+    MRC_TRY(check_mix(h, w, q.mix, q.mixAllowed));
+    if (q.mix != MRC_MIX_EACH && q.nChannelsOut != 1) return refuse("n_channels_out must be 1 under a mix of one channel");
+    c->mix = q.mix == MRC_MIX_EACH ? kNoMix : q.mix;
+    // ---- the ratio, or the length of the list
+    if (q.ratioList) {
+        if (q.nRatios < 1 || q.nRatios > MRC_MAX_STORE_RATIOS)
+            return refuse("n_ratios " + std::to_string(q.nRatios) + " is outside 1.." + std::to_string(MRC_MAX_STORE_RATIOS));
+    } else if (rows || q.resampled) {
+        if (rows && (q.up < 1 || q.down < 1))
+            return refuse((q.up < 1 ? "up " + std::to_string(q.up) : "down " + std::to_string(q.down)) + " is below 1");
+        if (!rows || q.up != q.down) {                       // (rows at up == down: ratio 1, zeros and rolloff are not looked at)
+            const std::string refusal = resample_spec(q.up, q.down, q.zeros, q.rolloff, &c->rs);
+            if (!refusal.empty()) return refuse(refusal);
+            c->filtered = true;
         }
-        for (int64_t k = 0; k < nTerms; ++k)                 // (terms present: ratio_of is not NULL)
-            if (ratios->ratioOf[k] < 0 || ratios->ratioOf[k] >= ratios->nRatios)
-                return fail(h, MRC_ERR_INVALID, w + ": ratio_of of term " + std::to_string(k) + " = " + std::to_string(ratios->ratioOf[k]) +
-                                                    " is outside the list of " + std::to_string(ratios->nRatios) + " ratios");
     }
-    ShapeSpec shape;
-    if (bands) {
-        const int nb = bands->nBands;
-        if (nb < 1 || nb > MRC_MAX_STORE_BANDS)
-            return fail(h, MRC_ERR_INVALID, w + ": n_bands " + std::to_string(nb) + " is outside 1.." + std::to_string(MRC_MAX_STORE_BANDS));
-        if (nTerms > 0 && (!bands->edgeHz || !bands->bandGain)) return fail(h, MRC_ERR_INVALID, w + ": edge_hz or band_gain is NULL");
-        shape.nBands = nb;
-        shape.bandGain = bands->bandGain;
-        int32_t lineLo[MRC_MAX_STORE_BANDS + 1];
-        for (int sh = 0; bands->edgeHz && sh < 4; ++sh) {
-            int a, b;
-            shape_ab(h->cfg, sh, &a, &b);
-            const std::string refusal = band_line_ranges((double)h->cfg.sample_rate, a, b, nb, bands->edgeHz, lineLo);
-            if (!refusal.empty()) return fail(h, MRC_ERR_INVALID, w + ": " + refusal);
-            shape.lineOff[sh] = (int64_t)shape.lineBand.size();
-            shape.lineBand.resize(shape.lineBand.size() + (size_t)((a + b) / 2), kNoLineBand);
-            uint16_t* lb = shape.lineBand.data() + shape.lineOff[sh];
-            for (int q = 0; q < nb; ++q)
-                for (int k = lineLo[q]; k < lineLo[q + 1]; ++k) lb[k] = (uint16_t)q;
-        }
+    // ---- the rows, their terms, the list of ratios and the bands
+    if (rows) {
+        if (q.nItems < 0) return refuse("n_items < 0");
+        if (!q.termOffset) return refuse("term_offset is NULL");
+        if (q.termOffset[0] != 0) return refuse("term_offset[0] = " + std::to_string(q.termOffset[0]) + " is not 0");
+        for (int64_t i = 0; i < q.nItems; ++i)
+            if (q.termOffset[i + 1] < q.termOffset[i]) return refuse("term_offset decreases at [" + std::to_string(i + 1) + "]");
+        const int64_t nTerms = c->nTerms = q.termOffset[q.nItems];
+        if (nTerms > 0 && (!q.file || !q.start || !q.gain)) return refuse("file, start or gain is NULL");
         for (int64_t k = 0; k < nTerms; ++k)
-            for (int q = 0; q < nb; ++q)
-                if (!std::isfinite(bands->bandGain[k * nb + q]))
-                    return fail(h, MRC_ERR_INVALID, w + ": band_gain of term " + std::to_string(k) + ", band " + std::to_string(q) + " is not finite");
+            if (!std::isfinite(q.gain[k])) return refuse("gain of term " + std::to_string(k) + " is not finite");
+        if (q.ratioList && nTerms > 0 && (!q.ratioUp || !q.ratioDown || !q.ratioOf))
+            return refuse("ratio_up, ratio_down or ratio_of is NULL");
+        if (q.ratioList && q.ratioUp && q.ratioDown) {       // the list is checked wherever it is given, terms or none
+            c->speeds.nRatios = q.nRatios;
+            for (int i = 0; i < q.nRatios; ++i) {
+                const int u = q.ratioUp[i], d = q.ratioDown[i];
+                const std::string at = "ratio " + std::to_string(i) + ": ";
+                if (u < 1 || d < 1) return refuse(at + (u < 1 ? "up " + std::to_string(u) : "down " + std::to_string(d)) + " is not positive");
+                c->speeds.r[i] = ResampleSpec{1, 1, 0, 0.0, 0};  // (u == d: the unit ratio, zeros and rolloff are not looked at)
+                if (u != d) {
+                    const std::string refusal = resample_spec(u, d, q.zeros, q.rolloff, &c->speeds.r[i]);
+                    if (!refusal.empty()) return refuse(at + refusal);
+                }
+            }
+            for (int64_t k = 0; k < nTerms; ++k)             // (terms present: ratio_of is not NULL)
+                if (q.ratioOf[k] < 0 || q.ratioOf[k] >= q.nRatios)
+                    return refuse("ratio_of of term " + std::to_string(k) + " = " + std::to_string(q.ratioOf[k]) +
+                                  " is outside the list of " + std::to_string(q.nRatios) + " ratios");
+        }
+        c->speedy = q.ratioList && nTerms > 0;
+        if (q.banded) {
+            const int nb = q.nBands;
+            if (nb < 1 || nb > MRC_MAX_STORE_BANDS)
+                return refuse("n_bands " + std::to_string(nb) + " is outside 1.." + std::to_string(MRC_MAX_STORE_BANDS));
+            if (nTerms > 0 && (!q.edgeHz || !q.bandGain)) return refuse("edge_hz or band_gain is NULL");
+            int32_t lineLo[MRC_MAX_STORE_BANDS + 1];
+            for (int sh = 0; q.edgeHz && sh < 4; ++sh) {     // per call one uint16 line-to-band table per block shape
+                int a, b;
+                shape_ab(h->cfg, sh, &a, &b);
+                const std::string refusal = band_line_ranges((double)h->cfg.sample_rate, a, b, nb, q.edgeHz, lineLo);
+                if (!refusal.empty()) return refuse(refusal);
+                c->shape.lineOff[sh] = (int64_t)c->shape.lineBand.size();
+                c->shape.lineBand.resize(c->shape.lineBand.size() + (size_t)((a + b) / 2), kNoLineBand);
+                uint16_t* lb = c->shape.lineBand.data() + c->shape.lineOff[sh];
+                for (int b0 = 0; b0 < nb; ++b0)
+                    for (int k = lineLo[b0]; k < lineLo[b0 + 1]; ++k) lb[k] = (uint16_t)b0;
+            }
+            for (int64_t k = 0; k < nTerms; ++k)
+                for (int b0 = 0; b0 < nb; ++b0)
+                    if (!std::isfinite(q.bandGain[k * nb + b0]))
+                        return refuse("band_gain of term " + std::to_string(k) + ", band " + std::to_string(b0) + " is not finite");
+            c->shaped = true;
+        }
     }
-    const SumSpec sum{n_items, term_offset, gain};
-    return decode_windows(s, fn, rate_divisor, mix == MRC_MIX_EACH ? nullptr : &mix, nTerms, file, start, window, n_channels_out,
-                          format, out, stream, up != down ? &r : nullptr, &sum, bands ? &shape : nullptr,
-                          ratios && nTerms > 0 ? &speeds : nullptr);
+    // ---- what every window call is asked: divisor, window, channels, format, files
+    MRC_TRY(check_divisor(h, w, q.rateDivisor));
+    if (!rows) {
+        if (q.nItems < 0) return refuse("n_items < 0");
+        c->nTerms = q.nItems;
+    }
+    if (!windowOk) return refuse("window must lie in [0, 2^40]");
+    if (q.nChannelsOut != 1 && q.nChannelsOut != 2) return refuse("n_channels_out must be 1 or 2");
+    if (format != MRC_WINDOW_PCM16 && format != MRC_WINDOW_F32 && format != MRC_WINDOW_F64)
+        return refuse("unknown format " + std::to_string(format));
+    if (!rows && q.nItems > 0 && (!q.file || !q.start)) return refuse("file or start is NULL");
+    c->empty = q.nItems == 0 || window == 0;
+    if (!banked && !c->empty && !out) return refuse("out is NULL");
+    MRC_TRY(check_files(s, w, c->nTerms, q.file, c->mix == kNoMix ? q.nChannelsOut : 0, rows ? "term" : "item"));
+    if (!banked) return MRC_OK;
+    // ---- the terms' impulse responses
+    const int64_t nIrs = (int64_t)s->irLen.size();
+    if (c->nTerms > 0 && !q.irOf) return refuse("ir_of is NULL");
+    for (int64_t k = 0; k < c->nTerms; ++k) {
+        const int64_t v = q.irOf[k];
+        if (v == -1) continue;
+        if (v >= 0 && nIrs == 0)
+            return refuse("ir_of of term " + std::to_string(k) + " = " + std::to_string(v) +
+                          " but the store has no impulse responses (mrc_pac_store_set_irs)");
+        if (v < 0 || v >= nIrs)
+            return refuse("ir_of of term " + std::to_string(k) + " = " + std::to_string(v) + " is neither -1 nor inside the bank of " +
+                          std::to_string(nIrs) + " impulse responses");
+        c->maxPreRoll = std::max(c->maxPreRoll, s->irLen[(size_t)v] - 1);
+    }
+    const std::string tooLong = " + the longest impulse response named - 1 = " + std::to_string(window + c->maxPreRoll) + " exceeds 2^40";
+    const bool overlong = window + c->maxPreRoll > kMaxWindow;
+    if (q.kind == WindowRequest::kReverb && overlong) return refuse("window" + tooLong);
+    if (!c->empty && !out) return refuse("out is NULL");
+    if (q.kind == WindowRequest::kStft && !c->empty && overlong) return refuse("L" + tooLong);
+    return MRC_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int mrc_pac_store_decode_window_sum(mrc_pac_store* s, int rate_divisor, int mix, int up, int down, int zeros, double rolloff,
-                                    int64_t n_items, const int64_t* term_offset, const int64_t* file, const int64_t* start,
-                                    const double* gain, int64_t window, int n_channels_out, int format, void* out, void* stream) {
-    return decode_window_rows(s, kWinSum, rate_divisor, mix, up, down, zeros, rolloff, nullptr, n_items, term_offset, file, start, gain,
-                              window, n_channels_out, format, out, stream);
-}
-
-int mrc_pac_store_decode_window_shaped(mrc_pac_store* s, int rate_divisor, int mix, int up, int down, int zeros, double rolloff,
-                                       int n_bands, const double* edge_hz, const double* band_gain, int64_t n_items,
-                                       const int64_t* term_offset, const int64_t* file, const int64_t* start, const double* gain,
-                                       int64_t window, int n_channels_out, int format, void* out, void* stream) {
-    const BandArgs bands{n_bands, edge_hz, band_gain};
-    return decode_window_rows(s, kWinShaped, rate_divisor, mix, up, down, zeros, rolloff, &bands, n_items, term_offset, file, start,
-                              gain, window, n_channels_out, format, out, stream);
-}
-
-int mrc_pac_store_decode_window_speeds(mrc_pac_store* s, int rate_divisor, int mix, int n_ratios, const int32_t* ratio_up,
-                                       const int32_t* ratio_down, int zeros, double rolloff, int n_bands, const double* edge_hz,
-                                       const double* band_gain, int64_t n_items, const int64_t* term_offset, const int64_t* file,
-                                       const int64_t* start, const double* gain, const int32_t* ratio_of, int64_t window,
-                                       int n_channels_out, int format, void* out, void* stream) {
-    MRC_TRY(store_alive(s, kWinSpeeds));
-    if (n_bands == 0 && (edge_hz || band_gain))
-        return fail(s->h, MRC_ERR_INVALID, std::string(kWinSpeeds) + ": n_bands is 0 (no band gains) but edge_hz or band_gain is not NULL");
-    const BandArgs bands{n_bands, edge_hz, band_gain};
-    const RatioArgs ratios{n_ratios, ratio_up, ratio_down, ratio_of};
-    return decode_window_rows(s, kWinSpeeds, rate_divisor, mix, 1, 1, zeros, rolloff, n_bands == 0 ? nullptr : &bands, n_items, term_offset,
-                              file, start, gain, window, n_channels_out, format, out, stream, &ratios);
-}
-
-}  // extern "C"
-
-namespace {
-
-// mrc_pac_store_decode_window_reverb: a slab loop AROUND the rows call.  Per slab of whole rows the existing machinery decodes
-// every term as a one-term row at gain 1.0 over (start - Lpre, window + Lpre) in MRC_WINDOW_F64 into StoreBufs::reverbDry --
-// 0.0 + 1.0 * v is v (and a -0.0 becomes +0.0, which no fold from +0.0 can tell apart) -- then reverb_forward_kernel
-// transforms the convolved terms' segments and reverb_fold_kernel folds the rows (mrc_kernels_reverb.hip), on the same stream.
-// The term and source records of a slab go up in one copy.
+// The reverb loop: per slab of whole rows the units loop decodes every term as a row of its own at gain 1.0 over
+// (start - Lpre, window + Lpre) in MRC_WINDOW_F64 into StoreBufs::reverbDry, then reverb_forward_kernel transforms the
+// convolved terms' segments and reverb_fold_kernel folds the rows (mrc_kernels_reverb.hip), on the same stream.  The term and
+// source records of a slab go up in one copy.
 const char* const kWinReverb = "mrc_pac_store_decode_window_reverb";
 const char* const kSetIrs = "mrc_pac_store_set_irs";
 constexpr int64_t kRevB = MRC_STORE_REVERB_BLOCK, kRevN = 2 * kRevB;
@@ -1345,104 +1398,47 @@ int set_irs(mrc_pac_store* s, int64_t n_irs, const int64_t* ir_offset, const dou
     return MRC_OK;
 }
 
-// The handle's slab size read as "one slab" by the calls made in its scope, for a caller that has cut the slab itself.  The one
-// place that sets handle state aside: never nested (decode_window_reverb holds one at a time; stft_window holds none).
-struct OneSlabScope {
-    mrc_handle* h;
-    int64_t was;
-    explicit OneSlabScope(mrc_handle* handle) : h(handle), was(handle->storeSlabSamples) { h->storeSlabSamples = 0; }
-    ~OneSlabScope() { h->storeSlabSamples = was; }
-    OneSlabScope(const OneSlabScope&) = delete;
-    OneSlabScope& operator=(const OneSlabScope&) = delete;
-};
-
-// fn: who is named in a refusal; oneSlab: the caller (stft_window) has cut the slab already and the call runs as one
-int decode_window_reverb(mrc_pac_store* s, int rate_divisor, int mix, int n_ratios, const int32_t* ratio_up, const int32_t* ratio_down,
-                         int zeros, double rolloff, int n_bands, const double* edge_hz, const double* band_gain, int64_t n_items,
-                         const int64_t* term_offset, const int64_t* file, const int64_t* start, const double* gain,
-                         const int32_t* ratio_of, const int32_t* ir_of, int64_t window, int n_channels_out, int format, void* out,
-                         void* stream, const char* fn = kWinReverb, bool oneSlab = false) {
-    MRC_TRY(store_alive(s, fn));
+// Two things follow from the RANGE the loop is given -- the whole call from decode_window_reverb, one STFT slab from
+// stft_loop -- and are kept as the nesting of the entries once made them:
+//   Lpre, the pre-roll, is the longest response named by the terms of the range - 1, not of the call: it decides which
+//   blocks are decoded and so chunks_parsed;
+//   a range without a convolved term takes the plain rows path: no dry buffer, no fold, the units loop's own slabs.
+constexpr int kReverbSpans[2][2] = {{0, 1}, {1, 2}};         // StoreBufs::reverbEv: forward | fold
+int reverb_loop(mrc_pac_store* s, const CheckedWindows& c, const WindowRun& run) {
+    const WindowRequest& q = c.q;
     mrc_handle* h = s->h;
-    const std::string w = fn;
-    s->reverbMs[0] = s->reverbMs[1] = 0.0;
-    if (n_bands == 0 && (edge_hz || band_gain))
-        return fail(h, MRC_ERR_INVALID, w + ": n_bands is 0 (no band gains) but edge_hz or band_gain is not NULL");
-    if (window < 0 || window > ((int64_t)1 << 40)) return fail(h, MRC_ERR_INVALID, w + ": window must lie in [0, 2^40]");
-    // every check of the rows call, made by that call at window 0: nothing is launched
-    const BandArgs bands{n_bands, edge_hz, band_gain};
-    const RatioArgs ratios{n_ratios, ratio_up, ratio_down, ratio_of};
-    MRC_TRY(decode_window_rows(s, fn, rate_divisor, mix, 1, 1, zeros, rolloff, n_bands == 0 ? nullptr : &bands, n_items, term_offset, file,
-                               start, gain, 0, n_channels_out, format, out, stream, &ratios));
-    const int64_t nTerms = term_offset[n_items], nIrs = (int64_t)s->irLen.size();
-    if (nTerms > 0 && !ir_of) return fail(h, MRC_ERR_INVALID, w + ": ir_of is NULL");
+    const int64_t* const term_offset = q.termOffset;
+    const int32_t* const ir_of = q.irOf;
     int64_t Lpre = 0;
-    bool anyConvolved = false;
-    for (int64_t k = 0; k < nTerms; ++k) {
-        const int64_t v = ir_of[k];
-        if (v == -1) continue;
-        if (v >= 0 && nIrs == 0)
-            return fail(h, MRC_ERR_INVALID, w + ": ir_of of term " + std::to_string(k) + " = " + std::to_string(v) +
-                                                " but the store has no impulse responses (mrc_pac_store_set_irs)");
-        if (v < 0 || v >= nIrs)
-            return fail(h, MRC_ERR_INVALID, w + ": ir_of of term " + std::to_string(k) + " = " + std::to_string(v) +
-                                                " is neither -1 nor inside the bank of " + std::to_string(nIrs) + " impulse responses");
-        Lpre = std::max(Lpre, s->irLen[(size_t)v] - 1);
-        anyConvolved = true;
-    }
-    if (!anyConvolved) {                                     // the speeds call's path, unchanged
-        if (!oneSlab)
-            return decode_window_rows(s, fn, rate_divisor, mix, 1, 1, zeros, rolloff, n_bands == 0 ? nullptr : &bands, n_items, term_offset,
-                                      file, start, gain, window, n_channels_out, format, out, stream, &ratios);
-        OneSlabScope scope(h);
-        return decode_window_rows(s, fn, rate_divisor, mix, 1, 1, zeros, rolloff, n_bands == 0 ? nullptr : &bands, n_items, term_offset,
-                                  file, start, gain, window, n_channels_out, format, out, stream, &ratios);
-    }
-    const int64_t Wd = window + Lpre;
-    if (Wd > ((int64_t)1 << 40))
-        return fail(h, MRC_ERR_INVALID, w + ": window + the longest impulse response named - 1 = " + std::to_string(Wd) + " exceeds 2^40");
-    if (n_items == 0 || window == 0) return MRC_OK;
-    if (!out) return fail(h, MRC_ERR_INVALID, w + ": out is NULL");
+    for (int64_t k = term_offset[run.first]; k < term_offset[run.last]; ++k)
+        if (ir_of[k] >= 0) Lpre = std::max(Lpre, s->irLen[(size_t)ir_of[k]]);     // (longest length; at least 1 if any)
+    if (Lpre == 0) return units_loop(s, c, run);
+    Lpre -= 1;
+    const int64_t window = run.window, Wd = window + Lpre;
+    const int format = run.format, nch = q.nChannelsOut;
 
     MRC_HIP(h, hipSetDevice(h->device));
     MRC_TRY(ensure_reverb_twiddles(h));
     StoreBufs& b = h->store;
     MRC_HIP(h, b.reverbEv.create());
-    hipStream_t st = pick_stream(h, stream);
+    hipStream_t st = pick_stream(h, q.stream);
     DrainGuard drain{{st, nullptr, nullptr}};
     const size_t elem = format == MRC_WINDOW_PCM16 ? 2 : format == MRC_WINDOW_F32 ? 4 : 8;
-    const int nch = n_channels_out;
-    const int64_t M = (window + kRevB - 1) / kRevB, slab = oneSlab ? 0 : h->storeSlabSamples, rowCap = std::max<int64_t>(1, 0x7fffffffLL / M);
-    int64_t stats[4] = {0, 0, 0, 0};
-    double ms[4] = {0, 0, 0, 0}, reverbMs[2] = {0, 0};
-    std::vector<int64_t> ident, starts;
-    std::vector<double> ones;
-    for (int64_t first = 0, last; first < n_items; first = last) {   // rows [first, last), their terms [u0, u0 + nT)
+    const int64_t M = (window + kRevB - 1) / kRevB, slab = run.slab, rowCap = std::max<int64_t>(1, 0x7fffffffLL / M);
+    for (int64_t first = run.first, last; first < run.last; first = last) {   // rows [first, last), their terms [u0, u0 + nT)
         last = first + 1;
-        while (last < n_items && last - first < rowCap && (slab == 0 || (term_offset[last + 1] - term_offset[first]) * Wd <= slab)) ++last;
+        while (last < run.last && last - first < rowCap && (slab == 0 || (term_offset[last + 1] - term_offset[first]) * Wd <= slab)) ++last;
         const int64_t nRows = last - first, u0 = term_offset[first], nT = term_offset[last] - u0;
-        unsigned char* outSlab = (unsigned char*)out + (size_t)first * nch * window * elem;
+        unsigned char* outSlab = (unsigned char*)run.out + (size_t)(first - run.first) * nch * window * elem;
         if (nT == 0) {                                       // rows without terms: +0.0
             MRC_HIP(h, hipMemsetAsync(outSlab, 0, (size_t)nRows * nch * window * elem, st));
-            stats[2] += 1;
+            s->stats[2] += 1;
             continue;
         }
-        // ---- the dry terms, by the existing machinery
+        // ---- the dry terms, by the units loop.  The slab is cut here, by output samples: the units loop runs it as one and
+        // does not cut it again by its intermediate spans, which would leave a short second slab behind every full one
         MRC_HIP(h, b.reverbDry.reserve(sizeof(double) * (size_t)(nT * nch * Wd)));
-        ident.resize((size_t)nT + 1);
-        starts.resize((size_t)nT);
-        ones.assign((size_t)nT, 1.0);
-        for (int64_t k = 0; k <= nT; ++k) ident[(size_t)k] = k;
-        for (int64_t k = 0; k < nT; ++k)                     // (a start that far down is below every file with or without the pre-roll)
-            starts[(size_t)k] = start[u0 + k] < INT64_MIN + Lpre ? INT64_MIN : start[u0 + k] - Lpre;
-        const BandArgs slabBands{n_bands, edge_hz, band_gain ? band_gain + u0 * n_bands : nullptr};
-        const RatioArgs slabRatios{n_ratios, ratio_up, ratio_down, ratio_of + u0};
-        // (the slab is cut here, by output samples: the inner call does not cut it again by its intermediate spans, which
-        // would leave a short second slab behind every full one)
-        OneSlabScope scope(h);
-        MRC_TRY(decode_window_rows(s, fn, rate_divisor, mix, 1, 1, zeros, rolloff, n_bands == 0 ? nullptr : &slabBands, nT, ident.data(),
-                                   file + u0, starts.data(), ones.data(), Wd, nch, MRC_WINDOW_F64, b.reverbDry.p, stream, &slabRatios));
-        for (int i = 0; i < 4; ++i) { stats[i] += s->stats[i]; ms[i] += s->ms[i]; }
+        MRC_TRY(units_loop(s, c, WindowRun{u0, u0 + nT, Wd, MRC_WINDOW_F64, b.reverbDry.p, 0, Lpre, true}));
 
         // ---- the records (one H2D copy): terms | the rows' term offsets | sources
         int64_t nConv = 0, nSpec = 0, maxSeg = 0;
@@ -1463,15 +1459,15 @@ int decode_window_reverb(mrc_pac_store* s, int rate_divisor, int mix, int n_rati
         long long* rowTerms = (long long*)(pin + oRows);
         ReverbSource* src = (ReverbSource*)(pin + oSrc);
         for (int64_t r = 0; r <= nRows; ++r) rowTerms[r] = term_offset[first + r] - u0;
-        for (int64_t k = 0, c = 0, spec = 0; k < nT; ++k) {
+        for (int64_t k = 0, conv = 0, spec = 0; k < nT; ++k) {
             const int64_t base = k * nch * Wd, v = ir_of[u0 + k];
             if (v < 0) {
-                terms[k] = ReverbTerm{base + Lpre, -1, 0, 0, 0, gain[u0 + k]};
+                terms[k] = ReverbTerm{base + Lpre, -1, 0, 0, 0, q.gain[u0 + k]};
                 continue;
             }
             const int64_t len = s->irLen[(size_t)v], P = (len + kRevB - 1) / kRevB, nSeg = M + P - 1;
-            terms[k] = ReverbTerm{base + Lpre, spec, s->irPart[(size_t)v], (int)P, 0, gain[u0 + k]};
-            src[c++] = ReverbSource{base, nch == 2 ? base + Wd : -1, Lpre - P * kRevB, Lpre - (len - 1), Wd, spec, (int)nSeg, (int)kRevN};
+            terms[k] = ReverbTerm{base + Lpre, spec, s->irPart[(size_t)v], (int)P, 0, q.gain[u0 + k]};
+            src[conv++] = ReverbSource{base, nch == 2 ? base + Wd : -1, Lpre - P * kRevB, Lpre - (len - 1), Wd, spec, (int)nSeg, (int)kRevN};
             spec += nSeg;
         }
         // ---- device: forward transforms of the convolved terms' segments, then the rows
@@ -1486,24 +1482,32 @@ int decode_window_reverb(mrc_pac_store* s, int rate_divisor, int mix, int n_rati
                                       b.reverbTw.as<double2>(), outSlab, st));
         MRC_HIP(h, hipEventRecord(b.reverbEv[2], st));
         MRC_HIP(h, hipStreamSynchronize(st));                // (the staging is written again by the next slab)
-        for (int i = 0; i < 2; ++i) {
-            double t = 0.0;
-            MRC_HIP(h, b.reverbEv.elapsed(i, i + 1, &t));
-            reverbMs[i] += t;
-        }
+        MRC_TRY(add_elapsed(h, b.reverbEv, kReverbSpans, 2, s->reverbMs));
     }
     MRC_HIP(h, hipStreamSynchronize(st));
-    for (int i = 0; i < 4; ++i) { s->stats[i] = stats[i]; s->ms[i] = ms[i]; }
-    s->ms[3] += reverbMs[0] + reverbMs[1];
-    s->reverbMs[0] = reverbMs[0];
-    s->reverbMs[1] = reverbMs[1];
     return MRC_OK;
 }
 
-// mrc_pac_store_stft_window: a slab loop AROUND the reverb entry.  Per slab of whole rows that entry writes the rows as
-// MRC_WINDOW_F64 over L = (n_frames - 1) hop + n_fft samples into StoreBufs::stftRows (its own dry-term scratch is in use
-// underneath), then stft_kernel (mrc_kernels_stft.hip) frames and transforms them on the same stream.  The twiddles, the frame
-// window and the bank's supports and weights go up once per call.
+// A window call from its request to its statistics: the totals zeroed, the one check, the loop of the request's kind over all
+// its rows under the handle's slab limit, and the reverb kernels' time counted into ms[3] once.
+int window_call(mrc_pac_store* s, const WindowRequest& q, int64_t window, int format, void* out) {
+    MRC_TRY(store_alive(s, q.fn));
+    const bool reverb = q.kind == WindowRequest::kReverb;
+    reset_stats(s);
+    if (reverb) s->reverbMs[0] = s->reverbMs[1] = 0.0;
+    CheckedWindows c;
+    MRC_TRY(check_windows(s, q, window, format, out, &c));
+    if (c.empty) return MRC_OK;
+    const WindowRun all{0, q.nItems, window, format, out, s->h->storeSlabSamples};
+    MRC_TRY(reverb ? reverb_loop(s, c, all) : units_loop(s, c, all));
+    if (reverb) s->ms[3] += s->reverbMs[0] + s->reverbMs[1];
+    return MRC_OK;
+}
+
+// The STFT loop: per slab of whole rows the reverb loop writes the rows as MRC_WINDOW_F64 over L = (n_frames - 1) hop + n_fft
+// samples into StoreBufs::stftRows (its own dry-term scratch is in use underneath), then stft_kernel (mrc_kernels_stft.hip)
+// frames and transforms them on the same stream.  The twiddles, the frame window and the bank's supports and weights go up once
+// per call.
 const char* const kStft = "mrc_pac_store_stft_window";
 
 // exp(-2 pi i t / n) for 0 <= t < n from long double, the quadrant taken out first: the axes are exact
@@ -1517,16 +1521,57 @@ void stft_twiddles(int n, double2* w) {
     }
 }
 
-int stft_window(mrc_pac_store* s, int rate_divisor, int mix, int n_ratios, const int32_t* ratio_up, const int32_t* ratio_down, int zeros,
-                double rolloff, int n_bands, const double* edge_hz, const double* band_gain, int64_t n_items,
-                const int64_t* term_offset, const int64_t* file, const int64_t* start, const double* gain, const int32_t* ratio_of,
-                const int32_t* ir_of, int n_fft, const double* frame_window, int64_t n_frames, int64_t hop, int mode, int n_filters,
-                const double* bank, int n_channels_out, int format, void* out, void* stream) {
-    const char* const fn = kStft;
+// rows [run.first, run.last) of the checked request through stft_kernel: P holds the call's tables and sizes, run.window is
+// P.L and run.out the first row's output
+constexpr int kStftSpans[1][2] = {{0, 1}};                   // StoreBufs::stftEv: stft_kernel
+int stft_loop(mrc_pac_store* s, const CheckedWindows& c, StftParams P, const WindowRun& run) {
+    mrc_handle* h = s->h;
+    StoreBufs& b = h->store;
+    MRC_HIP(h, b.stftEv.create());
+    hipStream_t st = pick_stream(h, c.q.stream);
+    DrainGuard drain{{st, nullptr, nullptr}};
+    const int nch = P.nch;
+    const int64_t L = run.window, nOut = P.mode == MRC_STFT_BANK ? P.nFilters : P.nFft / 2 + 1;
+    const size_t rowBytes = (size_t)nch * (size_t)nOut * (size_t)P.nFrames * (P.format == MRC_WINDOW_F32 ? 4 : 8) * (P.mode == MRC_STFT_COMPLEX ? 2 : 1);
+    const int64_t slab = run.slab, rowCap = std::max<int64_t>(1, 0x7fffffffLL / (nch * P.nFrames));
+    for (int64_t first = run.first, last; first < run.last; first = last) {   // rows [first, last)
+        last = first + 1;
+        while (last < run.last && last - first < rowCap && (slab == 0 || (last + 1 - first) * L <= slab)) ++last;
+        const int64_t nRows = last - first;
+        MRC_HIP(h, b.stftRows.reserve(sizeof(double) * (size_t)(nRows * nch * L)));
+        // (the slab is cut here, by the rows' samples: the reverb loop runs it as one slab of its own)
+        MRC_TRY(reverb_loop(s, c, WindowRun{first, last, L, MRC_WINDOW_F64, b.stftRows.p, 0}));
+        P.rows = b.stftRows.as<double>();
+        P.out = (unsigned char*)run.out + (size_t)(first - run.first) * rowBytes;
+        P.nRows = (int)nRows;
+        MRC_HIP(h, hipEventRecord(b.stftEv[0], st));
+        MRC_HIP(h, launch_stft(P, st));
+        MRC_HIP(h, hipEventRecord(b.stftEv[1], st));
+        MRC_HIP(h, hipStreamSynchronize(st));
+        MRC_TRY(add_elapsed(h, b.stftEv, kStftSpans, 1, &s->stftMs));
+    }
+    return MRC_OK;
+}
+
+struct StftArgs {                                            // the entry's own arguments, as the header names them
+    int n_fft;
+    const double* frame_window;
+    int64_t n_frames, hop;
+    int mode, n_filters;
+    const double* bank;
+};
+// mrc_pac_store_stft_window from its request: the call's own arguments are refused first, then the request's (check_windows);
+// the tables go up, the loop runs over all rows under the handle's slab limit, stft_kernel's time is counted into ms[3] once
+int stft_call(mrc_pac_store* s, const WindowRequest& q, const StftArgs& a, int format, void* out) {
+    const char* const fn = q.fn;
     MRC_TRY(store_alive(s, fn));
     mrc_handle* h = s->h;
     const std::string w = fn;
-    s->stftMs = 0.0;
+    const int n_fft = a.n_fft, mode = a.mode, n_filters = a.n_filters, n_channels_out = q.nChannelsOut;
+    const int64_t n_frames = a.n_frames, hop = a.hop;
+    const double *const frame_window = a.frame_window, *const bank = a.bank;
+    reset_stats(s);
+    s->stftMs = s->reverbMs[0] = s->reverbMs[1] = 0.0;
     // ---- this call's own arguments
     int nRad = 0;
     if (n_fft < 16 || n_fft > MRC_MAX_STFT_POINTS || (n_fft & 1) || stft_radices(n_fft / 2, &nRad) == 0)
@@ -1556,37 +1601,28 @@ int stft_window(mrc_pac_store* s, int rate_divisor, int mix, int n_ratios, const
     } else if (n_filters != 0 || bank) {
         return fail(h, MRC_ERR_INVALID, w + ": n_filters must be 0 and bank NULL unless mode is MRC_STFT_BANK");
     }
-    // ---- every check of the reverb entry, made by that entry at window 0: nothing is launched
-    MRC_TRY(decode_window_reverb(s, rate_divisor, mix, n_ratios, ratio_up, ratio_down, zeros, rolloff, n_bands, edge_hz, band_gain, n_items,
-                                 term_offset, file, start, gain, ratio_of, ir_of, 0, n_channels_out, MRC_WINDOW_F64, out, stream, fn));
-    if (n_items == 0 || n_frames == 0) return MRC_OK;
-    if (!out) return fail(h, MRC_ERR_INVALID, w + ": out is NULL");
-    const int64_t L = (n_frames - 1) * hop + n_fft;
-    // the reverb entry's bound on window + pre-roll, which its call at window 0 cannot reach (ir_of has been checked by it)
-    int64_t Lpre = 0;
-    for (int64_t k = 0; k < term_offset[n_items]; ++k)
-        if (ir_of[k] >= 0) Lpre = std::max(Lpre, s->irLen[(size_t)ir_of[k]] - 1);
-    if (L + Lpre > kMaxL)
-        return fail(h, MRC_ERR_INVALID, w + ": L + the longest impulse response named - 1 = " + std::to_string(L + Lpre) + " exceeds 2^40");
+    // ---- the request's, with the rows' length L as its window
+    const int64_t L = n_frames == 0 ? 0 : (n_frames - 1) * hop + n_fft;
+    CheckedWindows c;
+    MRC_TRY(check_windows(s, q, L, MRC_WINDOW_F64, out, &c));
+    if (c.empty) return MRC_OK;
 
     MRC_HIP(h, hipSetDevice(h->device));
     StoreBufs& b = h->store;
-    MRC_HIP(h, b.stftEv.create());
-    hipStream_t st = pick_stream(h, stream);
-    DrainGuard drain{{st, nullptr, nullptr}};
+    hipStream_t st = pick_stream(h, q.stream);
     // ---- the tables (one copy): twiddles | frame window | weights on the supports | lo, hi, offset per filter
     const int nF = mode == MRC_STFT_BANK ? n_filters : 0;
     std::vector<int32_t> tab((size_t)(3 * nF));
     std::vector<double> weights;
-    for (int q = 0; q < nF; ++q) {
-        const double* row = bank + (size_t)q * nBins;
+    for (int f = 0; f < nF; ++f) {
+        const double* row = bank + (size_t)f * nBins;
         int lo = 0, hi = nBins;
         while (lo < nBins && row[lo] == 0.0) ++lo;
         while (hi > lo && row[hi - 1] == 0.0) --hi;
         if (lo == nBins) lo = hi = 0;
-        tab[(size_t)q] = lo;
-        tab[(size_t)(nF + q)] = hi;
-        tab[(size_t)(2 * nF + q)] = (int32_t)weights.size();
+        tab[(size_t)f] = lo;
+        tab[(size_t)(nF + f)] = hi;
+        tab[(size_t)(2 * nF + f)] = (int32_t)weights.size();
         weights.insert(weights.end(), row + lo, row + hi);
     }
     StageLayout lay(256);
@@ -1609,43 +1645,8 @@ int stft_window(mrc_pac_store* s, int rate_divisor, int mix, int n_ratios, const
     P.bankW = (const double*)(dtab + oW);
     P.L = L; P.nFrames = n_frames; P.hop = hop; P.radices = radices;
     P.nch = n_channels_out; P.nFft = n_fft; P.nRad = nRad; P.mode = mode; P.format = format; P.nFilters = nF;
-    const int nch = n_channels_out;
-    const int64_t nOut = mode == MRC_STFT_BANK ? n_filters : nBins;
-    const size_t rowBytes = (size_t)nch * (size_t)nOut * (size_t)n_frames * (format == MRC_WINDOW_F32 ? 4 : 8) * (mode == MRC_STFT_COMPLEX ? 2 : 1);
-    const int64_t slab = h->storeSlabSamples, rowCap = std::max<int64_t>(1, 0x7fffffffLL / (nch * n_frames));
-    int64_t stats[4] = {0, 0, 0, 0};
-    double ms[4] = {0, 0, 0, 0}, reverbMs[2] = {0, 0}, stftMs = 0.0;
-    std::vector<int64_t> offs;
-    for (int64_t first = 0, last; first < n_items; first = last) {   // rows [first, last), their terms from u0
-        last = first + 1;
-        while (last < n_items && last - first < rowCap && (slab == 0 || (last + 1 - first) * L <= slab)) ++last;
-        const int64_t nRows = last - first, u0 = term_offset[first];
-        MRC_HIP(h, b.stftRows.reserve(sizeof(double) * (size_t)(nRows * nch * L)));
-        offs.resize((size_t)nRows + 1);
-        for (int64_t r = 0; r <= nRows; ++r) offs[(size_t)r] = term_offset[first + r] - u0;
-        // (the slab is cut here, by the rows' samples: the inner entry is told to run it as one slab of its own)
-        MRC_TRY(decode_window_reverb(s, rate_divisor, mix, n_ratios, ratio_up, ratio_down, zeros, rolloff, n_bands, edge_hz,
-                                     band_gain ? band_gain + u0 * n_bands : nullptr, nRows, offs.data(), file ? file + u0 : nullptr,
-                                     start ? start + u0 : nullptr, gain ? gain + u0 : nullptr, ratio_of ? ratio_of + u0 : nullptr,
-                                     ir_of ? ir_of + u0 : nullptr, L, nch, MRC_WINDOW_F64, b.stftRows.p, stream, fn, true));
-        for (int i = 0; i < 4; ++i) { stats[i] += s->stats[i]; ms[i] += s->ms[i]; }
-        for (int i = 0; i < 2; ++i) reverbMs[i] += s->reverbMs[i];
-        P.rows = b.stftRows.as<double>();
-        P.out = (unsigned char*)out + (size_t)first * rowBytes;
-        P.nRows = (int)nRows;
-        MRC_HIP(h, hipEventRecord(b.stftEv[0], st));
-        MRC_HIP(h, launch_stft(P, st));
-        MRC_HIP(h, hipEventRecord(b.stftEv[1], st));
-        MRC_HIP(h, hipStreamSynchronize(st));
-        double t = 0.0;
-        MRC_HIP(h, b.stftEv.elapsed(0, 1, &t));
-        stftMs += t;
-    }
-    for (int i = 0; i < 4; ++i) { s->stats[i] = stats[i]; s->ms[i] = ms[i]; }
-    s->ms[3] += stftMs;
-    s->reverbMs[0] = reverbMs[0];
-    s->reverbMs[1] = reverbMs[1];
-    s->stftMs = stftMs;
+    MRC_TRY(stft_loop(s, c, P, WindowRun{0, q.nItems, L, format, out, h->storeSlabSamples}));
+    s->ms[3] += s->reverbMs[0] + s->reverbMs[1] + s->stftMs;
     return MRC_OK;
 }
 
@@ -1669,8 +1670,13 @@ int mrc_pac_store_decode_window_reverb(mrc_pac_store* s, int rate_divisor, int m
                                        const double* band_gain, int64_t n_items, const int64_t* term_offset, const int64_t* file,
                                        const int64_t* start, const double* gain, const int32_t* ratio_of, const int32_t* ir_of,
                                        int64_t window, int n_channels_out, int format, void* out, void* stream) {
-    return decode_window_reverb(s, rate_divisor, mix, n_ratios, ratio_up, ratio_down, zeros, rolloff, n_bands, edge_hz, band_gain, n_items,
-                                term_offset, file, start, gain, ratio_of, ir_of, window, n_channels_out, format, out, stream);
+    WindowRequest q{kWinReverb, WindowRequest::kReverb};
+    q.rateDivisor = rate_divisor; q.mix = mix; q.zeros = zeros; q.rolloff = rolloff;
+    q.ratioList = true; q.nRatios = n_ratios; q.ratioUp = ratio_up; q.ratioDown = ratio_down; q.ratioOf = ratio_of;
+    q.banded = n_bands != 0; q.nBands = n_bands; q.edgeHz = edge_hz; q.bandGain = band_gain;
+    q.nItems = n_items; q.termOffset = term_offset; q.file = file; q.start = start; q.gain = gain; q.irOf = ir_of;
+    q.nChannelsOut = n_channels_out; q.stream = stream;
+    return window_call(s, q, window, format, out);
 }
 
 int mrc_pac_store_reverb_ms(mrc_pac_store* s, double* ms) {
@@ -1685,9 +1691,83 @@ int mrc_pac_store_stft_window(mrc_pac_store* s, int rate_divisor, int mix, int n
                               const int64_t* start, const double* gain, const int32_t* ratio_of, const int32_t* ir_of, int n_fft,
                               const double* frame_window, int64_t n_frames, int64_t hop, int mode, int n_filters, const double* bank,
                               int n_channels_out, int format, void* out, void* stream) {
-    return stft_window(s, rate_divisor, mix, n_ratios, ratio_up, ratio_down, zeros, rolloff, n_bands, edge_hz, band_gain, n_items,
-                       term_offset, file, start, gain, ratio_of, ir_of, n_fft, frame_window, n_frames, hop, mode, n_filters, bank,
-                       n_channels_out, format, out, stream);
+    WindowRequest q{kStft, WindowRequest::kStft};
+    q.rateDivisor = rate_divisor; q.mix = mix; q.zeros = zeros; q.rolloff = rolloff;
+    q.ratioList = true; q.nRatios = n_ratios; q.ratioUp = ratio_up; q.ratioDown = ratio_down; q.ratioOf = ratio_of;
+    q.banded = n_bands != 0; q.nBands = n_bands; q.edgeHz = edge_hz; q.bandGain = band_gain;
+    q.nItems = n_items; q.termOffset = term_offset; q.file = file; q.start = start; q.gain = gain; q.irOf = ir_of;
+    q.nChannelsOut = n_channels_out; q.stream = stream;
+    return stft_call(s, q, StftArgs{n_fft, frame_window, n_frames, hop, mode, n_filters, bank}, format, out);
+}
+
+int mrc_pac_store_decode_window(mrc_pac_store* s, int64_t n_items, const int64_t* file, const int64_t* start, int64_t window,
+                                int n_channels_out, int format, void* out, void* stream) {
+    WindowRequest q{kWin, WindowRequest::kItems};
+    q.nItems = n_items; q.file = file; q.start = start; q.nChannelsOut = n_channels_out; q.stream = stream;
+    return window_call(s, q, window, format, out);
+}
+
+int mrc_pac_store_decode_window_reduced(mrc_pac_store* s, int rate_divisor, int64_t n_items, const int64_t* file,
+                                        const int64_t* start, int64_t window, int n_channels_out, int format, void* out,
+                                        void* stream) {
+    WindowRequest q{kWinReduced, WindowRequest::kItems};
+    q.rateDivisor = rate_divisor;
+    q.nItems = n_items; q.file = file; q.start = start; q.nChannelsOut = n_channels_out; q.stream = stream;
+    return window_call(s, q, window, format, out);
+}
+
+int mrc_pac_store_decode_window_mix(mrc_pac_store* s, int rate_divisor, int mix, int64_t n_items, const int64_t* file,
+                                    const int64_t* start, int64_t window, int format, void* out, void* stream) {
+    WindowRequest q{kWinMix, WindowRequest::kItems};
+    q.rateDivisor = rate_divisor; q.mix = mix; q.mixAllowed = kMixOfOne;
+    q.nItems = n_items; q.file = file; q.start = start; q.nChannelsOut = 1; q.stream = stream;
+    return window_call(s, q, window, format, out);
+}
+
+int mrc_pac_store_decode_window_resampled(mrc_pac_store* s, int rate_divisor, int mix, int up, int down, int zeros, double rolloff,
+                                          int64_t n_items, const int64_t* file, const int64_t* start, int64_t window,
+                                          int n_channels_out, int format, void* out, void* stream) {
+    WindowRequest q{kWinResampled, WindowRequest::kItems};
+    q.rateDivisor = rate_divisor; q.mix = mix;
+    q.resampled = true; q.up = up; q.down = down; q.zeros = zeros; q.rolloff = rolloff;
+    q.nItems = n_items; q.file = file; q.start = start; q.nChannelsOut = n_channels_out; q.stream = stream;
+    return window_call(s, q, window, format, out);
+}
+
+int mrc_pac_store_decode_window_sum(mrc_pac_store* s, int rate_divisor, int mix, int up, int down, int zeros, double rolloff,
+                                    int64_t n_items, const int64_t* term_offset, const int64_t* file, const int64_t* start,
+                                    const double* gain, int64_t window, int n_channels_out, int format, void* out, void* stream) {
+    WindowRequest q{kWinSum, WindowRequest::kRows};
+    q.rateDivisor = rate_divisor; q.mix = mix; q.up = up; q.down = down; q.zeros = zeros; q.rolloff = rolloff;
+    q.nItems = n_items; q.termOffset = term_offset; q.file = file; q.start = start; q.gain = gain;
+    q.nChannelsOut = n_channels_out; q.stream = stream;
+    return window_call(s, q, window, format, out);
+}
+
+int mrc_pac_store_decode_window_shaped(mrc_pac_store* s, int rate_divisor, int mix, int up, int down, int zeros, double rolloff,
+                                       int n_bands, const double* edge_hz, const double* band_gain, int64_t n_items,
+                                       const int64_t* term_offset, const int64_t* file, const int64_t* start, const double* gain,
+                                       int64_t window, int n_channels_out, int format, void* out, void* stream) {
+    WindowRequest q{kWinShaped, WindowRequest::kRows};
+    q.rateDivisor = rate_divisor; q.mix = mix; q.up = up; q.down = down; q.zeros = zeros; q.rolloff = rolloff;
+    q.banded = true; q.nBands = n_bands; q.edgeHz = edge_hz; q.bandGain = band_gain;
+    q.nItems = n_items; q.termOffset = term_offset; q.file = file; q.start = start; q.gain = gain;
+    q.nChannelsOut = n_channels_out; q.stream = stream;
+    return window_call(s, q, window, format, out);
+}
+
+int mrc_pac_store_decode_window_speeds(mrc_pac_store* s, int rate_divisor, int mix, int n_ratios, const int32_t* ratio_up,
+                                       const int32_t* ratio_down, int zeros, double rolloff, int n_bands, const double* edge_hz,
+                                       const double* band_gain, int64_t n_items, const int64_t* term_offset, const int64_t* file,
+                                       const int64_t* start, const double* gain, const int32_t* ratio_of, int64_t window,
+                                       int n_channels_out, int format, void* out, void* stream) {
+    WindowRequest q{kWinSpeeds, WindowRequest::kRows};
+    q.rateDivisor = rate_divisor; q.mix = mix; q.zeros = zeros; q.rolloff = rolloff;
+    q.ratioList = true; q.nRatios = n_ratios; q.ratioUp = ratio_up; q.ratioDown = ratio_down; q.ratioOf = ratio_of;
+    q.banded = n_bands != 0; q.nBands = n_bands; q.edgeHz = edge_hz; q.bandGain = band_gain;
+    q.nItems = n_items; q.termOffset = term_offset; q.file = file; q.start = start; q.gain = gain;
+    q.nChannelsOut = n_channels_out; q.stream = stream;
+    return window_call(s, q, window, format, out);
 }
 
 int mrc_pac_store_stft_ms(mrc_pac_store* s, double* ms) {
@@ -1698,7 +1778,7 @@ int mrc_pac_store_stft_ms(mrc_pac_store* s, double* ms) {
 
 int mrc_pac_store_block_energy(mrc_pac_store* s, int rate_divisor, int mix, int64_t n_sel, const int64_t* file,
                                int64_t* entry_offset, int64_t entry_cap, int64_t* entry_block, double* energy, void* stream) {
-    return block_energy(s, rate_divisor, mix, n_sel, file, entry_offset, entry_cap, entry_block, energy, stream);
+    return block_energy(s, BlockEnergyRequest{rate_divisor, mix, n_sel, file, entry_offset, entry_cap, entry_block, energy, stream});
 }
 
 int mrc_synthesis_shape(int a, int b, int rate_divisor) {

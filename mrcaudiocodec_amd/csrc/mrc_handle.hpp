@@ -227,28 +227,38 @@ struct NmrBufs {
     double ms[4] = {0, 0, 0, 0};
 };
 
-// Windows of resident `.pac` files (mrc_pac_store_decode_window, mrc_api_store.cpp): the workspace of one slab, reused from
-// slab to slab and from call to call.  The parsing tables, the error word and its page-locked copy are DecodeBufs' (pac_parse).
+// Windows of resident `.pac` files (mrc_pac_store_*, mrc_api_store.cpp): the workspace of one slab of each of its loops, reused
+// from slab to slab and from call to call -- the loops nest (STFT over reverb over units), so each has buffers of its own.  The
+// parsing tables, the error word and its page-locked copy are DecodeBufs' (pac_parse).
 struct ResampleTable {               // the filter of one (up, down, zeros, rolloff), uploaded once (mrc_resample_taps.hpp)
     DevBuf taps;                     // [2 W][up]
     int W = 0, evenOdd = 0, skew = 0;   // half width; resample_out_kernel's LDS layout (resample_lds_layout)
     int skewNatural = 0;             // the better skew under the natural lane map (resample_multi_sum_out_kernel)
 };
+struct StoreNeed { int64_t item, file, block; };   // a block a slab must parse; item: index in the slab
 struct StoreBufs {
     std::map<std::tuple<int, int, int, double>, ResampleTable> resample;   // mrc_pac_store_decode_window_resampled's filters
+    // The host planner's scratch, cleared per slab and kept between slabs and calls: megabytes at thousands of items, which
+    // a call would otherwise allocate and free each time -- and whether the C library then gives the pages back and faults
+    // them in again at the next call depends on the history of the process, not on the call.
+    std::vector<StoreNeed> needs;
+    std::vector<WindowItem> items;
+    std::vector<BandItem> bandItems;
+    std::vector<int64_t> firstTile;
+    std::vector<EnergyEntry> entries[kUnpackGroups];
     DevBuf in;                       // one H2D copy per slab (a StageLayout): plan | group descriptors | block offsets | items
                                      // (| the items' output starts: decode_window_resampled)
     DevBuf groups;                   // dense per-(shape, kind) arrays of the parsed chunks
     DevBuf planes;                   // float64, window + 4 n_mdct_lines samples per item and decoded channel
     PinnedBuf pinIn;                 // written again only after the slab that read it has been synchronised
     EventSet<6> ev;                  // start | plan uploaded | unpacked ; synthesis starts | planes done | windows written
-    // mrc_pac_store_decode_window_reverb: a slab's dry terms [term][channel][window + pre-roll] (float64, written by the
-    // existing calls), the spectra of its convolved terms' segments, the term and source records (one H2D copy per slab from
+    // the reverb loop (reverb_loop): a slab's dry terms [term][channel][window + pre-roll] (float64, written by the units
+    // loop), the spectra of its convolved terms' segments, the term and source records (one H2D copy per slab from
     // their page-locked staging), the twiddle quadrant of the N-point transform (once per handle)
     DevBuf reverbDry, reverbSpec, reverbIn, reverbTw;
     PinnedBuf reverbPin;
     EventSet<3> reverbEv;            // forward transforms start | fold starts | windows written
-    // mrc_pac_store_stft_window: a slab's rows [row][channel][L] (float64, written by the reverb entry, whose own scratch is
+    // the STFT loop (stft_loop): a slab's rows [row][channel][L] (float64, written by the reverb loop, whose own scratch is
     // in use underneath), and the call's tables in one allocation: twiddles | frame window | bank weights | bank supports
     DevBuf stftRows, stftTab;
     EventSet<2> stftEv;              // stft_kernel starts | ended
@@ -389,7 +399,9 @@ struct mrc_pac_store {
     // 32 bytes per tap, rounded up to whole partitions), and per response its length and first partition
     mrc::DevBuf irBank;
     std::vector<int64_t> irLen, irPart;
-    double reverbMs[2] = {0, 0};     // last decode_window_reverb: reverb_forward_kernel | reverb_fold_kernel
+    // The statistics of the last call.  The store is the accumulator: a window entry zeroes what it reports, every slab of
+    // every loop it runs adds to it, and the reverb and STFT kernels' times are counted into ms[3] once, at the end.
+    double reverbMs[2] = {0, 0};     // last decode_window_reverb or stft_window: reverb_forward_kernel | reverb_fold_kernel
     double stftMs = 0;               // last stft_window: stft_kernel, summed over the slabs
     int64_t stats[4] = {0, 0, 0, 0}; // last decode_window: chunks parsed, decode_kernel launches, slabs, plan bytes uploaded
     double ms[4] = {0, 0, 0, 0};     // ... plan upload | unpack | synthesis | window_out_kernel (resampled: resample_out_kernel)

@@ -104,6 +104,7 @@ waveform tensor in between:
         e = store.stft_window(files, starts, 98, 160, 400, bank=bank, output="bank", rate_divisor=2, mix="mid", resample=(2, 3))
         logmel = torch.log(e.clamp_min(1e-10))                                 # [len(files)][1][80][98]
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -684,6 +685,69 @@ def _formats():
     return {torch.int16: _lib.MRC_WINDOW_PCM16, torch.float32: _lib.MRC_WINDOW_F32, torch.float64: _lib.MRC_WINDOW_F64}
 
 
+class WindowRows(collections.namedtuple("WindowRows", "rate_divisor mix resample channels bands speeds irs offsets files starts gains")):
+    """The checked row arguments of a window call: rate_divisor an int, mix None or its MRC_MIX_* value, resample None or
+    (up, down, zeros, rolloff), channels as given (1 under a mix), bands None or (edges, gains [terms][n_bands]), speeds None or
+    (ratios, zeros, rolloff, index int32 [terms]), irs None or int32 [terms], offsets int64 [rows + 1], files, starts and gains
+    flat and contiguous.  decode_window's items are rows of one term each at gain 1.0."""
+    __slots__ = ()
+
+
+def window_entry(store, rows, caller, window, channels, fmt, out, stream, stft=None):
+    """The library entry a window call goes to and its arguments -> (name, args, keep): the ONE place that names the
+    mrc_pac_store_decode_window* entries and mrc_pac_store_stft_window.  rows: a WindowRows; caller: "decode_window",
+    "decode_window_sum" or "stft_window"; store, out and stream: the store's pointer, the output's and the stream as ints or
+    None (no device is needed to ask); stft: stft_window's (n_fft, window array, n_frames, hop, mode, matrix or None).  keep
+    holds the arrays made here whose pointers args carries.  The entry per combination, first match:
+        stft_window                          mrc_pac_store_stft_window (ratios default to the one base ratio, ir_of to -1)
+        ir_index given                       ..._reverb
+        speeds given                         ..._speeds
+        band_gains given                     ..._shaped
+        decode_window_sum                    ..._sum
+        decode_window: resample given        ..._resampled
+                       mix given             ..._mix
+                       rate_divisor > 1      ..._reduced
+                       else                  mrc_pac_store_decode_window"""
+    pad = lambda a: a.ctypes.data if a.size else None
+    mix = _lib.MRC_MIX_EACH if rows.mix is None else rows.mix
+    n = rows.offsets.size - 1
+    terms = (n, rows.offsets.ctypes.data, pad(rows.files), pad(rows.starts), pad(rows.gains))
+    tail = (window, channels, fmt, out or None, stream or None)
+    up, down, zeros, rolloff = rows.resample if rows.resample is not None else (1, 1, RESAMPLE_ZEROS, RESAMPLE_ROLLOFF)
+    if rows.bands is None:
+        bands = (0, None, None)
+    else:
+        bands = (rows.bands[0].size - 1, rows.bands[0].ctypes.data, pad(rows.bands[1]))
+    if stft is not None or rows.irs is not None or rows.speeds is not None:      # the entries that take a list of ratios
+        ratios, zeros, rolloff, index = rows.speeds or ([(up, down)], zeros, rolloff, np.zeros(rows.files.size, np.int32))
+        ups = np.ascontiguousarray([r[0] for r in ratios], dtype=np.int32)
+        downs = np.ascontiguousarray([r[1] for r in ratios], dtype=np.int32)
+        irs = rows.irs if rows.irs is not None else np.full(rows.files.size, -1, np.int32)
+        head = (store, rows.rate_divisor, mix, len(ratios), ups.ctypes.data, downs.ctypes.data, zeros, rolloff) + bands + terms + (pad(index),)
+        keep = (ups, downs, index, irs)
+        if stft is not None:
+            n_fft, frame_window, n_frames, hop, mode, matrix = stft
+            own = (n_fft, frame_window.ctypes.data, n_frames, hop, mode, 0 if matrix is None else matrix.shape[0],
+                   None if matrix is None else matrix.ctypes.data)
+            return "mrc_pac_store_stft_window", head + (pad(irs),) + own + tail[1:], keep
+        if rows.irs is not None:
+            return "mrc_pac_store_decode_window_reverb", head + (pad(irs),) + tail, keep
+        return "mrc_pac_store_decode_window_speeds", head + tail, keep
+    single = (store, rows.rate_divisor, mix, up, down, zeros, rolloff)
+    if rows.bands is not None:
+        return "mrc_pac_store_decode_window_shaped", single + bands + terms + tail, ()
+    if caller == "decode_window_sum":
+        return "mrc_pac_store_decode_window_sum", single + terms + tail, ()
+    items = (n, pad(rows.files), pad(rows.starts))
+    if rows.resample is not None:
+        return "mrc_pac_store_decode_window_resampled", single + items + tail, ()
+    if rows.mix is not None:
+        return "mrc_pac_store_decode_window_mix", (store, rows.rate_divisor, mix) + items + (window,) + tail[2:], ()
+    if rows.rate_divisor > 1:
+        return "mrc_pac_store_decode_window_reduced", (store, rows.rate_divisor) + items + tail, ()
+    return "mrc_pac_store_decode_window", (store,) + items + tail, ()
+
+
 class PacStore:
     """bufs: a list of bytes-like `.pac` files carrying the handle's codec parameters, mono and stereo mixed at will.
     .n_channels, .n_samples (per channel, as Handle.decode_pac_pcm16 returns them), .n_blocks: one NumPy value per file;
@@ -748,22 +812,18 @@ class PacStore:
                 raise ValueError("n_samples_resampled: %s must be a positive int, got %r" % (name, v))
         return -((-n * int(up)) // int(down))
 
-    def _window_out(self, what, n, files, window, channels, dtype, out, stream):
-        """the output side of decode_window and decode_window_sum -> (format, channels, out, stream): dtype (None: int16, or
-        out's), channels (None: the largest channel count among the files named), the tensor [n][channels][window] (given: it
-        must be that, else ValueError) and the stream (None: torch's current one)"""
+    def _channels_named(self, files, channels):
+        """channels, or for None the largest channel count among the files named that the store has (none: 1)"""
+        if channels is not None:
+            return channels
+        inside = files[(files >= 0) & (files < len(self))]
+        return int(self.n_channels[inside].max()) if inside.size else 1
+
+    def _out_tensor(self, what, shape, dtype, out, stream):
+        """-> (out, stream): the contiguous tensor of that shape and dtype on the handle's device (given: it must be that,
+        else ValueError) and the stream (None: torch's current one)"""
         import torch
-        if dtype is None:
-            dtype = torch.int16 if out is None else out.dtype
-        fmt = _formats().get(dtype)
-        if fmt is None:
-            raise ValueError("%s: dtype must be torch.int16, torch.float32 or torch.float64, got %s" % (what, dtype))
-        if channels is None:
-            inside = files[(files >= 0) & (files < len(self))]
-            channels = int(self.n_channels[inside].max()) if inside.size else 1
-        channels = int(channels)
         dev = torch.device("cuda", self._handle.cfg.device_id)
-        shape = (n, channels, max(window, 0))
         if out is None:
             out = torch.empty(shape, dtype=dtype, device=dev)
         elif not isinstance(out, torch.Tensor) or out.dtype != dtype or tuple(out.shape) != shape or out.device != dev \
@@ -771,7 +831,33 @@ class PacStore:
             raise ValueError("%s: out must be a contiguous %s tensor of shape %s on %s" % (what, dtype, shape, dev))
         if stream is None:
             stream = torch.cuda.current_stream(dev).cuda_stream
-        return fmt, channels, out, stream
+        return out, stream
+
+    def _out_side(self, what, files, channels, shape, dtype, out, stream, one_or_two=False):
+        """the output side of decode_window, decode_window_sum and stft_window -> (channels, out, stream): channels (None: as
+        _channels_named; one_or_two: anything but 1 or 2 is a ValueError), then _out_tensor over shape(channels)"""
+        channels = self._channels_named(files, channels)
+        if one_or_two and (not _is_int(channels) or int(channels) not in (1, 2)):
+            raise ValueError("%s: channels must be None, 1 or 2, got %r" % (what, channels))
+        channels = int(channels)
+        return (channels,) + self._out_tensor(what, shape(channels), dtype, out, stream)
+
+    def _window_out(self, what, n, files, window, channels, dtype, out, stream):
+        """decode_window's and decode_window_sum's -> (format, channels, out, stream): dtype (None: int16, or out's) and
+        _out_side over [n][channels][window]"""
+        import torch
+        if dtype is None:
+            dtype = torch.int16 if out is None else out.dtype
+        fmt = _formats().get(dtype)
+        if fmt is None:
+            raise ValueError("%s: dtype must be torch.int16, torch.float32 or torch.float64, got %s" % (what, dtype))
+        return (fmt,) + self._out_side(what, files, channels, lambda c: (n, c, max(window, 0)), dtype, out, stream)
+
+    def _call_window(self, rows, caller, window, channels, fmt, out, stream, stft=None):
+        """window_entry's choice, called (its arrays live until the call returns); -> out"""
+        name, args, _keep = window_entry(self._s, rows, caller, window, channels, fmt, out.data_ptr() if out.numel() else None, stream, stft)
+        self._handle._check(getattr(lib, name)(*args))
+        return out
 
     def _band_args(self, what, band_gains, band_edges_hz, unit_shape):
         """band_gains / band_edges_hz of a window call -> None, or (edges float64 [n_bands + 1], gains float64 [units][n_bands]);
@@ -820,38 +906,6 @@ class PacStore:
         ms = np.zeros(2, np.float64)
         self._handle._check(lib.mrc_pac_store_reverb_ms(self._s, ms.ctypes.data))
         return {"forward": float(ms[0]), "fold": float(ms[1])}
-
-    def _reverb(self, rate_divisor, mix, resample, speeds, bands, ir_index, n, offsets, files, starts, gains, window, channels, fmt,
-                out, stream):
-        """mrc_pac_store_decode_window_reverb over checked arguments; speeds None (every term at resample's ratio, None: 1 / 1)
-        or (ratios, zeros, rolloff, index [terms]), bands None or (edges, gains [terms][n_bands]), ir_index int32 [terms]"""
-        if speeds is None:
-            up, down, zeros, rolloff = resample if resample is not None else (1, 1, RESAMPLE_ZEROS, RESAMPLE_ROLLOFF)
-            speeds = ([(up, down)], zeros, rolloff, np.zeros(files.size, np.int32))
-        ratios, zeros, rolloff, index = speeds
-        ups = np.ascontiguousarray([r[0] for r in ratios], dtype=np.int32)
-        downs = np.ascontiguousarray([r[1] for r in ratios], dtype=np.int32)
-        pad = lambda a: a.ctypes.data if a.size else None
-        edges, band_gains = bands if bands is not None else (None, None)
-        self._handle._check(lib.mrc_pac_store_decode_window_reverb(
-            self._s, rate_divisor, _lib.MRC_MIX_EACH if mix is None else mix, len(ratios), ups.ctypes.data, downs.ctypes.data, zeros,
-            rolloff, 0 if bands is None else edges.size - 1, None if bands is None else edges.ctypes.data,
-            None if bands is None else pad(band_gains), n, offsets.ctypes.data, pad(files), pad(starts), pad(gains), pad(index),
-            pad(ir_index), window, channels, fmt, out.data_ptr() if out.numel() else None, stream or None))
-
-    def _speeds(self, rate_divisor, mix, speeds, bands, n, offsets, files, starts, gains, window, channels, fmt, out, stream):
-        """mrc_pac_store_decode_window_speeds over checked arguments; speeds = (ratios, zeros, rolloff, index [terms]), bands
-        None or (edges, gains [terms][n_bands])"""
-        ratios, zeros, rolloff, index = speeds
-        ups = np.ascontiguousarray([r[0] for r in ratios], dtype=np.int32)
-        downs = np.ascontiguousarray([r[1] for r in ratios], dtype=np.int32)
-        pad = lambda a: a.ctypes.data if a.size else None
-        edges, band_gains = bands if bands is not None else (None, None)
-        self._handle._check(lib.mrc_pac_store_decode_window_speeds(
-            self._s, rate_divisor, _lib.MRC_MIX_EACH if mix is None else mix, len(ratios), ups.ctypes.data, downs.ctypes.data, zeros,
-            rolloff, 0 if bands is None else edges.size - 1, None if bands is None else edges.ctypes.data,
-            None if bands is None else pad(band_gains), n, offsets.ctypes.data, pad(files), pad(starts), pad(gains), pad(index), window,
-            channels, fmt, out.data_ptr() if out.numel() else None, stream or None))
 
     def source_spans(self, starts, window, ratios, index, rate_divisor=1):
         """Where the units of decode_window(speed_factors=, speed_index=) lie in the signal at 1 / rate_divisor of the sample
@@ -943,41 +997,9 @@ class PacStore:
         speeds = self._speed_args("decode_window", resample_arg, speed_factors, speed_index, (n,))
         irs = None if ir_index is None else check_ir_index(ir_index, (n,), self._ir_lengths.size)
         fmt, channels, out, stream = self._window_out("decode_window", n, files, window, channels, dtype, out, stream)
-        if irs is not None:
-            offsets, ones = np.arange(n + 1, dtype=np.int64), np.ones(n, np.float64)
-            self._reverb(rate_divisor, mix, resample, speeds, bands, irs, n, offsets, files, starts, ones, window, channels, fmt, out,
-                         stream)
-            return out
-        if speeds is not None:
-            offsets, ones = np.arange(n + 1, dtype=np.int64), np.ones(n, np.float64)
-            self._speeds(rate_divisor, mix, speeds, bands, n, offsets, files, starts, ones, window, channels, fmt, out, stream)
-            return out
-        if bands is not None:
-            offsets, ones = np.arange(n + 1, dtype=np.int64), np.ones(n, np.float64)
-            self._shaped(rate_divisor, mix, resample, bands, n, offsets, files, starts, ones, window, channels, fmt, out, stream)
-            return out
-        tail = (n, files.ctypes.data, starts.ctypes.data, window, channels, fmt, out.data_ptr() if out.numel() else None,
-                stream or None)
-        if resample is not None:
-            self._handle._check(lib.mrc_pac_store_decode_window_resampled(
-                self._s, rate_divisor, _lib.MRC_MIX_EACH if mix is None else mix, *resample, *tail))
-        elif mix is not None:
-            self._handle._check(lib.mrc_pac_store_decode_window_mix(self._s, rate_divisor, mix, *tail[:4], *tail[5:]))
-        elif rate_divisor == 1:
-            self._handle._check(lib.mrc_pac_store_decode_window(self._s, *tail))
-        else:
-            self._handle._check(lib.mrc_pac_store_decode_window_reduced(self._s, rate_divisor, *tail))
-        return out
-
-    def _shaped(self, rate_divisor, mix, resample, bands, n, offsets, files, starts, gains, window, channels, fmt, out, stream):
-        """mrc_pac_store_decode_window_shaped over checked arguments; bands = (edges, gains [terms][n_bands])"""
-        up, down, zeros, rolloff = resample if resample is not None else (1, 1, RESAMPLE_ZEROS, RESAMPLE_ROLLOFF)
-        pad = lambda a: a.ctypes.data if a.size else None
-        edges, band_gains = bands
-        self._handle._check(lib.mrc_pac_store_decode_window_shaped(
-            self._s, rate_divisor, _lib.MRC_MIX_EACH if mix is None else mix, up, down, zeros, rolloff, edges.size - 1,
-            edges.ctypes.data, pad(band_gains), n, offsets.ctypes.data, pad(files), pad(starts), pad(gains), window, channels, fmt,
-            out.data_ptr() if out.numel() else None, stream or None))
+        rows = WindowRows(rate_divisor, mix, resample, channels, bands, speeds, irs, np.arange(n + 1, dtype=np.int64), files, starts,
+                          np.ones(n, np.float64))
+        return self._call_window(rows, "decode_window", window, channels, fmt, out, stream)
 
     def decode_window_sum(self, files, starts, gains, window, item_offsets=None, channels=None, dtype=None, out=None, stream=None,
                           rate_divisor=1, mix=None, resample=None, band_gains=None, band_edges_hz=None, speed_factors=None,
@@ -1007,32 +1029,15 @@ class PacStore:
         through a room over dry noise is one call.  It composes with resample, speed_factors / speed_index, band_gains, mix
         and rate_divisor: the response acts last, at the term's output rate.  None: this call as it always was."""
         what = "decode_window_sum"
-        rate_divisor, mix, resample, channels, bands, speeds, irs, offsets, files, starts, gains = self._sum_rows(
-            what, files, starts, gains, item_offsets, channels, rate_divisor, mix, resample, band_gains, band_edges_hz, speed_factors,
-            speed_index, ir_index)
-        n, window = offsets.size - 1, int(window)
-        fmt, channels, out, stream = self._window_out(what, n, files, window, channels, dtype, out, stream)
-        if irs is not None:
-            self._reverb(rate_divisor, mix, resample, speeds, bands, irs, n, offsets, files, starts, gains, window, channels, fmt, out,
-                         stream)
-            return out
-        if speeds is not None:
-            self._speeds(rate_divisor, mix, speeds, bands, n, offsets, files, starts, gains, window, channels, fmt, out, stream)
-            return out
-        if bands is not None:
-            self._shaped(rate_divisor, mix, resample, bands, n, offsets, files, starts, gains, window, channels, fmt, out, stream)
-            return out
-        up, down, zeros, rolloff = resample if resample is not None else (1, 1, RESAMPLE_ZEROS, RESAMPLE_ROLLOFF)
-        pad = lambda a: a.ctypes.data if a.size else None
-        self._handle._check(lib.mrc_pac_store_decode_window_sum(
-            self._s, rate_divisor, _lib.MRC_MIX_EACH if mix is None else mix, up, down, zeros, rolloff, n, offsets.ctypes.data,
-            pad(files), pad(starts), pad(gains), window, channels, fmt, out.data_ptr() if out.numel() else None, stream or None))
-        return out
+        rows = self._sum_rows(what, files, starts, gains, item_offsets, channels, rate_divisor, mix, resample, band_gains, band_edges_hz,
+                              speed_factors, speed_index, ir_index)
+        n, window = rows.offsets.size - 1, int(window)
+        fmt, channels, out, stream = self._window_out(what, n, rows.files, window, rows.channels, dtype, out, stream)
+        return self._call_window(rows, what, window, channels, fmt, out, stream)
 
     def _sum_rows(self, what, files, starts, gains, item_offsets, channels, rate_divisor, mix, resample, band_gains, band_edges_hz,
                   speed_factors, speed_index, ir_index):
-        """the row arguments of decode_window_sum and stft_window, checked in the one order -> (rate_divisor, mix, resample,
-        channels, bands, speeds, irs, offsets int64 [n + 1], files, starts, gains flat and contiguous); ValueError as
+        """the row arguments of decode_window_sum and stft_window, checked in the one order -> a WindowRows; ValueError as
         decode_window_sum documents"""
         rate_divisor = check_rate_divisor(rate_divisor, what)
         mix = check_mix(mix, channels, what)
@@ -1063,7 +1068,7 @@ class PacStore:
         bad = np.flatnonzero(~np.isfinite(gains))
         if bad.size:
             raise ValueError("%s: gains must be finite, got %r at term %d" % (what, float(gains[bad[0]]), int(bad[0])))
-        return rate_divisor, mix, resample, channels, bands, speeds, irs, offsets, files, starts, gains
+        return WindowRows(rate_divisor, mix, resample, channels, bands, speeds, irs, offsets, files, starts, gains)
 
     def stft_window(self, files, starts, n_frames, hop, n_fft, frame_window=None, bank=None, output="power", center=False,
                     gains=None, item_offsets=None, channels=None, dtype=None, out=None, stream=None, rate_divisor=1, mix=None,
@@ -1097,14 +1102,13 @@ class PacStore:
             if item_offsets is not None:
                 raise ValueError("%s: item_offsets goes with gains" % what)
             gains, item_offsets = np.ones(files.size, np.float64), np.arange(files.size + 1, dtype=np.int64)
-        rate_divisor, mix, resample, channels, bands, speeds, irs, offsets, files, starts, gains = self._sum_rows(
-            what, files, starts, gains, item_offsets, channels, rate_divisor, mix, resample, band_gains, band_edges_hz, speed_factors,
-            speed_index, ir_index)
+        rows = self._sum_rows(what, files, starts, gains, item_offsets, channels, rate_divisor, mix, resample, band_gains, band_edges_hz,
+                              speed_factors, speed_index, ir_index)
         if not isinstance(center, (bool, np.bool_)):
             raise ValueError("%s: center must be True or False, got %r" % (what, center))
         if center:
-            starts = starts - n_fft // 2
-        n = offsets.size - 1
+            rows = rows._replace(starts=rows.starts - n_fft // 2)
+        n = rows.offsets.size - 1
         is_complex = mode == _lib.MRC_STFT_COMPLEX
         real = {torch.float32: torch.float32, torch.float64: torch.float64, torch.complex64: torch.float32,
                 torch.complex128: torch.float64}
@@ -1115,40 +1119,11 @@ class PacStore:
                              % (what, " (or complex64 / complex128)" if is_complex else "", dtype))
         real_dtype = real[dtype]
         result_dtype = {torch.float32: torch.complex64, torch.float64: torch.complex128}[real_dtype] if is_complex else real_dtype
-        if channels is None:
-            inside = files[(files >= 0) & (files < len(self))]
-            channels = int(self.n_channels[inside].max()) if inside.size else 1
-        if not _is_int(channels) or int(channels) not in (1, 2):
-            raise ValueError("%s: channels must be None, 1 or 2, got %r" % (what, channels))
-        channels = int(channels)
-        rows = matrix.shape[0] if matrix is not None else n_fft // 2 + 1
-        dev = torch.device("cuda", self._handle.cfg.device_id)
-        shape = (n, channels, rows, n_frames)
-        if out is None:
-            out = torch.empty(shape, dtype=result_dtype, device=dev)
-        elif not isinstance(out, torch.Tensor) or out.dtype != result_dtype or tuple(out.shape) != shape or out.device != dev \
-                or not out.is_contiguous():
-            raise ValueError("%s: out must be a contiguous %s tensor of shape %s on %s" % (what, result_dtype, shape, dev))
-        if stream is None:
-            stream = torch.cuda.current_stream(dev).cuda_stream
-        if speeds is None:
-            up, down, zeros, rolloff = resample if resample is not None else (1, 1, RESAMPLE_ZEROS, RESAMPLE_ROLLOFF)
-            speeds = ([(up, down)], zeros, rolloff, np.zeros(files.size, np.int32))
-        ratios, zeros, rolloff, index = speeds
-        if irs is None:
-            irs = np.full(files.size, -1, np.int32)
-        ups = np.ascontiguousarray([r[0] for r in ratios], dtype=np.int32)
-        downs = np.ascontiguousarray([r[1] for r in ratios], dtype=np.int32)
-        pad = lambda a: a.ctypes.data if a.size else None
-        edges, band_rows = bands if bands is not None else (None, None)
-        self._handle._check(lib.mrc_pac_store_stft_window(
-            self._s, rate_divisor, _lib.MRC_MIX_EACH if mix is None else mix, len(ratios), ups.ctypes.data, downs.ctypes.data, zeros,
-            rolloff, 0 if bands is None else edges.size - 1, None if bands is None else edges.ctypes.data,
-            None if bands is None else pad(band_rows), n, offsets.ctypes.data, pad(files), pad(starts), pad(gains), pad(index), pad(irs),
-            n_fft, window.ctypes.data, n_frames, hop, mode, 0 if matrix is None else matrix.shape[0],
-            None if matrix is None else matrix.ctypes.data, channels, _formats()[real_dtype], out.data_ptr() if out.numel() else None,
-            stream or None))
-        return out
+        n_out = matrix.shape[0] if matrix is not None else n_fft // 2 + 1
+        channels, out, stream = self._out_side(what, rows.files, rows.channels, lambda c: (n, c, n_out, n_frames), result_dtype, out,
+                                               stream, one_or_two=True)
+        return self._call_window(rows, what, n_frames, channels, _formats()[real_dtype], out, stream,
+                                 stft=(n_fft, window, n_frames, hop, mode, matrix))
 
     def stft_ms(self):
         """mrc_pac_store_stft_ms: the device time of the last stft_window's stft_kernel, summed over its slabs"""
@@ -1180,25 +1155,15 @@ class PacStore:
             dtype = torch.float32 if out is None else out.dtype
         if dtype not in (torch.float32, torch.float64):
             raise ValueError("%s: dtype must be torch.float32 or torch.float64, got %s" % (what, dtype))
-        if channels is None:
-            inside = files[(files >= 0) & (files < len(self))]
-            channels = int(self.n_channels[inside].max()) if inside.size else 1
-        if isinstance(channels, bool) or not isinstance(channels, (int, np.integer)) or int(channels) not in (1, 2):
+        channels = self._channels_named(files, channels)
+        if not _is_int(channels) or int(channels) not in (1, 2):
             raise ValueError("%s: channels must be None, 1 or 2, got %r" % (what, channels))
         channels = int(channels)
         if n and (files.min() < 0 or files.max() >= len(self)):
             raise ValueError("%s: files must be indices into the store's %d files, got %r" % (what, len(self), files.tolist()))
         if mix is None and n and int(self.n_channels[files].max()) > channels:
             raise ValueError("%s: a stereo file in a one-channel call (channels=1): ask for 2 channels or a mix" % what)
-        dev = torch.device("cuda", self._handle.cfg.device_id)
-        shape = (n, channels, n_rows, n_frames)
-        if out is None:
-            out = torch.empty(shape, dtype=dtype, device=dev)
-        elif not isinstance(out, torch.Tensor) or out.dtype != dtype or tuple(out.shape) != shape or out.device != dev \
-                or not out.is_contiguous():
-            raise ValueError("%s: out must be a contiguous %s tensor of shape %s on %s" % (what, dtype, shape, dev))
-        if stream is None:
-            stream = torch.cuda.current_stream(dev).cuda_stream
+        out, stream = self._out_tensor(what, (n, channels, n_rows, n_frames), dtype, out, stream)
         self._handle._check(launch(_lib.MRC_MIX_EACH if mix is None else mix, n, files.ctypes.data, starts.ctypes.data, n_frames, hop,
                                    table, channels, _formats()[dtype], out.data_ptr() if out.numel() else None, stream or None))
         return out

@@ -90,28 +90,7 @@ def test_binding_of_the_band_calls():
 
 
 # ------------------------------------------------------------------ Python-side refusals
-class _NoLibrary:
-    """in place of the library: any call through it fails the test"""
-
-    def __getattr__(self, name):
-        raise AssertionError("the library was reached: %s" % name)
-
-
-class _Cfg:
-    device_id = 0
-
-
-class _Handle:
-    cfg = _Cfg()
-
-
-def _husk(monkeypatch):
-    from mrcaudiocodec_amd import store
-    monkeypatch.setattr(store, "lib", _NoLibrary())
-    s = store.PacStore.__new__(store.PacStore)
-    s._handle, s._s, s._levels = _Handle(), None, {}
-    s.n_channels, s.n_samples, s.n_blocks = np.array([2, 1], np.int32), np.array([6144, 6144], np.int64), np.array([7, 6], np.int64)
-    return s
+from store_kit import husk as _husk
 
 
 def test_band_energy_window_refuses_bad_arguments_before_any_library_call(monkeypatch):

@@ -86,20 +86,9 @@ def test_smallest_and_factor_three_syntheses_are_among_the_files():
 
 
 # ------------------------------------------------------------------ Python-side refusals
-class _NoLibrary:
-    """in place of the library: any call through it fails the test"""
-
-    def __getattr__(self, name):
-        raise AssertionError("the library was reached: %s" % name)
-
-
 def _husk(monkeypatch):
-    from mrcaudiocodec_amd import store
-    monkeypatch.setattr(store, "lib", _NoLibrary())
-    s = store.PacStore.__new__(store.PacStore)
-    s._handle, s._s = None, None
-    s.n_channels, s.n_samples = np.array([2], np.int32), np.array([6144], np.int64)
-    return s
+    import store_kit
+    return store_kit.husk(monkeypatch, n_channels=(2,), handle=False)
 
 
 def test_bad_mix_is_refused_before_any_library_call(monkeypatch):

@@ -139,19 +139,9 @@ def test_cli_refuses_a_rate_divisor_that_makes_no_sense(argv, text, capsys):
     assert e.value.code == 2 and text in capsys.readouterr().err
 
 
-class _NoLibrary:
-    """in place of the library: any call through it fails the test"""
-
-    def __getattr__(self, name):
-        raise AssertionError("the library was reached: %s" % name)
-
-
 def test_bad_rate_divisor_is_refused_before_any_library_call(monkeypatch):
-    from mrcaudiocodec_amd import store
-    monkeypatch.setattr(store, "lib", _NoLibrary())
-    s = store.PacStore.__new__(store.PacStore)
-    s._handle, s._s = None, None
-    s.n_channels, s.n_samples = np.array([2], np.int32), np.array([6144], np.int64)
+    import store_kit
+    s = store_kit.husk(monkeypatch, n_channels=(2,), handle=False)
     for bad in (0, 3, 8, -2, 2.0, "2", None, True):
         with pytest.raises(ValueError, match="rate_divisor must be an int in {1, 2, 4}"):
             s.decode_window([0], [0], 16, rate_divisor=bad)

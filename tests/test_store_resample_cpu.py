@@ -138,20 +138,9 @@ def test_restatement_fold_on_a_signal_it_can_be_checked_on():
 
 
 # ------------------------------------------------------------------ Python-side checks
-class _NoLibrary:
-    """in place of the library: any call through it fails the test"""
-
-    def __getattr__(self, name):
-        raise AssertionError("the library was reached: %s" % name)
-
-
 def _husk(monkeypatch):
-    from mrcaudiocodec_amd import store
-    monkeypatch.setattr(store, "lib", _NoLibrary())
-    s = store.PacStore.__new__(store.PacStore)
-    s._handle, s._s = None, None
-    s.n_channels, s.n_samples = np.array([2], np.int32), np.array([6144], np.int64)
-    return s
+    import store_kit
+    return store_kit.husk(monkeypatch, n_channels=(2,), handle=False)
 
 
 @pytest.mark.parametrize("bad,text", [

@@ -29,32 +29,9 @@ def test_binding_of_the_reverb_calls():
 
 
 # ------------------------------------------------------------------ Python-side checks
-class _NoLibrary:
-    """in place of the library: any call through it fails the test"""
-
-    def __getattr__(self, name):
-        raise AssertionError("the library was reached: %s" % name)
-
-
-class _Cfg:
-    sample_rate, device_id = 48000, 0
-
-
-class _Handle:
-    cfg = _Cfg()
-
-    def __getattr__(self, name):
-        raise AssertionError("the handle was reached: %s" % name)
-
-
 def _husk(monkeypatch, n_irs=3):
-    from mrcaudiocodec_amd import store
-    monkeypatch.setattr(store, "lib", _NoLibrary())
-    s = store.PacStore.__new__(store.PacStore)
-    s._handle, s._s = _Handle(), None
-    s.n_channels, s.n_samples = np.array([2, 1], np.int32), np.array([6144, 6144], np.int64)
-    s._ir_lengths = np.full(n_irs, 100, np.int64)
-    return s
+    import store_kit
+    return store_kit.husk(monkeypatch, n_irs=n_irs)
 
 
 @pytest.mark.parametrize("ir_index,text", [

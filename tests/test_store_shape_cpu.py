@@ -131,28 +131,7 @@ def test_the_restatement_is_no_reference_for_a_lone_block_whose_aliasing_cancels
 
 
 # ------------------------------------------------------------------ Python-side checks
-class _NoLibrary:
-    """in place of the library: any call through it fails the test"""
-
-    def __getattr__(self, name):
-        raise AssertionError("the library was reached: %s" % name)
-
-
-class _Cfg:
-    sample_rate, device_id = 48000, 0
-
-
-class _Handle:
-    cfg = _Cfg()
-
-
-def _husk(monkeypatch):
-    from mrcaudiocodec_amd import store
-    monkeypatch.setattr(store, "lib", _NoLibrary())
-    s = store.PacStore.__new__(store.PacStore)
-    s._handle, s._s = _Handle(), None
-    s.n_channels, s.n_samples = np.array([2, 1], np.int32), np.array([6144, 6144], np.int64)
-    return s
+from store_kit import husk as _husk
 
 
 _NAN, _INF = float("nan"), float("inf")

@@ -10,6 +10,7 @@ import pytest
 
 import chain_kit as kit
 import stft_reference as SR
+import store_kit
 
 ACCEPTED = (16, 18, 20, 30, 400, 2048)
 REFUSED = (14, 22, 401, 2050, 4096)
@@ -182,30 +183,8 @@ def test_check_stft():
 
 
 # ------------------------------------------------------------------ PacStore.stft_window's refusals, before any library call
-class _NoLibrary:
-    def __getattr__(self, name):
-        raise AssertionError("the library was reached: %s" % name)
-
-
-class _Cfg:
-    sample_rate, device_id = 48000, 0
-
-
-class _Handle:
-    cfg = _Cfg()
-
-    def __getattr__(self, name):
-        raise AssertionError("the handle was reached: %s" % name)
-
-
 def _husk(monkeypatch):
-    from mrcaudiocodec_amd import store
-    monkeypatch.setattr(store, "lib", _NoLibrary())
-    s = store.PacStore.__new__(store.PacStore)
-    s._handle, s._s = _Handle(), None
-    s.n_channels, s.n_samples = np.array([2, 1], np.int32), np.array([6144, 6144], np.int64)
-    s._ir_lengths = np.full(3, 100, np.int64)
-    return s
+    return store_kit.husk(monkeypatch, n_irs=3)
 
 
 def test_argument_errors_are_value_errors_before_any_library_call(monkeypatch):

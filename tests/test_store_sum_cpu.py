@@ -51,20 +51,9 @@ def test_flatten():
 
 
 # ------------------------------------------------------------------ Python-side checks
-class _NoLibrary:
-    """in place of the library: any call through it fails the test"""
-
-    def __getattr__(self, name):
-        raise AssertionError("the library was reached: %s" % name)
-
-
 def _husk(monkeypatch):
-    from mrcaudiocodec_amd import store
-    monkeypatch.setattr(store, "lib", _NoLibrary())
-    s = store.PacStore.__new__(store.PacStore)
-    s._handle, s._s = None, None
-    s.n_channels, s.n_samples = np.array([2, 1], np.int32), np.array([6144, 6144], np.int64)
-    return s
+    import store_kit
+    return store_kit.husk(monkeypatch, handle=False)
 
 
 @pytest.mark.parametrize("args,kw,text", [
