@@ -1386,6 +1386,67 @@ int mrc_pac_store_stft_window(mrc_pac_store* s, int rate_divisor, int mix, int n
                               void* stream);
 int mrc_pac_store_stft_ms(mrc_pac_store* s, double* ms /*[1]: stft_kernel of the last call */);
 
+/* Routes: rows of SEVERAL output channels, a gain and a response per (term, output channel), in the one call that reads the
+ * terms -- an utterance through the C microphones of one room as [items][C][window]; the reverberant mixture, the dry speech
+ * and the noise alone of the SAME terms as three channels.  Each term is parsed, synthesised and written to the dry scratch
+ * once, whatever the number of channels it reaches.
+ * THE CALL.  mrc_pac_store_decode_window_routed takes every argument of mrc_pac_store_decode_window_reverb but gain and ir_of;
+ * in their place stand route_gain and route_ir, [n_terms][n_channels_out]: route_ir[k][c] is MRC_ROUTE_NONE (term k does not
+ * reach channel c: no work, no contribution), -1 (dry) or the index of a response of the bank.
+ * EVERY TERM GIVES ONE CHANNEL: mix is MRC_MIX_MID, _LEFT or _RIGHT, or it is MRC_MIX_EACH and every file named is mono (a
+ * stereo file is then refused as a one-channel call refuses it).  n_channels_out, 1..MRC_MAX_STORE_ROUTE_CHANNELS, counts the
+ * OUTPUT channels and has nothing to do with the source.
+ * THE VALUE, to the bit: out[i][c] is the row mrc_pac_store_decode_window_reverb gives with n_channels_out = 1 over item i's
+ * terms whose route to c is not MRC_ROUTE_NONE, in the order given, with gain[k] = route_gain[k][c] and ir_of[k] =
+ * route_ir[k][c] and every other argument equal, in all three formats.  No tolerance of its own: a convolved term's bound is
+ * that call's.  A row all of whose routes to a channel are absent is +0.0 there.  To the bit nothing depends on the order of
+ * the rows, on what shares the call, on the slab size, on the bank's layout, on the launch grid, nor on which other channels
+ * the call has, their order, or how the kernel groups them (MRC_OPT_STORE_ROUTE_GROUP).
+ * WHAT IS SHARED.  A term's span is lengthened by Lpre = (the longest response any route of the call's terms names) - 1 -- a
+ * longer pre-roll changes no bit -- and decoded once.  Forward transforms: ONE source per (term, distinct response LENGTH among
+ * its wet routes).  A segment is zero outside [-(len(h) - 1), window) and the number of segments follows len(h), so routes
+ * share spectra exactly when their responses have equal lengths (the microphones of one array); lengths are not rounded to
+ * partitions for sharing.  reverb_route_fold_kernel then runs one inverse transform per (term, channel), as the reverb call
+ * does per term; the channels of a workgroup that share a source load its spectra once per partition.
+ * mrc_pac_store_stft_window_routed: the same row arguments, then mrc_pac_store_stft_window's own; out
+ * [i][c][k | q][m]: channel c is mrc_pac_store_stft_window on that one-channel row, bit for bit in all three modes.
+ * MRC_ERR_INVALID naming the argument, before any device work and with `out` untouched: every refusal of the reverb call,
+ * respectively the STFT call, under this call's name; n_channels_out outside 1..MRC_MAX_STORE_ROUTE_CHANNELS; MRC_MIX_EACH with
+ * a stereo file; route_gain or route_ir NULL with terms present; a gain that is not finite (term and channel named); an
+ * index below MRC_ROUTE_NONE or outside the bank (term and channel named); an index >= 0 while the store has no bank;
+ * window + Lpre beyond 2^40.  n_items == 0 or window == 0: MRC_OK, nothing written.
+ * Slabs: the reverb call's rule, the terms counted at window + Lpre ONCE, not per channel; a slab's rows are also capped so
+ * that its workgroups (rows x output blocks x channel groups) stay below 2^31.  The route records go up in the slab's one
+ * staging copy.  mrc_pac_store_stats and mrc_pac_store_reverb_ms describe the call as they do the reverb call (a one-channel
+ * call without an absent route and without a wet route IS the speeds call, as there).  mrc_pac_store_route_info, of the last
+ * routed call, summed over its slabs: counts[0] forward segments transformed, counts[1] inverse transforms, counts[2] bytes
+ * of spectra written. */
+#define MRC_MAX_STORE_ROUTE_CHANNELS 16
+#define MRC_ROUTE_NONE (-2)   /* the term does not reach this channel: no work, no contribution */
+int mrc_pac_store_decode_window_routed(mrc_pac_store* s, int rate_divisor, int mix, int n_ratios,
+                                       const int32_t* ratio_up /*[n_ratios]*/, const int32_t* ratio_down /*[n_ratios]*/, int zeros,
+                                       double rolloff, int n_bands /* 0: no band gains */, const double* edge_hz /*[n_bands+1]*/,
+                                       const double* band_gain /*[n_terms][n_bands]*/, int64_t n_items,
+                                       const int64_t* term_offset /*[n_items+1]*/, const int64_t* file /*[n_terms]*/,
+                                       const int64_t* start /*[n_terms]*/, const int32_t* ratio_of /*[n_terms]: index into the list*/,
+                                       const double* route_gain /*[n_terms][n_channels_out]*/,
+                                       const int32_t* route_ir /*[n_terms][n_channels_out]: MRC_ROUTE_NONE, -1 dry, or an index into the bank*/,
+                                       int64_t window, int n_channels_out /* 1..16 */, int format,
+                                       void* out /* DEVICE [n_items][n_channels_out][window] */, void* stream);
+int mrc_pac_store_stft_window_routed(mrc_pac_store* s, int rate_divisor, int mix, int n_ratios,
+                                     const int32_t* ratio_up /*[n_ratios]*/, const int32_t* ratio_down /*[n_ratios]*/, int zeros,
+                                     double rolloff, int n_bands /* 0: no band gains */, const double* edge_hz /*[n_bands+1]*/,
+                                     const double* band_gain /*[n_terms][n_bands]*/, int64_t n_items,
+                                     const int64_t* term_offset /*[n_items+1]*/, const int64_t* file /*[n_terms]*/,
+                                     const int64_t* start /*[n_terms]*/, const int32_t* ratio_of /*[n_terms]: index into the list*/,
+                                     const double* route_gain /*[n_terms][n_channels_out]*/,
+                                     const int32_t* route_ir /*[n_terms][n_channels_out]*/, int n_fft,
+                                     const double* frame_window /* HOST [n_fft] */, int64_t n_frames, int64_t hop, int mode,
+                                     int n_filters, const double* bank /* HOST [n_filters][n_fft/2+1], MRC_STFT_BANK only */,
+                                     int n_channels_out /* 1..16 */, int format /* MRC_WINDOW_F32 | MRC_WINDOW_F64 */,
+                                     void* out /* DEVICE */, void* stream);
+int mrc_pac_store_route_info(mrc_pac_store* s, int64_t* counts /*[3]*/);
+
 /* Per-stage device time of the most recent timed call when timing is enabled (hipEvents on the launch stream; the call
  * then synchronises).  Timed: mrc_dev_encode / mrc_dev_encode_ex and mrc_encode_mono / mrc_encode_joint (the _blocks
  * forms: their last shape group).  Not timed: the stage calls (mrc_dev_mdct, mrc_dev_smr, mrc_dev_alloc_quant),
@@ -1422,6 +1483,11 @@ int mrc_set_timing(mrc_handle* h, int enabled);
  * whatever the size of the call: 16 bytes per sample of margin planes and about as much of parsed chunks for stereo.
  * Default 2^24 (~270 MB of planes); 0: one slab.  The results do not depend on it. */
 #define MRC_OPT_STORE_SLAB_SAMPLES 7
+/* MRC_OPT_STORE_ROUTE_GROUP = 0 | 1 | 2: the output channels one workgroup of reverb_route_fold_kernel serves
+ * (mrc_pac_store_decode_window_routed); the two channels of a group that share a source load its spectra once.  Default 0:
+ * chosen per slab -- 2 where at least half of the slab's wet routes have such a neighbour (the microphones of an array), else
+ * 1 (measured: DESIGN.md).  The results do not depend on it. */
+#define MRC_OPT_STORE_ROUTE_GROUP 8
 int mrc_set_option(mrc_handle* h, int option, int value);
 int mrc_get_option(mrc_handle* h, int option, int32_t* value);
 int mrc_get_stage_ms(mrc_handle* h, double* ms /*[3]*/);

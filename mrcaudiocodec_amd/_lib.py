@@ -23,6 +23,9 @@ MRC_MIX_MID, MRC_MIX_LEFT, MRC_MIX_RIGHT = 0, 1, 2               # mrc_pac_store
 MRC_MIX_EACH = 3                                                 # mrc_pac_store_block_energy: every channel of the file
 MRC_FILTER_NORM_NONE, MRC_FILTER_NORM_SLANEY = 0, 1              # mrc_filterbank_line_weights' norms
 MRC_OPT_STORE_SLAB_SAMPLES = 7
+MRC_OPT_STORE_ROUTE_GROUP = 8                                    # reverb_route_fold_kernel: output channels per workgroup (0: per slab | 1 | 2)
+MRC_MAX_STORE_ROUTE_CHANNELS = 16                                # mrc_pac_store_decode_window_routed: output channels of a row
+MRC_ROUTE_NONE = -2                                              # ... a route that does not exist
 MRC_STORE_REVERB_BLOCK = 1024                                    # mrc_pac_store_decode_window_reverb: the overlap-save hop B (N = 2 B)
 MRC_MAX_STORE_IR_TAPS = 1 << 17                                  # mrc_pac_store_set_irs: taps of one impulse response
 MRC_STFT_COMPLEX, MRC_STFT_POWER, MRC_STFT_BANK = 0, 1, 2        # mrc_pac_store_stft_window's modes
@@ -267,6 +270,14 @@ def _load():
                                                 C.c_int, _f64p, C.c_int64, C.c_int64, C.c_int, C.c_int, _f64p, C.c_int, C.c_int,
                                                 C.c_void_p, C.c_void_p]),
         "mrc_pac_store_stft_ms": (C.c_int, [C.c_void_p, _f64p]),
+        "mrc_pac_store_decode_window_routed": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, C.c_int, C.c_double,
+                                                         C.c_int, _f64p, _f64p, C.c_int64, _i64p, _i64p, _i64p, _i32p, _f64p, _i32p,
+                                                         C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+        "mrc_pac_store_stft_window_routed": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, C.c_int, C.c_double,
+                                                       C.c_int, _f64p, _f64p, C.c_int64, _i64p, _i64p, _i64p, _i32p, _f64p, _i32p,
+                                                       C.c_int, _f64p, C.c_int64, C.c_int64, C.c_int, C.c_int, _f64p, C.c_int, C.c_int,
+                                                       C.c_void_p, C.c_void_p]),
+        "mrc_pac_store_route_info": (C.c_int, [C.c_void_p, _i64p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = the library does not export the header's symbol

@@ -866,6 +866,50 @@ def read_ir(path, rate_out):
         raise ValueError("--ir: %s: %s" % (path, e))
 
 
+def check_array_ir_args(array_ir, ir, decode):
+    """--array-ir as given (None: not given) -> the path or None.  It decodes one channel through the C responses of a microphone
+    array into a C-channel WAV: refused without -d, and together with --ir (one room or one array)."""
+    if array_ir is None:
+        return None
+    if not decode:
+        raise ValueError("--array-ir decodes a file through the responses of a microphone array: it needs -d")
+    if ir is not None:
+        raise ValueError("--array-ir and --ir both convolve the decoded file: give one of them")
+    return array_ir
+
+
+def read_array_ir(path, rate_out):
+    """the impulse responses of --array-ir -> a list of C float64 [taps] at rate_out Hz, 1 <= C <= store.MAX_ROUTE_CHANNELS.  A
+    .npy file holds a [C][taps] array of numbers taken as it is (sampled at the output rate); anything else is a C-channel
+    16-bit PCM WAV, read with read_wav, each channel brought from the file's rate to rate_out by store.ir_at_rate."""
+    from .store import MAX_ROUTE_CHANNELS, check_impulse_responses, ir_at_rate
+    what = "--array-ir"
+    if str(path).lower().endswith(".npy"):
+        try:
+            taps = np.load(path, allow_pickle=False)
+        except (OSError, ValueError) as e:
+            raise ValueError("%s: %s: %s" % (what, path, e))
+        if taps.ndim != 2 or not 1 <= taps.shape[0] <= MAX_ROUTE_CHANNELS:
+            raise ValueError("%s: %s: the array must be [C][taps] with 1 to %d microphones, got shape %s"
+                             % (what, path, MAX_ROUTE_CHANNELS, taps.shape))
+        try:
+            offsets, flat = check_impulse_responses(list(taps), what)
+        except ValueError as e:
+            raise ValueError("%s (%s)" % (e, path))
+        return [flat[offsets[j]:offsets[j + 1]] for j in range(taps.shape[0])]
+    try:
+        rate, n_ch, num_samples, x = read_wav(path, 1)
+    except (OSError, ValueError) as e:
+        raise ValueError("%s: %s: %s" % (what, path, e))
+    if not 1 <= n_ch <= MAX_ROUTE_CHANNELS or num_samples < 1:
+        raise ValueError("%s: %s: a WAV of impulse responses must have 1 to %d channels and at least one sample, got %d x %d"
+                         % (what, path, MAX_ROUTE_CHANNELS, n_ch, num_samples))
+    try:
+        return [ir_at_rate(x[c, :num_samples], int(rate), int(rate_out)) for c in range(n_ch)]
+    except ValueError as e:
+        raise ValueError("%s: %s: %s" % (what, path, e))
+
+
 CODEC_SETTINGS = ("sample_rate", "n_mdct_lines", "n_scale_bits", "n_mant_size_bits")   # what a .pac header says of its codec
 
 
@@ -885,7 +929,7 @@ def _levels_of_mix(store, rate_divisor, mix):
 
 
 def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=1, mix=None, sample_rate=None, overlay=None,
-                    band_gains=None, speed=None, ir=None, stft=None):
+                    band_gains=None, speed=None, ir=None, stft=None, array_ir=None):
     """excerpt: None (the whole file, mrc_decode_pac_pcm16) or (start, samples): that many samples from sample `start` on
     (samples None: to the end of the file), decoded through a one-file PacStore -- only the blocks the excerpt overlaps are
     parsed and synthesised; what lies outside the file is silence.  rate_divisor 2 or 4: at that fraction of the sample rate,
@@ -907,6 +951,10 @@ def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=
     ir: None or the path of an impulse response (read_ir: a .npy array at the output rate, or a mono 16-bit WAV brought to it):
     the file convolved with it through the store as well (PacStore.decode_window(ir_index=)), last of all -- at the output rate,
     after the speed; the overlay stays dry, the same one call.  The output keeps the length it has without --ir.
+    array_ir: None or the path of the C impulse responses of a microphone array (read_array_ir): ONE channel of the file (mix; None:
+    "mid" for a stereo file) through every one of them in one PacStore.decode_window_routed call -- the file is parsed,
+    synthesised and transformed once -- into a C-channel WAV (with stft: C channels of spectra); the overlay is dry on every
+    channel.  Not together with ir.
     stft: None, or check_stft_energies_args' dict: wav_path is then a .npy file and receives PacStore.stft_window of the very row
     the other arguments describe, (samples - n_fft) // hop + 1 whole frames of it (none: an empty array), in place of the WAV
     -> the array as written.
@@ -948,9 +996,10 @@ def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=
         except ValueError as e:
             raise ValueError("--speed: %s" % e)
     if (rate_divisor != 1 or mix is not None or resample is not None or overlay is not None or band_gains is not None
-            or speed is not None or ir is not None or stft is not None) and excerpt is None:
+            or speed is not None or ir is not None or stft is not None or array_ir is not None) and excerpt is None:
         excerpt = (0, None)
     taps = None if ir is None else read_ir(ir, cfg.sample_rate // rate_divisor if sample_rate is None else int(sample_rate))
+    mics = None if array_ir is None else read_array_ir(array_ir, cfg.sample_rate // rate_divisor if sample_rate is None else int(sample_rate))
     h = Handle(sample_rate=cfg.sample_rate, n_mdct_lines=cfg.n_mdct_lines, n_scale_bits=cfg.n_scale_bits,
                n_mant_size_bits=cfg.n_mant_size_bits, device_id=device_id)
     try:
@@ -970,6 +1019,12 @@ def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=
                 if taps is not None:                     # the file through the room; the overlay dry
                     store.set_impulse_responses([taps])
                     shaped.update(ir_index=[0] if overlay is None else [[0, -1]])
+                if mics is not None:                     # one channel of the file through every microphone; the overlay dry
+                    if mix is None and int(store.n_channels.max()) > 1:
+                        mix = "mid"
+                    store.set_impulse_responses(mics)
+                    from .store import array_routes
+                    routes = dict(zip(("route_gains", "route_irs"), array_routes([0] if overlay is None else [[0, -1]], len(mics))))
                 if stft is not None:                     # the same row, framed and transformed instead of written
                     from .store import mel_bin_weights, mel_points
                     rate_out = cfg.sample_rate // rate_divisor if sample_rate is None else int(sample_rate)
@@ -985,12 +1040,21 @@ def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=
                     window = lambda files, starts, _samples, **kw: store.stft_window(files, starts, frames, stft["hop"], stft["n_fft"],
                                                                                      **spectrum, **kw)
                     window_sum = lambda files, starts, gains, _samples, **kw: window(files, starts, _samples, gains=gains, **kw)
+                    routed = window                      # (routes in the place of gains: 1-D one term per item, or [n][K])
                 else:
                     window, window_sum = store.decode_window, store.decode_window_sum
+                    # (files, starts, the routes and every per-term argument keep the one shape they were built in: a 1-D list is
+                    # rows of one term each)
+                    routed = lambda files, starts, _samples, route_gains, route_irs, **kw: store.decode_window_routed(
+                        files, starts, route_gains, route_irs, _samples,
+                        item_offsets=np.arange(len(files) + 1) if np.ndim(files) == 1 else None, **kw)
                 if overlay is None:
                     if band_gains is not None:
                         shaped["band_gains"] = band_gains[1]
-                    got = window([0], [start], samples, rate_divisor=rate_divisor, mix=mix, resample=resample, **shaped)
+                    if mics is not None:
+                        got = routed([0], [start], samples, rate_divisor=rate_divisor, mix=mix, resample=resample, **routes, **shaped)
+                    else:
+                        got = window([0], [start], samples, rate_divisor=rate_divisor, mix=mix, resample=resample, **shaped)
                 else:
                     # the levels live at the rate divisor's rate: the excerpt's span there (the whole of it, rounded outwards)
                     up, down = resample if resample is not None else (1, 1)
@@ -1004,8 +1068,13 @@ def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=
                     print("overlay: %s at a factor of %.9g (%g dB under the excerpt)" % (overlay[0], gain, overlay[1]))
                     if band_gains is not None:           # (the overlay's row: ones)
                         shaped["band_gains"] = np.stack([band_gains[1], np.ones_like(band_gains[1])])[None]
-                    got = window_sum([[0, 1]], [[start, overlay[2]]], [[1.0, gain]], samples, rate_divisor=rate_divisor,
-                                     mix=mix, resample=resample, **shaped)
+                    if mics is not None:                 # (the overlay's factor on every channel)
+                        routes["route_gains"] = routes["route_gains"] * np.array([1.0, gain])[None, :, None]
+                        got = routed([[0, 1]], [[start, overlay[2]]], samples, rate_divisor=rate_divisor, mix=mix,
+                                     resample=resample, **routes, **shaped)
+                    else:
+                        got = window_sum([[0, 1]], [[start, overlay[2]]], [[1.0, gain]], samples, rate_divisor=rate_divisor,
+                                         mix=mix, resample=resample, **shaped)
                 inter = got[0].cpu().numpy() if stft is not None else np.ascontiguousarray(got[0].cpu().numpy().T)
     finally:
         h.close()
@@ -1160,6 +1229,11 @@ def main(argv=None):
                     help="with -d: convolve the decoded file with the impulse response in FILE, a .npy float array sampled at the "
                          "output rate or a mono 16-bit WAV (brought to the output rate), through the resident store on the device; "
                          "composes with --sample-rate, --speed, --mix, --overlay (the overlay stays dry), --start and --samples")
+    ap.add_argument("--array-ir", default=None, metavar="FILE",
+                    help="with -d: decode ONE channel of the file (--mix; mid by default for a stereo file) through the C impulse "
+                         "responses in FILE, a .npy float array [C][taps] sampled at the output rate or a C-channel 16-bit WAV "
+                         "(brought to the output rate), into a C-channel WAV -- one microphone each, the file parsed and "
+                         "transformed once; composes with what --ir composes with and is refused together with --ir")
     ap.add_argument("--levels", nargs="+", default=None, metavar="PAC",
                     help="no src, no dst: print one JSON line per .pac file with its channels, samples, RMS level per channel "
                          "(dB re full scale) and its loudest and quietest window on the short-block grid, from the block "
@@ -1212,7 +1286,7 @@ def main(argv=None):
         given_energies = dict(
             given, **{"--levels": a.levels is not None, "--levels-window": a.levels_window is not None,
                       "--rate-divisor": a.rate_divisor is not None, "--band-gains-db": a.band_gains_db is not None,
-                      "--speed": a.speed is not None, "--ir": a.ir is not None})
+                      "--speed": a.speed is not None, "--ir": a.ir is not None, "--array-ir": a.array_ir is not None})
         stft = check_stft_energies_args(a.stft_energies, a.n_fft, a.hop, a.win_length, a.mel, a.f_min, a.f_max, a.mel_scale, a.filter_norm,
                                         a.complex, dict(given_energies, **{"--band-energies": a.band_energies,
                                                                            "--band-edges": a.band_edges is not None,
@@ -1237,6 +1311,7 @@ def main(argv=None):
         band_gains = check_band_gains_db_args(a.band_gains_db, row)
         speed = check_speed_args(a.speed, row)
         ir = check_ir_args(a.ir, row)
+        array_ir = check_array_ir_args(a.array_ir, ir, row)
         if levels is not None:
             from .store import check_levels_mix
             check_levels_mix(mix, "--mix")
@@ -1244,7 +1319,7 @@ def main(argv=None):
         ap.error(str(e))
     if stft is not None:
         try:
-            spectrum = decode_pac_file(a.src, a.dst, a.device, excerpt, rate_divisor, mix, sample_rate, overlay, band_gains, speed, ir, stft)
+            spectrum = decode_pac_file(a.src, a.dst, a.device, excerpt, rate_divisor, mix, sample_rate, overlay, band_gains, speed, ir, stft, array_ir)
         except ValueError as e:
             ap.error(str(e))
         print("%s: %s %s" % (a.dst, " x ".join(str(v) for v in spectrum.shape), spectrum.dtype))
@@ -1312,7 +1387,7 @@ def main(argv=None):
         return
     if a.decode:
         try:
-            pcm = decode_pac_file(a.src, a.dst, a.device, excerpt, rate_divisor, mix, sample_rate, overlay, band_gains, speed, ir)
+            pcm = decode_pac_file(a.src, a.dst, a.device, excerpt, rate_divisor, mix, sample_rate, overlay, band_gains, speed, ir, array_ir=array_ir)
         except ValueError as e:
             ap.error(str(e))
         print("%s: %d channels x %d samples" % (a.dst, pcm.shape[0], pcm.shape[1]))

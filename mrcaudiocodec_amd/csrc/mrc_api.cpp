@@ -200,6 +200,11 @@ int mrc_set_option(mrc_handle* h, int option, int value) {
         h->storeSlabSamples = value;
         return MRC_OK;
     }
+    if (option == MRC_OPT_STORE_ROUTE_GROUP) {
+        if (value < 0 || value > 2) return fail(h, MRC_ERR_INVALID, "mrc_set_option: MRC_OPT_STORE_ROUTE_GROUP takes 0 (chosen per slab), 1 or 2");
+        h->storeRouteGroup = value;
+        return MRC_OK;
+    }
     if (option == MRC_OPT_CHAIN_THREADS) {
         if (value != 0 && value != 256 && value != 512 && value != 1024) return fail(h, MRC_ERR_INVALID, "mrc_set_option: MRC_OPT_CHAIN_THREADS takes 0, 256, 512 or 1024");
         h->chainThreads = value;
@@ -218,6 +223,7 @@ int mrc_get_option(mrc_handle* h, int option, int32_t* value) {
         case MRC_OPT_SENSITIVITY: *value = h->sensMode; return MRC_OK;
         case MRC_OPT_CHAIN_SLAB_BLOCKS: *value = (int32_t)h->chainSlabBlocks; return MRC_OK;
         case MRC_OPT_STORE_SLAB_SAMPLES: *value = (int32_t)h->storeSlabSamples; return MRC_OK;
+        case MRC_OPT_STORE_ROUTE_GROUP: *value = h->storeRouteGroup; return MRC_OK;
         default: return fail(h, MRC_ERR_INVALID, "mrc_get_option: unknown option");
     }
 }

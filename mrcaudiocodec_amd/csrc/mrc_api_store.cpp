@@ -4,7 +4,7 @@
 // create: pac_plan_scan -- the host plan of mrc_decode_pac_pcm16, one scan in the tree -- gives every file's chunks, block
 // shapes and positions; the bytes go to the device in one copy and never cross PCIe again.
 //
-// The window calls (decode_window and its eight kin, stft_window) are one path:
+// The window calls (decode_window and its nine kin, stft_window and stft_window_routed) are one path:
 //   request   every extern "C" entry fills a WindowRequest -- what the widest entry takes, the caller's arrays as they came --
 //             and does nothing else.
 //   check     check_windows turns it into a CheckedWindows once per public call: the internal mix, the one filter or the list
@@ -84,6 +84,11 @@
 //
 // stft_window, the short-time Fourier transform of those rows: stft_loop has reverb_loop write a slab's rows as float64 into
 // a second scratch buffer and stft_kernel (mrc_kernels_stft.hip) frames and transforms them.
+//
+// decode_window_routed and stft_window_routed, rows of several OUTPUT channels with a gain and a response per (term, channel):
+// the routed kinds of the request, through the same reverb_loop.  A term is decoded with one channel, once; its routes stand
+// where the reverb call has one gain and one response; it gets a source of forward transforms per distinct response length
+// among its wet routes, and reverb_route_fold_kernel writes the rows' channels.  The STFT loop sees rows of that many channels.
 //
 // block_energy, ((a + b) / D) * the sum of squares of a block's first 1 / D decoded lines, per channel or for the mid, for
 // every block of the selected files: the same slab plan (stage_slab, parse_slab) over runs of whole blocks instead of the
@@ -406,7 +411,7 @@ int get_resample_tables(mrc_handle* h, int n, const ResampleSpec* r, const Resam
 // ---- the window calls: one request, checked once, run by three loops over row ranges (see the head of the file)
 // What the widest entry takes, without the STFT's own arguments.  Every extern "C" window entry fills one and nothing else.
 struct WindowRequest {
-    enum Kind { kItems, kRows, kReverb, kStft };             // which checks are made and in what order (check_windows)
+    enum Kind { kItems, kRows, kReverb, kStft, kRouted, kStftRouted };   // which checks are made and in what order (check_windows)
     const char* fn;                                          // the entry point's name, in front of every refusal
     Kind kind;
     int rateDivisor = 1;
@@ -427,9 +432,17 @@ struct WindowRequest {
     const int64_t *termOffset = nullptr, *file = nullptr, *start = nullptr;
     const double* gain = nullptr;
     const int32_t* irOf = nullptr;
-    int nChannelsOut = 1;
+    int nChannelsOut = 1;                                    // the channels DECODED per unit and, unless routed, written per row
+    // a routed kind: every term gives one channel (nChannelsOut == 1) and reaches routeChannels output channels; gain and irOf
+    // are then the route arrays, [n_terms][routeChannels]
+    int routeChannels = 0;
     void* stream = nullptr;
     bool rows() const { return kind != kItems; }
+    bool routed() const { return kind == kRouted || kind == kStftRouted; }
+    bool stft() const { return kind == kStft || kind == kStftRouted; }
+    bool banked() const { return kind != kItems && kind != kRows; }
+    int routesPerTerm() const { return routed() ? routeChannels : 1; }   // the stride of gain and irOf
+    int rowChannels() const { return routed() ? routeChannels : nChannelsOut; }
 };
 struct SpeedSpec {
     int nRatios;
@@ -1205,13 +1218,18 @@ int check_windows(mrc_pac_store* s, const WindowRequest& q, int64_t window, int 
     mrc_handle* h = s->h;
     const std::string w = q.fn;
     const auto refuse = [&](const std::string& what) { return fail(h, MRC_ERR_INVALID, w + ": " + what); };
-    const bool rows = q.rows(), banked = q.kind == WindowRequest::kReverb || q.kind == WindowRequest::kStft;
+    const bool rows = q.rows(), banked = q.banked(), routed = q.routed(), stft = q.stft();
+    const int C = q.routesPerTerm();
+    // a route's place in every refusal that names one
+    const auto route = [C](int64_t r) { return "term " + std::to_string(r / C) + ", channel " + std::to_string(r % C); };
     const bool windowOk = window >= 0 && window <= kMaxWindow;
     c->q = q;
     if (q.ratioList && q.nBands == 0 && (q.edgeHz || q.bandGain))
         return refuse("n_bands is 0 (no band gains) but edge_hz or band_gain is not NULL");
-    if (q.kind == WindowRequest::kReverb && !windowOk) return refuse("window must lie in [0, 2^40]");
+    if (banked && !stft && !windowOk) return refuse("window must lie in [0, 2^40]");
     MRC_TRY(check_mix(h, w, q.mix, q.mixAllowed));
+    if (routed && (q.routeChannels < 1 || q.routeChannels > MRC_MAX_STORE_ROUTE_CHANNELS))
+        return refuse("n_channels_out " + std::to_string(q.routeChannels) + " is outside 1.." + std::to_string(MRC_MAX_STORE_ROUTE_CHANNELS));
     if (q.mix != MRC_MIX_EACH && q.nChannelsOut != 1) return refuse("n_channels_out must be 1 under a mix of one channel");
     c->mix = q.mix == MRC_MIX_EACH ? kNoMix : q.mix;
     // ---- the ratio, or the length of the list
@@ -1235,9 +1253,16 @@ int check_windows(mrc_pac_store* s, const WindowRequest& q, int64_t window, int 
         for (int64_t i = 0; i < q.nItems; ++i)
             if (q.termOffset[i + 1] < q.termOffset[i]) return refuse("term_offset decreases at [" + std::to_string(i + 1) + "]");
         const int64_t nTerms = c->nTerms = q.termOffset[q.nItems];
-        if (nTerms > 0 && (!q.file || !q.start || !q.gain)) return refuse("file, start or gain is NULL");
-        for (int64_t k = 0; k < nTerms; ++k)
-            if (!std::isfinite(q.gain[k])) return refuse("gain of term " + std::to_string(k) + " is not finite");
+        if (routed) {
+            if (nTerms > 0 && (!q.file || !q.start)) return refuse("file or start is NULL");
+            if (nTerms > 0 && (!q.gain || !q.irOf)) return refuse("route_gain or route_ir is NULL");
+            for (int64_t r = 0; r < nTerms * C; ++r)
+                if (!std::isfinite(q.gain[r])) return refuse("route_gain of " + route(r) + " is not finite");
+        } else {
+            if (nTerms > 0 && (!q.file || !q.start || !q.gain)) return refuse("file, start or gain is NULL");
+            for (int64_t k = 0; k < nTerms; ++k)
+                if (!std::isfinite(q.gain[k])) return refuse("gain of term " + std::to_string(k) + " is not finite");
+        }
         if (q.ratioList && nTerms > 0 && (!q.ratioUp || !q.ratioDown || !q.ratioOf))
             return refuse("ratio_up, ratio_down or ratio_of is NULL");
         if (q.ratioList && q.ratioUp && q.ratioDown) {       // the list is checked wherever it is given, terms or none
@@ -1300,22 +1325,23 @@ int check_windows(mrc_pac_store* s, const WindowRequest& q, int64_t window, int 
     // ---- the terms' impulse responses
     const int64_t nIrs = (int64_t)s->irLen.size();
     if (c->nTerms > 0 && !q.irOf) return refuse("ir_of is NULL");
-    for (int64_t k = 0; k < c->nTerms; ++k) {
-        const int64_t v = q.irOf[k];
-        if (v == -1) continue;
+    for (int64_t r = 0; r < c->nTerms * C; ++r) {
+        const int64_t v = q.irOf[r];
+        if (v == -1 || (routed && v == MRC_ROUTE_NONE)) continue;
+        const std::string name = routed ? "route_ir of " + route(r) : "ir_of of term " + std::to_string(r);
         if (v >= 0 && nIrs == 0)
-            return refuse("ir_of of term " + std::to_string(k) + " = " + std::to_string(v) +
-                          " but the store has no impulse responses (mrc_pac_store_set_irs)");
+            return refuse(name + " = " + std::to_string(v) + " but the store has no impulse responses (mrc_pac_store_set_irs)");
         if (v < 0 || v >= nIrs)
-            return refuse("ir_of of term " + std::to_string(k) + " = " + std::to_string(v) + " is neither -1 nor inside the bank of " +
+            return refuse(name + " = " + std::to_string(v) + (routed ? " is none of MRC_ROUTE_NONE (-2), -1 and an index into the bank of " :
+                                                                       " is neither -1 nor inside the bank of ") +
                           std::to_string(nIrs) + " impulse responses");
         c->maxPreRoll = std::max(c->maxPreRoll, s->irLen[(size_t)v] - 1);
     }
     const std::string tooLong = " + the longest impulse response named - 1 = " + std::to_string(window + c->maxPreRoll) + " exceeds 2^40";
     const bool overlong = window + c->maxPreRoll > kMaxWindow;
-    if (q.kind == WindowRequest::kReverb && overlong) return refuse("window" + tooLong);
+    if (!stft && overlong) return refuse("window" + tooLong);
     if (!c->empty && !out) return refuse("out is NULL");
-    if (q.kind == WindowRequest::kStft && !c->empty && overlong) return refuse("L" + tooLong);
+    if (stft && !c->empty && overlong) return refuse("L" + tooLong);
     return MRC_OK;
 }
 
@@ -1324,6 +1350,7 @@ int check_windows(mrc_pac_store* s, const WindowRequest& q, int64_t window, int 
 // convolved terms' segments and reverb_fold_kernel folds the rows (mrc_kernels_reverb.hip), on the same stream.  The term and
 // source records of a slab go up in one copy.
 const char* const kWinReverb = "mrc_pac_store_decode_window_reverb";
+const char* const kWinRouted = "mrc_pac_store_decode_window_routed";
 const char* const kSetIrs = "mrc_pac_store_set_irs";
 constexpr int64_t kRevB = MRC_STORE_REVERB_BLOCK, kRevN = 2 * kRevB;
 
@@ -1409,13 +1436,34 @@ int reverb_loop(mrc_pac_store* s, const CheckedWindows& c, const WindowRun& run)
     mrc_handle* h = s->h;
     const int64_t* const term_offset = q.termOffset;
     const int32_t* const ir_of = q.irOf;
+    // A routed request is the same loop with C routes per term where the others have one: gain and ir_of are [term][C], the
+    // terms are decoded with ONE channel, the rows have C, a term has a source per distinct response LENGTH among its wet
+    // routes (spectra are shared exactly where the lengths are equal: a segment is zero outside [-(len(h) - 1), window) and
+    // the number of segments follows len(h)), and reverb_route_fold_kernel folds.  A range without a wet route takes the
+    // plain rows path only where that IS the row: one channel, no absent route (gain is then the rows call's [n_terms]).
+    const bool routed = q.routed();
+    const int C = q.routesPerTerm(), nch = q.nChannelsOut, nchOut = q.rowChannels();
     int64_t Lpre = 0;
-    for (int64_t k = term_offset[run.first]; k < term_offset[run.last]; ++k)
-        if (ir_of[k] >= 0) Lpre = std::max(Lpre, s->irLen[(size_t)ir_of[k]]);     // (longest length; at least 1 if any)
-    if (Lpre == 0) return units_loop(s, c, run);
-    Lpre -= 1;
+    bool absent = false;
+    for (int64_t r = term_offset[run.first] * C; r < term_offset[run.last] * C; ++r) {
+        if (ir_of[r] >= 0) Lpre = std::max(Lpre, s->irLen[(size_t)ir_of[r]]);     // (longest length; at least 1 if any)
+        absent = absent || ir_of[r] == MRC_ROUTE_NONE;
+    }
+    if (Lpre == 0 && (!routed || (C == 1 && !absent))) return units_loop(s, c, run);
+    Lpre = std::max<int64_t>(Lpre, 1) - 1;
     const int64_t window = run.window, Wd = window + Lpre;
-    const int format = run.format, nch = q.nChannelsOut;
+    const int format = run.format;
+    // the distinct response lengths among term k's wet routes, in the order of their first channel -> their number
+    const auto lengths_of = [&](int64_t k, int64_t* lens) {
+        int n = 0;
+        for (int ch = 0; ch < C; ++ch) {
+            const int64_t v = ir_of[k * C + ch];
+            if (v < 0) continue;
+            const int64_t len = s->irLen[(size_t)v];
+            if (std::find(lens, lens + n, len) == lens + n) lens[n++] = len;
+        }
+        return n;
+    };
 
     MRC_HIP(h, hipSetDevice(h->device));
     MRC_TRY(ensure_reverb_twiddles(h));
@@ -1424,14 +1472,15 @@ int reverb_loop(mrc_pac_store* s, const CheckedWindows& c, const WindowRun& run)
     hipStream_t st = pick_stream(h, q.stream);
     DrainGuard drain{{st, nullptr, nullptr}};
     const size_t elem = format == MRC_WINDOW_PCM16 ? 2 : format == MRC_WINDOW_F32 ? 4 : 8;
-    const int64_t M = (window + kRevB - 1) / kRevB, slab = run.slab, rowCap = std::max<int64_t>(1, 0x7fffffffLL / M);
+    // (a row takes M workgroups, a routed row at most M per channel: the fold's grid stays below 2^31)
+    const int64_t M = (window + kRevB - 1) / kRevB, slab = run.slab, rowCap = std::max<int64_t>(1, 0x7fffffffLL / (M * C));
     for (int64_t first = run.first, last; first < run.last; first = last) {   // rows [first, last), their terms [u0, u0 + nT)
         last = first + 1;
         while (last < run.last && last - first < rowCap && (slab == 0 || (term_offset[last + 1] - term_offset[first]) * Wd <= slab)) ++last;
         const int64_t nRows = last - first, u0 = term_offset[first], nT = term_offset[last] - u0;
-        unsigned char* outSlab = (unsigned char*)run.out + (size_t)(first - run.first) * nch * window * elem;
+        unsigned char* outSlab = (unsigned char*)run.out + (size_t)(first - run.first) * nchOut * window * elem;
         if (nT == 0) {                                       // rows without terms: +0.0
-            MRC_HIP(h, hipMemsetAsync(outSlab, 0, (size_t)nRows * nch * window * elem, st));
+            MRC_HIP(h, hipMemsetAsync(outSlab, 0, (size_t)nRows * nchOut * window * elem, st));
             s->stats[2] += 1;
             continue;
         }
@@ -1440,17 +1489,17 @@ int reverb_loop(mrc_pac_store* s, const CheckedWindows& c, const WindowRun& run)
         MRC_HIP(h, b.reverbDry.reserve(sizeof(double) * (size_t)(nT * nch * Wd)));
         MRC_TRY(units_loop(s, c, WindowRun{u0, u0 + nT, Wd, MRC_WINDOW_F64, b.reverbDry.p, 0, Lpre, true}));
 
-        // ---- the records (one H2D copy): terms | the rows' term offsets | sources
-        int64_t nConv = 0, nSpec = 0, maxSeg = 0;
+        // ---- the records (one H2D copy): terms, C routes each | the rows' term offsets | sources
+        int64_t nConv = 0, nSpec = 0, maxSeg = 0, lens[MRC_MAX_STORE_ROUTE_CHANNELS], specOf[MRC_MAX_STORE_ROUTE_CHANNELS];
         for (int64_t k = 0; k < nT; ++k)
-            if (ir_of[u0 + k] >= 0) {
-                const int64_t nSeg = M + (s->irLen[(size_t)ir_of[u0 + k]] + kRevB - 1) / kRevB - 1;
+            for (int i = 0, n = lengths_of(u0 + k, lens); i < n; ++i) {
+                const int64_t nSeg = M + (lens[i] + kRevB - 1) / kRevB - 1;
                 nConv += 1;
                 nSpec += nSeg;
                 maxSeg = std::max(maxSeg, nSeg);
             }
         StageLayout lay(256);
-        const size_t oTerms = lay.add<ReverbTerm>(nT), oRows = lay.add<long long>(nRows + 1), oSrc = lay.add<ReverbSource>(nConv);
+        const size_t oTerms = lay.add<ReverbTerm>(nT * C), oRows = lay.add<long long>(nRows + 1), oSrc = lay.add<ReverbSource>(nConv);
         MRC_HIP(h, b.reverbPin.reserve(lay.total()));
         MRC_HIP(h, b.reverbIn.reserve(lay.total()));
         MRC_HIP(h, b.reverbSpec.reserve(std::max<size_t>(sizeof(double2) * (size_t)(nSpec * kRevN), 256)));
@@ -1459,16 +1508,36 @@ int reverb_loop(mrc_pac_store* s, const CheckedWindows& c, const WindowRun& run)
         long long* rowTerms = (long long*)(pin + oRows);
         ReverbSource* src = (ReverbSource*)(pin + oSrc);
         for (int64_t r = 0; r <= nRows; ++r) rowTerms[r] = term_offset[first + r] - u0;
+        int64_t nWet = 0, nPaired = 0;                       // wet routes | those whose neighbour in a group of two shares their source
         for (int64_t k = 0, conv = 0, spec = 0; k < nT; ++k) {
-            const int64_t base = k * nch * Wd, v = ir_of[u0 + k];
-            if (v < 0) {
-                terms[k] = ReverbTerm{base + Lpre, -1, 0, 0, 0, q.gain[u0 + k]};
-                continue;
+            const int64_t base = k * nch * Wd;
+            const int n = lengths_of(u0 + k, lens);
+            for (int i = 0; i < n; ++i) {
+                const int64_t P = (lens[i] + kRevB - 1) / kRevB, nSeg = M + P - 1;
+                specOf[i] = spec;
+                src[conv++] = ReverbSource{base, nch == 2 ? base + Wd : -1, Lpre - P * kRevB, Lpre - (lens[i] - 1), Wd, spec, (int)nSeg, (int)kRevN};
+                spec += nSeg;
             }
-            const int64_t len = s->irLen[(size_t)v], P = (len + kRevB - 1) / kRevB, nSeg = M + P - 1;
-            terms[k] = ReverbTerm{base + Lpre, spec, s->irPart[(size_t)v], (int)P, 0, q.gain[u0 + k]};
-            src[conv++] = ReverbSource{base, nch == 2 ? base + Wd : -1, Lpre - P * kRevB, Lpre - (len - 1), Wd, spec, (int)nSeg, (int)kRevN};
-            spec += nSeg;
+            for (int ch = 0; ch < C; ++ch) {
+                const int64_t r = (u0 + k) * C + ch, v = ir_of[r];
+                if (v < 0) {                                 // -1 dry (kRouteDry), MRC_ROUTE_NONE absent (kRouteNone)
+                    terms[k * C + ch] = ReverbTerm{base + Lpre, v, 0, 0, 0, q.gain[r]};
+                    continue;
+                }
+                const int64_t len = s->irLen[(size_t)v];
+                terms[k * C + ch] = ReverbTerm{base + Lpre, specOf[std::find(lens, lens + n, len) - lens], s->irPart[(size_t)v],
+                                               (int)((len + kRevB - 1) / kRevB), 0, q.gain[r]};
+                nWet += 1;
+                if (ch & 1) nPaired += 2 * (terms[k * C + ch - 1].spec == terms[k * C + ch].spec);
+            }
+        }
+        // the channels one workgroup serves: two where at least half the slab's wet routes then load their spectra together
+        // (an array's microphones), else one -- measured; the option forces either, the bits are the same
+        const int group = h->storeRouteGroup ? h->storeRouteGroup : 2 * nPaired >= nWet && nWet > 0 ? 2 : 1;
+        if (routed) {
+            s->routeInfo[0] += nSpec;
+            s->routeInfo[1] += nWet * M;
+            s->routeInfo[2] += nSpec * kRevN * (int64_t)sizeof(double2);
         }
         // ---- device: forward transforms of the convolved terms' segments, then the rows
         unsigned char* din = b.reverbIn.as<unsigned char>();
@@ -1477,9 +1546,14 @@ int reverb_loop(mrc_pac_store* s, const CheckedWindows& c, const WindowRun& run)
         MRC_HIP(h, launch_reverb_forward(nConv, maxSeg, (const ReverbSource*)(din + oSrc), b.reverbDry.as<double>(),
                                          b.reverbTw.as<double2>(), b.reverbSpec.as<double2>(), st));
         MRC_HIP(h, hipEventRecord(b.reverbEv[1], st));
-        MRC_HIP(h, launch_reverb_fold(nRows, (const ReverbTerm*)(din + oTerms), (const long long*)(din + oRows), window, nch, format, Wd,
-                                      b.reverbDry.as<double>(), b.reverbSpec.as<double2>(), s->irBank.as<double2>(),
-                                      b.reverbTw.as<double2>(), outSlab, st));
+        if (routed)
+            MRC_HIP(h, launch_reverb_route_fold(nRows, (const ReverbTerm*)(din + oTerms), (const long long*)(din + oRows), window, C,
+                                                group, format, b.reverbDry.as<double>(), b.reverbSpec.as<double2>(),
+                                                s->irBank.as<double2>(), b.reverbTw.as<double2>(), outSlab, st));
+        else
+            MRC_HIP(h, launch_reverb_fold(nRows, (const ReverbTerm*)(din + oTerms), (const long long*)(din + oRows), window, nch, format,
+                                          Wd, b.reverbDry.as<double>(), b.reverbSpec.as<double2>(), s->irBank.as<double2>(),
+                                          b.reverbTw.as<double2>(), outSlab, st));
         MRC_HIP(h, hipEventRecord(b.reverbEv[2], st));
         MRC_HIP(h, hipStreamSynchronize(st));                // (the staging is written again by the next slab)
         MRC_TRY(add_elapsed(h, b.reverbEv, kReverbSpans, 2, s->reverbMs));
@@ -1492,9 +1566,10 @@ int reverb_loop(mrc_pac_store* s, const CheckedWindows& c, const WindowRun& run)
 // its rows under the handle's slab limit, and the reverb kernels' time counted into ms[3] once.
 int window_call(mrc_pac_store* s, const WindowRequest& q, int64_t window, int format, void* out) {
     MRC_TRY(store_alive(s, q.fn));
-    const bool reverb = q.kind == WindowRequest::kReverb;
+    const bool reverb = q.banked();
     reset_stats(s);
     if (reverb) s->reverbMs[0] = s->reverbMs[1] = 0.0;
+    if (q.routed()) s->routeInfo[0] = s->routeInfo[1] = s->routeInfo[2] = 0;
     CheckedWindows c;
     MRC_TRY(check_windows(s, q, window, format, out, &c));
     if (c.empty) return MRC_OK;
@@ -1509,6 +1584,7 @@ int window_call(mrc_pac_store* s, const WindowRequest& q, int64_t window, int fo
 // frames and transforms them on the same stream.  The twiddles, the frame window and the bank's supports and weights go up once
 // per call.
 const char* const kStft = "mrc_pac_store_stft_window";
+const char* const kStftRouted = "mrc_pac_store_stft_window_routed";
 
 // exp(-2 pi i t / n) for 0 <= t < n from long double, the quadrant taken out first: the axes are exact
 void stft_twiddles(int n, double2* w) {
@@ -1567,11 +1643,12 @@ int stft_call(mrc_pac_store* s, const WindowRequest& q, const StftArgs& a, int f
     MRC_TRY(store_alive(s, fn));
     mrc_handle* h = s->h;
     const std::string w = fn;
-    const int n_fft = a.n_fft, mode = a.mode, n_filters = a.n_filters, n_channels_out = q.nChannelsOut;
+    const int n_fft = a.n_fft, mode = a.mode, n_filters = a.n_filters, n_channels_out = q.rowChannels();
     const int64_t n_frames = a.n_frames, hop = a.hop;
     const double *const frame_window = a.frame_window, *const bank = a.bank;
     reset_stats(s);
     s->stftMs = s->reverbMs[0] = s->reverbMs[1] = 0.0;
+    if (q.routed()) s->routeInfo[0] = s->routeInfo[1] = s->routeInfo[2] = 0;
     // ---- this call's own arguments
     int nRad = 0;
     if (n_fft < 16 || n_fft > MRC_MAX_STFT_POINTS || (n_fft & 1) || stft_radices(n_fft / 2, &nRad) == 0)
@@ -1698,6 +1775,43 @@ int mrc_pac_store_stft_window(mrc_pac_store* s, int rate_divisor, int mix, int n
     q.nItems = n_items; q.termOffset = term_offset; q.file = file; q.start = start; q.gain = gain; q.irOf = ir_of;
     q.nChannelsOut = n_channels_out; q.stream = stream;
     return stft_call(s, q, StftArgs{n_fft, frame_window, n_frames, hop, mode, n_filters, bank}, format, out);
+}
+
+int mrc_pac_store_decode_window_routed(mrc_pac_store* s, int rate_divisor, int mix, int n_ratios, const int32_t* ratio_up,
+                                       const int32_t* ratio_down, int zeros, double rolloff, int n_bands, const double* edge_hz,
+                                       const double* band_gain, int64_t n_items, const int64_t* term_offset, const int64_t* file,
+                                       const int64_t* start, const int32_t* ratio_of, const double* route_gain,
+                                       const int32_t* route_ir, int64_t window, int n_channels_out, int format, void* out,
+                                       void* stream) {
+    WindowRequest q{kWinRouted, WindowRequest::kRouted};
+    q.rateDivisor = rate_divisor; q.mix = mix; q.zeros = zeros; q.rolloff = rolloff;
+    q.ratioList = true; q.nRatios = n_ratios; q.ratioUp = ratio_up; q.ratioDown = ratio_down; q.ratioOf = ratio_of;
+    q.banded = n_bands != 0; q.nBands = n_bands; q.edgeHz = edge_hz; q.bandGain = band_gain;
+    q.nItems = n_items; q.termOffset = term_offset; q.file = file; q.start = start; q.gain = route_gain; q.irOf = route_ir;
+    q.nChannelsOut = 1; q.routeChannels = n_channels_out; q.stream = stream;
+    return window_call(s, q, window, format, out);
+}
+
+int mrc_pac_store_stft_window_routed(mrc_pac_store* s, int rate_divisor, int mix, int n_ratios, const int32_t* ratio_up,
+                                     const int32_t* ratio_down, int zeros, double rolloff, int n_bands, const double* edge_hz,
+                                     const double* band_gain, int64_t n_items, const int64_t* term_offset, const int64_t* file,
+                                     const int64_t* start, const int32_t* ratio_of, const double* route_gain,
+                                     const int32_t* route_ir, int n_fft, const double* frame_window, int64_t n_frames, int64_t hop,
+                                     int mode, int n_filters, const double* bank, int n_channels_out, int format, void* out,
+                                     void* stream) {
+    WindowRequest q{kStftRouted, WindowRequest::kStftRouted};
+    q.rateDivisor = rate_divisor; q.mix = mix; q.zeros = zeros; q.rolloff = rolloff;
+    q.ratioList = true; q.nRatios = n_ratios; q.ratioUp = ratio_up; q.ratioDown = ratio_down; q.ratioOf = ratio_of;
+    q.banded = n_bands != 0; q.nBands = n_bands; q.edgeHz = edge_hz; q.bandGain = band_gain;
+    q.nItems = n_items; q.termOffset = term_offset; q.file = file; q.start = start; q.gain = route_gain; q.irOf = route_ir;
+    q.nChannelsOut = 1; q.routeChannels = n_channels_out; q.stream = stream;
+    return stft_call(s, q, StftArgs{n_fft, frame_window, n_frames, hop, mode, n_filters, bank}, format, out);
+}
+
+int mrc_pac_store_route_info(mrc_pac_store* s, int64_t* counts) {
+    MRC_TRY(store_alive(s, "mrc_pac_store_route_info"));
+    for (int i = 0; counts && i < 3; ++i) counts[i] = s->routeInfo[i];
+    return MRC_OK;
 }
 
 int mrc_pac_store_decode_window(mrc_pac_store* s, int64_t n_items, const int64_t* file, const int64_t* start, int64_t window,

@@ -403,6 +403,7 @@ struct mrc_pac_store {
     // every loop it runs adds to it, and the reverb and STFT kernels' times are counted into ms[3] once, at the end.
     double reverbMs[2] = {0, 0};     // last decode_window_reverb or stft_window: reverb_forward_kernel | reverb_fold_kernel
     double stftMs = 0;               // last stft_window: stft_kernel, summed over the slabs
+    int64_t routeInfo[3] = {0, 0, 0};   // last routed call: forward segments transformed, inverse transforms, bytes of spectra
     int64_t stats[4] = {0, 0, 0, 0}; // last decode_window: chunks parsed, decode_kernel launches, slabs, plan bytes uploaded
     double ms[4] = {0, 0, 0, 0};     // ... plan upload | unpack | synthesis | window_out_kernel (resampled: resample_out_kernel)
                                      // (after block_energy: block_energy_kernel launches in [1]; ms: upload | unpack | that kernel | 0;
@@ -437,6 +438,7 @@ struct mrc_handle {
     mrc::StoreBufs store;            // mrc_pac_store_decode_window: see mrc_api_store.cpp
     std::vector<mrc_pac_store*> stores;   // the live stores of this handle (not owned: mrc_pac_store_destroy deletes them)
     int64_t storeSlabSamples = (int64_t)1 << 24;   // mrc_set_option(MRC_OPT_STORE_SLAB_SAMPLES)
+    int storeRouteGroup = 0;         // mrc_set_option(MRC_OPT_STORE_ROUTE_GROUP): channels per workgroup of reverb_route_fold_kernel; 0: per slab
     double chainMs[4] = {0, 0, 0, 0};   // last chained encode: phase A, phase B, pack, whole call (host clock)
     bool timing = false;
     bool exactSpread = false;        // mrc_set_option(MRC_OPT_EXACT_SPREAD)

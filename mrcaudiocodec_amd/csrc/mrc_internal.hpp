@@ -339,6 +339,17 @@ struct ReverbTerm {
 hipError_t launch_reverb_fold(int64_t nRows, const ReverbTerm* terms /* device */, const long long* termOffset /* device */,
                               int64_t window, int nchOut, int format, int64_t chStride, const double* dry, const double2* spectra,
                               const double2* bank, const double2* twiddle, void* out, hipStream_t st);
+// mrc_pac_store_decode_window_routed: a term has one dry channel and a route per output channel, routes [term][nChannels], each a
+// ReverbTerm whose spec is kRouteNone (no contribution), kRouteDry, or the first spectrum of the term's source of that
+// response's length (routes of one length share a source); .dry is the term's dry channel in every record.
+// out [nRows][nChannels][window]: channel c is launch_reverb_fold's one-channel row over the routes to c that are not absent,
+// bit for bit.  One workgroup per (row, output block, group of `group` channels: 1 or 2); a channel's bits do not depend on
+// the group.
+constexpr long long kRouteDry = -1, kRouteNone = -2;
+inline int64_t reverb_route_groups(int nChannels, int group) { return (nChannels + group - 1) / group; }
+hipError_t launch_reverb_route_fold(int64_t nRows, const ReverbTerm* routes /* device */, const long long* termOffset /* device */,
+                                    int64_t window, int nChannels, int group, int format, const double* dry, const double2* spectra,
+                                    const double2* bank, const double2* twiddle, void* out, hipStream_t st);
 // mrc_pac_store_stft_window (mrc_kernels_stft.hip).  rows (device) float64 [nRows][nch][L], L = (nFrames - 1) hop + nFft;
 // win (device) [nFft]; tw (device) exp(-2 pi i t / nFft) for 0 <= t < nFft; radices: the passes of the nFft / 2 point complex
 // transform, four bits each from the lowest (stft_radices); mode MRC_STFT_*, format MRC_WINDOW_F32 | _F64.  MRC_STFT_BANK:

@@ -26,8 +26,17 @@
 //   way.  One inverse transform per convolved term: a term's y then depends on that term alone, and the row is the documented
 //   fold over its terms whatever their kinds.  store_window_value converts the sum once.
 //
-// LDS: two buffers of N double2 and the twiddle quadrant, 72 KiB at N = 2048 -- two workgroups per CU.  No atomics; nothing
-// depends on the grid.
+// reverb_route_fold_kernel<G>   the fold of mrc_pac_store_decode_window_routed: one workgroup per (row, output block, group of
+//   up to G output channels).  A term has ONE dry channel and a route record per output channel -- absent, dry, or a response
+//   with the spectra of the term's source of that response's length.  Per channel the arithmetic is reverb_fold_kernel's,
+//   expression for expression (the library is built without FMA contraction): the dry fold, Z = sum_p X[m - p] H[p] with p
+//   ascending, ONE inverse transform per (term, channel), the gain's product rounded once, then added.  What the group shares
+//   is the load of X: the channels of the group whose routes name the same source -- responses of one length -- walk the
+//   partitions together, eight X bins per thread loaded once per partition for all of them.  A channel's bits depend on its
+//   own routes alone, whatever shares its group.
+//
+// LDS: two buffers of N double2 and the twiddle quadrant, 72 KiB at N = 2048 -- two workgroups per CU, all three kernels.  No
+// atomics; nothing depends on the grid.
 #include "mrc_device.hpp"
 
 namespace mrc {
@@ -152,6 +161,106 @@ __global__ __launch_bounds__(kReverbThreads) void reverb_fold_kernel(const Rever
     }
 }
 
+// routes [term][C] (ReverbTerm: spec kRouteDry, kRouteNone or the source's first spectrum; .dry the term's one dry channel in
+// every record); out [row][C][window]
+template <int G>
+__global__ __launch_bounds__(kReverbThreads) void reverb_route_fold_kernel(const ReverbTerm* __restrict__ routes,
+                                                                           const long long* __restrict__ termOffset, int64_t window,
+                                                                           int64_t blocks, int C, int groups, int format,
+                                                                           const double* __restrict__ dry,
+                                                                           const double2* __restrict__ spectra,
+                                                                           const double2* __restrict__ bank,
+                                                                           const double2* __restrict__ twiddle, void* __restrict__ out) {
+    __shared__ double2 A[kN], Bf[kN], wq[kN / 4];
+    const int tid = threadIdx.x;
+    const int64_t cell = (int64_t)blockIdx.x / groups, row = cell / blocks, m = cell - row * blocks;
+    const int c0 = (int)((int64_t)blockIdx.x - cell * groups) * G, nc = min(G, C - c0);      // channels [c0, c0 + nc): >= 1
+    for (int i = tid; i < kN / 4; i += kReverbThreads) wq[i] = twiddle[i];
+    const int64_t jEnd = termOffset[row + 1];
+    double acc[G][kOuts];
+#pragma unroll
+    for (int i = 0; i < G; ++i)
+#pragma unroll
+        for (int q = 0; q < kOuts; ++q) acc[i][q] = 0.0;
+    for (int64_t j = termOffset[row]; j < jEnd; ++j) {
+        // the term's routes to the group's channels: the same for the whole workgroup
+        ReverbTerm rt[G];
+        bool anyDry = false;
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            rt[i] = routes[j * C + c0 + min(i, nc - 1)];
+            if (i >= nc) rt[i].spec = kRouteNone;
+            anyDry = anyDry || rt[i].spec == kRouteDry;
+        }
+        if (anyDry) {                                                // dry: sum_out_kernel's fold, the sample loaded once
+#pragma unroll
+            for (int q = 0; q < kOuts; ++q) {
+                const int64_t t = m * kB + tid + q * kReverbThreads;
+                if (t >= window) continue;
+                const double v = dry[rt[0].dry + t];
+#pragma unroll
+                for (int i = 0; i < G; ++i)
+                    if (rt[i].spec == kRouteDry) acc[i][q] = __dadd_rn(acc[i][q], __dmul_rn(rt[i].gain, v));
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < G; ++i) {                                // wet: channel i leads the channels behind it on its source
+            if (rt[i].spec < 0) continue;
+            bool led = false;
+#pragma unroll
+            for (int e = 0; e < i; ++e) led = led || rt[e].spec == rt[i].spec;
+            if (led) continue;                                       // (done with channel e)
+            double2 z[G][kBins];
+#pragma unroll
+            for (int e = i; e < G; ++e)
+#pragma unroll
+                for (int q = 0; q < kBins; ++q) z[e][q] = make_double2(0.0, 0.0);
+            const double2* X = spectra + (rt[i].spec + m + rt[i].nPart - 1) * kN + tid;     // segment m - p: kN back per partition
+            for (int p = 0; p < rt[i].nPart; ++p, X -= kN) {
+                double2 x[kBins];
+#pragma unroll
+                for (int q = 0; q < kBins; ++q) x[q] = X[q * kReverbThreads];
+#pragma unroll
+                for (int e = i; e < G; ++e) {
+                    if (rt[e].spec != rt[i].spec) continue;          // (one source: one length, one nPart)
+                    const double2* H = bank + (rt[e].ir + p) * kN + tid;
+                    double2 h[kBins];
+#pragma unroll
+                    for (int q = 0; q < kBins; ++q) h[q] = H[q * kReverbThreads];
+#pragma unroll
+                    for (int q = 0; q < kBins; ++q) {
+                        const double2 v = cmul(x[q], h[q]);
+                        z[e][q] = make_double2(z[e][q].x + v.x, z[e][q].y + v.y);
+                    }
+                }
+            }
+#pragma unroll
+            for (int e = i; e < G; ++e) {                            // one inverse transform per (term, channel)
+                if (rt[e].spec != rt[i].spec) continue;
+                __syncthreads();                                     // (the twiddles staged; the last reads of A done)
+#pragma unroll
+                for (int q = 0; q < kBins; ++q) A[tid + q * kReverbThreads] = make_double2(z[e][q].x, -z[e][q].y);
+                __syncthreads();
+                const double2* T = reverb_fft(A, Bf, wq, tid);
+#pragma unroll
+                for (int q = 0; q < kOuts; ++q) {
+                    const double2 v = T[kB + tid + q * kReverbThreads];
+                    acc[e][q] = __dadd_rn(acc[e][q], __dmul_rn(rt[e].gain, v.x * (1.0 / kN)));
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < G; ++i) {
+        if (i >= nc) continue;
+#pragma unroll
+        for (int q = 0; q < kOuts; ++q) {
+            const int64_t t = m * kB + tid + q * kReverbThreads;
+            if (t < window) store_window_value(out, (row * C + c0 + i) * window + t, format, acc[i][q]);
+        }
+    }
+}
+
 }  // namespace
 
 hipError_t launch_reverb_forward(int64_t nSources, int64_t maxSeg, const ReverbSource* sources, const double* samples,
@@ -171,6 +280,24 @@ hipError_t launch_reverb_fold(int64_t nRows, const ReverbTerm* terms, const long
     if (nRows > 0x7fffffffLL / blocks) return hipErrorInvalidValue;
     hipLaunchKernelGGL(reverb_fold_kernel, dim3((unsigned)(nRows * blocks)), dim3(kReverbThreads), 0, st, terms, termOffset, window,
                        blocks, nchOut, format, chStride, dry, spectra, bank, twiddle, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_reverb_route_fold(int64_t nRows, const ReverbTerm* routes, const long long* termOffset, int64_t window,
+                                    int nChannels, int group, int format, const double* dry, const double2* spectra,
+                                    const double2* bank, const double2* twiddle, void* out, hipStream_t st) {
+    const int64_t blocks = (window + kB - 1) / kB, groups = reverb_route_groups(nChannels, group);
+    if (nRows <= 0 || blocks <= 0) return hipSuccess;
+    if (nChannels < 1 || nRows > 0x7fffffffLL / (blocks * groups)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(nRows * blocks * groups)), threads(kReverbThreads);
+    if (group == 1)
+        hipLaunchKernelGGL(reverb_route_fold_kernel<1>, grid, threads, 0, st, routes, termOffset, window, blocks, nChannels, (int)groups,
+                           format, dry, spectra, bank, twiddle, out);
+    else if (group == 2)
+        hipLaunchKernelGGL(reverb_route_fold_kernel<2>, grid, threads, 0, st, routes, termOffset, window, blocks, nChannels, (int)groups,
+                           format, dry, spectra, bank, twiddle, out);
+    else
+        return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

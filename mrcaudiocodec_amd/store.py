@@ -320,6 +320,79 @@ def check_ir_index(ir_index, unit_shape, n_irs, what="decode_window"):
     return np.ascontiguousarray(idx.astype(np.int32))
 
 
+ROUTE_NONE = _lib.MRC_ROUTE_NONE                      # route_irs: the term does not reach this channel
+MAX_ROUTE_CHANNELS = _lib.MRC_MAX_STORE_ROUTE_CHANNELS
+
+
+def check_routes(route_gains, route_irs, n_terms, n_irs, what="decode_window_routed"):
+    """the routes of a routed window call -> (gains float64 [n_terms][C], irs int32 [n_terms][C]), contiguous, else ValueError:
+    two arrays of ONE shape, the call's terms (any leading axes with n_terms entries in all) and a last axis of 1 to
+    MAX_ROUTE_CHANNELS output channels; gains finite numbers; irs ints, each ROUTE_NONE (the term does not reach the channel),
+    -1 (dry) or an index into the store's bank of n_irs impulse responses"""
+    try:
+        g = np.asarray(route_gains)
+        if g.dtype == object or g.dtype.kind not in "fiu":
+            raise TypeError
+        g = g.astype(np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("%s: route_gains must be numbers, got %r" % (what, route_gains))
+    try:
+        idx = np.asarray(route_irs)
+        if idx.dtype == object or idx.dtype.kind not in "iu":
+            raise TypeError
+    except (TypeError, ValueError):
+        raise ValueError("%s: route_irs must be ints, got %r" % (what, route_irs))
+    n_terms = int(n_terms)
+    if g.shape != idx.shape or g.ndim < 2 or not 1 <= g.shape[-1] <= MAX_ROUTE_CHANNELS or \
+            int(np.prod(g.shape[:-1], dtype=np.int64)) != n_terms:
+        raise ValueError("%s: route_gains and route_irs must have one shape, the %d terms and a last axis of 1 to %d channels, "
+                         "got %s and %s" % (what, n_terms, MAX_ROUTE_CHANNELS, g.shape, idx.shape))
+    n_ch = g.shape[-1]
+    g, idx = g.reshape(n_terms, n_ch), idx.reshape(n_terms, n_ch)
+    at = lambda bad: (int(bad[0]) // n_ch, int(bad[0]) % n_ch)
+    bad = np.flatnonzero(~np.isfinite(g))
+    if bad.size:
+        raise ValueError("%s: route_gains must be finite, got %r at term %d, channel %d" % ((what, float(g.flat[bad[0]])) + at(bad)))
+    bad = np.flatnonzero(idx < ROUTE_NONE)
+    if bad.size:
+        raise ValueError("%s: route_irs must be ROUTE_NONE (%d), -1 or an index into the bank, got %d at term %d, channel %d"
+                         % ((what, ROUTE_NONE, int(idx.flat[bad[0]])) + at(bad)))
+    bad = np.flatnonzero(idx >= n_irs)
+    if bad.size:
+        if n_irs == 0:
+            raise ValueError("%s: route_irs names impulse response %d at term %d, channel %d, but the store has none "
+                             "(set_impulse_responses)" % ((what, int(idx.flat[bad[0]])) + at(bad)))
+        raise ValueError("%s: route_irs must be ROUTE_NONE (%d), -1 or lie in 0..%d (the store's impulse responses), got %d at "
+                         "term %d, channel %d" % ((what, ROUTE_NONE, n_irs - 1, int(idx.flat[bad[0]])) + at(bad)))
+    return np.ascontiguousarray(g), np.ascontiguousarray(idx.astype(np.int32))
+
+
+def array_routes(room_of, n_mics, gains=None):
+    """The routes of terms heard by a microphone array -> (route_gains float64, route_irs int32), both of room_of's shape plus a
+    last axis [n_mics], for a bank laid out room-major: microphone c of room r is impulse response r * n_mics + c.  room_of:
+    ints, the room of every term; -1: the term is dry on every channel.  gains: None (1.0), or numbers of room_of's shape (one
+    gain per term, the same on every microphone) or of the result's shape.  ValueError for rooms that are not ints >= -1, an
+    n_mics outside 1..MAX_ROUTE_CHANNELS and gains of another shape."""
+    what = "array_routes"
+    if not _is_int(n_mics) or not 1 <= int(n_mics) <= MAX_ROUTE_CHANNELS:
+        raise ValueError("%s: n_mics must be an int in 1..%d, got %r" % (what, MAX_ROUTE_CHANNELS, n_mics))
+    n_mics = int(n_mics)
+    rooms = np.asarray(room_of)
+    if rooms.dtype == object or rooms.dtype.kind not in "iu" or (rooms.size and int(rooms.min()) < -1):
+        raise ValueError("%s: room_of must be ints >= -1 (-1: a dry term), got %r" % (what, room_of))
+    rooms = rooms.astype(np.int64)
+    irs = np.where(rooms[..., None] < 0, -1, rooms[..., None] * n_mics + np.arange(n_mics, dtype=np.int64))
+    g = np.ones(irs.shape, np.float64)
+    if gains is not None:
+        gains = np.asarray(gains, dtype=np.float64)
+        if gains.shape == rooms.shape:
+            gains = gains[..., None]
+        elif gains.shape != irs.shape:
+            raise ValueError("%s: gains must have shape %s or %s, got %s" % (what, rooms.shape, irs.shape, gains.shape))
+        g = g * gains
+    return g, irs.astype(np.int32)
+
+
 def ir_at_rate(ir, rate_in, rate_out):
     """A recorded room impulse response at the rate the terms are read at -> float64 [ceil(len(ir) * rate_out / rate_in)].  Host
     NumPy over the library's own polyphase filter (resample_taps(up, down), up / down = rate_out / rate_in reduced): output n
@@ -685,11 +758,14 @@ def _formats():
     return {torch.int16: _lib.MRC_WINDOW_PCM16, torch.float32: _lib.MRC_WINDOW_F32, torch.float64: _lib.MRC_WINDOW_F64}
 
 
-class WindowRows(collections.namedtuple("WindowRows", "rate_divisor mix resample channels bands speeds irs offsets files starts gains")):
+class WindowRows(collections.namedtuple("WindowRows", "rate_divisor mix resample channels bands speeds irs offsets files starts gains routes",
+                                        defaults=(None,))):
     """The checked row arguments of a window call: rate_divisor an int, mix None or its MRC_MIX_* value, resample None or
     (up, down, zeros, rolloff), channels as given (1 under a mix), bands None or (edges, gains [terms][n_bands]), speeds None or
     (ratios, zeros, rolloff, index int32 [terms]), irs None or int32 [terms], offsets int64 [rows + 1], files, starts and gains
-    flat and contiguous.  decode_window's items are rows of one term each at gain 1.0."""
+    flat and contiguous.  decode_window's items are rows of one term each at gain 1.0.  routes: None, or check_routes' (gains
+    float64 [terms][C], irs int32 [terms][C]) of a routed call -- gains and irs are then not looked at, and channels is 1, what
+    every term gives."""
     __slots__ = ()
 
 
@@ -699,6 +775,8 @@ def window_entry(store, rows, caller, window, channels, fmt, out, stream, stft=N
     "decode_window_sum" or "stft_window"; store, out and stream: the store's pointer, the output's and the stream as ints or
     None (no device is needed to ask); stft: stft_window's (n_fft, window array, n_frames, hop, mode, matrix or None).  keep
     holds the arrays made here whose pointers args carries.  The entry per combination, first match:
+        routes given: stft_window            mrc_pac_store_stft_window_routed  (route_gain and route_ir in place of gain and
+                      else                   ..._routed                         ir_of; `channels` is the routes' last axis)
         stft_window                          mrc_pac_store_stft_window (ratios default to the one base ratio, ir_of to -1)
         ir_index given                       ..._reverb
         speeds given                         ..._speeds
@@ -718,7 +796,7 @@ def window_entry(store, rows, caller, window, channels, fmt, out, stream, stft=N
         bands = (0, None, None)
     else:
         bands = (rows.bands[0].size - 1, rows.bands[0].ctypes.data, pad(rows.bands[1]))
-    if stft is not None or rows.irs is not None or rows.speeds is not None:      # the entries that take a list of ratios
+    if stft is not None or rows.irs is not None or rows.speeds is not None or rows.routes is not None:   # ... take a list of ratios
         ratios, zeros, rolloff, index = rows.speeds or ([(up, down)], zeros, rolloff, np.zeros(rows.files.size, np.int32))
         ups = np.ascontiguousarray([r[0] for r in ratios], dtype=np.int32)
         downs = np.ascontiguousarray([r[1] for r in ratios], dtype=np.int32)
@@ -729,6 +807,12 @@ def window_entry(store, rows, caller, window, channels, fmt, out, stream, stft=N
             n_fft, frame_window, n_frames, hop, mode, matrix = stft
             own = (n_fft, frame_window.ctypes.data, n_frames, hop, mode, 0 if matrix is None else matrix.shape[0],
                    None if matrix is None else matrix.ctypes.data)
+        if rows.routes is not None:                          # (gain and ir_of leave, the two route arrays stand in their place)
+            routed = head[:-2] + (pad(index), pad(rows.routes[0]), pad(rows.routes[1]))
+            if stft is not None:
+                return "mrc_pac_store_stft_window_routed", routed + own + tail[1:], keep
+            return "mrc_pac_store_decode_window_routed", routed + tail, keep
+        if stft is not None:
             return "mrc_pac_store_stft_window", head + (pad(irs),) + own + tail[1:], keep
         if rows.irs is not None:
             return "mrc_pac_store_decode_window_reverb", head + (pad(irs),) + tail, keep
@@ -1035,6 +1119,55 @@ class PacStore:
         fmt, channels, out, stream = self._window_out(what, n, rows.files, window, rows.channels, dtype, out, stream)
         return self._call_window(rows, what, window, channels, fmt, out, stream)
 
+    def decode_window_routed(self, files, starts, route_gains, route_irs, window, item_offsets=None, dtype=None, out=None,
+                             stream=None, rate_divisor=1, mix=None, resample=None, band_gains=None, band_edges_hz=None,
+                             speed_factors=None, speed_index=None):
+        """mrc_pac_store_decode_window_routed -> a torch tensor [n][C][window] on the handle's device: rows of C OUTPUT channels
+        from terms that each give ONE channel, with a gain and a response per (term, output channel) -- an utterance through the
+        C microphones of a room (array_routes builds the routes), or the reverberant mixture, the dry speech and the noise
+        alone of the same terms as three channels -- in one call that parses, synthesises and transforms every term once.
+        files, starts, item_offsets: as decode_window_sum's ([n][K], or 1-D with item_offsets).  route_gains, route_irs: the
+        shape of files plus a last axis [C], 1 <= C <= MAX_ROUTE_CHANNELS; route_irs[k][c] is ROUTE_NONE (term k does not reach
+        channel c), -1 (dry) or an index into the store's bank (set_impulse_responses).
+        Channel c of item i is, bit for bit and in every dtype, decode_window_sum(..., ir_index=)[i][0] over the item's terms whose
+        route to c is not ROUTE_NONE, in the order given, with gains route_gains[:, c] and ir_index route_irs[:, c], every
+        other argument equal; a channel no term reaches is +0.0.  Nothing depends on which other channels the call has.
+        mix: "mid", "left" or "right"; None only where every file named is mono (the library refuses a stereo file then).
+        window, dtype, out, stream, rate_divisor, resample, band_gains, band_edges_hz, speed_factors, speed_index: as
+        decode_window_sum's, per term.  Routes of another shape, gains that are not finite and an index below ROUTE_NONE or
+        outside the bank are ValueErrors (check_routes), before any library call.  route_info() says what the call shared."""
+        what = "decode_window_routed"
+        files, starts = self._routed_terms(what, files, starts)
+        rows = self._sum_rows(what, files, starts, np.ones(files.shape, np.float64), item_offsets, None, rate_divisor, mix, resample,
+                              band_gains, band_edges_hz, speed_factors, speed_index, None)
+        routes = check_routes(route_gains, route_irs, rows.files.size, self._ir_lengths.size, what)
+        rows = rows._replace(channels=1, routes=routes)
+        n, window, n_ch = rows.offsets.size - 1, int(window), routes[0].shape[1]
+        import torch
+        if dtype is None:
+            dtype = torch.int16 if out is None else out.dtype
+        fmt = _formats().get(dtype)
+        if fmt is None:
+            raise ValueError("%s: dtype must be torch.int16, torch.float32 or torch.float64, got %s" % (what, dtype))
+        out, stream = self._out_tensor(what, (n, n_ch, max(window, 0)), dtype, out, stream)
+        return self._call_window(rows, what, window, n_ch, fmt, out, stream)
+
+    @staticmethod
+    def _routed_terms(what, files, starts):
+        """files and starts of a routed call as int64 arrays of one shape, else ValueError (a routed call has no gains to name)"""
+        files, starts = np.asarray(files, dtype=np.int64), np.asarray(starts, dtype=np.int64)
+        if files.shape != starts.shape:
+            raise ValueError("%s: files and starts must have one shape, got %s and %s" % (what, files.shape, starts.shape))
+        return files, starts
+
+    def route_info(self):
+        """mrc_pac_store_route_info: what the last routed call (decode_window_routed, stft_window(route_gains=)) did, summed
+        over its slabs -- forward_segments transformed (one source per term and distinct response length among its wet routes),
+        inverse_transforms (one per wet route and output block) and the spectra_bytes written"""
+        counts = np.zeros(3, np.int64)
+        self._handle._check(lib.mrc_pac_store_route_info(self._s, counts.ctypes.data))
+        return {"forward_segments": int(counts[0]), "inverse_transforms": int(counts[1]), "spectra_bytes": int(counts[2])}
+
     def _sum_rows(self, what, files, starts, gains, item_offsets, channels, rate_divisor, mix, resample, band_gains, band_edges_hz,
                   speed_factors, speed_index, ir_index):
         """the row arguments of decode_window_sum and stft_window, checked in the one order -> a WindowRows; ValueError as
@@ -1072,7 +1205,8 @@ class PacStore:
 
     def stft_window(self, files, starts, n_frames, hop, n_fft, frame_window=None, bank=None, output="power", center=False,
                     gains=None, item_offsets=None, channels=None, dtype=None, out=None, stream=None, rate_divisor=1, mix=None,
-                    resample=None, band_gains=None, band_edges_hz=None, speed_factors=None, speed_index=None, ir_index=None):
+                    resample=None, band_gains=None, band_edges_hz=None, speed_factors=None, speed_index=None, ir_index=None,
+                    route_gains=None, route_irs=None):
         """mrc_pac_store_stft_window -> a torch tensor [n][channels][n_fft // 2 + 1 | filters][n_frames] on the handle's device:
         the short-time Fourier transform of the rows decode_window_sum gives on the same row arguments, without the rows ever
         being written out.  Row i is that call's float64 row over (n_frames - 1) hop + n_fft samples from its terms' starts;
@@ -1090,10 +1224,26 @@ class PacStore:
         decode_window_sum's.  channels, stream, rate_divisor, mix, resample, band_gains, band_edges_hz, speed_factors,
         speed_index, ir_index: decode_window_sum's, unchanged.  dtype: torch.float32 (the default) or torch.float64 (complex64
         or complex128 for output="complex"); out: a contiguous tensor of the result's shape and dtype.  Argument errors are
-        ValueErrors before any library call."""
+        ValueErrors before any library call.
+        route_gains, route_irs: None, or the routes of decode_window_routed (mrc_pac_store_stft_window_routed): the result is
+        [n][C][n_fft // 2 + 1 | filters][n_frames], channel c the transform of that call's channel c, bit for bit.  They stand in
+        the place of gains and ir_index and are refused together with either, and with channels; files and starts are 1-D (one
+        term per item, or terms with item_offsets) or [n][K]."""
         import torch
         what = "stft_window"
         n_fft, hop, n_frames, window, matrix, mode = check_stft(n_fft, hop, n_frames, frame_window, bank, output, what)
+        routed = route_gains is not None or route_irs is not None
+        if routed:
+            if route_gains is None or route_irs is None:
+                raise ValueError("%s: route_gains and route_irs go together, got only %s"
+                                 % (what, "route_irs" if route_gains is None else "route_gains"))
+            for name, v in (("gains", gains), ("ir_index", ir_index), ("channels", channels)):
+                if v is not None:
+                    raise ValueError("%s: route_gains and route_irs stand in the place of gains and ir_index and give the channels; "
+                                     "%s must be None with them" % (what, name))
+            files, starts = self._routed_terms(what, files, starts)
+            if item_offsets is not None or files.ndim != 1:
+                gains = np.ones(files.shape, np.float64)
         if gains is None:
             files = np.asarray(files, dtype=np.int64).reshape(-1)
             starts = np.asarray(starts, dtype=np.int64).reshape(-1)
@@ -1120,8 +1270,13 @@ class PacStore:
         real_dtype = real[dtype]
         result_dtype = {torch.float32: torch.complex64, torch.float64: torch.complex128}[real_dtype] if is_complex else real_dtype
         n_out = matrix.shape[0] if matrix is not None else n_fft // 2 + 1
-        channels, out, stream = self._out_side(what, rows.files, rows.channels, lambda c: (n, c, n_out, n_frames), result_dtype, out,
-                                               stream, one_or_two=True)
+        if routed:
+            routes = check_routes(route_gains, route_irs, rows.files.size, self._ir_lengths.size, what)
+            rows, channels = rows._replace(channels=1, routes=routes), routes[0].shape[1]
+            out, stream = self._out_tensor(what, (n, channels, n_out, n_frames), result_dtype, out, stream)
+        else:
+            channels, out, stream = self._out_side(what, rows.files, rows.channels, lambda c: (n, c, n_out, n_frames), result_dtype,
+                                                   out, stream, one_or_two=True)
         return self._call_window(rows, what, n_frames, channels, _formats()[real_dtype], out, stream,
                                  stft=(n_fft, window, n_frames, hop, mode, matrix))
 
