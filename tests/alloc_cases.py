@@ -44,18 +44,25 @@ def group_size(n_tot):
 
 
 def layout(cfg):
-    """the band table and sizes of a configuration"""
-    a, b, joint, tbps = cfg
+    """the band table and sizes of a configuration (with a fifth entry, a setting of tests/settings_kit.py: that setting's)"""
+    a, b, joint, tbps = cfg[:4]
 
     def make():
-        sfb = fast.bands_for(a, b)
+        P, max_mant = params(tbps), MAX_MANT
+        if len(cfg) > 4:
+            import settings_kit as sk
+            f = sk.full(cfg[4])
+            P = dict(sampleRate=f["sample_rate"], nMDCTLines=f["n_mdct_lines"], nScaleBits=f["n_scale_bits"],
+                     nMantSizeBits=f["n_mant_size_bits"], targetBitsPerSample=tbps, blkswBitA=f["blksw_bits_a"],
+                     blkswBitB=f["blksw_bits_b"])
+            max_mant = sk.max_mant_bits(cfg[4])
+        sfb = fast.bands_for(a, b, P["nMDCTLines"], P["sampleRate"])
         nb, half = sfb.nBands, (a + b) // 2
         ns = 2 if joint else 1
         n_lines = np.tile(np.asarray(sfb.nLines, dtype=np.int64), ns)
-        P = params(tbps)
         base = fast.joint_budget(P, half, nb, 0) if joint else fast.mono_budget(P, half, nb)
         return dict(sfb=sfb, nb=nb, half=half, ns=ns, nsig=4 if joint else 1, n_tot=ns * nb, n_lines=n_lines, base=base,
-                    fill=MAX_MANT * int(n_lines.sum()), P=P)
+                    fill=max_mant * int(n_lines.sum()), P=P, max_mant=max_mant, n_scale_bits=P["nScaleBits"])
     return _cached(("layout",) + tuple(cfg), make)
 
 
@@ -130,7 +137,9 @@ def _edge_values():
 
 def make_lines(cfg, n, rng):
     """-> lines [n][nsig][half] (unscaled), overall_scale [n][nsig].  |line * 2^overall_scale| < 1 for every signal.  Joint:
-    per band R = L (switch on) or R = 0 (off), M and S independent data."""
+    per band R = L (switch on) or R = 0 (off), M and S independent data.  (On these two inputs every order of summation
+    gives the same switch: the decisions themselves are exercised by tests/ms_switch_cases.py, whose bands sit on the
+    threshold.)"""
     lay = layout(cfg)
     sfb, nb, half, nsig, joint = lay["sfb"], lay["nb"], lay["half"], lay["nsig"], cfg[2]
     edge = _edge_values()
@@ -206,7 +215,7 @@ def _quantise(cfg, coded, bits):
     """fast._quantise_batch per stream -> scale_factor [n][ns][nb], mantissa [n][ns][half]"""
     lay = layout(cfg)
     nb = lay["nb"]
-    sf, mant = zip(*[fast._quantise_batch(coded[:, s], bits[:, s * nb:(s + 1) * nb], lay["sfb"], N_SCALE_BITS)
+    sf, mant = zip(*[fast._quantise_batch(coded[:, s], bits[:, s * nb:(s + 1) * nb], lay["sfb"], lay["n_scale_bits"])
                      for s in range(lay["ns"])])
     return np.stack(sf, axis=1), np.stack(mant, axis=1)
 
