@@ -1447,6 +1447,70 @@ int mrc_pac_store_stft_window_routed(mrc_pac_store* s, int rate_divisor, int mix
                                      void* out /* DEVICE */, void* stream);
 int mrc_pac_store_route_info(mrc_pac_store* s, int64_t* counts /*[3]*/);
 
+/* Spans: a term that sounds in PART of its row, with a linear fade at either end -- a row of eight utterances laid end to end
+ * (packing), pieces of one file in another order, 0.5 s out of the middle of a file at 0.3 s into a 4 s background, a hole
+ * cut into an utterance, a crossfade at a splice -- in the one call that reads the terms.
+ * THE CALLS.  mrc_pac_store_decode_window_spans takes every argument of mrc_pac_store_decode_window_reverb, and
+ * mrc_pac_store_stft_window_spans every argument of mrc_pac_store_stft_window, in that order, and right after ir_of
+ *   span_first, span_len [n_terms]   in ROW samples -- output samples at the term's own ratio, as start and window are; row
+ *                                    sample 0 is the row's first.  start[k] keeps its meaning: the position in the file's signal
+ *                                    that stands at row sample 0, so "the piece that begins at source sample p, placed at row
+ *                                    sample a" is start = p - a, span_first = a;
+ *   fade_in, fade_out [n_terms]      samples of linear ramp inside the span's two ends; either may be NULL: 0.
+ * ONE TERM.  With v_k[c][t] what the reverb call defines for term k (its dry window, for every integer t from -Lpre on) and
+ * j = t - span_first[k]: the term is silent for j < 0 or j >= span_len[k] -- it adds nothing -- and else d_k[t] = e v_k[t],
+ *   j < fade_in                e = (2 j + 1) / (2 fade_in)
+ *   j >= span_len - fade_out   e = (2 (span_len - 1 - j) + 1) / (2 fade_out)
+ *   otherwise                  d_k[t] is v_k[t] itself, no product;
+ * e is ONE division of the two exact integers as doubles, e v ONE product (no fused multiply-add).  fade_in + fade_out <=
+ * span_len, so at most one ramp holds at a sample; the half-sample ramp is symmetric and never 0 or 1, and a fade-out of F
+ * samples laid over a fade-in of F samples has weights that add to 1: a linear crossfade.
+ * Everything after the envelope is the reverb call's: a dry term enters the row's left fold as gain[k] * d_k[t] in the order of
+ * the terms; a convolved term is y_k[t] = sum over j of h[j] d_k[t - j] -- the response acts LAST, a gated piece rings on
+ * past its span; formats, channel map, zeros outside a file, damage rules and the STFT of the row are unchanged.
+ * To the bit: all four arrays NULL IS the reverb / STFT call (same path, same statistics); spans that cover every sample the
+ * call reads, without fades, equal it in every format; K dry terms at gain 1.0 whose spans abut and tile [0, window) give the
+ * concatenation of the K existing one-term windows; nothing depends on the order of the rows, on what shares the call, on the
+ * slab size or on the grid (the order of a row's terms stays part of the definition).
+ * WORK FOLLOWS THE SPANS.  A_k = [span_first, span_first + span_len) cut to [-Lpre, window), Lpre the range's pre-roll (0
+ * without a convolved term).  A_k empty: the term needs no block, gets no plane, parses nothing.  Else its blocks are exactly
+ * those the one-term call parses for (file[k], start[k] + a0, a1 - a0) at its ratio, A_k = [a0, a1): damage outside A_k is
+ * never read and never reported, and chunks_parsed of a call without convolved terms is the sum of those calls' counts.
+ * Planes and slabs (no convolved term): every term's planes have ONE length per call, S' + 4 n_mdct_lines / rate_divisor, S' the
+ * largest plane span of any A_k -- a1 - a0 at the unit ratio, ceil((a1 - a0 - 1) down / up) + 2 W otherwise -- not the
+ * window's; a slab is a run of whole rows whose terms, each counted at S', sum to at most MRC_OPT_STORE_SLAB_SAMPLES.  A row of
+ * eight abutting pieces of window / 8 counts about one window.  With a convolved term the dry scratch stays window + Lpre wide
+ * per term and the slab rule is the reverb call's.
+ * MRC_ERR_INVALID naming the argument and the term, before any device work and with `out` untouched: every refusal of the
+ * underlying entry (under this call's name); span_first without span_len or the reverse; a fade array without spans; span_len
+ * < 0 or > 2^40; |span_first| > 2^40; a negative fade; fade_in + fade_out > span_len. */
+int mrc_pac_store_decode_window_spans(mrc_pac_store* s, int rate_divisor, int mix, int n_ratios,
+                                      const int32_t* ratio_up /*[n_ratios]*/, const int32_t* ratio_down /*[n_ratios]*/, int zeros,
+                                      double rolloff, int n_bands /* 0: no band gains */, const double* edge_hz /*[n_bands+1]*/,
+                                      const double* band_gain /*[n_terms][n_bands]*/, int64_t n_items,
+                                      const int64_t* term_offset /*[n_items+1]*/, const int64_t* file /*[n_terms]*/,
+                                      const int64_t* start /*[n_terms]*/, const double* gain /*[n_terms]*/,
+                                      const int32_t* ratio_of /*[n_terms]: index into the list*/,
+                                      const int32_t* ir_of /*[n_terms]: -1 or index into the bank*/,
+                                      const int64_t* span_first /*[n_terms]*/, const int64_t* span_len /*[n_terms]*/,
+                                      const int64_t* fade_in /*[n_terms] or NULL: 0*/, const int64_t* fade_out /*[n_terms] or NULL: 0*/,
+                                      int64_t window, int n_channels_out, int format,
+                                      void* out /* DEVICE [n_items][n_channels_out][window] */, void* stream);
+int mrc_pac_store_stft_window_spans(mrc_pac_store* s, int rate_divisor, int mix, int n_ratios,
+                                    const int32_t* ratio_up /*[n_ratios]*/, const int32_t* ratio_down /*[n_ratios]*/, int zeros,
+                                    double rolloff, int n_bands /* 0: no band gains */, const double* edge_hz /*[n_bands+1]*/,
+                                    const double* band_gain /*[n_terms][n_bands]*/, int64_t n_items,
+                                    const int64_t* term_offset /*[n_items+1]*/, const int64_t* file /*[n_terms]*/,
+                                    const int64_t* start /*[n_terms]*/, const double* gain /*[n_terms]*/,
+                                    const int32_t* ratio_of /*[n_terms]: index into the list*/,
+                                    const int32_t* ir_of /*[n_terms]: -1 or index into the bank*/,
+                                    const int64_t* span_first /*[n_terms]*/, const int64_t* span_len /*[n_terms]*/,
+                                    const int64_t* fade_in /*[n_terms] or NULL: 0*/, const int64_t* fade_out /*[n_terms] or NULL: 0*/,
+                                    int n_fft, const double* frame_window /* HOST [n_fft] */, int64_t n_frames, int64_t hop, int mode,
+                                    int n_filters, const double* bank /* HOST [n_filters][n_fft/2+1], MRC_STFT_BANK only */,
+                                    int n_channels_out, int format /* MRC_WINDOW_F32 | MRC_WINDOW_F64 */, void* out /* DEVICE */,
+                                    void* stream);
+
 /* Per-stage device time of the most recent timed call when timing is enabled (hipEvents on the launch stream; the call
  * then synchronises).  Timed: mrc_dev_encode / mrc_dev_encode_ex and mrc_encode_mono / mrc_encode_joint (the _blocks
  * forms: their last shape group).  Not timed: the stage calls (mrc_dev_mdct, mrc_dev_smr, mrc_dev_alloc_quant),

@@ -278,6 +278,14 @@ def _load():
                                                        C.c_int, _f64p, C.c_int64, C.c_int64, C.c_int, C.c_int, _f64p, C.c_int, C.c_int,
                                                        C.c_void_p, C.c_void_p]),
         "mrc_pac_store_route_info": (C.c_int, [C.c_void_p, _i64p]),
+        "mrc_pac_store_decode_window_spans": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, C.c_int, C.c_double,
+                                                        C.c_int, _f64p, _f64p, C.c_int64, _i64p, _i64p, _i64p, _f64p, _i32p, _i32p,
+                                                        _i64p, _i64p, _i64p, _i64p, C.c_int64, C.c_int, C.c_int, C.c_void_p,
+                                                        C.c_void_p]),
+        "mrc_pac_store_stft_window_spans": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, C.c_int, C.c_double,
+                                                      C.c_int, _f64p, _f64p, C.c_int64, _i64p, _i64p, _i64p, _f64p, _i32p, _i32p,
+                                                      _i64p, _i64p, _i64p, _i64p, C.c_int, _f64p, C.c_int64, C.c_int64, C.c_int,
+                                                      C.c_int, _f64p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)          # AttributeError here = the library does not export the header's symbol

@@ -77,6 +77,10 @@ on the bins (store.mel_bin_weights: torchaudio's rule), with --complex the compl
 Hann of W taps (default N) centred in N points; frame j is samples [j H, j H + N) of the row, and --samples is rounded down to
 whole frames.  It composes with the flags -d takes for a row: --start, --samples, --rate-divisor, --sample-rate, --mix, --speed,
 --ir, --band-gains-db, --overlay, --snr-db; it refuses -d itself and every encode, levels and line-energy flag.
+One after another:  python -m mrcaudiocodec_amd.cli -d in.pac out.wav --append other.pac [--crossfade N]  decodes in.pac followed by
+other.pac (same codec settings) in ONE call of two terms with spans (PacStore.decode_window_sum(span_first=, span_len=)); with
+--crossfade the two overlap by N output samples, in.pac fading out and other.pac fading in linearly.  Composes with
+--rate-divisor, --sample-rate and --mix; refused without -d and with the other row flags.
 
 Quality (mrc_pac_nmr): --nmr on an encode prints, per file written (every rung of a ladder), one JSON line with the
 noise-to-mask ratio of the file against the WAV, measured with the codec's own masking model: nmr_max_db (worst band),
@@ -1089,6 +1093,76 @@ def decode_pac_file(pac_path, wav_path, device_id=0, excerpt=None, rate_divisor=
     return inter.T
 
 
+def check_append_args(append, crossfade, decode, others):
+    """--append and --crossfade as given (None: not given) -> (path, crossfade in samples), or None without --append.  --append
+    decodes src followed by a second file in one call: refused without -d, and with every flag in `others` that is given (it
+    composes with --rate-divisor, --sample-rate and --mix alone); --crossfade is refused without --append and is a whole number
+    of output samples >= 0."""
+    if append is None:
+        if crossfade is not None:
+            raise ValueError("--crossfade belongs to --append: it needs --append")
+        return None
+    if not decode:
+        raise ValueError("--append decodes src followed by a second .pac file: it needs -d")
+    for flag, given in others.items():
+        if given:
+            raise ValueError("--append composes with --rate-divisor, --sample-rate and --mix: it does not take %s" % flag)
+    if crossfade is not None and (isinstance(crossfade, bool) or not isinstance(crossfade, (int, np.integer)) or crossfade < 0):
+        raise ValueError("--crossfade: %r is not a whole number of samples >= 0" % (crossfade,))
+    return str(append), (0 if crossfade is None else int(crossfade))
+
+
+def decode_appended_files(pac_path, wav_path, append, device_id=0, rate_divisor=1, mix=None, sample_rate=None):
+    """-d --append: src followed by append[0], the two overlapping by append[1] output samples over which src fades out and
+    the second file fades in (0: they abut), in ONE PacStore.decode_window_sum call of two terms with spans
+    (store.concat_spans); each file is parsed and synthesised under its own piece only.  rate_divisor, mix and sample_rate
+    as decode_pac_file's.  Both files carry the same codec settings and channel count (a mix makes one channel of either).
+    -> int16 [nCh][samples] as written."""
+    bufs = []
+    for path in (pac_path, append[0]):
+        with open(path, "rb") as fp:
+            bufs.append(fp.read())
+    try:
+        (cfg, nch, _, _), (other, nch2, _, _) = pacfile.read_header(bufs[0]), pacfile.read_header(bufs[1])
+    except MrcError as e:
+        raise ValueError("--append: not a .pac file (%s)" % e)
+    for name in CODEC_SETTINGS:
+        if getattr(other, name) != getattr(cfg, name):
+            raise ValueError("--append: %s differs: %s has %d, %s has %d" % (name, pac_path, getattr(cfg, name), append[0], getattr(other, name)))
+    mix = check_mix_args(mix, True)
+    if mix is None and nch != nch2:
+        raise ValueError("--append: %s has %d channel(s), %s has %d: give --mix" % (pac_path, nch, append[0], nch2))
+    rate_divisor = check_rate_divisor_args(rate_divisor, True)
+    if cfg.sample_rate % rate_divisor:
+        raise ValueError("--rate-divisor %d does not divide the file's sample rate, %d Hz" % (rate_divisor, cfg.sample_rate))
+    resample = None
+    if check_sample_rate_args(sample_rate, True, rate_divisor != 1) is not None:
+        from .store import resample_plan
+        rate_divisor, up, down = resample_plan(cfg.sample_rate, int(sample_rate))
+        resample = None if up == down else (up, down)
+    rate_out = cfg.sample_rate // rate_divisor if sample_rate is None else int(sample_rate)
+    h = Handle(sample_rate=cfg.sample_rate, n_mdct_lines=cfg.n_mdct_lines, n_scale_bits=cfg.n_scale_bits,
+               n_mant_size_bits=cfg.n_mant_size_bits, device_id=device_id)
+    try:
+        from .store import PacStore, concat_spans
+        with PacStore(h, bufs) as store:
+            n = store.n_samples_at(rate_divisor) if resample is None else store.n_samples_resampled(*resample, rate_divisor)
+            try:
+                starts, first, length, fin, fout = concat_spans([[int(n[0]), int(n[1])]], [[0, 0]], crossfade=append[1])
+            except ValueError as e:
+                raise ValueError("--crossfade: %s" % e)
+            got = store.decode_window_sum([[0, 1]], starts, [[1.0, 1.0]], int(first[0, 1] + length[0, 1]), rate_divisor=rate_divisor, mix=mix,
+                                          resample=resample, span_first=first, span_len=length, fade_in=fin, fade_out=fout)
+            inter = np.ascontiguousarray(got[0].cpu().numpy().T)
+    finally:
+        h.close()
+    data = inter.astype("<i2", copy=False)
+    with open(wav_path, "wb") as fp:
+        fp.write(wav_header(inter.shape[1], data.nbytes, rate_out))
+        fp.write(data.tobytes())
+    return inter.T
+
+
 def measure_files(wav_path, pac_paths, bits_per_sample=None, device_id=0, exact_spread=False):
     """The NMR of each `.pac` file in pac_paths against the WAV it was coded from, in one library call (mrc_pac_nmr).
     bits_per_sample: one value per file (or None) for the report.  -> one dict per file: file, bits_per_sample and the
@@ -1216,6 +1290,11 @@ def main(argv=None):
     ap.add_argument("--overlay-start", type=int, default=None, metavar="N",
                     help="with --overlay: the overlay's sample that falls on the excerpt's first (default 0; negative: the "
                          "overlay begins that many samples into the excerpt)")
+    ap.add_argument("--append", default=None, metavar="PAC",
+                    help="with -d: decode src followed by this .pac file (same codec settings) in one call of two terms with "
+                         "spans; composes with --rate-divisor, --sample-rate and --mix")
+    ap.add_argument("--crossfade", type=int, default=None, metavar="N",
+                    help="with --append: the two files overlap by N output samples, src fading out and PAC fading in linearly")
     ap.add_argument("--band-gains-db", default=None, metavar="LO-HI:DB,...",
                     help="with -d: multiply the MDCT lines between LO and HI Hz by DB decibels (-inf: silence them) before the "
                          "inverse transform, e.g. 0-300:-inf,3400-24000:-inf for a telephone band; bands ascend and do not "
@@ -1312,6 +1391,10 @@ def main(argv=None):
         speed = check_speed_args(a.speed, row)
         ir = check_ir_args(a.ir, row)
         array_ir = check_array_ir_args(a.array_ir, ir, row)
+        append = check_append_args(a.append, a.crossfade, a.decode, {
+            "--start": a.start is not None, "--samples": a.samples is not None, "--overlay": a.overlay is not None,
+            "--band-gains-db": a.band_gains_db is not None, "--speed": a.speed is not None, "--ir": a.ir is not None,
+            "--array-ir": a.array_ir is not None, "--stft-energies": a.stft_energies, "--nmr": a.nmr, "--measure": a.measure})
         if levels is not None:
             from .store import check_levels_mix
             check_levels_mix(mix, "--mix")
@@ -1384,6 +1467,13 @@ def main(argv=None):
         if missing:
             ap.error("--measure: no such file: %s" % ", ".join(missing))
         _print_nmr(ap, a, paths, None if rates is None else [v for (_, v) in rates])
+        return
+    if a.decode and append is not None:
+        try:
+            pcm = decode_appended_files(a.src, a.dst, append, a.device, rate_divisor, mix, sample_rate)
+        except ValueError as e:
+            ap.error(str(e))
+        print("%s: %d channels x %d samples" % (a.dst, pcm.shape[0], pcm.shape[1]))
         return
     if a.decode:
         try:

@@ -90,6 +90,12 @@
 // where the reverb call has one gain and one response; it gets a source of forward transforms per distinct response length
 // among its wet routes, and reverb_route_fold_kernel writes the rows' channels.  The STFT loop sees rows of that many channels.
 //
+// decode_window_spans and stft_window_spans, terms that sound in part of their row and fade at its ends: the reverb and STFT
+// requests with four more arrays, and no loop of their own.  The units loop narrows what it plans for a term to the term's span cut
+// to the row (under termRows moved up by the pre-roll), sizes the planes by the longest span of the range instead of the window,
+// sends a TermSpan record per term up beside the SumTerms and launches the span kernels (mrc_kernels_store_span.hip); reverb_loop
+// and stft_loop read their terms through it as ever.  A request without spans runs what it ran.
+//
 // block_energy, ((a + b) / D) * the sum of squares of a block's first 1 / D decoded lines, per channel or for the mid, for
 // every block of the selected files: the same slab plan (stage_slab, parse_slab) over runs of whole blocks instead of the
 // blocks of windows, then block_energy_kernel per group (mrc_kernels_store.hip) in place of planes, synthesis and output.
@@ -432,12 +438,16 @@ struct WindowRequest {
     const int64_t *termOffset = nullptr, *file = nullptr, *start = nullptr;
     const double* gain = nullptr;
     const int32_t* irOf = nullptr;
+    // the audible span of every term in row samples and its linear fades (spanFirst NULL: every term is the whole row, the
+    // call as it was; a NULL fade array: 0)
+    const int64_t *spanFirst = nullptr, *spanLen = nullptr, *fadeIn = nullptr, *fadeOut = nullptr;
     int nChannelsOut = 1;                                    // the channels DECODED per unit and, unless routed, written per row
     // a routed kind: every term gives one channel (nChannelsOut == 1) and reaches routeChannels output channels; gain and irOf
     // are then the route arrays, [n_terms][routeChannels]
     int routeChannels = 0;
     void* stream = nullptr;
     bool rows() const { return kind != kItems; }
+    bool spans() const { return spanFirst != nullptr; }
     bool routed() const { return kind == kRouted || kind == kStftRouted; }
     bool stft() const { return kind == kStft || kind == kStftRouted; }
     bool banked() const { return kind != kItems && kind != kRows; }
@@ -513,6 +523,20 @@ int units_loop(mrc_pac_store* s, const CheckedWindows& c, const WindowRun& run) 
     const auto unitsBefore = [rowTerms](int64_t row) { return rowTerms ? rowTerms[row] : row; };
     // (a start that far down is below every file with or without the pre-roll)
     const auto startOf = [&](int64_t k) { return q.start[k] < INT64_MIN + run.preRoll ? INT64_MIN : q.start[k] - run.preRoll; };
+    // spans: term k sounds at the run's row samples [a0, a1) = its span, moved up by the pre-roll as the run's rows begin that
+    // much before the call's, cut to the row -> whether that is any sample.  Without spans every term is the whole row.
+    const bool spans = q.spans();
+    // (spans come with a list of ratios, the reverb and STFT entries' arguments: asked before anything is launched)
+    if (spans && !q.ratioList) return fail(s->h, MRC_ERR_INVALID, std::string(q.fn) + ": internal error: spans without a list of ratios");
+    const auto audible = [&](int64_t k, int64_t* a0, int64_t* a1) {
+        *a0 = 0;
+        *a1 = window;
+        if (!spans) return true;
+        const int64_t f = q.spanFirst[k] + run.preRoll;
+        *a0 = std::max<int64_t>(f, 0);
+        *a1 = std::min<int64_t>(f + q.spanLen[k], window);
+        return *a0 < *a1;
+    };
 
     MRC_TRY(ensure_decode_consts(h));
     StoreBufs& b = h->store;
@@ -538,6 +562,14 @@ int units_loop(mrc_pac_store* s, const CheckedWindows& c, const WindowRun& run) 
             span = std::max<int64_t>(span, r.W ? ((window - 1) * r.down + r.up - 1) / r.up + 2 * r.W : window);
         }
     }
+    if (spans) {                                             // planes as long as the range's longest span asks, not as the window
+        span = 0;
+        for (int64_t k = unitsBefore(run.first), a0, a1; k < unitsBefore(run.last); ++k) {
+            if (!audible(k, &a0, &a1)) continue;
+            const ResampleSpec* r = rs ? rs : speeds && speeds->r[q.ratioOf[k]].W ? &speeds->r[q.ratioOf[k]] : nullptr;
+            span = std::max<int64_t>(span, r ? ((a1 - a0 - 1) * r->down + r->up - 1) / r->up + 2 * r->W : a1 - a0);
+        }
+    }
     const int64_t far = (int64_t)1 << 52;                    // an output start beyond it is beyond every file: (start + window) * down fits
     const int64_t planeLen = span + 4 * L, tiles = (window + 255) / 256;
     const int64_t slab = run.slab, itemCap = std::max<int64_t>(1, 0x7fffffffLL / (tiles * n_channels_out));
@@ -560,16 +592,19 @@ int units_loop(mrc_pac_store* s, const CheckedWindows& c, const WindowRun& run) 
             const int64_t f = file[u0 + k];
             const size_t before = needs.size();
             const int64_t outStart = startOf(u0 + k);
-            int64_t at = outStart, len = window;             // the samples the planes must hold: [at, at + len)
+            int64_t a0, a1;                                  // the row samples the term gives: all of them without spans
+            if (!audible(u0 + k, &a0, &a1)) continue;        // silent in this row: no block, no plane, nothing parsed
+            if (spans && (outStart > far || outStart < -far)) continue;      // (beyond every file; outStart + a0 is then safe to form)
+            int64_t at = outStart + a0, len = a1 - a0;       // the samples the planes must hold: [at, at + len)
             if (rs) {
                 if (at > far || at < -far) continue;
                 at = floor_div(at * down, up) - W + 1;
-                len = floor_div((outStart + window - 1) * down, up) + W - at + 1;
+                len = floor_div((outStart + a1 - 1) * down, up) + W - at + 1;
             } else if (speeds && speeds->r[q.ratioOf[u0 + k]].W) {
                 const ResampleSpec& r = speeds->r[q.ratioOf[u0 + k]];
                 if (at > far || at < -far) continue;
                 at = floor_div(at * r.down, r.up) - r.W + 1;
-                len = floor_div((outStart + window - 1) * r.down, r.up) + r.W - at + 1;
+                len = floor_div((outStart + a1 - 1) * r.down, r.up) + r.W - at + 1;
             }
             needed_blocks(*s, cfg, D, k, f, at, len, &needs);
             if (needs.size() == before) continue;            // all zeros: its plane does not exist
@@ -585,7 +620,7 @@ int units_loop(mrc_pac_store* s, const CheckedWindows& c, const WindowRun& run) 
         // ---- staging (one H2D copy): plan | groups | block offsets | items (a sum: term records | the rows' term offsets);
         // a slot's offset is its block's place in the item's plane: the block's position in the file's padded plane, the
         // window's start at 2 L
-        size_t oOffs = 0, oItems = 0, oOutStart = 0, oLineBand = 0, oBandGain = 0, oUnit = 0, oRatioOf = 0, oRatios = 0;
+        size_t oOffs = 0, oItems = 0, oOutStart = 0, oLineBand = 0, oBandGain = 0, oUnit = 0, oRatioOf = 0, oRatios = 0, oSpans = 0;
         SlabStage S;
         MRC_TRY(stage_slab(
             s, fn, mix, needs, &pl, &S,
@@ -607,6 +642,7 @@ int units_loop(mrc_pac_store* s, const CheckedWindows& c, const WindowRun& run) 
                     oRatioOf = lay->add<int>(nSlab);
                     oRatios = lay->add<SpeedRatio>(speeds->nRatios);
                 }
+                if (spans) oSpans = lay->add<TermSpan>(nSlab);
             },
             [&](const Need& n, int g, int slot, int ch, bool pair) {
                 const WindowItem& it = items[(size_t)n.item];
@@ -630,6 +666,14 @@ int units_loop(mrc_pac_store* s, const CheckedWindows& c, const WindowRun& run) 
         } else {
             std::memcpy(S.pin + oItems, items.data(), sizeof(WindowItem) * nSlab);
             if (rs) std::memcpy(S.pin + oOutStart, q.start + first, sizeof(long long) * nSlab);
+        }
+        if (spans) {                                         // (spans come with rows: the records lie beside the SumTerms)
+            TermSpan* sp = (TermSpan*)(S.pin + oSpans);
+            for (int64_t k = 0, a0, a1; k < nSlab; ++k) {
+                audible(u0 + k, &a0, &a1);
+                sp[k] = TermSpan{q.spanFirst[u0 + k] + run.preRoll, q.spanLen[u0 + k], q.fadeIn ? q.fadeIn[u0 + k] : 0,
+                                 q.fadeOut ? q.fadeOut[u0 + k] : 0, a0};
+            }
         }
         if (speeds) {
             int* ratioOf = (int*)(S.pin + oRatioOf);
@@ -680,7 +724,23 @@ int units_loop(mrc_pac_store* s, const CheckedWindows& c, const WindowRun& run) 
             }));
         s->stats[1] += pl.groupsUsed();
         MRC_HIP(h, hipEventRecord(b.ev[4], st));
-        if (speeds)
+        // spans come with a list of ratios (the reverb and STFT entries' arguments).  A list of ONE ratio goes to the single-ratio
+        // kernels -- the bits are the same, a fold's order being per output, and a ratio like 3 / 2 keeps its evenOdd LDS layout
+        const TermSpan* spansDev = (const TermSpan*)(din + oSpans);
+        const ResampleSpec* one = spans && speeds && speeds->nRatios == 1 ? &speeds->r[0] : nullptr;
+        if (one && one->W == 0)
+            MRC_HIP(h, launch_span_sum_out(nSlabRows, (const SumTerm*)(din + oItems), spansDev, (const long long*)(din + oOutStart), window,
+                                           n_channels_out, format, (int)L, planeLen, x, outSlab, st));
+        else if (one)
+            MRC_HIP(h, launch_span_resample_sum_out(nSlabRows, (const SumTerm*)(din + oItems), spansDev, (const long long*)(din + oOutStart),
+                                                    window, n_channels_out, format, (int)L, planeLen, one->up, one->down, one->W,
+                                                    tables[0]->evenOdd, tables[0]->skew, (const double*)tables[0]->taps.p, x, outSlab, st));
+        else if (spans)
+            MRC_HIP(h, launch_span_resample_multi_sum_out(nSlabRows, (const SumTerm*)(din + oItems), spansDev, (const int*)(din + oRatioOf),
+                                                          (const SpeedRatio*)(din + oRatios), ratios, speeds->nRatios,
+                                                          (const long long*)(din + oOutStart), window, n_channels_out, format, (int)L,
+                                                          planeLen, x, outSlab, st));
+        else if (speeds)
             MRC_HIP(h, launch_resample_multi_sum_out(nSlabRows, (const SumTerm*)(din + oItems), (const int*)(din + oRatioOf),
                                                      (const SpeedRatio*)(din + oRatios), ratios, speeds->nRatios,
                                                      (const long long*)(din + oOutStart), window, n_channels_out, format, (int)L,
@@ -1213,7 +1273,7 @@ namespace {
 // call passes its row length L (0 without frames) and MRC_WINDOW_F64.  The kinds differ only in where window and out are
 // looked at: a reverb call refuses a bad window before its rows and a NULL out last of all, an STFT call has refused its own
 // arguments before it comes here and names L in its bound on the pre-roll.
-constexpr int64_t kMaxWindow = (int64_t)1 << 40;
+constexpr int64_t kMaxWindow = (int64_t)1 << 40;             // of a window, and of a span's length and |first sample|
 int check_windows(mrc_pac_store* s, const WindowRequest& q, int64_t window, int format, void* out, CheckedWindows* c) {
     mrc_handle* h = s->h;
     const std::string w = q.fn;
@@ -1306,6 +1366,23 @@ int check_windows(mrc_pac_store* s, const WindowRequest& q, int64_t window, int 
                         return refuse("band_gain of term " + std::to_string(k) + ", band " + std::to_string(b0) + " is not finite");
             c->shaped = true;
         }
+        // ---- the spans and their fades
+        if ((q.spanFirst != nullptr) != (q.spanLen != nullptr))
+            return refuse(q.spanFirst ? "span_first is given without span_len" : "span_len is given without span_first");
+        if (!q.spanFirst && (q.fadeIn || q.fadeOut))
+            return refuse(std::string(q.fadeIn ? "fade_in" : "fade_out") + " is given without spans (span_first and span_len)");
+        for (int64_t k = 0; q.spanFirst && k < nTerms; ++k) {
+            const std::string term = " of term " + std::to_string(k);
+            const int64_t len = q.spanLen[k], first = q.spanFirst[k], fi = q.fadeIn ? q.fadeIn[k] : 0, fo = q.fadeOut ? q.fadeOut[k] : 0;
+            if (len < 0 || len > kMaxWindow) return refuse("span_len" + term + " = " + std::to_string(len) + " is outside [0, 2^40]");
+            if (first < -kMaxWindow || first > kMaxWindow)
+                return refuse("span_first" + term + " = " + std::to_string(first) + " is outside [-2^40, 2^40]");
+            if (fi < 0) return refuse("fade_in" + term + " = " + std::to_string(fi) + " is negative");
+            if (fo < 0) return refuse("fade_out" + term + " = " + std::to_string(fo) + " is negative");
+            if (fi > len || fo > len - fi)
+                return refuse("fade_in + fade_out" + term + " = " + std::to_string(fi) + " + " + std::to_string(fo) +
+                              " exceeds its span_len = " + std::to_string(len));
+        }
     }
     // ---- what every window call is asked: divisor, window, channels, format, files
     MRC_TRY(check_divisor(h, w, q.rateDivisor));
@@ -1351,6 +1428,7 @@ int check_windows(mrc_pac_store* s, const WindowRequest& q, int64_t window, int 
 // source records of a slab go up in one copy.
 const char* const kWinReverb = "mrc_pac_store_decode_window_reverb";
 const char* const kWinRouted = "mrc_pac_store_decode_window_routed";
+const char* const kWinSpans = "mrc_pac_store_decode_window_spans";
 const char* const kSetIrs = "mrc_pac_store_set_irs";
 constexpr int64_t kRevB = MRC_STORE_REVERB_BLOCK, kRevN = 2 * kRevB;
 
@@ -1585,6 +1663,7 @@ int window_call(mrc_pac_store* s, const WindowRequest& q, int64_t window, int fo
 // per call.
 const char* const kStft = "mrc_pac_store_stft_window";
 const char* const kStftRouted = "mrc_pac_store_stft_window_routed";
+const char* const kStftWithSpans = "mrc_pac_store_stft_window_spans";
 
 // exp(-2 pi i t / n) for 0 <= t < n from long double, the quadrant taken out first: the axes are exact
 void stft_twiddles(int n, double2* w) {
@@ -1754,6 +1833,41 @@ int mrc_pac_store_decode_window_reverb(mrc_pac_store* s, int rate_divisor, int m
     q.nItems = n_items; q.termOffset = term_offset; q.file = file; q.start = start; q.gain = gain; q.irOf = ir_of;
     q.nChannelsOut = n_channels_out; q.stream = stream;
     return window_call(s, q, window, format, out);
+}
+
+int mrc_pac_store_decode_window_spans(mrc_pac_store* s, int rate_divisor, int mix, int n_ratios, const int32_t* ratio_up,
+                                      const int32_t* ratio_down, int zeros, double rolloff, int n_bands, const double* edge_hz,
+                                      const double* band_gain, int64_t n_items, const int64_t* term_offset, const int64_t* file,
+                                      const int64_t* start, const double* gain, const int32_t* ratio_of, const int32_t* ir_of,
+                                      const int64_t* span_first, const int64_t* span_len, const int64_t* fade_in,
+                                      const int64_t* fade_out, int64_t window, int n_channels_out, int format, void* out,
+                                      void* stream) {
+    WindowRequest q{kWinSpans, WindowRequest::kReverb};
+    q.rateDivisor = rate_divisor; q.mix = mix; q.zeros = zeros; q.rolloff = rolloff;
+    q.ratioList = true; q.nRatios = n_ratios; q.ratioUp = ratio_up; q.ratioDown = ratio_down; q.ratioOf = ratio_of;
+    q.banded = n_bands != 0; q.nBands = n_bands; q.edgeHz = edge_hz; q.bandGain = band_gain;
+    q.nItems = n_items; q.termOffset = term_offset; q.file = file; q.start = start; q.gain = gain; q.irOf = ir_of;
+    q.spanFirst = span_first; q.spanLen = span_len; q.fadeIn = fade_in; q.fadeOut = fade_out;
+    q.nChannelsOut = n_channels_out; q.stream = stream;
+    return window_call(s, q, window, format, out);
+}
+
+int mrc_pac_store_stft_window_spans(mrc_pac_store* s, int rate_divisor, int mix, int n_ratios, const int32_t* ratio_up,
+                                    const int32_t* ratio_down, int zeros, double rolloff, int n_bands, const double* edge_hz,
+                                    const double* band_gain, int64_t n_items, const int64_t* term_offset, const int64_t* file,
+                                    const int64_t* start, const double* gain, const int32_t* ratio_of, const int32_t* ir_of,
+                                    const int64_t* span_first, const int64_t* span_len, const int64_t* fade_in,
+                                    const int64_t* fade_out, int n_fft, const double* frame_window, int64_t n_frames, int64_t hop,
+                                    int mode, int n_filters, const double* bank, int n_channels_out, int format, void* out,
+                                    void* stream) {
+    WindowRequest q{kStftWithSpans, WindowRequest::kStft};
+    q.rateDivisor = rate_divisor; q.mix = mix; q.zeros = zeros; q.rolloff = rolloff;
+    q.ratioList = true; q.nRatios = n_ratios; q.ratioUp = ratio_up; q.ratioDown = ratio_down; q.ratioOf = ratio_of;
+    q.banded = n_bands != 0; q.nBands = n_bands; q.edgeHz = edge_hz; q.bandGain = band_gain;
+    q.nItems = n_items; q.termOffset = term_offset; q.file = file; q.start = start; q.gain = gain; q.irOf = ir_of;
+    q.spanFirst = span_first; q.spanLen = span_len; q.fadeIn = fade_in; q.fadeOut = fade_out;
+    q.nChannelsOut = n_channels_out; q.stream = stream;
+    return stft_call(s, q, StftArgs{n_fft, frame_window, n_frames, hop, mode, n_filters, bank}, format, out);
 }
 
 int mrc_pac_store_reverb_ms(mrc_pac_store* s, double* ms) {

@@ -314,6 +314,27 @@ hipError_t launch_resample_multi_sum_out(int64_t nRows, const SumTerm* terms, co
                                          const SpeedRatio* ratiosHost, int nRatios, const long long* termOffset, int64_t window,
                                          int nchOut, int format, int L, int64_t planeLen, const double* planes, void* out,
                                          hipStream_t st);
+// mrc_pac_store_decode_window_spans: the audible part of one term, a record beside its SumTerm (which keeps its layout).  The
+// term sounds at row samples first <= t < first + len and is silent elsewhere; with j = t - first its value is e * v, e =
+// (2 j + 1) / (2 fadeIn) where j < fadeIn, (2 (len - 1 - j) + 1) / (2 fadeOut) where j >= len - fadeOut, else v itself
+// (fadeIn + fadeOut <= len: one ramp at most).  The term's planes were planned for [first, first + len) cut to the row, NOT
+// for the row: a term of the unit ratio keeps row sample t at plane[2 L + t - origin] and SumTerm::w.start is the file's
+// sample at row sample `origin`; a resampled term keeps its intermediate samples as ever (w.start the first of them).
+struct TermSpan {
+    long long first, len, fadeIn, fadeOut, origin;
+};
+// launch_sum_out, launch_resample_sum_out and launch_resample_multi_sum_out over terms with spans (spans [terms]: device).
+// Planes of planeLen doubles in all three.  A sample outside a term's span is never read from its plane.
+hipError_t launch_span_sum_out(int64_t nRows, const SumTerm* terms, const TermSpan* spans, const long long* termOffset,
+                               int64_t window, int nchOut, int format, int L, int64_t planeLen, const double* planes, void* out,
+                               hipStream_t st);
+hipError_t launch_span_resample_sum_out(int64_t nRows, const SumTerm* terms, const TermSpan* spans, const long long* termOffset,
+                                        int64_t window, int nchOut, int format, int L, int64_t planeLen, int up, int down, int W,
+                                        int evenOdd, int skew, const double* taps, const double* planes, void* out, hipStream_t st);
+hipError_t launch_span_resample_multi_sum_out(int64_t nRows, const SumTerm* terms, const TermSpan* spans, const int* ratioOf,
+                                              const SpeedRatio* ratios, const SpeedRatio* ratiosHost, int nRatios,
+                                              const long long* termOffset, int64_t window, int nchOut, int format, int L,
+                                              int64_t planeLen, const double* planes, void* out, hipStream_t st);
 // mrc_pac_store_decode_window_reverb (mrc_kernels_reverb.hip): overlap-save at a hop of B = MRC_STORE_REVERB_BLOCK samples and
 // transforms of N = 2 B points.  A source of forward transforms: sample i < take of segment seg < nSeg is g = first + seg B + i,
 // its value samples[re + g] + i samples[im + g] (im < 0: no imaginary part) where lo <= g < hi and zero elsewhere; the

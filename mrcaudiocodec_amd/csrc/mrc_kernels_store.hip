@@ -62,6 +62,9 @@
 //     to the global address space (GlobalTaps): tap rows of up == 1 and up == 2 are scalar loads again, the general case
 //     global loads -- the same mix of loads as resample_sum_out_kernel has.
 //
+//   The tile sizes, floor_div, the polyphase fold (resample_fold, resample_fold_up) and the sums' read-ahead live in
+//   mrc_store_fold.hpp, which the span forms of the three folding kernels (mrc_kernels_store_span.hip) include as well.
+//
 //   block_energy_kernel   the energy a block adds to the decoded signal, from its MDCT lines alone
 //     (mrc_pac_store_block_energy).  The windowed MDCT with the codec's transition windows is an orthogonal lapped
 //     transform; with the reference's scaling (mdct.py: forward 2 / N, inverse 2) a block of shape (a, b) holds
@@ -120,12 +123,11 @@
 //     before the frame's end: acc += (double)ov2 * B, ov2 = 2 |tile and frame| > 0 an exact integer.  A frame that meets
 //     no tile is +0.0.  MRC_WINDOW_F32 converts acc once.  No atomics; nothing depends on the grid or the slab.
 #include "mrc_decode_lines.hpp"
+#include "mrc_store_fold.hpp"
 
 namespace mrc {
 using namespace dev;
 namespace {
-
-constexpr int kWindowThreads = 256;
 
 // (store_window_value, out[o] = v in the caller's format: mrc_device.hpp, shared with mrc_kernels_reverb.hip)
 
@@ -144,56 +146,6 @@ __global__ __launch_bounds__(kWindowThreads) void window_out_kernel(const Window
     if (pos >= 0 && pos < it.nSamples)
         v = planes[it.plane + (int64_t)(it.nch == 2 ? c : 0) * (window + 4 * (int64_t)L) + 2 * (int64_t)L + t];
     store_window_value(out, row * window + t, format, v);
-}
-
-constexpr int kResampleThreads = 256, kResampleWave = 64;
-constexpr int kResampleRun = 4089;                                   // doubles a workgroup stages at most: 255 * 8 + 2 * 1024 + 1
-constexpr int kResampleLds = kResampleRun + kResampleRun / 32 + 1;   // ... with one double of padding per 32 (skew)
-
-__device__ inline int64_t floor_div(int64_t a, int64_t b) {         // b > 0
-    const int64_t q = a / b;
-    return (a % b != 0 && a < 0) ? q - 1 : q;
-}
-
-// (Taps: a pointer to const double -- the kernel argument of the single-ratio kernels, or GlobalTaps where the pointer was read
-// out of memory and the compiler has to be told the address space that it sees for itself in a kernel argument)
-using GlobalTaps = const __attribute__((address_space(1))) double*;
-
-// v = the left fold from +0.0 over j ascending of taps[j][p] * run[first + j], every product rounded once, then added.
-// kUp: 1 or 2 -- `up` itself: a tap's row is read at addresses the whole wave shares (scalar loads) and the lane picks its
-// phase's -- or 0: any `up`, each lane loads taps[j][p].  kSkew: the run's layout.  Eight taps and samples are read ahead of
-// their eight additions.
-template <int kUp, bool kSkew, class Taps>
-__device__ inline double resample_fold(Taps __restrict__ taps, int up, int p, const double* run, int first, int nTaps) {
-    const auto tap = [&](int j) {
-        if (kUp == 1) return taps[j];
-        if (kUp == 2) {
-            const double c0 = taps[2 * j], c1 = taps[2 * j + 1];
-            return p ? c1 : c0;
-        }
-        return taps[(int64_t)j * up + p];
-    };
-    const auto at = [](int i) { return kSkew ? i + (i >> 5) : i; };
-    double acc = 0.0;
-    int j = 0;
-    for (; j + 8 <= nTaps; j += 8) {
-        double c[8], y[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            c[u] = tap(j + u);
-            y[u] = run[at(first + j + u)];
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) acc = __dadd_rn(acc, __dmul_rn(c[u], y[u]));
-    }
-    for (; j < nTaps; ++j) acc = __dadd_rn(acc, __dmul_rn(tap(j), run[at(first + j)]));
-    return acc;
-}
-template <bool kSkew, class Taps>
-__device__ inline double resample_fold_up(Taps __restrict__ taps, int up, int p, const double* run, int first, int nTaps) {
-    return up == 1 ? resample_fold<1, kSkew>(taps, up, p, run, first, nTaps)
-         : up == 2 ? resample_fold<2, kSkew>(taps, up, p, run, first, nTaps)
-                   : resample_fold<0, kSkew>(taps, up, p, run, first, nTaps);
 }
 
 __global__ __launch_bounds__(kResampleThreads) void resample_out_kernel(const WindowItem* __restrict__ items,
@@ -244,8 +196,6 @@ __device__ inline double sum_term_sample(const SumTerm& tm, int c, int64_t t, in
     if (pos >= 0 && pos < tm.w.nSamples) y = planes[tm.w.plane + (int64_t)(tm.w.nch == 2 ? c : 0) * planeLen + 2 * (int64_t)L + t];
     return y;
 }
-
-constexpr int kSumAhead = 4;                                         // terms whose samples are loaded ahead of their additions
 
 __global__ __launch_bounds__(kWindowThreads) void sum_out_kernel(const SumTerm* __restrict__ terms,
                                                                  const long long* __restrict__ termOffset, int64_t window,

@@ -103,6 +103,26 @@ waveform tensor in between:
         bank = mel_bin_weights(400, 16000, mel_points(80, 0.0, 8000.0))        # [80][201], torchaudio's melscale_fbanks rule
         e = store.stft_window(files, starts, 98, 160, 400, bank=bank, output="bank", rate_divisor=2, mix="mid", resample=(2, 3))
         logmel = torch.log(e.clamp_min(1e-10))                                 # [len(files)][1][80][98]
+
+span_first=, span_len=, fade_in=, fade_out= (mrc_pac_store_decode_window_spans) let a term of a sum sound in PART of its row, with a
+linear fade at either end; what is parsed and synthesised follows the spans, not the window.  Concatenation -- a row of pieces
+laid end to end, eight utterances packed into one 10 s row or pieces of one file in another order, optionally crossfaded --
+is one call; concat_spans does the arithmetic (a term's start is the source position that stands at row sample 0):
+
+        lengths = np.full((len(rows), 8), 20000)                               # eight pieces of 1.25 s per row at 16 kHz
+        starts, first, length, fin, fout = concat_spans(lengths, piece_starts, crossfade=160)
+        x = store.decode_window_sum(piece_files, starts, np.ones(starts.shape), int(first[0, -1] + length[0, -1]), dtype=torch.float32,
+                                    rate_divisor=2, mix="mid", resample=(2, 3), span_first=first, span_len=length,
+                                    fade_in=fin, fade_out=fout)
+
+A placed, cropped event -- 0.5 s from source sample p of the event's file at 0.3 s into a 4 s background, faded over 5 ms; the
+event's file is parsed under its 0.5 s only:
+
+        at, n = 4800, 8000
+        x = store.decode_window_sum(np.stack([background, event], 1), np.stack([b_starts, p - at], 1), np.stack([np.ones_like(g), g], 1),
+                                    64000, dtype=torch.float32, rate_divisor=2, mix="mid", resample=(2, 3),
+                                    span_first=np.stack([np.zeros_like(p), np.full_like(p, at)], 1),
+                                    span_len=np.stack([np.full_like(p, 64000), np.full_like(p, n)], 1), fade_in=[0, 80], fade_out=[0, 80])
 """
 import collections
 import ctypes as C
@@ -318,6 +338,94 @@ def check_ir_index(ir_index, unit_shape, n_irs, what="decode_window"):
         raise ValueError("%s: ir_index must be -1 or lie in 0..%d (the store's impulse responses), got %d at unit %d"
                          % (what, n_irs - 1, int(idx[bad[0]]), int(bad[0])))
     return np.ascontiguousarray(idx.astype(np.int32))
+
+
+MAX_SPAN = 1 << 40                        # of span_len and of |span_first| (the library's bound on a window)
+
+
+def check_spans(span_first, span_len, fade_in, fade_out, unit_shape, what="decode_window_sum"):
+    """The spans of a call's terms and their fades as int64 arrays of unit_shape, the shape of files -> (span_first, span_len,
+    fade_in, fade_out), or None where all four are None.  span_first and span_len go together and have the shape of files; a
+    fade is None (0), a scalar (every term) or an array of that shape.  ValueError: one of span_first / span_len without the
+    other, a fade without spans, another shape, values that are not whole numbers, span_len outside [0, 2^40], |span_first|
+    above 2^40, a negative fade, fade_in + fade_out above the term's span_len."""
+    if span_first is None and span_len is None:
+        for name, v in (("fade_in", fade_in), ("fade_out", fade_out)):
+            if v is not None:
+                raise ValueError("%s: %s goes with span_first and span_len" % (what, name))
+        return None
+    if span_first is None or span_len is None:
+        raise ValueError("%s: span_first and span_len go together, got only %s" % (what, "span_len" if span_first is None else "span_first"))
+    out = []
+    for name, v, scalar_ok in (("span_first", span_first, False), ("span_len", span_len, False), ("fade_in", fade_in, True),
+                               ("fade_out", fade_out, True)):
+        a = np.asarray(0 if v is None else v)
+        if a.dtype.kind not in "iu" or a.dtype == np.bool_:
+            if a.dtype.kind != "f" or not np.all(np.isfinite(a)) or np.any(a != np.floor(a)):
+                raise ValueError("%s: %s must hold whole numbers, got %r" % (what, name, v))
+        if a.dtype.kind == "f" and a.size and np.max(np.abs(a)) > 2.0 ** 62:
+            raise ValueError("%s: %s is out of range, got %r" % (what, name, v))
+        a = a.astype(np.int64)
+        if scalar_ok and a.ndim == 0:
+            a = np.full(unit_shape, int(a), np.int64)
+        if a.shape != tuple(unit_shape):
+            raise ValueError("%s: %s must have the shape of files %s%s, got %s"
+                             % (what, name, tuple(unit_shape), " or be a scalar" if scalar_ok else "", a.shape))
+        out.append(np.ascontiguousarray(a.reshape(-1)))
+    first, length, fin, fout = out
+    for name, bad in (("span_len must lie in [0, 2^40]", (length < 0) | (length > MAX_SPAN)),
+                      ("span_first must lie in [-2^40, 2^40]", np.abs(first) > MAX_SPAN),
+                      ("fade_in must not be negative", fin < 0), ("fade_out must not be negative", fout < 0),
+                      ("fade_in + fade_out must not exceed span_len", fin + fout > length)):
+        at = np.flatnonzero(bad)
+        if at.size:
+            k = int(at[0])
+            raise ValueError("%s: %s, got span_first %d, span_len %d, fade_in %d, fade_out %d at term %d"
+                             % (what, name, first[k], length[k], fin[k], fout[k], k))
+    return first, length, fin, fout
+
+
+def concat_spans(lengths, source_starts, crossfade=0, item_offsets=None):
+    """Rows of pieces laid end to end -> (starts, span_first, span_len, fade_in, fade_out) for decode_window_sum and
+    stft_window, each of the shape of lengths.  lengths, source_starts: [n][K], or 1-D [terms] with item_offsets [n + 1] as those
+    calls take them; piece k is lengths[k] row samples from source position source_starts[k] of its file (both in output
+    samples at the term's ratio).  A row's first piece begins at row sample 0 and every later one `crossfade` samples before
+    its predecessor ends; over that overlap the earlier piece fades out and the later one fades in, linearly, their weights
+    adding to 1 (crossfade=0: the pieces abut, no fade).  A row's outer ends are not faded.  The row ends at span_first +
+    span_len of its last piece.  ValueError: shapes that do not agree, a negative length or crossfade, and a crossfade longer
+    than half an inner piece (a piece that fades at both ends) or than a row's first or last piece."""
+    lengths, src = np.asarray(lengths, dtype=np.int64), np.asarray(source_starts, dtype=np.int64)
+    if lengths.shape != src.shape:
+        raise ValueError("concat_spans: lengths and source_starts must have one shape, got %s and %s" % (lengths.shape, src.shape))
+    if isinstance(crossfade, (bool, np.bool_)) or not _is_int(crossfade) or crossfade < 0:
+        raise ValueError("concat_spans: crossfade must be a whole number >= 0, got %r" % (crossfade,))
+    crossfade = int(crossfade)
+    if item_offsets is None:
+        if lengths.ndim != 2:
+            raise ValueError("concat_spans: lengths must be [n][K], or 1-D with item_offsets; got shape %s" % (lengths.shape,))
+        offsets = np.arange(lengths.shape[0] + 1, dtype=np.int64) * lengths.shape[1]
+    else:
+        offsets = np.asarray(item_offsets, dtype=np.int64)
+        if lengths.ndim != 1 or offsets.ndim != 1 or offsets.size < 1 or offsets[0] != 0 or np.any(np.diff(offsets) < 0) or \
+                offsets[-1] != lengths.size:
+            raise ValueError("concat_spans: with item_offsets, lengths must be 1-D and item_offsets [n + 1], start at 0, not "
+                             "decrease and end at the number of pieces; got %r" % (item_offsets,))
+    shape, flat, src = lengths.shape, lengths.reshape(-1), src.reshape(-1)
+    if np.any(flat < 0):
+        raise ValueError("concat_spans: lengths must not be negative, got %d at piece %d" % (flat[flat < 0][0], np.flatnonzero(flat < 0)[0]))
+    first, fin, fout = np.zeros(flat.size, np.int64), np.zeros(flat.size, np.int64), np.zeros(flat.size, np.int64)
+    for i in range(offsets.size - 1):
+        a, b = int(offsets[i]), int(offsets[i + 1])
+        at = 0
+        for k in range(a, b):
+            fin[k] = crossfade if k > a else 0
+            fout[k] = crossfade if k < b - 1 else 0
+            if fin[k] + fout[k] > flat[k]:
+                raise ValueError("concat_spans: crossfade %d does not fit piece %d of %d samples, which fades over %d"
+                                 % (crossfade, k, flat[k], fin[k] + fout[k]))
+            first[k] = at - fin[k]
+            at = first[k] + flat[k]
+    return tuple(v.reshape(shape) for v in (src - first, first, flat.copy(), fin, fout))
 
 
 ROUTE_NONE = _lib.MRC_ROUTE_NONE                      # route_irs: the term does not reach this channel
@@ -758,14 +866,14 @@ def _formats():
     return {torch.int16: _lib.MRC_WINDOW_PCM16, torch.float32: _lib.MRC_WINDOW_F32, torch.float64: _lib.MRC_WINDOW_F64}
 
 
-class WindowRows(collections.namedtuple("WindowRows", "rate_divisor mix resample channels bands speeds irs offsets files starts gains routes",
-                                        defaults=(None,))):
+class WindowRows(collections.namedtuple("WindowRows", "rate_divisor mix resample channels bands speeds irs offsets files starts gains routes spans",
+                                        defaults=(None, None))):
     """The checked row arguments of a window call: rate_divisor an int, mix None or its MRC_MIX_* value, resample None or
     (up, down, zeros, rolloff), channels as given (1 under a mix), bands None or (edges, gains [terms][n_bands]), speeds None or
     (ratios, zeros, rolloff, index int32 [terms]), irs None or int32 [terms], offsets int64 [rows + 1], files, starts and gains
     flat and contiguous.  decode_window's items are rows of one term each at gain 1.0.  routes: None, or check_routes' (gains
     float64 [terms][C], irs int32 [terms][C]) of a routed call -- gains and irs are then not looked at, and channels is 1, what
-    every term gives."""
+    every term gives.  spans: None, or check_spans' (span_first, span_len, fade_in, fade_out), int64 [terms] each."""
     __slots__ = ()
 
 
@@ -777,6 +885,8 @@ def window_entry(store, rows, caller, window, channels, fmt, out, stream, stft=N
     holds the arrays made here whose pointers args carries.  The entry per combination, first match:
         routes given: stft_window            mrc_pac_store_stft_window_routed  (route_gain and route_ir in place of gain and
                       else                   ..._routed                         ir_of; `channels` is the routes' last axis)
+        spans given:  stft_window            mrc_pac_store_stft_window_spans   (the reverb / STFT entry's arguments with the
+                      else                   ..._spans                          four span arrays behind ir_of)
         stft_window                          mrc_pac_store_stft_window (ratios default to the one base ratio, ir_of to -1)
         ir_index given                       ..._reverb
         speeds given                         ..._speeds
@@ -796,7 +906,7 @@ def window_entry(store, rows, caller, window, channels, fmt, out, stream, stft=N
         bands = (0, None, None)
     else:
         bands = (rows.bands[0].size - 1, rows.bands[0].ctypes.data, pad(rows.bands[1]))
-    if stft is not None or rows.irs is not None or rows.speeds is not None or rows.routes is not None:   # ... take a list of ratios
+    if stft is not None or rows.irs is not None or rows.speeds is not None or rows.routes is not None or rows.spans is not None:   # ... take a list of ratios
         ratios, zeros, rolloff, index = rows.speeds or ([(up, down)], zeros, rolloff, np.zeros(rows.files.size, np.int32))
         ups = np.ascontiguousarray([r[0] for r in ratios], dtype=np.int32)
         downs = np.ascontiguousarray([r[1] for r in ratios], dtype=np.int32)
@@ -812,6 +922,11 @@ def window_entry(store, rows, caller, window, channels, fmt, out, stream, stft=N
             if stft is not None:
                 return "mrc_pac_store_stft_window_routed", routed + own + tail[1:], keep
             return "mrc_pac_store_decode_window_routed", routed + tail, keep
+        if rows.spans is not None:
+            spans = tuple(pad(a) for a in rows.spans)
+            if stft is not None:
+                return "mrc_pac_store_stft_window_spans", head + (pad(irs),) + spans + own + tail[1:], keep
+            return "mrc_pac_store_decode_window_spans", head + (pad(irs),) + spans + tail, keep
         if stft is not None:
             return "mrc_pac_store_stft_window", head + (pad(irs),) + own + tail[1:], keep
         if rows.irs is not None:
@@ -1087,7 +1202,7 @@ class PacStore:
 
     def decode_window_sum(self, files, starts, gains, window, item_offsets=None, channels=None, dtype=None, out=None, stream=None,
                           rate_divisor=1, mix=None, resample=None, band_gains=None, band_edges_hz=None, speed_factors=None,
-                          speed_index=None, ir_index=None):
+                          speed_index=None, ir_index=None, span_first=None, span_len=None, fade_in=None, fade_out=None):
         """mrc_pac_store_decode_window_sum -> a torch tensor [n][channels][window] on the handle's device: item i is the sum
         over its terms k, IN THE ORDER GIVEN, of gains[k] * (the float64 window decode_window gives for files[k], starts[k]
         at this rate_divisor, mix and resample), folded from +0.0 with every product rounded once, then added -- speech over
@@ -1111,10 +1226,18 @@ class PacStore:
         ir_index: as decode_window's, PER TERM (mrc_pac_store_decode_window_reverb): it has the shape of files, and term k is
         convolved with impulse response ir_index[k] of the store's bank before it is weighted and added, -1 for none -- speech
         through a room over dry noise is one call.  It composes with resample, speed_factors / speed_index, band_gains, mix
-        and rate_divisor: the response acts last, at the term's output rate.  None: this call as it always was."""
+        and rate_divisor: the response acts last, at the term's output rate.  None: this call as it always was.
+        span_first, span_len, fade_in, fade_out: PER TERM (mrc_pac_store_decode_window_spans), the shape of files (a fade may be
+        a scalar, every term, or None, 0): term k sounds only at row samples span_first[k] <= t < span_first[k] + span_len[k], its
+        first fade_in and last fade_out samples there on a linear ramp ((2 j + 1) / (2 fade) at the j-th sample from the end it
+        fades at), and adds nothing elsewhere.  starts[k] stays the source position at row sample 0, so the piece from source
+        sample p placed at row sample a is starts = p - a, span_first = a; concat_spans lays pieces end to end.  Only the blocks
+        under a term's span are parsed and synthesised.  Spans compose with every argument above (the response acts after the
+        envelope, a gated piece rings on); check_spans makes the ValueErrors.  None: this call as it always was."""
         what = "decode_window_sum"
         rows = self._sum_rows(what, files, starts, gains, item_offsets, channels, rate_divisor, mix, resample, band_gains, band_edges_hz,
                               speed_factors, speed_index, ir_index)
+        rows = rows._replace(spans=check_spans(span_first, span_len, fade_in, fade_out, np.shape(files), what))
         n, window = rows.offsets.size - 1, int(window)
         fmt, channels, out, stream = self._window_out(what, n, rows.files, window, rows.channels, dtype, out, stream)
         return self._call_window(rows, what, window, channels, fmt, out, stream)
@@ -1206,7 +1329,7 @@ class PacStore:
     def stft_window(self, files, starts, n_frames, hop, n_fft, frame_window=None, bank=None, output="power", center=False,
                     gains=None, item_offsets=None, channels=None, dtype=None, out=None, stream=None, rate_divisor=1, mix=None,
                     resample=None, band_gains=None, band_edges_hz=None, speed_factors=None, speed_index=None, ir_index=None,
-                    route_gains=None, route_irs=None):
+                    route_gains=None, route_irs=None, span_first=None, span_len=None, fade_in=None, fade_out=None):
         """mrc_pac_store_stft_window -> a torch tensor [n][channels][n_fft // 2 + 1 | filters][n_frames] on the handle's device:
         the short-time Fourier transform of the rows decode_window_sum gives on the same row arguments, without the rows ever
         being written out.  Row i is that call's float64 row over (n_frames - 1) hop + n_fft samples from its terms' starts;
@@ -1228,7 +1351,10 @@ class PacStore:
         route_gains, route_irs: None, or the routes of decode_window_routed (mrc_pac_store_stft_window_routed): the result is
         [n][C][n_fft // 2 + 1 | filters][n_frames], channel c the transform of that call's channel c, bit for bit.  They stand in
         the place of gains and ir_index and are refused together with either, and with channels; files and starts are 1-D (one
-        term per item, or terms with item_offsets) or [n][K]."""
+        term per item, or terms with item_offsets) or [n][K].
+        span_first, span_len, fade_in, fade_out: decode_window_sum's (mrc_pac_store_stft_window_spans), in the shape of files;
+        center=True adds n_fft // 2 to span_first as it subtracts it from starts, so a span keeps its place in the signal.
+        Routed calls do not take spans."""
         import torch
         what = "stft_window"
         n_fft, hop, n_frames, window, matrix, mode = check_stft(n_fft, hop, n_frames, frame_window, bank, output, what)
@@ -1256,8 +1382,14 @@ class PacStore:
                               speed_factors, speed_index, ir_index)
         if not isinstance(center, (bool, np.bool_)):
             raise ValueError("%s: center must be True or False, got %r" % (what, center))
+        spans = check_spans(span_first, span_len, fade_in, fade_out, np.shape(files), what)
+        if spans is not None and routed:
+            raise ValueError("%s: route_gains and route_irs do not go with spans" % what)
         if center:
             rows = rows._replace(starts=rows.starts - n_fft // 2)
+            if spans is not None:
+                spans = (spans[0] + n_fft // 2,) + spans[1:]
+        rows = rows._replace(spans=spans)
         n = rows.offsets.size - 1
         is_complex = mode == _lib.MRC_STFT_COMPLEX
         real = {torch.float32: torch.float32, torch.float64: torch.float64, torch.complex64: torch.float32,
