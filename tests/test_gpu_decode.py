@@ -3,6 +3,9 @@ GPU parity tests of the decode side ("next" row f-4), through the C ABI: mrc_dec
 mrc_dev_decode + mrc_dev_pcm16 behind pacfile.decode_pac, against oracle/decode.py.  Bars: windowed blocks and
 overlap-added streams within 1e-12 of the block peak (the reference's IMDCT is an N-point inverse FFT, ours an
 N/4-point one: same ~1e-13 as the forward transform), 16-bit PCM codes equal.
+What this file does not cover -- other field widths than the default, files, the parsers, overlap-add, the store's seven other
+decode kernels and its energy readers, integers no encoder writes -- is in tests/test_gpu_decode_cases.py, on the crafted blocks
+and files of tests/decode_cases.py.
 """
 import types
 

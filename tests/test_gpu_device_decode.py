@@ -30,9 +30,10 @@ _HANDLES = {}
 
 def _handle_for(cfg):
     from mrcaudiocodec_amd import Handle
-    key = (cfg.sample_rate, cfg.n_mant_size_bits)
+    fields = ("sample_rate", "n_mdct_lines", "n_short", "n_scale_bits", "n_mant_size_bits", "blksw_bits_a", "blksw_bits_b")
+    key = tuple(getattr(cfg, k) for k in fields)             # (setting E of the crafted cases: 3 scale bits, 5 size bits)
     if key not in _HANDLES:
-        _HANDLES[key] = Handle(sample_rate=cfg.sample_rate, n_mant_size_bits=cfg.n_mant_size_bits)
+        _HANDLES[key] = Handle(**dict(zip(fields, key)))
     return _HANDLES[key]
 
 
@@ -88,7 +89,8 @@ def _compare(cases, hd=None):
 def test_dev_unpack_equals_host_parser_on_corpus():
     bases = UC.base_cases()
     n_acc, n_rej = _compare(bases)
-    assert n_rej == 0 and n_acc == len(bases)
+    assert n_rej == 0 and n_acc == len(bases) >= 144                         # (the crafted decode cases among them)
+    assert sum(c["label"].startswith("crafted_") for c in bases) == 36
 
 
 def test_dev_unpack_agrees_on_damaged_chunks():

@@ -98,9 +98,10 @@ def _check(cases, tmp_path):
 def test_portable_parser_equals_host_parser_on_corpus(tmp_path):
     bases = UC.base_cases()
     n_acc, n_rej, _ = _check(bases, tmp_path)
-    assert n_rej == 0 and n_acc == len(bases) >= 60
+    assert n_rej == 0 and n_acc == len(bases) >= 144
     labels = " ".join(c["label"] for c in bases)
-    for part in ("ref_a48_pac", "ref_b44_pac_raw", "switched_huff1", "mono_", "table3_", "jtable0_", "_m5_"):
+    for part in ("ref_a48_pac", "ref_b44_pac_raw", "switched_huff1", "mono_", "table3_", "jtable0_", "_m5_", "crafted_default_full_2ch/joint",
+                 "crafted_default_main_2ch_huffman/flush", "crafted_E_one_line_1ch_huffman", "crafted_E_main_2ch/joint"):
         assert part in labels
 
 

@@ -2,7 +2,7 @@
 Chunk-parser corpus shared by tests/test_unpack_portable.py (the portable parser compiled for the host) and
 tests/test_gpu_device_decode.py (the same parser on the device): `.pac` chunk sets as mrc_unpack_blocks takes them --
 the reference CLI's own files, oracle-written block-switched stereo streams, mono files, chunks forced onto every
-Huffman table, a 5-bit allocation-field configuration -- and seeded corruptions of them.  Built on the CPU only.
+Huffman table, a 5-bit allocation-field configuration, the crafted decode cases of tests/decode_cases.py -- and seeded corruptions of them.  Built on the CPU only.
 
 A case is a dict: cfg (MrcConfig), buf (bytes), offsets (int64 [n * nch]), nch, joint, label.
 """
@@ -98,6 +98,12 @@ def base_cases():
                 blob = head + d.tobytes()
                 out.append(dict(cfg=cfg, buf=blob, offsets=ppac.scan_chunks(blob, len(head)), nch=2, joint=True,
                                 label="jtable%d_m%d_%d_%d" % (t, mant_bits, a, b)))
+    # the crafted decode cases (tests/decode_cases.py) at the default setting and at E, raw and Huffman-coded: every band at the
+    # widest allocation, sign bits alone, one non-zero line, streams without bits, idle fields
+    import decode_cases as dc
+    for sid in dc.HUFFMAN_SETS:
+        for pf in dc.files(sid):
+            out += _file_cases(pf["data"], "crafted_" + pf["label"].replace("/", "_"), dc.config(sid))
     return out
 
 
